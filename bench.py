@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the MolNexTR predict hot path on MI355X (molecules/s at 384x384, batch 32 per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 `--gpus N` with N > 1 and no torchrun environment: bench.py launches itself under `python -m torch.distributed.run
@@ -39,6 +39,12 @@ Rank 0 prints ONE JSON line (contract in the task statement). Beyond the contrac
                   the same workload on this box's host cores: thread sweep, B in {1, 32}, encoder /
                   decoder split, natural and fixed-T=128 decode, median of 3 after a warm-up, 1-thread figure, lscpu model
   parity_note     what "SMILES exact-match" can mean here (RDKit is not installable: token SMILES + atom / bond sets).
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed path returned for its LAST step (the last batch of 32
+images of rank 0): DIR/tokens.npy [32,480], lengths.npy [32], atom_idx.npy [32,kmax], n_atoms.npy [32],
+edges.npy [32,kmax,kmax] (and scores.npy [32] with --beam > 1), every array as float32 (the integers are exact). The
+images and weights are pure functions of the arguments, so two builds run with the same arguments can be compared
+array by array.
 """
 import argparse
 import json
@@ -381,6 +387,17 @@ def land_records(out, kmax, rank, world, n_local, pinned, gather=False):
     return dst, k
 
 
+def dump_outputs(dirname, arrays):
+    """Device result tensors of one step -> DIR/<name>.npy in float32 (small integers and fp32 scores: exact)."""
+    os.makedirs(dirname, exist_ok=True)
+    host = {name: t.cpu().numpy().astype(np.float32) for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > 64 << 20:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the 64 MB budget")
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -408,6 +425,9 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sub", action="store_true", help="skip the sub-results (latency / fixed-T / parity / beam)")
     ap.add_argument("--force-gather", action="store_true", help="run the RCCL record gather even with one rank")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step (rank 0's last batch of 32) as "
+                         "DIR/<name>.npy in float32")
     args = ap.parse_args()
 
     if not torch.cuda.is_available():
@@ -447,14 +467,21 @@ def main():
     stats = {}
     host_buf = {}
 
-    def process(e, imgs, count, how, max_len=args.max_len, stop_on_eos=True, beam=args.beam, land=True):
-        """`count` steps over resident images; returns the (gathered) result records on the host."""
+    def process(e, imgs, count, how, max_len=args.max_len, stop_on_eos=True, beam=args.beam, land=True, keep_last=False):
+        """`count` steps over resident images; returns the (gathered) result records on the host. keep_last: leave views of
+        the last step's output tensors in stats["last_step"] (for --dump-outputs)."""
         if how in ("pipeline", "beam"):
             out = e.predict(imgs, ref_batch=BATCH, max_len=max_len, stop_on_eos=stop_on_eos, beam=beam)
             tokens, lengths, atom_idx, n_atoms, edges = (out[k] for k in ("tokens", "lengths", "atom_idx", "n_atoms", "edges"))
         else:
             parts = [run_batch(e, imgs[i * BATCH:(i + 1) * BATCH], kmax, max_len, beam) for i in range(count)]
             tokens, lengths, atom_idx, n_atoms, edges = (torch.cat([p[j] for p in parts]) for j in range(5))
+            out = {}
+        if keep_last:             # views of the last step's rows: no copy inside the timed region
+            res = {"tokens": tokens, "lengths": lengths, "atom_idx": atom_idx, "n_atoms": n_atoms, "edges": edges}
+            if "scores" in out:
+                res["scores"] = out["scores"]
+            stats["last_step"] = {k: v[-BATCH:] for k, v in res.items()}
         stats["lens"], stats["atoms"] = lengths.cpu().numpy(), n_atoms.cpu().numpy()
         rec = None
         if max_len == shard.MAX_LEN and land:
@@ -499,10 +526,14 @@ def main():
     if live:
         eng.profile(stride)              # HIP events on the encoder stream, live inside the timed region
     eng.gemm_clock(reset=True)           # shader-clock counters of the persistent GEMM launches: zeroed before the timed region
-    elapsed = timed(lambda: process(eng, imgs, args.steps, mode))
+    elapsed = timed(lambda: process(eng, imgs, args.steps, mode, keep_last=bool(args.dump_outputs)))
     gemm_mhz = eng.gemm_clock(reset=True)     # ... and read after it: every gemm256x3 launch of the timed job
     live_prof = eng.profile_read_all() if live else None
     eng.profile(False)
+    last_step = stats.pop("last_step", None)
+    if last_step is not None and rank == 0:
+        dump_outputs(args.dump_outputs, last_step)
+    del last_step
     main_stats = dict(stats)
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)

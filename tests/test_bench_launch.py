@@ -186,3 +186,25 @@ def test_traffic_figure_is_only_taken_from_a_file_made_with_these_kernel_sources
     ns = {"__file__": os.path.join(ROOT, "tools", "collect_traffic.py"), "out": {}}
     exec(src[src.index("# the GEMM kernel sources the counters were collected on"):src.index("json.dump(out, open(sys.argv[3]")], ns)
     assert ns["out"]["library_sha16"] == have
+
+
+def test_dump_outputs_writes_every_array_as_float32_within_the_budget(tmp_path):
+    """--dump-outputs: one step's result tensors (int32 / uint8 / fp32 as the engine returns them) land as DIR/<name>.npy in
+    float32 with their values exact; more than 64 MB in all is refused."""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(0)
+    arrays = {"tokens": torch.randint(0, 3000, (32, 480), generator=g, dtype=torch.int32),
+              "lengths": torch.randint(1, 481, (32,), generator=g, dtype=torch.int32),
+              "edges": torch.randint(0, 7, (32, 160, 160), generator=g, dtype=torch.int32).to(torch.uint8),
+              "scores": torch.randn(32, generator=g)}
+    d = tmp_path / "dump"
+    bench.dump_outputs(str(d), arrays)
+    assert sorted(p.name for p in d.iterdir()) == ["edges.npy", "lengths.npy", "scores.npy", "tokens.npy"]
+    for name, t in arrays.items():
+        a = np.load(d / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == tuple(t.shape)
+        assert np.array_equal(a, t.numpy().astype(np.float32)) and np.array_equal(a.astype(t.numpy().dtype), t.numpy())
+    with pytest.raises(SystemExit, match="64 MB"):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": torch.zeros(64 << 18 | 1, dtype=torch.uint8)})
+    assert not (tmp_path / "big").exists() or not any((tmp_path / "big").iterdir())

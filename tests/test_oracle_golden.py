@@ -66,9 +66,11 @@ def test_decoder_greedy_with_compaction(golden_dir, synth_ckpt):
     res = greedy_decode(feats, synth_ckpt["decoder"], trace=True)
     assert len(set(g["lens"].tolist())) > 3, "fixture must contain rows of different length"
     _check_greedy(g, res, 480)
+    # rtol 1e-6 (~8 fp32 ulps): the logits reach |80|, and the host BLAS picks its fp32 summation order by CPU (an AVX2 sgemm
+    # path lands up to 7.6e-5 off the golden on those, 3.6e-7 relative beyond the 5e-5); every logit near 0 is still held to 5e-5
     for s in range(4):
         alive, logits = res.logits_trace[s]
-        np.testing.assert_allclose(logits.numpy(), g[f"logits_step{s}"], atol=5e-5)
+        np.testing.assert_allclose(logits.numpy(), g[f"logits_step{s}"], atol=5e-5, rtol=1e-6)
 
 
 def test_decoder_max_length_finish(golden_dir, synth_ckpt):
