@@ -233,7 +233,9 @@ int mnx_preprocess(mnx_engine* h, const uint8_t* rgb, int32_t height, int32_t wi
 
 /* Token classes for the on-device atom-position scan used by mnx_predict (the 'indices' that
  * CharTokenizer.sequence_to_smiles derives, MolNexTR/tokenization.py:464-515). flags[id]: bit0 = is_symbol(id),
- * bit1 = is_atom(id) for id < n (= number of vocabulary symbols); the ids of '[' ']' 'C' 'l' 'B' 'r'. */
+ * bit1 = is_atom(id), bits 2-4 = length of the id's name in characters - 1 (read by the confidences only: an atom's
+ * score spans as many ids as its symbol has characters, and '<unk>' is one id of five characters; 0 = one character)
+ * for id < n (= number of vocabulary symbols); the ids of '[' ']' 'C' 'l' 'B' 'r'. */
 int mnx_set_token_classes(mnx_engine* h, const uint8_t* flags, int32_t n, int32_t lbracket, int32_t rbracket,
                           int32_t id_C, int32_t id_l, int32_t id_B, int32_t id_r);
 
@@ -258,6 +260,31 @@ int mnx_atom_scan(mnx_engine* h, const int32_t* tokens, const int32_t* lengths, 
 int mnx_predict(mnx_engine* h, const float* images, int32_t n_img, int32_t ref_batch, int32_t max_len,
                 int32_t stop_on_eos, int32_t* tokens, int32_t* lengths, int32_t* n_atoms, int32_t* atom_idx,
                 uint8_t* edges, int32_t kmax, void* stream);
+
+/* mnx_predict with the confidences of `Decoder.decode(compute_confidence=True)` (MolNexTR/components.py:456-469 atom
+ * scores, :485-491 edge scores and overall score; decoding/greedy_search.py:109-110 token scores): the same inputs and
+ * outputs with stop_on_eos = 1, and per image, all in the same continuous-batching pipeline (they are computed on the
+ * device when a reference batch retires):
+ *   token_logp    device fp32 [n_img,max_len] or NULL: masked log-prob of every emitted id, EOS included (0 beyond lengths)
+ *   edge_scores   device fp64 [n_img,kmax,kmax]: probability of the chosen bond class, float64-averaged as in
+ *                 get_edge_prediction (MolNexTR/components.py:383-400); rows / cols >= n_atoms are not written
+ *   atom_scores   device fp64 [n_img,kmax]: geometric mean of exp(log-prob) over the ids that spell the atom's symbol
+ *                 (as many ids back from its last one as the symbol has characters, Python slice semantics); 0 beyond n_atoms
+ *   overall_score device fp64 [n_img]: exp(mean log-prob) * sqrt(product of edge_scores[0:n_atoms, 0:n_atoms])
+ * Synchronous with respect to its outputs; reports MNX_ERR_RANGE as mnx_predict does. */
+int mnx_predict_confidence(mnx_engine* h, const float* images, int32_t n_img, int32_t ref_batch, int32_t max_len,
+                           int32_t* tokens, int32_t* lengths, int32_t* n_atoms, int32_t* atom_idx, uint8_t* edges,
+                           int32_t kmax, float* token_logp, double* edge_scores, double* atom_scores, double* overall_score,
+                           void* stream);
+
+/* The confidence computation on its own (test aid and building block of mnx_predict_confidence; replaces the
+ * compute_confidence lines of MolNexTR/components.py:456-469,485-491): tokens device int32 [n,T] (T <= 512), lengths
+ * device int32 [n], token_logp device fp32 [n,T], atom_idx device int32 [n,kmax] and n_atoms device int32 [n] (as the
+ * atom scan writes them), edge_scores device fp64 [n,kmax,kmax] -> atom_scores device fp64 [n,kmax], overall_score device
+ * fp64 [n], defined as for mnx_predict_confidence. Deterministic (fixed-order reductions). Asynchronous on `stream`. */
+int mnx_confidence(mnx_engine* h, const int32_t* tokens, const int32_t* lengths, const float* token_logp, int32_t n,
+                   int32_t T, const int32_t* atom_idx, const int32_t* n_atoms, const double* edge_scores, int32_t kmax,
+                   double* atom_scores, double* overall_score, void* stream);
 
 /* mnx_predict with beam search (BASELINE config 5): the same inputs and outputs, every reference batch searched as
  * mnx_decode_beam does (n_best = 1: the best hypothesis; atom positions and the bond head run on ITS tokens and decoder

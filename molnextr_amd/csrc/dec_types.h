@@ -113,7 +113,7 @@ struct BeamBuffers {
 
 // token classes for the on-device atom-position scan (CharTokenizer.sequence_to_smiles 'indices')
 struct TokenClasses {
-    unsigned char flags[256];      // bit0 is_symbol, bit1 is_atom
+    unsigned char flags[256];      // bit0 is_symbol, bit1 is_atom, bits 2-4 name length - 1 (confidence_kernel)
     int lbracket, rbracket, id_C, id_l, id_B, id_r, x0, y0, vocab;
 };
 
@@ -150,6 +150,14 @@ hipError_t atoms_enqueue(const DecBuffers& b, const TokenClasses* tc_dev, const 
                          int* atom_idx, int* n_atoms, hipStream_t s);
 hipError_t atoms_enqueue_raw(const TokenClasses* tc_dev, const int* tokens, const int* lens, int n, int T, int kmax,
                              int* atom_idx, int* n_atoms, hipStream_t s);
+// per-atom and per-sequence confidences (decoder.hip confidence_kernel): tokens / lengths / log-probs of the slots in
+// slots_dev (confidence_enqueue) or of rows 0..n-1 of [n,T] arrays (_raw); atom_idx / n_atoms / scores per row
+hipError_t confidence_enqueue(const DecBuffers& b, const TokenClasses* tc_dev, const int* slots_dev, int n, int kmax,
+                              const int* atom_idx, const int* n_atoms, const double* scores, double* atom_scores,
+                              double* overall, hipStream_t s);
+hipError_t confidence_enqueue_raw(const TokenClasses* tc_dev, const int* tokens, const int* lens, const float* logp, int n,
+                                  int T, int kmax, const int* atom_idx, const int* n_atoms, const double* scores,
+                                  double* atom_scores, double* overall, hipStream_t s);
 hipError_t edges_enqueue(const DecWeights& w, const DecBuffers& bf, const float* hidden, const int* slot_map,
                          const int* atom_idx, const int* n_atoms, int B, int kmax, int row_stride_T,
                          unsigned char* edges, double* scores, hipStream_t s);

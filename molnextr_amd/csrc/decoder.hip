@@ -902,20 +902,11 @@ hipError_t dec_enqueue_tick_rows(const DecWeights& w, const DecBuffers& b, int r
 // sequence (reference tokenization.py:464-515): for every atom token group followed by "x y <next>", the
 // position of <next>. One thread per sequence (a <= 480-step scan).
 // =============================================================================================
-__global__ __launch_bounds__(64) void atom_scan_kernel(const int* __restrict__ lens, const int* __restrict__ tokens,
-                                                       const TokenClasses* __restrict__ tc, const int* __restrict__ slots,
-                                                       int n_rows, int T, int kmax, int* __restrict__ atom_idx,
-                                                       int* __restrict__ n_atoms) {
-    // one workgroup per sequence: the ids are staged in LDS by all lanes, then lane 0 runs the sequential scan
-    __shared__ int seq[512];
-    __shared__ unsigned char fl[256];
-    const int row = blockIdx.x;
-    const int slot = slots ? slots[row] : row;
-    const int n = min(lens[slot], 512);
-    for (int i = threadIdx.x; i < n; i += 64) seq[i] = tokens[(size_t)slot * T + i];
-    for (int i = threadIdx.x; i < 256; i += 64) fl[i] = tc->flags[i];
-    __syncthreads();
-    if (threadIdx.x != 0) return;
+// The sequential walk of the scan over seq[0, n) (ids staged in LDS): calls emit(k, i0, j) for the k-th atom, whose symbol
+// tokens are [i0, j) and whose decoder position is j + 2; returns the number of atoms found (kmax does not bound it).
+template <typename Emit>
+__device__ __forceinline__ int atom_walk(const int* seq, int n, const unsigned char* fl, const TokenClasses* __restrict__ tc,
+                                         Emit emit) {
     const int x0 = tc->x0, y0 = tc->y0, lb = tc->lbracket, rb = tc->rbracket;
     const int iC = tc->id_C, il = tc->id_l, iB = tc->id_B, ir = tc->id_r;
     int i = 0, k = 0;
@@ -937,13 +928,33 @@ __global__ __launch_bounds__(64) void atom_scan_kernel(const int* __restrict__ l
             j = i + 1;
         }
         if (j + 2 < n && seq[j] >= x0 && seq[j] < y0 && seq[j + 1] >= y0) {
-            if (k < kmax) atom_idx[(size_t)row * kmax + k] = j + 2;
+            emit(k, i, j);
             ++k;
             i = j + 2;
         } else {
             i = j;
         }
     }
+    return k;
+}
+
+__global__ __launch_bounds__(64) void atom_scan_kernel(const int* __restrict__ lens, const int* __restrict__ tokens,
+                                                       const TokenClasses* __restrict__ tc, const int* __restrict__ slots,
+                                                       int n_rows, int T, int kmax, int* __restrict__ atom_idx,
+                                                       int* __restrict__ n_atoms) {
+    // one workgroup per sequence: the ids are staged in LDS by all lanes, then lane 0 runs the sequential scan
+    __shared__ int seq[512];
+    __shared__ unsigned char fl[256];
+    const int row = blockIdx.x;
+    const int slot = slots ? slots[row] : row;
+    const int n = min(lens[slot], 512);
+    for (int i = threadIdx.x; i < n; i += 64) seq[i] = tokens[(size_t)slot * T + i];
+    for (int i = threadIdx.x; i < 256; i += 64) fl[i] = tc->flags[i];
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const int k = atom_walk(seq, n, fl, tc, [&](int a, int, int j) {
+        if (a < kmax) atom_idx[(size_t)row * kmax + a] = j + 2;
+    });
     n_atoms[row] = k < kmax ? k : kmax;
 }
 
@@ -958,6 +969,94 @@ hipError_t atoms_enqueue_raw(const TokenClasses* tc_dev, const int* tokens, cons
                              int* atom_idx, int* n_atoms, hipStream_t s) {
     hipLaunchKernelGGL(atom_scan_kernel, dim3(n), dim3(64), 0, s, lens, tokens, tc_dev, (const int*)nullptr, n, T, kmax,
                        atom_idx, n_atoms);
+    return hipGetLastError();
+}
+
+// =============================================================================================
+// Confidences (decode_batch(compute_confidence=True); reference components.py:456-469,485-491, greedy_search.py:109-110),
+// in fp64 on the fp32 masked log-probs:
+//   atom_scores[a]  = prod(exp(logp[lo:i+1])) ** (1/L), i = atom_idx[a] - 3 (last symbol token), L = characters of the
+//                     atom's symbol (flags bits 2-4 = name length - 1, summed over its tokens), lo = i - L + 1 with Python
+//                     slice semantics (a negative start wraps to len + lo; an empty slice gives 1.0)
+//   overall_score   = exp(mean(logp[0:len])) * sqrt(prod(scores[0:k, 0:k]))
+// One workgroup per sequence. The spans come from the atom scan's own walk (lane 0); everything else is spread over the
+// lanes, and the sum / product are fixed-order tree reductions (no atomics: the result does not depend on timing).
+// =============================================================================================
+constexpr int CONF_THREADS = 256;
+
+__global__ __launch_bounds__(CONF_THREADS) void confidence_kernel(
+        const int* __restrict__ lens, const int* __restrict__ tokens, const float* __restrict__ logp,
+        const TokenClasses* __restrict__ tc, const int* __restrict__ slots, int T, int kmax,
+        const int* __restrict__ atom_idx, const int* __restrict__ n_atoms, const double* __restrict__ scores,
+        double* __restrict__ atom_scores, double* __restrict__ overall) {
+    __shared__ int seq[512];
+    __shared__ double ts[512];
+    __shared__ unsigned char fl[256];
+    __shared__ int span_len[256];                 // characters of atom a's symbol (an atom takes >= 3 of <= 512 ids)
+    __shared__ double red_sum[CONF_THREADS], red_prod[CONF_THREADS];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const int slot = slots ? slots[row] : row;
+    const int n = min(min(lens[slot], T), 512);
+    const int k = min(max(n_atoms[row], 0), kmax);
+    double sum = 0.0, prod = 1.0;
+    for (int i = tid; i < n; i += CONF_THREADS) {
+        seq[i] = tokens[(size_t)slot * T + i];
+        const double l = (double)logp[(size_t)slot * T + i];
+        ts[i] = exp(l);
+        sum += l;
+    }
+    for (int i = tid; i < 256; i += CONF_THREADS) { fl[i] = tc->flags[i]; span_len[i] = 1; }
+    const double* sc = scores + (size_t)row * kmax * kmax;
+    for (int e = tid; e < k * k; e += CONF_THREADS) prod *= sc[(e / k) * kmax + e % k];
+    red_sum[tid] = sum;
+    red_prod[tid] = prod;
+    __syncthreads();
+    if (tid == 0) {
+        atom_walk(seq, n, fl, tc, [&](int a, int i0, int j) {
+            if (a < 256) {
+                int L = 0;
+                for (int q = i0; q < j; ++q) L += ((fl[seq[q]] >> 2) & 7) + 1;
+                span_len[a] = L;
+            }
+        });
+    }
+    for (int w = CONF_THREADS / 2; w > 0; w >>= 1) {       // its barriers also publish span_len to every lane
+        if (tid < w) {
+            red_sum[tid] += red_sum[tid + w];
+            red_prod[tid] *= red_prod[tid + w];
+        }
+        __syncthreads();
+    }
+    for (int a = tid; a < kmax; a += CONF_THREADS) {
+        double v = 0.0;
+        if (a < k) {
+            const int L = a < 256 ? span_len[a] : 1;
+            const int i = atom_idx[(size_t)row * kmax + a] - 3;
+            int lo = i - L + 1, hi = i + 1;                  // ts[lo:hi] as Python slices it
+            if (lo < 0) lo = max(lo + n, 0); else lo = min(lo, n);
+            if (hi < 0) hi = max(hi + n, 0); else hi = min(hi, n);
+            double p = 1.0;
+            for (int t = lo; t < hi; ++t) p *= ts[t];
+            v = pow(p, 1.0 / L);
+        }
+        atom_scores[(size_t)row * kmax + a] = v;
+    }
+    if (tid == 0) overall[row] = exp(red_sum[0] / n) * sqrt(red_prod[0]);
+}
+
+hipError_t confidence_enqueue(const DecBuffers& b, const TokenClasses* tc_dev, const int* slots_dev, int n, int kmax,
+                              const int* atom_idx, const int* n_atoms, const double* scores, double* atom_scores,
+                              double* overall, hipStream_t s) {
+    hipLaunchKernelGGL(confidence_kernel, dim3(n), dim3(CONF_THREADS), 0, s, b.st->len, b.tokens, b.logp, tc_dev, slots_dev,
+                       b.T, kmax, atom_idx, n_atoms, scores, atom_scores, overall);
+    return hipGetLastError();
+}
+
+hipError_t confidence_enqueue_raw(const TokenClasses* tc_dev, const int* tokens, const int* lens, const float* logp, int n,
+                                  int T, int kmax, const int* atom_idx, const int* n_atoms, const double* scores,
+                                  double* atom_scores, double* overall, hipStream_t s) {
+    hipLaunchKernelGGL(confidence_kernel, dim3(n), dim3(CONF_THREADS), 0, s, lens, tokens, logp, tc_dev, (const int*)nullptr,
+                       T, kmax, atom_idx, n_atoms, scores, atom_scores, overall);
     return hipGetLastError();
 }
 

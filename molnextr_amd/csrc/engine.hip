@@ -1248,20 +1248,49 @@ int mnx_atom_scan(mnx_engine* h, const int32_t* tokens, const int32_t* lengths, 
     return MNX_OK;
 }
 
-// The whole hot path for n_img images with continuous batching (see include/molnextr_hip.h).
-int mnx_predict(mnx_engine* h, const float* images, int32_t n_img, int32_t ref_batch, int32_t max_len,
-                int32_t stop_on_eos, int32_t* tokens, int32_t* lengths, int32_t* n_atoms, int32_t* atom_idx,
-                uint8_t* edges, int32_t kmax, void* stream) {
+int mnx_confidence(mnx_engine* h, const int32_t* tokens, const int32_t* lengths, const float* token_logp, int32_t n,
+                   int32_t T, const int32_t* atom_idx, const int32_t* n_atoms, const double* edge_scores, int32_t kmax,
+                   double* atom_scores, double* overall_score, void* stream) {
     if (!h) return MNX_ERR_INVALID_ARG;
-    if (!images || !tokens || !lengths || !n_atoms || !atom_idx || !edges || n_img < 1) {
-        h->err = "mnx_predict: null/empty argument";
+    if (!tokens || !lengths || !token_logp || !atom_idx || !n_atoms || !edge_scores || !atom_scores || !overall_score ||
+        n < 1 || T < 1 || kmax < 1) {
+        h->err = "mnx_confidence: null/empty argument";
         return MNX_ERR_INVALID_ARG;
     }
-    if (!h->have_tc) { h->err = "mnx_predict: call mnx_set_token_classes first"; return MNX_ERR_INVALID_ARG; }
+    if (!h->have_tc) { h->err = "mnx_confidence: call mnx_set_token_classes first"; return MNX_ERR_INVALID_ARG; }
+    if (T > 512 || kmax > h->db.kmax) { h->err = "mnx_confidence: T <= 512 and kmax <= cfg.max_atoms required"; return MNX_ERR_CAPACITY; }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, confidence_enqueue_raw(h->tc_dev, tokens, lengths, token_logp, n, T, kmax, atom_idx, n_atoms, edge_scores,
+                                     atom_scores, overall_score, (hipStream_t)stream));
+    return MNX_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// outputs of mnx_predict_confidence, per image (token_logp may be null)
+struct ConfOut {
+    float* token_logp;
+    double *edge_scores, *atom_scores, *overall;
+};
+}  // namespace
+
+// The whole hot path for n_img images with continuous batching (see include/molnextr_hip.h): the body of mnx_predict and,
+// with `conf`, of mnx_predict_confidence. Without `conf` it enqueues exactly mnx_predict's launches.
+static int predict_impl(mnx_engine* h, const char* name, const float* images, int32_t n_img, int32_t ref_batch,
+                        int32_t max_len, int32_t stop_on_eos, int32_t* tokens, int32_t* lengths, int32_t* n_atoms,
+                        int32_t* atom_idx, uint8_t* edges, int32_t kmax, const ConfOut* conf, void* stream) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    if (!images || !tokens || !lengths || !n_atoms || !atom_idx || !edges || n_img < 1 ||
+        (conf && (!conf->edge_scores || !conf->atom_scores || !conf->overall))) {
+        h->err = std::string(name) + ": null/empty argument";
+        return MNX_ERR_INVALID_ARG;
+    }
+    if (!h->have_tc) { h->err = std::string(name) + ": call mnx_set_token_classes first"; return MNX_ERR_INVALID_ARG; }
     const mnx_config& c = h->cfg;
     if (ref_batch < 1 || ref_batch > ROW_TILE || ref_batch > c.max_batch || max_len < 1 || max_len > c.max_len ||
         kmax < 1 || kmax > h->db.kmax) {
-        h->err = "mnx_predict: ref_batch <= min(32, max_batch), max_len <= cfg.max_len, kmax <= cfg.max_atoms required";
+        h->err = std::string(name) + ": ref_batch <= min(32, max_batch), max_len <= cfg.max_len, kmax <= cfg.max_atoms required";
         return MNX_ERR_CAPACITY;
     }
     hipStream_t s = (hipStream_t)stream;
@@ -1402,11 +1431,16 @@ int mnx_predict(mnx_engine* h, const float* images, int32_t n_img, int32_t ref_b
                     int* sl_dev = h->slot_lists + (size_t)ck.tag * ROW_TILE;
                     int* o_idx = atom_idx + (size_t)ck.first * kmax;
                     int* o_na = n_atoms + ck.first;
+                    float* o_logp = conf && conf->token_logp ? conf->token_logp + (size_t)ck.first * max_len : nullptr;
+                    double* o_scores = conf ? conf->edge_scores + (size_t)ck.first * kmax * kmax : nullptr;
                     HIPCHK(h, gather_enqueue(h->db, sl_dev, ck.n, max_len, tokens + (size_t)ck.first * max_len,
-                                             lengths + ck.first, nullptr, nullptr, s));
+                                             lengths + ck.first, o_logp, nullptr, s));
                     HIPCHK(h, atoms_enqueue(h->db, h->tc_dev, sl_dev, ck.n, kmax, o_idx, o_na, s));
                     HIPCHK(h, edges_enqueue(h->dw, h->db, h->db.hidden, sl_dev, o_idx, o_na, ck.n, kmax, h->db.T,
-                                            edges + (size_t)ck.first * kmax * kmax, nullptr, s));
+                                            edges + (size_t)ck.first * kmax * kmax, o_scores, s));
+                    if (conf)
+                        HIPCHK(h, confidence_enqueue(h->db, h->tc_dev, sl_dev, ck.n, kmax, o_idx, o_na, o_scores,
+                                                     conf->atom_scores + (size_t)ck.first * kmax, conf->overall + ck.first, s));
                     free_tags.push_back(ck.tag);
                     live.erase(live.begin() + i);
                     ++done;
@@ -1418,11 +1452,29 @@ int mnx_predict(mnx_engine* h, const float* images, int32_t n_img, int32_t ref_b
         if (tf) fprintf(tf, "%.3f seq %d live %zu next %d next_enc %d done %d free_tiles %zu\n", now_ms() - t_begin, seq,
                         live.size(), next, next_enc, done, free_tags.size());
         ++seq;
-        if (seq > 200000) { h->err = "mnx_predict: watchdog (decode did not terminate)"; return MNX_ERR_HIP; }
+        if (seq > 200000) { h->err = std::string(name) + ": watchdog (decode did not terminate)"; return MNX_ERR_HIP; }
     }
     HIPCHK(h, hipStreamSynchronize(s));
     if (tf) fprintf(tf, "%.3f end host_wait_ms %.3f\n", now_ms() - t_begin, host_wait_ms);
     return check_encoder_range(h, s);
+}
+
+extern "C" {
+
+int mnx_predict(mnx_engine* h, const float* images, int32_t n_img, int32_t ref_batch, int32_t max_len,
+                int32_t stop_on_eos, int32_t* tokens, int32_t* lengths, int32_t* n_atoms, int32_t* atom_idx,
+                uint8_t* edges, int32_t kmax, void* stream) {
+    return predict_impl(h, "mnx_predict", images, n_img, ref_batch, max_len, stop_on_eos, tokens, lengths, n_atoms, atom_idx,
+                        edges, kmax, nullptr, stream);
+}
+
+int mnx_predict_confidence(mnx_engine* h, const float* images, int32_t n_img, int32_t ref_batch, int32_t max_len,
+                           int32_t* tokens, int32_t* lengths, int32_t* n_atoms, int32_t* atom_idx, uint8_t* edges,
+                           int32_t kmax, float* token_logp, double* edge_scores, double* atom_scores, double* overall_score,
+                           void* stream) {
+    const ConfOut conf{token_logp, edge_scores, atom_scores, overall_score};
+    return predict_impl(h, "mnx_predict_confidence", images, n_img, ref_batch, max_len, 1, tokens, lengths, n_atoms,
+                        atom_idx, edges, kmax, &conf, stream);
 }
 
 int mnx_gemm_clock(mnx_engine* h, int32_t reset, double* mhz) {

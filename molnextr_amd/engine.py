@@ -23,7 +23,8 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
            "mnx_set_encoder_tap", "mnx_decode_greedy", "mnx_edges", "mnx_gemm16", "mnx_profile_enable",
            "mnx_profile_read", "mnx_set_token_classes", "mnx_predict", "mnx_atom_scan", "mnx_decode_beam", "mnx_preprocess",
            "mnx_probe_decode_attn", "mnx_predict_beam", "mnx_set_split_terms", "mnx_encoder_status",
-           "mnx_gemm16_split", "mnx_decode_forced", "mnx_gemm_clock", "mnx_probe_mfma", "mnx_set_op_terms")
+           "mnx_gemm16_split", "mnx_decode_forced", "mnx_gemm_clock", "mnx_probe_mfma", "mnx_set_op_terms",
+           "mnx_predict_confidence", "mnx_confidence")
 
 # Encoder operand modes (include/molnextr_hip.h MNX_DTYPE_*). "fp16x3" — split fp16 operands, three MFMA terms per
 # product, fp32-class results — is the default: it is the fastest mode whose results stay a factor of four inside north_star's
@@ -139,6 +140,10 @@ def load_library():
     lib.mnx_decode_beam.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.mnx_predict.restype = C.c_int
     lib.mnx_predict.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]
+    lib.mnx_predict_confidence.restype = C.c_int
+    lib.mnx_predict_confidence.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.mnx_confidence.restype = C.c_int
+    lib.mnx_confidence.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp]
     lib.mnx_predict_beam.restype = C.c_int
     lib.mnx_predict_beam.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp]
     if lib.mnx_abi_version() != ABI_VERSION:
@@ -214,12 +219,22 @@ class Engine:
         g = enc.img_size // enc.patch >> (len(enc.depths) - 1)
         self.n_mem = g * g
 
+    @staticmethod
+    def token_class_flags(tok) -> bytes:
+        """mnx_set_token_classes flags of every symbol id of `tok`: bit0 is_symbol, bit1 is_atom, bits 2-4 the length of a
+        symbol's name in characters - 1 (the span of an atom's confidence: '<unk>' is one id of five characters)."""
+        def flag(i):
+            if not tok.is_symbol(i):
+                return 0
+            return 1 | (2 if tok.is_atom(i) else 0) | (min(len(tok.itos[i]), 8) - 1) << 2
+        return bytes(flag(i) for i in range(tok.offset))
+
     def _set_token_classes(self):
-        """Hands the vocabulary's token classes to the on-device atom-position scan (mnx_predict)."""
+        """Hands the vocabulary's token classes to the on-device atom-position scan and confidences (mnx_predict)."""
         from .tokenizer import CharTokenizer
         tok = CharTokenizer(64)
         n = tok.offset
-        flags = bytes((1 if tok.is_symbol(i) else 0) | (2 if tok.is_atom(i) else 0) for i in range(n))
+        flags = self.token_class_flags(tok)
         ids = [tok.stoi[c] for c in "[]ClBr"]
         self._check(self.lib.mnx_set_token_classes(self.h, flags, n, *ids), "mnx_set_token_classes")
 
@@ -395,10 +410,12 @@ class Engine:
 
     # -- whole path, continuous batching ----------------------------------------------------------
     def predict(self, images: torch.Tensor, ref_batch: int = 32, max_len: Optional[int] = None,
-                stop_on_eos: bool = True, beam: int = 1) -> dict:
+                stop_on_eos: bool = True, beam: int = 1, confidence: bool = False) -> dict:
         """Encoder + decode + atom positions + bond head for all images: greedy with continuous batching (mnx_predict),
         or beam search reference batch by reference batch with the encoder running ahead (mnx_predict_beam; adds
-        'scores', the average log-prob of the returned hypothesis)."""
+        'scores', the average log-prob of the returned hypothesis). confidence=True (greedy, stop_on_eos only):
+        mnx_predict_confidence, which adds 'token_logp' [n,max_len] fp32, 'edge_scores' [n,kmax,kmax], 'atom_scores'
+        [n,kmax] and 'overall_score' [n] fp64."""
         assert images.is_cuda and images.dtype == torch.float32 and images.is_contiguous()
         n = images.shape[0]
         max_len = self.max_len if max_len is None else max_len
@@ -408,6 +425,21 @@ class Engine:
         n_atoms = torch.empty(n, dtype=torch.int32, device=dev)
         atom_idx = torch.zeros(n, k, dtype=torch.int32, device=dev)
         edges = torch.zeros(n, k, k, dtype=torch.uint8, device=dev)
+        if confidence:
+            if beam > 1:
+                raise NotImplementedError("beam search does not track token scores (neither does the reference's)")
+            if not stop_on_eos:
+                raise ValueError("confidences are computed for the reference's decode (stop_on_eos=True)")
+            logp = torch.zeros(n, max_len, dtype=torch.float32, device=dev)
+            edge_scores = torch.zeros(n, k, k, dtype=torch.float64, device=dev)
+            atom_scores = torch.zeros(n, k, dtype=torch.float64, device=dev)
+            overall = torch.zeros(n, dtype=torch.float64, device=dev)
+            rc = self.lib.mnx_predict_confidence(self.h, _ptr(images), n, ref_batch, max_len, _ptr(tokens), _ptr(lengths),
+                                                 _ptr(n_atoms), _ptr(atom_idx), _ptr(edges), k, _ptr(logp), _ptr(edge_scores),
+                                                 _ptr(atom_scores), _ptr(overall), _stream())
+            self._check(rc, "mnx_predict_confidence")
+            return {"tokens": tokens, "lengths": lengths, "n_atoms": n_atoms, "atom_idx": atom_idx, "edges": edges,
+                    "token_logp": logp, "edge_scores": edge_scores, "atom_scores": atom_scores, "overall_score": overall}
         if beam > 1:
             scores = torch.zeros(n, dtype=torch.float32, device=dev)
             rc = self.lib.mnx_predict_beam(self.h, _ptr(images), n, ref_batch, beam, max_len, _ptr(tokens), _ptr(lengths),
@@ -429,6 +461,27 @@ class Engine:
         self._check(self.lib.mnx_atom_scan(self.h, _ptr(tokens), _ptr(lengths), n, T, kmax, _ptr(idx), _ptr(cnt),
                                            _stream()), "mnx_atom_scan")
         return idx, cnt
+
+    def confidence(self, tokens: torch.Tensor, lengths: torch.Tensor, token_logp: torch.Tensor, atom_idx: torch.Tensor,
+                   n_atoms: torch.Tensor, edge_scores: torch.Tensor):
+        """On-device confidences (mnx_confidence) of [n,T] id sequences with their log-probs, atom positions [n,kmax] and
+        fp64 edge scores [n,kmax,kmax]: (atom_scores [n,kmax], overall_score [n]), both fp64."""
+        n, T = tokens.shape
+        kmax = atom_idx.shape[1]
+        dev = tokens.device
+        tokens = tokens.to(dtype=torch.int32).contiguous()
+        lengths = lengths.to(device=dev, dtype=torch.int32).contiguous()
+        token_logp = token_logp.to(device=dev, dtype=torch.float32).contiguous()
+        atom_idx = atom_idx.to(device=dev, dtype=torch.int32).contiguous()
+        n_atoms = n_atoms.to(device=dev, dtype=torch.int32).contiguous()
+        edge_scores = edge_scores.to(device=dev, dtype=torch.float64).contiguous()
+        assert tuple(token_logp.shape) == (n, T) and tuple(edge_scores.shape) == (n, kmax, kmax)
+        atom_scores = torch.zeros(n, kmax, dtype=torch.float64, device=dev)
+        overall = torch.zeros(n, dtype=torch.float64, device=dev)
+        self._check(self.lib.mnx_confidence(self.h, _ptr(tokens), _ptr(lengths), _ptr(token_logp), n, T, _ptr(atom_idx),
+                                            _ptr(n_atoms), _ptr(edge_scores), kmax, _ptr(atom_scores), _ptr(overall),
+                                            _stream()), "mnx_confidence")
+        return atom_scores, overall
 
     def profile(self, enable):
         """True / n: bracket the GEMMs of every n-th encode call with HIP events (at most 16 calls); False: off."""

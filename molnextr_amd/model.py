@@ -98,18 +98,28 @@ def decode_batch(engine: Engine, features: torch.Tensor, tokenizer=None, ref_bat
 
 
 def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_batch_size: int = 16,
-                     max_len: Optional[int] = None, beam_size: int = 1) -> List[dict]:
+                     max_len: Optional[int] = None, beam_size: int = 1, compute_confidence: bool = False) -> List[dict]:
     """Encoder + Decoder.decode for MANY images through the engine's continuous-batching path (mnx_predict):
     same per-image dicts as `decode_batch`, identical results (the on-device atom scan equals
-    sequence_to_smiles' indices), much higher throughput. Confidences are not available on this path.
-    beam_size > 1: mnx_predict_beam (best hypothesis per image, 'beam_scores' = [its average log-prob])."""
+    sequence_to_smiles' indices), much higher throughput. compute_confidence=True: mnx_predict_confidence, the same
+    pipeline with the confidences computed on the device when a reference batch retires; the dicts gain the keys of
+    decode_batch(compute_confidence=True) ('atom_scores' in 'chartok_coords', 'edge_scores', 'overall_score').
+    beam_size > 1: mnx_predict_beam (best hypothesis per image, 'beam_scores' = [its average log-prob]); no confidences."""
     tok = (tokenizer or get_tokenizer())["chartok_coords"]
-    out = engine.predict(images, ref_batch=ref_batch_size, max_len=max_len, beam=beam_size)
+    if compute_confidence and beam_size > 1:
+        raise NotImplementedError("beam search does not track token scores (neither does the reference's)")
+    conf = {"confidence": True} if compute_confidence else {}
+    out = engine.predict(images, ref_batch=ref_batch_size, max_len=max_len, beam=beam_size, **conf)
     scores = out["scores"].cpu().numpy() if beam_size > 1 else None
     lens = out["lengths"].cpu().numpy()
     toks = out["tokens"].cpu().numpy()
     n_atoms = out["n_atoms"].cpu().numpy()
     edges = out["edges"].cpu().numpy()
+    if compute_confidence:
+        k_hi = int(n_atoms.max(initial=0))          # only the atoms of this call cross to the host (fp64 [n,160,160]: 205 KB each)
+        edge_scores = out["edge_scores"][:, :k_hi, :k_hi].cpu().numpy()
+        atom_scores = out["atom_scores"][:, :k_hi].cpu().numpy()
+        overall = out["overall_score"].cpu().numpy()
     preds = []
     for b in range(len(lens)):
         r = tok.sequence_to_smiles(toks[b, :lens[b]].tolist())
@@ -118,6 +128,10 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
         preds.append({"chartok_coords": r, "edges": edges[b, :k, :k].astype(int).tolist()})
         if scores is not None:
             preds[-1]["beam_scores"] = [float(scores[b])]
+        if compute_confidence:
+            r["atom_scores"] = atom_scores[b, :k].tolist()
+            preds[-1]["edge_scores"] = edge_scores[b, :k, :k].tolist()
+            preds[-1]["overall_score"] = float(overall[b])
     return preds
 
 
@@ -294,34 +308,20 @@ class molnextr:
             # results depend on the row inside the reference batch (positional-encoding quirk), so a silently
             # different batch size would silently change tokens
             raise ValueError(f"batch_size must be 1..{cap} (one reference batch per {ROWS}-row decode tile); got {batch_size}")
-        if not return_confidence:
-            # throughput path: many images per engine call, reference batches of `batch_size` kept as numbering units;
-            # the group is a whole number of reference batches so that batch boundaries do not drift between groups
-            group = (self.group_images // batch_size) * batch_size
-            groups = [input_images[i:i + group] for i in range(0, len(input_images), group)]
-            gen = self._prefetched(groups)
-            try:
-                for x in gen:
-                    preds += self._with_fallback(
-                        lambda eng: predict_pipeline(eng, x, self.tokenizer, ref_batch_size=batch_size))
-                    self._groups_done += 1
-            finally:
-                if hasattr(gen, "close"):
-                    gen.close()         # a call abandoned by _RestartCall leaves no helper thread behind
-        else:
-            step = max(self.engine.max_batch // batch_size, 1) * batch_size
-            for i in range(0, len(input_images), step):
-                x = self._transform(input_images[i:i + step])
-
-                def conf_job(eng):
-                    feats = eng.encode(x)
-                    if eng.encoder_nonfinite():          # fp16 operand range exceeded (mnx_predict reports it by itself)
-                        from .engine import MNX_ERR_RANGE
-                        raise MnxError("encoder features are not finite: an activation left the fp16 range of the operand "
-                                       f"mode '{eng.dtype}'", code=MNX_ERR_RANGE)
-                    return decode_batch(eng, feats, self.tokenizer, ref_batch_size=batch_size, compute_confidence=True)
-                preds += self._with_fallback(conf_job)
+        # throughput path: many images per engine call, reference batches of `batch_size` kept as numbering units;
+        # the group is a whole number of reference batches so that batch boundaries do not drift between groups
+        group = (self.group_images // batch_size) * batch_size
+        groups = [input_images[i:i + group] for i in range(0, len(input_images), group)]
+        conf = {"compute_confidence": True} if return_confidence else {}
+        gen = self._prefetched(groups)
+        try:
+            for x in gen:
+                preds += self._with_fallback(
+                    lambda eng: predict_pipeline(eng, x, self.tokenizer, ref_batch_size=batch_size, **conf))
                 self._groups_done += 1
+        finally:
+            if hasattr(gen, "close"):
+                gen.close()         # a call abandoned by _RestartCall leaves no helper thread behind
         return preds
 
     def _assemble(self, preds: List[dict], input_images: List, return_atoms_bonds: bool, return_confidence: bool):
