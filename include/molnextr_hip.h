@@ -317,6 +317,18 @@ int mnx_gemm16_split(mnx_engine* h, int32_t epi, const void* A, int64_t a_lo, co
                      void* C, int64_t c_lo, const float* bias, int32_t M, int32_t N, int32_t K, int32_t terms,
                      void* stream);
 
+/* Test aid: the encoder's window attention (12x12 windows, head_dim 32) on caller device buffers, with the engine's
+ * compute_dtype. qkv [B*H*W, 3C] and out [B*H*W, C] are token-major in the original (unshifted) token order, table is the
+ * reference's relative_position_bias_table, fp32 [(2*12-1)^2, heads] (the layout mnx_create uploads). shift = 0 or
+ * 1..11 (the cyclic shift and its -100 region mask, as the encoder's odd blocks run it with 6). Split compute_dtypes
+ * (BF16X3 / FP16X3 / FP16X3M): qkv and out point at hi planes, qkv_lo / out_lo are the ELEMENT offsets of the lo planes
+ * (>= the hi plane's size, multiples of 8), terms = 3 (window_attn_pipe_kernel) or 1 (kh.qh and vh.ph alone:
+ * window_attn_split_kernel); terms = 3 | 0x100 runs window_attn_split_kernel with three terms. The other compute_dtypes
+ * take qkv_lo = out_lo = 0 and terms = 1. Buffers are 16-byte aligned. MNX_ERR_INVALID_ARG (with mnx_last_error) for any
+ * other shape, offset or dtype / terms combination. Asynchronous on `stream`. */
+int mnx_window_attn(mnx_engine* h, const void* qkv, int64_t qkv_lo, const float* table, void* out, int64_t out_lo,
+                    int32_t B, int32_t H, int32_t W, int32_t C, int32_t heads, int32_t shift, int32_t terms, void* stream);
+
 /* Measurement aid for bench.py: while enabled, mnx_encode brackets every kernel launch of the sampled calls with a
  * pair of HIP events recorded on the stream the kernel is launched on (also inside mnx_predict, i.e. live in a timed
  * region). `enable` = n > 0: every n-th mnx_encode call since the enable is sampled, at most 4 calls (the event pool

@@ -4,6 +4,8 @@
 // MFMA GEMMs are produced here as 16-bit (bf16 by default).
 #include <stdlib.h>
 
+#include <algorithm>
+
 #include "common.h"
 #include "kernels.h"
 
@@ -755,8 +757,8 @@ __global__ __launch_bounds__(576, 6) void window_attn_pipe_kernel(const T* __res
         const int var = i / WN, t = i % WN, ty = t / WS, tx = t % WS;
         const int reg = ((var & 2) ? (ty < WS - shift ? 1 : 2) : 0) * 3 + ((var & 1) ? (tx < WS - shift ? 1 : 2) : 0);
         int e = (ty * (2 * WS - 1) + tx) | (reg << 16);
-        if (!MASKED && var == 1) e = (ty * W + tx) * 6 * C;      // the unmasked kernel's offset tables, see below
-        if (!MASKED && var == 2) e = (ty * W + tx) * 2 * C;
+        if (!MASKED && var == 1) e = (int)((unsigned)(ty * W + tx) * 6u * (unsigned)C);   // the unmasked kernel's offset tables, see below
+        if (!MASKED && var == 2) e = (int)((unsigned)(ty * W + tx) * 2u * (unsigned)C);
         kinfo4[i] = e;
     }
     // Unmasked kernel (round 6): its windows never wrap around the image (cls 0: no shift; cls 1: the inner windows of a shifted
@@ -812,17 +814,23 @@ __global__ __launch_bounds__(576, 6) void window_attn_pipe_kernel(const T* __res
         const int ty = (key * 171) >> 11, tx = key - ty * WS;     // key / 12, key % 12 for key < 144
         int y = w.wy * WS + ty + shift; if (y >= H) y -= H;
         int x = w.wx * WS + tx + shift; if (x >= W) x -= W;
-        return (unsigned)((w.b * H + y) * W + x);
+        return ((unsigned)w.b * (unsigned)H + (unsigned)y) * (unsigned)W + (unsigned)x;
     };
-    // byte offset of (token `key`, head of the item) in a qkv plane / in a context plane (< 2^32)
+    // row of the window's first token (unmasked kernel: its windows do not wrap around the image)
+    auto window_row = [=](const Item& w) {
+        return ((unsigned)w.b * (unsigned)H + (unsigned)(w.wy * WS + shift)) * (unsigned)W + (unsigned)(w.wx * WS + shift);
+    };
+    // byte offset of (token `key`, head of the item) in a qkv plane / in a context plane. All of it is unsigned 32-bit
+    // arithmetic; launch_window_attn hands the kernel at most 2^32 bytes of qkv plane per launch (image chunks), so no
+    // offset wraps (a context plane is a third of that)
     auto qkv_off = [=](const Item& w, int key, bool tab) {
         if (!MASKED && tab)
-            return (unsigned)(((w.b * H + w.wy * WS + shift) * W + w.wx * WS + shift) * 6 * C + w.head * HD * 2) + (unsigned)rel_qkv[key];
+            return window_row(w) * 6u * (unsigned)C + (unsigned)(w.head * HD * 2) + (unsigned)rel_qkv[key];
         return (token_row(w, key) * 3u * (unsigned)C + (unsigned)(w.head * HD)) * 2u;
     };
     auto ctx_off = [=](const Item& w, int key, bool tab) {
         if (!MASKED && tab)
-            return (unsigned)(((w.b * H + w.wy * WS + shift) * W + w.wx * WS + shift) * 2 * C + w.head * HD * 2) + (unsigned)rel_ctx[key];
+            return window_row(w) * 2u * (unsigned)C + (unsigned)(w.head * HD * 2) + (unsigned)rel_ctx[key];
         return (token_row(w, key) * (unsigned)C + (unsigned)(w.head * HD)) * 2u;
     };
     // DMA: wave w moves key rows 16w..16w+15, lane l row 16w + l/4, LDS piece l%4 (K: global piece l%4; V: global
@@ -844,7 +852,7 @@ __global__ __launch_bounds__(576, 6) void window_attn_pipe_kernel(const T* __res
     v8 qh_n, ql_n;
     float tab_n;
     int var_n;
-    unsigned ooff_n;                                // bytes into a context plane; < 2^32 (M*C*2 <= 5.3e8)
+    unsigned ooff_n;                                // bytes into a context plane (< 2^32: see qkv_off)
     auto fetch_q = [&](const Item& w, bool tab) {   // MFMA role: query 16w + fr, channel group fg
         const int tid = thread_id(), fr = tid & 15, fg = (tid >> 4) & 3;
         const unsigned qb = qkv_off(w, wave * 16 + fr, tab) + (unsigned)(fg * 16);
@@ -1013,29 +1021,40 @@ static hipError_t attn_lds_opt_in() {
 
 hipError_t launch_window_attn(int dtype, const void* qkv16, const float* rel_table, void* out16, int B, int H, int W,
                               int C, int heads, int shift, hipStream_t s, size_t qkv_lo, size_t out_lo, int terms) {
+    const bool force_split = (terms & 0x100) != 0;     // test aid: window_attn_split_kernel at terms = 3 as well
+    terms &= 0xff;
     if (C != heads * HD || H % WS || W % WS) return hipErrorInvalidValue;
     dim3 grid(B * (H / WS) * (W / WS) * heads);
     if (dt_split(dtype)) {
-        if (qkv_lo == 0 || out_lo == 0 || (terms != 1 && terms != 3)) return hipErrorInvalidValue;
-        if (terms == 3) {
+        if (qkv_lo == 0 || out_lo == 0 || (terms != 1 && terms != 3) || (force_split && terms != 3)) return hipErrorInvalidValue;
+        if (terms == 3 && !force_split) {
             // persistent form: two 576-thread workgroups per CU (80.6 KB of LDS each), contiguous item ranges; one launch
-            // for the windows without shift mask, one for the border windows of a shifted layer
+            // for the windows without shift mask, one for the border windows of a shifted layer. The kernel addresses a
+            // plane as one base pointer + 32-bit byte offsets, so the images go in chunks of at most 2^32 bytes of qkv
+            // plane (606 images of Swin-B stage 1 at 384^2: one chunk up to there); the lo-plane offsets are relative to
+            // the base and move with it
             const int nWh = H / WS, nWw = W / WS;
-            const int n_plain = shift > 0 ? B * (nWh - 1) * (nWw - 1) * heads : (int)grid.x;
-            const int n_border = shift > 0 ? B * (nWh + nWw - 1) * heads : 0;
+            const size_t img_qkv = (size_t)H * W * 3 * C, img_out = (size_t)H * W * C;   // elements per image
+            const int chunk = (int)std::min<size_t>((size_t)B, ((size_t)1 << 32) / (img_qkv * 2));
+            if (chunk < 1) return hipErrorInvalidValue;
 #define MNX_ATTN_PIPE(TT, MASKED, CLS, NITEMS)                                                                          \
     do {                                                                                                                \
         hipError_t e_ = attn_lds_opt_in<window_attn_pipe_kernel<TT, MASKED>>();                                           \
         if (e_ != hipSuccess) return e_;                                                                                \
         hipLaunchKernelGGL((window_attn_pipe_kernel<TT, MASKED>), dim3((NITEMS) < 2 * persistent_cus() ? (NITEMS) : 2 * persistent_cus()), dim3(576), WA_LDS, s,  \
-                           (const TT*)qkv16, qkv_lo, rel_table, (TT*)out16, out_lo, H, W, C, heads, shift, CLS, NITEMS); \
+                           (const TT*)qkv16 + b0 * img_qkv, qkv_lo, rel_table, (TT*)out16 + b0 * img_out, out_lo, H, W, C, heads, shift, CLS, NITEMS); \
     } while (0)
-            if (dtype == MNX_DT_F16X3) {
-                if (n_plain > 0) MNX_ATTN_PIPE(f16_t, false, shift > 0 ? 1 : 0, n_plain);
-                if (n_border > 0) MNX_ATTN_PIPE(f16_t, true, 2, n_border);
-            } else {
-                if (n_plain > 0) MNX_ATTN_PIPE(bf16_t, false, shift > 0 ? 1 : 0, n_plain);
-                if (n_border > 0) MNX_ATTN_PIPE(bf16_t, true, 2, n_border);
+            for (size_t b0 = 0; b0 < (size_t)B; b0 += chunk) {
+                const int nb = (int)std::min<size_t>(chunk, B - b0);
+                const int n_plain = shift > 0 ? nb * (nWh - 1) * (nWw - 1) * heads : nb * nWh * nWw * heads;
+                const int n_border = shift > 0 ? nb * (nWh + nWw - 1) * heads : 0;
+                if (dtype == MNX_DT_F16X3) {
+                    if (n_plain > 0) MNX_ATTN_PIPE(f16_t, false, shift > 0 ? 1 : 0, n_plain);
+                    if (n_border > 0) MNX_ATTN_PIPE(f16_t, true, 2, n_border);
+                } else {
+                    if (n_plain > 0) MNX_ATTN_PIPE(bf16_t, false, shift > 0 ? 1 : 0, n_plain);
+                    if (n_border > 0) MNX_ATTN_PIPE(bf16_t, true, 2, n_border);
+                }
             }
 #undef MNX_ATTN_PIPE
             return hipGetLastError();
@@ -1048,6 +1067,7 @@ hipError_t launch_window_attn(int dtype, const void* qkv16, const float* rel_tab
                                (bf16_t*)out16, out_lo, H, W, C, heads, shift, terms);
         return hipGetLastError();
     }
+    if (force_split) return hipErrorInvalidValue;
 #define MNX_ATTN(TT)                                                                                                  \
     hipLaunchKernelGGL((window_attn_kernel<TT>), grid, dim3(576), 0, s, (const TT*)qkv16, rel_table, (TT*)out16, H, W, \
                        C, heads, shift)

@@ -6,6 +6,7 @@
 
 #include <time.h>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -1594,6 +1595,35 @@ int mnx_gemm16_split(mnx_engine* h, int32_t epi, const void* A, int64_t a_lo, co
     }
     HIPCHK(h, launch_gemm16(h->dt, epi, A, W, C, bias, epi == EPI_RESID_F32 ? (const float*)C : nullptr, M, N,
                             K, (hipStream_t)stream, &sp));
+    return MNX_OK;
+}
+
+int mnx_window_attn(mnx_engine* h, const void* qkv, int64_t qkv_lo, const float* table, void* out, int64_t out_lo,
+                    int32_t B, int32_t H, int32_t W, int32_t C, int32_t heads, int32_t shift, int32_t terms, void* stream) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    auto bad = [&](const char* m) { h->err = std::string("mnx_window_attn: ") + m; return MNX_ERR_INVALID_ARG; };
+    if (!qkv || !table || !out) return bad("null pointer");
+    if (((uintptr_t)qkv | (uintptr_t)out) & 15) return bad("qkv and out must be 16-byte aligned");
+    if (B < 1 || H < 12 || W < 12 || H % 12 || W % 12) return bad("B >= 1 and H, W positive multiples of the window (12) required");
+    if (heads < 1 || C != heads * 32) return bad("C must be heads * 32 (head_dim 32)");
+    if (shift < 0 || shift >= 12) return bad("shift must be 0..11");
+    const int64_t rows = (int64_t)B * H * W;
+    if (rows > INT32_MAX || (int64_t)B * (H / 12) * (W / 12) * heads > INT32_MAX)
+        return bad("B * H * W and the number of (window, head) items must fit in int32");
+    const bool split = dt_split(h->dt);
+    const int base = terms & 0xff;
+    if ((terms & ~0x1ff) || (split ? (base != 1 && base != 3) || ((terms & 0x100) && base != 3) : terms != 1))
+        return bad("terms must be 1 or 3 (| 0x100 with 3) for the split compute_dtypes and 1 for the others");
+    if (split) {
+        if (qkv_lo < rows * 3 * C || out_lo < rows * C || (qkv_lo | out_lo) & 7)
+            return bad("qkv_lo / out_lo must be at least the hi plane's size and multiples of 8 elements");
+        if ((int64_t)H * W * 3 * C * 2 > ((int64_t)1 << 32)) return bad("one image's qkv plane exceeds 2^32 bytes");
+    } else if (qkv_lo || out_lo) {
+        return bad("qkv_lo / out_lo must be 0 for the single-plane compute_dtypes");
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, launch_window_attn(h->dt, qkv, table, out, B, H, W, C, heads, shift, (hipStream_t)stream, (size_t)qkv_lo,
+                                 (size_t)out_lo, terms));
     return MNX_OK;
 }
 

@@ -82,7 +82,8 @@ hipError_t launch_layernorm16(int dtype, const float* x, const float* gamma, con
 hipError_t launch_merge_ln16(int dtype, const float* x, const float* gamma, const float* beta, void* y16, int B, int H,
                              int W, int C, float eps, hipStream_t s, size_t y_lo = 0, int planes = 2);
 // window attention: qkv16 [B*H*W, 3C] -> out16 [B*H*W, C] (original token order); table [529, heads] fp32.
-// Split dtypes: qkv_lo / out_lo = element offsets of the lo planes; terms as SplitArgs::terms.
+// Split dtypes: qkv_lo / out_lo = element offsets of the lo planes; terms as SplitArgs::terms (1 or 3; test aid:
+// terms | 0x100 runs window_attn_split_kernel at terms = 3 instead of the persistent window_attn_pipe_kernel).
 hipError_t launch_window_attn(int dtype, const void* qkv16, const float* rel_table, void* out16, int B, int H, int W,
                               int C, int heads, int shift, hipStream_t s, size_t qkv_lo = 0, size_t out_lo = 0,
                               int terms = 3);

@@ -24,7 +24,7 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
            "mnx_profile_read", "mnx_set_token_classes", "mnx_predict", "mnx_atom_scan", "mnx_decode_beam", "mnx_preprocess",
            "mnx_probe_decode_attn", "mnx_predict_beam", "mnx_set_split_terms", "mnx_encoder_status",
            "mnx_gemm16_split", "mnx_decode_forced", "mnx_gemm_clock", "mnx_probe_mfma", "mnx_set_op_terms",
-           "mnx_predict_confidence", "mnx_confidence")
+           "mnx_predict_confidence", "mnx_confidence", "mnx_window_attn")
 
 # Encoder operand modes (include/molnextr_hip.h MNX_DTYPE_*). "fp16x3" — split fp16 operands, three MFMA terms per
 # product, fp32-class results — is the default: it is the fastest mode whose results stay a factor of four inside north_star's
@@ -120,6 +120,8 @@ def load_library():
     lib.mnx_gemm16.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, vp]
     lib.mnx_gemm16_split.restype = C.c_int
     lib.mnx_gemm16_split.argtypes = [vp, i32, vp, C.c_int64, vp, C.c_int64, C.c_float, vp, C.c_int64, vp, i32, i32, i32, i32, vp]
+    lib.mnx_window_attn.restype = C.c_int
+    lib.mnx_window_attn.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.mnx_profile_enable.restype = C.c_int
     lib.mnx_profile_enable.argtypes = [vp, i32]
     lib.mnx_profile_read.restype = C.c_int
@@ -537,6 +539,17 @@ class Engine:
         self._check(self.lib.mnx_gemm16_split(self.h, epi, _ptr(A2), M * K, _ptr(W2), N * K, float(oscale), _ptr(Cout), c_lo,
                                               _ptr(bias), M, N, K, terms, _stream()), "mnx_gemm16_split")
         return Cout
+
+    def window_attn(self, qkv: torch.Tensor, table: torch.Tensor, out: torch.Tensor, B: int, H: int, W: int, heads: int,
+                    shift: int, terms: int = 3, qkv_lo: int = 0, out_lo: int = 0):
+        """The encoder's window attention on caller buffers (test aid, mnx_window_attn): qkv [B*H*W, 3C] -> out [B*H*W, C]
+        in the engine's operand type, table fp32 [529, heads]. Split modes: qkv / out start with the hi planes, qkv_lo /
+        out_lo are the element offsets of the lo planes from them; terms 3, 1 or 3 | 0x100 (the non-persistent kernel).
+        Plain modes: terms = 1."""
+        assert qkv.is_cuda and out.is_cuda and table.is_cuda and table.dtype == torch.float32 and table.is_contiguous()
+        self._check(self.lib.mnx_window_attn(self.h, _ptr(qkv), qkv_lo, _ptr(table), _ptr(out), out_lo, B, H, W, heads * 32,
+                                             heads, shift, terms, _stream()), "mnx_window_attn")
+        return out
 
     def gemm16(self, epi: int, A: torch.Tensor, Wt: torch.Tensor, Cout: torch.Tensor, bias: Optional[torch.Tensor]):
         M, K = A.shape
