@@ -329,6 +329,16 @@ int mnx_gemm16_split(mnx_engine* h, int32_t epi, const void* A, int64_t a_lo, co
 int mnx_window_attn(mnx_engine* h, const void* qkv, int64_t qkv_lo, const float* table, void* out, int64_t out_lo,
                     int32_t B, int32_t H, int32_t W, int32_t C, int32_t heads, int32_t shift, int32_t terms, void* stream);
 
+/* Test aid: copy one raw block of the decoder's K / V cache (24-bit block fixed point, molnextr_amd/csrc/kvq.h) into the
+ * device buffer dst: which = 0 self-attention keys, 1 self-attention values, 2 memory keys, 3 memory values; layer
+ * 0..dec_layers-1, head 0..dec_heads-1; owner = the slot (0..dec_slots-1) of a self block or the memory block of a memory
+ * one. A block is the nk rows of one (owner, layer, head), nk = (max_len + 3) & ~3 for self blocks and (S + 3) & ~3 for
+ * memory blocks (S = 144 memory positions): nk * 100 bytes, laid out as [nk][32] int16 hi | [nk][32] uint8 lo | [nk]
+ * float scale; row j holds q = hi * 256 + lo and the value q * scale. After mnx_decode_greedy / mnx_decode_forced, row b
+ * of the call used slot b (its key t at row t) and memory block b. Out-of-range arguments return MNX_ERR_INVALID_ARG
+ * (with mnx_last_error). Asynchronous on `stream`. */
+int mnx_kv_block(mnx_engine* h, int32_t which, int32_t layer, int32_t owner, int32_t head, void* dst, void* stream);
+
 /* Measurement aid for bench.py: while enabled, mnx_encode brackets every kernel launch of the sampled calls with a
  * pair of HIP events recorded on the stream the kernel is launched on (also inside mnx_predict, i.e. live in a timed
  * region). `enable` = n > 0: every n-th mnx_encode call since the enable is sampled, at most 4 calls (the event pool

@@ -1627,4 +1627,28 @@ int mnx_window_attn(mnx_engine* h, const void* qkv, int64_t qkv_lo, const float*
     return MNX_OK;
 }
 
+int mnx_kv_block(mnx_engine* h, int32_t which, int32_t layer, int32_t owner, int32_t head, void* dst, void* stream) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    auto bad = [&](const char* m) { h->err = std::string("mnx_kv_block: ") + m; return MNX_ERR_INVALID_ARG; };
+    const mnx_config& c = h->cfg;
+    const DecBuffers& db = h->db;
+    if (!dst) return bad("null dst");
+    if (which < 0 || which > 3) return bad("which must be 0 (self K), 1 (self V), 2 (memory K) or 3 (memory V)");
+    if (layer < 0 || layer >= c.dec_layers || head < 0 || head >= c.dec_heads) return bad("layer or head out of range");
+    const char* src;
+    size_t bytes;
+    if (which < 2) {
+        if (owner < 0 || owner >= db.slots) return bad("slot out of range");
+        bytes = kvq_block_bytes(db.Tq);   // self_k / self_v: [layer][slot][head] blocks of Tq rows
+        src = (which == 0 ? db.self_k : db.self_v) + (((size_t)layer * db.slots + owner) * c.dec_heads + head) * bytes;
+    } else {
+        if (owner < 0 || owner >= db.mem_blocks) return bad("memory block out of range");
+        bytes = kvq_block_bytes(db.Sq);   // mem_kv: [memory block][layer][K|V][head] blocks of Sq rows
+        src = db.mem_kv + ((((size_t)owner * c.dec_layers + layer) * 2 + (which - 2)) * c.dec_heads + head) * bytes;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return MNX_OK;
+}
+
 }  // extern "C"

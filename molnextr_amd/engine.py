@@ -24,7 +24,7 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
            "mnx_profile_read", "mnx_set_token_classes", "mnx_predict", "mnx_atom_scan", "mnx_decode_beam", "mnx_preprocess",
            "mnx_probe_decode_attn", "mnx_predict_beam", "mnx_set_split_terms", "mnx_encoder_status",
            "mnx_gemm16_split", "mnx_decode_forced", "mnx_gemm_clock", "mnx_probe_mfma", "mnx_set_op_terms",
-           "mnx_predict_confidence", "mnx_confidence", "mnx_window_attn")
+           "mnx_predict_confidence", "mnx_confidence", "mnx_window_attn", "mnx_kv_block")
 
 # Encoder operand modes (include/molnextr_hip.h MNX_DTYPE_*). "fp16x3" — split fp16 operands, three MFMA terms per
 # product, fp32-class results — is the default: it is the fastest mode whose results stay a factor of four inside north_star's
@@ -122,6 +122,8 @@ def load_library():
     lib.mnx_gemm16_split.argtypes = [vp, i32, vp, C.c_int64, vp, C.c_int64, C.c_float, vp, C.c_int64, vp, i32, i32, i32, i32, vp]
     lib.mnx_window_attn.restype = C.c_int
     lib.mnx_window_attn.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, i32, i32, i32, i32, i32, i32, i32, vp]
+    lib.mnx_kv_block.restype = C.c_int
+    lib.mnx_kv_block.argtypes = [vp, i32, i32, i32, i32, vp, vp]
     lib.mnx_profile_enable.restype = C.c_int
     lib.mnx_profile_enable.argtypes = [vp, i32]
     lib.mnx_profile_read.restype = C.c_int
@@ -549,6 +551,21 @@ class Engine:
         assert qkv.is_cuda and out.is_cuda and table.is_cuda and table.dtype == torch.float32 and table.is_contiguous()
         self._check(self.lib.mnx_window_attn(self.h, _ptr(qkv), qkv_lo, _ptr(table), _ptr(out), out_lo, B, H, W, heads * 32,
                                              heads, shift, terms, _stream()), "mnx_window_attn")
+        return out
+
+    KV_WHICH = {"self_k": 0, "self_v": 1, "mem_k": 2, "mem_v": 3}
+
+    def kv_block(self, which: str, layer: int, owner: int, head: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One raw block of the decoder's K / V cache (test aid, mnx_kv_block) as uint8 bytes on the device: which is a key
+        of KV_WHICH, owner the slot (self) or memory block (memory); after decode_greedy / decode_forced row b used slot b and
+        memory block b. The block holds nk = kvq_rows(max_len) (self) or kvq_rows(144) (memory) rows of 100 bytes:
+        [nk][32] int16 hi | [nk][32] uint8 lo | [nk] float32 scale (csrc/kvq.h)."""
+        nk = ((self.max_len if which.startswith("self") else self.n_mem) + 3) & ~3
+        if out is None:
+            out = torch.empty(nk * 100, dtype=torch.uint8, device=torch.device("cuda", self.device))
+        assert out.is_cuda and out.dtype == torch.uint8 and out.numel() >= nk * 100
+        self._check(self.lib.mnx_kv_block(self.h, self.KV_WHICH[which], layer, owner, head, _ptr(out), _stream()),
+                    "mnx_kv_block")
         return out
 
     def gemm16(self, epi: int, A: torch.Tensor, Wt: torch.Tensor, Cout: torch.Tensor, bias: Optional[torch.Tensor]):

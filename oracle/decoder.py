@@ -163,3 +163,69 @@ def greedy_decode(features, sd, cfg: DecoderConfig = DECODER_DEFAULT, max_len: O
     hidden = [hid[r, :len(toks[r])].clone() for r in range(B)]
     scores = [float(torch.tensor(lp_r).mean().exp()) for lp_r in logps]
     return GreedyResult(toks, logps, hidden, scores, fin_step, logits_trace)
+
+
+@torch.no_grad()
+def forced_decode(features, sd, ids, lens, cfg: DecoderConfig = DECODER_DEFAULT, dtype=torch.float64, kv=None,
+                  drop_key=None) -> torch.Tensor:
+    """greedy_decode's loop TEACHER-FORCED along `ids` [B,T] (row r stops after lens[r] steps): the raw logits of every
+    (row, step) as [B, max(lens), V] in `dtype` (NaN past a row's length). Every operation runs in `dtype` — the softmax
+    included, which greedy_decode evaluates in float32 — so dtype=float64 is a float64 restatement of the decode, and
+    float32 forced along greedy_decode's own tokens repeats its trace bit for bit (tests/test_oracle_forced.py).
+    The PE row is the row's rank in the current (compacted) batch, as in greedy_decode.
+
+    Test aids for modified oracles: kv(t) rounds every self- and memory-K / V row (t [..., dh]) as it is stored;
+    drop_key = j removes key j from every self-attention softmax once the row has passed it (step > j)."""
+    sd = {k: v.to(dtype) if v.is_floating_point() else v for k, v in sd.items()}
+    ids = torch.as_tensor(ids, dtype=torch.long)
+    lens = [int(n) for n in lens]
+    memory = F.linear(features.reshape(features.shape[0], -1, features.shape[-1]).to(dtype),
+                      sd[P + "enc_trans_layer.0.weight"], sd[P + "enc_trans_layer.0.bias"])
+    B, S, D = memory.shape
+    h, dh, L = cfg.heads, cfg.d_model // cfg.heads, cfg.layers
+    rnd = kv if kv is not None else (lambda t: t)
+    mem_kv = [(rnd(k), rnd(v)) for k, v in cross_kv(memory, sd, cfg)]
+    emb_w = sd[P + "embeddings.make_embedding.emb_luts.0.weight"]
+    pe = sd[P + "embeddings.make_embedding.pe.pe"].reshape(-1, D)
+    T = max(lens)
+    self_k = torch.zeros(L, B, h, T, dh, dtype=dtype)
+    self_v = torch.zeros(L, B, h, T, dh, dtype=dtype)
+    logits_out = torch.full((B, T, cfg.vocab), float("nan"), dtype=dtype)
+
+    def mha(q, k, v, prefix, step):
+        n = q.shape[0]
+        qh = q.reshape(n, h, 1, dh) / math.sqrt(dh)
+        s = qh @ k.transpose(2, 3)
+        if step is not None and drop_key is not None and step > drop_key:
+            s[..., drop_key] = -math.inf
+        return _lin((s.softmax(-1) @ v).reshape(n, h * dh), sd, prefix + ".final_linear")
+
+    alive = list(range(B))
+    prev = torch.full((B,), cfg.sos_id, dtype=torch.long)
+    for step in range(T):
+        idx = torch.tensor(alive)
+        n = len(alive)
+        x = emb_w[prev[idx]] * math.sqrt(D) + pe[:n]            # PE by compacted row, as greedy_decode
+        for l in range(L):
+            lp = f"{P}decoder.transformer_layers.{l}"
+            xn = _ln(x, sd, lp + ".layer_norm_1")
+            self_k[l, idx, :, step] = rnd(_lin(xn, sd, lp + ".self_attn.linear_keys").reshape(n, h, dh))
+            self_v[l, idx, :, step] = rnd(_lin(xn, sd, lp + ".self_attn.linear_values").reshape(n, h, dh))
+            q = _lin(xn, sd, lp + ".self_attn.linear_query")
+            a = mha(q, self_k[l, idx, :, :step + 1], self_v[l, idx, :, :step + 1], lp + ".self_attn", step)
+            query = a + x
+            q2 = _lin(_ln(query, sd, lp + ".layer_norm_2"), sd, lp + ".context_attn.linear_query")
+            y = mha(q2, mem_kv[l][0][idx], mem_kv[l][1][idx], lp + ".context_attn", None) + query
+            ff = lp + ".feed_forward"
+            x = _lin(F.gelu(_lin(_ln(y, sd, ff + ".layer_norm"), sd, ff + ".w_1")), sd, ff + ".w_2") + y
+        logits = _lin(_ln(x, sd, P + "decoder.layer_norm"), sd, P + "output_layer")
+        nxt = []
+        for i, r in enumerate(alive):
+            logits_out[r, step] = logits[i]
+            prev[r] = int(ids[r, step])
+            if step + 1 < lens[r]:
+                nxt.append(r)
+        alive = nxt
+        if not alive:
+            break
+    return logits_out

@@ -203,12 +203,16 @@ def round_sig(x, bits, fp16_range=False):
 def round_block(x, bits):
     """Block fixed point along the LAST axis (the 32 channels of one key / value row of one head): the row shares a power-of-two
     scale 2^e >= max |x| of the row, every element is an integer of `bits` bits (two's complement, round to nearest) times
-    2^(e - bits + 1). What a K / V cache row stored as int16 / int24 + one exponent byte keeps: absolute error <= 2^(e - bits)."""
-    amax = x.abs().amax(-1, keepdim=True).clamp_min(1e-30)
-    e = torch.floor(torch.log2(amax)) + 1.0                    # 2^e > amax
-    q = torch.exp2(e - (bits - 1))
+    2^(e - bits + 1). What a K / V cache row stored as int16 / int24 + one exponent byte keeps: absolute error <= 2^(e - bits).
+    e is kvq_quant's: frexp's exponent of the float32 row max (0 for a row of zeros), clamped to [-100, 120], so that at
+    bits = 24 finite rows round exactly as csrc/kvq.h stores them (oracle/kvq.py states the format bit for bit)."""
+    x = x.float()
+    _, e = torch.frexp(x.abs().amax(-1, keepdim=True))       # amax = f 2^e, f in [0.5, 1): 2^e > amax
+    e = e.clamp(-100, 120)
+    one = torch.ones_like(e, dtype=torch.float32)
     lim = 2.0 ** (bits - 1)
-    return torch.clamp(torch.round(x / q), -lim, lim - 1) * q
+    y = torch.clamp(torch.round(x * torch.ldexp(one, bits - 1 - e)), -lim, lim - 1)   # round half to even
+    return y * torch.ldexp(one, e - (bits - 1))
 
 
 @torch.no_grad()
