@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the MolNexTR predict hot path on MI355X (molecules/s at 384x384, batch 32 per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 `--gpus N` with N > 1 and no torchrun environment: bench.py launches itself under `python -m torch.distributed.run
@@ -21,23 +21,29 @@ every batch of 32 stays ONE reference batch (its own positional-encoding numberi
 the decoder at once and finished rows are refilled with the next batch. `--beam 5` times BASELINE config 5 instead
 (beam 5 x batch 32 through mnx_predict_beam: up to 8 reference batches share one step sequence, encoder running ahead).
 
-Rank 0 prints ONE JSON line (contract in the task statement). Beyond the contract it carries
+Rank 0 prints ONE JSON line (contract in the task statement). A plain run sets up, warms up, times the K steps, writes
+--dump-outputs and prints the line: after the timed steps it only reads what was measured during them. Everything that
+takes runs of its own (replays, probes, sub-results, the CPU baseline) runs with `--full` alone, after the timed steps;
+without it those fields are null. Beyond the contract the line carries
   roofline        the dominant FLOP kernel (encoder GEMMs, 16-bit MFMA): ALGORITHMIC FLOP (2*M*N*K per launch) divided by
                   event-bracketed durations measured LIVE on the encoder stream inside the timed region (at most 4 encoder
-                  launch groups are bracketed, whatever --steps is); `isolated` = the same launches replayed afterwards;
+                  launch groups are bracketed, whatever --steps is; null without --full when nothing was bracketed live:
+                  --mode batch, --beam > 1); `isolated` (--full) = the same launches replayed afterwards;
                   peak = 2500 TFLOP/s dense bf16 / fp16 (MI355X_MICROARCH.md). In the split modes the matrix pipe executes
                   2-3 MFMA terms per algorithmic product: `mfma_terms` = their FLOP-weighted average (3 for fp16x3, 2.33 for
-                  fp16x3m) and `frac_of_peak_executed` = mfma_terms x frac.
+                  fp16x3m) and `frac_of_peak_executed` = mfma_terms x frac. The sustained MFMA rate (--full) comes from a
+                  probe run after the timed steps.
                   `stage34` = the same figures for the block Linears of Swin stages 3 and 4 (C >= 512, the MFMA-bound shapes)
-  roofline_extra  HBM-bound kernel classes: LayerNorm / window attention / patch embedding (live, same events) and the
-                  two per-row decode attention kernels (isolated probe at a fixed operating point): algorithmic bytes /
-                  duration against 8 TB/s
-  sub_results     (N = 1 only, after the timed region) latency mode (one batch of 32 at a time), fixed-T=128 decode
+  roofline_extra  HBM-bound kernel classes: LayerNorm / window attention / patch embedding (live, same events; --full adds
+                  their isolated replay) and, with --full, the two per-row decode attention kernels (isolated probe at a
+                  fixed operating point): algorithmic bytes / duration against 8 TB/s
+  sub_results     (--full, N = 1 only, after the timed region) latency mode (one batch of 32 at a time), fixed-T=128 decode
                   (deterministic work), beam 5 x batch 32, the throughput of the opt-in two-term mode fp16x3m and of the plain
                   bf16 operand mode (fastest, not token-exact) next to the default mode's
-  cpu_baseline    the CPU oracle (oracle/, bit-equal to the reference in the build container) on a bounded sample of
-                  the same workload on this box's host cores: thread sweep, B in {1, 32}, encoder /
-                  decoder split, natural and fixed-T=128 decode, median of 3 after a warm-up, 1-thread figure, lscpu model
+  cpu_baseline    (--full, N = 1 only) the CPU oracle (oracle/, bit-equal to the reference in the build container) on a
+                  bounded sample of the same workload on this box's host cores: thread sweep,
+                  B in {1, 32}, encoder / decoder split, natural and fixed-T=128 decode, median of 3 after a warm-up,
+                  1-thread figure, lscpu model
   parity_note     what "SMILES exact-match" can mean here (RDKit is not installable: token SMILES + atom / bond sets).
 
 `--dump-outputs DIR` writes, after the timed steps, what the timed path returned for its LAST step (the last batch of 32
@@ -54,6 +60,7 @@ import statistics
 import subprocess
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -398,7 +405,7 @@ def dump_outputs(dirname, arrays):
         np.save(os.path.join(dirname, name + ".npy"), a)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=512)
@@ -422,13 +429,20 @@ def main():
                          "driver's command; 2173 vs 2172 at 512 steps (1024: 2057)")
     ap.add_argument("--slots", type=int, default=int(os.environ.get("MNX_SLOTS", "3072")),
                     help="sequences resident in the decoder (multiple of 32, <= 4096)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sub", action="store_true", help="skip the sub-results (latency / fixed-T / parity / beam)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what takes runs of its own: the isolated GEMM / kernel replays, the "
+                         "MFMA and decode-attention probes, the sub-results and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-sub", action="store_true", help="with --full: skip the sub-results (latency / fixed-T / parity / beam)")
     ap.add_argument("--force-gather", action="store_true", help="run the RCCL record gather even with one rank")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the outputs of the last timed step (rank 0's last batch of 32) as "
                          "DIR/<name>.npy in float32")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: the product path has no CPU fallback")
@@ -442,6 +456,13 @@ def main():
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
     rank_cpu_set = pin_rank(local, world)         # before the engine starts its helper threads
+    # the checkpoint and the image pool are pure functions of (seed, image index); host threads make them at once (numpy
+    # releases the GIL) while the process group and the engine are set up
+    # step s, rank r owns images [(s*world + r)*32, +32): every step has its own images (8 distinct batches cycle)
+    n_distinct = 8
+    maker = ThreadPoolExecutor(max_workers=1 + n_distinct)
+    ck_job = maker.submit(W.synthetic_checkpoint, 0)
+    pool_jobs = [maker.submit(W.synthetic_images, BATCH, first_index=(s * world + rank) * BATCH) for s in range(n_distinct)]
     use_dist = world > 1 or ("RANK" in os.environ and args.force_gather)
     if use_dist:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -453,13 +474,12 @@ def main():
     from molnextr_amd.engine import Engine
 
     mode = "beam" if args.beam > 1 else args.mode
-    ck = W.synthetic_checkpoint(0)
+    ck = ck_job.result()
     eb = max(BATCH, args.encode_batch)   # images per encoder launch group
     eng = Engine(ck["encoder"], ck["decoder"], device=local, max_batch=eb, dtype=args.dtype, dec_slots=args.slots)
     kmax = eng.max_atoms
-    # step s, rank r owns images [(s*world + r)*32, +32): every step has its own images (8 distinct batches cycle)
-    n_distinct = 8
-    pool = [W.synthetic_images(BATCH, first_index=(s * world + rank) * BATCH).to(dev) for s in range(n_distinct)]
+    pool = [job.result().to(dev) for job in pool_jobs]
+    maker.shutdown()
 
     def images_for(first_step, count):
         return torch.cat([pool[(first_step + i) % n_distinct] for i in range(count)]).contiguous()
@@ -544,17 +564,21 @@ def main():
     if rank == 0:
         # ---- roofline of the dominant FLOP kernel (all encoder GEMM launches). `achieved` is measured LIVE: HIP events
         # around every kernel of <= 4 encoder launch groups spread over the timed region, i.e. next to the decoder; the
-        # same launches replayed afterwards on an otherwise idle GPU are reported as `isolated`.
-        eng.profile(True)
-        for i in range(min(args.steps * BATCH // eb, 4)):
-            eng.encode(imgs[i * eb:(i + 1) * eb].contiguous())
-        iso = eng.profile_read_all()
-        eng.profile(False)
+        # same launches replayed afterwards on an otherwise idle GPU are reported as `isolated` (--full).
+        iso = None
+        if args.full:
+            eng.profile(True)
+            for i in range(min(args.steps * BATCH // eb, 4)):
+                eng.encode(imgs[i * eb:(i + 1) * eb].contiguous())
+            iso = eng.profile_read_all()
+            eng.profile(False)
         split = args.dtype in ("fp16x3", "fp16x3m", "bf16x3")
         two = two_term_layers(FP16X3M_TWO_TERM) if args.dtype == "fp16x3m" else frozenset()
         terms = round(gemm_mfma_terms(split, two), 4)      # FLOP-weighted average over the encoder's Linears
 
         def family(prof, kinds):
+            if not prof:
+                return 0.0, 0, 0
             ms = sum(prof[k][0] for k in kinds)
             fl = sum(prof[k][1] for k in kinds)
             n = sum(prof[k][2] for k in kinds)
@@ -573,7 +597,7 @@ def main():
         traffic, traffic_src = gemm_traffic(args.dtype, eb)
         # what the matrix pipes sustain on THIS device under its power budget (register-only fp16 MFMA loop on random
         # operands, ~30 ms, measured now): the encoder GEMMs are power-limited, the nominal 2.5 PFLOP/s assumes 2.4 GHz
-        sus_tf, sus_mhz = eng.probe_mfma(30)
+        sus_tf, sus_mhz = eng.probe_mfma(30) if args.full else (0.0, 0.0)
         mfma = {"fp16x3": "v_mfma_f32_16x16x32_f16 x 3 terms", "bf16x3": "v_mfma_f32_16x16x32_bf16 x 3 terms",
                 "fp16x3m": f"v_mfma_f32_16x16x32_f16 x 3 terms, x 2 in {'/'.join(FP16X3M_TWO_TERM)}: {terms} on average",
                 "bf16": "v_mfma_f32_16x16x32_bf16", "fp16": "v_mfma_f32_16x16x32_f16", "fp32": "v_mfma_f32_16x16x4_f32"}[args.dtype]
@@ -590,9 +614,11 @@ def main():
                               "peak_at_live_clock": round(PEAK_BF16_TFLOPS * gemm_mhz / 2400.0, 1) if gemm_mhz > 0 else None,
                               "frac_of_peak_at_live_clock_executed": (round(terms * achieved / (PEAK_BF16_TFLOPS * gemm_mhz / 2400.0), 4)
                                                                       if gemm_mhz > 0 else None),
-                              "sustained_mfma_tflops": round(sus_tf, 1), "sustained_mfma_mhz": round(sus_mhz, 0),
+                              "sustained_mfma_tflops": round(sus_tf, 1) if sus_tf > 0 else None,
+                              "sustained_mfma_mhz": round(sus_mhz, 0) if sus_tf > 0 else None,
                               "frac_of_sustained_executed": round(terms * achieved / sus_tf, 4) if sus_tf > 0 else None,
-                              "what": "mnx_gemm_clock / mnx_probe_mfma, both measured in this run (include/molnextr_hip.h)"},
+                              "what": "mnx_gemm_clock over the timed steps, mnx_probe_mfma after them (--full only), measured in this "
+                                      "run (include/molnextr_hip.h)"},
                     "traffic": traffic, "traffic_source": traffic_src,
                     "algorithmic_bytes_per_launch": round(gemm_algorithmic_bytes(eb, 2 if split else 1, two)),
                     "images_per_launch": eb,
@@ -600,14 +626,17 @@ def main():
                     "flop_per_launch_avg": round(gemm_flop / max(launches, 1)),
                     "measured": ("live: HIP events on the encoder stream inside the timed region (<= 4 launch groups)"
                                  if src is live_prof else "replay after the timed region"),
-                    "isolated": {"achieved": round(isolated, 1), "avg_launch_us": round(iso_ms * 1e3 / max(iso_n, 1), 2),
-                                 "launches": int(iso_n)},
+                    "isolated": ({"achieved": round(isolated, 1), "avg_launch_us": round(iso_ms * 1e3 / max(iso_n, 1), 2),
+                                  "launches": int(iso_n)} if iso else None),
                     "stage34": {"what": "block Linears with C >= 512 (Swin-B stages 3 and 4: qkv / proj / fc1 / fc2, the MFMA-bound "
                                         "shapes; north_star's >= 60 % target applies to these)",
                                 "achieved": round(s34, 1), "frac": round(s34 / PEAK_BF16_TFLOPS, 4),
                                 "frac_of_peak_executed": round(terms * s34 / PEAK_BF16_TFLOPS, 4), "launches": int(s_n),
                                 "avg_launch_us": round(s_ms * 1e3 / max(s_n, 1), 2),
-                                "isolated": {"achieved": round(s34_iso, 1), "frac": round(s34_iso / PEAK_BF16_TFLOPS, 4)}}}
+                                "isolated": ({"achieved": round(s34_iso, 1), "frac": round(s34_iso / PEAK_BF16_TFLOPS, 4)}
+                                             if iso else None)}}
+        if src is None:           # nothing bracketed live (--mode batch, --beam > 1) and no replay without --full
+            roofline = None
         extra = []
         for kind, label in (("layernorm", "mnx::layernorm16_kernel (fp32 in, 16-bit operand planes out)"),
                             ("window_attn", "mnx::window_attn_kernel (qkv in, context out)"),
@@ -620,18 +649,19 @@ def main():
                 extra.append({"kernel": label, "bound": "hbm", "measured": tag, "achieved": round(gbs, 1), "peak": PEAK_HBM_GBS,
                               "unit": "GB/s", "frac": round(gbs / PEAK_HBM_GBS, 4), "launches": int(n),
                               "avg_launch_us": round(ms * 1e3 / n, 2), "algorithmic_bytes_per_launch": round(byts / n)})
-        rows_p, t_p = min(768, args.slots), 64
-        self_ms, cross_ms = eng.probe_decode_attn(rows_p, t_p, 24)   # 4 cycles over the 6 layers' K/V: HBM, not Infinity Cache
-        # a cached K / V row of 32 channels is 100 bytes (24-bit block fixed point: int16 hi + uint8 lo per element + one scale, csrc/kvq.h)
-        for label, ms, byts in (("mnx::dec_attn_kernel, self-attention (K/V cache of the sequence, 3 bytes per element + a scale per row)", self_ms, rows_p * 8 * (t_p + 1) * 200),
-                                ("mnx::dec_attn_kernel, cross-attention (projected memory K/V, 144 keys, 3 bytes per element + a scale per row)", cross_ms, rows_p * 8 * 144 * 200)):
-            gbs = byts / (ms * 1e-3) / 1e9
-            extra.append({"kernel": label, "bound": "hbm", "measured": f"isolated probe: {rows_p} rows at position {t_p}, launches cycle the 6 layers' K/V (> 256 MB per cycle)",
-                          "achieved": round(gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(gbs / PEAK_HBM_GBS, 4),
-                          "avg_launch_us": round(ms * 1e3, 2), "algorithmic_bytes_per_launch": int(byts)})
+        if args.full:
+            rows_p, t_p = min(768, args.slots), 64
+            self_ms, cross_ms = eng.probe_decode_attn(rows_p, t_p, 24)   # 4 cycles over the 6 layers' K/V: HBM, not Infinity Cache
+            # a cached K / V row of 32 channels is 100 bytes (24-bit block fixed point: int16 hi + uint8 lo per element + one scale, csrc/kvq.h)
+            for label, ms, byts in (("mnx::dec_attn_kernel, self-attention (K/V cache of the sequence, 3 bytes per element + a scale per row)", self_ms, rows_p * 8 * (t_p + 1) * 200),
+                                    ("mnx::dec_attn_kernel, cross-attention (projected memory K/V, 144 keys, 3 bytes per element + a scale per row)", cross_ms, rows_p * 8 * 144 * 200)):
+                gbs = byts / (ms * 1e-3) / 1e9
+                extra.append({"kernel": label, "bound": "hbm", "measured": f"isolated probe: {rows_p} rows at position {t_p}, launches cycle the 6 layers' K/V (> 256 MB per cycle)",
+                              "achieved": round(gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(gbs / PEAK_HBM_GBS, 4),
+                              "avg_launch_us": round(ms * 1e3, 2), "algorithmic_bytes_per_launch": int(byts)})
 
         sub = None
-        if world == 1 and not args.no_sub:
+        if args.full and world == 1 and not args.no_sub:
             sub = {}
             nb = 3
             x = images_for(0, nb)
@@ -689,7 +719,7 @@ def main():
                                                        "mode, NOT token-exact vs the reference (argmax near-ties flip: tests/test_gpu_pixels.py, "
                                                        "profiles/r04_pixels_parity.json)",
                                                "molecules_per_s": round(ns * BATCH / t, 1)}
-        cpu = None if (args.no_cpu_baseline or world > 1) else cpu_baseline(ck)   # host baseline: rank 0 at N=1 only
+        cpu = cpu_baseline(ck) if (args.full and not args.no_cpu_baseline and world == 1) else None   # rank 0 at N=1 only
         total = args.steps * BATCH * world
         if mode == "beam":
             workload = (f"BASELINE config 5: beam {args.beam} x batch 32 synthetic 384x384x3 images per GPU through mnx_predict_beam "

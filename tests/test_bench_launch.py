@@ -56,6 +56,14 @@ def test_spawn_command_is_one_rank_per_gpu_on_loopback(monkeypatch):
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_plain_run_leaves_what_takes_runs_of_its_own_to_full():
+    """`bench.py --gpus 1 --steps N --warmup W` does only what its headline figure needs; the isolated replays, probes,
+    sub-results and CPU baseline run with --full alone, which is off by default."""
+    args = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert (args.gpus, args.steps, args.warmup, args.full, args.dump_outputs) == (1, 20, 5, False, None)
+    assert bench.parse_args(["--full"]).full is True
+
+
 def test_bench_without_gpu_fails_loudly():
     import torch
     if torch.cuda.is_available():
