@@ -248,9 +248,11 @@ int mnx_atom_scan(mnx_engine* h, const int32_t* tokens, const int32_t* lengths, 
  * `molnextr.predict_images` (MolNexTR/model.py:102-109: encoder + decoder.decode for every chunk) up to, but not
  * including, the host-side detokenisation to symbols / coordinates.
  *   images    device fp32 [n_img,3,S,S]
- *   ref_batch images are decoded as consecutive reference batches of this many rows (<= 32): every batch is one
- *             positional-encoding numbering, exactly as if the reference had been called with this batch_size
- * Up to cfg.dec_slots sequences (dec_slots / 32 reference batches; 2048 by default) are resident on the GPU at once;
+ *   ref_batch images are decoded as consecutive reference batches of this many rows, 1 <= ref_batch <=
+ *             min(512, cfg.max_batch, cfg.dec_slots, cfg.pe_len) (MNX_ERR_CAPACITY otherwise; mnx_last_error names the
+ *             bound): every batch is one positional-encoding numbering, exactly as if the reference had been called with
+ *             this batch_size. A batch holds ceil(ref_batch / 32) tiles of 32 rows for as long as its longest row runs.
+ * Up to cfg.dec_slots sequences (dec_slots / 32 row tiles; 2048 by default) are resident on the GPU at once;
  * every decode tick advances all of them by one token, finished batches are retired (atom positions + bond head run on device) and the freed rows are
  * refilled with the next batch while the encoder of the following batch runs on a second stream.
  *   stop_on_eos 1 = reference behaviour; 0 = every sequence runs to max_len (bench aid: deterministic decode work)
@@ -263,7 +265,7 @@ int mnx_predict(mnx_engine* h, const float* images, int32_t n_img, int32_t ref_b
 
 /* mnx_predict with the confidences of `Decoder.decode(compute_confidence=True)` (MolNexTR/components.py:456-469 atom
  * scores, :485-491 edge scores and overall score; decoding/greedy_search.py:109-110 token scores): the same inputs and
- * outputs with stop_on_eos = 1, and per image, all in the same continuous-batching pipeline (they are computed on the
+ * outputs (ref_batch up to 512 as there) with stop_on_eos = 1, and per image, all in the same continuous-batching pipeline (they are computed on the
  * device when a reference batch retires):
  *   token_logp    device fp32 [n_img,max_len] or NULL: masked log-prob of every emitted id, EOS included (0 beyond lengths)
  *   edge_scores   device fp64 [n_img,kmax,kmax]: probability of the chosen bond class, float64-averaged as in

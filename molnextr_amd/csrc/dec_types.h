@@ -7,9 +7,11 @@ namespace mnx {
 
 constexpr int MAX_SLOTS = 4096;    // capacity of the sequence-state arrays (cfg.dec_slots <= this; default 2048 in use)
 constexpr int BEGIN_THREADS = 1024;
-constexpr int ROW_TILE = 32;       // rows per workgroup of the skinny linears; also the max reference batch
+constexpr int ROW_TILE = 32;       // rows per workgroup of the skinny linears; slots are handed out in tiles of this many
 constexpr int MAX_DEC_LAYERS = 8;
-constexpr int MAX_CHUNKS = 128;    // reference batches in flight (slots of one batch may be scattered)
+constexpr int MAX_CHUNKS = 128;    // reference batches in flight (slots of one batch may be scattered); MAX_SLOTS / ROW_TILE
+constexpr int MAX_REF_BATCH = 512; // rows of one reference batch on the greedy predict path (mnx_predict*)
+constexpr int CHUNK_TILES = MAX_REF_BATCH / ROW_TILE;   // 32-row alive masks per chunk in dec_begin_kernel
 
 // Decode state of every slot; lives in device memory and is advanced by the tick graph itself.
 // A "slot" is one sequence being decoded. Slots of one reference batch ("chunk") share a positional-encoding
@@ -24,7 +26,7 @@ struct DecState {
     int prev_tok[MAX_SLOTS];
     int len[MAX_SLOTS];
     int chunk[MAX_SLOTS];          // chunk tag 0..MAX_CHUNKS-1
-    int rowc[MAX_SLOTS];           // row index inside the reference batch
+    int rowc[MAX_SLOTS];           // row index inside the reference batch, 0..MAX_REF_BATCH-1
     int rank[MAX_SLOTS];           // PE row for the current tick
     int mem_blk[MAX_SLOTS];        // which 144-row block of mem_kv holds this slot's cross-attention K/V
     int max_len[MAX_SLOTS];

@@ -706,12 +706,15 @@ __global__ __launch_bounds__(1024) void dec_head4_kernel(HeadArgs a) {
 
 // Opens a tick: PE rank of every slot (rank among the alive slots of its chunk, by row index) and the alive
 // counters the host polls. One workgroup; the kernel boundary is the all-rows barrier.
+// A chunk (reference batch) of up to MAX_REF_BATCH rows keeps one 32-bit alive mask per 32 rows: row rowc sits in mask
+// rowc >> 5 of its chunk at bit rowc & 31, and its rank is the popcount of the masks below it plus the bits below it
+// in its own. A chunk of <= 32 rows only ever touches its first mask: ranks and counters are those of one 32-bit mask.
 __global__ __launch_bounds__(BEGIN_THREADS) void dec_begin_kernel(DecState* st, int slots) {
-    __shared__ unsigned int s_mask[MAX_CHUNKS];     // bit r = row r of the chunk is alive (rows per chunk <= 32)
+    __shared__ unsigned int s_mask[MAX_CHUNKS * CHUNK_TILES];     // [chunk tag][32-row tile of the chunk]: bit = row alive
     __shared__ int s_wave[BEGIN_THREADS / 64];
     __shared__ int s_base;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid < MAX_CHUNKS) s_mask[tid] = 0u;
+    for (int i = tid; i < MAX_CHUNKS * CHUNK_TILES; i += BEGIN_THREADS) s_mask[i] = 0u;
     if (tid == 0) s_base = 0;
     __syncthreads();
     // pass 1: per-chunk alive bitmaps + compact list of alive slots in slot order
@@ -720,7 +723,10 @@ __global__ __launch_bounds__(BEGIN_THREADS) void dec_begin_kernel(DecState* st, 
         const int al = s < slots ? st->alive[s] : 0;
         const unsigned long long bal = __ballot(al != 0);
         if (lane == 0) s_wave[wave] = __popcll(bal);
-        if (al) atomicOr(&s_mask[st->chunk[s] & (MAX_CHUNKS - 1)], 1u << (st->rowc[s] & 31));
+        if (al) {
+            const int c = st->chunk[s] & (MAX_CHUNKS - 1), rc = st->rowc[s] & (MAX_REF_BATCH - 1);
+            atomicOr(&s_mask[c * CHUNK_TILES + (rc >> 5)], 1u << (rc & 31));
+        }
         __syncthreads();
         int base = s_base, total = 0;
         for (int w = 0; w < BEGIN_THREADS / 64; ++w) {
@@ -736,10 +742,17 @@ __global__ __launch_bounds__(BEGIN_THREADS) void dec_begin_kernel(DecState* st, 
     // pass 2: PE rank of every alive slot = alive chunk-mates with a smaller row index
     for (int s = tid; s < slots; s += BEGIN_THREADS)
         if (st->alive[s]) {
-            const int c = st->chunk[s] & (MAX_CHUNKS - 1), rc = st->rowc[s] & 31;
-            st->rank[s] = __popc(s_mask[c] & ((1u << rc) - 1u));
+            const int c = st->chunk[s] & (MAX_CHUNKS - 1), rc = st->rowc[s] & (MAX_REF_BATCH - 1);
+            const unsigned int* m = s_mask + c * CHUNK_TILES;
+            int r = __popc(m[rc >> 5] & ((1u << (rc & 31)) - 1u));
+            for (int j = 0; j < (rc >> 5); ++j) r += __popc(m[j]);
+            st->rank[s] = r;
         }
-    if (tid < MAX_CHUNKS) st->chunk_alive[tid] = __popc(s_mask[tid]);
+    if (tid < MAX_CHUNKS) {
+        int n = 0;
+        for (int j = 0; j < CHUNK_TILES; ++j) n += __popc(s_mask[tid * CHUNK_TILES + j]);
+        st->chunk_alive[tid] = n;
+    }
     if (tid == 0) { st->n_active = s_base; st->tick = st->tick + 1; }
     // row view (dec_types.h): active[] and rank[] above were written by other threads of this workgroup
     __syncthreads();

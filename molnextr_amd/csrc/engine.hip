@@ -97,7 +97,8 @@ struct mnx_engine {
     hipEvent_t ev_order = nullptr;
     float* feat_ring[2] = {nullptr, nullptr};
     hipEvent_t ev_enc_done[2] = {nullptr, nullptr}, ev_feat_free[2] = {nullptr, nullptr}, ev_poll[2] = {nullptr, nullptr};
-    int* slot_lists = nullptr;          // device [MAX_CHUNKS][32]
+    int* slot_lists = nullptr;          // device [MAX_CHUNKS][32]: slot list of every 32-slot row tile
+    int* rowc_seq = nullptr;            // device [MAX_REF_BATCH]: 0, 1, 2, ... (row indices of a chunk's tiles at admission)
     TokenClasses* tc_dev = nullptr;
     bool have_tc = false;
     int n_chunk_bufs = 0;
@@ -601,7 +602,7 @@ int mnx_create(const mnx_config* cfg, const mnx_weight_desc* weights, int32_t n_
     if (h->enc_flag && hipMemset(h->enc_flag, 0, sizeof(int)) != hipSuccess) P.problems.push_back("hipMemset failed");
     DecBuffers& db = h->db;
     const int SL = c.dec_slots > 0 ? c.dec_slots : 2048;
-    h->n_chunk_bufs = SL / ROW_TILE;   // one reference batch per 32-slot row tile
+    h->n_chunk_bufs = SL / ROW_TILE;   // 32-slot row tiles; a reference batch of n rows holds ceil(n / 32) of them
     db.T = c.max_len; db.S = (int)S; db.slots = SL; db.mem_blocks = h->n_chunk_bufs * ROW_TILE; db.kmax = c.max_atoms;
     db.st = (DecState*)P.dalloc(sizeof(DecState));
     db.x = (float*)P.dalloc((size_t)SL * D * 4);
@@ -643,6 +644,13 @@ int mnx_create(const mnx_config* cfg, const mnx_weight_desc* weights, int32_t n_
     h->feat_ring[0] = (float*)P.dalloc(ring_rows * S * CF * 4);
     h->feat_ring[1] = (float*)P.dalloc(ring_rows * S * CF * 4);
     h->slot_lists = (int*)P.dalloc((size_t)MAX_CHUNKS * ROW_TILE * 4);
+    h->rowc_seq = (int*)P.dalloc((size_t)MAX_REF_BATCH * 4);
+    if (h->rowc_seq) {
+        std::vector<int> seq_rows(MAX_REF_BATCH);
+        for (int i = 0; i < MAX_REF_BATCH; ++i) seq_rows[i] = i;
+        if (hipMemcpy(h->rowc_seq, seq_rows.data(), (size_t)MAX_REF_BATCH * 4, hipMemcpyHostToDevice) != hipSuccess)
+            P.problems.push_back("row index table upload failed");
+    }
     h->tc_dev = (TokenClasses*)P.dalloc(sizeof(TokenClasses));
     h->prep_bbox = (int*)P.dalloc(4 * sizeof(int));   // at create: mnx_preprocess may run beside another entry point
     {
@@ -1289,9 +1297,20 @@ static int predict_impl(mnx_engine* h, const char* name, const float* images, in
     }
     if (!h->have_tc) { h->err = std::string(name) + ": call mnx_set_token_classes first"; return MNX_ERR_INVALID_ARG; }
     const mnx_config& c = h->cfg;
-    if (ref_batch < 1 || ref_batch > ROW_TILE || ref_batch > c.max_batch || max_len < 1 || max_len > c.max_len ||
-        kmax < 1 || kmax > h->db.kmax) {
-        h->err = std::string(name) + ": ref_batch <= min(32, max_batch), max_len <= cfg.max_len, kmax <= cfg.max_atoms required";
+    const int SL = h->db.slots;
+    {   // a reference batch is decoded as ONE chunk (its PE numbering spans all of its rows): it must fit every bound at once
+        const char* hit = ref_batch > MAX_REF_BATCH ? "MAX_REF_BATCH" : ref_batch > c.max_batch ? "cfg.max_batch"
+                        : ref_batch > SL ? "cfg.dec_slots" : ref_batch > c.pe_len ? "cfg.pe_len" : nullptr;
+        const int lim = ref_batch > MAX_REF_BATCH ? MAX_REF_BATCH : ref_batch > c.max_batch ? c.max_batch
+                      : ref_batch > SL ? SL : c.pe_len;
+        if (hit) {
+            h->err = std::string(name) + ": ref_batch " + std::to_string(ref_batch) + " exceeds " + hit + " = " +
+                     std::to_string(lim);
+            return MNX_ERR_CAPACITY;
+        }
+    }
+    if (ref_batch < 1 || max_len < 1 || max_len > c.max_len || kmax < 1 || kmax > h->db.kmax) {
+        h->err = std::string(name) + ": 1 <= ref_batch, max_len <= cfg.max_len, kmax <= cfg.max_atoms required";
         return MNX_ERR_CAPACITY;
     }
     hipStream_t s = (hipStream_t)stream;
@@ -1300,14 +1319,17 @@ static int predict_impl(mnx_engine* h, const char* name, const float* images, in
         if (!h->own_stream) HIPCHK(h, hipStreamCreate(&h->own_stream));
         s = h->own_stream;
     }
-    const int S = h->db.S, D = c.dec_dim, SL = h->db.slots;
+    const int S = h->db.S, D = c.dec_dim;
     const size_t img_elems = (size_t)3 * c.img_size * c.img_size;
     const int n_chunks = (n_img + ref_batch - 1) / ref_batch;
-    struct Chunk { int first, n, tag, admit_seq; std::vector<int> slots; };
+    // A chunk (one reference batch) holds ceil(n / 32) row tiles, not necessarily contiguous; tile j holds its rows
+    // 32 j .. 32 j + 31 in slots tile * 32 + i, memory K/V blocks likewise, and its slot list at slot_lists[tile]. The chunk's
+    // tag (the PE numbering unit of dec_begin_kernel, the index of its alive counter) is its first tile: tags < MAX_CHUNKS.
+    struct Chunk { int first, n, tag, admit_seq; std::vector<int> tiles; };
     std::vector<Chunk> live;
-    std::vector<int> free_tags;      // a chunk tag is also its 32-slot row tile and its memory K/V block
-    for (int i = h->n_chunk_bufs - 1; i >= 0; --i) free_tags.push_back(i);
-    int* pinned = h->host_flag;                       // [2][1 + MAX_CHUNKS] snapshots, then slot lists
+    std::vector<int> free_tiles;
+    for (int i = h->n_chunk_bufs - 1; i >= 0; --i) free_tiles.push_back(i);
+    int* pinned = h->host_flag;                       // [2][1 + MAX_CHUNKS] snapshots, then slot lists per tile
     int* pin_slots = h->host_flag + 2 * (1 + MAX_CHUNKS);
     int rc = MNX_OK;
     int bound = 0;                                    // upper bound of alive rows (host-side, conservative)
@@ -1356,37 +1378,48 @@ static int predict_impl(mnx_engine* h, const char* name, const float* images, in
         }
         // ---- admission (in image order): only once the chunk's features are READY, so the decode stream never
         //      waits for the encoder; project the memory and admit on the decode stream
-        while (next < n_chunks && !free_tags.empty()) {
+        while (next < n_chunks) {
             int fb = -1;
             for (int i = 0; i < 2; ++i)
                 if (fb_first[i] >= 0 && next >= fb_first[i] && next < fb_first[i] + fb_count[i]) fb = i;
             if (fb < 0) break;
             const int first = next * ref_batch, n = std::min(ref_batch, n_img - first);
+            const int n_tiles = (n + ROW_TILE - 1) / ROW_TILE;
+            if ((int)free_tiles.size() < n_tiles) break;   // every row of a batch starts at step 0 together: wait for all tiles
             // nothing to decode: wait for the features instead of polling
             const bool idle = live.empty();
             hipError_t q = idle ? hipEventSynchronize(h->ev_enc_done[fb]) : hipEventQuery(h->ev_enc_done[fb]);
             if (q == hipErrorNotReady) break;
             if (q != hipSuccess) { h->err = std::string("encoder event: ") + hipGetErrorString(q); return MNX_ERR_HIP; }
             Chunk ck;
-            ck.first = first; ck.n = n; ck.tag = free_tags.back(); ck.admit_seq = seq;
-            free_tags.pop_back();
-            for (int i = 0; i < n; ++i) ck.slots.push_back(ck.tag * ROW_TILE + i);
+            ck.first = first; ck.n = n; ck.admit_seq = seq;
+            for (int j = 0; j < n_tiles; ++j) { ck.tiles.push_back(free_tiles.back()); free_tiles.pop_back(); }
+            ck.tag = ck.tiles[0];
             HIPCHK(h, hipStreamWaitEvent(s, h->ev_enc_done[fb], 0));   // already complete: ordering only
-            char* memkv = h->db.mem_kv + (size_t)ck.tag * ROW_TILE * c.dec_layers * 2 * c.dec_heads * kvq_block_bytes(h->db.Sq);
-            const float* feats = h->feat_ring[fb] + (size_t)(next - fb_first[fb]) * ref_batch * S * h->dw.enc_dim;
-            HIPCHK(h, launch_sgemm_tn(feats, h->dw.w_enc, h->dw.b_enc, h->db.memory, n * S, D, h->dw.enc_dim, s));
-            HIPCHK(h, launch_sgemm_tn(h->db.memory, h->dw.w_memkv, h->dw.b_memkv, h->db.mem_kv32, n * S, c.dec_layers * 2 * D, D, s, S));
-            HIPCHK(h, kvq_pack_enqueue(h->db.mem_kv32, memkv, n * c.dec_layers * 2 * c.dec_heads, S, h->db.Sq, s));
+            // memory projection tile by tile: the fp32 scratch (db.memory, db.mem_kv32) holds 32 rows
+            for (int j = 0; j < n_tiles; ++j) {
+                const int tile = ck.tiles[j], nj = std::min(ROW_TILE, n - j * ROW_TILE);
+                char* memkv = h->db.mem_kv + (size_t)tile * ROW_TILE * c.dec_layers * 2 * c.dec_heads * kvq_block_bytes(h->db.Sq);
+                const float* feats = h->feat_ring[fb] + ((size_t)(next - fb_first[fb]) * ref_batch + (size_t)j * ROW_TILE) * S * h->dw.enc_dim;
+                HIPCHK(h, launch_sgemm_tn(feats, h->dw.w_enc, h->dw.b_enc, h->db.memory, nj * S, D, h->dw.enc_dim, s));
+                HIPCHK(h, launch_sgemm_tn(h->db.memory, h->dw.w_memkv, h->dw.b_memkv, h->db.mem_kv32, nj * S, c.dec_layers * 2 * D, D, s, S));
+                HIPCHK(h, kvq_pack_enqueue(h->db.mem_kv32, memkv, nj * c.dec_layers * 2 * c.dec_heads, S, h->db.Sq, s));
+            }
             if (next + 1 == fb_first[fb] + fb_count[fb]) {    // last reference batch of the group: buffer is free again
                 HIPCHK(h, hipEventRecord(h->ev_feat_free[fb], s));
                 feat_used[fb] = true;
                 fb_first[fb] = -1;
             }
-            int* sl_dev = h->slot_lists + (size_t)ck.tag * ROW_TILE;
-            int* sl_pin = pin_slots + (size_t)ck.tag * ROW_TILE;     // pinned, private to this tag until it retires
-            for (int i = 0; i < n; ++i) sl_pin[i] = ck.slots[i];
-            HIPCHK(h, hipMemcpyAsync(sl_dev, sl_pin, (size_t)n * 4, hipMemcpyHostToDevice, s));
-            HIPCHK(h, dec_enqueue_admit(h->db, sl_dev, nullptr, n, ck.tag, ck.tag * ROW_TILE, max_len, stop_on_eos ? 1 : 0, s));
+            // every tile of the chunk is admitted before the next tick, rows 32 j + i under the chunk's one tag
+            for (int j = 0; j < n_tiles; ++j) {
+                const int tile = ck.tiles[j], nj = std::min(ROW_TILE, n - j * ROW_TILE);
+                int* sl_dev = h->slot_lists + (size_t)tile * ROW_TILE;
+                int* sl_pin = pin_slots + (size_t)tile * ROW_TILE;     // pinned, private to this tile until its chunk retires
+                for (int i = 0; i < nj; ++i) sl_pin[i] = tile * ROW_TILE + i;
+                HIPCHK(h, hipMemcpyAsync(sl_dev, sl_pin, (size_t)nj * 4, hipMemcpyHostToDevice, s));
+                HIPCHK(h, dec_enqueue_admit(h->db, sl_dev, h->rowc_seq + j * ROW_TILE, nj, ck.tag, tile * ROW_TILE, max_len,
+                                            stop_on_eos ? 1 : 0, s));
+            }
             bound += n;
             admits.emplace_back(seq, n);
             live.push_back(std::move(ck));
@@ -1398,12 +1431,13 @@ static int predict_impl(mnx_engine* h, const char* name, const float* images, in
         // (one graph per capacity, captured on first use: multiples of 64 up to 1024 rows, of 128 up to 2048, of 256 beyond)
         const int cap_step = bound <= 1024 ? 64 : bound <= 2048 ? 128 : 256;
         const int rows_cap = std::min(SL, (std::max(bound, 1) + cap_step - 1) / cap_step * cap_step);
-        // the begin kernel scans slot tiles 0 .. highest live tag only (tags are handed out lowest-first): a 20-batch job
+        // the begin kernel scans slot tiles 0 .. highest live tile only (tiles are handed out lowest-first): a 20-batch job
         // keeps it to 1024 of the 3072 slots — one pass of its 1024 threads instead of three; steps of 1024 keep the number of
         // tick graphs (one per scan range and capacity) small
-        int hi_tag = 0;
-        for (const Chunk& ck : live) hi_tag = std::max(hi_tag, ck.tag);
-        const int scan = std::min(SL, std::max(((hi_tag + 1) * ROW_TILE + 1023) / 1024 * 1024, rows_cap));
+        int hi_tile = 0;
+        for (const Chunk& ck : live)
+            for (int t : ck.tiles) hi_tile = std::max(hi_tile, t);
+        const int scan = std::min(SL, std::max(((hi_tile + 1) * ROW_TILE + 1023) / 1024 * 1024, rows_cap));
         hipGraphExec_t exec = nullptr;
         rc = get_tick_graph(h, scan, rows_cap, nullptr, 0, s, &exec);
         if (rc != MNX_OK) return rc;
@@ -1429,20 +1463,25 @@ static int predict_impl(mnx_engine* h, const char* name, const float* images, in
             for (size_t i = 0; i < live.size();) {
                 Chunk& ck = live[i];
                 if (ck.admit_seq <= ps && sn[1 + ck.tag] == 0) {
-                    int* sl_dev = h->slot_lists + (size_t)ck.tag * ROW_TILE;
-                    int* o_idx = atom_idx + (size_t)ck.first * kmax;
-                    int* o_na = n_atoms + ck.first;
-                    float* o_logp = conf && conf->token_logp ? conf->token_logp + (size_t)ck.first * max_len : nullptr;
-                    double* o_scores = conf ? conf->edge_scores + (size_t)ck.first * kmax * kmax : nullptr;
-                    HIPCHK(h, gather_enqueue(h->db, sl_dev, ck.n, max_len, tokens + (size_t)ck.first * max_len,
-                                             lengths + ck.first, o_logp, nullptr, s));
-                    HIPCHK(h, atoms_enqueue(h->db, h->tc_dev, sl_dev, ck.n, kmax, o_idx, o_na, s));
-                    HIPCHK(h, edges_enqueue(h->dw, h->db, h->db.hidden, sl_dev, o_idx, o_na, ck.n, kmax, h->db.T,
-                                            edges + (size_t)ck.first * kmax * kmax, o_scores, s));
-                    if (conf)
-                        HIPCHK(h, confidence_enqueue(h->db, h->tc_dev, sl_dev, ck.n, kmax, o_idx, o_na, o_scores,
-                                                     conf->atom_scores + (size_t)ck.first * kmax, conf->overall + ck.first, s));
-                    free_tags.push_back(ck.tag);
+                    // outputs tile by tile (the bond head's scratch holds 32 rows): rows 32 j .. of the chunk
+                    for (int j = 0; j < (int)ck.tiles.size(); ++j) {
+                        const int o = ck.first + j * ROW_TILE, nj = std::min(ROW_TILE, ck.n - j * ROW_TILE);
+                        int* sl_dev = h->slot_lists + (size_t)ck.tiles[j] * ROW_TILE;
+                        int* o_idx = atom_idx + (size_t)o * kmax;
+                        int* o_na = n_atoms + o;
+                        float* o_logp = conf && conf->token_logp ? conf->token_logp + (size_t)o * max_len : nullptr;
+                        double* o_scores = conf ? conf->edge_scores + (size_t)o * kmax * kmax : nullptr;
+                        HIPCHK(h, gather_enqueue(h->db, sl_dev, nj, max_len, tokens + (size_t)o * max_len, lengths + o, o_logp,
+                                                 nullptr, s));
+                        HIPCHK(h, atoms_enqueue(h->db, h->tc_dev, sl_dev, nj, kmax, o_idx, o_na, s));
+                        HIPCHK(h, edges_enqueue(h->dw, h->db, h->db.hidden, sl_dev, o_idx, o_na, nj, kmax, h->db.T,
+                                                edges + (size_t)o * kmax * kmax, o_scores, s));
+                        if (conf)
+                            HIPCHK(h, confidence_enqueue(h->db, h->tc_dev, sl_dev, nj, kmax, o_idx, o_na, o_scores,
+                                                         conf->atom_scores + (size_t)o * kmax, conf->overall + o, s));
+                    }
+                    for (int t : ck.tiles) free_tiles.push_back(t);   // handed out again last-first: tiles of a chunk need
+                                                                      // be neither contiguous nor ascending
                     live.erase(live.begin() + i);
                     ++done;
                 } else {
@@ -1451,7 +1490,7 @@ static int predict_impl(mnx_engine* h, const char* name, const float* images, in
             }
         }
         if (tf) fprintf(tf, "%.3f seq %d live %zu next %d next_enc %d done %d free_tiles %zu\n", now_ms() - t_begin, seq,
-                        live.size(), next, next_enc, done, free_tags.size());
+                        live.size(), next, next_enc, done, free_tiles.size());
         ++seq;
         if (seq > 200000) { h->err = std::string(name) + ": watchdog (decode did not terminate)"; return MNX_ERR_HIP; }
     }

@@ -167,7 +167,8 @@ def _stream():
 class Engine:
     """One engine per GPU. Holds the packed weights and all workspace for `max_batch` images."""
 
-    ROWS_PER_DECODE = 32
+    ROWS_PER_DECODE = 32      # rows per call of decode_greedy / decode_forced / decode_beam, and per reference batch of beam search
+    MAX_REF_BATCH = 512       # rows per reference batch of greedy `predict` (include/molnextr_hip.h mnx_predict)
 
     def __init__(self, encoder_state: Dict[str, torch.Tensor], decoder_state: Dict[str, torch.Tensor],
                  device: int = 0, max_batch: int = 32, enc: W.EncoderDims = W.SWIN_B, dec: W.DecoderDims = W.DEC,
@@ -185,6 +186,7 @@ class Engine:
                 raise ValueError(f"{k} differs from the (dy+11)*23+(dx+11) formula the kernels implement")
         self.enc, self.dec, self.device = enc, dec, device
         self.max_batch, self.max_len, self.max_atoms = max_batch, max_len, max_atoms
+        self.dec_slots = dec_slots or 2048
         cfg = MnxConfig()
         cfg.img_size, cfg.patch, cfg.embed_dim, cfg.n_stages = enc.img_size, enc.patch, enc.embed_dim, len(enc.depths)
         for i, (d, h) in enumerate(zip(enc.depths, enc.heads)):
@@ -413,11 +415,19 @@ class Engine:
         return edges, scores
 
     # -- whole path, continuous batching ----------------------------------------------------------
+    @property
+    def max_ref_batch(self) -> int:
+        """The largest `ref_batch` greedy `predict` accepts on this engine: min(MAX_REF_BATCH, max_batch, dec_slots)."""
+        return min(self.MAX_REF_BATCH, self.max_batch, self.dec_slots, self.dec.pe_len)
+
     def predict(self, images: torch.Tensor, ref_batch: int = 32, max_len: Optional[int] = None,
                 stop_on_eos: bool = True, beam: int = 1, confidence: bool = False) -> dict:
         """Encoder + decode + atom positions + bond head for all images: greedy with continuous batching (mnx_predict),
         or beam search reference batch by reference batch with the encoder running ahead (mnx_predict_beam; adds
-        'scores', the average log-prob of the returned hypothesis). confidence=True (greedy, stop_on_eos only):
+        'scores', the average log-prob of the returned hypothesis). Images are decoded as consecutive reference batches of
+        `ref_batch` rows, each numbered as one batch of the reference (its positional-encoding row quirk): greedy takes
+        1 <= ref_batch <= max_ref_batch (up to MAX_REF_BATCH = 512 rows), beam search up to ROWS_PER_DECODE = 32; beyond
+        that MnxError (MNX_ERR_CAPACITY) names the bound. confidence=True (greedy, stop_on_eos only):
         mnx_predict_confidence, which adds 'token_logp' [n,max_len] fp32, 'edge_scores' [n,kmax,kmax], 'atom_scores'
         [n,kmax] and 'overall_score' [n] fp64."""
         assert images.is_cuda and images.dtype == torch.float32 and images.is_contiguous()

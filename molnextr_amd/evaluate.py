@@ -82,6 +82,9 @@ class RangeFallback(RuntimeError):
     rebuilds its engine in the fallback mode (engine.RANGE_FALLBACK) and repeats the whole evaluation."""
 
 
+MAX_BATCH_SIZE = 256      # --batch_size: per-rank reference batches of 2 x 256 = 512 rows (Engine.MAX_REF_BATCH)
+
+
 def run_inference(engine, load_image: Callable[[int], np.ndarray], n_items: int, batch_size: int, rank: int = 0,
                   world: int = 1, tokenizer=None, group: int = 512, pad_to_square: bool = False) -> Dict[int, dict]:
     """valid_fn for this rank's shard, then the gather: returns {dataset index: prediction dict} on every rank
@@ -89,9 +92,10 @@ def run_inference(engine, load_image: Callable[[int], np.ndarray], n_items: int,
     pad_to_square: the PadToSquare step `get_transforms` inserts for the test files in PAD_TO_SQUARE_FILES."""
     tok = (tokenizer or get_tokenizer())["chartok_coords"]
     ref_batch = batch_size * 2
-    if ref_batch > engine.ROWS_PER_DECODE:
+    cap = getattr(engine, "MAX_REF_BATCH", engine.ROWS_PER_DECODE)     # rows of one reference batch on the greedy path
+    if ref_batch > cap:
         raise ValueError(f"per-rank batches of {ref_batch} exceed the engine's reference-batch capacity "
-                         f"({engine.ROWS_PER_DECODE}); use --batch_size <= {engine.ROWS_PER_DECODE // 2}")
+                         f"({cap}); use --batch_size <= {cap // 2}")
     mine = sampler_indices(n_items, rank, world)
     kmax = engine.max_atoms
     recs = []
@@ -202,7 +206,8 @@ def main(argv=None):
     ap.add_argument("--save_path", default="predict_output")
     ap.add_argument("--load_path", required=True,
                     help="checkpoint: reference .pth or .safetensors; 'synthetic' = deterministic test weights")
-    ap.add_argument("--batch_size", type=int, default=4, help="per-GPU batch size; inference uses twice that")
+    ap.add_argument("--batch_size", type=int, default=4,
+                    help=f"per-GPU batch size, 1..{MAX_BATCH_SIZE} (main.py's default 256); inference uses twice that")
     ap.add_argument("--dtype", default=None, choices=sorted(DTYPES),
                     help="encoder operand mode; default engine.DEFAULT_DTYPE = fp16x3 (every token / atom / bond as the reference's fp32 path; "
                          "fp16x3m = qkv / fc1 / fc2 of Swin stage 3 on two product terms: faster, tokens exact on everything measured, raw logits up to "
@@ -212,7 +217,10 @@ def main(argv=None):
                          "fp16 operand mode, which stays closer to the fp32 result than the reference's autocast path does "
                          "(tests/test_gpu_pixels.py, tests/golden/pixels_autocast_fp16.json)")
     args = ap.parse_args(argv)
+    if not 1 <= args.batch_size <= MAX_BATCH_SIZE:
+        ap.error(f"--batch_size must be 1..{MAX_BATCH_SIZE} (reference batches of 2 x batch_size <= {2 * MAX_BATCH_SIZE} rows)")
     dtype = args.dtype or ("fp16" if args.fp16 else DEFAULT_DTYPE)
+    max_batch = max(64, 2 * args.batch_size)          # one reference batch is encoded in one launch group
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -222,7 +230,7 @@ def main(argv=None):
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local))
     from .checkpoint import load_checkpoint               # strict validation, no optimizer state, safetensors-aware
     states = W.synthetic_checkpoint(0) if args.load_path == "synthetic" else load_checkpoint(args.load_path)
-    engine = Engine(states["encoder"], states["decoder"], device=local, max_batch=64, dtype=dtype)
+    engine = Engine(states["encoder"], states["decoder"], device=local, max_batch=max_batch, dtype=dtype)
     df = pd.read_csv(os.path.join(args.data_path, args.test_file))
     paths = [os.path.join(args.data_path, p) for p in df["file_path"]]
     def infer(e):
@@ -239,7 +247,7 @@ def main(argv=None):
             raise
         print(f"[rank {rank}] {err}: repeating the evaluation with --dtype {to} on every rank", file=sys.stderr, flush=True)
         engine.close()
-        engine = Engine(states["encoder"], states["decoder"], device=local, max_batch=64, dtype=to)
+        engine = Engine(states["encoder"], states["decoder"], device=local, max_batch=max_batch, dtype=to)
         preds = infer(engine)
     if rank == 0:
         if "image_id" not in df.columns:    # main.py:461-462

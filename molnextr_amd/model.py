@@ -23,6 +23,7 @@ from .tokenizer import get_tokenizer
 
 BOND_TYPES = ["", "single", "double", "triple", "aromatic", "solid wedge", "dashed wedge"]  # reference model.py:30
 ROWS = Engine.ROWS_PER_DECODE
+MAX_REF_BATCH = Engine.MAX_REF_BATCH      # rows of one reference batch on the continuous-batching greedy path (predict_pipeline)
 
 
 def decode_batch(engine: Engine, features: torch.Tensor, tokenizer=None, ref_batch_size: Optional[int] = None,
@@ -45,7 +46,8 @@ def decode_batch(engine: Engine, features: torch.Tensor, tokenizer=None, ref_bat
     B = features.shape[0]
     rbs = ref_batch_size or ROWS
     if rbs > ROWS:
-        raise ValueError(f"reference batches larger than {ROWS} rows are not supported by one engine call")
+        raise ValueError(f"decode_batch decodes reference batches of at most {ROWS} rows per engine call; use predict_pipeline "
+                         f"(greedy, up to {MAX_REF_BATCH} rows per reference batch) for ref_batch_size={rbs}")
     group = (ROWS // rbs) * rbs          # rows per engine call: whole reference batches only
     if beam_size > 1:
         if compute_confidence:
@@ -104,10 +106,15 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
     sequence_to_smiles' indices), much higher throughput. compute_confidence=True: mnx_predict_confidence, the same
     pipeline with the confidences computed on the device when a reference batch retires; the dicts gain the keys of
     decode_batch(compute_confidence=True) ('atom_scores' in 'chartok_coords', 'edge_scores', 'overall_score').
-    beam_size > 1: mnx_predict_beam (best hypothesis per image, 'beam_scores' = [its average log-prob]); no confidences."""
+    beam_size > 1: mnx_predict_beam (best hypothesis per image, 'beam_scores' = [its average log-prob]); no confidences.
+    ref_batch_size: rows per reference batch (the positional-encoding numbering unit), up to MAX_REF_BATCH = 512 for greedy
+    decoding (and the engine's max_batch / dec_slots: Engine.max_ref_batch), up to 32 with beam_size > 1."""
     tok = (tokenizer or get_tokenizer())["chartok_coords"]
     if compute_confidence and beam_size > 1:
         raise NotImplementedError("beam search does not track token scores (neither does the reference's)")
+    if beam_size > 1 and ref_batch_size > ROWS:
+        raise ValueError(f"beam search takes reference batches of at most {ROWS} rows; got ref_batch_size={ref_batch_size} "
+                         f"(greedy decoding takes up to {MAX_REF_BATCH})")
     conf = {"confidence": True} if compute_confidence else {}
     out = engine.predict(images, ref_batch=ref_batch_size, max_len=max_len, beam=beam_size, **conf)
     scores = out["scores"].cpu().numpy() if beam_size > 1 else None
@@ -197,16 +204,23 @@ class molnextr:
             import warnings
             warnings.warn(f"molnextr_amd: an encoder activation left the fp16 range of operand mode '{self.engine.dtype}' "
                           f"({e}); rebuilding the engine with dtype='{to}' and repeating the batch", RuntimeWarning)
-            dev = self.engine.device
-            self._join_prefetch()       # the helper of group g + 1 may still be inside mnx_preprocess on this handle
-            self.engine.close()
-            self.engine = Engine(self._states["encoder"], self._states["decoder"], device=dev, max_batch=self._max_batch,
-                                 dtype=to)
+            self._rebuild_engine(dtype=to)  # joins the helper of group g + 1: it may still be inside mnx_preprocess on this handle
             if self._groups_done:
                 # earlier groups of this predict_images call were computed in the fp16 mode: one call, one operand mode —
                 # the call starts again from its first image (predict_images catches this)
                 raise _RestartCall()
             return job(self.engine)
+
+    def _rebuild_engine(self, max_batch=None, dtype=None):
+        """Replaces the engine by one with this max_batch / operand mode (the others kept). The prefetch helper works on
+        the current engine, so it is joined before that engine is closed."""
+        dev, dtype = self.engine.device, dtype or self.engine.dtype
+        if max_batch is not None:
+            self._max_batch = max_batch
+        self._join_prefetch()
+        self.engine.close()
+        self.engine = Engine(self._states["encoder"], self._states["decoder"], device=dev, max_batch=self._max_batch,
+                             dtype=dtype)
 
     @staticmethod
     def _get_args(args_states=None):
@@ -302,12 +316,15 @@ class molnextr:
     def _predict_all(self, input_images: List, return_confidence: bool, batch_size: int) -> List[dict]:
         """The engine part of predict_images: one prediction dict per image, every group in ONE operand mode."""
         preds: List[dict] = []
-        cap = min(ROWS, self.engine.max_batch)
         batch_size = min(batch_size, len(input_images))     # a batch larger than the job is the whole job: same numbering
-        if batch_size < 1 or batch_size > cap:
+        if batch_size < 1 or batch_size > MAX_REF_BATCH:
             # results depend on the row inside the reference batch (positional-encoding quirk), so a silently
             # different batch size would silently change tokens
-            raise ValueError(f"batch_size must be 1..{cap} (one reference batch per {ROWS}-row decode tile); got {batch_size}")
+            raise ValueError(f"batch_size must be 1..{MAX_REF_BATCH} (one reference batch is decoded as one unit); got {batch_size}")
+        if batch_size > self.engine.max_batch:
+            # a reference batch is encoded in one launch group: grow the engine once (the encoder is bitwise batch-invariant,
+            # so results do not depend on max_batch)
+            self._rebuild_engine(max_batch=-(-batch_size // ROWS) * ROWS)
         # throughput path: many images per engine call, reference batches of `batch_size` kept as numbering units;
         # the group is a whole number of reference batches so that batch boundaries do not drift between groups
         group = (self.group_images // batch_size) * batch_size

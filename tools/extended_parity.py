@@ -9,6 +9,12 @@ mode, decodes free-running (tokens must be the oracle's) and teacher-forced alon
 token, argmax flips, raw logits of EVERY step). It writes one JSON record; nothing here is part of the product path.
 
     python tools/extended_parity.py [--ckpt 0|stress] [--batches 8] [--first 1000] [--dtype fp16x3m | --two TAGS] [--out file.json]
+                                    [--ref-batch N]
+
+--ref-batch N (default 32): reference batches of N images. Above 32 rows (up to 512) a batch is decoded as ONE reference batch
+on the continuous-batching path (Engine.predict with confidences: tokens and the log-prob of every emitted token) — teacher
+forcing and raw logits exist only for the 32-row decode calls, so such a record has no logit columns; a flip there is a row
+whose free-running ids leave the oracle's, counted once at its first differing step with the oracle's raw top-1 / top-2 margin.
 """
 import argparse
 import json
@@ -91,6 +97,56 @@ def check(eng, ck, first, batches, rows=32, label=None, verbose=True):
     return rec
 
 
+def check_refbatch(eng, ck, first, batches, rows, label=None, verbose=True):
+    """`batches` reference batches of `rows` (> 32) images from image `first`, each decoded as one batch by Engine.predict
+    and by the oracle: rows exact free-running, flips at first divergence, log-prob error along the common prefix."""
+    dev = torch.device("cuda", eng.device)
+    rec = {"first_image": first, "ref_batch": rows, "batches": [], "images": 0, "steps": 0, "flips": 0,
+           "rows_exact_free_running": 0, "logp_max_err": 0.0, "feature_max_err": 0.0, "flip_margins": []}
+    if label:
+        rec.update(label)
+    t0 = time.time()
+    for b in range(batches):
+        img = W.synthetic_images(rows, first_index=first + rows * b)
+        ref_f = torch.cat([encoder_forward(img[i:i + 8], ck["encoder"]) for i in range(0, rows, 8)])
+        ref = greedy_decode(ref_f, ck["decoder"], trace=True)
+        x = img.to(dev)
+        feats = torch.cat([eng.encode(x[i:i + eng.max_batch].contiguous()).cpu() for i in range(0, rows, eng.max_batch)])
+        ferr = float((feats - ref_f).abs().max())
+        out = eng.predict(x, ref_batch=rows, confidence=True)
+        toks, lens, lp = out["tokens"].cpu().numpy(), out["lengths"].cpu().numpy(), out["token_logp"].cpu().numpy()
+        perr, flips, exact, margins = 0.0, 0, 0, []
+        for r in range(rows):
+            g = np.array(ref.tokens[r], np.int32)
+            n = min(int(lens[r]), len(g))
+            bad = np.nonzero(toks[r, :n] != g[:n])[0]
+            d = int(bad[0]) if len(bad) else (None if int(lens[r]) == len(g) else n)
+            upto = len(g) if d is None else d
+            if upto:
+                perr = max(perr, float(np.abs(lp[r, :upto] - np.array(ref.token_logp[r][:upto], np.float32)).max()))
+            if d is None:
+                exact += 1
+                continue
+            flips += 1
+            alive, ref_lg = ref.logits_trace[d]
+            top = torch.log_softmax(ref_lg[alive.index(r)], -1).topk(2).values
+            margins.append(float(top[0] - top[1]))
+        brec = {"first_image": first + rows * b, "steps": int(sum(len(t) for t in ref.tokens)),
+                "len_max": int(max(len(t) for t in ref.tokens)), "feature_max_err": ferr, "logp_max_err": perr,
+                "flips": flips, "rows_exact_free_running": exact}
+        rec["batches"].append(brec)
+        rec["images"] += rows
+        rec["steps"] += brec["steps"]
+        rec["flips"] += flips
+        rec["rows_exact_free_running"] += exact
+        rec["flip_margins"] += [round(m, 6) for m in margins]
+        for k in ("logp_max_err", "feature_max_err"):
+            rec[k] = max(rec[k], brec[k])
+        if verbose:
+            print(json.dumps(brec), f"[{time.time() - t0:.0f} s]", flush=True)
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ckpt", default="0", choices=["0", "stress"])
@@ -100,14 +156,22 @@ def main():
     ap.add_argument("--two", default=None, help="fp16x3 engine with THIS two-term table (Engine.set_op_terms tags, e.g. qkv.s2,fc1.s2)")
     ap.add_argument("--threads", type=int, default=32)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--ref-batch", type=int, default=32, help="images per reference batch (1..512; above 32: see the docstring)")
     a = ap.parse_args()
+    if not 1 <= a.ref_batch <= Engine.MAX_REF_BATCH:
+        ap.error(f"--ref-batch must be 1..{Engine.MAX_REF_BATCH}")
     torch.set_num_threads(a.threads)
     ck = W.synthetic_checkpoint(1, stress=True) if a.ckpt == "stress" else W.synthetic_checkpoint(0)
-    eng = Engine(ck["encoder"], ck["decoder"], device=0, max_batch=32, dtype="fp16x3" if a.two is not None else a.dtype, dec_slots=64)
+    big = a.ref_batch > Engine.ROWS_PER_DECODE
+    eng = Engine(ck["encoder"], ck["decoder"], device=0, max_batch=max(32, a.ref_batch),
+                 dtype="fp16x3" if a.two is not None else a.dtype, dec_slots=max(64, -(-a.ref_batch // 32) * 32))
     if a.two is not None:
         eng.set_op_terms(tuple(t for t in a.two.split(",") if t))
     label = {"checkpoint": a.ckpt, "dtype": a.dtype if a.two is None else "fp16x3 + two-term table " + a.two}
-    rec = check(eng, ck, a.first, a.batches, label=label)
+    if big:
+        rec = check_refbatch(eng, ck, a.first, a.batches, a.ref_batch, label=label)
+    else:
+        rec = check(eng, ck, a.first, a.batches, rows=a.ref_batch, label=label)
     eng.close()
     print("EXTENDED_PARITY", json.dumps({k: v for k, v in rec.items() if k != "batches"}), flush=True)
     if a.out:

@@ -28,8 +28,13 @@ Fixtures (all small):
                        logits, top-1/top-2 margins of every step, atom positions, bond matrices — for one batch of 6
                        and one of 32, plus the plain-random decoder (molecule_like=False) cut at 64 steps
   crop_pad.json        CropWhite.update_params/apply + PadToSquare.apply of the reference's data_aug.py on ragged pages
+  pixels_refbatch.npz/.json  (named target `refbatch` only, not in the default set) Encoder.forward + Decoder.decode on
+                       W.synthetic_images(64) under synthetic_checkpoint(0) as ONE reference batch of 64 rows (the README's
+                       evaluation: --batch_size 32 -> 64-row batches) and one of 40 (a full 32-row tile plus a ragged one):
+                       ids, lengths, token log-probs, margins; smiles / symbols / coords / indices / bonds / confidences
 
     python tools/gen_golden.py [name ...]      # only the named groups: swin decoder edges tokenizer e2e beam pixels crop
+                                               # stress, and refbatch (never part of a plain run)
 """
 import hashlib
 import json
@@ -435,6 +440,50 @@ def gen_stress(Encoder, Decoder, args, tok):
     print("pixels_stress: atoms", [len(p["symbols"]) for p in js])
 
 
+def gen_refbatch(Encoder, Decoder, args, tok, ck):
+    """Reference batches larger than 32 rows: the reference numbers positional-encoding rows inside the whole batch, so
+    rows 32.. of a 64-row batch see pe[32..] at step 0. Encoder.forward + Decoder.decode of the reference on
+    W.synthetic_images(64) under synthetic_checkpoint(0), decoded as one batch of 64 and as one batch of 40 (its first 40
+    images). Bond classes (k x k) and edge scores (the upper triangle i <= j of the symmetric k x k matrix, row-major) of
+    every molecule are stored flat in the npz, concatenated in image order."""
+    N = 64
+    enc = Encoder(reference_args()).eval()
+    enc.load_state_dict(ck["encoder"], strict=True)
+    img = W.synthetic_images(N)
+    with torch.no_grad():
+        feats = torch.cat([enc(img[i:i + 4])[0] for i in range(0, N, 4)])
+    out = {}
+    dec = Decoder(args, tok).eval()
+    dec.load_state_dict(ck["decoder"], strict=True)
+    js = {}
+    for name, B in (("m64", 64), ("m40", 40)):
+        o, _, _ = _greedy_with_margins(dec, tok, feats[:B], 480, n_logit_steps=0)
+        for k, v in o.items():
+            out[f"{name}_{k}"] = v
+        fin = np.isfinite(o["margin"])
+        print(f"refbatch {name}: lens {o['lens'].tolist()} margin min {o['margin'][fin].min():.6f} "
+              f"median {np.median(o['margin'][fin]):.3f}")
+        dec.compute_confidence = True
+        with torch.no_grad():
+            preds = dec.decode(feats[:B])
+        dec.compute_confidence = False
+        out[f"{name}_edges"] = np.concatenate([np.array(p["edges"], dtype=np.uint8).ravel() for p in preds])
+        es = [np.array(p["edge_scores"], dtype=np.float32) for p in preds]
+        assert all(np.array_equal(e, e.T) for e in es)            # symmetric: the upper triangle is the whole matrix
+        out[f"{name}_edge_scores"] = np.concatenate([e[np.triu_indices(e.shape[0])] for e in es])
+        js[name] = [{"smiles": p["chartok_coords"]["smiles"], "symbols": p["chartok_coords"]["symbols"],
+                     "coords": p["chartok_coords"]["coords"], "indices": p["chartok_coords"]["indices"],
+                     "atom_scores": p["chartok_coords"]["atom_scores"], "overall_score": p["overall_score"]} for p in preds]
+        print(f"refbatch {name}: atoms", [len(p["symbols"]) for p in js[name]])
+    np.savez_compressed(os.path.join(GOLD, "pixels_refbatch.npz"), **out)
+    with open(os.path.join(GOLD, "pixels_refbatch.json"), "w") as f:
+        json.dump({"images": "W.synthetic_images(64)", "checkpoint": "W.synthetic_checkpoint(0)",
+                   "batches": {"m64": "one reference batch of images 0..63", "m40": "one reference batch of images 0..39"},
+                   "npz": "<name>_edges: k x k per molecule, <name>_edge_scores: its upper triangle (i <= j, row-major); "
+                          "flattened, concatenated in image order",
+                   "preds": js}, f)
+
+
 def gen_crop_pad():
     """CropWhite(pad=50) and PadToSquare of the reference's own data_aug.py (imported through a minimal
     albumentations / cv2 stand-in: both classes are pure numpy apart from a constant-border pad) on ragged pages:
@@ -497,6 +546,8 @@ def main():
         gen_stress(Encoder, Decoder, args, tok)
     if "crop" in want:
         gen_crop_pad()
+    if "refbatch" in want:
+        gen_refbatch(Encoder, Decoder, args, tok, ck)
     sizes = {f: os.path.getsize(os.path.join(GOLD, f)) for f in sorted(os.listdir(GOLD))}
     print("fixture bytes:", sizes, "total", sum(sizes.values()))
 
