@@ -89,21 +89,8 @@ struct FusedArgs {
     // lab aid (MNX_FUSED_STAMPS=<file>): [stage][block][phase] 100 MHz wall-clock stamps of the LAST tick, see tools/fused_stamps.py
     unsigned long long* stamps;
     int stage;
-    int row_base;            // first row of the tick branch this launch belongs to
-    // xcd != 0: the grid is (row tile slot, unit) instead of (unit, row tile) and slot x maps to the row tile whose 4-row group
-    // g satisfies g % 8 == x % 8. Workgroup b runs on XCD b % 8 (observed, for speed only), so every stage then works on a
-    // row's planes on the SAME XCD that wrote them: the consumer's plane loads hit that XCD's L2 instead of missing to memory.
-    int xcd;
 };
 
-// row tile of grid slot x of nt slots, tiles of R rows: consecutive 4-row groups on consecutive XCDs (nt * R / 4 a multiple of 8)
-template <int R>
-__device__ __forceinline__ int xcd_tile(int x, int nt) {
-    if (R >= 4) return x;
-    constexpr int Q = 4 / R;                 // tiles per 4-row group
-    const int groups = nt / Q;
-    return Q * (x % groups) + x / groups;
-}
 constexpr int STAMP_BLOCKS = 512, STAMP_PHASES = 12;
 #ifdef MNX_FUSED_STAMPS     // lab build only (make STAMPS=1): the stamps cost registers in kernels that have none to spare
 #define FSTAMP(ph)                                                                                                        \
@@ -514,8 +501,8 @@ __global__ __launch_bounds__(256 * R) void dec_fa_kernel(FusedArgs a) {
     typedef FaLds<R> Ld;
     constexpr int VP = R >= 4 ? 4 : 8;                   // value rows requested ahead (1024 threads: 128 registers each)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int h = a.xcd ? blockIdx.y : blockIdx.x;
-    const int row0 = a.row_base + (a.xcd ? xcd_tile<R>(blockIdx.x, gridDim.x) : (int)blockIdx.y) * R;
+    const int h = blockIdx.x;
+    const int row0 = (int)blockIdx.y * R;
     FSTAMP(0);
     const int4 rv = a.st->rowv[row0 + (tid >> 8)];       // {slot, t, prev_tok, rank} of the row this thread attends for
     const int n_act = a.st->n_active;
@@ -619,7 +606,7 @@ __global__ __launch_bounds__(512) void dec_ma_kernel(FusedArgs a) {
     constexpr int R = Ld::R;
     const int tid = threadIdx.x;
     const int h = blockIdx.x;
-    const int row0 = a.row_base + (int)blockIdx.y * R;
+    const int row0 = (int)blockIdx.y * R;
     const int n_act = a.st->n_active;
     typedef LinUnit<96, 8> U;                             // 2 column blocks x 8 chains on 8 waves: 2 chains per wave
     const U u = lin_unit<96, 8>();
@@ -671,7 +658,7 @@ __global__ __launch_bounds__(256 * R) void dec_mb_kernel(FusedArgs a) {
     constexpr int VP = R >= 4 ? 4 : 8;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, rt = tid & 255;
     const int h = blockIdx.x;
-    const int row0 = a.row_base + (int)blockIdx.y * R;
+    const int row0 = (int)blockIdx.y * R;
     const int4 rv = a.st->rowv[row0 + (tid >> 8)];       // {slot, t, prev_tok, rank}; dummy rows: slot 0, t 0
     const int n_act = a.st->n_active;
     const int nk = rv.y + 1;                             // keys of the row: positions 0 .. t
@@ -706,8 +693,8 @@ __global__ __launch_bounds__(256 * R) void dec_fb_kernel(FusedArgs a) {
     typedef FbLds<R> Ld;
     constexpr int VP = 5;                                // 144 memory rows = 4.5 x 32: every value row is prefetched
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int h = a.xcd ? blockIdx.y : blockIdx.x;
-    const int row0 = a.row_base + (a.xcd ? xcd_tile<R>(blockIdx.x, gridDim.x) : (int)blockIdx.y) * R;
+    const int h = blockIdx.x;
+    const int row0 = (int)blockIdx.y * R;
     FSTAMP(0);
     const int mb = __builtin_amdgcn_readfirstlane(a.st->row_mem[row0 + (tid >> 8)]);    // wave-uniform: scalar block bases
     const int n_act = a.st->n_active;
@@ -761,8 +748,8 @@ __global__ __launch_bounds__(256) void dec_fc_kernel(FusedArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     typedef FcLds<R> Ld;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int sl = a.xcd ? blockIdx.y : blockIdx.x;
-    const int row0 = a.row_base + (a.xcd ? xcd_tile<R>(blockIdx.x, gridDim.x) : (int)blockIdx.y) * R;
+    const int sl = blockIdx.x;
+    const int row0 = (int)blockIdx.y * R;
     FSTAMP(0);
     const int n_act = a.st->n_active;
     float b1w[64], b2w[64];
@@ -839,7 +826,7 @@ hipError_t dec_fused_init() {
 
 // R: rows per workgroup of the two attention stages (256 threads per row); RC: rows per workgroup of the feed-forward stage
 template <int R, int RC>
-static void fused_layers(const DecWeights& w, const DecBuffers& b, int row_base, int rows, int xcd, bool mid, hipStream_t s) {
+static void fused_layers(const DecWeights& w, const DecBuffers& b, int rows, bool mid, hipStream_t s) {
     const int D = 256, H = w.heads, T = b.T;
     int stage = 0;      // stage k reads stream k & 1 and partial buffer (k - 1) & 1, writes stream / partials (k + 1) & 1 / k & 1
     float* xb[2] = {b.x, b.x2};
@@ -850,8 +837,6 @@ static void fused_layers(const DecWeights& w, const DecBuffers& b, int row_base,
     a.Tq = b.Tq; a.Sq = b.Sq;
     a.mem_stride = (long long)((size_t)w.layers * 2 * H * mem_blk);
     a.stamps = g_stamps;
-    a.row_base = row_base;
-    a.xcd = (xcd && !mid && rows % 32 == 0) ? 1 : 0;
     a.qbuf = b.q;
     for (int l = 0; l < w.layers; ++l) {
         const DecLayerW& Lw = w.L[l];
@@ -862,7 +847,7 @@ static void fused_layers(const DecWeights& w, const DecBuffers& b, int row_base,
         a.gamma = Lw.ln1_g; a.beta = Lw.ln1_b; a.wqkv = Lw.wqkv_t; a.bqkv = Lw.bqkv; a.wo = Lw.wo_t;
         a.kcache = b.self_k + (size_t)l * b.slots * H * self_blk;
         a.vcache = b.self_v + (size_t)l * b.slots * H * self_blk;
-        const dim3 gab = a.xcd ? dim3(rows / R, H) : dim3(H, rows / R);
+        const dim3 gab(H, rows / R);
         if (mid) {      // the linear half on 16-row tiles, then the attention half on R-row tiles
             const dim3 gma(H, rows / MaLds::R);
             if (l == 0) hipLaunchKernelGGL((dec_ma_kernel<true>), gma, dim3(512), MaLds::total * 4, s, a);
@@ -882,30 +867,28 @@ static void fused_layers(const DecWeights& w, const DecBuffers& b, int row_base,
         a.stage = stage;
         a.xin = xb[stage & 1]; a.xout = xb[(stage + 1) & 1]; a.part_in = pb[(stage + 1) & 1]; a.part_out = pb[stage & 1];
         a.bias_in = Lw.bo2; a.gamma = Lw.lnf_g; a.beta = Lw.lnf_b; a.w1 = Lw.w1_t; a.b1 = Lw.b1; a.w2 = Lw.w2_t;
-        hipLaunchKernelGGL((dec_fc_kernel<RC>), a.xcd ? dim3(rows / RC, w.dff / FF_SLICE) : dim3(w.dff / FF_SLICE, rows / RC), dim3(256),
-                           FcLds<RC>::total * 4, s, a);
+        hipLaunchKernelGGL((dec_fc_kernel<RC>), dim3(w.dff / FF_SLICE, rows / RC), dim3(256), FcLds<RC>::total * 4, s, a);
         ++stage;
     }
 }
 
 // The 3 (mid form: 4) x layers kernels of a greedy tick for `rows` rows of capacity (a multiple of 16). row_tile is encoded as
-// R * 100 + RC (R in {2, 4}: rows per attention workgroup; RC in {4, 8, 16}: rows per feed-forward workgroup), + 1000: row tiles
-// pinned to XCDs, + 2000: the mid form.
+// R * 100 + RC (R in {2, 4}: rows per attention workgroup; RC in {4, 8, 16}: rows per feed-forward workgroup), + 2000: the mid
+// form.
 // Returns the stream buffer and the partial buffer the head has to sum (16 partials of the last w_2 + its bias).
-hipError_t dec_enqueue_fused_layers(const DecWeights& w, const DecBuffers& b, int row_base, int rows, int row_tile, hipStream_t s,
+hipError_t dec_enqueue_fused_layers(const DecWeights& w, const DecBuffers& b, int rows, int row_tile, hipStream_t s,
                                     const float** x_final, const float** part_final) {
     const bool mid = row_tile >= 2000;       // 2000 + 100 R + RC: the mid form (dec_ma + dec_mb instead of dec_fa)
-    const int xcd = (row_tile / 1000) & 1;   // 1000 + 100 R + RC: XCD-local row tiles (FusedArgs::xcd)
-    row_tile %= 1000;
+    if (mid) row_tile -= 2000;
     if (w.dff != 16 * FF_SLICE || w.heads != 8 || b.T + 1 > PS_SELF || b.S > PS_CROSS || (rows % 16) || !b.fpart ||
-        row_base + rows > b.fpart_rows)
+        rows > b.fpart_rows)
         return hipErrorInvalidValue;
     switch (row_tile) {
-        case 204: fused_layers<2, 4>(w, b, row_base, rows, xcd, mid, s); break;
-        case 208: fused_layers<2, 8>(w, b, row_base, rows, xcd, mid, s); break;
-        case 404: fused_layers<4, 4>(w, b, row_base, rows, xcd, mid, s); break;
-        case 408: fused_layers<4, 8>(w, b, row_base, rows, xcd, mid, s); break;
-        case 416: fused_layers<4, 16>(w, b, row_base, rows, xcd, mid, s); break;
+        case 204: fused_layers<2, 4>(w, b, rows, mid, s); break;
+        case 208: fused_layers<2, 8>(w, b, rows, mid, s); break;
+        case 404: fused_layers<4, 4>(w, b, rows, mid, s); break;
+        case 408: fused_layers<4, 8>(w, b, rows, mid, s); break;
+        case 416: fused_layers<4, 16>(w, b, rows, mid, s); break;
         default: return hipErrorInvalidValue;
     }
     const int stages = 3 * w.layers;

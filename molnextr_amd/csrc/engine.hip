@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <tuple>
 #include <unordered_map>
@@ -45,12 +46,11 @@ struct StageW {
 // op classes of the split modes (mnx_set_split_terms)
 enum { SPL_QKV = 1, SPL_ATTN = 2, SPL_PROJ = 4, SPL_FC1 = 8, SPL_FC2 = 16, SPL_MERGE = 32, SPL_ALL = 63 };
 struct GraphKey {
-    int slots, rows, trace, forced, tile, branches;
+    int slots, rows, trace, forced, tile;
     bool operator<(const GraphKey& o) const {
-        return std::tie(slots, rows, trace, forced, tile, branches) < std::tie(o.slots, o.rows, o.trace, o.forced, o.tile, o.branches);
+        return std::tie(slots, rows, trace, forced, tile) < std::tie(o.slots, o.rows, o.trace, o.forced, o.tile);
     }
 };
-constexpr int MAX_TICK_BRANCHES = 8;
 
 }  // namespace
 
@@ -94,7 +94,6 @@ struct mnx_engine {
     std::map<GraphKey, hipGraphExec_t> graphs;
     // continuous-batching pipeline (mnx_predict)
     hipStream_t enc_stream = nullptr;
-    hipEvent_t ev_order = nullptr;
     float* feat_ring[2] = {nullptr, nullptr};
     hipEvent_t ev_enc_done[2] = {nullptr, nullptr}, ev_feat_free[2] = {nullptr, nullptr}, ev_poll[2] = {nullptr, nullptr};
     int* slot_lists = nullptr;          // device [MAX_CHUNKS][32]: slot list of every 32-slot row tile
@@ -105,7 +104,8 @@ struct mnx_engine {
     bool use_graph = true;
     // greedy ticks of up to dec_fused_max rows run as three launches per layer (dec_fused.hip): dec_tile rows per workgroup in
     // the two attention stages (256 threads per row), dec_tile_ff rows in the feed-forward stage; larger ticks keep the
-    // 8-launches-per-layer kernels of decoder.hip (knobs MNX_DEC_TILE, MNX_DEC_TILE_FF, MNX_DEC_FUSED_MAX)
+    // 8-launches-per-layer kernels of decoder.hip (knobs MNX_DEC_TILE, MNX_DEC_TILE_FF, MNX_DEC_FUSED_MAX);
+    // dec_tile -1: 2 rows per workgroup up to 64 rows of capacity, 4 beyond
     int dec_tile = -1, dec_tile_ff = 4, dec_fused_max = 128;
     // ticks of more than dec_fused_max and up to dec_mid_max rows run the MID form (dec_fused.hip: dec_fa cut into a 16-row
     // linear launch and an attention launch, 4 launches per layer; bit-identical to the fused form, so that the capacity the
@@ -113,15 +113,6 @@ struct mnx_engine {
     // 8-launches-per-layer kernels of decoder.hip, whose 32-row linears move the fewest bytes per row (MNX_DEC_MID_MAX;
     // 4096 = every capacity: bit-reproducible jobs of any size, slower at >= 1024 rows)
     int dec_mid_max = 0;
-    int dec_xcd = 0;           // fused tick: row tiles pinned to XCDs so that a row's partial planes stay in one L2 (MNX_DEC_XCD)
-    // a tick of more than dec_branch_rows rows can be enqueued as up to dec_branch_max BRANCHES of rows on parallel branches
-    // of the tick graph (rows are independent through the whole stack). OFF by default (0): measured, the branches of a
-    // hipGraph do overlap but every launch gets slower and the fork / join costs more than the overlap buys — 192 rows as
-    // 2 x 96: 411 us against 374, 640 rows as 4 x 160: 1552 against 572. Kept as a tested knob
-    // (MNX_DEC_BRANCH_ROWS, MNX_DEC_BRANCH_MAX): the row_base plumbing costs nothing.
-    int dec_branch_rows = 0, dec_branch_max = 4;
-    hipStream_t tick_streams[MAX_TICK_BRANCHES] = {};
-    hipEvent_t ev_fork = nullptr, ev_join[MAX_TICK_BRANCHES] = {};   // dec_tile -1: 2 rows per workgroup up to 64 rows of capacity, 4 beyond
     hipStream_t own_stream = nullptr;   // used when the caller passes the legacy null stream (not capturable)
     // profiling (bench aid)
     bool profiling = false;
@@ -143,6 +134,12 @@ namespace {
             (h)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                                 \
             return MNX_ERR_HIP;                                                                           \
         }                                                                                                 \
+    } while (0)
+
+#define MNXCHK(expr)                                                                                      \
+    do {                                                                                                  \
+        const int rc_ = (expr);                                                                           \
+        if (rc_ != MNX_OK) return rc_;                                                                    \
     } while (0)
 
 struct Packer {
@@ -284,12 +281,6 @@ void mnx_destroy(mnx_engine* h) {
     for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);
     if (h->own_stream) hipStreamDestroy(h->own_stream);
     if (h->enc_stream) hipStreamDestroy(h->enc_stream);
-    if (h->ev_order) hipEventDestroy(h->ev_order);
-    if (h->ev_fork) hipEventDestroy(h->ev_fork);
-    for (int i = 1; i < MAX_TICK_BRANCHES; ++i) {
-        if (h->tick_streams[i]) hipStreamDestroy(h->tick_streams[i]);
-        if (h->ev_join[i]) hipEventDestroy(h->ev_join[i]);
-    }
     for (int i = 0; i < 2; ++i) {
         if (h->ev_enc_done[i]) hipEventDestroy(h->ev_enc_done[i]);
         if (h->ev_feat_free[i]) hipEventDestroy(h->ev_feat_free[i]);
@@ -360,9 +351,6 @@ int mnx_create(const mnx_config* cfg, const mnx_weight_desc* weights, int32_t n_
         }
         set_persistent_cus(n);
     }
-    if (const char* e = getenv("MNX_DEC_BRANCH_ROWS")) h->dec_branch_rows = atoi(e);
-    if (const char* e = getenv("MNX_DEC_BRANCH_MAX")) h->dec_branch_max = std::max(1, std::min(MAX_TICK_BRANCHES, atoi(e)));
-    if (const char* e = getenv("MNX_DEC_XCD")) h->dec_xcd = atoi(e) != 0;
     if (const char* e = getenv("MNX_DEC_TILE")) h->dec_tile = atoi(e);              // 0: never use the fused tick
     if (const char* e = getenv("MNX_DEC_TILE_FF")) h->dec_tile_ff = atoi(e);
     if (const char* e = getenv("MNX_DEC_FUSED_MAX")) h->dec_fused_max = atoi(e);    // largest capacity that runs fused
@@ -610,9 +598,7 @@ int mnx_create(const mnx_config* cfg, const mnx_weight_desc* weights, int32_t n_
     db.part = (float*)P.dalloc((size_t)(FF / 256) * SL * D * 4);
     // partial planes of the fused / mid tick: only ticks of up to max(dec_fused_max, dec_mid_max) rows of capacity touch them
     // (128 rows by default: 4 MB; every slot would be 100 MB at the bench's 3072)
-    // (tick branches — off by default — run fused tiles at any row offset of a larger tick: every slot then)
-    db.fpart_rows = h->dec_branch_rows > 0 ? SL
-                  : std::min(SL, std::max(ROW_TILE, (std::max(h->dec_fused_max, h->dec_mid_max) + ROW_TILE - 1) / ROW_TILE * ROW_TILE));
+    db.fpart_rows = std::min(SL, std::max(ROW_TILE, (std::max(h->dec_fused_max, h->dec_mid_max) + ROW_TILE - 1) / ROW_TILE * ROW_TILE));
     db.fpart = (float*)P.dalloc((size_t)2 * 16 * db.fpart_rows * D * 4);
     if (db.fpart && hipMemset(db.fpart, 0, (size_t)2 * 16 * db.fpart_rows * D * 4) != hipSuccess) P.problems.push_back("hipMemset failed");
     if (dec_fused_init() != hipSuccess) P.problems.push_back("dec_fused_init: LDS opt-in failed");
@@ -639,7 +625,6 @@ int mnx_create(const mnx_config* cfg, const mnx_weight_desc* weights, int32_t n_
     db.edge_g = (float*)P.dalloc((size_t)ROW_TILE * db.kmax * D * 4);
     db.edge_uv = (float*)P.dalloc((size_t)ROW_TILE * db.kmax * 2 * D * 4);
     db.edge_prob = (float*)P.dalloc((size_t)ROW_TILE * db.kmax * db.kmax * 8 * 4);
-    h->out_trace = nullptr;   // allocated lazily on first traced decode (test aid)
     const size_t ring_rows = std::max<size_t>(ROW_TILE, MB);   // one encode group (max_batch images) per buffer
     h->feat_ring[0] = (float*)P.dalloc(ring_rows * S * CF * 4);
     h->feat_ring[1] = (float*)P.dalloc(ring_rows * S * CF * 4);
@@ -660,14 +645,6 @@ int mnx_create(const mnx_config* cfg, const mnx_weight_desc* weights, int32_t n_
         int lo = 0, hi = 0;
         hipDeviceGetStreamPriorityRange(&lo, &hi);
         if (hipStreamCreateWithPriority(&h->enc_stream, hipStreamNonBlocking, hi) != hipSuccess) P.problems.push_back("stream create failed");
-        if (hipEventCreateWithFlags(&h->ev_order, hipEventDisableTiming) != hipSuccess) P.problems.push_back("event create failed");
-        if (h->dec_branch_rows > 0) {       // tick branches (off by default): their streams / events only when asked for
-            if (hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess) P.problems.push_back("event create failed");
-            for (int i = 1; i < MAX_TICK_BRANCHES; ++i)
-                if (hipStreamCreateWithFlags(&h->tick_streams[i], hipStreamNonBlocking) != hipSuccess ||
-                    hipEventCreateWithFlags(&h->ev_join[i], hipEventDisableTiming) != hipSuccess)
-                    P.problems.push_back("tick branch stream / event create failed");
-        }
     }
     for (int i = 0; i < 2; ++i)
         if (hipEventCreateWithFlags(&h->ev_enc_done[i], hipEventDisableTiming) != hipSuccess ||
@@ -849,9 +826,103 @@ int mnx_encode(mnx_engine* h, const float* images, int32_t B, float* features_ou
     return MNX_OK;
 }
 
-// row tiles of the fused greedy tick for a capacity of `rows` rows: 100 x attention tile + feed-forward tile (0: the
-// decoder.hip tick)
-static int tick_tile(const mnx_engine* h, int rows) {
+}  // extern "C"
+
+namespace {
+
+// The stream an entry point runs on, after selecting the engine's device: the caller's, or — for the legacy null stream,
+// which is not capturable — the engine's own default-flag stream (created on first use), which synchronises implicitly with
+// the null stream on both ends
+int caller_stream(mnx_engine* h, void* stream, hipStream_t* s) {
+    HIPCHK(h, hipSetDevice(h->device));
+    *s = (hipStream_t)stream;
+    if (!*s) {
+        if (!h->own_stream) HIPCHK(h, hipStreamCreate(&h->own_stream));
+        *s = h->own_stream;
+    }
+    return MNX_OK;
+}
+
+// A device buffer allocated by the first call that needs it and kept (allocs, bytes) until mnx_destroy
+template <typename T>
+int lazy_alloc(mnx_engine* h, T** p, size_t bytes) {
+    if (*p) return MNX_OK;
+    HIPCHK(h, hipMalloc((void**)p, bytes));
+    h->allocs.push_back(*p);
+    h->bytes += bytes;
+    return MNX_OK;
+}
+
+// The decoder memory of n images (n <= ROW_TILE: the fp32 scratch db.memory / db.mem_kv32 holds that many) from their encoder
+// features: enc_transform, then the cross-attention K / V of all layers in one SGEMM, packed into memory blocks
+// blk0 .. blk0 + n - 1
+int project_memory(mnx_engine* h, const float* feats, int n, int blk0, hipStream_t s) {
+    const mnx_config& c = h->cfg;
+    const int S = h->db.S, D = c.dec_dim;
+    char* memkv = h->db.mem_kv + (size_t)blk0 * c.dec_layers * 2 * c.dec_heads * kvq_block_bytes(h->db.Sq);
+    HIPCHK(h, launch_sgemm_tn(feats, h->dw.w_enc, h->dw.b_enc, h->db.memory, n * S, D, h->dw.enc_dim, s));
+    HIPCHK(h, launch_sgemm_tn(h->db.memory, h->dw.w_memkv, h->dw.b_memkv, h->db.mem_kv32, n * S, c.dec_layers * 2 * D, D, s, S));
+    HIPCHK(h, kvq_pack_enqueue(h->db.mem_kv32, memkv, n * c.dec_layers * 2 * c.dec_heads, S, h->db.Sq, s));
+    return MNX_OK;
+}
+
+// The two encoder feature buffers of mnx_predict / mnx_predict_beam. The encoder runs ahead on enc_stream, one GROUP of up
+// to `grp` reference batches (as many as max_batch holds) per buffer: it is batch-invariant, so bigger GEMM grids and fewer
+// launches cost nothing. Buffer i holds the features of reference batches [first[i], first[i] + count[i]) (first -1: free).
+// When a buffer counts as ready and where it is released stay with the callers.
+struct FeatRing {
+    mnx_engine* h;
+    const float* images;
+    int n_img, ref_batch, n_chunks, grp;
+    int first[2] = {-1, -1}, count[2] = {0, 0};
+    bool used[2] = {false, false};      // released before: a refill waits for ev_feat_free
+    int next_enc = 0;                   // next reference batch to hand to the encoder
+
+    // encode the next group into every free buffer on enc_stream; ev_enc_done[i] marks buffer i complete
+    int refill() {
+        const size_t img_elems = (size_t)3 * h->cfg.img_size * h->cfg.img_size;
+        for (int i = 0; i < 2; ++i) {
+            if (first[i] >= 0 || next_enc >= n_chunks) continue;
+            const int cnt = std::min(grp, n_chunks - next_enc);
+            const int f = next_enc * ref_batch, n = std::min(cnt * ref_batch, n_img - f);
+            if (used[i]) HIPCHK(h, hipStreamWaitEvent(h->enc_stream, h->ev_feat_free[i], 0));
+            MNXCHK(mnx_encode(h, images + (size_t)f * img_elems, n, h->feat_ring[i], h->enc_stream));
+            HIPCHK(h, hipEventRecord(h->ev_enc_done[i], h->enc_stream));
+            first[i] = next_enc;
+            count[i] = cnt;
+            next_enc += cnt;
+        }
+        return MNX_OK;
+    }
+    // the buffer that holds reference batch k, -1 if none does (yet)
+    int find(int k) const {
+        for (int i = 0; i < 2; ++i)
+            if (first[i] >= 0 && k >= first[i] && k < first[i] + count[i]) return i;
+        return -1;
+    }
+    int end(int i) const { return first[i] + count[i]; }     // one past the last reference batch of buffer i
+    const float* feats(int i, int k) const {                  // features of reference batch k (held by buffer i)
+        return h->feat_ring[i] + (size_t)(k - first[i]) * ref_batch * h->db.S * h->dw.enc_dim;
+    }
+    // buffer i may be refilled once stream s has reached this point
+    int release(int i, hipStream_t s) {
+        HIPCHK(h, hipEventRecord(h->ev_feat_free[i], s));
+        used[i] = true;
+        first[i] = -1;
+        return MNX_OK;
+    }
+};
+
+// every exit path of mnx_predict*: nothing of the call may still be in flight on either stream
+struct DrainGuard {
+    mnx_engine* h;
+    hipStream_t s;
+    ~DrainGuard() { (void)hipStreamSynchronize(h->enc_stream); (void)hipStreamSynchronize(s); }
+};
+
+// row tiles of the fused greedy tick for a capacity of `rows` rows: 100 x attention tile + feed-forward tile, + 2000 for the
+// mid form (0: the decoder.hip tick)
+int tick_tile(const mnx_engine* h, int rows) {
     const mnx_config& c = h->cfg;
     if (c.dec_ff != 1024 || c.dec_heads != 8 || c.dec_dim != 256 || c.max_len + 1 > 512 || h->db.S > 160) return 0;
     if (h->dec_tile == 0 || rows % 16 || rows > h->db.fpart_rows) return 0;
@@ -860,148 +931,143 @@ static int tick_tile(const mnx_engine* h, int rows) {
         return 2000 + 100 * 4 + 16;
     }
     const int r = h->dec_tile > 0 ? h->dec_tile : (rows <= 64 ? 2 : 4);
-    return (h->dec_xcd ? 1000 : 0) + 100 * r + h->dec_tile_ff;
+    return 100 * r + h->dec_tile_ff;
 }
 
-// Branches of a tick of `rows` rows of capacity: (first row, rows) pairs, multiples of 32 rows, covering [0, rows).
-static int tick_branches(const mnx_engine* h, int rows, bool single, int (*br)[2]) {
-    int nb = 1;
-    if (!single && h->dec_branch_rows > 0 && rows > h->dec_branch_rows)
-        nb = std::min(h->dec_branch_max, (rows + h->dec_branch_rows - 1) / h->dec_branch_rows);
-    const int tiles = rows / ROW_TILE;
-    nb = std::max(1, std::min(nb, tiles));
-    int base = 0;
-    for (int i = 0; i < nb; ++i) {
-        const int t = tiles / nb + (i < tiles % nb ? 1 : 0);
-        br[i][0] = base; br[i][1] = t * ROW_TILE;
-        base += t * ROW_TILE;
-    }
-    return nb;
+// One greedy tick on s: the begin kernel over `slots` slots, then the layers + head of `rows` rows of capacity
+hipError_t enqueue_tick(mnx_engine* h, int slots, int rows, float* trace, int trace_rows, hipStream_t s, const int* forced) {
+    return dec_enqueue_tick(h->dw, h->db, slots, rows, trace, trace_rows, s, nullptr, forced, tick_tile(h, rows));
 }
 
-// One tick on stream s: the begin kernel, then the layers + head of every branch — branch 0 on s, the others on the
-// engine's branch streams between a fork event and join events (under stream capture this records parallel branches of the
-// graph; without a graph it runs the same way eagerly).
-static hipError_t enqueue_tick(mnx_engine* h, int slots, int rows, float* trace, int trace_rows, hipStream_t s,
-                               const int* forced) {
-    int br[MAX_TICK_BRANCHES][2];
-    const int nb = tick_branches(h, rows, trace != nullptr || forced != nullptr, br);
-    hipError_t e = dec_enqueue_status(h->db, slots, s);       // the begin kernel
-    if (e != hipSuccess) return e;
-    if (nb > 1) {
-        if ((e = hipEventRecord(h->ev_fork, s)) != hipSuccess) return e;
-        for (int i = 1; i < nb; ++i)
-            if ((e = hipStreamWaitEvent(h->tick_streams[i], h->ev_fork, 0)) != hipSuccess) return e;
-    }
-    for (int i = 0; i < nb; ++i) {
-        hipStream_t si = i == 0 ? s : h->tick_streams[i];
-        e = dec_enqueue_tick_rows(h->dw, h->db, br[i][0], br[i][1], trace, trace_rows, si, nullptr, forced, tick_tile(h, br[i][1]));
-        if (e != hipSuccess) return e;
-    }
-    for (int i = 1; i < nb; ++i) {
-        if ((e = hipEventRecord(h->ev_join[i], h->tick_streams[i])) != hipSuccess) return e;
-        if ((e = hipStreamWaitEvent(s, h->ev_join[i], 0)) != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-static int get_tick_graph(mnx_engine* h, int slots, int rows, float* trace, int trace_rows, hipStream_t s,
-                          hipGraphExec_t* out, const int* forced = nullptr) {
+// Captures what enqueue() puts on s into a graph and instantiates it; the hipGraph_t is released on every path
+template <typename F>
+int capture_graph(mnx_engine* h, const char* what, hipStream_t s, F&& enqueue, hipGraphExec_t* out) {
     *out = nullptr;
-    if (!h->use_graph) return MNX_OK;
-    int br[MAX_TICK_BRANCHES][2];
-    const int nb = tick_branches(h, rows, trace != nullptr || forced != nullptr, br);
-    GraphKey key{slots, rows, trace ? trace_rows : 0, forced ? trace_rows : 0, tick_tile(h, br[0][1]), nb};
-    auto it = h->graphs.find(key);
-    if (it != h->graphs.end()) { *out = it->second; return MNX_OK; }
-    hipGraph_t g = nullptr;
-    hipGraphExec_t exec = nullptr;
     HIPCHK(h, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    hipError_t e = enqueue_tick(h, slots, rows, trace, trace_rows, s, forced);
-    hipError_t e2 = hipStreamEndCapture(s, &g);
-    if (e != hipSuccess || e2 != hipSuccess) {
-        h->err = std::string("decode tick capture failed: ") + hipGetErrorString(e != hipSuccess ? e : e2);
+    hipGraph_t g = nullptr;
+    hipError_t e = enqueue();
+    const hipError_t e2 = hipStreamEndCapture(s, &g);
+    if (e == hipSuccess) e = e2;
+    const char* step = "capture";
+    if (e == hipSuccess) {
+        step = "instantiate";
+        e = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
+    }
+    if (g) hipGraphDestroy(g);
+    if (e != hipSuccess) {
+        *out = nullptr;
+        h->err = std::string(what) + " " + step + " failed: " + hipGetErrorString(e);
         return MNX_ERR_HIP;
     }
-    HIPCHK(h, hipGraphInstantiate(&exec, g, nullptr, nullptr, 0));
-    hipGraphDestroy(g);
-    h->graphs[key] = exec;
-    *out = exec;
     return MNX_OK;
 }
 
-static int run_ticks(mnx_engine* h, hipGraphExec_t exec, int slots, int rows, float* trace, int trace_rows, int n,
-                     hipStream_t s, const int* forced = nullptr) {
-    for (int i = 0; i < n; ++i) {
-        if (exec) HIPCHK(h, hipGraphLaunch(exec, s));
-        else HIPCHK(h, enqueue_tick(h, slots, rows, trace, trace_rows, s, forced));
+// The graph of one greedy tick, captured on first use and kept until mnx_destroy (null under MNX_NO_GRAPH)
+int get_tick_graph(mnx_engine* h, int slots, int rows, float* trace, int trace_rows, hipStream_t s, hipGraphExec_t* out,
+                   const int* forced = nullptr) {
+    *out = nullptr;
+    if (!h->use_graph) return MNX_OK;
+    const GraphKey key{slots, rows, trace ? trace_rows : 0, forced ? trace_rows : 0, tick_tile(h, rows)};
+    auto it = h->graphs.find(key);
+    if (it != h->graphs.end()) { *out = it->second; return MNX_OK; }
+    MNXCHK(capture_graph(h, "decode tick", s, [&]() { return enqueue_tick(h, slots, rows, trace, trace_rows, s, forced); }, out));
+    h->graphs[key] = *out;
+    return MNX_OK;
+}
+
+// The step loop of mnx_decode_greedy / beam search: up to max_len steps in groups of 8 (a replay of exec each, or — no
+// graph — enqueue()); after every group the begin kernel over `slots` slots counts the alive rows, the host reads the count
+// back and stops at 0
+template <typename F>
+int run_steps(mnx_engine* h, hipGraphExec_t exec, F&& enqueue, int slots, int max_len, hipStream_t s) {
+    for (int t = 0; t < max_len; t += 8) {
+        for (int i = 0; i < std::min(8, max_len - t); ++i) HIPCHK(h, exec ? hipGraphLaunch(exec, s) : enqueue());
+        HIPCHK(h, dec_enqueue_status(h->db, slots, s));
+        HIPCHK(h, hipMemcpyAsync(h->host_flag, &h->db.st->n_active, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));
+        if (*h->host_flag == 0) break;
     }
     return MNX_OK;
 }
 
-static int decode_greedy_impl(mnx_engine* h, const float* features, int32_t B, const int32_t* chunk_id, int32_t max_len,
-                              int32_t stop_on_eos, const int32_t* forced_ids, int32_t* tokens, int32_t* lengths,
-                              float* token_logp, float* hidden, float* logits_trace, void* stream) {
+int decode_greedy_impl(mnx_engine* h, const float* features, int32_t B, const int32_t* chunk_id, int32_t max_len,
+                       int32_t stop_on_eos, const int32_t* forced_ids, int32_t* tokens, int32_t* lengths, float* token_logp,
+                       float* hidden, float* logits_trace, void* stream) {
     if (!h) return MNX_ERR_INVALID_ARG;
     if (!features || !tokens || !lengths || B < 1) { h->err = "mnx_decode_greedy: null/empty argument"; return MNX_ERR_INVALID_ARG; }
     if (B > ROW_TILE || max_len < 1 || max_len > h->cfg.max_len) {
         h->err = "mnx_decode_greedy: B must be <= 32 and max_len <= cfg.max_len";
         return MNX_ERR_CAPACITY;
     }
-    hipStream_t s = (hipStream_t)stream;
     const mnx_config& c = h->cfg;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!s) {   // a default-flag stream synchronises implicitly with the null stream on both ends
-        if (!h->own_stream) HIPCHK(h, hipStreamCreate(&h->own_stream));
-        s = h->own_stream;
-    }
-    const int S = h->db.S, D = c.dec_dim;
-    // enc_transform, then the cross-attention K/V of all layers in one SGEMM (memory block i = row i)
-    HIPCHK(h, launch_sgemm_tn(features, h->dw.w_enc, h->dw.b_enc, h->db.memory, B * S, D, h->dw.enc_dim, s));
-    HIPCHK(h, launch_sgemm_tn(h->db.memory, h->dw.w_memkv, h->dw.b_memkv, h->db.mem_kv32, B * S, c.dec_layers * 2 * D, D, s, S));
-    HIPCHK(h, kvq_pack_enqueue(h->db.mem_kv32, h->db.mem_kv, B * c.dec_layers * 2 * c.dec_heads, S, h->db.Sq, s));
+    hipStream_t s;
+    MNXCHK(caller_stream(h, stream, &s));
+    MNXCHK(project_memory(h, features, B, 0, s));     // memory block i = row i
     HIPCHK(h, dec_enqueue_reset(h->db, s));
     HIPCHK(h, dec_enqueue_admit_rows(h->db, chunk_id, B, max_len, stop_on_eos, s));
     float* trace = nullptr;
     if (logits_trace) {
-        if (!h->out_trace) {
-            HIPCHK(h, hipMalloc((void**)&h->out_trace, (size_t)c.max_len * ROW_TILE * c.vocab * 4));
-            h->allocs.push_back(h->out_trace);
-            h->bytes += (size_t)c.max_len * ROW_TILE * c.vocab * 4;
-        }
+        MNXCHK(lazy_alloc(h, &h->out_trace, (size_t)c.max_len * ROW_TILE * c.vocab * 4));
         trace = h->out_trace;
     }
     const int* forced = nullptr;
     if (forced_ids) {    // teacher forcing: the caller's [B, max_len] ids, re-strided to the state's [slot][T] rows
-        if (!h->forced_ids) {
-            const size_t bytes = (size_t)ROW_TILE * c.max_len * 4;
-            HIPCHK(h, hipMalloc((void**)&h->forced_ids, bytes));
-            h->allocs.push_back(h->forced_ids);
-            h->bytes += bytes;
-        }
+        MNXCHK(lazy_alloc(h, &h->forced_ids, (size_t)ROW_TILE * c.max_len * 4));
         HIPCHK(h, hipMemcpy2DAsync(h->forced_ids, (size_t)h->db.T * 4, forced_ids, (size_t)max_len * 4, (size_t)max_len * 4, B,
                                    hipMemcpyDeviceToDevice, s));
         forced = h->forced_ids;
     }
     hipGraphExec_t exec = nullptr;
-    int rc = get_tick_graph(h, ROW_TILE, ROW_TILE, trace, B, s, &exec, forced);
-    if (rc != MNX_OK) return rc;
-    const int poll = 8;
-    for (int t = 0; t < max_len;) {
-        const int n = std::min(poll, max_len - t);
-        rc = run_ticks(h, exec, ROW_TILE, ROW_TILE, trace, B, n, s, forced);
-        if (rc != MNX_OK) return rc;
-        t += n;
-        HIPCHK(h, dec_enqueue_status(h->db, ROW_TILE, s));
-        HIPCHK(h, hipMemcpyAsync(h->host_flag, &h->db.st->n_active, sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-        if (*h->host_flag == 0) break;
-    }
+    MNXCHK(get_tick_graph(h, ROW_TILE, ROW_TILE, trace, B, s, &exec, forced));
+    MNXCHK(run_steps(h, exec, [&]() { return enqueue_tick(h, ROW_TILE, ROW_TILE, trace, B, s, forced); }, ROW_TILE, max_len, s));
     HIPCHK(h, gather_enqueue(h->db, nullptr, B, max_len, tokens, lengths, token_logp, hidden, s));
     if (logits_trace) HIPCHK(h, hipMemcpyAsync(logits_trace, trace, (size_t)max_len * B * c.vocab * 4, hipMemcpyDeviceToDevice, s));
     HIPCHK(h, hipStreamSynchronize(s));
     return MNX_OK;
 }
+
+// Beam search over G reference batches in ONE step sequence: batch g = images [g ref_batch, (g + 1) ref_batch) of n_total
+// (features at feats[g]), every image K hypotheses, one row per hypothesis — G x ref_batch x K rows per step. Images are
+// independent; the positional-encoding rows are numbered inside each reference batch (beam_begin_kernel), so the result is
+// that of G separate searches. Outputs [n_total, n_best, ...].
+int decode_beam_groups(mnx_engine* h, const float* const* feats, int G, int ref_batch, int n_total, int beam, int n_best,
+                       int max_len, int32_t* tokens, int32_t* lengths, float* scores, float* hidden, hipStream_t s) {
+    const int D = h->cfg.dec_dim, T = h->db.T, B = n_total;
+    BeamBuffers& bm = h->beam;
+    // capacities: MAX_BEAM_IMGS images x MAX_BEAM hypotheses of state; 256 kept hypotheses (32 images x 8 ... 256 x 1)
+    constexpr int POOL = ROW_TILE * MAX_BEAM;
+    const int pool_stride = std::min(MAX_BEAM, POOL / B);
+    if (pool_stride < n_best) { h->err = "beam search: n_best x images exceeds the hypothesis pool (256)"; return MNX_ERR_CAPACITY; }
+    MNXCHK(lazy_alloc(h, &bm.bs, sizeof(BeamState)));
+    MNXCHK(lazy_alloc(h, &bm.blp, (size_t)MAX_BEAM_IMGS * MAX_BEAM * BEAM_LP_STRIDE * 4));
+    MNXCHK(lazy_alloc(h, &bm.anc, (size_t)MAX_BEAM_IMGS * MAX_BEAM * (T + 1) * 4));
+    MNXCHK(lazy_alloc(h, &bm.ptok, (size_t)POOL * T * 4));
+    if (hidden) MNXCHK(lazy_alloc(h, &bm.phid, (size_t)POOL * T * D * 4));
+    bm.B = B; bm.K = beam; bm.n_best = n_best; bm.anc_stride = T + 1; bm.ref_batch = ref_batch; bm.pool_stride = pool_stride;
+    BeamBuffers run = bm;
+    if (!hidden) run.phid = nullptr;
+    for (int g = 0; g < G; ++g)      // memory of batch g -> memory blocks g ref_batch ...
+        MNXCHK(project_memory(h, feats[g], std::min(ref_batch, B - g * ref_batch), g * ref_batch, s));
+    HIPCHK(h, dec_enqueue_reset(h->db, s));
+    HIPCHK(h, beam_enqueue_init(h->db, run, max_len, s));
+    const int rows = (B * beam + ROW_TILE - 1) / ROW_TILE * ROW_TILE;
+    // one step = begin + 6 layers + head + pick, captured once per call (its arguments depend on B / beam / n_best)
+    auto step = [&]() { return dec_enqueue_tick(h->dw, h->db, rows, rows, nullptr, 0, s, &run); };
+    hipGraphExec_t exec = nullptr;
+    if (h->use_graph) MNXCHK(capture_graph(h, "beam step", s, step, &exec));
+    struct ExecGuard {      // the per-call graph is released on every exit path
+        hipGraphExec_t e;
+        ~ExecGuard() { if (e) hipGraphExecDestroy(e); }
+    } guard{exec};
+    MNXCHK(run_steps(h, exec, step, rows, max_len, s));
+    HIPCHK(h, beam_enqueue_gather(h->db, run, max_len, tokens, lengths, scores, hidden, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    return MNX_OK;
+}
+
+}  // namespace
+
+extern "C" {
 
 int mnx_decode_greedy(mnx_engine* h, const float* features, int32_t B, const int32_t* chunk_id, int32_t max_len,
                       int32_t stop_on_eos, int32_t* tokens, int32_t* lengths, float* token_logp, float* hidden,
@@ -1018,83 +1084,6 @@ int mnx_decode_forced(mnx_engine* h, const float* features, int32_t B, const int
                               logits_trace, stream);
 }
 
-// Beam search over G reference batches in ONE step sequence: batch g = images [g ref_batch, (g + 1) ref_batch) of n_total
-// (features at feats[g]), every image K hypotheses, one row per hypothesis — G x ref_batch x K rows per step. Images are
-// independent; the positional-encoding rows are numbered inside each reference batch (beam_begin_kernel), so the result is
-// that of G separate searches. Outputs [n_total, n_best, ...].
-static int decode_beam_groups(mnx_engine* h, const float* const* feats, int G, int ref_batch, int n_total, int beam, int n_best,
-                              int max_len, int32_t* tokens, int32_t* lengths, float* scores, float* hidden, hipStream_t s) {
-    const mnx_config& c = h->cfg;
-    const int S = h->db.S, D = c.dec_dim, T = h->db.T, B = n_total;
-    BeamBuffers& bm = h->beam;
-    auto lazy = [&](void** p, size_t bytes) -> hipError_t {
-        if (*p) return hipSuccess;
-        hipError_t e = hipMalloc(p, bytes);
-        if (e == hipSuccess) { h->allocs.push_back(*p); h->bytes += bytes; }
-        return e;
-    };
-    // capacities: MAX_BEAM_IMGS images x MAX_BEAM hypotheses of state; 256 kept hypotheses (32 images x 8 ... 256 x 1)
-    constexpr int POOL = ROW_TILE * MAX_BEAM;
-    const int pool_stride = std::min(MAX_BEAM, POOL / B);
-    if (pool_stride < n_best) { h->err = "beam search: n_best x images exceeds the hypothesis pool (256)"; return MNX_ERR_CAPACITY; }
-    HIPCHK(h, lazy((void**)&bm.bs, sizeof(BeamState)));
-    HIPCHK(h, lazy((void**)&bm.blp, (size_t)MAX_BEAM_IMGS * MAX_BEAM * BEAM_LP_STRIDE * 4));
-    HIPCHK(h, lazy((void**)&bm.anc, (size_t)MAX_BEAM_IMGS * MAX_BEAM * (T + 1) * 4));
-    HIPCHK(h, lazy((void**)&bm.ptok, (size_t)POOL * T * 4));
-    if (hidden) HIPCHK(h, lazy((void**)&bm.phid, (size_t)POOL * T * D * 4));
-    bm.B = B; bm.K = beam; bm.n_best = n_best; bm.anc_stride = T + 1; bm.ref_batch = ref_batch; bm.pool_stride = pool_stride;
-    BeamBuffers run = bm;
-    if (!hidden) run.phid = nullptr;
-    for (int g = 0; g < G; ++g) {      // enc_transform + memory K / V of batch g -> memory blocks g ref_batch ...
-        const int n = std::min(ref_batch, B - g * ref_batch);
-        char* memkv = h->db.mem_kv + (size_t)g * ref_batch * c.dec_layers * 2 * c.dec_heads * kvq_block_bytes(h->db.Sq);
-        HIPCHK(h, launch_sgemm_tn(feats[g], h->dw.w_enc, h->dw.b_enc, h->db.memory, n * S, D, h->dw.enc_dim, s));
-        HIPCHK(h, launch_sgemm_tn(h->db.memory, h->dw.w_memkv, h->dw.b_memkv, h->db.mem_kv32, n * S, c.dec_layers * 2 * D, D, s, S));
-        HIPCHK(h, kvq_pack_enqueue(h->db.mem_kv32, memkv, n * c.dec_layers * 2 * c.dec_heads, S, h->db.Sq, s));
-    }
-    HIPCHK(h, dec_enqueue_reset(h->db, s));
-    HIPCHK(h, beam_enqueue_init(h->db, run, max_len, s));
-    const int rows = (B * beam + ROW_TILE - 1) / ROW_TILE * ROW_TILE;
-    // one step = begin + 6 layers + head + pick, captured once per call (its arguments depend on B / beam / n_best)
-    hipGraph_t g = nullptr;
-    hipGraphExec_t exec = nullptr;
-    if (h->use_graph) {
-        HIPCHK(h, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        hipError_t e = dec_enqueue_tick(h->dw, h->db, rows, rows, nullptr, 0, s, &run);
-        hipError_t e2 = hipStreamEndCapture(s, &g);
-        if (e != hipSuccess || e2 != hipSuccess) {
-            h->err = std::string("beam step capture failed: ") + hipGetErrorString(e != hipSuccess ? e : e2);
-            return MNX_ERR_HIP;
-        }
-        HIPCHK(h, hipGraphInstantiate(&exec, g, nullptr, nullptr, 0));
-        hipGraphDestroy(g);
-    }
-    struct ExecGuard {      // the per-call graph is released on every exit path
-        hipGraphExec_t& e;
-        ~ExecGuard() { if (e) { hipGraphExecDestroy(e); e = nullptr; } }
-    } guard{exec};
-    int rc = MNX_OK;
-    const int poll = 8;
-    for (int t = 0; t < max_len && rc == MNX_OK;) {
-        const int n = std::min(poll, max_len - t);
-        for (int i = 0; i < n; ++i) {
-            hipError_t e = exec ? hipGraphLaunch(exec, s) : dec_enqueue_tick(h->dw, h->db, rows, rows, nullptr, 0, s, &run);
-            if (e != hipSuccess) { h->err = std::string("beam step: ") + hipGetErrorString(e); rc = MNX_ERR_HIP; break; }
-        }
-        if (rc != MNX_OK) break;
-        t += n;
-        hipError_t e = dec_enqueue_status(h->db, rows, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(h->host_flag, &h->db.st->n_active, sizeof(int), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { h->err = std::string("beam poll: ") + hipGetErrorString(e); rc = MNX_ERR_HIP; break; }
-        if (*h->host_flag == 0) break;
-    }
-    if (rc != MNX_OK) return rc;
-    HIPCHK(h, beam_enqueue_gather(h->db, run, max_len, tokens, lengths, scores, hidden, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    return MNX_OK;
-}
-
 int mnx_decode_beam(mnx_engine* h, const float* features, int32_t B, int32_t beam, int32_t n_best, int32_t max_len,
                     int32_t* tokens, int32_t* lengths, float* scores, float* hidden, void* stream) {
     if (!h) return MNX_ERR_INVALID_ARG;
@@ -1108,12 +1097,8 @@ int mnx_decode_beam(mnx_engine* h, const float* features, int32_t B, int32_t bea
         h->err = "mnx_decode_beam: B <= 32, 1 <= n_best <= beam <= 8, max_len <= cfg.max_len (<= 511), B x beam <= dec_slots required";
         return MNX_ERR_CAPACITY;
     }
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!s) {
-        if (!h->own_stream) HIPCHK(h, hipStreamCreate(&h->own_stream));
-        s = h->own_stream;
-    }
+    hipStream_t s;
+    MNXCHK(caller_stream(h, stream, &s));
     return decode_beam_groups(h, &features, 1, B, B, beam, n_best, max_len, tokens, lengths, scores, hidden, s);
 }
 
@@ -1134,71 +1119,40 @@ int mnx_predict_beam(mnx_engine* h, const float* images, int32_t n_img, int32_t 
                  "ref_batch x beam <= dec_slots required";
         return MNX_ERR_CAPACITY;
     }
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!s) {
-        if (!h->own_stream) HIPCHK(h, hipStreamCreate(&h->own_stream));
-        s = h->own_stream;
-    }
-    const int S = h->db.S, D = c.dec_dim;
-    const size_t img_elems = (size_t)3 * c.img_size * c.img_size;
+    hipStream_t s;
+    MNXCHK(caller_stream(h, stream, &s));
+    const int D = c.dec_dim;
     // Reference batches searched together (one step sequence, decode_beam_groups): up to MNX_BEAM_GROUPS (default 8) batches
     // of one encoder launch group — a step of 4 x 160 rows costs 1.5x a step of 160 —, bounded by the state
     // capacity (MAX_BEAM_IMGS images, dec_slots rows) and by the memory blocks
     int g_max = 8;
     if (const char* e = getenv("MNX_BEAM_GROUPS")) g_max = std::max(1, atoi(e));
     g_max = std::max(1, std::min({g_max, MAX_BEAM_IMGS / ref_batch, h->db.slots / (ref_batch * beam), h->db.mem_blocks / ref_batch}));
-    if (!h->beam_hidden) {      // decoder outputs along the winning hypotheses of the reference batches of one search
-        const size_t bytes = (size_t)MAX_BEAM_IMGS * c.max_len * D * 4;
-        HIPCHK(h, hipMalloc((void**)&h->beam_hidden, bytes));
-        h->allocs.push_back(h->beam_hidden);
-        h->bytes += bytes;
-    }
-    struct ExitGuard {          // every exit path: nothing of this call may still be in flight
-        mnx_engine* h; hipStream_t s;
-        ~ExitGuard() { (void)hipStreamSynchronize(h->enc_stream); (void)hipStreamSynchronize(s); }
-    } exit_guard{h, s};
+    // decoder outputs along the winning hypotheses of the reference batches of one search
+    MNXCHK(lazy_alloc(h, &h->beam_hidden, (size_t)MAX_BEAM_IMGS * c.max_len * D * 4));
+    DrainGuard drain{h, s};
     // the encoder stream must not start before the caller's stream reaches this point (images ready)
     HIPCHK(h, hipMemsetAsync(h->enc_flag, 0, sizeof(int), s));     // the range flag is per call (see mnx_predict)
     HIPCHK(h, hipEventRecord(h->ev_poll[0], s));
     HIPCHK(h, hipStreamWaitEvent(h->enc_stream, h->ev_poll[0], 0));
     const int n_chunks = (n_img + ref_batch - 1) / ref_batch;
-    const int grp = std::max(1, c.max_batch / ref_batch);      // reference batches per encoder launch group
-    int fb_first[2] = {-1, -1}, fb_count[2] = {0, 0};
-    bool feat_used[2] = {false, false};
-    int next_enc = 0;
+    FeatRing ring{h, images, n_img, ref_batch, n_chunks, std::max(1, c.max_batch / ref_batch)};
     for (int ck = 0; ck < n_chunks;) {
         // keep both feature buffers busy on the encoder stream: the encoder of the following groups runs while the
         // beam search of these reference batches occupies the caller's stream
-        for (int fb = 0; fb < 2; ++fb) {
-            if (fb_first[fb] >= 0 || next_enc >= n_chunks) continue;
-            const int cnt = std::min(grp, n_chunks - next_enc);
-            const int first = next_enc * ref_batch, n = std::min(cnt * ref_batch, n_img - first);
-            if (feat_used[fb]) HIPCHK(h, hipStreamWaitEvent(h->enc_stream, h->ev_feat_free[fb], 0));
-            const int rc = mnx_encode(h, images + (size_t)first * img_elems, n, h->feat_ring[fb], h->enc_stream);
-            if (rc != MNX_OK) return rc;
-            HIPCHK(h, hipEventRecord(h->ev_enc_done[fb], h->enc_stream));
-            fb_first[fb] = next_enc; fb_count[fb] = cnt; next_enc += cnt;
-        }
-        int fb = -1;
-        for (int i = 0; i < 2; ++i)
-            if (fb_first[i] >= 0 && ck >= fb_first[i] && ck < fb_first[i] + fb_count[i]) fb = i;
+        MNXCHK(ring.refill());
+        const int fb = ring.find(ck);
         if (fb < 0) { h->err = "mnx_predict_beam: internal: reference batch without features"; return MNX_ERR_HIP; }
         // the next G reference batches of this feature buffer, searched together
-        const int G = std::min(g_max, fb_first[fb] + fb_count[fb] - ck);
+        const int G = std::min(g_max, ring.end(fb) - ck);
         const int first = ck * ref_batch, n = std::min(G * ref_batch, n_img - first);
         HIPCHK(h, hipStreamWaitEvent(s, h->ev_enc_done[fb], 0));
         const float* feats[MAX_BEAM_IMGS];
-        for (int g = 0; g < G; ++g) feats[g] = h->feat_ring[fb] + (size_t)(ck + g - fb_first[fb]) * ref_batch * S * h->dw.enc_dim;
+        for (int g = 0; g < G; ++g) feats[g] = ring.feats(fb, ck + g);
         int32_t* tok = tokens + (size_t)first * max_len;
-        int rc = decode_beam_groups(h, feats, G, ref_batch, n, beam, 1, max_len, tok, lengths + first, scores + first, h->beam_hidden, s);
-        if (rc != MNX_OK) return rc;
+        MNXCHK(decode_beam_groups(h, feats, G, ref_batch, n, beam, 1, max_len, tok, lengths + first, scores + first, h->beam_hidden, s));
         ck += G;
-        if (ck == fb_first[fb] + fb_count[fb]) {     // last reference batch of the group: the buffer is free again
-            HIPCHK(h, hipEventRecord(h->ev_feat_free[fb], s));
-            feat_used[fb] = true;
-            fb_first[fb] = -1;
-        }
+        if (ck == ring.end(fb)) MNXCHK(ring.release(fb, s));     // last reference batch of the group: the buffer is free again
         int32_t* aidx = atom_idx + (size_t)first * kmax;
         HIPCHK(h, atoms_enqueue_raw(h->tc_dev, tok, lengths + first, n, max_len, kmax, aidx, n_atoms + first, s));
         for (int o = 0; o < n; o += ROW_TILE) {      // the bond head's scratch holds one reference batch
@@ -1313,14 +1267,8 @@ static int predict_impl(mnx_engine* h, const char* name, const float* images, in
         h->err = std::string(name) + ": 1 <= ref_batch, max_len <= cfg.max_len, kmax <= cfg.max_atoms required";
         return MNX_ERR_CAPACITY;
     }
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!s) {
-        if (!h->own_stream) HIPCHK(h, hipStreamCreate(&h->own_stream));
-        s = h->own_stream;
-    }
-    const int S = h->db.S, D = c.dec_dim;
-    const size_t img_elems = (size_t)3 * c.img_size * c.img_size;
+    hipStream_t s;
+    MNXCHK(caller_stream(h, stream, &s));
     const int n_chunks = (n_img + ref_batch - 1) / ref_batch;
     // A chunk (one reference batch) holds ceil(n / 32) row tiles, not necessarily contiguous; tile j holds its rows
     // 32 j .. 32 j + 31 in slots tile * 32 + i, memory K/V blocks likewise, and its slot list at slot_lists[tile]. The chunk's
@@ -1331,7 +1279,6 @@ static int predict_impl(mnx_engine* h, const char* name, const float* images, in
     for (int i = h->n_chunk_bufs - 1; i >= 0; --i) free_tiles.push_back(i);
     int* pinned = h->host_flag;                       // [2][1 + MAX_CHUNKS] snapshots, then slot lists per tile
     int* pin_slots = h->host_flag + 2 * (1 + MAX_CHUNKS);
-    int rc = MNX_OK;
     int bound = 0;                                    // upper bound of alive rows (host-side, conservative)
     std::vector<std::pair<int, int>> admits;          // (iteration, rows) of every admission
     HIPCHK(h, dec_enqueue_reset(h->db, s));
@@ -1344,44 +1291,21 @@ static int predict_impl(mnx_engine* h, const char* name, const float* images, in
     int next = 0, done = 0, seq = 0;
     const char* trace_path = getenv("MNX_TRACE");
     FILE* tf = trace_path ? fopen(trace_path, "a") : nullptr;
-    struct ExitGuard {      // every exit path: nothing of this call may still be in flight, the trace file is closed
-        mnx_engine* h; hipStream_t s; FILE*& tf;
-        ~ExitGuard() {
-            (void)hipStreamSynchronize(h->enc_stream);
-            (void)hipStreamSynchronize(s);
-            if (tf) { fclose(tf); tf = nullptr; }
-        }
-    } exit_guard{h, s, tf};
+    const std::unique_ptr<FILE, int (*)(FILE*)> tf_close(tf, fclose);   // closed on every exit path, after the drain
+    DrainGuard drain{h, s};
     auto now_ms = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
     const double t_begin = now_ms();
     double host_wait_ms = 0.0;
-    int next_enc = 0;                       // next chunk to hand to the encoder stream
-    // the encoder is batch-invariant, so it runs on GROUPS of reference batches (as many as max_batch holds):
-    // bigger GEMM grids, half the launches; each reference batch of the group is admitted on its own
-    const int grp = std::max(1, c.max_batch / ref_batch);
-    int fb_first[2] = {-1, -1}, fb_count[2] = {0, 0};   // chunks [first, first+count) live in feature buffer i
-    bool feat_used[2] = {false, false};
+    // each reference batch of an encoder group is admitted on its own
+    FeatRing ring{h, images, n_img, ref_batch, n_chunks, std::max(1, c.max_batch / ref_batch)};
     const int ticks_per_poll = 4;            // measured: 2-4 equal, 8 = -4 % (retirement lags)
     while (done < n_chunks) {
         // ---- encoder prefetch: keep both feature buffers busy on the encoder stream
-        for (int fb = 0; fb < 2; ++fb) {
-            if (fb_first[fb] >= 0 || next_enc >= n_chunks) continue;
-            const int cnt = std::min(grp, n_chunks - next_enc);
-            const int first = next_enc * ref_batch, n = std::min(cnt * ref_batch, n_img - first);
-            if (feat_used[fb]) HIPCHK(h, hipStreamWaitEvent(h->enc_stream, h->ev_feat_free[fb], 0));
-            rc = mnx_encode(h, images + (size_t)first * img_elems, n, h->feat_ring[fb], h->enc_stream);
-            if (rc != MNX_OK) return rc;
-            HIPCHK(h, hipEventRecord(h->ev_enc_done[fb], h->enc_stream));
-            fb_first[fb] = next_enc;
-            fb_count[fb] = cnt;
-            next_enc += cnt;
-        }
+        MNXCHK(ring.refill());
         // ---- admission (in image order): only once the chunk's features are READY, so the decode stream never
         //      waits for the encoder; project the memory and admit on the decode stream
         while (next < n_chunks) {
-            int fb = -1;
-            for (int i = 0; i < 2; ++i)
-                if (fb_first[i] >= 0 && next >= fb_first[i] && next < fb_first[i] + fb_count[i]) fb = i;
+            const int fb = ring.find(next);
             if (fb < 0) break;
             const int first = next * ref_batch, n = std::min(ref_batch, n_img - first);
             const int n_tiles = (n + ROW_TILE - 1) / ROW_TILE;
@@ -1398,18 +1322,10 @@ static int predict_impl(mnx_engine* h, const char* name, const float* images, in
             HIPCHK(h, hipStreamWaitEvent(s, h->ev_enc_done[fb], 0));   // already complete: ordering only
             // memory projection tile by tile: the fp32 scratch (db.memory, db.mem_kv32) holds 32 rows
             for (int j = 0; j < n_tiles; ++j) {
-                const int tile = ck.tiles[j], nj = std::min(ROW_TILE, n - j * ROW_TILE);
-                char* memkv = h->db.mem_kv + (size_t)tile * ROW_TILE * c.dec_layers * 2 * c.dec_heads * kvq_block_bytes(h->db.Sq);
-                const float* feats = h->feat_ring[fb] + ((size_t)(next - fb_first[fb]) * ref_batch + (size_t)j * ROW_TILE) * S * h->dw.enc_dim;
-                HIPCHK(h, launch_sgemm_tn(feats, h->dw.w_enc, h->dw.b_enc, h->db.memory, nj * S, D, h->dw.enc_dim, s));
-                HIPCHK(h, launch_sgemm_tn(h->db.memory, h->dw.w_memkv, h->dw.b_memkv, h->db.mem_kv32, nj * S, c.dec_layers * 2 * D, D, s, S));
-                HIPCHK(h, kvq_pack_enqueue(h->db.mem_kv32, memkv, nj * c.dec_layers * 2 * c.dec_heads, S, h->db.Sq, s));
+                const float* feats = ring.feats(fb, next) + (size_t)j * ROW_TILE * h->db.S * h->dw.enc_dim;
+                MNXCHK(project_memory(h, feats, std::min(ROW_TILE, n - j * ROW_TILE), ck.tiles[j] * ROW_TILE, s));
             }
-            if (next + 1 == fb_first[fb] + fb_count[fb]) {    // last reference batch of the group: buffer is free again
-                HIPCHK(h, hipEventRecord(h->ev_feat_free[fb], s));
-                feat_used[fb] = true;
-                fb_first[fb] = -1;
-            }
+            if (next + 1 == ring.end(fb)) MNXCHK(ring.release(fb, s));   // last reference batch of the group: buffer is free again
             // every tile of the chunk is admitted before the next tick, rows 32 j + i under the chunk's one tag
             for (int j = 0; j < n_tiles; ++j) {
                 const int tile = ck.tiles[j], nj = std::min(ROW_TILE, n - j * ROW_TILE);
@@ -1439,10 +1355,9 @@ static int predict_impl(mnx_engine* h, const char* name, const float* images, in
             for (int t : ck.tiles) hi_tile = std::max(hi_tile, t);
         const int scan = std::min(SL, std::max(((hi_tile + 1) * ROW_TILE + 1023) / 1024 * 1024, rows_cap));
         hipGraphExec_t exec = nullptr;
-        rc = get_tick_graph(h, scan, rows_cap, nullptr, 0, s, &exec);
-        if (rc != MNX_OK) return rc;
-        rc = run_ticks(h, exec, scan, rows_cap, nullptr, 0, ticks_per_poll, s);
-        if (rc != MNX_OK) return rc;
+        MNXCHK(get_tick_graph(h, scan, rows_cap, nullptr, 0, s, &exec));
+        for (int i = 0; i < ticks_per_poll; ++i)
+            HIPCHK(h, exec ? hipGraphLaunch(exec, s) : enqueue_tick(h, scan, rows_cap, nullptr, 0, s, nullptr));
         HIPCHK(h, dec_enqueue_status(h->db, scan, s));
         int* snap = pinned + (seq & 1) * (1 + MAX_CHUNKS);
         HIPCHK(h, hipMemcpyAsync(snap, &h->db.st->n_active, (size_t)(1 + MAX_CHUNKS) * 4, hipMemcpyDeviceToHost, s));
@@ -1490,7 +1405,7 @@ static int predict_impl(mnx_engine* h, const char* name, const float* images, in
             }
         }
         if (tf) fprintf(tf, "%.3f seq %d live %zu next %d next_enc %d done %d free_tiles %zu\n", now_ms() - t_begin, seq,
-                        live.size(), next, next_enc, done, free_tiles.size());
+                        live.size(), next, ring.next_enc, done, free_tiles.size());
         ++seq;
         if (seq > 200000) { h->err = std::string(name) + ": watchdog (decode did not terminate)"; return MNX_ERR_HIP; }
     }
