@@ -145,7 +145,9 @@ int mnx_set_split_terms(mnx_engine* h, int32_t mask);
 /* compute_dtype FP16X3 / FP16X3M only: the Linear op classes (MNX_OP_* bits, not MNX_OP_ATTN) of encoder stage `stage`
  * (0-based; -1 = every stage) that run on TWO terms (ah.wh + ah.wl) in the Swin blocks first_block .. last_block of the stage
  * (0-based, last_block may exceed the depth; the patch-merging reduction counts as the stage's last block). FP16X3 starts
- * with none, FP16X3M with MNX_FP16X3M_TWO_TERM_BY_STAGE from MNX_FP16X3M_FIRST_BLOCK_BY_STAGE on; the weights are the same in both, so one engine can be measured under several tables
+ * with none, FP16X3M with MNX_FP16X3M_TWO_TERM_BY_STAGE from MNX_FP16X3M_FIRST_BLOCK_BY_STAGE on (an encoder of fewer than
+ * four stages takes the table's last n_stages rows). two_term_mask = -1 reinstalls that starting table on `stage` (-1: every
+ * stage; first_block / last_block are ignored). The weights are the same in both, so one engine can be measured under several tables
  * (tests/test_gpu_pixels.py; tools/study_split_terms.py is the CPU emulation). A 16-bit activation whose only consumer runs on
  * two terms is written as one plane. Takes effect at the next mnx_encode / mnx_predict call; not to be changed while one is
  * in flight. */

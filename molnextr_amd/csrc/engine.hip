@@ -264,6 +264,18 @@ int check_cfg(const mnx_config& c, std::string& why) {
     return MNX_OK;
 }
 
+// the compute_dtype's own two-term table on encoder stage st: none, or for FP16X3M the header's
+// MNX_FP16X3M_TWO_TERM_BY_STAGE / _FIRST_BLOCK_BY_STAGE, written for Swin-B's four stages — a shallower encoder (the tests'
+// tiny one) keeps its LAST stages' rows
+void install_mode_terms(mnx_engine* h, int st) {
+    const int by_stage[4] = MNX_FP16X3M_TWO_TERM_BY_STAGE, first[4] = MNX_FP16X3M_FIRST_BLOCK_BY_STAGE;
+    const bool m = h->cfg.compute_dtype == MNX_DTYPE_FP16X3M;
+    const int row = st + 4 - h->cfg.n_stages;
+    h->two_mask[st] = m ? by_stage[row] : 0;
+    h->two_first[st] = m ? first[row] : 0;
+    h->two_last[st] = 1 << 30;
+}
+
 }  // namespace
 
 extern "C" {
@@ -321,36 +333,11 @@ int mnx_create(const mnx_config* cfg, const mnx_weight_desc* weights, int32_t n_
     mnx_engine* h = new mnx_engine();
     h->cfg = *cfg;
     h->device = device;
-    // FP16X3M = the FP16X3 kernels and weights with the op classes of MNX_FP16X3M_TWO_TERM on two product terms
+    // FP16X3M = the FP16X3 kernels and weights with the op classes of MNX_FP16X3M_TWO_TERM_BY_STAGE on two product terms
     h->dt = cfg->compute_dtype == MNX_DTYPE_FP16X3M ? MNX_DT_F16X3 : cfg->compute_dtype;
-    if (cfg->compute_dtype == MNX_DTYPE_FP16X3M) {
-        const int by_stage[4] = MNX_FP16X3M_TWO_TERM_BY_STAGE;
-        // the table is written for Swin-B's four stages; a shallower encoder (the tests' tiny one) keeps its LAST stages' rows
-        const int first[4] = MNX_FP16X3M_FIRST_BLOCK_BY_STAGE;
-        for (int st = 0; st < cfg->n_stages; ++st) {
-            h->two_mask[st] = by_stage[st + 4 - cfg->n_stages];
-            h->two_first[st] = first[st + 4 - cfg->n_stages];
-        }
-    }
+    for (int st = 0; st < cfg->n_stages; ++st) install_mode_terms(h, st);
     const char* ng = getenv("MNX_NO_GRAPH");
     h->use_graph = !(ng && ng[0] == '1');
-    // MNX_ENC_CUS=n (default 256): the encoder's persistent kernels (gemm256x3_kernel: one 150 KB-LDS workgroup per CU for the
-    // length of a launch; window_attn_pipe_kernel: two) are launched on n workgroups (2 n), so that 256 - n CUs stay free for
-    // the decode stream's kernels while they run (DESIGN.md "co-residency": measured, not a win). The count is process-wide
-    // (gemm256.hip keeps it) and is set by EVERY mnx_create: an engine created without the variable restores 256, so that no
-    // engine inherits another one's value.
-    {
-        int n = 256;
-        if (const char* e = getenv("MNX_ENC_CUS")) {
-            n = atoi(e);
-            if (n < 64 || n > 256) {
-                g_create_error = "mnx_create: MNX_ENC_CUS must be 64..256";
-                delete h;
-                return MNX_ERR_INVALID_ARG;
-            }
-        }
-        set_persistent_cus(n);
-    }
     if (const char* e = getenv("MNX_DEC_TILE")) h->dec_tile = atoi(e);              // 0: never use the fused tick
     if (const char* e = getenv("MNX_DEC_TILE_FF")) h->dec_tile_ff = atoi(e);
     if (const char* e = getenv("MNX_DEC_FUSED_MAX")) h->dec_fused_max = atoi(e);    // largest capacity that runs fused
@@ -688,8 +675,13 @@ int mnx_set_op_terms(mnx_engine* h, int32_t stage, int32_t two_term_mask, int32_
     if (!h) return MNX_ERR_INVALID_ARG;
     if (h->dt != MNX_DT_F16X3) { h->err = "mnx_set_op_terms: compute_dtype must be FP16X3 or FP16X3M"; return MNX_ERR_INVALID_ARG; }
     if (stage < -1 || stage >= h->cfg.n_stages) { h->err = "mnx_set_op_terms: stage must be -1 (all) or 0..n_stages-1"; return MNX_ERR_INVALID_ARG; }
+    if (two_term_mask == -1) {      // the mode's own table (first_block / last_block ignored)
+        for (int st = 0; st < h->cfg.n_stages; ++st)
+            if (stage < 0 || stage == st) install_mode_terms(h, st);
+        return MNX_OK;
+    }
     if (two_term_mask < 0 || two_term_mask > SPL_ALL || (two_term_mask & SPL_ATTN)) {
-        h->err = "mnx_set_op_terms: mask must be a subset of the Linear classes (1 qkv, 4 proj, 8 fc1, 16 fc2, 32 merge)";
+        h->err = "mnx_set_op_terms: mask must be -1 (the mode's own table) or a subset of the Linear classes (1 qkv, 4 proj, 8 fc1, 16 fc2, 32 merge)";
         return MNX_ERR_INVALID_ARG;
     }
     if (first_block < 0 || last_block < first_block) { h->err = "mnx_set_op_terms: 0 <= first_block <= last_block required"; return MNX_ERR_INVALID_ARG; }

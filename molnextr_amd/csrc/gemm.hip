@@ -508,12 +508,16 @@ static hipError_t launch_t(int epi, const void* A, const void* W, void* C, const
     return launch_bn<T, 128, SPLIT>(epi, A, W, C, bias, resid, M, N, K, s, sp);
 }
 
+// the bias epilogue always writes both planes: its consumer (qkv -> window attention) runs on three terms
+static bool one_plane_bias(int epi, const SplitArgs* sp) { return epi == EPI_BIAS_16 && sp && sp->c_planes == 1; }
+
 hipError_t launch_gemm16_tile128(int dtype, int epi, const void* A, const void* W, void* C, const float* bias,
                                  const float* resid, int M, int N, int K, hipStream_t s, const SplitArgs* sp) {
     if ((K & 7) || (N & 7) || M <= 0) return hipErrorInvalidValue;
     if (dtype == MNX_DT_F32) return launch_f32(epi, A, W, C, bias, resid, M, N, K, s);
     if (dt_split(dtype)) {
-        if (!sp || sp->terms < 1 || sp->terms > 3 || (sp->c_planes != 1 && sp->c_planes != 2)) return hipErrorInvalidValue;
+        if (!sp || sp->terms < 1 || sp->terms > 3 || (sp->c_planes != 1 && sp->c_planes != 2) || one_plane_bias(epi, sp))
+            return hipErrorInvalidValue;
         return dtype == MNX_DT_F16X3 ? launch_t<f16_t, true>(epi, A, W, C, bias, resid, M, N, K, s, *sp)
                                      : launch_t<bf16_t, true>(epi, A, W, C, bias, resid, M, N, K, s, *sp);
     }
@@ -525,7 +529,7 @@ hipError_t launch_gemm16_tile128(int dtype, int epi, const void* A, const void* 
 // rows that launch_gemm16 gives to gemm256x3_kernel (the rest goes to the 128x128 kernel); 0 = none
 static int x3_main_rows(int dtype, int epi, int M, int N, int K, int terms) {
     if (!dt_split(dtype) || (terms != 3 && !(terms == 2 && dtype == MNX_DT_F16X3)) || !gemm256x3_supports(dtype, epi, M, N, K)) return 0;
-    const int tn = N / 256, tm = M / 256, tiles = tm * tn, cus = persistent_cus();
+    const int tn = N / 256, tm = M / 256, tiles = tm * tn, cus = PERSISTENT_CUS;
     int tm_main = tm;
     if (tiles % cus != 0 && (tiles % cus) * 10 < cus * 8) tm_main = (tiles / cus) * cus / tn;
     return tm_main * 256;
@@ -542,6 +546,7 @@ const char* gemm16_route(int dtype, int epi, int M, int N, int K, int terms, boo
 
 hipError_t launch_gemm16(int dtype, int epi, const void* A, const void* W, void* C, const float* bias,
                          const float* resid, int M, int N, int K, hipStream_t s, const SplitArgs* sp) {
+    if (dt_split(dtype) && one_plane_bias(epi, sp)) return hipErrorInvalidValue;
     // Split modes with three (two) terms: the six- (four-) phase 256x256 kernel (gemm256x3_kernel) takes the rows that fill whole
     // rounds of 256 tiles (one workgroup per CU walks its tiles in rounds; a last round that is at least 80 % full is
     // taken too), the 128x128 kernel (2-3 workgroups per CU) the remaining rows. Shape-only, like everything below.
@@ -554,11 +559,9 @@ hipError_t launch_gemm16(int dtype, int epi, const void* A, const void* W, void*
                                      (char*)C + (size_t)r0 * N * (out16 ? es : sizeof(float)), bias,
                                      resid ? resid + (size_t)r0 * N : nullptr, M - r0, N, K, s, sp);
     }
-    // shape-only dispatch (never data-dependent; the one environment input is the persistent workgroup count of MNX_ENC_CUS,
-    // which moves rows between gemm256x3_kernel and the 128x128 kernel — the two add the same numbers in the same order, so
-    // the results do not change: test_persistent_encoder_grids_on_fewer_cus_...): the persistent 256x256 kernel for the 16-bit-output
-    // layers whose tile count fills the chip, the persistent 256x128 kernel for the fp32-output layers likewise, the
-    // 128x128 kernel for everything else
+    // shape-only dispatch (never data-dependent, never environment-dependent): the persistent 256x256 kernel for the
+    // 16-bit-output layers whose tile count fills the chip, the persistent 256x128 kernel for the fp32-output layers
+    // likewise, the 128x128 kernel for everything else
     if (bias && gemm256_supports(dtype, epi, M, N, K)) return launch_gemm256(dtype, epi, A, W, C, bias, M, N, K, s, sp);
     if (gemm_res_preferred(dtype, epi, M, N, K)) return launch_gemm_res(dtype, epi, A, W, (float*)C, bias, resid, M, N, K, s, sp);
     return launch_gemm16_tile128(dtype, epi, A, W, C, bias, resid, M, N, K, s, sp);

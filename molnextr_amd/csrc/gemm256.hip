@@ -763,12 +763,6 @@ static hipError_t lds_opt_in(int lds_bytes = P_LDS) {
     return e;
 }
 
-// Workgroups of a persistent launch (one per CU). 256 = the whole chip; the engine lowers it when the decode stream owns a
-// CU partition (engine.hip, MNX_DEC_CUS), tools/gemm_lab to see how the loop scales with the CUs it runs on.
-static int g_persistent_cus = 256;
-void set_persistent_cus(int n) { g_persistent_cus = n < 1 ? 1 : n > 256 ? 256 : n; }
-int persistent_cus() { return g_persistent_cus; }
-
 // gemm256x3_kernel: split dtypes, any of the four epilogues, whole 256x256 tiles, >= 2 K-tiles.
 bool gemm256x3_supports(int dtype, int epi, int M, int N, int K) {
     if (!dt_split(dtype)) return false;
@@ -778,7 +772,7 @@ bool gemm256x3_supports(int dtype, int epi, int M, int N, int K) {
 
 // Instantiated forms: three terms with both output planes (every split layer of FP16X3 / BF16X3), and for fp16 the forms
 // FP16X3M needs — two terms (any epilogue) and a GELU output that keeps the hi plane only (fc1 when fc2 runs on two terms;
-// the bias epilogue — qkv — always feeds the three-term attention).
+// the bias epilogue — qkv — always feeds the three-term attention: launch_gemm16 refuses it with one plane).
 // bf16 operands never run on two terms (a bf16 hi plane alone is the plain bf16 mode).
 hipError_t launch_gemm256x3(int dtype, int epi, const void* A, const void* W, void* C, const float* bias,
                             const float* resid, int M, int N, int K, hipStream_t s, const SplitArgs* sp) {
@@ -791,8 +785,7 @@ hipError_t launch_gemm256x3(int dtype, int epi, const void* A, const void* W, vo
     if (dtype != MNX_DT_F16X3 && (sp->terms != 3 || !lo_out)) return hipErrorInvalidValue;
     const SplitArgs spv = *sp;
     const int tm = M / TM, tn = N / TN;
-    const int cus = persistent_cus();
-    const int grid = tm * tn < cus ? tm * tn : cus;
+    const int grid = tm * tn < PERSISTENT_CUS ? tm * tn : PERSISTENT_CUS;
 #define MNX_G256X3_GO(TT, E, TERMS, LO)                                                                                    \
     do {                                                                                                                  \
         const hipError_t attr = lds_opt_in<gemm256x3_kernel<TT, E, TERMS, LO>>(X3_LDS);                                     \
@@ -809,14 +802,14 @@ hipError_t launch_gemm256x3(int dtype, int epi, const void* A, const void* W, vo
         }
     } else if (spv.terms == 3) {
         switch (epi) {
-            case EPI_BIAS_16: if (!lo_out) return hipErrorInvalidValue; MNX_G256X3_GO(f16_t, EPI_BIAS_16, 3, true); break;
+            case EPI_BIAS_16: MNX_G256X3_GO(f16_t, EPI_BIAS_16, 3, true); break;
             case EPI_GELU_16: if (lo_out) MNX_G256X3_GO(f16_t, EPI_GELU_16, 3, true); else MNX_G256X3_GO(f16_t, EPI_GELU_16, 3, false); break;
             case EPI_RESID_F32: MNX_G256X3_GO(f16_t, EPI_RESID_F32, 3, true); break;
             default: MNX_G256X3_GO(f16_t, EPI_BIAS_F32, 3, true); break;
         }
     } else {
         switch (epi) {
-            case EPI_BIAS_16: if (!lo_out) return hipErrorInvalidValue; MNX_G256X3_GO(f16_t, EPI_BIAS_16, 2, true); break;
+            case EPI_BIAS_16: MNX_G256X3_GO(f16_t, EPI_BIAS_16, 2, true); break;
             case EPI_GELU_16: if (lo_out) MNX_G256X3_GO(f16_t, EPI_GELU_16, 2, true); else MNX_G256X3_GO(f16_t, EPI_GELU_16, 2, false); break;
             case EPI_RESID_F32: MNX_G256X3_GO(f16_t, EPI_RESID_F32, 2, true); break;
             default: MNX_G256X3_GO(f16_t, EPI_BIAS_F32, 2, true); break;

@@ -24,7 +24,7 @@ enum { EPI_BIAS_16 = 0, EPI_GELU_16 = 1, EPI_RESID_F32 = 2, EPI_BIAS_F32 = 3 };
 // ignored —, the weight keeps both: the weight's rounding is systematic, the activation's is noise; compute_dtype FP16X3M,
 // DESIGN.md section 4.3); 1 = ah.wh only (error-budget aid: the layer runs as the plain 16-bit mode would).
 // c_planes (16-bit-output epilogues): 2 = hi and lo output planes; 1 = the hi plane only (c_lo ignored) — for a consumer
-// that runs on two terms. The hi plane is the same bits either way.
+// that runs on two terms. The hi plane is the same bits either way. EPI_BIAS_16 takes 2 only (refused on every route).
 struct SplitArgs {
     size_t a_lo = 0, w_lo = 0, c_lo = 0;
     float oscale = 1.f;
@@ -52,9 +52,8 @@ hipError_t launch_gemm256(int dtype, int epi, const void* A, const void* W, void
 // tile it is given on one workgroup per CU in rounds of 256: launch_gemm16 hands it whole rounds and the 128x128 kernel
 // the remaining rows.
 bool gemm256x3_supports(int dtype, int epi, int M, int N, int K);
-// workgroups of a persistent launch = CUs the encoder stream may occupy (default 256, the whole chip)
-void set_persistent_cus(int n);
-int persistent_cus();
+// workgroups of a persistent launch (gemm256x3_kernel: one per CU; window_attn_pipe_kernel: two) = the whole chip
+constexpr int PERSISTENT_CUS = 256;
 // measurement aids (gemm256.hip): shader clock of the gemm256x3_kernel launches since the last reset; sustained rate of a
 // register-only fp16 MFMA loop on random operands (every CU, `iters` x 8 instructions per wave)
 hipError_t x3_clock_read(double* mhz, bool reset);

@@ -40,8 +40,20 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
 DTYPES = {"bf16": 0, "fp16": 1, "fp32": 2, "bf16x3": 3, "fp16x3": 4, "fp16x3m": 5}
 DEFAULT_DTYPE = "fp16x3"
 SPLIT_CLASSES = {"qkv": 1, "attn": 2, "proj": 4, "fc1": 8, "fc2": 16, "merge": 32}
-FP16X3M_BLOCKS = {}                                       # {stage: (first_block, last_block)}: MNX_FP16X3M_FIRST_BLOCK_BY_STAGE
-FP16X3M_TWO_TERM = ("qkv.s2", "fc1.s2", "fc2.s2")       # include/molnextr_hip.h MNX_FP16X3M_TWO_TERM_BY_STAGE (tags: "cls" or "cls.sN", N 0-based)
+# FP16X3M's table for Swin-B's four stages, as set_op_terms arguments. The library installs it from include/molnextr_hip.h
+# MNX_FP16X3M_TWO_TERM_BY_STAGE / _FIRST_BLOCK_BY_STAGE (tests/test_abi.py checks that these two say the same).
+FP16X3M_BLOCKS = {}                                       # {stage: (first_block, last_block)}
+FP16X3M_TWO_TERM = ("qkv.s2", "fc1.s2", "fc2.s2")       # tags: "cls" or "cls.sN", N 0-based
+
+
+def two_term_masks(two_term, n_stages):
+    """Per-stage MNX_OP_* masks of set_op_terms tags ("cls" or "cls.sN")."""
+    masks = [0] * n_stages
+    for tag in two_term:
+        cls, _, st = tag.partition(".s")
+        for i in ([int(st)] if st else range(n_stages)):
+            masks[i] |= SPLIT_CLASSES[cls]
+    return masks
 
 
 class MnxConfig(C.Structure):
@@ -287,17 +299,13 @@ class Engine:
         """fp16x3 / fp16x3m engines: the Linear op classes that run on TWO product terms (ah.wh + ah.wl), as tags "cls" (every
         stage) or "cls.sN" (encoder stage N, 0-based) with cls a name of SPLIT_CLASSES other than 'attn' — the syntax of
         tools/study_split_terms.py --two. blocks: {stage: (first_block, last_block)} restricts a stage's table to those Swin
-        blocks (default: all of them). None = the mode's own table (fp16x3: none, fp16x3m: FP16X3M_TWO_TERM / _BLOCKS)."""
+        blocks (default: all of them). None = the mode's own table as the engine was created with it (fp16x3: none, fp16x3m:
+        the header's, on the encoder's last stages); blocks must then be None."""
         if two_term is None:
-            two_term = FP16X3M_TWO_TERM if self.dtype == "fp16x3m" else ()
-            blocks = FP16X3M_BLOCKS if self.dtype == "fp16x3m" and blocks is None else blocks
-        n = len(self.enc.depths)
-        masks = [0] * n
-        for tag in two_term:
-            cls, _, st = tag.partition(".s")
-            for i in ([int(st)] if st else range(n)):
-                masks[i] |= SPLIT_CLASSES[cls]
-        for i, m in enumerate(masks):
+            assert blocks is None, "blocks go with an explicit table"
+            self._check(self.lib.mnx_set_op_terms(self.h, -1, -1, 0, 0), "mnx_set_op_terms")
+            return
+        for i, m in enumerate(two_term_masks(two_term, len(self.enc.depths))):
             lo, hi = (blocks or {}).get(i, (0, 1 << 30))
             self._check(self.lib.mnx_set_op_terms(self.h, i, m, lo, hi), "mnx_set_op_terms")
 

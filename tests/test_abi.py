@@ -31,6 +31,22 @@ def test_abi_version(lib):
     assert lib.mnx_abi_version() == engine.ABI_VERSION == 7
 
 
+def test_fp16x3m_table_matches_header():
+    """engine.FP16X3M_TWO_TERM / FP16X3M_BLOCKS describe the four-stage table the library installs from the header"""
+    with open(os.path.join(ROOT, "include", "molnextr_hip.h")) as f:
+        hdr = f.read()
+    ops = {m[0]: int(m[1]) for m in re.findall(r"\b(MNX_OP_[A-Z0-9]+) = (\d+)", hdr)}
+    assert {k[len("MNX_OP_"):].lower(): v for k, v in ops.items()} == engine.SPLIT_CLASSES
+
+    def macro(name):
+        rows = re.search(r"#define " + name + r" \{([^}]*)\}", hdr).group(1).split(",")
+        return [sum(ops[t] if t in ops else int(t) for t in (t.strip() for t in row.split("|"))) for row in rows]
+
+    assert macro("MNX_FP16X3M_TWO_TERM_BY_STAGE") == engine.two_term_masks(engine.FP16X3M_TWO_TERM, 4)
+    first = macro("MNX_FP16X3M_FIRST_BLOCK_BY_STAGE")
+    assert [engine.FP16X3M_BLOCKS.get(i, (0, 1 << 30)) for i in range(4)] == [(f, 1 << 30) for f in first]
+
+
 def test_config_struct_layout_matches_header():
     # 20 int32 fields + two int32[4] arrays = 26 int32
     assert ctypes.sizeof(engine.MnxConfig) == 26 * 4

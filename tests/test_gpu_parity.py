@@ -88,7 +88,9 @@ def test_gemm_split_operand_modes(dev, dtype, M, N, K):
     loops) and the six-phase persistent 256x256 one (gemm256x3_kernel: the last three shapes, all four epilogues; the
     576-tile shape splits into 2 whole rounds on it + the remaining rows on the 128-tile kernel) — against a float64 product of the
     SAME fp32 inputs, every output element: fp32-class accuracy from 16-bit matrix instructions, the exact-erf GELU, the
-    hi + lo output planes, the power-of-two weight scale, and terms = 1 degrading to the plain 16-bit product."""
+    hi + lo output planes, the power-of-two weight scale, and terms = 1 degrading to the plain 16-bit product. Every
+    three-term epilogue's output equals the 128-tile kernel's alone (| 0x200) bit for bit: an image's features must not
+    depend on which kernel its rows land in (launch_gemm16 splits a layer's rows between them by shape)."""
     e = _tiny_engine(dtype)
     td = torch.float16 if dtype == "fp16x3" else torch.bfloat16
     g = torch.Generator().manual_seed(M + N + K)
@@ -100,22 +102,32 @@ def test_gemm_split_operand_modes(dev, dtype, M, N, K):
     A2, W2 = _split_planes(A, td), _split_planes(Wt, td, wscale)
     # what the planes can represent at best: the product of the rounded sums
     tol = 3e-6 if dtype == "fp16x3" else 2e-4
+
+    def tile128(epi, c, b):         # the same launch on the 128-tile kernel alone, on a copy of the output's initial state
+        c = c.clone()
+        e.gemm16_split(epi | 0x200, A2, W2, c, b, oscale=1.0 / wscale)
+        return c
+
     out = torch.zeros(M, N, device=dev)
     e.gemm16_split(3, A2, W2, out, bias, oscale=1.0 / wscale)
     assert (out.double() - ref).abs().max().item() < tol * max(1.0, ref.abs().max().item())
+    assert torch.equal(tile128(3, torch.zeros_like(out), bias), out)
     out.fill_(7.0)
     e.gemm16_split(3, A2, W2, out, None, oscale=1.0 / wscale)          # a layer without bias (patch-merging reduction)
     assert (out.double() - (ref - bias.double())).abs().max().item() < tol * max(1.0, ref.abs().max().item())
+    assert torch.equal(tile128(3, torch.full_like(out, 7.0), None), out)
     res = torch.randn(M, N, generator=g).to(dev)
     r2 = res.clone()
     e.gemm16_split(2, A2, W2, r2, bias, oscale=1.0 / wscale)
     assert (r2.double() - (ref + res.double())).abs().max().item() < tol * max(1.0, ref.abs().max().item())
+    assert torch.equal(tile128(2, res, bias), r2)
     again = res.clone()
     e.gemm16_split(2, A2, W2, again, bias, oscale=1.0 / wscale)
     assert torch.equal(again, r2)                                       # same launch twice: bit-identical
     for epi, want in ((0, ref), (1, torch.nn.functional.gelu(ref))):
         o2 = torch.zeros(2, M, N, device=dev, dtype=td)
         e.gemm16_split(epi, A2, W2, o2, bias, oscale=1.0 / wscale)
+        assert torch.equal(tile128(epi, torch.zeros_like(o2), bias), o2), epi
         got = o2[0].double() + o2[1].double()
         assert (got - want).abs().max().item() < tol * max(1.0, want.abs().max().item()), epi
         half_ulp = 2.0 ** -10 if td == torch.float16 else 2.0 ** -7          # |lo| <= half an ulp of hi
@@ -134,8 +146,8 @@ def test_gemm_two_term_form(dev, M, N, K):
     nor multiplied) on both kernels — the 128-tile one (DMA and non-DMA K loops) and the four-phase form of the persistent
     256x256 kernel (the last five shapes; one, two and several K-tiles per tile, several tiles per workgroup, a ragged round)
     — against a float64 product of the ROUNDED activation (the hi plane) with the unrounded weight, every output element,
-    all four epilogues; the one-plane output (hi only, for a two-term consumer) is the two-plane output's hi plane bit for bit;
-    and the two kernels add the same fp32 numbers in the same order (an image's features must not depend on which kernel
+    all four epilogues; the one-plane output (hi only, for a two-term consumer) is the two-plane output's hi plane bit for bit
+    in the GELU epilogue and refused in the bias one (qkv always feeds the three-term attention) on every route; and the two kernels add the same fp32 numbers in the same order (an image's features must not depend on which kernel
     its rows land in: launch_gemm16 splits a layer's rows between them by batch size)."""
     e = _tiny_engine("fp16x3")
     td = torch.float16
@@ -182,6 +194,11 @@ def test_gemm_two_term_form(dev, M, N, K):
                 one128 = torch.full((1, M, N), 3.0, device=dev, dtype=td)
                 e.gemm16_split(1 | 0x400 | 0x200, a_in, W2, one128, bias, oscale=1.0 / wscale, terms=terms)
                 assert torch.equal(one128[0], two[0]), terms
+    from molnextr_amd.engine import MnxError
+    one = torch.zeros(1, M, N, device=dev, dtype=td)
+    for epi in (0 | 0x400, 0 | 0x400 | 0x200):     # the one-plane bias epilogue: refused on x3, 128 and x3+128 shapes alike
+        with pytest.raises(MnxError):
+            e.gemm16_split(epi, A2, W2, one, bias, oscale=1.0 / wscale, terms=2)
     e.close()
     eb = _tiny_engine("bf16x3")
     with pytest.raises(Exception):          # bf16 operands never run on two terms
@@ -273,6 +290,21 @@ def test_swin_tiny_every_block_vs_reference_golden(golden_dir, dev, dtype, tol):
     assert np.abs(e.encode(img).cpu().numpy() - gold["features"]).max() < tol
     e.close()
 
+
+
+def test_fp16x3m_table_is_restored_on_a_two_stage_encoder(dev):
+    """set_op_terms(None) reinstalls the table an fp16x3m engine was created with (include/molnextr_hip.h's, on the tiny
+    encoder's last two stages): features bit for bit those of a fresh fp16x3m engine after another table ran."""
+    img = W.hash_normal("swin_tiny_img", (2, 3, 96, 96), 1.0).to(dev)
+    fresh = _tiny_engine("fp16x3m")
+    want = fresh.encode(img).cpu()
+    fresh.close()
+    e = _tiny_engine("fp16x3m")
+    e.set_op_terms(("fc1",))
+    assert not torch.equal(e.encode(img).cpu(), want), "the other table must change the features"
+    e.set_op_terms(None)
+    assert torch.equal(e.encode(img).cpu(), want)
+    e.close()
 
 def test_swin_full_vs_reference_golden(golden_dir, eng, dev):
     gold = np.load(os.path.join(golden_dir, "swin_full.npz"))
@@ -439,37 +471,6 @@ def test_fused_and_unfused_ticks_mix_in_one_job(eng, dev, synth_ckpt):
             e.close()
     for r in res[1:]:
         _same_predictions(res[0], r)
-
-
-def test_persistent_encoder_grids_on_fewer_cus_give_identical_predictions(eng, dev, synth_ckpt):
-    """MNX_ENC_CUS=n launches the encoder's persistent kernels (gemm256x3_kernel, window_attn_pipe_kernel) on n (2 n)
-    workgroups so that 256 - n CUs stay free for the decode stream. Which workgroup computes a tile, and how a
-    layer's rows are split between the 256x256 and the 128x128 kernel, changes with n; the results must not (every GEMM kernel
-    adds an element's terms in one order). The setting is process-wide: restored to 256 at the end."""
-    from molnextr_amd.engine import Engine
-    imgs = W.synthetic_images(96, first_index=900).to(dev)
-    want = {k: v.cpu() for k, v in eng.predict(imgs, ref_batch=32).items()}
-    fwant = eng.encode(imgs[:32].contiguous()).cpu()
-    old = os.environ.get("MNX_ENC_CUS")
-    try:
-        for n in (224, 192):
-            os.environ["MNX_ENC_CUS"] = str(n)
-            e = Engine(synth_ckpt["encoder"], synth_ckpt["decoder"], device=0, max_batch=96, dec_slots=128, dtype="fp16x3")
-            try:
-                assert torch.equal(e.encode(imgs[:32].contiguous()).cpu(), fwant), f"features differ bitwise at {n} workgroups"
-                _same_predictions(want, {k: v.cpu() for k, v in e.predict(imgs, ref_batch=32).items()})
-            finally:
-                e.close()
-        with pytest.raises(Exception, match="MNX_ENC_CUS"):
-            os.environ["MNX_ENC_CUS"] = "32"
-            Engine(synth_ckpt["encoder"], synth_ckpt["decoder"], device=0, max_batch=32, dec_slots=64, dtype="fp16x3")
-    finally:
-        os.environ["MNX_ENC_CUS"] = "256"
-        Engine(synth_ckpt["encoder"], synth_ckpt["decoder"], device=0, max_batch=32, dec_slots=64, dtype="fp16x3").close()
-        if old is None:
-            os.environ.pop("MNX_ENC_CUS", None)
-        else:
-            os.environ["MNX_ENC_CUS"] = old
 
 
 @pytest.mark.parametrize("B,beam,n_best,max_len", [(4, 3, 2, 160), (3, 5, 5, 96), (2, 8, 1, 64), (5, 2, 2, 480),

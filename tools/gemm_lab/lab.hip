@@ -113,12 +113,11 @@ int main(int argc, char** argv) {
         printf("background copy alone: %.2f TB/s (read + write), %d workgroups\n", 10 * 2.0 * bn * 16 / (ms * 1e-3) * 1e-12, bg_wgs);
     }
     const int dt = split ? mnx::MNX_DT_F16X3 : mnx::MNX_DT_BF16;
-    // environment: MNX_LAB_ZERO=1 all operands zero (what does the clock do without toggling data?), MNX_LAB_CUS=n persistent
-    // launches on n workgroups, MNX_LAB_NOBASE=1 the 128x128 kernel is run once (for the comparison) but not timed
+    // environment: MNX_LAB_ZERO=1 all operands zero (what does the clock do without toggling data?), MNX_LAB_NOBASE=1 the
+    // 128x128 kernel is run once (for the comparison) but not timed
     const bool zero = getenv("MNX_LAB_ZERO") && atoi(getenv("MNX_LAB_ZERO"));
     const bool nobase = getenv("MNX_LAB_NOBASE") && atoi(getenv("MNX_LAB_NOBASE"));
-    if (getenv("MNX_LAB_CUS")) mnx::set_persistent_cus(atoi(getenv("MNX_LAB_CUS")));
-    printf("persistent workgroups %d%s\n", mnx::persistent_cus(), zero ? ", ZERO operands" : "");
+    printf("persistent workgroups %d%s\n", mnx::PERSISTENT_CUS, zero ? ", ZERO operands" : "");
     std::vector<Shape> shapes;
     const int L[4] = {9216, 2304, 576, 144}, C[4] = {128, 256, 512, 1024};
     static char names[64][32];
