@@ -52,3 +52,50 @@ int run(const mnx_weight_desc* weights, int n_weights, const float* host_images 
     mnx_destroy(eng);
     return rc != MNX_OK;
 }
+
+/* The same from raw pages (HWC uint8 RGB, every page its own size): all pages transformed by ONE mnx_preprocess_batch call
+ * into gray bytes, which mnx_predict_gray8 reads directly — a twelfth of the bytes of the fp32 images above, the same results
+ * bit for bit. `eng` as created in run(); n_pages <= MNX_PREP_MAX_PAGES per call. */
+int run_from_pages(mnx_engine* eng, const uint8_t* const* host_pages, const int32_t* heights, const int32_t* widths,
+                   int n_pages) {
+    mnx_page* table = (mnx_page*)malloc((size_t)n_pages * sizeof(mnx_page));
+    uint64_t arena_bytes = 0;
+    int32_t tallest = 1;
+    int i, rc;
+    uint8_t *arena = NULL, *gray = NULL, *edges = NULL;
+    mnx_page* table_dev = NULL;
+    int32_t *tokens = NULL, *lengths = NULL, *n_atoms = NULL, *atom_idx = NULL;
+    if (!table) return 1;
+    for (i = 0; i < n_pages; ++i) {          /* pages side by side in one arena, each at a multiple of 16 bytes */
+        table[i].offset = arena_bytes;
+        table[i].height = heights[i];
+        table[i].width = widths[i];
+        arena_bytes += ((uint64_t)3 * (uint64_t)heights[i] * (uint64_t)widths[i] + 15u) & ~(uint64_t)15;
+        if (heights[i] > tallest) tallest = heights[i];
+    }
+    hipMalloc((void**)&arena, (size_t)arena_bytes);
+    hipMalloc((void**)&table_dev, (size_t)n_pages * sizeof(mnx_page));
+    hipMalloc((void**)&gray, (size_t)n_pages * 384 * 384);
+    hipMalloc((void**)&tokens, (size_t)n_pages * 480 * 4);
+    hipMalloc((void**)&lengths, (size_t)n_pages * 4);
+    hipMalloc((void**)&n_atoms, (size_t)n_pages * 4);
+    hipMalloc((void**)&atom_idx, (size_t)n_pages * 160 * 4);
+    hipMalloc((void**)&edges, (size_t)n_pages * 160 * 160);
+    for (i = 0; i < n_pages; ++i)            /* (a real host stages the pages in ONE pinned buffer and copies once) */
+        hipMemcpy(arena + table[i].offset, host_pages[i], (size_t)3 * (size_t)heights[i] * (size_t)widths[i], 1);
+    hipMemcpy(table_dev, table, (size_t)n_pages * sizeof(mnx_page), 1 /* hipMemcpyHostToDevice */);
+
+    rc = mnx_preprocess_batch(eng, arena, table_dev, n_pages, tallest, /*pad=*/50, /*pad_to_square=*/0, /*crops_out=*/NULL,
+                              gray, MNX_IMG_GRAY8, /*stream=*/NULL);
+    if (rc != MNX_OK) fprintf(stderr, "mnx_preprocess_batch: %s\n", mnx_last_error(eng));
+    /* the four confidence pointers all NULL: mnx_predict's outputs; all four set: mnx_predict_confidence's */
+    if (rc == MNX_OK) {
+        rc = mnx_predict_gray8(eng, gray, n_pages, /*ref_batch=*/16, /*max_len=*/480, tokens, lengths, n_atoms, atom_idx, edges,
+                               /*kmax=*/160, NULL, NULL, NULL, NULL, /*stream=*/NULL);
+        if (rc != MNX_OK) fprintf(stderr, "mnx_predict_gray8: %s\n", mnx_last_error(eng));
+    }
+    hipFree(arena); hipFree(table_dev); hipFree(gray); hipFree(tokens); hipFree(lengths); hipFree(n_atoms); hipFree(atom_idx);
+    hipFree(edges);
+    free(table);
+    return rc != MNX_OK;
+}

@@ -10,9 +10,9 @@
  * pointers and sizes (no torch / C++ types), return 0 on success or a negative mnx_status, never throw, and
  * enqueue their GPU work on the caller's HIP stream. Device pointers are raw HBM addresses (e.g. a PyTorch-ROCm
  * tensor's data_ptr()). A handle is bound to one device and is not re-entrant: one in-flight call per handle —
- * except that ONE mnx_preprocess call (its only state is a private 16-byte scratch) may run on another thread and
- * stream beside any other entry point, so that the next images can be uploaded and transformed while mnx_predict
- * works; different handles (GPUs) may be driven from different threads or processes. The only process-wide state is the
+ * except that ONE call of the preprocess family (mnx_preprocess or mnx_preprocess_batch; their only state is private box
+ * scratch) may run on another thread and stream beside any other entry point, so that the next pages can be uploaded and
+ * transformed while mnx_predict works; different handles (GPUs) may be driven from different threads or processes. The only process-wide state is the
  * message of the last failed mnx_create (read it with mnx_last_error(NULL) from the thread that called mnx_create).
  */
 #ifndef MOLNEXTR_HIP_H
@@ -130,6 +130,12 @@ size_t mnx_workspace_bytes(const mnx_engine* h);
  * features_out: device fp32 [B, (S/32)^2, 8*embed_dim]. Asynchronous on `stream`. */
 int mnx_encode(mnx_engine* h, const float* images, int32_t B, float* features_out, void* stream);
 
+/* mnx_encode on the transform's gray bytes: gray device uint8 [B,S,S] (mnx_preprocess_batch with MNX_IMG_GRAY8; 4-byte
+ * aligned). The patch embedding expands a byte g to the three channels (float(g) - 255 mean[c]) * (1 / (255 std[c])) — the
+ * two fp32 operations the transform's fp32 output went through — so features_out equals mnx_encode's on the fp32 image of the
+ * same bytes bit for bit. */
+int mnx_encode_gray8(mnx_engine* h, const uint8_t* gray, int32_t B, float* features_out, void* stream);
+
 /* Debug/test aid: copy the fp32 residual stream after execution item `item` of the next mnx_encode calls into
  * `dst` (device). Items: 0 = patch_embed, then every Swin block and every patch-merging in execution order.
  * item < 0 disables. */
@@ -233,6 +239,31 @@ int mnx_edges(mnx_engine* h, const float* hidden, const int32_t* atom_idx, const
 int mnx_preprocess(mnx_engine* h, const uint8_t* rgb, int32_t height, int32_t width, int32_t pad,
                    int32_t pad_to_square, int32_t* crop_out, float* out, void* stream);
 
+/* The same transform for n pages in ONE call: three kernel launches whatever n (box init, boxes of all pages, resize of all
+ * pages), no host synchronisation, no per-page host work, no host read of `pages`.
+ *   arena      device bytes holding the pages as HWC uint8 RGB, page i at arena + pages[i].offset (any arena size: every
+ *              address is 64-bit). The caller guarantees offset + 3 * height * width <= the arena's size.
+ *   pages      DEVICE table of n entries; offset a multiple of 16, 1 <= height, width <= 16384 (the host never reads the
+ *              table, so it cannot refuse an entry; one with height or width < 1 is transformed as a blank page)
+ *   n          1 .. MNX_PREP_MAX_PAGES per call (the box scratch mnx_create reserved; MNX_ERR_CAPACITY beyond, the message
+ *              names the bound); a longer list takes several calls
+ *   max_height the tallest of the n pages (sizes the box kernel's grid; rows beyond it would not be scanned)
+ *   crops_out  device int32 [n,4] or NULL: row i as mnx_preprocess's crop_out
+ *   out        MNX_IMG_F32: device fp32 [n,3,S,S], word for word what n calls of mnx_preprocess write;
+ *              MNX_IMG_GRAY8: device uint8 [n,S,S], the gray value in front of Normalize — the input of mnx_encode_gray8 /
+ *              mnx_predict_gray8, a twelfth of the bytes (S = cfg.img_size)
+ * MNX_ERR_INVALID_ARG: null pointer, n < 1, max_height outside 1..16384, pad outside 0..4096, unknown out_format, arena or
+ * out misaligned (16 / 4 bytes). Asynchronous on `stream`. */
+typedef struct {
+    uint64_t offset;            /* bytes into `arena`, multiple of 16 */
+    int32_t height, width;
+} mnx_page;
+enum { MNX_IMG_F32 = 0, MNX_IMG_GRAY8 = 1 };
+#define MNX_PREP_MAX_PAGES 4096
+int mnx_preprocess_batch(mnx_engine* h, const uint8_t* arena, const mnx_page* pages, int32_t n, int32_t max_height,
+                         int32_t pad, int32_t pad_to_square, int32_t* crops_out, void* out, int32_t out_format,
+                         void* stream);
+
 /* Token classes for the on-device atom-position scan used by mnx_predict (the 'indices' that
  * CharTokenizer.sequence_to_smiles derives, MolNexTR/tokenization.py:464-515). flags[id]: bit0 = is_symbol(id),
  * bit1 = is_atom(id), bits 2-4 = length of the id's name in characters - 1 (read by the confidences only: an atom's
@@ -280,6 +311,15 @@ int mnx_predict_confidence(mnx_engine* h, const float* images, int32_t n_img, in
                            int32_t* tokens, int32_t* lengths, int32_t* n_atoms, int32_t* atom_idx, uint8_t* edges,
                            int32_t kmax, float* token_logp, double* edge_scores, double* atom_scores, double* overall_score,
                            void* stream);
+
+/* mnx_predict (the four confidence pointers all NULL) or mnx_predict_confidence (all four set; anything between is
+ * MNX_ERR_INVALID_ARG) on gray bytes: gray device uint8 [n_img,S,S] as for mnx_encode_gray8, stop_on_eos = 1. The same
+ * limits, MNX_ERR_RANGE reporting and continuous batching, and the same outputs bit for bit as on the fp32 images of the
+ * same bytes. The format travels as an argument: a handle has no "current image format". Beam search stays on fp32 images
+ * (mnx_predict_beam): out of scope here. */
+int mnx_predict_gray8(mnx_engine* h, const uint8_t* gray, int32_t n_img, int32_t ref_batch, int32_t max_len,
+                      int32_t* tokens, int32_t* lengths, int32_t* n_atoms, int32_t* atom_idx, uint8_t* edges, int32_t kmax,
+                      float* token_logp, double* edge_scores, double* atom_scores, double* overall_score, void* stream);
 
 /* The confidence computation on its own (test aid and building block of mnx_predict_confidence; replaces the
  * compute_confidence lines of MolNexTR/components.py:456-469,485-491): tokens device int32 [n,T] (T <= 512), lengths

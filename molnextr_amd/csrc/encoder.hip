@@ -32,6 +32,17 @@ namespace mnx {
 // sq); fma(d * rstd, gamma, beta)): that is what the first form compiled to, and left to -ffp-contract the compiler vectorised
 // the three-patch form into separate multiplies and adds — the encoder output changed in its last bits (tools/features_hash.py
 // compares the two libraries: identical now).
+// GRAY (the body's pixel-source argument): the image arrives as the transform's gray bytes [B,S,S] (preprocess.hip GRAY8) and
+// not as three fp32 planes that are affine copies of them. A source line is then loaded ONCE (4 * 96 dwords per chunk, two
+// per thread, where the fp32 source takes five quads per thread) and stored as the three channel lines
+// (float(g) - mean255[ci]) * inv[ci] — the two fp32 operations prep_resize_kernel performs, on the constants of
+// norm_consts() — into the same LDS places; from the first __syncthreads() on the code is the same, so the tokens are
+// bit-identical. The statements live in patch_embed_body.inc and are included into two kernels rather than one kernel growing a
+// second template argument: the fp32 kernel keeps its name (tests/test_device_math.py finds its four instantiations by it)
+// and, instruction for instruction, its ISA.
+// Registers (hipcc of ROCm 7.2; the tap loop's "244" below is an earlier compiler's count of the same kernel): patch_embed_kernel
+// <4> 106, <8> 150, <12> 200, <16> 246; patch_embed_gray8_kernel <4> 90, <8> 132, <12> 182, <16> 228 (two dwords in flight
+// instead of five quads); no scratch in any of the eight, two workgroups per CU at C = 128 in both.
 constexpr int PE_NP = 3;            // 96 patches per chunk: one chunk per row at 384 x 384
 template <int CPT>
 __global__ __launch_bounds__(256) void patch_embed_kernel(const float* __restrict__ img, const float* __restrict__ w_t,
@@ -39,133 +50,22 @@ __global__ __launch_bounds__(256) void patch_embed_kernel(const float* __restric
                                                           const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, float* __restrict__ x,
                                                           int S, int G, int rpw) {
-    constexpr int C = 8 * CPT;
-    constexpr int PW = 128 * PE_NP;             // pixels per staged line
-    constexpr int WS = C + 4;                   // weight row stride in LDS
-    constexpr bool SWZ = CPT == 16;             // parts 4..7 (channels 64..127) stored 4 floats later
-    constexpr int NWQ = (12 * C + 255) / 256;   // weight quads per thread
-    constexpr int NPQ = (12 * (PW / 4) + 255) / 256;
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float* wt = sm;             // [48][WS]
-    float* pix = sm + 48 * WS;  // [3][4][PW]
-    const int tid = threadIdx.x;
-    const int b = blockIdx.y;
-    const int p = tid >> 3, part = tid & 7;
-    const int c0 = part * CPT;
-    f32x4 wq[NWQ];
-#pragma unroll
-    for (int k = 0; k < NWQ; ++k) wq[k] = ((const f32x4*)w_t)[min(tid + 256 * k, 12 * C - 1)];
-    // a workgroup takes `rpw` consecutive patch rows (round 6: two at G % 2 == 0 — the 24 KB of weights are staged once per
-    // workgroup, a quarter of what a patch row moves into the CU) in chunks of 96 patches; per output nothing changes
-    const int nchunk = (G + 32 * PE_NP - 1) / (32 * PE_NP);
-    for (int ch = 0; ch < rpw * nchunk; ++ch) {
-        const int py = blockIdx.x * rpw + ch / nchunk, px0 = (ch % nchunk) * 32 * PE_NP;
-        f32x4 pq[NPQ];
-#pragma unroll
-        for (int k = 0; k < NPQ; ++k) {
-            const int i = min(tid + 256 * k, 12 * (PW / 4) - 1);
-            const int line = i / (PW / 4), xq = i % (PW / 4);       // line = ci * 4 + ky
-            const int gx = px0 * 4 + xq * 4;                        // S % 4 == 0: a quad is inside the image or outside it
-            pq[k] = *(const f32x4*)(img + ((size_t)(b * 3 + (line >> 2)) * S + (py * 4 + (line & 3))) * S + min(gx, S - 4));
-        }
-        f32x4 bq[CPT / 4];
-#pragma unroll
-        for (int j = 0; j < CPT / 4; ++j) bq[j] = *(const f32x4*)(bias + c0 + 4 * j);
-        __builtin_amdgcn_sched_barrier(0);      // keep the requests together, ahead of the first wait
-        if (ch > 0) __syncthreads();            // the previous chunk's pixels have been consumed
-        else {
-#pragma unroll
-            for (int k = 0; k < NWQ; ++k) {
-                const int i = tid + 256 * k;
-                const int row = i / (C / 4), c = (i % (C / 4)) * 4;
-                if (i < 12 * C) *(f32x4*)(wt + row * WS + c + (SWZ ? (c >> 6) * 4 : 0)) = wq[k];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < NPQ; ++k) {
-            const int i = tid + 256 * k;
-            const int line = i / (PW / 4), xq = i % (PW / 4);
-            f32x4 v = pq[k];
-            if (px0 * 4 + xq * 4 >= S) v = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (i < 12 * (PW / 4)) *(f32x4*)(pix + line * PW + xq * 4) = v;
-        }
-        __syncthreads();
-        float acc[PE_NP][CPT];
-#pragma unroll
-        for (int j = 0; j < CPT; ++j)
-#pragma unroll
-            for (int q = 0; q < PE_NP; ++q) acc[q][j] = bq[j >> 2][j & 3];
-        // tap loop, software-pipelined by hand: the weight quads of tap t + 1 (and, at kx = 3, the next line's pixels) are
-        // requested before tap t's FMAs, the scheduling barrier keeps a tap's requests ahead of the previous tap's FMAs. (244
-        // registers at C = 128: two workgroups per CU, where the LDS would allow three — capped at 168 registers the compiler
-        // spills 70; two are enough to cover one workgroup's staging with the other's taps.)
-        const float* wbase = wt + c0 + (SWZ ? (part >> 2) * 4 : 0);
-        const float* pbase = pix + p * 4;
-        f32x4 wc[CPT / 4], pv[PE_NP];
-#pragma unroll
-        for (int j = 0; j < CPT / 4; ++j) wc[j] = *(const f32x4*)(wbase + 4 * j);
-#pragma unroll
-        for (int q = 0; q < PE_NP; ++q) pv[q] = *(const f32x4*)(pbase + q * 128);
-#pragma unroll 1
-        for (int line = 0; line < 12; ++line) {
-            f32x4 pn[PE_NP];
-#pragma unroll
-            for (int kx = 0; kx < 4; ++kx) {
-                f32x4 wn[CPT / 4];
-                const float* wr = wbase + min(line * 4 + kx + 1, 47) * WS;
-#pragma unroll
-                for (int j = 0; j < CPT / 4; ++j) wn[j] = *(const f32x4*)(wr + 4 * j);
-                if (kx == 3) {
-                    const float* pr = pbase + min(line + 1, 11) * PW;
-#pragma unroll
-                    for (int q = 0; q < PE_NP; ++q) pn[q] = *(const f32x4*)(pr + q * 128);
-                }
-#pragma unroll
-                for (int j = 0; j < CPT; j += 4) {
-                    const f32x4 w4 = wc[j >> 2];
-#pragma unroll
-                    for (int q = 0; q < PE_NP; ++q) {
-                        const float v = pv[q][kx];
-                        acc[q][j] = fmaf(v, w4[0], acc[q][j]); acc[q][j + 1] = fmaf(v, w4[1], acc[q][j + 1]);
-                        acc[q][j + 2] = fmaf(v, w4[2], acc[q][j + 2]); acc[q][j + 3] = fmaf(v, w4[3], acc[q][j + 3]);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int j = 0; j < CPT / 4; ++j) wc[j] = wn[j];
-            }
-#pragma unroll
-            for (int q = 0; q < PE_NP; ++q) pv[q] = pn[q];
-        }
-        __builtin_amdgcn_sched_barrier(0);      // gamma / beta requested here, not above the tap loop (32 registers)
-        f32x4 g4[CPT / 4], b4[CPT / 4];
-#pragma unroll
-        for (int j = 0; j < CPT / 4; ++j) { g4[j] = *(const f32x4*)(gamma + c0 + 4 * j); b4[j] = *(const f32x4*)(beta + c0 + 4 * j); }
-#pragma unroll
-        for (int q = 0; q < PE_NP; ++q) {
-            const int px = px0 + q * 32 + p;
-            float s = 0.f;
-#pragma unroll
-            for (int j = 0; j < CPT; ++j) s += acc[q][j];
-            s += __shfl_xor(s, 1, 64); s += __shfl_xor(s, 2, 64); s += __shfl_xor(s, 4, 64);
-            const float mean = s / (float)C;
-            float sq = 0.f;
-#pragma unroll
-            for (int j = 0; j < CPT; ++j) { acc[q][j] -= mean; sq = fmaf(acc[q][j], acc[q][j], sq); }
-            sq += __shfl_xor(sq, 1, 64); sq += __shfl_xor(sq, 2, 64); sq += __shfl_xor(sq, 4, 64);
-            const float rstd = rsqrtf(sq / (float)C + 1e-5f);
-            if (px < G) {
-                float* o = x + ((size_t)(b * G + py) * G + px) * C + c0;
-#pragma unroll
-                for (int j = 0; j < CPT; j += 4) {
-                    f32x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaf(acc[q][j + e] * rstd, g4[j >> 2][e], b4[j >> 2][e]);
-                    *(f32x4*)(o + j) = v;
-                }
-            }
-        }
-    }
+    constexpr bool GRAY = false;
+    const uint8_t* gray = nullptr;
+    const NormConsts nc{};
+#include "patch_embed_body.inc"
+}
+
+template <int CPT>
+__global__ __launch_bounds__(256) void patch_embed_gray8_kernel(const uint8_t* __restrict__ gray, const NormConsts nc,
+                                                                const float* __restrict__ w_t,
+                                                                const float* __restrict__ bias,
+                                                                const float* __restrict__ gamma,
+                                                                const float* __restrict__ beta, float* __restrict__ x,
+                                                                int S, int G, int rpw) {
+    constexpr bool GRAY = true;
+    const float* img = nullptr;
+#include "patch_embed_body.inc"
 }
 
 hipError_t launch_patch_embed(const float* img, const float* w_t, const float* bias, const float* gamma,
@@ -180,6 +80,23 @@ hipError_t launch_patch_embed(const float* img, const float* w_t, const float* b
         case 8: hipLaunchKernelGGL(patch_embed_kernel<8>, grid, block, smem, s, img, w_t, bias, gamma, beta, x, S, G, rpw); break;
         case 12: hipLaunchKernelGGL(patch_embed_kernel<12>, grid, block, smem, s, img, w_t, bias, gamma, beta, x, S, G, rpw); break;
         default: hipLaunchKernelGGL(patch_embed_kernel<16>, grid, block, smem, s, img, w_t, bias, gamma, beta, x, S, G, rpw); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_patch_embed_gray8(const uint8_t* gray, const float* w_t, const float* bias, const float* gamma,
+                                    const float* beta, float* x, int B, int S, int C, hipStream_t s) {
+    if (C > 128 || (C & 31) || (S & 3) || S < 4 || ((uintptr_t)gray & 3)) return hipErrorInvalidValue;
+    const int G = S / 4;
+    const int rpw = (G % 2 == 0) ? 2 : 1;
+    dim3 grid(G / rpw, B), block(256);
+    size_t smem = (size_t)(48 * (C + 4) + 3 * 4 * 128 * PE_NP) * sizeof(float);
+    const NormConsts nc = norm_consts();
+    switch (C >> 3) {
+        case 4: hipLaunchKernelGGL(patch_embed_gray8_kernel<4>, grid, block, smem, s, gray, nc, w_t, bias, gamma, beta, x, S, G, rpw); break;
+        case 8: hipLaunchKernelGGL(patch_embed_gray8_kernel<8>, grid, block, smem, s, gray, nc, w_t, bias, gamma, beta, x, S, G, rpw); break;
+        case 12: hipLaunchKernelGGL(patch_embed_gray8_kernel<12>, grid, block, smem, s, gray, nc, w_t, bias, gamma, beta, x, S, G, rpw); break;
+        default: hipLaunchKernelGGL(patch_embed_gray8_kernel<16>, grid, block, smem, s, gray, nc, w_t, bias, gamma, beta, x, S, G, rpw); break;
     }
     return hipGetLastError();
 }

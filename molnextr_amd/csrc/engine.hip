@@ -89,6 +89,7 @@ struct mnx_engine {
     int* forced_ids = nullptr;  // [32, max_len] teacher-forcing ids of mnx_decode_forced (lazy; test aid)
     BeamBuffers beam{};        // allocated lazily on the first mnx_decode_beam
     int* prep_bbox = nullptr;  // scratch of mnx_preprocess
+    int* prep_bbox_batch = nullptr;   // [MNX_PREP_MAX_PAGES][4]: scratch of mnx_preprocess_batch (its own: the two may not share)
     float* beam_hidden = nullptr;   // mnx_predict_beam: [32, max_len, dec_dim] decoder outputs of the winners (lazy)
     int* host_flag = nullptr;  // pinned: [2][1 + MAX_CHUNKS] poll snapshots + slot lists
     std::map<GraphKey, hipGraphExec_t> graphs;
@@ -625,6 +626,7 @@ int mnx_create(const mnx_config* cfg, const mnx_weight_desc* weights, int32_t n_
     }
     h->tc_dev = (TokenClasses*)P.dalloc(sizeof(TokenClasses));
     h->prep_bbox = (int*)P.dalloc(4 * sizeof(int));   // at create: mnx_preprocess may run beside another entry point
+    h->prep_bbox_batch = (int*)P.dalloc((size_t)MNX_PREP_MAX_PAGES * 4 * sizeof(int));
     {
         // Encoder and decoder run concurrently on separate streams; the encoder stream gets the high priority (its
         // large GEMM grids otherwise queue behind the decode ticks' many small kernels: measured +1.6 %). Partitioning
@@ -715,10 +717,13 @@ static int check_encoder_range(mnx_engine* h, hipStream_t s) {
     return MNX_ERR_RANGE;
 }
 
-int mnx_encode(mnx_engine* h, const float* images, int32_t B, float* features_out, void* stream) {
+// mnx_encode / mnx_encode_gray8: the image source is (pointer, MNX_IMG_* format); only the patch embedding looks at it
+static int encode_impl(mnx_engine* h, const char* name, const void* images, int fmt, int32_t B, float* features_out,
+                       void* stream) {
     if (!h) return MNX_ERR_INVALID_ARG;
-    if (!images || !features_out || B < 1) { h->err = "mnx_encode: null/empty argument"; return MNX_ERR_INVALID_ARG; }
-    if (B > h->cfg.max_batch) { h->err = "mnx_encode: B exceeds max_batch"; return MNX_ERR_CAPACITY; }
+    if (!images || !features_out || B < 1) { h->err = std::string(name) + ": null/empty argument"; return MNX_ERR_INVALID_ARG; }
+    if (fmt == MNX_IMG_GRAY8 && ((uintptr_t)images & 3)) { h->err = std::string(name) + ": gray must be 4-byte aligned"; return MNX_ERR_INVALID_ARG; }
+    if (B > h->cfg.max_batch) { h->err = std::string(name) + ": B exceeds max_batch"; return MNX_ERR_CAPACITY; }
     hipStream_t s = (hipStream_t)stream;
     const mnx_config& c = h->cfg;
     const int dt = h->dt;
@@ -782,8 +787,14 @@ int mnx_encode(mnx_engine* h, const float* images, int32_t B, float* features_ou
         return timed(1, (double)M * Cc * (4.0 + (y16 ? es * planes / 2 : 0.0) + (y32 ? 4.0 : 0.0)),
                      [&]() { return launch_layernorm16(dt, x, g, b, y16, y32, M, Cc, 1e-5f, s, h->xn_lo, y32 ? h->enc_flag : nullptr, planes); });
     };
-    HIPCHK(h, timed(3, (double)B * (3.0 * c.img_size * c.img_size + (double)Hh * Ww * C) * 4.0,
-                    [&]() { return launch_patch_embed(images, h->pe_wt, h->pe_b, h->pe_g, h->pe_beta, cur, B, c.img_size, C, s); }));
+    if (fmt == MNX_IMG_GRAY8)
+        HIPCHK(h, timed(3, (double)B * ((double)c.img_size * c.img_size + (double)Hh * Ww * C * 4.0), [&]() {
+            return launch_patch_embed_gray8((const uint8_t*)images, h->pe_wt, h->pe_b, h->pe_g, h->pe_beta, cur, B, c.img_size, C, s);
+        }));
+    else
+        HIPCHK(h, timed(3, (double)B * (3.0 * c.img_size * c.img_size + (double)Hh * Ww * C) * 4.0, [&]() {
+            return launch_patch_embed((const float*)images, h->pe_wt, h->pe_b, h->pe_g, h->pe_beta, cur, B, c.img_size, C, s);
+        }));
     HIPCHK(h, tap((size_t)B * Hh * Ww * C));
     for (int si = 0; si < c.n_stages; ++si) {
         StageW& st = h->stages[si];
@@ -816,6 +827,14 @@ int mnx_encode(mnx_engine* h, const float* images, int32_t B, float* features_ou
     }
     HIPCHK(h, ln(cur, h->fn_g, h->fn_b, nullptr, features_out, B * Hh * Ww, C));
     return MNX_OK;
+}
+
+int mnx_encode(mnx_engine* h, const float* images, int32_t B, float* features_out, void* stream) {
+    return encode_impl(h, "mnx_encode", images, MNX_IMG_F32, B, features_out, stream);
+}
+
+int mnx_encode_gray8(mnx_engine* h, const uint8_t* gray, int32_t B, float* features_out, void* stream) {
+    return encode_impl(h, "mnx_encode_gray8", gray, MNX_IMG_GRAY8, B, features_out, stream);
 }
 
 }  // extern "C"
@@ -864,7 +883,8 @@ int project_memory(mnx_engine* h, const float* feats, int n, int blk0, hipStream
 // When a buffer counts as ready and where it is released stay with the callers.
 struct FeatRing {
     mnx_engine* h;
-    const float* images;
+    const void* images;                 // [n_img,3,S,S] fp32 or [n_img,S,S] gray bytes ...
+    int fmt;                            // ... as MNX_IMG_* says: this struct is the one caller of the encoder
     int n_img, ref_batch, n_chunks, grp;
     int first[2] = {-1, -1}, count[2] = {0, 0};
     bool used[2] = {false, false};      // released before: a refill waits for ev_feat_free
@@ -872,13 +892,14 @@ struct FeatRing {
 
     // encode the next group into every free buffer on enc_stream; ev_enc_done[i] marks buffer i complete
     int refill() {
-        const size_t img_elems = (size_t)3 * h->cfg.img_size * h->cfg.img_size;
+        const size_t img_bytes = (size_t)h->cfg.img_size * h->cfg.img_size * (fmt == MNX_IMG_GRAY8 ? 1 : 3 * sizeof(float));
         for (int i = 0; i < 2; ++i) {
             if (first[i] >= 0 || next_enc >= n_chunks) continue;
             const int cnt = std::min(grp, n_chunks - next_enc);
             const int f = next_enc * ref_batch, n = std::min(cnt * ref_batch, n_img - f);
             if (used[i]) HIPCHK(h, hipStreamWaitEvent(h->enc_stream, h->ev_feat_free[i], 0));
-            MNXCHK(mnx_encode(h, images + (size_t)f * img_elems, n, h->feat_ring[i], h->enc_stream));
+            MNXCHK(encode_impl(h, fmt == MNX_IMG_GRAY8 ? "mnx_encode_gray8" : "mnx_encode", (const char*)images + (size_t)f * img_bytes,
+                               fmt, n, h->feat_ring[i], h->enc_stream));
             HIPCHK(h, hipEventRecord(h->ev_enc_done[i], h->enc_stream));
             first[i] = next_enc;
             count[i] = cnt;
@@ -1128,7 +1149,7 @@ int mnx_predict_beam(mnx_engine* h, const float* images, int32_t n_img, int32_t 
     HIPCHK(h, hipEventRecord(h->ev_poll[0], s));
     HIPCHK(h, hipStreamWaitEvent(h->enc_stream, h->ev_poll[0], 0));
     const int n_chunks = (n_img + ref_batch - 1) / ref_batch;
-    FeatRing ring{h, images, n_img, ref_batch, n_chunks, std::max(1, c.max_batch / ref_batch)};
+    FeatRing ring{h, images, MNX_IMG_F32, n_img, ref_batch, n_chunks, std::max(1, c.max_batch / ref_batch)};
     for (int ck = 0; ck < n_chunks;) {
         // keep both feature buffers busy on the encoder stream: the encoder of the following groups runs while the
         // beam search of these reference batches occupies the caller's stream
@@ -1165,6 +1186,33 @@ int mnx_preprocess(mnx_engine* h, const uint8_t* rgb, int32_t height, int32_t wi
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, launch_preprocess(rgb, height, width, pad, pad_to_square ? 1 : 0, h->cfg.img_size, h->prep_bbox, crop_out, out,
                                 (hipStream_t)stream));
+    return MNX_OK;
+}
+
+int mnx_preprocess_batch(mnx_engine* h, const uint8_t* arena, const mnx_page* pages, int32_t n, int32_t max_height,
+                         int32_t pad, int32_t pad_to_square, int32_t* crops_out, void* out, int32_t out_format,
+                         void* stream) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    if (!arena || !pages || !out || n < 1) { h->err = "mnx_preprocess_batch: null/empty argument"; return MNX_ERR_INVALID_ARG; }
+    if (out_format != MNX_IMG_F32 && out_format != MNX_IMG_GRAY8) {
+        h->err = "mnx_preprocess_batch: out_format must be MNX_IMG_F32 or MNX_IMG_GRAY8";
+        return MNX_ERR_INVALID_ARG;
+    }
+    if (max_height < 1 || max_height > 16384 || pad < 0 || pad > 4096) {
+        h->err = "mnx_preprocess_batch: 1 <= max_height <= 16384 and 0 <= pad <= 4096 required";
+        return MNX_ERR_INVALID_ARG;
+    }
+    if (((uintptr_t)arena & 15) || ((uintptr_t)pages & 7) || ((uintptr_t)out & 3) || ((uintptr_t)crops_out & 3)) {
+        h->err = "mnx_preprocess_batch: arena must be 16-byte, pages 8-byte, out and crops_out 4-byte aligned";
+        return MNX_ERR_INVALID_ARG;
+    }
+    if (n > MNX_PREP_MAX_PAGES) {
+        h->err = "mnx_preprocess_batch: n " + std::to_string(n) + " exceeds MNX_PREP_MAX_PAGES = " + std::to_string(MNX_PREP_MAX_PAGES);
+        return MNX_ERR_CAPACITY;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, launch_preprocess_batch(arena, pages, n, max_height, pad, pad_to_square ? 1 : 0, h->cfg.img_size,
+                                      h->prep_bbox_batch, crops_out, out, out_format == MNX_IMG_GRAY8, (hipStream_t)stream));
     return MNX_OK;
 }
 
@@ -1232,7 +1280,7 @@ struct ConfOut {
 
 // The whole hot path for n_img images with continuous batching (see include/molnextr_hip.h): the body of mnx_predict and,
 // with `conf`, of mnx_predict_confidence. Without `conf` it enqueues exactly mnx_predict's launches.
-static int predict_impl(mnx_engine* h, const char* name, const float* images, int32_t n_img, int32_t ref_batch,
+static int predict_impl(mnx_engine* h, const char* name, const void* images, int img_fmt, int32_t n_img, int32_t ref_batch,
                         int32_t max_len, int32_t stop_on_eos, int32_t* tokens, int32_t* lengths, int32_t* n_atoms,
                         int32_t* atom_idx, uint8_t* edges, int32_t kmax, const ConfOut* conf, void* stream) {
     if (!h) return MNX_ERR_INVALID_ARG;
@@ -1241,6 +1289,7 @@ static int predict_impl(mnx_engine* h, const char* name, const float* images, in
         h->err = std::string(name) + ": null/empty argument";
         return MNX_ERR_INVALID_ARG;
     }
+    if (img_fmt == MNX_IMG_GRAY8 && ((uintptr_t)images & 3)) { h->err = std::string(name) + ": gray must be 4-byte aligned"; return MNX_ERR_INVALID_ARG; }
     if (!h->have_tc) { h->err = std::string(name) + ": call mnx_set_token_classes first"; return MNX_ERR_INVALID_ARG; }
     const mnx_config& c = h->cfg;
     const int SL = h->db.slots;
@@ -1289,7 +1338,7 @@ static int predict_impl(mnx_engine* h, const char* name, const float* images, in
     const double t_begin = now_ms();
     double host_wait_ms = 0.0;
     // each reference batch of an encoder group is admitted on its own
-    FeatRing ring{h, images, n_img, ref_batch, n_chunks, std::max(1, c.max_batch / ref_batch)};
+    FeatRing ring{h, images, img_fmt, n_img, ref_batch, n_chunks, std::max(1, c.max_batch / ref_batch)};
     const int ticks_per_poll = 4;            // measured: 2-4 equal, 8 = -4 % (retirement lags)
     while (done < n_chunks) {
         // ---- encoder prefetch: keep both feature buffers busy on the encoder stream
@@ -1411,7 +1460,7 @@ extern "C" {
 int mnx_predict(mnx_engine* h, const float* images, int32_t n_img, int32_t ref_batch, int32_t max_len,
                 int32_t stop_on_eos, int32_t* tokens, int32_t* lengths, int32_t* n_atoms, int32_t* atom_idx,
                 uint8_t* edges, int32_t kmax, void* stream) {
-    return predict_impl(h, "mnx_predict", images, n_img, ref_batch, max_len, stop_on_eos, tokens, lengths, n_atoms, atom_idx,
+    return predict_impl(h, "mnx_predict", images, MNX_IMG_F32, n_img, ref_batch, max_len, stop_on_eos, tokens, lengths, n_atoms, atom_idx,
                         edges, kmax, nullptr, stream);
 }
 
@@ -1420,8 +1469,22 @@ int mnx_predict_confidence(mnx_engine* h, const float* images, int32_t n_img, in
                            int32_t kmax, float* token_logp, double* edge_scores, double* atom_scores, double* overall_score,
                            void* stream) {
     const ConfOut conf{token_logp, edge_scores, atom_scores, overall_score};
-    return predict_impl(h, "mnx_predict_confidence", images, n_img, ref_batch, max_len, 1, tokens, lengths, n_atoms,
+    return predict_impl(h, "mnx_predict_confidence", images, MNX_IMG_F32, n_img, ref_batch, max_len, 1, tokens, lengths, n_atoms,
                         atom_idx, edges, kmax, &conf, stream);
+}
+
+int mnx_predict_gray8(mnx_engine* h, const uint8_t* gray, int32_t n_img, int32_t ref_batch, int32_t max_len,
+                      int32_t* tokens, int32_t* lengths, int32_t* n_atoms, int32_t* atom_idx, uint8_t* edges, int32_t kmax,
+                      float* token_logp, double* edge_scores, double* atom_scores, double* overall_score, void* stream) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    const int n_conf = !!token_logp + !!edge_scores + !!atom_scores + !!overall_score;
+    if (n_conf != 0 && n_conf != 4) {
+        h->err = "mnx_predict_gray8: the four confidence pointers must be all NULL or all set";
+        return MNX_ERR_INVALID_ARG;
+    }
+    const ConfOut conf{token_logp, edge_scores, atom_scores, overall_score};
+    return predict_impl(h, "mnx_predict_gray8", gray, MNX_IMG_GRAY8, n_img, ref_batch, max_len, 1, tokens, lengths, n_atoms,
+                        atom_idx, edges, kmax, n_conf ? &conf : nullptr, stream);
 }
 
 int mnx_gemm_clock(mnx_engine* h, int32_t reset, double* mhz) {

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/molnextr_hip.h"
+
 namespace mnx {
 
 // F32: parity mode, every encoder operand in fp32 on the exact-fp32 MFMA (1/16 rate).
@@ -71,6 +73,10 @@ hipError_t launch_gemm_res(int dtype, int epi, const void* A, const void* W, flo
 // images [B,3,S,S] fp32 NCHW -> x [B,(S/4)^2,C] fp32 (conv 4x4/4 + bias + LayerNorm, eps 1e-5)
 hipError_t launch_patch_embed(const float* img, const float* w_t /*[48][C]*/, const float* bias, const float* gamma,
                               const float* beta, float* x, int B, int S, int C, hipStream_t s);
+// the same from gray bytes [B,S,S] (preprocess.hip's GRAY8 output): the three normalised channels are expanded while the
+// pixel lines are staged, everything behind that is patch_embed_kernel's code — bit-identical tokens
+hipError_t launch_patch_embed_gray8(const uint8_t* gray, const float* w_t /*[48][C]*/, const float* bias, const float* gamma,
+                                    const float* beta, float* x, int B, int S, int C, hipStream_t s);
 // y16[M,C] = LayerNorm(x[M,C]) (eps) as 16-bit; optionally also fp32 copy y32. Split dtypes: y16 = hi plane, the lo plane
 // is written y_lo ELEMENTS behind it. nonfinite_flag (device int, may be null): set to 1 when a row's result is not finite.
 // Split dtypes with planes == 1: only the hi plane is written (the consumer runs on two terms), y_lo is ignored.
@@ -94,6 +100,15 @@ hipError_t launch_cast16(int dtype, const float* x, void* y16, size_t n, hipStre
 // HWC uint8 RGB page -> [3,S,S] fp32 (CropWhite(pad) + bilinear resize + gray + ImageNet normalise); bbox: 4 ints scratch
 hipError_t launch_preprocess(const uint8_t* rgb, int H, int W, int pad, int square, int S, int* bbox, int* crop_out,
                              float* out, hipStream_t s);
+// Normalize(ImageNet) on a gray byte g: channel c of the encoder's input is (float(g) - mean255[c]) * inv[c]. Derived in one
+// place (preprocess.hip) for the resize kernels that write fp32 images and for the patch embedding that reads gray bytes.
+struct NormConsts { float mean255[3], inv[3]; };
+NormConsts norm_consts();
+// n pages of `arena` (HWC uint8 RGB at pages[i].offset; `pages` is a DEVICE table) -> fp32 [n,3,S,S], or with gray8 the
+// gray byte in front of the normalisation, uint8 [n,S,S]. Three launches whatever n; bbox: 4 n ints of scratch; crops:
+// device [n,4] or null; max_height: the tallest page (sizes the box kernel's grid).
+hipError_t launch_preprocess_batch(const uint8_t* arena, const mnx_page* pages, int n, int max_height, int pad, int square,
+                                   int S, int* bbox, int* crops, void* out, bool gray8, hipStream_t s);
 
 // ---- decoder.hip ----------------------------------------------------------------------------
 struct DecWeights;   // device pointers, see engine.cpp

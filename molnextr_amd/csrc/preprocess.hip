@@ -65,39 +65,85 @@ struct PrepArgs {
 };
 
 __global__ __launch_bounds__(256) void prep_resize_kernel(PrepArgs a) {
-    const int dx = blockIdx.x * 16 + (threadIdx.x & 15), dy = blockIdx.y * 16 + (threadIdx.x >> 4);
-    int top = 0, bottom = a.H, left = 0, right = a.W;
-    if (a.bbox[1] >= 0) { top = a.bbox[0]; bottom = a.bbox[1] + 1; left = a.bbox[2]; right = a.bbox[3] + 1; }
-    const int hc = bottom - top, wc = right - left;
-    if (a.crop_out && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-        a.crop_out[0] = top; a.crop_out[1] = a.H - bottom; a.crop_out[2] = left; a.crop_out[3] = a.W - right;
+    constexpr bool GRAY8 = false;
+#include "prep_resize_body.inc"
+}
+
+// ---- all pages of one mnx_preprocess_batch call: three launches whatever n ----------------------------------------------
+// The pages are ragged and their table lives on the device (the host never reads it), so the box kernel runs a
+// (row, page) grid of max_height x n workgroups in which a workgroup whose row lies beyond its page leaves at once: a
+// flattened row index would need the prefix sums of the heights, i.e. a host pass over the table or a device scan in front,
+// for workgroups that cost nothing when they exit on their first compare. Every address into the arena is 64-bit.
+__global__ __launch_bounds__(256) void prep_bbox_init_batch_kernel(const mnx_page* __restrict__ pages, int n, int* bbox) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) { bbox[4 * i] = pages[i].height; bbox[4 * i + 1] = -1; bbox[4 * i + 2] = pages[i].width; bbox[4 * i + 3] = -1; }
+}
+
+__global__ __launch_bounds__(256) void prep_bbox_batch_kernel(const uint8_t* __restrict__ arena,
+                                                              const mnx_page* __restrict__ pages, int* bbox) {
+    __shared__ int s_min[4], s_max[4];
+    const mnx_page pg = pages[blockIdx.y];
+    const int y = blockIdx.x, W = pg.width, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (y >= pg.height) return;       // uniform over the workgroup
+    const uint8_t* row = arena + (size_t)pg.offset + (size_t)y * W * 3;
+    int mn = W, mx = -1;
+    for (int x = tid; x < W; x += 256) {
+        const bool ink = row[3 * x] != 255 || row[3 * x + 1] != 255 || row[3 * x + 2] != 255;
+        if (ink) { mn = min(mn, x); mx = max(mx, x); }
     }
-    int Hp = hc + 2 * a.pad, Wp = wc + 2 * a.pad, pad_t = a.pad, pad_l = a.pad;
-    if (a.square) {      // PadToSquare after CropWhite (reference data_aug.py:286-301): diff//2 first, the rest after
-        const int diff = Hp > Wp ? Hp - Wp : Wp - Hp;
-        if (Hp <= Wp) { pad_t += diff / 2; Hp = Wp; } else { pad_l += diff / 2; Wp = Hp; }
-    }
-    if (dx >= a.S || dy >= a.S) return;
-    int y0, y1, wy0, wy1, x0, x1, wx0, wx1;
-    linear_tap(dy, Hp, a.S, y0, y1, wy0, wy1);
-    linear_tap(dx, Wp, a.S, x0, x1, wx0, wx1);
-    auto px = [&](int y, int x, int c) -> int {      // the cropped page with its white border, never materialised
-        y -= pad_t; x -= pad_l;
-        if (y < 0 || y >= hc || x < 0 || x >= wc) return 255;
-        return a.rgb[((size_t)(top + y) * a.W + left + x) * 3 + c];
-    };
-    int ch[3];
 #pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        mn = min(mn, __shfl_xor(mn, o, 64));
+        mx = max(mx, __shfl_xor(mx, o, 64));
+    }
+    if (lane == 0) { s_min[wave] = mn; s_max[wave] = mx; }
+    __syncthreads();
+    if (tid == 0) {
+        int* bb = bbox + 4 * blockIdx.y;
+        mn = min(min(s_min[0], s_min[1]), min(s_min[2], s_min[3]));
+        mx = max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3]));
+        if (mx >= 0) {
+            atomicMin(&bb[0], y); atomicMax(&bb[1], y);
+            atomicMin(&bb[2], mn); atomicMax(&bb[3], mx);
+        }
+    }
+}
+
+struct PrepBatchArgs {
+    const uint8_t* arena;
+    const mnx_page* pages;
+    const int* bbox;     // [n][4]
+    int* crops;          // [n][4] or null
+    void* out;           // GRAY8: uint8 [n, S, S]; otherwise fp32 [n, 3, S, S]
+    int pad, S, square;
+    NormConsts nc;
+};
+
+template <bool GRAY8>
+__global__ __launch_bounds__(256) void prep_resize_batch_kernel(PrepBatchArgs b) {
+    const size_t i = blockIdx.z;
+    const mnx_page pg = b.pages[i];
+    const size_t img = (size_t)b.S * b.S;
+    PrepArgs a;
+    a.rgb = b.arena + (size_t)pg.offset;
+    a.bbox = b.bbox + 4 * i;
+    a.crop_out = b.crops ? b.crops + 4 * i : nullptr;
+    a.out = GRAY8 ? (float*)((uint8_t*)b.out + i * img) : (float*)b.out + i * 3 * img;
+    a.H = pg.height; a.W = pg.width; a.pad = b.pad; a.S = b.S; a.square = b.square;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { a.mean255[c] = b.nc.mean255[c]; a.inv[c] = b.nc.inv[c]; }
+#include "prep_resize_body.inc"
+}
+
+NormConsts norm_consts() {
+    NormConsts k;
+    const float mean[3] = {0.485f, 0.456f, 0.406f}, sd[3] = {0.229f, 0.224f, 0.225f};   // IMAGENET_DEFAULT_MEAN / STD
     for (int c = 0; c < 3; ++c) {
-        const int r0 = px(y0, x0, c) * wx0 + px(y0, x1, c) * wx1;
-        const int r1 = px(y1, x0, c) * wx0 + px(y1, x1, c) * wx1;
-        const int v = (((wy0 * (r0 >> 4)) >> 16) + ((wy1 * (r1 >> 4)) >> 16) + 2) >> 2;
-        ch[c] = min(max(v, 0), 255);
+        volatile float m = mean[c] * 255.0f, d = sd[c] * 255.0f;   // fp32 products, as numpy computes them
+        k.mean255[c] = m;
+        k.inv[c] = 1.0f / d;
     }
-    const int gray = (ch[0] * 4899 + ch[1] * 9617 + ch[2] * 1868 + 8192) >> 14;     // cv2 RGB2GRAY
-    const float g = (float)(gray & 255);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) a.out[((size_t)c * a.S + dy) * a.S + dx] = (g - a.mean255[c]) * a.inv[c];
+    return k;
 }
 
 hipError_t launch_preprocess(const uint8_t* rgb, int H, int W, int pad, int square, int S, int* bbox, int* crop_out,
@@ -106,13 +152,23 @@ hipError_t launch_preprocess(const uint8_t* rgb, int H, int W, int pad, int squa
     hipLaunchKernelGGL(prep_bbox_kernel, dim3(H), dim3(256), 0, s, rgb, H, W, bbox);
     PrepArgs a;
     a.rgb = rgb; a.bbox = bbox; a.crop_out = crop_out; a.out = out; a.H = H; a.W = W; a.pad = pad; a.S = S; a.square = square;
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, sd[3] = {0.229f, 0.224f, 0.225f};   // IMAGENET_DEFAULT_MEAN / STD
-    for (int c = 0; c < 3; ++c) {
-        volatile float m = mean[c] * 255.0f, d = sd[c] * 255.0f;   // fp32 products, as numpy computes them
-        a.mean255[c] = m;
-        a.inv[c] = 1.0f / d;
-    }
+    const NormConsts k = norm_consts();
+    for (int c = 0; c < 3; ++c) { a.mean255[c] = k.mean255[c]; a.inv[c] = k.inv[c]; }
     hipLaunchKernelGGL(prep_resize_kernel, dim3((S + 15) / 16, (S + 15) / 16), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_preprocess_batch(const uint8_t* arena, const mnx_page* pages, int n, int max_height, int pad, int square,
+                                   int S, int* bbox, int* crops, void* out, bool gray8, hipStream_t s) {
+    if (n < 1 || n > 65535 || max_height < 1) return hipErrorInvalidValue;      // grid.y / grid.z carry the page
+    hipLaunchKernelGGL(prep_bbox_init_batch_kernel, dim3((n + 255) / 256), dim3(256), 0, s, pages, n, bbox);
+    hipLaunchKernelGGL(prep_bbox_batch_kernel, dim3(max_height, n), dim3(256), 0, s, arena, pages, bbox);
+    PrepBatchArgs a;
+    a.arena = arena; a.pages = pages; a.bbox = bbox; a.crops = crops; a.out = out; a.pad = pad; a.S = S; a.square = square;
+    a.nc = norm_consts();
+    const dim3 grid((S + 15) / 16, (S + 15) / 16, n);
+    if (gray8) hipLaunchKernelGGL(prep_resize_batch_kernel<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(prep_resize_batch_kernel<false>, grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

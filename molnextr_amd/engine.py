@@ -24,7 +24,8 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
            "mnx_profile_read", "mnx_set_token_classes", "mnx_predict", "mnx_atom_scan", "mnx_decode_beam", "mnx_preprocess",
            "mnx_probe_decode_attn", "mnx_predict_beam", "mnx_set_split_terms", "mnx_encoder_status",
            "mnx_gemm16_split", "mnx_decode_forced", "mnx_gemm_clock", "mnx_probe_mfma", "mnx_set_op_terms",
-           "mnx_predict_confidence", "mnx_confidence", "mnx_window_attn", "mnx_kv_block")
+           "mnx_predict_confidence", "mnx_confidence", "mnx_window_attn", "mnx_kv_block", "mnx_preprocess_batch",
+           "mnx_encode_gray8", "mnx_predict_gray8")
 
 # Encoder operand modes (include/molnextr_hip.h MNX_DTYPE_*). "fp16x3" — split fp16 operands, three MFMA terms per
 # product, fp32-class results — is the default: it is the fastest mode whose results stay a factor of four inside north_star's
@@ -69,6 +70,13 @@ class MnxWeightDesc(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("ndim", C.c_int32), ("shape", C.c_int64 * 4)]
 
 
+class MnxPage(C.Structure):
+    """include/molnextr_hip.h mnx_page: one page of a mnx_preprocess_batch arena."""
+    _fields_ = [("offset", C.c_uint64), ("height", C.c_int32), ("width", C.c_int32)]
+
+
+PREP_MAX_PAGES = 4096                   # include/molnextr_hip.h MNX_PREP_MAX_PAGES: pages per mnx_preprocess_batch call
+IMAGE_FORMATS = {"fp32": 0, "gray8": 1}  # MNX_IMG_*: what the transform hands to the encoder
 MNX_ERR_RANGE = -6      # include/molnextr_hip.h: the encoder produced non-finite features (fp16 operand range)
 RANGE_FALLBACK = {"fp16x3": "bf16x3", "fp16x3m": "bf16x3", "fp16": "bf16"}    # the same operand structure with the fp32 exponent range
 
@@ -152,6 +160,12 @@ def load_library():
     lib.mnx_atom_scan.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.mnx_preprocess.restype = C.c_int
     lib.mnx_preprocess.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
+    lib.mnx_preprocess_batch.restype = C.c_int
+    lib.mnx_preprocess_batch.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp]
+    lib.mnx_encode_gray8.restype = C.c_int
+    lib.mnx_encode_gray8.argtypes = [vp, vp, i32, vp, vp]
+    lib.mnx_predict_gray8.restype = C.c_int
+    lib.mnx_predict_gray8.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
     lib.mnx_decode_beam.restype = C.c_int
     lib.mnx_decode_beam.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.mnx_predict.restype = C.c_int
@@ -184,7 +198,17 @@ class Engine:
 
     def __init__(self, encoder_state: Dict[str, torch.Tensor], decoder_state: Dict[str, torch.Tensor],
                  device: int = 0, max_batch: int = 32, enc: W.EncoderDims = W.SWIN_B, dec: W.DecoderDims = W.DEC,
-                 dtype: str = DEFAULT_DTYPE, max_len: int = 480, max_atoms: int = 160, dec_slots: int = 2048):
+                 dtype: str = DEFAULT_DTYPE, max_len: int = 480, max_atoms: int = 160, dec_slots: int = 2048,
+                 image_format: str = "fp32"):
+        """image_format: what `preprocess` returns — "fp32" [n,3,S,S] normalised (the per-image mnx_preprocess path) or
+        "gray8" [n,S,S] gray bytes (preprocess_batch: one mnx_preprocess_batch per PREP_MAX_PAGES pages, a twelfth of the
+        bytes). `encode` / `predict` take either and give bit-identical results; the choice is this object's, the library
+        handle has no format state."""
+        if image_format not in IMAGE_FORMATS:
+            raise ValueError(f"image_format must be one of {sorted(IMAGE_FORMATS)}, got {image_format!r}")
+        self.image_format = image_format
+        self._stage = None            # pinned staging of preprocess_batch: kept, grown geometrically
+        self._stage_free = None       # event: the last H2D copy out of _stage has completed
         self.lib = load_library()
         if not torch.cuda.is_available():
             raise MnxError("no HIP device visible: molnextr_amd needs an MI355X (gfx950); there is no CPU fallback")
@@ -276,13 +300,26 @@ class Engine:
         return int(self.lib.mnx_workspace_bytes(self.h))
 
     # -- Encoder.forward -------------------------------------------------------------------------
+    def _is_gray(self, images: torch.Tensor) -> bool:
+        """Which of the two image forms `images` is: uint8 [n,S,S] gray bytes (True) or fp32 [n,3,S,S] normalised (False)."""
+        S = self.enc.img_size
+        assert images.is_cuda and images.is_contiguous()
+        if images.dtype == torch.uint8:
+            assert tuple(images.shape[1:]) == (S, S), images.shape
+            return True
+        assert images.dtype == torch.float32 and tuple(images.shape[1:]) == (3, S, S), (images.dtype, images.shape)
+        return False
+
     def encode(self, images: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        assert images.is_cuda and images.dtype == torch.float32 and images.is_contiguous()
+        """fp32 [B,3,S,S] normalised images (mnx_encode) or uint8 [B,S,S] gray bytes (mnx_encode_gray8) -> features."""
+        gray = self._is_gray(images)
         B = images.shape[0]
-        assert tuple(images.shape[1:]) == (3, self.enc.img_size, self.enc.img_size), images.shape
         if out is None:
             out = torch.empty(B, self.n_mem, self.n_feat, device=images.device, dtype=torch.float32)
-        self._check(self.lib.mnx_encode(self.h, _ptr(images), B, _ptr(out), _stream()), "mnx_encode")
+        if gray:
+            self._check(self.lib.mnx_encode_gray8(self.h, _ptr(images), B, _ptr(out), _stream()), "mnx_encode_gray8")
+        else:
+            self._check(self.lib.mnx_encode(self.h, _ptr(images), B, _ptr(out), _stream()), "mnx_encode")
         return out
 
     def set_tap(self, item: int, dst: Optional[torch.Tensor]):
@@ -361,7 +398,10 @@ class Engine:
     def preprocess(self, images, pad: int = 50, pad_to_square: bool = False, return_crops: bool = False):
         """List of HWC uint8 RGB pages (numpy arrays or tensors, any sizes) -> [n,3,S,S] fp32 on the device.
         pad_to_square: PadToSquare after CropWhite (the reference's transform for real/acs.csv and real/UOB.csv).
-        return_crops: also return the CropWhite parameters [n,4] (crop_top, crop_bottom, crop_left, crop_right)."""
+        return_crops: also return the CropWhite parameters [n,4] (crop_top, crop_bottom, crop_left, crop_right).
+        An engine built with image_format="gray8" forwards to preprocess_batch(out="gray8"): uint8 [n,S,S]."""
+        if self.image_format == "gray8":
+            return self.preprocess_batch(images, pad=pad, pad_to_square=pad_to_square, return_crops=return_crops, out="gray8")
         dev = torch.device("cuda", self.device)
         S = self.enc.img_size
         out = torch.empty(len(images), 3, S, S, dtype=torch.float32, device=dev)
@@ -388,6 +428,100 @@ class Engine:
                         "mnx_preprocess")
         torch.cuda.current_stream().synchronize()      # the uploaded pages must outlive the kernels
         return (out, crops) if return_crops else out
+
+    def _staging(self, nbytes: int) -> torch.Tensor:
+        """The pinned staging buffer of preprocess_batch with room for nbytes, free to be overwritten: ONE buffer per
+        engine, grown geometrically; a refill waits for the event behind the previous copy out of it (not for the device)."""
+        if self._stage_free is not None:
+            self._stage_free.synchronize()
+        if self._stage is None or self._stage.numel() < nbytes:
+            self._stage = torch.empty(max(nbytes, 2 * (self._stage.numel() if self._stage is not None else 0), 1 << 20),
+                                      dtype=torch.uint8, pin_memory=True)
+        return self._stage
+
+    def preprocess_batch(self, images, pad: int = 50, pad_to_square: bool = False, return_crops: bool = False,
+                         out: str = "gray8"):
+        """`preprocess` for the whole list at once (mnx_preprocess_batch): the pages are packed into one pinned staging
+        buffer behind their table, ONE H2D copy carries both, pages that already live on the device are copied into the
+        arena there, and every PREP_MAX_PAGES pages (or STAGE_MAX_BYTES of them) take one library call of three launches. out: "gray8" -> uint8 [n,S,S]
+        (the input of encode / predict at a twelfth of the bytes), "fp32" -> [n,3,S,S] as `preprocess` writes it.
+        One call at a time per engine (the staging buffer and the library's box scratch are the engine's)."""
+        if out not in IMAGE_FORMATS:
+            raise ValueError(f"out must be one of {sorted(IMAGE_FORMATS)}, got {out!r}")
+        dev = torch.device("cuda", self.device)
+        S, n = self.enc.img_size, len(images)
+        res = (torch.empty(n, S, S, dtype=torch.uint8, device=dev) if out == "gray8"
+               else torch.empty(n, 3, S, S, dtype=torch.float32, device=dev))
+        crops = torch.zeros(n, 4, dtype=torch.int32, device=dev) if return_crops else None
+        if n == 0:
+            return (res, crops) if return_crops else res
+        # a call's pages are cut into chunks of at most PREP_MAX_PAGES pages and STAGE_MAX_BYTES bytes (one page at least):
+        # one staging fill, one H2D copy and one library call each
+        sizes = []
+        for i, im in enumerate(images):
+            shp = im.shape if hasattr(im, "shape") else np.shape(im)
+            h, w = int(shp[0]), int(shp[1])
+            if h < 1 or w < 1 or h > 16384 or w > 16384:
+                raise ValueError(f"page {i}: {h} x {w} is outside 1..16384")
+            sizes.append((3 * h * w + 15) & ~15)
+        keep, p0 = [], 0
+        while p0 < n:
+            p1, nbytes = p0 + 1, sizes[p0]
+            while p1 < n and p1 - p0 < PREP_MAX_PAGES and nbytes + sizes[p1] <= self.STAGE_MAX_BYTES:
+                nbytes += sizes[p1]
+                p1 += 1
+            keep.append(self._preprocess_chunk(images[p0:p1], pad, pad_to_square, crops[p0:p1] if return_crops else None,
+                                               res[p0:p1], IMAGE_FORMATS[out]))
+            p0 = p1
+        torch.cuda.current_stream().synchronize()      # the arenas (`keep`) must outlive the kernels
+        return (res, crops) if return_crops else res
+
+    STAGE_MAX_BYTES = 1 << 30     # pinned staging (and device arena) per mnx_preprocess_batch call of preprocess_batch
+
+    def _preprocess_chunk(self, images, pad, pad_to_square, crops, res, fmt):
+        """One mnx_preprocess_batch call of preprocess_batch; returns the device buffer the enqueued kernels read."""
+        dev, n = res.device, len(images)
+        # layout: [page table: n x 16 bytes][pages, each at a multiple of 16]; host pages are written into the staging
+        # buffer, device pages only reserve their place in the arena
+        pages, host, on_dev, off = (MnxPage * n)(), [], [], 0
+        for i, im in enumerate(images):
+            if torch.is_tensor(im) and im.is_cuda:
+                t = im if im.dim() == 3 else im[..., None].expand(-1, -1, 3)
+                t = t[..., :3].to(dtype=torch.uint8).contiguous()
+                on_dev.append((i, t))
+                h, w = t.shape[0], t.shape[1]
+            else:
+                a = np.asarray(im)
+                if a.ndim == 2:
+                    a = a[..., None]
+                host.append((i, a))
+                h, w = a.shape[0], a.shape[1]
+            pages[i].offset, pages[i].height, pages[i].width = off, h, w
+            off += (3 * h * w + 15) & ~15
+        table = 16 * n
+        # everything up to the end of the last host page crosses the bus: the table alone when every page is on the device
+        end = table + max([pages[i].offset + 3 * pages[i].height * pages[i].width for i, _ in host], default=0)
+        stage = self._staging(end)
+        flat = stage.numpy()
+        flat[:table] = np.frombuffer(pages, dtype=np.uint8)
+        for i, a in host:
+            h, w, o = pages[i].height, pages[i].width, table + pages[i].offset
+            flat[o:o + 3 * h * w].reshape(h, w, 3)[...] = a[..., :3]      # one channel broadcasts to three
+        # the device side is allocated per call (the caching allocator recycles it); the copy is asynchronous on this stream
+        # and can overlap the engine working on another one
+        buf = torch.empty(table + off, dtype=torch.uint8, device=dev)
+        buf[:end].copy_(stage[:end], non_blocking=True)
+        self._stage_free = torch.cuda.Event()
+        self._stage_free.record()
+        arena = buf[table:]
+        for i, t in on_dev:
+            o = pages[i].offset
+            arena[o:o + t.numel()].copy_(t.reshape(-1), non_blocking=True)
+        tallest = max(pages[i].height for i in range(n))
+        rc = self.lib.mnx_preprocess_batch(self.h, _ptr(arena), _ptr(buf), n, tallest, pad, int(pad_to_square), _ptr(crops),
+                                           _ptr(res), fmt, _stream())
+        self._check(rc, "mnx_preprocess_batch")
+        return buf
 
     # -- TransformerDecoderAR.decode, beam_size > 1 --------------------------------------------------
     def decode_beam(self, features: torch.Tensor, beam: int = 5, n_best: int = 1, max_len: Optional[int] = None,
@@ -437,8 +571,15 @@ class Engine:
         1 <= ref_batch <= max_ref_batch (up to MAX_REF_BATCH = 512 rows), beam search up to ROWS_PER_DECODE = 32; beyond
         that MnxError (MNX_ERR_CAPACITY) names the bound. confidence=True (greedy, stop_on_eos only):
         mnx_predict_confidence, which adds 'token_logp' [n,max_len] fp32, 'edge_scores' [n,kmax,kmax], 'atom_scores'
-        [n,kmax] and 'overall_score' [n] fp64."""
-        assert images.is_cuda and images.dtype == torch.float32 and images.is_contiguous()
+        [n,kmax] and 'overall_score' [n] fp64. images: fp32 [n,3,S,S] normalised, or uint8 [n,S,S] gray bytes
+        (mnx_predict_gray8: greedy with stop_on_eos only; beam search stays on fp32 images) — the same results bit for bit."""
+        gray = self._is_gray(images)
+        if gray and beam > 1:
+            raise ValueError("beam search takes fp32 images: the library has no gray-byte beam entry point (mnx_predict_beam "
+                             "reads [n,3,S,S] fp32); use preprocess_batch(out='fp32') or image_format='fp32'")
+        if gray and not stop_on_eos:
+            raise ValueError("gray-byte input runs the reference's decode (stop_on_eos=True); fixed-length decoding is a bench "
+                             "aid of the fp32 entry point")
         n = images.shape[0]
         max_len = self.max_len if max_len is None else max_len
         dev, k = images.device, self.max_atoms
@@ -456,10 +597,11 @@ class Engine:
             edge_scores = torch.zeros(n, k, k, dtype=torch.float64, device=dev)
             atom_scores = torch.zeros(n, k, dtype=torch.float64, device=dev)
             overall = torch.zeros(n, dtype=torch.float64, device=dev)
-            rc = self.lib.mnx_predict_confidence(self.h, _ptr(images), n, ref_batch, max_len, _ptr(tokens), _ptr(lengths),
-                                                 _ptr(n_atoms), _ptr(atom_idx), _ptr(edges), k, _ptr(logp), _ptr(edge_scores),
-                                                 _ptr(atom_scores), _ptr(overall), _stream())
-            self._check(rc, "mnx_predict_confidence")
+            fn = "mnx_predict_gray8" if gray else "mnx_predict_confidence"
+            rc = getattr(self.lib, fn)(self.h, _ptr(images), n, ref_batch, max_len, _ptr(tokens), _ptr(lengths),
+                                       _ptr(n_atoms), _ptr(atom_idx), _ptr(edges), k, _ptr(logp), _ptr(edge_scores),
+                                       _ptr(atom_scores), _ptr(overall), _stream())
+            self._check(rc, fn)
             return {"tokens": tokens, "lengths": lengths, "n_atoms": n_atoms, "atom_idx": atom_idx, "edges": edges,
                     "token_logp": logp, "edge_scores": edge_scores, "atom_scores": atom_scores, "overall_score": overall}
         if beam > 1:
@@ -469,6 +611,11 @@ class Engine:
             self._check(rc, "mnx_predict_beam")
             return {"tokens": tokens, "lengths": lengths, "n_atoms": n_atoms, "atom_idx": atom_idx, "edges": edges,
                     "scores": scores}
+        if gray:
+            rc = self.lib.mnx_predict_gray8(self.h, _ptr(images), n, ref_batch, max_len, _ptr(tokens), _ptr(lengths),
+                                            _ptr(n_atoms), _ptr(atom_idx), _ptr(edges), k, None, None, None, None, _stream())
+            self._check(rc, "mnx_predict_gray8")
+            return {"tokens": tokens, "lengths": lengths, "n_atoms": n_atoms, "atom_idx": atom_idx, "edges": edges}
         rc = self.lib.mnx_predict(self.h, _ptr(images), n, ref_batch, max_len, int(stop_on_eos), _ptr(tokens), _ptr(lengths),
                                   _ptr(n_atoms), _ptr(atom_idx), _ptr(edges), k, _stream())
         self._check(rc, "mnx_predict")

@@ -216,6 +216,9 @@ def main(argv=None):
                     help="the reference's flag (main.py:40, exps/eval.sh: fp16 autocast): without --dtype it selects the one-plane "
                          "fp16 operand mode, which stays closer to the fp32 result than the reference's autocast path does "
                          "(tests/test_gpu_pixels.py, tests/golden/pixels_autocast_fp16.json)")
+    ap.add_argument("--image_format", default="fp32", choices=["fp32", "gray8"],
+                    help="what the transform hands to the encoder: fp32 = normalised [n,3,S,S], one mnx_preprocess per page; gray8 = "
+                         "the gray byte per pixel, all pages of a group in one mnx_preprocess_batch (same predictions bit for bit)")
     args = ap.parse_args(argv)
     if not 1 <= args.batch_size <= MAX_BATCH_SIZE:
         ap.error(f"--batch_size must be 1..{MAX_BATCH_SIZE} (reference batches of 2 x batch_size <= {2 * MAX_BATCH_SIZE} rows)")
@@ -230,7 +233,8 @@ def main(argv=None):
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local))
     from .checkpoint import load_checkpoint               # strict validation, no optimizer state, safetensors-aware
     states = W.synthetic_checkpoint(0) if args.load_path == "synthetic" else load_checkpoint(args.load_path)
-    engine = Engine(states["encoder"], states["decoder"], device=local, max_batch=max_batch, dtype=dtype)
+    engine = Engine(states["encoder"], states["decoder"], device=local, max_batch=max_batch, dtype=dtype,
+                    image_format=args.image_format)
     df = pd.read_csv(os.path.join(args.data_path, args.test_file))
     paths = [os.path.join(args.data_path, p) for p in df["file_path"]]
     def infer(e):
@@ -247,7 +251,8 @@ def main(argv=None):
             raise
         print(f"[rank {rank}] {err}: repeating the evaluation with --dtype {to} on every rank", file=sys.stderr, flush=True)
         engine.close()
-        engine = Engine(states["encoder"], states["decoder"], device=local, max_batch=max_batch, dtype=to)
+        engine = Engine(states["encoder"], states["decoder"], device=local, max_batch=max_batch, dtype=to,
+                        image_format=args.image_format)
         preds = infer(engine)
     if rank == 0:
         if "image_id" not in df.columns:    # main.py:461-462

@@ -18,7 +18,7 @@ import torch
 
 from . import weights as W
 from .engine import DEFAULT_DTYPE, Engine, MnxError
-from .preprocess import load_image_rgb, transform_image
+from .preprocess import load_image_rgb, transform_image, transform_image_gray
 from .tokenizer import get_tokenizer
 
 BOND_TYPES = ["", "single", "double", "triple", "aromatic", "solid wedge", "dashed wedge"]  # reference model.py:30
@@ -159,10 +159,15 @@ class molnextr:
     measured, raw logits within 5e-4 on the fixtures, 7.2e-4 on further images and up to 1.2e-3 on a hostile checkpoint — at and
     beyond north_star's 1e-3),
     'bf16x3' (three terms with the fp32 exponent range), 'fp32' (exact-fp32 MFMA, slowest), 'bf16' / 'fp16' (fastest; argmax
-    decisions near a tie can differ)."""
+    decisions near a tie can differ).
+    image_format: what the transform hands to the encoder — "fp32" (the default: normalised [n,3,S,S], one mnx_preprocess per
+    page) or "gray8" (the gray byte per pixel, [n,S,S]: all pages of a group in one mnx_preprocess_batch, a twelfth of the
+    staged bytes; every output bit for bit the same)."""
+
+    image_format = "fp32"
 
     def __init__(self, model_path, device=None, max_batch: int = 32, dtype: str = DEFAULT_DTYPE,
-                 device_preprocess: bool = True):
+                 device_preprocess: bool = True, image_format: str = "fp32"):
         if model_path is None:
             raise ValueError("molnextr(model_path): a checkpoint path is required (pass 'synthetic' explicitly for the "
                              "deterministic test checkpoint)")
@@ -181,8 +186,11 @@ class molnextr:
         self.args = args
         self.tokenizer = get_tokenizer(args)
         self._states, self._max_batch = states, max_batch      # kept for the operand-range fallback (_with_fallback)
+        if image_format not in ("fp32", "gray8"):
+            raise ValueError(f"image_format must be 'fp32' or 'gray8', got {image_format!r}")
+        self.image_format = image_format
         self.engine = Engine(states["encoder"], states["decoder"], device=device.index or 0, max_batch=max_batch,
-                             dtype=dtype)
+                             dtype=dtype, image_format=image_format)
         self.input_size = args.input_size
         self.device_preprocess = device_preprocess
         self.group_images = 1024          # images per engine call of the throughput path (whole reference batches)
@@ -220,7 +228,7 @@ class molnextr:
         self._join_prefetch()
         self.engine.close()
         self.engine = Engine(self._states["encoder"], self._states["decoder"], device=dev, max_batch=self._max_batch,
-                             dtype=dtype)
+                             dtype=dtype, image_format=self.image_format)
 
     @staticmethod
     def _get_args(args_states=None):
@@ -240,8 +248,9 @@ class molnextr:
         bit-identical host restatement when `device_preprocess` is off. The result is a torch tensor of integer-exact
         arithmetic: it does not depend on the engine's operand mode and outlives the engine that made it."""
         if self.device_preprocess:
-            return (engine or self.engine).preprocess(images)
-        return torch.from_numpy(np.stack([transform_image(im, self.input_size) for im in images])).to(self.device)
+            return (engine or self.engine).preprocess(images)      # the engine carries the image format
+        host = transform_image_gray if self.image_format == "gray8" else transform_image
+        return torch.from_numpy(np.stack([host(im, self.input_size) for im in images])).to(self.device)
 
     _prefetch_thread = None       # the helper thread of the running _prefetched generator, if one is in flight
 

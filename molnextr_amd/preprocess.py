@@ -85,23 +85,41 @@ def resize_bilinear_u8(img: np.ndarray, size: int) -> np.ndarray:
     return np.clip(out, 0, 255).astype(np.uint8)
 
 
-def to_gray_rgb(img: np.ndarray) -> np.ndarray:
+def to_gray(img: np.ndarray) -> np.ndarray:
+    """cv2.cvtColor(RGB2GRAY) on HWC uint8: one byte per pixel."""
     g = (img[..., 0].astype(np.int64) * 4899 + img[..., 1].astype(np.int64) * 9617 +
          img[..., 2].astype(np.int64) * 1868 + 8192) >> 14
-    return np.repeat(g.astype(np.uint8)[..., None], 3, axis=2)
+    return g.astype(np.uint8)
 
 
-def transform_image(img: np.ndarray, input_size: int = 384, square: bool = False) -> np.ndarray:
-    """HWC uint8 RGB -> CHW float32, normalised: the tensor the device path takes. square: PadToSquare after CropWhite."""
+def to_gray_rgb(img: np.ndarray) -> np.ndarray:
+    return np.repeat(to_gray(img)[..., None], 3, axis=2)
+
+
+def transform_image_gray(img: np.ndarray, input_size: int = 384, square: bool = False) -> np.ndarray:
+    """HWC uint8 RGB -> uint8 [S,S]: the transform up to ToGray, i.e. everything that carries information — Normalize only
+    makes three affine copies of this byte (normalise_gray). What the device path takes with image_format "gray8"
+    (mnx_preprocess_batch MNX_IMG_GRAY8 writes the same bytes). square: PadToSquare after CropWhite."""
     if img.ndim == 2:
         img = np.repeat(img[..., None], 3, axis=2)
     img = np.ascontiguousarray(img[..., :3], dtype=np.uint8)
     page = crop_white(img, 50)
     if square:
         page = pad_to_square(page)
-    x = to_gray_rgb(resize_bilinear_u8(page, input_size)).astype(np.float32)
+    return np.ascontiguousarray(to_gray(resize_bilinear_u8(page, input_size)))
+
+
+def normalise_gray(gray: np.ndarray) -> np.ndarray:
+    """uint8 [S,S] -> CHW float32 [3,S,S]: Normalize(ImageNet) of the gray byte replicated to three channels, channel c =
+    (float32(g) - 255 mean[c]) * (1 / (255 std[c])) in fp32 — the two operations the device kernels perform."""
+    x = np.repeat(np.asarray(gray, dtype=np.uint8)[..., None], 3, axis=2).astype(np.float32)
     x = (x - MEAN * 255.0) * (1.0 / (STD * 255.0))
     return np.ascontiguousarray(x.transpose(2, 0, 1), dtype=np.float32)
+
+
+def transform_image(img: np.ndarray, input_size: int = 384, square: bool = False) -> np.ndarray:
+    """HWC uint8 RGB -> CHW float32, normalised: the tensor the device path takes. square: PadToSquare after CropWhite."""
+    return normalise_gray(transform_image_gray(img, input_size, square))
 
 
 def load_image_rgb(path: str) -> np.ndarray:
