@@ -195,6 +195,29 @@ int mnx_decode_forced(mnx_engine* h, const float* features, int32_t B, const int
                       const int32_t* forced_ids, int32_t* argmax_ids, int32_t* lengths, float* forced_logp,
                       float* logits_trace, void* stream);
 
+/* LABEL-GUIDED greedy decoding: coordinate prediction for a KNOWN structure, `TransformerDecoderAR.decode(..., labels=...)`
+ * (MolNexTR/components.py:253-334, the label handling at :284-332; decoding/greedy_search.py:76-127), which the reference
+ * reaches from main.py --predict_coords with labels = smiles_to_sequence(smiles, mask_ratio=1) (dataset.py:459-464,
+ * tokenization.py:429-462): every symbol a forced id, every atom's x and y '<mask>' (id 4). The guided sibling of
+ * mnx_decode_greedy: the same arguments (stop_on_eos = 1) and
+ *   labels     device int32 [B,L], L >= 2: column 0 '<sos>', a row ends with '<eos>' and is padded with '<pad>'; only the
+ *              first min(L, max_len + 1) ids of a row are read (copied to an engine-owned table, one row per decode slot,
+ *              allocated by the first guided call)
+ * Semantics, per row b and step s:
+ *   - the input of step s is labels[b][s] unless that is '<mask>', then the row's own pick of step s - 1; the grammar mask
+ *     follows that mixed id (components.py:300-303); the EOS ban at step 0 and the max_len finish are mnx_decode_greedy's;
+ *   - tokens[b][s] is the MERGED id: labels[b][s+1] unless that is '<mask>', then the own pick (components.py:331-332);
+ *     token_logp[b][s] is the own argmax's masked log-prob, at forced positions too — not the forced id's
+ *     (greedy_search.py:80,86; mnx_decode_forced differs in this); hidden is the model's own output of every step;
+ *   - while s + 1 < L the row finishes iff labels[b][s+1] is '<eos>' — its own '<eos>' at a masked position does not finish
+ *     it; finished rows leave the batch and the others' positional-encoding rows move up, labels travelling with their rows;
+ *   - OURS: a row still alive at step L - 1 and beyond (its label holds no '<eos>', or max_len + 1 < L cut it) goes on
+ *     free-running — own picks as input, finish on its own '<eos>' or at max_len — where the reference raises IndexError.
+ * MNX_ERR_INVALID_ARG: labels NULL or L < 2; MNX_ERR_CAPACITY as mnx_decode_greedy. Synchronous with respect to its outputs. */
+int mnx_decode_guided(mnx_engine* h, const float* features, int32_t B, const int32_t* chunk_id, int32_t max_len,
+                      const int32_t* labels, int32_t L, int32_t* tokens, int32_t* lengths, float* token_logp, float* hidden,
+                      float* logits_trace, void* stream);
+
 /* Beam search over one reference batch — the `beam_size > 1` branch of TransformerDecoderAR.decode
  * (MolNexTR/components.py:253-334 with decoding/beam_search.py). The reference's own branch cannot run;
  * the strategy follows BeamSearch.advance/update_finished (beam_search.py:84-190: average log-prob over emitted
@@ -320,6 +343,25 @@ int mnx_predict_confidence(mnx_engine* h, const float* images, int32_t n_img, in
 int mnx_predict_gray8(mnx_engine* h, const uint8_t* gray, int32_t n_img, int32_t ref_batch, int32_t max_len,
                       int32_t* tokens, int32_t* lengths, int32_t* n_atoms, int32_t* atom_idx, uint8_t* edges, int32_t kmax,
                       float* token_logp, double* edge_scores, double* atom_scores, double* overall_score, void* stream);
+
+/* The continuous-batching pipeline with LABELS: main.py --predict_coords of the reference (dataset.py:459-464 makes the
+ * labels, components.py:284-332 and greedy_search.py:76-127 decode along them, components.py:452-491 derives atoms, bonds and
+ * confidences from the merged ids, the own-pick scores and the own decoder outputs). Inputs and outputs of mnx_predict_gray8,
+ * every row decoded as mnx_decode_guided defines (its free-running extension beyond L included):
+ *   images     img_format MNX_IMG_F32: device fp32 [n_img,3,S,S]; MNX_IMG_GRAY8: device uint8 [n_img,S,S], 4-byte aligned.
+ *              The format travels as an argument; both give the same outputs bit for bit on the same bytes.
+ *   ref_batch  up to 512 under mnx_predict's capacity rules
+ *   labels     device int32 [n_img,L], L >= 2, row i belongs to image i; min(L, max_len + 1) ids of a row are copied to the
+ *              engine's per-slot label table on the decode stream when its reference batch is admitted (the table,
+ *              dec_slots x (cfg.max_len + 2) ids, is allocated by the first guided call and kept until mnx_destroy)
+ *   the four confidence pointers: all NULL or all set, as for mnx_predict_gray8
+ * Guided ticks replay graphs of their own; a guided job never invalidates the graphs of unguided ones.
+ * MNX_ERR_INVALID_ARG: labels NULL, L < 2, unknown img_format, misaligned gray, confidence pointers partly set;
+ * MNX_ERR_CAPACITY and MNX_ERR_RANGE as mnx_predict. Synchronous with respect to its outputs. */
+int mnx_predict_guided(mnx_engine* h, const void* images, int32_t img_format, int32_t n_img, int32_t ref_batch,
+                       int32_t max_len, const int32_t* labels, int32_t L, int32_t* tokens, int32_t* lengths, int32_t* n_atoms,
+                       int32_t* atom_idx, uint8_t* edges, int32_t kmax, float* token_logp, double* edge_scores,
+                       double* atom_scores, double* overall_score, void* stream);
 
 /* The confidence computation on its own (test aid and building block of mnx_predict_confidence; replaces the
  * compute_confidence lines of MolNexTR/components.py:456-469,485-491): tokens device int32 [n,T] (T <= 512), lengths

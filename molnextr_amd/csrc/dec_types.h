@@ -121,17 +121,29 @@ struct TokenClasses {
 
 // fp32 projected memory K / V of `n_blocks` (image, layer, K|V, head) blocks of S rows -> quantised blocks at dst (kvq.h)
 hipError_t kvq_pack_enqueue(const float* src, char* dst, int n_blocks, int S, int Sq, hipStream_t s);
+// Label-guided decoding (mnx_decode_guided / mnx_predict_guided): what an admission installs for its rows. The engine owns
+// `table`, [dec_slots][stride] ids, row of slot s = {n, labels[0 .. n - 1]}; src is the caller's device [rows, L] labels of
+// the rows being admitted, n = min(L, max_len + 1) <= stride - 1 the ids kept of each.
+constexpr int GUIDE_MASK = 4;      // '<mask>' of the tokenizer: a label position the model fills in itself
+struct GuideRows {
+    int* table;
+    int stride;
+    const int* src;
+    int L, n;
+};
+// g (both admits): also install the rows' labels (null: unguided)
 hipError_t dec_enqueue_admit(const DecBuffers& b, const int* slots_dev, const int* rowc_dev, int n, int chunk_tag,
-                             int mem_blk0, int max_len, int stop_on_eos, hipStream_t s);
+                             int mem_blk0, int max_len, int stop_on_eos, hipStream_t s, const GuideRows* g = nullptr);
 hipError_t dec_enqueue_reset(const DecBuffers& b, hipStream_t s);
 hipError_t dec_enqueue_status(const DecBuffers& b, int slots, hipStream_t s);
 // forced: [trace_rows, T] ids or null — teacher forcing of slots 0..trace_rows-1 (test aid, see HeadArgs)
+// glab: the label table (GuideRows::table, glab_stride ids per slot) or null — non-null runs the GUIDED greedy heads
 // fused_tile: 0 = the 8-launches-per-layer tick of decoder.hip (always used by beam search); 100 R + RC = the three-launches-
 // per-layer tick of dec_fused.hip with R (2, 4) rows per attention workgroup and RC (4, 8, 16) rows per feed-forward workgroup;
 // 2000 + 100 R + RC = its mid form (four launches per layer, bit-identical)
 hipError_t dec_enqueue_tick(const DecWeights& w, const DecBuffers& b, int slots_scan, int rows, float* logits_trace,
                             int trace_rows, hipStream_t s, const BeamBuffers* beam = nullptr, const int* forced = nullptr,
-                            int fused_tile = 0);
+                            int fused_tile = 0, const int* glab = nullptr, int glab_stride = 0);
 // dec_fused.hip
 hipError_t dec_fused_init();
 void dec_fused_dump_stamps(const char* path);   // lab aid (MNX_FUSED_STAMPS)
@@ -143,7 +155,7 @@ hipError_t beam_enqueue_gather(const DecBuffers& b, const BeamBuffers& bm, int o
 hipError_t dec_probe_attn(const DecWeights& w, const DecBuffers& b, int rows, int t, int iters, hipEvent_t* ev,
                           hipStream_t s);
 hipError_t dec_enqueue_admit_rows(const DecBuffers& b, const int* chunk_ids_dev, int n, int max_len, int stop_on_eos,
-                                  hipStream_t s);
+                                  hipStream_t s, const GuideRows* g = nullptr);
 hipError_t gather_enqueue(const DecBuffers& b, const int* slots_dev, int n_rows, int out_len, int* o_tokens, int* o_len,
                           float* o_logp, float* o_hidden, hipStream_t s);
 hipError_t atoms_enqueue(const DecBuffers& b, const TokenClasses* tc_dev, const int* slots_dev, int n, int kmax,

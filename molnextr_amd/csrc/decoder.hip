@@ -479,105 +479,44 @@ struct HeadArgs {
     int V, VP, T, x0, y0, eos, trace_rows;
 };
 
+// GUIDED heads only (label-guided decoding, mnx_decode_guided / mnx_predict_guided; reference components.py:284-332,
+// greedy_search.py:76-127): a second kernel argument, so that the unguided kernels keep their argument block as it is.
+struct GuideTab {
+    const int* lab;        // [slots, stride]: row of slot s = {n, labels[0], ..., labels[n - 1]}, n = ids held
+    int stride;
+};
+
+// What a GUIDED head does with its own pick `bi` (masked log-prob bv) of row `slot` at step t, on one thread:
+//   next = labels[t + 1] if t + 1 < n, else MASK          (n = ids held of the row's label; labels[0] is <sos>)
+//   the id that advances the row — next step's input, grammar-mask source and merged output token t — is `next` unless
+//   that is MASK, then the own pick (components.py:284-303,331-332);
+//   recorded score = bv, the own pick's, at forced positions too (greedy_search.py:80,86);
+//   finish: inside the label iff next == <eos> (an own <eos> at a masked position does not finish the row), beyond it
+//   (ours: the reference raises IndexError) on the own <eos>; and at max_len as always.
+__device__ __forceinline__ void guided_advance(const HeadArgs& a, int slot, int t, int next, bool inside, int bi, float bv) {
+    const int adv = next == GUIDE_MASK ? bi : next;
+    a.tokens[(size_t)slot * a.T + t] = adv;
+    a.token_logp[(size_t)slot * a.T + t] = bv;
+    a.st->prev_tok[slot] = adv;
+    a.st->len[slot] = t + 1;
+    a.st->t[slot] = t + 1;
+    const bool fin = inside ? next == a.eos : bi == a.eos;
+    if (fin || t + 1 >= a.st->max_len[slot]) a.st->alive[slot] = 0;
+}
+
 template <bool BEAM>
 __global__ __launch_bounds__(256) void dec_head_kernel(HeadArgs a) {
-    __shared__ float hv[256];
-    __shared__ float red[8];
-    __shared__ int redi[8];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int row = blockIdx.x;
-    const int4 rv = a.st->rowv[row];
-    const int n_act = a.st->n_active;
-    f32x4 xrow = *(const f32x4*)(a.x + (size_t)row * 256 + lane * 4);
-    if (a.tree_bias) {
-        const float* pp = a.part + (size_t)row * 256 + lane * 4;
-        const size_t ps = (size_t)a.part_stride;
-        f32x4 p[16];
-#pragma unroll
-        for (int z = 0; z < 16; ++z) p[z] = *(const f32x4*)(pp + z * ps);
-#pragma unroll
-        for (int w = 1; w < 16; w *= 2)
-#pragma unroll
-            for (int i = 0; i < 16; i += 2 * w) p[i] += p[i + w];
-        xrow = xrow + (p[0] + *(const f32x4*)(a.tree_bias + lane * 4));
-    } else if (a.part) {
-        const float* pp = a.part + (size_t)row * 256 + lane * 4;
-        const size_t ps = (size_t)a.part_stride;
-        f32x4 sum = *(const f32x4*)pp;
-        for (int z = 1; z < a.n_part; ++z) sum += *(const f32x4*)(pp + z * ps);
-        xrow = sum + xrow;
-    }
-    if (row >= n_act) return;
-    const int slot = rv.x, t = rv.y;
-    if (wave == 0) {
-        f32x4 v = xrow;
-        const float mean = wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.0f / 256.0f);
-        v -= mean;
-        const float var = wave_sum(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]) * (1.0f / 256.0f);
-        const f32x4 o = v * rsqrtf(var + 1e-6f) * *(const f32x4*)(a.gamma + lane * 4) + *(const f32x4*)(a.beta + lane * 4);
-        *(f32x4*)(hv + lane * 4) = o;
-        *(f32x4*)(a.hidden + ((size_t)slot * a.T + t) * 256 + lane * 4) = o;
-    }
-    __syncthreads();
-    const bool valid = tid < a.V;
-    float logit = -3.0e38f;
-    if (valid) {
-        float s = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll 8
-        for (int k = 0; k < 256; k += 4) {     // 32 independent coalesced loads in flight per unrolled body
-            s = fmaf(hv[k], a.wout_t[k * a.VP + tid], s);
-            s1 = fmaf(hv[k + 1], a.wout_t[(k + 1) * a.VP + tid], s1);
-            s2 = fmaf(hv[k + 2], a.wout_t[(k + 2) * a.VP + tid], s2);
-            s3 = fmaf(hv[k + 3], a.wout_t[(k + 3) * a.VP + tid], s3);
-        }
-        logit = (s + s1) + (s2 + s3) + a.bout[tid];
-        if (a.logits_trace && slot < a.trace_rows) a.logits_trace[((size_t)t * a.trace_rows + slot) * a.V + tid] = logit;
-    }
-    // log_softmax
-    float m = wave_max(logit);
-    if (lane == 0) red[wave] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    float e = valid ? expf(logit - m) : 0.f;
-    e = wave_sum(e);
-    if (lane == 0) red[4 + wave] = e;
-    __syncthreads();
-    const float lse = m + logf(red[4] + red[5] + red[6] + red[7]);
-    float lp = logit - lse;
-    const int prev = rv.z;
-    if (prev >= a.x0 && prev < a.y0) { if (tid < a.y0) lp = -10000.0f; }     // after an x-bin: only y-bins
-    else if (prev >= a.y0)           { if (tid >= a.x0) lp = -10000.0f; }    // after a y-bin: no coordinate bins
-    if (t == 0 && tid == a.eos) lp = -1e20f;                                  // min_length = 1
-    if (BEAM) {
-        if (valid) a.blp[(size_t)slot * BEAM_LP_STRIDE + tid] = lp;
-        return;
-    }
-    if (!valid) lp = -3.0e38f;
-    // argmax, lowest index wins ties (topk(1))
-    float bv = lp;
-    int bi = tid;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-    }
-    __syncthreads();
-    if (lane == 0) { red[wave] = bv; redi[wave] = bi; }
-    __syncthreads();
-    const int ftok = (a.forced && slot < a.trace_rows) ? a.forced[(size_t)slot * a.T + t] : -1;
-    if (ftok >= 0 && tid == ftok) a.token_logp[(size_t)slot * a.T + t] = lp;
-    if (tid == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (red[w] > bv || (red[w] == bv && redi[w] < bi)) { bv = red[w]; bi = redi[w]; }
-        a.tokens[(size_t)slot * a.T + t] = bi;
-        if (ftok < 0) a.token_logp[(size_t)slot * a.T + t] = bv;
-        const int adv = ftok >= 0 ? ftok : bi;
-        a.st->prev_tok[slot] = adv;
-        a.st->len[slot] = t + 1;
-        a.st->t[slot] = t + 1;
-        if ((a.st->stop_on_eos[slot] && adv == a.eos) || t + 1 >= a.st->max_len[slot]) a.st->alive[slot] = 0;
-    }
+#define MNX_HEAD_GUIDED 0
+#include "dec_head_body.inc"
+#undef MNX_HEAD_GUIDED
+}
+
+// Label-guided greedy head: the same text with the label bookkeeping compiled in (no runtime branch in either kernel)
+__global__ __launch_bounds__(256) void dec_head_guided_kernel(HeadArgs a, GuideTab g) {
+    constexpr bool BEAM = false;
+#define MNX_HEAD_GUIDED 1
+#include "dec_head_body.inc"
+#undef MNX_HEAD_GUIDED
 }
 
 // The head of the fused tick (dec_fused.hip): the same chain for one row on 1024 threads — the output layer's 232 x 256
@@ -585,118 +524,15 @@ __global__ __launch_bounds__(256) void dec_head_kernel(HeadArgs a) {
 // multiplying k in [64 kq, 64 kq + 64) (four interleaved fmaf chains, as dec_head_kernel's), the quarters summed
 // (q0 + q1) + (q2 + q3). Greedy only; everything after the logits is dec_head_kernel's code on the first 256 threads.
 __global__ __launch_bounds__(1024) void dec_head4_kernel(HeadArgs a) {
-    __shared__ float hv[256];
-    __shared__ float lq[4][256];
-    __shared__ float red[8];
-    __shared__ int redi[8];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = tid & 255, kq = tid >> 8;
-    const int row = blockIdx.x;
-    const int4 rv = a.st->rowv[row];
-    const int n_act = a.st->n_active;
-    const bool valid = col < a.V;
-    // requests in the order of need: the row's stream + partial planes (wave 0), then — a dummy row (capacity > alive rows)
-    // leaves here, before it asks for 237 KB of weights — the output layer's weights (16 per batch, 4 batches; they are not
-    // needed before the LayerNorm below)
-    f32x4 p[16];
-    f32x4 xv = {0.f, 0.f, 0.f, 0.f};
-    if (wave == 0) {
-        const float* pp = a.part + (size_t)row * 256 + lane * 4;
-        const size_t ps = (size_t)a.part_stride;
-#pragma unroll
-        for (int z = 0; z < 16; ++z) p[z] = *(const f32x4*)(pp + z * ps);
-        xv = *(const f32x4*)(a.x + (size_t)row * 256 + lane * 4);
-    }
-    if (row >= n_act) return;
-    float wk[16];
-    const float* wp = a.wout_t + (size_t)(64 * kq) * a.VP + (valid ? col : 0);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) wk[k] = wp[(size_t)k * a.VP];
-    if (wave == 0) {
-        f32x4 v = xv;
-#pragma unroll
-        for (int w = 1; w < 16; w *= 2)
-#pragma unroll
-            for (int i = 0; i < 16; i += 2 * w) p[i] += p[i + w];
-        v = v + (p[0] + *(const f32x4*)(a.tree_bias + lane * 4));
-        const float mean = wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.0f / 256.0f);
-        v -= mean;
-        const float var = wave_sum(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]) * (1.0f / 256.0f);
-        const f32x4 o = v * rsqrtf(var + 1e-6f) * *(const f32x4*)(a.gamma + lane * 4) + *(const f32x4*)(a.beta + lane * 4);
-        *(f32x4*)(hv + lane * 4) = o;
-        *(f32x4*)(a.hidden + ((size_t)rv.x * a.T + rv.y) * 256 + lane * 4) = o;
-    }
-    __syncthreads();
-    {
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        const float* hq = hv + 64 * kq;
-#pragma unroll
-        for (int kb = 0; kb < 64; kb += 16) {
-            float wn[16];
-            if (kb + 16 < 64) {
-#pragma unroll
-                for (int k = 0; k < 16; ++k) wn[k] = wp[(size_t)(kb + 16 + k) * a.VP];
-            }
-#pragma unroll
-            for (int k = 0; k < 16; k += 4) {
-                s0 = fmaf(hq[kb + k], wk[k], s0);
-                s1 = fmaf(hq[kb + k + 1], wk[k + 1], s1);
-                s2 = fmaf(hq[kb + k + 2], wk[k + 2], s2);
-                s3 = fmaf(hq[kb + k + 3], wk[k + 3], s3);
-            }
-            if (kb + 16 < 64) {
-#pragma unroll
-                for (int k = 0; k < 16; ++k) wk[k] = wn[k];
-            }
-        }
-        lq[kq][col] = (s0 + s1) + (s2 + s3);
-    }
-    __syncthreads();
-    const int slot = rv.x, t = rv.y;
-    float logit = -3.0e38f;
-    if (tid < 256 && valid) {
-        logit = ((lq[0][col] + lq[1][col]) + (lq[2][col] + lq[3][col])) + a.bout[col];
-        if (a.logits_trace && slot < a.trace_rows) a.logits_trace[((size_t)t * a.trace_rows + slot) * a.V + col] = logit;
-    }
-    // log_softmax (the first four waves hold the 232 logits, the others contribute neutral elements)
-    float m = wave_max(logit);
-    if (lane == 0 && wave < 4) red[wave] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    float e = (tid < 256 && valid) ? expf(logit - m) : 0.f;
-    e = wave_sum(e);
-    if (lane == 0 && wave < 4) red[4 + wave] = e;
-    __syncthreads();
-    const float lse = m + logf(red[4] + red[5] + red[6] + red[7]);
-    float lp = logit - lse;
-    const int prev = rv.z;
-    if (prev >= a.x0 && prev < a.y0) { if (col < a.y0) lp = -10000.0f; }     // after an x-bin: only y-bins
-    else if (prev >= a.y0)           { if (col >= a.x0) lp = -10000.0f; }    // after a y-bin: no coordinate bins
-    if (t == 0 && col == a.eos) lp = -1e20f;                                  // min_length = 1
-    if (!(tid < 256 && valid)) lp = -3.0e38f;
-    // argmax, lowest index wins ties (topk(1)); threads beyond the first 256 carry neutral elements
-    float bv = lp;
-    int bi = tid;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0 && wave < 4) { red[wave] = bv; redi[wave] = bi; }
-    __syncthreads();
-    const int ftok = (a.forced && slot < a.trace_rows) ? a.forced[(size_t)slot * a.T + t] : -1;
-    if (ftok >= 0 && tid == ftok) a.token_logp[(size_t)slot * a.T + t] = lp;
-    if (tid == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (red[w] > bv || (red[w] == bv && redi[w] < bi)) { bv = red[w]; bi = redi[w]; }
-        a.tokens[(size_t)slot * a.T + t] = bi;
-        if (ftok < 0) a.token_logp[(size_t)slot * a.T + t] = bv;
-        const int adv = ftok >= 0 ? ftok : bi;
-        a.st->prev_tok[slot] = adv;
-        a.st->len[slot] = t + 1;
-        a.st->t[slot] = t + 1;
-        if ((a.st->stop_on_eos[slot] && adv == a.eos) || t + 1 >= a.st->max_len[slot]) a.st->alive[slot] = 0;
-    }
+#define MNX_HEAD_GUIDED 0
+#include "dec_head4_body.inc"
+#undef MNX_HEAD_GUIDED
+}
+
+__global__ __launch_bounds__(1024) void dec_head4_guided_kernel(HeadArgs a, GuideTab g) {
+#define MNX_HEAD_GUIDED 1
+#include "dec_head4_body.inc"
+#undef MNX_HEAD_GUIDED
 }
 
 // Opens a tick: PE rank of every slot (rank among the alive slots of its chunk, by row index) and the alive
@@ -803,10 +639,22 @@ hipError_t dec_enqueue_reset(const DecBuffers& b, hipStream_t s) {
     return hipGetLastError();
 }
 
+// Guided admission: row i of g.src (the caller's [rows, L] labels) -> the label row of slot slots[i] (slot i when slots is
+// null) of the engine's table: {g.n, the first g.n ids}. One workgroup per row; g.n + 1 <= g.stride (the host guarantees it).
+__global__ __launch_bounds__(64) void dec_admit_labels_kernel(GuideRows g, const int* __restrict__ slots) {
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const int slot = slots ? slots[row] : row;
+    int* dst = g.table + (size_t)slot * g.stride;
+    const int* src = g.src + (size_t)row * g.L;
+    if (tid == 0) dst[0] = g.n;
+    for (int j = tid; j < g.n; j += 64) dst[1 + j] = src[j];
+}
+
 hipError_t dec_enqueue_admit(const DecBuffers& b, const int* slots_dev, const int* rowc_dev, int n, int chunk_tag,
-                             int mem_blk0, int max_len, int stop_on_eos, hipStream_t s) {
+                             int mem_blk0, int max_len, int stop_on_eos, hipStream_t s, const GuideRows* g) {
     hipLaunchKernelGGL(dec_admit_kernel, dim3(1), dim3(64), 0, s, b.st, slots_dev, rowc_dev, n, chunk_tag, mem_blk0,
                        max_len, stop_on_eos, 1);
+    if (g) hipLaunchKernelGGL(dec_admit_labels_kernel, dim3(n), dim3(64), 0, s, *g, slots_dev);
     return hipGetLastError();
 }
 
@@ -817,7 +665,9 @@ __global__ void beam_pick_kernel(DecState* st, BeamBuffers bm, const float* hidd
 // compact active list. slots_scan: state slots the begin kernel scans; rows: capacity of the compact active list this tick
 // is launched for (a multiple of 32, >= the number of alive slots — the host guarantees it).
 hipError_t dec_enqueue_tick(const DecWeights& w, const DecBuffers& b, int slots_scan, int rows, float* logits_trace,
-                            int trace_rows, hipStream_t s, const BeamBuffers* beam, const int* forced, int fused_tile) {
+                            int trace_rows, hipStream_t s, const BeamBuffers* beam, const int* forced, int fused_tile,
+                            const int* glab, int glab_stride) {
+    if (glab && (beam || forced)) return hipErrorInvalidValue;      // guided ticks are greedy ticks of their own: nothing enqueued
     if (beam) hipLaunchKernelGGL(beam_begin_kernel, dim3(1), dim3(256), 0, s, b.st, beam->B, beam->K, beam->ref_batch);
     else hipLaunchKernelGGL(dec_begin_kernel, dim3(1), dim3(BEGIN_THREADS), 0, s, b.st, slots_scan);
     const int D = 256, H = w.heads, T = b.T;
@@ -887,7 +737,11 @@ hipError_t dec_enqueue_tick(const DecWeights& w, const DecBuffers& b, int slots_
     h.tokens = b.tokens; h.token_logp = b.logp; h.hidden = b.hidden; h.logits_trace = logits_trace;
     h.V = w.vocab; h.VP = w.vpad; h.T = T; h.x0 = w.sym_offset; h.y0 = w.sym_offset + w.bins;
     h.eos = 2; h.trace_rows = trace_rows; h.forced = forced;
-    if (beam) {
+    const GuideTab gt{glab, glab_stride};
+    if (glab) {
+        if (fused) hipLaunchKernelGGL(dec_head4_guided_kernel, dim3(slots), dim3(1024), 0, s, h, gt);
+        else hipLaunchKernelGGL(dec_head_guided_kernel, dim3(slots), dim3(256), 0, s, h, gt);
+    } else if (beam) {
         h.blp = beam->blp;
         hipLaunchKernelGGL(dec_head_kernel<true>, dim3(slots), dim3(256), 0, s, h);
         hipLaunchKernelGGL(beam_pick_kernel, dim3(beam->B), dim3(256), 0, s, b.st, *beam, b.hidden, b.tokens, T, w.vocab, 2);
@@ -1259,8 +1113,9 @@ __global__ void dec_admit_rows_kernel(DecState* st, const int* chunk_ids, int n,
 }
 
 hipError_t dec_enqueue_admit_rows(const DecBuffers& b, const int* chunk_ids_dev, int n, int max_len, int stop_on_eos,
-                                  hipStream_t s) {
+                                  hipStream_t s, const GuideRows* g) {
     hipLaunchKernelGGL(dec_admit_rows_kernel, dim3(1), dim3(64), 0, s, b.st, chunk_ids_dev, n, max_len, stop_on_eos, 1);
+    if (g) hipLaunchKernelGGL(dec_admit_labels_kernel, dim3(n), dim3(64), 0, s, *g, (const int*)nullptr);
     return hipGetLastError();
 }
 

@@ -46,9 +46,9 @@ struct StageW {
 // op classes of the split modes (mnx_set_split_terms)
 enum { SPL_QKV = 1, SPL_ATTN = 2, SPL_PROJ = 4, SPL_FC1 = 8, SPL_FC2 = 16, SPL_MERGE = 32, SPL_ALL = 63 };
 struct GraphKey {
-    int slots, rows, trace, forced, tile;
+    int slots, rows, trace, forced, tile, guided;
     bool operator<(const GraphKey& o) const {
-        return std::tie(slots, rows, trace, forced, tile) < std::tie(o.slots, o.rows, o.trace, o.forced, o.tile);
+        return std::tie(slots, rows, trace, forced, tile, guided) < std::tie(o.slots, o.rows, o.trace, o.forced, o.tile, o.guided);
     }
 };
 
@@ -87,6 +87,8 @@ struct mnx_engine {
     DecBuffers db{};
     float* out_trace = nullptr;
     int* forced_ids = nullptr;  // [32, max_len] teacher-forcing ids of mnx_decode_forced (lazy; test aid)
+    int* guide_labels = nullptr;   // [dec_slots, max_len + 2] label row of every slot, {ids held, the ids}: label-guided decoding
+                                   // (mnx_decode_guided / mnx_predict_guided; lazy, written at admission — dec_types.h GuideRows)
     BeamBuffers beam{};        // allocated lazily on the first mnx_decode_beam
     int* prep_bbox = nullptr;  // scratch of mnx_preprocess
     int* prep_bbox_batch = nullptr;   // [MNX_PREP_MAX_PAGES][4]: scratch of mnx_preprocess_batch (its own: the two may not share)
@@ -948,8 +950,18 @@ int tick_tile(const mnx_engine* h, int rows) {
 }
 
 // One greedy tick on s: the begin kernel over `slots` slots, then the layers + head of `rows` rows of capacity
-hipError_t enqueue_tick(mnx_engine* h, int slots, int rows, float* trace, int trace_rows, hipStream_t s, const int* forced) {
-    return dec_enqueue_tick(h->dw, h->db, slots, rows, trace, trace_rows, s, nullptr, forced, tick_tile(h, rows));
+// (guided: the label-guided heads, reading h->guide_labels)
+hipError_t enqueue_tick(mnx_engine* h, int slots, int rows, float* trace, int trace_rows, hipStream_t s, const int* forced,
+                        bool guided = false) {
+    return dec_enqueue_tick(h->dw, h->db, slots, rows, trace, trace_rows, s, nullptr, forced, tick_tile(h, rows),
+                            guided ? h->guide_labels : nullptr, h->db.T + 2);
+}
+
+// The label table of guided decoding and what an admission of rows whose labels start at `src` installs from it
+int guide_rows(mnx_engine* h, const int32_t* src, int L, int max_len, GuideRows* g) {
+    MNXCHK(lazy_alloc(h, &h->guide_labels, (size_t)h->db.slots * (h->db.T + 2) * 4));
+    *g = GuideRows{h->guide_labels, h->db.T + 2, src, L, std::min(L, max_len + 1)};      // max_len <= T: n + 1 <= stride
+    return MNX_OK;
 }
 
 // Captures what enqueue() puts on s into a graph and instantiates it; the hipGraph_t is released on every path
@@ -977,13 +989,14 @@ int capture_graph(mnx_engine* h, const char* what, hipStream_t s, F&& enqueue, h
 
 // The graph of one greedy tick, captured on first use and kept until mnx_destroy (null under MNX_NO_GRAPH)
 int get_tick_graph(mnx_engine* h, int slots, int rows, float* trace, int trace_rows, hipStream_t s, hipGraphExec_t* out,
-                   const int* forced = nullptr) {
+                   const int* forced = nullptr, bool guided = false) {
     *out = nullptr;
     if (!h->use_graph) return MNX_OK;
-    const GraphKey key{slots, rows, trace ? trace_rows : 0, forced ? trace_rows : 0, tick_tile(h, rows)};
+    // guided ticks are graphs of their own: an unguided graph is never recaptured because a guided job ran
+    const GraphKey key{slots, rows, trace ? trace_rows : 0, forced ? trace_rows : 0, tick_tile(h, rows), guided ? 1 : 0};
     auto it = h->graphs.find(key);
     if (it != h->graphs.end()) { *out = it->second; return MNX_OK; }
-    MNXCHK(capture_graph(h, "decode tick", s, [&]() { return enqueue_tick(h, slots, rows, trace, trace_rows, s, forced); }, out));
+    MNXCHK(capture_graph(h, "decode tick", s, [&]() { return enqueue_tick(h, slots, rows, trace, trace_rows, s, forced, guided); }, out));
     h->graphs[key] = *out;
     return MNX_OK;
 }
@@ -1005,11 +1018,12 @@ int run_steps(mnx_engine* h, hipGraphExec_t exec, F&& enqueue, int slots, int ma
 
 int decode_greedy_impl(mnx_engine* h, const float* features, int32_t B, const int32_t* chunk_id, int32_t max_len,
                        int32_t stop_on_eos, const int32_t* forced_ids, int32_t* tokens, int32_t* lengths, float* token_logp,
-                       float* hidden, float* logits_trace, void* stream) {
+                       float* hidden, float* logits_trace, void* stream, const int32_t* labels = nullptr, int32_t L = 0) {
     if (!h) return MNX_ERR_INVALID_ARG;
-    if (!features || !tokens || !lengths || B < 1) { h->err = "mnx_decode_greedy: null/empty argument"; return MNX_ERR_INVALID_ARG; }
+    const std::string fn = labels ? "mnx_decode_guided" : "mnx_decode_greedy";
+    if (!features || !tokens || !lengths || B < 1) { h->err = fn + ": null/empty argument"; return MNX_ERR_INVALID_ARG; }
     if (B > ROW_TILE || max_len < 1 || max_len > h->cfg.max_len) {
-        h->err = "mnx_decode_greedy: B must be <= 32 and max_len <= cfg.max_len";
+        h->err = fn + ": B must be <= 32 and max_len <= cfg.max_len";
         return MNX_ERR_CAPACITY;
     }
     const mnx_config& c = h->cfg;
@@ -1017,7 +1031,9 @@ int decode_greedy_impl(mnx_engine* h, const float* features, int32_t B, const in
     MNXCHK(caller_stream(h, stream, &s));
     MNXCHK(project_memory(h, features, B, 0, s));     // memory block i = row i
     HIPCHK(h, dec_enqueue_reset(h->db, s));
-    HIPCHK(h, dec_enqueue_admit_rows(h->db, chunk_id, B, max_len, stop_on_eos, s));
+    GuideRows guide{};
+    if (labels) MNXCHK(guide_rows(h, labels, L, max_len, &guide));
+    HIPCHK(h, dec_enqueue_admit_rows(h->db, chunk_id, B, max_len, stop_on_eos, s, labels ? &guide : nullptr));
     float* trace = nullptr;
     if (logits_trace) {
         MNXCHK(lazy_alloc(h, &h->out_trace, (size_t)c.max_len * ROW_TILE * c.vocab * 4));
@@ -1031,8 +1047,9 @@ int decode_greedy_impl(mnx_engine* h, const float* features, int32_t B, const in
         forced = h->forced_ids;
     }
     hipGraphExec_t exec = nullptr;
-    MNXCHK(get_tick_graph(h, ROW_TILE, ROW_TILE, trace, B, s, &exec, forced));
-    MNXCHK(run_steps(h, exec, [&]() { return enqueue_tick(h, ROW_TILE, ROW_TILE, trace, B, s, forced); }, ROW_TILE, max_len, s));
+    const bool guided = labels != nullptr;
+    MNXCHK(get_tick_graph(h, ROW_TILE, ROW_TILE, trace, B, s, &exec, forced, guided));
+    MNXCHK(run_steps(h, exec, [&]() { return enqueue_tick(h, ROW_TILE, ROW_TILE, trace, B, s, forced, guided); }, ROW_TILE, max_len, s));
     HIPCHK(h, gather_enqueue(h->db, nullptr, B, max_len, tokens, lengths, token_logp, hidden, s));
     if (logits_trace) HIPCHK(h, hipMemcpyAsync(logits_trace, trace, (size_t)max_len * B * c.vocab * 4, hipMemcpyDeviceToDevice, s));
     HIPCHK(h, hipStreamSynchronize(s));
@@ -1095,6 +1112,14 @@ int mnx_decode_forced(mnx_engine* h, const float* features, int32_t B, const int
     if (h && !forced_ids) { h->err = "mnx_decode_forced: forced_ids is null"; return MNX_ERR_INVALID_ARG; }
     return decode_greedy_impl(h, features, B, chunk_id, max_len, 1, forced_ids, argmax_ids, lengths, forced_logp, nullptr,
                               logits_trace, stream);
+}
+
+int mnx_decode_guided(mnx_engine* h, const float* features, int32_t B, const int32_t* chunk_id, int32_t max_len,
+                      const int32_t* labels, int32_t L, int32_t* tokens, int32_t* lengths, float* token_logp, float* hidden,
+                      float* logits_trace, void* stream) {
+    if (h && (!labels || L < 2)) { h->err = "mnx_decode_guided: labels is null or L < 2"; return MNX_ERR_INVALID_ARG; }
+    return decode_greedy_impl(h, features, B, chunk_id, max_len, 1, nullptr, tokens, lengths, token_logp, hidden, logits_trace,
+                              stream, labels, L);
 }
 
 int mnx_decode_beam(mnx_engine* h, const float* features, int32_t B, int32_t beam, int32_t n_best, int32_t max_len,
@@ -1282,7 +1307,8 @@ struct ConfOut {
 // with `conf`, of mnx_predict_confidence. Without `conf` it enqueues exactly mnx_predict's launches.
 static int predict_impl(mnx_engine* h, const char* name, const void* images, int img_fmt, int32_t n_img, int32_t ref_batch,
                         int32_t max_len, int32_t stop_on_eos, int32_t* tokens, int32_t* lengths, int32_t* n_atoms,
-                        int32_t* atom_idx, uint8_t* edges, int32_t kmax, const ConfOut* conf, void* stream) {
+                        int32_t* atom_idx, uint8_t* edges, int32_t kmax, const ConfOut* conf, void* stream,
+                        const int32_t* labels = nullptr, int32_t L = 0) {
     if (!h) return MNX_ERR_INVALID_ARG;
     if (!images || !tokens || !lengths || !n_atoms || !atom_idx || !edges || n_img < 1 ||
         (conf && (!conf->edge_scores || !conf->atom_scores || !conf->overall))) {
@@ -1310,6 +1336,9 @@ static int predict_impl(mnx_engine* h, const char* name, const void* images, int
     }
     hipStream_t s;
     MNXCHK(caller_stream(h, stream, &s));
+    const bool guided = labels != nullptr;      // label-guided: rows carry labels [n_img, L] (mnx_predict_guided)
+    GuideRows guide{};
+    if (guided) MNXCHK(guide_rows(h, labels, L, max_len, &guide));
     const int n_chunks = (n_img + ref_batch - 1) / ref_batch;
     // A chunk (one reference batch) holds ceil(n / 32) row tiles, not necessarily contiguous; tile j holds its rows
     // 32 j .. 32 j + 31 in slots tile * 32 + i, memory K/V blocks likewise, and its slot list at slot_lists[tile]. The chunk's
@@ -1374,8 +1403,9 @@ static int predict_impl(mnx_engine* h, const char* name, const void* images, int
                 int* sl_pin = pin_slots + (size_t)tile * ROW_TILE;     // pinned, private to this tile until its chunk retires
                 for (int i = 0; i < nj; ++i) sl_pin[i] = tile * ROW_TILE + i;
                 HIPCHK(h, hipMemcpyAsync(sl_dev, sl_pin, (size_t)nj * 4, hipMemcpyHostToDevice, s));
+                guide.src = guided ? labels + (size_t)(first + j * ROW_TILE) * L : nullptr;     // labels travel with their rows
                 HIPCHK(h, dec_enqueue_admit(h->db, sl_dev, h->rowc_seq + j * ROW_TILE, nj, ck.tag, tile * ROW_TILE, max_len,
-                                            stop_on_eos ? 1 : 0, s));
+                                            stop_on_eos ? 1 : 0, s, guided ? &guide : nullptr));
             }
             bound += n;
             admits.emplace_back(seq, n);
@@ -1396,9 +1426,9 @@ static int predict_impl(mnx_engine* h, const char* name, const void* images, int
             for (int t : ck.tiles) hi_tile = std::max(hi_tile, t);
         const int scan = std::min(SL, std::max(((hi_tile + 1) * ROW_TILE + 1023) / 1024 * 1024, rows_cap));
         hipGraphExec_t exec = nullptr;
-        MNXCHK(get_tick_graph(h, scan, rows_cap, nullptr, 0, s, &exec));
+        MNXCHK(get_tick_graph(h, scan, rows_cap, nullptr, 0, s, &exec, nullptr, guided));
         for (int i = 0; i < ticks_per_poll; ++i)
-            HIPCHK(h, exec ? hipGraphLaunch(exec, s) : enqueue_tick(h, scan, rows_cap, nullptr, 0, s, nullptr));
+            HIPCHK(h, exec ? hipGraphLaunch(exec, s) : enqueue_tick(h, scan, rows_cap, nullptr, 0, s, nullptr, guided));
         HIPCHK(h, dec_enqueue_status(h->db, scan, s));
         int* snap = pinned + (seq & 1) * (1 + MAX_CHUNKS);
         HIPCHK(h, hipMemcpyAsync(snap, &h->db.st->n_active, (size_t)(1 + MAX_CHUNKS) * 4, hipMemcpyDeviceToHost, s));
@@ -1485,6 +1515,26 @@ int mnx_predict_gray8(mnx_engine* h, const uint8_t* gray, int32_t n_img, int32_t
     const ConfOut conf{token_logp, edge_scores, atom_scores, overall_score};
     return predict_impl(h, "mnx_predict_gray8", gray, MNX_IMG_GRAY8, n_img, ref_batch, max_len, 1, tokens, lengths, n_atoms,
                         atom_idx, edges, kmax, n_conf ? &conf : nullptr, stream);
+}
+
+int mnx_predict_guided(mnx_engine* h, const void* images, int32_t img_format, int32_t n_img, int32_t ref_batch,
+                       int32_t max_len, const int32_t* labels, int32_t L, int32_t* tokens, int32_t* lengths, int32_t* n_atoms,
+                       int32_t* atom_idx, uint8_t* edges, int32_t kmax, float* token_logp, double* edge_scores,
+                       double* atom_scores, double* overall_score, void* stream) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    if (!labels || L < 2) { h->err = "mnx_predict_guided: labels is null or L < 2"; return MNX_ERR_INVALID_ARG; }
+    if (img_format != MNX_IMG_F32 && img_format != MNX_IMG_GRAY8) {
+        h->err = "mnx_predict_guided: img_format must be MNX_IMG_F32 or MNX_IMG_GRAY8";
+        return MNX_ERR_INVALID_ARG;
+    }
+    const int n_conf = !!token_logp + !!edge_scores + !!atom_scores + !!overall_score;
+    if (n_conf != 0 && n_conf != 4) {
+        h->err = "mnx_predict_guided: the four confidence pointers must be all NULL or all set";
+        return MNX_ERR_INVALID_ARG;
+    }
+    const ConfOut conf{token_logp, edge_scores, atom_scores, overall_score};
+    return predict_impl(h, "mnx_predict_guided", images, img_format, n_img, ref_batch, max_len, 1, tokens, lengths, n_atoms,
+                        atom_idx, edges, kmax, n_conf ? &conf : nullptr, stream, labels, L);
 }
 
 int mnx_gemm_clock(mnx_engine* h, int32_t reset, double* mhz) {

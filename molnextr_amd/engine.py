@@ -25,7 +25,7 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
            "mnx_probe_decode_attn", "mnx_predict_beam", "mnx_set_split_terms", "mnx_encoder_status",
            "mnx_gemm16_split", "mnx_decode_forced", "mnx_gemm_clock", "mnx_probe_mfma", "mnx_set_op_terms",
            "mnx_predict_confidence", "mnx_confidence", "mnx_window_attn", "mnx_kv_block", "mnx_preprocess_batch",
-           "mnx_encode_gray8", "mnx_predict_gray8")
+           "mnx_encode_gray8", "mnx_predict_gray8", "mnx_decode_guided", "mnx_predict_guided")
 
 # Encoder operand modes (include/molnextr_hip.h MNX_DTYPE_*). "fp16x3" — split fp16 operands, three MFMA terms per
 # product, fp32-class results — is the default: it is the fastest mode whose results stay a factor of four inside north_star's
@@ -166,6 +166,10 @@ def load_library():
     lib.mnx_encode_gray8.argtypes = [vp, vp, i32, vp, vp]
     lib.mnx_predict_gray8.restype = C.c_int
     lib.mnx_predict_gray8.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.mnx_decode_guided.restype = C.c_int
+    lib.mnx_decode_guided.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.mnx_predict_guided.restype = C.c_int
+    lib.mnx_predict_guided.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
     lib.mnx_decode_beam.restype = C.c_int
     lib.mnx_decode_beam.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.mnx_predict.restype = C.c_int
@@ -180,6 +184,24 @@ def load_library():
         raise ImportError(f"libmolnextr_hip.so ABI {lib.mnx_abi_version()} != binding ABI {ABI_VERSION}; rebuild")
     _lib = lib
     return lib
+
+
+def check_labels(labels, n: int, free_run=False) -> torch.Tensor:
+    """Labels of guided decoding as a contiguous int32 [n, L] tensor (on the device it came from): L >= 2, and an '<eos>'
+    (id 2) in every row that free_run does not exempt. A row without one would decode past its label, which the reference
+    answers with IndexError and the library with free-running (include/molnextr_hip.h); asking for that takes free_run:
+    True for every row, or one bool per row (the rows of a job that were cut at max_len, say)."""
+    lab = torch.as_tensor(labels)
+    if lab.dim() != 2 or lab.shape[0] != n or lab.shape[1] < 2:
+        raise ValueError(f"labels must be [n = {n}, L >= 2], got {tuple(lab.shape)}")
+    lab = lab.to(dtype=torch.int32).contiguous()
+    exempt = torch.as_tensor(free_run, dtype=torch.bool).reshape(-1)
+    if exempt.numel() not in (1, n):
+        raise ValueError(f"free_run must be a bool or {n} bools (one per label row), got {exempt.numel()}")
+    bad = (~(lab == 2).any(dim=1).cpu() & ~exempt.expand(n)).nonzero().flatten().tolist()
+    if bad:
+        raise ValueError(f"label rows {bad[:8]} hold no '<eos>' (free_run exempts rows that are meant to run on freely)")
+    return lab
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -374,6 +396,30 @@ class Engine:
         self._check(rc, "mnx_decode_greedy")
         return {"tokens": tokens, "lengths": lengths, "token_logp": logp, "hidden": hidden, "logits": trace}
 
+    def decode_guided(self, features: torch.Tensor, labels, chunk_id: Optional[torch.Tensor] = None,
+                      max_len: Optional[int] = None, want_hidden: bool = True, want_logp: bool = True,
+                      trace_logits: bool = False, free_run=False) -> dict:
+        """Label-guided greedy decode of up to ROWS_PER_DECODE rows (mnx_decode_guided; the reference's
+        TransformerDecoderAR.decode(labels=...)): labels [B,L] int, '<sos>' first, forced ids, '<mask>' (4) where the model
+        fills in, '<eos>', '<pad>'. Returns decode_greedy's dict: 'tokens' are the merged ids, 'token_logp' the own picks'.
+        A row without '<eos>' raises ValueError unless free_run exempts it (check_labels: a bool, or one per row)."""
+        assert features.is_cuda and features.dtype == torch.float32 and features.is_contiguous()
+        B = features.shape[0]
+        max_len = self.max_len if max_len is None else max_len
+        dev = features.device
+        lab = check_labels(labels, B, free_run).to(dev)
+        tokens = torch.empty(B, max_len, dtype=torch.int32, device=dev)
+        lengths = torch.empty(B, dtype=torch.int32, device=dev)
+        logp = torch.empty(B, max_len, dtype=torch.float32, device=dev) if want_logp else None
+        hidden = torch.empty(B, max_len, self.dec.d_model, dtype=torch.float32, device=dev) if want_hidden else None
+        trace = torch.empty(max_len, B, self.dec.vocab, dtype=torch.float32, device=dev) if trace_logits else None
+        if chunk_id is not None:
+            chunk_id = chunk_id.to(device=dev, dtype=torch.int32).contiguous()
+        rc = self.lib.mnx_decode_guided(self.h, _ptr(features), B, _ptr(chunk_id), max_len, _ptr(lab), lab.shape[1],
+                                        _ptr(tokens), _ptr(lengths), _ptr(logp), _ptr(hidden), _ptr(trace), _stream())
+        self._check(rc, "mnx_decode_guided")
+        return {"tokens": tokens, "lengths": lengths, "token_logp": logp, "hidden": hidden, "logits": trace}
+
     def decode_forced(self, features: torch.Tensor, forced_ids: torch.Tensor, max_len: Optional[int] = None,
                       trace_logits: bool = False) -> dict:
         """Teacher-forced greedy decode (test aid, mnx_decode_forced): rows advance with forced_ids [B,max_len] (each
@@ -563,7 +609,8 @@ class Engine:
         return min(self.MAX_REF_BATCH, self.max_batch, self.dec_slots, self.dec.pe_len)
 
     def predict(self, images: torch.Tensor, ref_batch: int = 32, max_len: Optional[int] = None,
-                stop_on_eos: bool = True, beam: int = 1, confidence: bool = False) -> dict:
+                stop_on_eos: bool = True, beam: int = 1, confidence: bool = False, labels=None,
+                free_run=False) -> dict:
         """Encoder + decode + atom positions + bond head for all images: greedy with continuous batching (mnx_predict),
         or beam search reference batch by reference batch with the encoder running ahead (mnx_predict_beam; adds
         'scores', the average log-prob of the returned hypothesis). Images are decoded as consecutive reference batches of
@@ -572,8 +619,15 @@ class Engine:
         that MnxError (MNX_ERR_CAPACITY) names the bound. confidence=True (greedy, stop_on_eos only):
         mnx_predict_confidence, which adds 'token_logp' [n,max_len] fp32, 'edge_scores' [n,kmax,kmax], 'atom_scores'
         [n,kmax] and 'overall_score' [n] fp64. images: fp32 [n,3,S,S] normalised, or uint8 [n,S,S] gray bytes
-        (mnx_predict_gray8: greedy with stop_on_eos only; beam search stays on fp32 images) — the same results bit for bit."""
+        (mnx_predict_gray8: greedy with stop_on_eos only; beam search stays on fp32 images) — the same results bit for bit.
+        labels [n,L] (see decode_guided): label-guided decoding of every image along its row (mnx_predict_guided; greedy with
+        stop_on_eos only, either image format, with or without confidences). A row without '<eos>' raises ValueError unless
+        free_run exempts it (check_labels: a bool, or one per row); an exempt row runs on freely beyond its label."""
         gray = self._is_gray(images)
+        if labels is not None:
+            if beam > 1 or not stop_on_eos:
+                raise ValueError("labels go with greedy decoding and stop_on_eos=True (beam search with labels is not built)")
+            labels = check_labels(labels, images.shape[0], free_run).to(images.device)
         if gray and beam > 1:
             raise ValueError("beam search takes fp32 images: the library has no gray-byte beam entry point (mnx_predict_beam "
                              "reads [n,3,S,S] fp32); use preprocess_batch(out='fp32') or image_format='fp32'")
@@ -597,10 +651,17 @@ class Engine:
             edge_scores = torch.zeros(n, k, k, dtype=torch.float64, device=dev)
             atom_scores = torch.zeros(n, k, dtype=torch.float64, device=dev)
             overall = torch.zeros(n, dtype=torch.float64, device=dev)
-            fn = "mnx_predict_gray8" if gray else "mnx_predict_confidence"
-            rc = getattr(self.lib, fn)(self.h, _ptr(images), n, ref_batch, max_len, _ptr(tokens), _ptr(lengths),
-                                       _ptr(n_atoms), _ptr(atom_idx), _ptr(edges), k, _ptr(logp), _ptr(edge_scores),
-                                       _ptr(atom_scores), _ptr(overall), _stream())
+            if labels is not None:
+                fn = "mnx_predict_guided"
+                rc = self.lib.mnx_predict_guided(self.h, _ptr(images), int(gray), n, ref_batch, max_len, _ptr(labels),
+                                                 labels.shape[1], _ptr(tokens), _ptr(lengths), _ptr(n_atoms), _ptr(atom_idx),
+                                                 _ptr(edges), k, _ptr(logp), _ptr(edge_scores), _ptr(atom_scores),
+                                                 _ptr(overall), _stream())
+            else:
+                fn = "mnx_predict_gray8" if gray else "mnx_predict_confidence"
+                rc = getattr(self.lib, fn)(self.h, _ptr(images), n, ref_batch, max_len, _ptr(tokens), _ptr(lengths),
+                                           _ptr(n_atoms), _ptr(atom_idx), _ptr(edges), k, _ptr(logp), _ptr(edge_scores),
+                                           _ptr(atom_scores), _ptr(overall), _stream())
             self._check(rc, fn)
             return {"tokens": tokens, "lengths": lengths, "n_atoms": n_atoms, "atom_idx": atom_idx, "edges": edges,
                     "token_logp": logp, "edge_scores": edge_scores, "atom_scores": atom_scores, "overall_score": overall}
@@ -611,6 +672,12 @@ class Engine:
             self._check(rc, "mnx_predict_beam")
             return {"tokens": tokens, "lengths": lengths, "n_atoms": n_atoms, "atom_idx": atom_idx, "edges": edges,
                     "scores": scores}
+        if labels is not None:
+            rc = self.lib.mnx_predict_guided(self.h, _ptr(images), int(gray), n, ref_batch, max_len, _ptr(labels),
+                                             labels.shape[1], _ptr(tokens), _ptr(lengths), _ptr(n_atoms), _ptr(atom_idx),
+                                             _ptr(edges), k, None, None, None, None, _stream())
+            self._check(rc, "mnx_predict_guided")
+            return {"tokens": tokens, "lengths": lengths, "n_atoms": n_atoms, "atom_idx": atom_idx, "edges": edges}
         if gray:
             rc = self.lib.mnx_predict_gray8(self.h, _ptr(images), n, ref_batch, max_len, _ptr(tokens), _ptr(lengths),
                                             _ptr(n_atoms), _ptr(atom_idx), _ptr(edges), k, None, None, None, None, _stream())

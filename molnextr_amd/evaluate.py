@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from . import shard
-from .tokenizer import get_tokenizer
+from .tokenizer import coords_labels, get_tokenizer
 
 
 def sampler_indices(n: int, rank: int, world: int) -> List[int]:
@@ -86,10 +86,15 @@ MAX_BATCH_SIZE = 256      # --batch_size: per-rank reference batches of 2 x 256 
 
 
 def run_inference(engine, load_image: Callable[[int], np.ndarray], n_items: int, batch_size: int, rank: int = 0,
-                  world: int = 1, tokenizer=None, group: int = 512, pad_to_square: bool = False) -> Dict[int, dict]:
+                  world: int = 1, tokenizer=None, group: int = 512, pad_to_square: bool = False,
+                  smiles: Optional[Sequence[str]] = None) -> Dict[int, dict]:
     """valid_fn for this rank's shard, then the gather: returns {dataset index: prediction dict} on every rank
     (the reference keeps it on all ranks too, main.py:295-301). `engine`: molnextr_amd.engine.Engine.
-    pad_to_square: the PadToSquare step `get_transforms` inserts for the test files in PAD_TO_SQUARE_FILES."""
+    pad_to_square: the PadToSquare step `get_transforms` inserts for the test files in PAD_TO_SQUARE_FILES.
+    smiles: the known structure of every item (main.py --predict_coords): item i is decoded along
+    smiles_to_sequence(smiles[i], mask_ratio=1) cut to max_len ids (dataset.py:459-464,473), label-guided. Only a row
+    that the cut shortened, and so lost its '<eos>', is passed on as free-running; every other row goes through the
+    engine's refusal of labels without '<eos>'."""
     tok = (tokenizer or get_tokenizer())["chartok_coords"]
     ref_batch = batch_size * 2
     cap = getattr(engine, "MAX_REF_BATCH", engine.ROWS_PER_DECODE)     # rows of one reference batch on the greedy path
@@ -114,7 +119,11 @@ def run_inference(engine, load_image: Callable[[int], np.ndarray], n_items: int,
         for g0 in range(0, len(mine), step):
             ids = mine[g0:g0 + step]
             x = engine.preprocess([load_image(i) for i in ids], pad_to_square=pad_to_square)
-            out = engine.predict(x, ref_batch=ref_batch)
+            guide = {}
+            if smiles is not None:
+                lab, cut = coords_labels(tok, [smiles[i] for i in ids], engine.max_len)
+                guide = {"labels": lab, "free_run": cut}      # a label cut at max_len has no '<eos>': its row ends at max_len
+            out = engine.predict(x, ref_batch=ref_batch, **guide)
             recs.append(shard.pack_records_device(out["tokens"], out["lengths"], out["atom_idx"], out["n_atoms"],
                                                   out["edges"]))
     except MnxError as err:
@@ -219,6 +228,10 @@ def main(argv=None):
     ap.add_argument("--image_format", default="fp32", choices=["fp32", "gray8"],
                     help="what the transform hands to the encoder: fp32 = normalised [n,3,S,S], one mnx_preprocess per page; gray8 = "
                          "the gray byte per pixel, all pages of a group in one mnx_preprocess_batch (same predictions bit for bit)")
+    ap.add_argument("--predict_coords", action="store_true",
+                    help="the reference's main.py --predict_coords: the test file's SMILES column is the known structure of every "
+                         "image; decoding is guided along it and only the atom coordinates are predicted. Writes image_id, SMILES "
+                         "(the input string), node_coords (main.py:534-535)")
     args = ap.parse_args(argv)
     if not 1 <= args.batch_size <= MAX_BATCH_SIZE:
         ap.error(f"--batch_size must be 1..{MAX_BATCH_SIZE} (reference batches of 2 x batch_size <= {2 * MAX_BATCH_SIZE} rows)")
@@ -237,9 +250,12 @@ def main(argv=None):
                     image_format=args.image_format)
     df = pd.read_csv(os.path.join(args.data_path, args.test_file))
     paths = [os.path.join(args.data_path, p) for p in df["file_path"]]
+    if args.predict_coords and "SMILES" not in df.columns:
+        ap.error("--predict_coords needs a SMILES column in --test_file")
+    known = ["" if pd.isna(s) else str(s) for s in df["SMILES"]] if args.predict_coords else None      # an empty cell: no atoms
     def infer(e):
         return run_inference(e, lambda i: load_image_rgb(paths[i]), len(df), args.batch_size, rank, world,
-                             pad_to_square=args.test_file in PAD_TO_SQUARE_FILES)
+                             pad_to_square=args.test_file in PAD_TO_SQUARE_FILES, smiles=known)
     try:
         preds = infer(engine)
     except RangeFallback as err:
@@ -258,7 +274,11 @@ def main(argv=None):
         if "image_id" not in df.columns:    # main.py:461-462
             df["image_id"] = [p.split("/")[-1].split(".")[0] for p in df["file_path"]]
         table = predictions_table(df["image_id"], preds)
-        scores = smiles_scores(df["SMILES"], table["SMILES"]) if "SMILES" in df.columns else None
+        if args.predict_coords:      # main.py:534-535: the known structure and where its atoms are
+            table = {"image_id": table["image_id"], "SMILES": known, "node_coords": table["node_coords"]}
+            scores = None            # the SMILES column is the input here: there is no predicted string to score
+        else:
+            scores = smiles_scores(df["SMILES"], table["SMILES"]) if "SMILES" in df.columns else None
         print(write_predictions(args.save_path, args.test_file, table, scores), json.dumps(scores))
     if world > 1:
         dist.barrier()

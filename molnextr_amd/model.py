@@ -19,7 +19,7 @@ import torch
 from . import weights as W
 from .engine import DEFAULT_DTYPE, Engine, MnxError
 from .preprocess import load_image_rgb, transform_image, transform_image_gray
-from .tokenizer import get_tokenizer
+from .tokenizer import coords_labels, get_tokenizer
 
 BOND_TYPES = ["", "single", "double", "triple", "aromatic", "solid wedge", "dashed wedge"]  # reference model.py:30
 ROWS = Engine.ROWS_PER_DECODE
@@ -100,7 +100,8 @@ def decode_batch(engine: Engine, features: torch.Tensor, tokenizer=None, ref_bat
 
 
 def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_batch_size: int = 16,
-                     max_len: Optional[int] = None, beam_size: int = 1, compute_confidence: bool = False) -> List[dict]:
+                     max_len: Optional[int] = None, beam_size: int = 1, compute_confidence: bool = False,
+                     labels=None, free_run=False) -> List[dict]:
     """Encoder + Decoder.decode for MANY images through the engine's continuous-batching path (mnx_predict):
     same per-image dicts as `decode_batch`, identical results (the on-device atom scan equals
     sequence_to_smiles' indices), much higher throughput. compute_confidence=True: mnx_predict_confidence, the same
@@ -108,14 +109,20 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
     decode_batch(compute_confidence=True) ('atom_scores' in 'chartok_coords', 'edge_scores', 'overall_score').
     beam_size > 1: mnx_predict_beam (best hypothesis per image, 'beam_scores' = [its average log-prob]); no confidences.
     ref_batch_size: rows per reference batch (the positional-encoding numbering unit), up to MAX_REF_BATCH = 512 for greedy
-    decoding (and the engine's max_batch / dec_slots: Engine.max_ref_batch), up to 32 with beam_size > 1."""
+    decoding (and the engine's max_batch / dec_slots: Engine.max_ref_batch), up to 32 with beam_size > 1.
+    labels: int [n, L] — label-guided decoding along row i for image i (mnx_predict_guided; Engine.decode_guided describes the
+    rows; a row without '<eos>' raises ValueError unless free_run — a bool, or one per row — exempts it); greedy only."""
     tok = (tokenizer or get_tokenizer())["chartok_coords"]
+    if labels is not None and beam_size > 1:
+        raise NotImplementedError("label-guided decoding is greedy (beam search with labels is not built)")
     if compute_confidence and beam_size > 1:
         raise NotImplementedError("beam search does not track token scores (neither does the reference's)")
     if beam_size > 1 and ref_batch_size > ROWS:
         raise ValueError(f"beam search takes reference batches of at most {ROWS} rows; got ref_batch_size={ref_batch_size} "
                          f"(greedy decoding takes up to {MAX_REF_BATCH})")
     conf = {"confidence": True} if compute_confidence else {}
+    if labels is not None:
+        conf.update(labels=labels, free_run=free_run)
     out = engine.predict(images, ref_batch=ref_batch_size, max_len=max_len, beam=beam_size, **conf)
     scores = out["scores"].cpu().numpy() if beam_size > 1 else None
     lens = out["lengths"].cpu().numpy()
@@ -322,8 +329,33 @@ class molnextr:
             self._groups_done = 0
         return self._assemble(preds, input_images, return_atoms_bonds, return_confidence)
 
-    def _predict_all(self, input_images: List, return_confidence: bool, batch_size: int) -> List[dict]:
-        """The engine part of predict_images: one prediction dict per image, every group in ONE operand mode."""
+    def predict_coords(self, input_images: List, smiles_list: List[str], return_confidence=False, batch_size=16):
+        """Coordinate prediction for KNOWN structures (the reference's main.py --predict_coords): image i is decoded along
+        smiles_list[i] tokenised with mask_ratio=1 (dataset.py:459-464) and cut to max_len ids (dataset.py:473), so the model
+        fills in every atom's x and y and the bond head reads the hidden states of that guided pass. Returns predict_images'
+        dicts with 'atom_sets' and 'bond_sets' always present. Greedy only; both image formats; the same grouping, prefetch
+        and range fallback as predict_images. A label that the cut shortened has lost its '<eos>': that row alone is passed on
+        as free-running (it ends at max_len); every other row goes through the engine's refusal of labels without '<eos>'."""
+        if len(input_images) != len(smiles_list):
+            raise ValueError(f"input_images and smiles_list must have the same length; got {len(input_images)} and {len(smiles_list)}")
+        if len(input_images) == 0:
+            return []
+        tok = self.tokenizer["chartok_coords"]
+        max_len = self.engine.max_len
+        labels, cut = coords_labels(tok, smiles_list, max_len)
+        try:
+            self._groups_done = 0
+            preds = self._predict_all(input_images, return_confidence, batch_size, labels, cut)
+        except _RestartCall:
+            self._groups_done = 0
+            preds = self._predict_all(input_images, return_confidence, batch_size, labels, cut)
+        finally:
+            self._groups_done = 0
+        return self._assemble(preds, input_images, True, return_confidence)
+
+    def _predict_all(self, input_images: List, return_confidence: bool, batch_size: int, labels=None, cut=None) -> List[dict]:
+        """The engine part of predict_images: one prediction dict per image, every group in ONE operand mode.
+        labels [n, L], cut [n] (coords_labels): label-guided (predict_coords); each group takes its rows."""
         preds: List[dict] = []
         batch_size = min(batch_size, len(input_images))     # a batch larger than the job is the whole job: same numbering
         if batch_size < 1 or batch_size > MAX_REF_BATCH:
@@ -342,6 +374,9 @@ class molnextr:
         gen = self._prefetched(groups)
         try:
             for x in gen:
+                if labels is not None:
+                    rows = slice(len(preds), len(preds) + x.shape[0])
+                    conf.update(labels=labels[rows], free_run=cut[rows])
                 preds += self._with_fallback(
                     lambda eng: predict_pipeline(eng, x, self.tokenizer, ref_batch_size=batch_size, **conf))
                 self._groups_done += 1

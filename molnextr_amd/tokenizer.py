@@ -11,11 +11,23 @@ Token id map (vocab/vocab_chars.json, 101 symbols): 0 <pad>, 1 <sos>, 2 <eos>, 3
 """
 import json
 import os
+import re
 
 PAD_ID, SOS_ID, EOS_ID, UNK_ID, MASK_ID = 0, 1, 2, 3, 4
 PAD, SOS, EOS, UNK, MASK = "<pad>", "<sos>", "<eos>", "<unk>", "<mask>"
 
 _VOCAB_DEFAULT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "vocab", "vocab_chars.json")
+
+
+# The atom-wise SMILES pattern published with SmilesPE / the Molecular Transformer (Schwaller et al.): a bracket atom, a
+# two-letter halogen, an organic-subset atom (aromatic ones included), a bond / branch / charge / dot symbol, a two-digit
+# ring closure "%nn", or one digit. Restated from the publication; tests pin it on fixtures made by the reference.
+_ATOMWISE = re.compile(r"(\[[^\]]+]|Br?|Cl?|N|O|S|P|F|I|b|c|n|o|s|p|\(|\)|\.|=|#|-|\+|\\|\/|:|~|@|\?|>|\*|\$|\%[0-9]{2}|[0-9])")
+
+
+def atomwise_tokenizer(smi):
+    """SMILES -> list of atom-wise tokens (characters the pattern does not know are dropped, as re.findall does)."""
+    return _ATOMWISE.findall(smi)
 
 
 class CharTokenizer:
@@ -83,6 +95,33 @@ class CharTokenizer:
             return [t >= x0 for t in range(V)]
         return [False] * V
 
+    # -- SMILES -> label ids (reference tokenization.py:429-462) ---------------------------------
+    def smiles_to_sequence(self, smiles, coords=None, mask_ratio=0, atom_only=False):
+        """(labels, indices): '<sos>', every character of every atom-wise token ('<unk>' outside the vocabulary), after
+        each atom token its x and y — '<mask>' twice with mask_ratio=1, the bins of coords[k] when coords is given, nothing
+        otherwise — then '<eos>'; indices[k] = position of the last id of atom k's group. mask_ratio is honoured for 0 and 1
+        only (anything between draws random numbers in the reference), and so is an atom beyond len(coords)."""
+        if mask_ratio not in (0, 1):
+            raise ValueError("mask_ratio must be 0 or 1: partial masking is random in the reference and not restated")
+        labels, indices, atom_idx = [SOS_ID], [], -1
+        for token in atomwise_tokenizer(smiles):
+            if atom_only and not self.is_atom_token(token):
+                continue
+            labels.extend(self.stoi.get(c, UNK_ID) for c in token)
+            if self.is_atom_token(token):
+                atom_idx += 1
+                if mask_ratio == 1:
+                    labels += [MASK_ID, MASK_ID]
+                elif coords is not None:
+                    if atom_idx >= len(coords):
+                        raise ValueError("fewer coordinates than atoms (the reference draws random ones)")
+                    x, y = coords[atom_idx]
+                    assert 0 <= x <= 1 and 0 <= y <= 1
+                    labels += [self.x_to_id(x), self.y_to_id(y)]
+                indices.append(len(labels) - 1)
+        labels.append(EOS_ID)
+        return labels, indices
+
     # -- ids -> {smiles, symbols, coords, indices} (reference tokenization.py:464-515) ----------
     def _atom_span_end(self, seq, i):
         """End (exclusive) of the atom token starting at i: '[...]' up to the closing bracket or the first
@@ -128,6 +167,20 @@ class CharTokenizer:
                 else:
                     i = j
         return {"smiles": "".join(pieces), "symbols": symbols, "indices": indices, "coords": coords}
+
+
+def coords_labels(tok, smiles_list, max_len: int):
+    """Labels of coordinate prediction for known structures: smiles_to_sequence(s, mask_ratio=1) of every SMILES (reference
+    dataset.py:459-464) cut to max_len ids (dataset.py:473) and padded with '<pad>' to a common L >= 2. Returns
+    (labels int32 [n, L], cut bool [n]): cut marks the rows the cut shortened, which have lost their '<eos>'."""
+    import numpy as np
+    seqs = [tok.smiles_to_sequence(s, mask_ratio=1)[0] for s in smiles_list]
+    cut = np.array([len(q) > max_len for q in seqs], dtype=bool)
+    labels = np.zeros((len(seqs), max(2, min(max_len, max((len(q) for q in seqs), default=2)))), dtype=np.int32)     # '<pad>' = 0
+    for i, q in enumerate(seqs):
+        q = q[:max_len]
+        labels[i, :len(q)] = q
+    return labels, cut
 
 
 def get_tokenizer(args=None):

@@ -32,9 +32,11 @@ Fixtures (all small):
                        W.synthetic_images(64) under synthetic_checkpoint(0) as ONE reference batch of 64 rows (the README's
                        evaluation: --batch_size 32 -> 64-row batches) and one of 40 (a full 32-row tile plus a ragged one):
                        ids, lengths, token log-probs, margins; smiles / symbols / coords / indices / bonds / confidences
+  guided.npz/.json     (named target `guided` only) TransformerDecoderAR.decode(labels=smiles_to_sequence(s, mask_ratio=1)):
+                       12 SMILES on hash_normal features, and one reference batch of 40 rows from pixels with bonds and confidences
 
-    python tools/gen_golden.py [name ...]      # only the named groups: swin decoder edges tokenizer e2e beam pixels crop
-                                               # stress, and refbatch (never part of a plain run)
+    python tools/gen_golden.py [name ...]      # only the named groups: swin decoder edges tokenizer e2e beam pixels crop stress
+                                               # (these make up a plain run), and refbatch, guided (only when named)
 """
 import hashlib
 import json
@@ -484,6 +486,127 @@ def gen_refbatch(Encoder, Decoder, args, tok, ck):
                    "preds": js}, f)
 
 
+GUIDED_SMILES = ["CC(=O)Oc1ccccc1C(=O)O", "[Na+].[Cl-]", "BrCCCl", "C1CC1", "", "C[C@H](N)C(=O)O.Cl", "c1ccc2c(c1)[nH]c1ccccc12",
+                 "CC(C)(C)OC(=O)N1CCC(CC1)C(=O)Nc1ccc(F)cc1Br", "C[C é]C", "O", "N#Cc1ccc(cc1)[N+](=O)[O-]", "C%10CCCCC%10"]
+# the 40-row batch from pixels: short molecules. Constraint on this list and on GUIDED_SMILES: the reference's smallest margin
+# over every stored step is >= 2e-3, twice the log-prob tolerance of the decoder goldens (asserted in _guided_ar)
+GUIDED_PX_SMILES = ["C", "CC", "O", "", "CCO", "C1CC1", "[Na+].[Cl-]", "BrCCCl", "N", "C{Si}C", "CC(=O)O", "c1ccccc1", "C=O"]
+
+
+def _guided_ar(dec, tok, feats, smiles, max_length=480, n_logit_steps=4):
+    """TransformerDecoderAR.decode(labels=...) of the reference along tok.smiles_to_sequence(s, mask_ratio=1) of every
+    SMILES: labels / indices, merged ids, lens, own-pick log-probs, hidden head / sum as run_greedy stores them, the first
+    logit steps and, for every (row, step), the margin between the best and second-best masked log-prob the strategy saw
+    (the input id of the grammar mask is the mixed one: label unless '<mask>', then the own previous pick)."""
+    t = tok["chartok_coords"]
+    ar = dec.decoder["chartok_coords"]
+    seqs = [t.smiles_to_sequence(s, mask_ratio=1) for s in smiles]
+    B, L = len(smiles), max(len(q[0]) for q in seqs)
+    lab = np.zeros((B, L), dtype=np.int32)
+    for b, (l, _) in enumerate(seqs):
+        lab[b, :len(l)] = l
+    logits, own = [], []
+    h = ar.output_layer.register_forward_hook(lambda m, i, o: logits.append(o.detach().squeeze(1).clone()))
+    with torch.no_grad():
+        preds, scores, token_scores, hidden = ar.decode(feats, 1, 1, max_length=max_length, labels=torch.from_numpy(lab).long())
+    h.remove()
+    lens = np.array([len(preds[b][0]) for b in range(B)], dtype=np.int32)
+    assert lens.tolist() == [len(l) - 1 for l, _ in seqs], lens
+    T = int(lens.max())
+    ids = np.full((B, T), -1, dtype=np.int32)
+    logp = np.zeros((B, T), dtype=np.float32)
+    margin = np.full((B, T), np.inf, dtype=np.float32)
+    pick = np.full((B, T), -1, dtype=np.int32)
+    hid_head = np.zeros((B, 8, 256), dtype=np.float32)
+    hid_sum = np.zeros((B, 256), dtype=np.float64)
+    for b in range(B):
+        ids[b, :lens[b]] = preds[b][0].numpy()
+        logp[b, :lens[b]] = np.log(np.array(token_scores[b][0], dtype=np.float64)).astype(np.float32)
+        hb = hidden[b][0].numpy()
+        hid_head[b, :min(8, lens[b])] = hb[:8]
+        hid_sum[b] = hb.astype(np.float64).sum(0)
+    for s, lg in enumerate(logits):
+        alive = [b for b in range(B) if lens[b] > s]
+        assert lg.shape[0] == len(alive), (s, lg.shape, len(alive))
+        lp = torch.log_softmax(lg, dim=-1)
+        prev = [int(lab[b, s]) if lab[b, s] != 4 else int(pick[b, s - 1]) for b in alive]
+        lp = lp.masked_fill(torch.tensor([t.get_output_mask(p) for p in prev]), -10000.0)
+        if s == 0:
+            lp[:, 2] = -1e20
+        top2 = lp.topk(2, dim=-1)
+        for r, b in enumerate(alive):
+            pick[b, s] = int(top2.indices[r, 0])
+            assert abs(float(top2.values[r, 0]) - float(logp[b, s])) < 1e-4, (s, b)
+            if lab[b, s + 1] == 4:
+                assert pick[b, s] == ids[b, s], (s, b)
+            margin[b, s] = float(top2.values[r, 0] - top2.values[r, 1])
+    out = {"labels": lab, "ids": ids, "lens": lens, "token_logp": logp, "margin": margin, "hidden_head": hid_head,
+           "hidden_sum": hid_sum}
+    for s in range(min(n_logit_steps, len(logits))):
+        out[f"logits_step{s}"] = logits[s].numpy()
+    fin = np.isfinite(margin)
+    assert margin[fin].min() >= 2e-3, f"smallest margin {margin[fin].min()}: choose other inputs"
+    return out, [q[1] for q in seqs], torch.from_numpy(lab).long()
+
+
+def _guided_full(dec, feats, lab):
+    """Decoder.decode(compute_confidence=True) with the AR decoder's decode wrapped to pass `labels`"""
+    ar = dec.decoder["chartok_coords"]
+    orig = ar.decode
+    ar.decode = lambda *a, **k: orig(*a, labels=lab, **k)
+    dec.compute_confidence = True
+    try:
+        with torch.no_grad():
+            preds = dec.decode(feats)
+    finally:
+        dec.compute_confidence = False
+        del ar.decode
+    return preds
+
+
+def gen_guided(Encoder, Decoder, args, tok, ck):
+    """Label-guided decoding (main.py --predict_coords): see _guided_ar. `ar` on hash_normal features, `px` from pixels
+    through the reference Encoder as ONE reference batch of 40 rows (GUIDED_PX_SMILES cycled). atomwise_tokenizer reaches the
+    reference through tools/ref_shims/SmilesPE (our restatement of the published regex), so the tokenizer pin is on the
+    published regex."""
+    dec = Decoder(args, tok).eval()
+    dec.load_state_dict(ck["decoder"], strict=True)
+    out, js = {}, {}
+    feats = W.hash_normal("guided_features", (len(GUIDED_SMILES), 144, 1024), 0.5)
+    o, indices, lab = _guided_ar(dec, tok, feats, GUIDED_SMILES)
+    out.update({f"ar_{k}": v for k, v in o.items()})
+    js["ar"] = {"smiles": GUIDED_SMILES, "indices": indices}
+    print("guided ar: lens", o["lens"].tolist(), "margin min", float(o["margin"][np.isfinite(o["margin"])].min()))
+    enc = Encoder(reference_args()).eval()
+    enc.load_state_dict(ck["encoder"], strict=True)
+    N = 40
+    with torch.no_grad():
+        pf = torch.cat([enc(W.synthetic_images(N)[i:i + 4])[0] for i in range(0, N, 4)])
+    px_smiles = [GUIDED_PX_SMILES[(i + 4) % len(GUIDED_PX_SMILES)] for i in range(N)]
+    o, indices, lab = _guided_ar(dec, tok, pf, px_smiles, n_logit_steps=0)
+    for k in ("hidden_head", "hidden_sum"):
+        o.pop(k)
+    out.update({f"px_{k}": v for k, v in o.items()})
+    print("guided px: lens", o["lens"].tolist(), "margin min", float(o["margin"][np.isfinite(o["margin"])].min()))
+    preds = _guided_full(dec, pf, lab)
+    out["px_edges"] = np.concatenate([np.array(p["edges"], dtype=np.uint8).ravel() for p in preds])
+    es = [np.array(p["edge_scores"], dtype=np.float32).reshape((len(p["chartok_coords"]["symbols"]),) * 2) for p in preds]
+    out["px_edge_scores"] = np.concatenate([e[np.triu_indices(e.shape[0])] for e in es])
+    js["px"] = {"smiles": px_smiles, "indices": indices,
+                "preds": [{"smiles": p["chartok_coords"]["smiles"], "symbols": p["chartok_coords"]["symbols"],
+                           "coords": p["chartok_coords"]["coords"], "indices": p["chartok_coords"]["indices"],
+                           "atom_scores": p["chartok_coords"]["atom_scores"], "overall_score": p["overall_score"]}
+                          for p in preds]}
+    np.savez_compressed(os.path.join(GOLD, "guided.npz"), **out)
+    with open(os.path.join(GOLD, "guided.json"), "w") as f:
+        json.dump({"note": "reference TransformerDecoderAR.decode(labels=smiles_to_sequence(s, mask_ratio=1)) under "
+                           "W.synthetic_checkpoint(0); ar: W.hash_normal('guided_features',(12,144,1024),0.5); px: "
+                           "W.synthetic_images(40) through the reference Encoder, one reference batch of 40. "
+                           "atomwise_tokenizer reached the reference through tools/ref_shims/SmilesPE (no SmilesPE installed): "
+                           "the tokenizer pin is on the published regex. npz px_edges / px_edge_scores as pixels_refbatch. "
+                           "Smallest stored margin asserted >= 2e-3 at generation.", **js}, f)
+
+
 def gen_crop_pad():
     """CropWhite(pad=50) and PadToSquare of the reference's own data_aug.py (imported through a minimal
     albumentations / cv2 stand-in: both classes are pure numpy apart from a constant-border pad) on ragged pages:
@@ -548,6 +671,8 @@ def main():
         gen_crop_pad()
     if "refbatch" in want:
         gen_refbatch(Encoder, Decoder, args, tok, ck)
+    if "guided" in want:
+        gen_guided(Encoder, Decoder, args, tok, ck)
     sizes = {f: os.path.getsize(os.path.join(GOLD, f)) for f in sorted(os.listdir(GOLD))}
     print("fixture bytes:", sizes, "total", sum(sizes.values()))
 
