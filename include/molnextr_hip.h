@@ -425,6 +425,44 @@ int mnx_window_attn(mnx_engine* h, const void* qkv, int64_t qkv_lo, const float*
  * (with mnx_last_error). Asynchronous on `stream`. */
 int mnx_kv_block(mnx_engine* h, int32_t which, int32_t layer, int32_t owner, int32_t head, void* dst, void* stream);
 
+/* Test aids: the encoder's non-GEMM kernels and the decoder's fp32 SGEMM on caller device buffers
+ * (tests/test_gpu_encoder_ops.py). None uses anything of the engine but its device and, where stated, its compute_dtype
+ * (FP16X3M counts as FP16X3). Every fp32 buffer is 16-byte aligned, a 16-bit output 8-byte. Each returns
+ * MNX_ERR_INVALID_ARG (with mnx_last_error, "mnx_<name>: ...") for a null or misaligned pointer or any size outside what
+ * is stated, and launches nothing then. Asynchronous on `stream`.
+ *
+ * mnx_patch_embed: Conv2d(3, C, 4, stride 4) + bias + LayerNorm(C, eps 1e-5) of B images -> x fp32 [B, (S/4)^2, C].
+ *   img: img_format MNX_IMG_F32 fp32 [B,3,S,S]; MNX_IMG_GRAY8 uint8 [B,S,S] (4-byte aligned), expanded to the three
+ *   normalised channels as mnx_encode_gray8 does — bit-identical tokens. w_t: the conv weight as [48][C], row
+ *   (ci * 4 + ky) * 4 + kx (the layout mnx_create uploads). C = 32, 64, 96 or 128; S a multiple of 4; B <= 65535. */
+int mnx_patch_embed(mnx_engine* h, const void* img, int32_t img_format, const float* w_t, const float* bias,
+                    const float* gamma, const float* beta, float* x, int32_t B, int32_t S, int32_t C, void* stream);
+
+/* mnx_layernorm16: LayerNorm over the C channels of x fp32 [M, C] (C a multiple of 4, 4..2048) -> y16 [M, C] in the
+ *   engine's operand type (FP32 engines: fp32) and / or y32 fp32 [M, C]; one of the two may be null. Split compute_dtypes:
+ *   y16 is the hi plane, the lo plane = RN16(value - hi) lies y_lo ELEMENTS behind it (>= M * C, a multiple of 8);
+ *   planes = 1 writes the hi plane only (y_lo is ignored). The other compute_dtypes take y_lo = 0 and planes = 2.
+ *   flag: device int32 or null; set to 1 (never cleared) when a row's variance is not finite and positive.
+ * mnx_merge_ln16: the patch-merging gather + LayerNorm(4C): x fp32 [B,H,W,C] (H, W even; C a multiple of 4, <= 512)
+ *   -> y16 [B * H/2 * W/2, 4C], row (b, i, j) = LayerNorm(concat of x[b, 2i+dy, 2j+dx, :], (dy,dx) = (0,0), (1,0), (0,1),
+ *   (1,1)). y_lo / planes as above. */
+int mnx_layernorm16(mnx_engine* h, const float* x, const float* gamma, const float* beta, void* y16, int64_t y_lo,
+                    float* y32, int32_t M, int32_t C, float eps, int32_t planes, int32_t* flag, void* stream);
+int mnx_merge_ln16(mnx_engine* h, const float* x, const float* gamma, const float* beta, void* y16, int64_t y_lo,
+                   int32_t B, int32_t H, int32_t W, int32_t C, float eps, int32_t planes, void* stream);
+
+/* mnx_cast16: x fp32 [n] (n a multiple of 4) -> y16 [n] in the engine's operand type (FP32 engines: a copy). Split
+ *   compute_dtypes: hi = RN16(scale * x), lo = RN16(scale * x - hi) y_lo >= n ELEMENTS (a multiple of 4) behind; scale is
+ *   meant to be a power of two. The other compute_dtypes take y_lo = 0 and IGNORE scale, as the kernel does. */
+int mnx_cast16(mnx_engine* h, const float* x, void* y16, int64_t y_lo, int64_t n, float scale, void* stream);
+
+/* mnx_sgemm_tn: the decoder's fp32 SGEMM C[M,N] = A[M,K] . W[N,K]^T + bias (bias fp32 [N] or null); K a multiple of 16,
+ *   N of 4. perm_S > 0 (N a multiple of 256, M of perm_S): element (m, n) is stored at
+ *   [m / perm_S][n / 256][(n % 256) / 32][m % perm_S][n % 32] — the projected memory K / V layout
+ *   [image][layer * 2 + K|V][head][position][32]. Independent of the compute_dtype. */
+int mnx_sgemm_tn(mnx_engine* h, const float* A, const float* W, const float* bias, float* C, int32_t M, int32_t N,
+                 int32_t K, int32_t perm_S, void* stream);
+
 /* Measurement aid for bench.py: while enabled, mnx_encode brackets every kernel launch of the sampled calls with a
  * pair of HIP events recorded on the stream the kernel is launched on (also inside mnx_predict, i.e. live in a timed
  * region). `enable` = n > 0: every n-th mnx_encode call since the enable is sampled, at most 4 calls (the event pool

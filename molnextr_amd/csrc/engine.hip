@@ -1710,4 +1710,119 @@ int mnx_kv_block(mnx_engine* h, int32_t which, int32_t layer, int32_t owner, int
     return MNX_OK;
 }
 
+// ---- test aids: the encoder's non-GEMM kernels and the fp32 SGEMM on caller buffers (tests/test_gpu_encoder_ops.py) ----
+// Each checks everything its launcher assumes (and what the launcher leaves to the encoder: positive sizes, alignment of
+// the 16-byte accesses) and launches nothing when it refuses.
+static bool misaligned16(std::initializer_list<const void*> ps) {
+    uintptr_t a = 0;
+    for (const void* p : ps) a |= (uintptr_t)p;
+    return (a & 15) != 0;
+}
+
+int mnx_patch_embed(mnx_engine* h, const void* img, int32_t img_format, const float* w_t, const float* bias,
+                    const float* gamma, const float* beta, float* x, int32_t B, int32_t S, int32_t C, void* stream) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    auto bad = [&](const char* m) { h->err = std::string("mnx_patch_embed: ") + m; return MNX_ERR_INVALID_ARG; };
+    if (img_format != MNX_IMG_F32 && img_format != MNX_IMG_GRAY8) return bad("img_format must be MNX_IMG_F32 or MNX_IMG_GRAY8");
+    if (!img || !w_t || !bias || !gamma || !beta || !x) return bad("null pointer");
+    if (misaligned16({w_t, bias, gamma, beta, x})) return bad("w_t, bias, gamma, beta and x must be 16-byte aligned");
+    if ((uintptr_t)img & (img_format == MNX_IMG_GRAY8 ? 3 : 15))
+        return bad("img must be 16-byte (MNX_IMG_F32) or 4-byte (MNX_IMG_GRAY8) aligned");
+    if (C < 32 || C > 128 || (C & 31)) return bad("C must be 32, 64, 96 or 128");
+    if (S < 4 || (S & 3)) return bad("S must be a positive multiple of the patch size (4)");
+    if (B < 1 || B > 65535) return bad("B must be 1..65535");
+    if ((int64_t)B * (S / 4) * (S / 4) > INT32_MAX) return bad("B * (S/4)^2 must fit in int32");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (img_format == MNX_IMG_GRAY8)
+        HIPCHK(h, launch_patch_embed_gray8((const uint8_t*)img, w_t, bias, gamma, beta, x, B, S, C, (hipStream_t)stream));
+    else
+        HIPCHK(h, launch_patch_embed((const float*)img, w_t, bias, gamma, beta, x, B, S, C, (hipStream_t)stream));
+    return MNX_OK;
+}
+
+int mnx_layernorm16(mnx_engine* h, const float* x, const float* gamma, const float* beta, void* y16, int64_t y_lo,
+                    float* y32, int32_t M, int32_t C, float eps, int32_t planes, int32_t* flag, void* stream) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    auto bad = [&](const char* m) { h->err = std::string("mnx_layernorm16: ") + m; return MNX_ERR_INVALID_ARG; };
+    if (!x || !gamma || !beta) return bad("null pointer");
+    if (!y16 && !y32) return bad("y16 and y32 are both null");
+    if (misaligned16({x, gamma, beta, y32}) || ((uintptr_t)y16 & 7) || (h->dt == MNX_DT_F32 && ((uintptr_t)y16 & 15)))
+        return bad("x, gamma, beta and y32 must be 16-byte aligned, y16 8-byte (16-byte for FP32)");
+    if ((uintptr_t)flag & 3) return bad("flag must be 4-byte aligned");
+    if (M < 1 || (int64_t)M + 8 > INT32_MAX) return bad("M must be positive (and M + 8 fit in int32)");
+    if (C < 4 || C > 2048 || (C & 3)) return bad("C must be a multiple of 4 in 4..2048");
+    if (!(eps >= 0.f)) return bad("eps must be >= 0");
+    if (planes != 1 && planes != 2) return bad("planes must be 1 or 2");
+    if (dt_split(h->dt)) {
+        if (planes == 2 && y16 && (y_lo < (int64_t)M * C || (y_lo & 7)))
+            return bad("y_lo must be at least M * C and a multiple of 8 elements");
+        if (y_lo < 0) return bad("y_lo must not be negative");
+    } else if (y_lo || planes != 2) {
+        return bad("y_lo must be 0 and planes 2 for the single-plane compute_dtypes");
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, launch_layernorm16(h->dt, x, gamma, beta, y16, y32, M, C, eps, (hipStream_t)stream, (size_t)y_lo, flag, planes));
+    return MNX_OK;
+}
+
+int mnx_merge_ln16(mnx_engine* h, const float* x, const float* gamma, const float* beta, void* y16, int64_t y_lo,
+                   int32_t B, int32_t H, int32_t W, int32_t C, float eps, int32_t planes, void* stream) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    auto bad = [&](const char* m) { h->err = std::string("mnx_merge_ln16: ") + m; return MNX_ERR_INVALID_ARG; };
+    if (!x || !gamma || !beta || !y16) return bad("null pointer");
+    if (misaligned16({x, gamma, beta}) || ((uintptr_t)y16 & 7) || (h->dt == MNX_DT_F32 && ((uintptr_t)y16 & 15)))
+        return bad("x, gamma and beta must be 16-byte aligned, y16 8-byte (16-byte for FP32)");
+    if (B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1)) return bad("B >= 1 and H, W positive even numbers required");
+    if (C < 4 || 4 * (int64_t)C > 2048 || (C & 3)) return bad("C must be a multiple of 4 in 4..512");
+    if ((int64_t)B * H * W > INT32_MAX) return bad("B * H * W must fit in int32");
+    if (!(eps >= 0.f)) return bad("eps must be >= 0");
+    if (planes != 1 && planes != 2) return bad("planes must be 1 or 2");
+    const int64_t out = (int64_t)B * (H / 2) * (W / 2) * 4 * C;
+    if (dt_split(h->dt)) {
+        if (planes == 2 && (y_lo < out || (y_lo & 7))) return bad("y_lo must be at least B * H/2 * W/2 * 4C and a multiple of 8 elements");
+        if (y_lo < 0) return bad("y_lo must not be negative");
+    } else if (y_lo || planes != 2) {
+        return bad("y_lo must be 0 and planes 2 for the single-plane compute_dtypes");
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, launch_merge_ln16(h->dt, x, gamma, beta, y16, B, H, W, C, eps, (hipStream_t)stream, (size_t)y_lo, planes));
+    return MNX_OK;
+}
+
+int mnx_cast16(mnx_engine* h, const float* x, void* y16, int64_t y_lo, int64_t n, float scale, void* stream) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    auto bad = [&](const char* m) { h->err = std::string("mnx_cast16: ") + m; return MNX_ERR_INVALID_ARG; };
+    if (!x || !y16) return bad("null pointer");
+    if (((uintptr_t)x & 15) || ((uintptr_t)y16 & 7) || (h->dt == MNX_DT_F32 && ((uintptr_t)y16 & 15)))
+        return bad("x must be 16-byte aligned, y16 8-byte (16-byte for FP32)");
+    if (n < 4 || (n & 3)) return bad("n must be a positive multiple of 4");
+    if (dt_split(h->dt)) {
+        if (y_lo < n || (y_lo & 3)) return bad("y_lo must be at least n and a multiple of 4 elements");
+        if (!(scale > 0.f) || !(scale < INFINITY)) return bad("scale must be positive and finite");
+    } else if (y_lo) {
+        return bad("y_lo must be 0 for the single-plane compute_dtypes");
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, launch_cast16(h->dt, x, y16, (size_t)n, (hipStream_t)stream, (size_t)y_lo, scale));
+    return MNX_OK;
+}
+
+int mnx_sgemm_tn(mnx_engine* h, const float* A, const float* W, const float* bias, float* C, int32_t M, int32_t N,
+                 int32_t K, int32_t perm_S, void* stream) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    auto bad = [&](const char* m) { h->err = std::string("mnx_sgemm_tn: ") + m; return MNX_ERR_INVALID_ARG; };
+    if (!A || !W || !C) return bad("null pointer");
+    if (misaligned16({A, W, bias, C})) return bad("A, W, bias and C must be 16-byte aligned");
+    if (M < 1 || N < 4 || K < 16) return bad("M >= 1, N >= 4 and K >= 16 required");
+    if (K & 15) return bad("K must be a multiple of 16");
+    if (N & 3) return bad("N must be a multiple of 4");
+    if (perm_S < 0) return bad("perm_S must not be negative");
+    if (perm_S > 0 && (N & 255)) return bad("perm_S needs N to be a multiple of 256");
+    if (perm_S > 0 && M % perm_S) return bad("perm_S must divide M");
+    if ((M + 63) / 64 > 65535) return bad("M must be at most 65535 * 64");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, launch_sgemm_tn(A, W, bias, C, M, N, K, (hipStream_t)stream, perm_S));
+    return MNX_OK;
+}
+
 }  // extern "C"

@@ -25,7 +25,8 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
            "mnx_probe_decode_attn", "mnx_predict_beam", "mnx_set_split_terms", "mnx_encoder_status",
            "mnx_gemm16_split", "mnx_decode_forced", "mnx_gemm_clock", "mnx_probe_mfma", "mnx_set_op_terms",
            "mnx_predict_confidence", "mnx_confidence", "mnx_window_attn", "mnx_kv_block", "mnx_preprocess_batch",
-           "mnx_encode_gray8", "mnx_predict_gray8", "mnx_decode_guided", "mnx_predict_guided")
+           "mnx_encode_gray8", "mnx_predict_gray8", "mnx_decode_guided", "mnx_predict_guided", "mnx_patch_embed",
+           "mnx_layernorm16", "mnx_merge_ln16", "mnx_cast16", "mnx_sgemm_tn")
 
 # Encoder operand modes (include/molnextr_hip.h MNX_DTYPE_*). "fp16x3" — split fp16 operands, three MFMA terms per
 # product, fp32-class results — is the default: it is the fastest mode whose results stay a factor of four inside north_star's
@@ -144,6 +145,16 @@ def load_library():
     lib.mnx_window_attn.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.mnx_kv_block.restype = C.c_int
     lib.mnx_kv_block.argtypes = [vp, i32, i32, i32, i32, vp, vp]
+    lib.mnx_patch_embed.restype = C.c_int
+    lib.mnx_patch_embed.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    lib.mnx_layernorm16.restype = C.c_int
+    lib.mnx_layernorm16.argtypes = [vp, vp, vp, vp, vp, C.c_int64, vp, i32, i32, C.c_float, i32, vp, vp]
+    lib.mnx_merge_ln16.restype = C.c_int
+    lib.mnx_merge_ln16.argtypes = [vp, vp, vp, vp, vp, C.c_int64, i32, i32, i32, i32, C.c_float, i32, vp]
+    lib.mnx_cast16.restype = C.c_int
+    lib.mnx_cast16.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.c_float, vp]
+    lib.mnx_sgemm_tn.restype = C.c_int
+    lib.mnx_sgemm_tn.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.mnx_profile_enable.restype = C.c_int
     lib.mnx_profile_enable.argtypes = [vp, i32]
     lib.mnx_profile_read.restype = C.c_int
@@ -799,6 +810,40 @@ class Engine:
         self._check(self.lib.mnx_kv_block(self.h, self.KV_WHICH[which], layer, owner, head, _ptr(out), _stream()),
                     "mnx_kv_block")
         return out
+
+    # -- the encoder's non-GEMM kernels and the fp32 SGEMM on caller buffers (test aids) -----------------------------------
+    # Thin: every argument goes to the library as given, which validates it (tests/test_gpu_encoder_ops.py).
+    def patch_embed(self, img: torch.Tensor, w_t: torch.Tensor, bias: torch.Tensor, gamma: torch.Tensor,
+                    beta: torch.Tensor, x: torch.Tensor, B: int, S: int, C_: int):
+        """mnx_patch_embed: img fp32 [B,3,S,S] or uint8 [B,S,S] (gray bytes), w_t fp32 [48, C] -> x fp32 [B, (S/4)^2, C]"""
+        fmt = IMAGE_FORMATS["gray8" if img.dtype == torch.uint8 else "fp32"]
+        self._check(self.lib.mnx_patch_embed(self.h, _ptr(img), fmt, _ptr(w_t), _ptr(bias), _ptr(gamma), _ptr(beta), _ptr(x),
+                                             B, S, C_, _stream()), "mnx_patch_embed")
+        return x
+
+    def layernorm16(self, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, y16: Optional[torch.Tensor],
+                    y32: Optional[torch.Tensor], M: int, C_: int, eps: float = 1e-5, y_lo: int = 0, planes: int = 2,
+                    flag: Optional[torch.Tensor] = None):
+        """mnx_layernorm16: x fp32 [M, C] -> y16 [M, C] in the engine's operand type (split modes: the hi plane, the lo plane
+        y_lo elements behind it; planes = 1: hi only) and / or y32 fp32 [M, C]; flag: device int32, set on a non-finite row."""
+        self._check(self.lib.mnx_layernorm16(self.h, _ptr(x), _ptr(gamma), _ptr(beta), _ptr(y16), y_lo, _ptr(y32), M, C_,
+                                             float(eps), planes, _ptr(flag), _stream()), "mnx_layernorm16")
+
+    def merge_ln16(self, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, y16: torch.Tensor, B: int, H: int,
+                   W_: int, C_: int, eps: float = 1e-5, y_lo: int = 0, planes: int = 2):
+        """mnx_merge_ln16: x fp32 [B,H,W,C] -> y16 [B * H/2 * W/2, 4C], the patch-merging gather + LayerNorm(4C)"""
+        self._check(self.lib.mnx_merge_ln16(self.h, _ptr(x), _ptr(gamma), _ptr(beta), _ptr(y16), y_lo, B, H, W_, C_,
+                                            float(eps), planes, _stream()), "mnx_merge_ln16")
+
+    def cast16(self, x: torch.Tensor, y16: torch.Tensor, n: int, y_lo: int = 0, scale: float = 1.0):
+        """mnx_cast16: x fp32 [n] -> y16 [n] in the engine's operand type; split modes: hi / lo planes of scale * x"""
+        self._check(self.lib.mnx_cast16(self.h, _ptr(x), _ptr(y16), y_lo, n, float(scale), _stream()), "mnx_cast16")
+
+    def sgemm_tn(self, A: torch.Tensor, Wt: torch.Tensor, bias: Optional[torch.Tensor], Cout: torch.Tensor, M: int, N: int,
+                 K: int, perm_S: int = 0):
+        """mnx_sgemm_tn: Cout[M,N] = A[M,K] . Wt[N,K]^T + bias in fp32; perm_S > 0: the [M/S][N/256][8][S][32] layout"""
+        self._check(self.lib.mnx_sgemm_tn(self.h, _ptr(A), _ptr(Wt), _ptr(bias), _ptr(Cout), M, N, K, perm_S, _stream()),
+                    "mnx_sgemm_tn")
 
     def gemm16(self, epi: int, A: torch.Tensor, Wt: torch.Tensor, Cout: torch.Tensor, bias: Optional[torch.Tensor]):
         M, K = A.shape
