@@ -12,6 +12,55 @@ extern int hipMalloc(void** p, size_t n);
 extern int hipFree(void* p);
 extern int hipMemcpy(void* dst, const void* src, size_t n, int kind);
 
+/* The molecules as packed tables (mnx_graph_pack): no tokenizer on the host. A first call with modest capacities; `totals`
+ * says what the job needs, so a second call with exactly that is the worst case. Prints molecule 0. */
+static int print_first_molecule(mnx_engine* eng, int n_images, const int32_t* tokens, const int32_t* lengths,
+                                const int32_t* atom_idx, const int32_t* n_atoms, const uint8_t* edges) {
+    uint32_t caps[3], totals[4] = {0, 0, 0, 0}, *totals_dev = NULL, k;
+    mnx_mol *mols_dev = NULL, mol;
+    mnx_atom *atoms_dev = NULL, *atoms = NULL;
+    mnx_bond *bonds_dev = NULL, *bonds = NULL;
+    char *text_dev = NULL, *text = NULL;
+    int rc = MNX_OK, attempt;
+    caps[0] = (uint32_t)n_images * 48; caps[1] = (uint32_t)n_images * 56; caps[2] = (uint32_t)n_images * 192;
+    hipMalloc((void**)&mols_dev, (size_t)n_images * sizeof(mnx_mol));
+    hipMalloc((void**)&totals_dev, sizeof totals);
+    for (attempt = 0; attempt < 2 && rc == MNX_OK; ++attempt) {
+        hipMalloc((void**)&atoms_dev, (size_t)caps[0] * sizeof(mnx_atom));
+        hipMalloc((void**)&bonds_dev, (size_t)caps[1] * sizeof(mnx_bond));
+        hipMalloc((void**)&text_dev, caps[2]);
+        /* no confidences here: the three score pointers NULL (mnx_predict_confidence's outputs would go in their place) */
+        rc = mnx_graph_pack(eng, tokens, lengths, n_images, 480, atom_idx, n_atoms, edges, 160, NULL, NULL, NULL, mols_dev,
+                            atoms_dev, caps[0], bonds_dev, caps[1], text_dev, caps[2], totals_dev, /*stream=*/NULL);
+        if (rc != MNX_OK) { fprintf(stderr, "mnx_graph_pack: %s\n", mnx_last_error(eng)); break; }
+        hipMemcpy(totals, totals_dev, sizeof totals, 2 /* hipMemcpyDeviceToHost: waits for the three launches */);
+        if (!totals[3]) break;
+        hipFree(atoms_dev); hipFree(bonds_dev); hipFree(text_dev);
+        atoms_dev = NULL; bonds_dev = NULL; text_dev = NULL;
+        caps[0] = totals[0]; caps[1] = totals[1]; caps[2] = totals[2];
+    }
+    if (rc == MNX_OK && !totals[3]) {
+        hipMemcpy(&mol, mols_dev, sizeof mol, 2);
+        atoms = (mnx_atom*)malloc((size_t)(mol.n_atoms + 1) * sizeof(mnx_atom));
+        bonds = (mnx_bond*)malloc((size_t)(mol.n_bonds + 1) * sizeof(mnx_bond));
+        text = (char*)malloc((size_t)mol.smiles_len + 1);
+        if (atoms && bonds && text) {
+            hipMemcpy(atoms, atoms_dev + mol.atom0, (size_t)mol.n_atoms * sizeof(mnx_atom), 2);
+            hipMemcpy(bonds, bonds_dev + mol.bond0, (size_t)mol.n_bonds * sizeof(mnx_bond), 2);
+            hipMemcpy(text, text_dev + mol.text0, mol.smiles_len, 2);
+            printf("molecule 0: %.*s%s\n", (int)mol.smiles_len, text, (mol.flags & MNX_MOL_TRUNCATED) ? " (atoms truncated)" : "");
+            for (k = 0; k < mol.n_atoms; ++k)      /* the symbol is a substring of the SMILES; coordinate = bin / (bins - 1) */
+                printf("  atom %u  %.*s  (%.3f, %.3f)\n", (unsigned)k, (int)atoms[k].sym_len, text + atoms[k].sym0,
+                       atoms[k].x_bin / 63.0, atoms[k].y_bin / 63.0);
+            for (k = 0; k < mol.n_bonds; ++k)
+                printf("  bond %u - %u  type %u\n", (unsigned)bonds[k].i, (unsigned)bonds[k].j, (unsigned)bonds[k].type);
+        }
+        free(atoms); free(bonds); free(text);
+    }
+    hipFree(mols_dev); hipFree(totals_dev); hipFree(atoms_dev); hipFree(bonds_dev); hipFree(text_dev);
+    return rc;
+}
+
 int run(const mnx_weight_desc* weights, int n_weights, const float* host_images /* [n,3,384,384] */, int n_images) {
     mnx_config cfg;
     memset(&cfg, 0, sizeof cfg);
@@ -28,6 +77,8 @@ int run(const mnx_weight_desc* weights, int n_weights, const float* host_images 
     }
     /* token classes of the vocabulary (CharTokenizer.is_symbol / is_atom) — see molnextr_amd/engine.py for the table */
     /* mnx_set_token_classes(eng, flags, 101, id_lbracket, id_rbracket, id_C, id_l, id_B, id_r); */
+    /* ... and the names of its 101 symbol ids as UTF-8 bytes, for mnx_graph_pack (vocab/vocab_chars.json in id order): */
+    /* mnx_set_vocab_text(eng, name_bytes, name_offsets, 101); */
 
     const size_t img_elems = (size_t)3 * 384 * 384;
     float* images = NULL;
@@ -46,7 +97,7 @@ int run(const mnx_weight_desc* weights, int n_weights, const float* host_images 
                          atom_idx,
                          edges, /*kmax=*/160, /*stream=*/NULL);
     if (rc != MNX_OK) fprintf(stderr, "mnx_predict: %s\n", mnx_last_error(eng));
-    /* ... copy tokens / lengths / atom_idx / edges back and detokenise (tokenization.py:464-515) ... */
+    if (rc == MNX_OK) rc = print_first_molecule(eng, n_images, tokens, lengths, atom_idx, n_atoms, edges);
 
     hipFree(images); hipFree(tokens); hipFree(lengths); hipFree(n_atoms); hipFree(atom_idx); hipFree(edges);
     mnx_destroy(eng);

@@ -302,7 +302,7 @@ int mnx_atom_scan(mnx_engine* h, const int32_t* tokens, const int32_t* lengths, 
 
 /* The whole hot path for a list of images, with continuous batching: replaces the body of the chunk loop of
  * `molnextr.predict_images` (MolNexTR/model.py:102-109: encoder + decoder.decode for every chunk) up to, but not
- * including, the host-side detokenisation to symbols / coordinates.
+ * including, the host-side detokenisation to symbols / coordinates (mnx_graph_pack does that on the device, as a post-pass).
  *   images    device fp32 [n_img,3,S,S]
  *   ref_batch images are decoded as consecutive reference batches of this many rows, 1 <= ref_batch <=
  *             min(512, cfg.max_batch, cfg.dec_slots, cfg.pe_len) (MNX_ERR_CAPACITY otherwise; mnx_last_error names the
@@ -371,6 +371,65 @@ int mnx_predict_guided(mnx_engine* h, const void* images, int32_t img_format, in
 int mnx_confidence(mnx_engine* h, const int32_t* tokens, const int32_t* lengths, const float* token_logp, int32_t n,
                    int32_t T, const int32_t* atom_idx, const int32_t* n_atoms, const double* edge_scores, int32_t kmax,
                    double* atom_scores, double* overall_score, void* stream);
+
+/* The names of the vocabulary's symbol ids, for mnx_graph_pack: the name of id i is bytes[offsets[i] .. offsets[i+1]), UTF-8,
+ * at most 8 bytes, for i < n; n must be cfg.sym_offset (at most 256): one name for every symbol id, so that no id is spelled
+ * as nothing. The reference vocabulary holds the five specials '<pad>' .. '<mask>' and one two-byte character; every other
+ * name is one byte. Copied to the device (host pointers, read before the call returns): the sibling of mnx_set_token_classes.
+ * MNX_ERR_INVALID_ARG (with mnx_last_error): null pointer, n outside 1..256, offsets[0] != 0, a name of more than 8 bytes or
+ * a decreasing offset, n != cfg.sym_offset. */
+int mnx_set_vocab_text(mnx_engine* h, const char* bytes, const uint32_t* offsets, int32_t n);
+
+/* Molecules as packed tables: the dense outputs of any mnx_predict* call (or of mnx_atom_scan / mnx_edges / mnx_confidence)
+ * turned on the device into what CharTokenizer.sequence_to_smiles (MolNexTR/tokenization.py:464-515) and the pair loop of
+ * predict_images (MolNexTR/model.py:135-143) derive from them on the host — per image the raw token SMILES, one record per
+ * atom and one per bond — so that a caller copies a few hundred bytes per image and needs no tokenizer of its own.
+ * A post-pass: it reads the outputs of mnx_predict*, changes none of them and touches no decode state.
+ *
+ * The three record types (natural C layout, no packing pragma; records are written whole, padding bytes as zeros):
+ *   struct mnx_mol, 40 bytes   atom0, bond0, text0: where the image's atoms / bonds / SMILES start in `atoms`, `bonds`, `text`
+ *                              (the tables of image b lie behind those of image b - 1); n_atoms, n_bonds, smiles_len: how many;
+ *                              flags bit 0: the token walk found more atoms than kmax and the tables hold the first kmax;
+ *                              overall_score (0 without scores)
+ *   struct mnx_atom, 24 bytes  the symbol is the sym_len bytes at text + text0 + sym0 (an atom's symbol is a substring of its
+ *                              molecule's SMILES: no second copy); index = its decoder position (atom_idx, the tokenizer's
+ *                              'indices'); x_bin, y_bin: the coordinate is bin / (cfg.coord_bins - 1), computed by the consumer
+ *                              in double — the reference's own Python division; score = atom_scores (0 without scores)
+ *   struct mnx_bond, 16 bytes  i < j; type = edges[i][j], rev = edges[j][i]; one record for every edges[i][j] != 0 with
+ *                              i < j < n_atoms, i ascending, then j ascending; score = edge_scores[i][j] (0 without scores)
+ * Inputs, device pointers exactly as mnx_predict* writes them: tokens int32 [n,T], lengths int32 [n], atom_idx int32 [n,kmax],
+ * n_atoms int32 [n], edges uint8 [n,kmax,kmax]; atom_scores fp64 [n,kmax], edge_scores fp64 [n,kmax,kmax], overall_score fp64
+ * [n]: all three or none. 1 <= n <= 65536, 1 <= T <= 512, 1 <= kmax <= cfg.max_atoms. The atoms come from the atom scan's own
+ * token walk over the ids (their count is min(walk, kmax)); bonds are read among the first min(that, n_atoms[b]) atoms.
+ * Outputs, device pointers the caller allocated: mols [n]; atoms [atom_cap], bonds [bond_cap] (8-byte aligned), text
+ * [text_cap] bytes (no terminators); totals uint32 [4] = {atoms, bonds, text bytes needed, 1 if any capacity was too small}.
+ * When a capacity is too small nothing is written beyond it, and mols and totals are complete all the same: read the needed
+ * sizes and call again. Deterministic word for word (every position comes from a prefix scan; no atomics). Three launches,
+ * asynchronous on `stream`, no allocation, no host synchronisation.
+ * MNX_ERR_INVALID_ARG (with mnx_last_error, "mnx_graph_pack: ..."): a null pointer (a table with capacity 0 may be null), a
+ * size outside the limits, the scores partly set, misaligned records, or no vocabulary text / token classes set. */
+typedef struct mnx_mol {
+    uint32_t atom0, n_atoms, bond0, n_bonds, text0, smiles_len;
+    uint32_t flags;             /* bit 0: more atoms than kmax, tables truncated to kmax */
+    uint32_t reserved;          /* 0 */
+    double overall_score;
+} mnx_mol;
+typedef struct mnx_atom {
+    uint32_t sym0;              /* bytes from the molecule's text0 */
+    uint16_t sym_len, index, x_bin, y_bin;
+    double score;
+} mnx_atom;
+typedef struct mnx_bond {
+    uint16_t i, j;
+    uint8_t type, rev;
+    double score;
+} mnx_bond;
+#define MNX_MOL_TRUNCATED 1u
+int mnx_graph_pack(mnx_engine* h, const int32_t* tokens, const int32_t* lengths, int32_t n, int32_t T,
+                   const int32_t* atom_idx, const int32_t* n_atoms, const uint8_t* edges, int32_t kmax,
+                   const double* atom_scores, const double* edge_scores, const double* overall_score, mnx_mol* mols,
+                   mnx_atom* atoms, uint32_t atom_cap, mnx_bond* bonds, uint32_t bond_cap, char* text, uint32_t text_cap,
+                   uint32_t* totals, void* stream);
 
 /* mnx_predict with beam search (BASELINE config 5): the same inputs and outputs, every reference batch searched as
  * mnx_decode_beam does (n_best = 1: the best hypothesis; atom positions and the bond head run on ITS tokens and decoder

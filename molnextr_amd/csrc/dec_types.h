@@ -3,6 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+struct mnx_mol;     // include/molnextr_hip.h: the records of mnx_graph_pack
+struct mnx_atom;
+struct mnx_bond;
+
 namespace mnx {
 
 constexpr int MAX_SLOTS = 4096;    // capacity of the sequence-state arrays (cfg.dec_slots <= this; default 2048 in use)
@@ -119,6 +123,12 @@ struct TokenClasses {
     int lbracket, rbracket, id_C, id_l, id_B, id_r, x0, y0, vocab;
 };
 
+// names of the vocabulary's symbol ids as UTF-8 bytes (mnx_set_vocab_text): what graph_pack.hip spells the SMILES with
+struct VocabText {
+    unsigned char len[256];        // bytes of id i's name, 0..8 (0 beyond the ids that were set)
+    unsigned char name[256][8];
+};
+
 // fp32 projected memory K / V of `n_blocks` (image, layer, K|V, head) blocks of S rows -> quantised blocks at dst (kvq.h)
 hipError_t kvq_pack_enqueue(const float* src, char* dst, int n_blocks, int S, int Sq, hipStream_t s);
 // Label-guided decoding (mnx_decode_guided / mnx_predict_guided): what an admission installs for its rows. The engine owns
@@ -170,6 +180,13 @@ hipError_t confidence_enqueue(const DecBuffers& b, const TokenClasses* tc_dev, c
 hipError_t confidence_enqueue_raw(const TokenClasses* tc_dev, const int* tokens, const int* lens, const float* logp, int n,
                                   int T, int kmax, const int* atom_idx, const int* n_atoms, const double* scores,
                                   double* atom_scores, double* overall, hipStream_t s);
+// graph_pack.hip: the dense outputs of n rows ([n,T] ids, [n,kmax] atoms, [n,kmax,kmax] bonds; the three score pointers all
+// null or all set) as packed records (mnx_graph_pack): count, scan and fill, three launches on s
+hipError_t graph_pack_enqueue(const TokenClasses* tc_dev, const VocabText* vt_dev, const int* tokens, const int* lens, int n,
+                              int T, int kmax, const int* atom_idx, const int* n_atoms, const unsigned char* edges,
+                              const double* atom_scores, const double* edge_scores, const double* overall, mnx_mol* mols,
+                              mnx_atom* atoms, unsigned atom_cap, mnx_bond* bonds, unsigned bond_cap, char* text,
+                              unsigned text_cap, unsigned* totals, hipStream_t s);
 hipError_t edges_enqueue(const DecWeights& w, const DecBuffers& bf, const float* hidden, const int* slot_map,
                          const int* atom_idx, const int* n_atoms, int B, int kmax, int row_stride_T,
                          unsigned char* edges, double* scores, hipStream_t s);

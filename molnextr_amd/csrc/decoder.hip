@@ -12,6 +12,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "dec_types.h"
+#include "atom_walk.h"
 #include "kvq.h"
 
 namespace mnx {
@@ -758,42 +759,7 @@ hipError_t dec_enqueue_tick(const DecWeights& w, const DecBuffers& b, int slots_
 // sequence (reference tokenization.py:464-515): for every atom token group followed by "x y <next>", the
 // position of <next>. One thread per sequence (a <= 480-step scan).
 // =============================================================================================
-// The sequential walk of the scan over seq[0, n) (ids staged in LDS): calls emit(k, i0, j) for the k-th atom, whose symbol
-// tokens are [i0, j) and whose decoder position is j + 2; returns the number of atoms found (kmax does not bound it).
-template <typename Emit>
-__device__ __forceinline__ int atom_walk(const int* seq, int n, const unsigned char* fl, const TokenClasses* __restrict__ tc,
-                                         Emit emit) {
-    const int x0 = tc->x0, y0 = tc->y0, lb = tc->lbracket, rb = tc->rbracket;
-    const int iC = tc->id_C, il = tc->id_l, iB = tc->id_B, ir = tc->id_r;
-    int i = 0, k = 0;
-    while (i < n) {
-        const int t = seq[i];
-        if (t == 2 || t == 0) break;                                  // <eos> / <pad>
-        if (t >= x0) { ++i; continue; }                               // coordinate bins
-        if (!(fl[t] & 2)) { ++i; continue; }                          // not an atom token
-        int j;
-        if (t == lb) {
-            j = i + 1;
-            while (j < n && seq[j] < x0 && (fl[seq[j]] & 1)) {
-                ++j;
-                if (seq[j - 1] == rb) break;
-            }
-        } else if (i + 1 < n && ((t == iC && seq[i + 1] == il) || (t == iB && seq[i + 1] == ir))) {
-            j = i + 2;
-        } else {
-            j = i + 1;
-        }
-        if (j + 2 < n && seq[j] >= x0 && seq[j] < y0 && seq[j + 1] >= y0) {
-            emit(k, i, j);
-            ++k;
-            i = j + 2;
-        } else {
-            i = j;
-        }
-    }
-    return k;
-}
-
+// The sequential walk itself is atom_walk (atom_walk.h), shared with graph_pack.hip.
 __global__ __launch_bounds__(64) void atom_scan_kernel(const int* __restrict__ lens, const int* __restrict__ tokens,
                                                        const TokenClasses* __restrict__ tc, const int* __restrict__ slots,
                                                        int n_rows, int T, int kmax, int* __restrict__ atom_idx,

@@ -103,6 +103,8 @@ struct mnx_engine {
     int* rowc_seq = nullptr;            // device [MAX_REF_BATCH]: 0, 1, 2, ... (row indices of a chunk's tiles at admission)
     TokenClasses* tc_dev = nullptr;
     bool have_tc = false;
+    VocabText* vt_dev = nullptr;        // names of the symbol ids (mnx_set_vocab_text), read by mnx_graph_pack
+    bool have_vt = false;
     int n_chunk_bufs = 0;
     bool use_graph = true;
     // greedy ticks of up to dec_fused_max rows run as three launches per layer (dec_fused.hip): dec_tile rows per workgroup in
@@ -627,6 +629,7 @@ int mnx_create(const mnx_config* cfg, const mnx_weight_desc* weights, int32_t n_
             P.problems.push_back("row index table upload failed");
     }
     h->tc_dev = (TokenClasses*)P.dalloc(sizeof(TokenClasses));
+    h->vt_dev = (VocabText*)P.dalloc(sizeof(VocabText));
     h->prep_bbox = (int*)P.dalloc(4 * sizeof(int));   // at create: mnx_preprocess may run beside another entry point
     h->prep_bbox_batch = (int*)P.dalloc((size_t)MNX_PREP_MAX_PAGES * 4 * sizeof(int));
     {
@@ -1264,6 +1267,63 @@ int mnx_set_token_classes(mnx_engine* h, const uint8_t* flags, int32_t n, int32_
     tc.x0 = h->cfg.sym_offset; tc.y0 = h->cfg.sym_offset + h->cfg.coord_bins; tc.vocab = h->cfg.vocab;
     HIPCHK(h, hipMemcpy(h->tc_dev, &tc, sizeof(tc), hipMemcpyHostToDevice));
     h->have_tc = true;
+    return MNX_OK;
+}
+
+int mnx_set_vocab_text(mnx_engine* h, const char* bytes, const uint32_t* offsets, int32_t n) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    if (!bytes || !offsets || n < 1 || n > 256) { h->err = "mnx_set_vocab_text: null pointer or n outside 1..256"; return MNX_ERR_INVALID_ARG; }
+    if (n != h->cfg.sym_offset) {     // a shorter table would spell shortened SMILES without a word
+        h->err = "mnx_set_vocab_text: n = " + std::to_string(n) + " names, but the vocabulary has cfg.sym_offset = " +
+                 std::to_string(h->cfg.sym_offset) + " symbol ids";
+        return MNX_ERR_INVALID_ARG;
+    }
+    if (offsets[0] != 0) { h->err = "mnx_set_vocab_text: offsets[0] must be 0"; return MNX_ERR_INVALID_ARG; }
+    VocabText vt{};
+    for (int i = 0; i < n; ++i) {
+        if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 8) {
+            h->err = "mnx_set_vocab_text: name of id " + std::to_string(i) + " is longer than 8 bytes or its offsets decrease";
+            return MNX_ERR_INVALID_ARG;
+        }
+        vt.len[i] = (unsigned char)(offsets[i + 1] - offsets[i]);
+        memcpy(vt.name[i], bytes + offsets[i], vt.len[i]);
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemcpy(h->vt_dev, &vt, sizeof(vt), hipMemcpyHostToDevice));
+    h->have_vt = true;
+    return MNX_OK;
+}
+
+int mnx_graph_pack(mnx_engine* h, const int32_t* tokens, const int32_t* lengths, int32_t n, int32_t T,
+                   const int32_t* atom_idx, const int32_t* n_atoms, const uint8_t* edges, int32_t kmax,
+                   const double* atom_scores, const double* edge_scores, const double* overall_score, mnx_mol* mols,
+                   mnx_atom* atoms, uint32_t atom_cap, mnx_bond* bonds, uint32_t bond_cap, char* text, uint32_t text_cap,
+                   uint32_t* totals, void* stream) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    if (!tokens || !lengths || !atom_idx || !n_atoms || !edges || !mols || !totals || (!atoms && atom_cap) ||
+        (!bonds && bond_cap) || (!text && text_cap)) {
+        h->err = "mnx_graph_pack: null pointer";
+        return MNX_ERR_INVALID_ARG;
+    }
+    if (n < 1 || n > 65536 || T < 1 || T > 512 || kmax < 1 || kmax > h->db.kmax) {
+        h->err = "mnx_graph_pack: 1 <= n <= 65536, 1 <= T <= 512 and 1 <= kmax <= cfg.max_atoms required";
+        return MNX_ERR_INVALID_ARG;
+    }
+    const int n_scores = (atom_scores != nullptr) + (edge_scores != nullptr) + (overall_score != nullptr);
+    if (n_scores != 0 && n_scores != 3) {
+        h->err = "mnx_graph_pack: atom_scores, edge_scores and overall_score go together (all three or none)";
+        return MNX_ERR_INVALID_ARG;
+    }
+    if (((uintptr_t)mols | (uintptr_t)atoms | (uintptr_t)bonds) & 7 || ((uintptr_t)totals & 3)) {
+        h->err = "mnx_graph_pack: mols, atoms and bonds must be 8-byte aligned, totals 4-byte";
+        return MNX_ERR_INVALID_ARG;
+    }
+    if (!h->have_tc) { h->err = "mnx_graph_pack: call mnx_set_token_classes first"; return MNX_ERR_INVALID_ARG; }
+    if (!h->have_vt) { h->err = "mnx_graph_pack: call mnx_set_vocab_text first"; return MNX_ERR_INVALID_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, graph_pack_enqueue(h->tc_dev, h->vt_dev, tokens, lengths, n, T, kmax, atom_idx, n_atoms, edges, atom_scores,
+                                 edge_scores, overall_score, mols, atoms, atom_cap, bonds, bond_cap, text, text_cap, totals,
+                                 (hipStream_t)stream));
     return MNX_OK;
 }
 

@@ -1,0 +1,255 @@
+// graph_pack.hip — the dense outputs of mnx_predict* as packed atom / bond / text tables (mnx_graph_pack): what
+// CharTokenizer.sequence_to_smiles (reference tokenization.py:464-515) and the pair loop of predict_images (model.py:135-143)
+// derive on the host, as three launches on the device.
+//   count  one workgroup per image: atoms, bonds and SMILES bytes of the image -> mols[b]
+//   scan   exclusive scan of the three counts over the images -> atom0 / bond0 / text0 of every image, totals
+//   fill   one workgroup per image: text, atom records, bond records behind those offsets
+// Every position in the tables follows from a prefix scan: no atomics, the output is the same word for word on every run.
+// Records are written as whole 64-bit words, padding bytes as zeros.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/molnextr_hip.h"
+#include "atom_walk.h"
+#include "dec_types.h"
+
+namespace mnx {
+
+static_assert(sizeof(mnx_mol) == 40 && sizeof(mnx_atom) == 24 && sizeof(mnx_bond) == 16, "record layout of molnextr_hip.h");
+
+namespace {
+
+constexpr int GP_THREADS = 256;
+constexpr int GP_T = 512;            // ids of a row held in LDS (mnx_confidence's limit)
+constexpr int GP_ATOMS = 256;        // atoms a row of GP_T ids can hold (an atom takes at least 3 ids): LDS span tables
+constexpr int SCAN_THREADS = 1024;
+
+// Exclusive prefix sum of one value per thread over a workgroup of NT threads (Hillis-Steele in LDS, two buffers); *total
+// receives the sum. buf holds 2 * NT words. Ends with a barrier, so it may be called again at once.
+template <int NT>
+__device__ __forceinline__ unsigned block_scan_excl(unsigned v, unsigned* buf, unsigned* total) {
+    const int tid = threadIdx.x;
+    int cur = 0;
+    buf[tid] = v;
+    __syncthreads();
+    for (int d = 1; d < NT; d <<= 1) {
+        const unsigned x = buf[cur * NT + tid] + (tid >= d ? buf[cur * NT + tid - d] : 0u);
+        buf[(cur ^ 1) * NT + tid] = x;
+        cur ^= 1;
+        __syncthreads();
+    }
+    const unsigned incl = buf[cur * NT + tid];
+    *total = buf[cur * NT + NT - 1];
+    __syncthreads();
+    return incl - v;
+}
+
+// What count and fill both need of one row, held in LDS.
+struct RowLds {
+    int seq[GP_T];
+    unsigned char fl[256];
+    unsigned char vlen[256];
+    int red[GP_THREADS];
+};
+
+// Stages the row's ids, the token classes and the name lengths; returns n = ids of the row and sets *end to the position of the
+// first '<eos>' / '<pad>' (n when there is none): the ids in front of it spell the SMILES.
+__device__ __forceinline__ int stage_row(RowLds& L, const int* __restrict__ tokens, const int* __restrict__ lens,
+                                         const TokenClasses* __restrict__ tc, const VocabText* __restrict__ vt, int row, int T,
+                                         int* end) {
+    const int tid = threadIdx.x;
+    const int n = max(min(min(lens[row], T), GP_T), 0);
+    int first = n;
+    for (int i = tid; i < n; i += GP_THREADS) {
+        const int t = tokens[(size_t)row * T + i];
+        L.seq[i] = t;
+        if ((t == 2 || t == 0) && i < first) first = i;
+    }
+    for (int i = tid; i < 256; i += GP_THREADS) { L.fl[i] = tc->flags[i]; L.vlen[i] = vt->len[i]; }
+    L.red[tid] = first;
+    __syncthreads();
+    for (int w = GP_THREADS / 2; w > 0; w >>= 1) {
+        if (tid < w) L.red[tid] = min(L.red[tid], L.red[tid + w]);
+        __syncthreads();
+    }
+    *end = L.red[0];
+    __syncthreads();
+    return n;
+}
+
+// bytes id t contributes to the SMILES: its name's, nothing for a coordinate bin (or an id outside the vocabulary)
+__device__ __forceinline__ unsigned name_bytes(const RowLds& L, int t, int x0) {
+    return (unsigned)t < (unsigned)min(x0, 256) ? L.vlen[t] : 0u;
+}
+
+__device__ __forceinline__ void store_mol_counts(mnx_mol* m, unsigned n_atoms, unsigned n_bonds, unsigned smiles_len,
+                                                 unsigned flags, double overall) {
+    // atom0 / bond0 / text0 are the scan's; everything else of the record is written here
+    m->n_atoms = n_atoms;
+    m->n_bonds = n_bonds;
+    m->smiles_len = smiles_len;
+    m->flags = flags;
+    m->reserved = 0;
+    m->overall_score = overall;
+}
+
+__global__ __launch_bounds__(GP_THREADS) void graph_count_kernel(
+        const int* __restrict__ tokens, const int* __restrict__ lens, const TokenClasses* __restrict__ tc,
+        const VocabText* __restrict__ vt, int T, int kmax, const int* __restrict__ n_atoms,
+        const unsigned char* __restrict__ edges, const double* __restrict__ overall, mnx_mol* __restrict__ mols) {
+    __shared__ RowLds L;
+    __shared__ unsigned scan[2 * GP_THREADS];
+    __shared__ int walk_k;
+    const int row = blockIdx.x, tid = threadIdx.x;
+    int end;
+    const int n = stage_row(L, tokens, lens, tc, vt, row, T, &end);
+    if (tid == 0) walk_k = atom_walk(L.seq, n, L.fl, tc, [](int, int, int) {});
+    const int x0 = tc->x0;
+    unsigned bytes = 0;
+    for (int i = tid; i < end; i += GP_THREADS) bytes += name_bytes(L, L.seq[i], x0);
+    unsigned text_total, bond_total;
+    block_scan_excl<GP_THREADS>(bytes, scan, &text_total);         // its barriers also publish walk_k
+    const int k = min(walk_k, kmax);
+    const int kb = min(k, max(n_atoms[row], 0));                   // rows / columns of `edges` that are defined
+    const unsigned char* e = edges + (size_t)row * kmax * kmax;
+    unsigned nb = 0;
+    for (int i = tid; i < kb; i += GP_THREADS)
+        for (int j = i + 1; j < kb; ++j) nb += e[(size_t)i * kmax + j] != 0;
+    block_scan_excl<GP_THREADS>(nb, scan, &bond_total);
+    if (tid == 0)
+        store_mol_counts(&mols[row], (unsigned)k, bond_total, text_total, walk_k > kmax ? 1u : 0u, overall ? overall[row] : 0.0);
+}
+
+// atom0 / bond0 / text0 of every image: an exclusive scan over the images in tiles of SCAN_THREADS with a running carry, by ONE
+// workgroup (n images are a few thousand words). 64-bit carries: a total beyond 2^32 - 1 saturates and sets totals[3].
+__global__ __launch_bounds__(SCAN_THREADS) void graph_scan_kernel(mnx_mol* __restrict__ mols, int n, unsigned atom_cap,
+                                                                  unsigned bond_cap, unsigned text_cap,
+                                                                  unsigned* __restrict__ totals) {
+    __shared__ unsigned scan[2 * SCAN_THREADS];
+    const int tid = threadIdx.x;
+    unsigned long long ca = 0, cb = 0, ct = 0;
+    for (int base = 0; base < n; base += SCAN_THREADS) {
+        const int b = base + tid;
+        const unsigned a = b < n ? mols[b].n_atoms : 0u, bo = b < n ? mols[b].n_bonds : 0u, t = b < n ? mols[b].smiles_len : 0u;
+        unsigned ta, tb, tt;
+        const unsigned ea = block_scan_excl<SCAN_THREADS>(a, scan, &ta);
+        const unsigned eb = block_scan_excl<SCAN_THREADS>(bo, scan, &tb);
+        const unsigned et = block_scan_excl<SCAN_THREADS>(t, scan, &tt);
+        if (b < n) {
+            mols[b].atom0 = (unsigned)min(ca + ea, 0xffffffffull);
+            mols[b].bond0 = (unsigned)min(cb + eb, 0xffffffffull);
+            mols[b].text0 = (unsigned)min(ct + et, 0xffffffffull);
+        }
+        ca += ta; cb += tb; ct += tt;
+    }
+    if (tid == 0) {
+        totals[0] = (unsigned)min(ca, 0xffffffffull);
+        totals[1] = (unsigned)min(cb, 0xffffffffull);
+        totals[2] = (unsigned)min(ct, 0xffffffffull);
+        totals[3] = (ca > atom_cap || cb > bond_cap || ct > text_cap) ? 1u : 0u;
+    }
+}
+
+__global__ __launch_bounds__(GP_THREADS) void graph_fill_kernel(
+        const int* __restrict__ tokens, const int* __restrict__ lens, const TokenClasses* __restrict__ tc,
+        const VocabText* __restrict__ vt, int T, int kmax, const int* __restrict__ atom_idx,
+        const int* __restrict__ n_atoms, const unsigned char* __restrict__ edges, const double* __restrict__ atom_scores,
+        const double* __restrict__ edge_scores, const mnx_mol* __restrict__ mols, unsigned long long* __restrict__ atoms,
+        unsigned atom_cap, unsigned long long* __restrict__ bonds, unsigned bond_cap, char* __restrict__ text,
+        unsigned text_cap) {
+    __shared__ RowLds L;
+    __shared__ unsigned scan[2 * GP_THREADS];
+    __shared__ unsigned off[GP_T + 1];               // byte offset of every id inside the image's SMILES
+    __shared__ unsigned char vname[256 * 8];
+    __shared__ short span0[GP_ATOMS], span1[GP_ATOMS];   // atom a: symbol ids [span0, span1), x at span1, y at span1 + 1
+    const int row = blockIdx.x, tid = threadIdx.x;
+    int end;
+    const int n = stage_row(L, tokens, lens, tc, vt, row, T, &end);
+    for (int i = tid; i < 256 * 8; i += GP_THREADS) vname[i] = vt->name[i >> 3][i & 7];
+    if (tid == 0)
+        atom_walk(L.seq, n, L.fl, tc, [&](int a, int i0, int j) {
+            if (a < GP_ATOMS) { span0[a] = (short)i0; span1[a] = (short)j; }
+        });
+    const mnx_mol m = mols[row];
+    const int x0 = tc->x0, y0 = tc->y0;
+
+    // ---- text: per-id byte offsets by a prefix scan (two neighbouring ids per thread), then every id copies its name ----
+    const int i0 = 2 * tid, i1 = 2 * tid + 1;
+    const unsigned b0 = i0 < end ? name_bytes(L, L.seq[i0], x0) : 0u, b1 = i1 < end ? name_bytes(L, L.seq[i1], x0) : 0u;
+    unsigned total;
+    const unsigned ex = block_scan_excl<GP_THREADS>(b0 + b1, scan, &total);     // its barriers publish vname and the spans
+    off[i0] = ex;
+    off[i1] = ex + b0;
+    if (tid == GP_THREADS - 1) off[GP_T] = total;
+    __syncthreads();
+    for (int i = tid; i < end; i += GP_THREADS) {
+        const int t = L.seq[i];
+        const unsigned nb = name_bytes(L, t, x0);
+        const unsigned at = m.text0 + off[i];
+        for (unsigned c = 0; c < nb; ++c)
+            if ((unsigned long long)at + c < text_cap) text[at + c] = (char)vname[t * 8 + c];
+    }
+
+    // ---- atoms: one record per atom of the walk, three 64-bit words ----
+    const int k = (int)m.n_atoms;
+    for (int a = tid; a < k; a += GP_THREADS) {
+        const unsigned long long at = (unsigned long long)m.atom0 + a;
+        if (at >= atom_cap) continue;
+        const int s0 = span0[a], s1 = span1[a];
+        const unsigned sym0 = off[s0], sym_len = off[s1] - off[s0];
+        const unsigned idx = (unsigned)atom_idx[(size_t)row * kmax + a] & 0xffffu;
+        const unsigned xb = (unsigned)(L.seq[s1] - x0) & 0xffffu, yb = (unsigned)(L.seq[s1 + 1] - y0) & 0xffffu;
+        const double sc = atom_scores ? atom_scores[(size_t)row * kmax + a] : 0.0;
+        unsigned long long* r = atoms + at * 3;
+        r[0] = (unsigned long long)sym0 | ((unsigned long long)(sym_len & 0xffffu) << 32) | ((unsigned long long)idx << 48);
+        r[1] = (unsigned long long)xb | ((unsigned long long)yb << 16);
+        r[2] = (unsigned long long)__double_as_longlong(sc);
+    }
+
+    // ---- bonds: ordered compaction — row counts, a scan over the rows (tiles of GP_THREADS rows with a carry), then every
+    //      row writes its own bonds in column order ----
+    const int kb = min(k, max(n_atoms[row], 0));
+    const unsigned char* e = edges + (size_t)row * kmax * kmax;
+    const double* es = edge_scores ? edge_scores + (size_t)row * kmax * kmax : nullptr;
+    unsigned carry = 0;
+    for (int base = 0; base < kb; base += GP_THREADS) {
+        const int i = base + tid;
+        unsigned cnt = 0;
+        if (i < kb)
+            for (int j = i + 1; j < kb; ++j) cnt += e[(size_t)i * kmax + j] != 0;
+        unsigned tile_total;
+        unsigned at = carry + block_scan_excl<GP_THREADS>(cnt, scan, &tile_total);
+        carry += tile_total;
+        if (i < kb && cnt)
+            for (int j = i + 1; j < kb; ++j) {
+                const unsigned ty = e[(size_t)i * kmax + j];
+                if (!ty) continue;
+                const unsigned long long o = (unsigned long long)m.bond0 + at;
+                ++at;
+                if (o >= bond_cap) continue;
+                const unsigned rv = e[(size_t)j * kmax + i];
+                const double sc = es ? es[(size_t)i * kmax + j] : 0.0;
+                bonds[o * 2] = (unsigned long long)(unsigned)i | ((unsigned long long)(unsigned)j << 16) |
+                               ((unsigned long long)ty << 32) | ((unsigned long long)rv << 40);
+                bonds[o * 2 + 1] = (unsigned long long)__double_as_longlong(sc);
+            }
+    }
+}
+
+}  // namespace
+
+hipError_t graph_pack_enqueue(const TokenClasses* tc_dev, const VocabText* vt_dev, const int* tokens, const int* lens, int n,
+                              int T, int kmax, const int* atom_idx, const int* n_atoms, const unsigned char* edges,
+                              const double* atom_scores, const double* edge_scores, const double* overall, mnx_mol* mols,
+                              mnx_atom* atoms, unsigned atom_cap, mnx_bond* bonds, unsigned bond_cap, char* text,
+                              unsigned text_cap, unsigned* totals, hipStream_t s) {
+    hipLaunchKernelGGL(graph_count_kernel, dim3(n), dim3(GP_THREADS), 0, s, tokens, lens, tc_dev, vt_dev, T, kmax, n_atoms,
+                       edges, overall, mols);
+    hipLaunchKernelGGL(graph_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, mols, n, atom_cap, bond_cap, text_cap, totals);
+    hipLaunchKernelGGL(graph_fill_kernel, dim3(n), dim3(GP_THREADS), 0, s, tokens, lens, tc_dev, vt_dev, T, kmax, atom_idx,
+                       n_atoms, edges, atom_scores, edge_scores, mols, (unsigned long long*)atoms, atom_cap,
+                       (unsigned long long*)bonds, bond_cap, text, text_cap);
+    return hipGetLastError();
+}
+
+}  // namespace mnx

@@ -26,7 +26,7 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
            "mnx_gemm16_split", "mnx_decode_forced", "mnx_gemm_clock", "mnx_probe_mfma", "mnx_set_op_terms",
            "mnx_predict_confidence", "mnx_confidence", "mnx_window_attn", "mnx_kv_block", "mnx_preprocess_batch",
            "mnx_encode_gray8", "mnx_predict_gray8", "mnx_decode_guided", "mnx_predict_guided", "mnx_patch_embed",
-           "mnx_layernorm16", "mnx_merge_ln16", "mnx_cast16", "mnx_sgemm_tn")
+           "mnx_layernorm16", "mnx_merge_ln16", "mnx_cast16", "mnx_sgemm_tn", "mnx_set_vocab_text", "mnx_graph_pack")
 
 # Encoder operand modes (include/molnextr_hip.h MNX_DTYPE_*). "fp16x3" — split fp16 operands, three MFMA terms per
 # product, fp32-class results — is the default: it is the fastest mode whose results stay a factor of four inside north_star's
@@ -74,6 +74,41 @@ class MnxWeightDesc(C.Structure):
 class MnxPage(C.Structure):
     """include/molnextr_hip.h mnx_page: one page of a mnx_preprocess_batch arena."""
     _fields_ = [("offset", C.c_uint64), ("height", C.c_int32), ("width", C.c_int32)]
+
+
+class MnxMol(C.Structure):
+    """include/molnextr_hip.h mnx_mol: one molecule of mnx_graph_pack (40 bytes)."""
+    _fields_ = [("atom0", C.c_uint32), ("n_atoms", C.c_uint32), ("bond0", C.c_uint32), ("n_bonds", C.c_uint32),
+                ("text0", C.c_uint32), ("smiles_len", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("overall_score", C.c_double)]
+
+
+class MnxAtom(C.Structure):
+    """include/molnextr_hip.h mnx_atom (24 bytes)."""
+    _fields_ = [("sym0", C.c_uint32), ("sym_len", C.c_uint16), ("index", C.c_uint16), ("x_bin", C.c_uint16),
+                ("y_bin", C.c_uint16), ("score", C.c_double)]
+
+
+class MnxBond(C.Structure):
+    """include/molnextr_hip.h mnx_bond (16 bytes)."""
+    _fields_ = [("i", C.c_uint16), ("j", C.c_uint16), ("type", C.c_uint8), ("rev", C.c_uint8), ("score", C.c_double)]
+
+
+# the same three records as numpy structured dtypes (C layout: align=True), what Engine.graph_pack returns
+MOL_DTYPE = np.dtype([("atom0", "<u4"), ("n_atoms", "<u4"), ("bond0", "<u4"), ("n_bonds", "<u4"), ("text0", "<u4"),
+                      ("smiles_len", "<u4"), ("flags", "<u4"), ("reserved", "<u4"), ("overall_score", "<f8")], align=True)
+ATOM_DTYPE = np.dtype([("sym0", "<u4"), ("sym_len", "<u2"), ("index", "<u2"), ("x_bin", "<u2"), ("y_bin", "<u2"),
+                       ("score", "<f8")], align=True)
+BOND_DTYPE = np.dtype([("i", "<u2"), ("j", "<u2"), ("type", "u1"), ("rev", "u1"), ("score", "<f8")], align=True)
+MOL_TRUNCATED = 1                       # mnx_mol.flags bit 0: more atoms than kmax, the tables hold the first kmax
+
+
+def vocab_text(tok):
+    """mnx_set_vocab_text arguments of a tokenizer: (bytes, uint32 offsets [n + 1], n) — the UTF-8 names of ids 0 .. n - 1."""
+    names = [tok.itos[i].encode("utf-8") for i in range(tok.offset)]
+    offsets = np.zeros(len(names) + 1, dtype=np.uint32)
+    offsets[1:] = np.cumsum([len(b) for b in names])
+    return b"".join(names), offsets, len(names)
 
 
 PREP_MAX_PAGES = 4096                   # include/molnextr_hip.h MNX_PREP_MAX_PAGES: pages per mnx_preprocess_batch call
@@ -167,6 +202,11 @@ def load_library():
     lib.mnx_probe_mfma.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), vp]
     lib.mnx_set_token_classes.restype = C.c_int
     lib.mnx_set_token_classes.argtypes = [vp, C.c_char_p, i32, i32, i32, i32, i32, i32, i32]
+    lib.mnx_set_vocab_text.restype = C.c_int
+    lib.mnx_set_vocab_text.argtypes = [vp, C.c_char_p, vp, i32]
+    lib.mnx_graph_pack.restype = C.c_int
+    lib.mnx_graph_pack.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp,
+                                   C.c_uint32, vp, vp]
     lib.mnx_atom_scan.restype = C.c_int
     lib.mnx_atom_scan.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.mnx_preprocess.restype = C.c_int
@@ -290,6 +330,7 @@ class Engine:
             raise MnxError(f"mnx_create failed ({rc}): {self.lib.mnx_last_error(None).decode()}")
         self.h = handle
         self._set_token_classes()
+        self._set_vocab_text()
         self.n_feat = enc.num_features
         g = enc.img_size // enc.patch >> (len(enc.depths) - 1)
         self.n_mem = g * g
@@ -312,6 +353,12 @@ class Engine:
         flags = self.token_class_flags(tok)
         ids = [tok.stoi[c] for c in "[]ClBr"]
         self._check(self.lib.mnx_set_token_classes(self.h, flags, n, *ids), "mnx_set_token_classes")
+
+    def _set_vocab_text(self):
+        """Hands the names of the vocabulary's symbol ids to the library: what graph_pack spells the SMILES with."""
+        from .tokenizer import CharTokenizer
+        text, offsets, n = vocab_text(CharTokenizer(64))
+        self._check(self.lib.mnx_set_vocab_text(self.h, text, offsets.ctypes.data, n), "mnx_set_vocab_text")
 
     def close(self):
         if getattr(self, "h", None):
@@ -698,6 +745,45 @@ class Engine:
                                   _ptr(n_atoms), _ptr(atom_idx), _ptr(edges), k, _stream())
         self._check(rc, "mnx_predict")
         return {"tokens": tokens, "lengths": lengths, "n_atoms": n_atoms, "atom_idx": atom_idx, "edges": edges}
+
+    # modest first capacities of graph_pack per image (a drug-like molecule has 20-40 heavy atoms, about as many bonds and a
+    # SMILES of well under 200 bytes); `totals` sizes the one repeat when a job needs more
+    PACK_GUESS = (48, 56, 192)
+
+    def graph_pack(self, out: dict, caps=None) -> dict:
+        """predict's result dict (device tensors) -> the molecules as numpy structured arrays (mnx_graph_pack): {'mols'
+        [n] MOL_DTYPE, 'atoms' ATOM_DTYPE, 'bonds' BOND_DTYPE, 'text' bytes, 'totals' uint32 [4]}. With 'atom_scores',
+        'edge_scores' and 'overall_score' in `out` the records carry the confidences, otherwise zeros. One D2H copy per table
+        (plus the 16 bytes of totals); starts from PACK_GUESS per image (or caps = (atom_cap, bond_cap, text_cap)) and
+        repeats at most once with the sizes `totals` reports."""
+        tokens, lengths = out["tokens"], out["lengths"]
+        n, T = tokens.shape
+        kmax = out["atom_idx"].shape[1]
+        dev = tokens.device
+        scored = out.get("edge_scores") is not None
+        sc = [out["atom_scores"], out["edge_scores"], out["overall_score"]] if scored else [None, None, None]
+        mols = torch.empty(n * MOL_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        totals = torch.empty(4, dtype=torch.int32, device=dev)
+        caps = tuple(int(c) for c in caps) if caps is not None else tuple(n * g for g in self.PACK_GUESS)
+        for attempt in range(2):
+            atoms = torch.empty(max(caps[0], 1) * ATOM_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            bonds = torch.empty(max(caps[1], 1) * BOND_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            text = torch.empty(max(caps[2], 1), dtype=torch.uint8, device=dev)
+            self._check(self.lib.mnx_graph_pack(self.h, _ptr(tokens), _ptr(lengths), n, T, _ptr(out["atom_idx"]),
+                                                _ptr(out["n_atoms"]), _ptr(out["edges"]), kmax, _ptr(sc[0]), _ptr(sc[1]),
+                                                _ptr(sc[2]), _ptr(mols), _ptr(atoms), caps[0], _ptr(bonds), caps[1], _ptr(text),
+                                                caps[2], _ptr(totals), _stream()), "mnx_graph_pack")
+            tot = totals.cpu().numpy().view(np.uint32)
+            if not tot[3]:
+                break
+            if attempt:
+                raise MnxError(f"mnx_graph_pack: capacities {caps} too small after sizing them from totals {tot.tolist()}")
+            caps = (int(tot[0]), int(tot[1]), int(tot[2]))
+        na, nb, nt = int(tot[0]), int(tot[1]), int(tot[2])
+        return {"mols": mols.cpu().numpy().view(MOL_DTYPE),
+                "atoms": atoms[:na * ATOM_DTYPE.itemsize].cpu().numpy().view(ATOM_DTYPE),
+                "bonds": bonds[:nb * BOND_DTYPE.itemsize].cpu().numpy().view(BOND_DTYPE),
+                "text": text[:nt].cpu().numpy().tobytes(), "totals": tot.copy()}
 
     def atom_scan(self, tokens: torch.Tensor, lengths: torch.Tensor, kmax: Optional[int] = None):
         """On-device CharTokenizer.sequence_to_smiles 'indices' for [n,T] int32 id sequences."""

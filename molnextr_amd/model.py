@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import weights as W
-from .engine import DEFAULT_DTYPE, Engine, MnxError
+from .engine import DEFAULT_DTYPE, MOL_TRUNCATED, Engine, MnxError
 from .preprocess import load_image_rgb, transform_image, transform_image_gray
 from .tokenizer import coords_labels, get_tokenizer
 
@@ -99,9 +99,42 @@ def decode_batch(engine: Engine, features: torch.Tensor, tokenizer=None, ref_bat
     return preds
 
 
+def unpack_graphs(mols, atoms, bonds, text, coord_bins: int = 64, with_scores: bool = False) -> List[dict]:
+    """The records of mnx_graph_pack (Engine.graph_pack's 'mols', 'atoms', 'bonds' structured arrays and 'text' bytes) as the
+    per-image dicts of predict_pipeline. Pure host code: every field is copied, the only arithmetic is the reference's own
+    coordinate division bin / (coord_bins - 1). 'chartok_coords' = {smiles, symbols, coords, indices[, atom_scores]};
+    'bonds' = [(i, j, type, rev[, score])] in the reference's loop order (i < j ascending) stands where the dense path has
+    'edges' (and 'edge_scores'); with_scores also carries 'overall_score'."""
+    text = bytes(text)
+    den = coord_bins - 1
+    a_sym0, a_len, a_idx = atoms["sym0"].tolist(), atoms["sym_len"].tolist(), atoms["index"].tolist()
+    a_x, a_y = atoms["x_bin"].tolist(), atoms["y_bin"].tolist()
+    b_i, b_j, b_t, b_r = bonds["i"].tolist(), bonds["j"].tolist(), bonds["type"].tolist(), bonds["rev"].tolist()
+    if with_scores:
+        a_sc, b_sc, overall = atoms["score"].tolist(), bonds["score"].tolist(), mols["overall_score"].tolist()
+    preds = []
+    for m, (a0, na, b0, nb, t0, tl) in enumerate(zip(mols["atom0"].tolist(), mols["n_atoms"].tolist(), mols["bond0"].tolist(),
+                                                     mols["n_bonds"].tolist(), mols["text0"].tolist(),
+                                                     mols["smiles_len"].tolist())):
+        a1, b1 = a0 + na, b0 + nb
+        r = {"smiles": text[t0:t0 + tl].decode("utf-8"),
+             "symbols": [text[t0 + s:t0 + s + n].decode("utf-8") for s, n in zip(a_sym0[a0:a1], a_len[a0:a1])],
+             "indices": a_idx[a0:a1],
+             "coords": [[x / den, y / den] for x, y in zip(a_x[a0:a1], a_y[a0:a1])]}
+        pred = {"chartok_coords": r}
+        if with_scores:
+            r["atom_scores"] = a_sc[a0:a1]
+            pred["bonds"] = list(zip(b_i[b0:b1], b_j[b0:b1], b_t[b0:b1], b_r[b0:b1], b_sc[b0:b1]))
+            pred["overall_score"] = overall[m]
+        else:
+            pred["bonds"] = list(zip(b_i[b0:b1], b_j[b0:b1], b_t[b0:b1], b_r[b0:b1]))
+        preds.append(pred)
+    return preds
+
+
 def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_batch_size: int = 16,
                      max_len: Optional[int] = None, beam_size: int = 1, compute_confidence: bool = False,
-                     labels=None, free_run=False) -> List[dict]:
+                     labels=None, free_run=False, packed: bool = False) -> List[dict]:
     """Encoder + Decoder.decode for MANY images through the engine's continuous-batching path (mnx_predict):
     same per-image dicts as `decode_batch`, identical results (the on-device atom scan equals
     sequence_to_smiles' indices), much higher throughput. compute_confidence=True: mnx_predict_confidence, the same
@@ -111,8 +144,14 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
     ref_batch_size: rows per reference batch (the positional-encoding numbering unit), up to MAX_REF_BATCH = 512 for greedy
     decoding (and the engine's max_batch / dec_slots: Engine.max_ref_batch), up to 32 with beam_size > 1.
     labels: int [n, L] — label-guided decoding along row i for image i (mnx_predict_guided; Engine.decode_guided describes the
-    rows; a row without '<eos>' raises ValueError unless free_run — a bool, or one per row — exempts it); greedy only."""
+    rows; a row without '<eos>' raises ValueError unless free_run — a bool, or one per row — exempts it); greedy only.
+    packed: the molecules are put together on the device (mnx_graph_pack) and only their records cross to the host
+    (unpack_graphs: 'bonds' instead of the dense 'edges' / 'edge_scores'); greedy only, beam search keeps the dense path.
+    The packed path does not run the host tokenizer, so it does not re-verify the device atom scan as the dense path's
+    assertion does: 'indices' are the scan's atom_idx, and a molecule beyond max_atoms raises RuntimeError."""
     tok = (tokenizer or get_tokenizer())["chartok_coords"]
+    if packed and beam_size > 1:
+        raise NotImplementedError("packed results are built for greedy decoding (beam search keeps the dense path)")
     if labels is not None and beam_size > 1:
         raise NotImplementedError("label-guided decoding is greedy (beam search with labels is not built)")
     if compute_confidence and beam_size > 1:
@@ -124,6 +163,11 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
     if labels is not None:
         conf.update(labels=labels, free_run=free_run)
     out = engine.predict(images, ref_batch=ref_batch_size, max_len=max_len, beam=beam_size, **conf)
+    if packed:
+        rec = engine.graph_pack(out)
+        if (rec["mols"]["flags"] & MOL_TRUNCATED).any():
+            raise RuntimeError(f"a molecule has more atoms than the engine capacity max_atoms={engine.max_atoms}")
+        return unpack_graphs(rec["mols"], rec["atoms"], rec["bonds"], rec["text"], tok.maxx, compute_confidence)
     scores = out["scores"].cpu().numpy() if beam_size > 1 else None
     lens = out["lengths"].cpu().numpy()
     toks = out["tokens"].cpu().numpy()
@@ -169,12 +213,15 @@ class molnextr:
     decisions near a tie can differ).
     image_format: what the transform hands to the encoder — "fp32" (the default: normalised [n,3,S,S], one mnx_preprocess per
     page) or "gray8" (the gray byte per pixel, [n,S,S]: all pages of a group in one mnx_preprocess_batch, a twelfth of the
-    staged bytes; every output bit for bit the same)."""
+    staged bytes; every output bit for bit the same).
+    packed_results: True = the molecules are put together on the device (mnx_graph_pack) and cross to the host as packed atom /
+    bond / text records instead of the dense token, bond and score matrices; the output dicts are the same."""
 
     image_format = "fp32"
+    packed_results = False
 
     def __init__(self, model_path, device=None, max_batch: int = 32, dtype: str = DEFAULT_DTYPE,
-                 device_preprocess: bool = True, image_format: str = "fp32"):
+                 device_preprocess: bool = True, image_format: str = "fp32", packed_results: bool = False):
         if model_path is None:
             raise ValueError("molnextr(model_path): a checkpoint path is required (pass 'synthetic' explicitly for the "
                              "deterministic test checkpoint)")
@@ -196,6 +243,7 @@ class molnextr:
         if image_format not in ("fp32", "gray8"):
             raise ValueError(f"image_format must be 'fp32' or 'gray8', got {image_format!r}")
         self.image_format = image_format
+        self.packed_results = bool(packed_results)
         self.engine = Engine(states["encoder"], states["decoder"], device=device.index or 0, max_batch=max_batch,
                              dtype=dtype, image_format=image_format)
         self.input_size = args.input_size
@@ -371,6 +419,8 @@ class molnextr:
         group = (self.group_images // batch_size) * batch_size
         groups = [input_images[i:i + group] for i in range(0, len(input_images), group)]
         conf = {"compute_confidence": True} if return_confidence else {}
+        if self.packed_results:
+            conf["packed"] = True
         gen = self._prefetched(groups)
         try:
             for x in gen:
@@ -387,10 +437,23 @@ class molnextr:
 
     def _assemble(self, preds: List[dict], input_images: List, return_atoms_bonds: bool, return_confidence: bool):
         """Output dicts of predict_images (reference model.py:111-196) from the per-image predictions."""
-        from .chem import convert_graph_to_smiles
+        from .chem import convert_graph_to_smiles, have_rdkit
+        packed = bool(preds) and "bonds" in preds[0]          # predictions of predict_pipeline(packed=True): bond records
+        if not packed:
+            edges = [p["edges"] for p in preds]
+        elif have_rdkit():                                    # chem.py reads edges[i][j] for i < j only: the upper triangle
+            edges = []
+            for p in preds:
+                k = len(p["chartok_coords"]["symbols"])
+                e = [[0] * k for _ in range(k)]
+                for b in p["bonds"]:
+                    e[b[0]][b[1]] = b[2]
+                edges.append(e)
+        else:
+            edges = [None] * len(preds)
         smiles_list, molblock_list, _ = convert_graph_to_smiles(
             [p["chartok_coords"]["coords"] for p in preds], [p["chartok_coords"]["symbols"] for p in preds],
-            [p["edges"] for p in preds], images=input_images)
+            edges, images=input_images)
         outputs = []
         for smiles, molfile, pred in zip(smiles_list, molblock_list, preds):
             d = {"predicted_smiles": smiles, "predicted_molfile": molfile}
@@ -403,6 +466,12 @@ class molnextr:
                         a["confidence"] = c["atom_scores"][i]
                     atoms.append(a)
                 d["atom_sets"] = atoms
+                if packed:                                    # one record per bond already, in the pair loop's order
+                    d["bond_sets"] = [
+                        {"atom_number": f"{b[0]}", "bond_type": BOND_TYPES[b[2]], "endpoints": (b[0], b[1]),
+                         **({"confidence": b[4]} if return_confidence else {})} for b in pred["bonds"]]
+                    outputs.append(d)
+                    continue
                 bonds = []
                 k = len(c["symbols"])
                 for i in range(k - 1):

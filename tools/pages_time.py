@@ -9,6 +9,9 @@ is part of the product path and no number is asserted.
     preprocess_batch(out="fp32") and (out="gray8"); wall time per call (host + device, the call synchronises) and the device
     time between two events around it;
 (b) predict_images from `--facade-pages` synthetic pages, batch_size 32, image_format fp32 against gray8: molecules / s;
+    then (gray8) the dense result path against the packed one (molnextr(packed_results=True): mnx_graph_pack), each with and
+    without return_confidence, with the result bytes per image that cross to the host in each; `--pack-out FILE` writes that
+    table to a file of its own, and `--pack-only N` runs N mnx_graph_pack calls over 1024 images alone (for a kernel trace);
 (c) patch embedding per 512 images from mnx_profile_read (kind 3), fp32 against gray input.
 The variants of a part alternate inside every repeat (A B A B ...), the table reports the median and the min .. max spread of
 each, and the spread of the fp32 path against itself is the yardstick for "not slower".
@@ -93,6 +96,69 @@ def part_b(n, repeats, lines):
         m.engine.close()
 
 
+def result_bytes(m, pages, conf):
+    """Result bytes per image copied to the host by predict_pipeline for one group of pages: dense (tokens, lengths, n_atoms,
+    edges [, the score matrices cut to the group's largest atom count]) and packed (the records and the 16 bytes of totals)."""
+    out = m.engine.predict(m._transform(pages), ref_batch=32, confidence=conf)
+    n, T = out["tokens"].shape
+    k = m.engine.max_atoms
+    dense = n * (4 * T + 4 + 4 + k * k)
+    full = dense + n * 8 * (k * k + k + 1)
+    if conf:
+        k_hi = int(out["n_atoms"].max())
+        dense += n * 8 * (k_hi * k_hi + k_hi + 1)
+    rec = m.engine.graph_pack(out)
+    packed = 16 + rec["mols"].nbytes + rec["atoms"].nbytes + rec["bonds"].nbytes + len(rec["text"])
+    return dense / n, (full if conf else dense) / n, packed / n
+
+
+def part_b_packed(n, repeats, lines):
+    """The facade's result side: dense against packed, alternating inside every repeat; the dense facade is the baseline."""
+    from molnextr_amd.model import molnextr
+    dev = torch.device("cuda", 0)
+    pages = [W.synthetic_page(i % 15) for i in range(n)]
+    ms = {"dense": molnextr("synthetic", dev, max_batch=32, image_format="gray8"),
+          "packed": molnextr("synthetic", dev, max_batch=32, image_format="gray8", packed_results=True)}
+    variants = [(k, c) for c in (False, True) for k in ms]
+    rate = {v: [] for v in variants}
+    for k, c in variants:
+        ms[k].predict_images(pages[:256], return_atoms_bonds=True, return_confidence=c, batch_size=32)
+    for _ in range(repeats):
+        for k, c in variants:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ms[k].predict_images(pages, return_atoms_bonds=True, return_confidence=c, batch_size=32)
+            rate[(k, c)].append(n / (time.perf_counter() - t0))
+    lines.append(f"(b2) predict_images(return_atoms_bonds=True) from {n} synthetic pages, batch_size 32, image_format gray8: "
+                 "molecules/s   median [min .. max] | result bytes per image copied to the host")
+    for c in (False, True):
+        dense_b, full_b, packed_b = result_bytes(ms["dense"], pages[:1024], c)
+        for k in ms:
+            note = (f"{dense_b:9.0f} B ({full_b:.0f} B before the k_hi slice)" if k == "dense" else
+                    f"{packed_b:9.0f} B (40 + 24 x atoms + 16 x bonds + text)")
+            lines.append(f"  {k:6s} return_confidence={str(c):5s} {fmt(rate[(k, c)])} molecules/s | {note}")
+    for c in (False, True):
+        d, p = rate[("dense", c)], rate[("packed", c)]
+        verdict = ("packed is faster than dense beyond the dense path's own spread" if min(p) > max(d) else
+                   "packed is slower than dense beyond the dense path's own spread" if max(p) < min(d) else
+                   "packed and dense overlap: no difference beyond the dense path's own spread")
+        lines.append(f"  return_confidence={str(c):5s}: packed / dense median {statistics.median(p) / statistics.median(d):.3f} - {verdict}")
+    for m in ms.values():
+        m.engine.close()
+
+
+def pack_only(calls):
+    """`calls` mnx_graph_pack calls over the dense outputs of 1024 images with confidences, and nothing else on the GPU
+    afterwards: run under a kernel trace, the three graph_* kernels of one call add up to its device time."""
+    from molnextr_amd.model import molnextr
+    m = molnextr("synthetic", torch.device("cuda", 0), max_batch=32, image_format="gray8")
+    out = m.engine.predict(m._transform([W.synthetic_page(i % 15) for i in range(1024)]), ref_batch=32, confidence=True)
+    for _ in range(calls):
+        rec = m.engine.graph_pack(out)
+    print(f"pack_only: {calls} calls over 1024 images, totals {rec['totals'].tolist()}")
+    m.engine.close()
+
+
 def part_c(eng, repeats, lines):
     from molnextr_amd.preprocess import normalise_gray
     dev = torch.device("cuda", eng.device)
@@ -123,8 +189,13 @@ def main():
     ap.add_argument("--facade-pages", type=int, default=2048)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--pack-out", default=None, help="write the dense-against-packed table of part b to this file")
+    ap.add_argument("--pack-only", type=int, default=0, help="run this many mnx_graph_pack calls over 1024 images and exit")
     args = ap.parse_args()
     parts = args.part.split(",")
+    if args.pack_only:
+        pack_only(args.pack_only)
+        return
     try:
         commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
     except OSError:
@@ -140,6 +211,12 @@ def main():
         eng.close()
     if "b" in parts:
         part_b(args.facade_pages, args.repeats, lines)
+        first = len(lines)
+        part_b_packed(args.facade_pages, args.repeats, lines)
+        if args.pack_out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.pack_out)), exist_ok=True)
+            with open(args.pack_out, "w") as f:
+                f.write("\n".join([lines[0]] + lines[first:]) + "\n")
     text = "\n".join(lines)
     print(text)
     if args.out:
