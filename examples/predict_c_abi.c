@@ -12,8 +12,39 @@ extern int hipMalloc(void** p, size_t n);
 extern int hipFree(void* p);
 extern int hipMemcpy(void* dst, const void* src, size_t n, int kind);
 
+/* Molecule 0 as a V2000 molfile, written on the device from the tables mnx_graph_pack left there (mnx_molfile_pack): a sizing
+ * call without a buffer, then the call that fills it. scale NULL: the reference's factor 10 on a square page. */
+static int print_first_molfile(mnx_engine* eng, int n_images, const mnx_mol* mols_dev, const mnx_atom* atoms_dev,
+                               const mnx_bond* bonds_dev, const char* text_dev, const uint32_t* table_sizes) {
+    uint32_t totals[2] = {0, 0}, *totals_dev = NULL;
+    mnx_molfile *files_dev = NULL, file;
+    char *out_dev = NULL, *out = NULL;
+    int rc, pass;
+    hipMalloc((void**)&files_dev, (size_t)n_images * sizeof(mnx_molfile));
+    hipMalloc((void**)&totals_dev, sizeof totals);
+    for (pass = 0; pass < 2; ++pass) {
+        rc = mnx_molfile_pack(eng, mols_dev, n_images, atoms_dev, table_sizes[0], bonds_dev, table_sizes[1], text_dev,
+                              table_sizes[2], /*scale=*/NULL, files_dev, out_dev, pass ? totals[0] : 0, totals_dev, /*stream=*/NULL);
+        if (rc != MNX_OK) { fprintf(stderr, "mnx_molfile_pack: %s\n", mnx_last_error(eng)); break; }
+        hipMemcpy(totals, totals_dev, sizeof totals, 2);
+        if (pass == 0 && totals[0]) hipMalloc((void**)&out_dev, totals[0]);
+    }
+    if (rc == MNX_OK) {
+        hipMemcpy(&file, files_dev, sizeof file, 2);
+        out = (char*)malloc((size_t)file.len + 1);
+        if (out && file.len) {       /* len 0: more than 999 atoms or bonds (MNX_MOLFILE_TOO_LARGE), or records beyond the tables */
+            hipMemcpy(out, out_dev + file.text0, file.len, 2);
+            printf("molfile 0 (%u bytes%s):\n%.*s", (unsigned)file.len,
+                   (file.flags & MNX_MOLFILE_PSEUDO_ATOM) ? ", with R-groups / abbreviations as pseudo-atoms" : "", (int)file.len, out);
+        }
+        free(out);
+    }
+    hipFree(files_dev); hipFree(totals_dev); hipFree(out_dev);
+    return rc;
+}
+
 /* The molecules as packed tables (mnx_graph_pack): no tokenizer on the host. A first call with modest capacities; `totals`
- * says what the job needs, so a second call with exactly that is the worst case. Prints molecule 0. */
+ * says what the job needs, so a second call with exactly that is the worst case. Prints molecule 0, then its molfile. */
 static int print_first_molecule(mnx_engine* eng, int n_images, const int32_t* tokens, const int32_t* lengths,
                                 const int32_t* atom_idx, const int32_t* n_atoms, const uint8_t* edges) {
     uint32_t caps[3], totals[4] = {0, 0, 0, 0}, *totals_dev = NULL, k;
@@ -56,6 +87,7 @@ static int print_first_molecule(mnx_engine* eng, int n_images, const int32_t* to
                 printf("  bond %u - %u  type %u\n", (unsigned)bonds[k].i, (unsigned)bonds[k].j, (unsigned)bonds[k].type);
         }
         free(atoms); free(bonds); free(text);
+        rc = print_first_molfile(eng, n_images, mols_dev, atoms_dev, bonds_dev, text_dev, totals);
     }
     hipFree(mols_dev); hipFree(totals_dev); hipFree(atoms_dev); hipFree(bonds_dev); hipFree(text_dev);
     return rc;
@@ -79,6 +111,9 @@ int run(const mnx_weight_desc* weights, int n_weights, const float* host_images 
     /* mnx_set_token_classes(eng, flags, 101, id_lbracket, id_rbracket, id_C, id_l, id_B, id_r); */
     /* ... and the names of its 101 symbol ids as UTF-8 bytes, for mnx_graph_pack (vocab/vocab_chars.json in id order): */
     /* mnx_set_vocab_text(eng, name_bytes, name_offsets, 101); */
+    /* ... and, for mnx_molfile_pack, the R-group and abbreviation names sorted bytewise (vocab/abbreviations.json); without
+     * this call the molfile step below is refused ("mnx_molfile_pack: call mnx_set_symbol_tables first") and run() fails: */
+    /* mnx_set_symbol_tables(eng, table_bytes, table_offsets, table_kinds, n_names); */
 
     const size_t img_elems = (size_t)3 * 384 * 384;
     float* images = NULL;

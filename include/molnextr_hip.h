@@ -431,6 +431,82 @@ int mnx_graph_pack(mnx_engine* h, const int32_t* tokens, const int32_t* lengths,
                    mnx_atom* atoms, uint32_t atom_cap, mnx_bond* bonds, uint32_t bond_cap, char* text, uint32_t text_cap,
                    uint32_t* totals, void* stream);
 
+/* The R-group and abbreviation names that _convert_graph_to_smiles tests an atom's symbol against before it reads it as a
+ * chemical element (MolNexTR/chemical.py:886-895, the tables of abbrs.py), for mnx_molfile_pack: name i is
+ * bytes[offsets[i] .. offsets[i+1]), 1..16 bytes, kinds[i] = 1 for an R-group and 2 for an abbreviation; n <= 512 names,
+ * strictly ascending bytewise (unsigned bytes; a prefix sorts in front of the longer name), so that the device finds a name
+ * by binary search. A name that is in both of the reference's tables ('Z') is listed once, as an R-group: that table is
+ * tested first. Copied to the device (host pointers, read before the call returns): a sibling of mnx_set_vocab_text.
+ * MNX_ERR_INVALID_ARG (with mnx_last_error): null pointer, n outside 0..512, offsets[0] != 0, a name of 0 or more than 16
+ * bytes, names not strictly ascending, a kind other than 1 or 2. */
+int mnx_set_symbol_tables(mnx_engine* h, const char* bytes, const uint32_t* offsets, const uint8_t* kinds, int32_t n);
+
+/* Molecules as CTfile V2000 molfiles, written on the device from the tables of mnx_graph_pack: the molecule that
+ * _convert_graph_to_smiles puts together with RDKit (MolNexTR/chemical.py:880-926: atoms by symbol class, bonds with their
+ * wedge classes), at the coordinates it hands to _verify_chirality (:935-939: x * ratio * 10, y * 10, y pointing up) and with
+ * the begin atom of a wedge moved to the chiral centre as :262-273 do. No SMILES (that needs RDKit's canonicaliser) and no
+ * abbreviation expansion. The format follows the CTfile specification; it is this library's own and not RDKit's writer byte
+ * for byte. A post-pass on a post-pass: it reads mols / atoms / bonds / text as mnx_graph_pack wrote them (device pointers,
+ * with the numbers of records / bytes those tables hold), changes none of them and touches no decode state.
+ *
+ * One atom, from the sym_len bytes of its symbol, in the reference's order of tests: one pair of enclosing '[' ']' is
+ * stripped; the inner text in the R-group table, or else in the abbreviation table, makes a pseudo-atom; else the WHOLE
+ * symbol is read as a SMILES atom — unbracketed B C N O P S F Cl Br I, b c n o p s, '*'; bracketed
+ * isotope? (element | b c n o p s se as | '*') ('@' | '@@')? ('H' digit?)? charge? (':' digits)?, element one of the 118
+ * symbols (longest match), charge a run of '+' or of '-' or one sign and a number, |charge| <= 15, isotope <= 999 —; what does
+ * not parse is a pseudo-atom too. The chirality mark is read and dropped (the reference clears the tag: stereo travels as
+ * wedges and coordinates).
+ *
+ * One molfile (every line ends with '\n'; no timestamp, so the bytes are deterministic):
+ *   header   an empty line, "  MolNexTR          2D", an empty line
+ *   counts   "%3d%3d  0  0  0  0  0  0  0  0999 V2000"
+ *   atom     "%10.4f%10.4f%10.4f %-3s 0  0  0  0  0%3d  0  0  0  0  0  0" (69 bytes), z = 0.0000. x and y in exact integer
+ *            arithmetic, in units of 1e-4: den = cfg.coord_bins - 1, bins clamped to 0..den,
+ *            ux = (2 * x_bin * Sx + den) / (2 * den), uy = (2 * (den - y_bin) * Sy + den) / (2 * den) (64-bit integer
+ *            division), printed as u / 10000 '.' u % 10000 (four digits). Symbol: the element, capitalised for aromatic
+ *            atoms; "R#" for an R-group named 'R' + a number 1..999; "R" for every other pseudo-atom and for '*'. A '*' that parses ('*', '[*]',
+ *            '[*+]') is an atom of the grammar whose symbol happens to be "R": it has no alias, keeps its charge and isotope
+ *            in M  CHG / M  ISO, and does NOT count as a pseudo-atom for flag bit 2. The %3d is
+ *            the valence field: for a parsed BRACKET atom without an aromatic bond H count + the sum of its bond orders
+ *            (classes 1, 5, 6 count 1, class 2 two, class 3 three), written as 15 when that is 0 and as 0 when it exceeds 14;
+ *            0 for every other atom. Known limit: a bracket atom on an aromatic bond ('[nH]') loses its hydrogen mark.
+ *   bond     "%3d%3d%3d%3d" (12 bytes), atoms 1-based: classes 1..4 are type 1..4 with stereo 0, classes 5 / 6 type 1 with
+ *            stereo 1 / 6 (any other class: type 8, stereo 0). When atom j's symbol is exactly one of [C@] [C@@] [C@H] [C@@H]
+ *            and `rev` is 5 or 6 the line reads j i with rev's type and stereo, otherwise i j with type's.
+ *   properties, in this order: "A  %3d" + a line with the inner symbol (at most 70 bytes, cut at a UTF-8 character boundary;
+ *            control bytes as '?') for every pseudo-atom from the tables or without a parse whose inner symbol is not empty;
+ *            "M  CHG", "M  ISO" (the isotopes of [13C] and the like), "M  RGP" (the numbers of the "R#" atoms), each as
+ *            "M  XXX%3d" + up to eight " %3d %3d" pairs per line, atoms ascending; "M  END".
+ *
+ *   struct mnx_molfile, 16 bytes  text0, len: the molecule's molfile is out[text0 .. text0 + len); flags bit 0: more than 999
+ *            atoms or bonds; bit 1: a record points beyond a table — atom0 + n_atoms, bond0 + n_bonds or text0 + smiles_len
+ *            beyond the sizes passed (a mnx_graph_pack output that was cut at a capacity, say), an atom's symbol beyond
+ *            n_text_bytes, a bond whose i or j is not an atom of the molecule —; either bit: no molfile, len = 0. Bit 2: the
+ *            molecule holds a pseudo-atom; bit 3: a copy of MNX_MOL_TRUNCATED.
+ * Inputs: mols [n], 1 <= n <= 65536; atoms [n_atom_records], bonds [n_bond_records] (8-byte aligned), text [n_text_bytes];
+ * scale device int32 [n,2] = {Sx, Sy} of every molecule in units of 1e-4, each 1..10 000 000, or NULL for Sx = Sy = 100000
+ * (the reference's factor 10 on a square page; Sx = round(100000 * width / height) gives its `ratio`). scale is device
+ * memory, which a host call cannot read without a synchronisation: a value outside the range is clamped by the kernel.
+ * mnx_set_symbol_tables must have been called.
+ * Outputs, device pointers the caller allocated: files [n]; out [out_cap] bytes (no terminators); totals uint32 [2] = {bytes
+ * needed, 1 if out_cap was too small}. Nothing is written beyond out_cap, and files and totals are complete all the same:
+ * read the needed size and call again. Deterministic byte for byte (every position comes from a prefix scan; no atomics).
+ * Three launches, asynchronous on `stream`, no allocation, no host synchronisation.
+ * MNX_ERR_INVALID_ARG (with mnx_last_error, "mnx_molfile_pack: ..."): a null pointer (a table of size 0 may be null), n
+ * outside 1..65536, misaligned records, or no symbol tables set; nothing is launched then. */
+typedef struct mnx_molfile {
+    uint32_t text0, len;
+    uint32_t flags;             /* MNX_MOLFILE_* */
+    uint32_t reserved;          /* 0 */
+} mnx_molfile;
+#define MNX_MOLFILE_TOO_LARGE 1u
+#define MNX_MOLFILE_BEYOND_TABLES 2u
+#define MNX_MOLFILE_PSEUDO_ATOM 4u
+#define MNX_MOLFILE_TRUNCATED 8u
+int mnx_molfile_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
+                     const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes,
+                     const int32_t* scale, mnx_molfile* files, char* out, uint32_t out_cap, uint32_t* totals, void* stream);
+
 /* mnx_predict with beam search (BASELINE config 5): the same inputs and outputs, every reference batch searched as
  * mnx_decode_beam does (n_best = 1: the best hypothesis; atom positions and the bond head run on ITS tokens and decoder
  * outputs) while the encoder of the following launch groups runs on the second stream. Up to MNX_BEAM_GROUPS (environment,

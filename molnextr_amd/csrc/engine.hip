@@ -105,6 +105,8 @@ struct mnx_engine {
     bool have_tc = false;
     VocabText* vt_dev = nullptr;        // names of the symbol ids (mnx_set_vocab_text), read by mnx_graph_pack
     bool have_vt = false;
+    SymbolTables* st_dev = nullptr;     // R-group and abbreviation names (mnx_set_symbol_tables), read by mnx_molfile_pack
+    bool have_st = false;
     int n_chunk_bufs = 0;
     bool use_graph = true;
     // greedy ticks of up to dec_fused_max rows run as three launches per layer (dec_fused.hip): dec_tile rows per workgroup in
@@ -630,6 +632,7 @@ int mnx_create(const mnx_config* cfg, const mnx_weight_desc* weights, int32_t n_
     }
     h->tc_dev = (TokenClasses*)P.dalloc(sizeof(TokenClasses));
     h->vt_dev = (VocabText*)P.dalloc(sizeof(VocabText));
+    h->st_dev = (SymbolTables*)P.dalloc(sizeof(SymbolTables));
     h->prep_bbox = (int*)P.dalloc(4 * sizeof(int));   // at create: mnx_preprocess may run beside another entry point
     h->prep_bbox_batch = (int*)P.dalloc((size_t)MNX_PREP_MAX_PAGES * 4 * sizeof(int));
     {
@@ -1324,6 +1327,56 @@ int mnx_graph_pack(mnx_engine* h, const int32_t* tokens, const int32_t* lengths,
     HIPCHK(h, graph_pack_enqueue(h->tc_dev, h->vt_dev, tokens, lengths, n, T, kmax, atom_idx, n_atoms, edges, atom_scores,
                                  edge_scores, overall_score, mols, atoms, atom_cap, bonds, bond_cap, text, text_cap, totals,
                                  (hipStream_t)stream));
+    return MNX_OK;
+}
+
+int mnx_set_symbol_tables(mnx_engine* h, const char* bytes, const uint32_t* offsets, const uint8_t* kinds, int32_t n) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    auto bad = [&](const std::string& m) { h->err = "mnx_set_symbol_tables: " + m; return MNX_ERR_INVALID_ARG; };
+    if (n < 0 || n > 512) return bad("n outside 0..512");
+    if (n > 0 && (!bytes || !offsets || !kinds)) return bad("null pointer");
+    if (n > 0 && offsets[0] != 0) return bad("offsets[0] must be 0");
+    auto st = std::make_unique<SymbolTables>();
+    memset(st.get(), 0, sizeof(SymbolTables));
+    st->n = n;
+    for (int i = 0; i < n; ++i) {
+        if (offsets[i + 1] <= offsets[i] || offsets[i + 1] - offsets[i] > 16)
+            return bad("name " + std::to_string(i) + " is empty or longer than 16 bytes, or its offsets decrease");
+        if (kinds[i] != 1 && kinds[i] != 2) return bad("kinds[" + std::to_string(i) + "] must be 1 (R-group) or 2 (abbreviation)");
+        st->len[i] = (unsigned char)(offsets[i + 1] - offsets[i]);
+        st->kind[i] = kinds[i];
+        memcpy(st->name[i], bytes + offsets[i], st->len[i]);
+        if (i > 0) {        // bytewise order, a prefix in front of the longer name: what the device's binary search assumes
+            const int m = std::min(st->len[i - 1], st->len[i]), c = memcmp(st->name[i - 1], st->name[i], (size_t)m);
+            if (c > 0 || (c == 0 && st->len[i - 1] >= st->len[i]))
+                return bad("names must be strictly ascending bytewise; name " + std::to_string(i) + " is not behind its predecessor");
+        }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemcpy(h->st_dev, st.get(), sizeof(SymbolTables), hipMemcpyHostToDevice));
+    h->have_st = true;
+    return MNX_OK;
+}
+
+int mnx_molfile_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
+                     const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes,
+                     const int32_t* scale, mnx_molfile* files, char* out, uint32_t out_cap, uint32_t* totals, void* stream) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    if (!mols || !files || !totals || (!atoms && n_atom_records) || (!bonds && n_bond_records) || (!text && n_text_bytes) ||
+        (!out && out_cap)) {
+        h->err = "mnx_molfile_pack: null pointer";
+        return MNX_ERR_INVALID_ARG;
+    }
+    if (n < 1 || n > 65536) { h->err = "mnx_molfile_pack: 1 <= n <= 65536 required"; return MNX_ERR_INVALID_ARG; }
+    if (((uintptr_t)mols | (uintptr_t)atoms | (uintptr_t)bonds) & 7 || (((uintptr_t)files | (uintptr_t)totals | (uintptr_t)scale) & 3)) {
+        h->err = "mnx_molfile_pack: mols, atoms and bonds must be 8-byte aligned, files, scale and totals 4-byte";
+        return MNX_ERR_INVALID_ARG;
+    }
+    if (!h->have_st) { h->err = "mnx_molfile_pack: call mnx_set_symbol_tables first"; return MNX_ERR_INVALID_ARG; }
+    if (h->cfg.coord_bins < 2) { h->err = "mnx_molfile_pack: cfg.coord_bins must be at least 2"; return MNX_ERR_INVALID_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, molfile_pack_enqueue(h->st_dev, mols, n, atoms, n_atom_records, bonds, n_bond_records, text, n_text_bytes, scale,
+                                   h->cfg.coord_bins, files, out, out_cap, totals, (hipStream_t)stream));
     return MNX_OK;
 }
 

@@ -11,6 +11,7 @@
 
 #include "../../include/molnextr_hip.h"
 #include "atom_walk.h"
+#include "block_scan.h"
 #include "dec_types.h"
 
 namespace mnx {
@@ -23,26 +24,6 @@ constexpr int GP_THREADS = 256;
 constexpr int GP_T = 512;            // ids of a row held in LDS (mnx_confidence's limit)
 constexpr int GP_ATOMS = 256;        // atoms a row of GP_T ids can hold (an atom takes at least 3 ids): LDS span tables
 constexpr int SCAN_THREADS = 1024;
-
-// Exclusive prefix sum of one value per thread over a workgroup of NT threads (Hillis-Steele in LDS, two buffers); *total
-// receives the sum. buf holds 2 * NT words. Ends with a barrier, so it may be called again at once.
-template <int NT>
-__device__ __forceinline__ unsigned block_scan_excl(unsigned v, unsigned* buf, unsigned* total) {
-    const int tid = threadIdx.x;
-    int cur = 0;
-    buf[tid] = v;
-    __syncthreads();
-    for (int d = 1; d < NT; d <<= 1) {
-        const unsigned x = buf[cur * NT + tid] + (tid >= d ? buf[cur * NT + tid - d] : 0u);
-        buf[(cur ^ 1) * NT + tid] = x;
-        cur ^= 1;
-        __syncthreads();
-    }
-    const unsigned incl = buf[cur * NT + tid];
-    *total = buf[cur * NT + NT - 1];
-    __syncthreads();
-    return incl - v;
-}
 
 // What count and fill both need of one row, held in LDS.
 struct RowLds {

@@ -1,0 +1,443 @@
+// molfile.hip — CTfile V2000 molfiles from the packed molecule tables of mnx_graph_pack (mnx_molfile_pack): the molecule
+// that _convert_graph_to_smiles (reference chemical.py:880-926) builds with RDKit — atoms by symbol class, bonds with their
+// wedges, the begin atom of a wedge moved to the chiral centre (chemical.py:262-273) — written as text on the device.
+//   count  one workgroup per molecule: symbol classes and the molfile's length -> files[b].len / flags
+//   scan   exclusive scan of the lengths over the molecules -> files[b].text0, totals
+//   fill   one workgroup per molecule: the bytes behind text0
+// Every line of a V2000 block has a fixed width (69-byte atom lines, 12-byte bond lines, property lines of 8 entries), so
+// every byte position follows from prefix scans: no atomics, the output is the same byte for byte on every run.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/molnextr_hip.h"
+#include "block_scan.h"
+#include "dec_types.h"
+
+namespace mnx {
+
+static_assert(sizeof(mnx_molfile) == 16, "record layout of molnextr_hip.h");
+
+namespace {
+
+constexpr int MF_THREADS = 256;
+constexpr int MF_MAX = 1024;             // atoms / bonds held in LDS: a molfile counts three digits (999)
+constexpr int MF_PER = MF_MAX / MF_THREADS;
+constexpr int MF_ALIAS = 70;             // bytes of an alias line
+constexpr int SCAN_THREADS = 1024;
+
+constexpr unsigned HEADER_BYTES = 25, COUNTS_BYTES = 40, ATOM_BYTES = 70, BOND_BYTES = 13, END_BYTES = 7;
+constexpr unsigned PROP_HEAD = 9, PROP_ENTRY = 8, PROP_PER_LINE = 8, PROP_LINE = PROP_HEAD + PROP_PER_LINE * PROP_ENTRY + 1;
+
+// ---- one atom's interpretation, packed into a word of LDS ----
+//   bits 0-1 class: 0 atom of the SMILES grammar, 1 pseudo-atom 'R', 2 numbered R-group 'R#'
+//   bit 2 bracket atom, bit 3 one of the four chiral carbon symbols, bits 4-7 H count, bits 8-12 charge + 15,
+//   bits 13-22 isotope (class 0) or R-group number (class 2), bits 23-29 alias bytes, bit 30 alias starts behind a '['
+constexpr unsigned CLS_ATOM = 0, CLS_PSEUDO = 1, CLS_RNUM = 2;
+__device__ __forceinline__ unsigned info_cls(unsigned w) { return w & 3u; }
+__device__ __forceinline__ int info_h(unsigned w) { return (int)(w >> 4 & 15u); }
+__device__ __forceinline__ int info_charge(unsigned w) { return (int)(w >> 8 & 31u) - 15; }
+__device__ __forceinline__ unsigned info_num(unsigned w) { return w >> 13 & 1023u; }
+__device__ __forceinline__ unsigned info_alias(unsigned w) { return w >> 23 & 127u; }
+
+// the 118 element symbols, two bytes each (a one-letter symbol is followed by a blank)
+__device__ const char ELEMENTS[] =
+    "H HeLiBeB C N O F NeNaMgAlSiP S ClArK CaScTiV CrMnFeCoNiCuZnGaGeAsSeBrKrRbSrY ZrNbMoTcRuRhPdAgCdInSnSbTeI XeCsBaLaCePrNdPm"
+    "SmEuGdTbDyHoErTmYbLuHfTaW ReOsIrPtAuHgTlPbBiPoAtRnFrRaAcThPaU NpPuAmCmBkCfEsFmMdNoLrRfDbSgBhHsMtDsRgCnNhFlMcLvTsOg";
+static_assert(sizeof(ELEMENTS) == 2 * 118 + 1, "118 elements");
+
+__device__ __forceinline__ bool is_element(unsigned char a, unsigned char b) {
+    for (int i = 0; i < 118; ++i)
+        if (ELEMENTS[2 * i] == (char)a && ELEMENTS[2 * i + 1] == (char)b) return true;
+    return false;
+}
+__device__ __forceinline__ bool is_digit(unsigned char c) { return c >= '0' && c <= '9'; }
+__device__ __forceinline__ bool is_organic_aromatic(unsigned char c) {
+    return c == 'b' || c == 'c' || c == 'n' || c == 'o' || c == 'p' || c == 's';
+}
+
+// index of the n bytes at s in the sorted name table, -1 when absent (binary search, bytewise order)
+__device__ __forceinline__ int table_find(const SymbolTables* __restrict__ st, const unsigned char* s, int n) {
+    if (n < 1 || n > 16) return -1;
+    int lo = 0, hi = st->n - 1;
+    while (lo <= hi) {
+        const int mid = (lo + hi) >> 1, ml = st->len[mid];
+        int c = 0;
+        for (int k = 0; k < min(n, ml) && c == 0; ++k) c = (int)s[k] - (int)st->name[mid][k];
+        if (c == 0) c = n - ml;
+        if (c == 0) return mid;
+        if (c < 0) hi = mid - 1; else lo = mid + 1;
+    }
+    return -1;
+}
+
+// The whole symbol as a SMILES atom (what Chem.AtomFromSmiles takes of the vocabulary's atoms, chemical.py:898): sets the
+// element's two bytes (capitalised; 'R' for '*'), H count, charge, isotope; false = no parse.
+__device__ __forceinline__ bool parse_smiles_atom(const unsigned char* s, int n, unsigned char* e0, unsigned char* e1, int* hcount,
+                                                  int* charge, int* isotope) {
+    *e1 = ' '; *hcount = 0; *charge = 0; *isotope = 0;
+    if (n < 1) return false;
+    if (s[0] != '[') {
+        const unsigned char c = s[0];
+        if (n == 1) {
+            if (c == 'B' || c == 'C' || c == 'N' || c == 'O' || c == 'P' || c == 'S' || c == 'F' || c == 'I') { *e0 = c; return true; }
+            if (is_organic_aromatic(c)) { *e0 = c - 32; return true; }
+            if (c == '*') { *e0 = 'R'; return true; }
+            return false;
+        }
+        if (n == 2 && ((c == 'C' && s[1] == 'l') || (c == 'B' && s[1] == 'r'))) { *e0 = c; *e1 = s[1]; return true; }
+        return false;
+    }
+    if (n < 3 || s[n - 1] != ']') return false;
+    const int e = n - 1;
+    int p = 1, iso = 0;
+    while (p < e && is_digit(s[p])) {
+        iso = iso * 10 + (s[p] - '0');
+        if (iso > 999) return false;
+        ++p;
+    }
+    if (p >= e) return false;
+    const unsigned char c = s[p], d = p + 1 < e ? s[p + 1] : 0;
+    if (c == '*') { *e0 = 'R'; ++p; }
+    else if ((c == 's' && d == 'e') || (c == 'a' && d == 's')) { *e0 = c - 32; *e1 = d; p += 2; }
+    else if (is_organic_aromatic(c)) { *e0 = c - 32; ++p; }
+    else if (c >= 'A' && c <= 'Z') {
+        if (d >= 'a' && d <= 'z' && is_element(c, d)) { *e0 = c; *e1 = d; p += 2; }      // the longest match wins
+        else if (is_element(c, ' ')) { *e0 = c; ++p; }
+        else return false;
+    } else return false;
+    if (p < e && s[p] == '@') { ++p; if (p < e && s[p] == '@') ++p; }       // read and dropped: stereo travels as wedges
+    if (p < e && s[p] == 'H') {
+        ++p; *hcount = 1;
+        if (p < e && is_digit(s[p])) { *hcount = s[p] - '0'; ++p; }
+    }
+    if (p < e && (s[p] == '+' || s[p] == '-')) {
+        const unsigned char sign = s[p];
+        int k = 0, v;
+        while (p < e && s[p] == sign) { ++k; ++p; }
+        if (k == 1 && p < e && is_digit(s[p])) {
+            v = 0;
+            while (p < e && is_digit(s[p])) {
+                v = v * 10 + (s[p] - '0');
+                if (v > 15) return false;
+                ++p;
+            }
+        } else v = k;
+        if (v > 15) return false;
+        *charge = sign == '+' ? v : -v;
+    }
+    if (p < e && s[p] == ':') {
+        ++p;
+        if (p >= e || !is_digit(s[p])) return false;
+        while (p < e && is_digit(s[p])) ++p;
+    }
+    *isotope = iso;
+    return p == e;
+}
+
+__device__ __forceinline__ bool bytes_are(const unsigned char* s, int n, const char* lit, int ln) {
+    if (n != ln) return false;
+    for (int k = 0; k < n; ++k)
+        if (s[k] != (unsigned char)lit[k]) return false;
+    return true;
+}
+
+// One atom: the order of tests of chemical.py:886-903 — brackets stripped, R-group table, abbreviation table, and only then
+// the whole symbol as a SMILES atom; no parse = pseudo-atom. *sym receives the three bytes of the symbol column.
+__device__ __forceinline__ unsigned interpret_atom(const SymbolTables* __restrict__ st, const unsigned char* s, int n, unsigned* sym) {
+    const bool strip = n >= 2 && s[0] == '[' && s[n - 1] == ']';
+    const unsigned char* in = strip ? s + 1 : s;
+    const int ni = strip ? n - 2 : n;
+    const bool chiral = bytes_are(s, n, "[C@]", 4) || bytes_are(s, n, "[C@@]", 5) || bytes_are(s, n, "[C@H]", 5) ||
+                        bytes_are(s, n, "[C@@H]", 6);
+    unsigned w = chiral ? 8u : 0u;
+    const int hit = table_find(st, in, ni);
+    unsigned char e0 = 'R', e1 = ' ';
+    int h = 0, q = 0, iso = 0;
+    if (hit < 0 && parse_smiles_atom(s, n, &e0, &e1, &h, &q, &iso)) {
+        w |= CLS_ATOM | (s[0] == '[' ? 4u : 0u) | (unsigned)h << 4 | (unsigned)(q + 15) << 8 | (unsigned)iso << 13;
+        *sym = e0 | (unsigned)e1 << 8 | (unsigned)' ' << 16;
+        return w;
+    }
+    unsigned num = 0;           // 'R' followed by digits carries its number (1..999), R-group table only
+    if (hit >= 0 && st->kind[hit] == 1 && ni >= 2 && in[0] == 'R') {
+        bool digits = true;
+        for (int k = 1; k < ni && digits; ++k) {
+            digits = is_digit(in[k]);
+            if (digits) num = min(num * 10 + (in[k] - '0'), 1000u);
+        }
+        if (!digits || num > 999) num = 0;
+    }
+    int al = min(ni, MF_ALIAS);
+    if (ni > MF_ALIAS)          // never cut a UTF-8 character in two
+        while (al > 0 && (in[al] & 0xC0) == 0x80) --al;
+    w |= (num ? CLS_RNUM : CLS_PSEUDO) | (unsigned)(15) << 8 | num << 13 | (unsigned)al << 23 | (strip ? 1u << 30 : 0u);
+    *sym = 'R' | (unsigned)(num ? '#' : ' ') << 8 | (unsigned)' ' << 16;
+    return w;
+}
+
+// k-th byte of "%3d" of v, -99 <= v <= 999
+__device__ __forceinline__ char d3(int v, int k) {
+    const int a = v < 0 ? -v : v;
+    if (k == 2) return (char)('0' + a % 10);
+    if (k == 1) return a >= 10 ? (char)('0' + a / 10 % 10) : (v < 0 ? '-' : ' ');
+    return a >= 100 ? (char)('0' + a / 100) : (v < 0 && a >= 10 ? '-' : ' ');
+}
+
+__device__ __forceinline__ unsigned prop_bytes(unsigned k) {     // a property section of k entries: lines of up to 8
+    return (k + PROP_PER_LINE - 1) / PROP_PER_LINE * (PROP_HEAD + 1) + k * PROP_ENTRY;
+}
+
+// header block and counts line; the six leading bytes of the counts line are the atom and bond counts
+__device__ const char MF_HEAD[] = "\n  MolNexTR          2D\n\n" "aaabbb  0  0  0  0  0  0  0  0999 V2000\n";
+static_assert(sizeof(MF_HEAD) == HEADER_BYTES + COUNTS_BYTES + 1, "header and counts line");
+
+template <bool FILL>
+__global__ __launch_bounds__(MF_THREADS) void molfile_kernel(
+        const mnx_mol* __restrict__ mols, const mnx_atom* __restrict__ atoms, unsigned n_atom_records,
+        const mnx_bond* __restrict__ bonds, unsigned n_bond_records, const unsigned char* __restrict__ text,
+        unsigned n_text_bytes, const SymbolTables* __restrict__ st, const int* __restrict__ scale, int den,
+        mnx_molfile* __restrict__ files, char* __restrict__ out, unsigned out_cap) {
+    __shared__ unsigned info[MF_MAX], sym[MF_MAX];
+    __shared__ unsigned aoff[MF_MAX], coff[MF_MAX];     // per atom: bytes of the alias lines / packed entry counts in front of it
+    __shared__ unsigned bnd[FILL ? MF_MAX : 1];         // fill: i | j << 10 | order << 20 | aromatic << 22, for the valence sums
+    __shared__ unsigned scan[2 * MF_THREADS];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const mnx_mol m = mols[b];
+    unsigned text0 = 0;
+    if (FILL) {
+        const mnx_molfile f = files[b];
+        if (f.len == 0) return;                         // refused by count (the same for every thread)
+        text0 = f.text0;
+    } else {
+        unsigned flags = (m.flags & MNX_MOL_TRUNCATED) ? 8u : 0u;
+        if (m.n_atoms > 999u || m.n_bonds > 999u) flags |= 1u;
+        if ((unsigned long long)m.atom0 + m.n_atoms > n_atom_records || (unsigned long long)m.bond0 + m.n_bonds > n_bond_records ||
+            (unsigned long long)m.text0 + m.smiles_len > n_text_bytes)
+            flags |= 2u;
+        if (flags & 3u) {
+            if (tid == 0) { files[b].len = 0; files[b].flags = flags; files[b].reserved = 0; }
+            return;
+        }
+    }
+    const int na = (int)m.n_atoms, nb = (int)m.n_bonds;
+    const mnx_atom* A = atoms + m.atom0;
+    const mnx_bond* B = bonds + m.bond0;
+
+    // ---- every atom's interpretation; a record that points beyond its table refuses the molecule ----
+    int bad = 0;
+    for (int a = tid; a < MF_MAX; a += MF_THREADS) {
+        unsigned w = 0, s3 = 0;
+        if (a < na) {
+            const unsigned s0 = A[a].sym0, sl = A[a].sym_len;
+            if ((unsigned long long)m.text0 + s0 + sl > n_text_bytes) bad = 1;
+            else w = interpret_atom(st, text + m.text0 + s0, (int)sl, &s3);
+        }
+        info[a] = w;
+        sym[a] = s3;
+    }
+    for (int k = tid; k < nb; k += MF_THREADS) {
+        const unsigned i = B[k].i, j = B[k].j, ty = B[k].type;
+        if (i >= (unsigned)na || j >= (unsigned)na) bad = 1;
+        if (FILL) bnd[k] = (i & 1023u) | (j & 1023u) << 10 | (ty <= 3 ? ty : (ty == 5 || ty == 6) ? 1u : 0u) << 20 | (ty == 4 ? 1u : 0u) << 22;
+    }
+    if (!FILL) {
+        if (__syncthreads_or(bad)) {
+            if (tid == 0) { files[b].len = 0; files[b].flags = ((m.flags & MNX_MOL_TRUNCATED) ? 8u : 0u) | 2u; files[b].reserved = 0; }
+            return;
+        }
+    } else {
+        __syncthreads();
+    }
+
+    // ---- positions: MF_PER neighbouring atoms per thread, two scans (alias bytes; CHG | ISO | RGP entries, 10 bits each) ----
+    unsigned va[MF_PER], vc[MF_PER], sa = 0, sc = 0;
+    int pseudo = 0;
+#pragma unroll
+    for (int q = 0; q < MF_PER; ++q) {
+        const unsigned w = info[MF_PER * tid + q];
+        const bool is_atom = MF_PER * tid + q < na;
+        const unsigned cls = info_cls(w), al = info_alias(w);
+        va[q] = al ? al + 8u : 0u;                       // "A  nnn\n" + the text + "\n"
+        vc[q] = !is_atom ? 0u
+                         : (info_charge(w) != 0 ? 1u : 0u) | (cls == CLS_ATOM && info_num(w) ? 1u << 10 : 0u) |
+                               (cls == CLS_RNUM ? 1u << 20 : 0u);
+        pseudo |= is_atom && cls != CLS_ATOM;
+        sa += va[q];
+        sc += vc[q];
+    }
+    unsigned alias_total, cnt_total;
+    unsigned ea = block_scan_excl<MF_THREADS>(sa, scan, &alias_total);
+    unsigned ec = block_scan_excl<MF_THREADS>(sc, scan, &cnt_total);
+    const unsigned n_chg = cnt_total & 1023u, n_iso = cnt_total >> 10 & 1023u, n_rgp = cnt_total >> 20 & 1023u;
+    const unsigned off_atoms = HEADER_BYTES + COUNTS_BYTES, off_bonds = off_atoms + ATOM_BYTES * na;
+    const unsigned off_alias = off_bonds + BOND_BYTES * nb, off_chg = off_alias + alias_total;
+    const unsigned off_iso = off_chg + prop_bytes(n_chg), off_rgp = off_iso + prop_bytes(n_iso);
+    const unsigned off_end = off_rgp + prop_bytes(n_rgp);
+    if (!FILL) {
+        pseudo = __syncthreads_or(pseudo);
+        if (tid == 0) {
+            files[b].len = off_end + END_BYTES;
+            files[b].flags = ((m.flags & MNX_MOL_TRUNCATED) ? 8u : 0u) | (pseudo ? 4u : 0u);
+            files[b].reserved = 0;
+        }
+        return;
+    }
+#pragma unroll
+    for (int q = 0; q < MF_PER; ++q) {
+        aoff[MF_PER * tid + q] = ea;
+        coff[MF_PER * tid + q] = ec;
+        ea += va[q];
+        ec += vc[q];
+    }
+    __syncthreads();
+
+    auto put = [&](unsigned off, char c) {               // nothing is written beyond out_cap
+        const unsigned long long at = (unsigned long long)text0 + off;
+        if (at < out_cap) out[at] = c;
+    };
+
+    // ---- header and counts line ----
+    if (tid < (int)(HEADER_BYTES + COUNTS_BYTES)) {
+        char c = MF_HEAD[tid];
+        const int k = tid - (int)HEADER_BYTES;
+        if (k >= 0 && k < 3) c = d3(na, k);
+        else if (k >= 3 && k < 6) c = d3(nb, k - 3);
+        put(tid, c);
+    }
+
+    // ---- atom lines: coordinates in exact integer arithmetic, units of 1e-4 ----
+    long long sx = 100000, sy = 100000;
+    if (scale) {
+        sx = min(max(scale[2 * b], 1), 10000000);
+        sy = min(max(scale[2 * b + 1], 1), 10000000);
+    }
+    for (int a = tid; a < na; a += MF_THREADS) {
+        const unsigned w = info[a], s3 = sym[a], o = off_atoms + ATOM_BYTES * a;
+        const long long xb = min((int)A[a].x_bin, den), yb = min((int)A[a].y_bin, den);
+        const unsigned u[3] = {(unsigned)((2 * xb * sx + den) / (2 * den)), (unsigned)((2 * (den - yb) * sy + den) / (2 * den)), 0u};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const unsigned ip = u[c] / 10000u, fp = u[c] % 10000u, oc = o + 10 * c;
+            put(oc, ' ');
+            put(oc + 1, ip >= 1000 ? (char)('0' + ip / 1000) : ' ');
+            put(oc + 2, ip >= 100 ? (char)('0' + ip / 100 % 10) : ' ');
+            put(oc + 3, ip >= 10 ? (char)('0' + ip / 10 % 10) : ' ');
+            put(oc + 4, (char)('0' + ip % 10));
+            put(oc + 5, '.');
+            put(oc + 6, (char)('0' + fp / 1000));
+            put(oc + 7, (char)('0' + fp / 100 % 10));
+            put(oc + 8, (char)('0' + fp / 10 % 10));
+            put(oc + 9, (char)('0' + fp % 10));
+        }
+        put(o + 30, ' ');
+        put(o + 31, (char)(s3 & 255u));
+        put(o + 32, (char)(s3 >> 8 & 255u));
+        put(o + 33, (char)(s3 >> 16 & 255u));
+        int val = 0;            // the valence field: bracket atoms of the grammar without an aromatic bond
+        if (info_cls(w) == CLS_ATOM && (w & 4u)) {
+            int sum = info_h(w);
+            bool arom = false;
+            for (int k = 0; k < nb; ++k) {
+                const unsigned e = bnd[k];
+                if ((e & 1023u) == (unsigned)a || (e >> 10 & 1023u) == (unsigned)a) { sum += (int)(e >> 20 & 3u); arom |= (e >> 22 & 1u) != 0; }
+            }
+            val = arom ? 0 : sum == 0 ? 15 : sum > 14 ? 0 : sum;
+        }
+        for (int p = 0; p < 35; ++p) {                   // " 0" and eleven "  0" fields, the sixth of them the valence
+            char c = p < 2 ? (p == 1 ? '0' : ' ') : ((p - 2) % 3 == 2 ? '0' : ' ');
+            if (p >= 14 && p < 17) c = d3(val, p - 14);
+            put(o + 34 + p, c);
+        }
+        put(o + 69, '\n');
+    }
+
+    // ---- bond lines: a wedge begins at a chiral carbon of the higher index when the reverse direction is a wedge ----
+    for (int k = tid; k < nb; k += MF_THREADS) {
+        const unsigned i = B[k].i, j = B[k].j, ty = B[k].type, rv = B[k].rev, o = off_bonds + BOND_BYTES * k;
+        const bool swap = (info[j & (MF_MAX - 1)] & 8u) && (rv == 5 || rv == 6);      // j < n_atoms: count checked it
+        const unsigned cls = swap ? rv : ty;
+        const int a1 = (int)(swap ? j : i) + 1, a2 = (int)(swap ? i : j) + 1;
+        const int bt = cls >= 1 && cls <= 4 ? (int)cls : (cls == 5 || cls == 6) ? 1 : 8, stereo = cls == 5 ? 1 : cls == 6 ? 6 : 0;
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            put(o + p, d3(a1, p));
+            put(o + 3 + p, d3(a2, p));
+            put(o + 6 + p, d3(bt, p));
+            put(o + 9 + p, d3(stereo, p));
+        }
+        put(o + 12, '\n');
+    }
+
+    // ---- property lines: aliases, then M  CHG, M  ISO, M  RGP in lines of up to eight entries ----
+    for (int a = tid; a < na; a += MF_THREADS) {
+        const unsigned w = info[a], al = info_alias(w);
+        if (al) {
+            const unsigned o = off_alias + aoff[a];
+            const unsigned char* in = text + m.text0 + A[a].sym0 + (w >> 30 & 1u);
+            put(o, 'A'); put(o + 1, ' '); put(o + 2, ' ');
+            for (int p = 0; p < 3; ++p) put(o + 3 + p, d3(a + 1, p));
+            put(o + 6, '\n');
+            for (unsigned k = 0; k < al; ++k) put(o + 7 + k, in[k] < 0x20 || in[k] == 0x7f ? '?' : (char)in[k]);
+            put(o + 7 + al, '\n');
+        }
+        const unsigned cls = info_cls(w);
+        const bool has[3] = {info_charge(w) != 0, cls == CLS_ATOM && info_num(w) != 0, cls == CLS_RNUM};
+        const int value[3] = {info_charge(w), (int)info_num(w), (int)info_num(w)};
+        const unsigned base[3] = {off_chg, off_iso, off_rgp}, total[3] = {n_chg, n_iso, n_rgp};
+        const char* tag = "CHGISORGP";
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            if (!has[q]) continue;
+            const unsigned e = coff[a] >> (10 * q) & 1023u, line = e / PROP_PER_LINE, pos = e % PROP_PER_LINE;
+            const unsigned o = base[q] + line * PROP_LINE;
+            if (pos == 0) {
+                const unsigned cnt = min(PROP_PER_LINE, total[q] - line * PROP_PER_LINE);
+                put(o, 'M'); put(o + 1, ' '); put(o + 2, ' ');
+                for (int p = 0; p < 3; ++p) { put(o + 3 + p, tag[3 * q + p]); put(o + 6 + p, d3((int)cnt, p)); }
+                put(o + PROP_HEAD + cnt * PROP_ENTRY, '\n');
+            }
+            const unsigned oe = o + PROP_HEAD + pos * PROP_ENTRY;
+            put(oe, ' ');
+            put(oe + 4, ' ');
+            for (int p = 0; p < 3; ++p) { put(oe + 1 + p, d3(a + 1, p)); put(oe + 5 + p, d3(value[q], p)); }
+        }
+    }
+    if (tid < (int)END_BYTES) put(off_end + tid, "M  END\n"[tid]);
+}
+
+// text0 of every molecule: an exclusive scan of the lengths in tiles of SCAN_THREADS with a running 64-bit carry, by ONE
+// workgroup (graph_pack.hip's scan over the images, on one column); a total beyond 2^32 - 1 saturates and sets totals[1].
+__global__ __launch_bounds__(SCAN_THREADS) void molfile_scan_kernel(mnx_molfile* __restrict__ files, int n, unsigned out_cap,
+                                                                    unsigned* __restrict__ totals) {
+    __shared__ unsigned scan[2 * SCAN_THREADS];
+    const int tid = threadIdx.x;
+    unsigned long long carry = 0;
+    for (int base = 0; base < n; base += SCAN_THREADS) {
+        const int b = base + tid;
+        unsigned t;
+        const unsigned e = block_scan_excl<SCAN_THREADS>(b < n ? files[b].len : 0u, scan, &t);
+        if (b < n) files[b].text0 = (unsigned)min(carry + e, 0xffffffffull);
+        carry += t;
+    }
+    if (tid == 0) {
+        totals[0] = (unsigned)min(carry, 0xffffffffull);
+        totals[1] = carry > out_cap ? 1u : 0u;
+    }
+}
+
+}  // namespace
+
+hipError_t molfile_pack_enqueue(const SymbolTables* st_dev, const mnx_mol* mols, int n, const mnx_atom* atoms,
+                                unsigned n_atom_records, const mnx_bond* bonds, unsigned n_bond_records, const char* text,
+                                unsigned n_text_bytes, const int* scale, int coord_bins, mnx_molfile* files, char* out,
+                                unsigned out_cap, unsigned* totals, hipStream_t s) {
+    const int den = coord_bins - 1;
+    hipLaunchKernelGGL(molfile_kernel<false>, dim3(n), dim3(MF_THREADS), 0, s, mols, atoms, n_atom_records, bonds,
+                       n_bond_records, (const unsigned char*)text, n_text_bytes, st_dev, scale, den, files, out, out_cap);
+    hipLaunchKernelGGL(molfile_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, files, n, out_cap, totals);
+    hipLaunchKernelGGL(molfile_kernel<true>, dim3(n), dim3(MF_THREADS), 0, s, mols, atoms, n_atom_records, bonds,
+                       n_bond_records, (const unsigned char*)text, n_text_bytes, st_dev, scale, den, files, out, out_cap);
+    return hipGetLastError();
+}
+
+}  // namespace mnx

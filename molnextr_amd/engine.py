@@ -26,7 +26,8 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
            "mnx_gemm16_split", "mnx_decode_forced", "mnx_gemm_clock", "mnx_probe_mfma", "mnx_set_op_terms",
            "mnx_predict_confidence", "mnx_confidence", "mnx_window_attn", "mnx_kv_block", "mnx_preprocess_batch",
            "mnx_encode_gray8", "mnx_predict_gray8", "mnx_decode_guided", "mnx_predict_guided", "mnx_patch_embed",
-           "mnx_layernorm16", "mnx_merge_ln16", "mnx_cast16", "mnx_sgemm_tn", "mnx_set_vocab_text", "mnx_graph_pack")
+           "mnx_layernorm16", "mnx_merge_ln16", "mnx_cast16", "mnx_sgemm_tn", "mnx_set_vocab_text", "mnx_graph_pack",
+           "mnx_set_symbol_tables", "mnx_molfile_pack")
 
 # Encoder operand modes (include/molnextr_hip.h MNX_DTYPE_*). "fp16x3" — split fp16 operands, three MFMA terms per
 # product, fp32-class results — is the default: it is the fastest mode whose results stay a factor of four inside north_star's
@@ -94,6 +95,11 @@ class MnxBond(C.Structure):
     _fields_ = [("i", C.c_uint16), ("j", C.c_uint16), ("type", C.c_uint8), ("rev", C.c_uint8), ("score", C.c_double)]
 
 
+class MnxMolfile(C.Structure):
+    """include/molnextr_hip.h mnx_molfile: one molecule of mnx_molfile_pack (16 bytes)."""
+    _fields_ = [("text0", C.c_uint32), ("len", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # the same three records as numpy structured dtypes (C layout: align=True), what Engine.graph_pack returns
 MOL_DTYPE = np.dtype([("atom0", "<u4"), ("n_atoms", "<u4"), ("bond0", "<u4"), ("n_bonds", "<u4"), ("text0", "<u4"),
                       ("smiles_len", "<u4"), ("flags", "<u4"), ("reserved", "<u4"), ("overall_score", "<f8")], align=True)
@@ -101,6 +107,10 @@ ATOM_DTYPE = np.dtype([("sym0", "<u4"), ("sym_len", "<u2"), ("index", "<u2"), ("
                        ("score", "<f8")], align=True)
 BOND_DTYPE = np.dtype([("i", "<u2"), ("j", "<u2"), ("type", "u1"), ("rev", "u1"), ("score", "<f8")], align=True)
 MOL_TRUNCATED = 1                       # mnx_mol.flags bit 0: more atoms than kmax, the tables hold the first kmax
+MOLFILE_DTYPE = np.dtype([("text0", "<u4"), ("len", "<u4"), ("flags", "<u4"), ("reserved", "<u4")], align=True)
+# mnx_molfile.flags (MNX_MOLFILE_*): no molfile (len 0) for more than 999 atoms / bonds or records beyond the tables passed;
+# the molecule holds a pseudo-atom (R-group, abbreviation, unparsable symbol); a copy of MOL_TRUNCATED
+MOLFILE_TOO_LARGE, MOLFILE_BEYOND_TABLES, MOLFILE_PSEUDO_ATOM, MOLFILE_TRUNCATED = 1, 2, 4, 8
 
 
 def vocab_text(tok):
@@ -109,6 +119,22 @@ def vocab_text(tok):
     offsets = np.zeros(len(names) + 1, dtype=np.uint32)
     offsets[1:] = np.cumsum([len(b) for b in names])
     return b"".join(names), offsets, len(names)
+
+
+def symbol_tables():
+    """mnx_set_symbol_tables arguments from vocab/abbreviations.json (chem.RGROUP_SYMBOLS / ABBREVIATIONS): (bytes, uint32
+    offsets [n + 1], uint8 kinds [n], n) — the UTF-8 names sorted bytewise, kind 1 R-group, 2 abbreviation. A name in both
+    tables is an R-group: the reference tests that table first (chemical.py:888-895)."""
+    from .chem import ABBREVIATIONS, RGROUP_SYMBOLS
+    kind = {s.encode("utf-8"): 2 for s in ABBREVIATIONS}
+    kind.update({s.encode("utf-8"): 1 for s in RGROUP_SYMBOLS})
+    names = sorted(kind)
+    long = [b for b in names if not 1 <= len(b) <= 16]
+    if long or len(names) > 512:
+        raise ValueError(f"symbol tables: {len(names)} names (at most 512), outside 1..16 bytes: {long}")
+    offsets = np.zeros(len(names) + 1, dtype=np.uint32)
+    offsets[1:] = np.cumsum([len(b) for b in names])
+    return b"".join(names), offsets, np.array([kind[b] for b in names], dtype=np.uint8), len(names)
 
 
 PREP_MAX_PAGES = 4096                   # include/molnextr_hip.h MNX_PREP_MAX_PAGES: pages per mnx_preprocess_batch call
@@ -207,6 +233,10 @@ def load_library():
     lib.mnx_graph_pack.restype = C.c_int
     lib.mnx_graph_pack.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp,
                                    C.c_uint32, vp, vp]
+    lib.mnx_set_symbol_tables.restype = C.c_int
+    lib.mnx_set_symbol_tables.argtypes = [vp, C.c_char_p, vp, vp, i32]
+    lib.mnx_molfile_pack.restype = C.c_int
+    lib.mnx_molfile_pack.argtypes = [vp, vp, i32, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp]
     lib.mnx_atom_scan.restype = C.c_int
     lib.mnx_atom_scan.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.mnx_preprocess.restype = C.c_int
@@ -331,6 +361,7 @@ class Engine:
         self.h = handle
         self._set_token_classes()
         self._set_vocab_text()
+        self._set_symbol_tables()
         self.n_feat = enc.num_features
         g = enc.img_size // enc.patch >> (len(enc.depths) - 1)
         self.n_mem = g * g
@@ -359,6 +390,12 @@ class Engine:
         from .tokenizer import CharTokenizer
         text, offsets, n = vocab_text(CharTokenizer(64))
         self._check(self.lib.mnx_set_vocab_text(self.h, text, offsets.ctypes.data, n), "mnx_set_vocab_text")
+
+    def _set_symbol_tables(self):
+        """Hands the R-group and abbreviation names to the library: what molfile_pack tests an atom's symbol against."""
+        text, offsets, kinds, n = symbol_tables()
+        self._check(self.lib.mnx_set_symbol_tables(self.h, text, offsets.ctypes.data, kinds.ctypes.data, n),
+                    "mnx_set_symbol_tables")
 
     def close(self):
         if getattr(self, "h", None):
@@ -750,12 +787,13 @@ class Engine:
     # SMILES of well under 200 bytes); `totals` sizes the one repeat when a job needs more
     PACK_GUESS = (48, 56, 192)
 
-    def graph_pack(self, out: dict, caps=None) -> dict:
+    def graph_pack(self, out: dict, caps=None, keep_device: bool = False) -> dict:
         """predict's result dict (device tensors) -> the molecules as numpy structured arrays (mnx_graph_pack): {'mols'
         [n] MOL_DTYPE, 'atoms' ATOM_DTYPE, 'bonds' BOND_DTYPE, 'text' bytes, 'totals' uint32 [4]}. With 'atom_scores',
         'edge_scores' and 'overall_score' in `out` the records carry the confidences, otherwise zeros. One D2H copy per table
         (plus the 16 bytes of totals); starts from PACK_GUESS per image (or caps = (atom_cap, bond_cap, text_cap)) and
-        repeats at most once with the sizes `totals` reports."""
+        repeats at most once with the sizes `totals` reports. keep_device: also 'device' = the four tables as the uint8 device
+        tensors they were written to, for molfile_pack."""
         tokens, lengths = out["tokens"], out["lengths"]
         n, T = tokens.shape
         kmax = out["atom_idx"].shape[1]
@@ -780,10 +818,50 @@ class Engine:
                 raise MnxError(f"mnx_graph_pack: capacities {caps} too small after sizing them from totals {tot.tolist()}")
             caps = (int(tot[0]), int(tot[1]), int(tot[2]))
         na, nb, nt = int(tot[0]), int(tot[1]), int(tot[2])
-        return {"mols": mols.cpu().numpy().view(MOL_DTYPE),
-                "atoms": atoms[:na * ATOM_DTYPE.itemsize].cpu().numpy().view(ATOM_DTYPE),
-                "bonds": bonds[:nb * BOND_DTYPE.itemsize].cpu().numpy().view(BOND_DTYPE),
-                "text": text[:nt].cpu().numpy().tobytes(), "totals": tot.copy()}
+        rec = {"mols": mols.cpu().numpy().view(MOL_DTYPE),
+               "atoms": atoms[:na * ATOM_DTYPE.itemsize].cpu().numpy().view(ATOM_DTYPE),
+               "bonds": bonds[:nb * BOND_DTYPE.itemsize].cpu().numpy().view(BOND_DTYPE),
+               "text": text[:nt].cpu().numpy().tobytes(), "totals": tot.copy()}
+        if keep_device:
+            rec["device"] = (mols, atoms, bonds, text)
+        return rec
+
+    MOLFILE_GUESS = 4096      # first capacity of molfile_pack per molecule (30 atoms and 30 bonds take about 2.6 KB)
+
+    def molfile_pack(self, rec: dict, scale=None, cap: Optional[int] = None):
+        """graph_pack's records -> (files [n] MOLFILE_DTYPE, bytes): the V2000 molfile of molecule b is
+        bytes[files[b]['text0'] : +files[b]['len']] (mnx_molfile_pack; len 0 and a flag for a molecule that gets none).
+        scale: int [n, 2] = (Sx, Sy) per molecule in units of 1e-4, None = 100000 each (include/molnextr_hip.h). The records
+        go back to the device as they are (or stay there: graph_pack(keep_device=True)); starts from MOLFILE_GUESS bytes per
+        molecule (or cap) and repeats at most once with the size `totals` reports."""
+        dev = torch.device("cuda", self.device)
+
+        def up(a):
+            raw = a if isinstance(a, (bytes, bytearray)) else np.ascontiguousarray(a).tobytes()
+            return torch.frombuffer(bytearray(raw) or bytearray(8), dtype=torch.uint8).to(dev)
+
+        n = len(rec["mols"])
+        na, nb, nt = len(rec["atoms"]), len(rec["bonds"]), len(rec["text"])
+        # graph_pack(keep_device=True) left its tables on the device: no second upload
+        mols, atoms, bonds, text = rec.get("device") or (up(rec["mols"]), up(rec["atoms"]), up(rec["bonds"]), up(rec["text"]))
+        sc = None
+        if scale is not None:
+            sc = torch.as_tensor(np.ascontiguousarray(scale, dtype=np.int32).reshape(n, 2)).to(dev)
+        files = torch.empty(n * MOLFILE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        totals = torch.empty(2, dtype=torch.int32, device=dev)
+        cap = int(cap) if cap is not None else n * self.MOLFILE_GUESS
+        for attempt in range(2):
+            out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+            self._check(self.lib.mnx_molfile_pack(self.h, _ptr(mols), n, _ptr(atoms) if na else None, na,
+                                                  _ptr(bonds) if nb else None, nb, _ptr(text) if nt else None, nt, _ptr(sc),
+                                                  _ptr(files), _ptr(out), cap, _ptr(totals), _stream()), "mnx_molfile_pack")
+            tot = totals.cpu().numpy().view(np.uint32)
+            if not tot[1]:
+                break
+            if attempt:
+                raise MnxError(f"mnx_molfile_pack: capacity {cap} too small after sizing it from totals {tot.tolist()}")
+            cap = int(tot[0])
+        return files.cpu().numpy().view(MOLFILE_DTYPE), out[:int(tot[0])].cpu().numpy().tobytes()
 
     def atom_scan(self, tokens: torch.Tensor, lengths: torch.Tensor, kmax: Optional[int] = None):
         """On-device CharTokenizer.sequence_to_smiles 'indices' for [n,T] int32 id sequences."""

@@ -134,7 +134,8 @@ def unpack_graphs(mols, atoms, bonds, text, coord_bins: int = 64, with_scores: b
 
 def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_batch_size: int = 16,
                      max_len: Optional[int] = None, beam_size: int = 1, compute_confidence: bool = False,
-                     labels=None, free_run=False, packed: bool = False) -> List[dict]:
+                     labels=None, free_run=False, packed: bool = False, molfile: bool = False,
+                     molfile_scale=None) -> List[dict]:
     """Encoder + Decoder.decode for MANY images through the engine's continuous-batching path (mnx_predict):
     same per-image dicts as `decode_batch`, identical results (the on-device atom scan equals
     sequence_to_smiles' indices), much higher throughput. compute_confidence=True: mnx_predict_confidence, the same
@@ -148,8 +149,13 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
     packed: the molecules are put together on the device (mnx_graph_pack) and only their records cross to the host
     (unpack_graphs: 'bonds' instead of the dense 'edges' / 'edge_scores'); greedy only, beam search keeps the dense path.
     The packed path does not run the host tokenizer, so it does not re-verify the device atom scan as the dense path's
-    assertion does: 'indices' are the scan's atom_idx, and a molecule beyond max_atoms raises RuntimeError."""
+    assertion does: 'indices' are the scan's atom_idx, and a molecule beyond max_atoms raises RuntimeError.
+    molfile (packed only): every dict gains 'molfile', the molecule as a V2000 molfile written on the device from the packed
+    tables (mnx_molfile_pack; a str, None for a molecule that gets none); molfile_scale: int [n, 2] = (Sx, Sy) per image in
+    units of 1e-4, None = 100000 each — the reference's factor 10 on a square page."""
     tok = (tokenizer or get_tokenizer())["chartok_coords"]
+    if molfile and not packed:
+        raise ValueError("molfile=True needs packed=True: the molfiles are written from the packed tables")
     if packed and beam_size > 1:
         raise NotImplementedError("packed results are built for greedy decoding (beam search keeps the dense path)")
     if labels is not None and beam_size > 1:
@@ -164,10 +170,16 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
         conf.update(labels=labels, free_run=free_run)
     out = engine.predict(images, ref_batch=ref_batch_size, max_len=max_len, beam=beam_size, **conf)
     if packed:
-        rec = engine.graph_pack(out)
+        rec = engine.graph_pack(out, keep_device=molfile)
         if (rec["mols"]["flags"] & MOL_TRUNCATED).any():
             raise RuntimeError(f"a molecule has more atoms than the engine capacity max_atoms={engine.max_atoms}")
-        return unpack_graphs(rec["mols"], rec["atoms"], rec["bonds"], rec["text"], tok.maxx, compute_confidence)
+        preds = unpack_graphs(rec["mols"], rec["atoms"], rec["bonds"], rec["text"], tok.maxx, compute_confidence)
+        if molfile:
+            files, data = engine.molfile_pack(rec, scale=molfile_scale)
+            for p, f in zip(preds, files):
+                t0, n = int(f["text0"]), int(f["len"])
+                p["molfile"] = data[t0:t0 + n].decode("utf-8", errors="replace") if n else None
+        return preds
     scores = out["scores"].cpu().numpy() if beam_size > 1 else None
     lens = out["lengths"].cpu().numpy()
     toks = out["tokens"].cpu().numpy()
@@ -193,6 +205,13 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
     return preds
 
 
+def page_scale(image) -> tuple:
+    """(Sx, Sy) of mnx_molfile_pack for one input page [height, width, ...]: Sx = round(100000 * width / height), the reference's
+    `ratio` times its factor 10 (chemical.py:935-937) in units of 1e-4, inside the call's range; Sy = 100000."""
+    height, width = int(image.shape[0]), int(image.shape[1])
+    return min(max((200000 * width + height) // (2 * height), 1), 10000000), 100000
+
+
 class _RestartCall(Exception):
     """Private: the facade's engine was rebuilt in the range-fallback mode after part of a call had been computed."""
 
@@ -215,13 +234,18 @@ class molnextr:
     page) or "gray8" (the gray byte per pixel, [n,S,S]: all pages of a group in one mnx_preprocess_batch, a twelfth of the
     staged bytes; every output bit for bit the same).
     packed_results: True = the molecules are put together on the device (mnx_graph_pack) and cross to the host as packed atom /
-    bond / text records instead of the dense token, bond and score matrices; the output dicts are the same."""
+    bond / text records instead of the dense token, bond and score matrices; the output dicts are the same.
+    graph_molfile: True (opt-in; implies the packed path) = when RDKit is absent 'predicted_molfile' is the V2000 molfile that
+    the device writes from the packed tables (mnx_molfile_pack: this library's own writer, not RDKit's), with the reference's
+    page ratio in x (chemical.py:935-937); 'predicted_smiles' stays None — a canonical SMILES needs RDKit."""
 
     image_format = "fp32"
     packed_results = False
+    graph_molfile = False
 
     def __init__(self, model_path, device=None, max_batch: int = 32, dtype: str = DEFAULT_DTYPE,
-                 device_preprocess: bool = True, image_format: str = "fp32", packed_results: bool = False):
+                 device_preprocess: bool = True, image_format: str = "fp32", packed_results: bool = False,
+                 graph_molfile: bool = False):
         if model_path is None:
             raise ValueError("molnextr(model_path): a checkpoint path is required (pass 'synthetic' explicitly for the "
                              "deterministic test checkpoint)")
@@ -244,6 +268,7 @@ class molnextr:
             raise ValueError(f"image_format must be 'fp32' or 'gray8', got {image_format!r}")
         self.image_format = image_format
         self.packed_results = bool(packed_results)
+        self.graph_molfile = bool(graph_molfile)
         self.engine = Engine(states["encoder"], states["decoder"], device=device.index or 0, max_batch=max_batch,
                              dtype=dtype, image_format=image_format)
         self.input_size = args.input_size
@@ -419,11 +444,14 @@ class molnextr:
         group = (self.group_images // batch_size) * batch_size
         groups = [input_images[i:i + group] for i in range(0, len(input_images), group)]
         conf = {"compute_confidence": True} if return_confidence else {}
-        if self.packed_results:
+        if self.packed_results or self.graph_molfile:
             conf["packed"] = True
         gen = self._prefetched(groups)
         try:
             for x in gen:
+                if self.graph_molfile:
+                    pages = input_images[len(preds):len(preds) + x.shape[0]]
+                    conf.update(molfile=True, molfile_scale=[page_scale(im) for im in pages])
                 if labels is not None:
                     rows = slice(len(preds), len(preds) + x.shape[0])
                     conf.update(labels=labels[rows], free_run=cut[rows])
@@ -456,6 +484,8 @@ class molnextr:
             edges, images=input_images)
         outputs = []
         for smiles, molfile, pred in zip(smiles_list, molblock_list, preds):
+            if molfile is None:                               # no RDKit: the device's own molfile, when it was asked for
+                molfile = pred.get("molfile")
             d = {"predicted_smiles": smiles, "predicted_molfile": molfile}
             if return_atoms_bonds:
                 c = pred["chartok_coords"]

@@ -12,7 +12,10 @@ is part of the product path and no number is asserted.
     then (gray8) the dense result path against the packed one (molnextr(packed_results=True): mnx_graph_pack), each with and
     without return_confidence, with the result bytes per image that cross to the host in each; `--pack-out FILE` writes that
     table to a file of its own, and `--pack-only N` runs N mnx_graph_pack calls over 1024 images alone (for a kernel trace);
-(c) patch embedding per 512 images from mnx_profile_read (kind 3), fp32 against gray input.
+(c) patch embedding per 512 images from mnx_profile_read (kind 3), fp32 against gray input;
+(m) (only when asked for: --part m) molfiles written on the device: one mnx_molfile_pack call over the packed tables of 1024
+    images between two events, and predict_images from `--facade-pages` pages with molnextr(graph_molfile=True) against the
+    packed facade without it; `--molfile-out FILE` writes the table to a file of its own.
 The variants of a part alternate inside every repeat (A B A B ...), the table reports the median and the min .. max spread of
 each, and the spread of the fp32 path against itself is the yardstick for "not slower".
 """
@@ -159,6 +162,61 @@ def pack_only(calls):
     m.engine.close()
 
 
+def part_m(n, repeats, lines):
+    """Molfiles from the device: the three launches of one mnx_molfile_pack call over 1024 images between two events (the
+    tables stay on the device, the output buffer has the exact size), then the facade with and without graph_molfile."""
+    import ctypes as C
+    from molnextr_amd.model import molnextr
+    dev = torch.device("cuda", 0)
+    pages = [W.synthetic_page(i % 15) for i in range(n)]
+    ms = {"packed": molnextr("synthetic", dev, max_batch=32, image_format="gray8", packed_results=True),
+          "packed + molfile": molnextr("synthetic", dev, max_batch=32, image_format="gray8", graph_molfile=True)}
+    eng = ms["packed"].engine
+    rec = eng.graph_pack(eng.predict(ms["packed"]._transform(pages[:1024]), ref_batch=32), keep_device=True)
+    files, data = eng.molfile_pack(rec)
+    mols, atoms, bonds, text = rec["device"]
+    na, nb, nt = (int(v) for v in rec["totals"][:3])
+    files_d = torch.empty(len(files) * 16, dtype=torch.uint8, device=dev)
+    out_d = torch.empty(len(data), dtype=torch.uint8, device=dev)
+    totals_d = torch.empty(2, dtype=torch.int32, device=dev)
+    ptr = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
+    ms_call = []
+    for i in range(repeats + 3):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        rc = eng.lib.mnx_molfile_pack(eng.h, ptr(mols), len(files), ptr(atoms), na, ptr(bonds), nb, ptr(text), nt, None, ptr(files_d),
+                                      ptr(out_d), len(data), ptr(totals_d), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        b.record()
+        torch.cuda.synchronize()
+        assert rc == 0 and out_d.cpu().numpy().tobytes() == data
+        if i >= 3:
+            ms_call.append(a.elapsed_time(b) * 1000.0)
+    lines.append(f"(m) one mnx_molfile_pack call over the packed tables of {len(files)} images ({na} atoms, {nb} bonds -> {len(data)} "
+                 f"bytes of molfiles, {int((files['len'] == 0).sum())} molecules without one): device us between two events around "
+                 "its three launches   median [min .. max]")
+    lines.append(f"  mnx_molfile_pack {fmt(ms_call)} us")
+    rate = {k: [] for k in ms}
+    for m in ms.values():
+        m.predict_images(pages[:256], batch_size=32)
+    for _ in range(repeats):
+        for k, m in ms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            m.predict_images(pages, batch_size=32)
+            rate[k].append(n / (time.perf_counter() - t0))
+    lines.append(f"    predict_images from {n} synthetic pages, batch_size 32, image_format gray8: molecules/s   median [min .. max]")
+    for k in ms:
+        lines.append(f"  {k:16s} {fmt(rate[k])} molecules/s")
+    p, q = rate["packed"], rate["packed + molfile"]
+    verdict = ("slower with molfiles beyond the packed facade's own spread" if max(q) < min(p) else
+               "faster with molfiles beyond the packed facade's own spread" if min(q) > max(p) else
+               "the two overlap: no difference beyond the packed facade's own spread")
+    lines.append(f"  with molfiles / without, median {statistics.median(q) / statistics.median(p):.3f} - {verdict}")
+    for m in ms.values():
+        m.engine.close()
+
+
 def part_c(eng, repeats, lines):
     from molnextr_amd.preprocess import normalise_gray
     dev = torch.device("cuda", eng.device)
@@ -190,6 +248,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--out", default=None)
     ap.add_argument("--pack-out", default=None, help="write the dense-against-packed table of part b to this file")
+    ap.add_argument("--molfile-out", default=None, help="write the table of part m to this file")
     ap.add_argument("--pack-only", type=int, default=0, help="run this many mnx_graph_pack calls over 1024 images and exit")
     args = ap.parse_args()
     parts = args.part.split(",")
@@ -216,6 +275,13 @@ def main():
         if args.pack_out:
             os.makedirs(os.path.dirname(os.path.abspath(args.pack_out)), exist_ok=True)
             with open(args.pack_out, "w") as f:
+                f.write("\n".join([lines[0]] + lines[first:]) + "\n")
+    if "m" in parts:
+        first = len(lines)
+        part_m(args.facade_pages, args.repeats, lines)
+        if args.molfile_out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.molfile_out)), exist_ok=True)
+            with open(args.molfile_out, "w") as f:
                 f.write("\n".join([lines[0]] + lines[first:]) + "\n")
     text = "\n".join(lines)
     print(text)
