@@ -43,8 +43,42 @@ static int print_first_molfile(mnx_engine* eng, int n_images, const mnx_mol* mol
     return rc;
 }
 
+/* Molecule 0 as a SMILES of the predicted graph, written on the device from the same tables (mnx_smiles_pack): the token SMILES
+ * printed above names the atoms, this one joins them with the bonds of the bond head. Valid, not canonical, no stereo; R-groups
+ * and abbreviations stay '*'. The same two passes; `order` (each atom's position in the string) is not asked for here. */
+static int print_first_graph_smiles(mnx_engine* eng, int n_images, const mnx_mol* mols_dev, const mnx_atom* atoms_dev,
+                                    const mnx_bond* bonds_dev, const char* text_dev, const uint32_t* table_sizes) {
+    uint32_t totals[2] = {0, 0}, *totals_dev = NULL;
+    mnx_smiles *recs_dev = NULL, rec;
+    char *out_dev = NULL, *out = NULL;
+    int rc, pass;
+    hipMalloc((void**)&recs_dev, (size_t)n_images * sizeof(mnx_smiles));
+    hipMalloc((void**)&totals_dev, sizeof totals);
+    for (pass = 0; pass < 2; ++pass) {
+        rc = mnx_smiles_pack(eng, mols_dev, n_images, atoms_dev, table_sizes[0], bonds_dev, table_sizes[1], text_dev,
+                             table_sizes[2], recs_dev, /*order=*/NULL, out_dev, pass ? totals[0] : 0, totals_dev, /*stream=*/NULL);
+        if (rc != MNX_OK) { fprintf(stderr, "mnx_smiles_pack: %s\n", mnx_last_error(eng)); break; }
+        hipMemcpy(totals, totals_dev, sizeof totals, 2);
+        if (pass == 0 && totals[0]) hipMalloc((void**)&out_dev, totals[0]);
+    }
+    if (rc == MNX_OK) {
+        hipMemcpy(&rec, recs_dev, sizeof rec, 2);
+        out = (char*)malloc((size_t)rec.len + 1);
+        if (rec.flags & (MNX_SMILES_TOO_LARGE | MNX_SMILES_BEYOND_TABLES | MNX_SMILES_DUPLICATE_BOND | MNX_SMILES_RING_NUMBERS)) {
+            printf("graph SMILES 0: none (flags 0x%x)\n", (unsigned)rec.flags);
+        } else if (out) {
+            if (rec.len) hipMemcpy(out, out_dev + rec.text0, rec.len, 2);
+            printf("graph SMILES 0: %.*s (%u ring bonds%s)\n", (int)rec.len, out, (unsigned)rec.n_rings,
+                   (rec.flags & MNX_SMILES_WEDGES_DROPPED) ? ", wedges dropped" : "");
+        }
+        free(out);
+    }
+    hipFree(recs_dev); hipFree(totals_dev); hipFree(out_dev);
+    return rc;
+}
+
 /* The molecules as packed tables (mnx_graph_pack): no tokenizer on the host. A first call with modest capacities; `totals`
- * says what the job needs, so a second call with exactly that is the worst case. Prints molecule 0, then its molfile. */
+ * says what the job needs, so a second call with exactly that is the worst case. Prints molecule 0 with its token SMILES, then its molfile and its graph SMILES. */
 static int print_first_molecule(mnx_engine* eng, int n_images, const int32_t* tokens, const int32_t* lengths,
                                 const int32_t* atom_idx, const int32_t* n_atoms, const uint8_t* edges) {
     uint32_t caps[3], totals[4] = {0, 0, 0, 0}, *totals_dev = NULL, k;
@@ -88,6 +122,7 @@ static int print_first_molecule(mnx_engine* eng, int n_images, const int32_t* to
         }
         free(atoms); free(bonds); free(text);
         rc = print_first_molfile(eng, n_images, mols_dev, atoms_dev, bonds_dev, text_dev, totals);
+        if (rc == MNX_OK) rc = print_first_graph_smiles(eng, n_images, mols_dev, atoms_dev, bonds_dev, text_dev, totals);
     }
     hipFree(mols_dev); hipFree(totals_dev); hipFree(atoms_dev); hipFree(bonds_dev); hipFree(text_dev);
     return rc;
@@ -111,8 +146,9 @@ int run(const mnx_weight_desc* weights, int n_weights, const float* host_images 
     /* mnx_set_token_classes(eng, flags, 101, id_lbracket, id_rbracket, id_C, id_l, id_B, id_r); */
     /* ... and the names of its 101 symbol ids as UTF-8 bytes, for mnx_graph_pack (vocab/vocab_chars.json in id order): */
     /* mnx_set_vocab_text(eng, name_bytes, name_offsets, 101); */
-    /* ... and, for mnx_molfile_pack, the R-group and abbreviation names sorted bytewise (vocab/abbreviations.json); without
-     * this call the molfile step below is refused ("mnx_molfile_pack: call mnx_set_symbol_tables first") and run() fails: */
+    /* ... and, for mnx_molfile_pack and mnx_smiles_pack, the R-group and abbreviation names sorted bytewise
+     * (vocab/abbreviations.json); without this call the molfile step below is refused ("mnx_molfile_pack: call
+     * mnx_set_symbol_tables first") and run() fails: */
     /* mnx_set_symbol_tables(eng, table_bytes, table_offsets, table_kinds, n_names); */
 
     const size_t img_elems = (size_t)3 * 384 * 384;

@@ -507,6 +507,71 @@ int mnx_molfile_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_at
                      const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes,
                      const int32_t* scale, mnx_molfile* files, char* out, uint32_t out_cap, uint32_t* totals, void* stream);
 
+/* Molecules as SMILES of the predicted GRAPH, written on the device from the tables of mnx_graph_pack: the atoms of the token
+ * string joined by the bonds of the bond head — the raw token SMILES in `text` names the atoms but its bonds can disagree
+ * with `bonds`. The string is VALID after the OpenSMILES grammar and NOT canonical (the walk below is fixed by the atom
+ * indices; any toolkit can canonicalise it); it carries no stereo ('@', '/', '\' are never written: wedges are dropped) and
+ * expands no abbreviation (a pseudo-atom is '*'). The third post-pass after mnx_graph_pack and mnx_molfile_pack, with the
+ * arguments, limits and error handling of the latter; it changes no input and touches no decode state.
+ *
+ * One atom is read exactly as mnx_molfile_pack reads it (brackets stripped, R-group table, abbreviation table, then the whole
+ * symbol through the bracket-atom grammar stated there) and written as
+ *   a parsed unbracketed atom (B C N O P S F Cl Br I, b c n o p s, '*'): its bytes as they are;
+ *   a parsed bracket atom: '[' isotope-if-nonzero, the element as spelled (lower case is kept: that is what makes an atom
+ *     aromatic), 'H' for one hydrogen or 'H' digit for more, the charge ('+' / '-' for +-1, else the sign and the decimal
+ *     magnitude), ']'; the chirality mark and the ':class' are dropped: [C@@H] -> [CH], [N++] -> [N+2], [C:12] -> [C],
+ *     [nH] stays [nH];
+ *   a pseudo-atom (a table name, or no parse): "[k*]" for an R-group named 'R' + a number k in 1..999 (the reference sets
+ *     that isotope on its '*' atom), '*' for every other; flag bit 2 is set as in the molfile; nothing is expanded.
+ * One bond is an unordered pair whose class is `type` (`rev` is ignored): 1, 5, 6 single; 2 '='; 3 '#'; 4 aromatic; any other
+ * '~'. A single bond is written as nothing, but as '-' between two aromatic (lower-case) atoms; an aromatic bond as nothing
+ * between two aromatic atoms and as ':' otherwise.
+ * The walk: components in the order of their lowest atom index, joined by '.'; depth-first from that atom, an atom's
+ * neighbours in ascending atom index; an unvisited neighbour becomes a child, every other bond that is not the bond to the
+ * parent is a ring bond. Behind an atom's own text stand its ring bonds, then its children in ascending index, every child but
+ * the last inside '(' ')', the bond symbol of a child directly in front of its atom (inside the parenthesis).
+ * Ring closure numbers, atoms taken in written order: at an atom first every ring bond whose other end was written earlier, in
+ * ascending written position of that end, as the number it was allotted (no bond symbol); then every ring bond whose other
+ * end comes later, in ascending written position of that end, as the bond symbol and the lowest free number >= 1. The numbers
+ * an atom closes are free from the next atom on (no number appears twice at one atom). 1..9 are a digit, 10..99 '%nn'; a
+ * molecule that would hold more than 99 numbers at once gets no SMILES.
+ *
+ *   struct mnx_smiles, 16 bytes  text0, len: the molecule's SMILES is out[text0 .. text0 + len); flags (MNX_SMILES_*): bit 0 more
+ *            than 999 atoms or bonds; bit 1 a record beyond the tables (the cases mnx_molfile_pack lists) or a bond with
+ *            i == j; bit 2 the molecule holds a pseudo-atom; bit 3 a copy of MNX_MOL_TRUNCATED; bit 4 the same atom pair in two
+ *            bond records; bit 5 more than 99 ring numbers in use; bit 6 a bond of class 5 or 6 was written as a plain single
+ *            bond; bit 7 a bond of an unknown class was written as '~'. On bits 0, 1, 4 or 5 the molecule gets no SMILES:
+ *            len = 0, and bits 6 and 7 stay clear (nothing was written). n_rings: the ring bonds = bonds - atoms + components
+ *            (0 on bits 0 and 1, whose records are not read). An empty molecule has len = 0 and flags = 0.
+ * Inputs: as mnx_molfile_pack (mols [n], 1 <= n <= 65536; atoms, bonds 8-byte aligned; text; the sizes of the three tables);
+ * the molecules' atom ranges must not overlap. mnx_set_symbol_tables must have been called.
+ * Outputs, device pointers the caller allocated: recs [n]; order uint16 [n_atom_records] or NULL: order[atom0 + k] = the 0-based
+ * position of the molecule's atom k among the atoms of its string (to carry coordinates and scores over to SMILES atom
+ * order), 0xFFFF for every atom of a molecule that gets no SMILES (entries of atoms outside the table, and of no molecule,
+ * are not written); out [out_cap] bytes (no terminators, no separators); totals uint32 [2] = {bytes needed, 1 if out_cap was
+ * too small}. Nothing is written beyond out_cap, and recs, order and totals are complete all the same: read the needed size
+ * and call again; a sizing call may pass out = NULL with out_cap = 0. Deterministic byte for byte (every output position
+ * comes from a prefix scan; no atomic decides a position or an order). Three launches, asynchronous on `stream`, no
+ * allocation, no host synchronisation.
+ * MNX_ERR_INVALID_ARG (with mnx_last_error, "mnx_smiles_pack: ..."): a null pointer (a table of size 0 and `order` may be
+ * null), n outside 1..65536, misaligned records, or no symbol tables set; nothing is launched then. */
+typedef struct mnx_smiles {
+    uint32_t text0, len;
+    uint32_t flags;             /* MNX_SMILES_* */
+    uint32_t n_rings;
+} mnx_smiles;
+#define MNX_SMILES_TOO_LARGE 1u
+#define MNX_SMILES_BEYOND_TABLES 2u
+#define MNX_SMILES_PSEUDO_ATOM 4u
+#define MNX_SMILES_TRUNCATED 8u
+#define MNX_SMILES_DUPLICATE_BOND 16u
+#define MNX_SMILES_RING_NUMBERS 32u
+#define MNX_SMILES_WEDGES_DROPPED 64u
+#define MNX_SMILES_UNKNOWN_BOND 128u
+int mnx_smiles_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
+                    const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_smiles* recs,
+                    uint16_t* order, char* out, uint32_t out_cap, uint32_t* totals, void* stream);
+
 /* mnx_predict with beam search (BASELINE config 5): the same inputs and outputs, every reference batch searched as
  * mnx_decode_beam does (n_best = 1: the best hypothesis; atom positions and the bond head run on ITS tokens and decoder
  * outputs) while the encoder of the following launch groups runs on the second stream. Up to MNX_BEAM_GROUPS (environment,

@@ -1,5 +1,5 @@
-// block_scan.h — the workgroup prefix scan of the count / scan / fill post-passes (graph_pack.hip, molfile.hip): one
-// definition (internal).
+// block_scan.h — the workgroup prefix scan of the count / scan / fill post-passes (graph_pack.hip, molfile.hip, smiles.hip)
+// and the scan of the text writers over their molecules: one definition (internal).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,6 +23,30 @@ __device__ __forceinline__ unsigned block_scan_excl(unsigned v, unsigned* buf, u
     *total = buf[cur * NT + NT - 1];
     __syncthreads();
     return incl - v;
+}
+
+constexpr int TEXT_SCAN_THREADS = 1024;
+
+// text0 of every record of a text writer (mnx_molfile, mnx_smiles: both begin with text0, len): an exclusive scan of the
+// lengths in tiles of TEXT_SCAN_THREADS with a running 64-bit carry, by ONE workgroup (graph_pack.hip's scan over the images,
+// on one column); a total beyond 2^32 - 1 saturates and sets totals[1].
+template <typename Rec>
+__global__ __launch_bounds__(TEXT_SCAN_THREADS) void text_scan_kernel(Rec* __restrict__ recs, int n, unsigned out_cap,
+                                                                      unsigned* __restrict__ totals) {
+    __shared__ unsigned scan[2 * TEXT_SCAN_THREADS];
+    const int tid = threadIdx.x;
+    unsigned long long carry = 0;
+    for (int base = 0; base < n; base += TEXT_SCAN_THREADS) {
+        const int b = base + tid;
+        unsigned t;
+        const unsigned e = block_scan_excl<TEXT_SCAN_THREADS>(b < n ? recs[b].len : 0u, scan, &t);
+        if (b < n) recs[b].text0 = (unsigned)min(carry + e, 0xffffffffull);
+        carry += t;
+    }
+    if (tid == 0) {
+        totals[0] = (unsigned)min(carry, 0xffffffffull);
+        totals[1] = carry > out_cap ? 1u : 0u;
+    }
 }
 
 }  // namespace mnx

@@ -7,6 +7,7 @@ struct mnx_mol;     // include/molnextr_hip.h: the records of mnx_graph_pack
 struct mnx_atom;
 struct mnx_bond;
 struct mnx_molfile; // the record of mnx_molfile_pack
+struct mnx_smiles;  // the record of mnx_smiles_pack
 
 namespace mnx {
 
@@ -188,7 +189,7 @@ hipError_t graph_pack_enqueue(const TokenClasses* tc_dev, const VocabText* vt_de
                               const double* atom_scores, const double* edge_scores, const double* overall, mnx_mol* mols,
                               mnx_atom* atoms, unsigned atom_cap, mnx_bond* bonds, unsigned bond_cap, char* text,
                               unsigned text_cap, unsigned* totals, hipStream_t s);
-// the R-group and abbreviation names (mnx_set_symbol_tables), sorted bytewise: what molfile.hip looks an atom's symbol up in
+// the R-group and abbreviation names (mnx_set_symbol_tables), sorted bytewise: what atom_symbol.h looks an atom's symbol up in
 struct SymbolTables {
     int n;
     unsigned char len[512];        // bytes of name i, 1..16
@@ -201,6 +202,12 @@ hipError_t molfile_pack_enqueue(const SymbolTables* st_dev, const mnx_mol* mols,
                                 unsigned n_atom_records, const mnx_bond* bonds, unsigned n_bond_records, const char* text,
                                 unsigned n_text_bytes, const int* scale, int coord_bins, mnx_molfile* files, char* out,
                                 unsigned out_cap, unsigned* totals, hipStream_t s);
+// smiles.hip: the packed tables of n molecules as graph SMILES behind one another in `out`, the atoms' written positions in
+// `order` (may be null) (mnx_smiles_pack): count, scan and fill, three launches on s
+hipError_t smiles_pack_enqueue(const SymbolTables* st_dev, const mnx_mol* mols, int n, const mnx_atom* atoms,
+                               unsigned n_atom_records, const mnx_bond* bonds, unsigned n_bond_records, const char* text,
+                               unsigned n_text_bytes, mnx_smiles* recs, unsigned short* order, char* out, unsigned out_cap,
+                               unsigned* totals, hipStream_t s);
 hipError_t edges_enqueue(const DecWeights& w, const DecBuffers& bf, const float* hidden, const int* slot_map,
                          const int* atom_idx, const int* n_atoms, int B, int kmax, int row_stride_T,
                          unsigned char* edges, double* scores, hipStream_t s);

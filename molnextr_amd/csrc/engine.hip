@@ -105,7 +105,7 @@ struct mnx_engine {
     bool have_tc = false;
     VocabText* vt_dev = nullptr;        // names of the symbol ids (mnx_set_vocab_text), read by mnx_graph_pack
     bool have_vt = false;
-    SymbolTables* st_dev = nullptr;     // R-group and abbreviation names (mnx_set_symbol_tables), read by mnx_molfile_pack
+    SymbolTables* st_dev = nullptr;     // R-group and abbreviation names (mnx_set_symbol_tables), read by mnx_molfile_pack and mnx_smiles_pack
     bool have_st = false;
     int n_chunk_bufs = 0;
     bool use_graph = true;
@@ -1377,6 +1377,27 @@ int mnx_molfile_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_at
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, molfile_pack_enqueue(h->st_dev, mols, n, atoms, n_atom_records, bonds, n_bond_records, text, n_text_bytes, scale,
                                    h->cfg.coord_bins, files, out, out_cap, totals, (hipStream_t)stream));
+    return MNX_OK;
+}
+
+int mnx_smiles_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
+                    const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_smiles* recs,
+                    uint16_t* order, char* out, uint32_t out_cap, uint32_t* totals, void* stream) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    if (!mols || !recs || !totals || (!atoms && n_atom_records) || (!bonds && n_bond_records) || (!text && n_text_bytes) ||
+        (!out && out_cap)) {
+        h->err = "mnx_smiles_pack: null pointer";
+        return MNX_ERR_INVALID_ARG;
+    }
+    if (n < 1 || n > 65536) { h->err = "mnx_smiles_pack: 1 <= n <= 65536 required"; return MNX_ERR_INVALID_ARG; }
+    if (((uintptr_t)mols | (uintptr_t)atoms | (uintptr_t)bonds) & 7 || (((uintptr_t)recs | (uintptr_t)totals) & 3) || ((uintptr_t)order & 1)) {
+        h->err = "mnx_smiles_pack: mols, atoms and bonds must be 8-byte aligned, recs and totals 4-byte, order 2-byte";
+        return MNX_ERR_INVALID_ARG;
+    }
+    if (!h->have_st) { h->err = "mnx_smiles_pack: call mnx_set_symbol_tables first"; return MNX_ERR_INVALID_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, smiles_pack_enqueue(h->st_dev, mols, n, atoms, n_atom_records, bonds, n_bond_records, text, n_text_bytes, recs, order,
+                                  out, out_cap, totals, (hipStream_t)stream));
     return MNX_OK;
 }
 

@@ -1,0 +1,383 @@
+// smiles.hip — a SMILES of the predicted graph from the packed molecule tables of mnx_graph_pack (mnx_smiles_pack): the atoms as
+// atom_symbol.h reads them, the bonds of the bond head, written by a depth-first walk after the OpenSMILES grammar. Valid, not
+// canonical (the walk's order is fixed by the atom indices), no stereo, pseudo-atoms as '*'.
+//   count  one workgroup per molecule: the walk and the length of its string -> recs[b].len / flags / n_rings
+//   scan   exclusive scan of the lengths over the molecules -> recs[b].text0, totals
+//   fill   one workgroup per molecule: the walk again, the bytes behind text0 and the atoms' positions in `order`
+// Inside a workgroup: atoms and neighbour lists in parallel, ONE lane for the search and the ring numbers (at most 999 atoms
+// and 999 bonds: kept simple), then every atom's piece of the string in parallel, placed by a prefix scan. LDS atomics only
+// count degrees and hand out slots of an unsorted list that is sorted afterwards, so no atomic decides a position or an order.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/molnextr_hip.h"
+#include "atom_symbol.h"
+#include "block_scan.h"
+#include "dec_types.h"
+
+namespace mnx {
+
+static_assert(sizeof(mnx_smiles) == 16, "record layout of molnextr_hip.h");
+
+namespace {
+
+constexpr int SM_THREADS = 256;
+constexpr int SM_MAX = 1024;             // atoms held in LDS (999 at most)
+constexpr int SM_PER = SM_MAX / SM_THREADS;
+constexpr int SM_SLOTS = 2 * SM_MAX;     // neighbour-list entries: two per bond (999 bonds at most)
+constexpr unsigned NONE = 0xFFFFu;
+constexpr unsigned REFUSED = MNX_SMILES_TOO_LARGE | MNX_SMILES_BEYOND_TABLES | MNX_SMILES_DUPLICATE_BOND | MNX_SMILES_RING_NUMBERS;
+
+// ---- one entry of a neighbour list ----
+//   bits 0-9 the neighbour, bits 10-12 the bond's written class, bits 13-22 the atom that owns the list, bit 23 a bond of the
+//   search tree (to the parent or to a child); every other bond is a ring bond
+constexpr unsigned B_SINGLE = 0, B_DOUBLE = 1, B_TRIPLE = 2, B_AROMATIC = 3, B_ANY = 4;
+constexpr unsigned SLOT_TREE = 1u << 23;
+__device__ __forceinline__ unsigned slot_nbr(unsigned e) { return e & 1023u; }
+__device__ __forceinline__ unsigned slot_cls(unsigned e) { return e >> 10 & 7u; }
+__device__ __forceinline__ unsigned slot_owner(unsigned e) { return e >> 13 & 1023u; }
+
+// the byte of a bond between two atoms, 0 = written as nothing
+__device__ __forceinline__ char bond_symbol(unsigned cls, bool both_aromatic) {
+    switch (cls) {
+        case B_SINGLE: return both_aromatic ? '-' : 0;
+        case B_DOUBLE: return '=';
+        case B_TRIPLE: return '#';
+        case B_AROMATIC: return both_aromatic ? 0 : ':';
+        default: return '~';
+    }
+}
+
+template <typename Put>
+__device__ __forceinline__ void put_number(unsigned v, Put put) {       // decimal, v <= 999
+    if (v >= 100) put((char)('0' + v / 100));
+    if (v >= 10) put((char)('0' + v / 10 % 10));
+    put((char)('0' + v % 10));
+}
+
+// One atom's text from its interpretation (atom_symbol.h) and the two bytes of its element.
+template <typename Put>
+__device__ __forceinline__ void put_atom(unsigned w, unsigned el, Put put) {
+    const unsigned cls = info_cls(w);
+    if (cls == CLS_PSEUDO) { put('*'); return; }
+    if (cls == CLS_RNUM) { put('['); put_number(info_num(w), put); put('*'); put(']'); return; }
+    const char e0 = (char)(el & 255u), e1 = (char)(el >> 8 & 255u);
+    const bool bracket = (w & 4u) != 0;
+    if (bracket) {
+        put('[');
+        if (info_num(w)) put_number(info_num(w), put);
+    }
+    put(e0 == 'R' && e1 == ' ' ? '*' : info_aromatic(w) ? (char)(e0 + 32) : e0);
+    if (e1 != ' ') put(e1);
+    if (bracket) {
+        const int h = info_h(w), q = info_charge(w);
+        if (h >= 1) put('H');
+        if (h >= 2) put((char)('0' + h));
+        if (q != 0) {
+            put(q > 0 ? '+' : '-');
+            if (q > 1 || q < -1) put_number((unsigned)(q > 0 ? q : -q), put);
+        }
+        put(']');
+    }
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
+        const mnx_mol* __restrict__ mols, const mnx_atom* __restrict__ atoms, unsigned n_atom_records,
+        const mnx_bond* __restrict__ bonds, unsigned n_bond_records, const unsigned char* __restrict__ text,
+        unsigned n_text_bytes, const SymbolTables* __restrict__ st, mnx_smiles* __restrict__ recs,
+        unsigned short* __restrict__ order, char* __restrict__ out, unsigned out_cap) {
+    __shared__ unsigned info[SM_MAX], elem[SM_MAX];
+    __shared__ unsigned off[SM_MAX + 1], cnt[SM_MAX];     // an atom's list is [off[a], off[a + 1]); cnt: degrees, then fill cursors
+    __shared__ unsigned raw[SM_SLOTS], adj[SM_SLOTS];     // the lists as the bonds came, then in ascending neighbour index
+    __shared__ unsigned scan[2 * SM_THREADS];
+    __shared__ unsigned short pos[SM_MAX], at[SM_MAX];    // atom -> written position, position -> atom
+    __shared__ unsigned short parent[SM_MAX], stk[SM_MAX], cur[SM_MAX];
+    __shared__ unsigned short done_child[SM_MAX], done_last[SM_MAX];  // the child an atom returned from, the atom written last inside it
+    __shared__ unsigned short closes[SM_MAX];             // ')' behind an atom's text
+    __shared__ unsigned char paren[SM_MAX], rnum[SM_SLOTS];
+    __shared__ unsigned walk[2];                          // components, 1 = more than 99 ring numbers in use
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const mnx_mol m = mols[b];
+    const unsigned base_flags = (m.flags & MNX_MOL_TRUNCATED) ? MNX_SMILES_TRUNCATED : 0u;
+    unsigned text0 = 0;
+    if (FILL) {
+        const mnx_smiles r = recs[b];
+        if (r.len == 0) {                                 // no string (the same for every thread): its atoms get no position
+            if (order && (r.flags & REFUSED))
+                for (unsigned a = tid; a < m.n_atoms && (unsigned long long)m.atom0 + a < n_atom_records; a += SM_THREADS)
+                    order[m.atom0 + a] = (unsigned short)NONE;
+            return;
+        }
+        text0 = r.text0;
+    } else {
+        unsigned flags = base_flags;
+        if (m.n_atoms > 999u || m.n_bonds > 999u) flags |= MNX_SMILES_TOO_LARGE;
+        if ((unsigned long long)m.atom0 + m.n_atoms > n_atom_records || (unsigned long long)m.bond0 + m.n_bonds > n_bond_records ||
+            (unsigned long long)m.text0 + m.smiles_len > n_text_bytes)
+            flags |= MNX_SMILES_BEYOND_TABLES;
+        if (flags & (MNX_SMILES_TOO_LARGE | MNX_SMILES_BEYOND_TABLES)) {
+            if (tid == 0) { recs[b].len = 0; recs[b].flags = flags; recs[b].n_rings = 0; }
+            return;
+        }
+    }
+    const int na = (int)m.n_atoms, nb = (int)m.n_bonds;
+    const mnx_atom* A = atoms + m.atom0;
+    const mnx_bond* B = bonds + m.bond0;
+
+    // ---- every atom's interpretation, every bond's degree counts; a record that points beyond its table refuses the molecule ----
+    int bad = 0, pseudo = 0, wedge = 0, any = 0;
+    for (int a = tid; a < SM_MAX; a += SM_THREADS) {
+        unsigned w = 0, s3 = 0;
+        if (a < na) {
+            const unsigned s0 = A[a].sym0, sl = A[a].sym_len;
+            if ((unsigned long long)m.text0 + s0 + sl > n_text_bytes) bad = 1;
+            else w = interpret_atom(st, text + m.text0 + s0, (int)sl, &s3);
+            pseudo |= info_cls(w) != CLS_ATOM;
+        }
+        info[a] = w;
+        elem[a] = s3;
+        cnt[a] = 0;
+        pos[a] = (unsigned short)NONE;
+        closes[a] = 0;
+        paren[a] = 0;
+    }
+    __syncthreads();
+    for (int k = tid; k < nb; k += SM_THREADS) {
+        const unsigned i = B[k].i, j = B[k].j, ty = B[k].type;
+        if (i >= (unsigned)na || j >= (unsigned)na || i == j) { bad = 1; continue; }
+        wedge |= ty == 5 || ty == 6;
+        any |= ty < 1 || ty > 6;
+        atomicAdd(&cnt[i], 1u);                           // a count does not depend on the order of its increments
+        atomicAdd(&cnt[j], 1u);
+    }
+    if (__syncthreads_or(bad)) {                          // (count refuses; fill never comes here: count left len = 0)
+        if (!FILL && tid == 0) { recs[b].len = 0; recs[b].flags = base_flags | MNX_SMILES_BEYOND_TABLES; recs[b].n_rings = 0; }
+        return;
+    }
+    if (!FILL) {
+        pseudo = __syncthreads_or(pseudo);
+        wedge = __syncthreads_or(wedge);
+        any = __syncthreads_or(any);
+    }
+
+    // ---- neighbour lists: offsets from a scan of the degrees, entries as the bonds come, then each list in ascending order ----
+    {
+        unsigned d[SM_PER], sum = 0, total;
+#pragma unroll
+        for (int q = 0; q < SM_PER; ++q) { d[q] = cnt[SM_PER * tid + q]; sum += d[q]; }
+        unsigned e = block_scan_excl<SM_THREADS>(sum, scan, &total);
+#pragma unroll
+        for (int q = 0; q < SM_PER; ++q) { off[SM_PER * tid + q] = e; cnt[SM_PER * tid + q] = 0; e += d[q]; }
+        if (tid == 0) off[SM_MAX] = total;
+    }
+    __syncthreads();
+    for (int k = tid; k < nb; k += SM_THREADS) {
+        const unsigned i = B[k].i, j = B[k].j, ty = B[k].type;
+        const unsigned cls = (ty == 1 || ty == 5 || ty == 6) ? B_SINGLE : ty == 2 ? B_DOUBLE : ty == 3 ? B_TRIPLE : ty == 4 ? B_AROMATIC : B_ANY;
+        raw[off[i] + atomicAdd(&cnt[i], 1u)] = j | cls << 10 | i << 13;       // any slot of the list: the sort below fixes the order
+        raw[off[j] + atomicAdd(&cnt[j], 1u)] = i | cls << 10 | j << 13;
+    }
+    __syncthreads();
+    int dup = 0;
+    for (int s = tid; s < 2 * nb; s += SM_THREADS) {      // rank of every entry inside its list; equal neighbours = a duplicate pair
+        const unsigned e = raw[s], mine = slot_nbr(e), a = slot_owner(e);
+        unsigned rank = 0;
+        for (unsigned t = off[a]; t < off[a + 1]; ++t) {
+            const unsigned n = slot_nbr(raw[t]);
+            rank += n < mine || (n == mine && t < (unsigned)s);
+            dup |= n == mine && t != (unsigned)s;
+        }
+        adj[off[a] + rank] = e;
+    }
+    dup = __syncthreads_or(dup);
+
+    // ---- the search, by one lane: depth-first from the lowest atom of every component, neighbours in ascending index, an
+    //      explicit stack (a path of 999 atoms is 998 deep). It leaves the written order, the tree bonds, the parentheses. ----
+    if (tid == 0) {
+        unsigned written = 0, comps = 0;
+        for (int root = 0; root < na; ++root) {
+            if (pos[root] != NONE) continue;
+            ++comps;
+            int sp = 0;
+            stk[0] = (unsigned short)root;
+            parent[root] = (unsigned short)NONE;
+            done_child[root] = (unsigned short)NONE;
+            cur[root] = (unsigned short)off[root];
+            pos[root] = (unsigned short)written;
+            at[written++] = (unsigned short)root;
+            while (sp >= 0) {
+                const unsigned a = stk[sp], c = cur[a];
+                if (c == off[a + 1]) {                    // a is finished: its parent remembers it and the atom written last
+                    if (--sp >= 0) {
+                        const unsigned p = stk[sp];
+                        done_child[p] = (unsigned short)a;
+                        done_last[p] = at[written - 1];
+                    }
+                    continue;
+                }
+                cur[a] = (unsigned short)(c + 1);
+                const unsigned n = slot_nbr(adj[c]);
+                if (n == parent[a]) { adj[c] |= SLOT_TREE; continue; }
+                if (pos[n] != NONE) continue;             // a ring bond
+                adj[c] |= SLOT_TREE;
+                if (done_child[a] != NONE) {              // a further child: the one before it goes inside parentheses
+                    paren[done_child[a]] = 1;
+                    closes[done_last[a]] += 1;
+                }
+                parent[n] = (unsigned short)a;
+                done_child[n] = (unsigned short)NONE;
+                cur[n] = (unsigned short)off[n];
+                pos[n] = (unsigned short)written;
+                at[written++] = (unsigned short)n;
+                stk[++sp] = (unsigned short)n;
+            }
+        }
+        walk[0] = comps;
+        walk[1] = 0;
+    }
+    __syncthreads();
+    const unsigned n_rings = (unsigned)nb + walk[0] - (unsigned)na;
+    if (dup) {                                            // (count refuses; fill never comes here)
+        if (!FILL && tid == 0) {
+            recs[b].len = 0;
+            recs[b].flags = base_flags | (pseudo ? MNX_SMILES_PSEUDO_ATOM : 0u) | MNX_SMILES_DUPLICATE_BOND;
+            recs[b].n_rings = n_rings;
+        }
+        return;
+    }
+
+    // ---- every list once more, now in ascending written position of the neighbour: ring closures, then ring openings ----
+    for (int s = tid; s < 2 * nb; s += SM_THREADS) {
+        const unsigned e = adj[s], mine = pos[slot_nbr(e)], a = slot_owner(e);
+        unsigned rank = 0;
+        for (unsigned t = off[a]; t < off[a + 1]; ++t) rank += pos[slot_nbr(adj[t])] < mine;
+        raw[off[a] + rank] = e;
+    }
+    __syncthreads();
+
+    // ---- ring numbers, by the same lane, atoms in written order: a free mask of 99 bits; what an atom closes is free from
+    //      the next atom on. An opening writes its number into the entries of both ends. ----
+    if (tid == 0) {
+        unsigned long long used[2] = {0, 0}, closed[2] = {0, 0};
+        unsigned in_use = 0, fail = 0;
+        for (int p = 0; p < na; ++p) {
+            const unsigned a = at[p];
+            in_use -= (unsigned)(__popcll(closed[0]) + __popcll(closed[1]));
+            used[0] &= ~closed[0]; used[1] &= ~closed[1];
+            closed[0] = closed[1] = 0;
+            unsigned opens = 0;
+            for (unsigned s = off[a]; s < off[a + 1]; ++s) opens += !(raw[s] & SLOT_TREE) && pos[slot_nbr(raw[s])] > (unsigned)p;
+            if (in_use + opens > 99u) { fail = 1; break; }
+            for (unsigned s = off[a]; s < off[a + 1]; ++s) {
+                const unsigned e = raw[s], n = slot_nbr(e);
+                if (e & SLOT_TREE) continue;
+                if (pos[n] < (unsigned)p) {
+                    const unsigned k = rnum[s] - 1u;
+                    closed[k >> 6] |= 1ull << (k & 63u);
+                    continue;
+                }
+                const unsigned k = ~used[0] ? (unsigned)__ffsll((long long)~used[0]) - 1u : 64u + (unsigned)__ffsll((long long)~used[1]) - 1u;
+                used[k >> 6] |= 1ull << (k & 63u);
+                ++in_use;
+                rnum[s] = (unsigned char)(k + 1u);
+                unsigned lo = off[n], hi = off[n + 1] - 1u;           // n's entry for a: its list is ordered by written position
+                while (lo < hi) {
+                    const unsigned mid = (lo + hi) >> 1;
+                    if (pos[slot_nbr(raw[mid])] < (unsigned)p) lo = mid + 1u; else hi = mid;
+                }
+                rnum[lo] = (unsigned char)(k + 1u);
+            }
+        }
+        walk[1] = fail;
+    }
+    __syncthreads();
+    if (walk[1]) {                                        // (count refuses; fill never comes here)
+        if (!FILL && tid == 0) {
+            recs[b].len = 0;
+            recs[b].flags = base_flags | (pseudo ? MNX_SMILES_PSEUDO_ATOM : 0u) | MNX_SMILES_RING_NUMBERS;
+            recs[b].n_rings = n_rings;
+        }
+        return;
+    }
+
+    // ---- the piece of the atom at written position p: '.' or '(' and the bond from its parent, its text, its ring items, the
+    //      ')' of every branch that ends behind it ----
+    auto piece = [&](unsigned p, auto put) {
+        const unsigned a = at[p], w = info[a], par = parent[a];
+        const bool aromatic = info_aromatic(w);
+        if (par == NONE) {
+            if (p > 0) put('.');
+        } else {
+            if (paren[a]) put('(');
+            for (unsigned s = off[a]; s < off[a + 1]; ++s) {
+                const unsigned e = raw[s];
+                if ((e & SLOT_TREE) && slot_nbr(e) == par) {
+                    const char c = bond_symbol(slot_cls(e), aromatic && info_aromatic(info[par]));
+                    if (c) put(c);
+                    break;
+                }
+            }
+        }
+        put_atom(w, elem[a], put);
+        for (unsigned s = off[a]; s < off[a + 1]; ++s) {
+            const unsigned e = raw[s], n = slot_nbr(e), r = rnum[s];
+            if (e & SLOT_TREE) continue;
+            if (pos[n] > p) {
+                const char c = bond_symbol(slot_cls(e), aromatic && info_aromatic(info[n]));
+                if (c) put(c);
+            }
+            if (r >= 10) { put('%'); put((char)('0' + r / 10)); }
+            put((char)('0' + r % 10));
+        }
+        for (unsigned k = 0; k < closes[a]; ++k) put(')');
+    };
+
+    // ---- positions: SM_PER neighbouring pieces per thread, one scan ----
+    unsigned len[SM_PER], sum = 0, total;
+#pragma unroll
+    for (int q = 0; q < SM_PER; ++q) {
+        unsigned l = 0;
+        if (SM_PER * tid + q < na) piece((unsigned)(SM_PER * tid + q), [&](char) { ++l; });
+        len[q] = l;
+        sum += l;
+    }
+    unsigned at_byte = block_scan_excl<SM_THREADS>(sum, scan, &total);
+    if (!FILL) {
+        if (tid == 0) {
+            recs[b].len = total;
+            recs[b].flags = base_flags | (pseudo ? MNX_SMILES_PSEUDO_ATOM : 0u) | (wedge ? MNX_SMILES_WEDGES_DROPPED : 0u) |
+                            (any ? MNX_SMILES_UNKNOWN_BOND : 0u);
+            recs[b].n_rings = n_rings;
+        }
+        return;
+    }
+#pragma unroll
+    for (int q = 0; q < SM_PER; ++q) {
+        if (SM_PER * tid + q >= na) break;
+        unsigned long long o = (unsigned long long)text0 + at_byte;
+        piece((unsigned)(SM_PER * tid + q), [&](char c) {                // nothing is written beyond out_cap
+            if (o < out_cap) out[o] = c;
+            ++o;
+        });
+        at_byte += len[q];
+    }
+    if (order)
+        for (int a = tid; a < na; a += SM_THREADS) order[m.atom0 + a] = pos[a];
+}
+
+}  // namespace
+
+hipError_t smiles_pack_enqueue(const SymbolTables* st_dev, const mnx_mol* mols, int n, const mnx_atom* atoms,
+                               unsigned n_atom_records, const mnx_bond* bonds, unsigned n_bond_records, const char* text,
+                               unsigned n_text_bytes, mnx_smiles* recs, unsigned short* order, char* out, unsigned out_cap,
+                               unsigned* totals, hipStream_t s) {
+    hipLaunchKernelGGL(smiles_kernel<false>, dim3(n), dim3(SM_THREADS), 0, s, mols, atoms, n_atom_records, bonds, n_bond_records,
+                       (const unsigned char*)text, n_text_bytes, st_dev, recs, order, out, out_cap);
+    hipLaunchKernelGGL(text_scan_kernel<mnx_smiles>, dim3(1), dim3(TEXT_SCAN_THREADS), 0, s, recs, n, out_cap, totals);
+    hipLaunchKernelGGL(smiles_kernel<true>, dim3(n), dim3(SM_THREADS), 0, s, mols, atoms, n_atom_records, bonds, n_bond_records,
+                       (const unsigned char*)text, n_text_bytes, st_dev, recs, order, out, out_cap);
+    return hipGetLastError();
+}
+
+}  // namespace mnx

@@ -27,7 +27,7 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
            "mnx_predict_confidence", "mnx_confidence", "mnx_window_attn", "mnx_kv_block", "mnx_preprocess_batch",
            "mnx_encode_gray8", "mnx_predict_gray8", "mnx_decode_guided", "mnx_predict_guided", "mnx_patch_embed",
            "mnx_layernorm16", "mnx_merge_ln16", "mnx_cast16", "mnx_sgemm_tn", "mnx_set_vocab_text", "mnx_graph_pack",
-           "mnx_set_symbol_tables", "mnx_molfile_pack")
+           "mnx_set_symbol_tables", "mnx_molfile_pack", "mnx_smiles_pack")
 
 # Encoder operand modes (include/molnextr_hip.h MNX_DTYPE_*). "fp16x3" — split fp16 operands, three MFMA terms per
 # product, fp32-class results — is the default: it is the fastest mode whose results stay a factor of four inside north_star's
@@ -100,6 +100,11 @@ class MnxMolfile(C.Structure):
     _fields_ = [("text0", C.c_uint32), ("len", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class MnxSmiles(C.Structure):
+    """include/molnextr_hip.h mnx_smiles: one molecule of mnx_smiles_pack (16 bytes)."""
+    _fields_ = [("text0", C.c_uint32), ("len", C.c_uint32), ("flags", C.c_uint32), ("n_rings", C.c_uint32)]
+
+
 # the same three records as numpy structured dtypes (C layout: align=True), what Engine.graph_pack returns
 MOL_DTYPE = np.dtype([("atom0", "<u4"), ("n_atoms", "<u4"), ("bond0", "<u4"), ("n_bonds", "<u4"), ("text0", "<u4"),
                       ("smiles_len", "<u4"), ("flags", "<u4"), ("reserved", "<u4"), ("overall_score", "<f8")], align=True)
@@ -111,6 +116,13 @@ MOLFILE_DTYPE = np.dtype([("text0", "<u4"), ("len", "<u4"), ("flags", "<u4"), ("
 # mnx_molfile.flags (MNX_MOLFILE_*): no molfile (len 0) for more than 999 atoms / bonds or records beyond the tables passed;
 # the molecule holds a pseudo-atom (R-group, abbreviation, unparsable symbol); a copy of MOL_TRUNCATED
 MOLFILE_TOO_LARGE, MOLFILE_BEYOND_TABLES, MOLFILE_PSEUDO_ATOM, MOLFILE_TRUNCATED = 1, 2, 4, 8
+SMILES_DTYPE = np.dtype([("text0", "<u4"), ("len", "<u4"), ("flags", "<u4"), ("n_rings", "<u4")], align=True)
+# mnx_smiles.flags (MNX_SMILES_*): the first four as the molfile's; the same atom pair in two bond records; more than 99 ring
+# closure numbers in use; wedge bonds written as plain single bonds; a bond of an unknown class written as '~'
+(SMILES_TOO_LARGE, SMILES_BEYOND_TABLES, SMILES_PSEUDO_ATOM, SMILES_TRUNCATED, SMILES_DUPLICATE_BOND, SMILES_RING_NUMBERS,
+ SMILES_WEDGES_DROPPED, SMILES_UNKNOWN_BOND) = 1, 2, 4, 8, 16, 32, 64, 128
+SMILES_REFUSED = SMILES_TOO_LARGE | SMILES_BEYOND_TABLES | SMILES_DUPLICATE_BOND | SMILES_RING_NUMBERS    # no SMILES: len 0
+SMILES_NO_POSITION = 0xFFFF             # `order` of an atom whose molecule got no SMILES
 
 
 def vocab_text(tok):
@@ -237,6 +249,8 @@ def load_library():
     lib.mnx_set_symbol_tables.argtypes = [vp, C.c_char_p, vp, vp, i32]
     lib.mnx_molfile_pack.restype = C.c_int
     lib.mnx_molfile_pack.argtypes = [vp, vp, i32, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp]
+    lib.mnx_smiles_pack.restype = C.c_int
+    lib.mnx_smiles_pack.argtypes = [vp, vp, i32, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp]
     lib.mnx_atom_scan.restype = C.c_int
     lib.mnx_atom_scan.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.mnx_preprocess.restype = C.c_int
@@ -793,7 +807,7 @@ class Engine:
         'edge_scores' and 'overall_score' in `out` the records carry the confidences, otherwise zeros. One D2H copy per table
         (plus the 16 bytes of totals); starts from PACK_GUESS per image (or caps = (atom_cap, bond_cap, text_cap)) and
         repeats at most once with the sizes `totals` reports. keep_device: also 'device' = the four tables as the uint8 device
-        tensors they were written to, for molfile_pack."""
+        tensors they were written to, for molfile_pack and smiles_pack."""
         tokens, lengths = out["tokens"], out["lengths"]
         n, T = tokens.shape
         kmax = out["atom_idx"].shape[1]
@@ -862,6 +876,42 @@ class Engine:
                 raise MnxError(f"mnx_molfile_pack: capacity {cap} too small after sizing it from totals {tot.tolist()}")
             cap = int(tot[0])
         return files.cpu().numpy().view(MOLFILE_DTYPE), out[:int(tot[0])].cpu().numpy().tobytes()
+
+    SMILES_GUESS = 256        # first capacity of smiles_pack per molecule (a drug-like SMILES is well under 200 bytes)
+
+    def smiles_pack(self, rec: dict, cap: Optional[int] = None):
+        """graph_pack's records -> (recs [n] SMILES_DTYPE, order uint16 [atoms], bytes): the graph SMILES of molecule b is
+        bytes[recs[b]['text0'] : +recs[b]['len']] (mnx_smiles_pack: valid, not canonical, no stereo, pseudo-atoms as '*'; len 0
+        and a flag of SMILES_REFUSED for a molecule that gets none), order[atom0 + k] the position of its atom k in that
+        string (SMILES_NO_POSITION without one). The records go back to the device as they are (or stay there:
+        graph_pack(keep_device=True)); starts from SMILES_GUESS bytes per molecule (or cap) and repeats at most once with the
+        size `totals` reports."""
+        dev = torch.device("cuda", self.device)
+
+        def up(a):
+            raw = a if isinstance(a, (bytes, bytearray)) else np.ascontiguousarray(a).tobytes()
+            return torch.frombuffer(bytearray(raw) or bytearray(8), dtype=torch.uint8).to(dev)
+
+        n = len(rec["mols"])
+        na, nb, nt = len(rec["atoms"]), len(rec["bonds"]), len(rec["text"])
+        mols, atoms, bonds, text = rec.get("device") or (up(rec["mols"]), up(rec["atoms"]), up(rec["bonds"]), up(rec["text"]))
+        recs = torch.empty(n * SMILES_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        order = torch.full((max(na, 1),), -1, dtype=torch.int16, device=dev)     # every entry SMILES_NO_POSITION
+        totals = torch.empty(2, dtype=torch.int32, device=dev)
+        cap = int(cap) if cap is not None else n * self.SMILES_GUESS
+        for attempt in range(2):
+            out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+            self._check(self.lib.mnx_smiles_pack(self.h, _ptr(mols), n, _ptr(atoms) if na else None, na,
+                                                 _ptr(bonds) if nb else None, nb, _ptr(text) if nt else None, nt, _ptr(recs),
+                                                 _ptr(order), _ptr(out), cap, _ptr(totals), _stream()), "mnx_smiles_pack")
+            tot = totals.cpu().numpy().view(np.uint32)
+            if not tot[1]:
+                break
+            if attempt:
+                raise MnxError(f"mnx_smiles_pack: capacity {cap} too small after sizing it from totals {tot.tolist()}")
+            cap = int(tot[0])
+        return (recs.cpu().numpy().view(SMILES_DTYPE), order[:na].cpu().numpy().view(np.uint16),
+                out[:int(tot[0])].cpu().numpy().tobytes())
 
     def atom_scan(self, tokens: torch.Tensor, lengths: torch.Tensor, kmax: Optional[int] = None):
         """On-device CharTokenizer.sequence_to_smiles 'indices' for [n,T] int32 id sequences."""

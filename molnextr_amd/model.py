@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import weights as W
-from .engine import DEFAULT_DTYPE, MOL_TRUNCATED, Engine, MnxError
+from .engine import DEFAULT_DTYPE, MOL_TRUNCATED, SMILES_REFUSED, Engine, MnxError
 from .preprocess import load_image_rgb, transform_image, transform_image_gray
 from .tokenizer import coords_labels, get_tokenizer
 
@@ -135,7 +135,7 @@ def unpack_graphs(mols, atoms, bonds, text, coord_bins: int = 64, with_scores: b
 def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_batch_size: int = 16,
                      max_len: Optional[int] = None, beam_size: int = 1, compute_confidence: bool = False,
                      labels=None, free_run=False, packed: bool = False, molfile: bool = False,
-                     molfile_scale=None) -> List[dict]:
+                     molfile_scale=None, smiles: bool = False) -> List[dict]:
     """Encoder + Decoder.decode for MANY images through the engine's continuous-batching path (mnx_predict):
     same per-image dicts as `decode_batch`, identical results (the on-device atom scan equals
     sequence_to_smiles' indices), much higher throughput. compute_confidence=True: mnx_predict_confidence, the same
@@ -152,10 +152,15 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
     assertion does: 'indices' are the scan's atom_idx, and a molecule beyond max_atoms raises RuntimeError.
     molfile (packed only): every dict gains 'molfile', the molecule as a V2000 molfile written on the device from the packed
     tables (mnx_molfile_pack; a str, None for a molecule that gets none); molfile_scale: int [n, 2] = (Sx, Sy) per image in
-    units of 1e-4, None = 100000 each — the reference's factor 10 on a square page."""
+    units of 1e-4, None = 100000 each — the reference's factor 10 on a square page.
+    smiles (packed only): every dict gains 'graph_smiles', a SMILES of the predicted graph written on the device from the packed
+    tables (mnx_smiles_pack: valid, not canonical, no stereo, abbreviations and R-groups as '*'; a str, None for a molecule
+    that gets none), and 'graph_smiles_order', the position of every atom in that string (None without one)."""
     tok = (tokenizer or get_tokenizer())["chartok_coords"]
     if molfile and not packed:
         raise ValueError("molfile=True needs packed=True: the molfiles are written from the packed tables")
+    if smiles and not packed:
+        raise ValueError("smiles=True needs packed=True: the graph SMILES are written from the packed tables")
     if packed and beam_size > 1:
         raise NotImplementedError("packed results are built for greedy decoding (beam search keeps the dense path)")
     if labels is not None and beam_size > 1:
@@ -170,7 +175,7 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
         conf.update(labels=labels, free_run=free_run)
     out = engine.predict(images, ref_batch=ref_batch_size, max_len=max_len, beam=beam_size, **conf)
     if packed:
-        rec = engine.graph_pack(out, keep_device=molfile)
+        rec = engine.graph_pack(out, keep_device=molfile or smiles)
         if (rec["mols"]["flags"] & MOL_TRUNCATED).any():
             raise RuntimeError(f"a molecule has more atoms than the engine capacity max_atoms={engine.max_atoms}")
         preds = unpack_graphs(rec["mols"], rec["atoms"], rec["bonds"], rec["text"], tok.maxx, compute_confidence)
@@ -179,6 +184,13 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
             for p, f in zip(preds, files):
                 t0, n = int(f["text0"]), int(f["len"])
                 p["molfile"] = data[t0:t0 + n].decode("utf-8", errors="replace") if n else None
+        if smiles:
+            recs, order, data = engine.smiles_pack(rec)
+            for p, r, m in zip(preds, recs, rec["mols"]):
+                t0, n, a0, na = int(r["text0"]), int(r["len"]), int(m["atom0"]), int(m["n_atoms"])
+                written = not int(r["flags"]) & SMILES_REFUSED               # an empty molecule is written as the empty string
+                p["graph_smiles"] = data[t0:t0 + n].decode("ascii") if written else None
+                p["graph_smiles_order"] = order[a0:a0 + na].tolist() if written else None
         return preds
     scores = out["scores"].cpu().numpy() if beam_size > 1 else None
     lens = out["lengths"].cpu().numpy()
@@ -237,15 +249,22 @@ class molnextr:
     bond / text records instead of the dense token, bond and score matrices; the output dicts are the same.
     graph_molfile: True (opt-in; implies the packed path) = when RDKit is absent 'predicted_molfile' is the V2000 molfile that
     the device writes from the packed tables (mnx_molfile_pack: this library's own writer, not RDKit's), with the reference's
-    page ratio in x (chemical.py:935-937); 'predicted_smiles' stays None — a canonical SMILES needs RDKit."""
+    page ratio in x (chemical.py:935-937); 'predicted_smiles' stays None — a canonical SMILES needs RDKit.
+    graph_smiles: True (opt-in; implies the packed path) = when RDKit is absent 'predicted_smiles' is the SMILES that the device
+    writes from the predicted graph (mnx_smiles_pack). That SMILES is valid but not canonical: two drawings of one molecule
+    can give two different strings, so compare them only after a toolkit has canonicalised both. It carries no stereo (no
+    '@', '/' or '\\': wedge bonds are written as plain single bonds), and an abbreviation or R-group stays a '*' atom
+    instead of being expanded. A molecule the writer refuses (more than 99 ring closures open at once, say) keeps None. The
+    default stays None; with RDKit present chem.py's path is unchanged."""
 
     image_format = "fp32"
     packed_results = False
     graph_molfile = False
+    graph_smiles = False
 
     def __init__(self, model_path, device=None, max_batch: int = 32, dtype: str = DEFAULT_DTYPE,
                  device_preprocess: bool = True, image_format: str = "fp32", packed_results: bool = False,
-                 graph_molfile: bool = False):
+                 graph_molfile: bool = False, graph_smiles: bool = False):
         if model_path is None:
             raise ValueError("molnextr(model_path): a checkpoint path is required (pass 'synthetic' explicitly for the "
                              "deterministic test checkpoint)")
@@ -269,6 +288,7 @@ class molnextr:
         self.image_format = image_format
         self.packed_results = bool(packed_results)
         self.graph_molfile = bool(graph_molfile)
+        self.graph_smiles = bool(graph_smiles)
         self.engine = Engine(states["encoder"], states["decoder"], device=device.index or 0, max_batch=max_batch,
                              dtype=dtype, image_format=image_format)
         self.input_size = args.input_size
@@ -444,8 +464,10 @@ class molnextr:
         group = (self.group_images // batch_size) * batch_size
         groups = [input_images[i:i + group] for i in range(0, len(input_images), group)]
         conf = {"compute_confidence": True} if return_confidence else {}
-        if self.packed_results or self.graph_molfile:
+        if self.packed_results or self.graph_molfile or self.graph_smiles:
             conf["packed"] = True
+        if self.graph_smiles:
+            conf["smiles"] = True
         gen = self._prefetched(groups)
         try:
             for x in gen:
@@ -486,6 +508,8 @@ class molnextr:
         for smiles, molfile, pred in zip(smiles_list, molblock_list, preds):
             if molfile is None:                               # no RDKit: the device's own molfile, when it was asked for
                 molfile = pred.get("molfile")
+            if smiles is None and not have_rdkit():           # no RDKit: the device's graph SMILES, when it was asked for
+                smiles = pred.get("graph_smiles")
             d = {"predicted_smiles": smiles, "predicted_molfile": molfile}
             if return_atoms_bonds:
                 c = pred["chartok_coords"]

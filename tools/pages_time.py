@@ -16,6 +16,9 @@ is part of the product path and no number is asserted.
 (m) (only when asked for: --part m) molfiles written on the device: one mnx_molfile_pack call over the packed tables of 1024
     images between two events, and predict_images from `--facade-pages` pages with molnextr(graph_molfile=True) against the
     packed facade without it; `--molfile-out FILE` writes the table to a file of its own.
+(s) (only when asked for: --part s) graph SMILES written on the device: one mnx_smiles_pack call over the packed tables of 1024
+    images between two events, alternating with one mnx_molfile_pack call over the same tables, with how many molecules were
+    written and how many refused per flag; `--smiles-out FILE` writes the table to a file of its own.
 The variants of a part alternate inside every repeat (A B A B ...), the table reports the median and the min .. max spread of
 each, and the spread of the fp32 path against itself is the yardstick for "not slower".
 """
@@ -217,6 +220,102 @@ def part_m(n, repeats, lines):
         m.engine.close()
 
 
+def druglike_records(n_mols, seed=0):
+    """Packed records of n_mols hand-made molecules of drug-like size: a chain of 20 .. 40 atoms, every seventh atom starting
+    an aromatic six-ring, a few hetero atoms and double bonds (about 1.1 bonds per atom) — (mols, atoms, bonds, text)"""
+    from molnextr_amd.engine import ATOM_DTYPE, BOND_DTYPE, MOL_DTYPE
+    rng = np.random.default_rng(seed)
+    mols = np.zeros(n_mols, MOL_DTYPE)
+    A, B, text = [], [], bytearray()
+    for b in range(n_mols):
+        n = int(rng.integers(20, 41))
+        syms, bonds = [b"C"] * n, {}
+        for k in range(n - 1):
+            bonds[(k, k + 1)] = 2 if rng.integers(0, 8) == 0 else 1
+        for r in range(0, n - 5, 7):
+            for k in range(r, r + 6):
+                syms[k] = b"n" if rng.integers(0, 6) == 0 else b"c"
+                bonds[(k, k + 1) if k < r + 5 else (r, r + 5)] = 4
+        for k in range(n):
+            if syms[k] == b"C" and rng.integers(0, 4) == 0:
+                syms[k] = (b"N", b"O", b"[C@@H]", b"Cl")[int(rng.integers(0, 4))]
+        own = b"".join(syms)
+        mols[b] = (len(A), n, len(B), len(bonds), len(text), len(own), 0, 0, 0.0)
+        off = 0
+        for k, sym in enumerate(syms):
+            A.append((off, len(sym), k, k % 64, k // 2 % 64, 0.0))
+            off += len(sym)
+        B += [(i, j, ty, 0, 0.0) for (i, j), ty in sorted(bonds.items())]
+        text += own
+    return mols, np.array(A, ATOM_DTYPE), np.array(B, BOND_DTYPE), bytes(text)
+
+
+def part_s(repeats, lines):
+    """Graph SMILES from the device: the three launches of one mnx_smiles_pack call over 1024 molecules between two events, next
+    to mnx_molfile_pack over the same tables (the tables stay on the device, the output buffers have the exact size) — on the
+    synthetic checkpoint's predictions, then on hand-made molecules of drug-like size."""
+    import ctypes as C
+    from molnextr_amd import engine as E
+    from molnextr_amd.model import molnextr
+    dev = torch.device("cuda", 0)
+    m = molnextr("synthetic", dev, max_batch=32, image_format="gray8", packed_results=True)
+    eng = m.engine
+    ptr = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
+    stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)      # noqa: E731
+
+    def measure(rec, what):
+        files, mol_data = eng.molfile_pack(rec)
+        recs, order, data = eng.smiles_pack(rec)
+        mols, atoms, bonds, text = rec["device"]
+        n, na, nb, nt = len(recs), len(rec["atoms"]), len(rec["bonds"]), len(rec["text"])
+        recs_d = torch.empty(n * 16, dtype=torch.uint8, device=dev)
+        order_d = torch.empty(max(na, 1), dtype=torch.int16, device=dev)
+        out_d = {"mnx_smiles_pack": torch.empty(max(len(data), 1), dtype=torch.uint8, device=dev),
+                 "mnx_molfile_pack": torch.empty(max(len(mol_data), 1), dtype=torch.uint8, device=dev)}
+        totals_d = torch.empty(2, dtype=torch.int32, device=dev)
+        calls = {"mnx_smiles_pack": lambda: eng.lib.mnx_smiles_pack(eng.h, ptr(mols), n, ptr(atoms), na, ptr(bonds), nb, ptr(text), nt,
+                                                                    ptr(recs_d), ptr(order_d), ptr(out_d["mnx_smiles_pack"]), len(data),
+                                                                    ptr(totals_d), stream()),
+                 "mnx_molfile_pack": lambda: eng.lib.mnx_molfile_pack(eng.h, ptr(mols), n, ptr(atoms), na, ptr(bonds), nb, ptr(text), nt, None,
+                                                                      ptr(recs_d), ptr(out_d["mnx_molfile_pack"]), len(mol_data),
+                                                                      ptr(totals_d), stream())}
+        want = {"mnx_smiles_pack": data, "mnx_molfile_pack": mol_data}
+        us = {k: [] for k in calls}
+        for i in range(repeats + 3):
+            for k, call in calls.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                a.record()
+                rc = call()
+                b.record()
+                torch.cuda.synchronize()
+                assert rc == 0 and out_d[k][:len(want[k])].cpu().numpy().tobytes() == want[k]
+                if i >= 3:
+                    us[k].append(a.elapsed_time(b) * 1000.0)
+        refused = (recs["flags"] & E.SMILES_REFUSED) != 0
+        lines.append(f"(s) one call over the packed tables of {n} {what} ({na} atoms, {nb} bonds): device us between two events around "
+                     "its three launches, the two calls alternating   median [min .. max]")
+        for k in calls:
+            lines.append(f"  {k:17s} {fmt(us[k])} us   -> {len(want[k])} bytes")
+        lines.append(f"  graph SMILES written for {int((~refused).sum())} of {n} molecules ({int(((~refused) & (recs['len'] == 0)).sum())} of "
+                     f"them empty), refused {int(refused.sum())}; ring bonds per molecule: median {int(np.median(recs['n_rings']))}, max "
+                     f"{int(recs['n_rings'].max())}; molfiles refused: {int((files['len'] == 0).sum())}")
+        for name in ("TOO_LARGE", "BEYOND_TABLES", "PSEUDO_ATOM", "TRUNCATED", "DUPLICATE_BOND", "RING_NUMBERS", "WEDGES_DROPPED", "UNKNOWN_BOND"):
+            lines.append(f"    flag {name:15s} {int((recs['flags'] & getattr(E, 'SMILES_' + name) != 0).sum()):5d} molecules")
+        sizes = sorted(int(k) for k in rec["mols"]["n_atoms"][~refused])
+        if sizes:
+            lines.append(f"    atoms of the written molecules: median {int(np.median(sizes))}, max {sizes[-1]}; the first string: "
+                         f"{data[recs['text0'][~refused][0]:][:recs['len'][~refused][0]].decode()[:120]}")
+
+    pages = [W.synthetic_page(i % 15) for i in range(1024)]
+    measure(eng.graph_pack(eng.predict(m._transform(pages), ref_batch=32), keep_device=True), "images of the synthetic checkpoint")
+    mols, atoms, bonds, text = druglike_records(1024)
+    up = lambda a: torch.frombuffer(bytearray(a if isinstance(a, bytes) else a.tobytes()) + bytearray(8), dtype=torch.uint8).to(dev)   # noqa: E731
+    measure({"mols": mols, "atoms": atoms, "bonds": bonds, "text": text, "device": (up(mols), up(atoms), up(bonds), up(text))},
+            "hand-made molecules of drug-like size")
+    m.engine.close()
+
+
 def part_c(eng, repeats, lines):
     from molnextr_amd.preprocess import normalise_gray
     dev = torch.device("cuda", eng.device)
@@ -249,6 +348,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--pack-out", default=None, help="write the dense-against-packed table of part b to this file")
     ap.add_argument("--molfile-out", default=None, help="write the table of part m to this file")
+    ap.add_argument("--smiles-out", default=None, help="write the table of part s to this file")
     ap.add_argument("--pack-only", type=int, default=0, help="run this many mnx_graph_pack calls over 1024 images and exit")
     args = ap.parse_args()
     parts = args.part.split(",")
@@ -282,6 +382,13 @@ def main():
         if args.molfile_out:
             os.makedirs(os.path.dirname(os.path.abspath(args.molfile_out)), exist_ok=True)
             with open(args.molfile_out, "w") as f:
+                f.write("\n".join([lines[0]] + lines[first:]) + "\n")
+    if "s" in parts:
+        first = len(lines)
+        part_s(args.repeats, lines)
+        if args.smiles_out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.smiles_out)), exist_ok=True)
+            with open(args.smiles_out, "w") as f:
                 f.write("\n".join([lines[0]] + lines[first:]) + "\n")
     text = "\n".join(lines)
     print(text)
