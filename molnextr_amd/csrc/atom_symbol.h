@@ -1,9 +1,12 @@
-// atom_symbol.h — one atom's symbol read as the reference's _convert_graph_to_smiles reads it (chemical.py:886-903): brackets
-// stripped, R-group table, abbreviation table, and only then the whole symbol through the bracket-atom grammar. Behind the
-// molfile writer (molfile.hip) and the SMILES writer (smiles.hip): one definition, so the two cannot drift apart (internal).
+// atom_symbol.h — what the molfile writer (molfile.hip) and the SMILES writer (smiles.hip) do alike before their own work: one
+// atom's symbol read as the reference's _convert_graph_to_smiles reads it (chemical.py:886-903: brackets stripped, R-group table,
+// abbreviation table, and only then the whole symbol through the bracket-atom grammar), and behind it the admission of one molecule
+// of the packed tables and the loop over its atoms. One definition, so the two cannot drift apart (internal). What the writers
+// decide differently stays in their kernels: the bond loops, and with them a bond from an atom to itself.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../../include/molnextr_hip.h"
 #include "dec_types.h"
 
 namespace mnx {
@@ -160,6 +163,52 @@ __device__ __forceinline__ unsigned interpret_atom(const SymbolTables* __restric
     w |= (num ? CLS_RNUM : CLS_PSEUDO) | (unsigned)(15) << 8 | num << 13 | (unsigned)al << 23 | (strip ? 1u << 30 : 0u);
     *sym = 'R' | (unsigned)(num ? '#' : ' ') << 8 | (unsigned)' ' << 16;
     return w;
+}
+
+// ---- one molecule of the packed tables (PackedTables, dec_types.h) ----
+// the flag bits that mean the same in both writers' records (molnextr_hip.h)
+constexpr unsigned PT_TOO_LARGE = MNX_MOLFILE_TOO_LARGE, PT_BEYOND_TABLES = MNX_MOLFILE_BEYOND_TABLES;
+constexpr unsigned PT_PSEUDO_ATOM = MNX_MOLFILE_PSEUDO_ATOM, PT_TRUNCATED = MNX_MOLFILE_TRUNCATED;
+static_assert(PT_TOO_LARGE == MNX_SMILES_TOO_LARGE && PT_BEYOND_TABLES == MNX_SMILES_BEYOND_TABLES &&
+              PT_PSEUDO_ATOM == MNX_SMILES_PSEUDO_ATOM && PT_TRUNCATED == MNX_SMILES_TRUNCATED, "one meaning, one value");
+
+// Molecule b: its record, its atoms and bonds, and in `flags` PT_TRUNCATED (a copy of MNX_MOL_TRUNCATED), PT_TOO_LARGE (more than
+// the 999 atoms or bonds that three digits count) and PT_BEYOND_TABLES (its records end behind a table). With one of the last two
+// the molecule is refused and A and B are not read.
+struct Molecule {
+    mnx_mol m;
+    const mnx_atom* A;
+    const mnx_bond* B;
+    unsigned flags;
+};
+
+__device__ __forceinline__ Molecule admit_molecule(const PackedTables& t, int b) {
+    const mnx_mol m = t.mols[b];
+    unsigned flags = (m.flags & MNX_MOL_TRUNCATED) ? PT_TRUNCATED : 0u;
+    if (m.n_atoms > 999u || m.n_bonds > 999u) flags |= PT_TOO_LARGE;
+    if ((unsigned long long)m.atom0 + m.n_atoms > t.n_atom_records || (unsigned long long)m.bond0 + m.n_bonds > t.n_bond_records ||
+        (unsigned long long)m.text0 + m.smiles_len > t.n_text_bytes)
+        flags |= PT_BEYOND_TABLES;
+    return {m, t.atoms + m.atom0, t.bonds + m.bond0, flags};
+}
+
+// Every atom of an admitted molecule, by NT threads: info[a] its interpretation, sym[a] the bytes of its symbol column, zeros
+// for n_atoms <= a < MAX. Returns whether one of this thread's atoms has a symbol that ends behind the text table.
+template <int MAX, int NT>
+__device__ __forceinline__ int interpret_atoms(const PackedTables& t, const SymbolTables* __restrict__ st, const Molecule& mol,
+                                               unsigned* info, unsigned* sym) {
+    int bad = 0;
+    for (int a = threadIdx.x; a < MAX; a += NT) {
+        unsigned w = 0, s3 = 0;
+        if (a < (int)mol.m.n_atoms) {
+            const unsigned s0 = mol.A[a].sym0, sl = mol.A[a].sym_len;
+            if ((unsigned long long)mol.m.text0 + s0 + sl > t.n_text_bytes) bad = 1;
+            else w = interpret_atom(st, t.text + mol.m.text0 + s0, (int)sl, &s3);
+        }
+        info[a] = w;
+        sym[a] = s3;
+    }
+    return bad;
 }
 
 }  // namespace mnx

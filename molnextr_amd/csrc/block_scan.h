@@ -1,5 +1,6 @@
 // block_scan.h — the workgroup prefix scan of the count / scan / fill post-passes (graph_pack.hip, molfile.hip, smiles.hip)
-// and the scan of the text writers over their molecules: one definition (internal).
+// and the scan of the text writers over their molecules: one definition (internal). What the text writers share in front of
+// their scans, per molecule, is in atom_symbol.h.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -196,18 +196,22 @@ struct SymbolTables {
     unsigned char kind[512];       // 1 R-group, 2 abbreviation
     unsigned char name[512][16];
 };
-// molfile.hip: the packed tables of n molecules as V2000 molfiles behind one another in `out` (mnx_molfile_pack): count, scan
-// and fill, three launches on s
-hipError_t molfile_pack_enqueue(const SymbolTables* st_dev, const mnx_mol* mols, int n, const mnx_atom* atoms,
-                                unsigned n_atom_records, const mnx_bond* bonds, unsigned n_bond_records, const char* text,
-                                unsigned n_text_bytes, const int* scale, int coord_bins, mnx_molfile* files, char* out,
-                                unsigned out_cap, unsigned* totals, hipStream_t s);
-// smiles.hip: the packed tables of n molecules as graph SMILES behind one another in `out`, the atoms' written positions in
-// `order` (may be null) (mnx_smiles_pack): count, scan and fill, three launches on s
-hipError_t smiles_pack_enqueue(const SymbolTables* st_dev, const mnx_mol* mols, int n, const mnx_atom* atoms,
-                               unsigned n_atom_records, const mnx_bond* bonds, unsigned n_bond_records, const char* text,
-                               unsigned n_text_bytes, mnx_smiles* recs, unsigned short* order, char* out, unsigned out_cap,
-                               unsigned* totals, hipStream_t s);
+// the packed tables of mnx_graph_pack as mnx_molfile_pack and mnx_smiles_pack receive them: each table with the number of records
+// the caller vouches for (a molecule that points beyond them is refused, atom_symbol.h). Passed to kernels by value.
+struct PackedTables {
+    const mnx_mol* mols;        int n;
+    const mnx_atom* atoms;      unsigned n_atom_records;
+    const mnx_bond* bonds;      unsigned n_bond_records;
+    const unsigned char* text;  unsigned n_text_bytes;
+};
+// molfile.hip: the molecules of t as V2000 molfiles behind one another in `out` (mnx_molfile_pack): count, scan and fill, three
+// launches on s
+hipError_t molfile_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, const int* scale, int coord_bins,
+                                mnx_molfile* files, char* out, unsigned out_cap, unsigned* totals, hipStream_t s);
+// smiles.hip: the molecules of t as graph SMILES behind one another in `out`, the atoms' written positions in `order` (may be
+// null) (mnx_smiles_pack): count, scan and fill, three launches on s
+hipError_t smiles_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, mnx_smiles* recs, unsigned short* order,
+                               char* out, unsigned out_cap, unsigned* totals, hipStream_t s);
 hipError_t edges_enqueue(const DecWeights& w, const DecBuffers& bf, const float* hidden, const int* slot_map,
                          const int* atom_idx, const int* n_atoms, int B, int kmax, int row_stride_T,
                          unsigned char* edges, double* scores, hipStream_t s);

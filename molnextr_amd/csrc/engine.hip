@@ -1358,46 +1358,44 @@ int mnx_set_symbol_tables(mnx_engine* h, const char* bytes, const uint32_t* offs
     return MNX_OK;
 }
 
+// What mnx_molfile_pack and mnx_smiles_pack test before they launch, in the order in which a call refused for two reasons
+// reports them. The entry point tests its own pointers (outs_null, outs_skew); `aligned` is how its alignment message ends.
+static int check_packed_tables(mnx_engine* h, const char* fn, const PackedTables& t, bool outs_null, bool outs_skew,
+                               const char* aligned) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    auto bad = [&](const std::string& m) { h->err = std::string(fn) + ": " + m; return MNX_ERR_INVALID_ARG; };
+    if (!t.mols || (!t.atoms && t.n_atom_records) || (!t.bonds && t.n_bond_records) || (!t.text && t.n_text_bytes) || outs_null)
+        return bad("null pointer");
+    if (t.n < 1 || t.n > 65536) return bad("1 <= n <= 65536 required");
+    if ((((uintptr_t)t.mols | (uintptr_t)t.atoms | (uintptr_t)t.bonds) & 7) || outs_skew)
+        return bad(std::string("mols, atoms and bonds must be 8-byte aligned, ") + aligned);
+    if (!h->have_st) return bad("call mnx_set_symbol_tables first");
+    return MNX_OK;
+}
+
 int mnx_molfile_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
                      const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes,
                      const int32_t* scale, mnx_molfile* files, char* out, uint32_t out_cap, uint32_t* totals, void* stream) {
-    if (!h) return MNX_ERR_INVALID_ARG;
-    if (!mols || !files || !totals || (!atoms && n_atom_records) || (!bonds && n_bond_records) || (!text && n_text_bytes) ||
-        (!out && out_cap)) {
-        h->err = "mnx_molfile_pack: null pointer";
-        return MNX_ERR_INVALID_ARG;
-    }
-    if (n < 1 || n > 65536) { h->err = "mnx_molfile_pack: 1 <= n <= 65536 required"; return MNX_ERR_INVALID_ARG; }
-    if (((uintptr_t)mols | (uintptr_t)atoms | (uintptr_t)bonds) & 7 || (((uintptr_t)files | (uintptr_t)totals | (uintptr_t)scale) & 3)) {
-        h->err = "mnx_molfile_pack: mols, atoms and bonds must be 8-byte aligned, files, scale and totals 4-byte";
-        return MNX_ERR_INVALID_ARG;
-    }
-    if (!h->have_st) { h->err = "mnx_molfile_pack: call mnx_set_symbol_tables first"; return MNX_ERR_INVALID_ARG; }
+    const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
+    if (int rc = check_packed_tables(h, "mnx_molfile_pack", t, !files || !totals || (!out && out_cap),
+                                     (((uintptr_t)files | (uintptr_t)totals | (uintptr_t)scale) & 3) != 0, "files, scale and totals 4-byte"))
+        return rc;
     if (h->cfg.coord_bins < 2) { h->err = "mnx_molfile_pack: cfg.coord_bins must be at least 2"; return MNX_ERR_INVALID_ARG; }
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, molfile_pack_enqueue(h->st_dev, mols, n, atoms, n_atom_records, bonds, n_bond_records, text, n_text_bytes, scale,
-                                   h->cfg.coord_bins, files, out, out_cap, totals, (hipStream_t)stream));
+    HIPCHK(h, molfile_pack_enqueue(h->st_dev, t, scale, h->cfg.coord_bins, files, out, out_cap, totals, (hipStream_t)stream));
     return MNX_OK;
 }
 
 int mnx_smiles_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
                     const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_smiles* recs,
                     uint16_t* order, char* out, uint32_t out_cap, uint32_t* totals, void* stream) {
-    if (!h) return MNX_ERR_INVALID_ARG;
-    if (!mols || !recs || !totals || (!atoms && n_atom_records) || (!bonds && n_bond_records) || (!text && n_text_bytes) ||
-        (!out && out_cap)) {
-        h->err = "mnx_smiles_pack: null pointer";
-        return MNX_ERR_INVALID_ARG;
-    }
-    if (n < 1 || n > 65536) { h->err = "mnx_smiles_pack: 1 <= n <= 65536 required"; return MNX_ERR_INVALID_ARG; }
-    if (((uintptr_t)mols | (uintptr_t)atoms | (uintptr_t)bonds) & 7 || (((uintptr_t)recs | (uintptr_t)totals) & 3) || ((uintptr_t)order & 1)) {
-        h->err = "mnx_smiles_pack: mols, atoms and bonds must be 8-byte aligned, recs and totals 4-byte, order 2-byte";
-        return MNX_ERR_INVALID_ARG;
-    }
-    if (!h->have_st) { h->err = "mnx_smiles_pack: call mnx_set_symbol_tables first"; return MNX_ERR_INVALID_ARG; }
+    const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
+    if (int rc = check_packed_tables(h, "mnx_smiles_pack", t, !recs || !totals || (!out && out_cap),
+                                     (((uintptr_t)recs | (uintptr_t)totals) & 3) != 0 || ((uintptr_t)order & 1) != 0,
+                                     "recs and totals 4-byte, order 2-byte"))
+        return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, smiles_pack_enqueue(h->st_dev, mols, n, atoms, n_atom_records, bonds, n_bond_records, text, n_text_bytes, recs, order,
-                                  out, out_cap, totals, (hipStream_t)stream));
+    HIPCHK(h, smiles_pack_enqueue(h->st_dev, t, recs, order, out, out_cap, totals, (hipStream_t)stream));
     return MNX_OK;
 }
 

@@ -2,6 +2,7 @@
 // that _convert_graph_to_smiles (reference chemical.py:880-926) builds with RDKit — atoms by symbol class, bonds with their
 // wedges, the begin atom of a wedge moved to the chiral centre (chemical.py:262-273) — written as text on the device.
 //   count  one workgroup per molecule: symbol classes and the molfile's length -> files[b].len / flags
+//          (which molecules are admitted and how an atom is read: atom_symbol.h, shared with smiles.hip)
 //   scan   exclusive scan of the lengths over the molecules -> files[b].text0, totals
 //   fill   one workgroup per molecule: the bytes behind text0
 // Every line of a V2000 block has a fixed width (69-byte atom lines, 12-byte bond lines, property lines of 8 entries), so
@@ -45,56 +46,43 @@ static_assert(sizeof(MF_HEAD) == HEADER_BYTES + COUNTS_BYTES + 1, "header and co
 
 template <bool FILL>
 __global__ __launch_bounds__(MF_THREADS) void molfile_kernel(
-        const mnx_mol* __restrict__ mols, const mnx_atom* __restrict__ atoms, unsigned n_atom_records,
-        const mnx_bond* __restrict__ bonds, unsigned n_bond_records, const unsigned char* __restrict__ text,
-        unsigned n_text_bytes, const SymbolTables* __restrict__ st, const int* __restrict__ scale, int den,
+        const PackedTables t, const SymbolTables* __restrict__ st, const int* __restrict__ scale, int den,
         mnx_molfile* __restrict__ files, char* __restrict__ out, unsigned out_cap) {
     __shared__ unsigned info[MF_MAX], sym[MF_MAX];
     __shared__ unsigned aoff[MF_MAX], coff[MF_MAX];     // per atom: bytes of the alias lines / packed entry counts in front of it
     __shared__ unsigned bnd[FILL ? MF_MAX : 1];         // fill: i | j << 10 | order << 20 | aromatic << 22, for the valence sums
     __shared__ unsigned scan[2 * MF_THREADS];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const mnx_mol m = mols[b];
+    const Molecule mol = admit_molecule(t, b);
+    const mnx_mol& m = mol.m;
+    const unsigned truncated = mol.flags & PT_TRUNCATED;
+    auto record = [&](unsigned len, unsigned flags) {   // count's result; len 0 = refused
+        if (tid == 0) { files[b].len = len; files[b].flags = flags; files[b].reserved = 0; }
+    };
     unsigned text0 = 0;
     if (FILL) {
         const mnx_molfile f = files[b];
         if (f.len == 0) return;                         // refused by count (the same for every thread)
         text0 = f.text0;
-    } else {
-        unsigned flags = (m.flags & MNX_MOL_TRUNCATED) ? 8u : 0u;
-        if (m.n_atoms > 999u || m.n_bonds > 999u) flags |= 1u;
-        if ((unsigned long long)m.atom0 + m.n_atoms > n_atom_records || (unsigned long long)m.bond0 + m.n_bonds > n_bond_records ||
-            (unsigned long long)m.text0 + m.smiles_len > n_text_bytes)
-            flags |= 2u;
-        if (flags & 3u) {
-            if (tid == 0) { files[b].len = 0; files[b].flags = flags; files[b].reserved = 0; }
-            return;
-        }
+    } else if (mol.flags & (PT_TOO_LARGE | PT_BEYOND_TABLES)) {
+        record(0, mol.flags);
+        return;
     }
     const int na = (int)m.n_atoms, nb = (int)m.n_bonds;
-    const mnx_atom* A = atoms + m.atom0;
-    const mnx_bond* B = bonds + m.bond0;
+    const mnx_atom* A = mol.A;
+    const mnx_bond* B = mol.B;
+    const unsigned char* text = t.text;
 
     // ---- every atom's interpretation; a record that points beyond its table refuses the molecule ----
-    int bad = 0;
-    for (int a = tid; a < MF_MAX; a += MF_THREADS) {
-        unsigned w = 0, s3 = 0;
-        if (a < na) {
-            const unsigned s0 = A[a].sym0, sl = A[a].sym_len;
-            if ((unsigned long long)m.text0 + s0 + sl > n_text_bytes) bad = 1;
-            else w = interpret_atom(st, text + m.text0 + s0, (int)sl, &s3);
-        }
-        info[a] = w;
-        sym[a] = s3;
-    }
+    int bad = interpret_atoms<MF_MAX, MF_THREADS>(t, st, mol, info, sym);
     for (int k = tid; k < nb; k += MF_THREADS) {
         const unsigned i = B[k].i, j = B[k].j, ty = B[k].type;
-        if (i >= (unsigned)na || j >= (unsigned)na) bad = 1;
+        if (i >= (unsigned)na || j >= (unsigned)na) bad = 1;        // i == j is written as it stands; the SMILES writer refuses it
         if (FILL) bnd[k] = (i & 1023u) | (j & 1023u) << 10 | (ty <= 3 ? ty : (ty == 5 || ty == 6) ? 1u : 0u) << 20 | (ty == 4 ? 1u : 0u) << 22;
     }
     if (!FILL) {
         if (__syncthreads_or(bad)) {
-            if (tid == 0) { files[b].len = 0; files[b].flags = ((m.flags & MNX_MOL_TRUNCATED) ? 8u : 0u) | 2u; files[b].reserved = 0; }
+            record(0, truncated | PT_BEYOND_TABLES);
             return;
         }
     } else {
@@ -127,11 +115,7 @@ __global__ __launch_bounds__(MF_THREADS) void molfile_kernel(
     const unsigned off_end = off_rgp + prop_bytes(n_rgp);
     if (!FILL) {
         pseudo = __syncthreads_or(pseudo);
-        if (tid == 0) {
-            files[b].len = off_end + END_BYTES;
-            files[b].flags = ((m.flags & MNX_MOL_TRUNCATED) ? 8u : 0u) | (pseudo ? 4u : 0u);
-            files[b].reserved = 0;
-        }
+        record(off_end + END_BYTES, truncated | (pseudo ? PT_PSEUDO_ATOM : 0u));
         return;
     }
 #pragma unroll
@@ -259,16 +243,12 @@ __global__ __launch_bounds__(MF_THREADS) void molfile_kernel(
 
 }  // namespace
 
-hipError_t molfile_pack_enqueue(const SymbolTables* st_dev, const mnx_mol* mols, int n, const mnx_atom* atoms,
-                                unsigned n_atom_records, const mnx_bond* bonds, unsigned n_bond_records, const char* text,
-                                unsigned n_text_bytes, const int* scale, int coord_bins, mnx_molfile* files, char* out,
-                                unsigned out_cap, unsigned* totals, hipStream_t s) {
+hipError_t molfile_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, const int* scale, int coord_bins,
+                                mnx_molfile* files, char* out, unsigned out_cap, unsigned* totals, hipStream_t s) {
     const int den = coord_bins - 1;
-    hipLaunchKernelGGL(molfile_kernel<false>, dim3(n), dim3(MF_THREADS), 0, s, mols, atoms, n_atom_records, bonds,
-                       n_bond_records, (const unsigned char*)text, n_text_bytes, st_dev, scale, den, files, out, out_cap);
-    hipLaunchKernelGGL(text_scan_kernel<mnx_molfile>, dim3(1), dim3(TEXT_SCAN_THREADS), 0, s, files, n, out_cap, totals);
-    hipLaunchKernelGGL(molfile_kernel<true>, dim3(n), dim3(MF_THREADS), 0, s, mols, atoms, n_atom_records, bonds,
-                       n_bond_records, (const unsigned char*)text, n_text_bytes, st_dev, scale, den, files, out, out_cap);
+    hipLaunchKernelGGL(molfile_kernel<false>, dim3(t.n), dim3(MF_THREADS), 0, s, t, st_dev, scale, den, files, out, out_cap);
+    hipLaunchKernelGGL(text_scan_kernel<mnx_molfile>, dim3(1), dim3(TEXT_SCAN_THREADS), 0, s, files, t.n, out_cap, totals);
+    hipLaunchKernelGGL(molfile_kernel<true>, dim3(t.n), dim3(MF_THREADS), 0, s, t, st_dev, scale, den, files, out, out_cap);
     return hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
-// smiles.hip — a SMILES of the predicted graph from the packed molecule tables of mnx_graph_pack (mnx_smiles_pack): the atoms as
-// atom_symbol.h reads them, the bonds of the bond head, written by a depth-first walk after the OpenSMILES grammar. Valid, not
-// canonical (the walk's order is fixed by the atom indices), no stereo, pseudo-atoms as '*'.
+// smiles.hip — a SMILES of the predicted graph from the packed molecule tables of mnx_graph_pack (mnx_smiles_pack): the molecules
+// that atom_symbol.h admits and the atoms as it reads them (shared with molfile.hip), the bonds of the bond head, written by a
+// depth-first walk after the OpenSMILES grammar. Valid, not canonical (the walk's order is fixed by the atom indices), no stereo,
+// pseudo-atoms as '*'.
 //   count  one workgroup per molecule: the walk and the length of its string -> recs[b].len / flags / n_rings
 //   scan   exclusive scan of the lengths over the molecules -> recs[b].text0, totals
 //   fill   one workgroup per molecule: the walk again, the bytes behind text0 and the atoms' positions in `order`
@@ -26,7 +27,7 @@ constexpr int SM_MAX = 1024;             // atoms held in LDS (999 at most)
 constexpr int SM_PER = SM_MAX / SM_THREADS;
 constexpr int SM_SLOTS = 2 * SM_MAX;     // neighbour-list entries: two per bond (999 bonds at most)
 constexpr unsigned NONE = 0xFFFFu;
-constexpr unsigned REFUSED = MNX_SMILES_TOO_LARGE | MNX_SMILES_BEYOND_TABLES | MNX_SMILES_DUPLICATE_BOND | MNX_SMILES_RING_NUMBERS;
+constexpr unsigned REFUSED = PT_TOO_LARGE | PT_BEYOND_TABLES | MNX_SMILES_DUPLICATE_BOND | MNX_SMILES_RING_NUMBERS;
 
 // ---- one entry of a neighbour list ----
 //   bits 0-9 the neighbour, bits 10-12 the bond's written class, bits 13-22 the atom that owns the list, bit 23 a bond of the
@@ -83,9 +84,7 @@ __device__ __forceinline__ void put_atom(unsigned w, unsigned el, Put put) {
 
 template <bool FILL>
 __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
-        const mnx_mol* __restrict__ mols, const mnx_atom* __restrict__ atoms, unsigned n_atom_records,
-        const mnx_bond* __restrict__ bonds, unsigned n_bond_records, const unsigned char* __restrict__ text,
-        unsigned n_text_bytes, const SymbolTables* __restrict__ st, mnx_smiles* __restrict__ recs,
+        const PackedTables t, const SymbolTables* __restrict__ st, mnx_smiles* __restrict__ recs,
         unsigned short* __restrict__ order, char* __restrict__ out, unsigned out_cap) {
     __shared__ unsigned info[SM_MAX], elem[SM_MAX];
     __shared__ unsigned off[SM_MAX + 1], cnt[SM_MAX];     // an atom's list is [off[a], off[a + 1]); cnt: degrees, then fill cursors
@@ -98,45 +97,34 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
     __shared__ unsigned char paren[SM_MAX], rnum[SM_SLOTS];
     __shared__ unsigned walk[2];                          // components, 1 = more than 99 ring numbers in use
     const int b = blockIdx.x, tid = threadIdx.x;
-    const mnx_mol m = mols[b];
-    const unsigned base_flags = (m.flags & MNX_MOL_TRUNCATED) ? MNX_SMILES_TRUNCATED : 0u;
+    const Molecule mol = admit_molecule(t, b);
+    const mnx_mol& m = mol.m;
+    const unsigned base_flags = mol.flags & PT_TRUNCATED;
+    auto record = [&](unsigned len, unsigned flags, unsigned n_rings) {     // count's result; len 0 with a bit of REFUSED = refused
+        if (tid == 0) { recs[b].len = len; recs[b].flags = flags; recs[b].n_rings = n_rings; }
+    };
     unsigned text0 = 0;
     if (FILL) {
         const mnx_smiles r = recs[b];
         if (r.len == 0) {                                 // no string (the same for every thread): its atoms get no position
             if (order && (r.flags & REFUSED))
-                for (unsigned a = tid; a < m.n_atoms && (unsigned long long)m.atom0 + a < n_atom_records; a += SM_THREADS)
+                for (unsigned a = tid; a < m.n_atoms && (unsigned long long)m.atom0 + a < t.n_atom_records; a += SM_THREADS)
                     order[m.atom0 + a] = (unsigned short)NONE;
             return;
         }
         text0 = r.text0;
-    } else {
-        unsigned flags = base_flags;
-        if (m.n_atoms > 999u || m.n_bonds > 999u) flags |= MNX_SMILES_TOO_LARGE;
-        if ((unsigned long long)m.atom0 + m.n_atoms > n_atom_records || (unsigned long long)m.bond0 + m.n_bonds > n_bond_records ||
-            (unsigned long long)m.text0 + m.smiles_len > n_text_bytes)
-            flags |= MNX_SMILES_BEYOND_TABLES;
-        if (flags & (MNX_SMILES_TOO_LARGE | MNX_SMILES_BEYOND_TABLES)) {
-            if (tid == 0) { recs[b].len = 0; recs[b].flags = flags; recs[b].n_rings = 0; }
-            return;
-        }
+    } else if (mol.flags & (PT_TOO_LARGE | PT_BEYOND_TABLES)) {
+        record(0, mol.flags, 0);
+        return;
     }
     const int na = (int)m.n_atoms, nb = (int)m.n_bonds;
-    const mnx_atom* A = atoms + m.atom0;
-    const mnx_bond* B = bonds + m.bond0;
+    const mnx_bond* B = mol.B;
 
-    // ---- every atom's interpretation, every bond's degree counts; a record that points beyond its table refuses the molecule ----
-    int bad = 0, pseudo = 0, wedge = 0, any = 0;
-    for (int a = tid; a < SM_MAX; a += SM_THREADS) {
-        unsigned w = 0, s3 = 0;
-        if (a < na) {
-            const unsigned s0 = A[a].sym0, sl = A[a].sym_len;
-            if ((unsigned long long)m.text0 + s0 + sl > n_text_bytes) bad = 1;
-            else w = interpret_atom(st, text + m.text0 + s0, (int)sl, &s3);
-            pseudo |= info_cls(w) != CLS_ATOM;
-        }
-        info[a] = w;
-        elem[a] = s3;
+    // ---- every atom's interpretation and the walk's own per-atom state, every bond's degree counts; a record that points
+    //      beyond its table refuses the molecule ----
+    int bad = interpret_atoms<SM_MAX, SM_THREADS>(t, st, mol, info, elem), pseudo = 0, wedge = 0, any = 0;
+    for (int a = tid; a < SM_MAX; a += SM_THREADS) {      // info[a] is this thread's own entry: no barrier in between
+        pseudo |= a < na && info_cls(info[a]) != CLS_ATOM;
         cnt[a] = 0;
         pos[a] = (unsigned short)NONE;
         closes[a] = 0;
@@ -145,14 +133,14 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
     __syncthreads();
     for (int k = tid; k < nb; k += SM_THREADS) {
         const unsigned i = B[k].i, j = B[k].j, ty = B[k].type;
-        if (i >= (unsigned)na || j >= (unsigned)na || i == j) { bad = 1; continue; }
+        if (i >= (unsigned)na || j >= (unsigned)na || i == j) { bad = 1; continue; }     // i == j: the molfile writer writes it
         wedge |= ty == 5 || ty == 6;
         any |= ty < 1 || ty > 6;
         atomicAdd(&cnt[i], 1u);                           // a count does not depend on the order of its increments
         atomicAdd(&cnt[j], 1u);
     }
     if (__syncthreads_or(bad)) {                          // (count refuses; fill never comes here: count left len = 0)
-        if (!FILL && tid == 0) { recs[b].len = 0; recs[b].flags = base_flags | MNX_SMILES_BEYOND_TABLES; recs[b].n_rings = 0; }
+        if (!FILL) record(0, base_flags | PT_BEYOND_TABLES, 0);
         return;
     }
     if (!FILL) {
@@ -239,11 +227,7 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
     __syncthreads();
     const unsigned n_rings = (unsigned)nb + walk[0] - (unsigned)na;
     if (dup) {                                            // (count refuses; fill never comes here)
-        if (!FILL && tid == 0) {
-            recs[b].len = 0;
-            recs[b].flags = base_flags | (pseudo ? MNX_SMILES_PSEUDO_ATOM : 0u) | MNX_SMILES_DUPLICATE_BOND;
-            recs[b].n_rings = n_rings;
-        }
+        if (!FILL) record(0, base_flags | (pseudo ? PT_PSEUDO_ATOM : 0u) | MNX_SMILES_DUPLICATE_BOND, n_rings);
         return;
     }
 
@@ -293,11 +277,7 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
     }
     __syncthreads();
     if (walk[1]) {                                        // (count refuses; fill never comes here)
-        if (!FILL && tid == 0) {
-            recs[b].len = 0;
-            recs[b].flags = base_flags | (pseudo ? MNX_SMILES_PSEUDO_ATOM : 0u) | MNX_SMILES_RING_NUMBERS;
-            recs[b].n_rings = n_rings;
-        }
+        if (!FILL) record(0, base_flags | (pseudo ? PT_PSEUDO_ATOM : 0u) | MNX_SMILES_RING_NUMBERS, n_rings);
         return;
     }
 
@@ -344,12 +324,8 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
     }
     unsigned at_byte = block_scan_excl<SM_THREADS>(sum, scan, &total);
     if (!FILL) {
-        if (tid == 0) {
-            recs[b].len = total;
-            recs[b].flags = base_flags | (pseudo ? MNX_SMILES_PSEUDO_ATOM : 0u) | (wedge ? MNX_SMILES_WEDGES_DROPPED : 0u) |
-                            (any ? MNX_SMILES_UNKNOWN_BOND : 0u);
-            recs[b].n_rings = n_rings;
-        }
+        record(total, base_flags | (pseudo ? PT_PSEUDO_ATOM : 0u) | (wedge ? MNX_SMILES_WEDGES_DROPPED : 0u) |
+                          (any ? MNX_SMILES_UNKNOWN_BOND : 0u), n_rings);
         return;
     }
 #pragma unroll
@@ -368,15 +344,11 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
 
 }  // namespace
 
-hipError_t smiles_pack_enqueue(const SymbolTables* st_dev, const mnx_mol* mols, int n, const mnx_atom* atoms,
-                               unsigned n_atom_records, const mnx_bond* bonds, unsigned n_bond_records, const char* text,
-                               unsigned n_text_bytes, mnx_smiles* recs, unsigned short* order, char* out, unsigned out_cap,
-                               unsigned* totals, hipStream_t s) {
-    hipLaunchKernelGGL(smiles_kernel<false>, dim3(n), dim3(SM_THREADS), 0, s, mols, atoms, n_atom_records, bonds, n_bond_records,
-                       (const unsigned char*)text, n_text_bytes, st_dev, recs, order, out, out_cap);
-    hipLaunchKernelGGL(text_scan_kernel<mnx_smiles>, dim3(1), dim3(TEXT_SCAN_THREADS), 0, s, recs, n, out_cap, totals);
-    hipLaunchKernelGGL(smiles_kernel<true>, dim3(n), dim3(SM_THREADS), 0, s, mols, atoms, n_atom_records, bonds, n_bond_records,
-                       (const unsigned char*)text, n_text_bytes, st_dev, recs, order, out, out_cap);
+hipError_t smiles_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, mnx_smiles* recs, unsigned short* order,
+                               char* out, unsigned out_cap, unsigned* totals, hipStream_t s) {
+    hipLaunchKernelGGL(smiles_kernel<false>, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, order, out, out_cap);
+    hipLaunchKernelGGL(text_scan_kernel<mnx_smiles>, dim3(1), dim3(TEXT_SCAN_THREADS), 0, s, recs, t.n, out_cap, totals);
+    hipLaunchKernelGGL(smiles_kernel<true>, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, order, out, out_cap);
     return hipGetLastError();
 }
 

@@ -840,6 +840,37 @@ class Engine:
             rec["device"] = (mols, atoms, bonds, text)
         return rec
 
+    def _packed_tables(self, rec: dict):
+        """graph_pack's records -> (the four tables as device tensors: those graph_pack(keep_device=True) left, or an upload;
+        the leading arguments mols, n, atoms, na, bonds, nb, text, nt of a writer, None for an empty table)"""
+        dev = torch.device("cuda", self.device)
+
+        def up(a):
+            raw = a if isinstance(a, (bytes, bytearray)) else np.ascontiguousarray(a).tobytes()
+            return torch.frombuffer(bytearray(raw) or bytearray(8), dtype=torch.uint8).to(dev)
+
+        tables = rec.get("device") or tuple(up(rec[k]) for k in ("mols", "atoms", "bonds", "text"))
+        args = [_ptr(tables[0]), len(rec["mols"])]
+        for t, k in zip(tables[1:], (len(rec["atoms"]), len(rec["bonds"]), len(rec["text"]))):
+            args += [_ptr(t) if k else None, k]
+        return tables, args
+
+    def _sized_text(self, fn: str, head, cap: int) -> bytes:
+        """One text writer, lib.<fn>(h, *head, out, out_cap, totals, stream), at capacity `cap` and at most once more with the
+        size `totals` reports: the bytes it wrote."""
+        dev = torch.device("cuda", self.device)
+        totals = torch.empty(2, dtype=torch.int32, device=dev)
+        for attempt in range(2):
+            out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+            self._check(getattr(self.lib, fn)(self.h, *head, _ptr(out), cap, _ptr(totals), _stream()), fn)
+            tot = totals.cpu().numpy().view(np.uint32)
+            if not tot[1]:
+                break
+            if attempt:
+                raise MnxError(f"{fn}: capacity {cap} too small after sizing it from totals {tot.tolist()}")
+            cap = int(tot[0])
+        return out[:int(tot[0])].cpu().numpy().tobytes()
+
     MOLFILE_GUESS = 4096      # first capacity of molfile_pack per molecule (30 atoms and 30 bonds take about 2.6 KB)
 
     def molfile_pack(self, rec: dict, scale=None, cap: Optional[int] = None):
@@ -849,33 +880,14 @@ class Engine:
         go back to the device as they are (or stay there: graph_pack(keep_device=True)); starts from MOLFILE_GUESS bytes per
         molecule (or cap) and repeats at most once with the size `totals` reports."""
         dev = torch.device("cuda", self.device)
-
-        def up(a):
-            raw = a if isinstance(a, (bytes, bytearray)) else np.ascontiguousarray(a).tobytes()
-            return torch.frombuffer(bytearray(raw) or bytearray(8), dtype=torch.uint8).to(dev)
-
         n = len(rec["mols"])
-        na, nb, nt = len(rec["atoms"]), len(rec["bonds"]), len(rec["text"])
-        # graph_pack(keep_device=True) left its tables on the device: no second upload
-        mols, atoms, bonds, text = rec.get("device") or (up(rec["mols"]), up(rec["atoms"]), up(rec["bonds"]), up(rec["text"]))
+        tables, args = self._packed_tables(rec)
         sc = None
         if scale is not None:
             sc = torch.as_tensor(np.ascontiguousarray(scale, dtype=np.int32).reshape(n, 2)).to(dev)
         files = torch.empty(n * MOLFILE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        totals = torch.empty(2, dtype=torch.int32, device=dev)
-        cap = int(cap) if cap is not None else n * self.MOLFILE_GUESS
-        for attempt in range(2):
-            out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
-            self._check(self.lib.mnx_molfile_pack(self.h, _ptr(mols), n, _ptr(atoms) if na else None, na,
-                                                  _ptr(bonds) if nb else None, nb, _ptr(text) if nt else None, nt, _ptr(sc),
-                                                  _ptr(files), _ptr(out), cap, _ptr(totals), _stream()), "mnx_molfile_pack")
-            tot = totals.cpu().numpy().view(np.uint32)
-            if not tot[1]:
-                break
-            if attempt:
-                raise MnxError(f"mnx_molfile_pack: capacity {cap} too small after sizing it from totals {tot.tolist()}")
-            cap = int(tot[0])
-        return files.cpu().numpy().view(MOLFILE_DTYPE), out[:int(tot[0])].cpu().numpy().tobytes()
+        data = self._sized_text("mnx_molfile_pack", args + [_ptr(sc), _ptr(files)], int(cap) if cap is not None else n * self.MOLFILE_GUESS)
+        return files.cpu().numpy().view(MOLFILE_DTYPE), data
 
     SMILES_GUESS = 256        # first capacity of smiles_pack per molecule (a drug-like SMILES is well under 200 bytes)
 
@@ -887,31 +899,12 @@ class Engine:
         graph_pack(keep_device=True)); starts from SMILES_GUESS bytes per molecule (or cap) and repeats at most once with the
         size `totals` reports."""
         dev = torch.device("cuda", self.device)
-
-        def up(a):
-            raw = a if isinstance(a, (bytes, bytearray)) else np.ascontiguousarray(a).tobytes()
-            return torch.frombuffer(bytearray(raw) or bytearray(8), dtype=torch.uint8).to(dev)
-
-        n = len(rec["mols"])
-        na, nb, nt = len(rec["atoms"]), len(rec["bonds"]), len(rec["text"])
-        mols, atoms, bonds, text = rec.get("device") or (up(rec["mols"]), up(rec["atoms"]), up(rec["bonds"]), up(rec["text"]))
+        n, na = len(rec["mols"]), len(rec["atoms"])
+        tables, args = self._packed_tables(rec)
         recs = torch.empty(n * SMILES_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         order = torch.full((max(na, 1),), -1, dtype=torch.int16, device=dev)     # every entry SMILES_NO_POSITION
-        totals = torch.empty(2, dtype=torch.int32, device=dev)
-        cap = int(cap) if cap is not None else n * self.SMILES_GUESS
-        for attempt in range(2):
-            out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
-            self._check(self.lib.mnx_smiles_pack(self.h, _ptr(mols), n, _ptr(atoms) if na else None, na,
-                                                 _ptr(bonds) if nb else None, nb, _ptr(text) if nt else None, nt, _ptr(recs),
-                                                 _ptr(order), _ptr(out), cap, _ptr(totals), _stream()), "mnx_smiles_pack")
-            tot = totals.cpu().numpy().view(np.uint32)
-            if not tot[1]:
-                break
-            if attempt:
-                raise MnxError(f"mnx_smiles_pack: capacity {cap} too small after sizing it from totals {tot.tolist()}")
-            cap = int(tot[0])
-        return (recs.cpu().numpy().view(SMILES_DTYPE), order[:na].cpu().numpy().view(np.uint16),
-                out[:int(tot[0])].cpu().numpy().tobytes())
+        data = self._sized_text("mnx_smiles_pack", args + [_ptr(recs), _ptr(order)], int(cap) if cap is not None else n * self.SMILES_GUESS)
+        return recs.cpu().numpy().view(SMILES_DTYPE), order[:na].cpu().numpy().view(np.uint16), data
 
     def atom_scan(self, tokens: torch.Tensor, lengths: torch.Tensor, kmax: Optional[int] = None):
         """On-device CharTokenizer.sequence_to_smiles 'indices' for [n,T] int32 id sequences."""

@@ -11,20 +11,13 @@ import pytest
 import torch
 
 import molfile_ref as R
+import smiles_ref as S
 import test_molfile_host as H
 from molnextr_amd import weights as W
 from molnextr_amd.engine import MOLFILE_DTYPE, Engine
+from packed_tables import FILL, GUARD, POOL, UTF2, Tables, _p, compare, random_molecule
 
 pytestmark = pytest.mark.gpu
-
-FILL, GUARD = 0x7F, 64
-UTF2 = "ŕ".encode("utf-8")              # the vocabulary's two-byte character
-
-# symbols of every class: parsed plain / bracket atoms, the four chiral carbons, table names, unparsable and empty ones
-POOL = [b"C", b"N", b"O", b"Cl", b"Br", b"c", b"n", b"s", b"I", b"[nH]", b"[NH3+]", b"[O-]", b"[13C]", b"[C@@H]", b"[C@]", b"[C@H]",
-        b"[C@@]", b"[R1]", b"[R12]", b"R", b"[OMe]", b"[Ac]", b"Ph", b"[Xx]", b"[C", b"*", b"[*]", b"[Fe+3]", b"[N++]", b"[se]", b"[2H]",
-        b"", b"[]", b"[C:12]", b"[" + UTF2 + b"]", UTF2, b"[[a*]]", b"[a*]", b"R'", b"[2, 4-Cl2C6H3]", b"[Si]", b"[CH12]", b"[U+15]",
-        b"[C-16]", b"[999Og]", b"<unk>", b"[\x01\x7f\n]", b"[3,5-[CF3]2C6H3]", b"[3,5-[CF3]2C6H3x]", b"Z", b"[H]", b"[Cn]", b"[C@@H2-]"]
 
 
 @pytest.fixture(scope="module")
@@ -38,35 +31,6 @@ def eng(synth_ckpt, dev):
     e = Engine(synth_ckpt["encoder"], synth_ckpt["decoder"], device=0, max_batch=32, dtype="fp16x3")
     yield e
     e.close()
-
-
-def random_molecule(rng, n_atoms, n_bonds, pool=POOL):
-    syms = [pool[k] for k in rng.integers(0, len(pool), n_atoms)]
-    xy = [(int(x), int(y)) for x, y in rng.integers(0, 64, (n_atoms, 2))]
-    bonds = []
-    for _ in range(n_bonds if n_atoms >= 2 else 0):
-        i, j = sorted(int(v) for v in rng.choice(n_atoms, 2, replace=False))
-        bonds.append((i, j, int(rng.integers(1, 7)), int(rng.integers(0, 7))))
-    return syms, xy, bonds
-
-
-def _up(dev, a):
-    raw = a if isinstance(a, bytes) else np.ascontiguousarray(a).tobytes()
-    return torch.frombuffer(bytearray(raw) + bytearray(8), dtype=torch.uint8).to(dev)
-
-
-def _p(t, off=0):
-    return None if t is None else C.c_void_p(t.data_ptr() + off)
-
-
-class Tables:
-    """packed records on the host and on the device"""
-
-    def __init__(self, dev, molecules=None, arrays=None):
-        self.mols, self.atoms, self.bonds, self.text = arrays if arrays is not None else R.build_tables(molecules)
-        self.n = len(self.mols)
-        self.d = [_up(dev, a) for a in (self.mols, self.atoms, self.bonds, self.text)]
-        self.dev = dev
 
 
 def run(eng, t, out_cap, scale=None, sizes=None, **over):
@@ -95,14 +59,7 @@ def check(eng, t, scale=None, sizes=None, ref_kw=None):
     rc, files, out, totals = run(eng, t, ref["total"], scale, sizes)
     assert rc == 0, eng.lib.mnx_last_error(eng.h)
     assert totals.tolist() == [ref["total"], 0]
-    for name in MOLFILE_DTYPE.names:
-        bad = np.nonzero(files[name] != ref["files"][name])[0]
-        assert bad.size == 0, (name, bad[:5], files[name][bad[:5]], ref["files"][name][bad[:5]])
-    got = out[:ref["total"]].tobytes()
-    if got != ref["out"]:
-        k = next(i for i, (x, y) in enumerate(zip(got, ref["out"])) if x != y)
-        raise AssertionError(f"first difference at byte {k}: {got[max(k - 80, 0):k + 40]!r} != {ref['out'][max(k - 80, 0):k + 40]!r}")
-    assert np.all(out[ref["total"]:] == FILL), "bytes behind the molfiles were overwritten"
+    compare(files, ref["files"], out, ref["out"], ref["total"], "molfiles")
     return ref
 
 
@@ -185,6 +142,22 @@ def test_records_beyond_the_tables(eng, dev):
     mols["flags"][5] = 1
     ref = check(eng, Tables(dev, arrays=(mols, atoms, bonds, text)))
     assert [int(f) & 10 for f in ref["files"]["flags"]] == [0, 2, 0, 2, 2, 8] and ref["files"]["len"][[1, 3, 4]].tolist() == [0, 0, 0]
+
+
+def test_self_bond_one_table_two_writers(eng, dev):
+    """The one rule on which the two writers of the packed tables differ: the molfile writes a bond from an atom to itself as the
+    record stands, the graph SMILES has no way to write it and refuses the molecule. One table through both writers at the
+    oracles' exact capacities, byte for byte; the neighbour is written by both."""
+    xy = [(3, 4), (10, 4), (3, 11), (10, 11)]
+    t = Tables(dev, [([b"C", b"N", b"O", b"C"], xy, [(0, 1, 1, 1), (2, 2, 1, 1), (2, 3, 2, 2)]), ([b"C", b"C"], xy[:2], [(0, 1, 1, 1)])])
+    ref = check(eng, t)
+    assert ref["files"]["flags"].tolist() == [0, 0] and ref["files"]["len"].tolist() == [391, 225] and b"\n  3  3  1  0\n" in ref["out"]
+    ref = S.pack(t.mols, t.atoms, t.bonds, t.text)
+    assert ref["recs"]["flags"].tolist() == [S.FLAG_BEYOND, 0] and ref["recs"]["len"].tolist() == [0, 2] and ref["out"] == b"CC"
+    rec = {"mols": t.mols, "atoms": t.atoms, "bonds": t.bonds, "text": t.text, "device": tuple(t.d)}
+    recs, order, data = eng.smiles_pack(rec, cap=ref["total"])
+    assert data == ref["out"] and recs.tobytes() == ref["recs"].tobytes() and order.tobytes() == ref["order"].tobytes()
+    assert order.tolist() == [S.NO_POSITION] * 4 + [0, 1]
 
 
 def test_capacities(eng, dev):

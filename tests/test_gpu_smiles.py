@@ -13,7 +13,7 @@ import smiles_ref as S
 import test_smiles_host as H
 from molnextr_amd import weights as W
 from molnextr_amd.engine import SMILES_DTYPE, SMILES_REFUSED, Engine
-from test_gpu_molfile import FILL, GUARD, POOL, Tables, _p, random_molecule
+from packed_tables import FILL, GUARD, POOL, Tables, _p, compare, random_molecule
 
 pytestmark = pytest.mark.gpu
 
@@ -67,14 +67,7 @@ def check(eng, t, sizes=None, ref_kw=None):
     rc, recs, order, out, totals = run(eng, t, ref["total"], sizes)
     assert rc == 0, eng.lib.mnx_last_error(eng.h)
     assert totals.tolist() == [ref["total"], 0]
-    for name in SMILES_DTYPE.names:
-        bad = np.nonzero(recs[name] != ref["recs"][name])[0]
-        assert bad.size == 0, (name, bad[:5], recs[name][bad[:5]], ref["recs"][name][bad[:5]])
-    got = out[:ref["total"]].tobytes()
-    if got != ref["out"]:
-        k = next(i for i, (x, y) in enumerate(zip(got, ref["out"])) if x != y)
-        raise AssertionError(f"first difference at byte {k}: {got[max(k - 80, 0):k + 40]!r} != {ref['out'][max(k - 80, 0):k + 40]!r}")
-    assert np.all(out[ref["total"]:] == FILL), "bytes behind the SMILES were overwritten"
+    compare(recs, ref["recs"], out, ref["out"], ref["total"], "SMILES")
     bad = np.nonzero(order != ref["order"])[0]
     assert bad.size == 0, ("order", bad[:5], order[bad[:5]], ref["order"][bad[:5]])
     return ref

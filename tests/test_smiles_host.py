@@ -11,7 +11,7 @@ import molfile_ref as M
 import smiles_ref as S
 from molnextr_amd import engine
 from molnextr_amd.model import predict_pipeline
-from test_gpu_molfile import POOL
+from packed_tables import POOL
 
 
 def ring(first, n, cls):
