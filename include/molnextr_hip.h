@@ -572,6 +572,52 @@ int mnx_smiles_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_ato
                     const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_smiles* recs,
                     uint16_t* order, char* out, uint32_t out_cap, uint32_t* totals, void* stream);
 
+/* mnx_smiles_pack with tetrahedral stereo marks: the same arguments, limits, error handling, sizing protocol and three
+ * launches, and the same string with ONE change — a candidate centre that resolves is written as [C@], [C@@], [C@H] or [C@@H]
+ * instead of [C] / [CH]. Removing every '@' from the string gives the string of mnx_smiles_pack byte for byte; `order` and
+ * n_rings are those of the plain call, len grows by 1 or 2 per mark. mnx_smiles_pack itself is unchanged. No '/' '\' at double
+ * bonds. The rule is this library's own, after the OpenSMILES definition of '@' / '@@' and the reference's "a wedge begins at
+ * the marked carbon" (_verify_chirality, MolNexTR/chemical.py:212-287: bond directions cleared, put back only at atoms whose
+ * token is one of the four symbols, as edges[c][n] seen from that atom; the 2D coordinates decide; every other tag cleared). It
+ * is NOT RDKit's AssignChiralTypesFromBondDirs: in degenerate drawings (neighbours on one line, a wedge between two
+ * neighbours that lie on a line through the centre) the two can differ. No symmetry check is made: a carbon with four
+ * identical substituents is marked like one with four different ones, and a canonicaliser downstream removes the marks of
+ * atoms that are no stereocentres.
+ *
+ * Candidate centre: an atom c for which all of these hold —
+ *   its symbol is exactly one of [C@] [C@@] [C@H] [C@@H] (the test of mnx_molfile_pack's bond lines) and is read as an atom
+ *     (it is no name of the symbol tables); H = 0 for [C@] [C@@], 1 for [C@H] [C@@H];
+ *   the number of its bond records + H = 4;
+ *   every one of its bonds has written class single (`type` 1, 5 or 6);
+ *   at least one of its bonds is a wedge SEEN FROM c. The class of a bond seen from c is `type` when c == i and `rev` when
+ *     c == j (edges[c][n]). Seen class 5 puts neighbour n at z = +1 (towards the viewer), seen class 6 at z = -1, every other
+ *     seen class at z = 0.
+ * Geometry: the vector of neighbour n is v(n) = (x_bin[n] - x_bin[c], y_bin[c] - y_bin[n], z) — the image's y axis points
+ *   down, the vector has y up. Exact 64-bit integer arithmetic; no scale (the sign depends neither on a positive scale of x
+ *   nor on the magnitude of z). The '@' or '@@' of the symbol itself is ignored: the mark comes from the drawing alone.
+ * Neighbour order of the string at c: the parent if c has one; then the implicit H if H = 1; then c's ring items in the order
+ *   they are written at c (closures, then openings, as stated above); then its children in written order.
+ * Four explicit neighbours n0..n3 in that order: d = det[v1 - v0, v2 - v0, v3 - v0] (the rows of a 3x3 determinant).
+ * Three explicit neighbours n0..n2 in that order: d = det[v0, v1, v2], negated when the H stands at an odd position of the
+ *   four — position 1, behind a parent; the H stands at position 0 only when c starts a component.
+ * Mark: d < 0 writes '@', d > 0 writes '@@' (directly behind the 'C'), d == 0 writes no mark.
+ * Examples (atoms with (x_bin, y_bin), bonds (i, j, type, rev)):
+ *   F(20,30) [C@@](20,20) Cl(20,10) Br(11,25) I(29,25), (0,1,6,5) (1,2,1,1) (1,3,1,1) (1,4,1,1)   ->  F[C@](Cl)(Br)I
+ *   N(10,20) [C@H](20,20) C(25,11) C(25,29) O(20,38) O(35,29), (0,1,1,1) (1,2,5,6) (1,3,1,1) (3,4,2,2) (3,5,1,1)
+ *                                                            ->  N[C@@H](C)C(=O)O, and with (1,2,6,5)  ->  N[C@H](C)C(=O)O
+ *   [C@H](20,20) C(30,26) C(30,14) F(10,20), (0,1,1,1) (0,2,1,1) (1,2,1,1) (0,3,5,6)               ->  [C@H]1(CC1)F
+ *
+ * Flags: bits 0-5 and 7 as in mnx_smiles_pack. Bit 6 (MNX_SMILES_WEDGES_DROPPED) is set only when some bond with `type` 5 or 6
+ * has NO end that received a mark; bit 8 (MNX_SMILES_STEREO) when at least one mark was written; bit 9
+ * (MNX_SMILES_STEREO_UNRESOLVED) when an atom with one of the four symbols and a wedge seen from it got no mark (the neighbour
+ * count, a bond that is not single, or d == 0). All three stay clear on a molecule that gets no SMILES.
+ * MNX_ERR_INVALID_ARG as mnx_smiles_pack, the text beginning "mnx_smiles_pack_stereo: ". */
+#define MNX_SMILES_STEREO 256u
+#define MNX_SMILES_STEREO_UNRESOLVED 512u
+int mnx_smiles_pack_stereo(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
+                           const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes,
+                           mnx_smiles* recs, uint16_t* order, char* out, uint32_t out_cap, uint32_t* totals, void* stream);
+
 /* mnx_predict with beam search (BASELINE config 5): the same inputs and outputs, every reference batch searched as
  * mnx_decode_beam does (n_best = 1: the best hypothesis; atom positions and the bond head run on ITS tokens and decoder
  * outputs) while the encoder of the following launch groups runs on the second stream. Up to MNX_BEAM_GROUPS (environment,

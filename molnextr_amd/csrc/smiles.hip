@@ -1,7 +1,8 @@
 // smiles.hip — a SMILES of the predicted graph from the packed molecule tables of mnx_graph_pack (mnx_smiles_pack): the molecules
 // that atom_symbol.h admits and the atoms as it reads them (shared with molfile.hip), the bonds of the bond head, written by a
-// depth-first walk after the OpenSMILES grammar. Valid, not canonical (the walk's order is fixed by the atom indices), no stereo,
-// pseudo-atoms as '*'.
+// depth-first walk after the OpenSMILES grammar. Valid, not canonical (the walk's order is fixed by the atom indices), pseudo-atoms
+// as '*'; no stereo (mnx_smiles_pack), or '@' / '@@' at the marked carbons that a wedge begins at (mnx_smiles_pack_stereo: one
+// more parallel stage, STEREO, behind the ring numbers; the plain instantiations hold none of it).
 //   count  one workgroup per molecule: the walk and the length of its string -> recs[b].len / flags / n_rings
 //   scan   exclusive scan of the lengths over the molecules -> recs[b].text0, totals
 //   fill   one workgroup per molecule: the walk again, the bytes behind text0 and the atoms' positions in `order`
@@ -31,12 +32,21 @@ constexpr unsigned REFUSED = PT_TOO_LARGE | PT_BEYOND_TABLES | MNX_SMILES_DUPLIC
 
 // ---- one entry of a neighbour list ----
 //   bits 0-9 the neighbour, bits 10-12 the bond's written class, bits 13-22 the atom that owns the list, bit 23 a bond of the
-//   search tree (to the parent or to a child); every other bond is a ring bond
+//   search tree (to the parent or to a child); every other bond is a ring bond; STEREO only: bit 24 the bond is a wedge (class
+//   5) as the owner sees it, bit 25 a dash (class 6). The rank sorts copy whole entries, so the bits travel with them.
 constexpr unsigned B_SINGLE = 0, B_DOUBLE = 1, B_TRIPLE = 2, B_AROMATIC = 3, B_ANY = 4;
-constexpr unsigned SLOT_TREE = 1u << 23;
+constexpr unsigned SLOT_TREE = 1u << 23, SLOT_UP = 1u << 24, SLOT_DOWN = 1u << 25;
 __device__ __forceinline__ unsigned slot_nbr(unsigned e) { return e & 1023u; }
 __device__ __forceinline__ unsigned slot_cls(unsigned e) { return e >> 10 & 7u; }
 __device__ __forceinline__ unsigned slot_owner(unsigned e) { return e >> 13 & 1023u; }
+__device__ __forceinline__ unsigned slot_seen(unsigned cls) { return cls == 5 ? SLOT_UP : cls == 6 ? SLOT_DOWN : 0u; }
+__device__ __forceinline__ long long slot_z(unsigned e) { return (long long)(e >> 24 & 1u) - (long long)(e >> 25 & 1u); }
+
+// det of the rows a, b, c, exact in 64 bits (|x|, |y| < 2^18 and |z| <= 2 here)
+__device__ __forceinline__ long long det3(long long ax, long long ay, long long az, long long bx, long long by, long long bz,
+                                          long long cx, long long cy, long long cz) {
+    return ax * (by * cz - bz * cy) - ay * (bx * cz - bz * cx) + az * (bx * cy - by * cx);
+}
 
 // the byte of a bond between two atoms, 0 = written as nothing
 __device__ __forceinline__ char bond_symbol(unsigned cls, bool both_aromatic) {
@@ -56,9 +66,10 @@ __device__ __forceinline__ void put_number(unsigned v, Put put) {       // decim
     put((char)('0' + v % 10));
 }
 
-// One atom's text from its interpretation (atom_symbol.h) and the two bytes of its element.
+// One atom's text from its interpretation (atom_symbol.h), the two bytes of its element and its stereo mark (0 none, 1 '@',
+// 2 '@@': only a bracket atom ever has one).
 template <typename Put>
-__device__ __forceinline__ void put_atom(unsigned w, unsigned el, Put put) {
+__device__ __forceinline__ void put_atom(unsigned w, unsigned el, unsigned mark, Put put) {
     const unsigned cls = info_cls(w);
     if (cls == CLS_PSEUDO) { put('*'); return; }
     if (cls == CLS_RNUM) { put('['); put_number(info_num(w), put); put('*'); put(']'); return; }
@@ -71,6 +82,8 @@ __device__ __forceinline__ void put_atom(unsigned w, unsigned el, Put put) {
     put(e0 == 'R' && e1 == ' ' ? '*' : info_aromatic(w) ? (char)(e0 + 32) : e0);
     if (e1 != ' ') put(e1);
     if (bracket) {
+        if (mark >= 1) put('@');
+        if (mark >= 2) put('@');
         const int h = info_h(w), q = info_charge(w);
         if (h >= 1) put('H');
         if (h >= 2) put((char)('0' + h));
@@ -82,7 +95,7 @@ __device__ __forceinline__ void put_atom(unsigned w, unsigned el, Put put) {
     }
 }
 
-template <bool FILL>
+template <bool FILL, bool STEREO>
 __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
         const PackedTables t, const SymbolTables* __restrict__ st, mnx_smiles* __restrict__ recs,
         unsigned short* __restrict__ order, char* __restrict__ out, unsigned out_cap) {
@@ -91,7 +104,7 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
     __shared__ unsigned raw[SM_SLOTS], adj[SM_SLOTS];     // the lists as the bonds came, then in ascending neighbour index
     __shared__ unsigned scan[2 * SM_THREADS];
     __shared__ unsigned short pos[SM_MAX], at[SM_MAX];    // atom -> written position, position -> atom
-    __shared__ unsigned short parent[SM_MAX], stk[SM_MAX], cur[SM_MAX];
+    __shared__ unsigned short parent[SM_MAX], stk[SM_MAX], cur[SM_MAX];   // stk: the search's stack, then (STEREO) every atom's mark
     __shared__ unsigned short done_child[SM_MAX], done_last[SM_MAX];  // the child an atom returned from, the atom written last inside it
     __shared__ unsigned short closes[SM_MAX];             // ')' behind an atom's text
     __shared__ unsigned char paren[SM_MAX], rnum[SM_SLOTS];
@@ -163,8 +176,9 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
     for (int k = tid; k < nb; k += SM_THREADS) {
         const unsigned i = B[k].i, j = B[k].j, ty = B[k].type;
         const unsigned cls = (ty == 1 || ty == 5 || ty == 6) ? B_SINGLE : ty == 2 ? B_DOUBLE : ty == 3 ? B_TRIPLE : ty == 4 ? B_AROMATIC : B_ANY;
-        raw[off[i] + atomicAdd(&cnt[i], 1u)] = j | cls << 10 | i << 13;       // any slot of the list: the sort below fixes the order
-        raw[off[j] + atomicAdd(&cnt[j], 1u)] = i | cls << 10 | j << 13;
+        const unsigned si = STEREO ? slot_seen(ty) : 0u, sj = STEREO ? slot_seen(B[k].rev) : 0u;     // edges[i][j], edges[j][i]
+        raw[off[i] + atomicAdd(&cnt[i], 1u)] = j | cls << 10 | i << 13 | si;  // any slot of the list: the sort below fixes the order
+        raw[off[j] + atomicAdd(&cnt[j], 1u)] = i | cls << 10 | j << 13 | sj;
     }
     __syncthreads();
     int dup = 0;
@@ -281,6 +295,59 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
         return;
     }
 
+    // ---- STEREO: every marked carbon that a wedge begins at, in parallel over the atoms (the rule: molnextr_hip.h). An atom's
+    //      list stands in ascending written position, so the string's neighbour order is: the parent (group 0), the ring items
+    //      in list order (group 1), the children in list order (group 2). The determinant is taken over the list as it stands
+    //      and flips with the parity of the permutation into that order: it is alternating in the neighbours. ----
+    int marked = 0, unresolved = 0, dropped = 0;
+    if (STEREO) {
+        for (int a = tid; a < na; a += SM_THREADS) {
+            const unsigned w = info[a], lo = off[a], hi = off[a + 1], p = pos[a];
+            unsigned mark = 0;
+            if (w & 8u) {
+                unsigned seen = 0, other = 0;
+                for (unsigned s = lo; s < hi; ++s) {
+                    seen |= raw[s] & (SLOT_UP | SLOT_DOWN);
+                    other |= slot_cls(raw[s]) != B_SINGLE;
+                }
+                const unsigned deg = hi - lo;
+                if (seen && !other && info_cls(w) == CLS_ATOM && deg + (unsigned)info_h(w) == 4u) {
+                    const unsigned e0 = raw[lo], e1 = raw[lo + 1], e2 = raw[lo + 2], e3 = deg == 4u ? raw[lo + 3] : e2;
+                    auto group = [&](unsigned e) { return !(e & SLOT_TREE) ? 1 : pos[slot_nbr(e)] < p ? 0 : 2; };
+                    const long long cx = mol.A[a].x_bin, cy = mol.A[a].y_bin;
+                    const mnx_atom A0 = mol.A[slot_nbr(e0)], A1 = mol.A[slot_nbr(e1)], A2 = mol.A[slot_nbr(e2)], A3 = mol.A[slot_nbr(e3)];
+                    const long long x0 = A0.x_bin - cx, y0 = cy - A0.y_bin, z0 = slot_z(e0);      // the image's y points down
+                    const long long x1 = A1.x_bin - cx, y1 = cy - A1.y_bin, z1 = slot_z(e1);
+                    const long long x2 = A2.x_bin - cx, y2 = cy - A2.y_bin, z2 = slot_z(e2);
+                    const long long x3 = A3.x_bin - cx, y3 = cy - A3.y_bin, z3 = slot_z(e3);
+                    const int g0 = group(e0), g1 = group(e1), g2 = group(e2), g3 = group(e3);
+                    int flips = (g0 > g1) + (g0 > g2) + (g1 > g2);
+                    long long d;
+                    if (deg == 4u) {
+                        flips += (g0 > g3) + (g1 > g3) + (g2 > g3);
+                        d = det3(x1 - x0, y1 - y0, z1 - z0, x2 - x0, y2 - y0, z2 - z0, x3 - x0, y3 - y0, z3 - z0);
+                    } else {
+                        flips += parent[a] != NONE;       // the implicit H stands behind a parent: an odd position of the four
+                        d = det3(x0, y0, z0, x1, y1, z1, x2, y2, z2);
+                    }
+                    if (flips & 1) d = -d;
+                    mark = d < 0 ? 1u : d > 0 ? 2u : 0u;
+                }
+                unresolved |= seen && !mark;
+            }
+            marked |= mark != 0;
+            stk[a] = (unsigned short)mark;
+        }
+        if (FILL) __syncthreads();
+        else {
+            marked = __syncthreads_or(marked);
+            unresolved = __syncthreads_or(unresolved);
+            for (int k = tid; k < nb; k += SM_THREADS)    // a wedge neither end of which received a mark
+                dropped |= (B[k].type == 5 || B[k].type == 6) && !stk[B[k].i] && !stk[B[k].j];
+            dropped = __syncthreads_or(dropped);
+        }
+    }
+
     // ---- the piece of the atom at written position p: '.' or '(' and the bond from its parent, its text, its ring items, the
     //      ')' of every branch that ends behind it ----
     auto piece = [&](unsigned p, auto put) {
@@ -299,7 +366,7 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
                 }
             }
         }
-        put_atom(w, elem[a], put);
+        put_atom(w, elem[a], STEREO ? stk[a] : 0u, put);
         for (unsigned s = off[a]; s < off[a + 1]; ++s) {
             const unsigned e = raw[s], n = slot_nbr(e), r = rnum[s];
             if (e & SLOT_TREE) continue;
@@ -324,8 +391,10 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
     }
     unsigned at_byte = block_scan_excl<SM_THREADS>(sum, scan, &total);
     if (!FILL) {
-        record(total, base_flags | (pseudo ? PT_PSEUDO_ATOM : 0u) | (wedge ? MNX_SMILES_WEDGES_DROPPED : 0u) |
-                          (any ? MNX_SMILES_UNKNOWN_BOND : 0u), n_rings);
+        const unsigned stereo = STEREO ? (dropped ? MNX_SMILES_WEDGES_DROPPED : 0u) | (marked ? MNX_SMILES_STEREO : 0u) |
+                                             (unresolved ? MNX_SMILES_STEREO_UNRESOLVED : 0u)
+                                       : wedge ? MNX_SMILES_WEDGES_DROPPED : 0u;
+        record(total, base_flags | (pseudo ? PT_PSEUDO_ATOM : 0u) | stereo | (any ? MNX_SMILES_UNKNOWN_BOND : 0u), n_rings);
         return;
     }
 #pragma unroll
@@ -344,11 +413,13 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
 
 }  // namespace
 
-hipError_t smiles_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, mnx_smiles* recs, unsigned short* order,
-                               char* out, unsigned out_cap, unsigned* totals, hipStream_t s) {
-    hipLaunchKernelGGL(smiles_kernel<false>, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, order, out, out_cap);
+hipError_t smiles_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, bool stereo, mnx_smiles* recs,
+                               unsigned short* order, char* out, unsigned out_cap, unsigned* totals, hipStream_t s) {
+    const auto count = stereo ? smiles_kernel<false, true> : smiles_kernel<false, false>;
+    const auto fill = stereo ? smiles_kernel<true, true> : smiles_kernel<true, false>;
+    hipLaunchKernelGGL(count, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, order, out, out_cap);
     hipLaunchKernelGGL(text_scan_kernel<mnx_smiles>, dim3(1), dim3(TEXT_SCAN_THREADS), 0, s, recs, t.n, out_cap, totals);
-    hipLaunchKernelGGL(smiles_kernel<true>, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, order, out, out_cap);
+    hipLaunchKernelGGL(fill, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, order, out, out_cap);
     return hipGetLastError();
 }
 

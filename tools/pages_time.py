@@ -17,8 +17,9 @@ is part of the product path and no number is asserted.
     images between two events, and predict_images from `--facade-pages` pages with molnextr(graph_molfile=True) against the
     packed facade without it; `--molfile-out FILE` writes the table to a file of its own.
 (s) (only when asked for: --part s) graph SMILES written on the device: one mnx_smiles_pack call over the packed tables of 1024
-    images between two events, alternating with one mnx_molfile_pack call over the same tables, with how many molecules were
-    written and how many refused per flag; `--smiles-out FILE` writes the table to a file of its own.
+    images between two events, alternating with one mnx_molfile_pack and one mnx_smiles_pack_stereo call over the same tables,
+    with how many molecules were written and how many refused per flag; `--smiles-out FILE` writes the table to a file of its
+    own.
 The variants of a part alternate inside every repeat (A B A B ...), the table reports the median and the min .. max spread of
 each, and the spread of the fp32 path against itself is the yardstick for "not slower".
 """
@@ -220,9 +221,11 @@ def part_m(n, repeats, lines):
         m.engine.close()
 
 
-def druglike_records(n_mols, seed=0):
+def druglike_records(n_mols, seed=0, centres=False):
     """Packed records of n_mols hand-made molecules of drug-like size: a chain of 20 .. 40 atoms, every seventh atom starting
-    an aromatic six-ring, a few hetero atoms and double bonds (about 1.1 bonds per atom) — (mols, atoms, bonds, text)"""
+    an aromatic six-ring, a few hetero atoms and double bonds (about 1.1 bonds per atom) — (mols, atoms, bonds, text).
+    centres: every [C@@H] of the chain also carries a methyl on a wedge or a dash that begins at it, and its chain bonds are
+    single: a candidate centre of mnx_smiles_pack_stereo (the molecules are the same otherwise)."""
     from molnextr_amd.engine import ATOM_DTYPE, BOND_DTYPE, MOL_DTYPE
     rng = np.random.default_rng(seed)
     mols = np.zeros(n_mols, MOL_DTYPE)
@@ -239,21 +242,33 @@ def druglike_records(n_mols, seed=0):
         for k in range(n):
             if syms[k] == b"C" and rng.integers(0, 4) == 0:
                 syms[k] = (b"N", b"O", b"[C@@H]", b"Cl")[int(rng.integers(0, 4))]
+        xy = [(k % 64, k // 2 % 64) for k in range(n)]
+        rev = {}
+        if centres:
+            for k in [k for k in range(n) if syms[k] == b"[C@@H]"]:
+                for pair in ((k - 1, k), (k, k + 1)):
+                    if pair in bonds:
+                        bonds[pair] = 1
+                bonds[(k, len(syms))] = 5 + k % 2
+                rev[(k, len(syms))] = 6 - k % 2
+                syms.append(b"C")
+                xy.append((xy[k][0], (xy[k][1] + 3) % 64))
         own = b"".join(syms)
-        mols[b] = (len(A), n, len(B), len(bonds), len(text), len(own), 0, 0, 0.0)
+        mols[b] = (len(A), len(syms), len(B), len(bonds), len(text), len(own), 0, 0, 0.0)
         off = 0
         for k, sym in enumerate(syms):
-            A.append((off, len(sym), k, k % 64, k // 2 % 64, 0.0))
+            A.append((off, len(sym), k, xy[k][0], xy[k][1], 0.0))
             off += len(sym)
-        B += [(i, j, ty, 0, 0.0) for (i, j), ty in sorted(bonds.items())]
+        B += [(i, j, ty, rev.get((i, j), 0), 0.0) for (i, j), ty in sorted(bonds.items())]
         text += own
     return mols, np.array(A, ATOM_DTYPE), np.array(B, BOND_DTYPE), bytes(text)
 
 
 def part_s(repeats, lines):
     """Graph SMILES from the device: the three launches of one mnx_smiles_pack call over 1024 molecules between two events, next
-    to mnx_molfile_pack over the same tables (the tables stay on the device, the output buffers have the exact size) — on the
-    synthetic checkpoint's predictions, then on hand-made molecules of drug-like size."""
+    to mnx_molfile_pack and mnx_smiles_pack_stereo over the same tables (the tables stay on the device, the output buffers have
+    the exact size) — on the synthetic checkpoint's predictions, on hand-made molecules of drug-like size, and on those with
+    candidate centres."""
     import ctypes as C
     from molnextr_amd import engine as E
     from molnextr_amd.model import molnextr
@@ -266,37 +281,55 @@ def part_s(repeats, lines):
     def measure(rec, what):
         files, mol_data = eng.molfile_pack(rec)
         recs, order, data = eng.smiles_pack(rec)
+        st_recs, _, st_data = eng.smiles_pack(rec, stereo=True)
         mols, atoms, bonds, text = rec["device"]
         n, na, nb, nt = len(recs), len(rec["atoms"]), len(rec["bonds"]), len(rec["text"])
         recs_d = torch.empty(n * 16, dtype=torch.uint8, device=dev)
         order_d = torch.empty(max(na, 1), dtype=torch.int16, device=dev)
         out_d = {"mnx_smiles_pack": torch.empty(max(len(data), 1), dtype=torch.uint8, device=dev),
-                 "mnx_molfile_pack": torch.empty(max(len(mol_data), 1), dtype=torch.uint8, device=dev)}
+                 "mnx_molfile_pack": torch.empty(max(len(mol_data), 1), dtype=torch.uint8, device=dev),
+                 "mnx_smiles_pack_stereo": torch.empty(max(len(st_data), 1), dtype=torch.uint8, device=dev)}
         totals_d = torch.empty(2, dtype=torch.int32, device=dev)
         calls = {"mnx_smiles_pack": lambda: eng.lib.mnx_smiles_pack(eng.h, ptr(mols), n, ptr(atoms), na, ptr(bonds), nb, ptr(text), nt,
                                                                     ptr(recs_d), ptr(order_d), ptr(out_d["mnx_smiles_pack"]), len(data),
                                                                     ptr(totals_d), stream()),
                  "mnx_molfile_pack": lambda: eng.lib.mnx_molfile_pack(eng.h, ptr(mols), n, ptr(atoms), na, ptr(bonds), nb, ptr(text), nt, None,
                                                                       ptr(recs_d), ptr(out_d["mnx_molfile_pack"]), len(mol_data),
-                                                                      ptr(totals_d), stream())}
-        want = {"mnx_smiles_pack": data, "mnx_molfile_pack": mol_data}
-        us = {k: [] for k in calls}
-        for i in range(repeats + 3):
-            for k, call in calls.items():
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                torch.cuda.synchronize()
-                a.record()
-                rc = call()
-                b.record()
-                torch.cuda.synchronize()
-                assert rc == 0 and out_d[k][:len(want[k])].cpu().numpy().tobytes() == want[k]
-                if i >= 3:
-                    us[k].append(a.elapsed_time(b) * 1000.0)
+                                                                      ptr(totals_d), stream()),
+                 "mnx_smiles_pack_stereo": lambda: eng.lib.mnx_smiles_pack_stereo(
+                     eng.h, ptr(mols), n, ptr(atoms), na, ptr(bonds), nb, ptr(text), nt, ptr(recs_d), ptr(order_d),
+                     ptr(out_d["mnx_smiles_pack_stereo"]), len(st_data), ptr(totals_d), stream())}
+        want = {"mnx_smiles_pack": data, "mnx_molfile_pack": mol_data, "mnx_smiles_pack_stereo": st_data}
+
+        def alternate(names):
+            us = {k: [] for k in names}
+            for i in range(repeats + 3):
+                for k in names:
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    a.record()
+                    rc = calls[k]()
+                    b.record()
+                    torch.cuda.synchronize()
+                    assert rc == 0 and out_d[k][:len(want[k])].cpu().numpy().tobytes() == want[k]
+                    if i >= 3:
+                        us[k].append(a.elapsed_time(b) * 1000.0)
+            return us
+
+        us = alternate(("mnx_smiles_pack", "mnx_molfile_pack"))              # the plain pair, measured as before the stereo call existed
+        pair = alternate(("mnx_smiles_pack", "mnx_smiles_pack_stereo"))      # then stereo against plain, in a pass of their own
         refused = (recs["flags"] & E.SMILES_REFUSED) != 0
         lines.append(f"(s) one call over the packed tables of {n} {what} ({na} atoms, {nb} bonds): device us between two events around "
                      "its three launches, the two calls alternating   median [min .. max]")
-        for k in calls:
+        for k in us:
             lines.append(f"  {k:17s} {fmt(us[k])} us   -> {len(want[k])} bytes")
+        lines.append("  stereo against plain, the two alternating in a pass of their own:")
+        for k in pair:
+            lines.append(f"  {k:22s} {fmt(pair[k])} us   -> {len(want[k])} bytes")
+        lines.append(f"  stereo / plain, median {statistics.median(pair['mnx_smiles_pack_stereo']) / statistics.median(pair['mnx_smiles_pack']):.3f}; "
+                     f"marks written: {st_data.count(b'@') - st_data.count(b'@@')} in {int((st_recs['flags'] & E.SMILES_STEREO != 0).sum())} "
+                     f"molecules, unresolved in {int((st_recs['flags'] & E.SMILES_STEREO_UNRESOLVED != 0).sum())}, wedges still dropped in "
+                     f"{int((st_recs['flags'] & E.SMILES_WEDGES_DROPPED != 0).sum())}")
         lines.append(f"  graph SMILES written for {int((~refused).sum())} of {n} molecules ({int(((~refused) & (recs['len'] == 0)).sum())} of "
                      f"them empty), refused {int(refused.sum())}; ring bonds per molecule: median {int(np.median(recs['n_rings']))}, max "
                      f"{int(recs['n_rings'].max())}; molfiles refused: {int((files['len'] == 0).sum())}")
@@ -313,6 +346,9 @@ def part_s(repeats, lines):
     up = lambda a: torch.frombuffer(bytearray(a if isinstance(a, bytes) else a.tobytes()) + bytearray(8), dtype=torch.uint8).to(dev)   # noqa: E731
     measure({"mols": mols, "atoms": atoms, "bonds": bonds, "text": text, "device": (up(mols), up(atoms), up(bonds), up(text))},
             "hand-made molecules of drug-like size")
+    mols, atoms, bonds, text = druglike_records(1024, centres=True)
+    measure({"mols": mols, "atoms": atoms, "bonds": bonds, "text": text, "device": (up(mols), up(atoms), up(bonds), up(text))},
+            "hand-made molecules of drug-like size with candidate centres")
     m.engine.close()
 
 
