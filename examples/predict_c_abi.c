@@ -43,11 +43,12 @@ static int print_first_molfile(mnx_engine* eng, int n_images, const mnx_mol* mol
     return rc;
 }
 
-/* Molecule 0 as a SMILES of the predicted graph, written on the device from the same tables (mnx_smiles_pack_stereo; the plain
- * mnx_smiles_pack takes the same arguments and writes the same string without '@'): the token SMILES printed above names the
- * atoms, this one joins them with the bonds of the bond head and marks the carbons at which a wedge begins with '@' / '@@'
- * after the drawing. Valid, not canonical, no '/' '\'; R-groups and abbreviations stay '*'. The same two passes; `order` (each
- * atom's position in the string) is not asked for here. */
+/* Molecule 0 as a SMILES of the predicted graph, written on the device from the same tables (mnx_smiles_pack_marks with both
+ * kinds of marks; the plain mnx_smiles_pack takes the same arguments without `marks` and writes the same string without '@',
+ * '/' and '\'): the token SMILES printed above names the atoms, this one joins them with the bonds of the bond head, marks the
+ * carbons at which a wedge begins with '@' / '@@' and the double bonds off every cycle with '/' and '\' after the drawing.
+ * Valid, not canonical; R-groups and abbreviations stay '*'. The same two passes; `order` (each atom's position in the
+ * string) is not asked for here. */
 static int print_first_graph_smiles(mnx_engine* eng, int n_images, const mnx_mol* mols_dev, const mnx_atom* atoms_dev,
                                     const mnx_bond* bonds_dev, const char* text_dev, const uint32_t* table_sizes) {
     uint32_t totals[2] = {0, 0}, *totals_dev = NULL;
@@ -57,9 +58,9 @@ static int print_first_graph_smiles(mnx_engine* eng, int n_images, const mnx_mol
     hipMalloc((void**)&recs_dev, (size_t)n_images * sizeof(mnx_smiles));
     hipMalloc((void**)&totals_dev, sizeof totals);
     for (pass = 0; pass < 2; ++pass) {
-        rc = mnx_smiles_pack_stereo(eng, mols_dev, n_images, atoms_dev, table_sizes[0], bonds_dev, table_sizes[1], text_dev,
-                                    table_sizes[2], recs_dev, /*order=*/NULL, out_dev, pass ? totals[0] : 0, totals_dev,
-                                    /*stream=*/NULL);
+        rc = mnx_smiles_pack_marks(eng, mols_dev, n_images, atoms_dev, table_sizes[0], bonds_dev, table_sizes[1], text_dev,
+                                   table_sizes[2], recs_dev, /*order=*/NULL, out_dev, pass ? totals[0] : 0, totals_dev,
+                                   MNX_SMILES_MARK_TETRAHEDRAL | MNX_SMILES_MARK_DOUBLE_BOND, /*stream=*/NULL);
         if (rc != MNX_OK) { fprintf(stderr, "%s\n", mnx_last_error(eng)); break; }
         hipMemcpy(totals, totals_dev, sizeof totals, 2);
         if (pass == 0 && totals[0]) hipMalloc((void**)&out_dev, totals[0]);
@@ -71,9 +72,12 @@ static int print_first_graph_smiles(mnx_engine* eng, int n_images, const mnx_mol
             printf("graph SMILES 0: none (flags 0x%x)\n", (unsigned)rec.flags);
         } else if (out) {
             if (rec.len) hipMemcpy(out, out_dev + rec.text0, rec.len, 2);
-            printf("graph SMILES 0: %.*s (%u ring bonds%s%s%s)\n", (int)rec.len, out, (unsigned)rec.n_rings,
+            printf("graph SMILES 0: %.*s (%u ring bonds%s%s%s%s%s%s)\n", (int)rec.len, out, (unsigned)rec.n_rings,
                    (rec.flags & MNX_SMILES_STEREO) ? ", stereo marks" : "",
                    (rec.flags & MNX_SMILES_STEREO_UNRESOLVED) ? ", a marked carbon unresolved" : "",
+                   (rec.flags & MNX_SMILES_EZ) ? ", double-bond marks" : "",
+                   (rec.flags & MNX_SMILES_EZ_UNRESOLVED) ? ", a double bond unresolved" : "",
+                   (rec.flags & MNX_SMILES_EZ_IMPLIED) ? ", a configuration implied" : "",
                    (rec.flags & MNX_SMILES_WEDGES_DROPPED) ? ", wedges dropped" : "");
         }
         free(out);

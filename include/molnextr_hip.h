@@ -510,7 +510,8 @@ int mnx_molfile_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_at
 /* Molecules as SMILES of the predicted GRAPH, written on the device from the tables of mnx_graph_pack: the atoms of the token
  * string joined by the bonds of the bond head — the raw token SMILES in `text` names the atoms but its bonds can disagree
  * with `bonds`. The string is VALID after the OpenSMILES grammar and NOT canonical (the walk below is fixed by the atom
- * indices; any toolkit can canonicalise it); it carries no stereo ('@', '/', '\' are never written: wedges are dropped) and
+ * indices; any toolkit can canonicalise it); it carries no stereo ('@', '/', '\' are never written by this call: wedges are
+ * dropped; mnx_smiles_pack_stereo and mnx_smiles_pack_marks below write them) and
  * expands no abbreviation (a pseudo-atom is '*'). The third post-pass after mnx_graph_pack and mnx_molfile_pack, with the
  * arguments, limits and error handling of the latter; it changes no input and touches no decode state.
  *
@@ -576,7 +577,7 @@ int mnx_smiles_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_ato
  * launches, and the same string with ONE change — a candidate centre that resolves is written as [C@], [C@@], [C@H] or [C@@H]
  * instead of [C] / [CH]. Removing every '@' from the string gives the string of mnx_smiles_pack byte for byte; `order` and
  * n_rings are those of the plain call, len grows by 1 or 2 per mark. mnx_smiles_pack itself is unchanged. No '/' '\' at double
- * bonds. The rule is this library's own, after the OpenSMILES definition of '@' / '@@' and the reference's "a wedge begins at
+ * bonds here: mnx_smiles_pack_marks below writes them. The rule is this library's own, after the OpenSMILES definition of '@' / '@@' and the reference's "a wedge begins at
  * the marked carbon" (_verify_chirality, MolNexTR/chemical.py:212-287: bond directions cleared, put back only at atoms whose
  * token is one of the four symbols, as edges[c][n] seen from that atom; the 2D coordinates decide; every other tag cleared). It
  * is NOT RDKit's AssignChiralTypesFromBondDirs: in degenerate drawings (neighbours on one line, a wedge between two
@@ -617,6 +618,72 @@ int mnx_smiles_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_ato
 int mnx_smiles_pack_stereo(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
                            const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes,
                            mnx_smiles* recs, uint16_t* order, char* out, uint32_t out_cap, uint32_t* totals, void* stream);
+
+/* mnx_smiles_pack with the marks the caller selects: the arguments of mnx_smiles_pack and `marks`, a set of MNX_SMILES_MARK_*,
+ * in front of `stream`; the same limits, sizing protocol (`totals`), `order`, refusal cases and three launches.
+ *   marks == 0                              the bytes, order, records and flags of mnx_smiles_pack
+ *   marks == MNX_SMILES_MARK_TETRAHEDRAL    those of mnx_smiles_pack_stereo
+ *   marks == MNX_SMILES_MARK_DOUBLE_BOND    '/' and '\' at double bonds, by the rule below
+ *   both                                    both kinds of marks, each by its own rule: neither looks at the other
+ * Any other bit is MNX_ERR_INVALID_ARG and nothing is launched. The two older calls are unchanged.
+ * Invariants: removing every '/' and '\' from the string of marks == 2 (and putting back the '-' where one of them replaced it
+ * between two aromatic atoms) gives the bytes of mnx_smiles_pack, and from marks == 3 those of mnx_smiles_pack_stereo; removing
+ * every '@' from marks == 3 gives marks == 2; `order` and n_rings never change, len grows by 1 per symbol written in front of
+ * an atom that had none and stays where a '-' is replaced.
+ *
+ * The rule of '/' and '\' is this library's own, after the OpenSMILES reading of the two symbols and the reference's way of
+ * taking double-bond E/Z from the 2D coordinates (_verify_chirality, MolNexTR/chemical.py:212-287: AssignStereochemistryFrom3D
+ * on the flat conformer). It is NOT RDKit's. No toolkit has parsed the output. No symmetry check is made: FC(F)=C(F)F is marked
+ * like any other double bond, and a canonicaliser downstream drops what is no stereo bond. Known limit: a double bond on a
+ * cycle of the molecule's bond graph is never marked, a macrocycle's included.
+ *
+ * Candidate: a bond record with `type` 2 for which all of these hold —
+ *   it lies on no cycle of the molecule's bond graph;
+ *   both its ends are read as atoms, not pseudo-atoms;
+ *   each end has 1 or 2 further bond records;
+ *   all of those have written class single (`type` 1, 5 or 6).
+ *   A candidate is therefore always a tree bond of the walk: a is its end written earlier, b (a's child) the other.
+ * Geometry, exact integers on the bins, y up (the image's y points down): the axis A = (x_bin[b] - x_bin[a], y_bin[a] - y_bin[b]);
+ *   a substituent s of the end u (u = a or b; every atom bonded to u but the other end) has v = (x_bin[s] - x_bin[u],
+ *   y_bin[u] - y_bin[s]) and side(s) = sign(A.x * v.y - A.y * v.x), with the same A at both ends: +1 is left of a -> b.
+ * Resolved: no substituent has side 0, and where an end has two substituents their sides are opposite. Substituents on ring
+ *   bonds count here. A candidate that does not resolve writes no marks (bit 11).
+ * Where the symbols go: only on tree bonds of the walk — the bond from a's parent to a, and the bonds from a and from b to
+ *   their children other than a -> b. The symbol stands in front of the child atom, where the bond's symbol stands (inside the
+ *   parenthesis), and replaces nothing, or the '-' between two aromatic atoms. A ring bond (a ring-closure digit) never
+ *   carries one. Every end of a candidate has at least one substituent on a tree bond, so every resolved candidate is marked
+ *   at both ends.
+ * Which symbol: with up(s) = (side(s) > 0) XOR flip, the candidate's flip being the same for all its substituents,
+ *   the bond u -> s to a child s of u = a or b is written '/' when up(s), else '\';
+ *   the bond p -> a from a's parent p is written '\' when up(p), else '/'.
+ * The flip: resolved candidates are taken in ascending written position of a. A candidate's directed bonds are listed as (1)
+ *   the bond from a's parent, (2) the bonds to a's other children in written order, (3) the bonds to b's children in written
+ *   order. If (1) exists and an earlier candidate (one that a's parent is an end of) already gave it a symbol, flip is the value
+ *   that reproduces that symbol; otherwise flip is the value that makes the first bond of the list '/'. Only (1) can have a
+ *   symbol already; these constraints run along tree bonds, so they form a forest and cannot conflict.
+ * Examples (atoms with (x_bin, y_bin), bonds (i, j, type, rev)):
+ *   F(0,20) C(10,10) C(20,10) F(30,0), (0,1,1,1) (1,2,2,2) (2,3,1,1)                    ->  F/C=C/F
+ *   the same with the last F at (30,20)                                                 ->  F/C=C\F
+ *   C(0,20) C(10,10) C(20,20) C(30,10) C(40,20) C(50,10), (0,1,1,1) (1,2,2,2) (2,3,1,1) (3,4,2,2) (4,5,1,1)
+ *                                                                                       ->  C/C=C/C=C/C
+ *   C(0,10) C(10,10) C(20,0) C(30,0) C(40,10) C(30,20) C(20,20) F(0,0), (0,1,2,2) (1,2,1,1) (2,3,1,1) (3,4,1,1) (4,5,1,1)
+ *   (5,6,1,1) (1,6,1,1) (0,7,1,1)                                                       ->  C(=C1/CCCCC1)/F
+ *
+ * Flags: bits 0-9 as the call with the same MNX_SMILES_MARK_TETRAHEDRAL bit gives them. Bit 10 (MNX_SMILES_EZ): at least one
+ * '/' or '\' was written. Bit 11 (MNX_SMILES_EZ_UNRESOLVED): a candidate got no marks. Bit 12 (MNX_SMILES_EZ_IMPLIED): a bond
+ * record with `type` 2 that is no resolved candidate has, at each of its two ends, a bond that carries a symbol — a reader
+ * takes a configuration from there that the drawing did not give; the caller can fall back to the string without double-bond
+ * marks for that molecule. All three stay clear on a molecule that gets no SMILES and without MNX_SMILES_MARK_DOUBLE_BOND.
+ * MNX_ERR_INVALID_ARG as mnx_smiles_pack, the text beginning "mnx_smiles_pack_marks: ". */
+#define MNX_SMILES_MARK_TETRAHEDRAL 1u
+#define MNX_SMILES_MARK_DOUBLE_BOND 2u
+#define MNX_SMILES_EZ 1024u
+#define MNX_SMILES_EZ_UNRESOLVED 2048u
+#define MNX_SMILES_EZ_IMPLIED 4096u
+int mnx_smiles_pack_marks(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
+                          const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes,
+                          mnx_smiles* recs, uint16_t* order, char* out, uint32_t out_cap, uint32_t* totals, uint32_t marks,
+                          void* stream);
 
 /* mnx_predict with beam search (BASELINE config 5): the same inputs and outputs, every reference batch searched as
  * mnx_decode_beam does (n_best = 1: the best hypothesis; atom positions and the bond head run on ITS tokens and decoder

@@ -16,6 +16,10 @@ cannot be installed, so nothing below can be executed or tested here. Behaviour:
     calls that are NOT restated (they cannot be validated here). A molecule that needs either — it has a wedge bond
     or an alias atom — is reported as failed (`None`, success False) instead of a plausible but different SMILES;
     only molecules that need neither get a SMILES.
+
+The device path can write a SMILES of the predicted graph on request, with '@' / '@@' from the wedges and '/' '\\' at double
+bonds from the coordinate bins (mnx_smiles_pack_marks, include/molnextr_hip.h: this project's own rules, not RDKit's, valid and
+not canonical); nothing in this module uses it.
 """
 import json
 import logging

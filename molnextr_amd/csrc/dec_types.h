@@ -209,8 +209,9 @@ struct PackedTables {
 hipError_t molfile_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, const int* scale, int coord_bins,
                                 mnx_molfile* files, char* out, unsigned out_cap, unsigned* totals, hipStream_t s);
 // smiles.hip: the molecules of t as graph SMILES behind one another in `out`, the atoms' written positions in `order` (may be
-// null) (mnx_smiles_pack; stereo: with the '@' / '@@' of mnx_smiles_pack_stereo): count, scan and fill, three launches on s
-hipError_t smiles_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, bool stereo, mnx_smiles* recs,
+// null) (mnx_smiles_pack; marks, MNX_SMILES_MARK_*: with the '@' / '@@' of mnx_smiles_pack_stereo and the '/' '\\' of
+// mnx_smiles_pack_marks): count, scan and fill, three launches on s
+hipError_t smiles_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, unsigned marks, mnx_smiles* recs,
                                unsigned short* order, char* out, unsigned out_cap, unsigned* totals, hipStream_t s);
 hipError_t edges_enqueue(const DecWeights& w, const DecBuffers& bf, const float* hidden, const int* slot_map,
                          const int* atom_idx, const int* n_atoms, int B, int kmax, int row_stride_T,

@@ -1358,7 +1358,7 @@ int mnx_set_symbol_tables(mnx_engine* h, const char* bytes, const uint32_t* offs
     return MNX_OK;
 }
 
-// What mnx_molfile_pack, mnx_smiles_pack and mnx_smiles_pack_stereo test before they launch, in the order in which a call refused for two reasons
+// What mnx_molfile_pack, mnx_smiles_pack, mnx_smiles_pack_stereo and mnx_smiles_pack_marks test before they launch, in the order in which a call refused for two reasons
 // reports them. The entry point tests its own pointers (outs_null, outs_skew); `aligned` is how its alignment message ends.
 static int check_packed_tables(mnx_engine* h, const char* fn, const PackedTables& t, bool outs_null, bool outs_skew,
                                const char* aligned) {
@@ -1386,15 +1386,19 @@ int mnx_molfile_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_at
     return MNX_OK;
 }
 
-// mnx_smiles_pack and mnx_smiles_pack_stereo: one check, one enqueue path, two pairs of kernels
-static int smiles_pack(mnx_engine* h, const char* fn, bool stereo, const PackedTables& t, mnx_smiles* recs, uint16_t* order,
+// mnx_smiles_pack, mnx_smiles_pack_stereo and mnx_smiles_pack_marks: one check, one enqueue path, a pair of kernels per set of marks
+static int smiles_pack(mnx_engine* h, const char* fn, uint32_t marks, const PackedTables& t, mnx_smiles* recs, uint16_t* order,
                        char* out, uint32_t out_cap, uint32_t* totals, void* stream) {
     if (int rc = check_packed_tables(h, fn, t, !recs || !totals || (!out && out_cap),
                                      (((uintptr_t)recs | (uintptr_t)totals) & 3) != 0 || ((uintptr_t)order & 1) != 0,
                                      "recs and totals 4-byte, order 2-byte"))
         return rc;
+    if (marks & ~(MNX_SMILES_MARK_TETRAHEDRAL | MNX_SMILES_MARK_DOUBLE_BOND)) {
+        h->err = std::string(fn) + ": marks may hold MNX_SMILES_MARK_TETRAHEDRAL and MNX_SMILES_MARK_DOUBLE_BOND only";
+        return MNX_ERR_INVALID_ARG;
+    }
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, smiles_pack_enqueue(h->st_dev, t, stereo, recs, order, out, out_cap, totals, (hipStream_t)stream));
+    HIPCHK(h, smiles_pack_enqueue(h->st_dev, t, marks, recs, order, out, out_cap, totals, (hipStream_t)stream));
     return MNX_OK;
 }
 
@@ -1402,14 +1406,22 @@ int mnx_smiles_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_ato
                     const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_smiles* recs,
                     uint16_t* order, char* out, uint32_t out_cap, uint32_t* totals, void* stream) {
     const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
-    return smiles_pack(h, "mnx_smiles_pack", false, t, recs, order, out, out_cap, totals, stream);
+    return smiles_pack(h, "mnx_smiles_pack", 0u, t, recs, order, out, out_cap, totals, stream);
 }
 
 int mnx_smiles_pack_stereo(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
                            const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes,
                            mnx_smiles* recs, uint16_t* order, char* out, uint32_t out_cap, uint32_t* totals, void* stream) {
     const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
-    return smiles_pack(h, "mnx_smiles_pack_stereo", true, t, recs, order, out, out_cap, totals, stream);
+    return smiles_pack(h, "mnx_smiles_pack_stereo", MNX_SMILES_MARK_TETRAHEDRAL, t, recs, order, out, out_cap, totals, stream);
+}
+
+int mnx_smiles_pack_marks(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
+                          const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes,
+                          mnx_smiles* recs, uint16_t* order, char* out, uint32_t out_cap, uint32_t* totals, uint32_t marks,
+                          void* stream) {
+    const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
+    return smiles_pack(h, "mnx_smiles_pack_marks", marks, t, recs, order, out, out_cap, totals, stream);
 }
 
 int mnx_atom_scan(mnx_engine* h, const int32_t* tokens, const int32_t* lengths, int32_t n, int32_t T, int32_t kmax,

@@ -2,7 +2,8 @@
 // that atom_symbol.h admits and the atoms as it reads them (shared with molfile.hip), the bonds of the bond head, written by a
 // depth-first walk after the OpenSMILES grammar. Valid, not canonical (the walk's order is fixed by the atom indices), pseudo-atoms
 // as '*'; no stereo (mnx_smiles_pack), or '@' / '@@' at the marked carbons that a wedge begins at (mnx_smiles_pack_stereo: one
-// more parallel stage, STEREO, behind the ring numbers; the plain instantiations hold none of it).
+// more parallel stage, STEREO, behind the ring numbers), or '/' and '\\' at the double bonds off every cycle (mnx_smiles_pack_marks:
+// the stage EZ behind that one). MARKS selects the stages; an instantiation holds none of the code of a stage it does not run.
 //   count  one workgroup per molecule: the walk and the length of its string -> recs[b].len / flags / n_rings
 //   scan   exclusive scan of the lengths over the molecules -> recs[b].text0, totals
 //   fill   one workgroup per molecule: the walk again, the bytes behind text0 and the atoms' positions in `order`
@@ -95,7 +96,15 @@ __device__ __forceinline__ void put_atom(unsigned w, unsigned el, unsigned mark,
     }
 }
 
-template <bool FILL, bool STEREO>
+// ---- EZ: what the atoms carry between its stages, in arrays of the search that are dead by then ----
+//   role (done_last)       ROLE_B: the bond to the parent is a resolved candidate (this atom is its b), ROLE_A: this atom is the a
+//                          of one, with its flip before forcing in bit 2; ROLE_UNRESOLVED: b of a candidate that got no marks
+//   child_dir (done_child) bit 0: the bond parent -> this atom takes a symbol from the candidate the parent is an end of, bit 1:
+//                          this atom lies on the left of that candidate's axis; in the end the symbol itself, 0 for none
+//   low, then flip (cur)   the lowest written position a ring bond reaches from the atom's subtree; then a's flip
+constexpr unsigned ROLE_B = 1, ROLE_A = 2, ROLE_F0 = 4, ROLE_UNRESOLVED = 8;
+
+template <bool FILL, unsigned MARKS>
 __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
         const PackedTables t, const SymbolTables* __restrict__ st, mnx_smiles* __restrict__ recs,
         unsigned short* __restrict__ order, char* __restrict__ out, unsigned out_cap) {
@@ -106,9 +115,11 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
     __shared__ unsigned short pos[SM_MAX], at[SM_MAX];    // atom -> written position, position -> atom
     __shared__ unsigned short parent[SM_MAX], stk[SM_MAX], cur[SM_MAX];   // stk: the search's stack, then (STEREO) every atom's mark
     __shared__ unsigned short done_child[SM_MAX], done_last[SM_MAX];  // the child an atom returned from, the atom written last inside it
+                                                          // (EZ: cur, done_child and done_last carry its state behind the search)
     __shared__ unsigned short closes[SM_MAX];             // ')' behind an atom's text
     __shared__ unsigned char paren[SM_MAX], rnum[SM_SLOTS];
     __shared__ unsigned walk[2];                          // components, 1 = more than 99 ring numbers in use
+    constexpr bool STEREO = (MARKS & MNX_SMILES_MARK_TETRAHEDRAL) != 0, EZ = (MARKS & MNX_SMILES_MARK_DOUBLE_BOND) != 0;
     const int b = blockIdx.x, tid = threadIdx.x;
     const Molecule mol = admit_molecule(t, b);
     const mnx_mol& m = mol.m;
@@ -348,6 +359,118 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
         }
     }
 
+    // ---- EZ: '/' and '\' at every candidate double bond that resolves (the rule: molnextr_hip.h). A candidate lies on no cycle,
+    //      so it is the tree bond into its later-written end b, and no ring bond joins b's subtree to an atom written before b.
+    //      Each atom belongs to at most one candidate (its other bonds are single), so the thread of b owns the whole candidate
+    //      and is the only writer of what it leaves at a, at b and at their children. ----
+    int directed = 0, ez_unresolved = 0, implied = 0;
+    if (EZ) {
+        unsigned short *low = cur, *flip = cur, *child_dir = done_child, *role = done_last;
+        const mnx_atom* A = mol.A;
+        for (int a = tid; a < na; a += SM_THREADS) {
+            unsigned l = NONE;
+            for (unsigned s = off[a]; s < off[a + 1]; ++s)
+                if (!(raw[s] & SLOT_TREE)) l = min(l, (unsigned)pos[slot_nbr(raw[s])]);
+            low[a] = (unsigned short)l;
+            child_dir[a] = 0;
+            role[a] = 0;
+        }
+        __syncthreads();
+        if (tid == 0)                                     // minimised up the tree: children are written behind their parent
+            for (int p = na - 1; p > 0; --p) {
+                const unsigned a = at[p], par = parent[a];
+                if (par != NONE && low[a] < low[par]) low[par] = low[a];
+            }
+        __syncthreads();
+        for (int c = tid; c < na; c += SM_THREADS) {
+            const unsigned a = parent[c];
+            if (a == NONE || low[c] < pos[c]) continue;
+            if (info_cls(info[c]) != CLS_ATOM || info_cls(info[a]) != CLS_ATOM) continue;
+            const unsigned dc = off[c + 1] - off[c], da = off[a + 1] - off[a];
+            if (dc < 2u || dc > 3u || da < 2u || da > 3u) continue;
+            const long long ax = (long long)A[c].x_bin - (long long)A[a].x_bin, ay = (long long)A[a].y_bin - (long long)A[c].y_bin;
+            auto side = [&](unsigned u, unsigned n) {         // the image's y points down
+                const long long vx = (long long)A[n].x_bin - (long long)A[u].x_bin, vy = (long long)A[u].y_bin - (long long)A[n].y_bin;
+                const long long d = ax * vy - ay * vx;
+                return d > 0 ? 1 : d < 0 ? -1 : 0;
+            };
+            bool candidate = true, resolved = true;
+            for (int end = 0; end < 2; ++end) {
+                const unsigned u = end ? (unsigned)c : a, v = end ? a : (unsigned)c;
+                int before = 0;
+                for (unsigned s = off[u]; s < off[u + 1]; ++s) {
+                    const unsigned e = raw[s], n = slot_nbr(e);
+                    if (n == v) { candidate &= slot_cls(e) == B_DOUBLE; continue; }
+                    candidate &= slot_cls(e) == B_SINGLE;
+                    const int sd = side(u, n);
+                    resolved &= sd != 0 && sd != before;
+                    before = sd;
+                }
+            }
+            if (!candidate) continue;
+            if (!resolved) { role[c] = (unsigned short)ROLE_UNRESOLVED; continue; }
+            unsigned f0 = 2;                              // the flip that makes the first directed bond of the list '/'
+            for (int end = 0; end < 2; ++end) {
+                const unsigned u = end ? (unsigned)c : a, v = end ? a : (unsigned)c;
+                for (unsigned s = off[u]; s < off[u + 1]; ++s) {        // tree bonds in written order: a's parent, then the children
+                    const unsigned e = raw[s], n = slot_nbr(e);
+                    if (n == v || !(e & SLOT_TREE)) continue;
+                    const unsigned up = side(u, n) > 0;
+                    if (pos[n] < pos[u]) f0 = up;
+                    else {
+                        child_dir[n] = (unsigned short)(1u | up << 1);
+                        if (f0 == 2u) f0 = !up;
+                    }
+                }
+            }
+            role[c] = (unsigned short)ROLE_B;
+            role[a] = (unsigned short)(ROLE_A | (f0 & 1u) * ROLE_F0);
+        }
+        __syncthreads();
+        if (tid == 0)                                     // a's flip, in written order: forced when an earlier candidate gave the
+            for (int p = 0; p < na; ++p) {                // bond to a's parent its symbol
+                const unsigned a = at[p], r = role[a];
+                if (!(r & ROLE_A)) continue;
+                unsigned f = (r & ROLE_F0) != 0;
+                const unsigned d = child_dir[a];
+                if (d & 1u) {
+                    const unsigned par = parent[a], first = role[par] & ROLE_A ? par : parent[par];
+                    f ^= 1u ^ (d >> 1 & 1u) ^ flip[first];
+                }
+                flip[a] = (unsigned short)f;
+            }
+        __syncthreads();
+        for (int x = tid; x < na; x += SM_THREADS) {      // the symbol in front of x
+            const unsigned d = child_dir[x], r = role[x];
+            unsigned sym = 0;
+            if (d & 1u) {
+                const unsigned par = parent[x], first = role[par] & ROLE_A ? par : parent[par];
+                sym = (d >> 1 & 1u) ^ flip[first] ? '/' : '\\';
+            } else if ((r & ROLE_A) && parent[x] != NONE) sym = '/';
+            child_dir[x] = (unsigned short)sym;
+            directed |= sym != 0;
+            ez_unresolved |= (r & ROLE_UNRESOLVED) != 0;
+        }
+        if (FILL) __syncthreads();
+        else {
+            directed = __syncthreads_or(directed);
+            ez_unresolved = __syncthreads_or(ez_unresolved);
+            auto has_directed = [&](unsigned u) {
+                unsigned any_dir = child_dir[u];
+                for (unsigned s = off[u]; s < off[u + 1]; ++s)
+                    if ((raw[s] & SLOT_TREE) && pos[slot_nbr(raw[s])] > pos[u]) any_dir |= child_dir[slot_nbr(raw[s])];
+                return any_dir != 0;
+            };
+            for (int k = tid; k < nb; k += SM_THREADS) {  // a double bond without marks of its own between two directed bonds
+                const unsigned i = B[k].i, j = B[k].j;
+                if (B[k].type != 2) continue;
+                const bool mine = (parent[j] == i && (role[j] & ROLE_B)) || (parent[i] == j && (role[i] & ROLE_B));
+                implied |= !mine && has_directed(i) && has_directed(j);
+            }
+            implied = __syncthreads_or(implied);
+        }
+    }
+
     // ---- the piece of the atom at written position p: '.' or '(' and the bond from its parent, its text, its ring items, the
     //      ')' of every branch that ends behind it ----
     auto piece = [&](unsigned p, auto put) {
@@ -360,7 +483,7 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
             for (unsigned s = off[a]; s < off[a + 1]; ++s) {
                 const unsigned e = raw[s];
                 if ((e & SLOT_TREE) && slot_nbr(e) == par) {
-                    const char c = bond_symbol(slot_cls(e), aromatic && info_aromatic(info[par]));
+                    const char c = EZ && done_child[a] ? (char)done_child[a] : bond_symbol(slot_cls(e), aromatic && info_aromatic(info[par]));
                     if (c) put(c);
                     break;
                 }
@@ -394,7 +517,9 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
         const unsigned stereo = STEREO ? (dropped ? MNX_SMILES_WEDGES_DROPPED : 0u) | (marked ? MNX_SMILES_STEREO : 0u) |
                                              (unresolved ? MNX_SMILES_STEREO_UNRESOLVED : 0u)
                                        : wedge ? MNX_SMILES_WEDGES_DROPPED : 0u;
-        record(total, base_flags | (pseudo ? PT_PSEUDO_ATOM : 0u) | stereo | (any ? MNX_SMILES_UNKNOWN_BOND : 0u), n_rings);
+        const unsigned ez = (directed ? MNX_SMILES_EZ : 0u) | (ez_unresolved ? MNX_SMILES_EZ_UNRESOLVED : 0u) |
+                            (implied ? MNX_SMILES_EZ_IMPLIED : 0u);
+        record(total, base_flags | (pseudo ? PT_PSEUDO_ATOM : 0u) | stereo | ez | (any ? MNX_SMILES_UNKNOWN_BOND : 0u), n_rings);
         return;
     }
 #pragma unroll
@@ -413,10 +538,12 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
 
 }  // namespace
 
-hipError_t smiles_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, bool stereo, mnx_smiles* recs,
+hipError_t smiles_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, unsigned marks, mnx_smiles* recs,
                                unsigned short* order, char* out, unsigned out_cap, unsigned* totals, hipStream_t s) {
-    const auto count = stereo ? smiles_kernel<false, true> : smiles_kernel<false, false>;
-    const auto fill = stereo ? smiles_kernel<true, true> : smiles_kernel<true, false>;
+    const auto count = marks == 3u ? smiles_kernel<false, 3u> : marks == 2u ? smiles_kernel<false, 2u>
+                     : marks == 1u ? smiles_kernel<false, 1u> : smiles_kernel<false, 0u>;
+    const auto fill = marks == 3u ? smiles_kernel<true, 3u> : marks == 2u ? smiles_kernel<true, 2u>
+                    : marks == 1u ? smiles_kernel<true, 1u> : smiles_kernel<true, 0u>;
     hipLaunchKernelGGL(count, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, order, out, out_cap);
     hipLaunchKernelGGL(text_scan_kernel<mnx_smiles>, dim3(1), dim3(TEXT_SCAN_THREADS), 0, s, recs, t.n, out_cap, totals);
     hipLaunchKernelGGL(fill, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, order, out, out_cap);

@@ -27,7 +27,8 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
            "mnx_predict_confidence", "mnx_confidence", "mnx_window_attn", "mnx_kv_block", "mnx_preprocess_batch",
            "mnx_encode_gray8", "mnx_predict_gray8", "mnx_decode_guided", "mnx_predict_guided", "mnx_patch_embed",
            "mnx_layernorm16", "mnx_merge_ln16", "mnx_cast16", "mnx_sgemm_tn", "mnx_set_vocab_text", "mnx_graph_pack",
-           "mnx_set_symbol_tables", "mnx_molfile_pack", "mnx_smiles_pack", "mnx_smiles_pack_stereo")
+           "mnx_set_symbol_tables", "mnx_molfile_pack", "mnx_smiles_pack", "mnx_smiles_pack_stereo",
+           "mnx_smiles_pack_marks")
 
 # Encoder operand modes (include/molnextr_hip.h MNX_DTYPE_*). "fp16x3" — split fp16 operands, three MFMA terms per
 # product, fp32-class results — is the default: it is the fastest mode whose results stay a factor of four inside north_star's
@@ -124,6 +125,11 @@ SMILES_DTYPE = np.dtype([("text0", "<u4"), ("len", "<u4"), ("flags", "<u4"), ("n
 # mnx_smiles_pack_stereo only: at least one '@' / '@@' was written; a marked carbon with a wedge seen from it got no mark. There
 # SMILES_WEDGES_DROPPED means a wedge bond neither end of which received a mark.
 SMILES_STEREO, SMILES_STEREO_UNRESOLVED = 256, 512
+# mnx_smiles_pack_marks with SMILES_MARK_DOUBLE_BOND only: at least one '/' or '\' was written; a candidate double bond got no
+# marks; a double bond without marks of its own stands between two directed bonds (a reader would take a configuration from there
+# that the drawing did not give: fall back to the string without double-bond marks for that molecule).
+SMILES_EZ, SMILES_EZ_UNRESOLVED, SMILES_EZ_IMPLIED = 1024, 2048, 4096
+SMILES_MARK_TETRAHEDRAL, SMILES_MARK_DOUBLE_BOND = 1, 2     # the `marks` of mnx_smiles_pack_marks
 SMILES_REFUSED = SMILES_TOO_LARGE | SMILES_BEYOND_TABLES | SMILES_DUPLICATE_BOND | SMILES_RING_NUMBERS    # no SMILES: len 0
 SMILES_NO_POSITION = 0xFFFF             # `order` of an atom whose molecule got no SMILES
 
@@ -256,6 +262,8 @@ def load_library():
     lib.mnx_smiles_pack.argtypes = [vp, vp, i32, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp]
     lib.mnx_smiles_pack_stereo.restype = C.c_int
     lib.mnx_smiles_pack_stereo.argtypes = list(lib.mnx_smiles_pack.argtypes)
+    lib.mnx_smiles_pack_marks.restype = C.c_int
+    lib.mnx_smiles_pack_marks.argtypes = lib.mnx_smiles_pack.argtypes[:-1] + [C.c_uint32, vp]
     lib.mnx_atom_scan.restype = C.c_int
     lib.mnx_atom_scan.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.mnx_preprocess.restype = C.c_int
@@ -860,14 +868,14 @@ class Engine:
             args += [_ptr(t) if k else None, k]
         return tables, args
 
-    def _sized_text(self, fn: str, head, cap: int) -> bytes:
-        """One text writer, lib.<fn>(h, *head, out, out_cap, totals, stream), at capacity `cap` and at most once more with the
-        size `totals` reports: the bytes it wrote."""
+    def _sized_text(self, fn: str, head, cap: int, tail=()) -> bytes:
+        """One text writer, lib.<fn>(h, *head, out, out_cap, totals, *tail, stream), at capacity `cap` and at most once more with
+        the size `totals` reports: the bytes it wrote."""
         dev = torch.device("cuda", self.device)
         totals = torch.empty(2, dtype=torch.int32, device=dev)
         for attempt in range(2):
             out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
-            self._check(getattr(self.lib, fn)(self.h, *head, _ptr(out), cap, _ptr(totals), _stream()), fn)
+            self._check(getattr(self.lib, fn)(self.h, *head, _ptr(out), cap, _ptr(totals), *tail, _stream()), fn)
             tot = totals.cpu().numpy().view(np.uint32)
             if not tot[1]:
                 break
@@ -896,21 +904,26 @@ class Engine:
 
     SMILES_GUESS = 256        # first capacity of smiles_pack per molecule (a drug-like SMILES is well under 200 bytes)
 
-    def smiles_pack(self, rec: dict, cap: Optional[int] = None, stereo: bool = False):
+    def smiles_pack(self, rec: dict, cap: Optional[int] = None, stereo: bool = False, double_bonds: bool = False):
         """graph_pack's records -> (recs [n] SMILES_DTYPE, order uint16 [atoms], bytes): the graph SMILES of molecule b is
         bytes[recs[b]['text0'] : +recs[b]['len']] (mnx_smiles_pack: valid, not canonical, no stereo, pseudo-atoms as '*'; len 0
         and a flag of SMILES_REFUSED for a molecule that gets none), order[atom0 + k] the position of its atom k in that
         string (SMILES_NO_POSITION without one). The records go back to the device as they are (or stay there:
         graph_pack(keep_device=True)); starts from SMILES_GUESS bytes per molecule (or cap) and repeats at most once with the
         size `totals` reports. stereo: mnx_smiles_pack_stereo — the same string with '@' / '@@' at the marked carbons that a
-        wedge begins at (the rule: include/molnextr_hip.h), flags with SMILES_STEREO / SMILES_STEREO_UNRESOLVED."""
+        wedge begins at (the rule: include/molnextr_hip.h), flags with SMILES_STEREO / SMILES_STEREO_UNRESOLVED. double_bonds:
+        mnx_smiles_pack_marks — '/' and '\\' at the double bonds off every cycle that the coordinate bins resolve (the rule: the
+        same header), with or without stereo's marks; flags with SMILES_EZ / SMILES_EZ_UNRESOLVED / SMILES_EZ_IMPLIED. Without
+        it the calls are the ones made before it existed."""
         dev = torch.device("cuda", self.device)
         n, na = len(rec["mols"]), len(rec["atoms"])
         tables, args = self._packed_tables(rec)
         recs = torch.empty(n * SMILES_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         order = torch.full((max(na, 1),), -1, dtype=torch.int16, device=dev)     # every entry SMILES_NO_POSITION
-        data = self._sized_text("mnx_smiles_pack_stereo" if stereo else "mnx_smiles_pack", args + [_ptr(recs), _ptr(order)],
-                                int(cap) if cap is not None else n * self.SMILES_GUESS)
+        fn, tail = ("mnx_smiles_pack_stereo" if stereo else "mnx_smiles_pack"), ()
+        if double_bonds:
+            fn, tail = "mnx_smiles_pack_marks", (SMILES_MARK_DOUBLE_BOND | (SMILES_MARK_TETRAHEDRAL if stereo else 0),)
+        data = self._sized_text(fn, args + [_ptr(recs), _ptr(order)], int(cap) if cap is not None else n * self.SMILES_GUESS, tail)
         return recs.cpu().numpy().view(SMILES_DTYPE), order[:na].cpu().numpy().view(np.uint16), data
 
     def atom_scan(self, tokens: torch.Tensor, lengths: torch.Tensor, kmax: Optional[int] = None):

@@ -135,7 +135,7 @@ def unpack_graphs(mols, atoms, bonds, text, coord_bins: int = 64, with_scores: b
 def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_batch_size: int = 16,
                      max_len: Optional[int] = None, beam_size: int = 1, compute_confidence: bool = False,
                      labels=None, free_run=False, packed: bool = False, molfile: bool = False,
-                     molfile_scale=None, smiles: bool = False, stereo: bool = False) -> List[dict]:
+                     molfile_scale=None, smiles: bool = False, stereo: bool = False, double_bonds: bool = False) -> List[dict]:
     """Encoder + Decoder.decode for MANY images through the engine's continuous-batching path (mnx_predict):
     same per-image dicts as `decode_batch`, identical results (the on-device atom scan equals
     sequence_to_smiles' indices), much higher throughput. compute_confidence=True: mnx_predict_confidence, the same
@@ -157,7 +157,10 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
     tables (mnx_smiles_pack: valid, not canonical, no stereo, abbreviations and R-groups as '*'; a str, None for a molecule
     that gets none), and 'graph_smiles_order', the position of every atom in that string (None without one).
     stereo (smiles only): the graph SMILES carry '@' / '@@' at the marked carbons that a wedge begins at, decided by the wedges and
-    the coordinate bins (mnx_smiles_pack_stereo: this library's own rule, include/molnextr_hip.h; no '/' '\\')."""
+    the coordinate bins (mnx_smiles_pack_stereo: this library's own rule, include/molnextr_hip.h; no '/' '\\').
+    double_bonds (smiles only): the graph SMILES carry '/' and '\\' at the double bonds off every cycle whose substituents the
+    coordinate bins put on either side (mnx_smiles_pack_marks: this library's own rule, the same header), with stereo's marks or
+    without; a double bond on a cycle is never marked and no symmetry check is made."""
     tok = (tokenizer or get_tokenizer())["chartok_coords"]
     if molfile and not packed:
         raise ValueError("molfile=True needs packed=True: the molfiles are written from the packed tables")
@@ -165,6 +168,8 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
         raise ValueError("smiles=True needs packed=True: the graph SMILES are written from the packed tables")
     if stereo and not smiles:
         raise ValueError("stereo=True needs smiles=True: the marks are written into the graph SMILES")
+    if double_bonds and not smiles:
+        raise ValueError("double_bonds=True needs smiles=True: the marks are written into the graph SMILES")
     if packed and beam_size > 1:
         raise NotImplementedError("packed results are built for greedy decoding (beam search keeps the dense path)")
     if labels is not None and beam_size > 1:
@@ -189,7 +194,7 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
                 t0, n = int(f["text0"]), int(f["len"])
                 p["molfile"] = data[t0:t0 + n].decode("utf-8", errors="replace") if n else None
         if smiles:
-            recs, order, data = engine.smiles_pack(rec, stereo=stereo)
+            recs, order, data = engine.smiles_pack(rec, stereo=stereo, **({"double_bonds": True} if double_bonds else {}))
             for p, r, m in zip(preds, recs, rec["mols"]):
                 t0, n, a0, na = int(r["text0"]), int(r["len"]), int(m["atom0"]), int(m["n_atoms"])
                 written = not int(r["flags"]) & SMILES_REFUSED               # an empty molecule is written as the empty string
@@ -257,21 +262,27 @@ class molnextr:
     graph_smiles: True (opt-in; implies the packed path) = when RDKit is absent 'predicted_smiles' is the SMILES that the device
     writes from the predicted graph (mnx_smiles_pack). That SMILES is valid but not canonical: two drawings of one molecule
     can give two different strings, so compare them only after a toolkit has canonicalised both. It carries no stereo (no
-    '@', '/' or '\\': wedge bonds are written as plain single bonds), and an abbreviation or R-group stays a '*' atom
+    '@', '/' or '\\' unless graph_stereo / graph_double_bonds ask for them: wedge bonds are written as plain single bonds), and
+    an abbreviation or R-group stays a '*' atom
     instead of being expanded. A molecule the writer refuses (more than 99 ring closures open at once, say) keeps None. The
     default stays None; with RDKit present chem.py's path is unchanged.
     graph_stereo: True (opt-in; needs graph_smiles) = that SMILES carries '@' / '@@' at the marked carbons that a wedge begins at
-    (mnx_smiles_pack_stereo: this library's own rule after OpenSMILES, not RDKit's; still no '/' '\\' and not canonical)."""
+    (mnx_smiles_pack_stereo: this library's own rule after OpenSMILES, not RDKit's; not canonical).
+    graph_double_bonds: True (opt-in; needs graph_smiles) = that SMILES carries '/' and '\\' at the double bonds off every cycle
+    that the coordinates resolve (mnx_smiles_pack_marks: this library's own rule after OpenSMILES, not RDKit's; no toolkit has
+    parsed it here; double bonds on a cycle and symmetry are not handled)."""
 
     image_format = "fp32"
     packed_results = False
     graph_molfile = False
     graph_smiles = False
     graph_stereo = False
+    graph_double_bonds = False
 
     def __init__(self, model_path, device=None, max_batch: int = 32, dtype: str = DEFAULT_DTYPE,
                  device_preprocess: bool = True, image_format: str = "fp32", packed_results: bool = False,
-                 graph_molfile: bool = False, graph_smiles: bool = False, graph_stereo: bool = False):
+                 graph_molfile: bool = False, graph_smiles: bool = False, graph_stereo: bool = False,
+                 graph_double_bonds: bool = False):
         if model_path is None:
             raise ValueError("molnextr(model_path): a checkpoint path is required (pass 'synthetic' explicitly for the "
                              "deterministic test checkpoint)")
@@ -299,6 +310,9 @@ class molnextr:
         self.graph_stereo = bool(graph_stereo)
         if self.graph_stereo and not self.graph_smiles:
             raise ValueError("graph_stereo=True needs graph_smiles=True: the marks are written into the graph SMILES")
+        self.graph_double_bonds = bool(graph_double_bonds)
+        if self.graph_double_bonds and not self.graph_smiles:
+            raise ValueError("graph_double_bonds=True needs graph_smiles=True: the marks are written into the graph SMILES")
         self.engine = Engine(states["encoder"], states["decoder"], device=device.index or 0, max_batch=max_batch,
                              dtype=dtype, image_format=image_format)
         self.input_size = args.input_size
@@ -479,6 +493,8 @@ class molnextr:
         if self.graph_smiles:
             conf["smiles"] = True
             conf["stereo"] = self.graph_stereo
+            if self.graph_double_bonds:
+                conf["double_bonds"] = True
         gen = self._prefetched(groups)
         try:
             for x in gen:

@@ -18,6 +18,7 @@ is part of the product path and no number is asserted.
     packed facade without it; `--molfile-out FILE` writes the table to a file of its own.
 (s) (only when asked for: --part s) graph SMILES written on the device: one mnx_smiles_pack call over the packed tables of 1024
     images between two events, alternating with one mnx_molfile_pack and one mnx_smiles_pack_stereo call over the same tables,
+    then mnx_smiles_pack_marks with marks 0, 1, 2 and 3 alternating with the two older SMILES calls in a pass of their own,
     with how many molecules were written and how many refused per flag; `--smiles-out FILE` writes the table to a file of its
     own.
 The variants of a part alternate inside every repeat (A B A B ...), the table reports the median and the min .. max spread of
@@ -300,6 +301,13 @@ def part_s(repeats, lines):
                      eng.h, ptr(mols), n, ptr(atoms), na, ptr(bonds), nb, ptr(text), nt, ptr(recs_d), ptr(order_d),
                      ptr(out_d["mnx_smiles_pack_stereo"]), len(st_data), ptr(totals_d), stream())}
         want = {"mnx_smiles_pack": data, "mnx_molfile_pack": mol_data, "mnx_smiles_pack_stereo": st_data}
+        ez = {2: eng.smiles_pack(rec, double_bonds=True), 3: eng.smiles_pack(rec, stereo=True, double_bonds=True)}
+        for marks, text_of in ((0, data), (1, st_data), (2, ez[2][2]), (3, ez[3][2])):       # mnx_smiles_pack_marks, every set of marks
+            k = f"marks {marks}"
+            out_d[k], want[k] = torch.empty(max(len(text_of), 1), dtype=torch.uint8, device=dev), text_of
+            calls[k] = lambda marks=marks, k=k: eng.lib.mnx_smiles_pack_marks(
+                eng.h, ptr(mols), n, ptr(atoms), na, ptr(bonds), nb, ptr(text), nt, ptr(recs_d), ptr(order_d), ptr(out_d[k]), len(want[k]),
+                ptr(totals_d), marks, stream())
 
         def alternate(names):
             us = {k: [] for k in names}
@@ -318,6 +326,9 @@ def part_s(repeats, lines):
 
         us = alternate(("mnx_smiles_pack", "mnx_molfile_pack"))              # the plain pair, measured as before the stereo call existed
         pair = alternate(("mnx_smiles_pack", "mnx_smiles_pack_stereo"))      # then stereo against plain, in a pass of their own
+        like0 = alternate(("marks 0", "mnx_molfile_pack"))                   # marks 0 and 1 measured the way the older calls are above
+        like1 = alternate(("mnx_smiles_pack", "marks 1"))
+        six = alternate(("mnx_smiles_pack", "mnx_smiles_pack_stereo", "marks 0", "marks 1", "marks 2", "marks 3"))   # and every set of marks
         refused = (recs["flags"] & E.SMILES_REFUSED) != 0
         lines.append(f"(s) one call over the packed tables of {n} {what} ({na} atoms, {nb} bonds): device us between two events around "
                      "its three launches, the two calls alternating   median [min .. max]")
@@ -330,6 +341,18 @@ def part_s(repeats, lines):
                      f"marks written: {st_data.count(b'@') - st_data.count(b'@@')} in {int((st_recs['flags'] & E.SMILES_STEREO != 0).sum())} "
                      f"molecules, unresolved in {int((st_recs['flags'] & E.SMILES_STEREO_UNRESOLVED != 0).sum())}, wedges still dropped in "
                      f"{int((st_recs['flags'] & E.SMILES_WEDGES_DROPPED != 0).sum())}")
+        lines.append("  mnx_smiles_pack_marks, marks 0 alternating with mnx_molfile_pack and marks 1 with mnx_smiles_pack, as the older calls above:")
+        lines.append(f"  {'marks 0':22s} {fmt(like0['marks 0'])} us   -> {len(want['marks 0'])} bytes")
+        lines.append(f"  {'marks 1':22s} {fmt(like1['marks 1'])} us   -> {len(want['marks 1'])} bytes")
+        lines.append("  mnx_smiles_pack_marks with every set of marks against the two older calls, the six alternating in a pass of their own:")
+        for k in six:
+            lines.append(f"  {k:22s} {fmt(six[k])} us   -> {len(want[k])} bytes")
+        base = {2: statistics.median(six["mnx_smiles_pack"]), 3: statistics.median(six["mnx_smiles_pack_stereo"])}
+        f2 = ez[2][0]["flags"]
+        lines.append(f"  marks 2 / plain, median {statistics.median(six['marks 2']) / base[2]:.3f}; marks 3 / stereo, median "
+                     f"{statistics.median(six['marks 3']) / base[3]:.3f}; '/' and '\\' written: {ez[2][2].count(b'/') + ez[2][2].count(bytes([92]))} in "
+                     f"{int((f2 & E.SMILES_EZ != 0).sum())} molecules, a candidate unresolved in {int((f2 & E.SMILES_EZ_UNRESOLVED != 0).sum())}, "
+                     f"a configuration implied in {int((f2 & E.SMILES_EZ_IMPLIED != 0).sum())}")
         lines.append(f"  graph SMILES written for {int((~refused).sum())} of {n} molecules ({int(((~refused) & (recs['len'] == 0)).sum())} of "
                      f"them empty), refused {int(refused.sum())}; ring bonds per molecule: median {int(np.median(recs['n_rings']))}, max "
                      f"{int(recs['n_rings'].max())}; molfiles refused: {int((files['len'] == 0).sum())}")
