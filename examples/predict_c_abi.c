@@ -86,6 +86,45 @@ static int print_first_graph_smiles(mnx_engine* eng, int n_images, const mnx_mol
     return rc;
 }
 
+/* Molecule 0 once more, on canonical atom ranks (mnx_smiles_pack_canonical, here without marks): the bytes no longer depend on
+ * the order in which the decoder emitted the atoms, so a host without a toolkit can compare, count and cache them. `rank` is
+ * required (it carries the ranks from the first launch to the others), `sym_class` and `order` are optional. This library's
+ * own ranking: NOT RDKit's canonical SMILES, and the header names the few graphs whose string still depends on the drawing. */
+static int print_first_canonical_smiles(mnx_engine* eng, int n_images, const mnx_mol* mols_dev, const mnx_atom* atoms_dev,
+                                        const mnx_bond* bonds_dev, const char* text_dev, const uint32_t* table_sizes) {
+    uint32_t totals[2] = {0, 0}, *totals_dev = NULL;
+    uint16_t* rank_dev = NULL;
+    mnx_smiles *recs_dev = NULL, rec;
+    char *out_dev = NULL, *out = NULL;
+    int rc, pass;
+    hipMalloc((void**)&recs_dev, (size_t)n_images * sizeof(mnx_smiles));
+    hipMalloc((void**)&totals_dev, sizeof totals);
+    hipMalloc((void**)&rank_dev, ((size_t)table_sizes[0] + 1) * sizeof(uint16_t));
+    for (pass = 0; pass < 2; ++pass) {
+        rc = mnx_smiles_pack_canonical(eng, mols_dev, n_images, atoms_dev, table_sizes[0], bonds_dev, table_sizes[1], text_dev,
+                                       table_sizes[2], recs_dev, /*order=*/NULL, rank_dev, /*sym_class=*/NULL, out_dev,
+                                       pass ? totals[0] : 0, totals_dev, /*marks=*/0, /*stream=*/NULL);
+        if (rc != MNX_OK) { fprintf(stderr, "%s\n", mnx_last_error(eng)); break; }
+        hipMemcpy(totals, totals_dev, sizeof totals, 2);
+        if (pass == 0 && totals[0]) hipMalloc((void**)&out_dev, totals[0]);
+    }
+    if (rc == MNX_OK) {
+        hipMemcpy(&rec, recs_dev, sizeof rec, 2);
+        out = (char*)malloc((size_t)rec.len + 1);
+        if (rec.flags & (MNX_SMILES_TOO_LARGE | MNX_SMILES_BEYOND_TABLES | MNX_SMILES_DUPLICATE_BOND | MNX_SMILES_RING_NUMBERS)) {
+            printf("canonical graph SMILES 0: none (flags 0x%x)\n", (unsigned)rec.flags);
+        } else if (out) {
+            if (rec.len) hipMemcpy(out, out_dev + rec.text0, rec.len, 2);
+            printf("canonical graph SMILES 0: %.*s%s%s\n", (int)rec.len, out,
+                   (rec.flags & MNX_SMILES_CANON_TIE) ? " (a tie broken by the drawing)" : "",
+                   (rec.flags & MNX_SMILES_CANON_TIE_INDEX) ? " (and one by the atom index)" : "");
+        }
+        free(out);
+    }
+    hipFree(recs_dev); hipFree(totals_dev); hipFree(rank_dev); hipFree(out_dev);
+    return rc;
+}
+
 /* The molecules as packed tables (mnx_graph_pack): no tokenizer on the host. A first call with modest capacities; `totals`
  * says what the job needs, so a second call with exactly that is the worst case. Prints molecule 0 with its token SMILES, then its molfile and its graph SMILES. */
 static int print_first_molecule(mnx_engine* eng, int n_images, const int32_t* tokens, const int32_t* lengths,
@@ -132,6 +171,7 @@ static int print_first_molecule(mnx_engine* eng, int n_images, const int32_t* to
         free(atoms); free(bonds); free(text);
         rc = print_first_molfile(eng, n_images, mols_dev, atoms_dev, bonds_dev, text_dev, totals);
         if (rc == MNX_OK) rc = print_first_graph_smiles(eng, n_images, mols_dev, atoms_dev, bonds_dev, text_dev, totals);
+        if (rc == MNX_OK) rc = print_first_canonical_smiles(eng, n_images, mols_dev, atoms_dev, bonds_dev, text_dev, totals);
     }
     hipFree(mols_dev); hipFree(totals_dev); hipFree(atoms_dev); hipFree(bonds_dev); hipFree(text_dev);
     return rc;

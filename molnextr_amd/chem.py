@@ -19,7 +19,10 @@ cannot be installed, so nothing below can be executed or tested here. Behaviour:
 
 The device path can write a SMILES of the predicted graph on request, with '@' / '@@' from the wedges and '/' '\\' at double
 bonds from the coordinate bins (mnx_smiles_pack_marks, include/molnextr_hip.h: this project's own rules, not RDKit's, valid and
-not canonical); nothing in this module uses it.
+not canonical), and on request on canonical atom ranks (mnx_smiles_pack_canonical, the same header): a string that does not
+depend on the numbering of a drawing's atoms, for deduplication and cache keys on a host without a toolkit. That ranking is this
+project's own too — it is NOT the canonical SMILES that `Chem.MolToSmiles` below returns, the two never compare, no toolkit has
+parsed it, and for a few graphs (the header's known limit) the string still depends on the drawing. Nothing in this module uses it.
 """
 import json
 import logging

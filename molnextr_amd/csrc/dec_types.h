@@ -213,6 +213,11 @@ hipError_t molfile_pack_enqueue(const SymbolTables* st_dev, const PackedTables& 
 // mnx_smiles_pack_marks): count, scan and fill, three launches on s
 hipError_t smiles_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, unsigned marks, mnx_smiles* recs,
                                unsigned short* order, char* out, unsigned out_cap, unsigned* totals, hipStream_t s);
+// smiles.hip: the same on canonical atom ranks (mnx_smiles_pack_canonical): the ranks into `rank`, the symmetry classes into
+// `sym_class` (may be null), then count, scan and fill on those ranks; four launches on s
+hipError_t smiles_canonical_enqueue(const SymbolTables* st_dev, const PackedTables& t, unsigned marks, mnx_smiles* recs,
+                                    unsigned short* order, unsigned short* rank, unsigned short* sym_class, char* out,
+                                    unsigned out_cap, unsigned* totals, hipStream_t s);
 hipError_t edges_enqueue(const DecWeights& w, const DecBuffers& bf, const float* hidden, const int* slot_map,
                          const int* atom_idx, const int* n_atoms, int B, int kmax, int row_stride_T,
                          unsigned char* edges, double* scores, hipStream_t s);

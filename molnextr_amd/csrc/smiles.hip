@@ -4,6 +4,8 @@
 // as '*'; no stereo (mnx_smiles_pack), or '@' / '@@' at the marked carbons that a wedge begins at (mnx_smiles_pack_stereo: one
 // more parallel stage, STEREO, behind the ring numbers), or '/' and '\\' at the double bonds off every cycle (mnx_smiles_pack_marks:
 // the stage EZ behind that one). MARKS selects the stages; an instantiation holds none of the code of a stage it does not run.
+// mnx_smiles_pack_canonical puts one kernel in front, canon_rank_kernel: canonical atom ranks by partition refinement, one
+// workgroup per molecule; count and fill (CANON) then walk by those ranks instead of the atom indices.
 //   count  one workgroup per molecule: the walk and the length of its string -> recs[b].len / flags / n_rings
 //   scan   exclusive scan of the lengths over the molecules -> recs[b].text0, totals
 //   fill   one workgroup per molecule: the walk again, the bytes behind text0 and the atoms' positions in `order`
@@ -104,10 +106,207 @@ __device__ __forceinline__ void put_atom(unsigned w, unsigned el, unsigned mark,
 //   low, then flip (cur)   the lowest written position a ring bond reaches from the atom's subtree; then a's flip
 constexpr unsigned ROLE_B = 1, ROLE_A = 2, ROLE_F0 = 4, ROLE_UNRESOLVED = 8;
 
-template <bool FILL, unsigned MARKS>
+// ---- canonical ranks (mnx_smiles_pack_canonical; the rule: molnextr_hip.h) ----
+constexpr unsigned CANON_BITS = MNX_SMILES_CANON_TIE | MNX_SMILES_CANON_TIE_INDEX;
+static_assert(SM_THREADS == 4 * 64, "block_min: four waves of 64");
+
+// the smallest of one value per thread, to every thread; red holds four values. Ends with a barrier.
+__device__ __forceinline__ unsigned long long block_min(unsigned long long v, unsigned long long* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long w = __shfl_xor(v, o, 64);
+        v = w < v ? w : v;
+    }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const unsigned long long a = red[0] < red[1] ? red[0] : red[1], c = red[2] < red[3] ? red[2] : red[3];
+    __syncthreads();
+    return a < c ? a : c;
+}
+
+// One workgroup per molecule: rank[atom0 + a] and sym_class[atom0 + a] (may be null) of every atom, 0xFFFF where the molecule
+// is refused on flag bits 0, 1 or 4, and the tie bits in recs[b].flags (0 without one), which count keeps. The prologue is
+// smiles_kernel's: admission, the atoms' interpretation, degrees and unsorted lists by LDS atomics, the duplicate test. The
+// keys never leave LDS: per round every list entry becomes r(n) * 8 + c (13 bits), each list is rank-sorted, and an atom's
+// new rank is a count over the other atoms, its list compared only with those of equal old rank (which have its degree: the
+// first key holds it and a round only splits classes). No atomic decides a rank: the lists are sorted by value each round.
+__global__ __launch_bounds__(SM_THREADS) void canon_rank_kernel(
+        const PackedTables t, const SymbolTables* __restrict__ st, mnx_smiles* __restrict__ recs,
+        unsigned short* __restrict__ rank, unsigned short* __restrict__ sym_class) {
+    __shared__ unsigned info[SM_MAX], elem[SM_MAX];
+    __shared__ unsigned off[SM_MAX + 1], cnt[SM_MAX];
+    __shared__ unsigned raw[SM_SLOTS];                    // the lists as the bonds came: neighbour, class, owner
+    __shared__ unsigned short key[SM_SLOTS], lst[SM_SLOTS];   // a round's entries r(n) * 8 + c as the lists stand, then sorted
+    __shared__ unsigned long long text8[SM_MAX];          // an atom's written bytes 0-7 (the first in the top byte) and 8-11,
+    __shared__ unsigned text4[SM_MAX];                    // zeros behind the last: a prefix compares smaller
+    __shared__ unsigned xy[SM_MAX];                       // x_bin << 16 | y_bin
+    __shared__ unsigned short rk[SM_MAX];
+    __shared__ unsigned scan[2 * SM_THREADS];
+    __shared__ unsigned long long red[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const Molecule mol = admit_molecule(t, b);
+    const mnx_mol& m = mol.m;
+    auto refuse = [&]() {
+        for (unsigned a = tid; a < m.n_atoms && (unsigned long long)m.atom0 + a < t.n_atom_records; a += SM_THREADS) {
+            rank[m.atom0 + a] = (unsigned short)NONE;
+            if (sym_class) sym_class[m.atom0 + a] = (unsigned short)NONE;
+        }
+        if (tid == 0) recs[b].flags = 0;
+    };
+    if (mol.flags & (PT_TOO_LARGE | PT_BEYOND_TABLES)) { refuse(); return; }
+    const int na = (int)m.n_atoms, nb = (int)m.n_bonds;
+    const mnx_bond* B = mol.B;
+
+    int bad = interpret_atoms<SM_MAX, SM_THREADS>(t, st, mol, info, elem);
+    for (int a = tid; a < SM_MAX; a += SM_THREADS) {
+        cnt[a] = 0;
+        xy[a] = a < na ? (unsigned)mol.A[a].x_bin << 16 | mol.A[a].y_bin : 0u;
+    }
+    __syncthreads();
+    for (int k = tid; k < nb; k += SM_THREADS) {
+        const unsigned i = B[k].i, j = B[k].j;
+        if (i >= (unsigned)na || j >= (unsigned)na || i == j) { bad = 1; continue; }
+        atomicAdd(&cnt[i], 1u);                           // a count does not depend on the order of its increments
+        atomicAdd(&cnt[j], 1u);
+    }
+    if (__syncthreads_or(bad)) { refuse(); return; }
+    {
+        unsigned d[SM_PER], sum = 0, total;
+#pragma unroll
+        for (int q = 0; q < SM_PER; ++q) { d[q] = cnt[SM_PER * tid + q]; sum += d[q]; }
+        unsigned e = block_scan_excl<SM_THREADS>(sum, scan, &total);
+#pragma unroll
+        for (int q = 0; q < SM_PER; ++q) { off[SM_PER * tid + q] = e; cnt[SM_PER * tid + q] = 0; e += d[q]; }
+        if (tid == 0) off[SM_MAX] = total;
+    }
+    __syncthreads();
+    for (int k = tid; k < nb; k += SM_THREADS) {
+        const unsigned i = B[k].i, j = B[k].j, ty = B[k].type;
+        const unsigned cls = (ty == 1 || ty == 5 || ty == 6) ? B_SINGLE : ty == 2 ? B_DOUBLE : ty == 3 ? B_TRIPLE : ty == 4 ? B_AROMATIC : B_ANY;
+        raw[off[i] + atomicAdd(&cnt[i], 1u)] = j | cls << 10 | i << 13;   // any slot of the list: every round sorts by value
+        raw[off[j] + atomicAdd(&cnt[j], 1u)] = i | cls << 10 | j << 13;
+    }
+    __syncthreads();
+    int dup = 0;
+    for (int s = tid; s < 2 * nb; s += SM_THREADS) {
+        const unsigned e = raw[s], mine = slot_nbr(e), a = slot_owner(e);
+        for (unsigned u = off[a]; u < off[a + 1]; ++u) dup |= slot_nbr(raw[u]) == mine && u != (unsigned)s;
+    }
+    if (__syncthreads_or(dup)) { refuse(); return; }
+
+    // ---- the initial key: the atom's written bytes (12 at most: '[', three digits, two letters, 'H' digit, sign and two
+    //      digits, ']'), then its degree ----
+    for (int a = tid; a < na; a += SM_THREADS) {
+        unsigned long long hi = 0;
+        unsigned lo = 0, n = 0;
+        put_atom(info[a], elem[a], 0u, [&](char c) {
+            if (n < 8u) hi |= (unsigned long long)(unsigned char)c << (56u - 8u * n);
+            else if (n < 12u) lo |= (unsigned)(unsigned char)c << (24u - 8u * (n - 8u));
+            ++n;
+        });
+        text8[a] = hi;
+        text4[a] = lo;
+    }
+    __syncthreads();
+    for (int a = tid; a < na; a += SM_THREADS) {
+        const unsigned long long hi = text8[a];
+        const unsigned lo = text4[a], deg = off[a + 1] - off[a];
+        unsigned less = 0;
+        for (int o = 0; o < na; ++o) {
+            const unsigned long long h = text8[o];
+            const unsigned l = text4[o], d = off[o + 1] - off[o];
+            less += h < hi || (h == hi && (l < lo || (l == lo && d < deg)));
+        }
+        rk[a] = (unsigned short)less;
+    }
+    __syncthreads();
+
+    // ---- one refinement round over the ranks in rk: whether a rank changed (a round that splits no class changes none), and
+    //      in vmin the lowest new rank among this thread's atoms that another atom shares ----
+    unsigned vmin = NONE;
+    auto round = [&]() {
+        for (int s = tid; s < 2 * nb; s += SM_THREADS) key[s] = (unsigned short)(rk[slot_nbr(raw[s])] * 8u + slot_cls(raw[s]));
+        __syncthreads();
+        for (int s = tid; s < 2 * nb; s += SM_THREADS) {
+            const unsigned a = slot_owner(raw[s]), mine = key[s];
+            unsigned at = off[a];
+            for (unsigned u = off[a]; u < off[a + 1]; ++u) at += key[u] < mine || (key[u] == mine && u < (unsigned)s);
+            lst[at] = (unsigned short)mine;
+        }
+        __syncthreads();
+        unsigned r[SM_PER], less[SM_PER], same[SM_PER];
+#pragma unroll
+        for (int q = 0; q < SM_PER; ++q) {
+            const int a = tid + q * SM_THREADS;
+            r[q] = a < na ? rk[a] : NONE;                 // NONE: no atom, nothing below is kept
+            less[q] = same[q] = 0;
+        }
+        for (int o = 0; o < na; ++o) {
+            const unsigned ro = rk[o];
+#pragma unroll
+            for (int q = 0; q < SM_PER; ++q) {
+                const int a = tid + q * SM_THREADS;
+                if (ro < r[q]) ++less[q];
+                else if (ro == r[q] && o != a) {
+                    const unsigned la = off[a], lo = off[o], d = off[a + 1] - la;
+                    int c = 0;
+                    for (unsigned k = 0; k < d && c == 0; ++k) c = (int)lst[lo + k] - (int)lst[la + k];
+                    less[q] += c < 0;
+                    same[q] += c == 0;
+                }
+            }
+        }
+        int changed = 0;
+        vmin = NONE;
+#pragma unroll
+        for (int q = 0; q < SM_PER; ++q) {
+            if (tid + q * SM_THREADS >= na) continue;
+            changed |= less[q] != r[q];
+            if (same[q]) vmin = min(vmin, less[q]);
+        }
+        changed = __syncthreads_or(changed);              // every thread has read the old ranks
+#pragma unroll
+        for (int q = 0; q < SM_PER; ++q)
+            if (tid + q * SM_THREADS < na) rk[tid + q * SM_THREADS] = (unsigned short)less[q];
+        __syncthreads();
+        return changed;
+    };
+
+    // ---- refine, break the lowest tie, refine again. The number of distinct ranks rises in every round but the last of a pass
+    //      and at every tie, from 1 at least to n_atoms: at most n_atoms passes, and in each at most n_atoms rounds (over all
+    //      passes at most 2 * n_atoms rounds). A round costs a thread at most 4 * n_atoms list comparisons. ----
+    unsigned flags = 0;
+    for (int pass = 0; pass < na; ++pass) {
+        for (int k = 0; k < na; ++k)
+            if (!round()) break;
+        if (pass == 0 && sym_class)
+            for (int a = tid; a < na; a += SM_THREADS) sym_class[m.atom0 + a] = rk[a];
+        const unsigned long long v = block_min(vmin, red);
+        if (v == NONE) break;                             // no rank is shared: a permutation
+        unsigned long long best = ~0ull;
+        for (int a = tid; a < na; a += SM_THREADS)
+            if (rk[a] == v) best = min(best, (unsigned long long)xy[a] << 16 | (unsigned)a);
+        best = block_min(best, red);                      // the smallest (x_bin, y_bin, atom index) keeps v
+        int by_index = 0;
+        for (int a = tid; a < na; a += SM_THREADS)
+            if (rk[a] == v && (unsigned)a != (unsigned)(best & 0xFFFFu)) {
+                by_index |= xy[a] == (unsigned)(best >> 16);
+                rk[a] = (unsigned short)(v + 1u);
+            }
+        by_index = __syncthreads_or(by_index);
+        flags |= MNX_SMILES_CANON_TIE | (by_index ? MNX_SMILES_CANON_TIE_INDEX : 0u);
+    }
+    for (int a = tid; a < na; a += SM_THREADS) rank[m.atom0 + a] = rk[a];
+    if (tid == 0) recs[b].flags = flags;
+}
+
+// CANON (mnx_smiles_pack_canonical): the walk runs on the ranks that canon_rank_kernel left in `rank` instead of on the atom
+// indices — the first sort of the lists and the order of the roots; every later stage works on written positions as it is.
+template <bool FILL, unsigned MARKS, bool CANON = false>
 __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
         const PackedTables t, const SymbolTables* __restrict__ st, mnx_smiles* __restrict__ recs,
-        unsigned short* __restrict__ order, char* __restrict__ out, unsigned out_cap) {
+        unsigned short* __restrict__ order, char* __restrict__ out, unsigned out_cap, const unsigned short* __restrict__ rank) {
+    __shared__ unsigned short rnk[CANON ? SM_MAX : 1], inv[CANON ? SM_MAX : 1];     // atom -> rank, rank -> atom
     __shared__ unsigned info[SM_MAX], elem[SM_MAX];
     __shared__ unsigned off[SM_MAX + 1], cnt[SM_MAX];     // an atom's list is [off[a], off[a + 1]); cnt: degrees, then fill cursors
     __shared__ unsigned raw[SM_SLOTS], adj[SM_SLOTS];     // the lists as the bonds came, then in ascending neighbour index
@@ -125,7 +324,10 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
     const mnx_mol& m = mol.m;
     const unsigned base_flags = mol.flags & PT_TRUNCATED;
     auto record = [&](unsigned len, unsigned flags, unsigned n_rings) {     // count's result; len 0 with a bit of REFUSED = refused
-        if (tid == 0) { recs[b].len = len; recs[b].flags = flags; recs[b].n_rings = n_rings; }
+        if (tid == 0) {                                   // CANON: the rank kernel left the tie bits there
+            if (CANON) flags |= recs[b].flags & CANON_BITS;
+            recs[b].len = len; recs[b].flags = flags; recs[b].n_rings = n_rings;
+        }
     };
     unsigned text0 = 0;
     if (FILL) {
@@ -143,6 +345,9 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
     }
     const int na = (int)m.n_atoms, nb = (int)m.n_bonds;
     const mnx_bond* B = mol.B;
+    // a record's `type`; CANON: of the record renumbered by the ranks, which has the lower rank as i — where the ends swap,
+    // `type` and `rev` swap (what each end sees of the bond, SLOT_UP / SLOT_DOWN below, stays with the end)
+    auto type_of = [&](int k, unsigned i, unsigned j) -> unsigned { return CANON && rnk[i] > rnk[j] ? B[k].rev : B[k].type; };
 
     // ---- every atom's interpretation and the walk's own per-atom state, every bond's degree counts; a record that points
     //      beyond its table refuses the molecule ----
@@ -153,11 +358,13 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
         pos[a] = (unsigned short)NONE;
         closes[a] = 0;
         paren[a] = 0;
+        if (CANON) rnk[a] = a < na ? rank[m.atom0 + a] : (unsigned short)NONE;
     }
     __syncthreads();
     for (int k = tid; k < nb; k += SM_THREADS) {
-        const unsigned i = B[k].i, j = B[k].j, ty = B[k].type;
+        const unsigned i = B[k].i, j = B[k].j;
         if (i >= (unsigned)na || j >= (unsigned)na || i == j) { bad = 1; continue; }     // i == j: the molfile writer writes it
+        const unsigned ty = type_of(k, i, j);
         wedge |= ty == 5 || ty == 6;
         any |= ty < 1 || ty > 6;
         atomicAdd(&cnt[i], 1u);                           // a count does not depend on the order of its increments
@@ -185,9 +392,9 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
     }
     __syncthreads();
     for (int k = tid; k < nb; k += SM_THREADS) {
-        const unsigned i = B[k].i, j = B[k].j, ty = B[k].type;
+        const unsigned i = B[k].i, j = B[k].j, ty = type_of(k, i, j);
         const unsigned cls = (ty == 1 || ty == 5 || ty == 6) ? B_SINGLE : ty == 2 ? B_DOUBLE : ty == 3 ? B_TRIPLE : ty == 4 ? B_AROMATIC : B_ANY;
-        const unsigned si = STEREO ? slot_seen(ty) : 0u, sj = STEREO ? slot_seen(B[k].rev) : 0u;     // edges[i][j], edges[j][i]
+        const unsigned si = STEREO ? slot_seen(B[k].type) : 0u, sj = STEREO ? slot_seen(B[k].rev) : 0u;     // edges[i][j], edges[j][i]
         raw[off[i] + atomicAdd(&cnt[i], 1u)] = j | cls << 10 | i << 13 | si;  // any slot of the list: the sort below fixes the order
         raw[off[j] + atomicAdd(&cnt[j], 1u)] = i | cls << 10 | j << 13 | sj;
     }
@@ -198,18 +405,30 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
         unsigned rank = 0;
         for (unsigned t = off[a]; t < off[a + 1]; ++t) {
             const unsigned n = slot_nbr(raw[t]);
-            rank += n < mine || (n == mine && t < (unsigned)s);
+            if (CANON) rank += rnk[n] < rnk[mine] || (rnk[n] == rnk[mine] && t < (unsigned)s);
+            else rank += n < mine || (n == mine && t < (unsigned)s);
             dup |= n == mine && t != (unsigned)s;
         }
         adj[off[a] + rank] = e;
     }
     dup = __syncthreads_or(dup);
+    if (CANON) {                                          // a duplicate pair left no ranks (0xFFFF): the search below, which
+        for (int a = tid; a < SM_MAX; a += SM_THREADS) {  // then only counts the components, runs on the indices
+            if (dup) rnk[a] = (unsigned short)a;
+            inv[a] = (unsigned short)a;
+        }
+        __syncthreads();
+        for (int a = tid; a < na; a += SM_THREADS)
+            if (rnk[a] < SM_MAX) inv[rnk[a]] = (unsigned short)a;
+        __syncthreads();
+    }
 
     // ---- the search, by one lane: depth-first from the lowest atom of every component, neighbours in ascending index, an
     //      explicit stack (a path of 999 atoms is 998 deep). It leaves the written order, the tree bonds, the parentheses. ----
     if (tid == 0) {
         unsigned written = 0, comps = 0;
-        for (int root = 0; root < na; ++root) {
+        for (int k = 0; k < na; ++k) {
+            const int root = CANON ? (int)inv[k] : k;
             if (pos[root] != NONE) continue;
             ++comps;
             int sp = 0;
@@ -353,8 +572,10 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
         else {
             marked = __syncthreads_or(marked);
             unresolved = __syncthreads_or(unresolved);
-            for (int k = tid; k < nb; k += SM_THREADS)    // a wedge neither end of which received a mark
-                dropped |= (B[k].type == 5 || B[k].type == 6) && !stk[B[k].i] && !stk[B[k].j];
+            for (int k = tid; k < nb; k += SM_THREADS) {  // a wedge neither end of which received a mark
+                const unsigned ty = type_of(k, B[k].i, B[k].j);
+                dropped |= (ty == 5 || ty == 6) && !stk[B[k].i] && !stk[B[k].j];
+            }
             dropped = __syncthreads_or(dropped);
         }
     }
@@ -463,7 +684,7 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
             };
             for (int k = tid; k < nb; k += SM_THREADS) {  // a double bond without marks of its own between two directed bonds
                 const unsigned i = B[k].i, j = B[k].j;
-                if (B[k].type != 2) continue;
+                if (type_of(k, i, j) != 2) continue;
                 const bool mine = (parent[j] == i && (role[j] & ROLE_B)) || (parent[i] == j && (role[i] & ROLE_B));
                 implied |= !mine && has_directed(i) && has_directed(j);
             }
@@ -544,9 +765,23 @@ hipError_t smiles_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t
                      : marks == 1u ? smiles_kernel<false, 1u> : smiles_kernel<false, 0u>;
     const auto fill = marks == 3u ? smiles_kernel<true, 3u> : marks == 2u ? smiles_kernel<true, 2u>
                     : marks == 1u ? smiles_kernel<true, 1u> : smiles_kernel<true, 0u>;
-    hipLaunchKernelGGL(count, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, order, out, out_cap);
+    hipLaunchKernelGGL(count, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, order, out, out_cap, nullptr);
     hipLaunchKernelGGL(text_scan_kernel<mnx_smiles>, dim3(1), dim3(TEXT_SCAN_THREADS), 0, s, recs, t.n, out_cap, totals);
-    hipLaunchKernelGGL(fill, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, order, out, out_cap);
+    hipLaunchKernelGGL(fill, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, order, out, out_cap, nullptr);
+    return hipGetLastError();
+}
+
+hipError_t smiles_canonical_enqueue(const SymbolTables* st_dev, const PackedTables& t, unsigned marks, mnx_smiles* recs,
+                                    unsigned short* order, unsigned short* rank, unsigned short* sym_class, char* out,
+                                    unsigned out_cap, unsigned* totals, hipStream_t s) {
+    const auto count = marks == 3u ? smiles_kernel<false, 3u, true> : marks == 2u ? smiles_kernel<false, 2u, true>
+                     : marks == 1u ? smiles_kernel<false, 1u, true> : smiles_kernel<false, 0u, true>;
+    const auto fill = marks == 3u ? smiles_kernel<true, 3u, true> : marks == 2u ? smiles_kernel<true, 2u, true>
+                    : marks == 1u ? smiles_kernel<true, 1u, true> : smiles_kernel<true, 0u, true>;
+    hipLaunchKernelGGL(canon_rank_kernel, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, rank, sym_class);
+    hipLaunchKernelGGL(count, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, order, out, out_cap, rank);
+    hipLaunchKernelGGL(text_scan_kernel<mnx_smiles>, dim3(1), dim3(TEXT_SCAN_THREADS), 0, s, recs, t.n, out_cap, totals);
+    hipLaunchKernelGGL(fill, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, order, out, out_cap, rank);
     return hipGetLastError();
 }
 

@@ -28,7 +28,7 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
            "mnx_encode_gray8", "mnx_predict_gray8", "mnx_decode_guided", "mnx_predict_guided", "mnx_patch_embed",
            "mnx_layernorm16", "mnx_merge_ln16", "mnx_cast16", "mnx_sgemm_tn", "mnx_set_vocab_text", "mnx_graph_pack",
            "mnx_set_symbol_tables", "mnx_molfile_pack", "mnx_smiles_pack", "mnx_smiles_pack_stereo",
-           "mnx_smiles_pack_marks")
+           "mnx_smiles_pack_marks", "mnx_smiles_pack_canonical")
 
 # Encoder operand modes (include/molnextr_hip.h MNX_DTYPE_*). "fp16x3" — split fp16 operands, three MFMA terms per
 # product, fp32-class results — is the default: it is the fastest mode whose results stay a factor of four inside north_star's
@@ -130,6 +130,9 @@ SMILES_STEREO, SMILES_STEREO_UNRESOLVED = 256, 512
 # that the drawing did not give: fall back to the string without double-bond marks for that molecule).
 SMILES_EZ, SMILES_EZ_UNRESOLVED, SMILES_EZ_IMPLIED = 1024, 2048, 4096
 SMILES_MARK_TETRAHEDRAL, SMILES_MARK_DOUBLE_BOND = 1, 2     # the `marks` of mnx_smiles_pack_marks
+# mnx_smiles_pack_canonical only: a tie between atoms of one rank was broken by the drawing; in one of them the atom index alone
+# decided (two tied atoms on one bin): only then can the bytes depend on the numbering of the drawing
+SMILES_CANON_TIE, SMILES_CANON_TIE_INDEX = 8192, 16384
 SMILES_REFUSED = SMILES_TOO_LARGE | SMILES_BEYOND_TABLES | SMILES_DUPLICATE_BOND | SMILES_RING_NUMBERS    # no SMILES: len 0
 SMILES_NO_POSITION = 0xFFFF             # `order` of an atom whose molecule got no SMILES
 
@@ -264,6 +267,8 @@ def load_library():
     lib.mnx_smiles_pack_stereo.argtypes = list(lib.mnx_smiles_pack.argtypes)
     lib.mnx_smiles_pack_marks.restype = C.c_int
     lib.mnx_smiles_pack_marks.argtypes = lib.mnx_smiles_pack.argtypes[:-1] + [C.c_uint32, vp]
+    lib.mnx_smiles_pack_canonical.restype = C.c_int
+    lib.mnx_smiles_pack_canonical.argtypes = lib.mnx_smiles_pack.argtypes[:11] + [vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp]
     lib.mnx_atom_scan.restype = C.c_int
     lib.mnx_atom_scan.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.mnx_preprocess.restype = C.c_int
@@ -904,7 +909,8 @@ class Engine:
 
     SMILES_GUESS = 256        # first capacity of smiles_pack per molecule (a drug-like SMILES is well under 200 bytes)
 
-    def smiles_pack(self, rec: dict, cap: Optional[int] = None, stereo: bool = False, double_bonds: bool = False):
+    def smiles_pack(self, rec: dict, cap: Optional[int] = None, stereo: bool = False, double_bonds: bool = False,
+                    canonical: bool = False):
         """graph_pack's records -> (recs [n] SMILES_DTYPE, order uint16 [atoms], bytes): the graph SMILES of molecule b is
         bytes[recs[b]['text0'] : +recs[b]['len']] (mnx_smiles_pack: valid, not canonical, no stereo, pseudo-atoms as '*'; len 0
         and a flag of SMILES_REFUSED for a molecule that gets none), order[atom0 + k] the position of its atom k in that
@@ -914,12 +920,23 @@ class Engine:
         wedge begins at (the rule: include/molnextr_hip.h), flags with SMILES_STEREO / SMILES_STEREO_UNRESOLVED. double_bonds:
         mnx_smiles_pack_marks — '/' and '\\' at the double bonds off every cycle that the coordinate bins resolve (the rule: the
         same header), with or without stereo's marks; flags with SMILES_EZ / SMILES_EZ_UNRESOLVED / SMILES_EZ_IMPLIED. Without
-        it the calls are the ones made before it existed."""
+        it the calls are the ones made before it existed. canonical: mnx_smiles_pack_canonical — the same writer on canonical
+        atom ranks, with the marks that stereo and double_bonds select; returns (recs, order, bytes, rank uint16 [atoms],
+        sym_class uint16 [atoms]): the bytes do not depend on the numbering of a drawing's atoms (flags with SMILES_CANON_TIE /
+        SMILES_CANON_TIE_INDEX; SMILES_NO_POSITION in rank and sym_class where the molecule was not read). This project's own
+        ranking, NOT RDKit's canonical SMILES; the known limit stands in the header."""
         dev = torch.device("cuda", self.device)
         n, na = len(rec["mols"]), len(rec["atoms"])
         tables, args = self._packed_tables(rec)
         recs = torch.empty(n * SMILES_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         order = torch.full((max(na, 1),), -1, dtype=torch.int16, device=dev)     # every entry SMILES_NO_POSITION
+        if canonical:
+            rank, sym_class = torch.full_like(order, -1), torch.full_like(order, -1)
+            marks = (SMILES_MARK_TETRAHEDRAL if stereo else 0) | (SMILES_MARK_DOUBLE_BOND if double_bonds else 0)
+            data = self._sized_text("mnx_smiles_pack_canonical", args + [_ptr(recs), _ptr(order), _ptr(rank), _ptr(sym_class)],
+                                    int(cap) if cap is not None else n * self.SMILES_GUESS, (marks,))
+            return (recs.cpu().numpy().view(SMILES_DTYPE), order[:na].cpu().numpy().view(np.uint16), data,
+                    rank[:na].cpu().numpy().view(np.uint16), sym_class[:na].cpu().numpy().view(np.uint16))
         fn, tail = ("mnx_smiles_pack_stereo" if stereo else "mnx_smiles_pack"), ()
         if double_bonds:
             fn, tail = "mnx_smiles_pack_marks", (SMILES_MARK_DOUBLE_BOND | (SMILES_MARK_TETRAHEDRAL if stereo else 0),)

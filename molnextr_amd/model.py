@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import weights as W
-from .engine import DEFAULT_DTYPE, MOL_TRUNCATED, SMILES_REFUSED, Engine, MnxError
+from .engine import DEFAULT_DTYPE, MOL_TRUNCATED, SMILES_NO_POSITION, SMILES_REFUSED, Engine, MnxError
 from .preprocess import load_image_rgb, transform_image, transform_image_gray
 from .tokenizer import coords_labels, get_tokenizer
 
@@ -99,12 +99,15 @@ def decode_batch(engine: Engine, features: torch.Tensor, tokenizer=None, ref_bat
     return preds
 
 
-def unpack_graphs(mols, atoms, bonds, text, coord_bins: int = 64, with_scores: bool = False) -> List[dict]:
+def unpack_graphs(mols, atoms, bonds, text, coord_bins: int = 64, with_scores: bool = False, rank=None,
+                  sym_class=None) -> List[dict]:
     """The records of mnx_graph_pack (Engine.graph_pack's 'mols', 'atoms', 'bonds' structured arrays and 'text' bytes) as the
     per-image dicts of predict_pipeline. Pure host code: every field is copied, the only arithmetic is the reference's own
     coordinate division bin / (coord_bins - 1). 'chartok_coords' = {smiles, symbols, coords, indices[, atom_scores]};
     'bonds' = [(i, j, type, rev[, score])] in the reference's loop order (i < j ascending) stands where the dense path has
-    'edges' (and 'edge_scores'); with_scores also carries 'overall_score'."""
+    'edges' (and 'edge_scores'); with_scores also carries 'overall_score'. rank, sym_class: the uint16 arrays of
+    Engine.smiles_pack(canonical=True), one entry per atom record — every dict gains 'canonical_rank' and 'symmetry_class', a
+    list per atom (None for a molecule whose atoms hold 0xFFFF: it was not ranked)."""
     text = bytes(text)
     den = coord_bins - 1
     a_sym0, a_len, a_idx = atoms["sym0"].tolist(), atoms["sym_len"].tolist(), atoms["index"].tolist()
@@ -128,6 +131,10 @@ def unpack_graphs(mols, atoms, bonds, text, coord_bins: int = 64, with_scores: b
             pred["overall_score"] = overall[m]
         else:
             pred["bonds"] = list(zip(b_i[b0:b1], b_j[b0:b1], b_t[b0:b1], b_r[b0:b1]))
+        for key, per_atom in (("canonical_rank", rank), ("symmetry_class", sym_class)):
+            if per_atom is not None:
+                v = per_atom[a0:a1].tolist()
+                pred[key] = None if SMILES_NO_POSITION in v else v
         preds.append(pred)
     return preds
 
@@ -135,7 +142,8 @@ def unpack_graphs(mols, atoms, bonds, text, coord_bins: int = 64, with_scores: b
 def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_batch_size: int = 16,
                      max_len: Optional[int] = None, beam_size: int = 1, compute_confidence: bool = False,
                      labels=None, free_run=False, packed: bool = False, molfile: bool = False,
-                     molfile_scale=None, smiles: bool = False, stereo: bool = False, double_bonds: bool = False) -> List[dict]:
+                     molfile_scale=None, smiles: bool = False, stereo: bool = False, double_bonds: bool = False,
+                     canonical: bool = False) -> List[dict]:
     """Encoder + Decoder.decode for MANY images through the engine's continuous-batching path (mnx_predict):
     same per-image dicts as `decode_batch`, identical results (the on-device atom scan equals
     sequence_to_smiles' indices), much higher throughput. compute_confidence=True: mnx_predict_confidence, the same
@@ -160,7 +168,12 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
     the coordinate bins (mnx_smiles_pack_stereo: this library's own rule, include/molnextr_hip.h; no '/' '\\').
     double_bonds (smiles only): the graph SMILES carry '/' and '\\' at the double bonds off every cycle whose substituents the
     coordinate bins put on either side (mnx_smiles_pack_marks: this library's own rule, the same header), with stereo's marks or
-    without; a double bond on a cycle is never marked and no symmetry check is made."""
+    without; a double bond on a cycle is never marked and no symmetry check is made.
+    canonical (smiles only): the graph SMILES are written on canonical atom ranks (mnx_smiles_pack_canonical, with the marks that
+    stereo and double_bonds select), so two numberings of one drawing give the same bytes, and every dict gains 'canonical_rank'
+    and 'symmetry_class', a list per atom (None for a molecule that was not ranked). This library's own ranking: it is NOT
+    RDKit's canonical SMILES, no toolkit has parsed it, and the header states the known limit (a few graphs whose string still
+    depends on the drawing)."""
     tok = (tokenizer or get_tokenizer())["chartok_coords"]
     if molfile and not packed:
         raise ValueError("molfile=True needs packed=True: the molfiles are written from the packed tables")
@@ -170,6 +183,8 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
         raise ValueError("stereo=True needs smiles=True: the marks are written into the graph SMILES")
     if double_bonds and not smiles:
         raise ValueError("double_bonds=True needs smiles=True: the marks are written into the graph SMILES")
+    if canonical and not smiles:
+        raise ValueError("canonical=True needs smiles=True: the ranks order the graph SMILES")
     if packed and beam_size > 1:
         raise NotImplementedError("packed results are built for greedy decoding (beam search keeps the dense path)")
     if labels is not None and beam_size > 1:
@@ -187,14 +202,17 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
         rec = engine.graph_pack(out, keep_device=molfile or smiles)
         if (rec["mols"]["flags"] & MOL_TRUNCATED).any():
             raise RuntimeError(f"a molecule has more atoms than the engine capacity max_atoms={engine.max_atoms}")
-        preds = unpack_graphs(rec["mols"], rec["atoms"], rec["bonds"], rec["text"], tok.maxx, compute_confidence)
+        ranked = engine.smiles_pack(rec, stereo=stereo, double_bonds=double_bonds, canonical=True) if canonical else None
+        preds = unpack_graphs(rec["mols"], rec["atoms"], rec["bonds"], rec["text"], tok.maxx, compute_confidence,
+                              **({"rank": ranked[3], "sym_class": ranked[4]} if canonical else {}))
         if molfile:
             files, data = engine.molfile_pack(rec, scale=molfile_scale)
             for p, f in zip(preds, files):
                 t0, n = int(f["text0"]), int(f["len"])
                 p["molfile"] = data[t0:t0 + n].decode("utf-8", errors="replace") if n else None
         if smiles:
-            recs, order, data = engine.smiles_pack(rec, stereo=stereo, **({"double_bonds": True} if double_bonds else {}))
+            recs, order, data = ranked[:3] if canonical else \
+                engine.smiles_pack(rec, stereo=stereo, **({"double_bonds": True} if double_bonds else {}))
             for p, r, m in zip(preds, recs, rec["mols"]):
                 t0, n, a0, na = int(r["text0"]), int(r["len"]), int(m["atom0"]), int(m["n_atoms"])
                 written = not int(r["flags"]) & SMILES_REFUSED               # an empty molecule is written as the empty string
@@ -270,7 +288,13 @@ class molnextr:
     (mnx_smiles_pack_stereo: this library's own rule after OpenSMILES, not RDKit's; not canonical).
     graph_double_bonds: True (opt-in; needs graph_smiles) = that SMILES carries '/' and '\\' at the double bonds off every cycle
     that the coordinates resolve (mnx_smiles_pack_marks: this library's own rule after OpenSMILES, not RDKit's; no toolkit has
-    parsed it here; double bonds on a cycle and symmetry are not handled)."""
+    parsed it here; double bonds on a cycle and symmetry are not handled).
+    graph_canonical: True (opt-in; needs graph_smiles; combines with graph_stereo / graph_double_bonds) = that SMILES is written
+    on canonical atom ranks (mnx_smiles_pack_canonical), so it does not depend on the order in which the decoder emitted the
+    atoms of a drawing, and every output dict gains 'canonical_rank' and 'symmetry_class', a list per atom (None for a
+    molecule that was not ranked). This library's own ranking: NOT RDKit's canonical SMILES (no toolkit has parsed it, and it
+    never compares with a toolkit's string); the known limit of include/molnextr_hip.h applies — a few graphs whose string
+    still depends on the drawing."""
 
     image_format = "fp32"
     packed_results = False
@@ -278,11 +302,12 @@ class molnextr:
     graph_smiles = False
     graph_stereo = False
     graph_double_bonds = False
+    graph_canonical = False
 
     def __init__(self, model_path, device=None, max_batch: int = 32, dtype: str = DEFAULT_DTYPE,
                  device_preprocess: bool = True, image_format: str = "fp32", packed_results: bool = False,
                  graph_molfile: bool = False, graph_smiles: bool = False, graph_stereo: bool = False,
-                 graph_double_bonds: bool = False):
+                 graph_double_bonds: bool = False, graph_canonical: bool = False):
         if model_path is None:
             raise ValueError("molnextr(model_path): a checkpoint path is required (pass 'synthetic' explicitly for the "
                              "deterministic test checkpoint)")
@@ -313,6 +338,9 @@ class molnextr:
         self.graph_double_bonds = bool(graph_double_bonds)
         if self.graph_double_bonds and not self.graph_smiles:
             raise ValueError("graph_double_bonds=True needs graph_smiles=True: the marks are written into the graph SMILES")
+        self.graph_canonical = bool(graph_canonical)
+        if self.graph_canonical and not self.graph_smiles:
+            raise ValueError("graph_canonical=True needs graph_smiles=True: the ranks order the graph SMILES")
         self.engine = Engine(states["encoder"], states["decoder"], device=device.index or 0, max_batch=max_batch,
                              dtype=dtype, image_format=image_format)
         self.input_size = args.input_size
@@ -495,6 +523,8 @@ class molnextr:
             conf["stereo"] = self.graph_stereo
             if self.graph_double_bonds:
                 conf["double_bonds"] = True
+            if self.graph_canonical:
+                conf["canonical"] = True
         gen = self._prefetched(groups)
         try:
             for x in gen:
@@ -538,6 +568,8 @@ class molnextr:
             if smiles is None and not have_rdkit():           # no RDKit: the device's graph SMILES, when it was asked for
                 smiles = pred.get("graph_smiles")
             d = {"predicted_smiles": smiles, "predicted_molfile": molfile}
+            if "canonical_rank" in pred:                      # graph_canonical: per atom, in the order of atom_sets
+                d["canonical_rank"], d["symmetry_class"] = pred["canonical_rank"], pred["symmetry_class"]
             if return_atoms_bonds:
                 c = pred["chartok_coords"]
                 atoms = []

@@ -19,6 +19,7 @@ is part of the product path and no number is asserted.
 (s) (only when asked for: --part s) graph SMILES written on the device: one mnx_smiles_pack call over the packed tables of 1024
     images between two events, alternating with one mnx_molfile_pack and one mnx_smiles_pack_stereo call over the same tables,
     then mnx_smiles_pack_marks with marks 0, 1, 2 and 3 alternating with the two older SMILES calls in a pass of their own,
+    then mnx_smiles_pack_canonical with each set of marks alternating with mnx_smiles_pack_marks in a pass of their own,
     with how many molecules were written and how many refused per flag; `--smiles-out FILE` writes the table to a file of its
     own.
 The variants of a part alternate inside every repeat (A B A B ...), the table reports the median and the min .. max spread of
@@ -265,6 +266,20 @@ def druglike_records(n_mols, seed=0, centres=False):
     return mols, np.array(A, ATOM_DTYPE), np.array(B, BOND_DTYPE), bytes(text)
 
 
+def longest_ranking_records():
+    """The two molecules on which the ranks of mnx_smiles_pack_canonical take longest, one molecule each: 999 identical isolated
+    atoms (998 ties, each followed by one round) and a ring of 999 (two ties, about a thousand rounds) — [(name, records)]."""
+    from molnextr_amd.engine import ATOM_DTYPE, BOND_DTYPE, MOL_DTYPE
+    out = []
+    for name, pairs in (("999 identical isolated atoms", []), ("a ring of 999 atoms", [(k, k + 1) for k in range(998)] + [(0, 998)])):
+        mols = np.zeros(1, MOL_DTYPE)
+        mols[0] = (0, 999, 0, len(pairs), 0, 999, 0, 0, 0.0)
+        atoms = np.array([(k, 1, k, k // 40, k % 40, 0.0) for k in range(999)], ATOM_DTYPE)
+        bonds = np.array([(i, j, 1, 1, 0.0) for i, j in pairs], BOND_DTYPE).reshape(-1)
+        out.append((name, {"mols": mols, "atoms": atoms, "bonds": bonds, "text": b"C" * 999}))
+    return out
+
+
 def part_s(repeats, lines):
     """Graph SMILES from the device: the three launches of one mnx_smiles_pack call over 1024 molecules between two events, next
     to mnx_molfile_pack and mnx_smiles_pack_stereo over the same tables (the tables stay on the device, the output buffers have
@@ -309,6 +324,17 @@ def part_s(repeats, lines):
                 eng.h, ptr(mols), n, ptr(atoms), na, ptr(bonds), nb, ptr(text), nt, ptr(recs_d), ptr(order_d), ptr(out_d[k]), len(want[k]),
                 ptr(totals_d), marks, stream())
 
+        canon = hasattr(eng.lib, "mnx_smiles_pack_canonical")        # absent from a build of before the call existed
+        if canon:                                                     # mnx_smiles_pack_canonical, every set of marks
+            rank_d, class_d = torch.empty_like(order_d), torch.empty_like(order_d)
+            cn = {marks: eng.smiles_pack(rec, stereo=bool(marks & 1), double_bonds=bool(marks & 2), canonical=True) for marks in range(4)}
+            for marks in range(4):
+                k = f"canonical {marks}"
+                out_d[k], want[k] = torch.empty(max(len(cn[marks][2]), 1), dtype=torch.uint8, device=dev), cn[marks][2]
+                calls[k] = lambda marks=marks, k=k: eng.lib.mnx_smiles_pack_canonical(
+                    eng.h, ptr(mols), n, ptr(atoms), na, ptr(bonds), nb, ptr(text), nt, ptr(recs_d), ptr(order_d), ptr(rank_d),
+                    ptr(class_d), ptr(out_d[k]), len(want[k]), ptr(totals_d), marks, stream())
+
         def alternate(names):
             us = {k: [] for k in names}
             for i in range(repeats + 3):
@@ -329,6 +355,7 @@ def part_s(repeats, lines):
         like0 = alternate(("marks 0", "mnx_molfile_pack"))                   # marks 0 and 1 measured the way the older calls are above
         like1 = alternate(("mnx_smiles_pack", "marks 1"))
         six = alternate(("mnx_smiles_pack", "mnx_smiles_pack_stereo", "marks 0", "marks 1", "marks 2", "marks 3"))   # and every set of marks
+        eight = alternate(tuple(f"{c} {marks}" for marks in range(4) for c in ("marks", "canonical"))) if canon else None
         refused = (recs["flags"] & E.SMILES_REFUSED) != 0
         lines.append(f"(s) one call over the packed tables of {n} {what} ({na} atoms, {nb} bonds): device us between two events around "
                      "its three launches, the two calls alternating   median [min .. max]")
@@ -353,6 +380,21 @@ def part_s(repeats, lines):
                      f"{statistics.median(six['marks 3']) / base[3]:.3f}; '/' and '\\' written: {ez[2][2].count(b'/') + ez[2][2].count(bytes([92]))} in "
                      f"{int((f2 & E.SMILES_EZ != 0).sum())} molecules, a candidate unresolved in {int((f2 & E.SMILES_EZ_UNRESOLVED != 0).sum())}, "
                      f"a configuration implied in {int((f2 & E.SMILES_EZ_IMPLIED != 0).sum())}")
+        if canon:
+            lines.append("  mnx_smiles_pack_canonical (four launches) against mnx_smiles_pack_marks with the same marks, the eight alternating "
+                         "in a pass of their own:")
+            for k in eight:
+                lines.append(f"  {k:22s} {fmt(eight[k])} us   -> {len(want[k])} bytes")
+            ratios = []
+            for marks in range(4):
+                base_us = statistics.median(eight[f"marks {marks}"])
+                r = [v / base_us for v in eight[f"canonical {marks}"]]
+                ratios.append(f"marks {marks}: {statistics.median(r):.2f} [{min(r):.2f} .. {max(r):.2f}]")
+            fc = cn[0][0]["flags"]
+            lines.append("  canonical / marks, each run over the median of marks   median [min .. max]: " + "; ".join(ratios))
+            lines.append(f"  a tie broken in {int((fc & E.SMILES_CANON_TIE != 0).sum())} molecules, one by the atom index alone in "
+                         f"{int((fc & E.SMILES_CANON_TIE_INDEX != 0).sum())}; strings that differ from the uncanonical ones: "
+                         f"{sum(cn[0][2][a:a + l] != data[b:b + l2] for a, l, b, l2 in zip(cn[0][0]['text0'].tolist(), cn[0][0]['len'].tolist(), recs['text0'].tolist(), recs['len'].tolist()))}")
         lines.append(f"  graph SMILES written for {int((~refused).sum())} of {n} molecules ({int(((~refused) & (recs['len'] == 0)).sum())} of "
                      f"them empty), refused {int(refused.sum())}; ring bonds per molecule: median {int(np.median(recs['n_rings']))}, max "
                      f"{int(recs['n_rings'].max())}; molfiles refused: {int((files['len'] == 0).sum())}")
@@ -372,6 +414,24 @@ def part_s(repeats, lines):
     mols, atoms, bonds, text = druglike_records(1024, centres=True)
     measure({"mols": mols, "atoms": atoms, "bonds": bonds, "text": text, "device": (up(mols), up(atoms), up(bonds), up(text))},
             "hand-made molecules of drug-like size with candidate centres")
+    if hasattr(eng.lib, "mnx_smiles_pack_canonical"):
+        lines.append("(s) mnx_smiles_pack_canonical on the two molecules that rank longest, one molecule (one workgroup) per call: device ms "
+                     "between two events around the four launches   median [min .. max]")
+        for name, rec in longest_ranking_records():
+            ms = []
+            for i in range(repeats + 1):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                rec["device"] = eng._packed_tables(rec)[0]
+                torch.cuda.synchronize()
+                a.record()
+                recs, order, data, rank, sym_class = eng.smiles_pack(rec, cap=2048, canonical=True)
+                b.record()
+                torch.cuda.synchronize()
+                assert len(data) >= 999 and sorted(rank.tolist()) == list(range(999))
+                if i:
+                    ms.append(a.elapsed_time(b))
+            lines.append(f"  {name:30s} {fmt(ms)} ms (with the copies of Engine.smiles_pack)   -> {len(data)} bytes, "
+                         f"{len(set(sym_class.tolist()))} symmetry class")
     m.engine.close()
 
 
