@@ -125,6 +125,44 @@ static int print_first_canonical_smiles(mnx_engine* eng, int n_images, const mnx
     return rc;
 }
 
+/* The same molecules with their abbreviation labels ('Ph', 'OMe', 'Boc', ...) replaced by atoms and bonds (mnx_expand_pack), and
+ * molecule 0's canonical SMILES written from THOSE tables: packed tables in, packed tables of the same record types out, so the
+ * writers above take them as they are. A sizing call with capacities 0 (`totals` is complete whatever the capacities), then
+ * the call itself. From a table only (a label without a fragment stays a '*'), the atoms of a fragment share the label's
+ * coordinates, and no toolkit has parsed the result. */
+static int print_first_expanded_smiles(mnx_engine* eng, int n_images, const mnx_mol* mols_dev, const mnx_atom* atoms_dev,
+                                       const mnx_bond* bonds_dev, const char* text_dev, const uint32_t* table_sizes) {
+    uint32_t totals[4] = {0, 0, 0, 0}, *totals_dev = NULL;
+    mnx_mol *mols2_dev = NULL, mol;
+    mnx_atom* atoms2_dev = NULL;
+    mnx_bond* bonds2_dev = NULL;
+    char* text2_dev = NULL;
+    int rc, pass;
+    hipMalloc((void**)&mols2_dev, (size_t)n_images * sizeof(mnx_mol));
+    hipMalloc((void**)&totals_dev, sizeof totals);
+    for (pass = 0; pass < 2; ++pass) {
+        rc = mnx_expand_pack(eng, mols_dev, n_images, atoms_dev, table_sizes[0], bonds_dev, table_sizes[1], text_dev, table_sizes[2],
+                             mols2_dev, atoms2_dev, pass ? totals[0] : 0, bonds2_dev, pass ? totals[1] : 0, text2_dev,
+                             pass ? totals[2] : 0, /*origin=*/NULL, totals_dev, /*stream=*/NULL);
+        if (rc != MNX_OK) { fprintf(stderr, "%s\n", mnx_last_error(eng)); break; }
+        hipMemcpy(totals, totals_dev, sizeof totals, 2);
+        if (pass == 0) {
+            hipMalloc((void**)&atoms2_dev, ((size_t)totals[0] + 1) * sizeof(mnx_atom));
+            hipMalloc((void**)&bonds2_dev, ((size_t)totals[1] + 1) * sizeof(mnx_bond));
+            hipMalloc((void**)&text2_dev, (size_t)totals[2] + 1);
+        }
+    }
+    if (rc == MNX_OK) {
+        hipMemcpy(&mol, mols2_dev, sizeof mol, 2);
+        printf("molecule 0 expanded: %u atoms, %u bonds%s%s%s\n", (unsigned)mol.n_atoms, (unsigned)mol.n_bonds,
+               (mol.flags & MNX_MOL_EXPANDED) ? ", a label replaced" : "", (mol.flags & MNX_MOL_LABEL_LEFT) ? ", a label left" : "",
+               (mol.flags & MNX_MOL_EXPAND_REFUSED) ? ", refused" : "");
+        rc = print_first_canonical_smiles(eng, n_images, mols2_dev, atoms2_dev, bonds2_dev, text2_dev, totals);
+    }
+    hipFree(mols2_dev); hipFree(totals_dev); hipFree(atoms2_dev); hipFree(bonds2_dev); hipFree(text2_dev);
+    return rc;
+}
+
 /* The molecules as packed tables (mnx_graph_pack): no tokenizer on the host. A first call with modest capacities; `totals`
  * says what the job needs, so a second call with exactly that is the worst case. Prints molecule 0 with its token SMILES, then its molfile and its graph SMILES. */
 static int print_first_molecule(mnx_engine* eng, int n_images, const int32_t* tokens, const int32_t* lengths,
@@ -172,6 +210,7 @@ static int print_first_molecule(mnx_engine* eng, int n_images, const int32_t* to
         rc = print_first_molfile(eng, n_images, mols_dev, atoms_dev, bonds_dev, text_dev, totals);
         if (rc == MNX_OK) rc = print_first_graph_smiles(eng, n_images, mols_dev, atoms_dev, bonds_dev, text_dev, totals);
         if (rc == MNX_OK) rc = print_first_canonical_smiles(eng, n_images, mols_dev, atoms_dev, bonds_dev, text_dev, totals);
+        if (rc == MNX_OK) rc = print_first_expanded_smiles(eng, n_images, mols_dev, atoms_dev, bonds_dev, text_dev, totals);
     }
     hipFree(mols_dev); hipFree(totals_dev); hipFree(atoms_dev); hipFree(bonds_dev); hipFree(text_dev);
     return rc;
@@ -199,6 +238,10 @@ int run(const mnx_weight_desc* weights, int n_weights, const float* host_images 
      * (vocab/abbreviations.json); without this call the molfile step below is refused ("mnx_molfile_pack: call
      * mnx_set_symbol_tables first") and run() fails: */
     /* mnx_set_symbol_tables(eng, table_bytes, table_offsets, table_kinds, n_names); */
+    /* ... and, for mnx_expand_pack, the fragments the abbreviation names stand for, as packed tables, with the fragment of every
+     * name of the call above or -1 (vocab/fragments.json through molnextr_amd/fragments.py): */
+    /* mnx_set_fragments(eng, frags, n_frags, frag_atoms, n_frag_atoms, frag_bonds, n_frag_bonds, frag_text, n_frag_text,
+     *                   frag_of_name, n_names); */
 
     const size_t img_elems = (size_t)3 * 384 * 384;
     float* images = NULL;

@@ -410,7 +410,7 @@ int mnx_set_vocab_text(mnx_engine* h, const char* bytes, const uint32_t* offsets
  * size outside the limits, the scores partly set, misaligned records, or no vocabulary text / token classes set. */
 typedef struct mnx_mol {
     uint32_t atom0, n_atoms, bond0, n_bonds, text0, smiles_len;
-    uint32_t flags;             /* bit 0: more atoms than kmax, tables truncated to kmax */
+    uint32_t flags;             /* bit 0: more atoms than kmax, tables truncated to kmax; MNX_MOL_EXPAND* of mnx_expand_pack */
     uint32_t reserved;          /* 0 */
     double overall_score;
 } mnx_mol;
@@ -438,15 +438,16 @@ int mnx_graph_pack(mnx_engine* h, const int32_t* tokens, const int32_t* lengths,
  * by binary search. A name that is in both of the reference's tables ('Z') is listed once, as an R-group: that table is
  * tested first. Copied to the device (host pointers, read before the call returns): a sibling of mnx_set_vocab_text.
  * MNX_ERR_INVALID_ARG (with mnx_last_error): null pointer, n outside 0..512, offsets[0] != 0, a name of 0 or more than 16
- * bytes, names not strictly ascending, a kind other than 1 or 2. */
+ * bytes, names not strictly ascending, a kind other than 1 or 2. A call drops the fragments of an earlier mnx_set_fragments
+ * (they are parallel to the names): set them again. */
 int mnx_set_symbol_tables(mnx_engine* h, const char* bytes, const uint32_t* offsets, const uint8_t* kinds, int32_t n);
 
 /* Molecules as CTfile V2000 molfiles, written on the device from the tables of mnx_graph_pack: the molecule that
  * _convert_graph_to_smiles puts together with RDKit (MolNexTR/chemical.py:880-926: atoms by symbol class, bonds with their
  * wedge classes), at the coordinates it hands to _verify_chirality (:935-939: x * ratio * 10, y * 10, y pointing up) and with
  * the begin atom of a wedge moved to the chiral centre as :262-273 do. No SMILES (that needs RDKit's canonicaliser) and no
- * abbreviation expansion. The format follows the CTfile specification; it is this library's own and not RDKit's writer byte
- * for byte. A post-pass on a post-pass: it reads mols / atoms / bonds / text as mnx_graph_pack wrote them (device pointers,
+ * abbreviation expansion (that is mnx_expand_pack, in front of this call). The format follows the CTfile specification; it is
+ * this library's own and not RDKit's writer byte for byte. A post-pass on a post-pass: it reads mols / atoms / bonds / text as mnx_graph_pack wrote them (device pointers,
  * with the numbers of records / bytes those tables hold), changes none of them and touches no decode state.
  *
  * One atom, from the sym_len bytes of its symbol, in the reference's order of tests: one pair of enclosing '[' ']' is
@@ -757,6 +758,79 @@ int mnx_smiles_pack_canonical(mnx_engine* h, const mnx_mol* mols, int32_t n, con
                               const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes,
                               mnx_smiles* recs, uint16_t* order, uint16_t* rank, uint16_t* sym_class, char* out,
                               uint32_t out_cap, uint32_t* totals, uint32_t marks, void* stream);
+
+/* The fragments that abbreviation labels stand for, for mnx_expand_pack: a label such as 'Ph', 'OMe' or 'Boc' that the tokenizer
+ * emits as ONE atom, as the atoms and bonds it means. The library is data of the caller (molnextr_amd/vocab/fragments.json, written
+ * from what each name means chemically; NOT the reference's abbrs.py), handed over as packed tables of the record types of
+ * mnx_graph_pack: one mnx_mol record is one fragment, with its mnx_atom / mnx_bond records and a text arena of the atom symbols.
+ * Atom 0 of a fragment is the attachment atom: every bond of the label goes to it. Of a fragment record atom0, n_atoms, bond0,
+ * n_bonds, text0 and smiles_len are read (smiles_len only to test that the text lies inside `text`); of an atom sym0 and sym_len;
+ * of a bond i, j, type and rev. frag_of_name [n_names] is parallel to the names of mnx_set_symbol_tables: the fragment of name k,
+ * or -1. The lookup of an atom's symbol therefore is the writers' own lookup in those names: "is an abbreviation" and "has a
+ * fragment" cannot drift apart. Host pointers, validated and copied to the device before the call returns (one allocation, sized
+ * here, freed by mnx_destroy or by the next call; a fragment's bonds are sorted by (i, j) in that copy): a sibling of
+ * mnx_set_symbol_tables, which must have been called, and which drops the fragments when it is called again.
+ * The caller vouches for one thing the library does not test: every fragment atom's symbol is an atom of the SMILES grammar
+ * under the interpretation of mnx_molfile_pack and no name of the tables (molnextr_amd/fragments.py tests it).
+ * MNX_ERR_INVALID_ARG (with mnx_last_error, "mnx_set_fragments: ..."), nothing is copied or launched then: no symbol tables set;
+ * n_frags outside 0..512; n_names not the n of mnx_set_symbol_tables; a null pointer (a table of size 0 may be null); a fragment
+ * of 0 or more than 32 atoms; records that end behind a table; a symbol of 0 or more than 8 bytes or one that ends behind the
+ * text; a bond without i < j < n_atoms, with a type outside 1..4 or with rev != type; the same pair of atoms in two bonds;
+ * frag_of_name[k] outside -1..n_frags-1, or >= 0 for a name that is not of kind 2. */
+int mnx_set_fragments(mnx_engine* h, const mnx_mol* frags, int32_t n_frags, const mnx_atom* atoms, uint32_t na,
+                      const mnx_bond* bonds, uint32_t nb, const char* text, uint32_t nt, const int32_t* frag_of_name,
+                      int32_t n_names);
+
+/* Abbreviation labels replaced by their atoms and bonds, on the device: packed tables of mnx_graph_pack in, packed tables of the
+ * SAME record types out, so that mnx_molfile_pack and the four mnx_smiles_pack calls run on the expanded molecule unchanged — a
+ * label on one drawing and the drawn-out group on another then get the same canonical string. What the reference's
+ * _expand_functional_group does for an alias that is a key of its table; from a table only: the reference's condensed-formula
+ * parser ('CH2CH3', 'N(CH3)2' built by a valence search) and its fragments of zero atoms ('H3', '(H)': delete the atom) are out
+ * of scope, such a label stays. No toolkit has parsed or sanitised the result. A post-pass on a post-pass: it reads the input
+ * tables, changes none of them (the outputs must not overlap them) and touches no decode state.
+ *
+ * Which atoms expand: an atom whose symbol, read as mnx_molfile_pack reads it (one pair of enclosing '[' ']' stripped, the
+ * R-group table first, then the abbreviation table), is an abbreviation (kind 2) whose frag_of_name is >= 0. R-groups, symbols
+ * without a parse and abbreviations without a fragment never expand.
+ * Atoms: the molecule's n_atoms atoms keep their indices. A label at index i becomes atom 0 of its fragment, still at index i.
+ * Fragment atoms 1..m-1 are appended behind the molecule's own atoms, labels in ascending index, fragment atoms in ascending
+ * order. Every atom of a fragment, the one at i included, takes the label's index, x_bin, y_bin and score: the coordinates
+ * COINCIDE inside a fragment — a 2D layout of fragments is out of scope (a molfile of the result is a connection table, not a
+ * drawing; the double-bond marks of mnx_smiles_pack_marks find nothing to resolve inside a fragment).
+ * Bonds: every bond record of the input is kept with its i, j, type, rev and score — a bond of the label goes to the attachment
+ * atom. Every fragment bond is added with its ends mapped to the new indices, rev = type and the score of the label atom. The
+ * table keeps the documented order, i ascending, then j ascending: row i holds the input's records of row i in their order and
+ * behind them, for a label, the fragment's bonds from the attachment atom by ascending j; the rows of the appended atoms hold the
+ * fragment's other bonds.
+ * Text: the text of an output molecule is its atoms' symbols behind one another in the order of the new indices, smiles_len its
+ * length. It is NO LONGER a token SMILES; mnx_atom.sym0 is a span of it as before.
+ * origin uint16 [atom_cap] (may be null): origin[atom0 + k] = the input index of the atom that output atom k came from — k itself
+ * for k < n_atoms of the input, the label's index for an appended atom.
+ * mnx_mol.flags of the output: bit 0 is copied; MNX_MOL_EXPANDED: at least one label was replaced; MNX_MOL_LABEL_LEFT: a
+ * pseudo-atom other than a parsed '*' remains (an R-group, an abbreviation without a fragment, a symbol without a parse);
+ * MNX_MOL_EXPAND_REFUSED: the molecule's records point beyond the tables passed — the test of MNX_MOLFILE_BEYOND_TABLES: atom0 +
+ * n_atoms, bond0 + n_bonds or text0 + smiles_len beyond the sizes passed, a symbol beyond n_text_bytes, a bond whose i or j is no
+ * atom of the molecule —, or its bond records are not sorted by i (a record's i below its predecessor's: the place of a label's
+ * bonds is found by a search in them; mnx_graph_pack writes them sorted), or it has more than 2047 atoms (2047 x 32 atoms always
+ * fit the uint16 indices), or more than 2^32 - 1 bonds afterwards. A refused molecule has n_atoms = n_bonds = smiles_len = 0 in
+ * mols_out. overall_score is copied.
+ * Inputs as mnx_molfile_pack's: mols [n], 1 <= n <= 65536; atoms [n_atom_records], bonds [n_bond_records] (8-byte aligned),
+ * text [n_text_bytes]. mnx_set_symbol_tables and mnx_set_fragments must have been called.
+ * Outputs, device pointers the caller allocated, as mnx_graph_pack's: mols_out [n]; atoms_out [atom_cap], bonds_out [bond_cap]
+ * (8-byte aligned), text_out [text_cap] bytes; totals uint32 [4] = {atoms, bonds, text bytes needed, 1 if any capacity was too
+ * small}. When a capacity is too small nothing is written beyond it (origin follows atom_cap), and mols_out and totals are
+ * complete all the same: read the needed sizes and call again. Deterministic word for word (every position comes from a prefix
+ * scan or a search in sorted records; no atomics); records are written whole, padding bytes as zeros. Three launches,
+ * asynchronous on `stream`, no allocation, no host synchronisation.
+ * MNX_ERR_INVALID_ARG (with mnx_last_error, "mnx_expand_pack: ..."): a null pointer (a table with capacity 0 may be null), n
+ * outside 1..65536, misaligned records, or no symbol tables / fragments set; nothing is launched then. */
+#define MNX_MOL_EXPANDED 2u
+#define MNX_MOL_LABEL_LEFT 4u
+#define MNX_MOL_EXPAND_REFUSED 8u
+int mnx_expand_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
+                    const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_mol* mols_out,
+                    mnx_atom* atoms_out, uint32_t atom_cap, mnx_bond* bonds_out, uint32_t bond_cap, char* text_out,
+                    uint32_t text_cap, uint16_t* origin, uint32_t* totals, void* stream);
 
 /* mnx_predict with beam search (BASELINE config 5): the same inputs and outputs, every reference batch searched as
  * mnx_decode_beam does (n_best = 1: the best hypothesis; atom positions and the bond head run on ITS tokens and decoder

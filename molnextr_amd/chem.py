@@ -22,7 +22,10 @@ bonds from the coordinate bins (mnx_smiles_pack_marks, include/molnextr_hip.h: t
 not canonical), and on request on canonical atom ranks (mnx_smiles_pack_canonical, the same header): a string that does not
 depend on the numbering of a drawing's atoms, for deduplication and cache keys on a host without a toolkit. That ranking is this
 project's own too — it is NOT the canonical SMILES that `Chem.MolToSmiles` below returns, the two never compare, no toolkit has
-parsed it, and for a few graphs (the header's known limit) the string still depends on the drawing. Nothing in this module uses it.
+parsed it, and for a few graphs (the header's known limit) the string still depends on the drawing. On request the device also
+replaces abbreviation labels by their atoms and bonds before it writes (mnx_expand_pack, vocab/fragments.json): the table branch
+of `_expand_functional_group` without a toolkit — from a table only (no condensed-formula parser, no zero-atom fragments), the
+atoms of a fragment on the label's coordinates, sanitised by nothing. Nothing in this module uses either.
 """
 import json
 import logging

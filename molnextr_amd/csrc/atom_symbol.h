@@ -131,8 +131,10 @@ __device__ __forceinline__ bool bytes_are(const unsigned char* s, int n, const c
 
 // One atom: the order of tests of chemical.py:886-903 — brackets stripped, R-group table, abbreviation table, and only then
 // the whole symbol as a SMILES atom; no parse = pseudo-atom. *sym receives the three bytes of a molfile's symbol column: the
-// element capitalised ('R' and a blank for a parsed '*'), "R#" for a numbered R-group, "R" for every other pseudo-atom.
-__device__ __forceinline__ unsigned interpret_atom(const SymbolTables* __restrict__ st, const unsigned char* s, int n, unsigned* sym) {
+// element capitalised ('R' and a blank for a parsed '*'), "R#" for a numbered R-group, "R" for every other pseudo-atom. *name
+// receives the index of the stripped symbol in the name tables, -1 when it is in neither (expand.hip asks which name it was).
+__device__ __forceinline__ unsigned interpret_atom(const SymbolTables* __restrict__ st, const unsigned char* s, int n, unsigned* sym,
+                                                   int* name) {
     const bool strip = n >= 2 && s[0] == '[' && s[n - 1] == ']';
     const unsigned char* in = strip ? s + 1 : s;
     const int ni = strip ? n - 2 : n;
@@ -140,6 +142,7 @@ __device__ __forceinline__ unsigned interpret_atom(const SymbolTables* __restric
                         bytes_are(s, n, "[C@@H]", 6);
     unsigned w = chiral ? 8u : 0u;
     const int hit = table_find(st, in, ni);
+    *name = hit;
     unsigned char e0 = 'R', e1 = ' ';
     bool lower = false;
     int h = 0, q = 0, iso = 0;
@@ -163,6 +166,11 @@ __device__ __forceinline__ unsigned interpret_atom(const SymbolTables* __restric
     w |= (num ? CLS_RNUM : CLS_PSEUDO) | (unsigned)(15) << 8 | num << 13 | (unsigned)al << 23 | (strip ? 1u << 30 : 0u);
     *sym = 'R' | (unsigned)(num ? '#' : ' ') << 8 | (unsigned)' ' << 16;
     return w;
+}
+
+__device__ __forceinline__ unsigned interpret_atom(const SymbolTables* __restrict__ st, const unsigned char* s, int n, unsigned* sym) {
+    int name;
+    return interpret_atom(st, s, n, sym, &name);
 }
 
 // ---- one molecule of the packed tables (PackedTables, dec_types.h) ----

@@ -218,6 +218,25 @@ hipError_t smiles_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t
 hipError_t smiles_canonical_enqueue(const SymbolTables* st_dev, const PackedTables& t, unsigned marks, mnx_smiles* recs,
                                     unsigned short* order, unsigned short* rank, unsigned short* sym_class, char* out,
                                     unsigned out_cap, unsigned* totals, hipStream_t s);
+// the fragment library (mnx_set_fragments) as the device holds it: ONE allocation — the table of fragment indices parallel to
+// SymbolTables' names, the fragment records, then their atoms, bonds and symbol bytes. The host has validated all of it and has
+// sorted every fragment's bonds by (i, j), so the bonds from atom 0 (the attachment atom) are the first n_bonds0 of a fragment.
+struct FragRec {
+    unsigned atom0, bond0, text0;       // where its atoms / bonds / symbol bytes begin in the three arrays
+    unsigned short n_atoms, n_bonds, n_bonds0, text_len;    // 1..32 atoms; text_len: its symbols behind one another
+};
+struct FragView {                       // passed to kernels by value
+    const int* frag_of_name;            // [SymbolTables::n] fragment index or -1
+    const FragRec* frag;
+    const unsigned* atoms;              // sym0 (bytes from the fragment's text0) | sym_len << 16
+    const unsigned* bonds;              // i | j << 8 | type << 16
+    const unsigned char* text;
+};
+// expand.hip: the molecules of t with every abbreviation label that has a fragment replaced by the fragment's atoms and bonds,
+// as packed tables of the same record types (mnx_expand_pack): count, scan and fill, three launches on s
+hipError_t expand_pack_enqueue(const SymbolTables* st_dev, const FragView& fv, const PackedTables& t, mnx_mol* mols,
+                               mnx_atom* atoms, unsigned atom_cap, mnx_bond* bonds, unsigned bond_cap, char* text,
+                               unsigned text_cap, unsigned short* origin, unsigned* totals, hipStream_t s);
 hipError_t edges_enqueue(const DecWeights& w, const DecBuffers& bf, const float* hidden, const int* slot_map,
                          const int* atom_idx, const int* n_atoms, int B, int kmax, int row_stride_T,
                          unsigned char* edges, double* scores, hipStream_t s);

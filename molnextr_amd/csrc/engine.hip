@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <time.h>
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -107,6 +108,10 @@ struct mnx_engine {
     bool have_vt = false;
     SymbolTables* st_dev = nullptr;     // R-group and abbreviation names (mnx_set_symbol_tables), read by mnx_molfile_pack and mnx_smiles_pack
     bool have_st = false;
+    int st_n = 0;                       // names of the last mnx_set_symbol_tables
+    void* frag_dev = nullptr;           // the fragment library (mnx_set_fragments): one allocation, fv points into it; read by mnx_expand_pack
+    FragView fv{};
+    bool have_frag = false;
     int n_chunk_bufs = 0;
     bool use_graph = true;
     // greedy ticks of up to dec_fused_max rows run as three launches per layer (dec_fused.hip): dec_tile rows per workgroup in
@@ -307,6 +312,7 @@ void mnx_destroy(mnx_engine* h) {
     }
     for (auto& ev : h->ev_pool) { hipEventDestroy(ev.a); hipEventDestroy(ev.b); }
     for (void* p : h->allocs) hipFree(p);
+    if (h->frag_dev) hipFree(h->frag_dev);
     if (h->host_flag) hipHostFree(h->host_flag);
     delete h;
 }
@@ -1355,10 +1361,102 @@ int mnx_set_symbol_tables(mnx_engine* h, const char* bytes, const uint32_t* offs
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipMemcpy(h->st_dev, st.get(), sizeof(SymbolTables), hipMemcpyHostToDevice));
     h->have_st = true;
+    h->st_n = n;
+    h->have_frag = false;       // a fragment table is parallel to the names it was set for
     return MNX_OK;
 }
 
-// What mnx_molfile_pack, mnx_smiles_pack, mnx_smiles_pack_stereo and mnx_smiles_pack_marks test before they launch, in the order in which a call refused for two reasons
+int mnx_set_fragments(mnx_engine* h, const mnx_mol* frags, int32_t n_frags, const mnx_atom* atoms, uint32_t na, const mnx_bond* bonds,
+                      uint32_t nb, const char* text, uint32_t nt, const int32_t* frag_of_name, int32_t n_names) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    auto bad = [&](const std::string& m) { h->err = "mnx_set_fragments: " + m; return MNX_ERR_INVALID_ARG; };
+    if (!h->have_st) return bad("call mnx_set_symbol_tables first");
+    if (n_frags < 0 || n_frags > 512) return bad("n_frags outside 0..512");
+    if (n_names != h->st_n) return bad("n_names must be the n of mnx_set_symbol_tables (" + std::to_string(h->st_n) + ")");
+    if ((n_frags > 0 && !frags) || (na && !atoms) || (nb && !bonds) || (nt && !text) || (n_names > 0 && !frag_of_name))
+        return bad("null pointer");
+    // the device copy, put together on the host: bonds sorted by (i, j), every fragment's symbols behind one another
+    std::vector<FragRec> rec((size_t)n_frags);
+    std::vector<unsigned> fa, fb;
+    std::vector<unsigned char> ft;
+    for (int f = 0; f < n_frags; ++f) {
+        const mnx_mol& m = frags[f];
+        const std::string who = "fragment " + std::to_string(f);
+        if (m.n_atoms < 1 || m.n_atoms > 32) return bad(who + " has " + std::to_string(m.n_atoms) + " atoms; 1 to 32 required");
+        if ((uint64_t)m.atom0 + m.n_atoms > na || (uint64_t)m.bond0 + m.n_bonds > nb || (uint64_t)m.text0 + m.smiles_len > nt)
+            return bad(who + ": its records end behind a table");
+        FragRec& r = rec[(size_t)f];
+        r.atom0 = (unsigned)fa.size(); r.bond0 = (unsigned)fb.size(); r.text0 = (unsigned)ft.size();
+        r.n_atoms = (unsigned short)m.n_atoms;
+        unsigned len = 0;
+        for (uint32_t a = 0; a < m.n_atoms; ++a) {
+            const mnx_atom& x = atoms[m.atom0 + a];
+            if (x.sym_len < 1 || x.sym_len > 8) return bad(who + ", atom " + std::to_string(a) + ": a symbol has 1 to 8 bytes");
+            if ((uint64_t)m.text0 + x.sym0 + x.sym_len > nt) return bad(who + ", atom " + std::to_string(a) + ": its symbol ends behind the text");
+            fa.push_back(len | (unsigned)x.sym_len << 16);
+            ft.insert(ft.end(), (const unsigned char*)text + m.text0 + x.sym0, (const unsigned char*)text + m.text0 + x.sym0 + x.sym_len);
+            len += x.sym_len;
+        }
+        r.text_len = (unsigned short)len;
+        std::vector<unsigned> own;
+        for (uint32_t k = 0; k < m.n_bonds; ++k) {
+            const mnx_bond& x = bonds[m.bond0 + k];
+            const std::string which = who + ", bond " + std::to_string(k);
+            if (!(x.i < x.j && x.j < m.n_atoms)) return bad(which + ": i < j < n_atoms required");
+            if (x.type < 1 || x.type > 4 || x.rev != x.type) return bad(which + ": type 1 to 4 and rev == type required");
+            own.push_back((unsigned)x.i | (unsigned)x.j << 8 | (unsigned)x.type << 16);
+        }
+        std::sort(own.begin(), own.end(), [](unsigned p, unsigned q) { return ((p & 0xff) << 8 | (p >> 8 & 0xff)) < ((q & 0xff) << 8 | (q >> 8 & 0xff)); });
+        unsigned n0 = 0;
+        for (size_t k = 0; k < own.size(); ++k) {
+            if (k > 0 && (own[k] & 0xffff) == (own[k - 1] & 0xffff)) return bad(who + ": the same pair of atoms in two bonds");
+            n0 += (own[k] & 0xff) == 0;
+        }
+        r.n_bonds = (unsigned short)own.size();
+        r.n_bonds0 = (unsigned short)n0;
+        fb.insert(fb.end(), own.begin(), own.end());
+    }
+    std::vector<unsigned char> kinds((size_t)std::max(n_names, 1));
+    {   // the kinds as the device holds them
+        auto st = std::make_unique<SymbolTables>();
+        HIPCHK(h, hipSetDevice(h->device));
+        HIPCHK(h, hipMemcpy(st.get(), h->st_dev, sizeof(SymbolTables), hipMemcpyDeviceToHost));
+        memcpy(kinds.data(), st->kind, (size_t)n_names);
+    }
+    for (int k = 0; k < n_names; ++k) {
+        if (frag_of_name[k] < -1 || frag_of_name[k] >= n_frags) return bad("frag_of_name[" + std::to_string(k) + "] outside -1.." + std::to_string(n_frags - 1));
+        if (frag_of_name[k] >= 0 && kinds[(size_t)k] != 2) return bad("frag_of_name[" + std::to_string(k) + "]: only an abbreviation (kind 2) takes a fragment");
+    }
+    // one allocation: frag_of_name | records | atoms | bonds | text, each part 8-byte aligned
+    auto up8 = [](size_t v) { return (v + 7) & ~(size_t)7; };
+    const size_t o_rec = up8((size_t)std::max(n_names, 1) * sizeof(int)), o_atoms = o_rec + up8(std::max(rec.size(), (size_t)1) * sizeof(FragRec));
+    const size_t o_bonds = o_atoms + up8(std::max(fa.size(), (size_t)1) * 4), o_text = o_bonds + up8(std::max(fb.size(), (size_t)1) * 4);
+    const size_t total = o_text + up8(std::max(ft.size(), (size_t)1));
+    std::vector<unsigned char> blob(total, 0);
+    if (n_names) memcpy(blob.data(), frag_of_name, (size_t)n_names * sizeof(int));
+    if (!rec.empty()) memcpy(blob.data() + o_rec, rec.data(), rec.size() * sizeof(FragRec));
+    if (!fa.empty()) memcpy(blob.data() + o_atoms, fa.data(), fa.size() * 4);
+    if (!fb.empty()) memcpy(blob.data() + o_bonds, fb.data(), fb.size() * 4);
+    if (!ft.empty()) memcpy(blob.data() + o_text, ft.data(), ft.size());
+    void* dev = nullptr;
+    HIPCHK(h, hipMalloc(&dev, total));
+    if (hipError_t e = hipMemcpy(dev, blob.data(), total, hipMemcpyHostToDevice); e != hipSuccess) {
+        hipFree(dev);
+        h->err = std::string("mnx_set_fragments: hipMemcpy: ") + hipGetErrorString(e);
+        return MNX_ERR_HIP;
+    }
+    if (h->frag_dev) {          // an earlier table may still be read by launches in flight
+        (void)hipDeviceSynchronize();
+        hipFree(h->frag_dev);
+    }
+    h->frag_dev = dev;
+    const unsigned char* d = (const unsigned char*)dev;
+    h->fv = FragView{(const int*)d, (const FragRec*)(d + o_rec), (const unsigned*)(d + o_atoms), (const unsigned*)(d + o_bonds), d + o_text};
+    h->have_frag = true;
+    return MNX_OK;
+}
+
+// What mnx_molfile_pack, mnx_expand_pack, mnx_smiles_pack, mnx_smiles_pack_stereo and mnx_smiles_pack_marks test before they launch, in the order in which a call refused for two reasons
 // reports them. The entry point tests its own pointers (outs_null, outs_skew); `aligned` is how its alignment message ends.
 static int check_packed_tables(mnx_engine* h, const char* fn, const PackedTables& t, bool outs_null, bool outs_skew,
                                const char* aligned) {
@@ -1383,6 +1481,24 @@ int mnx_molfile_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_at
     if (h->cfg.coord_bins < 2) { h->err = "mnx_molfile_pack: cfg.coord_bins must be at least 2"; return MNX_ERR_INVALID_ARG; }
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, molfile_pack_enqueue(h->st_dev, t, scale, h->cfg.coord_bins, files, out, out_cap, totals, (hipStream_t)stream));
+    return MNX_OK;
+}
+
+int mnx_expand_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
+                    const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_mol* mols_out,
+                    mnx_atom* atoms_out, uint32_t atom_cap, mnx_bond* bonds_out, uint32_t bond_cap, char* text_out, uint32_t text_cap,
+                    uint16_t* origin, uint32_t* totals, void* stream) {
+    const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
+    if (int rc = check_packed_tables(h, "mnx_expand_pack", t,
+                                     !mols_out || !totals || (!atoms_out && atom_cap) || (!bonds_out && bond_cap) || (!text_out && text_cap),
+                                     (((uintptr_t)mols_out | (uintptr_t)atoms_out | (uintptr_t)bonds_out) & 7) != 0 ||
+                                         ((uintptr_t)totals & 3) != 0 || ((uintptr_t)origin & 1) != 0,
+                                     "the output tables too, totals 4-byte, origin 2-byte"))
+        return rc;
+    if (!h->have_frag) { h->err = "mnx_expand_pack: call mnx_set_fragments first"; return MNX_ERR_INVALID_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, expand_pack_enqueue(h->st_dev, h->fv, t, mols_out, atoms_out, atom_cap, bonds_out, bond_cap, text_out, text_cap, origin,
+                                  totals, (hipStream_t)stream));
     return MNX_OK;
 }
 

@@ -2,7 +2,7 @@
 // CharTokenizer.sequence_to_smiles (reference tokenization.py:464-515) and the pair loop of predict_images (model.py:135-143)
 // derive on the host, as three launches on the device.
 //   count  one workgroup per image: atoms, bonds and SMILES bytes of the image -> mols[b]
-//   scan   exclusive scan of the three counts over the images -> atom0 / bond0 / text0 of every image, totals
+//   scan   exclusive scan of the three counts over the images -> atom0 / bond0 / text0 of every image, totals (block_scan.h)
 //   fill   one workgroup per image: text, atom records, bond records behind those offsets
 // Every position in the tables follows from a prefix scan: no atomics, the output is the same word for word on every run.
 // Records are written as whole 64-bit words, padding bytes as zeros.
@@ -23,7 +23,6 @@ namespace {
 constexpr int GP_THREADS = 256;
 constexpr int GP_T = 512;            // ids of a row held in LDS (mnx_confidence's limit)
 constexpr int GP_ATOMS = 256;        // atoms a row of GP_T ids can hold (an atom takes at least 3 ids): LDS span tables
-constexpr int SCAN_THREADS = 1024;
 
 // What count and fill both need of one row, held in LDS.
 struct RowLds {
@@ -99,36 +98,6 @@ __global__ __launch_bounds__(GP_THREADS) void graph_count_kernel(
     block_scan_excl<GP_THREADS>(nb, scan, &bond_total);
     if (tid == 0)
         store_mol_counts(&mols[row], (unsigned)k, bond_total, text_total, walk_k > kmax ? 1u : 0u, overall ? overall[row] : 0.0);
-}
-
-// atom0 / bond0 / text0 of every image: an exclusive scan over the images in tiles of SCAN_THREADS with a running carry, by ONE
-// workgroup (n images are a few thousand words). 64-bit carries: a total beyond 2^32 - 1 saturates and sets totals[3].
-__global__ __launch_bounds__(SCAN_THREADS) void graph_scan_kernel(mnx_mol* __restrict__ mols, int n, unsigned atom_cap,
-                                                                  unsigned bond_cap, unsigned text_cap,
-                                                                  unsigned* __restrict__ totals) {
-    __shared__ unsigned scan[2 * SCAN_THREADS];
-    const int tid = threadIdx.x;
-    unsigned long long ca = 0, cb = 0, ct = 0;
-    for (int base = 0; base < n; base += SCAN_THREADS) {
-        const int b = base + tid;
-        const unsigned a = b < n ? mols[b].n_atoms : 0u, bo = b < n ? mols[b].n_bonds : 0u, t = b < n ? mols[b].smiles_len : 0u;
-        unsigned ta, tb, tt;
-        const unsigned ea = block_scan_excl<SCAN_THREADS>(a, scan, &ta);
-        const unsigned eb = block_scan_excl<SCAN_THREADS>(bo, scan, &tb);
-        const unsigned et = block_scan_excl<SCAN_THREADS>(t, scan, &tt);
-        if (b < n) {
-            mols[b].atom0 = (unsigned)min(ca + ea, 0xffffffffull);
-            mols[b].bond0 = (unsigned)min(cb + eb, 0xffffffffull);
-            mols[b].text0 = (unsigned)min(ct + et, 0xffffffffull);
-        }
-        ca += ta; cb += tb; ct += tt;
-    }
-    if (tid == 0) {
-        totals[0] = (unsigned)min(ca, 0xffffffffull);
-        totals[1] = (unsigned)min(cb, 0xffffffffull);
-        totals[2] = (unsigned)min(ct, 0xffffffffull);
-        totals[3] = (ca > atom_cap || cb > bond_cap || ct > text_cap) ? 1u : 0u;
-    }
 }
 
 __global__ __launch_bounds__(GP_THREADS) void graph_fill_kernel(
@@ -226,7 +195,7 @@ hipError_t graph_pack_enqueue(const TokenClasses* tc_dev, const VocabText* vt_de
                               unsigned text_cap, unsigned* totals, hipStream_t s) {
     hipLaunchKernelGGL(graph_count_kernel, dim3(n), dim3(GP_THREADS), 0, s, tokens, lens, tc_dev, vt_dev, T, kmax, n_atoms,
                        edges, overall, mols);
-    hipLaunchKernelGGL(graph_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, mols, n, atom_cap, bond_cap, text_cap, totals);
+    hipLaunchKernelGGL(mol_scan_kernel, dim3(1), dim3(MOL_SCAN_THREADS), 0, s, mols, n, atom_cap, bond_cap, text_cap, totals);
     hipLaunchKernelGGL(graph_fill_kernel, dim3(n), dim3(GP_THREADS), 0, s, tokens, lens, tc_dev, vt_dev, T, kmax, atom_idx,
                        n_atoms, edges, atom_scores, edge_scores, mols, (unsigned long long*)atoms, atom_cap,
                        (unsigned long long*)bonds, bond_cap, text, text_cap);

@@ -28,7 +28,7 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
            "mnx_encode_gray8", "mnx_predict_gray8", "mnx_decode_guided", "mnx_predict_guided", "mnx_patch_embed",
            "mnx_layernorm16", "mnx_merge_ln16", "mnx_cast16", "mnx_sgemm_tn", "mnx_set_vocab_text", "mnx_graph_pack",
            "mnx_set_symbol_tables", "mnx_molfile_pack", "mnx_smiles_pack", "mnx_smiles_pack_stereo",
-           "mnx_smiles_pack_marks", "mnx_smiles_pack_canonical")
+           "mnx_smiles_pack_marks", "mnx_smiles_pack_canonical", "mnx_set_fragments", "mnx_expand_pack")
 
 # Encoder operand modes (include/molnextr_hip.h MNX_DTYPE_*). "fp16x3" — split fp16 operands, three MFMA terms per
 # product, fp32-class results — is the default: it is the fastest mode whose results stay a factor of four inside north_star's
@@ -113,6 +113,9 @@ ATOM_DTYPE = np.dtype([("sym0", "<u4"), ("sym_len", "<u2"), ("index", "<u2"), ("
                        ("score", "<f8")], align=True)
 BOND_DTYPE = np.dtype([("i", "<u2"), ("j", "<u2"), ("type", "u1"), ("rev", "u1"), ("score", "<f8")], align=True)
 MOL_TRUNCATED = 1                       # mnx_mol.flags bit 0: more atoms than kmax, the tables hold the first kmax
+# mnx_mol.flags of mnx_expand_pack's output (MNX_MOL_EXPAND*): a label was replaced by its fragment; a pseudo-atom other than a
+# parsed '*' remains; the molecule was refused (records beyond the tables, bonds not sorted by i, more than 2047 atoms): no records
+MOL_EXPANDED, MOL_LABEL_LEFT, MOL_EXPAND_REFUSED = 2, 4, 8
 MOLFILE_DTYPE = np.dtype([("text0", "<u4"), ("len", "<u4"), ("flags", "<u4"), ("reserved", "<u4")], align=True)
 # mnx_molfile.flags (MNX_MOLFILE_*): no molfile (len 0) for more than 999 atoms / bonds or records beyond the tables passed;
 # the molecule holds a pseudo-atom (R-group, abbreviation, unparsable symbol); a copy of MOL_TRUNCATED
@@ -269,6 +272,11 @@ def load_library():
     lib.mnx_smiles_pack_marks.argtypes = lib.mnx_smiles_pack.argtypes[:-1] + [C.c_uint32, vp]
     lib.mnx_smiles_pack_canonical.restype = C.c_int
     lib.mnx_smiles_pack_canonical.argtypes = lib.mnx_smiles_pack.argtypes[:11] + [vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp]
+    lib.mnx_set_fragments.restype = C.c_int
+    lib.mnx_set_fragments.argtypes = [vp, vp, i32, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, i32]
+    lib.mnx_expand_pack.restype = C.c_int
+    lib.mnx_expand_pack.argtypes = [vp, vp, i32, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint32, vp, C.c_uint32,
+                                    vp, C.c_uint32, vp, vp, vp]
     lib.mnx_atom_scan.restype = C.c_int
     lib.mnx_atom_scan.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.mnx_preprocess.restype = C.c_int
@@ -394,6 +402,7 @@ class Engine:
         self._set_token_classes()
         self._set_vocab_text()
         self._set_symbol_tables()
+        self._set_fragments()
         self.n_feat = enc.num_features
         g = enc.img_size // enc.patch >> (len(enc.depths) - 1)
         self.n_mem = g * g
@@ -428,6 +437,28 @@ class Engine:
         text, offsets, kinds, n = symbol_tables()
         self._check(self.lib.mnx_set_symbol_tables(self.h, text, offsets.ctypes.data, kinds.ctypes.data, n),
                     "mnx_set_symbol_tables")
+        self._have_symbol_tables = True
+
+    _have_symbol_tables = False
+
+    def _set_fragments(self):
+        """Hands the fragment library (vocab/fragments.json) to the library: what expand_pack replaces a label by. The table is
+        parallel to the names of _set_symbol_tables: a handle that was given no names takes no fragments."""
+        if not self._have_symbol_tables:
+            return
+        from .fragments import fragment_tables
+        self.set_fragments(*fragment_tables())
+
+    def set_fragments(self, mols, atoms, bonds, text, frag_of_name):
+        """mnx_set_fragments: packed tables of fragments (one MOL_DTYPE record each) and the int32 table parallel to the names of
+        symbol_tables(). Construction sets fragments.fragment_tables(); a caller with a library of its own replaces it here."""
+        mols, atoms, bonds = (np.ascontiguousarray(a) for a in (mols, atoms, bonds))
+        fo = np.ascontiguousarray(frag_of_name, dtype=np.int32)
+        text = bytes(text)
+        self._check(self.lib.mnx_set_fragments(self.h, mols.ctypes.data if len(mols) else None, len(mols),
+                                               atoms.ctypes.data if len(atoms) else None, len(atoms),
+                                               bonds.ctypes.data if len(bonds) else None, len(bonds), text if text else None,
+                                               len(text), fo.ctypes.data if len(fo) else None, len(fo)), "mnx_set_fragments")
 
     def close(self):
         if getattr(self, "h", None):
@@ -942,6 +973,46 @@ class Engine:
             fn, tail = "mnx_smiles_pack_marks", (SMILES_MARK_DOUBLE_BOND | (SMILES_MARK_TETRAHEDRAL if stereo else 0),)
         data = self._sized_text(fn, args + [_ptr(recs), _ptr(order)], int(cap) if cap is not None else n * self.SMILES_GUESS, tail)
         return recs.cpu().numpy().view(SMILES_DTYPE), order[:na].cpu().numpy().view(np.uint16), data
+
+    def expand_pack(self, rec: dict, caps=None, keep_device: bool = False) -> dict:
+        """graph_pack's records -> the same molecules with every abbreviation label that has a fragment replaced by the
+        fragment's atoms and bonds (mnx_expand_pack; the rule: include/molnextr_hip.h): a dict with graph_pack's keys — 'mols',
+        'atoms', 'bonds', 'text', 'totals' — plus 'origin' uint16 [atoms], the input index of the atom every output atom came
+        from. molfile_pack and smiles_pack take it as it is. 'text' is the atoms' symbols behind one another, no token SMILES;
+        the atoms of a fragment share the label's coordinates; mols['flags'] carries MOL_EXPANDED / MOL_LABEL_LEFT /
+        MOL_EXPAND_REFUSED. Starts from the input's sizes plus a margin (or caps = (atom_cap, bond_cap, text_cap)) and repeats
+        at most once with the sizes `totals` reports. keep_device: also 'device', as graph_pack."""
+        dev = torch.device("cuda", self.device)
+        n = len(rec["mols"])
+        tables, args = self._packed_tables(rec)
+        mols = torch.empty(n * MOL_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        totals = torch.empty(4, dtype=torch.int32, device=dev)
+        if caps is not None:
+            caps = tuple(int(c) for c in caps)
+        else:       # room for a label of about ten atoms per molecule before the repeat
+            caps = (len(rec["atoms"]) + 12 * n, len(rec["bonds"]) + 12 * n, len(rec["text"]) + 16 * n)
+        for attempt in range(2):
+            atoms = torch.empty(max(caps[0], 1) * ATOM_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            bonds = torch.empty(max(caps[1], 1) * BOND_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            text = torch.empty(max(caps[2], 1), dtype=torch.uint8, device=dev)
+            origin = torch.empty(max(caps[0], 1), dtype=torch.int16, device=dev)
+            self._check(self.lib.mnx_expand_pack(self.h, *args, _ptr(mols), _ptr(atoms), caps[0], _ptr(bonds), caps[1], _ptr(text),
+                                                 caps[2], _ptr(origin), _ptr(totals), _stream()), "mnx_expand_pack")
+            tot = totals.cpu().numpy().view(np.uint32)
+            if not tot[3]:
+                break
+            if attempt:
+                raise MnxError(f"mnx_expand_pack: capacities {caps} too small after sizing them from totals {tot.tolist()}")
+            caps = (int(tot[0]), int(tot[1]), int(tot[2]))
+        na, nb, nt = int(tot[0]), int(tot[1]), int(tot[2])
+        out = {"mols": mols.cpu().numpy().view(MOL_DTYPE),
+               "atoms": atoms[:na * ATOM_DTYPE.itemsize].cpu().numpy().view(ATOM_DTYPE),
+               "bonds": bonds[:nb * BOND_DTYPE.itemsize].cpu().numpy().view(BOND_DTYPE),
+               "text": text[:nt].cpu().numpy().tobytes(), "totals": tot.copy(),
+               "origin": origin[:na].cpu().numpy().view(np.uint16)}
+        if keep_device:
+            out["device"] = (mols, atoms, bonds, text)
+        return out
 
     def atom_scan(self, tokens: torch.Tensor, lengths: torch.Tensor, kmax: Optional[int] = None):
         """On-device CharTokenizer.sequence_to_smiles 'indices' for [n,T] int32 id sequences."""

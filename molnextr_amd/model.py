@@ -143,7 +143,7 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
                      max_len: Optional[int] = None, beam_size: int = 1, compute_confidence: bool = False,
                      labels=None, free_run=False, packed: bool = False, molfile: bool = False,
                      molfile_scale=None, smiles: bool = False, stereo: bool = False, double_bonds: bool = False,
-                     canonical: bool = False) -> List[dict]:
+                     canonical: bool = False, expand: bool = False) -> List[dict]:
     """Encoder + Decoder.decode for MANY images through the engine's continuous-batching path (mnx_predict):
     same per-image dicts as `decode_batch`, identical results (the on-device atom scan equals
     sequence_to_smiles' indices), much higher throughput. compute_confidence=True: mnx_predict_confidence, the same
@@ -173,8 +173,18 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
     stereo and double_bonds select), so two numberings of one drawing give the same bytes, and every dict gains 'canonical_rank'
     and 'symmetry_class', a list per atom (None for a molecule that was not ranked). This library's own ranking: it is NOT
     RDKit's canonical SMILES, no toolkit has parsed it, and the header states the known limit (a few graphs whose string still
-    depends on the drawing)."""
+    depends on the drawing).
+    expand (packed only): abbreviation labels that have a fragment in vocab/fragments.json ('Ph', 'OMe', 'Boc', ...) are replaced
+    by the fragment's atoms and bonds on the device before anything is written (mnx_expand_pack; the rule: the header), so
+    'molfile' and 'graph_smiles' describe the expanded molecule instead of writing 'R' / '*' for the label. Every dict gains
+    'expanded' = {'symbols', 'coords', 'bonds' [(i, j, type, rev[, score])], 'origin' (per expanded atom, the index of the
+    predicted atom it came from), 'flags' (MOL_EXPANDED / MOL_LABEL_LEFT of engine.py)}; 'graph_smiles_order', 'canonical_rank'
+    and 'symmetry_class' then have one entry per EXPANDED atom, in the order of expanded['symbols']. The predicted atoms and
+    bonds ('chartok_coords', 'bonds') are what they are without it. From a table only (no condensed-formula parser), the atoms
+    of a fragment share the label's coordinates, and no toolkit has parsed the result."""
     tok = (tokenizer or get_tokenizer())["chartok_coords"]
+    if expand and not packed:
+        raise ValueError("expand=True needs packed=True: the labels are replaced in the packed tables")
     if molfile and not packed:
         raise ValueError("molfile=True needs packed=True: the molfiles are written from the packed tables")
     if smiles and not packed:
@@ -202,9 +212,22 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
         rec = engine.graph_pack(out, keep_device=molfile or smiles)
         if (rec["mols"]["flags"] & MOL_TRUNCATED).any():
             raise RuntimeError(f"a molecule has more atoms than the engine capacity max_atoms={engine.max_atoms}")
+        drawn = rec                                                      # what the predicted atoms and bonds are read from
+        if expand:
+            rec = engine.expand_pack(drawn, keep_device=molfile or smiles)     # what the writers read
         ranked = engine.smiles_pack(rec, stereo=stereo, double_bonds=double_bonds, canonical=True) if canonical else None
-        preds = unpack_graphs(rec["mols"], rec["atoms"], rec["bonds"], rec["text"], tok.maxx, compute_confidence,
-                              **({"rank": ranked[3], "sym_class": ranked[4]} if canonical else {}))
+        per_atom = {"rank": ranked[3], "sym_class": ranked[4]} if canonical else {}
+        preds = unpack_graphs(drawn["mols"], drawn["atoms"], drawn["bonds"], drawn["text"], tok.maxx, compute_confidence,
+                              **({} if expand else per_atom))
+        if expand:
+            grown = unpack_graphs(rec["mols"], rec["atoms"], rec["bonds"], rec["text"], tok.maxx, compute_confidence, **per_atom)
+            for p, g, m in zip(preds, grown, rec["mols"]):
+                a0, na = int(m["atom0"]), int(m["n_atoms"])
+                p["expanded"] = {"symbols": g["chartok_coords"]["symbols"], "coords": g["chartok_coords"]["coords"],
+                                 "bonds": g["bonds"], "origin": rec["origin"][a0:a0 + na].tolist(), "flags": int(m["flags"])}
+                for key in ("canonical_rank", "symmetry_class"):
+                    if key in g:
+                        p[key] = g[key]
         if molfile:
             files, data = engine.molfile_pack(rec, scale=molfile_scale)
             for p, f in zip(preds, files):
@@ -303,11 +326,12 @@ class molnextr:
     graph_stereo = False
     graph_double_bonds = False
     graph_canonical = False
+    graph_expand = False
 
     def __init__(self, model_path, device=None, max_batch: int = 32, dtype: str = DEFAULT_DTYPE,
                  device_preprocess: bool = True, image_format: str = "fp32", packed_results: bool = False,
                  graph_molfile: bool = False, graph_smiles: bool = False, graph_stereo: bool = False,
-                 graph_double_bonds: bool = False, graph_canonical: bool = False):
+                 graph_double_bonds: bool = False, graph_canonical: bool = False, graph_expand: bool = False):
         if model_path is None:
             raise ValueError("molnextr(model_path): a checkpoint path is required (pass 'synthetic' explicitly for the "
                              "deterministic test checkpoint)")
@@ -341,6 +365,9 @@ class molnextr:
         self.graph_canonical = bool(graph_canonical)
         if self.graph_canonical and not self.graph_smiles:
             raise ValueError("graph_canonical=True needs graph_smiles=True: the ranks order the graph SMILES")
+        self.graph_expand = bool(graph_expand)
+        if self.graph_expand and not (self.graph_smiles or self.graph_molfile):
+            raise ValueError("graph_expand=True needs graph_smiles=True or graph_molfile=True: the expanded molecule is what they write")
         self.engine = Engine(states["encoder"], states["decoder"], device=device.index or 0, max_batch=max_batch,
                              dtype=dtype, image_format=image_format)
         self.input_size = args.input_size
@@ -525,6 +552,8 @@ class molnextr:
                 conf["double_bonds"] = True
             if self.graph_canonical:
                 conf["canonical"] = True
+        if self.graph_expand:
+            conf["expand"] = True
         gen = self._prefetched(groups)
         try:
             for x in gen:
@@ -570,6 +599,8 @@ class molnextr:
             d = {"predicted_smiles": smiles, "predicted_molfile": molfile}
             if "canonical_rank" in pred:                      # graph_canonical: per atom, in the order of atom_sets
                 d["canonical_rank"], d["symmetry_class"] = pred["canonical_rank"], pred["symmetry_class"]
+            if "expanded" in pred:                            # graph_expand: the molecule the two strings describe; the ranks then
+                d["expanded"] = pred["expanded"]              # follow expanded['symbols'], not atom_sets
             if return_atoms_bonds:
                 c = pred["chartok_coords"]
                 atoms = []

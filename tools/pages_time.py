@@ -22,6 +22,11 @@ is part of the product path and no number is asserted.
     then mnx_smiles_pack_canonical with each set of marks alternating with mnx_smiles_pack_marks in a pass of their own,
     with how many molecules were written and how many refused per flag; `--smiles-out FILE` writes the table to a file of its
     own.
+(x) (only when asked for: --part x) abbreviation expansion on the device: mnx_expand_pack alone, against mnx_graph_pack on the
+    same molecules (both are count / scan / fill passes over the same records), and mnx_expand_pack followed by
+    mnx_smiles_pack_canonical against the canonical writer on the unexpanded tables — on the synthetic checkpoint's predictions
+    (near-complete graphs), on hand-made molecules of drug-like size, and on those with a label at every ninth atom;
+    `--expand-out FILE` writes the table to a file of its own.
 The variants of a part alternate inside every repeat (A B A B ...), the table reports the median and the min .. max spread of
 each, and the spread of the fp32 path against itself is the yardstick for "not slower".
 """
@@ -223,11 +228,15 @@ def part_m(n, repeats, lines):
         m.engine.close()
 
 
-def druglike_records(n_mols, seed=0, centres=False):
+LABELS = (b"[OMe]", b"[Ph]", b"[tBu]", b"[CO2Et]", b"[NO2]", b"[Boc]")
+
+
+def druglike_records(n_mols, seed=0, centres=False, labels=False):
     """Packed records of n_mols hand-made molecules of drug-like size: a chain of 20 .. 40 atoms, every seventh atom starting
     an aromatic six-ring, a few hetero atoms and double bonds (about 1.1 bonds per atom) — (mols, atoms, bonds, text).
     centres: every [C@@H] of the chain also carries a methyl on a wedge or a dash that begins at it, and its chain bonds are
-    single: a candidate centre of mnx_smiles_pack_stereo (the molecules are the same otherwise)."""
+    single: a candidate centre of mnx_smiles_pack_stereo (the molecules are the same otherwise). labels: every ninth atom that is a
+    plain 'C' becomes an abbreviation label of mnx_expand_pack, the six of LABELS in turn (the same molecules otherwise)."""
     from molnextr_amd.engine import ATOM_DTYPE, BOND_DTYPE, MOL_DTYPE
     rng = np.random.default_rng(seed)
     mols = np.zeros(n_mols, MOL_DTYPE)
@@ -244,6 +253,10 @@ def druglike_records(n_mols, seed=0, centres=False):
         for k in range(n):
             if syms[k] == b"C" and rng.integers(0, 4) == 0:
                 syms[k] = (b"N", b"O", b"[C@@H]", b"Cl")[int(rng.integers(0, 4))]
+        if labels:
+            for k in range(8, n, 9):
+                if syms[k] == b"C":
+                    syms[k] = LABELS[k // 9 % len(LABELS)]
         xy = [(k % 64, k // 2 % 64) for k in range(n)]
         rev = {}
         if centres:
@@ -435,6 +448,120 @@ def part_s(repeats, lines):
     m.engine.close()
 
 
+def dense_of_records(eng, tok, mols, atoms, bonds, text):
+    """The dense arrays that mnx_graph_pack turns into these records: ids [n, T] (every atom's symbol, character by character, then
+    its two coordinate bins; '<eos>'), lengths, the atom scan over them, and the bond classes as a [n, kmax, kmax] matrix."""
+    dev = torch.device("cuda", eng.device)
+    n, kmax, rows = len(mols), eng.max_atoms, []
+    edges = np.zeros((n, kmax, kmax), np.uint8)
+    for b, m in enumerate(mols):
+        ids = []
+        for a in atoms[m["atom0"]:m["atom0"] + m["n_atoms"]]:
+            sym = text[m["text0"] + a["sym0"]:m["text0"] + a["sym0"] + a["sym_len"]].decode()
+            ids += [tok.stoi[c] for c in sym] + [tok.offset + int(a["x_bin"]), tok.offset + tok.maxx + int(a["y_bin"])]
+        rows.append(ids + [2])
+        for x in bonds[m["bond0"]:m["bond0"] + m["n_bonds"]]:
+            edges[b, x["i"], x["j"]], edges[b, x["j"], x["i"]] = x["type"], x["rev"]
+    T = max(len(r) for r in rows) + 1
+    assert T <= 512
+    tokens = torch.tensor([r + [0] * (T - len(r)) for r in rows], dtype=torch.int32, device=dev)
+    lengths = torch.tensor([len(r) for r in rows], dtype=torch.int32, device=dev)
+    atom_idx, n_atoms = eng.atom_scan(tokens, lengths)
+    return {"tokens": tokens, "lengths": lengths, "atom_idx": atom_idx, "n_atoms": n_atoms, "edges": torch.from_numpy(edges).to(dev)}
+
+
+def part_x(repeats, lines):
+    """Abbreviation expansion on the device: one mnx_expand_pack call (three launches) between two events, alternating with one
+    mnx_graph_pack call that writes the same molecules from the dense arrays, with mnx_expand_pack followed by
+    mnx_smiles_pack_canonical (marks 0), and with the canonical writer on the unexpanded tables. Every output buffer has the
+    exact size; the tables stay on the device."""
+    import ctypes as C
+    from molnextr_amd import engine as E
+    from molnextr_amd.model import molnextr
+    dev = torch.device("cuda", 0)
+    m = molnextr("synthetic", dev, max_batch=32, image_format="gray8", packed_results=True)
+    eng = m.engine
+    tok = m.tokenizer["chartok_coords"]
+    ptr = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
+    stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)      # noqa: E731
+    buf = lambda k: torch.empty(max(int(k), 1), dtype=torch.uint8, device=dev)      # noqa: E731
+
+    def measure(dense, what):
+        rec = eng.graph_pack(dense, keep_device=True)
+        ex = eng.expand_pack(rec, keep_device=True)
+        n, T, kmax = dense["tokens"].shape[0], dense["tokens"].shape[1], dense["atom_idx"].shape[1]
+        sizes = {"in": (len(rec["atoms"]), len(rec["bonds"]), len(rec["text"])), "out": (len(ex["atoms"]), len(ex["bonds"]), len(ex["text"]))}
+        cn = {k: eng.smiles_pack(r, canonical=True) for k, r in (("in", rec), ("out", ex))}
+        mols_d, totals_d = buf(n * 40), torch.empty(4, dtype=torch.int32, device=dev)
+        tab = {k: (buf(v[0] * 24), buf(v[1] * 16), buf(v[2])) for k, v in sizes.items()}
+        origin_d = torch.empty(max(sizes["out"][0], 1), dtype=torch.int16, device=dev)
+        recs_d = buf(n * 16)
+        words = [torch.empty(max(sizes["out"][0], 1), dtype=torch.int16, device=dev) for _ in range(3)]
+        out_d = {k: buf(len(v[2])) for k, v in cn.items()}
+
+        def graph_pack():
+            a, b, t = tab["in"]
+            return eng.lib.mnx_graph_pack(eng.h, ptr(dense["tokens"]), ptr(dense["lengths"]), n, T, ptr(dense["atom_idx"]),
+                                          ptr(dense["n_atoms"]), ptr(dense["edges"]), kmax, None, None, None, ptr(mols_d), ptr(a),
+                                          sizes["in"][0], ptr(b), sizes["in"][1], ptr(t), sizes["in"][2], ptr(totals_d), stream())
+
+        def expand():
+            i, (a, b, t) = rec["device"], tab["out"]
+            return eng.lib.mnx_expand_pack(eng.h, ptr(i[0]), n, ptr(i[1]), sizes["in"][0], ptr(i[2]), sizes["in"][1], ptr(i[3]),
+                                           sizes["in"][2], ptr(mols_d), ptr(a), sizes["out"][0], ptr(b), sizes["out"][1], ptr(t),
+                                           sizes["out"][2], ptr(origin_d), ptr(totals_d), stream())
+
+        def canonical(which, tables):
+            return eng.lib.mnx_smiles_pack_canonical(eng.h, ptr(tables[0]), n, ptr(tables[1]), sizes[which][0], ptr(tables[2]),
+                                                     sizes[which][1], ptr(tables[3]), sizes[which][2], ptr(recs_d), ptr(words[0]),
+                                                     ptr(words[1]), ptr(words[2]), ptr(out_d[which]), len(cn[which][2]), ptr(totals_d),
+                                                     0, stream())
+
+        calls = {"mnx_graph_pack": graph_pack, "mnx_expand_pack": expand,
+                 "canonical, unexpanded": lambda: canonical("in", rec["device"]),
+                 "expand + canonical": lambda: expand() or canonical("out", (mols_d,) + tab["out"])}
+        us = {k: [] for k in calls}
+        for i in range(repeats + 3):
+            for k, call in calls.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                a.record()
+                rc = call()
+                b.record()
+                torch.cuda.synchronize()
+                assert rc == 0 and not int(totals_d[-1] if k == "mnx_graph_pack" or k == "mnx_expand_pack" else totals_d[1]), k
+                if i >= 3:
+                    us[k].append(a.elapsed_time(b) * 1000.0)
+        assert tab["out"][0][:sizes["out"][0] * 24].cpu().numpy().tobytes() == ex["atoms"].tobytes()
+        assert out_d["out"][:len(cn["out"][2])].cpu().numpy().tobytes() == cn["out"][2]
+        flags = ex["mols"]["flags"]
+        lines.append(f"(x) one call over {n} {what}: {sizes['in'][0]} atoms, {sizes['in'][1]} bonds -> {sizes['out'][0]} atoms, "
+                     f"{sizes['out'][1]} bonds; expanded {int((flags & E.MOL_EXPANDED != 0).sum())} molecules, a label left in "
+                     f"{int((flags & E.MOL_LABEL_LEFT != 0).sum())}, refused {int((flags & E.MOL_EXPAND_REFUSED != 0).sum())}")
+        lines.append("  device us between two events around the launches, the four alternating   median [min .. max]")
+        for k in us:
+            lines.append(f"  {k:24s} {fmt(us[k])} us")
+        lines.append(f"  expand / graph_pack, median {statistics.median(us['mnx_expand_pack']) / statistics.median(us['mnx_graph_pack']):.2f}; "
+                     f"(expand + canonical) / canonical, median "
+                     f"{statistics.median(us['expand + canonical']) / statistics.median(us['canonical, unexpanded']):.2f}; canonical strings "
+                     f"with a '*': {sum(b'*' in cn['in'][2][a:a + l] for a, l in zip(cn['in'][0]['text0'].tolist(), cn['in'][0]['len'].tolist()))}"
+                     f" -> {sum(b'*' in cn['out'][2][a:a + l] for a, l in zip(cn['out'][0]['text0'].tolist(), cn['out'][0]['len'].tolist()))}")
+        return rec
+
+    pages = [W.synthetic_page(i % 15) for i in range(1024)]
+    measure(eng.predict(m._transform(pages), ref_batch=32), "images of the synthetic checkpoint (near-complete graphs)")
+    for labels, what in ((False, "hand-made molecules of drug-like size (no label: the pass copies)"),
+                         (True, "hand-made molecules of drug-like size with a label at every ninth atom")):
+        mols, atoms, bonds, text = druglike_records(1024, labels=labels)
+        rec = measure(dense_of_records(eng, tok, mols, atoms, bonds, text), what)
+        for key, want in (("mols", mols), ("atoms", atoms), ("bonds", bonds)):      # mnx_graph_pack wrote these very molecules
+            for name in want.dtype.names:
+                if name != "index":          # the decoder position of the atom, which hand-made records do not have
+                    assert np.array_equal(rec[key][name], want[name]), (key, name)
+        assert rec["text"] == text
+    m.engine.close()
+
+
 def part_c(eng, repeats, lines):
     from molnextr_amd.preprocess import normalise_gray
     dev = torch.device("cuda", eng.device)
@@ -468,6 +595,7 @@ def main():
     ap.add_argument("--pack-out", default=None, help="write the dense-against-packed table of part b to this file")
     ap.add_argument("--molfile-out", default=None, help="write the table of part m to this file")
     ap.add_argument("--smiles-out", default=None, help="write the table of part s to this file")
+    ap.add_argument("--expand-out", default=None, help="write the table of part x to this file")
     ap.add_argument("--pack-only", type=int, default=0, help="run this many mnx_graph_pack calls over 1024 images and exit")
     args = ap.parse_args()
     parts = args.part.split(",")
@@ -508,6 +636,13 @@ def main():
         if args.smiles_out:
             os.makedirs(os.path.dirname(os.path.abspath(args.smiles_out)), exist_ok=True)
             with open(args.smiles_out, "w") as f:
+                f.write("\n".join([lines[0]] + lines[first:]) + "\n")
+    if "x" in parts:
+        first = len(lines)
+        part_x(args.repeats, lines)
+        if args.expand_out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.expand_out)), exist_ok=True)
+            with open(args.expand_out, "w") as f:
                 f.write("\n".join([lines[0]] + lines[first:]) + "\n")
     text = "\n".join(lines)
     print(text)
