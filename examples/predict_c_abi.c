@@ -163,6 +163,40 @@ static int print_first_expanded_smiles(mnx_engine* eng, int n_images, const mnx_
     return rc;
 }
 
+/* A caller's own SMILES in the form the predictions are written in (mnx_smiles_read, then the canonical writer): two strings of
+ * one molecule read on the device into packed tables of the same record types, so print_first_canonical_smiles takes them as
+ * they are. Needs no symbol tables itself; a refused string (mnx_read.flags) is the empty molecule. No toolkit has parsed these
+ * strings: the reader and the writers are each other's check. */
+static int print_canonical_of_known_smiles(mnx_engine* eng) {
+    static const char known[] = "OCCc1ccccc1CCO";                 /* two strings behind one another: "OCC" and "c1ccccc1CCO" */
+    const uint32_t offsets[3] = {0, 3, 14};
+    uint32_t totals[4] = {0, 0, 0, 0}, *totals_dev = NULL, *offsets_dev = NULL;
+    char *bytes_dev = NULL, *text_dev = NULL;
+    mnx_mol* mols_dev = NULL;
+    mnx_read *recs_dev = NULL, recs[2];
+    mnx_atom* atoms_dev = NULL;
+    mnx_bond* bonds_dev = NULL;
+    int rc;
+    hipMalloc((void**)&bytes_dev, sizeof known); hipMalloc((void**)&offsets_dev, sizeof offsets);
+    hipMalloc((void**)&mols_dev, 2 * sizeof(mnx_mol)); hipMalloc((void**)&recs_dev, sizeof recs);
+    hipMalloc((void**)&atoms_dev, 14 * sizeof(mnx_atom)); hipMalloc((void**)&bonds_dev, 14 * sizeof(mnx_bond));   /* an atom and a */
+    hipMalloc((void**)&text_dev, 14); hipMalloc((void**)&totals_dev, sizeof totals);                               /* bond per byte */
+    hipMemcpy(bytes_dev, known, 14, 1 /* hipMemcpyHostToDevice */);
+    hipMemcpy(offsets_dev, offsets, sizeof offsets, 1);
+    rc = mnx_smiles_read(eng, bytes_dev, 14, offsets_dev, 2, mols_dev, recs_dev, atoms_dev, 14, bonds_dev, 14, text_dev, 14,
+                         totals_dev, /*stream=*/NULL);
+    if (rc != MNX_OK) fprintf(stderr, "%s\n", mnx_last_error(eng));
+    else {
+        hipMemcpy(totals, totals_dev, sizeof totals, 2);
+        hipMemcpy(recs, recs_dev, sizeof recs, 2);
+        if (recs[0].flags & MNX_READ_SYNTAX) printf("string 0: a rule of the grammar breaks at byte %u\n", (unsigned)recs[0].err_pos);
+        rc = print_first_canonical_smiles(eng, 2, mols_dev, atoms_dev, bonds_dev, text_dev, totals);
+    }
+    hipFree(bytes_dev); hipFree(offsets_dev); hipFree(mols_dev); hipFree(recs_dev); hipFree(atoms_dev); hipFree(bonds_dev);
+    hipFree(text_dev); hipFree(totals_dev);
+    return rc;
+}
+
 /* The molecules as packed tables (mnx_graph_pack): no tokenizer on the host. A first call with modest capacities; `totals`
  * says what the job needs, so a second call with exactly that is the worst case. Prints molecule 0 with its token SMILES, then its molfile and its graph SMILES. */
 static int print_first_molecule(mnx_engine* eng, int n_images, const int32_t* tokens, const int32_t* lengths,
@@ -211,6 +245,7 @@ static int print_first_molecule(mnx_engine* eng, int n_images, const int32_t* to
         if (rc == MNX_OK) rc = print_first_graph_smiles(eng, n_images, mols_dev, atoms_dev, bonds_dev, text_dev, totals);
         if (rc == MNX_OK) rc = print_first_canonical_smiles(eng, n_images, mols_dev, atoms_dev, bonds_dev, text_dev, totals);
         if (rc == MNX_OK) rc = print_first_expanded_smiles(eng, n_images, mols_dev, atoms_dev, bonds_dev, text_dev, totals);
+        if (rc == MNX_OK) rc = print_canonical_of_known_smiles(eng);
     }
     hipFree(mols_dev); hipFree(totals_dev); hipFree(atoms_dev); hipFree(bonds_dev); hipFree(text_dev);
     return rc;

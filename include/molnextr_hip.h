@@ -832,6 +832,91 @@ int mnx_expand_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_ato
                     mnx_atom* atoms_out, uint32_t atom_cap, mnx_bond* bonds_out, uint32_t bond_cap, char* text_out,
                     uint32_t text_cap, uint16_t* origin, uint32_t* totals, void* stream);
 
+/* SMILES text read into the packed molecule tables, on the device: the inverse of mnx_smiles_pack. Strings in, mnx_mol / mnx_atom /
+ * mnx_bond records and a text arena out, as mnx_graph_pack writes them, so that mnx_smiles_pack_canonical, mnx_expand_pack,
+ * mnx_molfile_pack and the other writers run on a caller's own molecules unchanged: a gold column or a list of known compounds gets
+ * the same canonical string as a prediction of the same graph. NO toolkit has parsed or produced any of these strings: this reader
+ * and the writers are each other's check, no more. The grammar is the OpenSMILES one without its stereo and without '~' and '$'; a
+ * bracket atom's bytes are COPIED, not interpreted (interpretation stays with the writers, which need mnx_set_symbol_tables; this
+ * call needs no tables). No kekulisation, no hydrogen counting, no normalisation of [CH] against C.
+ *
+ * String b is bytes[offsets[b] .. offsets[b+1]). The rule, on the bytes of one string, positions counted from its first byte:
+ * Brackets. A byte other than '[' and ']' is INSIDE when the nearest bracket in front of it is a '['. A '[' must be followed, as its
+ *   next bracket, by a ']' that is not the very next byte; a ']' must have a '[' as the nearest bracket in front of it.
+ * Tokens, from the bytes that are not inside:
+ *   atom     one of B C N O P S F I b c n o p s * (Cl and Br: a C followed by l, a B followed by r, are one atom of two bytes), or a
+ *            '[' with everything up to its ']' (one or more bytes, none of them a bracket). Atom k is the k-th atom token.
+ *   bond     - = # : / \      branch  ( and )      dot  .
+ *   ring     a digit 0..9, or '%' followed by two digits (numbers 00..99; '%' with anything else is an illegal byte; the two
+ *            digits are part of the token). Numbers 0, 00 and 0 .. 9 against 00 .. 09 are the same numbers.
+ *   illegal  every other byte, '~' and '$' among them, an l not behind C, an r not behind B, a stray ']'.
+ * The current atom: none at the start and behind a '.'; behind an atom token that atom; behind a ')' the atom that was current in
+ *   front of the matching '('. '(' leaves it as it is.
+ * Bonds. An atom token bonds to the current atom, if there is one. A ring token whose number is not open opens it at the current
+ *   atom; the next token with that number closes it: a bond between the atom that opened and the current atom, and the number is
+ *   free again (first occurrence opens, second closes, whatever stands between them). A bond token belongs to the atom or ring
+ *   token directly behind it. The type of a bond: '-' '/' '\' 1, '=' 2, '#' 3, ':' 4, from the bond token of a chain bond or of
+ *   either end of a ring bond (both ends may carry the same symbol); with no symbol 4 when both atoms are spelled in lower case,
+ *   else 1. An unbracketed atom is lower case by its first byte, a bracket atom by the first byte behind '[' and the digits that
+ *   follow it ([nH], [13cH], [se]: lower case; [2*]: not).
+ * Output of an admitted string: mols[b].n_atoms / n_bonds / smiles_len (the string's length; the molecule's text IS the string,
+ *   copied), flags = 0, reserved = 0, overall_score = 0. Atom k: sym0 / sym_len its token's span in the text, brackets included,
+ *   index = k, x_bin = y_bin = 0, score = 0. One bond record per bond: i < j in atom numbers, type, rev = type, score = 0; records
+ *   sorted by i, then j (what mnx_graph_pack writes and mnx_expand_pack requires). recs[b]: flags, err_pos = 0, n_rings = bonds -
+ *   atoms + components, where the components are the parts the '.' separate (1 + the number of '.'): the number of ring bonds. It
+ *   exceeds the cycle rank of the graph where a ring number joins two parts across a '.' ("C1.C1": one ring bond, no cycle).
+ *   MNX_READ_STEREO_DROPPED (not a refusal): the string holds a '/' or '\' bond token or an '@' inside a bracket atom. The bond is
+ *   single; the '@' stays in the text and the writers drop it.
+ *   The empty string is the empty molecule with flags 0.
+ * Refusals. A refused string is the empty molecule: n_atoms = n_bonds = smiles_len = 0, mols[b].flags = 0, and recs[b].flags holds
+ *   one bit only, tested in this order:
+ *   MNX_READ_BEYOND     offsets[b] > offsets[b+1], or offsets[b+1] > n_bytes. No byte is read.
+ *   MNX_READ_TOO_LARGE  more than 4096 bytes, or more than 999 atom tokens (the writers' limits); the string is examined no further.
+ *   MNX_READ_SYNTAX     err_pos = the LOWEST position named by any of the following, each of which stands for itself whatever else
+ *                       is wrong with the string (parentheses are matched as a stack that drops a ')' with nothing open; ring
+ *                       numbers open and close by occurrence; the current atom is as stated above):
+ *     an illegal byte: its position; a '[' whose next bracket is a '[' or that has none behind it, and "[]": the '[';
+ *     a bond token whose next token is no atom and no ring token (or that is the last token): the bond token;
+ *     a bond token that is the first token of the string or the first behind a '.';
+ *     a ring token, '(', ')' or '.' that is the first token of the string, the first behind a '.' or behind a '(', or that is
+ *       separated from one of these only by bond tokens: "()" , "((", "C(1", "C.1", "C(=1" break here;
+ *       so a ring token behind a ')' is admitted and belongs to the atom in front of the '(' ;
+ *     a '.' while a '(' is open; a '.' whose next token is no atom (or that is the last token): the '.';
+ *     a ')' with no '(' open; a '(' that is never closed: the '(' (the lowest, if several);
+ *     a ring number that is still open at the end: the token that opened it;
+ *     a ring token that closes with a symbol that differs from the opening token's symbol ('/' against '\' too), onto the atom
+ *       that opened it ("C11"), or onto a pair of atoms that has a bond already, be it a chain bond or an earlier ring bond
+ *       ("C1C1", "C12CCC12"): the closing token (of the later bond).
+ *   MNX_READ_TOO_LARGE  otherwise, more than 999 bonds.
+ * Examples (atoms; bonds i-j:type): "CCO" 3; 0-1:1 1-2:1. "CC(=O)[O-]" 4; 0-1:1 1-2:2 1-3:1. "c1ccccc1" 6; 0-1:4 0-5:4 1-2:4 2-3:4
+ *   3-4:4 4-5:4, n_rings 1. "c1ccccc1-c1ccccc1" 12; 5-6:1 among 13 bonds. "C1CC1.C1CC1" n_rings 2. "C%12CC%12" and "C0CC0" as
+ *   "C1CC1". "C=1CC1" and "C1CC=1" 0-1:1 0-2:2 1-2:1. "F/C=C/F" 0-1:1 1-2:2 2-3:1, STEREO_DROPPED. "[13CH3][C@@H](N)C(=O)O" 6
+ *   atoms, atom 0 = text[0..7), STEREO_DROPPED. "C(C)(C)(C)C" 0-1 0-2 0-3 0-4. "[Ph]C" 2 atoms (mnx_expand_pack expands the
+ *   first). "Cl" 1 atom of 2 bytes; "ClC" 2 atoms.
+ *
+ * Inputs, device pointers: bytes [n_bytes] (may be null when n_bytes is 0), offsets uint32 [n + 1], 1 <= n <= 65536.
+ * Outputs, device pointers the caller allocated: mols [n], recs [n]; atoms [atom_cap], bonds [bond_cap] (8-byte aligned), text
+ * [text_cap]; totals uint32 [4] = {atoms, bonds, text bytes needed, 1 if any capacity was too small}. When a capacity is too small
+ * nothing is written beyond it, and mols, recs and totals are complete all the same: read the needed sizes and call again. A table
+ * of capacity 0 may be null. Deterministic word for word (every position comes from a prefix scan or a rank; no atomic decides a
+ * position or an order); records are written whole, padding bytes as zeros. Three launches, asynchronous on `stream`, no allocation,
+ * no host synchronisation.
+ * MNX_ERR_INVALID_ARG (with mnx_last_error, "mnx_smiles_read: ..."): a null pointer, n outside 1..65536, misaligned records (mols,
+ * atoms, bonds 8-byte; recs, offsets, totals 4-byte); nothing is launched then. */
+typedef struct mnx_read {
+    uint32_t flags;             /* MNX_READ_* */
+    uint32_t err_pos;           /* MNX_READ_SYNTAX: the lowest position at which a rule breaks; else 0 */
+    uint32_t n_rings;
+    uint32_t reserved;          /* 0 */
+} mnx_read;
+#define MNX_READ_SYNTAX 1u
+#define MNX_READ_TOO_LARGE 2u
+#define MNX_READ_STEREO_DROPPED 4u
+#define MNX_READ_BEYOND 8u
+int mnx_smiles_read(mnx_engine* h, const char* bytes, uint32_t n_bytes, const uint32_t* offsets, int32_t n, mnx_mol* mols,
+                    mnx_read* recs, mnx_atom* atoms, uint32_t atom_cap, mnx_bond* bonds, uint32_t bond_cap, char* text,
+                    uint32_t text_cap, uint32_t* totals, void* stream);
+
 /* mnx_predict with beam search (BASELINE config 5): the same inputs and outputs, every reference batch searched as
  * mnx_decode_beam does (n_best = 1: the best hypothesis; atom positions and the bond head run on ITS tokens and decoder
  * outputs) while the encoder of the following launch groups runs on the second stream. Up to MNX_BEAM_GROUPS (environment,

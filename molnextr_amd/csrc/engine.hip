@@ -1502,6 +1502,22 @@ int mnx_expand_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_ato
     return MNX_OK;
 }
 
+int mnx_smiles_read(mnx_engine* h, const char* bytes, uint32_t n_bytes, const uint32_t* offsets, int32_t n, mnx_mol* mols,
+                    mnx_read* recs, mnx_atom* atoms, uint32_t atom_cap, mnx_bond* bonds, uint32_t bond_cap, char* text,
+                    uint32_t text_cap, uint32_t* totals, void* stream) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    auto bad = [&](const char* m) { h->err = std::string("mnx_smiles_read: ") + m; return MNX_ERR_INVALID_ARG; };
+    if ((!bytes && n_bytes) || !offsets || !mols || !recs || !totals || (!atoms && atom_cap) || (!bonds && bond_cap) || (!text && text_cap))
+        return bad("null pointer");
+    if (n < 1 || n > 65536) return bad("1 <= n <= 65536 required");
+    if ((((uintptr_t)mols | (uintptr_t)atoms | (uintptr_t)bonds) & 7) || (((uintptr_t)recs | (uintptr_t)offsets | (uintptr_t)totals) & 3))
+        return bad("mols, atoms and bonds must be 8-byte aligned, recs, offsets and totals 4-byte");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, smiles_read_enqueue((const unsigned char*)bytes, n_bytes, offsets, n, mols, recs, atoms, atom_cap, bonds, bond_cap, text,
+                                  text_cap, totals, (hipStream_t)stream));
+    return MNX_OK;
+}
+
 // mnx_smiles_pack, mnx_smiles_pack_stereo, mnx_smiles_pack_marks and mnx_smiles_pack_canonical: one check, one enqueue path, a
 // pair of kernels per set of marks; canonical: on the ranks that one more kernel in front of them leaves in `rank`
 static int smiles_pack(mnx_engine* h, const char* fn, uint32_t marks, const PackedTables& t, mnx_smiles* recs, uint16_t* order,

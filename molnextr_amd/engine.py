@@ -28,7 +28,7 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
            "mnx_encode_gray8", "mnx_predict_gray8", "mnx_decode_guided", "mnx_predict_guided", "mnx_patch_embed",
            "mnx_layernorm16", "mnx_merge_ln16", "mnx_cast16", "mnx_sgemm_tn", "mnx_set_vocab_text", "mnx_graph_pack",
            "mnx_set_symbol_tables", "mnx_molfile_pack", "mnx_smiles_pack", "mnx_smiles_pack_stereo",
-           "mnx_smiles_pack_marks", "mnx_smiles_pack_canonical", "mnx_set_fragments", "mnx_expand_pack")
+           "mnx_smiles_pack_marks", "mnx_smiles_pack_canonical", "mnx_set_fragments", "mnx_expand_pack", "mnx_smiles_read")
 
 # Encoder operand modes (include/molnextr_hip.h MNX_DTYPE_*). "fp16x3" — split fp16 operands, three MFMA terms per
 # product, fp32-class results — is the default: it is the fastest mode whose results stay a factor of four inside north_star's
@@ -138,6 +138,11 @@ SMILES_MARK_TETRAHEDRAL, SMILES_MARK_DOUBLE_BOND = 1, 2     # the `marks` of mnx
 SMILES_CANON_TIE, SMILES_CANON_TIE_INDEX = 8192, 16384
 SMILES_REFUSED = SMILES_TOO_LARGE | SMILES_BEYOND_TABLES | SMILES_DUPLICATE_BOND | SMILES_RING_NUMBERS    # no SMILES: len 0
 SMILES_NO_POSITION = 0xFFFF             # `order` of an atom whose molecule got no SMILES
+# mnx_read, one string of mnx_smiles_read (16 bytes), and its flags (MNX_READ_*): a rule of the grammar breaks at err_pos; more
+# than 4096 bytes, 999 atoms or 999 bonds; '/' '\' or '@' were read and dropped (no refusal); offsets beyond the bytes passed
+READ_DTYPE = np.dtype([("flags", "<u4"), ("err_pos", "<u4"), ("n_rings", "<u4"), ("reserved", "<u4")], align=True)
+READ_SYNTAX, READ_TOO_LARGE, READ_STEREO_DROPPED, READ_BEYOND = 1, 2, 4, 8
+READ_REFUSED = READ_SYNTAX | READ_TOO_LARGE | READ_BEYOND      # the empty molecule stands in its place
 
 
 def vocab_text(tok):
@@ -277,6 +282,8 @@ def load_library():
     lib.mnx_expand_pack.restype = C.c_int
     lib.mnx_expand_pack.argtypes = [vp, vp, i32, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint32, vp, C.c_uint32,
                                     vp, C.c_uint32, vp, vp, vp]
+    lib.mnx_smiles_read.restype = C.c_int
+    lib.mnx_smiles_read.argtypes = [vp, vp, C.c_uint32, vp, i32, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp]
     lib.mnx_atom_scan.restype = C.c_int
     lib.mnx_atom_scan.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.mnx_preprocess.restype = C.c_int
@@ -1010,6 +1017,56 @@ class Engine:
                "bonds": bonds[:nb * BOND_DTYPE.itemsize].cpu().numpy().view(BOND_DTYPE),
                "text": text[:nt].cpu().numpy().tobytes(), "totals": tot.copy(),
                "origin": origin[:na].cpu().numpy().view(np.uint16)}
+        if keep_device:
+            out["device"] = (mols, atoms, bonds, text)
+        return out
+
+    def smiles_read(self, strings, caps=None, keep_device: bool = False) -> dict:
+        """SMILES strings (str or bytes) -> the molecules as packed tables, read on the device (mnx_smiles_read; the rule:
+        include/molnextr_hip.h): a dict with graph_pack's keys — 'mols', 'atoms', 'bonds', 'text', 'totals' — plus 'read' [n]
+        READ_DTYPE (flags READ_*, err_pos, n_rings). molfile_pack, smiles_pack(... canonical=True) and expand_pack take it as it
+        is. A refused string (READ_REFUSED) is the empty molecule. Starts from PACK_GUESS atoms and bonds per string, one per byte
+        at the most (or caps = (atom_cap, bond_cap, text_cap)) and repeats at most once with the sizes `totals` reports.
+        keep_device: also 'device', as graph_pack."""
+        dev = torch.device("cuda", self.device)
+        raw = [x.encode("utf-8") if isinstance(x, str) else bytes(x) for x in strings]
+        n = len(raw)
+        if n < 1:
+            raise ValueError("smiles_read needs at least one string")
+        lens = np.fromiter((len(x) for x in raw), dtype=np.int64, count=n)
+        if int(lens.sum()) > 0xFFFFFFFF:
+            raise ValueError("smiles_read: more than 2^32 - 1 bytes in one call")
+        offsets = np.zeros(n + 1, dtype=np.uint32)
+        offsets[1:] = np.cumsum(lens)
+        arena = b"".join(raw)
+        d_bytes = torch.frombuffer(bytearray(arena) or bytearray(8), dtype=torch.uint8).to(dev)
+        d_off = torch.from_numpy(offsets.view(np.int32)).to(dev)
+        mols = torch.empty(n * MOL_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        recs = torch.empty(n * READ_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        totals = torch.empty(4, dtype=torch.int32, device=dev)
+        if caps is not None:
+            caps = tuple(int(c) for c in caps)
+        else:       # an atom takes a byte at least, a string has about as many bonds as atoms, and its text is itself
+            caps = (min(len(arena), n * self.PACK_GUESS[0]), min(len(arena), n * self.PACK_GUESS[1]), len(arena))
+        for attempt in range(2):
+            atoms = torch.empty(max(caps[0], 1) * ATOM_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            bonds = torch.empty(max(caps[1], 1) * BOND_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            text = torch.empty(max(caps[2], 1), dtype=torch.uint8, device=dev)
+            self._check(self.lib.mnx_smiles_read(self.h, _ptr(d_bytes), len(arena), _ptr(d_off), n, _ptr(mols), _ptr(recs), _ptr(atoms),
+                                                 caps[0], _ptr(bonds), caps[1], _ptr(text), caps[2], _ptr(totals), _stream()),
+                        "mnx_smiles_read")
+            tot = totals.cpu().numpy().view(np.uint32)
+            if not tot[3]:
+                break
+            if attempt:
+                raise MnxError(f"mnx_smiles_read: capacities {caps} too small after sizing them from totals {tot.tolist()}")
+            caps = (int(tot[0]), int(tot[1]), int(tot[2]))
+        na, nb, nt = int(tot[0]), int(tot[1]), int(tot[2])
+        out = {"mols": mols.cpu().numpy().view(MOL_DTYPE),
+               "atoms": atoms[:na * ATOM_DTYPE.itemsize].cpu().numpy().view(ATOM_DTYPE),
+               "bonds": bonds[:nb * BOND_DTYPE.itemsize].cpu().numpy().view(BOND_DTYPE),
+               "text": text[:nt].cpu().numpy().tobytes(), "totals": tot.copy(),
+               "read": recs.cpu().numpy().view(READ_DTYPE)}
         if keep_device:
             out["device"] = (mols, atoms, bonds, text)
         return out

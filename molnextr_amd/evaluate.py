@@ -87,14 +87,16 @@ MAX_BATCH_SIZE = 256      # --batch_size: per-rank reference batches of 2 x 256 
 
 def run_inference(engine, load_image: Callable[[int], np.ndarray], n_items: int, batch_size: int, rank: int = 0,
                   world: int = 1, tokenizer=None, group: int = 512, pad_to_square: bool = False,
-                  smiles: Optional[Sequence[str]] = None) -> Dict[int, dict]:
+                  smiles: Optional[Sequence[str]] = None, keep_records: Optional[dict] = None) -> Dict[int, dict]:
     """valid_fn for this rank's shard, then the gather: returns {dataset index: prediction dict} on every rank
     (the reference keeps it on all ranks too, main.py:295-301). `engine`: molnextr_amd.engine.Engine.
     pad_to_square: the PadToSquare step `get_transforms` inserts for the test files in PAD_TO_SQUARE_FILES.
     smiles: the known structure of every item (main.py --predict_coords): item i is decoded along
     smiles_to_sequence(smiles[i], mask_ratio=1) cut to max_len ids (dataset.py:459-464,473), label-guided. Only a row
     that the cut shortened, and so lost its '<eos>', is passed on as free-running; every other row goes through the
-    engine's refusal of labels without '<eos>'."""
+    engine's refusal of labels without '<eos>'.
+    keep_records: a dict that receives 'records', the gathered dense records int32 [n_items, shard.record_words(kmax)] in
+    dataset order (graph_match_scores re-uploads them)."""
     tok = (tokenizer or get_tokenizer())["chartok_coords"]
     ref_batch = batch_size * 2
     cap = getattr(engine, "MAX_REF_BATCH", engine.ROWS_PER_DECODE)     # rows of one reference batch on the greedy path
@@ -151,6 +153,10 @@ def run_inference(engine, load_image: Callable[[int], np.ndarray], n_items: int,
     rows = shard.unpack_records(torch.from_numpy(np.ascontiguousarray(rec[:, 1:])), kmax)
     for r, row in enumerate(rows):
         preds[int(rec[r, 0])] = {"chartok_coords": tok.sequence_to_smiles(row["tokens"]), "edges": row["edges"]}
+    if keep_records is not None:
+        dense = np.zeros((n_items, rec.shape[1] - 1), dtype=np.int32)
+        dense[rec[:, 0]] = rec[:, 1:]                       # padded duplicates overwrite themselves
+        keep_records["records"] = dense
     return preds
 
 
@@ -203,12 +209,44 @@ def write_predictions(save_path: str, file_name: str, table: Dict[str, list], sc
     return out_csv
 
 
-def main(argv=None):
-    import pandas as pd
-    import torch.distributed as dist
-    from . import weights as W
-    from .engine import DEFAULT_DTYPE, DTYPES, Engine
-    from .preprocess import load_image_rgb
+def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: int = 512) -> Dict[str, float]:
+    """--graph_match: the share of items whose prediction and gold string are the same graph as THIS library's canonical SMILES
+    sees it (marks 0: no stereo), on the device. records: the gathered dense records in dataset order (shard.pack_records
+    layout), re-uploaded in chunks -> graph_pack -> mnx_smiles_pack_canonical; gold -> mnx_smiles_read -> the same writer. A
+    refused side is a mismatch. NOT the reference's RDKit `graph` score: nothing normalises [CH] against C, nothing kekulises,
+    stereo is dropped, and the canonical ranks keep the limit DESIGN 4.15 states."""
+    from .engine import READ_REFUSED, SMILES_REFUSED
+    from .shard import MAX_LEN
+    kmax = engine.max_atoms
+    dev = torch.device("cuda", engine.device)
+    gold = ["" if g is None or (isinstance(g, float) and np.isnan(g)) else str(g) for g in gold]
+    assert len(gold) == len(records)
+
+    def texts(rec):
+        recs, _, data, _, _ = engine.smiles_pack(rec, canonical=True)
+        return [None if int(r["flags"]) & SMILES_REFUSED else data[int(r["text0"]):int(r["text0"]) + int(r["len"])] for r in recs]
+
+    equal = unreadable = refused = 0
+    for c0 in range(0, len(gold), chunk):
+        rows = torch.from_numpy(np.ascontiguousarray(records[c0:c0 + chunk])).to(dev)
+        n = rows.shape[0]
+        e32 = rows[:, 2 + MAX_LEN + kmax:].contiguous()
+        out = {"lengths": rows[:, 0].contiguous(), "n_atoms": rows[:, 1].contiguous(), "tokens": rows[:, 2:2 + MAX_LEN].contiguous(),
+               "atom_idx": rows[:, 2 + MAX_LEN:2 + MAX_LEN + kmax].contiguous(),
+               "edges": e32.view(torch.uint8)[:, :kmax * kmax].reshape(n, kmax, kmax).contiguous()}
+        pred = texts(engine.graph_pack(out, keep_device=True))
+        read = engine.smiles_read(gold[c0:c0 + chunk], keep_device=True)
+        want = texts(read)
+        for p, w, r in zip(pred, want, read["read"]):
+            bad = bool(int(r["flags"]) & READ_REFUSED)
+            unreadable += bad
+            refused += p is None
+            equal += (not bad) and p is not None and w is not None and p == w
+    return {"graph_match_device": equal / len(gold) if gold else 0.0, "gold_unreadable": int(unreadable), "pred_refused": int(refused)}
+
+
+def build_parser() -> argparse.ArgumentParser:
+    from .engine import DTYPES
     ap = argparse.ArgumentParser(description="MolNexTR test-set inference on MI355X (reference main.py --do_test)")
     ap.add_argument("--data_path", default=".")
     ap.add_argument("--test_file", required=True, help="CSV with file_path (and SMILES / image_id) columns")
@@ -232,6 +270,22 @@ def main(argv=None):
                     help="the reference's main.py --predict_coords: the test file's SMILES column is the known structure of every "
                          "image; decoding is guided along it and only the atom coordinates are predicted. Writes image_id, SMILES "
                          "(the input string), node_coords (main.py:534-535)")
+    ap.add_argument("--graph_match", action="store_true",
+                    help="opt-in: add graph_match_device, gold_unreadable and pred_refused to the scores. Predictions (graph_pack) and "
+                         "the SMILES column (mnx_smiles_read) are both written as this library's canonical SMILES without stereo marks "
+                         "on the device and compared as strings; a refused side counts as a mismatch. This is NOT the reference's RDKit "
+                         "`graph` score: no normalisation of [CH] against C, no kekulisation, no stereo, and the canonical ranks have "
+                         "the known limit of DESIGN 4.15; no toolkit has parsed either string")
+    return ap
+
+
+def main(argv=None):
+    import pandas as pd
+    import torch.distributed as dist
+    from . import weights as W
+    from .engine import DEFAULT_DTYPE, Engine
+    from .preprocess import load_image_rgb
+    ap = build_parser()
     args = ap.parse_args(argv)
     if not 1 <= args.batch_size <= MAX_BATCH_SIZE:
         ap.error(f"--batch_size must be 1..{MAX_BATCH_SIZE} (reference batches of 2 x batch_size <= {2 * MAX_BATCH_SIZE} rows)")
@@ -253,9 +307,12 @@ def main(argv=None):
     if args.predict_coords and "SMILES" not in df.columns:
         ap.error("--predict_coords needs a SMILES column in --test_file")
     known = ["" if pd.isna(s) else str(s) for s in df["SMILES"]] if args.predict_coords else None      # an empty cell: no atoms
+    if args.graph_match and (args.predict_coords or "SMILES" not in df.columns):
+        ap.error("--graph_match compares predictions with the SMILES column of --test_file (and not under --predict_coords)")
+    kept = {} if args.graph_match else None
     def infer(e):
         return run_inference(e, lambda i: load_image_rgb(paths[i]), len(df), args.batch_size, rank, world,
-                             pad_to_square=args.test_file in PAD_TO_SQUARE_FILES, smiles=known)
+                             pad_to_square=args.test_file in PAD_TO_SQUARE_FILES, smiles=known, keep_records=kept)
     try:
         preds = infer(engine)
     except RangeFallback as err:
@@ -279,6 +336,8 @@ def main(argv=None):
             scores = None            # the SMILES column is the input here: there is no predicted string to score
         else:
             scores = smiles_scores(df["SMILES"], table["SMILES"]) if "SMILES" in df.columns else None
+            if args.graph_match:
+                scores.update(graph_match_scores(engine, kept["records"], list(df["SMILES"])))
         print(write_predictions(args.save_path, args.test_file, table, scores), json.dumps(scores))
     if world > 1:
         dist.barrier()

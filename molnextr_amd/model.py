@@ -267,6 +267,29 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
     return preds
 
 
+def canonical_smiles(engine: Engine, smiles_list, expand: bool = False) -> List[dict]:
+    """A caller's own SMILES in the form the device writes predictions in: mnx_smiles_read, optionally mnx_expand_pack ([Ph],
+    [OMe], ... replaced by their atoms), then mnx_smiles_pack_canonical without marks. Per item {'smiles': the canonical string,
+    None where the reader or the writer refused; 'read_flags' (engine.READ_*), 'err_pos' (of READ_SYNTAX), 'smiles_flags'
+    (engine.SMILES_*)}. Equal strings mean equal graphs as this library sees them — no stereo, no kekulisation, no [CH] against
+    C; it is NOT a toolkit's canonical SMILES and never compares with one."""
+    from .engine import READ_REFUSED, SMILES_REFUSED
+    smiles_list = list(smiles_list)
+    if not smiles_list:
+        return []
+    rec = engine.smiles_read(smiles_list, keep_device=True)
+    read = rec["read"]
+    if expand:
+        rec = engine.expand_pack(rec, keep_device=True)
+    recs, _, data, _, _ = engine.smiles_pack(rec, canonical=True)
+    out = []
+    for r, w in zip(read, recs):
+        ok = not (int(r["flags"]) & READ_REFUSED or int(w["flags"]) & SMILES_REFUSED)
+        out.append({"smiles": data[int(w["text0"]):int(w["text0"]) + int(w["len"])].decode("utf-8", "replace") if ok else None,
+                    "read_flags": int(r["flags"]), "err_pos": int(r["err_pos"]), "smiles_flags": int(w["flags"])})
+    return out
+
+
 def page_scale(image) -> tuple:
     """(Sx, Sy) of mnx_molfile_pack for one input page [height, width, ...]: Sx = round(100000 * width / height), the reference's
     `ratio` times its factor 10 (chemical.py:935-937) in units of 1e-4, inside the call's range; Sy = 100000."""
@@ -373,6 +396,11 @@ class molnextr:
         self.input_size = args.input_size
         self.device_preprocess = device_preprocess
         self.group_images = 1024          # images per engine call of the throughput path (whole reference batches)
+
+    def canonical_smiles(self, smiles_list, expand: bool = False) -> List[dict]:
+        """The canonical graph SMILES of the caller's own strings, for comparison with 'predicted_smiles' of graph_canonical=True
+        (model.canonical_smiles: read on the device, optionally expanded, written without marks)."""
+        return canonical_smiles(self.engine, smiles_list, expand=expand)
 
     _groups_done = 0          # groups of the running predict_images call that have produced predictions
 

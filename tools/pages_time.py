@@ -27,6 +27,9 @@ is part of the product path and no number is asserted.
     mnx_smiles_pack_canonical against the canonical writer on the unexpanded tables — on the synthetic checkpoint's predictions
     (near-complete graphs), on hand-made molecules of drug-like size, and on those with a label at every ninth atom;
     `--expand-out FILE` writes the table to a file of its own.
+(r) (only when asked for: --part r) SMILES read on the device: one mnx_smiles_read call over the strings of 1024 hand-made
+    molecules of drug-like size against the one mnx_smiles_pack call that writes those strings, then the worst strings the
+    reader admits, each alone in a call; `--read-out FILE` writes the table to a file of its own.
 The variants of a part alternate inside every repeat (A B A B ...), the table reports the median and the min .. max spread of
 each, and the spread of the fp32 path against itself is the yardstick for "not slower".
 """
@@ -562,6 +565,86 @@ def part_x(repeats, lines):
     m.engine.close()
 
 
+def part_r(repeats, lines):
+    """SMILES read on the device: one mnx_smiles_read call (three launches) over the strings of 1024 hand-made molecules of
+    drug-like size between two events, alternating with the one mnx_smiles_pack call that writes those strings from the packed
+    tables; then the worst strings the reader admits, each alone in a call (one workgroup), against a call on "C"."""
+    import ctypes as C
+    from molnextr_amd import engine as E
+    dev = torch.device("cuda", 0)
+    ck = W.synthetic_checkpoint(0)
+    eng = Engine(ck["encoder"], ck["decoder"], device=0, max_batch=2)
+    ptr = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
+    stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)      # noqa: E731
+    buf = lambda k: torch.empty(max(int(k), 1), dtype=torch.uint8, device=dev)      # noqa: E731
+
+    def timed(calls, check):
+        us = {k: [] for k in calls}
+        for i in range(repeats + 3):
+            for k, call in calls.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                a.record()
+                rc = call()
+                b.record()
+                torch.cuda.synchronize()
+                assert rc == 0 and check(k), k
+                if i >= 3:
+                    us[k].append(a.elapsed_time(b) * 1000.0)
+        return us
+
+    def reader(strings):
+        """(the call on exact-size buffers, its totals tensor, the result of Engine.smiles_read)"""
+        got = eng.smiles_read(strings)
+        arena = b"".join(strings)
+        offsets = np.zeros(len(strings) + 1, np.uint32)
+        offsets[1:] = np.cumsum([len(x) for x in strings])
+        d_bytes = torch.frombuffer(bytearray(arena), dtype=torch.uint8).to(dev)
+        d_off = torch.from_numpy(offsets.view(np.int32)).to(dev)
+        n, (na, nb, nt) = len(strings), (int(v) for v in got["totals"][:3])
+        keep = (d_bytes, d_off, buf(n * 40), buf(n * 16), buf(na * 24), buf(nb * 16), buf(nt), torch.empty(4, dtype=torch.int32, device=dev))
+
+        def call():
+            return eng.lib.mnx_smiles_read(eng.h, ptr(keep[0]), len(arena), ptr(keep[1]), n, ptr(keep[2]), ptr(keep[3]), ptr(keep[4]), na,
+                                           ptr(keep[5]), nb, ptr(keep[6]), nt, ptr(keep[7]), stream())
+        return call, keep, got
+
+    mols, atoms, bonds, text = druglike_records(1024)
+    rec = {"mols": mols, "atoms": atoms, "bonds": bonds, "text": text}
+    tables, args = eng._packed_tables(rec)
+    recs, order, data = eng.smiles_pack(rec)
+    strings = [data[int(r["text0"]):int(r["text0"]) + int(r["len"])] for r in recs]
+    recs_d, order_d, out_d = buf(len(mols) * 16), torch.empty(len(atoms), dtype=torch.int16, device=dev), buf(len(data))
+    totals_w = torch.empty(2, dtype=torch.int32, device=dev)
+    read, keep, got = reader(strings)
+    assert not got["read"]["flags"].any() and got["mols"]["n_atoms"].tolist() == mols["n_atoms"].tolist()
+    us = timed({"mnx_smiles_pack": lambda: eng.lib.mnx_smiles_pack(eng.h, *args, ptr(recs_d), ptr(order_d), ptr(out_d), len(data), ptr(totals_w), stream()),
+                "mnx_smiles_read": read}, lambda k: not int(totals_w[1] if k == "mnx_smiles_pack" else keep[7][3]))
+    assert out_d.cpu().numpy().tobytes() == data and keep[6].cpu().numpy().tobytes() == got["text"]
+    lines.append(f"(r) one call over {len(mols)} hand-made molecules of drug-like size: {len(atoms)} atoms, {len(bonds)} bonds, {len(data)} "
+                 f"bytes of SMILES (mnx_smiles_pack writes them, mnx_smiles_read reads those very strings back)")
+    lines.append("  device us between two events around the launches, the two alternating   median [min .. max]")
+    for k in us:
+        lines.append(f"  {k:18s} {fmt(us[k])} us")
+    lines.append(f"  read / write, median {statistics.median(us['mnx_smiles_read']) / statistics.median(us['mnx_smiles_pack']):.2f}")
+    worst = {"one atom: C": b"C",
+             "4096 bytes of chain, 586 atoms": b"[13CH2]" * 585 + b"C",
+             "4096 bytes of nesting, 682 deep": b"[CH](" * 682 + b"[CH]" + b")" * 682,
+             "99 ring numbers open at one atom, 677 bytes": b"C" + b"".join(b"%d" % r for r in range(1, 10)) + b"".join(b"%%%02d" % r for r in range(10, 100)) + b"N" + b"".join(b"C%%%02d" % r for r in range(1, 100)),
+             "999 atoms in one ring, 999 bonds": b"C1" + b"C" * 997 + b"C1"}
+    calls, keeps = {}, {}
+    for k, s in worst.items():
+        calls[k], keeps[k], got = reader([s])
+        assert not int(got["read"]["flags"][0]) & E.READ_REFUSED, (k, got["read"])
+        lines.append(f"  {k}: {len(s)} bytes -> {int(got['mols']['n_atoms'][0])} atoms, {int(got['mols']['n_bonds'][0])} bonds, {int(got['read']['n_rings'][0])} ring bonds")
+    us = timed(calls, lambda k: not int(keeps[k][7][3]))
+    lines.append("  one string per call (one workgroup of 256 in count and in fill, three launches)   median [min .. max]")
+    base = statistics.median(us["one atom: C"])
+    for k in us:
+        lines.append(f"  {k:46s} {fmt(us[k])} us   {statistics.median(us[k]) - base:+.1f} us against one atom")
+    eng.close()
+
+
 def part_c(eng, repeats, lines):
     from molnextr_amd.preprocess import normalise_gray
     dev = torch.device("cuda", eng.device)
@@ -596,6 +679,7 @@ def main():
     ap.add_argument("--molfile-out", default=None, help="write the table of part m to this file")
     ap.add_argument("--smiles-out", default=None, help="write the table of part s to this file")
     ap.add_argument("--expand-out", default=None, help="write the table of part x to this file")
+    ap.add_argument("--read-out", default=None, help="write the table of part r to this file")
     ap.add_argument("--pack-only", type=int, default=0, help="run this many mnx_graph_pack calls over 1024 images and exit")
     args = ap.parse_args()
     parts = args.part.split(",")
@@ -643,6 +727,13 @@ def main():
         if args.expand_out:
             os.makedirs(os.path.dirname(os.path.abspath(args.expand_out)), exist_ok=True)
             with open(args.expand_out, "w") as f:
+                f.write("\n".join([lines[0]] + lines[first:]) + "\n")
+    if "r" in parts:
+        first = len(lines)
+        part_r(args.repeats, lines)
+        if args.read_out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.read_out)), exist_ok=True)
+            with open(args.read_out, "w") as f:
                 f.write("\n".join([lines[0]] + lines[first:]) + "\n")
     text = "\n".join(lines)
     print(text)
