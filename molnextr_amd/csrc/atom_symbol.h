@@ -2,7 +2,8 @@
 // atom's symbol read as the reference's _convert_graph_to_smiles reads it (chemical.py:886-903: brackets stripped, R-group table,
 // abbreviation table, and only then the whole symbol through the bracket-atom grammar), and behind it the admission of one molecule
 // of the packed tables and the loop over its atoms. One definition, so the two cannot drift apart (internal). What the writers
-// decide differently stays in their kernels: the bond loops, and with them a bond from an atom to itself.
+// decide differently stays in their kernels: the bond loops, and with them a bond from an atom to itself. This is the INPUT side
+// of the post-passes (PackedTables); the output side of those that write tables again (TablesOut) is tables_out.h.
 #pragma once
 #include <hip/hip_runtime.h>
 

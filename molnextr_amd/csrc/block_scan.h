@@ -1,6 +1,7 @@
 // block_scan.h — the workgroup prefix scan of the count / scan / fill post-passes (graph_pack.hip, molfile.hip, smiles.hip,
-// expand.hip) and the scans of the text and table writers over their molecules: one definition (internal). What the text writers share in front of
-// their scans, per molecule, is in atom_symbol.h.
+// expand.hip, smiles_read.hip) and the scan of the text writers over their molecules: one definition (internal). What the text
+// writers share in front of their scans, per molecule, is in atom_symbol.h; the scan of the table writers over their molecules
+// stands with the rest of their output side in tables_out.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -31,8 +32,8 @@ __device__ __forceinline__ unsigned block_scan_excl(unsigned v, unsigned* buf, u
 constexpr int TEXT_SCAN_THREADS = 1024;
 
 // text0 of every record of a text writer (mnx_molfile, mnx_smiles: both begin with text0, len): an exclusive scan of the
-// lengths in tiles of TEXT_SCAN_THREADS with a running 64-bit carry, by ONE workgroup (graph_pack.hip's scan over the images,
-// on one column); a total beyond 2^32 - 1 saturates and sets totals[1].
+// lengths in tiles of TEXT_SCAN_THREADS with a running 64-bit carry, by ONE workgroup (the table writers' scan over their
+// molecules, tables_out.h, on one column); a total beyond 2^32 - 1 saturates and sets totals[1].
 template <typename Rec>
 __global__ __launch_bounds__(TEXT_SCAN_THREADS) void text_scan_kernel(Rec* __restrict__ recs, int n, unsigned out_cap,
                                                                       unsigned* __restrict__ totals) {
@@ -49,39 +50,6 @@ __global__ __launch_bounds__(TEXT_SCAN_THREADS) void text_scan_kernel(Rec* __res
     if (tid == 0) {
         totals[0] = (unsigned)min(carry, 0xffffffffull);
         totals[1] = carry > out_cap ? 1u : 0u;
-    }
-}
-
-constexpr int MOL_SCAN_THREADS = 1024;
-
-// atom0 / bond0 / text0 of every record of a table writer (mnx_graph_pack, mnx_expand_pack): an exclusive scan of n_atoms, n_bonds
-// and smiles_len over the molecules in tiles of MOL_SCAN_THREADS with a running carry, by ONE workgroup (n molecules are a few
-// thousand words). 64-bit carries: a total beyond 2^32 - 1 saturates and sets totals[3].
-static __global__ __launch_bounds__(MOL_SCAN_THREADS) void mol_scan_kernel(mnx_mol* __restrict__ mols, int n, unsigned atom_cap,
-                                                                           unsigned bond_cap, unsigned text_cap,
-                                                                           unsigned* __restrict__ totals) {
-    __shared__ unsigned scan[2 * MOL_SCAN_THREADS];
-    const int tid = threadIdx.x;
-    unsigned long long ca = 0, cb = 0, ct = 0;
-    for (int base = 0; base < n; base += MOL_SCAN_THREADS) {
-        const int b = base + tid;
-        const unsigned a = b < n ? mols[b].n_atoms : 0u, bo = b < n ? mols[b].n_bonds : 0u, t = b < n ? mols[b].smiles_len : 0u;
-        unsigned ta, tb, tt;
-        const unsigned ea = block_scan_excl<MOL_SCAN_THREADS>(a, scan, &ta);
-        const unsigned eb = block_scan_excl<MOL_SCAN_THREADS>(bo, scan, &tb);
-        const unsigned et = block_scan_excl<MOL_SCAN_THREADS>(t, scan, &tt);
-        if (b < n) {
-            mols[b].atom0 = (unsigned)min(ca + ea, 0xffffffffull);
-            mols[b].bond0 = (unsigned)min(cb + eb, 0xffffffffull);
-            mols[b].text0 = (unsigned)min(ct + et, 0xffffffffull);
-        }
-        ca += ta; cb += tb; ct += tt;
-    }
-    if (tid == 0) {
-        totals[0] = (unsigned)min(ca, 0xffffffffull);
-        totals[1] = (unsigned)min(cb, 0xffffffffull);
-        totals[2] = (unsigned)min(ct, 0xffffffffull);
-        totals[3] = (ca > atom_cap || cb > bond_cap || ct > text_cap) ? 1u : 0u;
     }
 }
 

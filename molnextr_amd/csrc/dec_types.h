@@ -182,13 +182,21 @@ hipError_t confidence_enqueue(const DecBuffers& b, const TokenClasses* tc_dev, c
 hipError_t confidence_enqueue_raw(const TokenClasses* tc_dev, const int* tokens, const int* lens, const float* logp, int n,
                                   int T, int kmax, const int* atom_idx, const int* n_atoms, const double* scores,
                                   double* atom_scores, double* overall, hipStream_t s);
+// the arenas a table writer (mnx_graph_pack, mnx_expand_pack, mnx_smiles_read) fills: the molecule records, then the atom and
+// bond records as 64-bit words and the text, each with its capacity in records / bytes. Passed to kernels by value; what is
+// done with it is in tables_out.h.
+struct TablesOut {
+    mnx_mol* mols;
+    unsigned long long* atoms;  unsigned atom_cap;
+    unsigned long long* bonds;  unsigned bond_cap;
+    char* text;                 unsigned text_cap;
+};
 // graph_pack.hip: the dense outputs of n rows ([n,T] ids, [n,kmax] atoms, [n,kmax,kmax] bonds; the three score pointers all
 // null or all set) as packed records (mnx_graph_pack): count, scan and fill, three launches on s
 hipError_t graph_pack_enqueue(const TokenClasses* tc_dev, const VocabText* vt_dev, const int* tokens, const int* lens, int n,
                               int T, int kmax, const int* atom_idx, const int* n_atoms, const unsigned char* edges,
-                              const double* atom_scores, const double* edge_scores, const double* overall, mnx_mol* mols,
-                              mnx_atom* atoms, unsigned atom_cap, mnx_bond* bonds, unsigned bond_cap, char* text,
-                              unsigned text_cap, unsigned* totals, hipStream_t s);
+                              const double* atom_scores, const double* edge_scores, const double* overall, const TablesOut& o,
+                              unsigned* totals, hipStream_t s);
 // the R-group and abbreviation names (mnx_set_symbol_tables), sorted bytewise: what atom_symbol.h looks an atom's symbol up in
 struct SymbolTables {
     int n;
@@ -210,14 +218,12 @@ hipError_t molfile_pack_enqueue(const SymbolTables* st_dev, const PackedTables& 
                                 mnx_molfile* files, char* out, unsigned out_cap, unsigned* totals, hipStream_t s);
 // smiles.hip: the molecules of t as graph SMILES behind one another in `out`, the atoms' written positions in `order` (may be
 // null) (mnx_smiles_pack; marks, MNX_SMILES_MARK_*: with the '@' / '@@' of mnx_smiles_pack_stereo and the '/' '\\' of
-// mnx_smiles_pack_marks): count, scan and fill, three launches on s
+// mnx_smiles_pack_marks): count, scan and fill, three launches on s.
+// rank set (null otherwise): the same on canonical atom ranks (mnx_smiles_pack_canonical) — one launch in front leaves the ranks
+// in `rank` and the symmetry classes in `sym_class` (may be null), then count, scan and fill on those ranks; four launches on s
 hipError_t smiles_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, unsigned marks, mnx_smiles* recs,
-                               unsigned short* order, char* out, unsigned out_cap, unsigned* totals, hipStream_t s);
-// smiles.hip: the same on canonical atom ranks (mnx_smiles_pack_canonical): the ranks into `rank`, the symmetry classes into
-// `sym_class` (may be null), then count, scan and fill on those ranks; four launches on s
-hipError_t smiles_canonical_enqueue(const SymbolTables* st_dev, const PackedTables& t, unsigned marks, mnx_smiles* recs,
-                                    unsigned short* order, unsigned short* rank, unsigned short* sym_class, char* out,
-                                    unsigned out_cap, unsigned* totals, hipStream_t s);
+                               unsigned short* order, unsigned short* rank, unsigned short* sym_class, char* out,
+                               unsigned out_cap, unsigned* totals, hipStream_t s);
 // the fragment library (mnx_set_fragments) as the device holds it: ONE allocation — the table of fragment indices parallel to
 // SymbolTables' names, the fragment records, then their atoms, bonds and symbol bytes. The host has validated all of it and has
 // sorted every fragment's bonds by (i, j), so the bonds from atom 0 (the attachment atom) are the first n_bonds0 of a fragment.
@@ -234,14 +240,12 @@ struct FragView {                       // passed to kernels by value
 };
 // expand.hip: the molecules of t with every abbreviation label that has a fragment replaced by the fragment's atoms and bonds,
 // as packed tables of the same record types (mnx_expand_pack): count, scan and fill, three launches on s
-hipError_t expand_pack_enqueue(const SymbolTables* st_dev, const FragView& fv, const PackedTables& t, mnx_mol* mols,
-                               mnx_atom* atoms, unsigned atom_cap, mnx_bond* bonds, unsigned bond_cap, char* text,
-                               unsigned text_cap, unsigned short* origin, unsigned* totals, hipStream_t s);
+hipError_t expand_pack_enqueue(const SymbolTables* st_dev, const FragView& fv, const PackedTables& t, const TablesOut& o,
+                               unsigned short* origin, unsigned* totals, hipStream_t s);
 // smiles_read.hip: string b = bytes[offsets[b] .. offsets[b + 1]) read as SMILES into packed tables of mnx_graph_pack's record types
 // (mnx_smiles_read): count, scan and fill, three launches on s
-hipError_t smiles_read_enqueue(const unsigned char* bytes, unsigned n_bytes, const unsigned* offsets, int n, mnx_mol* mols,
-                               mnx_read* recs, mnx_atom* atoms, unsigned atom_cap, mnx_bond* bonds, unsigned bond_cap, char* text,
-                               unsigned text_cap, unsigned* totals, hipStream_t s);
+hipError_t smiles_read_enqueue(const unsigned char* bytes, unsigned n_bytes, const unsigned* offsets, int n, mnx_read* recs,
+                               const TablesOut& o, unsigned* totals, hipStream_t s);
 hipError_t edges_enqueue(const DecWeights& w, const DecBuffers& bf, const float* hidden, const int* slot_map,
                          const int* atom_idx, const int* n_atoms, int B, int kmax, int row_stride_T,
                          unsigned char* edges, double* scores, hipStream_t s);

@@ -1303,14 +1303,26 @@ int mnx_set_vocab_text(mnx_engine* h, const char* bytes, const uint32_t* offsets
     return MNX_OK;
 }
 
+// The output tables of mnx_graph_pack, mnx_expand_pack and mnx_smiles_read with their `totals`: what each tests of them
+static TablesOut tables_out(mnx_mol* mols, mnx_atom* atoms, uint32_t atom_cap, mnx_bond* bonds, uint32_t bond_cap, char* text,
+                            uint32_t text_cap) {
+    return TablesOut{mols, (unsigned long long*)atoms, atom_cap, (unsigned long long*)bonds, bond_cap, text, text_cap};
+}
+static bool tables_out_null(const TablesOut& o, const uint32_t* totals) {
+    return !o.mols || !totals || (!o.atoms && o.atom_cap) || (!o.bonds && o.bond_cap) || (!o.text && o.text_cap);
+}
+static bool tables_out_skew(const TablesOut& o, const uint32_t* totals) {
+    return ((((uintptr_t)o.mols | (uintptr_t)o.atoms | (uintptr_t)o.bonds) & 7) | ((uintptr_t)totals & 3)) != 0;
+}
+
 int mnx_graph_pack(mnx_engine* h, const int32_t* tokens, const int32_t* lengths, int32_t n, int32_t T,
                    const int32_t* atom_idx, const int32_t* n_atoms, const uint8_t* edges, int32_t kmax,
                    const double* atom_scores, const double* edge_scores, const double* overall_score, mnx_mol* mols,
                    mnx_atom* atoms, uint32_t atom_cap, mnx_bond* bonds, uint32_t bond_cap, char* text, uint32_t text_cap,
                    uint32_t* totals, void* stream) {
     if (!h) return MNX_ERR_INVALID_ARG;
-    if (!tokens || !lengths || !atom_idx || !n_atoms || !edges || !mols || !totals || (!atoms && atom_cap) ||
-        (!bonds && bond_cap) || (!text && text_cap)) {
+    const TablesOut o = tables_out(mols, atoms, atom_cap, bonds, bond_cap, text, text_cap);
+    if (!tokens || !lengths || !atom_idx || !n_atoms || !edges || tables_out_null(o, totals)) {
         h->err = "mnx_graph_pack: null pointer";
         return MNX_ERR_INVALID_ARG;
     }
@@ -1323,7 +1335,7 @@ int mnx_graph_pack(mnx_engine* h, const int32_t* tokens, const int32_t* lengths,
         h->err = "mnx_graph_pack: atom_scores, edge_scores and overall_score go together (all three or none)";
         return MNX_ERR_INVALID_ARG;
     }
-    if (((uintptr_t)mols | (uintptr_t)atoms | (uintptr_t)bonds) & 7 || ((uintptr_t)totals & 3)) {
+    if (tables_out_skew(o, totals)) {
         h->err = "mnx_graph_pack: mols, atoms and bonds must be 8-byte aligned, totals 4-byte";
         return MNX_ERR_INVALID_ARG;
     }
@@ -1331,8 +1343,7 @@ int mnx_graph_pack(mnx_engine* h, const int32_t* tokens, const int32_t* lengths,
     if (!h->have_vt) { h->err = "mnx_graph_pack: call mnx_set_vocab_text first"; return MNX_ERR_INVALID_ARG; }
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, graph_pack_enqueue(h->tc_dev, h->vt_dev, tokens, lengths, n, T, kmax, atom_idx, n_atoms, edges, atom_scores,
-                                 edge_scores, overall_score, mols, atoms, atom_cap, bonds, bond_cap, text, text_cap, totals,
-                                 (hipStream_t)stream));
+                                 edge_scores, overall_score, o, totals, (hipStream_t)stream));
     return MNX_OK;
 }
 
@@ -1489,16 +1500,14 @@ int mnx_expand_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_ato
                     mnx_atom* atoms_out, uint32_t atom_cap, mnx_bond* bonds_out, uint32_t bond_cap, char* text_out, uint32_t text_cap,
                     uint16_t* origin, uint32_t* totals, void* stream) {
     const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
-    if (int rc = check_packed_tables(h, "mnx_expand_pack", t,
-                                     !mols_out || !totals || (!atoms_out && atom_cap) || (!bonds_out && bond_cap) || (!text_out && text_cap),
-                                     (((uintptr_t)mols_out | (uintptr_t)atoms_out | (uintptr_t)bonds_out) & 7) != 0 ||
-                                         ((uintptr_t)totals & 3) != 0 || ((uintptr_t)origin & 1) != 0,
+    const TablesOut o = tables_out(mols_out, atoms_out, atom_cap, bonds_out, bond_cap, text_out, text_cap);
+    if (int rc = check_packed_tables(h, "mnx_expand_pack", t, tables_out_null(o, totals),
+                                     tables_out_skew(o, totals) || ((uintptr_t)origin & 1) != 0,
                                      "the output tables too, totals 4-byte, origin 2-byte"))
         return rc;
     if (!h->have_frag) { h->err = "mnx_expand_pack: call mnx_set_fragments first"; return MNX_ERR_INVALID_ARG; }
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, expand_pack_enqueue(h->st_dev, h->fv, t, mols_out, atoms_out, atom_cap, bonds_out, bond_cap, text_out, text_cap, origin,
-                                  totals, (hipStream_t)stream));
+    HIPCHK(h, expand_pack_enqueue(h->st_dev, h->fv, t, o, origin, totals, (hipStream_t)stream));
     return MNX_OK;
 }
 
@@ -1507,14 +1516,13 @@ int mnx_smiles_read(mnx_engine* h, const char* bytes, uint32_t n_bytes, const ui
                     uint32_t text_cap, uint32_t* totals, void* stream) {
     if (!h) return MNX_ERR_INVALID_ARG;
     auto bad = [&](const char* m) { h->err = std::string("mnx_smiles_read: ") + m; return MNX_ERR_INVALID_ARG; };
-    if ((!bytes && n_bytes) || !offsets || !mols || !recs || !totals || (!atoms && atom_cap) || (!bonds && bond_cap) || (!text && text_cap))
-        return bad("null pointer");
+    const TablesOut o = tables_out(mols, atoms, atom_cap, bonds, bond_cap, text, text_cap);
+    if ((!bytes && n_bytes) || !offsets || !recs || tables_out_null(o, totals)) return bad("null pointer");
     if (n < 1 || n > 65536) return bad("1 <= n <= 65536 required");
-    if ((((uintptr_t)mols | (uintptr_t)atoms | (uintptr_t)bonds) & 7) || (((uintptr_t)recs | (uintptr_t)offsets | (uintptr_t)totals) & 3))
+    if (tables_out_skew(o, totals) || (((uintptr_t)recs | (uintptr_t)offsets) & 3))
         return bad("mols, atoms and bonds must be 8-byte aligned, recs, offsets and totals 4-byte");
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, smiles_read_enqueue((const unsigned char*)bytes, n_bytes, offsets, n, mols, recs, atoms, atom_cap, bonds, bond_cap, text,
-                                  text_cap, totals, (hipStream_t)stream));
+    HIPCHK(h, smiles_read_enqueue((const unsigned char*)bytes, n_bytes, offsets, n, recs, o, totals, (hipStream_t)stream));
     return MNX_OK;
 }
 
@@ -1533,8 +1541,7 @@ static int smiles_pack(mnx_engine* h, const char* fn, uint32_t marks, const Pack
         return MNX_ERR_INVALID_ARG;
     }
     HIPCHK(h, hipSetDevice(h->device));
-    if (canonical) HIPCHK(h, smiles_canonical_enqueue(h->st_dev, t, marks, recs, order, rank, sym_class, out, out_cap, totals, (hipStream_t)stream));
-    else HIPCHK(h, smiles_pack_enqueue(h->st_dev, t, marks, recs, order, out, out_cap, totals, (hipStream_t)stream));
+    HIPCHK(h, smiles_pack_enqueue(h->st_dev, t, marks, recs, order, rank, sym_class, out, out_cap, totals, (hipStream_t)stream));
     return MNX_OK;
 }
 

@@ -4,25 +4,22 @@
 // same record types out, so that mnx_molfile_pack and the mnx_smiles_pack calls run on the expanded molecule unchanged.
 //   count  one workgroup per molecule: which atoms are labels with a fragment (atom_symbol.h reads the symbol, as the writers
 //          do), the atoms / bonds / text bytes of the expanded molecule -> mols_out[b]
-//   scan   exclusive scan of the three counts over the molecules -> atom0 / bond0 / text0, totals (block_scan.h)
+//   scan   exclusive scan of the three counts over the molecules -> atom0 / bond0 / text0, totals (tables_out.h)
 //   fill   one workgroup per molecule: the records behind those offsets
 // The rule stands in include/molnextr_hip.h. Every position follows from a prefix scan over the atoms (the appended atoms of a
 // label, the rows of the bond table, the bytes of the text) and, for a label's own row, from a binary search in the molecule's
-// bond records, which are sorted by i: no atomics, the output is the same word for word on every run. Records are written as
-// whole 64-bit words, padding bytes as zeros. The fragment tables are read from global memory (a few KB, shared by every
+// bond records, which are sorted by i: no atomics, the output is the same word for word on every run. Where a record's
+// fields go is tables_out.h. The fragment tables are read from global memory (a few KB, shared by every
 // workgroup of the launch).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/molnextr_hip.h"
 #include "atom_symbol.h"
-#include "block_scan.h"
 #include "dec_types.h"
+#include "tables_out.h"
 
 namespace mnx {
-
-static_assert(sizeof(mnx_mol) == 40 && sizeof(mnx_atom) == 24 && sizeof(mnx_bond) == 16, "record layout of molnextr_hip.h");
-
 namespace {
 
 constexpr int EX_THREADS = 256;
@@ -65,9 +62,8 @@ __device__ __forceinline__ Grow grow_of(const PackedTables& t, const SymbolTable
 
 template <bool FILL>
 __global__ __launch_bounds__(EX_THREADS) void expand_kernel(
-        const PackedTables t, const SymbolTables* __restrict__ st, const FragView fv, mnx_mol* __restrict__ mols_out,
-        unsigned long long* __restrict__ atoms_out, unsigned atom_cap, unsigned long long* __restrict__ bonds_out,
-        unsigned bond_cap, char* __restrict__ text_out, unsigned text_cap, unsigned short* __restrict__ origin) {
+        const PackedTables t, const SymbolTables* __restrict__ st, const FragView fv, const TablesOut o,
+        unsigned short* __restrict__ origin) {
     // fill: per atom, what lies in front of it — appended atoms, bonds from attachment atoms, bonds among appended atoms, bytes
     // of the molecule's own atoms' symbols, bytes of the appended atoms' symbols
     __shared__ unsigned off_atoms[FILL ? EX_MAX : 1], off_b0[FILL ? EX_MAX : 1], off_bin[FILL ? EX_MAX : 1];
@@ -78,17 +74,11 @@ __global__ __launch_bounds__(EX_THREADS) void expand_kernel(
     const Molecule mol = admit_molecule(t, b);
     const mnx_mol& m = mol.m;
     auto record = [&](unsigned n_atoms, unsigned n_bonds, unsigned text_len, unsigned flags) {      // count's result
-        if (tid == 0) {
-            mnx_mol* o = &mols_out[b];          // atom0 / bond0 / text0 are the scan's
-            o->n_atoms = n_atoms; o->n_bonds = n_bonds; o->smiles_len = text_len;
-            o->flags = flags | (m.flags & MNX_MOL_TRUNCATED);
-            o->reserved = 0;
-            o->overall_score = m.overall_score;
-        }
+        if (tid == 0) store_mol_counts(&o.mols[b], n_atoms, n_bonds, text_len, flags | (m.flags & MNX_MOL_TRUNCATED), m.overall_score);
     };
     mnx_mol mo;
     if (FILL) {
-        mo = mols_out[b];
+        mo = o.mols[b];
         if (mo.flags & MNX_MOL_EXPAND_REFUSED) return;      // refused by count (the same for every thread)
     } else if ((mol.flags & PT_BEYOND_TABLES) || m.n_atoms > EX_ATOM_LIMIT) {
         record(0, 0, 0, MNX_MOL_EXPAND_REFUSED);
@@ -147,26 +137,16 @@ __global__ __launch_bounds__(EX_THREADS) void expand_kernel(
     __syncthreads();
 
     const unsigned char* text_in = t.text + m.text0;
-    auto put_atom = [&](unsigned k, unsigned sym0, unsigned sym_len, unsigned long long w0, unsigned long long w1,
-                        unsigned long long w2, unsigned from) {     // atom k of the new molecule: index, bins and score of w0..w2
+    // atom k of the new molecule, its symbol at byte sym0 of the new text: index, bins and score of the input record w0..w2
+    auto atom = [&](unsigned k, unsigned sym0, const unsigned char* sym, unsigned sym_len, unsigned long long w0,
+                    unsigned long long w1, unsigned long long w2, unsigned from) {
         const unsigned long long at = (unsigned long long)mo.atom0 + k;
-        if (at >= atom_cap) return;
-        unsigned long long* r = atoms_out + at * 3;
-        r[0] = (unsigned long long)sym0 | ((unsigned long long)sym_len << 32) | (w0 & 0xffff000000000000ull);
-        r[1] = w1 & 0xffffffffull;
-        r[2] = w2;
-        if (origin) origin[at] = (unsigned short)from;
+        if (put_atom(o, at, atom_word0(sym0, sym_len, 0u) | (w0 & ATOM_INDEX_BITS), w1 & ATOM_BINS_BITS, w2) && origin)
+            origin[at] = (unsigned short)from;
+        put_text(o, (unsigned long long)mo.text0 + sym0, sym, sym_len);
     };
-    auto put_text = [&](unsigned at0, const unsigned char* src, unsigned n) {
-        const unsigned long long at = (unsigned long long)mo.text0 + at0;
-        for (unsigned c = 0; c < n; ++c)
-            if (at + c < text_cap) text_out[at + c] = (char)src[c];
-    };
-    auto put_bond = [&](unsigned k, unsigned long long w0, unsigned long long w1) {
-        const unsigned long long at = (unsigned long long)mo.bond0 + k;
-        if (at >= bond_cap) return;
-        bonds_out[at * 2] = w0 & 0xffffffffffffull;
-        bonds_out[at * 2 + 1] = w1;
+    auto bond = [&](unsigned k, unsigned long long w0, unsigned long long w1) {
+        put_bond(o, (unsigned long long)mo.bond0 + k, w0 & BOND_FIELD_BITS, w1);
     };
 
     // ---- atoms and text: the molecule's own atoms keep their indices, a label's further atoms follow behind them ----
@@ -175,8 +155,7 @@ __global__ __launch_bounds__(EX_THREADS) void expand_kernel(
         const int fi = frag_of[a];
         if (fi < 0) {
             const unsigned sl = (unsigned)(w0 >> 32) & 0xffffu;
-            put_atom((unsigned)a, off_text[a], sl, w0, w1, w2, (unsigned)a);
-            put_text(off_text[a], text_in + (unsigned)w0, sl);
+            atom((unsigned)a, off_text[a], text_in + (unsigned)w0, sl, w0, w1, w2, (unsigned)a);
             continue;
         }
         const FragRec f = fv.frag[fi];
@@ -186,8 +165,7 @@ __global__ __launch_bounds__(EX_THREADS) void expand_kernel(
         for (unsigned q = 0; q < f.n_atoms; ++q) {
             const unsigned fa = fv.atoms[f.atom0 + q], fs0 = fa & 0xffffu, fl = fa >> 16;
             const unsigned at = q == 0 ? off_text[a] : more0 + fs0 - len0;
-            put_atom(q == 0 ? (unsigned)a : first + q - 1, at, fl, w0, w1, w2, (unsigned)a);
-            put_text(at, fv.text + f.text0 + fs0, fl);
+            atom(q == 0 ? (unsigned)a : first + q - 1, at, fv.text + f.text0 + fs0, fl, w0, w1, w2, (unsigned)a);
         }
         // its bonds: those from the attachment atom behind the bond records of row a, the others in the rows of the appended atoms
         unsigned lo = 0, hi = nb;                                    // first record with i > a
@@ -199,28 +177,24 @@ __global__ __launch_bounds__(EX_THREADS) void expand_kernel(
         for (unsigned k = 0; k < f.n_bonds; ++k) {
             const unsigned fb = fv.bonds[f.bond0 + k], p = fb & 0xffu, q = fb >> 8 & 0xffu, ty = fb >> 16 & 0xffu;
             const unsigned i = p == 0 ? (unsigned)a : first + p - 1, j = first + q - 1;
-            put_bond(k < f.n_bonds0 ? row + k : inner + (k - f.n_bonds0),
-                     (unsigned long long)i | ((unsigned long long)j << 16) | ((unsigned long long)ty << 32) | ((unsigned long long)ty << 40), w2);
+            bond(k < f.n_bonds0 ? row + k : inner + (k - f.n_bonds0), bond_word0(i, j, ty, ty), w2);
         }
     }
 
     // ---- the molecule's own bonds, each moved back by the attachment bonds of the rows in front of its own ----
     for (unsigned k = tid; k < nb; k += EX_THREADS) {
         const unsigned long long w0 = B[2 * (size_t)k], w1 = B[2 * (size_t)k + 1];
-        put_bond(k + off_b0[(unsigned)w0 & (EX_MAX - 1)], w0, w1);
+        bond(k + off_b0[(unsigned)w0 & (EX_MAX - 1)], w0, w1);
     }
 }
 
 }  // namespace
 
-hipError_t expand_pack_enqueue(const SymbolTables* st_dev, const FragView& fv, const PackedTables& t, mnx_mol* mols,
-                               mnx_atom* atoms, unsigned atom_cap, mnx_bond* bonds, unsigned bond_cap, char* text,
-                               unsigned text_cap, unsigned short* origin, unsigned* totals, hipStream_t s) {
-    hipLaunchKernelGGL(expand_kernel<false>, dim3(t.n), dim3(EX_THREADS), 0, s, t, st_dev, fv, mols, (unsigned long long*)atoms,
-                       atom_cap, (unsigned long long*)bonds, bond_cap, text, text_cap, origin);
-    hipLaunchKernelGGL(mol_scan_kernel, dim3(1), dim3(MOL_SCAN_THREADS), 0, s, mols, t.n, atom_cap, bond_cap, text_cap, totals);
-    hipLaunchKernelGGL(expand_kernel<true>, dim3(t.n), dim3(EX_THREADS), 0, s, t, st_dev, fv, mols, (unsigned long long*)atoms,
-                       atom_cap, (unsigned long long*)bonds, bond_cap, text, text_cap, origin);
+hipError_t expand_pack_enqueue(const SymbolTables* st_dev, const FragView& fv, const PackedTables& t, const TablesOut& o,
+                               unsigned short* origin, unsigned* totals, hipStream_t s) {
+    hipLaunchKernelGGL(expand_kernel<false>, dim3(t.n), dim3(EX_THREADS), 0, s, t, st_dev, fv, o, origin);
+    hipLaunchKernelGGL(mol_scan_kernel, dim3(1), dim3(MOL_SCAN_THREADS), 0, s, o, t.n, totals);
+    hipLaunchKernelGGL(expand_kernel<true>, dim3(t.n), dim3(EX_THREADS), 0, s, t, st_dev, fv, o, origin);
     return hipGetLastError();
 }
 

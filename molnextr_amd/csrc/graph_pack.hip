@@ -2,22 +2,19 @@
 // CharTokenizer.sequence_to_smiles (reference tokenization.py:464-515) and the pair loop of predict_images (model.py:135-143)
 // derive on the host, as three launches on the device.
 //   count  one workgroup per image: atoms, bonds and SMILES bytes of the image -> mols[b]
-//   scan   exclusive scan of the three counts over the images -> atom0 / bond0 / text0 of every image, totals (block_scan.h)
+//   scan   exclusive scan of the three counts over the images -> atom0 / bond0 / text0 of every image, totals (tables_out.h)
 //   fill   one workgroup per image: text, atom records, bond records behind those offsets
 // Every position in the tables follows from a prefix scan: no atomics, the output is the same word for word on every run.
-// Records are written as whole 64-bit words, padding bytes as zeros.
+// Where a record's fields go — the words of a record, the capped stores — is tables_out.h too.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/molnextr_hip.h"
 #include "atom_walk.h"
-#include "block_scan.h"
 #include "dec_types.h"
+#include "tables_out.h"
 
 namespace mnx {
-
-static_assert(sizeof(mnx_mol) == 40 && sizeof(mnx_atom) == 24 && sizeof(mnx_bond) == 16, "record layout of molnextr_hip.h");
-
 namespace {
 
 constexpr int GP_THREADS = 256;
@@ -62,17 +59,6 @@ __device__ __forceinline__ unsigned name_bytes(const RowLds& L, int t, int x0) {
     return (unsigned)t < (unsigned)min(x0, 256) ? L.vlen[t] : 0u;
 }
 
-__device__ __forceinline__ void store_mol_counts(mnx_mol* m, unsigned n_atoms, unsigned n_bonds, unsigned smiles_len,
-                                                 unsigned flags, double overall) {
-    // atom0 / bond0 / text0 are the scan's; everything else of the record is written here
-    m->n_atoms = n_atoms;
-    m->n_bonds = n_bonds;
-    m->smiles_len = smiles_len;
-    m->flags = flags;
-    m->reserved = 0;
-    m->overall_score = overall;
-}
-
 __global__ __launch_bounds__(GP_THREADS) void graph_count_kernel(
         const int* __restrict__ tokens, const int* __restrict__ lens, const TokenClasses* __restrict__ tc,
         const VocabText* __restrict__ vt, int T, int kmax, const int* __restrict__ n_atoms,
@@ -104,9 +90,7 @@ __global__ __launch_bounds__(GP_THREADS) void graph_fill_kernel(
         const int* __restrict__ tokens, const int* __restrict__ lens, const TokenClasses* __restrict__ tc,
         const VocabText* __restrict__ vt, int T, int kmax, const int* __restrict__ atom_idx,
         const int* __restrict__ n_atoms, const unsigned char* __restrict__ edges, const double* __restrict__ atom_scores,
-        const double* __restrict__ edge_scores, const mnx_mol* __restrict__ mols, unsigned long long* __restrict__ atoms,
-        unsigned atom_cap, unsigned long long* __restrict__ bonds, unsigned bond_cap, char* __restrict__ text,
-        unsigned text_cap) {
+        const double* __restrict__ edge_scores, const TablesOut o) {
     __shared__ RowLds L;
     __shared__ unsigned scan[2 * GP_THREADS];
     __shared__ unsigned off[GP_T + 1];               // byte offset of every id inside the image's SMILES
@@ -120,7 +104,7 @@ __global__ __launch_bounds__(GP_THREADS) void graph_fill_kernel(
         atom_walk(L.seq, n, L.fl, tc, [&](int a, int i0, int j) {
             if (a < GP_ATOMS) { span0[a] = (short)i0; span1[a] = (short)j; }
         });
-    const mnx_mol m = mols[row];
+    const mnx_mol m = o.mols[row];
     const int x0 = tc->x0, y0 = tc->y0;
 
     // ---- text: per-id byte offsets by a prefix scan (two neighbouring ids per thread), then every id copies its name ----
@@ -134,26 +118,16 @@ __global__ __launch_bounds__(GP_THREADS) void graph_fill_kernel(
     __syncthreads();
     for (int i = tid; i < end; i += GP_THREADS) {
         const int t = L.seq[i];
-        const unsigned nb = name_bytes(L, t, x0);
-        const unsigned at = m.text0 + off[i];
-        for (unsigned c = 0; c < nb; ++c)
-            if ((unsigned long long)at + c < text_cap) text[at + c] = (char)vname[t * 8 + c];
+        put_text(o, m.text0 + off[i], vname + (t & 255) * 8, name_bytes(L, t, x0));      // no bytes for an id beyond 255
     }
 
-    // ---- atoms: one record per atom of the walk, three 64-bit words ----
+    // ---- atoms: one record per atom of the walk ----
     const int k = (int)m.n_atoms;
     for (int a = tid; a < k; a += GP_THREADS) {
-        const unsigned long long at = (unsigned long long)m.atom0 + a;
-        if (at >= atom_cap) continue;
         const int s0 = span0[a], s1 = span1[a];
-        const unsigned sym0 = off[s0], sym_len = off[s1] - off[s0];
-        const unsigned idx = (unsigned)atom_idx[(size_t)row * kmax + a] & 0xffffu;
-        const unsigned xb = (unsigned)(L.seq[s1] - x0) & 0xffffu, yb = (unsigned)(L.seq[s1 + 1] - y0) & 0xffffu;
-        const double sc = atom_scores ? atom_scores[(size_t)row * kmax + a] : 0.0;
-        unsigned long long* r = atoms + at * 3;
-        r[0] = (unsigned long long)sym0 | ((unsigned long long)(sym_len & 0xffffu) << 32) | ((unsigned long long)idx << 48);
-        r[1] = (unsigned long long)xb | ((unsigned long long)yb << 16);
-        r[2] = (unsigned long long)__double_as_longlong(sc);
+        put_atom(o, (unsigned long long)m.atom0 + a, atom_word0(off[s0], off[s1] - off[s0], (unsigned)atom_idx[(size_t)row * kmax + a]),
+                 atom_word1((unsigned)(L.seq[s1] - x0), (unsigned)(L.seq[s1 + 1] - y0)),
+                 score_word(atom_scores ? atom_scores[(size_t)row * kmax + a] : 0.0));
     }
 
     // ---- bonds: ordered compaction — row counts, a scan over the rows (tiles of GP_THREADS rows with a carry), then every
@@ -174,14 +148,9 @@ __global__ __launch_bounds__(GP_THREADS) void graph_fill_kernel(
             for (int j = i + 1; j < kb; ++j) {
                 const unsigned ty = e[(size_t)i * kmax + j];
                 if (!ty) continue;
-                const unsigned long long o = (unsigned long long)m.bond0 + at;
+                put_bond(o, (unsigned long long)m.bond0 + at, bond_word0((unsigned)i, (unsigned)j, ty, e[(size_t)j * kmax + i]),
+                         score_word(es ? es[(size_t)i * kmax + j] : 0.0));
                 ++at;
-                if (o >= bond_cap) continue;
-                const unsigned rv = e[(size_t)j * kmax + i];
-                const double sc = es ? es[(size_t)i * kmax + j] : 0.0;
-                bonds[o * 2] = (unsigned long long)(unsigned)i | ((unsigned long long)(unsigned)j << 16) |
-                               ((unsigned long long)ty << 32) | ((unsigned long long)rv << 40);
-                bonds[o * 2 + 1] = (unsigned long long)__double_as_longlong(sc);
             }
     }
 }
@@ -190,15 +159,13 @@ __global__ __launch_bounds__(GP_THREADS) void graph_fill_kernel(
 
 hipError_t graph_pack_enqueue(const TokenClasses* tc_dev, const VocabText* vt_dev, const int* tokens, const int* lens, int n,
                               int T, int kmax, const int* atom_idx, const int* n_atoms, const unsigned char* edges,
-                              const double* atom_scores, const double* edge_scores, const double* overall, mnx_mol* mols,
-                              mnx_atom* atoms, unsigned atom_cap, mnx_bond* bonds, unsigned bond_cap, char* text,
-                              unsigned text_cap, unsigned* totals, hipStream_t s) {
+                              const double* atom_scores, const double* edge_scores, const double* overall, const TablesOut& o,
+                              unsigned* totals, hipStream_t s) {
     hipLaunchKernelGGL(graph_count_kernel, dim3(n), dim3(GP_THREADS), 0, s, tokens, lens, tc_dev, vt_dev, T, kmax, n_atoms,
-                       edges, overall, mols);
-    hipLaunchKernelGGL(mol_scan_kernel, dim3(1), dim3(MOL_SCAN_THREADS), 0, s, mols, n, atom_cap, bond_cap, text_cap, totals);
+                       edges, overall, o.mols);
+    hipLaunchKernelGGL(mol_scan_kernel, dim3(1), dim3(MOL_SCAN_THREADS), 0, s, o, n, totals);
     hipLaunchKernelGGL(graph_fill_kernel, dim3(n), dim3(GP_THREADS), 0, s, tokens, lens, tc_dev, vt_dev, T, kmax, atom_idx,
-                       n_atoms, edges, atom_scores, edge_scores, mols, (unsigned long long*)atoms, atom_cap,
-                       (unsigned long long*)bonds, bond_cap, text, text_cap);
+                       n_atoms, edges, atom_scores, edge_scores, o);
     return hipGetLastError();
 }
 

@@ -45,6 +45,10 @@ __device__ __forceinline__ unsigned slot_owner(unsigned e) { return e >> 13 & 10
 __device__ __forceinline__ unsigned slot_seen(unsigned cls) { return cls == 5 ? SLOT_UP : cls == 6 ? SLOT_DOWN : 0u; }
 __device__ __forceinline__ long long slot_z(unsigned e) { return (long long)(e >> 24 & 1u) - (long long)(e >> 25 & 1u); }
 
+// the written class of a bond record's `type`: a wedge is a single bond
+__device__ __forceinline__ unsigned bond_class(unsigned ty) {
+    return (ty == 1 || ty == 5 || ty == 6) ? B_SINGLE : ty == 2 ? B_DOUBLE : ty == 3 ? B_TRIPLE : ty == 4 ? B_AROMATIC : B_ANY;
+}
 // det of the rows a, b, c, exact in 64 bits (|x|, |y| < 2^18 and |z| <= 2 here)
 __device__ __forceinline__ long long det3(long long ax, long long ay, long long az, long long bx, long long by, long long bz,
                                           long long cx, long long cy, long long cz) {
@@ -182,7 +186,7 @@ __global__ __launch_bounds__(SM_THREADS) void canon_rank_kernel(
     __syncthreads();
     for (int k = tid; k < nb; k += SM_THREADS) {
         const unsigned i = B[k].i, j = B[k].j, ty = B[k].type;
-        const unsigned cls = (ty == 1 || ty == 5 || ty == 6) ? B_SINGLE : ty == 2 ? B_DOUBLE : ty == 3 ? B_TRIPLE : ty == 4 ? B_AROMATIC : B_ANY;
+        const unsigned cls = bond_class(ty);
         raw[off[i] + atomicAdd(&cnt[i], 1u)] = j | cls << 10 | i << 13;   // any slot of the list: every round sorts by value
         raw[off[j] + atomicAdd(&cnt[j], 1u)] = i | cls << 10 | j << 13;
     }
@@ -393,7 +397,7 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
     __syncthreads();
     for (int k = tid; k < nb; k += SM_THREADS) {
         const unsigned i = B[k].i, j = B[k].j, ty = type_of(k, i, j);
-        const unsigned cls = (ty == 1 || ty == 5 || ty == 6) ? B_SINGLE : ty == 2 ? B_DOUBLE : ty == 3 ? B_TRIPLE : ty == 4 ? B_AROMATIC : B_ANY;
+        const unsigned cls = bond_class(ty);
         const unsigned si = STEREO ? slot_seen(B[k].type) : 0u, sj = STEREO ? slot_seen(B[k].rev) : 0u;     // edges[i][j], edges[j][i]
         raw[off[i] + atomicAdd(&cnt[i], 1u)] = j | cls << 10 | i << 13 | si;  // any slot of the list: the sort below fixes the order
         raw[off[j] + atomicAdd(&cnt[j], 1u)] = i | cls << 10 | j << 13 | sj;
@@ -757,28 +761,22 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
         for (int a = tid; a < na; a += SM_THREADS) order[m.atom0 + a] = pos[a];
 }
 
+// the kernel of a set of marks
+template <bool FILL, bool CANON>
+auto smiles_kernel_for(unsigned marks) {
+    return marks == 3u ? smiles_kernel<FILL, 3u, CANON> : marks == 2u ? smiles_kernel<FILL, 2u, CANON>
+         : marks == 1u ? smiles_kernel<FILL, 1u, CANON> : smiles_kernel<FILL, 0u, CANON>;
+}
+
 }  // namespace
 
 hipError_t smiles_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, unsigned marks, mnx_smiles* recs,
-                               unsigned short* order, char* out, unsigned out_cap, unsigned* totals, hipStream_t s) {
-    const auto count = marks == 3u ? smiles_kernel<false, 3u> : marks == 2u ? smiles_kernel<false, 2u>
-                     : marks == 1u ? smiles_kernel<false, 1u> : smiles_kernel<false, 0u>;
-    const auto fill = marks == 3u ? smiles_kernel<true, 3u> : marks == 2u ? smiles_kernel<true, 2u>
-                    : marks == 1u ? smiles_kernel<true, 1u> : smiles_kernel<true, 0u>;
-    hipLaunchKernelGGL(count, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, order, out, out_cap, nullptr);
-    hipLaunchKernelGGL(text_scan_kernel<mnx_smiles>, dim3(1), dim3(TEXT_SCAN_THREADS), 0, s, recs, t.n, out_cap, totals);
-    hipLaunchKernelGGL(fill, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, order, out, out_cap, nullptr);
-    return hipGetLastError();
-}
-
-hipError_t smiles_canonical_enqueue(const SymbolTables* st_dev, const PackedTables& t, unsigned marks, mnx_smiles* recs,
-                                    unsigned short* order, unsigned short* rank, unsigned short* sym_class, char* out,
-                                    unsigned out_cap, unsigned* totals, hipStream_t s) {
-    const auto count = marks == 3u ? smiles_kernel<false, 3u, true> : marks == 2u ? smiles_kernel<false, 2u, true>
-                     : marks == 1u ? smiles_kernel<false, 1u, true> : smiles_kernel<false, 0u, true>;
-    const auto fill = marks == 3u ? smiles_kernel<true, 3u, true> : marks == 2u ? smiles_kernel<true, 2u, true>
-                    : marks == 1u ? smiles_kernel<true, 1u, true> : smiles_kernel<true, 0u, true>;
-    hipLaunchKernelGGL(canon_rank_kernel, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, rank, sym_class);
+                               unsigned short* order, unsigned short* rank, unsigned short* sym_class, char* out,
+                               unsigned out_cap, unsigned* totals, hipStream_t s) {
+    const bool canon = rank != nullptr;
+    const auto count = canon ? smiles_kernel_for<false, true>(marks) : smiles_kernel_for<false, false>(marks);
+    const auto fill = canon ? smiles_kernel_for<true, true>(marks) : smiles_kernel_for<true, false>(marks);
+    if (canon) hipLaunchKernelGGL(canon_rank_kernel, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, rank, sym_class);
     hipLaunchKernelGGL(count, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, order, out, out_cap, rank);
     hipLaunchKernelGGL(text_scan_kernel<mnx_smiles>, dim3(1), dim3(TEXT_SCAN_THREADS), 0, s, recs, t.n, out_cap, totals);
     hipLaunchKernelGGL(fill, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, order, out, out_cap, rank);

@@ -1,7 +1,7 @@
 // smiles_read.hip — SMILES text read into the packed molecule tables (mnx_smiles_read): the inverse of mnx_smiles_pack, so that
 // every pass over mnx_mol / mnx_atom / mnx_bond (canonical ranks, expansion, molfiles) runs on a caller's own strings.
 //   count  one workgroup per string: tokens, atoms, bonds, the refusals -> mols[b] (n_atoms, n_bonds, smiles_len) and recs[b]
-//   scan   exclusive scan of the three counts over the strings -> atom0 / bond0 / text0, totals (block_scan.h, mol_scan_kernel)
+//   scan   exclusive scan of the three counts over the strings -> atom0 / bond0 / text0, totals (tables_out.h)
 //   fill   one workgroup per string: the same reading again, the records behind those offsets
 // The rule stands in include/molnextr_hip.h. A string of up to 4096 bytes lies in LDS, 16 neighbouring bytes per thread:
 //   parallel   the nearest bracket in front of every byte (a workgroup max scan) -> inside / outside a bracket atom, the bracket
@@ -13,20 +13,16 @@
 //   parallel   the rows of the bond table: a workgroup scan of the bonds per lower atom, then each bond's rank among its row's
 //              entries by their higher atom (as smiles.hip orders its lists), which also finds the same pair twice
 // Every position comes from a scan or a rank; the lowest error position is a minimum (LDS atomicMin on a value, no position or
-// order depends on it). No symbol tables: a bracket atom's bytes are copied, not interpreted. Records are written as whole 64-bit
-// words, padding bytes as zeros.
+// order depends on it). No symbol tables: a bracket atom's bytes are copied, not interpreted. Where a record's fields go is
+// tables_out.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/molnextr_hip.h"
-#include "block_scan.h"
 #include "dec_types.h"
+#include "tables_out.h"
 
 namespace mnx {
-
-static_assert(sizeof(mnx_mol) == 40 && sizeof(mnx_atom) == 24 && sizeof(mnx_bond) == 16 && sizeof(mnx_read) == 16,
-              "record layout of molnextr_hip.h");
-
 namespace {
 
 constexpr int SR_THREADS = 256;
@@ -72,8 +68,7 @@ __device__ __forceinline__ unsigned symbol_type(unsigned c) {
 template <bool FILL>
 __global__ __launch_bounds__(SR_THREADS) void smiles_read_kernel(
         const unsigned char* __restrict__ bytes, unsigned n_bytes, const unsigned* __restrict__ offsets,
-        mnx_mol* __restrict__ mols, mnx_read* __restrict__ recs, unsigned long long* __restrict__ atoms_out, unsigned atom_cap,
-        unsigned long long* __restrict__ bonds_out, unsigned bond_cap, char* __restrict__ text_out, unsigned text_cap) {
+        mnx_read* __restrict__ recs, const TablesOut o) {
     __shared__ unsigned char s[SR_BYTES + 4];            // the string, zeros behind it
     __shared__ unsigned char kind[SR_BYTES];             // the token a byte begins, K_NONE inside a token
     __shared__ unsigned short aux[SR_BYTES];             // first: at a '[' the position of its ']'; then the walk's stack of atoms
@@ -93,14 +88,12 @@ __global__ __launch_bounds__(SR_THREADS) void smiles_read_kernel(
 
     auto record = [&](unsigned n_atoms, unsigned n_bonds, unsigned len, unsigned flags, unsigned err_pos, unsigned n_rings) {
         if (FILL || tid != 0) return;
-        mnx_mol* o = &mols[b];              // atom0 / bond0 / text0 are the scan's
-        o->n_atoms = n_atoms; o->n_bonds = n_bonds; o->smiles_len = len;
-        o->flags = 0; o->reserved = 0; o->overall_score = 0.0;
+        store_mol_counts(&o.mols[b], n_atoms, n_bonds, len, 0u, 0.0);
         recs[b] = mnx_read{flags, err_pos, n_rings, 0u};
     };
     mnx_mol mo;
     if (FILL) {
-        mo = mols[b];
+        mo = o.mols[b];
         if (mo.smiles_len == 0) return;     // refused by count, or the empty string (the same for every thread)
     } else {
         if (o0 > o1 || o1 > n_bytes) { record(0, 0, 0, MNX_READ_BEYOND, 0, 0); return; }
@@ -327,37 +320,22 @@ __global__ __launch_bounds__(SR_THREADS) void smiles_read_kernel(
     }
 
     // ---- fill: count admitted the string, mo holds its offsets ----
-    for (unsigned k = tid; k < n_atoms; k += SR_THREADS) {
-        const unsigned long long at = (unsigned long long)mo.atom0 + k;
-        if (at >= atom_cap) continue;
-        unsigned long long* r = atoms_out + at * 3;
-        r[0] = (unsigned long long)apos[k] | (unsigned long long)(alen[k] & 0x7fffu) << 32 | (unsigned long long)k << 48;
-        r[1] = 0;
-        r[2] = 0;
-    }
+    for (unsigned k = tid; k < n_atoms; k += SR_THREADS)          // no bins, no scores
+        put_atom(o, (unsigned long long)mo.atom0 + k, atom_word0(apos[k], alen[k] & 0x7fffu, k), 0, 0);
     for (unsigned e = tid; e < n_ent; e += SR_THREADS) {
         const unsigned w = ent[e], i = w & 1023u, j = w >> 10 & 1023u, ty = w >> 20;
-        const unsigned long long at = (unsigned long long)mo.bond0 + rowoff[i] + eidx[e];
-        if (at >= bond_cap) continue;
-        bonds_out[at * 2] = (unsigned long long)i | (unsigned long long)j << 16 | (unsigned long long)ty << 32 | (unsigned long long)ty << 40;
-        bonds_out[at * 2 + 1] = 0;
+        put_bond(o, (unsigned long long)mo.bond0 + rowoff[i] + eidx[e], bond_word0(i, j, ty, ty), 0);
     }
-    for (int p = tid; p < L; p += SR_THREADS) {
-        const unsigned long long at = (unsigned long long)mo.text0 + (unsigned)p;
-        if (at < text_cap) text_out[at] = (char)s[p];
-    }
+    for (int p = tid; p < L; p += SR_THREADS) put_text(o, (unsigned long long)mo.text0 + (unsigned)p, &s[p], 1);
 }
 
 }  // namespace
 
-hipError_t smiles_read_enqueue(const unsigned char* bytes, unsigned n_bytes, const unsigned* offsets, int n, mnx_mol* mols,
-                               mnx_read* recs, mnx_atom* atoms, unsigned atom_cap, mnx_bond* bonds, unsigned bond_cap, char* text,
-                               unsigned text_cap, unsigned* totals, hipStream_t s) {
-    hipLaunchKernelGGL(smiles_read_kernel<false>, dim3(n), dim3(SR_THREADS), 0, s, bytes, n_bytes, offsets, mols, recs,
-                       (unsigned long long*)atoms, atom_cap, (unsigned long long*)bonds, bond_cap, text, text_cap);
-    hipLaunchKernelGGL(mol_scan_kernel, dim3(1), dim3(MOL_SCAN_THREADS), 0, s, mols, n, atom_cap, bond_cap, text_cap, totals);
-    hipLaunchKernelGGL(smiles_read_kernel<true>, dim3(n), dim3(SR_THREADS), 0, s, bytes, n_bytes, offsets, mols, recs,
-                       (unsigned long long*)atoms, atom_cap, (unsigned long long*)bonds, bond_cap, text, text_cap);
+hipError_t smiles_read_enqueue(const unsigned char* bytes, unsigned n_bytes, const unsigned* offsets, int n, mnx_read* recs,
+                               const TablesOut& o, unsigned* totals, hipStream_t s) {
+    hipLaunchKernelGGL(smiles_read_kernel<false>, dim3(n), dim3(SR_THREADS), 0, s, bytes, n_bytes, offsets, recs, o);
+    hipLaunchKernelGGL(mol_scan_kernel, dim3(1), dim3(MOL_SCAN_THREADS), 0, s, o, n, totals);
+    hipLaunchKernelGGL(smiles_read_kernel<true>, dim3(n), dim3(SR_THREADS), 0, s, bytes, n_bytes, offsets, recs, o);
     return hipGetLastError();
 }
 

@@ -870,22 +870,34 @@ class Engine:
         dev = tokens.device
         scored = out.get("edge_scores") is not None
         sc = [out["atom_scores"], out["edge_scores"], out["overall_score"]] if scored else [None, None, None]
+        head = [_ptr(tokens), _ptr(lengths), n, T, _ptr(out["atom_idx"]), _ptr(out["n_atoms"]), _ptr(out["edges"]), kmax,
+                _ptr(sc[0]), _ptr(sc[1]), _ptr(sc[2])]
+        return self._sized_tables("mnx_graph_pack", n, caps if caps is not None else tuple(n * g for g in self.PACK_GUESS),
+                                  lambda mols, arenas, totals: self.lib.mnx_graph_pack(self.h, *head, mols, *arenas, totals, _stream()),
+                                  dev, keep_device)
+
+    def _sized_tables(self, fn: str, n: int, caps, call, dev, keep_device: bool) -> dict:
+        """One table writer over n molecules at capacities caps = (atom_cap, bond_cap, text_cap) and at most once more with
+        the sizes `totals` reports: {'mols' [n] MOL_DTYPE, 'atoms' ATOM_DTYPE, 'bonds' BOND_DTYPE, 'text' bytes, 'totals'
+        uint32 [4]}, keep_device: plus 'device' = the four tables as the uint8 device tensors they were written to.
+        call(mols, arenas, totals) makes the library call lib.<fn> for one set of arenas and returns its code: mols and
+        totals are pointers, arenas = [atoms, atom_cap, bonds, bond_cap, text, text_cap] as the three writers take them. call runs
+        once per attempt, so an output of its own that is sized by a capacity (expand_pack's `origin`, by arenas[1]) is allocated
+        inside it; the caller reads the one of the last attempt."""
         mols = torch.empty(n * MOL_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         totals = torch.empty(4, dtype=torch.int32, device=dev)
-        caps = tuple(int(c) for c in caps) if caps is not None else tuple(n * g for g in self.PACK_GUESS)
+        caps = tuple(int(c) for c in caps)
         for attempt in range(2):
             atoms = torch.empty(max(caps[0], 1) * ATOM_DTYPE.itemsize, dtype=torch.uint8, device=dev)
             bonds = torch.empty(max(caps[1], 1) * BOND_DTYPE.itemsize, dtype=torch.uint8, device=dev)
             text = torch.empty(max(caps[2], 1), dtype=torch.uint8, device=dev)
-            self._check(self.lib.mnx_graph_pack(self.h, _ptr(tokens), _ptr(lengths), n, T, _ptr(out["atom_idx"]),
-                                                _ptr(out["n_atoms"]), _ptr(out["edges"]), kmax, _ptr(sc[0]), _ptr(sc[1]),
-                                                _ptr(sc[2]), _ptr(mols), _ptr(atoms), caps[0], _ptr(bonds), caps[1], _ptr(text),
-                                                caps[2], _ptr(totals), _stream()), "mnx_graph_pack")
+            arenas = [_ptr(atoms), caps[0], _ptr(bonds), caps[1], _ptr(text), caps[2]]
+            self._check(call(_ptr(mols), arenas, _ptr(totals)), fn)
             tot = totals.cpu().numpy().view(np.uint32)
             if not tot[3]:
                 break
             if attempt:
-                raise MnxError(f"mnx_graph_pack: capacities {caps} too small after sizing them from totals {tot.tolist()}")
+                raise MnxError(f"{fn}: capacities {caps} too small after sizing them from totals {tot.tolist()}")
             caps = (int(tot[0]), int(tot[1]), int(tot[2]))
         na, nb, nt = int(tot[0]), int(tot[1]), int(tot[2])
         rec = {"mols": mols.cpu().numpy().view(MOL_DTYPE),
@@ -992,33 +1004,16 @@ class Engine:
         dev = torch.device("cuda", self.device)
         n = len(rec["mols"])
         tables, args = self._packed_tables(rec)
-        mols = torch.empty(n * MOL_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        totals = torch.empty(4, dtype=torch.int32, device=dev)
-        if caps is not None:
-            caps = tuple(int(c) for c in caps)
-        else:       # room for a label of about ten atoms per molecule before the repeat
+        if caps is None:        # room for a label of about ten atoms per molecule before the repeat
             caps = (len(rec["atoms"]) + 12 * n, len(rec["bonds"]) + 12 * n, len(rec["text"]) + 16 * n)
-        for attempt in range(2):
-            atoms = torch.empty(max(caps[0], 1) * ATOM_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-            bonds = torch.empty(max(caps[1], 1) * BOND_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-            text = torch.empty(max(caps[2], 1), dtype=torch.uint8, device=dev)
-            origin = torch.empty(max(caps[0], 1), dtype=torch.int16, device=dev)
-            self._check(self.lib.mnx_expand_pack(self.h, *args, _ptr(mols), _ptr(atoms), caps[0], _ptr(bonds), caps[1], _ptr(text),
-                                                 caps[2], _ptr(origin), _ptr(totals), _stream()), "mnx_expand_pack")
-            tot = totals.cpu().numpy().view(np.uint32)
-            if not tot[3]:
-                break
-            if attempt:
-                raise MnxError(f"mnx_expand_pack: capacities {caps} too small after sizing them from totals {tot.tolist()}")
-            caps = (int(tot[0]), int(tot[1]), int(tot[2]))
-        na, nb, nt = int(tot[0]), int(tot[1]), int(tot[2])
-        out = {"mols": mols.cpu().numpy().view(MOL_DTYPE),
-               "atoms": atoms[:na * ATOM_DTYPE.itemsize].cpu().numpy().view(ATOM_DTYPE),
-               "bonds": bonds[:nb * BOND_DTYPE.itemsize].cpu().numpy().view(BOND_DTYPE),
-               "text": text[:nt].cpu().numpy().tobytes(), "totals": tot.copy(),
-               "origin": origin[:na].cpu().numpy().view(np.uint16)}
-        if keep_device:
-            out["device"] = (mols, atoms, bonds, text)
+        origin = []             # per atom: one per attempt, of the attempt's atom capacity
+
+        def call(mols, arenas, totals):
+            origin[:] = [torch.empty(max(arenas[1], 1), dtype=torch.int16, device=dev)]
+            return self.lib.mnx_expand_pack(self.h, *args, mols, *arenas, _ptr(origin[0]), totals, _stream())
+
+        out = self._sized_tables("mnx_expand_pack", n, caps, call, dev, keep_device)
+        out["origin"] = origin[0][:len(out["atoms"])].cpu().numpy().view(np.uint16)
         return out
 
     def smiles_read(self, strings, caps=None, keep_device: bool = False) -> dict:
@@ -1041,34 +1036,14 @@ class Engine:
         arena = b"".join(raw)
         d_bytes = torch.frombuffer(bytearray(arena) or bytearray(8), dtype=torch.uint8).to(dev)
         d_off = torch.from_numpy(offsets.view(np.int32)).to(dev)
-        mols = torch.empty(n * MOL_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        recs = torch.empty(n * READ_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        totals = torch.empty(4, dtype=torch.int32, device=dev)
-        if caps is not None:
-            caps = tuple(int(c) for c in caps)
-        else:       # an atom takes a byte at least, a string has about as many bonds as atoms, and its text is itself
+        recs = torch.empty(n * READ_DTYPE.itemsize, dtype=torch.uint8, device=dev)      # per string: one for both attempts
+        if caps is None:        # an atom takes a byte at least, a string has about as many bonds as atoms, and its text is itself
             caps = (min(len(arena), n * self.PACK_GUESS[0]), min(len(arena), n * self.PACK_GUESS[1]), len(arena))
-        for attempt in range(2):
-            atoms = torch.empty(max(caps[0], 1) * ATOM_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-            bonds = torch.empty(max(caps[1], 1) * BOND_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-            text = torch.empty(max(caps[2], 1), dtype=torch.uint8, device=dev)
-            self._check(self.lib.mnx_smiles_read(self.h, _ptr(d_bytes), len(arena), _ptr(d_off), n, _ptr(mols), _ptr(recs), _ptr(atoms),
-                                                 caps[0], _ptr(bonds), caps[1], _ptr(text), caps[2], _ptr(totals), _stream()),
-                        "mnx_smiles_read")
-            tot = totals.cpu().numpy().view(np.uint32)
-            if not tot[3]:
-                break
-            if attempt:
-                raise MnxError(f"mnx_smiles_read: capacities {caps} too small after sizing them from totals {tot.tolist()}")
-            caps = (int(tot[0]), int(tot[1]), int(tot[2]))
-        na, nb, nt = int(tot[0]), int(tot[1]), int(tot[2])
-        out = {"mols": mols.cpu().numpy().view(MOL_DTYPE),
-               "atoms": atoms[:na * ATOM_DTYPE.itemsize].cpu().numpy().view(ATOM_DTYPE),
-               "bonds": bonds[:nb * BOND_DTYPE.itemsize].cpu().numpy().view(BOND_DTYPE),
-               "text": text[:nt].cpu().numpy().tobytes(), "totals": tot.copy(),
-               "read": recs.cpu().numpy().view(READ_DTYPE)}
-        if keep_device:
-            out["device"] = (mols, atoms, bonds, text)
+        out = self._sized_tables("mnx_smiles_read", n, caps,
+                                 lambda mols, arenas, totals: self.lib.mnx_smiles_read(
+                                     self.h, _ptr(d_bytes), len(arena), _ptr(d_off), n, mols, _ptr(recs), *arenas, totals, _stream()),
+                                 dev, keep_device)
+        out["read"] = recs.cpu().numpy().view(READ_DTYPE)
         return out
 
     def atom_scan(self, tokens: torch.Tensor, lengths: torch.Tensor, kmax: Optional[int] = None):

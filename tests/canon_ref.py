@@ -14,10 +14,9 @@ import ez_ref as E
 import molfile_ref as M
 import smiles_ref as S
 import stereo_ref as T
-from molnextr_amd.engine import SMILES_DTYPE
 
 FLAG_TIE, FLAG_TIE_INDEX = 8192, 16384
-NO_RANK = 0xFFFF
+NO_RANK = S.NO_POSITION          # 0xFFFF: what pack() leaves where a molecule got no ranks
 BOND_CLASS = {1: 0, 5: 0, 6: 0, 2: 1, 3: 2, 4: 3}         # every other `type` is class 4
 
 
@@ -78,41 +77,8 @@ def smiles(symbols, xy, bonds, marks=0, tables=None):
 def pack(mols, atoms, bonds, text, marks=0, tables=None, n_atom_records=None, n_bond_records=None, n_text_bytes=None,
          order_fill=S.NO_POSITION):
     """mnx_smiles_pack_canonical on host arrays, as ez_ref.pack: {'recs', 'order', 'rank', 'sym_class', 'out', 'total'}"""
-    tables = M.name_tables() if tables is None else tables
-    text = bytes(text)
-    n_a = len(atoms) if n_atom_records is None else n_atom_records
-    n_b = len(bonds) if n_bond_records is None else n_bond_records
-    n_t = len(text) if n_text_bytes is None else n_text_bytes
-    recs = np.zeros(len(mols), SMILES_DTYPE)
-    order, rank, sym_class = (np.full(n_a, order_fill, np.uint16) for _ in range(3))
-    chunks, at = [], 0
-    for b, m in enumerate(mols):
-        a0, na, b0, nb, t0, tl = (int(m[k]) for k in ("atom0", "n_atoms", "bond0", "n_bonds", "text0", "smiles_len"))
-        flags = S.FLAG_TRUNCATED if int(m["flags"]) & 1 else 0
-        if na > 999 or nb > 999:
-            flags |= S.FLAG_TOO_LARGE
-        if a0 + na > n_a or b0 + nb > n_b or t0 + tl > n_t:
-            flags |= S.FLAG_BEYOND
-        data, where, n_rings, r, c = None, None, 0, None, None
-        if not flags & 3:
-            A, B = atoms[a0:a0 + na], bonds[b0:b0 + nb]
-            if any(t0 + int(a["sym0"]) + int(a["sym_len"]) > n_t for a in A) or \
-                    any(int(x["i"]) >= na or int(x["j"]) >= na or int(x["i"]) == int(x["j"]) for x in B):
-                flags |= S.FLAG_BEYOND
-            else:
-                syms = [text[t0 + int(a["sym0"]):t0 + int(a["sym0"]) + int(a["sym_len"])] for a in A]
-                data, where, f, n_rings, r, c = smiles(syms, [(int(a["x_bin"]), int(a["y_bin"])) for a in A],
-                                                       [(int(x["i"]), int(x["j"]), int(x["type"]), int(x["rev"])) for x in B], marks, tables)
-                flags |= f
-        end = min(a0 + na, n_a)
-        order[a0:end] = S.NO_POSITION if data is None else where
-        rank[a0:end] = NO_RANK if r is None else r
-        sym_class[a0:end] = NO_RANK if c is None else c
-        data = data or ""
-        recs[b] = (min(at, 0xFFFFFFFF), len(data), flags, n_rings)
-        chunks.append(data.encode("ascii"))
-        at += len(data)
-    return {"recs": recs, "order": order, "rank": rank, "sym_class": sym_class, "out": b"".join(chunks), "total": at}
+    return S.pack_with(lambda syms, xy, B, tb: smiles(syms, xy, B, marks, tb), mols, atoms, bonds, text, tables, n_atom_records,
+                       n_bond_records, n_text_bytes, order_fill, extra=("rank", "sym_class"))
 
 
 def redraw(mol, rng, bins=2048):

@@ -19,7 +19,6 @@ import numpy as np
 import molfile_ref as M
 import smiles_ref as S
 import stereo_ref as T
-from molnextr_amd.engine import SMILES_DTYPE
 
 FLAG_EZ, FLAG_EZ_UNRESOLVED, FLAG_EZ_IMPLIED = 1024, 2048, 4096
 MARK_TETRAHEDRAL, MARK_DOUBLE_BOND = 1, 2
@@ -191,41 +190,8 @@ def smiles(symbols, xy, bonds, marks=MARK_DOUBLE_BOND, tables=None):
 def pack(mols, atoms, bonds, text, marks=MARK_DOUBLE_BOND, tables=None, n_atom_records=None, n_bond_records=None, n_text_bytes=None,
          order_fill=S.NO_POSITION):
     """mnx_smiles_pack_marks on host arrays, as smiles_ref.pack: {'recs', 'order', 'out', 'total'}"""
-    tables = M.name_tables() if tables is None else tables
-    text = bytes(text)
-    n_a = len(atoms) if n_atom_records is None else n_atom_records
-    n_b = len(bonds) if n_bond_records is None else n_bond_records
-    n_t = len(text) if n_text_bytes is None else n_text_bytes
-    recs = np.zeros(len(mols), SMILES_DTYPE)
-    order = np.full(n_a, order_fill, np.uint16)
-    chunks, at = [], 0
-    for b, m in enumerate(mols):
-        a0, na, b0, nb, t0, tl = (int(m[k]) for k in ("atom0", "n_atoms", "bond0", "n_bonds", "text0", "smiles_len"))
-        flags = S.FLAG_TRUNCATED if int(m["flags"]) & 1 else 0
-        if na > 999 or nb > 999:
-            flags |= S.FLAG_TOO_LARGE
-        if a0 + na > n_a or b0 + nb > n_b or t0 + tl > n_t:
-            flags |= S.FLAG_BEYOND
-        data, where, n_rings = None, None, 0
-        if not flags & 3:
-            A, B = atoms[a0:a0 + na], bonds[b0:b0 + nb]
-            if any(t0 + int(a["sym0"]) + int(a["sym_len"]) > n_t for a in A) or \
-                    any(int(x["i"]) >= na or int(x["j"]) >= na or int(x["i"]) == int(x["j"]) for x in B):
-                flags |= S.FLAG_BEYOND
-            else:
-                syms = [text[t0 + int(a["sym0"]):t0 + int(a["sym0"]) + int(a["sym_len"])] for a in A]
-                data, where, f, n_rings, _ = smiles(syms, [(int(a["x_bin"]), int(a["y_bin"])) for a in A],
-                                                    [(int(x["i"]), int(x["j"]), int(x["type"]), int(x["rev"])) for x in B], marks, tables)
-                flags |= f
-        if data is None:
-            order[a0:min(a0 + na, n_a)] = S.NO_POSITION
-            data = ""
-        else:
-            order[a0:a0 + na] = where
-        recs[b] = (min(at, 0xFFFFFFFF), len(data), flags, n_rings)
-        chunks.append(data.encode("ascii"))
-        at += len(data)
-    return {"recs": recs, "order": order, "out": b"".join(chunks), "total": at}
+    return S.pack_with(lambda syms, xy, B, tb: smiles(syms, xy, B, marks, tb)[:4], mols, atoms, bonds, text, tables, n_atom_records,
+                       n_bond_records, n_text_bytes, order_fill)
 
 
 # ---------------------------------------------------------------------------------------------------------------- reader

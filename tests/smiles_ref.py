@@ -122,17 +122,19 @@ def smiles(symbols, bonds, tables=None):
     return text, [pos[a] for a in range(n)], flags, n_rings
 
 
-def pack(mols, atoms, bonds, text, tables=None, n_atom_records=None, n_bond_records=None, n_text_bytes=None, order_fill=NO_POSITION):
-    """mnx_smiles_pack on host arrays: {'recs' SMILES_DTYPE [n], 'order' uint16 [n_atom_records], 'out' bytes, 'total' int}. The
-    n_* default to the sizes of the arrays; smaller ones make the molecules whose records reach beyond them refused (flag bit
-    1). order_fill: what the entries of `order` that the call does not write hold."""
+def pack_with(writer, mols, atoms, bonds, text, tables, n_atom_records, n_bond_records, n_text_bytes, order_fill, extra=()):
+    """The loop of every pack() of the SMILES oracles: which molecules are admitted (the flag bits 0, 1 and 3), their symbols,
+    bins and bonds to writer(symbols, xy, bonds, tables) -> (text or None, written positions or None, flags, n_rings, then one
+    per-atom list or None for every name in `extra`), the records and the bytes behind one another. Returns {'recs', 'order',
+    *extra, 'out', 'total'}; a per-atom array holds NO_POSITION where the writer gave None and order_fill where the call
+    writes nothing."""
     tables = M.name_tables() if tables is None else tables
     text = bytes(text)
     n_a = len(atoms) if n_atom_records is None else n_atom_records
     n_b = len(bonds) if n_bond_records is None else n_bond_records
     n_t = len(text) if n_text_bytes is None else n_text_bytes
     recs = np.zeros(len(mols), SMILES_DTYPE)
-    order = np.full(n_a, order_fill, np.uint16)
+    per_atom = {k: np.full(n_a, order_fill, np.uint16) for k in ("order",) + tuple(extra)}
     chunks, at = [], 0
     for b, m in enumerate(mols):
         a0, na, b0, nb, t0, tl = (int(m[k]) for k in ("atom0", "n_atoms", "bond0", "n_bonds", "text0", "smiles_len"))
@@ -141,7 +143,7 @@ def pack(mols, atoms, bonds, text, tables=None, n_atom_records=None, n_bond_reco
             flags |= FLAG_TOO_LARGE
         if a0 + na > n_a or b0 + nb > n_b or t0 + tl > n_t:
             flags |= FLAG_BEYOND
-        data, where, n_rings = None, None, 0
+        written = (None, None, 0, 0) + (None,) * len(extra)
         if not flags & 3:
             A, B = atoms[a0:a0 + na], bonds[b0:b0 + nb]
             if any(t0 + int(a["sym0"]) + int(a["sym_len"]) > n_t for a in A) or \
@@ -149,17 +151,25 @@ def pack(mols, atoms, bonds, text, tables=None, n_atom_records=None, n_bond_reco
                 flags |= FLAG_BEYOND
             else:
                 syms = [text[t0 + int(a["sym0"]):t0 + int(a["sym0"]) + int(a["sym_len"])] for a in A]
-                data, where, f, n_rings = smiles(syms, [(int(x["i"]), int(x["j"]), int(x["type"]), int(x["rev"])) for x in B], tables)
-                flags |= f
-        if data is None:
-            order[a0:min(a0 + na, n_a)] = NO_POSITION
-            data = ""
-        else:
-            order[a0:a0 + na] = where
-        recs[b] = (min(at, 0xFFFFFFFF), len(data), flags, n_rings)
+                written = writer(syms, [(int(a["x_bin"]), int(a["y_bin"])) for a in A],
+                                 [(int(x["i"]), int(x["j"]), int(x["type"]), int(x["rev"])) for x in B], tables)
+                flags |= written[2]
+        data = written[0]
+        for arr, v in zip(per_atom.values(), (None if data is None else written[1],) + tuple(written[4:])):
+            arr[a0:min(a0 + na, n_a)] = NO_POSITION if v is None else v
+        data = data or ""
+        recs[b] = (min(at, 0xFFFFFFFF), len(data), flags, written[3])
         chunks.append(data.encode("ascii"))
         at += len(data)
-    return {"recs": recs, "order": order, "out": b"".join(chunks), "total": at}
+    return {"recs": recs, **per_atom, "out": b"".join(chunks), "total": at}
+
+
+def pack(mols, atoms, bonds, text, tables=None, n_atom_records=None, n_bond_records=None, n_text_bytes=None, order_fill=NO_POSITION):
+    """mnx_smiles_pack on host arrays: {'recs' SMILES_DTYPE [n], 'order' uint16 [n_atom_records], 'out' bytes, 'total' int}. The
+    n_* default to the sizes of the arrays; smaller ones make the molecules whose records reach beyond them refused (flag bit
+    1). order_fill: what the entries of `order` that the call does not write hold."""
+    return pack_with(lambda syms, xy, B, tb: smiles(syms, B, tb), mols, atoms, bonds, text, tables, n_atom_records, n_bond_records,
+                     n_text_bytes, order_fill)
 
 
 # ---------------------------------------------------------------------------------------------------------------- reader
