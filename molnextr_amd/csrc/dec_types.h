@@ -220,10 +220,13 @@ hipError_t molfile_pack_enqueue(const SymbolTables* st_dev, const PackedTables& 
 // null) (mnx_smiles_pack; marks, MNX_SMILES_MARK_*: with the '@' / '@@' of mnx_smiles_pack_stereo and the '/' '\\' of
 // mnx_smiles_pack_marks): count, scan and fill, three launches on s.
 // rank set (null otherwise): the same on canonical atom ranks (mnx_smiles_pack_canonical) — one launch in front leaves the ranks
-// in `rank` and the symmetry classes in `sym_class` (may be null), then count, scan and fill on those ranks; four launches on s
+// in `rank` and the symmetry classes in `sym_class` (may be null), then count, scan and fill on those ranks; four launches on s.
+// symmetric (rank and sym_class set): the same four launches with the symmetry rule of mnx_smiles_pack_symmetric for the marks,
+// every atom's MNX_ATOM_* bits in `atom_marks` (may be null)
 hipError_t smiles_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, unsigned marks, mnx_smiles* recs,
                                unsigned short* order, unsigned short* rank, unsigned short* sym_class, char* out,
-                               unsigned out_cap, unsigned* totals, hipStream_t s);
+                               unsigned out_cap, unsigned* totals, hipStream_t s, bool symmetric = false,
+                               unsigned char* atom_marks = nullptr);
 // the fragment library (mnx_set_fragments) as the device holds it: ONE allocation — the table of fragment indices parallel to
 // SymbolTables' names, the fragment records, then their atoms, bonds and symbol bytes. The host has validated all of it and has
 // sorted every fragment's bonds by (i, j), so the bonds from atom 0 (the attachment atom) are the first n_bonds0 of a fragment.

@@ -1526,12 +1526,13 @@ int mnx_smiles_read(mnx_engine* h, const char* bytes, uint32_t n_bytes, const ui
     return MNX_OK;
 }
 
-// mnx_smiles_pack, mnx_smiles_pack_stereo, mnx_smiles_pack_marks and mnx_smiles_pack_canonical: one check, one enqueue path, a
-// pair of kernels per set of marks; canonical: on the ranks that one more kernel in front of them leaves in `rank`
+// mnx_smiles_pack, mnx_smiles_pack_stereo, mnx_smiles_pack_marks, mnx_smiles_pack_canonical and mnx_smiles_pack_symmetric: one
+// check, one enqueue path, a pair of kernels per set of marks; canonical: on the ranks that one more kernel in front of them
+// leaves in `rank`; symmetric: canonical with the symmetry rule, which needs `sym_class` too
 static int smiles_pack(mnx_engine* h, const char* fn, uint32_t marks, const PackedTables& t, mnx_smiles* recs, uint16_t* order,
                        char* out, uint32_t out_cap, uint32_t* totals, void* stream, bool canonical = false, uint16_t* rank = nullptr,
-                       uint16_t* sym_class = nullptr) {
-    if (int rc = check_packed_tables(h, fn, t, !recs || !totals || (!out && out_cap) || (canonical && !rank),
+                       uint16_t* sym_class = nullptr, bool symmetric = false, uint8_t* atom_marks = nullptr) {
+    if (int rc = check_packed_tables(h, fn, t, !recs || !totals || (!out && out_cap) || (canonical && !rank) || (symmetric && !sym_class),
                                      (((uintptr_t)recs | (uintptr_t)totals) & 3) != 0 ||
                                          (((uintptr_t)order | (uintptr_t)rank | (uintptr_t)sym_class) & 1) != 0,
                                      canonical ? "recs and totals 4-byte, order, rank and sym_class 2-byte" : "recs and totals 4-byte, order 2-byte"))
@@ -1541,7 +1542,8 @@ static int smiles_pack(mnx_engine* h, const char* fn, uint32_t marks, const Pack
         return MNX_ERR_INVALID_ARG;
     }
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, smiles_pack_enqueue(h->st_dev, t, marks, recs, order, rank, sym_class, out, out_cap, totals, (hipStream_t)stream));
+    HIPCHK(h, smiles_pack_enqueue(h->st_dev, t, marks, recs, order, rank, sym_class, out, out_cap, totals, (hipStream_t)stream, symmetric,
+                                  atom_marks));
     return MNX_OK;
 }
 
@@ -1573,6 +1575,15 @@ int mnx_smiles_pack_canonical(mnx_engine* h, const mnx_mol* mols, int32_t n, con
                               uint32_t out_cap, uint32_t* totals, uint32_t marks, void* stream) {
     const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
     return smiles_pack(h, "mnx_smiles_pack_canonical", marks, t, recs, order, out, out_cap, totals, stream, true, rank, sym_class);
+}
+
+int mnx_smiles_pack_symmetric(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
+                              const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes,
+                              mnx_smiles* recs, uint16_t* order, uint16_t* rank, uint16_t* sym_class, uint8_t* atom_marks,
+                              char* out, uint32_t out_cap, uint32_t* totals, uint32_t marks, void* stream) {
+    const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
+    return smiles_pack(h, "mnx_smiles_pack_symmetric", marks, t, recs, order, out, out_cap, totals, stream, true, rank, sym_class,
+                       true, atom_marks);
 }
 
 int mnx_atom_scan(mnx_engine* h, const int32_t* tokens, const int32_t* lengths, int32_t n, int32_t T, int32_t kmax,

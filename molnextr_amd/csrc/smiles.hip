@@ -6,6 +6,8 @@
 // the stage EZ behind that one). MARKS selects the stages; an instantiation holds none of the code of a stage it does not run.
 // mnx_smiles_pack_canonical puts one kernel in front, canon_rank_kernel: canonical atom ranks by partition refinement, one
 // workgroup per molecule; count and fill (CANON) then walk by those ranks instead of the atom indices.
+// mnx_smiles_pack_symmetric is that call with one more switch, SYM: a candidate of STEREO or EZ with two neighbours of one symmetry
+// class on bonds off every cycle writes no mark.
 //   count  one workgroup per molecule: the walk and the length of its string -> recs[b].len / flags / n_rings
 //   scan   exclusive scan of the lengths over the molecules -> recs[b].text0, totals
 //   fill   one workgroup per molecule: the walk again, the bytes behind text0 and the atoms' positions in `order`
@@ -108,7 +110,8 @@ __device__ __forceinline__ void put_atom(unsigned w, unsigned el, unsigned mark,
 //   child_dir (done_child) bit 0: the bond parent -> this atom takes a symbol from the candidate the parent is an end of, bit 1:
 //                          this atom lies on the left of that candidate's axis; in the end the symbol itself, 0 for none
 //   low, then flip (cur)   the lowest written position a ring bond reaches from the atom's subtree; then a's flip
-constexpr unsigned ROLE_B = 1, ROLE_A = 2, ROLE_F0 = 4, ROLE_UNRESOLVED = 8;
+//   SYM adds ROLE_SYM at both ends of a candidate dropped for symmetry, and bit 2 of an atom's mark in stk (MNX_ATOM_MARK_SYM)
+constexpr unsigned ROLE_B = 1, ROLE_A = 2, ROLE_F0 = 4, ROLE_UNRESOLVED = 8, ROLE_SYM = 16;
 
 // ---- canonical ranks (mnx_smiles_pack_canonical; the rule: molnextr_hip.h) ----
 constexpr unsigned CANON_BITS = MNX_SMILES_CANON_TIE | MNX_SMILES_CANON_TIE_INDEX;
@@ -306,10 +309,16 @@ __global__ __launch_bounds__(SM_THREADS) void canon_rank_kernel(
 
 // CANON (mnx_smiles_pack_canonical): the walk runs on the ranks that canon_rank_kernel left in `rank` instead of on the atom
 // indices — the first sort of the lists and the order of the roots; every later stage works on written positions as it is.
-template <bool FILL, unsigned MARKS, bool CANON = false>
+// SYM (mnx_smiles_pack_symmetric, CANON only): a candidate of either stage with an equal pair (two neighbours of one class in
+// `sym_class`, read from global: a handful of reads per candidate, so the classes take no LDS; both on bonds off every cycle)
+// writes no mark. The low[] pass of EZ then runs in front of STEREO, for every set of marks but 0. fill leaves every atom's
+// MNX_ATOM_* bits in `atom_marks` (may be null), one owner thread per byte.
+template <bool FILL, unsigned MARKS, bool CANON = false, bool SYM = false>
 __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
         const PackedTables t, const SymbolTables* __restrict__ st, mnx_smiles* __restrict__ recs,
-        unsigned short* __restrict__ order, char* __restrict__ out, unsigned out_cap, const unsigned short* __restrict__ rank) {
+        unsigned short* __restrict__ order, char* __restrict__ out, unsigned out_cap, const unsigned short* __restrict__ rank,
+        const unsigned short* __restrict__ sym_class, unsigned char* __restrict__ atom_marks) {
+    static_assert(CANON || !SYM, "the symmetry rule reads the classes of the rank kernel");
     __shared__ unsigned short rnk[CANON ? SM_MAX : 1], inv[CANON ? SM_MAX : 1];     // atom -> rank, rank -> atom
     __shared__ unsigned info[SM_MAX], elem[SM_MAX];
     __shared__ unsigned off[SM_MAX + 1], cnt[SM_MAX];     // an atom's list is [off[a], off[a + 1]); cnt: degrees, then fill cursors
@@ -334,15 +343,19 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
         }
     };
     unsigned text0 = 0;
+    bool sym_on = SYM;                                    // SYM: the rule is off for a molecule that holds a pseudo-atom
     if (FILL) {
         const mnx_smiles r = recs[b];
         if (r.len == 0) {                                 // no string (the same for every thread): its atoms get no position
-            if (order && (r.flags & REFUSED))
-                for (unsigned a = tid; a < m.n_atoms && (unsigned long long)m.atom0 + a < t.n_atom_records; a += SM_THREADS)
-                    order[m.atom0 + a] = (unsigned short)NONE;
+            if ((order || (SYM && atom_marks)) && (r.flags & REFUSED))
+                for (unsigned a = tid; a < m.n_atoms && (unsigned long long)m.atom0 + a < t.n_atom_records; a += SM_THREADS) {
+                    if (order) order[m.atom0 + a] = (unsigned short)NONE;
+                    if (SYM && atom_marks) atom_marks[m.atom0 + a] = 0xFFu;
+                }
             return;
         }
         text0 = r.text0;
+        if (SYM) sym_on = !(r.flags & PT_PSEUDO_ATOM);
     } else if (mol.flags & (PT_TOO_LARGE | PT_BEYOND_TABLES)) {
         record(0, mol.flags, 0);
         return;
@@ -382,6 +395,7 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
         pseudo = __syncthreads_or(pseudo);
         wedge = __syncthreads_or(wedge);
         any = __syncthreads_or(any);
+        if (SYM) sym_on = !pseudo;
     }
 
     // ---- neighbour lists: offsets from a scan of the degrees, entries as the bonds come, then each list in ascending order ----
@@ -529,15 +543,52 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
         return;
     }
 
+    // ---- SYM: the lowest written position a ring bond reaches from every atom's subtree, in front of both stages (EZ's own
+    //      pass, which `cur` holds until EZ turns it into the flips). A tree bond parent -> x is off every cycle iff
+    //      low[x] >= pos[x]; a ring bond never is. ----
+    if (SYM && MARKS != 0u) {
+        for (int a = tid; a < na; a += SM_THREADS) {
+            unsigned l = NONE;
+            for (unsigned s = off[a]; s < off[a + 1]; ++s)
+                if (!(raw[s] & SLOT_TREE)) l = min(l, (unsigned)pos[slot_nbr(raw[s])]);
+            cur[a] = (unsigned short)l;
+        }
+        __syncthreads();
+        if (tid == 0)
+            for (int p = na - 1; p > 0; --p) {
+                const unsigned a = at[p], par = parent[a];
+                if (par != NONE && cur[a] < cur[par]) cur[par] = cur[a];
+            }
+        __syncthreads();
+    }
+    // an equal pair at u: two neighbours other than `skip` of one class, both on bonds off every cycle
+    auto equal_pair = [&](unsigned u, unsigned skip) {
+        auto free_nbr = [&](unsigned e) {                 // the neighbour of a list entry of u, NONE where the bond is on a cycle
+            const unsigned n = slot_nbr(e), x = pos[n] < pos[u] ? u : n;
+            return (e & SLOT_TREE) && n != skip && cur[x] >= pos[x] ? n : NONE;
+        };
+        for (unsigned s = off[u]; s + 1 < off[u + 1]; ++s) {
+            const unsigned n1 = free_nbr(raw[s]);
+            if (n1 == NONE) continue;
+            const unsigned c1 = sym_class[m.atom0 + n1];
+            for (unsigned q = s + 1; q < off[u + 1]; ++q) {
+                const unsigned n2 = free_nbr(raw[q]);
+                if (n2 != NONE && sym_class[m.atom0 + n2] == c1) return true;
+            }
+        }
+        return false;
+    };
+    auto mark_of = [&](unsigned a) -> unsigned { return SYM ? stk[a] & 3u : stk[a]; };
+
     // ---- STEREO: every marked carbon that a wedge begins at, in parallel over the atoms (the rule: molnextr_hip.h). An atom's
     //      list stands in ascending written position, so the string's neighbour order is: the parent (group 0), the ring items
     //      in list order (group 1), the children in list order (group 2). The determinant is taken over the list as it stands
     //      and flips with the parity of the permutation into that order: it is alternating in the neighbours. ----
-    int marked = 0, unresolved = 0, dropped = 0;
+    int marked = 0, unresolved = 0, dropped = 0, sym_dropped = 0;
     if (STEREO) {
         for (int a = tid; a < na; a += SM_THREADS) {
             const unsigned w = info[a], lo = off[a], hi = off[a + 1], p = pos[a];
-            unsigned mark = 0;
+            unsigned mark = 0, sym = 0;
             if (w & 8u) {
                 unsigned seen = 0, other = 0;
                 for (unsigned s = lo; s < hi; ++s) {
@@ -545,7 +596,9 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
                     other |= slot_cls(raw[s]) != B_SINGLE;
                 }
                 const unsigned deg = hi - lo;
-                if (seen && !other && info_cls(w) == CLS_ATOM && deg + (unsigned)info_h(w) == 4u) {
+                const bool candidate = seen && !other && info_cls(w) == CLS_ATOM && deg + (unsigned)info_h(w) == 4u;
+                if (SYM && sym_on && candidate) sym = equal_pair((unsigned)a, NONE);      // symmetry first: no determinant then
+                if (candidate && !sym) {
                     const unsigned e0 = raw[lo], e1 = raw[lo + 1], e2 = raw[lo + 2], e3 = deg == 4u ? raw[lo + 3] : e2;
                     auto group = [&](unsigned e) { return !(e & SLOT_TREE) ? 1 : pos[slot_nbr(e)] < p ? 0 : 2; };
                     const long long cx = mol.A[a].x_bin, cy = mol.A[a].y_bin;
@@ -567,10 +620,11 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
                     if (flips & 1) d = -d;
                     mark = d < 0 ? 1u : d > 0 ? 2u : 0u;
                 }
-                unresolved |= seen && !mark;
+                unresolved |= seen && !mark && !sym;
             }
             marked |= mark != 0;
-            stk[a] = (unsigned short)mark;
+            sym_dropped |= (int)sym;
+            stk[a] = (unsigned short)(mark | sym << 2);
         }
         if (FILL) __syncthreads();
         else {
@@ -578,7 +632,7 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
             unresolved = __syncthreads_or(unresolved);
             for (int k = tid; k < nb; k += SM_THREADS) {  // a wedge neither end of which received a mark
                 const unsigned ty = type_of(k, B[k].i, B[k].j);
-                dropped |= (ty == 5 || ty == 6) && !stk[B[k].i] && !stk[B[k].j];
+                dropped |= (ty == 5 || ty == 6) && !mark_of(B[k].i) && !mark_of(B[k].j);
             }
             dropped = __syncthreads_or(dropped);
         }
@@ -593,20 +647,24 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
         unsigned short *low = cur, *flip = cur, *child_dir = done_child, *role = done_last;
         const mnx_atom* A = mol.A;
         for (int a = tid; a < na; a += SM_THREADS) {
-            unsigned l = NONE;
-            for (unsigned s = off[a]; s < off[a + 1]; ++s)
-                if (!(raw[s] & SLOT_TREE)) l = min(l, (unsigned)pos[slot_nbr(raw[s])]);
-            low[a] = (unsigned short)l;
+            if (!SYM) {                                   // (SYM: low stands since the pass in front of STEREO)
+                unsigned l = NONE;
+                for (unsigned s = off[a]; s < off[a + 1]; ++s)
+                    if (!(raw[s] & SLOT_TREE)) l = min(l, (unsigned)pos[slot_nbr(raw[s])]);
+                low[a] = (unsigned short)l;
+            }
             child_dir[a] = 0;
             role[a] = 0;
         }
         __syncthreads();
-        if (tid == 0)                                     // minimised up the tree: children are written behind their parent
-            for (int p = na - 1; p > 0; --p) {
-                const unsigned a = at[p], par = parent[a];
-                if (par != NONE && low[a] < low[par]) low[par] = low[a];
-            }
-        __syncthreads();
+        if (!SYM) {
+            if (tid == 0)                                 // minimised up the tree: children are written behind their parent
+                for (int p = na - 1; p > 0; --p) {
+                    const unsigned a = at[p], par = parent[a];
+                    if (par != NONE && low[a] < low[par]) low[par] = low[a];
+                }
+            __syncthreads();
+        }
         for (int c = tid; c < na; c += SM_THREADS) {
             const unsigned a = parent[c];
             if (a == NONE || low[c] < pos[c]) continue;
@@ -633,6 +691,10 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
                 }
             }
             if (!candidate) continue;
+            if (SYM && sym_on && (equal_pair(a, (unsigned)c) || equal_pair((unsigned)c, a))) {    // no symbols, no part in the flips
+                role[c] = role[a] = (unsigned short)ROLE_SYM;
+                continue;
+            }
             if (!resolved) { role[c] = (unsigned short)ROLE_UNRESOLVED; continue; }
             unsigned f0 = 2;                              // the flip that makes the first directed bond of the list '/'
             for (int end = 0; end < 2; ++end) {
@@ -675,6 +737,7 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
             child_dir[x] = (unsigned short)sym;
             directed |= sym != 0;
             ez_unresolved |= (r & ROLE_UNRESOLVED) != 0;
+            if (SYM) sym_dropped |= (r & ROLE_SYM) != 0;
         }
         if (FILL) __syncthreads();
         else {
@@ -689,7 +752,8 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
             for (int k = tid; k < nb; k += SM_THREADS) {  // a double bond without marks of its own between two directed bonds
                 const unsigned i = B[k].i, j = B[k].j;
                 if (type_of(k, i, j) != 2) continue;
-                const bool mine = (parent[j] == i && (role[j] & ROLE_B)) || (parent[i] == j && (role[i] & ROLE_B));
+                constexpr unsigned OWN = ROLE_B | (SYM ? ROLE_SYM : 0u);   // (a double bond into an end of a symmetric candidate is it)
+                const bool mine = (parent[j] == i && (role[j] & OWN)) || (parent[i] == j && (role[i] & OWN));
                 implied |= !mine && has_directed(i) && has_directed(j);
             }
             implied = __syncthreads_or(implied);
@@ -714,7 +778,7 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
                 }
             }
         }
-        put_atom(w, elem[a], STEREO ? stk[a] : 0u, put);
+        put_atom(w, elem[a], STEREO ? mark_of(a) : 0u, put);
         for (unsigned s = off[a]; s < off[a + 1]; ++s) {
             const unsigned e = raw[s], n = slot_nbr(e), r = rnum[s];
             if (e & SLOT_TREE) continue;
@@ -739,12 +803,14 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
     }
     unsigned at_byte = block_scan_excl<SM_THREADS>(sum, scan, &total);
     if (!FILL) {
+        if (SYM && MARKS != 0u) sym_dropped = __syncthreads_or(sym_dropped);
+        const unsigned symmetric = SYM && sym_dropped ? MNX_SMILES_SYM_DROPPED : 0u;
         const unsigned stereo = STEREO ? (dropped ? MNX_SMILES_WEDGES_DROPPED : 0u) | (marked ? MNX_SMILES_STEREO : 0u) |
                                              (unresolved ? MNX_SMILES_STEREO_UNRESOLVED : 0u)
                                        : wedge ? MNX_SMILES_WEDGES_DROPPED : 0u;
         const unsigned ez = (directed ? MNX_SMILES_EZ : 0u) | (ez_unresolved ? MNX_SMILES_EZ_UNRESOLVED : 0u) |
                             (implied ? MNX_SMILES_EZ_IMPLIED : 0u);
-        record(total, base_flags | (pseudo ? PT_PSEUDO_ATOM : 0u) | stereo | ez | (any ? MNX_SMILES_UNKNOWN_BOND : 0u), n_rings);
+        record(total, base_flags | (pseudo ? PT_PSEUDO_ATOM : 0u) | stereo | ez | symmetric | (any ? MNX_SMILES_UNKNOWN_BOND : 0u), n_rings);
         return;
     }
 #pragma unroll
@@ -759,27 +825,35 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
     }
     if (order)
         for (int a = tid; a < na; a += SM_THREADS) order[m.atom0 + a] = pos[a];
+    if (SYM && atom_marks)                                // MNX_ATOM_MARK_CW / _CCW / _SYM are the bits of stk
+        for (int a = tid; a < na; a += SM_THREADS) {
+            const unsigned r = EZ ? done_last[a] : 0u;
+            atom_marks[m.atom0 + a] = (unsigned char)((STEREO ? stk[a] & 7u : 0u) | (r & (ROLE_A | ROLE_B) ? MNX_ATOM_EZ : 0u) |
+                                                      (r & ROLE_SYM ? MNX_ATOM_EZ_SYM : 0u));
+        }
 }
 
 // the kernel of a set of marks
-template <bool FILL, bool CANON>
+template <bool FILL, bool CANON, bool SYM = false>
 auto smiles_kernel_for(unsigned marks) {
-    return marks == 3u ? smiles_kernel<FILL, 3u, CANON> : marks == 2u ? smiles_kernel<FILL, 2u, CANON>
-         : marks == 1u ? smiles_kernel<FILL, 1u, CANON> : smiles_kernel<FILL, 0u, CANON>;
+    return marks == 3u ? smiles_kernel<FILL, 3u, CANON, SYM> : marks == 2u ? smiles_kernel<FILL, 2u, CANON, SYM>
+         : marks == 1u ? smiles_kernel<FILL, 1u, CANON, SYM> : smiles_kernel<FILL, 0u, CANON, SYM>;
 }
 
 }  // namespace
 
 hipError_t smiles_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, unsigned marks, mnx_smiles* recs,
                                unsigned short* order, unsigned short* rank, unsigned short* sym_class, char* out,
-                               unsigned out_cap, unsigned* totals, hipStream_t s) {
+                               unsigned out_cap, unsigned* totals, hipStream_t s, bool symmetric, unsigned char* atom_marks) {
     const bool canon = rank != nullptr;
-    const auto count = canon ? smiles_kernel_for<false, true>(marks) : smiles_kernel_for<false, false>(marks);
-    const auto fill = canon ? smiles_kernel_for<true, true>(marks) : smiles_kernel_for<true, false>(marks);
+    const auto count = symmetric ? smiles_kernel_for<false, true, true>(marks)
+                     : canon ? smiles_kernel_for<false, true>(marks) : smiles_kernel_for<false, false>(marks);
+    const auto fill = symmetric ? smiles_kernel_for<true, true, true>(marks)
+                    : canon ? smiles_kernel_for<true, true>(marks) : smiles_kernel_for<true, false>(marks);
     if (canon) hipLaunchKernelGGL(canon_rank_kernel, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, rank, sym_class);
-    hipLaunchKernelGGL(count, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, order, out, out_cap, rank);
+    hipLaunchKernelGGL(count, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, order, out, out_cap, rank, sym_class, atom_marks);
     hipLaunchKernelGGL(text_scan_kernel<mnx_smiles>, dim3(1), dim3(TEXT_SCAN_THREADS), 0, s, recs, t.n, out_cap, totals);
-    hipLaunchKernelGGL(fill, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, order, out, out_cap, rank);
+    hipLaunchKernelGGL(fill, dim3(t.n), dim3(SM_THREADS), 0, s, t, st_dev, recs, order, out, out_cap, rank, sym_class, atom_marks);
     return hipGetLastError();
 }
 

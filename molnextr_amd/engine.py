@@ -28,7 +28,7 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
            "mnx_encode_gray8", "mnx_predict_gray8", "mnx_decode_guided", "mnx_predict_guided", "mnx_patch_embed",
            "mnx_layernorm16", "mnx_merge_ln16", "mnx_cast16", "mnx_sgemm_tn", "mnx_set_vocab_text", "mnx_graph_pack",
            "mnx_set_symbol_tables", "mnx_molfile_pack", "mnx_smiles_pack", "mnx_smiles_pack_stereo",
-           "mnx_smiles_pack_marks", "mnx_smiles_pack_canonical", "mnx_set_fragments", "mnx_expand_pack", "mnx_smiles_read")
+           "mnx_smiles_pack_marks", "mnx_smiles_pack_canonical", "mnx_smiles_pack_symmetric", "mnx_set_fragments", "mnx_expand_pack", "mnx_smiles_read")
 
 # Encoder operand modes (include/molnextr_hip.h MNX_DTYPE_*). "fp16x3" — split fp16 operands, three MFMA terms per
 # product, fp32-class results — is the default: it is the fastest mode whose results stay a factor of four inside north_star's
@@ -136,6 +136,11 @@ SMILES_MARK_TETRAHEDRAL, SMILES_MARK_DOUBLE_BOND = 1, 2     # the `marks` of mnx
 # mnx_smiles_pack_canonical only: a tie between atoms of one rank was broken by the drawing; in one of them the atom index alone
 # decided (two tied atoms on one bin): only then can the bytes depend on the numbering of the drawing
 SMILES_CANON_TIE, SMILES_CANON_TIE_INDEX = 8192, 16384
+# mnx_smiles_pack_symmetric only: a candidate centre or double bond wrote no mark because two of its substituents share a symmetry
+# class; the per-atom bits of its `atom_marks` (ATOM_MARKS_NONE for every atom of a molecule that got no string)
+SMILES_SYM_DROPPED = 32768
+ATOM_MARK_CW, ATOM_MARK_CCW, ATOM_MARK_SYM, ATOM_EZ, ATOM_EZ_SYM = 1, 2, 4, 8, 16
+ATOM_MARKS_NONE = 0xFF
 SMILES_REFUSED = SMILES_TOO_LARGE | SMILES_BEYOND_TABLES | SMILES_DUPLICATE_BOND | SMILES_RING_NUMBERS    # no SMILES: len 0
 SMILES_NO_POSITION = 0xFFFF             # `order` of an atom whose molecule got no SMILES
 # mnx_read, one string of mnx_smiles_read (16 bytes), and its flags (MNX_READ_*): a rule of the grammar breaks at err_pos; more
@@ -277,6 +282,8 @@ def load_library():
     lib.mnx_smiles_pack_marks.argtypes = lib.mnx_smiles_pack.argtypes[:-1] + [C.c_uint32, vp]
     lib.mnx_smiles_pack_canonical.restype = C.c_int
     lib.mnx_smiles_pack_canonical.argtypes = lib.mnx_smiles_pack.argtypes[:11] + [vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp]
+    lib.mnx_smiles_pack_symmetric.restype = C.c_int
+    lib.mnx_smiles_pack_symmetric.argtypes = lib.mnx_smiles_pack.argtypes[:11] + [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp]
     lib.mnx_set_fragments.restype = C.c_int
     lib.mnx_set_fragments.argtypes = [vp, vp, i32, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, i32]
     lib.mnx_expand_pack.restype = C.c_int
@@ -960,7 +967,7 @@ class Engine:
     SMILES_GUESS = 256        # first capacity of smiles_pack per molecule (a drug-like SMILES is well under 200 bytes)
 
     def smiles_pack(self, rec: dict, cap: Optional[int] = None, stereo: bool = False, double_bonds: bool = False,
-                    canonical: bool = False):
+                    canonical: bool = False, symmetry: bool = False):
         """graph_pack's records -> (recs [n] SMILES_DTYPE, order uint16 [atoms], bytes): the graph SMILES of molecule b is
         bytes[recs[b]['text0'] : +recs[b]['len']] (mnx_smiles_pack: valid, not canonical, no stereo, pseudo-atoms as '*'; len 0
         and a flag of SMILES_REFUSED for a molecule that gets none), order[atom0 + k] the position of its atom k in that
@@ -974,7 +981,13 @@ class Engine:
         atom ranks, with the marks that stereo and double_bonds select; returns (recs, order, bytes, rank uint16 [atoms],
         sym_class uint16 [atoms]): the bytes do not depend on the numbering of a drawing's atoms (flags with SMILES_CANON_TIE /
         SMILES_CANON_TIE_INDEX; SMILES_NO_POSITION in rank and sym_class where the molecule was not read). This project's own
-        ranking, NOT RDKit's canonical SMILES; the known limit stands in the header."""
+        ranking, NOT RDKit's canonical SMILES; the known limit stands in the header. symmetry (canonical only, else ValueError):
+        mnx_smiles_pack_symmetric — a candidate centre or double bond with two substituents of one symmetry class, both on bonds
+        off every cycle, writes no mark (flags with SMILES_SYM_DROPPED; off for a molecule with a pseudo-atom: expand first);
+        returns a sixth value, atom_marks uint8 [atoms]: the ATOM_* bits per atom, ATOM_MARKS_NONE where `order` holds
+        SMILES_NO_POSITION. The ranks ignore stereo and a pair on ring bonds is never dropped: the limits stand in the header."""
+        if symmetry and not canonical:
+            raise ValueError("smiles_pack: symmetry=True needs canonical=True")
         dev = torch.device("cuda", self.device)
         n, na = len(rec["mols"]), len(rec["atoms"])
         tables, args = self._packed_tables(rec)
@@ -983,6 +996,14 @@ class Engine:
         if canonical:
             rank, sym_class = torch.full_like(order, -1), torch.full_like(order, -1)
             marks = (SMILES_MARK_TETRAHEDRAL if stereo else 0) | (SMILES_MARK_DOUBLE_BOND if double_bonds else 0)
+            if symmetry:
+                atom_marks = torch.zeros(max(na, 1), dtype=torch.uint8, device=dev)
+                data = self._sized_text("mnx_smiles_pack_symmetric",
+                                        args + [_ptr(recs), _ptr(order), _ptr(rank), _ptr(sym_class), _ptr(atom_marks)],
+                                        int(cap) if cap is not None else n * self.SMILES_GUESS, (marks,))
+                return (recs.cpu().numpy().view(SMILES_DTYPE), order[:na].cpu().numpy().view(np.uint16), data,
+                        rank[:na].cpu().numpy().view(np.uint16), sym_class[:na].cpu().numpy().view(np.uint16),
+                        atom_marks[:na].cpu().numpy())
             data = self._sized_text("mnx_smiles_pack_canonical", args + [_ptr(recs), _ptr(order), _ptr(rank), _ptr(sym_class)],
                                     int(cap) if cap is not None else n * self.SMILES_GUESS, (marks,))
             return (recs.cpu().numpy().view(SMILES_DTYPE), order[:na].cpu().numpy().view(np.uint16), data,

@@ -143,7 +143,7 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
                      max_len: Optional[int] = None, beam_size: int = 1, compute_confidence: bool = False,
                      labels=None, free_run=False, packed: bool = False, molfile: bool = False,
                      molfile_scale=None, smiles: bool = False, stereo: bool = False, double_bonds: bool = False,
-                     canonical: bool = False, expand: bool = False) -> List[dict]:
+                     canonical: bool = False, expand: bool = False, symmetry: bool = False) -> List[dict]:
     """Encoder + Decoder.decode for MANY images through the engine's continuous-batching path (mnx_predict):
     same per-image dicts as `decode_batch`, identical results (the on-device atom scan equals
     sequence_to_smiles' indices), much higher throughput. compute_confidence=True: mnx_predict_confidence, the same
@@ -174,6 +174,12 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
     and 'symmetry_class', a list per atom (None for a molecule that was not ranked). This library's own ranking: it is NOT
     RDKit's canonical SMILES, no toolkit has parsed it, and the header states the known limit (a few graphs whose string still
     depends on the drawing).
+    symmetry (smiles and canonical only, else ValueError): mnx_smiles_pack_symmetric instead — a candidate centre or double bond
+    with two substituents of one symmetry class, both on bonds off every cycle, writes no mark, so an isopropyl carbon drawn with
+    a wedge and its mirror image get one string. Every dict gains 'stereo_atoms', the ATOM_* bits of engine.py per atom (per
+    EXPANDED atom with expand), None for a molecule that got no string. The rule is off for a molecule with a pseudo-atom
+    (expand first), the ranks ignore stereo (a pseudo-asymmetric centre is dropped), a pair on ring bonds is never dropped, and
+    no toolkit has parsed the result: the limits stand in the header.
     expand (packed only): abbreviation labels that have a fragment in vocab/fragments.json ('Ph', 'OMe', 'Boc', ...) are replaced
     by the fragment's atoms and bonds on the device before anything is written (mnx_expand_pack; the rule: the header), so
     'molfile' and 'graph_smiles' describe the expanded molecule instead of writing 'R' / '*' for the label. Every dict gains
@@ -195,6 +201,8 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
         raise ValueError("double_bonds=True needs smiles=True: the marks are written into the graph SMILES")
     if canonical and not smiles:
         raise ValueError("canonical=True needs smiles=True: the ranks order the graph SMILES")
+    if symmetry and not (smiles and canonical):
+        raise ValueError("symmetry=True needs smiles=True and canonical=True: the rule reads the symmetry classes of the ranks")
     if packed and beam_size > 1:
         raise NotImplementedError("packed results are built for greedy decoding (beam search keeps the dense path)")
     if labels is not None and beam_size > 1:
@@ -215,7 +223,8 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
         drawn = rec                                                      # what the predicted atoms and bonds are read from
         if expand:
             rec = engine.expand_pack(drawn, keep_device=molfile or smiles)     # what the writers read
-        ranked = engine.smiles_pack(rec, stereo=stereo, double_bonds=double_bonds, canonical=True) if canonical else None
+        ranked = engine.smiles_pack(rec, stereo=stereo, double_bonds=double_bonds, canonical=True,
+                                    **({"symmetry": True} if symmetry else {})) if canonical else None
         per_atom = {"rank": ranked[3], "sym_class": ranked[4]} if canonical else {}
         preds = unpack_graphs(drawn["mols"], drawn["atoms"], drawn["bonds"], drawn["text"], tok.maxx, compute_confidence,
                               **({} if expand else per_atom))
@@ -241,6 +250,8 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
                 written = not int(r["flags"]) & SMILES_REFUSED               # an empty molecule is written as the empty string
                 p["graph_smiles"] = data[t0:t0 + n].decode("ascii") if written else None
                 p["graph_smiles_order"] = order[a0:a0 + na].tolist() if written else None
+                if symmetry:
+                    p["stereo_atoms"] = ranked[5][a0:a0 + na].tolist() if written else None
         return preds
     scores = out["scores"].cpu().numpy() if beam_size > 1 else None
     lens = out["lengths"].cpu().numpy()
@@ -340,7 +351,12 @@ class molnextr:
     atoms of a drawing, and every output dict gains 'canonical_rank' and 'symmetry_class', a list per atom (None for a
     molecule that was not ranked). This library's own ranking: NOT RDKit's canonical SMILES (no toolkit has parsed it, and it
     never compares with a toolkit's string); the known limit of include/molnextr_hip.h applies — a few graphs whose string
-    still depends on the drawing."""
+    still depends on the drawing.
+    graph_symmetry: True (opt-in, default False; needs graph_smiles and graph_canonical) = the marks of that SMILES pass the
+    symmetry rule of mnx_smiles_pack_symmetric (a centre or double bond with two substituents of one symmetry class, both on
+    bonds off every cycle, writes no mark), and every output dict gains 'stereo_atoms', the ATOM_* bits per atom (None for a
+    molecule that got no string). Off for a molecule with a pseudo-atom (combine with graph_expand); the ranks ignore stereo, a
+    pair on ring bonds is never dropped, and no toolkit has parsed the result: the limits stand in include/molnextr_hip.h."""
 
     image_format = "fp32"
     packed_results = False
@@ -349,12 +365,14 @@ class molnextr:
     graph_stereo = False
     graph_double_bonds = False
     graph_canonical = False
+    graph_symmetry = False
     graph_expand = False
 
     def __init__(self, model_path, device=None, max_batch: int = 32, dtype: str = DEFAULT_DTYPE,
                  device_preprocess: bool = True, image_format: str = "fp32", packed_results: bool = False,
                  graph_molfile: bool = False, graph_smiles: bool = False, graph_stereo: bool = False,
-                 graph_double_bonds: bool = False, graph_canonical: bool = False, graph_expand: bool = False):
+                 graph_double_bonds: bool = False, graph_canonical: bool = False, graph_expand: bool = False,
+                 graph_symmetry: bool = False):
         if model_path is None:
             raise ValueError("molnextr(model_path): a checkpoint path is required (pass 'synthetic' explicitly for the "
                              "deterministic test checkpoint)")
@@ -388,6 +406,9 @@ class molnextr:
         self.graph_canonical = bool(graph_canonical)
         if self.graph_canonical and not self.graph_smiles:
             raise ValueError("graph_canonical=True needs graph_smiles=True: the ranks order the graph SMILES")
+        self.graph_symmetry = bool(graph_symmetry)
+        if self.graph_symmetry and not (self.graph_smiles and self.graph_canonical):
+            raise ValueError("graph_symmetry=True needs graph_smiles=True and graph_canonical=True: the rule reads the symmetry classes")
         self.graph_expand = bool(graph_expand)
         if self.graph_expand and not (self.graph_smiles or self.graph_molfile):
             raise ValueError("graph_expand=True needs graph_smiles=True or graph_molfile=True: the expanded molecule is what they write")
@@ -580,6 +601,8 @@ class molnextr:
                 conf["double_bonds"] = True
             if self.graph_canonical:
                 conf["canonical"] = True
+            if self.graph_symmetry:
+                conf["symmetry"] = True
         if self.graph_expand:
             conf["expand"] = True
         gen = self._prefetched(groups)
@@ -627,6 +650,8 @@ class molnextr:
             d = {"predicted_smiles": smiles, "predicted_molfile": molfile}
             if "canonical_rank" in pred:                      # graph_canonical: per atom, in the order of atom_sets
                 d["canonical_rank"], d["symmetry_class"] = pred["canonical_rank"], pred["symmetry_class"]
+            if "stereo_atoms" in pred:                        # graph_symmetry: per atom, as the ranks
+                d["stereo_atoms"] = pred["stereo_atoms"]
             if "expanded" in pred:                            # graph_expand: the molecule the two strings describe; the ranks then
                 d["expanded"] = pred["expanded"]              # follow expanded['symbols'], not atom_sets
             if return_atoms_bonds:

@@ -20,6 +20,8 @@ is part of the product path and no number is asserted.
     images between two events, alternating with one mnx_molfile_pack and one mnx_smiles_pack_stereo call over the same tables,
     then mnx_smiles_pack_marks with marks 0, 1, 2 and 3 alternating with the two older SMILES calls in a pass of their own,
     then mnx_smiles_pack_canonical with each set of marks alternating with mnx_smiles_pack_marks in a pass of their own,
+    then mnx_smiles_pack_symmetric with each set of marks alternating with mnx_smiles_pack_canonical in a pass of their own
+    (also on the drug-like molecules with every third candidate centre a gem-dimethyl carbon, so that the rule fires),
     with how many molecules were written and how many refused per flag; `--smiles-out FILE` writes the table to a file of its
     own.
 (x) (only when asked for: --part x) abbreviation expansion on the device: mnx_expand_pack alone, against mnx_graph_pack on the
@@ -234,12 +236,15 @@ def part_m(n, repeats, lines):
 LABELS = (b"[OMe]", b"[Ph]", b"[tBu]", b"[CO2Et]", b"[NO2]", b"[Boc]")
 
 
-def druglike_records(n_mols, seed=0, centres=False, labels=False):
+def druglike_records(n_mols, seed=0, centres=False, labels=False, gem=False):
     """Packed records of n_mols hand-made molecules of drug-like size: a chain of 20 .. 40 atoms, every seventh atom starting
     an aromatic six-ring, a few hetero atoms and double bonds (about 1.1 bonds per atom) — (mols, atoms, bonds, text).
     centres: every [C@@H] of the chain also carries a methyl on a wedge or a dash that begins at it, and its chain bonds are
     single: a candidate centre of mnx_smiles_pack_stereo (the molecules are the same otherwise). labels: every ninth atom that is a
-    plain 'C' becomes an abbreviation label of mnx_expand_pack, the six of LABELS in turn (the same molecules otherwise)."""
+    plain 'C' becomes an abbreviation label of mnx_expand_pack, the six of LABELS in turn (the same molecules otherwise). gem
+    (with centres): every third centre is a [C@@] with a second methyl — a gem-dimethyl carbon, which mnx_smiles_pack_symmetric
+    drops — and every bond record carries its class in `rev` too, as mnx_graph_pack writes it (the older sets leave 0 there, so
+    a bond whose ends the ranks swap is written '~' and no centre beside it is a candidate)."""
     from molnextr_amd.engine import ATOM_DTYPE, BOND_DTYPE, MOL_DTYPE
     rng = np.random.default_rng(seed)
     mols = np.zeros(n_mols, MOL_DTYPE)
@@ -271,13 +276,18 @@ def druglike_records(n_mols, seed=0, centres=False, labels=False):
                 rev[(k, len(syms))] = 6 - k % 2
                 syms.append(b"C")
                 xy.append((xy[k][0], (xy[k][1] + 3) % 64))
+                if gem and k % 3 == 0:
+                    syms[k] = b"[C@@]"
+                    bonds[(k, len(syms))] = 1
+                    syms.append(b"C")
+                    xy.append(((xy[k][0] + 3) % 64, xy[k][1]))
         own = b"".join(syms)
         mols[b] = (len(A), len(syms), len(B), len(bonds), len(text), len(own), 0, 0, 0.0)
         off = 0
         for k, sym in enumerate(syms):
             A.append((off, len(sym), k, xy[k][0], xy[k][1], 0.0))
             off += len(sym)
-        B += [(i, j, ty, rev.get((i, j), 0), 0.0) for (i, j), ty in sorted(bonds.items())]
+        B += [(i, j, ty, rev.get((i, j), ty if gem else 0), 0.0) for (i, j), ty in sorted(bonds.items())]
         text += own
     return mols, np.array(A, ATOM_DTYPE), np.array(B, BOND_DTYPE), bytes(text)
 
@@ -351,6 +361,18 @@ def part_s(repeats, lines):
                     eng.h, ptr(mols), n, ptr(atoms), na, ptr(bonds), nb, ptr(text), nt, ptr(recs_d), ptr(order_d), ptr(rank_d),
                     ptr(class_d), ptr(out_d[k]), len(want[k]), ptr(totals_d), marks, stream())
 
+        sym = hasattr(eng.lib, "mnx_smiles_pack_symmetric")        # absent from a build of before the call existed
+        if sym:                                                     # mnx_smiles_pack_symmetric, every set of marks
+            marks_d = torch.empty(max(na, 1), dtype=torch.uint8, device=dev)
+            sy = {marks: eng.smiles_pack(rec, stereo=bool(marks & 1), double_bonds=bool(marks & 2), canonical=True, symmetry=True)
+                  for marks in range(4)}
+            for marks in range(4):
+                k = f"symmetric {marks}"
+                out_d[k], want[k] = torch.empty(max(len(sy[marks][2]), 1), dtype=torch.uint8, device=dev), sy[marks][2]
+                calls[k] = lambda marks=marks, k=k: eng.lib.mnx_smiles_pack_symmetric(
+                    eng.h, ptr(mols), n, ptr(atoms), na, ptr(bonds), nb, ptr(text), nt, ptr(recs_d), ptr(order_d), ptr(rank_d),
+                    ptr(class_d), ptr(marks_d), ptr(out_d[k]), len(want[k]), ptr(totals_d), marks, stream())
+
         def alternate(names):
             us = {k: [] for k in names}
             for i in range(repeats + 3):
@@ -372,6 +394,7 @@ def part_s(repeats, lines):
         like1 = alternate(("mnx_smiles_pack", "marks 1"))
         six = alternate(("mnx_smiles_pack", "mnx_smiles_pack_stereo", "marks 0", "marks 1", "marks 2", "marks 3"))   # and every set of marks
         eight = alternate(tuple(f"{c} {marks}" for marks in range(4) for c in ("marks", "canonical"))) if canon else None
+        again = alternate(tuple(f"{c} {marks}" for marks in range(4) for c in ("canonical", "symmetric"))) if sym else None
         refused = (recs["flags"] & E.SMILES_REFUSED) != 0
         lines.append(f"(s) one call over the packed tables of {n} {what} ({na} atoms, {nb} bonds): device us between two events around "
                      "its three launches, the two calls alternating   median [min .. max]")
@@ -411,6 +434,22 @@ def part_s(repeats, lines):
             lines.append(f"  a tie broken in {int((fc & E.SMILES_CANON_TIE != 0).sum())} molecules, one by the atom index alone in "
                          f"{int((fc & E.SMILES_CANON_TIE_INDEX != 0).sum())}; strings that differ from the uncanonical ones: "
                          f"{sum(cn[0][2][a:a + l] != data[b:b + l2] for a, l, b, l2 in zip(cn[0][0]['text0'].tolist(), cn[0][0]['len'].tolist(), recs['text0'].tolist(), recs['len'].tolist()))}")
+        if sym:
+            lines.append("  mnx_smiles_pack_symmetric against mnx_smiles_pack_canonical with the same marks (four launches each), the eight "
+                         "alternating in a pass of their own:")
+            for k in again:
+                lines.append(f"  {k:22s} {fmt(again[k])} us   -> {len(want[k])} bytes")
+            med = {k: statistics.median(v) for k, v in again.items()}
+            spread = max(max(v) - min(v) for v in again.values())
+            f3, bits = sy[3][0]["flags"], sy[3][5]
+            lines.append(f"  symmetric - canonical, medians: " + "; ".join(f"marks {q}: {med[f'symmetric {q}'] - med[f'canonical {q}']:+.2f} us" for q in range(4)))
+            lines.append(f"  the low pass at marks 1: symmetric 1 - canonical 1 = {med['symmetric 1'] - med['canonical 1']:+.2f} us against "
+                         f"canonical 3 - canonical 1 = {med['canonical 3'] - med['canonical 1']:+.2f} us; the widest min .. max of the pass: {spread:.2f} us")
+            lines.append(f"  marks 3: a mark dropped in {int((f3 & E.SMILES_SYM_DROPPED != 0).sum())} molecules ({int((bits == E.ATOM_MARK_SYM).sum())} centres, "
+                         f"{int(((bits != E.ATOM_MARKS_NONE) & (bits & E.ATOM_EZ_SYM != 0)).sum()) // 2} double bonds), kept: "
+                         f"{int(((bits != E.ATOM_MARKS_NONE) & (bits & 3 != 0)).sum())} centres, "
+                         f"{int(((bits != E.ATOM_MARKS_NONE) & (bits & E.ATOM_EZ != 0)).sum()) // 2} double bonds; the rule is off (a pseudo-atom) in "
+                         f"{int((f3 & E.SMILES_PSEUDO_ATOM != 0).sum())} molecules")
         lines.append(f"  graph SMILES written for {int((~refused).sum())} of {n} molecules ({int(((~refused) & (recs['len'] == 0)).sum())} of "
                      f"them empty), refused {int(refused.sum())}; ring bonds per molecule: median {int(np.median(recs['n_rings']))}, max "
                      f"{int(recs['n_rings'].max())}; molfiles refused: {int((files['len'] == 0).sum())}")
@@ -430,6 +469,10 @@ def part_s(repeats, lines):
     mols, atoms, bonds, text = druglike_records(1024, centres=True)
     measure({"mols": mols, "atoms": atoms, "bonds": bonds, "text": text, "device": (up(mols), up(atoms), up(bonds), up(text))},
             "hand-made molecules of drug-like size with candidate centres")
+    if hasattr(eng.lib, "mnx_smiles_pack_symmetric"):
+        mols, atoms, bonds, text = druglike_records(1024, centres=True, gem=True)
+        measure({"mols": mols, "atoms": atoms, "bonds": bonds, "text": text, "device": (up(mols), up(atoms), up(bonds), up(text))},
+                "hand-made molecules of drug-like size with candidate centres, every third a gem-dimethyl carbon")
     if hasattr(eng.lib, "mnx_smiles_pack_canonical"):
         lines.append("(s) mnx_smiles_pack_canonical on the two molecules that rank longest, one molecule (one workgroup) per call: device ms "
                      "between two events around the four launches   median [min .. max]")
