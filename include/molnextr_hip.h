@@ -1054,6 +1054,24 @@ int mnx_window_attn(mnx_engine* h, const void* qkv, int64_t qkv_lo, const float*
  * (with mnx_last_error). Asynchronous on `stream`. */
 int mnx_kv_block(mnx_engine* h, int32_t which, int32_t layer, int32_t owner, int32_t head, void* dst, void* stream);
 
+/* Test aid: the beam-search strategy kernels (begin, pick, gather) on scripted log-probs, without a decoder. table is device
+ * fp32 [max_len][B][beam][V]: the log-prob row that hypothesis j of ORIGINAL image b sees at step t lies at
+ * ((t * B + b) * beam + j) * V, whichever images have left the batch by then. One rule of the head is applied to a row
+ * and nothing else: at step 0 the eos column is read as -1e20 (min_length = 1); there is no grammar mask. V = 2..256
+ * stands in for the vocabulary and eos = 0..V-1 for its id; B <= 32, 1 <= n_best <= beam <= 8, 1 <= max_len <=
+ * cfg.max_len, B x beam <= dec_slots. The steps run as those of mnx_decode_beam do (no graph), until no image is alive.
+ * Outputs: tokens [B,n_best,max_len], lengths [B,n_best], scores [B,n_best] (device) as mnx_decode_beam gives them;
+ * *steps_run (HOST): the steps that found an image alive. Trace (device; all five pointers set, or all null), row (t, b)
+ * written at step t for every image b alive at the START of the step, all other rows left as the caller filled them:
+ * tr_parent / tr_token / tr_score [max_len][B][beam] — of every new hypothesis the parent 0..beam-1, the id and the fp32
+ * score the pick kernel ranked it by (its own word, (log-prob + cumulative) / (t + 2)); tr_alive [max_len][B] — 1 while the
+ * image stays in the batch after the step; tr_n_active [max_len] — the rows (alive images x beam) the begin kernel counted,
+ * written for the steps_run steps. MNX_ERR_INVALID_ARG (with mnx_last_error, "mnx_beam_scripted: ...") for anything else.
+ * Synchronises `stream` before it returns. */
+int mnx_beam_scripted(mnx_engine* h, const float* table, int32_t B, int32_t beam, int32_t n_best, int32_t max_len, int32_t V,
+                      int32_t eos, int32_t* tokens, int32_t* lengths, float* scores, int32_t* steps_run, int32_t* tr_parent,
+                      int32_t* tr_token, float* tr_score, int32_t* tr_alive, int32_t* tr_n_active, void* stream);
+
 /* Test aids: the encoder's non-GEMM kernels and the decoder's fp32 SGEMM on caller device buffers
  * (tests/test_gpu_encoder_ops.py). None uses anything of the engine but its device and, where stated, its compute_dtype
  * (FP16X3M counts as FP16X3). Every fp32 buffer is 16-byte aligned, a 16-bit output 8-byte. Each returns

@@ -117,6 +117,12 @@ struct BeamBuffers {
     int B, K, n_best, anc_stride;
     int ref_batch;   // images per reference batch: image i belongs to batch i / ref_batch (the PE numbering unit); B <= 32: B
     int pool_stride; // kept hypotheses stored per image (>= n_best)
+    // per-step trace of the pick kernel (mnx_beam_scripted; production leaves all four null): row (t, image) as the kernel
+    // decided it — parent 0..K-1, id and the fp32 score of every new hypothesis [steps][B][K], image still alive [steps][B]
+    int* tr_parent;
+    int* tr_token;
+    float* tr_score;
+    int* tr_alive;
 };
 
 // token classes for the on-device atom-position scan (CharTokenizer.sequence_to_smiles 'indices')
@@ -164,6 +170,10 @@ hipError_t dec_enqueue_fused_layers(const DecWeights& w, const DecBuffers& b, in
 hipError_t beam_enqueue_init(const DecBuffers& b, const BeamBuffers& bm, int max_len, hipStream_t s);
 hipError_t beam_enqueue_gather(const DecBuffers& b, const BeamBuffers& bm, int out_len, int* o_tokens, int* o_len,
                                float* o_scores, float* o_hidden, hipStream_t s);
+// one step of mnx_beam_scripted: beam_begin_kernel, its n_active -> *n_active_out (device), the table's rows of step t of the
+// alive slots -> bm.blp (eos banned at t == 0), beam_pick_kernel with the call's V and eos
+hipError_t beam_enqueue_script_step(const DecBuffers& b, const BeamBuffers& bm, const float* table, int V, int eos,
+                                    int* n_active_out, hipStream_t s);
 hipError_t dec_probe_attn(const DecWeights& w, const DecBuffers& b, int rows, int t, int iters, hipEvent_t* ev,
                           hipStream_t s);
 hipError_t dec_enqueue_admit_rows(const DecBuffers& b, const int* chunk_ids_dev, int n, int max_len, int stop_on_eos,

@@ -1223,6 +1223,10 @@ __global__ __launch_bounds__(256) void beam_pick_kernel(DecState* st, BeamBuffer
         etok[(size_t)slot * T + t] = tok;
         st->prev_tok[slot] = tok; st->t[slot] = t + 1; st->len[slot] = t + 1;
         bm.bs->cum[slot] = fin ? -1e10f : sel_score[tid] * len_f;  // :105, :134
+        if (bm.tr_score) {                                         // mnx_beam_scripted's trace; null in production
+            const size_t o = ((size_t)t * bm.B + img) * K + tid;
+            bm.tr_parent[o] = sel_idx[tid] / V; bm.tr_token[o] = tok; bm.tr_score[o] = sel_score[tid];
+        }
     }
     if (tid == 0) {                                                // update_finished (:131-165)
         BeamState* bs = bm.bs;
@@ -1249,6 +1253,7 @@ __global__ __launch_bounds__(256) void beam_pick_kernel(DecState* st, BeamBuffer
         n_tasks = nt;
         if (top && nh >= bm.n_best)                                                   // :152-153: the image is done
             for (int j = 0; j < K; ++j) st->alive[s0 + j] = 0;
+        if (bm.tr_score) bm.tr_alive[(size_t)t * bm.B + img] = !(top && nh >= bm.n_best);
     }
     __syncthreads();
     for (int q = 0; q < n_tasks; ++q) {            // materialise the kept hypotheses (ids + decoder outputs)
@@ -1290,6 +1295,30 @@ hipError_t beam_enqueue_gather(const DecBuffers& b, const BeamBuffers& bm, int o
                                float* o_scores, float* o_hidden, hipStream_t s) {
     hipLaunchKernelGGL(beam_gather_kernel, dim3(bm.n_best, bm.B), dim3(256), 0, s, bm, b.T, out_len, o_tokens, o_len,
                        o_scores, o_hidden);
+    return hipGetLastError();
+}
+
+// mnx_beam_scripted (test aid): in place of the decoder and the head, the log-prob row of every alive slot comes from the
+// caller's table [steps][B][K][V] (row of step t, image b, hypothesis j). The one rule of the head kept is min_length = 1:
+// at t == 0 the eos column is the head's -1e20. One workgroup per slot.
+__global__ __launch_bounds__(256) void beam_script_rows_kernel(const DecState* st, BeamBuffers bm,
+                                                               const float* __restrict__ table, int V, int eos) {
+    const int slot = blockIdx.x;
+    if (!st->alive[slot]) return;
+    const int t = st->t[slot];                     // < max_len <= steps of the table while the slot is alive
+    const float* src = table + ((size_t)t * bm.B * bm.K + slot) * V;
+    for (int v = threadIdx.x; v < V; v += 256)
+        bm.blp[(size_t)slot * BEAM_LP_STRIDE + v] = (t == 0 && v == eos) ? -1e20f : src[v];
+}
+
+// One scripted step: the begin kernel, its n_active copied to *n_active_out (device), the rows, the pick kernel.
+hipError_t beam_enqueue_script_step(const DecBuffers& b, const BeamBuffers& bm, const float* table, int V, int eos,
+                                    int* n_active_out, hipStream_t s) {
+    hipLaunchKernelGGL(beam_begin_kernel, dim3(1), dim3(256), 0, s, b.st, bm.B, bm.K, bm.ref_batch);
+    hipError_t e = hipMemcpyAsync(n_active_out, &b.st->n_active, sizeof(int), hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(beam_script_rows_kernel, dim3(bm.B * bm.K), dim3(256), 0, s, b.st, bm, table, V, eos);
+    hipLaunchKernelGGL(beam_pick_kernel, dim3(bm.B), dim3(256), 0, s, b.st, bm, b.hidden, b.tokens, b.T, V, eos);
     return hipGetLastError();
 }
 

@@ -88,6 +88,7 @@ struct mnx_engine {
     DecBuffers db{};
     float* out_trace = nullptr;
     int* forced_ids = nullptr;  // [32, max_len] teacher-forcing ids of mnx_decode_forced (lazy; test aid)
+    int* script_nact = nullptr; // [max_len] n_active of every step of mnx_beam_scripted (lazy; test aid)
     int* guide_labels = nullptr;   // [dec_slots, max_len + 2] label row of every slot, {ids held, the ids}: label-guided decoding
                                    // (mnx_decode_guided / mnx_predict_guided; lazy, written at admission — dec_types.h GuideRows)
     BeamBuffers beam{};        // allocated lazily on the first mnx_decode_beam
@@ -1068,25 +1069,35 @@ int decode_greedy_impl(mnx_engine* h, const float* features, int32_t B, const in
     return MNX_OK;
 }
 
+// kept hypotheses of all images (32 images x 8 ... 256 x 1) and how many of them one of B images may keep
+constexpr int BEAM_POOL = ROW_TILE * MAX_BEAM;
+inline int beam_pool_stride(int B) { return std::min(MAX_BEAM, BEAM_POOL / B); }
+
+// The engine's beam-search buffers (allocated by the first search) set up for B images x `beam` hypotheses
+int beam_buffers(mnx_engine* h, int B, int ref_batch, int beam, int n_best, bool hidden) {
+    const int D = h->cfg.dec_dim, T = h->db.T;
+    BeamBuffers& bm = h->beam;
+    const int pool_stride = beam_pool_stride(B);
+    if (pool_stride < n_best) { h->err = "beam search: n_best x images exceeds the hypothesis pool (256)"; return MNX_ERR_CAPACITY; }
+    MNXCHK(lazy_alloc(h, &bm.bs, sizeof(BeamState)));
+    MNXCHK(lazy_alloc(h, &bm.blp, (size_t)MAX_BEAM_IMGS * MAX_BEAM * BEAM_LP_STRIDE * 4));
+    MNXCHK(lazy_alloc(h, &bm.anc, (size_t)MAX_BEAM_IMGS * MAX_BEAM * (T + 1) * 4));
+    MNXCHK(lazy_alloc(h, &bm.ptok, (size_t)BEAM_POOL * T * 4));
+    if (hidden) MNXCHK(lazy_alloc(h, &bm.phid, (size_t)BEAM_POOL * T * D * 4));
+    bm.B = B; bm.K = beam; bm.n_best = n_best; bm.anc_stride = T + 1; bm.ref_batch = ref_batch; bm.pool_stride = pool_stride;
+    return MNX_OK;
+}
+
 // Beam search over G reference batches in ONE step sequence: batch g = images [g ref_batch, (g + 1) ref_batch) of n_total
 // (features at feats[g]), every image K hypotheses, one row per hypothesis — G x ref_batch x K rows per step. Images are
 // independent; the positional-encoding rows are numbered inside each reference batch (beam_begin_kernel), so the result is
 // that of G separate searches. Outputs [n_total, n_best, ...].
 int decode_beam_groups(mnx_engine* h, const float* const* feats, int G, int ref_batch, int n_total, int beam, int n_best,
                        int max_len, int32_t* tokens, int32_t* lengths, float* scores, float* hidden, hipStream_t s) {
-    const int D = h->cfg.dec_dim, T = h->db.T, B = n_total;
-    BeamBuffers& bm = h->beam;
+    const int B = n_total;
     // capacities: MAX_BEAM_IMGS images x MAX_BEAM hypotheses of state; 256 kept hypotheses (32 images x 8 ... 256 x 1)
-    constexpr int POOL = ROW_TILE * MAX_BEAM;
-    const int pool_stride = std::min(MAX_BEAM, POOL / B);
-    if (pool_stride < n_best) { h->err = "beam search: n_best x images exceeds the hypothesis pool (256)"; return MNX_ERR_CAPACITY; }
-    MNXCHK(lazy_alloc(h, &bm.bs, sizeof(BeamState)));
-    MNXCHK(lazy_alloc(h, &bm.blp, (size_t)MAX_BEAM_IMGS * MAX_BEAM * BEAM_LP_STRIDE * 4));
-    MNXCHK(lazy_alloc(h, &bm.anc, (size_t)MAX_BEAM_IMGS * MAX_BEAM * (T + 1) * 4));
-    MNXCHK(lazy_alloc(h, &bm.ptok, (size_t)POOL * T * 4));
-    if (hidden) MNXCHK(lazy_alloc(h, &bm.phid, (size_t)POOL * T * D * 4));
-    bm.B = B; bm.K = beam; bm.n_best = n_best; bm.anc_stride = T + 1; bm.ref_batch = ref_batch; bm.pool_stride = pool_stride;
-    BeamBuffers run = bm;
+    MNXCHK(beam_buffers(h, B, ref_batch, beam, n_best, hidden != nullptr));
+    BeamBuffers run = h->beam;
     if (!hidden) run.phid = nullptr;
     for (int g = 0; g < G; ++g)      // memory of batch g -> memory blocks g ref_batch ...
         MNXCHK(project_memory(h, feats[g], std::min(ref_batch, B - g * ref_batch), g * ref_batch, s));
@@ -2026,6 +2037,51 @@ int mnx_kv_block(mnx_engine* h, int32_t which, int32_t layer, int32_t owner, int
     }
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return MNX_OK;
+}
+
+int mnx_beam_scripted(mnx_engine* h, const float* table, int32_t B, int32_t beam, int32_t n_best, int32_t max_len, int32_t V,
+                      int32_t eos, int32_t* tokens, int32_t* lengths, float* scores, int32_t* steps_run, int32_t* tr_parent,
+                      int32_t* tr_token, float* tr_score, int32_t* tr_alive, int32_t* tr_n_active, void* stream) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    auto bad = [&](const char* m) { h->err = std::string("mnx_beam_scripted: ") + m; return MNX_ERR_INVALID_ARG; };
+    const mnx_config& c = h->cfg;
+    if (!table || !tokens || !lengths || !scores || !steps_run) return bad("null table, tokens, lengths, scores or steps_run");
+    const int n_tr = !!tr_parent + !!tr_token + !!tr_score + !!tr_alive + !!tr_n_active;
+    if (n_tr != 0 && n_tr != 5) return bad("the five trace pointers must be all null or all set");
+    if (B < 1) return bad("B must be 1..32");
+    if (beam < 1 || beam > MAX_BEAM) return bad("beam must be 1..8");
+    if (n_best < 1 || n_best > beam) return bad("n_best must be 1..beam");
+    if (V < 2 || V > BEAM_LP_STRIDE) return bad("V must be 2..256");
+    if (eos < 0 || eos >= V) return bad("eos must be 0..V-1");
+    if (max_len < 1 || max_len > c.max_len || c.max_len + 1 > BEAM_ANC_MAX) return bad("max_len must be 1..cfg.max_len (<= 511)");
+    // the pool first: with B <= 32 it keeps 8 per image, so only a larger B can ask for more than it holds
+    if (n_best > beam_pool_stride(B)) return bad("n_best exceeds the hypotheses the pool keeps per image (256 / B)");
+    if (B > ROW_TILE) return bad("B must be 1..32");
+    if (B * beam > h->db.slots) return bad("B x beam exceeds dec_slots");
+    hipStream_t s;
+    MNXCHK(caller_stream(h, stream, &s));
+    MNXCHK(beam_buffers(h, B, B, beam, n_best, false));
+    MNXCHK(lazy_alloc(h, &h->script_nact, (size_t)c.max_len * 4));
+    BeamBuffers run = h->beam;
+    run.phid = nullptr;
+    run.tr_parent = tr_parent; run.tr_token = tr_token; run.tr_score = tr_score; run.tr_alive = tr_alive;
+    HIPCHK(h, dec_enqueue_reset(h->db, s));
+    HIPCHK(h, beam_enqueue_init(h->db, run, max_len, s));
+    const int rows = (B * beam + ROW_TILE - 1) / ROW_TILE * ROW_TILE;
+    int step = 0;       // steps enqueued so far; the loop is run_steps' (groups of 8, then the alive count), without a graph
+    MNXCHK(run_steps(h, nullptr, [&]() { return beam_enqueue_script_step(h->db, run, table, V, eos, h->script_nact + step++, s); },
+                     rows, max_len, s));
+    HIPCHK(h, beam_enqueue_gather(h->db, run, max_len, tokens, lengths, scores, nullptr, s));
+    std::vector<int> nact(step);
+    HIPCHK(h, hipMemcpyAsync(nact.data(), h->script_nact, (size_t)step * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    int n_run = 0;      // a step whose begin kernel found no row alive ran nothing
+    while (n_run < step && nact[n_run] > 0) ++n_run;
+    if (tr_n_active && n_run)
+        HIPCHK(h, hipMemcpyAsync(tr_n_active, h->script_nact, (size_t)n_run * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    *steps_run = n_run;
     return MNX_OK;
 }
 

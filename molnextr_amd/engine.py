@@ -28,7 +28,8 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
            "mnx_encode_gray8", "mnx_predict_gray8", "mnx_decode_guided", "mnx_predict_guided", "mnx_patch_embed",
            "mnx_layernorm16", "mnx_merge_ln16", "mnx_cast16", "mnx_sgemm_tn", "mnx_set_vocab_text", "mnx_graph_pack",
            "mnx_set_symbol_tables", "mnx_molfile_pack", "mnx_smiles_pack", "mnx_smiles_pack_stereo",
-           "mnx_smiles_pack_marks", "mnx_smiles_pack_canonical", "mnx_smiles_pack_symmetric", "mnx_set_fragments", "mnx_expand_pack", "mnx_smiles_read")
+           "mnx_smiles_pack_marks", "mnx_smiles_pack_canonical", "mnx_smiles_pack_symmetric", "mnx_set_fragments", "mnx_expand_pack", "mnx_smiles_read",
+           "mnx_beam_scripted")
 
 # Encoder operand modes (include/molnextr_hip.h MNX_DTYPE_*). "fp16x3" — split fp16 operands, three MFMA terms per
 # product, fp32-class results — is the default: it is the fastest mode whose results stay a factor of four inside north_star's
@@ -243,6 +244,9 @@ def load_library():
     lib.mnx_window_attn.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.mnx_kv_block.restype = C.c_int
     lib.mnx_kv_block.argtypes = [vp, i32, i32, i32, i32, vp, vp]
+    lib.mnx_beam_scripted.restype = C.c_int
+    lib.mnx_beam_scripted.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, C.POINTER(C.c_int32), vp, vp, vp, vp,
+                                      vp, vp]
     lib.mnx_patch_embed.restype = C.c_int
     lib.mnx_patch_embed.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     lib.mnx_layernorm16.restype = C.c_int
@@ -759,6 +763,36 @@ class Engine:
                                       _ptr(scores), _ptr(hidden), _stream())
         self._check(rc, "mnx_decode_beam")
         return {"tokens": tokens, "lengths": lengths, "scores": scores, "hidden": hidden}
+
+    def beam_scripted(self, table: torch.Tensor, n_best: int = 1, eos: int = 2, trace: bool = True,
+                      fill: int = -7) -> dict:
+        """The beam-search strategy kernels on scripted log-probs (test aid, mnx_beam_scripted): table fp32
+        [max_len, B, beam, V] on the device, row (t, b, j) = what hypothesis j of original image b sees at step t; the eos
+        column of step 0 is banned, nothing else is applied. Returns tokens [B,n_best,max_len], lengths, scores as
+        decode_beam does, 'steps_run', and with trace=True the per-step 'parent', 'token', 'score' [max_len,B,beam], 'alive'
+        [max_len,B] and 'n_active' [max_len]: rows of images not alive at the start of a step keep `fill`."""
+        assert table.is_cuda and table.dtype == torch.float32 and table.is_contiguous() and table.dim() == 4
+        max_len, B, beam, V = table.shape
+        dev = table.device
+        out = {"tokens": torch.zeros(B, n_best, max_len, dtype=torch.int32, device=dev),
+               "lengths": torch.zeros(B, n_best, dtype=torch.int32, device=dev),
+               "scores": torch.zeros(B, n_best, dtype=torch.float32, device=dev)}
+        tr = {}
+        if trace:
+            tr = {"parent": torch.full((max_len, B, beam), fill, dtype=torch.int32, device=dev),
+                  "token": torch.full((max_len, B, beam), fill, dtype=torch.int32, device=dev),
+                  "score": torch.full((max_len, B, beam), float(fill), dtype=torch.float32, device=dev),
+                  "alive": torch.full((max_len, B), fill, dtype=torch.int32, device=dev),
+                  "n_active": torch.full((max_len,), fill, dtype=torch.int32, device=dev)}
+        steps = C.c_int32(-1)
+        rc = self.lib.mnx_beam_scripted(self.h, _ptr(table), B, beam, n_best, max_len, V, eos, _ptr(out["tokens"]),
+                                        _ptr(out["lengths"]), _ptr(out["scores"]), C.byref(steps), _ptr(tr.get("parent")),
+                                        _ptr(tr.get("token")), _ptr(tr.get("score")), _ptr(tr.get("alive")),
+                                        _ptr(tr.get("n_active")), _stream())
+        self._check(rc, "mnx_beam_scripted")
+        out.update(tr)
+        out["steps_run"] = steps.value
+        return out
 
     # -- GraphPredictor + get_edge_prediction ----------------------------------------------------
     def edges(self, hidden: torch.Tensor, atom_idx: torch.Tensor, n_atoms: torch.Tensor, want_scores: bool = False):
