@@ -240,8 +240,10 @@ int mnx_decode_beam(mnx_engine* h, const float* features, int32_t B, int32_t bea
  *   hidden   device fp32 [B,max_len,256] as written by mnx_decode_greedy
  *   atom_idx device int32 [B,kmax]: decoder position of each atom (CharTokenizer.sequence_to_smiles 'indices')
  *   n_atoms  device int32 [B]
- *   edges    device uint8 [B,kmax,kmax] bond class 0..6 (rows/cols >= n_atoms[b] undefined)
+ *   edges    device uint8 [B,kmax,kmax] bond class 0..6 (rows/cols >= n_atoms[b] are left as the caller filled them)
  *   scores   device fp64 [B,kmax,kmax] or NULL
+ * B <= 32, kmax <= cfg.max_atoms. Device values out of range are read as clamped, never trusted: n_atoms[b] outside
+ * 0..kmax as min(max(n_atoms[b], 0), kmax), atom_idx outside 0..max_len-1 as min(max(atom_idx, 0), max_len - 1).
  * Asynchronous on `stream`. */
 int mnx_edges(mnx_engine* h, const float* hidden, const int32_t* atom_idx, const int32_t* n_atoms, int32_t B,
               int32_t kmax, int32_t max_len, uint8_t* edges, double* scores, void* stream);
@@ -1071,6 +1073,14 @@ int mnx_kv_block(mnx_engine* h, int32_t which, int32_t layer, int32_t owner, int
 int mnx_beam_scripted(mnx_engine* h, const float* table, int32_t B, int32_t beam, int32_t n_best, int32_t max_len, int32_t V,
                       int32_t eos, int32_t* tokens, int32_t* lengths, float* scores, int32_t* steps_run, int32_t* tr_parent,
                       int32_t* tr_token, float* tr_score, int32_t* tr_alive, int32_t* tr_n_active, void* stream);
+
+/* Test aid: mnx_edges with one more output. After the same four launches it copies, device to device on `stream`, what
+ * the bond head's pair kernel left behind: probs device fp32 [B,kmax,kmax,8], laid out by the call's kmax; slots 0..6 of
+ * pair (i, j) are the softmax over the 7 bond classes (before get_edge_prediction) for i, j < n_atoms[b] (clamped as
+ * above). Slot 7 and every other pair are undefined. Arguments, clamping and errors as mnx_edges ("mnx_edge_probs: ...");
+ * a refused call launches and copies nothing. Asynchronous on `stream`. */
+int mnx_edge_probs(mnx_engine* h, const float* hidden, const int32_t* atom_idx, const int32_t* n_atoms, int32_t B,
+                   int32_t kmax, int32_t max_len, uint8_t* edges, double* scores, float* probs, void* stream);
 
 /* Test aids: the encoder's non-GEMM kernels and the decoder's fp32 SGEMM on caller device buffers
  * (tests/test_gpu_encoder_ops.py). None uses anything of the engine but its device and, where stated, its compute_dtype

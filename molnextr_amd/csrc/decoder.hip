@@ -891,8 +891,9 @@ __global__ void edge_gather_kernel(const float* __restrict__ hidden, const int* 
                                    const int* __restrict__ atom_idx, const int* __restrict__ n_atoms,
                                    float* __restrict__ g, int kmax, int max_len) {
     const int b = blockIdx.y, i = blockIdx.x, lane = threadIdx.x;
-    int idx = i < n_atoms[b] ? atom_idx[b * kmax + i] : 0;
-    idx = min(max(idx, 0), max_len - 1);
+    const int k = min(max(n_atoms[b], 0), kmax);                // a count outside 0..kmax is read as clamped
+    int idx = i < k ? atom_idx[b * kmax + i] : 0;
+    idx = min(max(idx, 0), max_len - 1);                        // and so is a position outside 0..max_len-1
     const size_t row = slot_map ? (size_t)slot_map[b] : (size_t)b;
     *(f32x4*)(g + ((size_t)b * kmax + i) * 256 + lane * 4) =
         *(const f32x4*)(hidden + (row * max_len + idx) * 256 + lane * 4);
@@ -905,7 +906,7 @@ __global__ __launch_bounds__(256) void edge_pair_kernel(const float* __restrict_
     __shared__ float us[256];
     __shared__ float w2s[7 * 256];
     const int b = blockIdx.y, i = blockIdx.x, tid = threadIdx.x;
-    const int k = n_atoms[b];
+    const int k = min(max(n_atoms[b], 0), kmax);
     if (i >= k) return;
     us[tid] = UV[((size_t)b * kmax + i) * 512 + tid];
     for (int q = tid; q < 7 * 256; q += 256) w2s[q] = w2[q];
@@ -941,7 +942,7 @@ __global__ __launch_bounds__(256) void edge_pair_kernel(const float* __restrict_
 __global__ void edge_sym_kernel(const float* __restrict__ prob, const int* __restrict__ n_atoms,
                                 unsigned char* __restrict__ edges, double* __restrict__ scores, int kmax) {
     const int b = blockIdx.z, i = blockIdx.y, j = blockIdx.x * blockDim.x + threadIdx.x;
-    const int k = n_atoms[b];
+    const int k = min(max(n_atoms[b], 0), kmax);
     if (i >= k || j >= k) return;
     const float* pij = prob + (((size_t)b * kmax + i) * kmax + j) * 8;
     const float* pji = prob + (((size_t)b * kmax + j) * kmax + i) * 8;

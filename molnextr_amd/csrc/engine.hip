@@ -1277,6 +1277,22 @@ int mnx_edges(mnx_engine* h, const float* hidden, const int32_t* atom_idx, const
     return MNX_OK;
 }
 
+// mnx_edge_probs (test aid): mnx_edges, then what edge_pair_kernel left in edge_prob for this B and kmax
+int mnx_edge_probs(mnx_engine* h, const float* hidden, const int32_t* atom_idx, const int32_t* n_atoms, int32_t B,
+                   int32_t kmax, int32_t max_len, uint8_t* edges, double* scores, float* probs, void* stream) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    if (!hidden || !atom_idx || !n_atoms || !edges || !probs || B < 1 || kmax < 1 || max_len < 1) {
+        h->err = "mnx_edge_probs: null/empty argument";
+        return MNX_ERR_INVALID_ARG;
+    }
+    if (B > ROW_TILE || kmax > h->db.kmax) { h->err = "mnx_edge_probs: B <= 32 and kmax <= cfg.max_atoms required"; return MNX_ERR_CAPACITY; }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, edges_enqueue(h->dw, h->db, hidden, nullptr, atom_idx, n_atoms, B, kmax, max_len, edges, scores, (hipStream_t)stream));
+    HIPCHK(h, hipMemcpyAsync(probs, h->db.edge_prob, (size_t)B * kmax * kmax * 8 * sizeof(float), hipMemcpyDeviceToDevice,
+                             (hipStream_t)stream));
+    return MNX_OK;
+}
+
 int mnx_set_token_classes(mnx_engine* h, const uint8_t* flags, int32_t n, int32_t lbracket, int32_t rbracket,
                           int32_t id_C, int32_t id_l, int32_t id_B, int32_t id_r) {
     if (!h || !flags || n < 1 || n > 256) return MNX_ERR_INVALID_ARG;

@@ -29,7 +29,7 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
            "mnx_layernorm16", "mnx_merge_ln16", "mnx_cast16", "mnx_sgemm_tn", "mnx_set_vocab_text", "mnx_graph_pack",
            "mnx_set_symbol_tables", "mnx_molfile_pack", "mnx_smiles_pack", "mnx_smiles_pack_stereo",
            "mnx_smiles_pack_marks", "mnx_smiles_pack_canonical", "mnx_smiles_pack_symmetric", "mnx_set_fragments", "mnx_expand_pack", "mnx_smiles_read",
-           "mnx_beam_scripted")
+           "mnx_beam_scripted", "mnx_edge_probs")
 
 # Encoder operand modes (include/molnextr_hip.h MNX_DTYPE_*). "fp16x3" — split fp16 operands, three MFMA terms per
 # product, fp32-class results — is the default: it is the fastest mode whose results stay a factor of four inside north_star's
@@ -242,6 +242,8 @@ def load_library():
     lib.mnx_gemm16_split.argtypes = [vp, i32, vp, C.c_int64, vp, C.c_int64, C.c_float, vp, C.c_int64, vp, i32, i32, i32, i32, vp]
     lib.mnx_window_attn.restype = C.c_int
     lib.mnx_window_attn.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, i32, i32, i32, i32, i32, i32, i32, vp]
+    lib.mnx_edge_probs.restype = C.c_int
+    lib.mnx_edge_probs.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]
     lib.mnx_kv_block.restype = C.c_int
     lib.mnx_kv_block.argtypes = [vp, i32, i32, i32, i32, vp, vp]
     lib.mnx_beam_scripted.restype = C.c_int
@@ -807,6 +809,22 @@ class Engine:
                                 _ptr(scores), _stream())
         self._check(rc, "mnx_edges")
         return edges, scores
+
+    def edge_probs(self, hidden: torch.Tensor, atom_idx: torch.Tensor, n_atoms: torch.Tensor, want_scores: bool = True):
+        """edges() plus the seven class probabilities of every pair as the pair kernel left them (test aid,
+        mnx_edge_probs): -> edges, scores, probs fp32 [B,kmax,kmax,8]; slot 7 and pairs beyond n_atoms[b] are undefined."""
+        assert hidden.is_cuda and hidden.dtype == torch.float32 and hidden.is_contiguous()
+        B, max_len, _ = hidden.shape
+        atom_idx = atom_idx.to(device=hidden.device, dtype=torch.int32).contiguous()
+        n_atoms = n_atoms.to(device=hidden.device, dtype=torch.int32).contiguous()
+        kmax = atom_idx.shape[1]
+        edges = torch.zeros(B, kmax, kmax, dtype=torch.uint8, device=hidden.device)
+        scores = torch.zeros(B, kmax, kmax, dtype=torch.float64, device=hidden.device) if want_scores else None
+        probs = torch.zeros(B, kmax, kmax, 8, dtype=torch.float32, device=hidden.device)
+        rc = self.lib.mnx_edge_probs(self.h, _ptr(hidden), _ptr(atom_idx), _ptr(n_atoms), B, kmax, max_len, _ptr(edges),
+                                     _ptr(scores), _ptr(probs), _stream())
+        self._check(rc, "mnx_edge_probs")
+        return edges, scores, probs
 
     # -- whole path, continuous batching ----------------------------------------------------------
     @property
