@@ -412,7 +412,7 @@ int mnx_set_vocab_text(mnx_engine* h, const char* bytes, const uint32_t* offsets
  * size outside the limits, the scores partly set, misaligned records, or no vocabulary text / token classes set. */
 typedef struct mnx_mol {
     uint32_t atom0, n_atoms, bond0, n_bonds, text0, smiles_len;
-    uint32_t flags;             /* bit 0: more atoms than kmax, tables truncated to kmax; MNX_MOL_EXPAND* of mnx_expand_pack */
+    uint32_t flags;             /* bit 0: more atoms than kmax, tables truncated to kmax; MNX_MOL_EXPAND* of mnx_expand_pack; bits 4-6 of mnx_normalize_pack */
     uint32_t reserved;          /* 0 */
     double overall_score;
 } mnx_mol;
@@ -918,13 +918,102 @@ int mnx_expand_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_ato
                     mnx_atom* atoms_out, uint32_t atom_cap, mnx_bond* bonds_out, uint32_t bond_cap, char* text_out,
                     uint32_t text_cap, uint16_t* origin, uint32_t* totals, void* stream);
 
+/* One normal spelling per atom, on the device: packed tables in, packed tables of the SAME record types out, with aromatic rings
+ * perceived from Kekule drawings, hydrogens counted and brackets dropped where a reader infers what they say. The canonical ranks key
+ * on the bytes a writer puts down for an atom, so without this pass c1ccccc1 never equals C1=CC=CC=C1, C[CH](C)F never equals
+ * CC(C)F, and a pyrrole drawn with N never equals [nH]. Intended order: mnx_smiles_read or mnx_graph_pack -> mnx_expand_pack ->
+ * THIS CALL -> mnx_molfile_pack / the mnx_smiles_pack calls, all of which run on the output unchanged.
+ * THE RULE IS THIS LIBRARY'S OWN. It is NOT RDKit's aromaticity model (nor Daylight's, nor any toolkit's), no toolkit has checked
+ * it, and a string written behind it never compares with a toolkit's. It only goes from Kekule to aromatic: nothing kekulises.
+ * A post-pass on a post-pass: it reads the input tables, changes none of them (the outputs must not overlap them) and touches no
+ * decode state. Atom and bond COUNTS and ORDER never change: only the text, an atom's sym0 / sym_len and a bond's type / rev do.
+ *
+ * The rule, per molecule:
+ * Interpretation. Every atom's symbol is read as mnx_molfile_pack reads it. COPIED, byte for byte, taking part in nothing below:
+ *   a pseudo-atom (R-group, abbreviation, a symbol without a parse), a parsed '*' with or without brackets, an atom whose element
+ *   is spelled in lower case already, and an EXCLUDED atom (next paragraph). The four chiral carbon symbols [C@] [C@@] [C@H]
+ *   [C@@H] are interpreted (their H count is the written one) but never candidates, and their bytes are copied too, so that
+ *   mnx_smiles_pack_stereo still finds its centres. Every other atom is INTERPRETED: (isotope, element, H, charge).
+ * Bonds. By `type` (rev is not read): 1, 5 and 6 are single (order 1), 2 double, 3 triple. An atom with a bond record of type 4
+ *   or of any other type, or with a record from the atom to itself, is EXCLUDED. So every bond of an atom that is not excluded has
+ *   an integer order; bo(a) is the sum of the orders of the bond records at a, deg(a) their number.
+ * Hydrogens H(a). A bracket atom has its written count. An unbracketed atom of the organic subset has v - bo(a) for the smallest
+ *   normal valence v >= bo(a), 0 when there is none: B 3; C 4; N 3, 5; O 2; P 3, 5; S 2, 4, 6; F, Cl, Br, I 1.
+ * Candidates. An interpreted C, N, O or S that is none of the chiral symbols, with deg <= 3, all its bond records to different
+ *   atoms, no triple bond, and one of
+ *     (d) exactly one double bond, and it is C with charge 0 or N with charge 0 or +1;
+ *     (p) no double bond, and it is N with charge 0 and deg + H = 3, or O or S with charge 0, deg = 2 and H = 0, or C with
+ *         charge -1 and deg + H = 3;
+ *     (e) no double bond, and it is C with charge +1.
+ * Rings. The ENUMERATED rings are the simple cycles of exactly 5 or 6 atoms that are all candidates (their bonds are single or
+ *   double by the above). A bond on an enumerated ring is a RING-SYSTEM bond. Which rings are enumerated does not depend on any
+ *   verdict, so no fixed point is iterated: the ring-system bonds are marked first, then every ring is judged.
+ * Electrons of atom a in ring R: (p) 2; (e) 0; (d) 1 when a's double bond is a ring-system bond (in R or in a fused enumerated
+ *   ring); (d) 0 when a is C and its double bond goes to an O, N or S atom (any spelling that parses) that lies on no enumerated
+ *   ring — the exocyclic C=O of a pyridone; in every other case R FAILS. R is AROMATIC when it does not fail and the sum is 6.
+ * Marking. Every atom of an aromatic ring becomes lower case; every bond of an aromatic ring gets type = rev = 4 (a wedge there
+ *   is lost). Every other bond record keeps its fields: the writers put '-' between two aromatic atoms joined by a single bond.
+ * Spelling of an interpreted atom, from (isotope, element, aromatic, H, charge): WITHOUT brackets when the element is of the
+ *   organic subset, there is no isotope, the charge is 0 and H is what a reader infers — for an upper-case atom the valence
+ *   table above on bo(a) (an upper-case atom has none of the new aromatic bonds, so bo is the same on the output), for a new c
+ *   3 - deg, for a new n, o, s 0. Otherwise a bracket atom exactly as mnx_smiles_pack spells one: '[', isotope, element, 'H' and
+ *   a count above 1, the sign and a count above 1, ']'; 12 bytes at most. An atom class ([C:12]) is dropped, as the writers drop it.
+ * Examples (strings as mnx_smiles_read reads and mnx_smiles_pack writes them): C1=CC=CC=C1 -> c1ccccc1. N1C=CC=C1 -> [nH]1cccc1.
+ *   CN1C=CC=C1 -> Cn1cccc1. C1=CN=CN1 -> c1cnc[nH]1. O=C1C=CC=CN1 -> O=c1cccc[nH]1. [CH-]1C=CC=C1 -> [cH-]1cccc1. Both Kekule
+ *   forms of naphthalene -> c1ccc2ccccc2c1 (the fused atoms count their double bond in the other ring). C1=CC=CC=C1C1=CC=CC=C1 ->
+ *   c1ccccc1-c1ccccc1. NOT aromatic: C1=CC=CCC1, C1=CC=CC1 (a CH2 is no candidate), O=C1C=CC(=O)C=C1 (4 electrons), C=C1C=CC=C1
+ *   (the exocyclic double bond goes to C). Brackets: C[CH](C)F -> CC(C)F, [CH3][CH2][OH] -> CCO; [CH2]C, [13CH4], [NH4+], [C] and
+ *   [C@H] stay. The de-marked [CH] that mnx_smiles_pack_symmetric writes is normalised only when that string is read back in.
+ * KNOWN LIMITS:
+ *   only rings of 5 and 6 atoms are examined: azulene, tropylium and cyclooctatetraene dianion stay Kekule;
+ *   a ring that holds a lower-case atom or a class-4 bond is not examined: a half-aromatic fused prediction stays as it came;
+ *   the other direction is not built: an aromatic input is never kekulised, so the normal form of a molecule is the aromatic one
+ *     only where this rule finds it;
+ *   an explicit [H] atom is an atom like any other and is not folded into a count;
+ *   the output is a fixed point of the call on everything tested (a second call changes no table), with one corner that is known
+ *     and was not met: a C whose exocyclic double bond goes to an N on a fused enumerated ring that fails while it holds an atom of
+ *     an aromatic ring counts 1 the first time and 0 the second, when that fused ring is no longer enumerated;
+ *   the H count noted for a copied atom is its written one: an atom this call wrote as a plain c notes 0 when it is copied later.
+ *
+ * Output. mols_out[b]: n_atoms and n_bonds of the input, smiles_len the length of the new text, which is the atoms' new symbols
+ * behind one another in atom order (as mnx_expand_pack's: NO token SMILES); flags = bit 0 copied | MNX_MOL_AROMATIZED (an atom
+ * became aromatic) | MNX_MOL_UNBRACKETED (a bracket atom lost its brackets); the MNX_MOL_EXPAND* bits of the input are not
+ * copied. An atom record keeps index, x_bin, y_bin and score; a bond record i, j and score; overall_score is copied.
+ * MNX_MOL_NORMALIZE_REFUSED: the molecule's records point beyond the tables passed (atom0 + n_atoms, bond0 + n_bonds or text0 +
+ * smiles_len beyond the sizes passed, a symbol beyond n_text_bytes, a bond whose i or j is no atom of the molecule), or it has
+ * more than 999 atoms or bonds (the writers' limit). A refused molecule has n_atoms = n_bonds = smiles_len = 0 in mols_out.
+ * atom_notes uint8 [atom_cap] (may be null): for output atom atom0 + k, bits 0-3 its H count (written for a bracket atom,
+ * inferred otherwise; 0 for a copied atom that is no bracket atom), MNX_NOTE_AROMATIZED: made aromatic by this call,
+ * MNX_NOTE_UNBRACKETED: its brackets were removed, MNX_NOTE_COPIED: the symbol was copied uninterpreted.
+ * Inputs as mnx_expand_pack's: mols [n], 1 <= n <= 65536; atoms [n_atom_records], bonds [n_bond_records] (8-byte aligned), text
+ * [n_text_bytes]. mnx_set_symbol_tables must have been called. Outputs, device pointers the caller allocated, with the sizing
+ * protocol of mnx_expand_pack: totals uint32 [4] = {atoms, bonds, text bytes needed, 1 if any capacity was too small}; when a
+ * capacity is too small nothing is written beyond it (atom_notes follows atom_cap), and mols_out and totals are complete all the
+ * same. Deterministic word for word: every position comes from a prefix scan, and the atomics of the kernel only count, add up
+ * and set bits of sets. Records are written whole, padding bytes as zeros. Three launches, asynchronous on `stream`, no
+ * allocation, no host synchronisation.
+ * MNX_ERR_INVALID_ARG (with mnx_last_error, "mnx_normalize_pack: ..."): a null pointer (a table with capacity 0 may be null), n
+ * outside 1..65536, misaligned records, or no symbol tables set; nothing is launched then. */
+#define MNX_MOL_AROMATIZED 16u
+#define MNX_MOL_UNBRACKETED 32u
+#define MNX_MOL_NORMALIZE_REFUSED 64u
+#define MNX_NOTE_H_MASK 15u
+#define MNX_NOTE_AROMATIZED 16u
+#define MNX_NOTE_UNBRACKETED 32u
+#define MNX_NOTE_COPIED 64u
+int mnx_normalize_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
+                       const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_mol* mols_out,
+                       mnx_atom* atoms_out, uint32_t atom_cap, mnx_bond* bonds_out, uint32_t bond_cap, char* text_out,
+                       uint32_t text_cap, uint8_t* atom_notes, uint32_t* totals, void* stream);
+
 /* SMILES text read into the packed molecule tables, on the device: the inverse of mnx_smiles_pack. Strings in, mnx_mol / mnx_atom /
  * mnx_bond records and a text arena out, as mnx_graph_pack writes them, so that mnx_smiles_pack_canonical, mnx_expand_pack,
  * mnx_molfile_pack and the other writers run on a caller's own molecules unchanged: a gold column or a list of known compounds gets
  * the same canonical string as a prediction of the same graph. NO toolkit has parsed or produced any of these strings: this reader
  * and the writers are each other's check, no more. The grammar is the OpenSMILES one without its stereo and without '~' and '$'; a
  * bracket atom's bytes are COPIED, not interpreted (interpretation stays with the writers, which need mnx_set_symbol_tables; this
- * call needs no tables). No kekulisation, no hydrogen counting, no normalisation of [CH] against C.
+ * call needs no tables). No kekulisation, no hydrogen counting, no normalisation of [CH] against C here: aromatic rings, hydrogen
+ * counts and brackets are mnx_normalize_pack's, behind this call.
  *
  * String b is bytes[offsets[b] .. offsets[b+1]). The rule, on the bytes of one string, positions counted from its first byte:
  * Brackets. A byte other than '[' and ']' is INSIDE when the nearest bracket in front of it is a '['. A '[' must be followed, as its

@@ -255,6 +255,11 @@ struct FragView {                       // passed to kernels by value
 // as packed tables of the same record types (mnx_expand_pack): count, scan and fill, three launches on s
 hipError_t expand_pack_enqueue(const SymbolTables* st_dev, const FragView& fv, const PackedTables& t, const TablesOut& o,
                                unsigned short* origin, unsigned* totals, hipStream_t s);
+// normalize.hip: the molecules of t with one normal spelling per atom — aromatic rings perceived, hydrogens counted, brackets
+// dropped where a reader infers them — as packed tables of the same record types (mnx_normalize_pack): count, scan and fill,
+// three launches on s; atom_notes (may be null) receives one byte per output atom
+hipError_t normalize_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, const TablesOut& o, unsigned char* atom_notes,
+                                  unsigned* totals, hipStream_t s);
 // smiles_read.hip: string b = bytes[offsets[b] .. offsets[b + 1]) read as SMILES into packed tables of mnx_graph_pack's record types
 // (mnx_smiles_read): count, scan and fill, three launches on s
 hipError_t smiles_read_enqueue(const unsigned char* bytes, unsigned n_bytes, const unsigned* offsets, int n, mnx_read* recs,

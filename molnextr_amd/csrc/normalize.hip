@@ -1,0 +1,365 @@
+// normalize.hip — one normal spelling per atom on the packed molecule tables (mnx_normalize_pack): aromatic rings perceived from
+// Kekule drawings, hydrogens counted, brackets dropped where a reader infers what they say. Packed tables in, packed tables of
+// the same record types out, atom and bond counts and order unchanged, so that every writer, the canonical ranks and
+// mnx_expand_pack run on the result as they are. The rule stands in include/molnextr_hip.h: it is this library's own and not a
+// toolkit's aromaticity model.
+//   count  one workgroup per molecule: the whole perception, the bytes of the new text -> mols_out[b]
+//   scan   exclusive scan of the three counts over the molecules -> atom0 / bond0 / text0, totals (tables_out.h)
+//   fill   one workgroup per molecule: the perception again, the records behind those offsets
+// Inside a workgroup: the atoms' interpretation (atom_symbol.h), then per atom its bond count, bond order sum and the first three
+// of its bonds in LDS (a candidate atom has at most three, so a graph of any density costs one pass over its bond records and
+// nothing that grows with a degree), then one thread per start atom walks the rings of 5 and 6 candidate atoms that begin at it
+// — twice: once to mark the bonds and atoms that lie on such a ring, once to judge every ring —, then every atom's new symbol,
+// placed by a prefix scan. LDS atomics count, add up, hand out the slots of a list that is sorted afterwards and set bits of
+// sets: no atomic decides a position, an order or a result. Every loop has a bound known at compile time or is a stride over
+// the molecule's records.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/molnextr_hip.h"
+#include "atom_symbol.h"
+#include "dec_types.h"
+#include "tables_out.h"
+
+namespace mnx {
+namespace {
+
+constexpr int NZ_THREADS = 256;
+constexpr int NZ_MAX = 1024;             // atoms held in LDS (999 at most)
+constexpr int NZ_PER = NZ_MAX / NZ_THREADS;
+constexpr unsigned NZ_NONE = 0xFFFFFFFFu;
+constexpr int NZ_WALK_STEPS = 384;       // 1 + 3 + 6 + 12 + 24 + 48 = 94 atoms on the walks from one start, four steps each
+
+// ---- one of an atom's first three bonds: bits 0-9 the neighbour, bits 10-11 the order (1..3), bits 12-21 the bond record ----
+__device__ __forceinline__ unsigned slot_nbr(unsigned e) { return e & 1023u; }
+__device__ __forceinline__ unsigned slot_order(unsigned e) { return e >> 10 & 3u; }
+__device__ __forceinline__ unsigned slot_bond(unsigned e) { return e >> 12 & 1023u; }
+
+// ---- an atom's state word ----
+//   bits 0-3 H count, bits 4-5 candidate kind (0 none, 1 (d), 2 (p), 3 (e)), bits 6-7 the slot of a (d) atom's double bond,
+//   bit 8 copied uninterpreted, bit 9 excluded by one of its bonds (set by the bond loop), bits 10-12 slot q is a ring-system bond,
+//   bit 13 the atom lies on an enumerated ring, bit 14 made aromatic, bits 15-17 slot q is a bond of an aromatic ring,
+//   bit 18 the symbol is copied although the atom is interpreted (the four chiral carbons)
+constexpr unsigned ST_KIND = 4, ST_DSLOT = 6, ST_COPY = 1u << 8, ST_EXCLUDED = 1u << 9, ST_RSB = 10, ST_ONRING = 1u << 13;
+constexpr unsigned ST_AROMATIC = 1u << 14, ST_AB = 15, ST_KEEP = 1u << 18;
+constexpr unsigned KIND_D = 1, KIND_P = 2, KIND_E = 3;
+__device__ __forceinline__ unsigned st_h(unsigned s) { return s & 15u; }
+__device__ __forceinline__ unsigned st_kind(unsigned s) { return s >> ST_KIND & 3u; }
+__device__ __forceinline__ unsigned st_dslot(unsigned s) { return s >> ST_DSLOT & 3u; }
+
+// the element of an interpreted atom as one number: its two bytes (atom_symbol.h: capitalised, a blank behind one letter)
+constexpr unsigned EL(char a, char b = ' ') { return (unsigned)(unsigned char)a | (unsigned)(unsigned char)b << 8; }
+__device__ __forceinline__ bool is_organic(unsigned el) {
+    return el == EL('B') || el == EL('C') || el == EL('N') || el == EL('O') || el == EL('P') || el == EL('S') || el == EL('F') ||
+           el == EL('C', 'l') || el == EL('B', 'r') || el == EL('I');
+}
+// the hydrogens a reader infers at an unbracketed upper-case atom with bond order sum bo: v - bo for the smallest normal
+// valence v >= bo, 0 when there is none
+__device__ __forceinline__ unsigned implicit_h(unsigned el, unsigned bo) {
+    unsigned v1, v2 = 0, v3 = 0;
+    if (el == EL('B')) v1 = 3;
+    else if (el == EL('C')) v1 = 4;
+    else if (el == EL('N') || el == EL('P')) { v1 = 3; v2 = 5; }
+    else if (el == EL('O')) v1 = 2;
+    else if (el == EL('S')) { v1 = 2; v2 = 4; v3 = 6; }
+    else v1 = 1;                          // F, Cl, Br, I
+    return bo <= v1 ? v1 - bo : bo <= v2 ? v2 - bo : bo <= v3 ? v3 - bo : 0u;
+}
+
+// An interpreted atom's new symbol, byte by byte: unbracketed when a reader infers everything the brackets would say, else a
+// bracket atom as smiles.hip spells one (isotope, element, 'H', 'Hk', sign and count; 12 bytes at most). inferred: the H count a
+// reader takes for the unbracketed spelling. Returns whether it was written without brackets.
+template <typename Put>
+__device__ __forceinline__ bool spell_atom(unsigned el, bool aromatic, unsigned iso, unsigned h, int q, unsigned inferred, Put put) {
+    const char e0 = (char)(el & 255u), e1 = (char)(el >> 8 & 255u);
+    const bool plain = is_organic(el) && iso == 0 && q == 0 && h == inferred;
+    if (!plain) {
+        put('[');
+        if (iso >= 100) put((char)('0' + iso / 100));
+        if (iso >= 10) put((char)('0' + iso / 10 % 10));
+        if (iso >= 1) put((char)('0' + iso % 10));
+    }
+    put(aromatic ? (char)(e0 + 32) : e0);
+    if (e1 != ' ') put(e1);
+    if (!plain) {
+        if (h >= 1) put('H');
+        if (h >= 2) put((char)('0' + h));
+        if (q != 0) {
+            const unsigned v = (unsigned)(q > 0 ? q : -q);
+            put(q > 0 ? '+' : '-');
+            if (v >= 10) put((char)('0' + v / 10));
+            if (v >= 2) put((char)('0' + v % 10));
+        }
+        put(']');
+    }
+    return plain;
+}
+
+// Every ring of 5 or 6 candidate atoms whose lowest atom is s, once: a depth-first walk from s over candidate neighbours of
+// higher index, closed when it comes back to s behind 5 or 6 atoms; of a ring's two directions the one whose second atom lies
+// below its last. The walk's atoms are 10-bit fields of `path` and the next slot to try at every depth a 2-bit field of `next`,
+// so nothing is indexed in registers. found(path, n): the ring's n atoms are fields 0 .. n - 1 of path.
+template <typename Found>
+__device__ __forceinline__ void walk_rings(unsigned s, const unsigned* st, const unsigned* nbr3, Found found) {
+    unsigned long long path = s;
+    unsigned next = 0;
+    int depth = 0;                        // the field of the walk's last atom
+    for (int step = 0; step < NZ_WALK_STEPS; ++step) {
+        const unsigned q = next >> (2 * depth) & 3u;
+        if (q == 3u) {
+            if (depth == 0) break;
+            next &= ~(3u << (2 * depth));
+            --depth;
+            continue;
+        }
+        next += 1u << (2 * depth);
+        const unsigned last = (unsigned)(path >> (10 * depth)) & 1023u;
+        const unsigned e = nbr3[3 * last + q];
+        if (e == NZ_NONE) continue;
+        const unsigned v = slot_nbr(e);
+        if (v == s) {
+            if (depth >= 4 && ((unsigned)(path >> 10) & 1023u) < last) found(path, depth + 1);
+            continue;
+        }
+        if (v < s || depth == 5 || st_kind(st[v]) == 0) continue;
+        bool seen = false;
+#pragma unroll
+        for (int d = 1; d < 6; ++d) seen |= d <= depth && ((unsigned)(path >> (10 * d)) & 1023u) == v;
+        if (seen) continue;
+        ++depth;
+        path = (path & ~(1023ull << (10 * depth))) | (unsigned long long)v << (10 * depth);
+    }
+}
+
+// the bit `base` + q of the slot q that holds atom u's bond to v (both candidates: u has at most three bonds, all to different
+// atoms); 0 when there is none
+__device__ __forceinline__ unsigned slot_bit(const unsigned* nbr3, unsigned u, unsigned v, unsigned base) {
+    unsigned bit = 0;
+#pragma unroll
+    for (unsigned q = 0; q < 3; ++q) {
+        const unsigned e = nbr3[3 * u + q];
+        if (e != NZ_NONE && slot_nbr(e) == v) bit = 1u << (base + q);
+    }
+    return bit;
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(NZ_THREADS) void normalize_kernel(
+        const PackedTables t, const SymbolTables* __restrict__ stab, const TablesOut o, unsigned char* __restrict__ notes) {
+    __shared__ unsigned info[NZ_MAX], elem[NZ_MAX];
+    __shared__ unsigned cnt[NZ_MAX];      // bond records at the atom: hands out the slots of nbr3
+    __shared__ unsigned acc[NZ_MAX];      // bits 0-11 bond order sum, bits 12-21 double bonds, bits 22-31 triple bonds
+    __shared__ unsigned st[NZ_MAX];
+    __shared__ unsigned nbr3[3 * NZ_MAX];
+    __shared__ unsigned scan[2 * NZ_THREADS];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const Molecule mol = admit_molecule(t, b);
+    const mnx_mol& m = mol.m;
+    auto record = [&](unsigned n_atoms, unsigned n_bonds, unsigned text_len, unsigned flags) {      // count's result
+        if (tid == 0) store_mol_counts(&o.mols[b], n_atoms, n_bonds, text_len, flags | (m.flags & MNX_MOL_TRUNCATED), m.overall_score);
+    };
+    mnx_mol mo;
+    if (FILL) {
+        mo = o.mols[b];
+        if (mo.flags & MNX_MOL_NORMALIZE_REFUSED) return;   // refused by count (the same for every thread)
+    } else if (mol.flags & (PT_BEYOND_TABLES | PT_TOO_LARGE)) {
+        record(0, 0, 0, MNX_MOL_NORMALIZE_REFUSED);
+        return;
+    }
+    const int na = (int)m.n_atoms, nb = (int)m.n_bonds;
+    const unsigned long long* A = (const unsigned long long*)mol.A;
+    const unsigned long long* B = (const unsigned long long*)mol.B;
+
+    // ---- the atoms as the writers read them; per atom its bond count, order sum and first three bonds ----
+    int bad = interpret_atoms<NZ_MAX, NZ_THREADS>(t, stab, mol, info, elem);
+    for (int a = tid; a < NZ_MAX; a += NZ_THREADS) {
+        cnt[a] = 0; acc[a] = 0; st[a] = 0;
+        nbr3[3 * a] = nbr3[3 * a + 1] = nbr3[3 * a + 2] = NZ_NONE;
+    }
+    __syncthreads();
+    for (int k = tid; k < nb; k += NZ_THREADS) {
+        const unsigned w = (unsigned)B[2 * (size_t)k], i = w & 0xffffu, j = w >> 16, ty = (unsigned)(B[2 * (size_t)k] >> 32) & 0xffu;
+        if (i >= (unsigned)na || j >= (unsigned)na) { bad = 1; continue; }
+        const unsigned order = (ty == 1 || ty == 5 || ty == 6) ? 1u : (ty == 2 || ty == 3) ? ty : 0u;
+        if (order == 0 || i == j) {       // class 4, no class of a bond, or a bond from an atom to itself: both ends are copied
+            atomicOr(&st[i], ST_EXCLUDED);
+            atomicOr(&st[j], ST_EXCLUDED);
+            continue;
+        }
+        const unsigned add = order | (order == 2 ? 1u << 12 : 0u) | (order == 3 ? 1u << 22 : 0u);
+        const unsigned si = atomicAdd(&cnt[i], 1u), sj = atomicAdd(&cnt[j], 1u);    // any slot: the three are sorted below
+        if (si < 3) nbr3[3 * i + si] = j | order << 10 | (unsigned)k << 12;
+        if (sj < 3) nbr3[3 * j + sj] = i | order << 10 | (unsigned)k << 12;
+        atomicAdd(&acc[i], add);          // sums and counts do not depend on the order of their terms
+        atomicAdd(&acc[j], add);
+    }
+    bad = __syncthreads_or(bad);
+    if (!FILL && bad) {                   // a symbol beyond the text or a bond that is no bond of the molecule
+        record(0, 0, 0, MNX_MOL_NORMALIZE_REFUSED);
+        return;
+    }
+
+    // ---- every atom: hydrogens, whether it is a candidate and of which kind; its three slots in ascending order ----
+    for (int a = tid; a < na; a += NZ_THREADS) {
+        const unsigned w = info[a], el = elem[a] & 0xffffu, deg = cnt[a];
+        const unsigned bo = acc[a] & 4095u, n_double = acc[a] >> 12 & 1023u, n_triple = acc[a] >> 22;
+        unsigned e0 = nbr3[3 * a], e1 = nbr3[3 * a + 1], e2 = nbr3[3 * a + 2], x;
+        if (e0 > e1) { x = e0; e0 = e1; e1 = x; }
+        if (e1 > e2) { x = e1; e1 = e2; e2 = x; }
+        if (e0 > e1) { x = e0; e0 = e1; e1 = x; }
+        nbr3[3 * a] = e0; nbr3[3 * a + 1] = e1; nbr3[3 * a + 2] = e2;
+        unsigned s = st[a] & ST_EXCLUDED;
+        if (info_cls(w) != CLS_ATOM || info_aromatic(w) || el == EL('R') || s) {
+            st[a] = s | ST_COPY | (info_cls(w) == CLS_ATOM ? (unsigned)info_h(w) : 0u);
+            continue;
+        }
+        const bool bracket = (w & 4u) != 0, chiral = (w & 8u) != 0;
+        const unsigned h = bracket ? (unsigned)info_h(w) : implicit_h(el, bo);
+        const int q = info_charge(w);
+        s = h | (chiral ? ST_KEEP : 0u);
+        const bool c = el == EL('C'), n = el == EL('N'), os = el == EL('O') || el == EL('S');
+        bool distinct = true;             // two bond records to one neighbour: no candidate
+        if (deg >= 2) distinct = slot_nbr(e0) != slot_nbr(e1);
+        if (deg == 3) distinct = distinct && slot_nbr(e1) != slot_nbr(e2) && slot_nbr(e0) != slot_nbr(e2);
+        if ((c || n || os) && !chiral && deg <= 3 && n_triple == 0 && distinct) {
+            if (n_double == 1 && ((c && q == 0) || (n && (q == 0 || q == 1)))) {
+                const unsigned ds = slot_order(e0) == 2 ? 0u : slot_order(e1) == 2 ? 1u : 2u;
+                s |= KIND_D << ST_KIND | ds << ST_DSLOT;
+            } else if (n_double == 0 && ((n && q == 0 && deg + h == 3) || (os && q == 0 && deg == 2 && h == 0) ||
+                                         (c && q == -1 && deg + h == 3))) {
+                s |= KIND_P << ST_KIND;
+            } else if (n_double == 0 && c && q == 1) {
+                s |= KIND_E << ST_KIND;
+            }
+        }
+        st[a] = s;
+    }
+    __syncthreads();
+
+    // ---- the enumerated rings, first pass: which bonds are ring-system bonds, which atoms lie on an enumerated ring ----
+    for (int a = tid; a < na; a += NZ_THREADS) {
+        if (st_kind(st[a]) == 0) continue;
+        walk_rings((unsigned)a, st, nbr3, [&](unsigned long long path, int n) {
+#pragma unroll
+            for (int d = 0; d < 6; ++d) {
+                if (d >= n) continue;
+                const unsigned u = (unsigned)(path >> (10 * d)) & 1023u;
+                const unsigned v = (unsigned)(path >> (10 * (d + 1 == n ? 0 : d + 1))) & 1023u;
+                atomicOr(&st[u], ST_ONRING | slot_bit(nbr3, u, v, ST_RSB));
+                atomicOr(&st[v], slot_bit(nbr3, v, u, ST_RSB));
+            }
+        });
+    }
+    __syncthreads();
+    // ---- second pass: every ring's electrons; the atoms and bonds of a ring with 6 become aromatic. The verdict bits (14-17)
+    //      are written here and read by no walk, so the verdicts do not depend on one another ----
+    for (int a = tid; a < na; a += NZ_THREADS) {
+        if (st_kind(st[a]) == 0) continue;
+        walk_rings((unsigned)a, st, nbr3, [&](unsigned long long path, int n) {
+            unsigned electrons = 0;
+            bool fails = false;
+#pragma unroll
+            for (int d = 0; d < 6; ++d) {
+                if (d >= n) continue;
+                const unsigned u = (unsigned)(path >> (10 * d)) & 1023u, su = st[u], kind = st_kind(su);
+                if (kind == KIND_P) electrons += 2;
+                else if (kind == KIND_D) {
+                    const unsigned ds = st_dslot(su);
+                    if (su >> (ST_RSB + ds) & 1u) electrons += 1;
+                    else {
+                        const unsigned x = slot_nbr(nbr3[3 * u + ds]), ex = elem[x] & 0xffffu;
+                        const bool hetero = info_cls(info[x]) == CLS_ATOM && (ex == EL('O') || ex == EL('N') || ex == EL('S'));
+                        if (!((elem[u] & 0xffffu) == EL('C') && hetero && !(st[x] & ST_ONRING))) fails = true;
+                    }
+                }
+            }
+            if (fails || electrons != 6) return;
+#pragma unroll
+            for (int d = 0; d < 6; ++d) {
+                if (d >= n) continue;
+                const unsigned u = (unsigned)(path >> (10 * d)) & 1023u;
+                const unsigned v = (unsigned)(path >> (10 * (d + 1 == n ? 0 : d + 1))) & 1023u;
+                atomicOr(&st[u], ST_AROMATIC | slot_bit(nbr3, u, v, ST_AB));
+                atomicOr(&st[v], slot_bit(nbr3, v, u, ST_AB));
+            }
+        });
+    }
+    __syncthreads();
+
+    // ---- every atom's new symbol: NZ_PER neighbouring atoms per thread, placed by a prefix scan over their lengths ----
+    const unsigned char* text_in = t.text + m.text0;
+    unsigned long long sym8[NZ_PER];      // a respelled symbol's bytes 0-7 (the first in the low byte) and 8-11
+    unsigned sym4[NZ_PER], len[NZ_PER], note[NZ_PER], sum = 0;
+    int any_aromatic = 0, any_plain = 0;
+#pragma unroll
+    for (int q = 0; q < NZ_PER; ++q) {
+        const int a = NZ_PER * tid + q;
+        sym8[q] = 0; sym4[q] = 0; len[q] = 0; note[q] = 0;
+        if (a >= na) continue;
+        const unsigned s = st[a], w = info[a];
+        note[q] = st_h(s);
+        if (s & ST_COPY) note[q] |= 64u;
+        if (s & (ST_COPY | ST_KEEP)) { len[q] = (unsigned)(A[3 * (size_t)a] >> 32) & 0xffffu; sum += len[q]; continue; }
+        const unsigned el = elem[a] & 0xffffu, deg = cnt[a], bo = acc[a] & 4095u;
+        const bool aromatic = (s & ST_AROMATIC) != 0;
+        const unsigned inferred = !aromatic ? implicit_h(el, bo) : el == EL('C') ? (deg <= 3 ? 3 - deg : 0u) : 0u;
+        unsigned n = 0;
+        unsigned long long lo = 0;
+        unsigned hi = 0;
+        const bool plain = spell_atom(el, aromatic, info_num(w), st_h(s), info_charge(w), inferred, [&](char c) {
+            if (n < 8u) lo |= (unsigned long long)(unsigned char)c << (8u * n);
+            else if (n < 12u) hi |= (unsigned)(unsigned char)c << (8u * (n - 8u));
+            ++n;
+        });
+        sym8[q] = lo; sym4[q] = hi; len[q] = n; sum += n;
+        if (aromatic) { note[q] |= 16u; any_aromatic = 1; }
+        if (plain && (w & 4u)) { note[q] |= 32u; any_plain = 1; }
+    }
+    unsigned total;
+    unsigned at = block_scan_excl<NZ_THREADS>(sum, scan, &total);
+    if (!FILL) {
+        any_aromatic = __syncthreads_or(any_aromatic);
+        any_plain = __syncthreads_or(any_plain);
+        record((unsigned)na, (unsigned)nb, total, (any_aromatic ? MNX_MOL_AROMATIZED : 0u) | (any_plain ? MNX_MOL_UNBRACKETED : 0u));
+        return;
+    }
+#pragma unroll
+    for (int q = 0; q < NZ_PER; ++q) {
+        const int a = NZ_PER * tid + q;
+        if (a >= na) continue;
+        const unsigned long long w0 = A[3 * (size_t)a], w1 = A[3 * (size_t)a + 1], w2 = A[3 * (size_t)a + 2];
+        const unsigned long long rec = (unsigned long long)mo.atom0 + (unsigned)a, to = (unsigned long long)mo.text0 + at;
+        if (put_atom(o, rec, atom_word0(at, len[q], 0u) | (w0 & ATOM_INDEX_BITS), w1 & ATOM_BINS_BITS, w2) && notes)
+            notes[rec] = (unsigned char)note[q];
+        if (st[a] & (ST_COPY | ST_KEEP)) put_text(o, to, text_in + (unsigned)w0, len[q]);
+        else
+            for (unsigned c = 0; c < len[q]; ++c)
+                if (to + c < o.text_cap) o.text[to + c] = (char)(c < 8u ? sym8[q] >> (8u * c) : (unsigned long long)(sym4[q] >> (8u * (c - 8u))));
+        at += len[q];
+    }
+    // ---- the bonds: type = rev = 4 on an aromatic ring, every other record as it is ----
+    for (int k = tid; k < nb; k += NZ_THREADS) {
+        unsigned long long w0 = B[2 * (size_t)k] & BOND_FIELD_BITS;
+        const unsigned i = (unsigned)w0 & 0xffffu, si = st[i];
+        bool aromatic = false;
+#pragma unroll
+        for (unsigned q = 0; q < 3; ++q) {
+            const unsigned e = nbr3[3 * i + q];
+            aromatic |= e != NZ_NONE && slot_bond(e) == (unsigned)k && (si >> (ST_AB + q) & 1u);
+        }
+        if (aromatic) w0 = (w0 & 0xffffffffull) | 4ull << 32 | 4ull << 40;
+        put_bond(o, (unsigned long long)mo.bond0 + (unsigned)k, w0, B[2 * (size_t)k + 1]);
+    }
+}
+
+}  // namespace
+
+hipError_t normalize_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, const TablesOut& o, unsigned char* atom_notes,
+                                  unsigned* totals, hipStream_t s) {
+    hipLaunchKernelGGL(normalize_kernel<false>, dim3(t.n), dim3(NZ_THREADS), 0, s, t, st_dev, o, atom_notes);
+    hipLaunchKernelGGL(mol_scan_kernel, dim3(1), dim3(MOL_SCAN_THREADS), 0, s, o, t.n, totals);
+    hipLaunchKernelGGL(normalize_kernel<true>, dim3(t.n), dim3(NZ_THREADS), 0, s, t, st_dev, o, atom_notes);
+    return hipGetLastError();
+}
+
+}  // namespace mnx

@@ -29,7 +29,7 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
            "mnx_layernorm16", "mnx_merge_ln16", "mnx_cast16", "mnx_sgemm_tn", "mnx_set_vocab_text", "mnx_graph_pack",
            "mnx_set_symbol_tables", "mnx_molfile_pack", "mnx_smiles_pack", "mnx_smiles_pack_stereo",
            "mnx_smiles_pack_marks", "mnx_smiles_pack_canonical", "mnx_smiles_pack_symmetric", "mnx_set_fragments", "mnx_expand_pack", "mnx_smiles_read",
-           "mnx_beam_scripted", "mnx_edge_probs")
+           "mnx_beam_scripted", "mnx_edge_probs", "mnx_normalize_pack")
 
 # Encoder operand modes (include/molnextr_hip.h MNX_DTYPE_*). "fp16x3" — split fp16 operands, three MFMA terms per
 # product, fp32-class results — is the default: it is the fastest mode whose results stay a factor of four inside north_star's
@@ -117,6 +117,11 @@ MOL_TRUNCATED = 1                       # mnx_mol.flags bit 0: more atoms than k
 # mnx_mol.flags of mnx_expand_pack's output (MNX_MOL_EXPAND*): a label was replaced by its fragment; a pseudo-atom other than a
 # parsed '*' remains; the molecule was refused (records beyond the tables, bonds not sorted by i, more than 2047 atoms): no records
 MOL_EXPANDED, MOL_LABEL_LEFT, MOL_EXPAND_REFUSED = 2, 4, 8
+# mnx_mol.flags of mnx_normalize_pack's output: an atom became aromatic; a bracket atom lost its brackets; the molecule was refused
+# (records beyond the tables, more than 999 atoms or bonds): no records. The bits of its `atom_notes`: the H count, made aromatic
+# by the call, brackets removed, the symbol copied uninterpreted
+MOL_AROMATIZED, MOL_UNBRACKETED, MOL_NORMALIZE_REFUSED = 16, 32, 64
+NOTE_H_MASK, NOTE_AROMATIZED, NOTE_UNBRACKETED, NOTE_COPIED = 15, 16, 32, 64
 MOLFILE_DTYPE = np.dtype([("text0", "<u4"), ("len", "<u4"), ("flags", "<u4"), ("reserved", "<u4")], align=True)
 # mnx_molfile.flags (MNX_MOLFILE_*): no molfile (len 0) for more than 999 atoms / bonds or records beyond the tables passed;
 # the molecule holds a pseudo-atom (R-group, abbreviation, unparsable symbol); a copy of MOL_TRUNCATED
@@ -295,6 +300,8 @@ def load_library():
     lib.mnx_expand_pack.restype = C.c_int
     lib.mnx_expand_pack.argtypes = [vp, vp, i32, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint32, vp, C.c_uint32,
                                     vp, C.c_uint32, vp, vp, vp]
+    lib.mnx_normalize_pack.restype = C.c_int
+    lib.mnx_normalize_pack.argtypes = lib.mnx_expand_pack.argtypes      # atom_notes in the place of origin
     lib.mnx_smiles_read.restype = C.c_int
     lib.mnx_smiles_read.argtypes = [vp, vp, C.c_uint32, vp, i32, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp]
     lib.mnx_atom_scan.restype = C.c_int
@@ -1087,6 +1094,31 @@ class Engine:
 
         out = self._sized_tables("mnx_expand_pack", n, caps, call, dev, keep_device)
         out["origin"] = origin[0][:len(out["atoms"])].cpu().numpy().view(np.uint16)
+        return out
+
+    def normalize_pack(self, rec: dict, caps=None, keep_device: bool = False) -> dict:
+        """graph_pack's records (or expand_pack's, or smiles_read's) -> the same molecules with one normal spelling per atom
+        (mnx_normalize_pack; the rule: include/molnextr_hip.h — this library's own, NOT a toolkit's aromaticity model): rings of 5
+        and 6 atoms that the rule finds aromatic get lower-case atoms and class-4 bonds, a bracket atom that says no more than a
+        reader infers loses its brackets, everything else is respelled as the writers spell it. A dict with graph_pack's keys —
+        'mols', 'atoms', 'bonds', 'text', 'totals' — plus 'atom_notes' uint8 [atoms]: NOTE_H_MASK the atom's H count,
+        NOTE_AROMATIZED / NOTE_UNBRACKETED / NOTE_COPIED. Atom and bond counts and order are the input's; mols['flags'] carries
+        MOL_AROMATIZED / MOL_UNBRACKETED / MOL_NORMALIZE_REFUSED. Starts from the input's sizes (a new symbol is rarely longer
+        than the old one; or caps = (atom_cap, bond_cap, text_cap)) and repeats at most once with the sizes `totals` reports.
+        keep_device: also 'device', as graph_pack."""
+        dev = torch.device("cuda", self.device)
+        n = len(rec["mols"])
+        tables, args = self._packed_tables(rec)
+        if caps is None:
+            caps = (len(rec["atoms"]), len(rec["bonds"]), len(rec["text"]) + 2 * n)
+        notes = []              # per atom: one per attempt, of the attempt's atom capacity
+
+        def call(mols, arenas, totals):
+            notes[:] = [torch.empty(max(arenas[1], 1), dtype=torch.uint8, device=dev)]
+            return self.lib.mnx_normalize_pack(self.h, *args, mols, *arenas, _ptr(notes[0]), totals, _stream())
+
+        out = self._sized_tables("mnx_normalize_pack", n, caps, call, dev, keep_device)
+        out["atom_notes"] = notes[0][:len(out["atoms"])].cpu().numpy()
         return out
 
     def smiles_read(self, strings, caps=None, keep_device: bool = False) -> dict:

@@ -209,12 +209,17 @@ def write_predictions(save_path: str, file_name: str, table: Dict[str, list], sc
     return out_csv
 
 
-def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: int = 512) -> Dict[str, float]:
+def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: int = 512, normalize: bool = False) -> Dict[str, float]:
     """--graph_match: the share of items whose prediction and gold string are the same graph as THIS library's canonical SMILES
     sees it (marks 0: no stereo), on the device. records: the gathered dense records in dataset order (shard.pack_records
     layout), re-uploaded in chunks -> graph_pack -> mnx_smiles_pack_canonical; gold -> mnx_smiles_read -> the same writer. A
     refused side is a mismatch. NOT the reference's RDKit `graph` score: nothing normalises [CH] against C, nothing kekulises,
-    stereo is dropped, and the canonical ranks keep the limit DESIGN 4.15 states."""
+    stereo is dropped, and the canonical ranks keep the limit DESIGN 4.15 states.
+    normalize (--graph_normalize): adds graph_match_normalized, the same comparison with BOTH sides passed through
+    mnx_normalize_pack first (this library's own aromaticity and bracket rule), so that a gold string in Kekule form
+    or with [CH] spelled out equals an aromatic prediction of the same graph. graph_match_device is what it is without the
+    flag. Still NOT the reference's RDKit `graph` score: the rule is not RDKit's model, nothing kekulises, rings of other sizes
+    than 5 and 6 stay as drawn, stereo is dropped."""
     from .engine import READ_REFUSED, SMILES_REFUSED
     from .shard import MAX_LEN
     kmax = engine.max_atoms
@@ -226,7 +231,7 @@ def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: 
         recs, _, data, _, _ = engine.smiles_pack(rec, canonical=True)
         return [None if int(r["flags"]) & SMILES_REFUSED else data[int(r["text0"]):int(r["text0"]) + int(r["len"])] for r in recs]
 
-    equal = unreadable = refused = 0
+    equal = equal_normalized = unreadable = refused = 0
     for c0 in range(0, len(gold), chunk):
         rows = torch.from_numpy(np.ascontiguousarray(records[c0:c0 + chunk])).to(dev)
         n = rows.shape[0]
@@ -234,7 +239,8 @@ def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: 
         out = {"lengths": rows[:, 0].contiguous(), "n_atoms": rows[:, 1].contiguous(), "tokens": rows[:, 2:2 + MAX_LEN].contiguous(),
                "atom_idx": rows[:, 2 + MAX_LEN:2 + MAX_LEN + kmax].contiguous(),
                "edges": e32.view(torch.uint8)[:, :kmax * kmax].reshape(n, kmax, kmax).contiguous()}
-        pred = texts(engine.graph_pack(out, keep_device=True))
+        packed = engine.graph_pack(out, keep_device=True)
+        pred = texts(packed)
         read = engine.smiles_read(gold[c0:c0 + chunk], keep_device=True)
         want = texts(read)
         for p, w, r in zip(pred, want, read["read"]):
@@ -242,7 +248,15 @@ def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: 
             unreadable += bad
             refused += p is None
             equal += (not bad) and p is not None and w is not None and p == w
-    return {"graph_match_device": equal / len(gold) if gold else 0.0, "gold_unreadable": int(unreadable), "pred_refused": int(refused)}
+        if normalize:
+            pred = texts(engine.normalize_pack(packed, keep_device=True))
+            want = texts(engine.normalize_pack(read, keep_device=True))
+            for p, w, r in zip(pred, want, read["read"]):
+                equal_normalized += not int(r["flags"]) & READ_REFUSED and p is not None and w is not None and p == w
+    scores = {"graph_match_device": equal / len(gold) if gold else 0.0, "gold_unreadable": int(unreadable), "pred_refused": int(refused)}
+    if normalize:
+        scores["graph_match_normalized"] = equal_normalized / len(gold) if gold else 0.0
+    return scores
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -276,6 +290,11 @@ def build_parser() -> argparse.ArgumentParser:
                          "on the device and compared as strings; a refused side counts as a mismatch. This is NOT the reference's RDKit "
                          "`graph` score: no normalisation of [CH] against C, no kekulisation, no stereo, and the canonical ranks have "
                          "the known limit of DESIGN 4.15; no toolkit has parsed either string")
+    ap.add_argument("--graph_normalize", action="store_true",
+                    help="opt-in, with --graph_match: add graph_match_normalized, the same comparison with both sides passed through "
+                         "mnx_normalize_pack first (aromatic rings of 5 and 6 atoms perceived from Kekule drawings, [CH] against C, N "
+                         "against [nH]: this library's own rule, DESIGN 4.19). graph_match_device stays as it is. Still NOT the "
+                         "reference's RDKit `graph` score: the rule is not RDKit's aromaticity model and no toolkit has checked it")
     return ap
 
 
@@ -289,6 +308,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if not 1 <= args.batch_size <= MAX_BATCH_SIZE:
         ap.error(f"--batch_size must be 1..{MAX_BATCH_SIZE} (reference batches of 2 x batch_size <= {2 * MAX_BATCH_SIZE} rows)")
+    if args.graph_normalize and not args.graph_match:
+        ap.error("--graph_normalize adds a score to --graph_match")
     dtype = args.dtype or ("fp16" if args.fp16 else DEFAULT_DTYPE)
     max_batch = max(64, 2 * args.batch_size)          # one reference batch is encoded in one launch group
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -337,7 +358,7 @@ def main(argv=None):
         else:
             scores = smiles_scores(df["SMILES"], table["SMILES"]) if "SMILES" in df.columns else None
             if args.graph_match:
-                scores.update(graph_match_scores(engine, kept["records"], list(df["SMILES"])))
+                scores.update(graph_match_scores(engine, kept["records"], list(df["SMILES"]), normalize=args.graph_normalize))
         print(write_predictions(args.save_path, args.test_file, table, scores), json.dumps(scores))
     if world > 1:
         dist.barrier()

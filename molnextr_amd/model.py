@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import weights as W
-from .engine import DEFAULT_DTYPE, MOL_TRUNCATED, SMILES_NO_POSITION, SMILES_REFUSED, Engine, MnxError
+from .engine import DEFAULT_DTYPE, MOL_TRUNCATED, NOTE_H_MASK, SMILES_NO_POSITION, SMILES_REFUSED, Engine, MnxError
 from .preprocess import load_image_rgb, transform_image, transform_image_gray
 from .tokenizer import coords_labels, get_tokenizer
 
@@ -143,7 +143,7 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
                      max_len: Optional[int] = None, beam_size: int = 1, compute_confidence: bool = False,
                      labels=None, free_run=False, packed: bool = False, molfile: bool = False,
                      molfile_scale=None, smiles: bool = False, stereo: bool = False, double_bonds: bool = False,
-                     canonical: bool = False, expand: bool = False, symmetry: bool = False) -> List[dict]:
+                     canonical: bool = False, expand: bool = False, symmetry: bool = False, normalize: bool = False) -> List[dict]:
     """Encoder + Decoder.decode for MANY images through the engine's continuous-batching path (mnx_predict):
     same per-image dicts as `decode_batch`, identical results (the on-device atom scan equals
     sequence_to_smiles' indices), much higher throughput. compute_confidence=True: mnx_predict_confidence, the same
@@ -187,8 +187,18 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
     predicted atom it came from), 'flags' (MOL_EXPANDED / MOL_LABEL_LEFT of engine.py)}; 'graph_smiles_order', 'canonical_rank'
     and 'symmetry_class' then have one entry per EXPANDED atom, in the order of expanded['symbols']. The predicted atoms and
     bonds ('chartok_coords', 'bonds') are what they are without it. From a table only (no condensed-formula parser), the atoms
-    of a fragment share the label's coordinates, and no toolkit has parsed the result."""
+    of a fragment share the label's coordinates, and no toolkit has parsed the result.
+    normalize (packed only; behind expand when both are set): the molecule is given one normal spelling per atom on the device
+    before anything is written (mnx_normalize_pack; the rule: the header) — rings of 5 and 6 atoms that the rule finds aromatic get
+    lower-case atoms and class-4 bonds, a bracket atom that says no more than a reader infers loses its brackets —, so a Kekule
+    drawing and an aromatic one, [CH] and C, N and [nH] get one canonical string. 'molfile' and 'graph_smiles' then describe the
+    normalised molecule, and every dict gains 'normalized' = {'symbols', 'bonds' [(i, j, type, rev[, score])], 'hydrogens' (per
+    atom: written for a bracket atom, inferred otherwise), 'notes' (the NOTE_* bits of engine.py per atom), 'flags'
+    (MOL_AROMATIZED / MOL_UNBRACKETED)}, atom for atom in the order of the expanded (or predicted) atoms. This library's own
+    rule: NOT RDKit's aromaticity model, no toolkit has checked it, nothing kekulises, rings of other sizes stay as drawn."""
     tok = (tokenizer or get_tokenizer())["chartok_coords"]
+    if normalize and not packed:
+        raise ValueError("normalize=True needs packed=True: the atoms are respelled in the packed tables")
     if expand and not packed:
         raise ValueError("expand=True needs packed=True: the labels are replaced in the packed tables")
     if molfile and not packed:
@@ -222,21 +232,32 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
             raise RuntimeError(f"a molecule has more atoms than the engine capacity max_atoms={engine.max_atoms}")
         drawn = rec                                                      # what the predicted atoms and bonds are read from
         if expand:
-            rec = engine.expand_pack(drawn, keep_device=molfile or smiles)     # what the writers read
+            rec = engine.expand_pack(drawn, keep_device=molfile or smiles or normalize)     # what the writers read
+        grown_rec = rec
+        if normalize:
+            rec = engine.normalize_pack(rec, keep_device=molfile or smiles)
         ranked = engine.smiles_pack(rec, stereo=stereo, double_bonds=double_bonds, canonical=True,
                                     **({"symmetry": True} if symmetry else {})) if canonical else None
         per_atom = {"rank": ranked[3], "sym_class": ranked[4]} if canonical else {}
         preds = unpack_graphs(drawn["mols"], drawn["atoms"], drawn["bonds"], drawn["text"], tok.maxx, compute_confidence,
                               **({} if expand else per_atom))
         if expand:
-            grown = unpack_graphs(rec["mols"], rec["atoms"], rec["bonds"], rec["text"], tok.maxx, compute_confidence, **per_atom)
-            for p, g, m in zip(preds, grown, rec["mols"]):
+            grown = unpack_graphs(grown_rec["mols"], grown_rec["atoms"], grown_rec["bonds"], grown_rec["text"], tok.maxx,
+                                  compute_confidence, **per_atom)
+            for p, g, m in zip(preds, grown, grown_rec["mols"]):
                 a0, na = int(m["atom0"]), int(m["n_atoms"])
                 p["expanded"] = {"symbols": g["chartok_coords"]["symbols"], "coords": g["chartok_coords"]["coords"],
-                                 "bonds": g["bonds"], "origin": rec["origin"][a0:a0 + na].tolist(), "flags": int(m["flags"])}
+                                 "bonds": g["bonds"], "origin": grown_rec["origin"][a0:a0 + na].tolist(), "flags": int(m["flags"])}
                 for key in ("canonical_rank", "symmetry_class"):
                     if key in g:
                         p[key] = g[key]
+        if normalize:
+            normal = unpack_graphs(rec["mols"], rec["atoms"], rec["bonds"], rec["text"], tok.maxx, compute_confidence)
+            for p, g, m in zip(preds, normal, rec["mols"]):
+                a0, na = int(m["atom0"]), int(m["n_atoms"])
+                notes = rec["atom_notes"][a0:a0 + na]
+                p["normalized"] = {"symbols": g["chartok_coords"]["symbols"], "bonds": g["bonds"],
+                                   "hydrogens": (notes & NOTE_H_MASK).tolist(), "notes": notes.tolist(), "flags": int(m["flags"])}
         if molfile:
             files, data = engine.molfile_pack(rec, scale=molfile_scale)
             for p, f in zip(preds, files):
@@ -278,12 +299,14 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
     return preds
 
 
-def canonical_smiles(engine: Engine, smiles_list, expand: bool = False) -> List[dict]:
+def canonical_smiles(engine: Engine, smiles_list, expand: bool = False, normalize: bool = False) -> List[dict]:
     """A caller's own SMILES in the form the device writes predictions in: mnx_smiles_read, optionally mnx_expand_pack ([Ph],
     [OMe], ... replaced by their atoms), then mnx_smiles_pack_canonical without marks. Per item {'smiles': the canonical string,
     None where the reader or the writer refused; 'read_flags' (engine.READ_*), 'err_pos' (of READ_SYNTAX), 'smiles_flags'
     (engine.SMILES_*)}. Equal strings mean equal graphs as this library sees them — no stereo, no kekulisation, no [CH] against
-    C; it is NOT a toolkit's canonical SMILES and never compares with one."""
+    C; it is NOT a toolkit's canonical SMILES and never compares with one. normalize: mnx_normalize_pack in front of the writer
+    (behind the expansion): aromatic rings of 5 and 6 atoms perceived from a Kekule string, [CH] against C, N against [nH] — this
+    library's own rule, not a toolkit's aromaticity model; the items gain 'normalize_flags' (engine.MOL_AROMATIZED / ...)."""
     from .engine import READ_REFUSED, SMILES_REFUSED
     smiles_list = list(smiles_list)
     if not smiles_list:
@@ -292,12 +315,16 @@ def canonical_smiles(engine: Engine, smiles_list, expand: bool = False) -> List[
     read = rec["read"]
     if expand:
         rec = engine.expand_pack(rec, keep_device=True)
+    if normalize:
+        rec = engine.normalize_pack(rec, keep_device=True)
     recs, _, data, _, _ = engine.smiles_pack(rec, canonical=True)
     out = []
-    for r, w in zip(read, recs):
+    for r, w, m in zip(read, recs, rec["mols"]):
         ok = not (int(r["flags"]) & READ_REFUSED or int(w["flags"]) & SMILES_REFUSED)
         out.append({"smiles": data[int(w["text0"]):int(w["text0"]) + int(w["len"])].decode("utf-8", "replace") if ok else None,
                     "read_flags": int(r["flags"]), "err_pos": int(r["err_pos"]), "smiles_flags": int(w["flags"])})
+        if normalize:
+            out[-1]["normalize_flags"] = int(m["flags"])
     return out
 
 
@@ -356,7 +383,12 @@ class molnextr:
     symmetry rule of mnx_smiles_pack_symmetric (a centre or double bond with two substituents of one symmetry class, both on
     bonds off every cycle, writes no mark), and every output dict gains 'stereo_atoms', the ATOM_* bits per atom (None for a
     molecule that got no string). Off for a molecule with a pseudo-atom (combine with graph_expand); the ranks ignore stereo, a
-    pair on ring bonds is never dropped, and no toolkit has parsed the result: the limits stand in include/molnextr_hip.h."""
+    pair on ring bonds is never dropped, and no toolkit has parsed the result: the limits stand in include/molnextr_hip.h.
+    graph_normalize: True (opt-in, default False; needs graph_smiles or graph_molfile; behind graph_expand) = the molecule gets one
+    normal spelling per atom before it is written (mnx_normalize_pack: aromatic rings of 5 and 6 atoms perceived from a Kekule
+    drawing, brackets dropped where a reader infers them), and every output dict gains 'hydrogens', the H count per atom (in the
+    order of expanded['symbols'] with graph_expand, of atom_sets without), and 'normalized' (symbols, bonds, notes, flags). This
+    library's own rule, NOT RDKit's aromaticity model; nothing kekulises and no toolkit has checked it."""
 
     image_format = "fp32"
     packed_results = False
@@ -367,12 +399,13 @@ class molnextr:
     graph_canonical = False
     graph_symmetry = False
     graph_expand = False
+    graph_normalize = False
 
     def __init__(self, model_path, device=None, max_batch: int = 32, dtype: str = DEFAULT_DTYPE,
                  device_preprocess: bool = True, image_format: str = "fp32", packed_results: bool = False,
                  graph_molfile: bool = False, graph_smiles: bool = False, graph_stereo: bool = False,
                  graph_double_bonds: bool = False, graph_canonical: bool = False, graph_expand: bool = False,
-                 graph_symmetry: bool = False):
+                 graph_symmetry: bool = False, graph_normalize: bool = False):
         if model_path is None:
             raise ValueError("molnextr(model_path): a checkpoint path is required (pass 'synthetic' explicitly for the "
                              "deterministic test checkpoint)")
@@ -412,16 +445,19 @@ class molnextr:
         self.graph_expand = bool(graph_expand)
         if self.graph_expand and not (self.graph_smiles or self.graph_molfile):
             raise ValueError("graph_expand=True needs graph_smiles=True or graph_molfile=True: the expanded molecule is what they write")
+        self.graph_normalize = bool(graph_normalize)
+        if self.graph_normalize and not (self.graph_smiles or self.graph_molfile):
+            raise ValueError("graph_normalize=True needs graph_smiles=True or graph_molfile=True: the normalised molecule is what they write")
         self.engine = Engine(states["encoder"], states["decoder"], device=device.index or 0, max_batch=max_batch,
                              dtype=dtype, image_format=image_format)
         self.input_size = args.input_size
         self.device_preprocess = device_preprocess
         self.group_images = 1024          # images per engine call of the throughput path (whole reference batches)
 
-    def canonical_smiles(self, smiles_list, expand: bool = False) -> List[dict]:
+    def canonical_smiles(self, smiles_list, expand: bool = False, normalize: bool = False) -> List[dict]:
         """The canonical graph SMILES of the caller's own strings, for comparison with 'predicted_smiles' of graph_canonical=True
-        (model.canonical_smiles: read on the device, optionally expanded, written without marks)."""
-        return canonical_smiles(self.engine, smiles_list, expand=expand)
+        (model.canonical_smiles: read on the device, optionally expanded and normalised, written without marks)."""
+        return canonical_smiles(self.engine, smiles_list, expand=expand, normalize=normalize)
 
     _groups_done = 0          # groups of the running predict_images call that have produced predictions
 
@@ -605,6 +641,8 @@ class molnextr:
                 conf["symmetry"] = True
         if self.graph_expand:
             conf["expand"] = True
+        if self.graph_normalize:
+            conf["normalize"] = True
         gen = self._prefetched(groups)
         try:
             for x in gen:
@@ -654,6 +692,8 @@ class molnextr:
                 d["stereo_atoms"] = pred["stereo_atoms"]
             if "expanded" in pred:                            # graph_expand: the molecule the two strings describe; the ranks then
                 d["expanded"] = pred["expanded"]              # follow expanded['symbols'], not atom_sets
+            if "normalized" in pred:                          # graph_normalize: per atom of the molecule that was written
+                d["hydrogens"], d["normalized"] = pred["normalized"]["hydrogens"], pred["normalized"]
             if return_atoms_bonds:
                 c = pred["chartok_coords"]
                 atoms = []

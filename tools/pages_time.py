@@ -32,6 +32,10 @@ is part of the product path and no number is asserted.
 (r) (only when asked for: --part r) SMILES read on the device: one mnx_smiles_read call over the strings of 1024 hand-made
     molecules of drug-like size against the one mnx_smiles_pack call that writes those strings, then the worst strings the
     reader admits, each alone in a call; `--read-out FILE` writes the table to a file of its own.
+(n) (only when asked for: --part n) normalisation on the device: mnx_normalize_pack alone, against mnx_expand_pack on the same
+    input tables (the same shape of pass), and followed by mnx_smiles_pack_canonical against the canonical writer on the tables
+    as they came — on the synthetic checkpoint's predictions (near-complete graphs), on hand-made molecules of drug-like size
+    with aromatic rings, and on those with the rings in Kekule form; `--normalize-out FILE` writes the table to a file of its own.
 The variants of a part alternate inside every repeat (A B A B ...), the table reports the median and the min .. max spread of
 each, and the spread of the fp32 path against itself is the yardstick for "not slower".
 """
@@ -236,7 +240,7 @@ def part_m(n, repeats, lines):
 LABELS = (b"[OMe]", b"[Ph]", b"[tBu]", b"[CO2Et]", b"[NO2]", b"[Boc]")
 
 
-def druglike_records(n_mols, seed=0, centres=False, labels=False, gem=False):
+def druglike_records(n_mols, seed=0, centres=False, labels=False, gem=False, kekule=False):
     """Packed records of n_mols hand-made molecules of drug-like size: a chain of 20 .. 40 atoms, every seventh atom starting
     an aromatic six-ring, a few hetero atoms and double bonds (about 1.1 bonds per atom) — (mols, atoms, bonds, text).
     centres: every [C@@H] of the chain also carries a methyl on a wedge or a dash that begins at it, and its chain bonds are
@@ -244,7 +248,9 @@ def druglike_records(n_mols, seed=0, centres=False, labels=False, gem=False):
     plain 'C' becomes an abbreviation label of mnx_expand_pack, the six of LABELS in turn (the same molecules otherwise). gem
     (with centres): every third centre is a [C@@] with a second methyl — a gem-dimethyl carbon, which mnx_smiles_pack_symmetric
     drops — and every bond record carries its class in `rev` too, as mnx_graph_pack writes it (the older sets leave 0 there, so
-    a bond whose ends the ranks swap is written '~' and no centre beside it is a candidate)."""
+    a bond whose ends the ranks swap is written '~' and no centre beside it is a candidate). kekule: the six-rings are drawn in
+    Kekule form — upper-case atoms, double and single bonds in turn — for mnx_normalize_pack to perceive (the same molecules
+    otherwise)."""
     from molnextr_amd.engine import ATOM_DTYPE, BOND_DTYPE, MOL_DTYPE
     rng = np.random.default_rng(seed)
     mols = np.zeros(n_mols, MOL_DTYPE)
@@ -265,6 +271,11 @@ def druglike_records(n_mols, seed=0, centres=False, labels=False, gem=False):
             for k in range(8, n, 9):
                 if syms[k] == b"C":
                     syms[k] = LABELS[k // 9 % len(LABELS)]
+        if kekule:
+            for r in range(0, n - 5, 7):
+                for k in range(r, r + 6):
+                    syms[k] = syms[k].upper()
+                    bonds[(k, k + 1) if k < r + 5 else (r, r + 5)] = 2 - (k - r) % 2
         xy = [(k % 64, k // 2 % 64) for k in range(n)]
         rev = {}
         if centres:
@@ -608,6 +619,83 @@ def part_x(repeats, lines):
     m.engine.close()
 
 
+def part_n(repeats, lines):
+    """Normalisation on the device: one mnx_normalize_pack call (three launches) between two events, alternating with one
+    mnx_expand_pack call on the same input tables (the same shape of pass: count, scan, fill, one workgroup per molecule), with
+    the canonical writer on the input and with normalize followed by the canonical writer. Every output buffer has the exact
+    size; the tables stay on the device."""
+    import ctypes as C
+    from molnextr_amd import engine as E
+    from molnextr_amd.model import molnextr
+    dev = torch.device("cuda", 0)
+    m = molnextr("synthetic", dev, max_batch=32, image_format="gray8", packed_results=True)
+    eng = m.engine
+    ptr = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
+    stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)      # noqa: E731
+    buf = lambda k: torch.empty(max(int(k), 1), dtype=torch.uint8, device=dev)      # noqa: E731
+
+    def measure(rec, what):
+        tables, args = eng._packed_tables(rec)
+        n = len(rec["mols"])
+        ex, nz = eng.expand_pack(rec), eng.normalize_pack(rec, keep_device=True)
+        cn = {"in": eng.smiles_pack(rec, canonical=True), "out": eng.smiles_pack(nz, canonical=True)}
+        sizes = {k: (len(r["atoms"]), len(r["bonds"]), len(r["text"])) for k, r in (("in", rec), ("x", ex), ("n", nz))}
+        mols_d, totals_d, totals_w = buf(n * 40), torch.zeros(4, dtype=torch.int32, device=dev), torch.zeros(2, dtype=torch.int32, device=dev)
+        tab = {k: (buf(sizes[k][0] * 24), buf(sizes[k][1] * 16), buf(sizes[k][2])) for k in ("x", "n")}
+        origin_d = torch.empty(max(sizes["x"][0], 1), dtype=torch.int16, device=dev)
+        notes_d = buf(sizes["n"][0])
+        recs_d = buf(n * 16)
+        words = [torch.empty(max(sizes["n"][0], 1), dtype=torch.int16, device=dev) for _ in range(3)]
+        out_d = buf(max(len(cn["in"][2]), len(cn["out"][2])))
+
+        def table_pass(fn, k, extra):
+            a, b, t = tab[k]
+            return fn(eng.h, *args, ptr(mols_d), ptr(a), sizes[k][0], ptr(b), sizes[k][1], ptr(t), sizes[k][2], ptr(extra), ptr(totals_d), stream())
+
+        def canonical(head, which):
+            return eng.lib.mnx_smiles_pack_canonical(eng.h, *head, ptr(recs_d), ptr(words[0]), ptr(words[1]), ptr(words[2]), ptr(out_d),
+                                                     len(cn[which][2]), ptr(totals_w), 0, stream())
+
+        normal_head = [ptr(mols_d), n, ptr(tab["n"][0]), sizes["n"][0], ptr(tab["n"][1]), sizes["n"][1], ptr(tab["n"][2]), sizes["n"][2]]
+        normalize = lambda: table_pass(eng.lib.mnx_normalize_pack, "n", notes_d)      # noqa: E731
+        calls = {"mnx_expand_pack": lambda: table_pass(eng.lib.mnx_expand_pack, "x", origin_d), "mnx_normalize_pack": normalize,
+                 "canonical, as it came": lambda: canonical(args, "in"),
+                 "normalize + canonical": lambda: normalize() or canonical(normal_head, "out")}
+        us = {k: [] for k in calls}
+        for i in range(repeats + 3):
+            for k, call in calls.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                a.record()
+                rc = call()
+                b.record()
+                torch.cuda.synchronize()
+                assert rc == 0 and not int(totals_d[3]) and not int(totals_w[1]), k
+                if i >= 3:
+                    us[k].append(a.elapsed_time(b) * 1000.0)
+        assert tab["n"][2][:sizes["n"][2]].cpu().numpy().tobytes() == nz["text"] and notes_d[:sizes["n"][0]].cpu().numpy().tobytes() == nz["atom_notes"].tobytes()
+        assert out_d[:len(cn["out"][2])].cpu().numpy().tobytes() == cn["out"][2]
+        flags, notes = nz["mols"]["flags"], nz["atom_notes"]
+        lines.append(f"(n) one call over {n} {what}: {sizes['in'][0]} atoms, {sizes['in'][1]} bonds, {sizes['in'][2]} -> {sizes['n'][2]} bytes of "
+                     f"text; aromatized {int((flags & E.MOL_AROMATIZED != 0).sum())} molecules ({int((notes & E.NOTE_AROMATIZED != 0).sum())} atoms), "
+                     f"brackets removed in {int((flags & E.MOL_UNBRACKETED != 0).sum())}, refused {int((flags & E.MOL_NORMALIZE_REFUSED != 0).sum())}; "
+                     f"the canonical writer refuses {int((cn['in'][0]['flags'] & E.SMILES_REFUSED != 0).sum())}")
+        lines.append("  device us between two events around the launches, the four alternating   median [min .. max]")
+        for k in us:
+            lines.append(f"  {k:24s} {fmt(us[k])} us")
+        lines.append(f"  normalize / expand, median {statistics.median(us['mnx_normalize_pack']) / statistics.median(us['mnx_expand_pack']):.2f}; "
+                     f"(normalize + canonical) / canonical, median "
+                     f"{statistics.median(us['normalize + canonical']) / statistics.median(us['canonical, as it came']):.2f}")
+
+    pages = [W.synthetic_page(i % 15) for i in range(1024)]
+    measure(eng.graph_pack(eng.predict(m._transform(pages), ref_batch=32)), "images of the synthetic checkpoint (near-complete graphs)")
+    for kekule, what in ((False, "hand-made molecules of drug-like size, rings aromatic already (the pass copies them)"),
+                         (True, "hand-made molecules of drug-like size, rings in Kekule form")):
+        mols, atoms, bonds, text = druglike_records(1024, kekule=kekule)
+        measure({"mols": mols, "atoms": atoms, "bonds": bonds, "text": text}, what)
+    m.engine.close()
+
+
 def part_r(repeats, lines):
     """SMILES read on the device: one mnx_smiles_read call (three launches) over the strings of 1024 hand-made molecules of
     drug-like size between two events, alternating with the one mnx_smiles_pack call that writes those strings from the packed
@@ -723,6 +811,7 @@ def main():
     ap.add_argument("--smiles-out", default=None, help="write the table of part s to this file")
     ap.add_argument("--expand-out", default=None, help="write the table of part x to this file")
     ap.add_argument("--read-out", default=None, help="write the table of part r to this file")
+    ap.add_argument("--normalize-out", default=None, help="write the table of part n to this file")
     ap.add_argument("--pack-only", type=int, default=0, help="run this many mnx_graph_pack calls over 1024 images and exit")
     args = ap.parse_args()
     parts = args.part.split(",")
@@ -777,6 +866,13 @@ def main():
         if args.read_out:
             os.makedirs(os.path.dirname(os.path.abspath(args.read_out)), exist_ok=True)
             with open(args.read_out, "w") as f:
+                f.write("\n".join([lines[0]] + lines[first:]) + "\n")
+    if "n" in parts:
+        first = len(lines)
+        part_n(args.repeats, lines)
+        if args.normalize_out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.normalize_out)), exist_ok=True)
+            with open(args.normalize_out, "w") as f:
                 f.write("\n".join([lines[0]] + lines[first:]) + "\n")
     text = "\n".join(lines)
     print(text)
