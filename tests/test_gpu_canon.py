@@ -3,11 +3,8 @@ against the oracle of tests/canon_ref.py, byte for byte and word for word (recs,
 tolerances), for marks 0..3: the strings that pin the rule, the generated molecules of the CPU tests, the device against its own
 older call on the renumbered tables, renumbered and shuffled tables, the sizes at which the kernel's loops take another turn,
 the refusal cases, the protocol, the two molecules that make the ranking run longest, and one end-to-end run."""
-import ctypes as C
-
 import numpy as np
 import pytest
-import torch
 
 import canon_ref as K
 import ez_ref as E
@@ -15,28 +12,15 @@ import smiles_ref as S
 import stereo_ref as T
 import test_canon_host as H
 from molnextr_amd import weights as W
-from molnextr_amd.engine import SMILES_CANON_TIE, SMILES_CANON_TIE_INDEX, SMILES_DTYPE, SMILES_REFUSED, Engine
-from packed_tables import FILL, GUARD, Tables, _p, compare, random_molecule
+from molnextr_amd.engine import SMILES_CANON_TIE, SMILES_CANON_TIE_INDEX, SMILES_REFUSED
+from packed_tables import (FILL, WORD_FILL, Tables, _p, assert_refused, call_text, compare_text, dev, eng, random_molecule,  # noqa: F401
+                           same_results, texts)
 
 pytestmark = pytest.mark.gpu
 
-WORD_FILL = FILL | FILL << 8
 TIE_BITS = SMILES_CANON_TIE | SMILES_CANON_TIE_INDEX
 E2E_FIRST_INDEX = 500          # the batch of the plain writer's end-to-end test
 MODES = (0, 1, 2, 3)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def eng(synth_ckpt, dev):
-    e = Engine(synth_ckpt["encoder"], synth_ckpt["decoder"], device=0, max_batch=32, dtype="fp16x3")
-    yield e
-    e.close()
 
 
 @pytest.fixture(scope="module")
@@ -48,42 +32,14 @@ def generated(dev):
 
 
 def run(eng, t, out_cap, marks=0, **over):
-    """One call into FILL-filled outputs with GUARD bytes behind each: (rc, recs, order, rank, sym_class, the whole out arena,
-    totals)"""
-    na, nb, nt = len(t.atoms), len(t.bonds), len(t.text)
-    recs = torch.full((t.n * 16 + GUARD,), FILL, dtype=torch.uint8, device=t.dev)
-    words = [torch.full((na * 2 + GUARD,), FILL, dtype=torch.uint8, device=t.dev) for _ in range(3)]
-    out = torch.full((out_cap + GUARD,), FILL, dtype=torch.uint8, device=t.dev)
-    totals = torch.full((8,), FILL, dtype=torch.uint8, device=t.dev)
-    a = {"h": eng.h, "mols": _p(t.d[0]), "n": t.n, "atoms": _p(t.d[1]), "na": na, "bonds": _p(t.d[2]), "nb": nb, "text": _p(t.d[3]),
-         "nt": nt, "recs": _p(recs), "order": _p(words[0]), "rank": _p(words[1]), "sym_class": _p(words[2]), "out": _p(out),
-         "out_cap": out_cap, "totals": _p(totals), "marks": marks, "stream": C.c_void_p(torch.cuda.current_stream().cuda_stream)}
-    a.update(over)
-    rc = eng.lib.mnx_smiles_pack_canonical(*a.values())
-    torch.cuda.synchronize()
-    r, o = recs.cpu().numpy(), out.cpu().numpy()
-    w = [x.cpu().numpy() for x in words]
-    assert np.all(r[t.n * 16:] == FILL), "bytes behind recs were overwritten"
-    assert all(np.all(x[na * 2:] == FILL) for x in w), "bytes behind order, rank or sym_class were overwritten"
-    order, rank, sym_class = (x[:na * 2].view(np.uint16) for x in w)
-    return rc, r[:t.n * 16].view(SMILES_DTYPE), order, rank, sym_class, o, totals.cpu().numpy().view(np.uint32)
+    return call_text("mnx_smiles_pack_canonical", eng, t, out_cap, marks=marks, **over)
 
 
 def check(eng, t, marks, ref=None):
     """the device's recs, order, rank, sym_class, bytes and totals equal the oracle's at the exact capacity; returns the oracle's"""
     ref = ref or K.pack(t.mols, t.atoms, t.bonds, t.text, marks, order_fill=WORD_FILL)
-    rc, recs, order, rank, sym_class, out, totals = run(eng, t, ref["total"], marks)
-    assert rc == 0, eng.lib.mnx_last_error(eng.h)
-    assert totals.tolist() == [ref["total"], 0]
-    compare(recs, ref["recs"], out, ref["out"], ref["total"], "SMILES")
-    for name, got in (("rank", rank), ("sym_class", sym_class), ("order", order)):
-        bad = np.nonzero(got != ref[name])[0]
-        assert bad.size == 0, (name, bad[:5], got[bad[:5]], ref[name][bad[:5]])
+    compare_text(run(eng, t, ref["total"], marks), ref, "SMILES")
     return ref
-
-
-def texts(ref):
-    return [ref["out"][r["text0"]:r["text0"] + r["len"]].decode() for r in ref["recs"]]
 
 
 @pytest.mark.parametrize("marks", MODES)
@@ -123,16 +79,17 @@ def renumbered_tables(t, rank):
 def test_device_against_its_own_older_call_on_the_renumbered_tables(eng, dev, generated, marks):
     """the tables renumbered by the returned ranks go through mnx_smiles_pack_marks: the same bytes, lengths and n_rings, the
     same flags apart from the tie bits, and `order` carried over through the ranks"""
-    import test_gpu_ez as G
     mols, t, refs = generated
     need = refs[marks]["total"]
-    rc, recs, order, rank, sym_class, out, totals = run(eng, t, need, marks)
-    assert rc == 0 and totals.tolist() == [need, 0]
+    a = run(eng, t, need, marks)
+    assert a.rc == 0 and a.totals.tolist() == [need, 0]
+    recs, order, rank = a.recs, a.order, a.rank
     atoms, bonds = renumbered_tables(t, rank)
     moved = Tables(dev, arrays=(t.mols, atoms, bonds, t.text))
-    rc, recs2, order2, out2, totals2 = G.run(eng, moved, need, marks)
-    assert rc == 0 and totals2.tolist() == [need, 0]
-    assert np.array_equal(out[:need], out2[:need])
+    b = call_text("mnx_smiles_pack_marks", eng, moved, need, marks=marks)
+    assert b.rc == 0 and b.totals.tolist() == [need, 0]
+    recs2, order2 = b.recs, b.order
+    assert np.array_equal(a.out[:need], b.out[:need])
     for name in ("text0", "len", "n_rings"):
         assert np.array_equal(recs[name], recs2[name]), name
     assert np.array_equal(recs["flags"] & ~np.uint32(TIE_BITS), recs2["flags"]) and (recs["flags"] & SMILES_CANON_TIE).any()
@@ -154,12 +111,12 @@ def test_renumbered_and_bond_shuffled_tables_give_identical_bytes(eng, dev, gene
     for marks in MODES:
         need = refs[marks]["total"]
         a, b = run(eng, t, need, marks), run(eng, t2, need, marks)
-        assert a[0] == b[0] == 0 and a[6].tolist() == b[6].tolist() == [need, 0]
-        assert a[1].tobytes() == b[1].tobytes() and np.array_equal(a[5], b[5])
+        assert a.rc == b.rc == 0 and a.totals.tolist() == b.totals.tolist() == [need, 0]
+        assert a.recs.tobytes() == b.recs.tobytes() and np.array_equal(a.out, b.out)
         for m, p in zip(t.mols, perms):
             a0, na = int(m["atom0"]), int(m["n_atoms"])
-            for w in (2, 3, 4):                               # order, rank, sym_class: atom k is now atom p[k]
-                assert np.array_equal(a[w][a0:a0 + na], b[w][a0:a0 + na][p])
+            for w in ("order", "rank", "sym_class"):          # atom k is now atom p[k]
+                assert np.array_equal(getattr(a, w)[a0:a0 + na], getattr(b, w)[a0:a0 + na][p])
 
 
 def chain(n, rng):
@@ -232,11 +189,12 @@ def test_records_beyond_the_tables_are_refused(eng, dev):
     for short in ({"na": len(t.atoms) - 1}, {"nb": len(t.bonds) - 1}, {"nt": len(t.text) - 1}):
         names = {"na": "n_atom_records", "nb": "n_bond_records", "nt": "n_text_bytes"}
         ref = K.pack(t.mols, t.atoms, t.bonds, t.text, 3, order_fill=WORD_FILL, **{names[k]: v for k, v in short.items()})
-        rc, recs, order, rank, sym_class, out, totals = run(eng, t, ref["total"], 3, **short)
-        assert rc == 0 and totals.tolist() == [ref["total"], 0] and recs.tobytes() == ref["recs"].tobytes()
-        assert ref["recs"]["flags"][-1] == S.FLAG_BEYOND and out[:ref["total"]].tobytes() == ref["out"]
+        a = run(eng, t, ref["total"], 3, **short)
+        assert a.rc == 0 and a.totals.tolist() == [ref["total"], 0] and a.recs.tobytes() == ref["recs"].tobytes()
+        assert ref["recs"]["flags"][-1] == S.FLAG_BEYOND and a.out[:ref["total"]].tobytes() == ref["out"]
         n = len(ref["rank"])
-        for got, name in ((order, "order"), (rank, "rank"), (sym_class, "sym_class")):
+        for name in ("order", "rank", "sym_class"):
+            got = getattr(a, name)
             assert np.array_equal(got[:n], ref[name]) and (got[n:] == WORD_FILL).all(), name
 
 
@@ -252,15 +210,15 @@ def test_protocol(eng, generated):
     mols, t, refs = generated
     ref = refs[3]
     need = ref["total"]
-    rc, recs, order, rank, sym_class, out, totals = run(eng, t, 0, 3, out=None)
-    assert rc == 0 and totals.tolist() == [need, 1] and recs.tobytes() == ref["recs"].tobytes() and np.all(out == FILL)
-    assert order.tobytes() == ref["order"].tobytes() and rank.tobytes() == ref["rank"].tobytes() and sym_class.tobytes() == ref["sym_class"].tobytes()
-    rc, recs, order, rank, sym_class, out, totals = run(eng, t, need - 1, 3)
-    assert rc == 0 and totals.tolist() == [need, 1] and recs.tobytes() == ref["recs"].tobytes() and rank.tobytes() == ref["rank"].tobytes()
-    assert out[:need - 1].tobytes() == ref["out"][:need - 1] and np.all(out[need - 1:] == FILL)
-    rc, recs, order, rank, sym_class, out, totals = run(eng, t, need, 3, order=None, sym_class=None)
-    assert rc == 0 and totals.tolist() == [need, 0] and recs.tobytes() == ref["recs"].tobytes() and rank.tobytes() == ref["rank"].tobytes()
-    assert out[:need].tobytes() == ref["out"] and (order == WORD_FILL).all() and (sym_class == WORD_FILL).all()
+    a = run(eng, t, 0, 3, out=None)
+    assert a.rc == 0 and a.totals.tolist() == [need, 1] and a.recs.tobytes() == ref["recs"].tobytes() and np.all(a.out == FILL)
+    assert a.order.tobytes() == ref["order"].tobytes() and a.rank.tobytes() == ref["rank"].tobytes() and a.sym_class.tobytes() == ref["sym_class"].tobytes()
+    a = run(eng, t, need - 1, 3)
+    assert a.rc == 0 and a.totals.tolist() == [need, 1] and a.recs.tobytes() == ref["recs"].tobytes() and a.rank.tobytes() == ref["rank"].tobytes()
+    assert a.out[:need - 1].tobytes() == ref["out"][:need - 1] and np.all(a.out[need - 1:] == FILL)
+    a = run(eng, t, need, 3, order=None, sym_class=None)
+    assert a.rc == 0 and a.totals.tolist() == [need, 0] and a.recs.tobytes() == ref["recs"].tobytes() and a.rank.tobytes() == ref["rank"].tobytes()
+    assert a.out[:need].tobytes() == ref["out"] and (a.order == WORD_FILL).all() and (a.sym_class == WORD_FILL).all()
 
 
 def test_refused_calls_launch_nothing_and_name_the_new_function(eng, dev):
@@ -268,13 +226,9 @@ def test_refused_calls_launch_nothing_and_name_the_new_function(eng, dev):
     need = K.pack(t.mols, t.atoms, t.bonds, t.text, 3)["total"]
 
     def refused(expect, **over):
-        rc, recs, order, rank, sym_class, out, totals = run(eng, t, need, **{"marks": 3, **over})
-        msg = eng.lib.mnx_last_error(eng.h).decode()
-        assert rc == -1 and msg == "mnx_smiles_pack_canonical: " + expect, (over, rc, msg)
-        assert np.all(recs.view(np.uint8) == FILL) and np.all(out == FILL) and np.all(totals.view(np.uint8) == FILL), over
-        assert np.all(order == WORD_FILL) and np.all(rank == WORD_FILL) and np.all(sym_class == WORD_FILL), over
+        assert_refused(run(eng, t, need, **{"marks": 3, **over}), "mnx_smiles_pack_canonical: " + expect)
 
-    assert run(eng, t, need, 3)[0] == 0
+    assert run(eng, t, need, 3).rc == 0
     for marks in (4, 8, 0x80000001):
         refused("marks may hold MNX_SMILES_MARK_TETRAHEDRAL and MNX_SMILES_MARK_DOUBLE_BOND only", marks=marks)
     for name in ("rank", "mols", "atoms", "recs", "out", "totals"):
@@ -288,7 +242,8 @@ def test_two_runs_are_word_identical(eng, generated):
     mols, t, refs = generated
     for marks in (0, 3):
         a, b = run(eng, t, refs[marks]["total"], marks), run(eng, t, refs[marks]["total"], marks)
-        assert a[0] == b[0] == 0 and all(a[k].tobytes() == b[k].tobytes() for k in (1, 2, 3, 4, 5, 6))
+        same_results(a, b)
+        assert a.rc == b.rc == 0
 
 
 def test_the_two_molecules_that_rank_longest(eng, dev):

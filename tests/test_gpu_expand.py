@@ -3,11 +3,10 @@ oracle of tests/expand_ref.py, records field by field and tables byte for byte (
 kernel's scans, searches and loops take another turn, the refusals, the capacity protocol, determinism, the argument errors of
 mnx_set_fragments, the chain into the canonical SMILES writer and the molfile writer, the label-versus-drawn-out pairs of the
 host test, and one end-to-end run."""
-import ctypes as C
+import functools
 
 import numpy as np
 import pytest
-import torch
 
 import canon_ref as K
 import expand_ref as X
@@ -15,26 +14,13 @@ import molfile_ref as M
 import test_expand_host as H
 from molnextr_amd import fragments as F
 from molnextr_amd import weights as W
-from molnextr_amd.engine import (ATOM_DTYPE, BOND_DTYPE, MOL_DTYPE, MOL_EXPAND_REFUSED, MOL_EXPANDED, MOL_LABEL_LEFT, Engine,
-                                 symbol_tables)
-from packed_tables import FILL, GUARD, UTF2, Tables, _p
+from molnextr_amd.engine import MOL_EXPAND_REFUSED, MOL_EXPANDED, MOL_LABEL_LEFT, Engine, symbol_tables
+from packed_tables import (UTF2, Tables, _p, assert_refused, call_tables, clean, compare_tables, dev, eng, mol, path, same_mols,  # noqa: F401
+                           same_results)
 
 pytestmark = pytest.mark.gpu
 
 E2E_FIRST_INDEX = 500          # the batch of the writers' end-to-end tests
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def eng(synth_ckpt, dev):
-    e = Engine(synth_ckpt["encoder"], synth_ckpt["decoder"], device=0, max_batch=32, dtype="fp16x3")
-    yield e
-    e.close()
 
 
 @pytest.fixture(scope="module")
@@ -47,62 +33,14 @@ def library(tables):
     return X.library(tables=tables)
 
 
-def clean(a):
-    """the records of a structured array as the device writes them: padding bytes as zeros"""
-    z = np.zeros(len(a), a.dtype)
-    for name in a.dtype.names:
-        z[name] = a[name]
-    return z.tobytes()
-
-
-def run(eng, t, caps, **over):
-    """One call into FILL-filled outputs with GUARD bytes behind each capacity: (rc, mols, atoms bytes, bonds bytes, text bytes,
-    origin bytes, totals), each table as the whole arena"""
-    sizes = (t.n * MOL_DTYPE.itemsize, caps[0] * ATOM_DTYPE.itemsize, caps[1] * BOND_DTYPE.itemsize, caps[2], caps[0] * 2, 16)
-    bufs = [torch.full((s + GUARD,), FILL, dtype=torch.uint8, device=t.dev) for s in sizes]
-    a = {"h": eng.h, "mols": _p(t.d[0]), "n": t.n, "atoms": _p(t.d[1]), "na": len(t.atoms), "bonds": _p(t.d[2]), "nb": len(t.bonds),
-         "text": _p(t.d[3]), "nt": len(t.text), "mols_out": _p(bufs[0]), "atoms_out": _p(bufs[1]), "atom_cap": caps[0],
-         "bonds_out": _p(bufs[2]), "bond_cap": caps[1], "text_out": _p(bufs[3]), "text_cap": caps[2], "origin": _p(bufs[4]),
-         "totals": _p(bufs[5]), "stream": C.c_void_p(torch.cuda.current_stream().cuda_stream)}
-    a.update(over)
-    rc = eng.lib.mnx_expand_pack(*a.values())
-    torch.cuda.synchronize()
-    host = [b.cpu().numpy() for b in bufs]
-    for h, s, what in zip(host, sizes, ("mols_out", "atoms_out", "bonds_out", "text_out", "origin", "totals")):
-        assert np.all(h[s:] == FILL), f"bytes behind {what} were overwritten"
-    return (rc, host[0][:sizes[0]].view(MOL_DTYPE), host[1][:sizes[1]], host[2][:sizes[2]], host[3][:sizes[3]], host[4][:sizes[4]],
-            host[5][:16].view(np.uint32))
-
-
-def same_mols(got, want):
-    for name in MOL_DTYPE.names:
-        bad = np.nonzero(got[name] != want[name])[0]
-        assert bad.size == 0, (name, bad[:5], got[name][bad[:5]], want[name][bad[:5]])
+run = functools.partial(call_tables, "mnx_expand_pack")       # run(eng, t, caps, **over); the result's `side` is `origin`
 
 
 def check(eng, t, library, tables, ref=None):
     """the device's tables equal the oracle's at the exact capacities, byte for byte; returns the oracle's"""
     ref = ref or X.pack(t.mols, t.atoms, t.bonds, t.text, frags=library, tables=tables)
-    rc, mols, atoms, bonds, text, origin, totals = run(eng, t, ref["totals"])
-    assert rc == 0, eng.lib.mnx_last_error(eng.h)
-    assert totals.tolist() == list(ref["totals"]) + [0]
-    same_mols(mols, ref["mols"])
-    assert mols.tobytes() == clean(ref["mols"])
-    for got, want, size, what in ((atoms, ref["atoms"], 24, "atom"), (bonds, ref["bonds"], 16, "bond")):
-        want = np.frombuffer(clean(want), np.uint8)
-        bad = np.nonzero(got != want)[0]
-        assert bad.size == 0, (what, "record", bad[0] // size, got[bad[0] // size * size:][:size], want[bad[0] // size * size:][:size])
-    assert text.tobytes() == ref["text"]
-    assert origin.view(np.uint16).tolist() == ref["origin"].tolist()
+    compare_tables(run(eng, t, ref["totals"]), ref, "origin")
     return ref
-
-
-def mol(symbols, bonds=()):
-    return list(symbols), [(3 * k % 64, 5 * k % 64) for k in range(len(symbols))], [tuple(b) for b in bonds]
-
-
-def path(n, ty=1):
-    return [(k, k + 1, ty, ty) for k in range(n - 1)]
 
 
 SMALL = [
@@ -149,8 +87,7 @@ def test_1025_random_molecules_and_two_runs_with_identical_bytes(eng, batch, lib
     t, ref = batch
     assert 500 < (ref["mols"]["flags"] & MOL_EXPANDED).astype(bool).sum() and (ref["mols"]["flags"] & MOL_LABEL_LEFT).any()
     check(eng, t, library, tables, ref)
-    first, second = run(eng, t, ref["totals"]), run(eng, t, ref["totals"])
-    assert all(a.tobytes() == b.tobytes() for a, b in zip(first[1:], second[1:]))
+    same_results(run(eng, t, ref["totals"]), run(eng, t, ref["totals"]))
 
 
 def test_large_molecules_and_refusals(eng, dev, library, tables):
@@ -172,10 +109,10 @@ def test_large_molecules_and_refusals(eng, dev, library, tables):
         want = X.pack(t.mols, t.atoms, t.bonds, t.text, frags=library, tables=tables, n_atom_records=cut.get("na"),
                       n_bond_records=cut.get("nb"), n_text_bytes=cut.get("nt"))
         assert int(want["mols"]["flags"][-1]) & MOL_EXPAND_REFUSED
-        rc, mols, atoms, bonds, text, origin, totals = run(eng, t, want["totals"], **cut)
-        assert rc == 0 and totals.tolist() == list(want["totals"]) + [0]
-        same_mols(mols, want["mols"])
-        assert atoms.tobytes() == clean(want["atoms"]) and bonds.tobytes() == clean(want["bonds"]) and text.tobytes() == want["text"]
+        a = run(eng, t, want["totals"], **cut)
+        assert a.rc == 0 and a.totals.tolist() == list(want["totals"]) + [0]
+        same_mols(a.mols, want["mols"])
+        assert a.atoms.tobytes() == clean(want["atoms"]) and a.bonds.tobytes() == clean(want["bonds"]) and a.text.tobytes() == want["text"]
     mols, atoms, bonds, text = M.build_tables([ok, ok])
     atoms["sym0"][3] = 60000
     check(eng, Tables(dev, arrays=(mols, atoms, bonds, text)), library, tables)
@@ -210,14 +147,14 @@ def test_capacities_exact_and_one_short(eng, batch):
     for k in range(3):
         caps = list(full)
         caps[k] -= 1
-        rc, mols, atoms, bonds, text, origin, totals = run(eng, t, caps)           # run() checks the FILL bytes behind every capacity
-        assert rc == 0 and totals.tolist() == full + [1]
-        same_mols(mols, ref["mols"])
-        for got, want in zip((atoms, bonds, text, origin), exact):
+        a = run(eng, t, caps)                                                      # run() checks the FILL bytes behind every capacity
+        assert a.rc == 0 and a.totals.tolist() == full + [1]
+        same_mols(a.mols, ref["mols"])
+        for got, want in zip((a.atoms, a.bonds, a.text, a.side), exact):
             assert np.array_equal(got, want[:len(got)])
-    rc, mols, atoms, bonds, text, origin, totals = run(eng, t, (0, 0, 0), atoms_out=None, bonds_out=None, text_out=None, origin=None)
-    assert rc == 0 and totals.tolist() == full + [1]                               # the sizing call
-    same_mols(mols, ref["mols"])
+    a = run(eng, t, (0, 0, 0), atoms_out=None, bonds_out=None, text_out=None, origin=None)
+    assert a.rc == 0 and a.totals.tolist() == full + [1]                           # the sizing call
+    same_mols(a.mols, ref["mols"])
 
 
 def test_engine_expand_pack_sizes_itself(eng, batch):
@@ -325,10 +262,10 @@ def test_set_fragments_argument_errors(eng, dev, synth_ckpt, library, tables):
         keep, a = fragment_args(bare)
         assert bare.lib.mnx_set_fragments(*a.values()) == -1 and b"call mnx_set_symbol_tables first" in bare.lib.mnx_last_error(bare.h)
         t = Tables(dev, SMALL)
-        rc = run(bare, t, (1, 1, 1))[0]
+        rc = run(bare, t, (1, 1, 1)).rc
         assert rc == -1 and b"mnx_expand_pack: call mnx_set_symbol_tables first" in bare.lib.mnx_last_error(bare.h)
         Engine._set_symbol_tables(bare)
-        rc = run(bare, t, (1, 1, 1))[0]
+        rc = run(bare, t, (1, 1, 1)).rc
         assert rc == -1 and b"mnx_expand_pack: call mnx_set_fragments first" in bare.lib.mnx_last_error(bare.h)
         keep, a = fragment_args(bare, n_frags=0, frag_of_name=lambda x: x.fill(-1))     # an empty library: nothing expands
         assert bare.lib.mnx_set_fragments(*a.values()) == 0
@@ -336,7 +273,7 @@ def test_set_fragments_argument_errors(eng, dev, synth_ckpt, library, tables):
         Engine._set_fragments(bare)
         check(bare, t, library, tables)
         Engine._set_symbol_tables(bare)                                            # new names drop the fragments
-        assert run(bare, t, (1, 1, 1))[0] == -1 and b"call mnx_set_fragments first" in bare.lib.mnx_last_error(bare.h)
+        assert run(bare, t, (1, 1, 1)).rc == -1 and b"call mnx_set_fragments first" in bare.lib.mnx_last_error(bare.h)
     finally:
         bare.close()
 
@@ -345,10 +282,7 @@ def test_expand_pack_argument_errors(eng, dev):
     t = Tables(dev, SMALL)
 
     def refused(expect, **over):
-        rc = run(eng, t, (64, 64, 64), **over)
-        assert rc[0] == -1 and all(np.all(x == FILL) for x in rc[2:6]) and np.all(rc[1].view(np.uint8) == FILL)
-        msg = eng.lib.mnx_last_error(eng.h).decode()
-        assert msg == "mnx_expand_pack: " + expect, msg
+        assert_refused(run(eng, t, (64, 64, 64), **over), "mnx_expand_pack: " + expect)
 
     for name in ("mols", "atoms", "bonds", "text", "mols_out", "atoms_out", "bonds_out", "text_out", "totals"):
         refused("null pointer", **{name: None})

@@ -3,37 +3,22 @@ against the oracle of tests/ez_ref.py, byte for byte and record for record, `ord
 and marks == 3: the strings that pin the rule, the generated molecules of the CPU tests, the sizes at which the kernel's loops
 take another turn, the capacity and argument handling, marks == 0 and 1 against the two older calls, the strip invariants on the
 device, and one end-to-end run."""
-import ctypes as C
-
 import numpy as np
 import pytest
-import torch
 
 import ez_ref as E
 import stereo_ref as T
 import test_ez_host as H
 from molnextr_amd import weights as W
-from molnextr_amd.engine import SMILES_DTYPE, SMILES_EZ, SMILES_EZ_IMPLIED, SMILES_EZ_UNRESOLVED, SMILES_REFUSED, Engine
-from packed_tables import FILL, GUARD, Tables, _p, compare, random_molecule
+from molnextr_amd.engine import SMILES_EZ, SMILES_EZ_IMPLIED, SMILES_EZ_UNRESOLVED, SMILES_REFUSED, Engine
+from packed_tables import (FILL, Tables, _p, assert_refused, call_text, compare_text, dev, device_texts, eng, random_molecule,  # noqa: F401
+                           same_results, texts)
+from packed_tables import WORD_FILL as ORDER_FILL
 
 pytestmark = pytest.mark.gpu
 
-ORDER_FILL = FILL | FILL << 8
 E2E_FIRST_INDEX = 500          # the batch of the plain writer's end-to-end test: two of its eight molecules are written
 MODES = (2, 3)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def eng(synth_ckpt, dev):
-    e = Engine(synth_ckpt["encoder"], synth_ckpt["decoder"], device=0, max_batch=32, dtype="fp16x3")
-    yield e
-    e.close()
 
 
 @pytest.fixture(scope="module")
@@ -51,44 +36,15 @@ def pool(dev):
 
 
 def run(eng, t, out_cap, marks=2, fn="mnx_smiles_pack_marks", **over):
-    """One call into FILL-filled outputs with GUARD bytes behind each: (rc, recs, order, the whole out arena, totals)"""
-    na, nb, nt = len(t.atoms), len(t.bonds), len(t.text)
-    recs = torch.full((t.n * 16 + GUARD,), FILL, dtype=torch.uint8, device=t.dev)
-    order = torch.full((na * 2 + GUARD,), FILL, dtype=torch.uint8, device=t.dev)
-    out = torch.full((out_cap + GUARD,), FILL, dtype=torch.uint8, device=t.dev)
-    totals = torch.full((8,), FILL, dtype=torch.uint8, device=t.dev)
-    a = {"h": eng.h, "mols": _p(t.d[0]), "n": t.n, "atoms": _p(t.d[1]), "na": na, "bonds": _p(t.d[2]), "nb": nb, "text": _p(t.d[3]),
-         "nt": nt, "recs": _p(recs), "order": _p(order), "out": _p(out), "out_cap": out_cap, "totals": _p(totals), "marks": marks,
-         "stream": C.c_void_p(torch.cuda.current_stream().cuda_stream)}
-    if fn != "mnx_smiles_pack_marks":
-        del a["marks"]
-    a.update(over)
-    rc = getattr(eng.lib, fn)(*a.values())
-    torch.cuda.synchronize()
-    r, o, w = recs.cpu().numpy(), out.cpu().numpy(), order.cpu().numpy()
-    assert np.all(r[t.n * 16:] == FILL), "bytes behind recs were overwritten"
-    assert np.all(w[na * 2:] == FILL), "bytes behind order were overwritten"
-    return rc, r[:t.n * 16].view(SMILES_DTYPE), w[:na * 2].view(np.uint16), o, totals.cpu().numpy().view(np.uint32)
+    """the older calls (fn) take no marks"""
+    return call_text(fn, eng, t, out_cap, **({"marks": marks} if fn == "mnx_smiles_pack_marks" else {}), **over)
 
 
 def check(eng, t, marks, ref=None):
     """the device's recs, order, bytes and totals equal the oracle's at the exact capacity; returns the oracle's result"""
     ref = ref or E.pack(t.mols, t.atoms, t.bonds, t.text, marks, order_fill=ORDER_FILL)
-    rc, recs, order, out, totals = run(eng, t, ref["total"], marks)
-    assert rc == 0, eng.lib.mnx_last_error(eng.h)
-    assert totals.tolist() == [ref["total"], 0]
-    compare(recs, ref["recs"], out, ref["out"], ref["total"], "SMILES")
-    bad = np.nonzero(order != ref["order"])[0]
-    assert bad.size == 0, ("order", bad[:5], order[bad[:5]], ref["order"][bad[:5]])
+    compare_text(run(eng, t, ref["total"], marks), ref, "SMILES")
     return ref
-
-
-def texts(ref):
-    return [ref["out"][r["text0"]:r["text0"] + r["len"]].decode() for r in ref["recs"]]
-
-
-def device_texts(recs, out):
-    return [out[r["text0"]:r["text0"] + r["len"]].tobytes().decode() for r in recs]
 
 
 @pytest.mark.parametrize("marks", MODES)
@@ -169,22 +125,22 @@ def test_capacities(eng, generated, marks):
     mols, t, refs = generated
     ref = refs[marks]
     need = ref["total"]
-    rc, recs, order, out, totals = run(eng, t, 0, marks, out=None)
-    assert rc == 0 and totals.tolist() == [need, 1] and recs.tobytes() == ref["recs"].tobytes() and order.tobytes() == ref["order"].tobytes()
-    assert np.all(out == FILL)
+    a = run(eng, t, 0, marks, out=None)
+    assert a.rc == 0 and a.totals.tolist() == [need, 1] and a.recs.tobytes() == ref["recs"].tobytes() and a.order.tobytes() == ref["order"].tobytes()
+    assert np.all(a.out == FILL)
     for cap in (need, need - 1):
-        rc, recs, order, out, totals = run(eng, t, cap, marks)
-        assert rc == 0 and totals.tolist() == [need, int(cap < need)]
-        assert recs.tobytes() == ref["recs"].tobytes() and order.tobytes() == ref["order"].tobytes()
-        assert out[:cap].tobytes() == ref["out"][:cap] and np.all(out[cap:] == FILL), cap
+        a = run(eng, t, cap, marks)
+        assert a.rc == 0 and a.totals.tolist() == [need, int(cap < need)]
+        assert a.recs.tobytes() == ref["recs"].tobytes() and a.order.tobytes() == ref["order"].tobytes()
+        assert a.out[:cap].tobytes() == ref["out"][:cap] and np.all(a.out[cap:] == FILL), cap
 
 
 def test_two_runs_are_byte_identical(eng, generated):
     mols, t, refs = generated
     for marks in MODES:
         a, b = run(eng, t, refs[marks]["total"], marks), run(eng, t, refs[marks]["total"], marks)
-        assert a[0] == b[0] == 0 and a[1].tobytes() == b[1].tobytes() and a[2].tobytes() == b[2].tobytes()
-        assert np.array_equal(a[3], b[3]) and a[4].tolist() == b[4].tolist() == [refs[marks]["total"], 0]
+        same_results(a, b)
+        assert a.rc == b.rc == 0 and a.totals.tolist() == b.totals.tolist() == [refs[marks]["total"], 0]
 
 
 def test_marks_0_and_1_are_the_older_calls(eng, generated, pool):
@@ -192,11 +148,11 @@ def test_marks_0_and_1_are_the_older_calls(eng, generated, pool):
     generated set and on random graphs with refused molecules among them"""
     for t in (generated[1], pool):
         for marks, fn in ((0, "mnx_smiles_pack"), (1, "mnx_smiles_pack_stereo")):
-            need = int(run(eng, t, 0, fn=fn, out=None)[4][0])
+            need = int(run(eng, t, 0, fn=fn, out=None).totals[0])
             old, new = run(eng, t, need, fn=fn), run(eng, t, need, marks)
-            assert old[0] == new[0] == 0 and old[4].tolist() == new[4].tolist() == [need, 0]
-            assert old[1].tobytes() == new[1].tobytes() and old[2].tobytes() == new[2].tobytes() and np.array_equal(old[3], new[3])
-            assert not (new[1]["flags"] & 0x1C00).any() and need > 1000
+            same_results(old, new)
+            assert old.rc == new.rc == 0 and old.totals.tolist() == new.totals.tolist() == [need, 0]
+            assert not (new.recs["flags"] & 0x1C00).any() and need > 1000
 
 
 def test_strip_invariants_on_the_device(eng, generated, pool):
@@ -206,10 +162,10 @@ def test_strip_invariants_on_the_device(eng, generated, pool):
     for t in (generated[1], pool):
         got = {}
         for marks in (0, 1, 2, 3):
-            need = int(run(eng, t, 0, marks, out=None)[4][0])
-            rc, recs, order, out, totals = run(eng, t, need, marks)
-            assert rc == 0 and totals.tolist() == [need, 0]
-            got[marks] = (device_texts(recs, out), recs, order)
+            need = int(run(eng, t, 0, marks, out=None).totals[0])
+            a = run(eng, t, need, marks)
+            assert a.rc == 0 and a.totals.tolist() == [need, 0]
+            got[marks] = (device_texts(a.recs, a.out), a.recs, a.order)
         for with_ez, without in ((2, 0), (3, 1)):
             assert [E.strip(s) for s in got[with_ez][0]] == got[without][0]
             assert got[with_ez][2].tobytes() == got[without][2].tobytes()
@@ -229,13 +185,9 @@ def test_refused_calls_launch_nothing_and_name_the_new_function(eng, dev, synth_
     need = E.pack(t.mols, t.atoms, t.bonds, t.text, 3)["total"]
 
     def refused(expect, **over):
-        rc, recs, order, out, totals = run(eng, t, need, **{"marks": 3, **over})
-        msg = eng.lib.mnx_last_error(over.get("h", eng.h)).decode()
-        assert rc == -1 and msg == "mnx_smiles_pack_marks: " + expect, (over, rc, msg)
-        assert np.all(recs.view(np.uint8) == FILL) and np.all(out == FILL) and np.all(totals.view(np.uint8) == FILL), over
-        assert np.all(order == ORDER_FILL), over
+        assert_refused(run(eng, t, need, **{"marks": 3, **over}), "mnx_smiles_pack_marks: " + expect)
 
-    assert run(eng, t, need, 3)[0] == 0
+    assert run(eng, t, need, 3).rc == 0
     for marks in (4, 7, 8, 0x80000002):
         refused("marks may hold MNX_SMILES_MARK_TETRAHEDRAL and MNX_SMILES_MARK_DOUBLE_BOND only", marks=marks)
     for name in ("mols", "atoms", "bonds", "text", "recs", "out", "totals"):

@@ -10,23 +10,9 @@ import torch
 import graph_ref
 from molnextr_amd import weights as W
 from molnextr_amd.engine import ATOM_DTYPE, BOND_DTYPE, MOL_DTYPE, Engine, vocab_text
+from packed_tables import Inputs, _p, call_tables, dev, eng  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-CANARY, GUARD = 0xA5, 64
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def eng(synth_ckpt, dev):
-    e = Engine(synth_ckpt["encoder"], synth_ckpt["decoder"], device=0, max_batch=32, dtype="fp16x3")
-    yield e
-    e.close()
 
 
 @pytest.fixture(scope="module")
@@ -55,29 +41,21 @@ class Case:
         return c
 
 
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
+def call(eng, case, caps, **over):
+    """One mnx_graph_pack call on the dense inputs of `case`: the harness's named result; over: arguments by name"""
+    tk, ln, ai, na, ed, s0, s1, s2 = case.d
+    head = {"tokens": _p(tk), "lengths": _p(ln), "n": case.n, "T": tk.shape[1], "atom_idx": _p(ai), "n_atoms": _p(na), "edges": _p(ed),
+            "kmax": case.kmax, "atom_scores": _p(s0), "edge_scores": _p(s1), "overall": _p(s2)}
+    return call_tables("mnx_graph_pack", eng, Inputs(tk.device, case.n, head), caps, **over)
 
 
 def run_pack(eng, dev, case, caps):
-    """One mnx_graph_pack call into arenas of exactly `caps` records / bytes with GUARD canary bytes behind each; returns
-    (rc, {'mols', 'atoms', 'bonds', 'text', 'totals'} as read back, whole arenas as raw bytes)."""
-    sizes = (caps[0] * ATOM_DTYPE.itemsize, caps[1] * BOND_DTYPE.itemsize, caps[2])
-    arenas = [torch.full((s + GUARD,), CANARY, dtype=torch.uint8, device=dev) for s in sizes]
-    mols = torch.full((case.n * MOL_DTYPE.itemsize + GUARD,), CANARY, dtype=torch.uint8, device=dev)
-    totals = torch.full((4,), -1, dtype=torch.int32, device=dev)
-    tk, ln, ai, na, ed, s0, s1, s2 = case.d
-    rc = eng.lib.mnx_graph_pack(eng.h, _p(tk), _p(ln), case.n, tk.shape[1], _p(ai), _p(na), _p(ed), case.kmax, _p(s0), _p(s1),
-                                _p(s2), _p(mols), _p(arenas[0]), caps[0], _p(arenas[1]), caps[1], _p(arenas[2]), caps[2],
-                                _p(totals), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    raw = [a.cpu().numpy() for a in arenas] + [mols.cpu().numpy()]
-    tot = totals.cpu().numpy().view(np.uint32)
-    out = {"mols": raw[3][:case.n * MOL_DTYPE.itemsize].view(MOL_DTYPE), "totals": tot,
-           "atoms": raw[0][:sizes[0]].view(ATOM_DTYPE), "bonds": raw[1][:sizes[1]].view(BOND_DTYPE), "text": raw[2][:sizes[2]].tobytes()}
-    for r, s in zip(raw, sizes + (case.n * MOL_DTYPE.itemsize,)):
-        assert np.all(r[s:] == CANARY), "bytes behind an arena were overwritten"
-    return rc, out, raw
+    """One mnx_graph_pack call into arenas of exactly `caps` records / bytes with guard bytes behind each; returns
+    (rc, {'mols', 'atoms', 'bonds', 'text', 'totals'} as read back, the arenas as raw bytes)."""
+    got = call(eng, case, caps)
+    out = {"mols": got.mols, "totals": got.totals, "atoms": got.atoms.view(ATOM_DTYPE), "bonds": got.bonds.view(BOND_DTYPE),
+           "text": got.text.tobytes()}
+    return got.rc, out, [got.atoms, got.bonds, got.text, got.mols.view(np.uint8)]
 
 
 def assert_records_equal(got, ref, n_atoms=None, n_bonds=None, n_text=None):
@@ -233,19 +211,8 @@ def test_engine_graph_pack_grows_once(eng, fuzz):
 
 
 def _call(eng, case, **over):
-    tk, ln, ai, na, ed, s0, s1, s2 = case.d
-    dev = tk.device
-    bufs = {"mols": torch.zeros(case.n * 40, dtype=torch.uint8, device=dev), "atoms": torch.zeros(24 * 64, dtype=torch.uint8, device=dev),
-            "bonds": torch.zeros(16 * 64, dtype=torch.uint8, device=dev), "text": torch.zeros(64, dtype=torch.uint8, device=dev),
-            "totals": torch.zeros(4, dtype=torch.int32, device=dev)}
-    a = {"h": eng.h, "tokens": _p(tk), "lengths": _p(ln), "n": case.n, "T": tk.shape[1], "atom_idx": _p(ai), "n_atoms": _p(na),
-         "edges": _p(ed), "kmax": case.kmax, "atom_scores": _p(s0), "edge_scores": _p(s1), "overall": _p(s2),
-         "mols": _p(bufs["mols"]), "atoms": _p(bufs["atoms"]), "atom_cap": 64, "bonds": _p(bufs["bonds"]), "bond_cap": 64,
-         "text": _p(bufs["text"]), "text_cap": 64, "totals": _p(bufs["totals"]), "stream": None}
-    a.update(over)
-    rc = eng.lib.mnx_graph_pack(*a.values())
-    torch.cuda.synchronize()
-    return rc, eng.lib.mnx_last_error(a["h"]).decode()
+    got = call(eng, case, (64, 64, 64), **over)
+    return got.rc, got.error
 
 
 def test_argument_checks(eng, dev, synth_ckpt, tok, hand):

@@ -4,62 +4,30 @@ sizes at which the kernels take another path, the capacity and argument handling
 Engine.predict, predict_pipeline and the facade. The kernel's rounding is never seen at an exact tie here: the engine's 64
 coordinate bins give the odd den = 63, and 2 * bin * S is even (tests/test_molfile_host.py::test_coordinate_rule shows it and
 covers the tie in the oracle with den = 64); the kernel rounds with the same integer expression."""
-import ctypes as C
+import functools
 
 import numpy as np
 import pytest
-import torch
 
 import molfile_ref as R
 import smiles_ref as S
 import test_molfile_host as H
 from molnextr_amd import weights as W
-from molnextr_amd.engine import MOLFILE_DTYPE, Engine
-from packed_tables import FILL, GUARD, POOL, UTF2, Tables, _p, compare, random_molecule
+from molnextr_amd.engine import Engine
+from packed_tables import (FILL, POOL, UTF2, Tables, _p, assert_refused, call_text, compare_text, dev, eng, random_molecule,  # noqa: F401
+                           same_results)
 
 pytestmark = pytest.mark.gpu
 
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def eng(synth_ckpt, dev):
-    e = Engine(synth_ckpt["encoder"], synth_ckpt["decoder"], device=0, max_batch=32, dtype="fp16x3")
-    yield e
-    e.close()
-
-
-def run(eng, t, out_cap, scale=None, sizes=None, **over):
-    """One mnx_molfile_pack call into FILL-filled outputs with GUARD bytes behind `out`: (rc, files, the whole out
-    arena, totals); scale: an int array [n, 2], or a raw pointer passed on as it is"""
-    na, nb, nt = sizes if sizes is not None else (len(t.atoms), len(t.bonds), len(t.text))
-    files = torch.full((t.n * 16 + GUARD,), FILL, dtype=torch.uint8, device=t.dev)
-    out = torch.full((out_cap + GUARD,), FILL, dtype=torch.uint8, device=t.dev)
-    totals = torch.full((8,), FILL, dtype=torch.uint8, device=t.dev)
-    sc = scale if scale is None or isinstance(scale, C.c_void_p) else torch.from_numpy(np.ascontiguousarray(scale, dtype=np.int32)).to(t.dev)
-    a = {"h": eng.h, "mols": _p(t.d[0]), "n": t.n, "atoms": _p(t.d[1]), "na": na, "bonds": _p(t.d[2]), "nb": nb, "text": _p(t.d[3]),
-         "nt": nt, "scale": sc if isinstance(sc, C.c_void_p) else _p(sc), "files": _p(files), "out": _p(out), "out_cap": out_cap, "totals": _p(totals),
-         "stream": C.c_void_p(torch.cuda.current_stream().cuda_stream)}
-    a.update(over)
-    rc = eng.lib.mnx_molfile_pack(*a.values())
-    torch.cuda.synchronize()
-    f, o = files.cpu().numpy(), out.cpu().numpy()
-    assert np.all(f[t.n * 16:] == FILL), "bytes behind files were overwritten"
-    return rc, f[:t.n * 16].view(MOLFILE_DTYPE), o, totals.cpu().numpy().view(np.uint32)
+# run(eng, t, out_cap, sizes=None, **over); the result's `recs` are the `files`; scale: an int array [n, 2] or a raw pointer
+run = functools.partial(call_text, "mnx_molfile_pack")
 
 
 def check(eng, t, scale=None, sizes=None, ref_kw=None):
     """the device's files, bytes and totals equal the oracle's at the exact capacity; returns the oracle's result"""
     kw = dict(zip(("n_atom_records", "n_bond_records", "n_text_bytes"), sizes)) if sizes is not None else {}
     ref = R.pack(t.mols, t.atoms, t.bonds, t.text, scale=scale, **kw, **(ref_kw or {}))
-    rc, files, out, totals = run(eng, t, ref["total"], scale, sizes)
-    assert rc == 0, eng.lib.mnx_last_error(eng.h)
-    assert totals.tolist() == [ref["total"], 0]
-    compare(files, ref["files"], out, ref["out"], ref["total"], "molfiles")
+    compare_text(run(eng, t, ref["total"], sizes, scale=scale), ref, "molfiles")
     return ref
 
 
@@ -167,12 +135,12 @@ def test_capacities(eng, dev):
     ref = R.pack(t.mols, t.atoms, t.bonds, t.text)
     need = ref["total"]
     for cap in (0, need - 1, need // 2, need):
-        rc, files, out, totals = run(eng, t, cap)
-        assert rc == 0 and totals.tolist() == [need, int(cap < need)]
-        assert files.tobytes() == ref["files"].tobytes()
-        assert out[:cap].tobytes() == ref["out"][:cap] and np.all(out[cap:] == FILL), cap
-    rc, files, _, totals = run(eng, t, 0, out=None)             # a sizing call needs no buffer
-    assert rc == 0 and totals.tolist() == [need, 1] and files.tobytes() == ref["files"].tobytes()
+        a = run(eng, t, cap)
+        assert a.rc == 0 and a.totals.tolist() == [need, int(cap < need)]
+        assert a.recs.tobytes() == ref["files"].tobytes()
+        assert a.out[:cap].tobytes() == ref["out"][:cap] and np.all(a.out[cap:] == FILL), cap
+    a = run(eng, t, 0, out=None)                                # a sizing call needs no buffer
+    assert a.rc == 0 and a.totals.tolist() == [need, 1] and a.recs.tobytes() == ref["files"].tobytes()
 
 
 def test_scales_and_clamped_bins(eng, dev):
@@ -198,7 +166,8 @@ def test_two_runs_are_byte_identical(eng, dev):
     t = Tables(dev, [random_molecule(rng, int(k), int(k) + 3) for k in rng.integers(0, 60, 200)])
     need = R.pack(t.mols, t.atoms, t.bonds, t.text)["total"]
     a, b = run(eng, t, need), run(eng, t, need)
-    assert a[0] == b[0] == 0 and a[1].tobytes() == b[1].tobytes() and np.array_equal(a[2], b[2]) and a[3].tolist() == b[3].tolist()
+    same_results(a, b)
+    assert a.rc == b.rc == 0
 
 
 def test_refused_calls_leave_the_outputs_untouched(eng, dev, synth_ckpt):
@@ -207,12 +176,9 @@ def test_refused_calls_leave_the_outputs_untouched(eng, dev, synth_ckpt):
     need = R.pack(t.mols, t.atoms, t.bonds, t.text)["total"]
 
     def refused(expect, **over):
-        rc, files, out, totals = run(eng, t, need, **over)
-        msg = eng.lib.mnx_last_error(over.get("h", eng.h)).decode()
-        assert rc == -1 and msg == "mnx_molfile_pack: " + expect, (over, rc, msg)
-        assert np.all(files.view(np.uint8) == FILL) and np.all(out == FILL) and np.all(totals.view(np.uint8) == FILL), over
+        assert_refused(run(eng, t, need, **over), "mnx_molfile_pack: " + expect)
 
-    assert run(eng, t, need)[0] == 0
+    assert run(eng, t, need).rc == 0
     for name in ("mols", "atoms", "bonds", "text", "files", "out", "totals"):
         refused("null pointer", **{name: None})
     for n in (0, -1, 65537):
@@ -248,13 +214,13 @@ def test_refused_calls_leave_the_outputs_untouched(eng, dev, synth_ckpt):
         assert set_tables(b"R1Ac", ok[1], ok[2], 2)[0] == -1                          # a refused table leaves the last one in place
         two = Tables(dev, [([b"[Ac]", b"[R1]", b"[OMe]", b"Ph"], [(1, 1)] * 4, [])])
         ref = R.pack(two.mols, two.atoms, two.bonds, two.text, tables={b"Ac": 2, b"R1": 1})
-        rc, files, out, totals = run(eng, two, ref["total"], h=bare.h)
-        assert rc == 0 and out[:ref["total"]].tobytes() == ref["out"] and files.tobytes() == ref["files"].tobytes()
+        a = run(eng, two, ref["total"], h=bare.h)
+        assert a.rc == 0 and a.out[:ref["total"]].tobytes() == ref["out"] and a.recs.tobytes() == ref["files"].tobytes()
         assert ref["out"].count(b"\nA  ") == 4 and b"M  RGP  1   2   1" in ref["out"]   # 'OMe', 'Ph': no table, no parse
         assert lib.mnx_set_symbol_tables(bare.h, None, None, None, 0) == 0            # no names at all: everything is parsed
         ref = R.pack(two.mols, two.atoms, two.bonds, two.text, tables={})
-        rc, files, out, _ = run(eng, two, ref["total"], h=bare.h)
-        assert rc == 0 and out[:ref["total"]].tobytes() == ref["out"] and b" Ac " in ref["out"] and b"M  RGP" not in ref["out"]
+        a = run(eng, two, ref["total"], h=bare.h)
+        assert a.rc == 0 and a.out[:ref["total"]].tobytes() == ref["out"] and b" Ac " in ref["out"] and b"M  RGP" not in ref["out"]
     finally:
         bare.close()
 

@@ -3,7 +3,7 @@ records field by field and all four tables and `atom_notes` byte for byte (no to
 molecules, the sizes at which the kernel's loops take another turn, the refusals, the capacity protocol, determinism, every argument
 error, the chains read -> normalize -> canonical writer and expand -> normalize, one end-to-end run and evaluate's
 --graph_normalize. The rule is the project's own (include/molnextr_hip.h): no toolkit has checked it."""
-import ctypes as C
+import functools
 import json
 
 import numpy as np
@@ -15,87 +15,24 @@ import normalize_ref as N
 import test_normalize_host as H
 from molnextr_amd import evaluate as E
 from molnextr_amd import weights as W
-from molnextr_amd.engine import (ATOM_DTYPE, BOND_DTYPE, MOL_AROMATIZED, MOL_DTYPE, MOL_NORMALIZE_REFUSED, MOL_UNBRACKETED, NOTE_H_MASK,
-                                 SMILES_REFUSED, Engine)
+from molnextr_amd.engine import MOL_AROMATIZED, MOL_NORMALIZE_REFUSED, MOL_UNBRACKETED, NOTE_H_MASK, SMILES_REFUSED, Engine
 from molnextr_amd.model import canonical_smiles, predict_pipeline
 from molnextr_amd.shard import MAX_LEN, pack_records
-from packed_tables import FILL, GUARD, Tables, _p
+from packed_tables import (FILL, Tables, _p, assert_refused, call_tables, clean, compare_tables, dev, eng, mol, path, same_mols,  # noqa: F401
+                           same_results)
 
 pytestmark = pytest.mark.gpu
 TABLES = H.TABLES
 
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def eng(synth_ckpt, dev):
-    e = Engine(synth_ckpt["encoder"], synth_ckpt["decoder"], device=0, max_batch=32, dtype="fp16x3")
-    yield e
-    e.close()
-
-
-def clean(a):
-    """the records of a structured array as the device writes them: padding bytes as zeros"""
-    z = np.zeros(len(a), a.dtype)
-    for name in a.dtype.names:
-        z[name] = a[name]
-    return z.tobytes()
-
-
-def run(eng, t, caps, **over):
-    """One call into FILL-filled outputs with GUARD bytes behind each capacity: (rc, mols, atoms bytes, bonds bytes, text bytes,
-    notes bytes, totals), each table as the whole arena"""
-    sizes = (t.n * MOL_DTYPE.itemsize, caps[0] * ATOM_DTYPE.itemsize, caps[1] * BOND_DTYPE.itemsize, caps[2], caps[0], 16)
-    bufs = [torch.full((s + GUARD,), FILL, dtype=torch.uint8, device=t.dev) for s in sizes]
-    a = {"h": eng.h, "mols": _p(t.d[0]), "n": t.n, "atoms": _p(t.d[1]), "na": len(t.atoms), "bonds": _p(t.d[2]), "nb": len(t.bonds),
-         "text": _p(t.d[3]), "nt": len(t.text), "mols_out": _p(bufs[0]), "atoms_out": _p(bufs[1]), "atom_cap": caps[0],
-         "bonds_out": _p(bufs[2]), "bond_cap": caps[1], "text_out": _p(bufs[3]), "text_cap": caps[2], "atom_notes": _p(bufs[4]),
-         "totals": _p(bufs[5]), "stream": C.c_void_p(torch.cuda.current_stream().cuda_stream)}
-    a.update(over)
-    rc = eng.lib.mnx_normalize_pack(*a.values())
-    torch.cuda.synchronize()
-    host = [b.cpu().numpy() for b in bufs]
-    for h, s, what in zip(host, sizes, ("mols_out", "atoms_out", "bonds_out", "text_out", "atom_notes", "totals")):
-        assert np.all(h[s:] == FILL), f"bytes behind {what} were overwritten"
-    return (rc, host[0][:sizes[0]].view(MOL_DTYPE), host[1][:sizes[1]], host[2][:sizes[2]], host[3][:sizes[3]], host[4][:sizes[4]],
-            host[5][:16].view(np.uint32))
-
-
-def same_mols(got, want):
-    for name in MOL_DTYPE.names:
-        bad = np.nonzero(got[name] != want[name])[0]
-        assert bad.size == 0, (name, bad[:5], got[name][bad[:5]], want[name][bad[:5]])
+run = functools.partial(call_tables, "mnx_normalize_pack")    # run(eng, t, caps, **over); the result's `side` is `atom_notes`
 
 
 def check(eng, t, ref=None, **cut):
     """the device's tables equal the oracle's at the exact capacities, byte for byte; returns the oracle's"""
     ref = ref or N.pack(t.mols, t.atoms, t.bonds, t.text, tables=TABLES, n_atom_records=cut.get("na"), n_bond_records=cut.get("nb"),
                         n_text_bytes=cut.get("nt"))
-    rc, mols, atoms, bonds, text, notes, totals = run(eng, t, ref["totals"], **cut)
-    assert rc == 0, eng.lib.mnx_last_error(eng.h)
-    assert totals.tolist() == list(ref["totals"]) + [0]
-    same_mols(mols, ref["mols"])
-    assert mols.tobytes() == clean(ref["mols"])
-    assert text.tobytes() == ref["text"], (text.tobytes()[:200], ref["text"][:200])
-    for got, want, size, what in ((atoms, ref["atoms"], 24, "atom"), (bonds, ref["bonds"], 16, "bond")):
-        want = np.frombuffer(clean(want), np.uint8)
-        bad = np.nonzero(got != want)[0]
-        assert bad.size == 0, (what, "record", bad[0] // size, got[bad[0] // size * size:][:size], want[bad[0] // size * size:][:size])
-    bad = np.nonzero(notes != ref["atom_notes"])[0]
-    assert bad.size == 0, ("atom_notes", bad[:5], notes[bad[:5]], ref["atom_notes"][bad[:5]])
+    compare_tables(run(eng, t, ref["totals"], **cut), ref, "atom_notes")
     return ref
-
-
-def mol(symbols, bonds=()):
-    return list(symbols), [(3 * k % 64, 5 * k % 64) for k in range(len(symbols))], [tuple(b) for b in bonds]
-
-
-def path(n, ty=1, first=0):
-    return [(first + k, first + k + 1, ty, ty) for k in range(n - 1)]
 
 
 def hand_strings():
@@ -137,8 +74,7 @@ def test_1025_generated_molecules_and_two_runs_with_identical_bytes(eng, batch):
     assert (flags & MOL_AROMATIZED).astype(bool).sum() > 100 and (flags & MOL_UNBRACKETED).astype(bool).sum() > 100
     assert (ref["atom_notes"] & 64).any() and not (flags & MOL_NORMALIZE_REFUSED).any()
     check(eng, t, ref)
-    first, second = run(eng, t, ref["totals"]), run(eng, t, ref["totals"])
-    assert all(a.tobytes() == b.tobytes() for a, b in zip(first[1:], second[1:]))
+    same_results(run(eng, t, ref["totals"]), run(eng, t, ref["totals"]))
 
 
 def acene(rings, first=0):
@@ -233,16 +169,16 @@ def test_capacities_exact_and_one_short(eng, batch):
     for k in range(3):
         caps = list(full)
         caps[k] -= 1
-        rc, mols, atoms, bonds, text, notes, totals = run(eng, t, caps)            # run() checks the FILL bytes behind every capacity
-        assert rc == 0 and totals.tolist() == full + [1]
-        same_mols(mols, ref["mols"])
-        for got, want in zip((atoms, bonds, text, notes), exact):
+        a = run(eng, t, caps)                                                      # run() checks the FILL bytes behind every capacity
+        assert a.rc == 0 and a.totals.tolist() == full + [1]
+        same_mols(a.mols, ref["mols"])
+        for got, want in zip((a.atoms, a.bonds, a.text, a.side), exact):
             assert np.array_equal(got, want[:len(got)])
-    rc, mols, atoms, bonds, text, notes, totals = run(eng, t, (0, 0, 0), atoms_out=None, bonds_out=None, text_out=None, atom_notes=None)
-    assert rc == 0 and totals.tolist() == full + [1]                               # the sizing call
-    same_mols(mols, ref["mols"])
-    rc, mols, atoms, bonds, text, notes, totals = run(eng, t, full, atom_notes=None)   # the notes are optional
-    assert rc == 0 and totals.tolist() == full + [0] and np.all(notes == FILL) and text.tobytes() == ref["text"]
+    a = run(eng, t, (0, 0, 0), atoms_out=None, bonds_out=None, text_out=None, atom_notes=None)
+    assert a.rc == 0 and a.totals.tolist() == full + [1]                           # the sizing call
+    same_mols(a.mols, ref["mols"])
+    a = run(eng, t, full, atom_notes=None)                                         # the notes are optional
+    assert a.rc == 0 and a.totals.tolist() == full + [0] and np.all(a.side == FILL) and a.text.tobytes() == ref["text"]
 
 
 def test_engine_normalize_pack_sizes_itself(eng, batch):
@@ -259,10 +195,7 @@ def test_argument_errors(eng, dev, synth_ckpt):
     t = Tables(dev, [mol([b"C", b"[CH3]"], path(2))])
 
     def refused(expect, **over):
-        rc = run(eng, t, (64, 64, 64), **over)
-        assert rc[0] == -1 and all(np.all(x == FILL) for x in rc[2:6]) and np.all(rc[1].view(np.uint8) == FILL)
-        msg = eng.lib.mnx_last_error(eng.h).decode()
-        assert msg == "mnx_normalize_pack: " + expect, msg
+        assert_refused(run(eng, t, (64, 64, 64), **over), "mnx_normalize_pack: " + expect)
 
     for name in ("mols", "atoms", "bonds", "text", "mols_out", "atoms_out", "bonds_out", "text_out", "totals"):
         refused("null pointer", **{name: None})
@@ -273,9 +206,9 @@ def test_argument_errors(eng, dev, synth_ckpt):
         refused(aligned, **{name: _p(t.d[k], 4)})
     refused(aligned, totals=_p(t.d[0], 2))
     odd = torch.zeros(80, dtype=torch.uint8, device=dev)
-    assert run(eng, t, (64, 64, 64), atom_notes=_p(odd, 1))[0] == 0                # a byte array needs no alignment
+    assert run(eng, t, (64, 64, 64), atom_notes=_p(odd, 1)).rc == 0                # a byte array needs no alignment
     assert odd.cpu().tolist()[:4] == [0, 3, 3 | 32, 0]
-    assert run(eng, t, (0, 0, 0), atoms_out=None, bonds_out=None, text_out=None)[0] == 0      # a table of capacity 0 may be null
+    assert run(eng, t, (0, 0, 0), atoms_out=None, bonds_out=None, text_out=None).rc == 0      # a table of capacity 0 may be null
 
     class Bare(Engine):                                                            # a fresh handle that was told no tables
         def _set_symbol_tables(self):
@@ -285,7 +218,7 @@ def test_argument_errors(eng, dev, synth_ckpt):
             pass
     bare = Bare(synth_ckpt["encoder"], synth_ckpt["decoder"], device=0, max_batch=2, dec_slots=32)
     try:
-        assert run(bare, t, (64, 64, 64))[0] == -1
+        assert run(bare, t, (64, 64, 64)).rc == -1
         assert bare.lib.mnx_last_error(bare.h) == b"mnx_normalize_pack: call mnx_set_symbol_tables first"
         Engine._set_symbol_tables(bare)                                            # no fragments are needed
         check(bare, t)

@@ -2,74 +2,35 @@
 tests/smiles_ref.py, byte for byte and record for record, `order` included (no tolerances), on hand-built tables uploaded with
 torch: the sizes at which the kernels take another path, the limits of the walk and of the ring numbers, the capacity and
 argument handling, and one end-to-end run through Engine.predict, predict_pipeline and the facade."""
-import ctypes as C
+import functools
 
 import numpy as np
 import pytest
-import torch
 
-import molfile_ref as M
+import packed_tables as P
 import smiles_ref as S
 import test_smiles_host as H
 from molnextr_amd import weights as W
-from molnextr_amd.engine import SMILES_DTYPE, SMILES_REFUSED, Engine
-from packed_tables import FILL, GUARD, POOL, Tables, _p, compare, random_molecule
+from molnextr_amd.engine import SMILES_REFUSED, Engine
+from packed_tables import FILL, POOL, Tables, _p, assert_refused, compare_text, dev, eng, random_molecule, same_results  # noqa: F401
+from packed_tables import WORD_FILL as ORDER_FILL
 
 pytestmark = pytest.mark.gpu
 
-ORDER_FILL = FILL | FILL << 8
 # Images 500..507, the batch the molfile test takes: its molecules of 12 and 10 atoms (images 503 and 507, complete graphs like
 # all of them) stay under 99 ring numbers and get a string; two of 25 atoms are refused for ring numbers, four for > 999 bonds.
 E2E_FIRST_INDEX = 500
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def eng(synth_ckpt, dev):
-    e = Engine(synth_ckpt["encoder"], synth_ckpt["decoder"], device=0, max_batch=32, dtype="fp16x3")
-    yield e
-    e.close()
-
-
-def mol(syms, bonds):
-    return syms, [(0, 0)] * len(syms), bonds
-
-
-def run(eng, t, out_cap, sizes=None, **over):
-    """One mnx_smiles_pack call into FILL-filled outputs with GUARD bytes behind each: (rc, recs, order, the whole out arena,
-    totals)"""
-    na, nb, nt = sizes if sizes is not None else (len(t.atoms), len(t.bonds), len(t.text))
-    recs = torch.full((t.n * 16 + GUARD,), FILL, dtype=torch.uint8, device=t.dev)
-    order = torch.full((na * 2 + GUARD,), FILL, dtype=torch.uint8, device=t.dev)
-    out = torch.full((out_cap + GUARD,), FILL, dtype=torch.uint8, device=t.dev)
-    totals = torch.full((8,), FILL, dtype=torch.uint8, device=t.dev)
-    a = {"h": eng.h, "mols": _p(t.d[0]), "n": t.n, "atoms": _p(t.d[1]), "na": na, "bonds": _p(t.d[2]), "nb": nb, "text": _p(t.d[3]),
-         "nt": nt, "recs": _p(recs), "order": _p(order), "out": _p(out), "out_cap": out_cap, "totals": _p(totals),
-         "stream": C.c_void_p(torch.cuda.current_stream().cuda_stream)}
-    a.update(over)
-    rc = eng.lib.mnx_smiles_pack(*a.values())
-    torch.cuda.synchronize()
-    r, o, w = recs.cpu().numpy(), out.cpu().numpy(), order.cpu().numpy()
-    assert np.all(r[t.n * 16:] == FILL), "bytes behind recs were overwritten"
-    assert np.all(w[na * 2:] == FILL), "bytes behind order were overwritten"
-    return rc, r[:t.n * 16].view(SMILES_DTYPE), w[:na * 2].view(np.uint16), o, totals.cpu().numpy().view(np.uint32)
+mol = functools.partial(P.mol, flat=True)                     # the plain writer reads no coordinates: every atom at (0, 0)
+run = functools.partial(P.call_text, "mnx_smiles_pack")       # run(eng, t, out_cap, sizes=None, **over)
 
 
 def check(eng, t, sizes=None, ref_kw=None):
     """the device's recs, order, bytes and totals equal the oracle's at the exact capacity; returns the oracle's result"""
     kw = dict(zip(("n_atom_records", "n_bond_records", "n_text_bytes"), sizes)) if sizes is not None else {}
     ref = S.pack(t.mols, t.atoms, t.bonds, t.text, order_fill=ORDER_FILL, **kw, **(ref_kw or {}))
-    rc, recs, order, out, totals = run(eng, t, ref["total"], sizes)
-    assert rc == 0, eng.lib.mnx_last_error(eng.h)
-    assert totals.tolist() == [ref["total"], 0]
-    compare(recs, ref["recs"], out, ref["out"], ref["total"], "SMILES")
-    bad = np.nonzero(order != ref["order"])[0]
-    assert bad.size == 0, ("order", bad[:5], order[bad[:5]], ref["order"][bad[:5]])
+    compare_text(run(eng, t, ref["total"], sizes), ref, "SMILES")
     return ref
 
 
@@ -187,15 +148,15 @@ def test_capacities(eng, dev):
     ref = S.pack(t.mols, t.atoms, t.bonds, t.text)
     need = ref["total"]
     for cap in (0, need - 1, need // 2, need):
-        rc, recs, order, out, totals = run(eng, t, cap)
-        assert rc == 0 and totals.tolist() == [need, int(cap < need)]
-        assert recs.tobytes() == ref["recs"].tobytes() and order.tobytes() == ref["order"].tobytes()
-        assert out[:cap].tobytes() == ref["out"][:cap] and np.all(out[cap:] == FILL), cap
-    rc, recs, order, _, totals = run(eng, t, 0, out=None)       # a sizing call needs no buffer
-    assert rc == 0 and totals.tolist() == [need, 1] and recs.tobytes() == ref["recs"].tobytes() and order.tobytes() == ref["order"].tobytes()
-    rc, recs, order, out, totals = run(eng, t, need, order=None)
-    assert rc == 0 and totals.tolist() == [need, 0] and recs.tobytes() == ref["recs"].tobytes() and np.all(order == ORDER_FILL)
-    assert out[:need].tobytes() == ref["out"]
+        a = run(eng, t, cap)
+        assert a.rc == 0 and a.totals.tolist() == [need, int(cap < need)]
+        assert a.recs.tobytes() == ref["recs"].tobytes() and a.order.tobytes() == ref["order"].tobytes()
+        assert a.out[:cap].tobytes() == ref["out"][:cap] and np.all(a.out[cap:] == FILL), cap
+    a = run(eng, t, 0, out=None)                                # a sizing call needs no buffer
+    assert a.rc == 0 and a.totals.tolist() == [need, 1] and a.recs.tobytes() == ref["recs"].tobytes() and a.order.tobytes() == ref["order"].tobytes()
+    a = run(eng, t, need, order=None)
+    assert a.rc == 0 and a.totals.tolist() == [need, 0] and a.recs.tobytes() == ref["recs"].tobytes() and np.all(a.order == ORDER_FILL)
+    assert a.out[:need].tobytes() == ref["out"]
 
 
 def test_two_runs_are_byte_identical(eng, dev):
@@ -203,8 +164,8 @@ def test_two_runs_are_byte_identical(eng, dev):
     t = Tables(dev, [H.random_graph(rng, int(k), int(k) + 3) for k in rng.integers(0, 60, 200)])
     need = S.pack(t.mols, t.atoms, t.bonds, t.text)["total"]
     a, b = run(eng, t, need), run(eng, t, need)
-    assert a[0] == b[0] == 0 and a[1].tobytes() == b[1].tobytes() and a[2].tobytes() == b[2].tobytes()
-    assert np.array_equal(a[3], b[3]) and a[4].tolist() == b[4].tolist() == [need, 0]
+    same_results(a, b)
+    assert a.rc == b.rc == 0 and a.totals.tolist() == b.totals.tolist() == [need, 0]
 
 
 def test_refused_calls_leave_the_outputs_untouched(eng, dev, synth_ckpt):
@@ -213,13 +174,9 @@ def test_refused_calls_leave_the_outputs_untouched(eng, dev, synth_ckpt):
     need = S.pack(t.mols, t.atoms, t.bonds, t.text)["total"]
 
     def refused(expect, **over):
-        rc, recs, order, out, totals = run(eng, t, need, **over)
-        msg = eng.lib.mnx_last_error(over.get("h", eng.h)).decode()
-        assert rc == -1 and msg == "mnx_smiles_pack: " + expect, (over, rc, msg)
-        assert np.all(recs.view(np.uint8) == FILL) and np.all(out == FILL) and np.all(totals.view(np.uint8) == FILL), over
-        assert np.all(order == ORDER_FILL), over
+        assert_refused(run(eng, t, need, **over), "mnx_smiles_pack: " + expect)
 
-    assert run(eng, t, need)[0] == 0
+    assert run(eng, t, need).rc == 0
     for name in ("mols", "atoms", "bonds", "text", "recs", "out", "totals"):
         refused("null pointer", **{name: None})
     for n in (0, -1, 65537):
@@ -241,8 +198,8 @@ def test_refused_calls_leave_the_outputs_untouched(eng, dev, synth_ckpt):
         assert bare.lib.mnx_set_symbol_tables(bare.h, ok[0], ok[1].ctypes.data, ok[2].ctypes.data, 2) == 0
         two = Tables(dev, [mol([b"[Ac]", b"[R1]", b"[OMe]", b"[R2]"], H.path(4))])
         ref = S.pack(two.mols, two.atoms, two.bonds, two.text, tables={b"Ac": 2, b"R1": 1})
-        rc, recs, order, out, _ = run(eng, two, ref["total"], h=bare.h)
-        assert rc == 0 and out[:ref["total"]].tobytes() == ref["out"] == b"*[1*]**" and recs.tobytes() == ref["recs"].tobytes()
+        a = run(eng, two, ref["total"], h=bare.h)
+        assert a.rc == 0 and a.out[:ref["total"]].tobytes() == ref["out"] == b"*[1*]**" and a.recs.tobytes() == ref["recs"].tobytes()
     finally:
         bare.close()
 

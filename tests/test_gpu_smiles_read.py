@@ -3,42 +3,26 @@ tests/smiles_read_ref.py, records field by field and tables byte for byte (no to
 capacity: the smallest shapes at which the kernel takes another turn (one byte, 255 / 256 / 257 bytes around the workgroup, the
 4096-byte and 999-atom limits, deep nesting, every ring number), every refusal, the capacity protocol, determinism, the argument
 errors, and the chains into the writers on the device."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
-import canon_ref as K
 import molfile_ref as M
 import smiles_read_ref as R
 import smiles_ref as S
 import test_smiles_read_host as H
-from molnextr_amd.engine import ATOM_DTYPE, BOND_DTYPE, MOL_DTYPE, READ_DTYPE, READ_REFUSED, Engine
-from packed_tables import FILL, GUARD, _p
+from molnextr_amd.engine import READ_DTYPE, READ_REFUSED, Engine
+from packed_tables import Inputs, _p, assert_refused, call_tables, clean, compare_tables, dev, same_results  # noqa: F401
+from packed_tables import same_mols as same
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def eng(synth_ckpt, dev):
+def eng(synth_ckpt, dev):                                    # the reader needs no room for images: an engine of its own, max_batch 4
     e = Engine(synth_ckpt["encoder"], synth_ckpt["decoder"], device=0, max_batch=4, dtype="fp16x3")
     yield e
     e.close()
-
-
-def clean(a):
-    """the records of a structured array as the device writes them: padding bytes as zeros"""
-    z = np.zeros(len(a), a.dtype)
-    for name in a.dtype.names:
-        z[name] = a[name]
-    return z.tobytes()
 
 
 def arena_of(strings):
@@ -48,30 +32,15 @@ def arena_of(strings):
 
 
 def run(eng, dev, arena, offs, caps, tail=8, **over):
-    """One call into FILL-filled outputs with GUARD bytes behind each capacity: (rc, mols, recs, atoms bytes, bonds bytes, text
-    bytes, totals). The arena is uploaded with `tail` spare bytes behind it."""
-    n = len(offs) - 1
+    """One mnx_smiles_read call, the arena uploaded with `tail` spare bytes behind it; the result's `side` are the recs' bytes"""
     d_bytes = torch.frombuffer(bytearray(arena) + bytearray(b"[" * tail), dtype=torch.uint8).to(dev) if len(arena) + tail else None
     d_off = torch.from_numpy(np.asarray(offs, np.uint32).view(np.int32).copy()).to(dev)
-    sizes = (n * MOL_DTYPE.itemsize, n * READ_DTYPE.itemsize, caps[0] * ATOM_DTYPE.itemsize, caps[1] * BOND_DTYPE.itemsize, caps[2], 16)
-    bufs = [torch.full((s + GUARD,), FILL, dtype=torch.uint8, device=dev) for s in sizes]
-    a = {"h": eng.h, "bytes": _p(d_bytes), "n_bytes": len(arena), "offsets": _p(d_off), "n": n, "mols": _p(bufs[0]), "recs": _p(bufs[1]),
-         "atoms": _p(bufs[2]), "atom_cap": caps[0], "bonds": _p(bufs[3]), "bond_cap": caps[1], "text": _p(bufs[4]), "text_cap": caps[2],
-         "totals": _p(bufs[5]), "stream": C.c_void_p(torch.cuda.current_stream().cuda_stream)}
-    a.update(over)
-    rc = eng.lib.mnx_smiles_read(*a.values())
-    torch.cuda.synchronize()
-    host = [b.cpu().numpy() for b in bufs]
-    for h, s, what in zip(host, sizes, ("mols", "recs", "atoms", "bonds", "text", "totals")):
-        assert np.all(h[s:] == FILL), f"bytes behind {what} were overwritten"
-    return (rc, host[0][:sizes[0]].view(MOL_DTYPE), host[1][:sizes[1]].view(READ_DTYPE), host[2][:sizes[2]], host[3][:sizes[3]],
-            host[4][:sizes[4]], host[5][:16].view(np.uint32))
+    head = {"bytes": _p(d_bytes), "n_bytes": len(arena), "offsets": _p(d_off), "n": len(offs) - 1}
+    return call_tables("mnx_smiles_read", eng, Inputs(dev, len(offs) - 1, head), caps, **over)
 
 
-def same(got, want):
-    for name in got.dtype.names:
-        bad = np.nonzero(got[name] != want[name])[0]
-        assert bad.size == 0, (name, bad[:5], got[name][bad[:5]], want[name][bad[:5]])
+def recs_of(got):
+    return got.side.view(READ_DTYPE)
 
 
 def check(eng, dev, strings=None, ref=None, arena=None, offsets=None, n_bytes=None):
@@ -80,17 +49,7 @@ def check(eng, dev, strings=None, ref=None, arena=None, offsets=None, n_bytes=No
         arena, offsets = arena_of(strings)
     ref = ref or R.pack(strings, arena=arena, offsets=offsets, n_bytes=n_bytes)
     over = {} if n_bytes is None else {"n_bytes": n_bytes}
-    rc, mols, recs, atoms, bonds, text, totals = run(eng, dev, arena, offsets, ref["totals"], **over)
-    assert rc == 0, eng.lib.mnx_last_error(eng.h)
-    assert totals.tolist() == list(ref["totals"]) + [0]
-    same(recs, ref["recs"])
-    same(mols, ref["mols"])
-    assert mols.tobytes() == clean(ref["mols"]) and recs.tobytes() == ref["recs"].tobytes()
-    for got, want, size, what in ((atoms, ref["atoms"], 24, "atom"), (bonds, ref["bonds"], 16, "bond")):
-        want = np.frombuffer(clean(want), np.uint8)
-        bad = np.nonzero(got != want)[0]
-        assert bad.size == 0, (what, "record", bad[0] // size, got[bad[0] // size * size:][:size], want[bad[0] // size * size:][:size])
-    assert text.tobytes() == ref["text"]
+    compare_tables(run(eng, dev, arena, offsets, ref["totals"], **over), ref, "recs")
     return ref
 
 
@@ -176,8 +135,8 @@ def test_offsets_beyond_the_bytes_and_an_open_bracket_as_the_last_byte(eng, dev)
     ref = R.pack([b"CC", b"C["])
     assert ref["recs"]["flags"].tolist() == [0, R.SYNTAX] and ref["recs"]["err_pos"].tolist() == [0, 1]
     check(eng, dev, ref=ref, arena=arena, offsets=offsets)
-    rc = run(eng, dev, arena, offsets, ref["totals"], tail=0)                        # and with nothing allocated behind it
-    assert rc[0] == 0 and rc[2]["flags"].tolist() == [0, R.SYNTAX]
+    a = run(eng, dev, arena, offsets, ref["totals"], tail=0)                         # and with nothing allocated behind it
+    assert a.rc == 0 and recs_of(a)["flags"].tolist() == [0, R.SYNTAX]
 
 
 @pytest.fixture(scope="module")
@@ -200,8 +159,7 @@ def test_1025_strings_and_two_runs_with_identical_bytes(eng, dev, batch):
     assert 40 < (ref["recs"]["flags"] & R.SYNTAX).astype(bool).sum() < 110
     check(eng, dev, texts, ref)
     arena, offsets = arena_of(texts)
-    first, second = run(eng, dev, arena, offsets, ref["totals"]), run(eng, dev, arena, offsets, ref["totals"])
-    assert all(a.tobytes() == b.tobytes() for a, b in zip(first[1:], second[1:]))
+    same_results(run(eng, dev, arena, offsets, ref["totals"]), run(eng, dev, arena, offsets, ref["totals"]))
 
 
 def test_capacities_one_short_then_exact(eng, dev, batch):
@@ -214,15 +172,15 @@ def test_capacities_one_short_then_exact(eng, dev, batch):
     for k in range(3):
         caps = list(full)
         caps[k] -= 1
-        rc, mols, recs, atoms, bonds, text, totals = run(eng, dev, arena, offsets, caps)     # run() checks the guard bytes
-        assert rc == 0 and totals.tolist() == full + [1]
-        same(mols, ref["mols"])
-        same(recs, ref["recs"])
-        for got, want in zip((atoms, bonds, text), exact):
+        a = run(eng, dev, arena, offsets, caps)                                          # run() checks the guard bytes
+        assert a.rc == 0 and a.totals.tolist() == full + [1]
+        same(a.mols, ref["mols"])
+        same(recs_of(a), ref["recs"])
+        for got, want in zip((a.atoms, a.bonds, a.text), exact):
             assert np.array_equal(got, want[:len(got)])
-    rc, mols, recs, atoms, bonds, text, totals = run(eng, dev, arena, offsets, (0, 0, 0), atoms=None, bonds=None, text=None)
-    assert rc == 0 and totals.tolist() == full + [1]
-    same(mols, ref["mols"])
+    a = run(eng, dev, arena, offsets, (0, 0, 0), atoms=None, bonds=None, text=None)
+    assert a.rc == 0 and a.totals.tolist() == full + [1]
+    same(a.mols, ref["mols"])
     check(eng, dev, texts, ref)
 
 
@@ -242,10 +200,7 @@ def test_argument_errors(eng, dev):
     d_off = torch.from_numpy(offsets.view(np.int32).copy()).to(dev)
 
     def refused(expect, **over):
-        rc = run(eng, dev, arena, offsets, (16, 16, 16), **over)
-        assert rc[0] == -1 and all(np.all(x == FILL) for x in rc[3:6]) and np.all(rc[1].view(np.uint8) == FILL) and np.all(rc[2].view(np.uint8) == FILL)
-        msg = eng.lib.mnx_last_error(eng.h).decode()
-        assert msg == "mnx_smiles_read: " + expect, msg
+        assert_refused(run(eng, dev, arena, offsets, (16, 16, 16), **over), "mnx_smiles_read: " + expect)
 
     for name in ("bytes", "offsets", "mols", "recs", "atoms", "bonds", "text", "totals"):
         refused("null pointer", **{name: None})
@@ -256,7 +211,7 @@ def test_argument_errors(eng, dev):
     for name, off in (("mols", 4), ("atoms", 4), ("bonds", 4), ("recs", 2), ("totals", 2)):
         refused(aligned, **{name: _p(spare, off)})
     refused(aligned, offsets=_p(d_off, 2))
-    assert run(eng, dev, b"", [0, 0], (0, 0, 0), tail=0, atoms=None, bonds=None, text=None)[0] == 0     # no bytes at all: nothing may be null-checked
+    assert run(eng, dev, b"", [0, 0], (0, 0, 0), tail=0, atoms=None, bonds=None, text=None).rc == 0     # no bytes at all: nothing may be null-checked
 
 
 def test_write_read_write_on_the_device(eng, batch):

@@ -2,37 +2,21 @@
 tests/stereo_ref.py, byte for byte and record for record, `order` included (no tolerances): the strings that pin the rule, the
 generated molecules of the CPU tests, the sizes at which the kernel's loops take another turn, the capacity and argument
 handling of the sibling call, the property that removing the marks gives mnx_smiles_pack's output, and one end-to-end run."""
-import ctypes as C
-
 import numpy as np
 import pytest
-import torch
 
-import molfile_ref as M
 import smiles_ref as S
 import stereo_ref as T
 import test_stereo_host as H
 from molnextr_amd import weights as W
-from molnextr_amd.engine import SMILES_DTYPE, SMILES_REFUSED, SMILES_STEREO, SMILES_STEREO_UNRESOLVED, Engine
-from packed_tables import FILL, GUARD, POOL, Tables, _p, compare, random_molecule
+from molnextr_amd.engine import SMILES_REFUSED, SMILES_STEREO, SMILES_STEREO_UNRESOLVED, Engine
+from packed_tables import (FILL, Tables, _p, assert_refused, call_text, compare_text, dev, device_texts, eng, random_molecule,  # noqa: F401
+                           same_results, texts)
+from packed_tables import WORD_FILL as ORDER_FILL
 
 pytestmark = pytest.mark.gpu
 
-ORDER_FILL = FILL | FILL << 8
 E2E_FIRST_INDEX = 500          # the batch of the plain writer's end-to-end test: two of its eight molecules are written
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def eng(synth_ckpt, dev):
-    e = Engine(synth_ckpt["encoder"], synth_ckpt["decoder"], device=0, max_batch=32, dtype="fp16x3")
-    yield e
-    e.close()
 
 
 @pytest.fixture(scope="module")
@@ -43,38 +27,14 @@ def generated(dev):
 
 
 def run(eng, t, out_cap, fn="mnx_smiles_pack_stereo", **over):
-    """One call into FILL-filled outputs with GUARD bytes behind each: (rc, recs, order, the whole out arena, totals)"""
-    na, nb, nt = len(t.atoms), len(t.bonds), len(t.text)
-    recs = torch.full((t.n * 16 + GUARD,), FILL, dtype=torch.uint8, device=t.dev)
-    order = torch.full((na * 2 + GUARD,), FILL, dtype=torch.uint8, device=t.dev)
-    out = torch.full((out_cap + GUARD,), FILL, dtype=torch.uint8, device=t.dev)
-    totals = torch.full((8,), FILL, dtype=torch.uint8, device=t.dev)
-    a = {"h": eng.h, "mols": _p(t.d[0]), "n": t.n, "atoms": _p(t.d[1]), "na": na, "bonds": _p(t.d[2]), "nb": nb, "text": _p(t.d[3]),
-         "nt": nt, "recs": _p(recs), "order": _p(order), "out": _p(out), "out_cap": out_cap, "totals": _p(totals),
-         "stream": C.c_void_p(torch.cuda.current_stream().cuda_stream)}
-    a.update(over)
-    rc = getattr(eng.lib, fn)(*a.values())
-    torch.cuda.synchronize()
-    r, o, w = recs.cpu().numpy(), out.cpu().numpy(), order.cpu().numpy()
-    assert np.all(r[t.n * 16:] == FILL), "bytes behind recs were overwritten"
-    assert np.all(w[na * 2:] == FILL), "bytes behind order were overwritten"
-    return rc, r[:t.n * 16].view(SMILES_DTYPE), w[:na * 2].view(np.uint16), o, totals.cpu().numpy().view(np.uint32)
+    return call_text(fn, eng, t, out_cap, **over)
 
 
 def check(eng, t, ref=None):
     """the device's recs, order, bytes and totals equal the oracle's at the exact capacity; returns the oracle's result"""
     ref = ref or T.pack(t.mols, t.atoms, t.bonds, t.text, order_fill=ORDER_FILL)
-    rc, recs, order, out, totals = run(eng, t, ref["total"])
-    assert rc == 0, eng.lib.mnx_last_error(eng.h)
-    assert totals.tolist() == [ref["total"], 0]
-    compare(recs, ref["recs"], out, ref["out"], ref["total"], "SMILES")
-    bad = np.nonzero(order != ref["order"])[0]
-    assert bad.size == 0, ("order", bad[:5], order[bad[:5]], ref["order"][bad[:5]])
+    compare_text(run(eng, t, ref["total"]), ref, "SMILES")
     return ref
-
-
-def texts(ref):
-    return [ref["out"][r["text0"]:r["text0"] + r["len"]].decode() for r in ref["recs"]]
 
 
 def test_pinned_strings_and_flag_cases(eng, dev):
@@ -137,20 +97,20 @@ def test_capacities(eng, generated):
     out_cap"""
     mols, t, ref = generated
     need = ref["total"]
-    rc, recs, order, _, totals = run(eng, t, 0, out=None)
-    assert rc == 0 and totals.tolist() == [need, 1] and recs.tobytes() == ref["recs"].tobytes() and order.tobytes() == ref["order"].tobytes()
+    a = run(eng, t, 0, out=None)
+    assert a.rc == 0 and a.totals.tolist() == [need, 1] and a.recs.tobytes() == ref["recs"].tobytes() and a.order.tobytes() == ref["order"].tobytes()
     for cap in (need, need - 1):
-        rc, recs, order, out, totals = run(eng, t, cap)
-        assert rc == 0 and totals.tolist() == [need, int(cap < need)]
-        assert recs.tobytes() == ref["recs"].tobytes() and order.tobytes() == ref["order"].tobytes()
-        assert out[:cap].tobytes() == ref["out"][:cap] and np.all(out[cap:] == FILL), cap
+        a = run(eng, t, cap)
+        assert a.rc == 0 and a.totals.tolist() == [need, int(cap < need)]
+        assert a.recs.tobytes() == ref["recs"].tobytes() and a.order.tobytes() == ref["order"].tobytes()
+        assert a.out[:cap].tobytes() == ref["out"][:cap] and np.all(a.out[cap:] == FILL), cap
 
 
 def test_two_runs_are_byte_identical(eng, generated):
     mols, t, ref = generated
     a, b = run(eng, t, ref["total"]), run(eng, t, ref["total"])
-    assert a[0] == b[0] == 0 and a[1].tobytes() == b[1].tobytes() and a[2].tobytes() == b[2].tobytes()
-    assert np.array_equal(a[3], b[3]) and a[4].tolist() == b[4].tolist() == [ref["total"], 0]
+    same_results(a, b)
+    assert a.rc == b.rc == 0 and a.totals.tolist() == b.totals.tolist() == [ref["total"], 0]
 
 
 def test_without_the_marks_it_is_the_plain_writer(eng, dev, generated):
@@ -160,10 +120,10 @@ def test_without_the_marks_it_is_the_plain_writer(eng, dev, generated):
     pool = Tables(dev, [random_molecule(rng, int(n), int(n) + int(rng.integers(-2, 3))) for n in rng.integers(3, 40, 200)])
     for t in (generated[1], pool):
         ref = check(eng, t)
-        rc, recs, order, out, totals = run(eng, t, ref["total"], fn="mnx_smiles_pack")
-        assert rc == 0
-        plain = [out[r["text0"]:r["text0"] + r["len"]].tobytes().decode() for r in recs]
-        assert [s.replace("@", "") for s in texts(ref)] == plain and order.tobytes() == ref["order"].tobytes()
+        a = run(eng, t, ref["total"], fn="mnx_smiles_pack")
+        assert a.rc == 0
+        recs, plain = a.recs, device_texts(a.recs, a.out)
+        assert [s.replace("@", "") for s in texts(ref)] == plain and a.order.tobytes() == ref["order"].tobytes()
         assert recs["n_rings"].tolist() == ref["recs"]["n_rings"].tolist()
         assert ((recs["flags"] ^ ref["recs"]["flags"]) & 0xBF == 0).all() and not (recs["flags"] & 0x300).any()
         assert (ref["recs"]["len"] - recs["len"]).tolist() == [s.count("@") for s in texts(ref)]
@@ -176,13 +136,9 @@ def test_refused_calls_launch_nothing_and_name_the_new_function(eng, dev, synth_
     need = T.pack(t.mols, t.atoms, t.bonds, t.text)["total"]
 
     def refused(expect, **over):
-        rc, recs, order, out, totals = run(eng, t, need, **over)
-        msg = eng.lib.mnx_last_error(over.get("h", eng.h)).decode()
-        assert rc == -1 and msg == "mnx_smiles_pack_stereo: " + expect, (over, rc, msg)
-        assert np.all(recs.view(np.uint8) == FILL) and np.all(out == FILL) and np.all(totals.view(np.uint8) == FILL), over
-        assert np.all(order == ORDER_FILL), over
+        assert_refused(run(eng, t, need, **over), "mnx_smiles_pack_stereo: " + expect)
 
-    assert run(eng, t, need)[0] == 0
+    assert run(eng, t, need).rc == 0
     for name in ("mols", "atoms", "bonds", "text", "recs", "out", "totals"):
         refused("null pointer", **{name: None})
     for n in (0, -1, 65537):

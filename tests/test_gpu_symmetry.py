@@ -3,11 +3,8 @@ of tests/symmetry_ref.py, byte for byte and word for word (recs, order, rank, sy
 tolerances), for marks 0..3: the strings that pin the rule, the generated molecules of the CPU tests, the device against its
 own mnx_smiles_pack_canonical, molecules at odd offsets and the refusal cases, the largest molecule, the protocol, and one
 end-to-end run."""
-import ctypes as C
-
 import numpy as np
 import pytest
-import torch
 
 import canon_ref as K
 import ez_ref as E
@@ -17,28 +14,15 @@ import symmetry_ref as Y
 import test_canon_host as H
 import test_symmetry_host as HS
 from molnextr_amd import weights as W
-from molnextr_amd.engine import ATOM_MARKS_NONE, SMILES_DTYPE, SMILES_REFUSED, SMILES_SYM_DROPPED, Engine
-from packed_tables import FILL, GUARD, Tables, _p, compare
+from molnextr_amd.engine import ATOM_MARKS_NONE, SMILES_REFUSED, SMILES_SYM_DROPPED
+from packed_tables import (FILL, WORD_FILL, Tables, _p, assert_refused, call_text, compare_text, dev, device_texts, eng,  # noqa: F401
+                           same_results, texts)
 
 pytestmark = pytest.mark.gpu
 
-WORD_FILL = FILL | FILL << 8
 E2E_FIRST_INDEX = 500          # the batch of the plain writer's end-to-end test
 MODES = (0, 1, 2, 3)
 NAME = "mnx_smiles_pack_symmetric: "
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def eng(synth_ckpt, dev):
-    e = Engine(synth_ckpt["encoder"], synth_ckpt["decoder"], device=0, max_batch=32, dtype="fp16x3")
-    yield e
-    e.close()
 
 
 def oracle(t, marks, **sizes):
@@ -65,48 +49,16 @@ def generated(dev):
 
 
 def run(eng, t, out_cap, marks=0, fn="mnx_smiles_pack_symmetric", **over):
-    """One call into FILL-filled outputs with GUARD bytes behind each: (rc, recs, order, rank, sym_class, the whole out arena,
-    totals, atom_marks); fn = "mnx_smiles_pack_canonical": the older call on the same buffers (atom_marks stays FILL)"""
-    na, nb, nt = len(t.atoms), len(t.bonds), len(t.text)
-    recs = torch.full((t.n * 16 + GUARD,), FILL, dtype=torch.uint8, device=t.dev)
-    words = [torch.full((na * 2 + GUARD,), FILL, dtype=torch.uint8, device=t.dev) for _ in range(3)]
-    marks_out = torch.full((na + GUARD,), FILL, dtype=torch.uint8, device=t.dev)
-    out = torch.full((out_cap + GUARD,), FILL, dtype=torch.uint8, device=t.dev)
-    totals = torch.full((8,), FILL, dtype=torch.uint8, device=t.dev)
-    a = {"h": eng.h, "mols": _p(t.d[0]), "n": t.n, "atoms": _p(t.d[1]), "na": na, "bonds": _p(t.d[2]), "nb": nb, "text": _p(t.d[3]),
-         "nt": nt, "recs": _p(recs), "order": _p(words[0]), "rank": _p(words[1]), "sym_class": _p(words[2]), "atom_marks": _p(marks_out),
-         "out": _p(out), "out_cap": out_cap, "totals": _p(totals), "marks": marks,
-         "stream": C.c_void_p(torch.cuda.current_stream().cuda_stream)}
-    a.update(over)
-    if fn != "mnx_smiles_pack_symmetric":
-        del a["atom_marks"]
-    rc = getattr(eng.lib, fn)(*a.values())
-    torch.cuda.synchronize()
-    r, o, am = recs.cpu().numpy(), out.cpu().numpy(), marks_out.cpu().numpy()
-    w = [x.cpu().numpy() for x in words]
-    assert np.all(r[t.n * 16:] == FILL), "bytes behind recs were overwritten"
-    assert all(np.all(x[na * 2:] == FILL) for x in w), "bytes behind order, rank or sym_class were overwritten"
-    assert np.all(am[na:] == FILL), "bytes behind atom_marks were overwritten"
-    order, rank, sym_class = (x[:na * 2].view(np.uint16) for x in w)
-    return rc, r[:t.n * 16].view(SMILES_DTYPE), order, rank, sym_class, o, totals.cpu().numpy().view(np.uint32), am[:na]
+    """fn = "mnx_smiles_pack_canonical": the older call, which has no atom_marks"""
+    return call_text(fn, eng, t, out_cap, marks=marks, **over)
 
 
 def check(eng, t, marks, ref=None):
     """the device's recs, order, rank, sym_class, atom_marks, bytes and totals equal the oracle's at the exact capacity; returns
     the oracle's"""
     ref = ref or oracle(t, marks)
-    rc, recs, order, rank, sym_class, out, totals, atom_marks = run(eng, t, ref["total"], marks)
-    assert rc == 0, eng.lib.mnx_last_error(eng.h)
-    assert totals.tolist() == [ref["total"], 0]
-    compare(recs, ref["recs"], out, ref["out"], ref["total"], "SMILES")
-    for name, got in (("rank", rank), ("sym_class", sym_class), ("order", order), ("atom_marks", atom_marks)):
-        bad = np.nonzero(got != ref[name])[0]
-        assert bad.size == 0, (name, bad[:5], got[bad[:5]], ref[name][bad[:5]])
+    compare_text(run(eng, t, ref["total"], marks), ref, "SMILES")
     return ref
-
-
-def texts(ref):
-    return [ref["out"][r["text0"]:r["text0"] + r["len"]].decode() for r in ref["recs"]]
 
 
 @pytest.mark.parametrize("marks", MODES)
@@ -144,21 +96,22 @@ def test_device_against_its_own_canonical_call(eng, generated):
         cap = refs[marks]["total"] + 16384                  # the canonical strings are longer where marks were dropped
         new = run(eng, t, cap, marks)
         old = run(eng, t, cap, marks, fn="mnx_smiles_pack_canonical")
-        assert new[0] == old[0] == 0 and new[6][1] == old[6][1] == 0
-        assert all(np.array_equal(new[k], old[k]) for k in (2, 3, 4)) and np.array_equal(new[1]["n_rings"], old[1]["n_rings"])
-        assert np.array_equal(new[1]["flags"] & Y.KEPT_BITS, old[1]["flags"] & Y.KEPT_BITS)
-        got, was = ([x[5][r["text0"]:r["text0"] + r["len"]].tobytes().decode() for r in x[1]] for x in (new, old))
+        assert new.rc == old.rc == 0 and new.totals[1] == old.totals[1] == 0
+        assert all(np.array_equal(getattr(new, k), getattr(old, k)) for k in ("order", "rank", "sym_class"))
+        assert np.array_equal(new.recs["n_rings"], old.recs["n_rings"])
+        assert np.array_equal(new.recs["flags"] & Y.KEPT_BITS, old.recs["flags"] & Y.KEPT_BITS)
+        got, was = (device_texts(x.recs, x.out) for x in (new, old))
         plain = got if marks == 0 else plain
         fired = 0
         for b, (g, w) in enumerate(zip(got, was)):
-            if not new[1]["flags"][b] & SMILES_SYM_DROPPED:
-                assert g == w and new[1]["flags"][b] == old[1]["flags"][b], (marks, b)
+            if not new.recs["flags"][b] & SMILES_SYM_DROPPED:
+                assert g == w and new.recs["flags"][b] == old.recs["flags"][b], (marks, b)
             else:
                 fired += 1
             assert E.strip(g.replace("@", "")) == plain[b], (marks, b)
         assert fired == 0 if marks == 0 else fired >= 30
         if marks == 0:
-            assert new[1].tobytes() == old[1].tobytes() and np.array_equal(new[5], old[5]) and not new[7].any()
+            assert new.recs.tobytes() == old.recs.tobytes() and np.array_equal(new.out, old.out) and not new.atom_marks.any()
 
 
 CHAIN = ([b"O", b"C", b"C"], [(0, 0), (10, 0), (20, 0)], [(0, 1, 1, 1), (1, 2, 1, 1)])
@@ -202,18 +155,18 @@ def test_protocol(eng, generated):
     mols, t, refs = generated
     ref = refs[3]
     need = ref["total"]
-    rc, recs, order, rank, sym_class, out, totals, atom_marks = run(eng, t, 0, 3, out=None)
-    assert rc == 0 and totals.tolist() == [need, 1] and recs.tobytes() == ref["recs"].tobytes() and np.all(out == FILL)
-    assert order.tobytes() == ref["order"].tobytes() and rank.tobytes() == ref["rank"].tobytes() and sym_class.tobytes() == ref["sym_class"].tobytes()
-    assert atom_marks.tobytes() == ref["atom_marks"].tobytes()
-    rc, recs, order, rank, sym_class, out, totals, atom_marks = run(eng, t, need - 1, 3)
-    assert rc == 0 and totals.tolist() == [need, 1] and recs.tobytes() == ref["recs"].tobytes() and rank.tobytes() == ref["rank"].tobytes()
-    assert out[:need - 1].tobytes() == ref["out"][:need - 1] and np.all(out[need - 1:] == FILL), "nothing is written beyond out_cap"
-    assert atom_marks.tobytes() == ref["atom_marks"].tobytes()
-    rc, recs, order, rank, sym_class, out, totals, atom_marks = run(eng, t, need, 3, order=None, atom_marks=None)
-    assert rc == 0 and totals.tolist() == [need, 0] and recs.tobytes() == ref["recs"].tobytes() and rank.tobytes() == ref["rank"].tobytes()
-    assert out[:need].tobytes() == ref["out"] and np.all(out[need:] == FILL) and (order == WORD_FILL).all() and (atom_marks == FILL).all()
-    assert sym_class.tobytes() == ref["sym_class"].tobytes()
+    a = run(eng, t, 0, 3, out=None)
+    assert a.rc == 0 and a.totals.tolist() == [need, 1] and a.recs.tobytes() == ref["recs"].tobytes() and np.all(a.out == FILL)
+    assert a.order.tobytes() == ref["order"].tobytes() and a.rank.tobytes() == ref["rank"].tobytes() and a.sym_class.tobytes() == ref["sym_class"].tobytes()
+    assert a.atom_marks.tobytes() == ref["atom_marks"].tobytes()
+    a = run(eng, t, need - 1, 3)
+    assert a.rc == 0 and a.totals.tolist() == [need, 1] and a.recs.tobytes() == ref["recs"].tobytes() and a.rank.tobytes() == ref["rank"].tobytes()
+    assert a.out[:need - 1].tobytes() == ref["out"][:need - 1] and np.all(a.out[need - 1:] == FILL), "nothing is written beyond out_cap"
+    assert a.atom_marks.tobytes() == ref["atom_marks"].tobytes()
+    a = run(eng, t, need, 3, order=None, atom_marks=None)
+    assert a.rc == 0 and a.totals.tolist() == [need, 0] and a.recs.tobytes() == ref["recs"].tobytes() and a.rank.tobytes() == ref["rank"].tobytes()
+    assert a.out[:need].tobytes() == ref["out"] and np.all(a.out[need:] == FILL) and (a.order == WORD_FILL).all() and (a.atom_marks == FILL).all()
+    assert a.sym_class.tobytes() == ref["sym_class"].tobytes()
 
 
 def test_refused_calls_launch_nothing_and_name_the_new_function(eng, pinned):
@@ -221,13 +174,9 @@ def test_refused_calls_launch_nothing_and_name_the_new_function(eng, pinned):
     need = oracle(t, 3)["total"]
 
     def refused(expect, **over):
-        rc, recs, order, rank, sym_class, out, totals, atom_marks = run(eng, t, need, **{"marks": 3, **over})
-        msg = eng.lib.mnx_last_error(eng.h).decode()
-        assert rc == -1 and msg == NAME + expect, (over, rc, msg)
-        assert np.all(recs.view(np.uint8) == FILL) and np.all(out == FILL) and np.all(totals.view(np.uint8) == FILL), over
-        assert np.all(order == WORD_FILL) and np.all(rank == WORD_FILL) and np.all(sym_class == WORD_FILL) and np.all(atom_marks == FILL), over
+        assert_refused(run(eng, t, need, **{"marks": 3, **over}), NAME + expect)
 
-    assert run(eng, t, need, 3)[0] == 0
+    assert run(eng, t, need, 3).rc == 0
     for marks in (4, 8, 0x80000001):
         refused("marks may hold MNX_SMILES_MARK_TETRAHEDRAL and MNX_SMILES_MARK_DOUBLE_BOND only", marks=marks)
     for name in ("rank", "sym_class", "mols", "atoms", "recs", "out", "totals"):
@@ -243,7 +192,8 @@ def test_two_runs_are_word_identical(eng, generated):
     mols, t, refs = generated
     for marks in (1, 3):
         a, b = run(eng, t, refs[marks]["total"], marks), run(eng, t, refs[marks]["total"], marks)
-        assert a[0] == b[0] == 0 and all(a[k].tobytes() == b[k].tobytes() for k in range(1, 8))
+        same_results(a, b)
+        assert a.rc == b.rc == 0
 
 
 def test_end_to_end_predict_pipeline_and_molnextr(eng, dev, synth_ckpt, monkeypatch):

@@ -11,16 +11,12 @@ import molfile_ref as M
 import smiles_ref as S
 from molnextr_amd import engine
 from molnextr_amd.model import predict_pipeline
-from packed_tables import POOL
+from packed_tables import POOL, path
 
 
 def ring(first, n, cls):
     """bonds of a ring over atoms first .. first + n - 1"""
     return [(first + k, first + k + 1, cls, cls) for k in range(n - 1)] + [(first, first + n - 1, cls, cls)]
-
-
-def path(n, cls=1):
-    return [(k, k + 1, cls, cls) for k in range(n - 1)]
 
 
 CUBE = [(0, 1), (1, 2), (2, 3), (0, 3), (4, 5), (5, 6), (6, 7), (4, 7), (0, 4), (1, 5), (2, 6), (3, 7)]
