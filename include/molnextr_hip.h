@@ -412,7 +412,7 @@ int mnx_set_vocab_text(mnx_engine* h, const char* bytes, const uint32_t* offsets
  * size outside the limits, the scores partly set, misaligned records, or no vocabulary text / token classes set. */
 typedef struct mnx_mol {
     uint32_t atom0, n_atoms, bond0, n_bonds, text0, smiles_len;
-    uint32_t flags;             /* bit 0: more atoms than kmax, tables truncated to kmax; MNX_MOL_EXPAND* of mnx_expand_pack; bits 4-6 of mnx_normalize_pack */
+    uint32_t flags;             /* bit 0: more atoms than kmax, tables truncated to kmax; MNX_MOL_EXPAND* of mnx_expand_pack; bits 4-6 of mnx_normalize_pack; bits 7-9 of mnx_kekulize_pack */
     uint32_t reserved;          /* 0 */
     double overall_score;
 } mnx_mol;
@@ -924,7 +924,8 @@ int mnx_expand_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_ato
  * CC(C)F, and a pyrrole drawn with N never equals [nH]. Intended order: mnx_smiles_read or mnx_graph_pack -> mnx_expand_pack ->
  * THIS CALL -> mnx_molfile_pack / the mnx_smiles_pack calls, all of which run on the output unchanged.
  * THE RULE IS THIS LIBRARY'S OWN. It is NOT RDKit's aromaticity model (nor Daylight's, nor any toolkit's), no toolkit has checked
- * it, and a string written behind it never compares with a toolkit's. It only goes from Kekule to aromatic: nothing kekulises.
+ * it, and a string written behind it never compares with a toolkit's. It only goes from Kekule to aromatic: the other direction is
+ * mnx_kekulize_pack's, below.
  * A post-pass on a post-pass: it reads the input tables, changes none of them (the outputs must not overlap them) and touches no
  * decode state. Atom and bond COUNTS and ORDER never change: only the text, an atom's sym0 / sym_len and a bond's type / rev do.
  *
@@ -967,8 +968,8 @@ int mnx_expand_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_ato
  * KNOWN LIMITS:
  *   only rings of 5 and 6 atoms are examined: azulene, tropylium and cyclooctatetraene dianion stay Kekule;
  *   a ring that holds a lower-case atom or a class-4 bond is not examined: a half-aromatic fused prediction stays as it came;
- *   the other direction is not built: an aromatic input is never kekulised, so the normal form of a molecule is the aromatic one
- *     only where this rule finds it;
+ *   this call never kekulises: an aromatic input stays as it came. mnx_kekulize_pack in front of this call gives a half-aromatic
+ *     molecule, and an aromatic ring this rule cannot find (azulene), one form;
  *   an explicit [H] atom is an atom like any other and is not folded into a count;
  *   the output is a fixed point of the call on everything tested (a second call changes no table), with one corner that is known
  *     and was not met: a C whose exocyclic double bond goes to an N on a fused enumerated ring that fails while it holds an atom of
@@ -1005,6 +1006,90 @@ int mnx_normalize_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_
                        const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_mol* mols_out,
                        mnx_atom* atoms_out, uint32_t atom_cap, mnx_bond* bonds_out, uint32_t bond_cap, char* text_out,
                        uint32_t text_cap, uint8_t* atom_notes, uint32_t* totals, void* stream);
+
+/* Kekule structures for the aromatic systems of the packed molecule tables, on the device: the inverse of what
+ * mnx_normalize_pack perceives. Lower-case atoms on type-4 bonds — as mnx_smiles_read reads c1ccccc1, as the bond head predicts an
+ * aromatic ring, as mnx_normalize_pack writes one — become upper-case atoms on double and single bonds, so that a molfile carries
+ * no bond type 4 (which the CTfile format keeps for queries) and a molecule has a form that does not depend on which rings a
+ * perception rule finds. Packed tables in, packed tables of the same record types out. The intended order is mnx_smiles_read /
+ * mnx_graph_pack -> mnx_expand_pack -> THIS CALL -> mnx_normalize_pack (optional) -> the writers.
+ * A Kekule structure is a perfect matching of the atoms that must take a double bond, so whether an output is valid can be checked
+ * without a toolkit. ONLY THE CHOICE AMONG SEVERAL VALID MATCHINGS IS THIS LIBRARY'S OWN, fixed by the search order below. The rule
+ * is NOT RDKit's Kekulize (nor any toolkit's) and no toolkit has checked it.
+ * A post-pass on a post-pass: it reads the input tables, changes none of them (the outputs must not overlap them) and touches no
+ * decode state. Atom and bond COUNTS and ORDER never change: only the text, sym0 / sym_len of the atoms of kekulised systems and
+ * type / rev of their type-4 bond records do.
+ *
+ * The rule, per molecule:
+ * Interpretation. Every atom's symbol is read as mnx_molfile_pack reads it. An AROMATIC ATOM is an interpreted atom whose element
+ *   is spelled in lower case (the reader accepts b c n o p s, and se and as in brackets). Everything else — upper-case atoms,
+ *   pseudo-atoms, '*', symbols without a parse — is copied byte for byte and is no aromatic atom.
+ * Bond orders. By `type` (rev is not read): 1, 5, 6 and 4 count 1, 2 counts 2, 3 counts 3, every other type 0. bo(a) is the sum
+ *   over the bond records at a (a record from an atom to itself counts at both of its ends). H(a) is the written count for a
+ *   bracket atom, max(0, 3 - bo) for an unbracketed c, and 0 for every other unbracketed lower-case atom.
+ * Systems. The vertices are the aromatic atoms, the edges the type-4 records between two aromatic atoms. A SYSTEM is a connected
+ *   component; an aromatic atom without a type-4 record is a system of one. A system is BLOCKED, and stays exactly as it came,
+ *   when one of its atoms has a type-4 record whose other end is no aromatic atom, or more than three type-4 records, or two
+ *   records (of any type) to the same atom or a record to itself, or a record of a type outside 1..6.
+ * Needy atoms. v is 4 for c; 3 for b, n, p and as, where a charge of +1 makes n and p 4 and a charge of -1 makes b 4; 2 for o, s
+ *   and se, or 3 at charge +1; 3 for c at charge +1 or -1. An atom is NEEDY iff v - bo - H == 1. So pyridine n, the [n+] of an
+ *   N-oxide, pyrylium [o+] and an ordinary c are needy; [nH], N-methyl n, o, s, the c(=O) of a pyridone, [cH-] and [cH+] are
+ *   not. An (element, charge) pair that is not listed is not needy.
+ * Matching, per system, independent of every other system. The edges of the search are the type-4 records between two needy atoms
+ *   of the system. An odd number of needy atoms fails at once, and so does a needy atom without a needy neighbour. Otherwise the
+ *   search is depth first: take the lowest-index unmatched needy atom and try its unmatched needy neighbours in ascending atom
+ *   index; each pairing tried counts one STEP; a pairing is undone at once when it leaves an unmatched needy atom of the system
+ *   with no unmatched needy neighbour (only the neighbours of the two atoms just paired can be in that state); when no candidate
+ *   is left, backtrack to the previous pairing; backtracking from the first atom fails the system. More than max_steps steps in
+ *   one system fails it with the limit bit; max_steps == 0 means MNX_KEKULE_DEFAULT_STEPS. The first complete matching found is
+ *   the result. Pruning removes only failing branches, so the result is the lexicographically first matching in that order, and a
+ *   search without pruning finds the same one; the step count is defined with the pruning.
+ * Writing a system that succeeded. Every atom becomes upper case, spelled by mnx_normalize_pack's spelling rule for an upper-case
+ *   atom from (isotope, element, H, charge) and the new bo (one more for a matched atom): without brackets when the element is of
+ *   the organic subset, there is no isotope, the charge is 0 and H is what the valence table infers; otherwise a bracket atom
+ *   exactly as mnx_smiles_pack spells one. H never changes. Matched records get type = rev = 2, the system's other type-4 records
+ *   type = rev = 1; every other record keeps every field. Atoms of systems that failed or were blocked, and all other atoms, are
+ *   copied byte for byte.
+ * Examples (strings as mnx_smiles_read reads and mnx_smiles_pack writes them): c1ccccc1 -> C1=CC=CC=C1. c1cc[nH]c1 -> C=1C=CNC1 (a
+ *   pyrrole with N). O=c1cccc[nH]1 -> O=C1C=CC=CN1. c1ccc2ccccc2c1 -> C1=CC=C2C=CC=CC2=C1. c1ccccc1-c1ccccc1 ->
+ *   C1=CC=CC=C1C1=CC=CC=C1 (the link stays single). c1cccc1 is left aromatic, with MNX_MOL_KEKULE_LEFT. [cH-]1cccc1 ->
+ *   [CH-]1C=CC=C1. Azulene c1ccc2cccc2cc1 -> C1=CC=C2C=CC=C2C=C1, although mnx_normalize_pack cannot find it.
+ * KNOWN LIMITS:
+ *   the choice among valid matchings is this library's own order; it is not RDKit's Kekulize and no toolkit has checked it;
+ *   that order follows the atom numbering: two numberings of one system can get different Kekule structures, and only
+ *     mnx_normalize_pack behind this call makes them one form again, where its rule finds the rings (not in azulene);
+ *   an aromatic ring drawn with a wedge (type 5 or 6 inside a ring of lower-case atoms) loses nothing here: the wedge is no type-4
+ *     record and keeps its fields; mnx_normalize_pack behind this call loses it;
+ *   a system that holds an upper-case atom on a type-4 bond is left untouched, and so is one with no matching (c1cccc1,
+ *     triangulene) or one whose search runs beyond max_steps;
+ *   the search is serial inside one system: one lane of the workgroup per system.
+ *
+ * Output. mols_out[b]: n_atoms and n_bonds of the input, smiles_len the length of the new text, which is the atoms' symbols behind
+ * one another in atom order (NO token SMILES); flags = bit 0 copied | MNX_MOL_KEKULIZED (a system was rewritten) |
+ * MNX_MOL_KEKULE_LEFT (a system stayed aromatic); the MNX_MOL_EXPAND* and mnx_normalize_pack's bits of the input are not copied. An
+ * atom record keeps index, x_bin, y_bin and score; a bond record i, j and score; overall_score is copied.
+ * MNX_MOL_KEKULIZE_REFUSED: as MNX_MOL_NORMALIZE_REFUSED — records beyond the tables passed, a symbol beyond n_text_bytes, a bond
+ * whose i or j is no atom of the molecule, or more than 999 atoms or bonds; n_atoms = n_bonds = smiles_len = 0 in mols_out then.
+ * atom_notes uint8 [atom_cap] (may be null): for output atom atom0 + k, bits 0-3 H of an aromatic atom (0 for every other atom),
+ * MNX_NOTE_KEKULIZED: rewritten by this call, MNX_NOTE_KEKULE_LEFT: an aromatic atom that stayed as it came, with
+ * MNX_NOTE_KEKULE_LIMIT when the step limit was the reason, MNX_NOTE_COPIED: no aromatic atom.
+ * Inputs, outputs, the sizing protocol with totals [4] and the capped stores are mnx_normalize_pack's; max_steps stands in front of
+ * stream. mnx_set_symbol_tables must have been called. Deterministic word for word: every position comes from a prefix scan, the
+ * search of a system is serial, and the atomics of the kernel only count, add up, set bits of sets and take the minimum of a set.
+ * Three launches, asynchronous on `stream`, no allocation, no host synchronisation.
+ * MNX_ERR_INVALID_ARG (with mnx_last_error, "mnx_kekulize_pack: ..."): a null pointer (a table with capacity 0 may be null), n
+ * outside 1..65536, misaligned records, or no symbol tables set; nothing is launched then. */
+#define MNX_MOL_KEKULIZED 128u
+#define MNX_MOL_KEKULE_LEFT 256u
+#define MNX_MOL_KEKULIZE_REFUSED 512u
+#define MNX_NOTE_KEKULIZED 16u
+#define MNX_NOTE_KEKULE_LEFT 32u
+#define MNX_NOTE_KEKULE_LIMIT 128u
+#define MNX_KEKULE_DEFAULT_STEPS 16384u
+int mnx_kekulize_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
+                      const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_mol* mols_out,
+                      mnx_atom* atoms_out, uint32_t atom_cap, mnx_bond* bonds_out, uint32_t bond_cap, char* text_out,
+                      uint32_t text_cap, uint8_t* atom_notes, uint32_t* totals, uint32_t max_steps, void* stream);
 
 /* SMILES text read into the packed molecule tables, on the device: the inverse of mnx_smiles_pack. Strings in, mnx_mol / mnx_atom /
  * mnx_bond records and a text arena out, as mnx_graph_pack writes them, so that mnx_smiles_pack_canonical, mnx_expand_pack,

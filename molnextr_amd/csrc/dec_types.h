@@ -260,6 +260,12 @@ hipError_t expand_pack_enqueue(const SymbolTables* st_dev, const FragView& fv, c
 // three launches on s; atom_notes (may be null) receives one byte per output atom
 hipError_t normalize_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, const TablesOut& o, unsigned char* atom_notes,
                                   unsigned* totals, hipStream_t s);
+
+// kekulize.hip: the molecules of t with every aromatic system that has a Kekule structure written as one — upper-case atoms,
+// double and single bonds — as packed tables of the same record types (mnx_kekulize_pack): count, scan and fill, asynchronous on
+// s. max_steps: the pairings one system's search may try, 0 = MNX_KEKULE_DEFAULT_STEPS.
+hipError_t kekulize_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, const TablesOut& o, unsigned char* atom_notes,
+                                 unsigned* totals, unsigned max_steps, hipStream_t s);
 // smiles_read.hip: string b = bytes[offsets[b] .. offsets[b + 1]) read as SMILES into packed tables of mnx_graph_pack's record types
 // (mnx_smiles_read): count, scan and fill, three launches on s
 hipError_t smiles_read_enqueue(const unsigned char* bytes, unsigned n_bytes, const unsigned* offsets, int n, mnx_read* recs,

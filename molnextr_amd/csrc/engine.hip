@@ -1552,6 +1552,20 @@ int mnx_normalize_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_
     return MNX_OK;
 }
 
+int mnx_kekulize_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
+                      const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_mol* mols_out,
+                      mnx_atom* atoms_out, uint32_t atom_cap, mnx_bond* bonds_out, uint32_t bond_cap, char* text_out,
+                      uint32_t text_cap, uint8_t* atom_notes, uint32_t* totals, uint32_t max_steps, void* stream) {
+    const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
+    const TablesOut o = tables_out(mols_out, atoms_out, atom_cap, bonds_out, bond_cap, text_out, text_cap);
+    if (int rc = check_packed_tables(h, "mnx_kekulize_pack", t, tables_out_null(o, totals), tables_out_skew(o, totals),
+                                     "the output tables too, totals 4-byte"))
+        return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, kekulize_pack_enqueue(h->st_dev, t, o, atom_notes, totals, max_steps, (hipStream_t)stream));
+    return MNX_OK;
+}
+
 int mnx_smiles_read(mnx_engine* h, const char* bytes, uint32_t n_bytes, const uint32_t* offsets, int32_t n, mnx_mol* mols,
                     mnx_read* recs, mnx_atom* atoms, uint32_t atom_cap, mnx_bond* bonds, uint32_t bond_cap, char* text,
                     uint32_t text_cap, uint32_t* totals, void* stream) {

@@ -29,7 +29,7 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
            "mnx_layernorm16", "mnx_merge_ln16", "mnx_cast16", "mnx_sgemm_tn", "mnx_set_vocab_text", "mnx_graph_pack",
            "mnx_set_symbol_tables", "mnx_molfile_pack", "mnx_smiles_pack", "mnx_smiles_pack_stereo",
            "mnx_smiles_pack_marks", "mnx_smiles_pack_canonical", "mnx_smiles_pack_symmetric", "mnx_set_fragments", "mnx_expand_pack", "mnx_smiles_read",
-           "mnx_beam_scripted", "mnx_edge_probs", "mnx_normalize_pack")
+           "mnx_beam_scripted", "mnx_edge_probs", "mnx_normalize_pack", "mnx_kekulize_pack")
 
 # Encoder operand modes (include/molnextr_hip.h MNX_DTYPE_*). "fp16x3" — split fp16 operands, three MFMA terms per
 # product, fp32-class results — is the default: it is the fastest mode whose results stay a factor of four inside north_star's
@@ -121,6 +121,11 @@ MOL_EXPANDED, MOL_LABEL_LEFT, MOL_EXPAND_REFUSED = 2, 4, 8
 # (records beyond the tables, more than 999 atoms or bonds): no records. The bits of its `atom_notes`: the H count, made aromatic
 # by the call, brackets removed, the symbol copied uninterpreted
 MOL_AROMATIZED, MOL_UNBRACKETED, MOL_NORMALIZE_REFUSED = 16, 32, 64
+# mnx_mol.flags of mnx_kekulize_pack's output: a system was rewritten; a system stayed aromatic; the molecule was refused. Its
+# atom_notes: NOTE_H_MASK, NOTE_COPIED and the three bits below; KEKULE_DEFAULT_STEPS is what max_steps = 0 stands for
+MOL_KEKULIZED, MOL_KEKULE_LEFT, MOL_KEKULIZE_REFUSED = 128, 256, 512
+NOTE_KEKULIZED, NOTE_KEKULE_LEFT, NOTE_KEKULE_LIMIT = 16, 32, 128
+KEKULE_DEFAULT_STEPS = 16384
 NOTE_H_MASK, NOTE_AROMATIZED, NOTE_UNBRACKETED, NOTE_COPIED = 15, 16, 32, 64
 MOLFILE_DTYPE = np.dtype([("text0", "<u4"), ("len", "<u4"), ("flags", "<u4"), ("reserved", "<u4")], align=True)
 # mnx_molfile.flags (MNX_MOLFILE_*): no molfile (len 0) for more than 999 atoms / bonds or records beyond the tables passed;
@@ -302,6 +307,8 @@ def load_library():
                                     vp, C.c_uint32, vp, vp, vp]
     lib.mnx_normalize_pack.restype = C.c_int
     lib.mnx_normalize_pack.argtypes = lib.mnx_expand_pack.argtypes      # atom_notes in the place of origin
+    lib.mnx_kekulize_pack.restype = C.c_int                             # normalize's arguments, max_steps in front of stream
+    lib.mnx_kekulize_pack.argtypes = lib.mnx_expand_pack.argtypes[:-1] + [C.c_uint32, lib.mnx_expand_pack.argtypes[-1]]
     lib.mnx_smiles_read.restype = C.c_int
     lib.mnx_smiles_read.argtypes = [vp, vp, C.c_uint32, vp, i32, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp]
     lib.mnx_atom_scan.restype = C.c_int
@@ -1118,6 +1125,31 @@ class Engine:
             return self.lib.mnx_normalize_pack(self.h, *args, mols, *arenas, _ptr(notes[0]), totals, _stream())
 
         out = self._sized_tables("mnx_normalize_pack", n, caps, call, dev, keep_device)
+        out["atom_notes"] = notes[0][:len(out["atoms"])].cpu().numpy()
+        return out
+
+    def kekulize_pack(self, rec: dict, caps=None, keep_device: bool = False, max_steps: int = 0) -> dict:
+        """graph_pack's records (or expand_pack's, or smiles_read's) -> the same molecules with every aromatic system that has a
+        Kekule structure written as one (mnx_kekulize_pack; the rule: include/molnextr_hip.h): lower-case atoms on type-4 bonds
+        become upper-case atoms on double and single bonds, H counts kept; a system without a matching, a blocked one and one
+        whose search passes max_steps pairings (0: KEKULE_DEFAULT_STEPS) stay as they came. A Kekule structure is a perfect
+        matching; the choice among several is this library's own search order, NOT RDKit's Kekulize. A dict with graph_pack's
+        keys — 'mols', 'atoms', 'bonds', 'text', 'totals' — plus 'atom_notes' uint8 [atoms]: NOTE_H_MASK the H count of an
+        aromatic atom, NOTE_KEKULIZED / NOTE_KEKULE_LEFT (with NOTE_KEKULE_LIMIT) / NOTE_COPIED. Atom and bond counts and order
+        are the input's; mols['flags'] carries MOL_KEKULIZED / MOL_KEKULE_LEFT / MOL_KEKULIZE_REFUSED. Run it behind expand_pack
+        and in front of normalize_pack. Sizes itself as normalize_pack does; keep_device: also 'device', as graph_pack."""
+        dev = torch.device("cuda", self.device)
+        n = len(rec["mols"])
+        tables, args = self._packed_tables(rec)
+        if caps is None:
+            caps = (len(rec["atoms"]), len(rec["bonds"]), len(rec["text"]) + 2 * n)
+        notes = []              # per atom: one per attempt, of the attempt's atom capacity
+
+        def call(mols, arenas, totals):
+            notes[:] = [torch.empty(max(arenas[1], 1), dtype=torch.uint8, device=dev)]
+            return self.lib.mnx_kekulize_pack(self.h, *args, mols, *arenas, _ptr(notes[0]), totals, int(max_steps), _stream())
+
+        out = self._sized_tables("mnx_kekulize_pack", n, caps, call, dev, keep_device)
         out["atom_notes"] = notes[0][:len(out["atoms"])].cpu().numpy()
         return out
 

@@ -209,7 +209,8 @@ def write_predictions(save_path: str, file_name: str, table: Dict[str, list], sc
     return out_csv
 
 
-def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: int = 512, normalize: bool = False) -> Dict[str, float]:
+def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: int = 512, normalize: bool = False,
+                       kekulize: bool = False) -> Dict[str, float]:
     """--graph_match: the share of items whose prediction and gold string are the same graph as THIS library's canonical SMILES
     sees it (marks 0: no stereo), on the device. records: the gathered dense records in dataset order (shard.pack_records
     layout), re-uploaded in chunks -> graph_pack -> mnx_smiles_pack_canonical; gold -> mnx_smiles_read -> the same writer. A
@@ -219,7 +220,12 @@ def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: 
     mnx_normalize_pack first (this library's own aromaticity and bracket rule), so that a gold string in Kekule form
     or with [CH] spelled out equals an aromatic prediction of the same graph. graph_match_device is what it is without the
     flag. Still NOT the reference's RDKit `graph` score: the rule is not RDKit's model, nothing kekulises, rings of other sizes
-    than 5 and 6 stay as drawn, stereo is dropped."""
+    than 5 and 6 stay as drawn, stereo is dropped.
+    kekulize (--graph_kekulize): adds graph_match_kekulized — BOTH sides pass through mnx_kekulize_pack, then
+    mnx_normalize_pack, and are ranked then, so that an aromatic prediction equals a gold string in aromatic,
+    Kekule or half-aromatic form, and an aromatic azulene equals its Kekule string although normalize finds no ring of 7. The
+    other scores stay as they are. Still NOT the reference's RDKit `graph` score: the matching is this library's own search
+    order and not RDKit's Kekulize, the aromaticity rule is not RDKit's model, stereo is dropped, and no toolkit has checked either."""
     from .engine import READ_REFUSED, SMILES_REFUSED
     from .shard import MAX_LEN
     kmax = engine.max_atoms
@@ -231,7 +237,7 @@ def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: 
         recs, _, data, _, _ = engine.smiles_pack(rec, canonical=True)
         return [None if int(r["flags"]) & SMILES_REFUSED else data[int(r["text0"]):int(r["text0"]) + int(r["len"])] for r in recs]
 
-    equal = equal_normalized = unreadable = refused = 0
+    equal = equal_normalized = equal_kekulized = unreadable = refused = 0
     for c0 in range(0, len(gold), chunk):
         rows = torch.from_numpy(np.ascontiguousarray(records[c0:c0 + chunk])).to(dev)
         n = rows.shape[0]
@@ -253,9 +259,15 @@ def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: 
             want = texts(engine.normalize_pack(read, keep_device=True))
             for p, w, r in zip(pred, want, read["read"]):
                 equal_normalized += not int(r["flags"]) & READ_REFUSED and p is not None and w is not None and p == w
+        if kekulize:
+            pred, want = (texts(engine.normalize_pack(engine.kekulize_pack(side, keep_device=True), keep_device=True)) for side in (packed, read))
+            for p, w, r in zip(pred, want, read["read"]):
+                equal_kekulized += not int(r["flags"]) & READ_REFUSED and p is not None and w is not None and p == w
     scores = {"graph_match_device": equal / len(gold) if gold else 0.0, "gold_unreadable": int(unreadable), "pred_refused": int(refused)}
     if normalize:
         scores["graph_match_normalized"] = equal_normalized / len(gold) if gold else 0.0
+    if kekulize:
+        scores["graph_match_kekulized"] = equal_kekulized / len(gold) if gold else 0.0
     return scores
 
 
@@ -295,6 +307,12 @@ def build_parser() -> argparse.ArgumentParser:
                          "mnx_normalize_pack first (aromatic rings of 5 and 6 atoms perceived from Kekule drawings, [CH] against C, N "
                          "against [nH]: this library's own rule, DESIGN 4.19). graph_match_device stays as it is. Still NOT the "
                          "reference's RDKit `graph` score: the rule is not RDKit's aromaticity model and no toolkit has checked it")
+    ap.add_argument("--graph_kekulize", action="store_true",
+                    help="opt-in, with --graph_match: add graph_match_kekulized, the same comparison with both sides passed through "
+                         "mnx_kekulize_pack and then mnx_normalize_pack first, so that aromatic, Kekule and half-aromatic forms of one "
+                         "molecule compare equal, rings of 7 included (DESIGN 4.20). The other scores stay as they are. Still NOT the "
+                         "reference's RDKit `graph` score: the choice among Kekule structures is this library's own search order, not "
+                         "RDKit's Kekulize, the aromaticity rule is not RDKit's model, and no toolkit has checked either")
     return ap
 
 
@@ -310,6 +328,8 @@ def main(argv=None):
         ap.error(f"--batch_size must be 1..{MAX_BATCH_SIZE} (reference batches of 2 x batch_size <= {2 * MAX_BATCH_SIZE} rows)")
     if args.graph_normalize and not args.graph_match:
         ap.error("--graph_normalize adds a score to --graph_match")
+    if args.graph_kekulize and not args.graph_match:
+        ap.error("--graph_kekulize adds a score to --graph_match")
     dtype = args.dtype or ("fp16" if args.fp16 else DEFAULT_DTYPE)
     max_batch = max(64, 2 * args.batch_size)          # one reference batch is encoded in one launch group
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -358,7 +378,8 @@ def main(argv=None):
         else:
             scores = smiles_scores(df["SMILES"], table["SMILES"]) if "SMILES" in df.columns else None
             if args.graph_match:
-                scores.update(graph_match_scores(engine, kept["records"], list(df["SMILES"]), normalize=args.graph_normalize))
+                scores.update(graph_match_scores(engine, kept["records"], list(df["SMILES"]), normalize=args.graph_normalize,
+                                                 kekulize=args.graph_kekulize))
         print(write_predictions(args.save_path, args.test_file, table, scores), json.dumps(scores))
     if world > 1:
         dist.barrier()

@@ -143,7 +143,8 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
                      max_len: Optional[int] = None, beam_size: int = 1, compute_confidence: bool = False,
                      labels=None, free_run=False, packed: bool = False, molfile: bool = False,
                      molfile_scale=None, smiles: bool = False, stereo: bool = False, double_bonds: bool = False,
-                     canonical: bool = False, expand: bool = False, symmetry: bool = False, normalize: bool = False) -> List[dict]:
+                     canonical: bool = False, expand: bool = False, symmetry: bool = False, normalize: bool = False,
+                     kekulize: bool = False) -> List[dict]:
     """Encoder + Decoder.decode for MANY images through the engine's continuous-batching path (mnx_predict):
     same per-image dicts as `decode_batch`, identical results (the on-device atom scan equals
     sequence_to_smiles' indices), much higher throughput. compute_confidence=True: mnx_predict_confidence, the same
@@ -195,10 +196,19 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
     normalised molecule, and every dict gains 'normalized' = {'symbols', 'bonds' [(i, j, type, rev[, score])], 'hydrogens' (per
     atom: written for a bracket atom, inferred otherwise), 'notes' (the NOTE_* bits of engine.py per atom), 'flags'
     (MOL_AROMATIZED / MOL_UNBRACKETED)}, atom for atom in the order of the expanded (or predicted) atoms. This library's own
-    rule: NOT RDKit's aromaticity model, no toolkit has checked it, nothing kekulises, rings of other sizes stay as drawn."""
+    rule: NOT RDKit's aromaticity model, no toolkit has checked it, rings of other sizes stay as drawn.
+    kekulize (packed only; behind expand and in front of normalize): every aromatic system that has a Kekule structure is written
+    as one on the device before anything else runs on the molecule (mnx_kekulize_pack; the rule: the header) — lower-case atoms on
+    class-4 bonds become upper-case atoms on double and single bonds, so 'molfile' carries no bond type 4 for them. Every dict
+    gains 'kekulized' = {'symbols', 'bonds', 'hydrogens' (per aromatic atom), 'notes' (NOTE_KEKULIZED / NOTE_KEKULE_LEFT /
+    NOTE_KEKULE_LIMIT / NOTE_COPIED of engine.py per atom), 'flags' (MOL_KEKULIZED / MOL_KEKULE_LEFT)}, the molecule as it left
+    that pass. A Kekule structure is a perfect matching; the choice among several is this library's own search order, NOT RDKit's
+    Kekulize, and a system without a matching or on a class-4 bond to an upper-case atom stays aromatic."""
     tok = (tokenizer or get_tokenizer())["chartok_coords"]
     if normalize and not packed:
         raise ValueError("normalize=True needs packed=True: the atoms are respelled in the packed tables")
+    if kekulize and not packed:
+        raise ValueError("kekulize=True needs packed=True: the aromatic systems are rewritten in the packed tables")
     if expand and not packed:
         raise ValueError("expand=True needs packed=True: the labels are replaced in the packed tables")
     if molfile and not packed:
@@ -232,8 +242,10 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
             raise RuntimeError(f"a molecule has more atoms than the engine capacity max_atoms={engine.max_atoms}")
         drawn = rec                                                      # what the predicted atoms and bonds are read from
         if expand:
-            rec = engine.expand_pack(drawn, keep_device=molfile or smiles or normalize)     # what the writers read
+            rec = engine.expand_pack(drawn, keep_device=molfile or smiles or normalize or kekulize)     # what the writers read
         grown_rec = rec
+        if kekulize:
+            rec = kekule_rec = engine.kekulize_pack(rec, keep_device=molfile or smiles or normalize)
         if normalize:
             rec = engine.normalize_pack(rec, keep_device=molfile or smiles)
         ranked = engine.smiles_pack(rec, stereo=stereo, double_bonds=double_bonds, canonical=True,
@@ -251,13 +263,15 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
                 for key in ("canonical_rank", "symmetry_class"):
                     if key in g:
                         p[key] = g[key]
-        if normalize:
-            normal = unpack_graphs(rec["mols"], rec["atoms"], rec["bonds"], rec["text"], tok.maxx, compute_confidence)
-            for p, g, m in zip(preds, normal, rec["mols"]):
+        for key, respelled in (("kekulized", kekule_rec if kekulize else None), ("normalized", rec if normalize else None)):
+            if respelled is None:
+                continue
+            after = unpack_graphs(respelled["mols"], respelled["atoms"], respelled["bonds"], respelled["text"], tok.maxx, compute_confidence)
+            for p, g, m in zip(preds, after, respelled["mols"]):
                 a0, na = int(m["atom0"]), int(m["n_atoms"])
-                notes = rec["atom_notes"][a0:a0 + na]
-                p["normalized"] = {"symbols": g["chartok_coords"]["symbols"], "bonds": g["bonds"],
-                                   "hydrogens": (notes & NOTE_H_MASK).tolist(), "notes": notes.tolist(), "flags": int(m["flags"])}
+                notes = respelled["atom_notes"][a0:a0 + na]
+                p[key] = {"symbols": g["chartok_coords"]["symbols"], "bonds": g["bonds"],
+                          "hydrogens": (notes & NOTE_H_MASK).tolist(), "notes": notes.tolist(), "flags": int(m["flags"])}
         if molfile:
             files, data = engine.molfile_pack(rec, scale=molfile_scale)
             for p, f in zip(preds, files):
@@ -299,14 +313,18 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
     return preds
 
 
-def canonical_smiles(engine: Engine, smiles_list, expand: bool = False, normalize: bool = False) -> List[dict]:
+def canonical_smiles(engine: Engine, smiles_list, expand: bool = False, normalize: bool = False, kekulize: bool = False) -> List[dict]:
     """A caller's own SMILES in the form the device writes predictions in: mnx_smiles_read, optionally mnx_expand_pack ([Ph],
     [OMe], ... replaced by their atoms), then mnx_smiles_pack_canonical without marks. Per item {'smiles': the canonical string,
     None where the reader or the writer refused; 'read_flags' (engine.READ_*), 'err_pos' (of READ_SYNTAX), 'smiles_flags'
     (engine.SMILES_*)}. Equal strings mean equal graphs as this library sees them — no stereo, no kekulisation, no [CH] against
     C; it is NOT a toolkit's canonical SMILES and never compares with one. normalize: mnx_normalize_pack in front of the writer
     (behind the expansion): aromatic rings of 5 and 6 atoms perceived from a Kekule string, [CH] against C, N against [nH] — this
-    library's own rule, not a toolkit's aromaticity model; the items gain 'normalize_flags' (engine.MOL_AROMATIZED / ...)."""
+    library's own rule, not a toolkit's aromaticity model; the items gain 'normalize_flags' (engine.MOL_AROMATIZED / ...).
+    kekulize: mnx_kekulize_pack behind the expansion and in front of normalize — an aromatic string is written as a Kekule
+    structure first (a perfect matching in this library's own search order, not RDKit's Kekulize), so that with normalize an
+    aromatic string, a Kekule string and a half-aromatic one of the same molecule get one string where the rule finds the rings,
+    and without it azulene and its aromatic form do; the items gain 'kekulize_flags' (engine.MOL_KEKULIZED / ...)."""
     from .engine import READ_REFUSED, SMILES_REFUSED
     smiles_list = list(smiles_list)
     if not smiles_list:
@@ -315,16 +333,21 @@ def canonical_smiles(engine: Engine, smiles_list, expand: bool = False, normaliz
     read = rec["read"]
     if expand:
         rec = engine.expand_pack(rec, keep_device=True)
+    if kekulize:
+        rec = engine.kekulize_pack(rec, keep_device=True)
+    kekulize_flags = rec["mols"]["flags"]
     if normalize:
         rec = engine.normalize_pack(rec, keep_device=True)
     recs, _, data, _, _ = engine.smiles_pack(rec, canonical=True)
     out = []
-    for r, w, m in zip(read, recs, rec["mols"]):
+    for r, w, m, kf in zip(read, recs, rec["mols"], kekulize_flags):
         ok = not (int(r["flags"]) & READ_REFUSED or int(w["flags"]) & SMILES_REFUSED)
         out.append({"smiles": data[int(w["text0"]):int(w["text0"]) + int(w["len"])].decode("utf-8", "replace") if ok else None,
                     "read_flags": int(r["flags"]), "err_pos": int(r["err_pos"]), "smiles_flags": int(w["flags"])})
         if normalize:
             out[-1]["normalize_flags"] = int(m["flags"])
+        if kekulize:
+            out[-1]["kekulize_flags"] = int(kf)
     return out
 
 
@@ -388,7 +411,13 @@ class molnextr:
     normal spelling per atom before it is written (mnx_normalize_pack: aromatic rings of 5 and 6 atoms perceived from a Kekule
     drawing, brackets dropped where a reader infers them), and every output dict gains 'hydrogens', the H count per atom (in the
     order of expanded['symbols'] with graph_expand, of atom_sets without), and 'normalized' (symbols, bonds, notes, flags). This
-    library's own rule, NOT RDKit's aromaticity model; nothing kekulises and no toolkit has checked it."""
+    library's own rule, NOT RDKit's aromaticity model; no toolkit has checked it.
+    graph_kekulize: True (opt-in, default False; needs graph_smiles or graph_molfile; behind graph_expand, in front of
+    graph_normalize) = every aromatic system that has a Kekule structure is written as one before the molecule is written
+    (mnx_kekulize_pack), so the molfile of an aromatic prediction carries bond types 1 and 2 in the place of the query type 4,
+    and every output dict gains 'kekulized' (symbols, bonds, hydrogens, notes, flags). A Kekule structure is a perfect
+    matching; the choice among several is this library's own search order, NOT RDKit's Kekulize, and a system without a
+    matching stays aromatic (flags & MOL_KEKULE_LEFT)."""
 
     image_format = "fp32"
     packed_results = False
@@ -400,12 +429,13 @@ class molnextr:
     graph_symmetry = False
     graph_expand = False
     graph_normalize = False
+    graph_kekulize = False
 
     def __init__(self, model_path, device=None, max_batch: int = 32, dtype: str = DEFAULT_DTYPE,
                  device_preprocess: bool = True, image_format: str = "fp32", packed_results: bool = False,
                  graph_molfile: bool = False, graph_smiles: bool = False, graph_stereo: bool = False,
                  graph_double_bonds: bool = False, graph_canonical: bool = False, graph_expand: bool = False,
-                 graph_symmetry: bool = False, graph_normalize: bool = False):
+                 graph_symmetry: bool = False, graph_normalize: bool = False, graph_kekulize: bool = False):
         if model_path is None:
             raise ValueError("molnextr(model_path): a checkpoint path is required (pass 'synthetic' explicitly for the "
                              "deterministic test checkpoint)")
@@ -448,16 +478,19 @@ class molnextr:
         self.graph_normalize = bool(graph_normalize)
         if self.graph_normalize and not (self.graph_smiles or self.graph_molfile):
             raise ValueError("graph_normalize=True needs graph_smiles=True or graph_molfile=True: the normalised molecule is what they write")
+        self.graph_kekulize = bool(graph_kekulize)
+        if self.graph_kekulize and not (self.graph_smiles or self.graph_molfile):
+            raise ValueError("graph_kekulize=True needs graph_smiles=True or graph_molfile=True: the kekulised molecule is what they write")
         self.engine = Engine(states["encoder"], states["decoder"], device=device.index or 0, max_batch=max_batch,
                              dtype=dtype, image_format=image_format)
         self.input_size = args.input_size
         self.device_preprocess = device_preprocess
         self.group_images = 1024          # images per engine call of the throughput path (whole reference batches)
 
-    def canonical_smiles(self, smiles_list, expand: bool = False, normalize: bool = False) -> List[dict]:
+    def canonical_smiles(self, smiles_list, expand: bool = False, normalize: bool = False, kekulize: bool = False) -> List[dict]:
         """The canonical graph SMILES of the caller's own strings, for comparison with 'predicted_smiles' of graph_canonical=True
         (model.canonical_smiles: read on the device, optionally expanded and normalised, written without marks)."""
-        return canonical_smiles(self.engine, smiles_list, expand=expand, normalize=normalize)
+        return canonical_smiles(self.engine, smiles_list, expand=expand, normalize=normalize, kekulize=kekulize)
 
     _groups_done = 0          # groups of the running predict_images call that have produced predictions
 
@@ -643,6 +676,8 @@ class molnextr:
             conf["expand"] = True
         if self.graph_normalize:
             conf["normalize"] = True
+        if self.graph_kekulize:
+            conf["kekulize"] = True
         gen = self._prefetched(groups)
         try:
             for x in gen:
@@ -694,6 +729,8 @@ class molnextr:
                 d["expanded"] = pred["expanded"]              # follow expanded['symbols'], not atom_sets
             if "normalized" in pred:                          # graph_normalize: per atom of the molecule that was written
                 d["hydrogens"], d["normalized"] = pred["normalized"]["hydrogens"], pred["normalized"]
+            if "kekulized" in pred:                           # graph_kekulize: the molecule as it left mnx_kekulize_pack
+                d["kekulized"] = pred["kekulized"]
             if return_atoms_bonds:
                 c = pred["chartok_coords"]
                 atoms = []

@@ -35,7 +35,8 @@ is part of the product path and no number is asserted.
 (n) (only when asked for: --part n) normalisation on the device: mnx_normalize_pack alone, against mnx_expand_pack on the same
     input tables (the same shape of pass), and followed by mnx_smiles_pack_canonical against the canonical writer on the tables
     as they came — on the synthetic checkpoint's predictions (near-complete graphs), on hand-made molecules of drug-like size
-    with aromatic rings, and on those with the rings in Kekule form; `--normalize-out FILE` writes the table to a file of its own.
+    with aromatic rings, and on those with the rings in Kekule form; and mnx_kekulize_pack, the inverse pass, on the same tables
+    at the default step limit and at a limit of one step; `--normalize-out FILE` writes the table to a file of its own.
 The variants of a part alternate inside every repeat (A B A B ...), the table reports the median and the min .. max spread of
 each, and the spread of the fp32 path against itself is the yardstick for "not slower".
 """
@@ -622,8 +623,10 @@ def part_x(repeats, lines):
 def part_n(repeats, lines):
     """Normalisation on the device: one mnx_normalize_pack call (three launches) between two events, alternating with one
     mnx_expand_pack call on the same input tables (the same shape of pass: count, scan, fill, one workgroup per molecule), with
-    the canonical writer on the input and with normalize followed by the canonical writer. Every output buffer has the exact
-    size; the tables stay on the device."""
+    the canonical writer on the input and with normalize followed by the canonical writer, and with one mnx_kekulize_pack call
+    (the same shape of pass again) at the default step limit and at a limit of one step, where every search ends at its second
+    pairing: what the two differ by is the serial search lane. Every output buffer has the exact size; the tables stay on the
+    device."""
     import ctypes as C
     from molnextr_amd import engine as E
     from molnextr_amd.model import molnextr
@@ -637,11 +640,12 @@ def part_n(repeats, lines):
     def measure(rec, what):
         tables, args = eng._packed_tables(rec)
         n = len(rec["mols"])
-        ex, nz = eng.expand_pack(rec), eng.normalize_pack(rec, keep_device=True)
+        ex, nz, kk = eng.expand_pack(rec), eng.normalize_pack(rec, keep_device=True), eng.kekulize_pack(rec)
         cn = {"in": eng.smiles_pack(rec, canonical=True), "out": eng.smiles_pack(nz, canonical=True)}
-        sizes = {k: (len(r["atoms"]), len(r["bonds"]), len(r["text"])) for k, r in (("in", rec), ("x", ex), ("n", nz))}
+        sizes = {k: (len(r["atoms"]), len(r["bonds"]), len(r["text"])) for k, r in (("in", rec), ("x", ex), ("n", nz), ("k", kk))}
         mols_d, totals_d, totals_w = buf(n * 40), torch.zeros(4, dtype=torch.int32, device=dev), torch.zeros(2, dtype=torch.int32, device=dev)
-        tab = {k: (buf(sizes[k][0] * 24), buf(sizes[k][1] * 16), buf(sizes[k][2])) for k in ("x", "n")}
+        tab = {k: (buf(sizes[k][0] * 24), buf(sizes[k][1] * 16), buf(sizes[k][2])) for k in ("x", "n", "k")}
+        kek_notes_d = buf(sizes["k"][0])
         origin_d = torch.empty(max(sizes["x"][0], 1), dtype=torch.int16, device=dev)
         notes_d = buf(sizes["n"][0])
         recs_d = buf(n * 16)
@@ -658,9 +662,16 @@ def part_n(repeats, lines):
 
         normal_head = [ptr(mols_d), n, ptr(tab["n"][0]), sizes["n"][0], ptr(tab["n"][1]), sizes["n"][1], ptr(tab["n"][2]), sizes["n"][2]]
         normalize = lambda: table_pass(eng.lib.mnx_normalize_pack, "n", notes_d)      # noqa: E731
+
+        def kekulize(max_steps):
+            a, b, t = tab["k"]
+            return eng.lib.mnx_kekulize_pack(eng.h, *args, ptr(mols_d), ptr(a), sizes["k"][0], ptr(b), sizes["k"][1], ptr(t), sizes["k"][2],
+                                             ptr(kek_notes_d), ptr(totals_d), max_steps, stream())
+
         calls = {"mnx_expand_pack": lambda: table_pass(eng.lib.mnx_expand_pack, "x", origin_d), "mnx_normalize_pack": normalize,
                  "canonical, as it came": lambda: canonical(args, "in"),
-                 "normalize + canonical": lambda: normalize() or canonical(normal_head, "out")}
+                 "normalize + canonical": lambda: normalize() or canonical(normal_head, "out"),
+                 "mnx_kekulize_pack, 1 step": lambda: kekulize(1), "mnx_kekulize_pack": lambda: kekulize(0)}
         us = {k: [] for k in calls}
         for i in range(repeats + 3):
             for k, call in calls.items():
@@ -675,17 +686,24 @@ def part_n(repeats, lines):
                     us[k].append(a.elapsed_time(b) * 1000.0)
         assert tab["n"][2][:sizes["n"][2]].cpu().numpy().tobytes() == nz["text"] and notes_d[:sizes["n"][0]].cpu().numpy().tobytes() == nz["atom_notes"].tobytes()
         assert out_d[:len(cn["out"][2])].cpu().numpy().tobytes() == cn["out"][2]
+        assert tab["k"][2][:sizes["k"][2]].cpu().numpy().tobytes() == kk["text"] and kek_notes_d[:sizes["k"][0]].cpu().numpy().tobytes() == kk["atom_notes"].tobytes()
         flags, notes = nz["mols"]["flags"], nz["atom_notes"]
         lines.append(f"(n) one call over {n} {what}: {sizes['in'][0]} atoms, {sizes['in'][1]} bonds, {sizes['in'][2]} -> {sizes['n'][2]} bytes of "
                      f"text; aromatized {int((flags & E.MOL_AROMATIZED != 0).sum())} molecules ({int((notes & E.NOTE_AROMATIZED != 0).sum())} atoms), "
                      f"brackets removed in {int((flags & E.MOL_UNBRACKETED != 0).sum())}, refused {int((flags & E.MOL_NORMALIZE_REFUSED != 0).sum())}; "
                      f"the canonical writer refuses {int((cn['in'][0]['flags'] & E.SMILES_REFUSED != 0).sum())}")
-        lines.append("  device us between two events around the launches, the four alternating   median [min .. max]")
+        lines.append(f"    kekulized {int((kk['mols']['flags'] & E.MOL_KEKULIZED != 0).sum())} molecules ({int((kk['atom_notes'] & E.NOTE_KEKULIZED != 0).sum())} atoms), "
+                     f"left aromatic in {int((kk['mols']['flags'] & E.MOL_KEKULE_LEFT != 0).sum())}, refused {int((kk['mols']['flags'] & E.MOL_KEKULIZE_REFUSED != 0).sum())}")
+        lines.append("  device us between two events around the launches, the six alternating   median [min .. max]")
         for k in us:
             lines.append(f"  {k:24s} {fmt(us[k])} us")
         lines.append(f"  normalize / expand, median {statistics.median(us['mnx_normalize_pack']) / statistics.median(us['mnx_expand_pack']):.2f}; "
                      f"(normalize + canonical) / canonical, median "
                      f"{statistics.median(us['normalize + canonical']) / statistics.median(us['canonical, as it came']):.2f}")
+        ratios = sorted(k / z for k, z in zip(us["mnx_kekulize_pack"], us["mnx_normalize_pack"]))
+        search = 1.0 - statistics.median(us["mnx_kekulize_pack, 1 step"]) / statistics.median(us["mnx_kekulize_pack"])
+        lines.append(f"  kekulize / normalize, run by run: median {statistics.median(ratios):.2f} [{ratios[0]:.2f} .. {ratios[-1]:.2f}]; "
+                     f"the search beyond its first step: {100.0 * search:.0f} % of the call")
 
     pages = [W.synthetic_page(i % 15) for i in range(1024)]
     measure(eng.graph_pack(eng.predict(m._transform(pages), ref_batch=32)), "images of the synthetic checkpoint (near-complete graphs)")
