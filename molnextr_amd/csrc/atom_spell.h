@@ -1,5 +1,5 @@
-// atom_spell.h — an interpreted atom written out again, for the passes that respell atoms on the packed tables (normalize.hip,
-// kekulize.hip), once (internal): the element as one number, the organic subset, the hydrogens a reader infers at an unbracketed
+// atom_spell.h — an interpreted atom written out again, for the passes that respell atoms on the packed tables (normalize.hip and
+// kekulize.hip, through respell_pass.h, which packs the bytes into registers), once (internal): the element as one number, the organic subset, the hydrogens a reader infers at an unbracketed
 // upper-case atom, and the symbol byte by byte — unbracketed where a reader infers what the brackets would say, else a bracket atom
 // as smiles.hip spells one.
 #pragma once

@@ -1494,8 +1494,8 @@ int mnx_set_fragments(mnx_engine* h, const mnx_mol* frags, int32_t n_frags, cons
     return MNX_OK;
 }
 
-// What mnx_molfile_pack, mnx_expand_pack, mnx_smiles_pack, mnx_smiles_pack_stereo and mnx_smiles_pack_marks test before they launch, in the order in which a call refused for two reasons
-// reports them. The entry point tests its own pointers (outs_null, outs_skew); `aligned` is how its alignment message ends.
+// What mnx_molfile_pack, mnx_expand_pack, mnx_normalize_pack, mnx_kekulize_pack and the five mnx_smiles_pack* test before they launch, in
+// the order in which a call refused for two reasons reports them. Its own pointers (outs_null, outs_skew) the entry point tests; `aligned` ends its alignment message.
 static int check_packed_tables(mnx_engine* h, const char* fn, const PackedTables& t, bool outs_null, bool outs_skew,
                                const char* aligned) {
     if (!h) return MNX_ERR_INVALID_ARG;
@@ -1538,18 +1538,24 @@ int mnx_expand_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_ato
     return MNX_OK;
 }
 
+// mnx_normalize_pack and mnx_kekulize_pack (kekulize, with its max_steps): one check, one way to the pass's three launches
+static int respell_pack(mnx_engine* h, const char* fn, const PackedTables& t, const TablesOut& o, uint8_t* atom_notes, uint32_t* totals,
+                        void* stream, bool kekulize = false, uint32_t max_steps = 0) {
+    if (int rc = check_packed_tables(h, fn, t, tables_out_null(o, totals), tables_out_skew(o, totals), "the output tables too, totals 4-byte"))
+        return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (kekulize) HIPCHK(h, kekulize_pack_enqueue(h->st_dev, t, o, atom_notes, totals, max_steps, (hipStream_t)stream));
+    else HIPCHK(h, normalize_pack_enqueue(h->st_dev, t, o, atom_notes, totals, (hipStream_t)stream));
+    return MNX_OK;
+}
+
 int mnx_normalize_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
                        const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_mol* mols_out,
                        mnx_atom* atoms_out, uint32_t atom_cap, mnx_bond* bonds_out, uint32_t bond_cap, char* text_out,
                        uint32_t text_cap, uint8_t* atom_notes, uint32_t* totals, void* stream) {
     const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
     const TablesOut o = tables_out(mols_out, atoms_out, atom_cap, bonds_out, bond_cap, text_out, text_cap);
-    if (int rc = check_packed_tables(h, "mnx_normalize_pack", t, tables_out_null(o, totals), tables_out_skew(o, totals),
-                                     "the output tables too, totals 4-byte"))
-        return rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, normalize_pack_enqueue(h->st_dev, t, o, atom_notes, totals, (hipStream_t)stream));
-    return MNX_OK;
+    return respell_pack(h, "mnx_normalize_pack", t, o, atom_notes, totals, stream);
 }
 
 int mnx_kekulize_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
@@ -1558,12 +1564,7 @@ int mnx_kekulize_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_a
                       uint32_t text_cap, uint8_t* atom_notes, uint32_t* totals, uint32_t max_steps, void* stream) {
     const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
     const TablesOut o = tables_out(mols_out, atoms_out, atom_cap, bonds_out, bond_cap, text_out, text_cap);
-    if (int rc = check_packed_tables(h, "mnx_kekulize_pack", t, tables_out_null(o, totals), tables_out_skew(o, totals),
-                                     "the output tables too, totals 4-byte"))
-        return rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, kekulize_pack_enqueue(h->st_dev, t, o, atom_notes, totals, max_steps, (hipStream_t)stream));
-    return MNX_OK;
+    return respell_pack(h, "mnx_kekulize_pack", t, o, atom_notes, totals, stream, true, max_steps);
 }
 
 int mnx_smiles_read(mnx_engine* h, const char* bytes, uint32_t n_bytes, const uint32_t* offsets, int32_t n, mnx_mol* mols,

@@ -192,10 +192,7 @@ __global__ __launch_bounds__(EX_THREADS) void expand_kernel(
 
 hipError_t expand_pack_enqueue(const SymbolTables* st_dev, const FragView& fv, const PackedTables& t, const TablesOut& o,
                                unsigned short* origin, unsigned* totals, hipStream_t s) {
-    hipLaunchKernelGGL(expand_kernel<false>, dim3(t.n), dim3(EX_THREADS), 0, s, t, st_dev, fv, o, origin);
-    hipLaunchKernelGGL(mol_scan_kernel, dim3(1), dim3(MOL_SCAN_THREADS), 0, s, o, t.n, totals);
-    hipLaunchKernelGGL(expand_kernel<true>, dim3(t.n), dim3(EX_THREADS), 0, s, t, st_dev, fv, o, origin);
-    return hipGetLastError();
+    return count_scan_fill(expand_kernel<false>, expand_kernel<true>, t.n, EX_THREADS, o, totals, s, t, st_dev, fv, o, origin);
 }
 
 }  // namespace mnx

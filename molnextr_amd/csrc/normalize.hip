@@ -1,35 +1,19 @@
 // normalize.hip — one normal spelling per atom on the packed molecule tables (mnx_normalize_pack): aromatic rings perceived from
-// Kekule drawings, hydrogens counted, brackets dropped where a reader infers what they say. Packed tables in, packed tables of
-// the same record types out, atom and bond counts and order unchanged, so that every writer, the canonical ranks and
-// mnx_expand_pack run on the result as they are. The rule stands in include/molnextr_hip.h: it is this library's own and not a
-// toolkit's aromaticity model.
-//   count  one workgroup per molecule: the whole perception, the bytes of the new text -> mols_out[b]
-//   scan   exclusive scan of the three counts over the molecules -> atom0 / bond0 / text0, totals (tables_out.h)
-//   fill   one workgroup per molecule: the perception again, the records behind those offsets
-// Inside a workgroup: the atoms' interpretation (atom_symbol.h), then per atom its bond count, bond order sum and the first three
-// of its bonds in LDS (a candidate atom has at most three, so a graph of any density costs one pass over its bond records and
-// nothing that grows with a degree), then one thread per start atom walks the rings of 5 and 6 candidate atoms that begin at it
-// — twice: once to mark the bonds and atoms that lie on such a ring, once to judge every ring —, then every atom's new symbol,
-// placed by a prefix scan. LDS atomics count, add up, hand out the slots of a list that is sorted afterwards and set bits of
-// sets: no atomic decides a position, an order or a result. Every loop has a bound known at compile time or is a stride over
-// the molecule's records.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/molnextr_hip.h"
-#include "atom_spell.h"
-#include "atom_symbol.h"
-#include "dec_types.h"
-#include "tables_out.h"
+// Kekule drawings, hydrogens counted, brackets dropped where a reader infers what they say, so that every writer, the canonical
+// ranks and mnx_expand_pack run on the result as they are. A pass of respell_pass.h, where its frame is: count, scan and fill,
+// admission and refusal, the slots, the symbols' placing, the records written. The rule stands in include/molnextr_hip.h: it is
+// this library's own and not a toolkit's aromaticity model. Inside a workgroup, in count and again in fill: the atoms'
+// interpretation (atom_symbol.h), then per atom its bond count, bond order sum and the first three of its bonds in LDS (a
+// candidate atom has at most three, so a graph of any density costs one pass over its bond records and nothing that grows with a
+// degree), then one thread per start atom walks the rings of 5 and 6 candidate atoms that begin at it — twice: once to mark the
+// bonds and atoms that lie on such a ring, once to judge every ring —, then every atom's new symbol. Every loop has a bound known
+// at compile time or is a stride over the molecule's records.
+#include "respell_pass.h"
 
 namespace mnx {
 namespace {
 
-constexpr int NZ_THREADS = 256;
-constexpr int NZ_MAX = 1024;             // atoms held in LDS (999 at most)
-constexpr int NZ_PER = NZ_MAX / NZ_THREADS;
-constexpr unsigned NZ_NONE = 0xFFFFFFFFu;
-constexpr int NZ_WALK_STEPS = 384;       // 1 + 3 + 6 + 12 + 24 + 48 = 94 atoms on the walks from one start, four steps each
+constexpr int NZ_WALK_STEPS = 384;      // 1 + 3 + 6 + 12 + 24 + 48 = 94 atoms on the walks from one start, four steps each
 
 // ---- one of an atom's first three bonds: bits 0-9 the neighbour, bits 10-11 the order (1..3), bits 12-21 the bond record ----
 __device__ __forceinline__ unsigned slot_nbr(unsigned e) { return e & 1023u; }
@@ -44,7 +28,6 @@ __device__ __forceinline__ unsigned slot_bond(unsigned e) { return e >> 12 & 102
 constexpr unsigned ST_KIND = 4, ST_DSLOT = 6, ST_COPY = 1u << 8, ST_EXCLUDED = 1u << 9, ST_RSB = 10, ST_ONRING = 1u << 13;
 constexpr unsigned ST_AROMATIC = 1u << 14, ST_AB = 15, ST_KEEP = 1u << 18;
 constexpr unsigned KIND_D = 1, KIND_P = 2, KIND_E = 3;
-__device__ __forceinline__ unsigned st_h(unsigned s) { return s & 15u; }
 __device__ __forceinline__ unsigned st_kind(unsigned s) { return s >> ST_KIND & 3u; }
 __device__ __forceinline__ unsigned st_dslot(unsigned s) { return s >> ST_DSLOT & 3u; }
 
@@ -68,7 +51,7 @@ __device__ __forceinline__ void walk_rings(unsigned s, const unsigned* st, const
         next += 1u << (2 * depth);
         const unsigned last = (unsigned)(path >> (10 * depth)) & 1023u;
         const unsigned e = nbr3[3 * last + q];
-        if (e == NZ_NONE) continue;
+        if (e == RS_NONE) continue;
         const unsigned v = slot_nbr(e);
         if (v == s) {
             if (depth >= 4 && ((unsigned)(path >> 10) & 1023u) < last) found(path, depth + 1);
@@ -91,48 +74,35 @@ __device__ __forceinline__ unsigned slot_bit(const unsigned* nbr3, unsigned u, u
 #pragma unroll
     for (unsigned q = 0; q < 3; ++q) {
         const unsigned e = nbr3[3 * u + q];
-        if (e != NZ_NONE && slot_nbr(e) == v) bit = 1u << (base + q);
+        if (e != RS_NONE && slot_nbr(e) == v) bit = 1u << (base + q);
     }
     return bit;
 }
 
 template <bool FILL>
-__global__ __launch_bounds__(NZ_THREADS) void normalize_kernel(
+__global__ __launch_bounds__(RS_THREADS) void normalize_kernel(
         const PackedTables t, const SymbolTables* __restrict__ stab, const TablesOut o, unsigned char* __restrict__ notes) {
-    __shared__ unsigned info[NZ_MAX], elem[NZ_MAX];
-    __shared__ unsigned cnt[NZ_MAX];      // bond records at the atom: hands out the slots of nbr3
-    __shared__ unsigned acc[NZ_MAX];      // bits 0-11 bond order sum, bits 12-21 double bonds, bits 22-31 triple bonds
-    __shared__ unsigned st[NZ_MAX];
-    __shared__ unsigned nbr3[3 * NZ_MAX];
-    __shared__ unsigned scan[2 * NZ_THREADS];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const Molecule mol = admit_molecule(t, b);
-    const mnx_mol& m = mol.m;
-    auto record = [&](unsigned n_atoms, unsigned n_bonds, unsigned text_len, unsigned flags) {      // count's result
-        if (tid == 0) store_mol_counts(&o.mols[b], n_atoms, n_bonds, text_len, flags | (m.flags & MNX_MOL_TRUNCATED), m.overall_score);
-    };
-    mnx_mol mo;
-    if (FILL) {
-        mo = o.mols[b];
-        if (mo.flags & MNX_MOL_NORMALIZE_REFUSED) return;   // refused by count (the same for every thread)
-    } else if (mol.flags & (PT_BEYOND_TABLES | PT_TOO_LARGE)) {
-        record(0, 0, 0, MNX_MOL_NORMALIZE_REFUSED);
-        return;
-    }
-    const int na = (int)m.n_atoms, nb = (int)m.n_bonds;
-    const unsigned long long* A = (const unsigned long long*)mol.A;
-    const unsigned long long* B = (const unsigned long long*)mol.B;
+    __shared__ unsigned info[RS_MAX], elem[RS_MAX];
+    __shared__ unsigned cnt[RS_MAX];      // bond records at the atom: hands out the slots of nbr3
+    __shared__ unsigned acc[RS_MAX];      // bits 0-11 bond order sum, bits 12-21 double bonds, bits 22-31 triple bonds
+    __shared__ unsigned st[RS_MAX];
+    __shared__ unsigned nbr3[3 * RS_MAX];
+    __shared__ unsigned scan[2 * RS_THREADS];
+    const int tid = threadIdx.x;
+    RespellPass<FILL> p(t, o, MNX_MOL_NORMALIZE_REFUSED);
+    if (!p.admitted()) return;
+    const int na = p.na, nb = p.nb;
 
     // ---- the atoms as the writers read them; per atom its bond count, order sum and first three bonds ----
-    int bad = interpret_atoms<NZ_MAX, NZ_THREADS>(t, stab, mol, info, elem);
-    for (int a = tid; a < NZ_MAX; a += NZ_THREADS) {
+    int bad = interpret_atoms<RS_MAX, RS_THREADS>(t, stab, p.mol, info, elem);
+    for (int a = tid; a < RS_MAX; a += RS_THREADS) {
         cnt[a] = 0; acc[a] = 0; st[a] = 0;
-        nbr3[3 * a] = nbr3[3 * a + 1] = nbr3[3 * a + 2] = NZ_NONE;
+        nbr3[3 * a] = nbr3[3 * a + 1] = nbr3[3 * a + 2] = RS_NONE;
     }
     __syncthreads();
-    for (int k = tid; k < nb; k += NZ_THREADS) {
-        const unsigned w = (unsigned)B[2 * (size_t)k], i = w & 0xffffu, j = w >> 16, ty = (unsigned)(B[2 * (size_t)k] >> 32) & 0xffu;
-        if (i >= (unsigned)na || j >= (unsigned)na) { bad = 1; continue; }
+    for (int k = tid; k < nb; k += RS_THREADS) {
+        const auto [i, j, ty, beyond] = p.bond(k);
+        if (beyond) { bad = 1; continue; }
         const unsigned order = (ty == 1 || ty == 5 || ty == 6) ? 1u : (ty == 2 || ty == 3) ? ty : 0u;
         if (order == 0 || i == j) {       // class 4, no class of a bond, or a bond from an atom to itself: both ends are copied
             atomicOr(&st[i], ST_EXCLUDED);
@@ -140,27 +110,18 @@ __global__ __launch_bounds__(NZ_THREADS) void normalize_kernel(
             continue;
         }
         const unsigned add = order | (order == 2 ? 1u << 12 : 0u) | (order == 3 ? 1u << 22 : 0u);
-        const unsigned si = atomicAdd(&cnt[i], 1u), sj = atomicAdd(&cnt[j], 1u);    // any slot: the three are sorted below
-        if (si < 3) nbr3[3 * i + si] = j | order << 10 | (unsigned)k << 12;
-        if (sj < 3) nbr3[3 * j + sj] = i | order << 10 | (unsigned)k << 12;
+        hand_out_slots(cnt, nbr3, i, j | order << 10 | (unsigned)k << 12, j, i | order << 10 | (unsigned)k << 12);
         atomicAdd(&acc[i], add);          // sums and counts do not depend on the order of their terms
         atomicAdd(&acc[j], add);
     }
-    bad = __syncthreads_or(bad);
-    if (!FILL && bad) {                   // a symbol beyond the text or a bond that is no bond of the molecule
-        record(0, 0, 0, MNX_MOL_NORMALIZE_REFUSED);
-        return;
-    }
+    if (p.refuses(bad)) return;           // a symbol beyond the text or a bond that is no bond of the molecule
 
     // ---- every atom: hydrogens, whether it is a candidate and of which kind; its three slots in ascending order ----
-    for (int a = tid; a < na; a += NZ_THREADS) {
+    for (int a = tid; a < na; a += RS_THREADS) {
         const unsigned w = info[a], el = elem[a] & 0xffffu, deg = cnt[a];
         const unsigned bo = acc[a] & 4095u, n_double = acc[a] >> 12 & 1023u, n_triple = acc[a] >> 22;
-        unsigned e0 = nbr3[3 * a], e1 = nbr3[3 * a + 1], e2 = nbr3[3 * a + 2], x;
-        if (e0 > e1) { x = e0; e0 = e1; e1 = x; }
-        if (e1 > e2) { x = e1; e1 = e2; e2 = x; }
-        if (e0 > e1) { x = e0; e0 = e1; e1 = x; }
-        nbr3[3 * a] = e0; nbr3[3 * a + 1] = e1; nbr3[3 * a + 2] = e2;
+        unsigned e0, e1, e2;
+        sort_slots(&nbr3[3 * a], e0, e1, e2);
         unsigned s = st[a] & ST_EXCLUDED;
         if (info_cls(w) != CLS_ATOM || info_aromatic(w) || el == EL('R') || s) {
             st[a] = s | ST_COPY | (info_cls(w) == CLS_ATOM ? (unsigned)info_h(w) : 0u);
@@ -190,7 +151,7 @@ __global__ __launch_bounds__(NZ_THREADS) void normalize_kernel(
     __syncthreads();
 
     // ---- the enumerated rings, first pass: which bonds are ring-system bonds, which atoms lie on an enumerated ring ----
-    for (int a = tid; a < na; a += NZ_THREADS) {
+    for (int a = tid; a < na; a += RS_THREADS) {
         if (st_kind(st[a]) == 0) continue;
         walk_rings((unsigned)a, st, nbr3, [&](unsigned long long path, int n) {
 #pragma unroll
@@ -206,7 +167,7 @@ __global__ __launch_bounds__(NZ_THREADS) void normalize_kernel(
     __syncthreads();
     // ---- second pass: every ring's electrons; the atoms and bonds of a ring with 6 become aromatic. The verdict bits (14-17)
     //      are written here and read by no walk, so the verdicts do not depend on one another ----
-    for (int a = tid; a < na; a += NZ_THREADS) {
+    for (int a = tid; a < na; a += RS_THREADS) {
         if (st_kind(st[a]) == 0) continue;
         walk_rings((unsigned)a, st, nbr3, [&](unsigned long long path, int n) {
             unsigned electrons = 0;
@@ -239,80 +200,40 @@ __global__ __launch_bounds__(NZ_THREADS) void normalize_kernel(
     }
     __syncthreads();
 
-    // ---- every atom's new symbol: NZ_PER neighbouring atoms per thread, placed by a prefix scan over their lengths ----
-    const unsigned char* text_in = t.text + m.text0;
-    unsigned long long sym8[NZ_PER];      // a respelled symbol's bytes 0-7 (the first in the low byte) and 8-11
-    unsigned sym4[NZ_PER], len[NZ_PER], note[NZ_PER], sum = 0;
-    int any_aromatic = 0, any_plain = 0;
-#pragma unroll
-    for (int q = 0; q < NZ_PER; ++q) {
-        const int a = NZ_PER * tid + q;
-        sym8[q] = 0; sym4[q] = 0; len[q] = 0; note[q] = 0;
-        if (a >= na) continue;
-        const unsigned s = st[a], w = info[a];
-        note[q] = st_h(s);
-        if (s & ST_COPY) note[q] |= 64u;
-        if (s & (ST_COPY | ST_KEEP)) { len[q] = (unsigned)(A[3 * (size_t)a] >> 32) & 0xffffu; sum += len[q]; continue; }
-        const unsigned el = elem[a] & 0xffffu, deg = cnt[a], bo = acc[a] & 4095u;
-        const bool aromatic = (s & ST_AROMATIC) != 0;
-        const unsigned inferred = !aromatic ? implicit_h(el, bo) : el == EL('C') ? (deg <= 3 ? 3 - deg : 0u) : 0u;
-        unsigned n = 0;
-        unsigned long long lo = 0;
-        unsigned hi = 0;
-        const bool plain = spell_atom(el, aromatic, info_num(w), st_h(s), info_charge(w), inferred, [&](char c) {
-            if (n < 8u) lo |= (unsigned long long)(unsigned char)c << (8u * n);
-            else if (n < 12u) hi |= (unsigned)(unsigned char)c << (8u * (n - 8u));
-            ++n;
-        });
-        sym8[q] = lo; sym4[q] = hi; len[q] = n; sum += n;
-        if (aromatic) { note[q] |= 16u; any_aromatic = 1; }
-        if (plain && (w & 4u)) { note[q] |= 32u; any_plain = 1; }
-    }
-    unsigned total;
-    unsigned at = block_scan_excl<NZ_THREADS>(sum, scan, &total);
-    if (!FILL) {
-        any_aromatic = __syncthreads_or(any_aromatic);
-        any_plain = __syncthreads_or(any_plain);
-        record((unsigned)na, (unsigned)nb, total, (any_aromatic ? MNX_MOL_AROMATIZED : 0u) | (any_plain ? MNX_MOL_UNBRACKETED : 0u));
-        return;
-    }
-#pragma unroll
-    for (int q = 0; q < NZ_PER; ++q) {
-        const int a = NZ_PER * tid + q;
-        if (a >= na) continue;
-        const unsigned long long w0 = A[3 * (size_t)a], w1 = A[3 * (size_t)a + 1], w2 = A[3 * (size_t)a + 2];
-        const unsigned long long rec = (unsigned long long)mo.atom0 + (unsigned)a, to = (unsigned long long)mo.text0 + at;
-        if (put_atom(o, rec, atom_word0(at, len[q], 0u) | (w0 & ATOM_INDEX_BITS), w1 & ATOM_BINS_BITS, w2) && notes)
-            notes[rec] = (unsigned char)note[q];
-        if (st[a] & (ST_COPY | ST_KEEP)) put_text(o, to, text_in + (unsigned)w0, len[q]);
-        else
-            for (unsigned c = 0; c < len[q]; ++c)
-                if (to + c < o.text_cap) o.text[to + c] = (char)(c < 8u ? sym8[q] >> (8u * c) : (unsigned long long)(sym4[q] >> (8u * (c - 8u))));
-        at += len[q];
-    }
+    // ---- every atom's new symbol; an atom copied uninterpreted and a chiral carbon keep theirs ----
+    p.atoms(scan, notes, MNX_NOTE_AROMATIZED, MNX_MOL_AROMATIZED, MNX_NOTE_UNBRACKETED, MNX_MOL_UNBRACKETED,
+            [&](int a, Spelled& sym, unsigned& note) {
+                const unsigned s = st[a], w = info[a];
+                note = st_h(s);
+                if (s & ST_COPY) note |= MNX_NOTE_COPIED;
+                if (s & (ST_COPY | ST_KEEP)) return true;
+                const unsigned el = elem[a] & 0xffffu, deg = cnt[a], bo = acc[a] & 4095u;
+                const bool aromatic = (s & ST_AROMATIC) != 0;
+                const unsigned inferred = !aromatic ? implicit_h(el, bo) : el == EL('C') ? (deg <= 3 ? 3 - deg : 0u) : 0u;
+                const bool plain = spell_packed(sym, el, aromatic, info_num(w), st_h(s), info_charge(w), inferred);
+                if (aromatic) note |= MNX_NOTE_AROMATIZED;
+                if (plain && (w & 4u)) note |= MNX_NOTE_UNBRACKETED;
+                return false;
+            });
+    if (!FILL) return;
     // ---- the bonds: type = rev = 4 on an aromatic ring, every other record as it is ----
-    for (int k = tid; k < nb; k += NZ_THREADS) {
-        unsigned long long w0 = B[2 * (size_t)k] & BOND_FIELD_BITS;
-        const unsigned i = (unsigned)w0 & 0xffffu, si = st[i];
+    p.bonds([&](int k, unsigned i) {
+        const unsigned si = st[i];
         bool aromatic = false;
 #pragma unroll
         for (unsigned q = 0; q < 3; ++q) {
             const unsigned e = nbr3[3 * i + q];
-            aromatic |= e != NZ_NONE && slot_bond(e) == (unsigned)k && (si >> (ST_AB + q) & 1u);
+            aromatic |= e != RS_NONE && slot_bond(e) == (unsigned)k && (si >> (ST_AB + q) & 1u);
         }
-        if (aromatic) w0 = (w0 & 0xffffffffull) | 4ull << 32 | 4ull << 40;
-        put_bond(o, (unsigned long long)mo.bond0 + (unsigned)k, w0, B[2 * (size_t)k + 1]);
-    }
+        return aromatic ? 4ull : 0ull;
+    });
 }
 
 }  // namespace
 
 hipError_t normalize_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, const TablesOut& o, unsigned char* atom_notes,
                                   unsigned* totals, hipStream_t s) {
-    hipLaunchKernelGGL(normalize_kernel<false>, dim3(t.n), dim3(NZ_THREADS), 0, s, t, st_dev, o, atom_notes);
-    hipLaunchKernelGGL(mol_scan_kernel, dim3(1), dim3(MOL_SCAN_THREADS), 0, s, o, t.n, totals);
-    hipLaunchKernelGGL(normalize_kernel<true>, dim3(t.n), dim3(NZ_THREADS), 0, s, t, st_dev, o, atom_notes);
-    return hipGetLastError();
+    return count_scan_fill(normalize_kernel<false>, normalize_kernel<true>, t.n, RS_THREADS, o, totals, s, t, st_dev, o, atom_notes);
 }
 
 }  // namespace mnx

@@ -333,10 +333,7 @@ __global__ __launch_bounds__(SR_THREADS) void smiles_read_kernel(
 
 hipError_t smiles_read_enqueue(const unsigned char* bytes, unsigned n_bytes, const unsigned* offsets, int n, mnx_read* recs,
                                const TablesOut& o, unsigned* totals, hipStream_t s) {
-    hipLaunchKernelGGL(smiles_read_kernel<false>, dim3(n), dim3(SR_THREADS), 0, s, bytes, n_bytes, offsets, recs, o);
-    hipLaunchKernelGGL(mol_scan_kernel, dim3(1), dim3(MOL_SCAN_THREADS), 0, s, o, n, totals);
-    hipLaunchKernelGGL(smiles_read_kernel<true>, dim3(n), dim3(SR_THREADS), 0, s, bytes, n_bytes, offsets, recs, o);
-    return hipGetLastError();
+    return count_scan_fill(smiles_read_kernel<false>, smiles_read_kernel<true>, n, SR_THREADS, o, totals, s, bytes, n_bytes, offsets, recs, o);
 }
 
 }  // namespace mnx

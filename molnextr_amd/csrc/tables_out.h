@@ -1,7 +1,8 @@
-// tables_out.h — the output side of the table writers (graph_pack.hip, expand.hip, smiles_read.hip), once (internal): how the
-// fields of an atom and a bond record lie in their 64-bit words, the capped stores behind an offset, what a count kernel leaves
-// in mnx_mol, and the scan over the molecules between count and fill. A fill kernel says where a record's fields come from;
-// where they go is here. The arenas arrive as a TablesOut (dec_types.h).
+// tables_out.h — the output side of the table writers (graph_pack.hip, expand.hip, smiles_read.hip, and normalize.hip and
+// kekulize.hip through respell_pass.h), once (internal): how the fields of an atom and a bond record lie in their 64-bit words,
+// the capped stores behind an offset, what a count kernel leaves in mnx_mol, the scan over the molecules between count and fill,
+// and the three launches. A fill kernel says where a record's fields come from; where they go is here. The arenas arrive as a
+// TablesOut (dec_types.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -98,6 +99,17 @@ static __global__ __launch_bounds__(MOL_SCAN_THREADS) void mol_scan_kernel(const
         totals[2] = (unsigned)min(ct, 0xffffffffull);
         totals[3] = (ca > o.atom_cap || cb > o.bond_cap || ct > o.text_cap) ? 1u : 0u;
     }
+}
+
+// The three launches of a table writer whose count and fill kernels take the same arguments, one workgroup of `threads` per
+// molecule: count, the scan over the n molecules, fill.
+template <typename Count, typename Fill, typename... Args>
+hipError_t count_scan_fill(Count count_kernel, Fill fill_kernel, int n, int threads, const TablesOut& o, unsigned* totals,
+                           hipStream_t s, Args... args) {
+    hipLaunchKernelGGL(count_kernel, dim3(n), dim3(threads), 0, s, args...);
+    hipLaunchKernelGGL(mol_scan_kernel, dim3(1), dim3(MOL_SCAN_THREADS), 0, s, o, n, totals);
+    hipLaunchKernelGGL(fill_kernel, dim3(n), dim3(threads), 0, s, args...);
+    return hipGetLastError();
 }
 
 }  // namespace mnx

@@ -949,14 +949,14 @@ class Engine:
                                   lambda mols, arenas, totals: self.lib.mnx_graph_pack(self.h, *head, mols, *arenas, totals, _stream()),
                                   dev, keep_device)
 
-    def _sized_tables(self, fn: str, n: int, caps, call, dev, keep_device: bool) -> dict:
+    def _sized_tables(self, fn: str, n: int, caps, call, dev, keep_device: bool, side=None) -> dict:
         """One table writer over n molecules at capacities caps = (atom_cap, bond_cap, text_cap) and at most once more with
         the sizes `totals` reports: {'mols' [n] MOL_DTYPE, 'atoms' ATOM_DTYPE, 'bonds' BOND_DTYPE, 'text' bytes, 'totals'
         uint32 [4]}, keep_device: plus 'device' = the four tables as the uint8 device tensors they were written to.
         call(mols, arenas, totals) makes the library call lib.<fn> for one set of arenas and returns its code: mols and
-        totals are pointers, arenas = [atoms, atom_cap, bonds, bond_cap, text, text_cap] as the three writers take them. call runs
-        once per attempt, so an output of its own that is sized by a capacity (expand_pack's `origin`, by arenas[1]) is allocated
-        inside it; the caller reads the one of the last attempt."""
+        totals are pointers, arenas = [atoms, atom_cap, bonds, bond_cap, text, text_cap] as the three writers take them. side: the
+        torch dtype of an output per atom (expand_pack's `origin`, the `atom_notes`), allocated at every attempt's atom capacity:
+        call takes its pointer as a fourth argument, and 'side' is the last attempt's, one element per atom, on the device."""
         mols = torch.empty(n * MOL_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         totals = torch.empty(4, dtype=torch.int32, device=dev)
         caps = tuple(int(c) for c in caps)
@@ -965,7 +965,8 @@ class Engine:
             bonds = torch.empty(max(caps[1], 1) * BOND_DTYPE.itemsize, dtype=torch.uint8, device=dev)
             text = torch.empty(max(caps[2], 1), dtype=torch.uint8, device=dev)
             arenas = [_ptr(atoms), caps[0], _ptr(bonds), caps[1], _ptr(text), caps[2]]
-            self._check(call(_ptr(mols), arenas, _ptr(totals)), fn)
+            per_atom = [] if side is None else [torch.empty(max(caps[0], 1), dtype=side, device=dev)]
+            self._check(call(_ptr(mols), arenas, _ptr(totals), *map(_ptr, per_atom)), fn)
             tot = totals.cpu().numpy().view(np.uint32)
             if not tot[3]:
                 break
@@ -979,6 +980,8 @@ class Engine:
                "text": text[:nt].cpu().numpy().tobytes(), "totals": tot.copy()}
         if keep_device:
             rec["device"] = (mols, atoms, bonds, text)
+        if per_atom:
+            rec["side"] = per_atom[0][:na]
         return rec
 
     def _packed_tables(self, rec: dict):
@@ -1093,14 +1096,24 @@ class Engine:
         tables, args = self._packed_tables(rec)
         if caps is None:        # room for a label of about ten atoms per molecule before the repeat
             caps = (len(rec["atoms"]) + 12 * n, len(rec["bonds"]) + 12 * n, len(rec["text"]) + 16 * n)
-        origin = []             # per atom: one per attempt, of the attempt's atom capacity
+        out = self._sized_tables("mnx_expand_pack", n, caps,
+                                 lambda mols, arenas, totals, origin: self.lib.mnx_expand_pack(self.h, *args, mols, *arenas, origin, totals, _stream()),
+                                 dev, keep_device, side=torch.int16)
+        out["origin"] = out.pop("side").cpu().numpy().view(np.uint16)
+        return out
 
-        def call(mols, arenas, totals):
-            origin[:] = [torch.empty(max(arenas[1], 1), dtype=torch.int16, device=dev)]
-            return self.lib.mnx_expand_pack(self.h, *args, mols, *arenas, _ptr(origin[0]), totals, _stream())
-
-        out = self._sized_tables("mnx_expand_pack", n, caps, call, dev, keep_device)
-        out["origin"] = origin[0][:len(out["atoms"])].cpu().numpy().view(np.uint16)
+    def _respell_pack(self, fn: str, rec: dict, caps, keep_device: bool, tail=()) -> dict:
+        """normalize_pack and kekulize_pack: lib.<fn>(h, tables, mols_out, arenas, atom_notes, totals, *tail, stream) from the
+        input's sizes — a new symbol is rarely longer than the old one — or caps, with 'atom_notes' uint8 [atoms]"""
+        dev = torch.device("cuda", self.device)
+        n = len(rec["mols"])
+        tables, args = self._packed_tables(rec)
+        if caps is None:
+            caps = (len(rec["atoms"]), len(rec["bonds"]), len(rec["text"]) + 2 * n)
+        out = self._sized_tables(fn, n, caps,
+                                 lambda mols, arenas, totals, notes: getattr(self.lib, fn)(self.h, *args, mols, *arenas, notes, totals, *tail, _stream()),
+                                 dev, keep_device, side=torch.uint8)
+        out["atom_notes"] = out.pop("side").cpu().numpy()
         return out
 
     def normalize_pack(self, rec: dict, caps=None, keep_device: bool = False) -> dict:
@@ -1113,20 +1126,7 @@ class Engine:
         MOL_AROMATIZED / MOL_UNBRACKETED / MOL_NORMALIZE_REFUSED. Starts from the input's sizes (a new symbol is rarely longer
         than the old one; or caps = (atom_cap, bond_cap, text_cap)) and repeats at most once with the sizes `totals` reports.
         keep_device: also 'device', as graph_pack."""
-        dev = torch.device("cuda", self.device)
-        n = len(rec["mols"])
-        tables, args = self._packed_tables(rec)
-        if caps is None:
-            caps = (len(rec["atoms"]), len(rec["bonds"]), len(rec["text"]) + 2 * n)
-        notes = []              # per atom: one per attempt, of the attempt's atom capacity
-
-        def call(mols, arenas, totals):
-            notes[:] = [torch.empty(max(arenas[1], 1), dtype=torch.uint8, device=dev)]
-            return self.lib.mnx_normalize_pack(self.h, *args, mols, *arenas, _ptr(notes[0]), totals, _stream())
-
-        out = self._sized_tables("mnx_normalize_pack", n, caps, call, dev, keep_device)
-        out["atom_notes"] = notes[0][:len(out["atoms"])].cpu().numpy()
-        return out
+        return self._respell_pack("mnx_normalize_pack", rec, caps, keep_device)
 
     def kekulize_pack(self, rec: dict, caps=None, keep_device: bool = False, max_steps: int = 0) -> dict:
         """graph_pack's records (or expand_pack's, or smiles_read's) -> the same molecules with every aromatic system that has a
@@ -1138,20 +1138,7 @@ class Engine:
         aromatic atom, NOTE_KEKULIZED / NOTE_KEKULE_LEFT (with NOTE_KEKULE_LIMIT) / NOTE_COPIED. Atom and bond counts and order
         are the input's; mols['flags'] carries MOL_KEKULIZED / MOL_KEKULE_LEFT / MOL_KEKULIZE_REFUSED. Run it behind expand_pack
         and in front of normalize_pack. Sizes itself as normalize_pack does; keep_device: also 'device', as graph_pack."""
-        dev = torch.device("cuda", self.device)
-        n = len(rec["mols"])
-        tables, args = self._packed_tables(rec)
-        if caps is None:
-            caps = (len(rec["atoms"]), len(rec["bonds"]), len(rec["text"]) + 2 * n)
-        notes = []              # per atom: one per attempt, of the attempt's atom capacity
-
-        def call(mols, arenas, totals):
-            notes[:] = [torch.empty(max(arenas[1], 1), dtype=torch.uint8, device=dev)]
-            return self.lib.mnx_kekulize_pack(self.h, *args, mols, *arenas, _ptr(notes[0]), totals, int(max_steps), _stream())
-
-        out = self._sized_tables("mnx_kekulize_pack", n, caps, call, dev, keep_device)
-        out["atom_notes"] = notes[0][:len(out["atoms"])].cpu().numpy()
-        return out
+        return self._respell_pack("mnx_kekulize_pack", rec, caps, keep_device, (int(max_steps),))
 
     def smiles_read(self, strings, caps=None, keep_device: bool = False) -> dict:
         """SMILES strings (str or bytes) -> the molecules as packed tables, read on the device (mnx_smiles_read; the rule:

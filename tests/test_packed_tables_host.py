@@ -117,3 +117,26 @@ def test_same_results_sees_every_field(text_pair, tables_pair):
                 same_results(got, got._replace(**{field: x}))
         with pytest.raises(AssertionError):
             same_results(got, got._replace(rc=1))
+
+
+def test_the_respelling_passes_keep_their_python_signatures_and_c_argument_lists():
+    """Engine.normalize_pack and Engine.kekulize_pack as documented, and the argument types of the two library functions in the
+    header's count and order: h, the four input tables with their sizes, mols_out, the three arenas with their capacities,
+    atom_notes, totals, (max_steps,) stream"""
+    import ctypes as C
+    import inspect
+
+    from molnextr_amd import engine
+    def parameters(f):
+        return [(p.name, p.default) for p in inspect.signature(f).parameters.values()]
+
+    free = inspect.Parameter.empty
+    assert parameters(engine.Engine.normalize_pack) == [("self", free), ("rec", free), ("caps", None), ("keep_device", False)]
+    assert parameters(engine.Engine.kekulize_pack) == [("self", free), ("rec", free), ("caps", None), ("keep_device", False), ("max_steps", 0)]
+    vp, u32 = C.c_void_p, C.c_uint32
+    tables_in = [vp, C.c_int32, vp, u32, vp, u32, vp, u32]
+    tables_out = [vp, vp, u32, vp, u32, vp, u32]
+    lib = engine.load_library()
+    assert list(lib.mnx_normalize_pack.argtypes) == [vp] + tables_in + tables_out + [vp, vp, vp]
+    assert list(lib.mnx_kekulize_pack.argtypes) == [vp] + tables_in + tables_out + [vp, vp, u32, vp]
+    assert lib.mnx_normalize_pack.restype is C.c_int and lib.mnx_kekulize_pack.restype is C.c_int
