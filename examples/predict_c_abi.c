@@ -163,6 +163,44 @@ static int print_first_expanded_smiles(mnx_engine* eng, int n_images, const mnx_
     return rc;
 }
 
+/* The same molecules with their condensed-formula labels ('CH2CH3', 'N(CH3)2', 'COOCH3', 'CH2Ph': labels that are in neither
+ * name table) replaced by the atoms and bonds a valence-guided search finds for them (mnx_formula_pack), in front of the
+ * expansion above, which also replaces the group tokens a formula holds ('[Ph]'): the same two passes of sizing and writing. The
+ * rule is this library's own repair of the reference's search; no toolkit has parsed the result, and a label the search finds
+ * no structure for stays a '*'. */
+static int print_first_formula_smiles(mnx_engine* eng, int n_images, const mnx_mol* mols_dev, const mnx_atom* atoms_dev,
+                                      const mnx_bond* bonds_dev, const char* text_dev, const uint32_t* table_sizes) {
+    uint32_t totals[4] = {0, 0, 0, 0}, *totals_dev = NULL;
+    mnx_mol *mols2_dev = NULL, mol;
+    mnx_atom* atoms2_dev = NULL;
+    mnx_bond* bonds2_dev = NULL;
+    char* text2_dev = NULL;
+    int rc, pass;
+    hipMalloc((void**)&mols2_dev, (size_t)n_images * sizeof(mnx_mol));
+    hipMalloc((void**)&totals_dev, sizeof totals);
+    for (pass = 0; pass < 2; ++pass) {
+        rc = mnx_formula_pack(eng, mols_dev, n_images, atoms_dev, table_sizes[0], bonds_dev, table_sizes[1], text_dev, table_sizes[2],
+                              mols2_dev, atoms2_dev, pass ? totals[0] : 0, bonds2_dev, pass ? totals[1] : 0, text2_dev,
+                              pass ? totals[2] : 0, /*origin=*/NULL, totals_dev, /*max_steps=*/0, /*stream=*/NULL);
+        if (rc != MNX_OK) { fprintf(stderr, "%s\n", mnx_last_error(eng)); break; }
+        hipMemcpy(totals, totals_dev, sizeof totals, 2);
+        if (pass == 0) {
+            hipMalloc((void**)&atoms2_dev, ((size_t)totals[0] + 1) * sizeof(mnx_atom));
+            hipMalloc((void**)&bonds2_dev, ((size_t)totals[1] + 1) * sizeof(mnx_bond));
+            hipMalloc((void**)&text2_dev, (size_t)totals[2] + 1);
+        }
+    }
+    if (rc == MNX_OK) {
+        hipMemcpy(&mol, mols2_dev, sizeof mol, 2);
+        printf("molecule 0 with its formulas replaced: %u atoms, %u bonds%s%s%s\n", (unsigned)mol.n_atoms, (unsigned)mol.n_bonds,
+               (mol.flags & MNX_MOL_FORMULA_EXPANDED) ? ", a formula replaced" : "", (mol.flags & MNX_MOL_FORMULA_LEFT) ? ", a formula left" : "",
+               (mol.flags & MNX_MOL_FORMULA_REFUSED) ? ", refused" : "");
+        rc = print_first_expanded_smiles(eng, n_images, mols2_dev, atoms2_dev, bonds2_dev, text2_dev, totals);
+    }
+    hipFree(mols2_dev); hipFree(totals_dev); hipFree(atoms2_dev); hipFree(bonds2_dev); hipFree(text2_dev);
+    return rc;
+}
+
 /* A caller's own SMILES in the form the predictions are written in (mnx_smiles_read, then the canonical writer): two strings of
  * one molecule read on the device into packed tables of the same record types, so print_first_canonical_smiles takes them as
  * they are. Needs no symbol tables itself; a refused string (mnx_read.flags) is the empty molecule. No toolkit has parsed these
@@ -245,6 +283,7 @@ static int print_first_molecule(mnx_engine* eng, int n_images, const int32_t* to
         if (rc == MNX_OK) rc = print_first_graph_smiles(eng, n_images, mols_dev, atoms_dev, bonds_dev, text_dev, totals);
         if (rc == MNX_OK) rc = print_first_canonical_smiles(eng, n_images, mols_dev, atoms_dev, bonds_dev, text_dev, totals);
         if (rc == MNX_OK) rc = print_first_expanded_smiles(eng, n_images, mols_dev, atoms_dev, bonds_dev, text_dev, totals);
+        if (rc == MNX_OK) rc = print_first_formula_smiles(eng, n_images, mols_dev, atoms_dev, bonds_dev, text_dev, totals);
         if (rc == MNX_OK) rc = print_canonical_of_known_smiles(eng);
     }
     hipFree(mols_dev); hipFree(totals_dev); hipFree(atoms_dev); hipFree(bonds_dev); hipFree(text_dev);

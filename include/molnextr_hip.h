@@ -412,7 +412,7 @@ int mnx_set_vocab_text(mnx_engine* h, const char* bytes, const uint32_t* offsets
  * size outside the limits, the scores partly set, misaligned records, or no vocabulary text / token classes set. */
 typedef struct mnx_mol {
     uint32_t atom0, n_atoms, bond0, n_bonds, text0, smiles_len;
-    uint32_t flags;             /* bit 0: more atoms than kmax, tables truncated to kmax; MNX_MOL_EXPAND* of mnx_expand_pack; bits 4-6 of mnx_normalize_pack; bits 7-9 of mnx_kekulize_pack */
+    uint32_t flags;             /* bit 0: more atoms than kmax, tables truncated to kmax; MNX_MOL_EXPAND* of mnx_expand_pack; bits 4-6 of mnx_normalize_pack; bits 7-9 of mnx_kekulize_pack; bits 10, 11, 16, 17 of mnx_formula_pack */
     uint32_t reserved;          /* 0 */
     double overall_score;
 } mnx_mol;
@@ -870,9 +870,9 @@ int mnx_set_fragments(mnx_engine* h, const mnx_mol* frags, int32_t n_frags, cons
 /* Abbreviation labels replaced by their atoms and bonds, on the device: packed tables of mnx_graph_pack in, packed tables of the
  * SAME record types out, so that mnx_molfile_pack and the four mnx_smiles_pack calls run on the expanded molecule unchanged — a
  * label on one drawing and the drawn-out group on another then get the same canonical string. What the reference's
- * _expand_functional_group does for an alias that is a key of its table; from a table only: the reference's condensed-formula
- * parser ('CH2CH3', 'N(CH3)2' built by a valence search) and its fragments of zero atoms ('H3', '(H)': delete the atom) are out
- * of scope, such a label stays. No toolkit has parsed or sanitised the result. A post-pass on a post-pass: it reads the input
+ * _expand_functional_group does for an alias that is a key of its table; from a table only: a condensed formula ('CH2CH3',
+ * 'N(CH3)2') is mnx_formula_pack's, in front of this call, and the reference's fragments of zero atoms ('H3', '(H)': delete the
+ * atom) are out of scope, such a label stays. No toolkit has parsed or sanitised the result. A post-pass on a post-pass: it reads the input
  * tables, changes none of them (the outputs must not overlap them) and touches no decode state.
  *
  * Which atoms expand: an atom whose symbol, read as mnx_molfile_pack reads it (one pair of enclosing '[' ']' stripped, the
@@ -917,6 +917,82 @@ int mnx_expand_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_ato
                     const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_mol* mols_out,
                     mnx_atom* atoms_out, uint32_t atom_cap, mnx_bond* bonds_out, uint32_t bond_cap, char* text_out,
                     uint32_t text_cap, uint16_t* origin, uint32_t* totals, void* stream);
+
+/* Condensed-formula labels replaced by the atoms and bonds they spell, on the device: packed tables in, packed tables of the SAME
+ * record types out. mnx_expand_pack replaces a label only when its name has a fragment; every other label the tokenizer can spell
+ * character by character ('CH2CH3', 'N(CH3)2', 'COOCH3', 'SO2CH3', 'CH2Ph', '(CH2)2OH') is this call's. Intended order:
+ * mnx_graph_pack or mnx_smiles_read -> THIS CALL -> mnx_expand_pack -> mnx_kekulize_pack -> mnx_normalize_pack -> the writers.
+ * THE RULE IS THIS LIBRARY'S OWN: it keeps the shape of the reference's valence-guided search (get_smiles_from_symbol: placement
+ * order, branch-or-chain decision, direction retry) and repairs it so that its result is a molecule — hydrogens are counted,
+ * no bond above order 3, no bonds left over at the end, a step limit. No toolkit has parsed the result. A post-pass on a post-pass:
+ * it reads the input tables, changes none of them (the outputs must not overlap them) and touches no decode state.
+ *
+ * Candidates: an atom whose symbol, read as mnx_molfile_pack reads it, has no parse as an atom of the grammar, is in neither
+ *   symbol table, and has 2 to 20 bytes after one pair of enclosing '[' ']' is stripped. R-groups and table names never come
+ *   here, with or without a fragment. A candidate with a bond record of class 4 (aromatic), or of a type outside 1, 2, 3, 5, 6,
+ *   stays a label.
+ * Tokens, left to right: '(' , ')' and a run of digits (a count, 1..99). At an upper-case byte the maximal run [A-Z][a-z]*: if it
+ *   is an element of the valence table, that element; otherwise the longest name of the abbreviation table that HAS a fragment
+ *   (frag_of_name >= 0) and matches at this position is a group token. At a lower-case byte only such a name matches ('tBu' in
+ *   'CO2tBu'). Any other byte ('=', '#', '+', '-', ',', ...): the label stays.
+ * Valences, in the order of trial: H 1; B 3; C 4; N 3, 5; O 2; F, Cl, Br, I 1; Si 4; P 5, 3; S 6, 4, 2. A group token has
+ *   valence 1. P and S try the highest first: the condensed formulas that occur (SO2, PO3, SO2NH2) mean that state, and the end
+ *   condition rejects it where it is wrong (SH, SCH3).
+ * Units: an element, a group token or a parenthesised sequence (not empty, nesting depth at most 3), each with an optional count
+ *   behind it; a count anywhere else: the label stays. Counts are written out: a unit with count k is k units, but 'Hk' is ONE
+ *   unit of k hydrogens. 'C' with a count n > 1 directly followed by an element X with count m is n times C, each followed by
+ *   m / n X, the remainder behind the last: C2H5 = CH2CH3. More than 96 units and parentheses, or more than 32 heavy atoms and
+ *   group tokens, written out: the label stays.
+ * The search: start = the bond-order sum of the label's bond records (types 1, 5, 6 count 1; 2 and 3 their order); above 6 the
+ *   label stays. Direction 1 places the units from left to right; if that finds no structure, direction -1 places them from
+ *   right to left (every parenthesis turned round). Units are placed in order onto a CURRENT atom with `free` bonds:
+ *   - The first heavy atom or group token of the label takes the label's bonds: it needs a valence v >= start, becomes the current
+ *     atom, free = v - start.
+ *   - A heavy atom or group token of valence v, with free >= 1: if free > v it is a leaf on a bond of order v and free -= v;
+ *     otherwise its bond has order `free`, it becomes the current atom, and free = v - free. free == 0: the branch fails.
+ *   - k hydrogens need free >= k and are recorded as the H COUNT of the current atom, free -= k; they are never atoms, and
+ *     without a current atom (first of the label or of a branch) the branch fails.
+ *   - '(' with a current atom that has more than 1 bond free opens a BRANCH: its first heavy atom hangs on the current atom
+ *     (valence >= 1, free = v - 1) and the units up to its ')' are placed onto it and its successors. At the ')' the bonds left
+ *     free raise the order of the joining bond to 1 + left, the current atom is the one in front of the '(' again, and its free
+ *     bonds are reduced by that order: C(O)CH3 is C(=O)C. Left-over bonds beyond those of the current atom fail the branch.
+ *     Any other '(' (1 bond free, or no current atom yet) and its ')' change nothing: the group continues the chain. 0 bonds
+ *     free: the branch fails.
+ *   - A bond order above 3 fails the branch.
+ *   - The end of the label needs free == 0: every hydrogen of a condensed formula is written, nothing is inferred.
+ *   - Valences are tried in table order with backtracking through the whole label (depth first; the last element placed that
+ *     has another valence tries it next).
+ *   - Every placement of a heavy atom, a group token or a unit of hydrogens is a step, counted over both directions; beyond
+ *     max_steps (0: MNX_FORMULA_DEFAULT_STEPS) the label stays and MNX_MOL_FORMULA_LIMIT is set.
+ * Output: exactly mnx_expand_pack's rule for atoms, bonds, text and origin, with the searched structure in the place of the
+ *   table's fragment: atom 0 is the first placed atom and stays at the label's index, the others are appended behind the
+ *   molecule's own atoms in placement order, labels in ascending index; all atoms of a structure share the label's index,
+ *   coordinates and score; the structure's bonds have rev = type and the label atom's score, the rows sorted by (i, j) as there.
+ *   A heavy atom is spelled unbracketed when it is of B C N O P S F Cl Br I and a reader infers its H count from its bond-order
+ *   sum (the smallest normal valence that fits, as mnx_normalize_pack), else as a bracket atom with its H count: CH2CH3 writes
+ *   'C', 'C' — the bytes the table's Et gives —, Si(CH3)3 writes '[Si]', 'C', 'C', 'C'. A group token is written as '[Name]', so
+ *   that the following mnx_expand_pack expands it.
+ * mnx_mol.flags of the output: bit 0 is copied; MNX_MOL_FORMULA_EXPANDED: at least one label was replaced;
+ *   MNX_MOL_FORMULA_LEFT: a candidate stayed (no tokenisation, no structure, too large, a bond that is no bond order, the step
+ *   limit); MNX_MOL_FORMULA_LIMIT: the search of a label passed the step limit; MNX_MOL_FORMULA_REFUSED: the refusal conditions
+ *   of MNX_MOL_EXPAND_REFUSED. A refused molecule has n_atoms = n_bonds = smiles_len = 0 in mols_out. overall_score is copied.
+ * What it is not: a two-ended label ('CH2CH2' between two atoms) keeps all its bonds on atom 0 and usually finds no structure —
+ *   that would need the drawing's left and right; rings (C6H5, C6H11), explicit bond symbols, charges and isotopes ('D' included)
+ *   are refused; PO3H2 finds no structure, because the chain rule gives the second O the last bonds; where several structures are
+ *   valid the valence order decides.
+ * Inputs, outputs, the capacity / totals protocol, determinism and the launches (three, asynchronous on `stream`, no allocation, no
+ * host synchronisation) are mnx_expand_pack's. mnx_set_symbol_tables and mnx_set_fragments must have been called.
+ * MNX_ERR_INVALID_ARG (with mnx_last_error, "mnx_formula_pack: ..."): a null pointer (a table with capacity 0 may be null), n
+ * outside 1..65536, misaligned records, or no symbol tables / fragments set; nothing is launched then. */
+#define MNX_MOL_FORMULA_EXPANDED 1024u
+#define MNX_MOL_FORMULA_LEFT 2048u
+#define MNX_MOL_FORMULA_LIMIT 65536u
+#define MNX_MOL_FORMULA_REFUSED 131072u
+#define MNX_FORMULA_DEFAULT_STEPS 4096u
+int mnx_formula_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
+                     const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_mol* mols_out,
+                     mnx_atom* atoms_out, uint32_t atom_cap, mnx_bond* bonds_out, uint32_t bond_cap, char* text_out,
+                     uint32_t text_cap, uint16_t* origin, uint32_t* totals, uint32_t max_steps, void* stream);
 
 /* One normal spelling per atom, on the device: packed tables in, packed tables of the SAME record types out, with aromatic rings
  * perceived from Kekule drawings, hydrogens counted and brackets dropped where a reader infers what they say. The canonical ranks key

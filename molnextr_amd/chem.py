@@ -24,8 +24,8 @@ depend on the numbering of a drawing's atoms, for deduplication and cache keys o
 project's own too — it is NOT the canonical SMILES that `Chem.MolToSmiles` below returns, the two never compare, no toolkit has
 parsed it, and for a few graphs (the header's known limit) the string still depends on the drawing. On request the device also
 replaces abbreviation labels by their atoms and bonds before it writes (mnx_expand_pack, vocab/fragments.json): the table branch
-of `_expand_functional_group` without a toolkit — from a table only (no condensed-formula parser, no zero-atom fragments), the
-atoms of a fragment on the label's coordinates, sanitised by nothing. Nothing in this module uses either.
+of `_expand_functional_group` without a toolkit — from a table only (a condensed formula is mnx_formula_pack's, on request too;
+no zero-atom fragments), the atoms of a fragment on the label's coordinates, sanitised by nothing. Nothing in this module uses either.
 """
 import json
 import logging

@@ -255,6 +255,11 @@ struct FragView {                       // passed to kernels by value
 // as packed tables of the same record types (mnx_expand_pack): count, scan and fill, three launches on s
 hipError_t expand_pack_enqueue(const SymbolTables* st_dev, const FragView& fv, const PackedTables& t, const TablesOut& o,
                                unsigned short* origin, unsigned* totals, hipStream_t s);
+// formula.hip: the molecules of t with every condensed-formula label that the search finds a structure for replaced by its atoms and
+// bonds, as packed tables of the same record types (mnx_formula_pack): count, scan and fill, three launches on s. max_steps: the
+// placements one label's search may try, 0 = MNX_FORMULA_DEFAULT_STEPS.
+hipError_t formula_pack_enqueue(const SymbolTables* st_dev, const FragView& fv, const PackedTables& t, const TablesOut& o,
+                                unsigned short* origin, unsigned* totals, unsigned max_steps, hipStream_t s);
 // normalize.hip: the molecules of t with one normal spelling per atom — aromatic rings perceived, hydrogens counted, brackets
 // dropped where a reader infers them — as packed tables of the same record types (mnx_normalize_pack): count, scan and fill,
 // three launches on s; atom_notes (may be null) receives one byte per output atom

@@ -29,7 +29,7 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
            "mnx_layernorm16", "mnx_merge_ln16", "mnx_cast16", "mnx_sgemm_tn", "mnx_set_vocab_text", "mnx_graph_pack",
            "mnx_set_symbol_tables", "mnx_molfile_pack", "mnx_smiles_pack", "mnx_smiles_pack_stereo",
            "mnx_smiles_pack_marks", "mnx_smiles_pack_canonical", "mnx_smiles_pack_symmetric", "mnx_set_fragments", "mnx_expand_pack", "mnx_smiles_read",
-           "mnx_beam_scripted", "mnx_edge_probs", "mnx_normalize_pack", "mnx_kekulize_pack")
+           "mnx_beam_scripted", "mnx_edge_probs", "mnx_normalize_pack", "mnx_kekulize_pack", "mnx_formula_pack")
 
 # Encoder operand modes (include/molnextr_hip.h MNX_DTYPE_*). "fp16x3" — split fp16 operands, three MFMA terms per
 # product, fp32-class results — is the default: it is the fastest mode whose results stay a factor of four inside north_star's
@@ -127,6 +127,11 @@ MOL_KEKULIZED, MOL_KEKULE_LEFT, MOL_KEKULIZE_REFUSED = 128, 256, 512
 NOTE_KEKULIZED, NOTE_KEKULE_LEFT, NOTE_KEKULE_LIMIT = 16, 32, 128
 KEKULE_DEFAULT_STEPS = 16384
 NOTE_H_MASK, NOTE_AROMATIZED, NOTE_UNBRACKETED, NOTE_COPIED = 15, 16, 32, 64
+# mnx_mol.flags of mnx_formula_pack's output: a condensed-formula label was replaced by the structure the search found; a candidate
+# label stayed; the search of a label passed the step limit; the molecule was refused (as MOL_EXPAND_REFUSED): no records.
+# FORMULA_DEFAULT_STEPS is what max_steps = 0 stands for
+MOL_FORMULA_EXPANDED, MOL_FORMULA_LEFT, MOL_FORMULA_LIMIT, MOL_FORMULA_REFUSED = 1 << 10, 1 << 11, 1 << 16, 1 << 17
+FORMULA_DEFAULT_STEPS = 4096
 MOLFILE_DTYPE = np.dtype([("text0", "<u4"), ("len", "<u4"), ("flags", "<u4"), ("reserved", "<u4")], align=True)
 # mnx_molfile.flags (MNX_MOLFILE_*): no molfile (len 0) for more than 999 atoms / bonds or records beyond the tables passed;
 # the molecule holds a pseudo-atom (R-group, abbreviation, unparsable symbol); a copy of MOL_TRUNCATED
@@ -309,6 +314,8 @@ def load_library():
     lib.mnx_normalize_pack.argtypes = lib.mnx_expand_pack.argtypes      # atom_notes in the place of origin
     lib.mnx_kekulize_pack.restype = C.c_int                             # normalize's arguments, max_steps in front of stream
     lib.mnx_kekulize_pack.argtypes = lib.mnx_expand_pack.argtypes[:-1] + [C.c_uint32, lib.mnx_expand_pack.argtypes[-1]]
+    lib.mnx_formula_pack.restype = C.c_int                              # expand's arguments, max_steps in front of stream
+    lib.mnx_formula_pack.argtypes = lib.mnx_kekulize_pack.argtypes
     lib.mnx_smiles_read.restype = C.c_int
     lib.mnx_smiles_read.argtypes = [vp, vp, C.c_uint32, vp, i32, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp]
     lib.mnx_atom_scan.restype = C.c_int
@@ -1098,6 +1105,27 @@ class Engine:
             caps = (len(rec["atoms"]) + 12 * n, len(rec["bonds"]) + 12 * n, len(rec["text"]) + 16 * n)
         out = self._sized_tables("mnx_expand_pack", n, caps,
                                  lambda mols, arenas, totals, origin: self.lib.mnx_expand_pack(self.h, *args, mols, *arenas, origin, totals, _stream()),
+                                 dev, keep_device, side=torch.int16)
+        out["origin"] = out.pop("side").cpu().numpy().view(np.uint16)
+        return out
+
+    def formula_pack(self, rec: dict, caps=None, keep_device: bool = False, max_steps: int = 0) -> dict:
+        """graph_pack's records (or smiles_read's) -> the same molecules with every condensed-formula label ('CH2CH3', 'N(CH3)2',
+        'COOCH3', 'CH2Ph': a symbol without a parse that is in neither name table, 2 to 20 bytes) that the valence search finds a
+        structure for replaced by its atoms and bonds (mnx_formula_pack; the rule: include/molnextr_hip.h — this library's own
+        repair of the reference's search, no toolkit has parsed the result). A group token inside a label ('Ph' in 'CH2Ph') is
+        written as '[Ph]': run expand_pack behind this call. A dict with expand_pack's keys — 'mols', 'atoms', 'bonds', 'text',
+        'totals', 'origin' —; mols['flags'] carries MOL_FORMULA_EXPANDED / MOL_FORMULA_LEFT / MOL_FORMULA_LIMIT /
+        MOL_FORMULA_REFUSED. max_steps: the placements one label's search may try (0: FORMULA_DEFAULT_STEPS). Sizes itself as
+        expand_pack does; keep_device: also 'device', as graph_pack."""
+        dev = torch.device("cuda", self.device)
+        n = len(rec["mols"])
+        tables, args = self._packed_tables(rec)
+        if caps is None:        # room for a label of about ten atoms per molecule before the repeat
+            caps = (len(rec["atoms"]) + 12 * n, len(rec["bonds"]) + 12 * n, len(rec["text"]) + 16 * n)
+        out = self._sized_tables("mnx_formula_pack", n, caps,
+                                 lambda mols, arenas, totals, origin: self.lib.mnx_formula_pack(self.h, *args, mols, *arenas, origin, totals,
+                                                                                               int(max_steps), _stream()),
                                  dev, keep_device, side=torch.int16)
         out["origin"] = out.pop("side").cpu().numpy().view(np.uint16)
         return out

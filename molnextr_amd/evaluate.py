@@ -210,7 +210,7 @@ def write_predictions(save_path: str, file_name: str, table: Dict[str, list], sc
 
 
 def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: int = 512, normalize: bool = False,
-                       kekulize: bool = False) -> Dict[str, float]:
+                       kekulize: bool = False, formula: bool = False) -> Dict[str, float]:
     """--graph_match: the share of items whose prediction and gold string are the same graph as THIS library's canonical SMILES
     sees it (marks 0: no stereo), on the device. records: the gathered dense records in dataset order (shard.pack_records
     layout), re-uploaded in chunks -> graph_pack -> mnx_smiles_pack_canonical; gold -> mnx_smiles_read -> the same writer. A
@@ -225,7 +225,12 @@ def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: 
     mnx_normalize_pack, and are ranked then, so that an aromatic prediction equals a gold string in aromatic,
     Kekule or half-aromatic form, and an aromatic azulene equals its Kekule string although normalize finds no ring of 7. The
     other scores stay as they are. Still NOT the reference's RDKit `graph` score: the matching is this library's own search
-    order and not RDKit's Kekulize, the aromaticity rule is not RDKit's model, stereo is dropped, and no toolkit has checked either."""
+    order and not RDKit's Kekulize, the aromaticity rule is not RDKit's model, stereo is dropped, and no toolkit has checked either.
+    formula (--graph_formula): adds graph_match_formula — BOTH sides pass through mnx_formula_pack and then mnx_expand_pack and
+    are ranked then, so that a predicted label 'CH2CH3' or 'COOCH3' equals a gold string that draws the group out,
+    and a gold [Et] equals a predicted 'C2H5'. The other scores stay as they are. NOT the reference's RDKit `graph` score: the
+    structure of a formula is this library's own repaired search, not the reference's RDKit bookkeeping, nothing normalises or
+    kekulises here, stereo is dropped, and no toolkit has parsed the result."""
     from .engine import READ_REFUSED, SMILES_REFUSED
     from .shard import MAX_LEN
     kmax = engine.max_atoms
@@ -237,7 +242,7 @@ def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: 
         recs, _, data, _, _ = engine.smiles_pack(rec, canonical=True)
         return [None if int(r["flags"]) & SMILES_REFUSED else data[int(r["text0"]):int(r["text0"]) + int(r["len"])] for r in recs]
 
-    equal = equal_normalized = equal_kekulized = unreadable = refused = 0
+    equal = equal_normalized = equal_kekulized = equal_formula = unreadable = refused = 0
     for c0 in range(0, len(gold), chunk):
         rows = torch.from_numpy(np.ascontiguousarray(records[c0:c0 + chunk])).to(dev)
         n = rows.shape[0]
@@ -263,11 +268,17 @@ def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: 
             pred, want = (texts(engine.normalize_pack(engine.kekulize_pack(side, keep_device=True), keep_device=True)) for side in (packed, read))
             for p, w, r in zip(pred, want, read["read"]):
                 equal_kekulized += not int(r["flags"]) & READ_REFUSED and p is not None and w is not None and p == w
+        if formula:
+            pred, want = (texts(engine.expand_pack(engine.formula_pack(side, keep_device=True), keep_device=True)) for side in (packed, read))
+            for p, w, r in zip(pred, want, read["read"]):
+                equal_formula += not int(r["flags"]) & READ_REFUSED and p is not None and w is not None and p == w
     scores = {"graph_match_device": equal / len(gold) if gold else 0.0, "gold_unreadable": int(unreadable), "pred_refused": int(refused)}
     if normalize:
         scores["graph_match_normalized"] = equal_normalized / len(gold) if gold else 0.0
     if kekulize:
         scores["graph_match_kekulized"] = equal_kekulized / len(gold) if gold else 0.0
+    if formula:
+        scores["graph_match_formula"] = equal_formula / len(gold) if gold else 0.0
     return scores
 
 
@@ -313,6 +324,12 @@ def build_parser() -> argparse.ArgumentParser:
                          "molecule compare equal, rings of 7 included (DESIGN 4.20). The other scores stay as they are. Still NOT the "
                          "reference's RDKit `graph` score: the choice among Kekule structures is this library's own search order, not "
                          "RDKit's Kekulize, the aromaticity rule is not RDKit's model, and no toolkit has checked either")
+    ap.add_argument("--graph_formula", action="store_true",
+                    help="opt-in, with --graph_match: add graph_match_formula, the same comparison with both sides passed through "
+                         "mnx_formula_pack and then mnx_expand_pack first, so that a condensed-formula label ('CH2CH3', 'COOCH3') "
+                         "equals the group drawn out (DESIGN 4.22). The other scores stay as they are. It is NOT the reference's "
+                         "`graph` score: the structure of a formula is this library's own repaired valence search, not the "
+                         "reference's RDKit bookkeeping, and no toolkit has parsed the result")
     return ap
 
 
@@ -330,6 +347,8 @@ def main(argv=None):
         ap.error("--graph_normalize adds a score to --graph_match")
     if args.graph_kekulize and not args.graph_match:
         ap.error("--graph_kekulize adds a score to --graph_match")
+    if args.graph_formula and not args.graph_match:
+        ap.error("--graph_formula adds a score to --graph_match")
     dtype = args.dtype or ("fp16" if args.fp16 else DEFAULT_DTYPE)
     max_batch = max(64, 2 * args.batch_size)          # one reference batch is encoded in one launch group
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -379,7 +398,7 @@ def main(argv=None):
             scores = smiles_scores(df["SMILES"], table["SMILES"]) if "SMILES" in df.columns else None
             if args.graph_match:
                 scores.update(graph_match_scores(engine, kept["records"], list(df["SMILES"]), normalize=args.graph_normalize,
-                                                 kekulize=args.graph_kekulize))
+                                                 kekulize=args.graph_kekulize, **({"formula": True} if args.graph_formula else {})))
         print(write_predictions(args.save_path, args.test_file, table, scores), json.dumps(scores))
     if world > 1:
         dist.barrier()

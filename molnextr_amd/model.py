@@ -11,13 +11,14 @@ atom positions on the host (tokenizer.py), as in the reference. No CPU fallback 
 from __future__ import annotations
 
 import argparse
+import re
 from typing import List, Optional
 
 import numpy as np
 import torch
 
 from . import weights as W
-from .engine import DEFAULT_DTYPE, MOL_TRUNCATED, NOTE_H_MASK, SMILES_NO_POSITION, SMILES_REFUSED, Engine, MnxError
+from .engine import DEFAULT_DTYPE, MOL_FORMULA_LEFT, MOL_TRUNCATED, NOTE_H_MASK, SMILES_NO_POSITION, SMILES_REFUSED, Engine, MnxError
 from .preprocess import load_image_rgb, transform_image, transform_image_gray
 from .tokenizer import coords_labels, get_tokenizer
 
@@ -144,7 +145,7 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
                      labels=None, free_run=False, packed: bool = False, molfile: bool = False,
                      molfile_scale=None, smiles: bool = False, stereo: bool = False, double_bonds: bool = False,
                      canonical: bool = False, expand: bool = False, symmetry: bool = False, normalize: bool = False,
-                     kekulize: bool = False) -> List[dict]:
+                     kekulize: bool = False, formula: bool = False) -> List[dict]:
     """Encoder + Decoder.decode for MANY images through the engine's continuous-batching path (mnx_predict):
     same per-image dicts as `decode_batch`, identical results (the on-device atom scan equals
     sequence_to_smiles' indices), much higher throughput. compute_confidence=True: mnx_predict_confidence, the same
@@ -187,7 +188,7 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
     'expanded' = {'symbols', 'coords', 'bonds' [(i, j, type, rev[, score])], 'origin' (per expanded atom, the index of the
     predicted atom it came from), 'flags' (MOL_EXPANDED / MOL_LABEL_LEFT of engine.py)}; 'graph_smiles_order', 'canonical_rank'
     and 'symmetry_class' then have one entry per EXPANDED atom, in the order of expanded['symbols']. The predicted atoms and
-    bonds ('chartok_coords', 'bonds') are what they are without it. From a table only (no condensed-formula parser), the atoms
+    bonds ('chartok_coords', 'bonds') are what they are without it. From a table only (a condensed formula is `formula`'s, below), the atoms
     of a fragment share the label's coordinates, and no toolkit has parsed the result.
     normalize (packed only; behind expand when both are set): the molecule is given one normal spelling per atom on the device
     before anything is written (mnx_normalize_pack; the rule: the header) — rings of 5 and 6 atoms that the rule finds aromatic get
@@ -203,8 +204,18 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
     gains 'kekulized' = {'symbols', 'bonds', 'hydrogens' (per aromatic atom), 'notes' (NOTE_KEKULIZED / NOTE_KEKULE_LEFT /
     NOTE_KEKULE_LIMIT / NOTE_COPIED of engine.py per atom), 'flags' (MOL_KEKULIZED / MOL_KEKULE_LEFT)}, the molecule as it left
     that pass. A Kekule structure is a perfect matching; the choice among several is this library's own search order, NOT RDKit's
-    Kekulize, and a system without a matching or on a class-4 bond to an upper-case atom stays aromatic."""
+    Kekulize, and a system without a matching or on a class-4 bond to an upper-case atom stays aromatic.
+    formula (packed only; in front of expand): condensed-formula labels that are in neither name table ('CH2CH3', 'N(CH3)2',
+    'COOCH3', 'CH2Ph') are replaced on the device by the atoms and bonds a valence-guided search finds for them
+    (mnx_formula_pack; the rule: the header — this library's own repair of the reference's search, no toolkit has parsed the
+    result), before expand replaces the table's labels and the group tokens a formula holds ('[Ph]'). Every dict gains 'formula'
+    = {'symbols', 'coords', 'bonds', 'origin', 'flags' (MOL_FORMULA_EXPANDED / MOL_FORMULA_LEFT / MOL_FORMULA_LIMIT of
+    engine.py), 'replaced' (the predicted atoms whose label was replaced), 'left' (the predicted atoms that were candidates and
+    stayed)}, the molecule as it left that pass; expanded['origin'] still names the PREDICTED atom. Without expand the per-atom
+    lists of the writers have one entry per atom of formula['symbols']."""
     tok = (tokenizer or get_tokenizer())["chartok_coords"]
+    if formula and not packed:
+        raise ValueError("formula=True needs packed=True: the labels are replaced in the packed tables")
     if normalize and not packed:
         raise ValueError("normalize=True needs packed=True: the atoms are respelled in the packed tables")
     if kekulize and not packed:
@@ -241,8 +252,10 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
         if (rec["mols"]["flags"] & MOL_TRUNCATED).any():
             raise RuntimeError(f"a molecule has more atoms than the engine capacity max_atoms={engine.max_atoms}")
         drawn = rec                                                      # what the predicted atoms and bonds are read from
+        if formula:
+            rec = formula_rec = engine.formula_pack(drawn, keep_device=molfile or smiles or normalize or kekulize or expand)
         if expand:
-            rec = engine.expand_pack(drawn, keep_device=molfile or smiles or normalize or kekulize)     # what the writers read
+            rec = engine.expand_pack(rec, keep_device=molfile or smiles or normalize or kekulize)     # what the writers read
         grown_rec = rec
         if kekulize:
             rec = kekule_rec = engine.kekulize_pack(rec, keep_device=molfile or smiles or normalize)
@@ -252,14 +265,31 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
                                     **({"symmetry": True} if symmetry else {})) if canonical else None
         per_atom = {"rank": ranked[3], "sym_class": ranked[4]} if canonical else {}
         preds = unpack_graphs(drawn["mols"], drawn["atoms"], drawn["bonds"], drawn["text"], tok.maxx, compute_confidence,
-                              **({} if expand else per_atom))
+                              **({} if expand or formula else per_atom))
+        if formula:
+            found = unpack_graphs(formula_rec["mols"], formula_rec["atoms"], formula_rec["bonds"], formula_rec["text"], tok.maxx,
+                                  compute_confidence, **({} if expand else per_atom))
+            for p, g, m in zip(preds, found, formula_rec["mols"]):
+                a0, na = int(m["atom0"]), int(m["n_atoms"])
+                before, after = p["chartok_coords"]["symbols"], g["chartok_coords"]["symbols"]
+                p["formula"] = {"symbols": after, "coords": g["chartok_coords"]["coords"], "bonds": g["bonds"],
+                                "origin": formula_rec["origin"][a0:a0 + na].tolist(), "flags": int(m["flags"]),
+                                "replaced": [a for a, s in enumerate(before) if after[a] != s],
+                                "left": [a for a, s in enumerate(before) if after[a] == s and int(m["flags"]) & MOL_FORMULA_LEFT
+                                         and formula_candidate(s)]}
+                for key in ("canonical_rank", "symmetry_class"):
+                    if key in g:
+                        p[key] = g[key]
         if expand:
             grown = unpack_graphs(grown_rec["mols"], grown_rec["atoms"], grown_rec["bonds"], grown_rec["text"], tok.maxx,
                                   compute_confidence, **per_atom)
             for p, g, m in zip(preds, grown, grown_rec["mols"]):
                 a0, na = int(m["atom0"]), int(m["n_atoms"])
+                origin = grown_rec["origin"][a0:a0 + na].tolist()
+                if formula:                                              # through the formula pass back to the predicted atom
+                    origin = [p["formula"]["origin"][k] for k in origin]
                 p["expanded"] = {"symbols": g["chartok_coords"]["symbols"], "coords": g["chartok_coords"]["coords"],
-                                 "bonds": g["bonds"], "origin": grown_rec["origin"][a0:a0 + na].tolist(), "flags": int(m["flags"])}
+                                 "bonds": g["bonds"], "origin": origin, "flags": int(m["flags"])}
                 for key in ("canonical_rank", "symmetry_class"):
                     if key in g:
                         p[key] = g[key]
@@ -313,7 +343,19 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
     return preds
 
 
-def canonical_smiles(engine: Engine, smiles_list, expand: bool = False, normalize: bool = False, kekulize: bool = False) -> List[dict]:
+_SMILES_ATOM = re.compile(r"Cl|Br|[BCNOPSFIbcnops*]|\[\d{0,3}(se|as|[bcnops]|\*|[A-Z][a-z]?)(@@?)?(H\d?)?(\++|-+|[+-]\d+)?(:\d+)?\]")
+
+
+def formula_candidate(symbol: str) -> bool:
+    """Whether mnx_formula_pack takes an atom's symbol for a condensed formula: in neither name table, 2 to 20 bytes without its
+    brackets, and no atom of the SMILES grammar (the host's reading of the header's candidate rule, for reporting only)."""
+    from .chem import classify_symbol
+    inner = symbol[1:-1] if len(symbol) >= 2 and symbol[0] == "[" and symbol[-1] == "]" else symbol
+    return classify_symbol(symbol) == "atom" and 2 <= len(inner.encode("utf-8")) <= 20 and _SMILES_ATOM.fullmatch(symbol) is None
+
+
+def canonical_smiles(engine: Engine, smiles_list, expand: bool = False, normalize: bool = False, kekulize: bool = False,
+                     formula: bool = False) -> List[dict]:
     """A caller's own SMILES in the form the device writes predictions in: mnx_smiles_read, optionally mnx_expand_pack ([Ph],
     [OMe], ... replaced by their atoms), then mnx_smiles_pack_canonical without marks. Per item {'smiles': the canonical string,
     None where the reader or the writer refused; 'read_flags' (engine.READ_*), 'err_pos' (of READ_SYNTAX), 'smiles_flags'
@@ -324,13 +366,19 @@ def canonical_smiles(engine: Engine, smiles_list, expand: bool = False, normaliz
     kekulize: mnx_kekulize_pack behind the expansion and in front of normalize — an aromatic string is written as a Kekule
     structure first (a perfect matching in this library's own search order, not RDKit's Kekulize), so that with normalize an
     aromatic string, a Kekule string and a half-aromatic one of the same molecule get one string where the rule finds the rings,
-    and without it azulene and its aromatic form do; the items gain 'kekulize_flags' (engine.MOL_KEKULIZED / ...)."""
+    and without it azulene and its aromatic form do; the items gain 'kekulize_flags' (engine.MOL_KEKULIZED / ...).
+    formula: mnx_formula_pack in front of the expansion — a condensed-formula atom such as [CH2CH3] or [N(CH3)2] is replaced by
+    the atoms a valence search finds for it (this library's own rule; combine with expand for the group tokens a formula
+    holds); the items gain 'formula_flags' (engine.MOL_FORMULA_EXPANDED / ...)."""
     from .engine import READ_REFUSED, SMILES_REFUSED
     smiles_list = list(smiles_list)
     if not smiles_list:
         return []
     rec = engine.smiles_read(smiles_list, keep_device=True)
     read = rec["read"]
+    if formula:
+        rec = engine.formula_pack(rec, keep_device=True)
+    formula_flags = rec["mols"]["flags"]
     if expand:
         rec = engine.expand_pack(rec, keep_device=True)
     if kekulize:
@@ -340,7 +388,7 @@ def canonical_smiles(engine: Engine, smiles_list, expand: bool = False, normaliz
         rec = engine.normalize_pack(rec, keep_device=True)
     recs, _, data, _, _ = engine.smiles_pack(rec, canonical=True)
     out = []
-    for r, w, m, kf in zip(read, recs, rec["mols"], kekulize_flags):
+    for r, w, m, kf, ff in zip(read, recs, rec["mols"], kekulize_flags, formula_flags):
         ok = not (int(r["flags"]) & READ_REFUSED or int(w["flags"]) & SMILES_REFUSED)
         out.append({"smiles": data[int(w["text0"]):int(w["text0"]) + int(w["len"])].decode("utf-8", "replace") if ok else None,
                     "read_flags": int(r["flags"]), "err_pos": int(r["err_pos"]), "smiles_flags": int(w["flags"])})
@@ -348,6 +396,8 @@ def canonical_smiles(engine: Engine, smiles_list, expand: bool = False, normaliz
             out[-1]["normalize_flags"] = int(m["flags"])
         if kekulize:
             out[-1]["kekulize_flags"] = int(kf)
+        if formula:
+            out[-1]["formula_flags"] = int(ff)
     return out
 
 
@@ -417,7 +467,13 @@ class molnextr:
     (mnx_kekulize_pack), so the molfile of an aromatic prediction carries bond types 1 and 2 in the place of the query type 4,
     and every output dict gains 'kekulized' (symbols, bonds, hydrogens, notes, flags). A Kekule structure is a perfect
     matching; the choice among several is this library's own search order, NOT RDKit's Kekulize, and a system without a
-    matching stays aromatic (flags & MOL_KEKULE_LEFT)."""
+    matching stays aromatic (flags & MOL_KEKULE_LEFT).
+    graph_formula: True (opt-in, default False; needs graph_smiles or graph_molfile; in front of graph_expand) = a condensed-formula
+    label that is in neither name table ('CH2CH3', 'N(CH3)2', 'COOCH3', 'CH2Ph') is replaced by the atoms and bonds a
+    valence-guided search finds for it before anything is written (mnx_formula_pack), and every output dict gains 'formula'
+    (symbols, coords, bonds, origin, flags, and 'replaced' / 'left': the predicted atoms whose label was replaced / stayed). This
+    library's own repair of the reference's search: no toolkit has parsed the result, rings, charges, explicit bonds and
+    two-ended labels stay labels; combine with graph_expand for the group tokens a formula holds ('Ph' in 'CH2Ph')."""
 
     image_format = "fp32"
     packed_results = False
@@ -430,12 +486,14 @@ class molnextr:
     graph_expand = False
     graph_normalize = False
     graph_kekulize = False
+    graph_formula = False
 
     def __init__(self, model_path, device=None, max_batch: int = 32, dtype: str = DEFAULT_DTYPE,
                  device_preprocess: bool = True, image_format: str = "fp32", packed_results: bool = False,
                  graph_molfile: bool = False, graph_smiles: bool = False, graph_stereo: bool = False,
                  graph_double_bonds: bool = False, graph_canonical: bool = False, graph_expand: bool = False,
-                 graph_symmetry: bool = False, graph_normalize: bool = False, graph_kekulize: bool = False):
+                 graph_symmetry: bool = False, graph_normalize: bool = False, graph_kekulize: bool = False,
+                 graph_formula: bool = False):
         if model_path is None:
             raise ValueError("molnextr(model_path): a checkpoint path is required (pass 'synthetic' explicitly for the "
                              "deterministic test checkpoint)")
@@ -481,16 +539,21 @@ class molnextr:
         self.graph_kekulize = bool(graph_kekulize)
         if self.graph_kekulize and not (self.graph_smiles or self.graph_molfile):
             raise ValueError("graph_kekulize=True needs graph_smiles=True or graph_molfile=True: the kekulised molecule is what they write")
+        self.graph_formula = bool(graph_formula)
+        if self.graph_formula and not (self.graph_smiles or self.graph_molfile):
+            raise ValueError("graph_formula=True needs graph_smiles=True or graph_molfile=True: the molecule with its formulas replaced is what they write")
         self.engine = Engine(states["encoder"], states["decoder"], device=device.index or 0, max_batch=max_batch,
                              dtype=dtype, image_format=image_format)
         self.input_size = args.input_size
         self.device_preprocess = device_preprocess
         self.group_images = 1024          # images per engine call of the throughput path (whole reference batches)
 
-    def canonical_smiles(self, smiles_list, expand: bool = False, normalize: bool = False, kekulize: bool = False) -> List[dict]:
+    def canonical_smiles(self, smiles_list, expand: bool = False, normalize: bool = False, kekulize: bool = False,
+                         formula: bool = False) -> List[dict]:
         """The canonical graph SMILES of the caller's own strings, for comparison with 'predicted_smiles' of graph_canonical=True
         (model.canonical_smiles: read on the device, optionally expanded and normalised, written without marks)."""
-        return canonical_smiles(self.engine, smiles_list, expand=expand, normalize=normalize, kekulize=kekulize)
+        return canonical_smiles(self.engine, smiles_list, expand=expand, normalize=normalize, kekulize=kekulize,
+                                **({"formula": True} if formula else {}))
 
     _groups_done = 0          # groups of the running predict_images call that have produced predictions
 
@@ -678,6 +741,8 @@ class molnextr:
             conf["normalize"] = True
         if self.graph_kekulize:
             conf["kekulize"] = True
+        if self.graph_formula:
+            conf["formula"] = True
         gen = self._prefetched(groups)
         try:
             for x in gen:
@@ -731,6 +796,8 @@ class molnextr:
                 d["hydrogens"], d["normalized"] = pred["normalized"]["hydrogens"], pred["normalized"]
             if "kekulized" in pred:                           # graph_kekulize: the molecule as it left mnx_kekulize_pack
                 d["kekulized"] = pred["kekulized"]
+            if "formula" in pred:                             # graph_formula: the molecule as it left mnx_formula_pack
+                d["formula"] = pred["formula"]
             if return_atoms_bonds:
                 c = pred["chartok_coords"]
                 atoms = []

@@ -32,6 +32,10 @@ is part of the product path and no number is asserted.
 (r) (only when asked for: --part r) SMILES read on the device: one mnx_smiles_read call over the strings of 1024 hand-made
     molecules of drug-like size against the one mnx_smiles_pack call that writes those strings, then the worst strings the
     reader admits, each alone in a call; `--read-out FILE` writes the table to a file of its own.
+(f) (only when asked for: --part f) condensed formulas on the device: mnx_formula_pack alone, against mnx_expand_pack on the same
+    tables (the same frame: count, scan, fill, one workgroup per molecule), on the drug-like tables of part x and on those with a
+    condensed formula in the place of every label; at the default step limit and at a limit of one step, where every search ends
+    at its first placement: what the two differ by is the serial search lane
 (n) (only when asked for: --part n) normalisation on the device: mnx_normalize_pack alone, against mnx_expand_pack on the same
     input tables (the same shape of pass), and followed by mnx_smiles_pack_canonical against the canonical writer on the tables
     as they came — on the synthetic checkpoint's predictions (near-complete graphs), on hand-made molecules of drug-like size
@@ -246,7 +250,8 @@ def druglike_records(n_mols, seed=0, centres=False, labels=False, gem=False, kek
     an aromatic six-ring, a few hetero atoms and double bonds (about 1.1 bonds per atom) — (mols, atoms, bonds, text).
     centres: every [C@@H] of the chain also carries a methyl on a wedge or a dash that begins at it, and its chain bonds are
     single: a candidate centre of mnx_smiles_pack_stereo (the molecules are the same otherwise). labels: every ninth atom that is a
-    plain 'C' becomes an abbreviation label of mnx_expand_pack, the six of LABELS in turn (the same molecules otherwise). gem
+    plain 'C' becomes an abbreviation label of mnx_expand_pack, the six of LABELS in turn, or of the tuple passed as `labels`
+    (the same molecules otherwise). gem
     (with centres): every third centre is a [C@@] with a second methyl — a gem-dimethyl carbon, which mnx_smiles_pack_symmetric
     drops — and every bond record carries its class in `rev` too, as mnx_graph_pack writes it (the older sets leave 0 there, so
     a bond whose ends the ranks swap is written '~' and no centre beside it is a candidate). kekule: the six-rings are drawn in
@@ -271,7 +276,7 @@ def druglike_records(n_mols, seed=0, centres=False, labels=False, gem=False, kek
         if labels:
             for k in range(8, n, 9):
                 if syms[k] == b"C":
-                    syms[k] = LABELS[k // 9 % len(LABELS)]
+                    syms[k] = (LABELS if labels is True else labels)[k // 9 % len(LABELS)]
         if kekule:
             for r in range(0, n - 5, 7):
                 for k in range(r, r + 6):
@@ -714,6 +719,74 @@ def part_n(repeats, lines):
     m.engine.close()
 
 
+# a label of druglike_records stands inside the chain, so each formula is spelled for two bonds; none is a table name
+FORMULAS = (b"[CHOCH3]", b"[CHPh]", b"[CHC(CH3)3]", b"[CHCOOC2H5]", b"[NCH3]", b"[CHNHCOOC(CH3)3]")
+
+
+def part_f(repeats, lines):
+    """Condensed formulas on the device: one mnx_formula_pack call (three launches) between two events, alternating with one
+    mnx_expand_pack call on the same input tables, at the default step limit and at a limit of one step. Every output buffer has
+    the exact size; the tables stay on the device."""
+    import ctypes as C
+    from molnextr_amd import engine as E
+    dev = torch.device("cuda", 0)
+    ck = W.synthetic_checkpoint(0)
+    eng = Engine(ck["encoder"], ck["decoder"], device=0, max_batch=2)
+    ptr = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
+    stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)      # noqa: E731
+    buf = lambda k: torch.empty(max(int(k), 1), dtype=torch.uint8, device=dev)      # noqa: E731
+
+    def measure(rec, what):
+        tables, args = eng._packed_tables(rec)
+        n = len(rec["mols"])
+        out = {"x": eng.expand_pack(rec), "f": eng.formula_pack(rec), "f1": eng.formula_pack(rec, max_steps=1)}
+        sizes = {k: (len(r["atoms"]), len(r["bonds"]), len(r["text"])) for k, r in out.items()}
+        mols_d, totals_d = buf(n * 40), torch.zeros(4, dtype=torch.int32, device=dev)
+        tab = {k: (buf(v[0] * 24), buf(v[1] * 16), buf(v[2])) for k, v in sizes.items()}
+        origin_d = torch.empty(max(max(v[0] for v in sizes.values()), 1), dtype=torch.int16, device=dev)
+
+        def table_pass(fn, k, *tail):
+            a, b, t = tab[k]
+            return fn(eng.h, *args, ptr(mols_d), ptr(a), sizes[k][0], ptr(b), sizes[k][1], ptr(t), sizes[k][2], ptr(origin_d), ptr(totals_d),
+                      *tail, stream())
+
+        calls = {"mnx_expand_pack": lambda: table_pass(eng.lib.mnx_expand_pack, "x"),
+                 "mnx_formula_pack, 1 step": lambda: table_pass(eng.lib.mnx_formula_pack, "f1", 1),
+                 "mnx_formula_pack": lambda: table_pass(eng.lib.mnx_formula_pack, "f", 0)}
+        us = {k: [] for k in calls}
+        for i in range(repeats + 3):
+            for k, call in calls.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                a.record()
+                rc = call()
+                b.record()
+                torch.cuda.synchronize()
+                assert rc == 0 and not int(totals_d[3]), k
+                if i >= 3:
+                    us[k].append(a.elapsed_time(b) * 1000.0)
+        assert tab["f"][0][:sizes["f"][0] * 24].cpu().numpy().tobytes() == out["f"]["atoms"].tobytes()
+        assert tab["f"][2][:sizes["f"][2]].cpu().numpy().tobytes() == out["f"]["text"]
+        flags = out["f"]["mols"]["flags"]
+        lines.append(f"(f) one call over {n} {what}: {len(rec['atoms'])} atoms, {len(rec['bonds'])} bonds -> {sizes['f'][0]} atoms, "
+                     f"{sizes['f'][1]} bonds; a formula replaced in {int((flags & E.MOL_FORMULA_EXPANDED != 0).sum())} molecules, left in "
+                     f"{int((flags & E.MOL_FORMULA_LEFT != 0).sum())}, step limit in {int((flags & E.MOL_FORMULA_LIMIT != 0).sum())}, refused "
+                     f"{int((flags & E.MOL_FORMULA_REFUSED != 0).sum())}; mnx_expand_pack on the same tables -> {sizes['x'][0]} atoms")
+        lines.append("  device us between two events around the launches, the three alternating   median [min .. max]")
+        for k in us:
+            lines.append(f"  {k:24s} {fmt(us[k])} us")
+        search = 1.0 - statistics.median(us["mnx_formula_pack, 1 step"]) / statistics.median(us["mnx_formula_pack"])
+        lines.append(f"  formula / expand, median {statistics.median(us['mnx_formula_pack']) / statistics.median(us['mnx_expand_pack']):.2f}; "
+                     f"the searches beyond their first step: {100.0 * search:.0f} % of the call")
+
+    for labels, what in ((False, "hand-made molecules of drug-like size (no label: both passes copy)"),
+                         (True, "hand-made molecules of drug-like size with a table label at every ninth atom (the formula pass copies)"),
+                         (FORMULAS, "hand-made molecules of drug-like size with a condensed formula at every ninth atom (expand copies)")):
+        mols, atoms, bonds, text = druglike_records(1024, labels=labels)
+        measure({"mols": mols, "atoms": atoms, "bonds": bonds, "text": text}, what)
+    eng.close()
+
+
 def part_r(repeats, lines):
     """SMILES read on the device: one mnx_smiles_read call (three launches) over the strings of 1024 hand-made molecules of
     drug-like size between two events, alternating with the one mnx_smiles_pack call that writes those strings from the packed
@@ -830,6 +903,7 @@ def main():
     ap.add_argument("--expand-out", default=None, help="write the table of part x to this file")
     ap.add_argument("--read-out", default=None, help="write the table of part r to this file")
     ap.add_argument("--normalize-out", default=None, help="write the table of part n to this file")
+    ap.add_argument("--formula-out", default=None, help="write the table of part f to this file")
     ap.add_argument("--pack-only", type=int, default=0, help="run this many mnx_graph_pack calls over 1024 images and exit")
     args = ap.parse_args()
     parts = args.part.split(",")
@@ -891,6 +965,13 @@ def main():
         if args.normalize_out:
             os.makedirs(os.path.dirname(os.path.abspath(args.normalize_out)), exist_ok=True)
             with open(args.normalize_out, "w") as f:
+                f.write("\n".join([lines[0]] + lines[first:]) + "\n")
+    if "f" in parts:
+        first = len(lines)
+        part_f(args.repeats, lines)
+        if args.formula_out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.formula_out)), exist_ok=True)
+            with open(args.formula_out, "w") as f:
                 f.write("\n".join([lines[0]] + lines[first:]) + "\n")
     text = "\n".join(lines)
     print(text)
