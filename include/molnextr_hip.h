@@ -1324,6 +1324,30 @@ int mnx_beam_scripted(mnx_engine* h, const float* table, int32_t B, int32_t beam
                       int32_t eos, int32_t* tokens, int32_t* lengths, float* scores, int32_t* steps_run, int32_t* tr_parent,
                       int32_t* tr_token, float* tr_score, int32_t* tr_alive, int32_t* tr_n_active, void* stream);
 
+/* Test aid: mnx_decode_beam with the CHOICE of every step read from a script, the real decoder running underneath — teacher
+ * forcing of beam search, so that a hypothesis' keys and values can be sent through any sequence of ancestor slots and the
+ * logits compared step by step (a free-running search cannot be: its ranked candidates come within fp32 noise of each other).
+ * features, B, beam, n_best, max_len, tokens, lengths, scores, hidden: as mnx_decode_beam (hidden may be null).
+ * script_parent, script_token: HOST int32 [max_len][B][beam], script_len elements each (>= max_len x B x beam): new hypothesis
+ * j of ORIGINAL image b at step t descends from hypothesis script_parent (0..beam-1) and emits id script_token
+ * (0..vocab-1). The script replaces the pick kernel's K arg-max rounds and nothing else: the score of a new hypothesis is the
+ * kernel's own expression for that candidate ((masked log-prob in the parent's row + the parent's cumulative) / (t + 2)), and
+ * ancestry, finishing on <eos> or max_len, the pool of finished hypotheses, an image leaving and the gathers of ids and hidden
+ * rows run as in mnx_decode_beam. Entries of an image that has left are validated and not read.
+ * A script may not do what a top-K cannot: emit <eos> (2) at step 0, where the head bans it; descend from a hypothesis that
+ * has finished; make the same (parent, token) choice twice for one image at one step. The library does not check these
+ * three (the result is then not a beam search's); Engine.decode_beam_forced does. As in mnx_decode_beam only hypothesis 0
+ * of an image starts with a cumulative log-prob of 0, the others with -inf: descendants of those score -inf.
+ * logits_trace (may be null): device fp32 [max_len][B x beam][V], the raw logits of slot b * beam + j at step t, written for
+ * the slots alive at that step; every other row is left as the caller filled it.
+ * Every element of the script and every size is checked before anything is launched, and the checked copy is what the
+ * device reads: MNX_ERR_INVALID_ARG (with mnx_last_error, "mnx_decode_beam_forced: ...") for a null pointer (but hidden,
+ * logits_trace), B outside 1..32, beam outside 1..8, n_best outside 1..beam, max_len outside 1..cfg.max_len, B x beam >
+ * dec_slots, script_len too small, a parent or an id out of range. Synchronises `stream` before it returns. */
+int mnx_decode_beam_forced(mnx_engine* h, const float* features, int32_t B, int32_t beam, int32_t n_best, int32_t max_len,
+                           const int32_t* script_parent, const int32_t* script_token, int64_t script_len, int32_t* tokens,
+                           int32_t* lengths, float* scores, float* hidden, float* logits_trace, void* stream);
+
 /* Test aid: mnx_edges with one more output. After the same four launches it copies, device to device on `stream`, what
  * the bond head's pair kernel left behind: probs device fp32 [B,kmax,kmax,8], laid out by the call's kmax; slots 0..6 of
  * pair (i, j) are the softmax over the 7 bond classes (before get_edge_prediction) for i, j < n_atoms[b] (clamped as

@@ -123,6 +123,11 @@ struct BeamBuffers {
     int* tr_token;
     float* tr_score;
     int* tr_alive;
+    // the choice of every step read from a script instead of the K arg-max rounds (mnx_decode_beam_forced; production leaves both
+    // null): device [steps][B][K], new hypothesis j of image b at step t descends from hypothesis sc_parent (0..K-1, validated
+    // on the host) and emits id sc_token (0..V-1)
+    const int* sc_parent;
+    const int* sc_token;
 };
 
 // token classes for the on-device atom-position scan (CharTokenizer.sequence_to_smiles 'indices')
@@ -154,6 +159,8 @@ hipError_t dec_enqueue_admit(const DecBuffers& b, const int* slots_dev, const in
                              int mem_blk0, int max_len, int stop_on_eos, hipStream_t s, const GuideRows* g = nullptr);
 hipError_t dec_enqueue_reset(const DecBuffers& b, hipStream_t s);
 hipError_t dec_enqueue_status(const DecBuffers& b, int slots, hipStream_t s);
+// logits_trace: [T][trace_rows][V] or null — the head writes the raw logits of slot s < trace_rows at step t to row (t, s)
+// (greedy: mnx_decode_greedy / _forced / _guided; beam search: mnx_decode_beam_forced alone, production passes null)
 // forced: [trace_rows, T] ids or null — teacher forcing of slots 0..trace_rows-1 (test aid, see HeadArgs)
 // glab: the label table (GuideRows::table, glab_stride ids per slot) or null — non-null runs the GUIDED greedy heads
 // fused_tile: 0 = the 8-launches-per-layer tick of decoder.hip (always used by beam search); 100 R + RC = the three-launches-

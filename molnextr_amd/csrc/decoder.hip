@@ -660,6 +660,7 @@ hipError_t dec_enqueue_admit(const DecBuffers& b, const int* slots_dev, const in
 }
 
 __global__ void beam_begin_kernel(DecState* st, int B, int K, int ref_batch);
+template <bool SCRIPT>
 __global__ void beam_pick_kernel(DecState* st, BeamBuffers bm, const float* hidden, int* etok, int T, int V, int eos);
 
 // One tick: the begin kernel (beam search: its own, over the hypotheses), then the layers + head for rows [0, rows) of the
@@ -745,7 +746,10 @@ hipError_t dec_enqueue_tick(const DecWeights& w, const DecBuffers& b, int slots_
     } else if (beam) {
         h.blp = beam->blp;
         hipLaunchKernelGGL(dec_head_kernel<true>, dim3(slots), dim3(256), 0, s, h);
-        hipLaunchKernelGGL(beam_pick_kernel, dim3(beam->B), dim3(256), 0, s, b.st, *beam, b.hidden, b.tokens, T, w.vocab, 2);
+        if (beam->sc_parent)
+            hipLaunchKernelGGL(beam_pick_kernel<true>, dim3(beam->B), dim3(256), 0, s, b.st, *beam, b.hidden, b.tokens, T, w.vocab, 2);
+        else
+            hipLaunchKernelGGL(beam_pick_kernel<false>, dim3(beam->B), dim3(256), 0, s, b.st, *beam, b.hidden, b.tokens, T, w.vocab, 2);
     } else if (fused) {
         hipLaunchKernelGGL(dec_head4_kernel, dim3(slots), dim3(1024), 0, s, h);
     } else {
@@ -1152,6 +1156,9 @@ __global__ void beam_begin_kernel(DecState* st, int B, int K, int ref_batch) {
     }
 }
 
+// SCRIPT (mnx_decode_beam_forced, test aid): the K new hypotheses are the script's (bm.sc_parent, bm.sc_token) instead of the
+// K best; their scores are the same expression, and everything after the choice is the one code.
+template <bool SCRIPT>
 __global__ __launch_bounds__(256) void beam_pick_kernel(DecState* st, BeamBuffers bm, const float* hidden, int* etok,
                                                         int T, int V, int eos) {
     __shared__ int lanc[MAX_BEAM][BEAM_ANC_MAX];
@@ -1181,7 +1188,16 @@ __global__ __launch_bounds__(256) void beam_pick_kernel(DecState* st, BeamBuffer
             idx[i] = flat;
         }
     }
-    for (int r = 0; r < K; ++r) {                  // top-K by K arg-max rounds (:69-82), ties -> lowest flat index
+    if (SCRIPT) {
+        if (tid < K) {
+            const size_t o = ((size_t)t * bm.B + img) * K + tid;
+            const int j = bm.sc_parent[o], v = bm.sc_token[o];
+            sel_score[tid] = (bm.blp[(size_t)(s0 + j) * BEAM_LP_STRIDE + v] + bm.bs->cum[s0 + j]) / len_f;
+            sel_idx[tid] = j * V + v;
+        }
+        __syncthreads();
+    }
+    for (int r = 0; r < (SCRIPT ? 0 : K); ++r) {   // top-K by K arg-max rounds (:69-82), ties -> lowest flat index
         float bv = NEG_INF;
         int bi = 0x7fffffff;
 #pragma unroll
@@ -1319,7 +1335,7 @@ hipError_t beam_enqueue_script_step(const DecBuffers& b, const BeamBuffers& bm, 
     hipError_t e = hipMemcpyAsync(n_active_out, &b.st->n_active, sizeof(int), hipMemcpyDeviceToDevice, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(beam_script_rows_kernel, dim3(bm.B * bm.K), dim3(256), 0, s, b.st, bm, table, V, eos);
-    hipLaunchKernelGGL(beam_pick_kernel, dim3(bm.B), dim3(256), 0, s, b.st, bm, b.hidden, b.tokens, b.T, V, eos);
+    hipLaunchKernelGGL(beam_pick_kernel<false>, dim3(bm.B), dim3(256), 0, s, b.st, bm, b.hidden, b.tokens, b.T, V, eos);
     return hipGetLastError();
 }
 

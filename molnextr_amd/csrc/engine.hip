@@ -89,6 +89,7 @@ struct mnx_engine {
     float* out_trace = nullptr;
     int* forced_ids = nullptr;  // [32, max_len] teacher-forcing ids of mnx_decode_forced (lazy; test aid)
     int* script_nact = nullptr; // [max_len] n_active of every step of mnx_beam_scripted (lazy; test aid)
+    int* beam_script = nullptr; // [2][max_len][32 x 8] parents, then ids, of mnx_decode_beam_forced (lazy; test aid)
     int* guide_labels = nullptr;   // [dec_slots, max_len + 2] label row of every slot, {ids held, the ids}: label-guided decoding
                                    // (mnx_decode_guided / mnx_predict_guided; lazy, written at admission — dec_types.h GuideRows)
     BeamBuffers beam{};        // allocated lazily on the first mnx_decode_beam
@@ -1092,20 +1093,24 @@ int beam_buffers(mnx_engine* h, int B, int ref_batch, int beam, int n_best, bool
 // (features at feats[g]), every image K hypotheses, one row per hypothesis — G x ref_batch x K rows per step. Images are
 // independent; the positional-encoding rows are numbered inside each reference batch (beam_begin_kernel), so the result is
 // that of G separate searches. Outputs [n_total, n_best, ...].
+// script (mnx_decode_beam_forced; null otherwise): device [2][max_len][B][beam], the parents, then the ids, that replace every
+// step's choice; logits_trace (may be null): device [max_len][B x beam][V], row (t, slot) written by the head
 int decode_beam_groups(mnx_engine* h, const float* const* feats, int G, int ref_batch, int n_total, int beam, int n_best,
-                       int max_len, int32_t* tokens, int32_t* lengths, float* scores, float* hidden, hipStream_t s) {
+                       int max_len, int32_t* tokens, int32_t* lengths, float* scores, float* hidden, hipStream_t s,
+                       const int* script = nullptr, float* logits_trace = nullptr) {
     const int B = n_total;
     // capacities: MAX_BEAM_IMGS images x MAX_BEAM hypotheses of state; 256 kept hypotheses (32 images x 8 ... 256 x 1)
     MNXCHK(beam_buffers(h, B, ref_batch, beam, n_best, hidden != nullptr));
     BeamBuffers run = h->beam;
     if (!hidden) run.phid = nullptr;
+    if (script) { run.sc_parent = script; run.sc_token = script + (size_t)max_len * B * beam; }
     for (int g = 0; g < G; ++g)      // memory of batch g -> memory blocks g ref_batch ...
         MNXCHK(project_memory(h, feats[g], std::min(ref_batch, B - g * ref_batch), g * ref_batch, s));
     HIPCHK(h, dec_enqueue_reset(h->db, s));
     HIPCHK(h, beam_enqueue_init(h->db, run, max_len, s));
     const int rows = (B * beam + ROW_TILE - 1) / ROW_TILE * ROW_TILE;
     // one step = begin + 6 layers + head + pick, captured once per call (its arguments depend on B / beam / n_best)
-    auto step = [&]() { return dec_enqueue_tick(h->dw, h->db, rows, rows, nullptr, 0, s, &run); };
+    auto step = [&]() { return dec_enqueue_tick(h->dw, h->db, rows, rows, logits_trace, logits_trace ? B * beam : 0, s, &run); };
     hipGraphExec_t exec = nullptr;
     if (h->use_graph) MNXCHK(capture_graph(h, "beam step", s, step, &exec));
     struct ExecGuard {      // the per-call graph is released on every exit path
@@ -2144,6 +2149,43 @@ int mnx_beam_scripted(mnx_engine* h, const float* table, int32_t B, int32_t beam
     HIPCHK(h, hipStreamSynchronize(s));
     *steps_run = n_run;
     return MNX_OK;
+}
+
+int mnx_decode_beam_forced(mnx_engine* h, const float* features, int32_t B, int32_t beam, int32_t n_best, int32_t max_len,
+                           const int32_t* script_parent, const int32_t* script_token, int64_t script_len, int32_t* tokens,
+                           int32_t* lengths, float* scores, float* hidden, float* logits_trace, void* stream) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    auto bad = [&](const std::string& m) { h->err = "mnx_decode_beam_forced: " + m; return MNX_ERR_INVALID_ARG; };
+    const mnx_config& c = h->cfg;
+    if (!features || !script_parent || !script_token || !tokens || !lengths || !scores)
+        return bad("null features, script_parent, script_token, tokens, lengths or scores");
+    if (B < 1 || B > ROW_TILE) return bad("B must be 1..32");
+    if (beam < 1 || beam > MAX_BEAM) return bad("beam must be 1..8");
+    if (n_best < 1 || n_best > beam) return bad("n_best must be 1..beam");
+    if (max_len < 1 || max_len > c.max_len || c.max_len + 1 > BEAM_ANC_MAX) return bad("max_len must be 1..cfg.max_len (<= 511)");
+    if (c.vocab > BEAM_LP_STRIDE) return bad("the vocabulary exceeds 256 ids");
+    if (B * beam > h->db.slots) return bad("B x beam exceeds dec_slots");
+    const size_t n = (size_t)max_len * B * beam;
+    if (script_len < 0 || (uint64_t)script_len < n) return bad("script_len is less than max_len x B x beam");
+    // the script as the device will read it: every element checked on its way into the copy that is uploaded
+    std::vector<int> script(2 * n);
+    auto at = [&](size_t i, int x) {
+        return "[" + std::to_string(i / ((size_t)B * beam)) + "][" + std::to_string(i / beam % B) + "][" + std::to_string(i % beam) +
+               "] = " + std::to_string(x);
+    };
+    for (size_t i = 0; i < n; ++i) {
+        const int p = script_parent[i], v = script_token[i];
+        if (p < 0 || p >= beam) return bad("script_parent" + at(i, p) + " is outside 0..beam-1");
+        if (v < 0 || v >= c.vocab) return bad("script_token" + at(i, v) + " is outside 0..vocab-1");
+        script[i] = p; script[n + i] = v;
+    }
+    hipStream_t s;
+    MNXCHK(caller_stream(h, stream, &s));
+    MNXCHK(lazy_alloc(h, &h->beam_script, (size_t)2 * c.max_len * ROW_TILE * MAX_BEAM * 4));
+    HIPCHK(h, hipMemcpyAsync(h->beam_script, script.data(), 2 * n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipStreamSynchronize(s));      // `script` is pageable host memory of this call
+    return decode_beam_groups(h, &features, 1, B, B, beam, n_best, max_len, tokens, lengths, scores, hidden, s, h->beam_script,
+                              logits_trace);
 }
 
 // ---- test aids: the encoder's non-GEMM kernels and the fp32 SGEMM on caller buffers (tests/test_gpu_encoder_ops.py) ----

@@ -29,7 +29,8 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
            "mnx_layernorm16", "mnx_merge_ln16", "mnx_cast16", "mnx_sgemm_tn", "mnx_set_vocab_text", "mnx_graph_pack",
            "mnx_set_symbol_tables", "mnx_molfile_pack", "mnx_smiles_pack", "mnx_smiles_pack_stereo",
            "mnx_smiles_pack_marks", "mnx_smiles_pack_canonical", "mnx_smiles_pack_symmetric", "mnx_set_fragments", "mnx_expand_pack", "mnx_smiles_read",
-           "mnx_beam_scripted", "mnx_edge_probs", "mnx_normalize_pack", "mnx_kekulize_pack", "mnx_formula_pack")
+           "mnx_beam_scripted", "mnx_edge_probs", "mnx_normalize_pack", "mnx_kekulize_pack", "mnx_formula_pack",
+           "mnx_decode_beam_forced")
 
 # Encoder operand modes (include/molnextr_hip.h MNX_DTYPE_*). "fp16x3" — split fp16 operands, three MFMA terms per
 # product, fp32-class results — is the default: it is the fastest mode whose results stay a factor of four inside north_star's
@@ -264,6 +265,8 @@ def load_library():
     lib.mnx_beam_scripted.restype = C.c_int
     lib.mnx_beam_scripted.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, C.POINTER(C.c_int32), vp, vp, vp, vp,
                                       vp, vp]
+    lib.mnx_decode_beam_forced.restype = C.c_int
+    lib.mnx_decode_beam_forced.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
     lib.mnx_patch_embed.restype = C.c_int
     lib.mnx_patch_embed.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     lib.mnx_layernorm16.restype = C.c_int
@@ -364,6 +367,40 @@ def check_labels(labels, n: int, free_run=False) -> torch.Tensor:
     if bad:
         raise ValueError(f"label rows {bad[:8]} hold no '<eos>' (free_run exempts rows that are meant to run on freely)")
     return lab
+
+
+def check_beam_script(parent, token, n_best: int, vocab: int, eos: int = 2):
+    """The script of Engine.decode_beam_forced as two contiguous host int32 [max_len, B, beam] tensors. ValueError for a
+    shape or an element out of range and for what no top-K could have chosen (include/molnextr_hip.h): '<eos>' at step 0, a
+    hypothesis that has finished as a parent, the same (parent, token) twice for one image at one step. Images are followed
+    as the search will run them (an image leaves once its top hypothesis has finished at some step and n_best are stored);
+    entries of an image that has left are only range-checked."""
+    par = torch.as_tensor(parent).cpu()
+    tok = torch.as_tensor(token).cpu()
+    if par.dim() != 3 or par.shape != tok.shape or par.is_floating_point() or tok.is_floating_point():
+        raise ValueError(f"script parent / token must be int [max_len, B, beam], got {tuple(par.shape)} and {tuple(tok.shape)}")
+    max_len, B, K = par.shape
+    if not 1 <= n_best <= K:
+        raise ValueError(f"n_best must be 1..beam = {K}, got {n_best}")
+    for name, a, hi in (("parent", par, K), ("token", tok, vocab)):
+        bad = ((a < 0) | (a >= hi)).nonzero()
+        if len(bad):
+            raise ValueError(f"script {name}{bad[0].tolist()} = {int(a[tuple(bad[0])])} is outside 0..{hi - 1}")
+    p, v = par.tolist(), tok.tolist()
+    for b in range(B):
+        finished, top, stored = [False] * K, False, 0
+        for t in range(max_len):
+            if t == 0 and eos in v[t][b]:
+                raise ValueError(f"script: image {b} emits '<eos>' at step 0, where the head bans it")
+            if any(finished[j] for j in p[t][b]):
+                raise ValueError(f"script: step {t} image {b} descends from a finished hypothesis")
+            if len(set(zip(p[t][b], v[t][b]))) < K:
+                raise ValueError(f"script: step {t} image {b} makes the same (parent, token) choice twice")
+            finished = [x == eos or t + 1 == max_len for x in v[t][b]]
+            top, stored = top or finished[0], stored + sum(finished)
+            if top and stored >= n_best:
+                break
+    return par.to(torch.int32).contiguous(), tok.to(torch.int32).contiguous()
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -786,6 +823,29 @@ class Engine:
                                       _ptr(scores), _ptr(hidden), _stream())
         self._check(rc, "mnx_decode_beam")
         return {"tokens": tokens, "lengths": lengths, "scores": scores, "hidden": hidden}
+
+    def decode_beam_forced(self, features: torch.Tensor, parent, token, n_best: int = 1, want_hidden: bool = True,
+                           trace_logits: bool = True, fill: float = float("nan")) -> dict:
+        """Beam search whose choices are read from a script while the real decoder runs (test aid, mnx_decode_beam_forced):
+        parent / token int [max_len, B, beam] — new hypothesis j of original image b at step t descends from hypothesis parent
+        and emits id token (check_beam_script: what a script may not do raises ValueError). Returns decode_beam's dict and,
+        with trace_logits, 'logits' [max_len, B*beam, V]: the raw logits of slot b * beam + j at step t, `fill` where the
+        slot was not alive."""
+        assert features.is_cuda and features.dtype == torch.float32 and features.is_contiguous()
+        par, tok = check_beam_script(parent, token, n_best, self.dec.vocab)
+        max_len, B, beam = par.shape
+        if features.shape[0] != B:
+            raise ValueError(f"the script is for {B} images, features for {features.shape[0]}")
+        dev = features.device
+        tokens = torch.zeros(B, n_best, max_len, dtype=torch.int32, device=dev)
+        lengths = torch.zeros(B, n_best, dtype=torch.int32, device=dev)
+        scores = torch.zeros(B, n_best, dtype=torch.float32, device=dev)
+        hidden = torch.zeros(B, n_best, max_len, self.dec.d_model, dtype=torch.float32, device=dev) if want_hidden else None
+        trace = torch.full((max_len, B * beam, self.dec.vocab), fill, dtype=torch.float32, device=dev) if trace_logits else None
+        rc = self.lib.mnx_decode_beam_forced(self.h, _ptr(features), B, beam, n_best, max_len, _ptr(par), _ptr(tok), par.numel(),
+                                             _ptr(tokens), _ptr(lengths), _ptr(scores), _ptr(hidden), _ptr(trace), _stream())
+        self._check(rc, "mnx_decode_beam_forced")
+        return {"tokens": tokens, "lengths": lengths, "scores": scores, "hidden": hidden, "logits": trace}
 
     def beam_scripted(self, table: torch.Tensor, n_best: int = 1, eos: int = 2, trace: bool = True,
                       fill: int = -7) -> dict:
