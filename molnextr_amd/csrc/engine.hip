@@ -1527,20 +1527,26 @@ int mnx_molfile_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_at
     return MNX_OK;
 }
 
+// mnx_expand_pack and mnx_formula_pack (formula, with its max_steps): one check, one way to the pass's three launches
+static int grow_pack(mnx_engine* h, const char* fn, const PackedTables& t, const TablesOut& o, uint16_t* origin, uint32_t* totals,
+                     void* stream, bool formula = false, uint32_t max_steps = 0) {
+    if (int rc = check_packed_tables(h, fn, t, tables_out_null(o, totals), tables_out_skew(o, totals) || ((uintptr_t)origin & 1) != 0,
+                                     "the output tables too, totals 4-byte, origin 2-byte"))
+        return rc;
+    if (!h->have_frag) { h->err = std::string(fn) + ": call mnx_set_fragments first"; return MNX_ERR_INVALID_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (formula) HIPCHK(h, formula_pack_enqueue(h->st_dev, h->fv, t, o, origin, totals, max_steps, (hipStream_t)stream));
+    else HIPCHK(h, expand_pack_enqueue(h->st_dev, h->fv, t, o, origin, totals, (hipStream_t)stream));
+    return MNX_OK;
+}
+
 int mnx_expand_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
                     const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_mol* mols_out,
                     mnx_atom* atoms_out, uint32_t atom_cap, mnx_bond* bonds_out, uint32_t bond_cap, char* text_out, uint32_t text_cap,
                     uint16_t* origin, uint32_t* totals, void* stream) {
     const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
     const TablesOut o = tables_out(mols_out, atoms_out, atom_cap, bonds_out, bond_cap, text_out, text_cap);
-    if (int rc = check_packed_tables(h, "mnx_expand_pack", t, tables_out_null(o, totals),
-                                     tables_out_skew(o, totals) || ((uintptr_t)origin & 1) != 0,
-                                     "the output tables too, totals 4-byte, origin 2-byte"))
-        return rc;
-    if (!h->have_frag) { h->err = "mnx_expand_pack: call mnx_set_fragments first"; return MNX_ERR_INVALID_ARG; }
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, expand_pack_enqueue(h->st_dev, h->fv, t, o, origin, totals, (hipStream_t)stream));
-    return MNX_OK;
+    return grow_pack(h, "mnx_expand_pack", t, o, origin, totals, stream);
 }
 
 int mnx_formula_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
@@ -1549,14 +1555,7 @@ int mnx_formula_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_at
                      uint16_t* origin, uint32_t* totals, uint32_t max_steps, void* stream) {
     const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
     const TablesOut o = tables_out(mols_out, atoms_out, atom_cap, bonds_out, bond_cap, text_out, text_cap);
-    if (int rc = check_packed_tables(h, "mnx_formula_pack", t, tables_out_null(o, totals),
-                                     tables_out_skew(o, totals) || ((uintptr_t)origin & 1) != 0,
-                                     "the output tables too, totals 4-byte, origin 2-byte"))
-        return rc;
-    if (!h->have_frag) { h->err = "mnx_formula_pack: call mnx_set_fragments first"; return MNX_ERR_INVALID_ARG; }
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, formula_pack_enqueue(h->st_dev, h->fv, t, o, origin, totals, max_steps, (hipStream_t)stream));
-    return MNX_OK;
+    return grow_pack(h, "mnx_formula_pack", t, o, origin, totals, stream, true, max_steps);
 }
 
 // mnx_normalize_pack and mnx_kekulize_pack (kekulize, with its max_steps): one check, one way to the pass's three launches

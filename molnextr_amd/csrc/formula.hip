@@ -9,8 +9,8 @@
 //          and the searches a third time for the records of the labels
 // One lane per candidate label runs the tokenizer and the search, FM_LANES labels at a time, each lane with its own slots of three
 // LDS arrays (items, states, atoms), lane-minor, so that no lane indexes an array of its own by a variable. Every position follows
-// from the prefix scan and, for a label's own row, from a binary search in the molecule's bond records, which are sorted by i: no
-// atomics, the output is the same word for word on every run. expand.hip's frame, with nothing shared but tables_out.h.
+// from the prefix scan and, for a label's own row, from a binary search in the molecule's bond records, which are sorted by i: that
+// frame is grow_pass.h, shared with expand.hip; here is what a label is and the atoms, symbols and bonds of the structure found.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -19,15 +19,11 @@
 #include "atom_symbol.h"
 #include "dec_types.h"
 #include "formula_search.h"
-#include "tables_out.h"
+#include "grow_pass.h"
 
 namespace mnx {
 namespace {
 
-constexpr int FM_THREADS = 256;
-constexpr int FM_MAX = 2048;             // atoms of a molecule held in LDS: 2047 atoms x 32 atoms of a label fit a uint16 index
-constexpr int FM_PER = FM_MAX / FM_THREADS;
-constexpr unsigned FM_ATOM_LIMIT = 2047;
 constexpr int FM_LANES = 32;             // labels searched side by side: 16 KB of search state
 
 static_assert(MNX_FORMULA_DEFAULT_STEPS == formula::DEFAULT_STEPS, "one default");
@@ -57,50 +53,37 @@ __device__ __forceinline__ void spell_found(const SymbolTables* __restrict__ st,
 }
 
 template <bool FILL>
-__global__ __launch_bounds__(FM_THREADS) void formula_kernel(
+__global__ __launch_bounds__(GR_THREADS) void formula_kernel(
         const PackedTables t, const SymbolTables* __restrict__ st, const FragView fv, const TablesOut o,
         unsigned short* __restrict__ origin, const unsigned max_steps) {
-    // fill: per atom, what lies in front of it — appended atoms, bonds from first atoms, bonds among appended atoms, bytes of the
-    // molecule's own atoms' symbols, bytes of the appended atoms' symbols (first the sizes, then their scan)
-    __shared__ unsigned short off_atoms[FILL ? FM_MAX : 1], off_b0[FILL ? FM_MAX : 1], off_bin[FILL ? FM_MAX : 1];
-    __shared__ unsigned off_text[FILL ? FM_MAX : 1], off_more[FILL ? FM_MAX : 1];
-    __shared__ unsigned char replaced[FILL ? FM_MAX : 1];
-    __shared__ unsigned short cand[FM_MAX];                       // the candidate labels in ascending order
+    // fill: the five arrays of grow_pass.h, first the sizes, then their scan; a structure is a tree, 2047 x 31 bonds fit 16 bits
+    __shared__ unsigned short off_atoms[FILL ? GR_MAX : 1], off_b0[FILL ? GR_MAX : 1], off_bin[FILL ? GR_MAX : 1];
+    __shared__ unsigned off_text[FILL ? GR_MAX : 1], off_more[FILL ? GR_MAX : 1];
+    __shared__ unsigned char replaced[FILL ? GR_MAX : 1];
+    __shared__ unsigned short cand[GR_MAX];                       // the candidate labels in ascending order
     __shared__ unsigned short s_item[formula::MAX_ITEMS * FM_LANES], s_snap[formula::MAX_ITEMS * FM_LANES];
     __shared__ unsigned s_atom[formula::MAX_ATOMS * FM_LANES];
-    __shared__ unsigned scan[2 * FM_THREADS];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const Molecule mol = admit_molecule(t, b);
-    const mnx_mol& m = mol.m;
-    auto record = [&](unsigned n_atoms, unsigned n_bonds, unsigned text_len, unsigned flags) {      // count's result
-        if (tid == 0) store_mol_counts(&o.mols[b], n_atoms, n_bonds, text_len, flags | (m.flags & MNX_MOL_TRUNCATED), m.overall_score);
-    };
-    mnx_mol mo;
-    if (FILL) {
-        mo = o.mols[b];
-        if (mo.flags & MNX_MOL_FORMULA_REFUSED) return;     // refused by count (the same for every thread)
-    } else if ((mol.flags & PT_BEYOND_TABLES) || m.n_atoms > FM_ATOM_LIMIT) {
-        record(0, 0, 0, MNX_MOL_FORMULA_REFUSED);
-        return;
-    }
-    const int na = (int)m.n_atoms;
-    const unsigned nb = m.n_bonds;
-    const unsigned long long* A = (const unsigned long long*)mol.A;
-    const unsigned long long* B = (const unsigned long long*)mol.B;
-    const unsigned char* text_in = t.text + m.text0;
+    __shared__ unsigned scan[2 * GR_THREADS];
+    GrowPass<FILL, unsigned short> p(t, o, MNX_MOL_FORMULA_REFUSED, origin, off_atoms, off_b0, off_bin, off_text, off_more);
+    if (!p.admitted()) return;
+    const int tid = threadIdx.x, na = p.na;
+    const unsigned nb = p.nb;
+    const Molecule& mol = p.mol;
+    const unsigned long long *A = p.A, *B = p.B;
+    const unsigned char* text_in = p.text_in();
 
-    // ---- every atom: FM_PER neighbouring atoms per thread; the candidates into their list ----
+    // ---- every atom: GR_PER neighbouring atoms per thread; the candidates into their list ----
     int bad = 0;
     unsigned is_cand = 0, n_mine = 0;
 #pragma unroll
-    for (int q = 0; q < FM_PER; ++q) {
-        const int a = FM_PER * tid + q;
+    for (int q = 0; q < GR_PER; ++q) {
+        const int a = GR_PER * tid + q;
         unsigned sl = 0;
         bool c = false;
         if (a < na) {
             const unsigned s0 = mol.A[a].sym0;
             sl = mol.A[a].sym_len;
-            if ((unsigned long long)m.text0 + s0 + sl > t.n_text_bytes) bad = 1;
+            if ((unsigned long long)mol.m.text0 + s0 + sl > t.n_text_bytes) bad = 1;
             else {
                 unsigned s3;
                 int name;
@@ -113,22 +96,13 @@ __global__ __launch_bounds__(FM_THREADS) void formula_kernel(
         if (FILL) { off_atoms[a] = 0; off_b0[a] = 0; off_bin[a] = 0; off_text[a] = sl; off_more[a] = 0; replaced[a] = 0; }
         if (c) { is_cand |= 1u << q; ++n_mine; }
     }
-    if (!FILL) {
-        // a bond that is no bond of the molecule, or bond records that are not sorted by i (the position of a label's new bonds
-        // is found by a search in them), refuse the molecule as a symbol beyond the text does
-        for (unsigned k = tid; k < nb; k += FM_THREADS) {
-            const unsigned w = (unsigned)B[2 * (size_t)k], i = w & 0xffffu, j = w >> 16;
-            if (i >= (unsigned)na || j >= (unsigned)na) bad = 1;
-            if (k > 0 && ((unsigned)B[2 * (size_t)(k - 1)] & 0xffffu) > i) bad = 1;
-        }
-        if (__syncthreads_or(bad)) { record(0, 0, 0, MNX_MOL_FORMULA_REFUSED); return; }
-    }
+    if (!FILL && p.bonds_refuse(bad)) return;
     unsigned n_cand;
     {
-        unsigned e = block_scan_excl<FM_THREADS>(n_mine, scan, &n_cand);
+        unsigned e = block_scan_excl<GR_THREADS>(n_mine, scan, &n_cand);
 #pragma unroll
-        for (int q = 0; q < FM_PER; ++q)
-            if (is_cand >> q & 1u) cand[e++] = (unsigned short)(FM_PER * tid + q);
+        for (int q = 0; q < GR_PER; ++q)
+            if (is_cand >> q & 1u) cand[e++] = (unsigned short)(GR_PER * tid + q);
     }
     __syncthreads();
 
@@ -176,17 +150,17 @@ __global__ __launch_bounds__(FM_THREADS) void formula_kernel(
         }
         unsigned own_text = 0, t_atoms, t_text, t_own;
 #pragma unroll
-        for (int q = 0; q < FM_PER; ++q)
-            if (FM_PER * tid + q < na) own_text += mol.A[FM_PER * tid + q].sym_len;
-        block_scan_excl<FM_THREADS>(add_atoms, scan, &t_atoms);
-        block_scan_excl<FM_THREADS>(add_text, scan, &t_text);
-        block_scan_excl<FM_THREADS>(own_text, scan, &t_own);
+        for (int q = 0; q < GR_PER; ++q)
+            if (GR_PER * tid + q < na) own_text += mol.A[GR_PER * tid + q].sym_len;
+        block_scan_excl<GR_THREADS>(add_atoms, scan, &t_atoms);
+        block_scan_excl<GR_THREADS>(add_text, scan, &t_text);
+        block_scan_excl<GR_THREADS>(own_text, scan, &t_own);
         const unsigned all = (__syncthreads_or((int)(flags & MNX_MOL_FORMULA_EXPANDED)) ? MNX_MOL_FORMULA_EXPANDED : 0u) |
                              (__syncthreads_or((int)(flags & MNX_MOL_FORMULA_LEFT)) ? MNX_MOL_FORMULA_LEFT : 0u) |
                              (__syncthreads_or((int)(flags & MNX_MOL_FORMULA_LIMIT)) ? MNX_MOL_FORMULA_LIMIT : 0u);
         const unsigned long long n_bonds = (unsigned long long)nb + t_atoms;
-        if (n_bonds > 0xffffffffull) record(0, 0, 0, MNX_MOL_FORMULA_REFUSED);
-        else record((unsigned)na + t_atoms, (unsigned)n_bonds, t_own + t_text, all);
+        if (n_bonds > 0xffffffffull) p.record(0, 0, 0, MNX_MOL_FORMULA_REFUSED);
+        else p.record((unsigned)na + t_atoms, (unsigned)n_bonds, t_own + t_text, all);
         return;
     }
 
@@ -200,62 +174,22 @@ __global__ __launch_bounds__(FM_THREADS) void formula_kernel(
         for (unsigned k = 1; k < f.n; ++k) b0 += formula::atom_parent(atom[k * FM_LANES]) == 0;
         spell_found(st, atom, f, 0, [&](char) { ++first; });
         for (unsigned k = 1; k < f.n; ++k) spell_found(st, atom, f, k, [&](char) { ++more; });
-        off_atoms[a] = (unsigned short)(f.n - 1);
-        off_b0[a] = (unsigned short)b0;
-        off_bin[a] = (unsigned short)(f.n - 1 - b0);
-        off_text[a] = first;
-        off_more[a] = more;
-        replaced[a] = 1;
+        off_atoms[a] = (unsigned short)(f.n - 1); off_b0[a] = (unsigned short)b0; off_bin[a] = (unsigned short)(f.n - 1 - b0);
+        off_text[a] = first; off_more[a] = more; replaced[a] = 1;
     }
     __syncthreads();
-    unsigned t_b0, t_text;
-    {
-        unsigned v[5][FM_PER], s[5] = {0, 0, 0, 0, 0}, e[5], total;
+    unsigned v[GR_SIZES][GR_PER];
 #pragma unroll
-        for (int q = 0; q < FM_PER; ++q) {
-            const int a = FM_PER * tid + q;
-            v[0][q] = off_atoms[a]; v[1][q] = off_b0[a]; v[2][q] = off_bin[a]; v[3][q] = off_text[a]; v[4][q] = off_more[a];
-#pragma unroll
-            for (int c = 0; c < 5; ++c) s[c] += v[c][q];
-        }
-        e[0] = block_scan_excl<FM_THREADS>(s[0], scan, &total);
-        e[1] = block_scan_excl<FM_THREADS>(s[1], scan, &t_b0);
-        e[2] = block_scan_excl<FM_THREADS>(s[2], scan, &total);
-        e[3] = block_scan_excl<FM_THREADS>(s[3], scan, &t_text);
-        e[4] = block_scan_excl<FM_THREADS>(s[4], scan, &total);
-#pragma unroll
-        for (int q = 0; q < FM_PER; ++q) {
-            const int a = FM_PER * tid + q;
-            off_atoms[a] = (unsigned short)e[0]; off_b0[a] = (unsigned short)e[1]; off_bin[a] = (unsigned short)e[2];
-            off_text[a] = e[3]; off_more[a] = e[4];
-#pragma unroll
-            for (int c = 0; c < 5; ++c) e[c] += v[c][q];
-        }
+    for (int q = 0; q < GR_PER; ++q) {
+        const int a = GR_PER * tid + q;
+        v[GR_ATOMS][q] = off_atoms[a]; v[GR_B0][q] = off_b0[a]; v[GR_BIN][q] = off_bin[a]; v[GR_TEXT][q] = off_text[a]; v[GR_MORE][q] = off_more[a];
     }
-    __syncthreads();
+    p.place(v, scan);
 
-    // atom k of the new molecule, its symbol of sym_len bytes at byte sym0 of the new text (the bytes are written apart): index,
-    // bins and score of the input record w0..w2
-    auto put_record = [&](unsigned k, unsigned sym0, unsigned sym_len, unsigned long long w0, unsigned long long w1,
-                          unsigned long long w2, unsigned from) {
-        const unsigned long long at = (unsigned long long)mo.atom0 + k;
-        if (put_atom(o, at, atom_word0(sym0, sym_len, 0u) | (w0 & ATOM_INDEX_BITS), w1 & ATOM_BINS_BITS, w2) && origin)
-            origin[at] = (unsigned short)from;
-    };
-
-    // ---- the molecule's own atoms and bonds: the atoms keep their indices, a bond moves back by the new bonds of the rows in
-    //      front of its own ----
-    for (int a = tid; a < na; a += FM_THREADS) {
-        if (replaced[a]) continue;
-        const unsigned long long w0 = A[3 * (size_t)a], w1 = A[3 * (size_t)a + 1], w2 = A[3 * (size_t)a + 2];
-        const unsigned sl = (unsigned)(w0 >> 32) & 0xffffu;
-        put_record((unsigned)a, off_text[a], sl, w0, w1, w2, (unsigned)a);
-        put_text(o, (unsigned long long)mo.text0 + off_text[a], text_in + (unsigned)w0, sl);
-    }
-    for (unsigned k = tid; k < nb; k += FM_THREADS) {
-        const unsigned long long w0 = B[2 * (size_t)k], w1 = B[2 * (size_t)k + 1];
-        put_bond(o, (unsigned long long)mo.bond0 + k + off_b0[(unsigned)w0 & (FM_MAX - 1)], w0 & BOND_FIELD_BITS, w1);
-    }
+    // ---- the molecule's own atoms and bonds ----
+    for (int a = tid; a < na; a += GR_THREADS)
+        if (!replaced[a]) p.put_own_atom(a);
+    p.own_bonds();
 
     // ---- the labels: the first atom in the label's place, the others behind the molecule's own in placement order ----
     for (unsigned base = 0; base < n_cand; base += FM_LANES) {
@@ -264,35 +198,29 @@ __global__ __launch_bounds__(FM_THREADS) void formula_kernel(
         if (!replaced[a]) continue;
         const Found f = find(a);
         const unsigned long long w0 = A[3 * (size_t)a], w1 = A[3 * (size_t)a + 1], w2 = A[3 * (size_t)a + 2];
-        const unsigned first = (unsigned)na + off_atoms[a];          // new index of atom 1 of the structure
+        const unsigned first = p.first(a);
         unsigned at = off_text[a];                                   // where the next symbol begins in the new text
         for (unsigned k = 0; k < f.n; ++k) {
-            if (k == 1) at = t_text + off_more[a];
+            if (k == 1) at = p.more(a);
             unsigned len = 0;
             spell_found(st, atom, f, k, [&](char c) {
-                const unsigned long long p = (unsigned long long)mo.text0 + at + len;
-                if (p < o.text_cap) o.text[p] = c;
+                const unsigned long long to = (unsigned long long)p.mo.text0 + at + len;
+                if (to < o.text_cap) o.text[to] = c;
                 ++len;
             });
-            put_record(k == 0 ? a : first + k - 1, at, len, w0, w1, w2, a);
+            p.put_record(k == 0 ? a : first + k - 1, at, len, w0, w1, w2, a);
             at += len;
         }
         // its bonds: those from the first atom behind the bond records of row a, the others in the rows of the appended atoms
-        unsigned lo = 0, hi = nb;                                    // first record with i > a
-        while (lo < hi) {
-            const unsigned mid = lo + ((hi - lo) >> 1);
-            if (((unsigned)B[2 * (size_t)mid] & 0xffffu) <= a) lo = mid + 1; else hi = mid;
-        }
-        const unsigned row = lo + off_b0[a], inner = nb + t_b0 + off_bin[a];
+        const unsigned row = p.row(a), inner = p.inner(a);
         for (unsigned k = 1; k < f.n; ++k) {
-            const unsigned w = atom[k * FM_LANES], p = formula::atom_parent(w), ty = formula::atom_order(w);
-            unsigned before = 0;                                     // the bonds in front of (p, k) among those of its kind
+            const unsigned w = atom[k * FM_LANES], pa = formula::atom_parent(w), ty = formula::atom_order(w);
+            unsigned before = 0;                                     // the bonds in front of (pa, k) among those of its kind
             for (unsigned c = 1; c < f.n; ++c) {
                 const unsigned pc = formula::atom_parent(atom[c * FM_LANES]);
-                before += (p == 0) ? (pc == 0 && c < k) : (pc != 0 && (pc < p || (pc == p && c < k)));
+                before += (pa == 0) ? (pc == 0 && c < k) : (pc != 0 && (pc < pa || (pc == pa && c < k)));
             }
-            put_bond(o, (unsigned long long)mo.bond0 + (p == 0 ? row : inner) + before,
-                     bond_word0(p == 0 ? a : first + p - 1, first + k - 1, ty, ty), w2);
+            p.put_new_bond((pa == 0 ? row : inner) + before, pa == 0 ? a : first + pa - 1, first + k - 1, ty, w2);
         }
     }
 }
@@ -301,7 +229,7 @@ __global__ __launch_bounds__(FM_THREADS) void formula_kernel(
 
 hipError_t formula_pack_enqueue(const SymbolTables* st_dev, const FragView& fv, const PackedTables& t, const TablesOut& o,
                                 unsigned short* origin, unsigned* totals, unsigned max_steps, hipStream_t s) {
-    return count_scan_fill(formula_kernel<false>, formula_kernel<true>, t.n, FM_THREADS, o, totals, s, t, st_dev, fv, o, origin, max_steps);
+    return count_scan_fill(formula_kernel<false>, formula_kernel<true>, t.n, GR_THREADS, o, totals, s, t, st_dev, fv, o, origin, max_steps);
 }
 
 }  // namespace mnx

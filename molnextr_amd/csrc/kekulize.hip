@@ -1,5 +1,5 @@
 // kekulize.hip — aromatic systems of the packed molecule tables written as Kekule structures (mnx_kekulize_pack): the inverse of
-// what normalize.hip perceives, and a pass of respell_pass.h, where its frame is: count, scan and fill, admission and refusal,
+// what normalize.hip perceives, and a pass of respell_pass.h, where its frame is: count, scan and fill, admission and refusal (table_pass.h),
 // the slots, the symbols' placing, the records written. The rule stands in include/molnextr_hip.h: a Kekule structure is a
 // perfect matching of the atoms that must take a double bond, and the choice among several is this library's own search order,
 // not a toolkit's. Inside a workgroup, in count and again in fill: the atoms' interpretation (atom_symbol.h); one stride over the

@@ -1,7 +1,7 @@
 // normalize.hip — one normal spelling per atom on the packed molecule tables (mnx_normalize_pack): aromatic rings perceived from
 // Kekule drawings, hydrogens counted, brackets dropped where a reader infers what they say, so that every writer, the canonical
 // ranks and mnx_expand_pack run on the result as they are. A pass of respell_pass.h, where its frame is: count, scan and fill,
-// admission and refusal, the slots, the symbols' placing, the records written. The rule stands in include/molnextr_hip.h: it is
+// admission and refusal (table_pass.h), the slots, the symbols' placing, the records written. The rule stands in include/molnextr_hip.h: it is
 // this library's own and not a toolkit's aromaticity model. Inside a workgroup, in count and again in fill: the atoms'
 // interpretation (atom_symbol.h), then per atom its bond count, bond order sum and the first three of its bonds in LDS (a
 // candidate atom has at most three, so a graph of any density costs one pass over its bond records and nothing that grows with a

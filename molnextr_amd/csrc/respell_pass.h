@@ -1,13 +1,13 @@
 // respell_pass.h — the frame of a pass that respells atoms in place on the packed molecule tables (normalize.hip, kekulize.hip),
 // once (internal): packed tables in, packed tables of the same record types out, atom and bond counts and order unchanged, every
 // atom with a new or a copied symbol. One workgroup of RS_THREADS per molecule, run twice (count, fill; tables_out.h). A pass says
-// which atoms it respells, how, and which bonds change their type; who is admitted, what a refusal leaves, where the symbols go
-// and what is written is here. LDS atomics count, add up, hand out the slots of a list that is sorted afterwards, set bits of
-// sets and take the minimum of a set: no atomic decides a position, an order or a result.
+// which atoms it respells, how, and which bonds change their type; where the symbols go and what is written is here, who is
+// admitted and what a refusal leaves is table_pass.h, shared with grow_pass.h. LDS atomics count, add up, hand out the slots of
+// a list that is sorted afterwards, set bits of sets and take the minimum of a set: no atomic decides a position, an order or a
+// result.
 #pragma once
 #include "atom_spell.h"
-#include "atom_symbol.h"
-#include "tables_out.h"
+#include "table_pass.h"
 
 namespace mnx {
 
@@ -57,45 +57,15 @@ __device__ __forceinline__ void put_spelled(const TablesOut& o, unsigned long lo
         if (at + c < o.text_cap) o.text[at + c] = (char)(c < 8u ? s.lo >> (8u * c) : (unsigned long long)(s.hi >> (8u * (c - 8u))));
 }
 
-struct BondEnds { unsigned i, j, ty; bool beyond; };     // a bond record's atoms and type; beyond: no bond of the molecule
-
-// Molecule blockIdx.x in one workgroup of a pass, count (FILL = false) or fill. refused: the pass's MNX_MOL_*_REFUSED.
+// Molecule blockIdx.x in one workgroup of a respelling pass, count (FILL = false) or fill (table_pass.h).
 template <bool FILL>
-struct RespellPass {
-    const PackedTables& t;
-    const TablesOut& o;
-    const unsigned refused;
-    const Molecule mol;
-    mnx_mol mo;                           // fill: what count and the scan left of the molecule
-    const int na, nb;
-    const unsigned long long *A, *B;      // the molecule's atom and bond records as 64-bit words (tables_out.h)
+struct RespellPass : TablePass<FILL> {
+    using P = TablePass<FILL>;
+    using P::t; using P::o; using P::mol; using P::mo; using P::na; using P::nb; using P::A; using P::B; using P::record;
 
-    __device__ __forceinline__ RespellPass(const PackedTables& t, const TablesOut& o, unsigned refused)
-        : t(t), o(o), refused(refused), mol(admit_molecule(t, blockIdx.x)), na((int)mol.m.n_atoms), nb((int)mol.m.n_bonds),
-          A((const unsigned long long*)mol.A), B((const unsigned long long*)mol.B) {}
-
-    __device__ __forceinline__ void record(unsigned n_atoms, unsigned n_bonds, unsigned text_len, unsigned flags) const {    // count's result
-        if (threadIdx.x == 0)
-            store_mol_counts(&o.mols[blockIdx.x], n_atoms, n_bonds, text_len, flags | (mol.m.flags & MNX_MOL_TRUNCATED), mol.m.overall_score);
-    }
-    // Whether there is anything to do (the same for every thread): count refuses a molecule whose records lie beyond the tables or
-    // that is too large, fill leaves one alone that count refused. A and B are read only behind this.
-    __device__ __forceinline__ bool admitted() {
-        if (FILL) mo = o.mols[blockIdx.x];
-        const bool ok = FILL ? !(mo.flags & refused) : !(mol.flags & (PT_BEYOND_TABLES | PT_TOO_LARGE));
-        if (!FILL && !ok) record(0, 0, 0, refused);
-        return ok;
-    }
-    __device__ __forceinline__ BondEnds bond(int k) const {
-        const unsigned w = (unsigned)B[2 * (size_t)k], i = w & 0xffffu, j = w >> 16, ty = (unsigned)(B[2 * (size_t)k] >> 32) & 0xffu;
-        return {i, j, ty, i >= (unsigned)na || j >= (unsigned)na};
-    }
-    // one barrier: whether a thread found a symbol beyond the text or a bond that is no bond of the molecule; count refuses then
-    __device__ __forceinline__ bool refuses(int bad) const {
-        bad = __syncthreads_or(bad);
-        if (!FILL && bad) record(0, 0, 0, refused);
-        return !FILL && bad;
-    }
+    __device__ __forceinline__ RespellPass(const PackedTables& t, const TablesOut& o, unsigned refused) : P(t, o, refused) {}
+    // too large: more than the 999 atoms or bonds of RS_MAX
+    __device__ __forceinline__ bool admitted() { return P::admitted((mol.flags & PT_TOO_LARGE) != 0); }
 
     // Every atom's new symbol: RS_PER neighbouring atoms per thread, placed by a prefix scan over their lengths (scan: 2 *
     // RS_THREADS words of LDS). spell(a, sym, note) sets atom a's note and either spells it into sym or returns true: the symbol
@@ -105,7 +75,7 @@ struct RespellPass {
     __device__ __forceinline__ void atoms(unsigned* scan, unsigned char* __restrict__ notes, unsigned note0, unsigned flag0,
                                           unsigned note1, unsigned flag1, Spell spell) {
         const int tid = threadIdx.x;
-        const unsigned char* text_in = t.text + mol.m.text0;
+        const unsigned char* text_in = P::text_in();
         Spelled sym[RS_PER];
         unsigned note[RS_PER], sum = 0, copied = 0;        // bit q: this thread's atom q keeps its symbol
         int vote0 = 0, vote1 = 0;
@@ -147,7 +117,7 @@ struct RespellPass {
     // fill: every bond record as it is, but with type = rev = new_type(k, i) of record k with first atom i where that is not 0
     template <typename NewType>
     __device__ __forceinline__ void bonds(NewType new_type) const {
-        for (int k = threadIdx.x; k < nb; k += RS_THREADS) {
+        for (int k = threadIdx.x; k < (int)nb; k += RS_THREADS) {
             unsigned long long w0 = B[2 * (size_t)k] & BOND_FIELD_BITS;
             const unsigned long long ty = new_type(k, (unsigned)w0 & 0xffffu);
             if (ty) w0 = (w0 & 0xffffffffull) | ty << 32 | ty << 40;

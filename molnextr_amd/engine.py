@@ -1150,6 +1150,20 @@ class Engine:
         data = self._sized_text(fn, args + [_ptr(recs), _ptr(order)], int(cap) if cap is not None else n * self.SMILES_GUESS, tail)
         return recs.cpu().numpy().view(SMILES_DTYPE), order[:na].cpu().numpy().view(np.uint16), data
 
+    def _grow_pack(self, fn: str, rec: dict, caps, keep_device: bool, tail=()) -> dict:
+        """expand_pack and formula_pack: lib.<fn>(h, tables, mols_out, arenas, origin, totals, *tail, stream) from the input's
+        sizes plus room for a label of about ten atoms per molecule, or caps, with 'origin' uint16 [atoms]"""
+        dev = torch.device("cuda", self.device)
+        n = len(rec["mols"])
+        tables, args = self._packed_tables(rec)
+        if caps is None:
+            caps = (len(rec["atoms"]) + 12 * n, len(rec["bonds"]) + 12 * n, len(rec["text"]) + 16 * n)
+        out = self._sized_tables(fn, n, caps,
+                                 lambda mols, arenas, totals, origin: getattr(self.lib, fn)(self.h, *args, mols, *arenas, origin, totals, *tail, _stream()),
+                                 dev, keep_device, side=torch.int16)
+        out["origin"] = out.pop("side").cpu().numpy().view(np.uint16)
+        return out
+
     def expand_pack(self, rec: dict, caps=None, keep_device: bool = False) -> dict:
         """graph_pack's records -> the same molecules with every abbreviation label that has a fragment replaced by the
         fragment's atoms and bonds (mnx_expand_pack; the rule: include/molnextr_hip.h): a dict with graph_pack's keys — 'mols',
@@ -1158,16 +1172,7 @@ class Engine:
         the atoms of a fragment share the label's coordinates; mols['flags'] carries MOL_EXPANDED / MOL_LABEL_LEFT /
         MOL_EXPAND_REFUSED. Starts from the input's sizes plus a margin (or caps = (atom_cap, bond_cap, text_cap)) and repeats
         at most once with the sizes `totals` reports. keep_device: also 'device', as graph_pack."""
-        dev = torch.device("cuda", self.device)
-        n = len(rec["mols"])
-        tables, args = self._packed_tables(rec)
-        if caps is None:        # room for a label of about ten atoms per molecule before the repeat
-            caps = (len(rec["atoms"]) + 12 * n, len(rec["bonds"]) + 12 * n, len(rec["text"]) + 16 * n)
-        out = self._sized_tables("mnx_expand_pack", n, caps,
-                                 lambda mols, arenas, totals, origin: self.lib.mnx_expand_pack(self.h, *args, mols, *arenas, origin, totals, _stream()),
-                                 dev, keep_device, side=torch.int16)
-        out["origin"] = out.pop("side").cpu().numpy().view(np.uint16)
-        return out
+        return self._grow_pack("mnx_expand_pack", rec, caps, keep_device)
 
     def formula_pack(self, rec: dict, caps=None, keep_device: bool = False, max_steps: int = 0) -> dict:
         """graph_pack's records (or smiles_read's) -> the same molecules with every condensed-formula label ('CH2CH3', 'N(CH3)2',
@@ -1178,17 +1183,7 @@ class Engine:
         'totals', 'origin' —; mols['flags'] carries MOL_FORMULA_EXPANDED / MOL_FORMULA_LEFT / MOL_FORMULA_LIMIT /
         MOL_FORMULA_REFUSED. max_steps: the placements one label's search may try (0: FORMULA_DEFAULT_STEPS). Sizes itself as
         expand_pack does; keep_device: also 'device', as graph_pack."""
-        dev = torch.device("cuda", self.device)
-        n = len(rec["mols"])
-        tables, args = self._packed_tables(rec)
-        if caps is None:        # room for a label of about ten atoms per molecule before the repeat
-            caps = (len(rec["atoms"]) + 12 * n, len(rec["bonds"]) + 12 * n, len(rec["text"]) + 16 * n)
-        out = self._sized_tables("mnx_formula_pack", n, caps,
-                                 lambda mols, arenas, totals, origin: self.lib.mnx_formula_pack(self.h, *args, mols, *arenas, origin, totals,
-                                                                                               int(max_steps), _stream()),
-                                 dev, keep_device, side=torch.int16)
-        out["origin"] = out.pop("side").cpu().numpy().view(np.uint16)
-        return out
+        return self._grow_pack("mnx_formula_pack", rec, caps, keep_device, (int(max_steps),))
 
     def _respell_pack(self, fn: str, rec: dict, caps, keep_device: bool, tail=()) -> dict:
         """normalize_pack and kekulize_pack: lib.<fn>(h, tables, mols_out, arenas, atom_notes, totals, *tail, stream) from the

@@ -109,6 +109,9 @@ TEXT_ARGS = {"mnx_smiles_pack": "recs order out out_cap totals",
              "mnx_molfile_pack": "scale files out out_cap totals"}
 TABLE_ARGS = {"mnx_expand_pack": "mols_out atoms_out atom_cap bonds_out bond_cap text_out text_cap origin totals",
               "mnx_normalize_pack": "mols_out atoms_out atom_cap bonds_out bond_cap text_out text_cap atom_notes totals",
+              # a step limit goes in as step_cap: the harness sizes no output for a name that ends in _cap, and a limit is a capacity of steps
+              "mnx_kekulize_pack": "mols_out atoms_out atom_cap bonds_out bond_cap text_out text_cap atom_notes totals step_cap",
+              "mnx_formula_pack": "mols_out atoms_out atom_cap bonds_out bond_cap text_out text_cap origin totals step_cap",
               "mnx_smiles_read": "mols recs atoms atom_cap bonds bond_cap text text_cap totals",
               "mnx_graph_pack": "mols atoms atom_cap bonds bond_cap text text_cap totals"}
 SIDES = ("origin", "atom_notes", "recs")

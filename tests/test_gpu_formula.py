@@ -10,7 +10,6 @@ import pytest
 import expand_ref as X
 import formula_ref as F
 import molfile_ref as M
-import packed_tables
 import test_formula_host as FH
 import test_normalize_host as H
 from molnextr_amd import weights as W
@@ -20,7 +19,6 @@ from packed_tables import Tables, _p, assert_refused, call_tables, clean, compar
 
 pytestmark = pytest.mark.gpu
 
-packed_tables.TABLE_ARGS["mnx_formula_pack"] = "mols_out atoms_out atom_cap bonds_out bond_cap text_out text_cap origin totals step_cap"       # a name on _cap: an input of the harness
 TABLES, FRAGS = FH.TABLES, FH.FRAGS
 SEARCH_LANES = 32               # labels one workgroup searches side by side (formula.hip FM_LANES)
 

@@ -28,10 +28,6 @@ from test_gpu_normalize import ETHANOL, records_of
 pytestmark = pytest.mark.gpu
 TABLES = H.TABLES
 
-# the entry point in the harness: normalize's arguments and the step limit in front of the stream. The harness sizes no output
-# for a name that ends in _cap, which is what the limit is: a capacity of steps
-packed_tables.TABLE_ARGS["mnx_kekulize_pack"] = "mols_out atoms_out atom_cap bonds_out bond_cap text_out text_cap atom_notes totals step_cap"
-
 
 def run(eng, t, caps, max_steps=0, **over):
     """one call at the capacities caps; the result's `side` is `atom_notes`"""
