@@ -159,6 +159,28 @@ static int print_first_expanded_smiles(mnx_engine* eng, int n_images, const mnx_
                (mol.flags & MNX_MOL_EXPAND_REFUSED) ? ", refused" : "");
         rc = print_first_canonical_smiles(eng, n_images, mols2_dev, atoms2_dev, bonds2_dev, text2_dev, totals);
     }
+    if (rc == MNX_OK) {     /* behind the expansion: only the largest connected component (mnx_main_pack, the reference's
+                             * --keep_main_molecule). Nothing grows, so tables of the input's sizes always suffice. */
+        mnx_mol* mols3_dev = NULL;
+        mnx_atom* atoms3_dev = NULL;
+        mnx_bond* bonds3_dev = NULL;
+        char* text3_dev = NULL;
+        hipMalloc((void**)&mols3_dev, (size_t)n_images * sizeof(mnx_mol));
+        hipMalloc((void**)&atoms3_dev, ((size_t)totals[0] + 1) * sizeof(mnx_atom));
+        hipMalloc((void**)&bonds3_dev, ((size_t)totals[1] + 1) * sizeof(mnx_bond));
+        hipMalloc((void**)&text3_dev, (size_t)totals[2] + 1);
+        rc = mnx_main_pack(eng, mols2_dev, n_images, atoms2_dev, totals[0], bonds2_dev, totals[1], text2_dev, totals[2], mols3_dev,
+                           atoms3_dev, totals[0], bonds3_dev, totals[1], text3_dev, totals[2], /*origin=*/NULL, totals_dev, /*stream=*/NULL);
+        if (rc != MNX_OK) fprintf(stderr, "%s\n", mnx_last_error(eng));
+        else {
+            hipMemcpy(totals, totals_dev, sizeof totals, 2);
+            hipMemcpy(&mol, mols3_dev, sizeof mol, 2);
+            printf("molecule 0, main component: %u atoms%s%s\n", (unsigned)mol.n_atoms, (mol.flags & MNX_MOL_MAIN_KEPT) ? ", atoms dropped" : "",
+                   (mol.flags & MNX_MOL_MAIN_TIE) ? ", a tie" : "");
+            rc = print_first_canonical_smiles(eng, n_images, mols3_dev, atoms3_dev, bonds3_dev, text3_dev, totals);
+        }
+        hipFree(mols3_dev); hipFree(atoms3_dev); hipFree(bonds3_dev); hipFree(text3_dev);
+    }
     hipFree(mols2_dev); hipFree(totals_dev); hipFree(atoms2_dev); hipFree(bonds2_dev); hipFree(text2_dev);
     return rc;
 }

@@ -412,7 +412,7 @@ int mnx_set_vocab_text(mnx_engine* h, const char* bytes, const uint32_t* offsets
  * size outside the limits, the scores partly set, misaligned records, or no vocabulary text / token classes set. */
 typedef struct mnx_mol {
     uint32_t atom0, n_atoms, bond0, n_bonds, text0, smiles_len;
-    uint32_t flags;             /* bit 0: more atoms than kmax, tables truncated to kmax; MNX_MOL_EXPAND* of mnx_expand_pack; bits 4-6 of mnx_normalize_pack; bits 7-9 of mnx_kekulize_pack; bits 10, 11, 16, 17 of mnx_formula_pack */
+    uint32_t flags;             /* bit 0: more atoms than kmax, tables truncated to kmax; MNX_MOL_EXPAND* of mnx_expand_pack; bits 4-6 of mnx_normalize_pack; bits 7-9 of mnx_kekulize_pack; bits 10, 11, 16, 17 of mnx_formula_pack; bits 18-20 of mnx_main_pack */
     uint32_t reserved;          /* 0 */
     double overall_score;
 } mnx_mol;
@@ -993,6 +993,50 @@ int mnx_formula_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_at
                      const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_mol* mols_out,
                      mnx_atom* atoms_out, uint32_t atom_cap, mnx_bond* bonds_out, uint32_t bond_cap, char* text_out,
                      uint32_t text_cap, uint16_t* origin, uint32_t* totals, uint32_t max_steps, void* stream);
+
+/* The main molecule of every molecule, on the device: packed tables in, packed tables of the SAME record types out, with the
+ * connected component that has the most atoms kept and every other atom and its bonds dropped — salts, counter-ions, solvent and
+ * the stray atoms a bond head leaves unconnected. Intended order: mnx_graph_pack or mnx_smiles_read -> mnx_formula_pack ->
+ * mnx_expand_pack -> THIS CALL -> mnx_kekulize_pack -> mnx_normalize_pack -> the writers: behind the expansion, so that a label
+ * counts with the atoms it stands for, as the reference counts them after _expand_functional_group ('[Ph].CCCCC' keeps the ring
+ * behind mnx_expand_pack and the chain in front of it).
+ * THE RULE IS THE REFERENCE'S (_keep_main_molecule: GetMolFrags, np.argmax of the sizes): it is graph connectivity and a maximum
+ * and needs no toolkit to state. A component is a set of atoms joined by bond records; every record joins its ends whatever its
+ * type, a record with i == j joins nothing, the same pair in several records counts once. The size of a component is the number
+ * of its atom records (hydrogens that a symbol implies are no atoms). The component with the most atoms stays; among components of
+ * that size the one that holds the lowest atom index stays, as the reference's first of the largest does. A post-pass on a
+ * post-pass: it reads the input tables, changes none of them (the outputs must not overlap them) and touches no decode state.
+ *
+ * Atoms: the kept atoms in ascending input index, renumbered from 0; index, x_bin, y_bin and score are copied.
+ * Bonds: a record is kept iff its i is kept (its j is then kept too), in the input's order, i and j mapped to the new indices;
+ * type, rev and score are copied. The records need not be sorted; a table sorted by (i, j) stays sorted.
+ * Text: the text of an output molecule is the kept atoms' symbols behind one another in the order of the new indices, smiles_len
+ * its length, as mnx_expand_pack leaves it — also for a molecule of one component or none, which keeps every atom: the output
+ * has one form. mnx_atom.sym0 is a span of it as before. The symbols are copied, not read: no symbol tables are needed.
+ * origin uint16 [atom_cap] (may be null): origin[atom0 + k] = the input index of output atom k.
+ * mnx_mol.flags of the output: bit 0 is copied, the bits of the other passes are not; MNX_MOL_MAIN_KEPT: the molecule had more
+ * than one component and atoms were dropped; MNX_MOL_MAIN_TIE: another component had as many atoms as the kept one, so the choice
+ * rests on the numbering of the atoms, as the reference's does; MNX_MOL_MAIN_REFUSED: the molecule's records point beyond the
+ * tables passed — atom0 + n_atoms, bond0 + n_bonds or text0 + smiles_len beyond the sizes passed, a symbol beyond n_text_bytes, a
+ * bond whose i or j is no atom of the molecule —, or it has more than 2047 atoms (any number of bond records). A refused molecule
+ * has n_atoms = n_bonds = smiles_len = 0 in mols_out. overall_score is copied.
+ * Inputs and outputs as mnx_expand_pack's, argument for argument: mols [n], 1 <= n <= 65536; atoms [n_atom_records], bonds
+ * [n_bond_records] (8-byte aligned), text [n_text_bytes]; mols_out [n]; atoms_out [atom_cap], bonds_out [bond_cap] (8-byte
+ * aligned), text_out [text_cap] bytes; totals uint32 [4] = {atoms, bonds, text bytes needed, 1 if any capacity was too small}.
+ * Nothing grows: the input's sizes always suffice. When a capacity is too small nothing is written beyond it (origin follows
+ * atom_cap), and mols_out and totals are complete all the same: read the needed sizes and call again. Deterministic word for word:
+ * every position comes from a prefix scan; the components come from integer minima, sums and one maximum in on-chip memory, whose
+ * results do not depend on the order they are taken in. Records are written whole, padding bytes as zeros. Three launches,
+ * asynchronous on `stream`, no allocation, no host synchronisation.
+ * MNX_ERR_INVALID_ARG (with mnx_last_error, "mnx_main_pack: ..."): a null pointer (a table with capacity 0 may be null), n outside
+ * 1..65536, or misaligned records; nothing is launched then. */
+#define MNX_MOL_MAIN_KEPT 262144u
+#define MNX_MOL_MAIN_TIE 524288u
+#define MNX_MOL_MAIN_REFUSED 1048576u
+int mnx_main_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
+                  const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_mol* mols_out,
+                  mnx_atom* atoms_out, uint32_t atom_cap, mnx_bond* bonds_out, uint32_t bond_cap, char* text_out,
+                  uint32_t text_cap, uint16_t* origin, uint32_t* totals, void* stream);
 
 /* One normal spelling per atom, on the device: packed tables in, packed tables of the SAME record types out, with aromatic rings
  * perceived from Kekule drawings, hydrogens counted and brackets dropped where a reader infers what they say. The canonical ranks key

@@ -267,6 +267,10 @@ hipError_t expand_pack_enqueue(const SymbolTables* st_dev, const FragView& fv, c
 // placements one label's search may try, 0 = MNX_FORMULA_DEFAULT_STEPS.
 hipError_t formula_pack_enqueue(const SymbolTables* st_dev, const FragView& fv, const PackedTables& t, const TablesOut& o,
                                 unsigned short* origin, unsigned* totals, unsigned max_steps, hipStream_t s);
+// main_mol.hip: of every molecule of t the connected component with the most atoms (among equals the one with the lowest atom), the
+// other atoms and their bonds dropped, as packed tables of the same record types (mnx_main_pack): count, scan and fill, three
+// launches on s
+hipError_t main_pack_enqueue(const PackedTables& t, const TablesOut& o, unsigned short* origin, unsigned* totals, hipStream_t s);
 // normalize.hip: the molecules of t with one normal spelling per atom — aromatic rings perceived, hydrogens counted, brackets
 // dropped where a reader infers them — as packed tables of the same record types (mnx_normalize_pack): count, scan and fill,
 // three launches on s; atom_notes (may be null) receives one byte per output atom

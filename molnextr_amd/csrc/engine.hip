@@ -1502,7 +1502,7 @@ int mnx_set_fragments(mnx_engine* h, const mnx_mol* frags, int32_t n_frags, cons
 // What mnx_molfile_pack, mnx_expand_pack, mnx_normalize_pack, mnx_kekulize_pack and the five mnx_smiles_pack* test before they launch, in
 // the order in which a call refused for two reasons reports them. Its own pointers (outs_null, outs_skew) the entry point tests; `aligned` ends its alignment message.
 static int check_packed_tables(mnx_engine* h, const char* fn, const PackedTables& t, bool outs_null, bool outs_skew,
-                               const char* aligned) {
+                               const char* aligned, bool reads_symbols = true) {
     if (!h) return MNX_ERR_INVALID_ARG;
     auto bad = [&](const std::string& m) { h->err = std::string(fn) + ": " + m; return MNX_ERR_INVALID_ARG; };
     if (!t.mols || (!t.atoms && t.n_atom_records) || (!t.bonds && t.n_bond_records) || (!t.text && t.n_text_bytes) || outs_null)
@@ -1510,7 +1510,7 @@ static int check_packed_tables(mnx_engine* h, const char* fn, const PackedTables
     if (t.n < 1 || t.n > 65536) return bad("1 <= n <= 65536 required");
     if ((((uintptr_t)t.mols | (uintptr_t)t.atoms | (uintptr_t)t.bonds) & 7) || outs_skew)
         return bad(std::string("mols, atoms and bonds must be 8-byte aligned, ") + aligned);
-    if (!h->have_st) return bad("call mnx_set_symbol_tables first");
+    if (reads_symbols && !h->have_st) return bad("call mnx_set_symbol_tables first");
     return MNX_OK;
 }
 
@@ -1556,6 +1556,21 @@ int mnx_formula_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_at
     const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
     const TablesOut o = tables_out(mols_out, atoms_out, atom_cap, bonds_out, bond_cap, text_out, text_cap);
     return grow_pack(h, "mnx_formula_pack", t, o, origin, totals, stream, true, max_steps);
+}
+
+// mnx_main_pack reads no symbol: it needs neither symbol tables nor fragments
+int mnx_main_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
+                  const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_mol* mols_out,
+                  mnx_atom* atoms_out, uint32_t atom_cap, mnx_bond* bonds_out, uint32_t bond_cap, char* text_out, uint32_t text_cap,
+                  uint16_t* origin, uint32_t* totals, void* stream) {
+    const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
+    const TablesOut o = tables_out(mols_out, atoms_out, atom_cap, bonds_out, bond_cap, text_out, text_cap);
+    if (int rc = check_packed_tables(h, "mnx_main_pack", t, tables_out_null(o, totals), tables_out_skew(o, totals) || ((uintptr_t)origin & 1) != 0,
+                                     "the output tables too, totals 4-byte, origin 2-byte", false))
+        return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, main_pack_enqueue(t, o, origin, totals, (hipStream_t)stream));
+    return MNX_OK;
 }
 
 // mnx_normalize_pack and mnx_kekulize_pack (kekulize, with its max_steps): one check, one way to the pass's three launches

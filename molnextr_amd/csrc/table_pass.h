@@ -1,5 +1,5 @@
 // table_pass.h — one molecule of a pass from packed tables to packed tables in one workgroup, run twice (count, fill;
-// tables_out.h): what the frames of respell_pass.h and grow_pass.h share, once (internal). Who is admitted, what a refusal
+// tables_out.h): what the frames of respell_pass.h, grow_pass.h and select_pass.h share, once (internal). Who is admitted, what a refusal
 // leaves and how count's result is stored is here; who is too large is the frame's.
 #pragma once
 #include "atom_symbol.h"

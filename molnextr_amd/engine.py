@@ -30,7 +30,7 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
            "mnx_set_symbol_tables", "mnx_molfile_pack", "mnx_smiles_pack", "mnx_smiles_pack_stereo",
            "mnx_smiles_pack_marks", "mnx_smiles_pack_canonical", "mnx_smiles_pack_symmetric", "mnx_set_fragments", "mnx_expand_pack", "mnx_smiles_read",
            "mnx_beam_scripted", "mnx_edge_probs", "mnx_normalize_pack", "mnx_kekulize_pack", "mnx_formula_pack",
-           "mnx_decode_beam_forced")
+           "mnx_decode_beam_forced", "mnx_main_pack")
 
 # Encoder operand modes (include/molnextr_hip.h MNX_DTYPE_*). "fp16x3" — split fp16 operands, three MFMA terms per
 # product, fp32-class results — is the default: it is the fastest mode whose results stay a factor of four inside north_star's
@@ -133,6 +133,10 @@ NOTE_H_MASK, NOTE_AROMATIZED, NOTE_UNBRACKETED, NOTE_COPIED = 15, 16, 32, 64
 # FORMULA_DEFAULT_STEPS is what max_steps = 0 stands for
 MOL_FORMULA_EXPANDED, MOL_FORMULA_LEFT, MOL_FORMULA_LIMIT, MOL_FORMULA_REFUSED = 1 << 10, 1 << 11, 1 << 16, 1 << 17
 FORMULA_DEFAULT_STEPS = 4096
+# mnx_mol.flags of mnx_main_pack's output: the molecule had more than one component and atoms were dropped; another component had
+# as many atoms as the kept one (the choice rests on the atom numbering, as the reference's); the molecule was refused (records
+# beyond the tables, a bond to no atom of the molecule, more than 2047 atoms): no records
+MOL_MAIN_KEPT, MOL_MAIN_TIE, MOL_MAIN_REFUSED = 1 << 18, 1 << 19, 1 << 20
 MOLFILE_DTYPE = np.dtype([("text0", "<u4"), ("len", "<u4"), ("flags", "<u4"), ("reserved", "<u4")], align=True)
 # mnx_molfile.flags (MNX_MOLFILE_*): no molfile (len 0) for more than 999 atoms / bonds or records beyond the tables passed;
 # the molecule holds a pseudo-atom (R-group, abbreviation, unparsable symbol); a copy of MOL_TRUNCATED
@@ -319,6 +323,8 @@ def load_library():
     lib.mnx_kekulize_pack.argtypes = lib.mnx_expand_pack.argtypes[:-1] + [C.c_uint32, lib.mnx_expand_pack.argtypes[-1]]
     lib.mnx_formula_pack.restype = C.c_int                              # expand's arguments, max_steps in front of stream
     lib.mnx_formula_pack.argtypes = lib.mnx_kekulize_pack.argtypes
+    lib.mnx_main_pack.restype = C.c_int
+    lib.mnx_main_pack.argtypes = lib.mnx_expand_pack.argtypes           # expand's arguments exactly
     lib.mnx_smiles_read.restype = C.c_int
     lib.mnx_smiles_read.argtypes = [vp, vp, C.c_uint32, vp, i32, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp]
     lib.mnx_atom_scan.restype = C.c_int
@@ -1184,6 +1190,25 @@ class Engine:
         MOL_FORMULA_REFUSED. max_steps: the placements one label's search may try (0: FORMULA_DEFAULT_STEPS). Sizes itself as
         expand_pack does; keep_device: also 'device', as graph_pack."""
         return self._grow_pack("mnx_formula_pack", rec, caps, keep_device, (int(max_steps),))
+
+    def main_pack(self, rec: dict, caps=None, keep_device: bool = False) -> dict:
+        """graph_pack's records (or expand_pack's, or smiles_read's) -> of every molecule the connected component with the most
+        atoms, among equals the one with the lowest atom, every other atom and its bonds dropped (mnx_main_pack; the rule: the
+        reference's _keep_main_molecule, include/molnextr_hip.h): a dict with graph_pack's keys — 'mols', 'atoms', 'bonds',
+        'text', 'totals' — plus 'origin' uint16 [atoms], the input index of every kept atom. 'text' is the kept atoms' symbols
+        behind one another, as expand_pack's; mols['flags'] carries MOL_MAIN_KEPT / MOL_MAIN_TIE / MOL_MAIN_REFUSED. Run it
+        behind expand_pack, so that a label counts with the atoms it stands for, and in front of kekulize_pack. Sized from the
+        input — nothing grows — or caps = (atom_cap, bond_cap, text_cap), then once more with the sizes `totals` reports.
+        keep_device: also 'device', as graph_pack."""
+        dev = torch.device("cuda", self.device)
+        tables, args = self._packed_tables(rec)
+        if caps is None:
+            caps = (len(rec["atoms"]), len(rec["bonds"]), len(rec["text"]))
+        out = self._sized_tables("mnx_main_pack", len(rec["mols"]), caps,
+                                 lambda mols, arenas, totals, origin: self.lib.mnx_main_pack(self.h, *args, mols, *arenas, origin, totals, _stream()),
+                                 dev, keep_device, side=torch.int16)
+        out["origin"] = out.pop("side").cpu().numpy().view(np.uint16)
+        return out
 
     def _respell_pack(self, fn: str, rec: dict, caps, keep_device: bool, tail=()) -> dict:
         """normalize_pack and kekulize_pack: lib.<fn>(h, tables, mols_out, arenas, atom_notes, totals, *tail, stream) from the

@@ -210,7 +210,7 @@ def write_predictions(save_path: str, file_name: str, table: Dict[str, list], sc
 
 
 def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: int = 512, normalize: bool = False,
-                       kekulize: bool = False, formula: bool = False) -> Dict[str, float]:
+                       kekulize: bool = False, formula: bool = False, keep_main: bool = False) -> Dict[str, float]:
     """--graph_match: the share of items whose prediction and gold string are the same graph as THIS library's canonical SMILES
     sees it (marks 0: no stereo), on the device. records: the gathered dense records in dataset order (shard.pack_records
     layout), re-uploaded in chunks -> graph_pack -> mnx_smiles_pack_canonical; gold -> mnx_smiles_read -> the same writer. A
@@ -230,7 +230,12 @@ def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: 
     are ranked then, so that a predicted label 'CH2CH3' or 'COOCH3' equals a gold string that draws the group out,
     and a gold [Et] equals a predicted 'C2H5'. The other scores stay as they are. NOT the reference's RDKit `graph` score: the
     structure of a formula is this library's own repaired search, not the reference's RDKit bookkeeping, nothing normalises or
-    kekulises here, stereo is dropped, and no toolkit has parsed the result."""
+    kekulises here, stereo is dropped, and no toolkit has parsed the result.
+    keep_main (--graph_keep_main): adds graph_match_main — the prediction goes graph_pack -> mnx_main_pack -> the canonical
+    writer, so only its connected component with the most atoms (among equals the one with the lowest atom) is compared; the
+    gold side is left as read, as in the reference, whose --keep_main trims predictions only. The other scores stay as they
+    are. Only the component rule is the reference's (_keep_main_molecule): the comparison is still this
+    project's canonical string and NOT the reference's RDKit `graph` score."""
     from .engine import READ_REFUSED, SMILES_REFUSED
     from .shard import MAX_LEN
     kmax = engine.max_atoms
@@ -242,7 +247,7 @@ def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: 
         recs, _, data, _, _ = engine.smiles_pack(rec, canonical=True)
         return [None if int(r["flags"]) & SMILES_REFUSED else data[int(r["text0"]):int(r["text0"]) + int(r["len"])] for r in recs]
 
-    equal = equal_normalized = equal_kekulized = equal_formula = unreadable = refused = 0
+    equal = equal_normalized = equal_kekulized = equal_formula = equal_main = unreadable = refused = 0
     for c0 in range(0, len(gold), chunk):
         rows = torch.from_numpy(np.ascontiguousarray(records[c0:c0 + chunk])).to(dev)
         n = rows.shape[0]
@@ -253,7 +258,7 @@ def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: 
         packed = engine.graph_pack(out, keep_device=True)
         pred = texts(packed)
         read = engine.smiles_read(gold[c0:c0 + chunk], keep_device=True)
-        want = texts(read)
+        want = want_read = texts(read)
         for p, w, r in zip(pred, want, read["read"]):
             bad = bool(int(r["flags"]) & READ_REFUSED)
             unreadable += bad
@@ -272,6 +277,10 @@ def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: 
             pred, want = (texts(engine.expand_pack(engine.formula_pack(side, keep_device=True), keep_device=True)) for side in (packed, read))
             for p, w, r in zip(pred, want, read["read"]):
                 equal_formula += not int(r["flags"]) & READ_REFUSED and p is not None and w is not None and p == w
+        if keep_main:
+            pred = texts(engine.main_pack(packed, keep_device=True))
+            for p, w, r in zip(pred, want_read, read["read"]):
+                equal_main += not int(r["flags"]) & READ_REFUSED and p is not None and w is not None and p == w
     scores = {"graph_match_device": equal / len(gold) if gold else 0.0, "gold_unreadable": int(unreadable), "pred_refused": int(refused)}
     if normalize:
         scores["graph_match_normalized"] = equal_normalized / len(gold) if gold else 0.0
@@ -279,6 +288,8 @@ def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: 
         scores["graph_match_kekulized"] = equal_kekulized / len(gold) if gold else 0.0
     if formula:
         scores["graph_match_formula"] = equal_formula / len(gold) if gold else 0.0
+    if keep_main:
+        scores["graph_match_main"] = equal_main / len(gold) if gold else 0.0
     return scores
 
 
@@ -330,6 +341,12 @@ def build_parser() -> argparse.ArgumentParser:
                          "equals the group drawn out (DESIGN 4.22). The other scores stay as they are. It is NOT the reference's "
                          "`graph` score: the structure of a formula is this library's own repaired valence search, not the "
                          "reference's RDKit bookkeeping, and no toolkit has parsed the result")
+    ap.add_argument("--graph_keep_main", action="store_true",
+                    help="opt-in, with --graph_match: add graph_match_main, the same comparison with the PREDICTION passed through "
+                         "mnx_main_pack first, so that only its connected component with the most atoms is compared (DESIGN 4.24); "
+                         "the gold side is left as read, as the reference's --keep_main trims predictions only. The other scores "
+                         "stay as they are. Only the component rule is the reference's: the comparison is this project's canonical "
+                         "string, NOT the reference's RDKit `graph` score")
     return ap
 
 
@@ -349,6 +366,8 @@ def main(argv=None):
         ap.error("--graph_kekulize adds a score to --graph_match")
     if args.graph_formula and not args.graph_match:
         ap.error("--graph_formula adds a score to --graph_match")
+    if args.graph_keep_main and not args.graph_match:
+        ap.error("--graph_keep_main adds a score to --graph_match")
     dtype = args.dtype or ("fp16" if args.fp16 else DEFAULT_DTYPE)
     max_batch = max(64, 2 * args.batch_size)          # one reference batch is encoded in one launch group
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -398,7 +417,8 @@ def main(argv=None):
             scores = smiles_scores(df["SMILES"], table["SMILES"]) if "SMILES" in df.columns else None
             if args.graph_match:
                 scores.update(graph_match_scores(engine, kept["records"], list(df["SMILES"]), normalize=args.graph_normalize,
-                                                 kekulize=args.graph_kekulize, **({"formula": True} if args.graph_formula else {})))
+                                                 kekulize=args.graph_kekulize, **({"formula": True} if args.graph_formula else {}),
+                                                 **({"keep_main": True} if args.graph_keep_main else {})))
         print(write_predictions(args.save_path, args.test_file, table, scores), json.dumps(scores))
     if world > 1:
         dist.barrier()

@@ -145,7 +145,7 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
                      labels=None, free_run=False, packed: bool = False, molfile: bool = False,
                      molfile_scale=None, smiles: bool = False, stereo: bool = False, double_bonds: bool = False,
                      canonical: bool = False, expand: bool = False, symmetry: bool = False, normalize: bool = False,
-                     kekulize: bool = False, formula: bool = False) -> List[dict]:
+                     kekulize: bool = False, formula: bool = False, keep_main: bool = False) -> List[dict]:
     """Encoder + Decoder.decode for MANY images through the engine's continuous-batching path (mnx_predict):
     same per-image dicts as `decode_batch`, identical results (the on-device atom scan equals
     sequence_to_smiles' indices), much higher throughput. compute_confidence=True: mnx_predict_confidence, the same
@@ -212,10 +212,20 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
     = {'symbols', 'coords', 'bonds', 'origin', 'flags' (MOL_FORMULA_EXPANDED / MOL_FORMULA_LEFT / MOL_FORMULA_LIMIT of
     engine.py), 'replaced' (the predicted atoms whose label was replaced), 'left' (the predicted atoms that were candidates and
     stayed)}, the molecule as it left that pass; expanded['origin'] still names the PREDICTED atom. Without expand the per-atom
-    lists of the writers have one entry per atom of formula['symbols']."""
+    lists of the writers have one entry per atom of formula['symbols'].
+    keep_main (packed only; behind expand and in front of kekulize): of every molecule the connected component with the most atoms
+    stays — among equals the one with the lowest atom — and every other atom and its bonds are dropped on the device before
+    anything else runs on the molecule (mnx_main_pack; the rule is the reference's _keep_main_molecule: salts, counter-ions and
+    stray atoms go; behind expand, so that a label counts with the atoms it stands for). 'molfile' and 'graph_smiles' then
+    describe the main molecule, and every dict gains 'main' = {'symbols', 'coords', 'bonds', 'origin' (per kept atom, its index
+    in the molecule the pass received: expanded['symbols'] with expand, else formula['symbols'] with formula, else the predicted
+    atoms), 'flags' (MOL_MAIN_KEPT / MOL_MAIN_TIE of engine.py)}; the per-atom lists of the writers have one entry per atom of
+    main['symbols']. The predicted atoms and bonds ('chartok_coords', 'bonds') are what they are without it."""
     tok = (tokenizer or get_tokenizer())["chartok_coords"]
     if formula and not packed:
         raise ValueError("formula=True needs packed=True: the labels are replaced in the packed tables")
+    if keep_main and not packed:
+        raise ValueError("keep_main=True needs packed=True: the atoms are dropped from the packed tables")
     if normalize and not packed:
         raise ValueError("normalize=True needs packed=True: the atoms are respelled in the packed tables")
     if kekulize and not packed:
@@ -253,10 +263,12 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
             raise RuntimeError(f"a molecule has more atoms than the engine capacity max_atoms={engine.max_atoms}")
         drawn = rec                                                      # what the predicted atoms and bonds are read from
         if formula:
-            rec = formula_rec = engine.formula_pack(drawn, keep_device=molfile or smiles or normalize or kekulize or expand)
+            rec = formula_rec = engine.formula_pack(drawn, keep_device=molfile or smiles or normalize or kekulize or expand or keep_main)
         if expand:
-            rec = engine.expand_pack(rec, keep_device=molfile or smiles or normalize or kekulize)     # what the writers read
+            rec = engine.expand_pack(rec, keep_device=molfile or smiles or normalize or kekulize or keep_main)     # what the writers read
         grown_rec = rec
+        if keep_main:
+            rec = main_rec = engine.main_pack(rec, keep_device=molfile or smiles or normalize or kekulize)
         if kekulize:
             rec = kekule_rec = engine.kekulize_pack(rec, keep_device=molfile or smiles or normalize)
         if normalize:
@@ -265,10 +277,10 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
                                     **({"symmetry": True} if symmetry else {})) if canonical else None
         per_atom = {"rank": ranked[3], "sym_class": ranked[4]} if canonical else {}
         preds = unpack_graphs(drawn["mols"], drawn["atoms"], drawn["bonds"], drawn["text"], tok.maxx, compute_confidence,
-                              **({} if expand or formula else per_atom))
+                              **({} if expand or formula or keep_main else per_atom))
         if formula:
             found = unpack_graphs(formula_rec["mols"], formula_rec["atoms"], formula_rec["bonds"], formula_rec["text"], tok.maxx,
-                                  compute_confidence, **({} if expand else per_atom))
+                                  compute_confidence, **({} if expand or keep_main else per_atom))
             for p, g, m in zip(preds, found, formula_rec["mols"]):
                 a0, na = int(m["atom0"]), int(m["n_atoms"])
                 before, after = p["chartok_coords"]["symbols"], g["chartok_coords"]["symbols"]
@@ -282,7 +294,7 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
                         p[key] = g[key]
         if expand:
             grown = unpack_graphs(grown_rec["mols"], grown_rec["atoms"], grown_rec["bonds"], grown_rec["text"], tok.maxx,
-                                  compute_confidence, **per_atom)
+                                  compute_confidence, **({} if keep_main else per_atom))
             for p, g, m in zip(preds, grown, grown_rec["mols"]):
                 a0, na = int(m["atom0"]), int(m["n_atoms"])
                 origin = grown_rec["origin"][a0:a0 + na].tolist()
@@ -290,6 +302,16 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
                     origin = [p["formula"]["origin"][k] for k in origin]
                 p["expanded"] = {"symbols": g["chartok_coords"]["symbols"], "coords": g["chartok_coords"]["coords"],
                                  "bonds": g["bonds"], "origin": origin, "flags": int(m["flags"])}
+                for key in ("canonical_rank", "symmetry_class"):
+                    if key in g:
+                        p[key] = g[key]
+        if keep_main:
+            kept = unpack_graphs(main_rec["mols"], main_rec["atoms"], main_rec["bonds"], main_rec["text"], tok.maxx,
+                                 compute_confidence, **per_atom)
+            for p, g, m in zip(preds, kept, main_rec["mols"]):
+                a0, na = int(m["atom0"]), int(m["n_atoms"])
+                p["main"] = {"symbols": g["chartok_coords"]["symbols"], "coords": g["chartok_coords"]["coords"],
+                             "bonds": g["bonds"], "origin": main_rec["origin"][a0:a0 + na].tolist(), "flags": int(m["flags"])}
                 for key in ("canonical_rank", "symmetry_class"):
                     if key in g:
                         p[key] = g[key]
@@ -355,7 +377,7 @@ def formula_candidate(symbol: str) -> bool:
 
 
 def canonical_smiles(engine: Engine, smiles_list, expand: bool = False, normalize: bool = False, kekulize: bool = False,
-                     formula: bool = False) -> List[dict]:
+                     formula: bool = False, keep_main: bool = False) -> List[dict]:
     """A caller's own SMILES in the form the device writes predictions in: mnx_smiles_read, optionally mnx_expand_pack ([Ph],
     [OMe], ... replaced by their atoms), then mnx_smiles_pack_canonical without marks. Per item {'smiles': the canonical string,
     None where the reader or the writer refused; 'read_flags' (engine.READ_*), 'err_pos' (of READ_SYNTAX), 'smiles_flags'
@@ -369,7 +391,10 @@ def canonical_smiles(engine: Engine, smiles_list, expand: bool = False, normaliz
     and without it azulene and its aromatic form do; the items gain 'kekulize_flags' (engine.MOL_KEKULIZED / ...).
     formula: mnx_formula_pack in front of the expansion — a condensed-formula atom such as [CH2CH3] or [N(CH3)2] is replaced by
     the atoms a valence search finds for it (this library's own rule; combine with expand for the group tokens a formula
-    holds); the items gain 'formula_flags' (engine.MOL_FORMULA_EXPANDED / ...)."""
+    holds); the items gain 'formula_flags' (engine.MOL_FORMULA_EXPANDED / ...).
+    keep_main: mnx_main_pack behind the expansion and in front of kekulize — only the connected component with the most atoms is
+    written, among equals the one with the lowest atom (the reference's _keep_main_molecule: 'CCO.[Na+]' is written as 'CCO'
+    is); the items gain 'main_flags' (engine.MOL_MAIN_KEPT / MOL_MAIN_TIE)."""
     from .engine import READ_REFUSED, SMILES_REFUSED
     smiles_list = list(smiles_list)
     if not smiles_list:
@@ -381,6 +406,9 @@ def canonical_smiles(engine: Engine, smiles_list, expand: bool = False, normaliz
     formula_flags = rec["mols"]["flags"]
     if expand:
         rec = engine.expand_pack(rec, keep_device=True)
+    if keep_main:
+        rec = engine.main_pack(rec, keep_device=True)
+    main_flags = rec["mols"]["flags"]
     if kekulize:
         rec = engine.kekulize_pack(rec, keep_device=True)
     kekulize_flags = rec["mols"]["flags"]
@@ -388,7 +416,7 @@ def canonical_smiles(engine: Engine, smiles_list, expand: bool = False, normaliz
         rec = engine.normalize_pack(rec, keep_device=True)
     recs, _, data, _, _ = engine.smiles_pack(rec, canonical=True)
     out = []
-    for r, w, m, kf, ff in zip(read, recs, rec["mols"], kekulize_flags, formula_flags):
+    for r, w, m, kf, ff, mf in zip(read, recs, rec["mols"], kekulize_flags, formula_flags, main_flags):
         ok = not (int(r["flags"]) & READ_REFUSED or int(w["flags"]) & SMILES_REFUSED)
         out.append({"smiles": data[int(w["text0"]):int(w["text0"]) + int(w["len"])].decode("utf-8", "replace") if ok else None,
                     "read_flags": int(r["flags"]), "err_pos": int(r["err_pos"]), "smiles_flags": int(w["flags"])})
@@ -398,6 +426,8 @@ def canonical_smiles(engine: Engine, smiles_list, expand: bool = False, normaliz
             out[-1]["kekulize_flags"] = int(kf)
         if formula:
             out[-1]["formula_flags"] = int(ff)
+        if keep_main:
+            out[-1]["main_flags"] = int(mf)
     return out
 
 
@@ -473,7 +503,12 @@ class molnextr:
     valence-guided search finds for it before anything is written (mnx_formula_pack), and every output dict gains 'formula'
     (symbols, coords, bonds, origin, flags, and 'replaced' / 'left': the predicted atoms whose label was replaced / stayed). This
     library's own repair of the reference's search: no toolkit has parsed the result, rings, charges, explicit bonds and
-    two-ended labels stay labels; combine with graph_expand for the group tokens a formula holds ('Ph' in 'CH2Ph')."""
+    two-ended labels stay labels; combine with graph_expand for the group tokens a formula holds ('Ph' in 'CH2Ph').
+    graph_keep_main: True (opt-in, default False; needs graph_smiles or graph_molfile; behind graph_expand, in front of
+    graph_kekulize) = only the connected component with the most atoms is written, among equals the one with the lowest atom
+    (mnx_main_pack: the reference's _keep_main_molecule — salts, counter-ions and stray atoms are dropped), and every output
+    dict gains 'main_atoms', the kept atoms' indices in the molecule the pass received (expanded['symbols'] with graph_expand,
+    atom_sets without), and 'main' (symbols, coords, bonds, origin, flags). The per-atom lists then follow main['symbols']."""
 
     image_format = "fp32"
     packed_results = False
@@ -487,13 +522,14 @@ class molnextr:
     graph_normalize = False
     graph_kekulize = False
     graph_formula = False
+    graph_keep_main = False
 
     def __init__(self, model_path, device=None, max_batch: int = 32, dtype: str = DEFAULT_DTYPE,
                  device_preprocess: bool = True, image_format: str = "fp32", packed_results: bool = False,
                  graph_molfile: bool = False, graph_smiles: bool = False, graph_stereo: bool = False,
                  graph_double_bonds: bool = False, graph_canonical: bool = False, graph_expand: bool = False,
                  graph_symmetry: bool = False, graph_normalize: bool = False, graph_kekulize: bool = False,
-                 graph_formula: bool = False):
+                 graph_formula: bool = False, graph_keep_main: bool = False):
         if model_path is None:
             raise ValueError("molnextr(model_path): a checkpoint path is required (pass 'synthetic' explicitly for the "
                              "deterministic test checkpoint)")
@@ -542,6 +578,9 @@ class molnextr:
         self.graph_formula = bool(graph_formula)
         if self.graph_formula and not (self.graph_smiles or self.graph_molfile):
             raise ValueError("graph_formula=True needs graph_smiles=True or graph_molfile=True: the molecule with its formulas replaced is what they write")
+        self.graph_keep_main = bool(graph_keep_main)
+        if self.graph_keep_main and not (self.graph_smiles or self.graph_molfile):
+            raise ValueError("graph_keep_main=True needs graph_smiles=True or graph_molfile=True: the main molecule is what they write")
         self.engine = Engine(states["encoder"], states["decoder"], device=device.index or 0, max_batch=max_batch,
                              dtype=dtype, image_format=image_format)
         self.input_size = args.input_size
@@ -549,11 +588,11 @@ class molnextr:
         self.group_images = 1024          # images per engine call of the throughput path (whole reference batches)
 
     def canonical_smiles(self, smiles_list, expand: bool = False, normalize: bool = False, kekulize: bool = False,
-                         formula: bool = False) -> List[dict]:
+                         formula: bool = False, keep_main: bool = False) -> List[dict]:
         """The canonical graph SMILES of the caller's own strings, for comparison with 'predicted_smiles' of graph_canonical=True
         (model.canonical_smiles: read on the device, optionally expanded and normalised, written without marks)."""
         return canonical_smiles(self.engine, smiles_list, expand=expand, normalize=normalize, kekulize=kekulize,
-                                **({"formula": True} if formula else {}))
+                                **({"formula": True} if formula else {}), **({"keep_main": True} if keep_main else {}))
 
     _groups_done = 0          # groups of the running predict_images call that have produced predictions
 
@@ -743,6 +782,8 @@ class molnextr:
             conf["kekulize"] = True
         if self.graph_formula:
             conf["formula"] = True
+        if self.graph_keep_main:
+            conf["keep_main"] = True
         gen = self._prefetched(groups)
         try:
             for x in gen:
@@ -798,6 +839,8 @@ class molnextr:
                 d["kekulized"] = pred["kekulized"]
             if "formula" in pred:                             # graph_formula: the molecule as it left mnx_formula_pack
                 d["formula"] = pred["formula"]
+            if "main" in pred:                                # graph_keep_main: the main molecule and where its atoms came from
+                d["main_atoms"], d["main"] = pred["main"]["origin"], pred["main"]
             if return_atoms_bonds:
                 c = pred["chartok_coords"]
                 atoms = []

@@ -50,10 +50,12 @@ class MolNexTRSingleton:
         cls._device_name = f"ROCm GPU: {torch.cuda.get_device_name(cls._device)}"
 
 
-def canonical_smiles(smiles_list, expand: bool = False, normalize: bool = False, kekulize: bool = False):
+def canonical_smiles(smiles_list, expand: bool = False, normalize: bool = False, kekulize: bool = False, keep_main: bool = False):
     """The caller's own SMILES in the canonical form the device writes (no reference counterpart; model.canonical_smiles): per
-    item {'smiles' (None where refused), 'read_flags', 'err_pos', 'smiles_flags'}. Not a toolkit's canonical SMILES."""
-    return MolNexTRSingleton.get_instance().canonical_smiles(smiles_list, expand=expand, normalize=normalize, kekulize=kekulize)
+    item {'smiles' (None where refused), 'read_flags', 'err_pos', 'smiles_flags'}. Not a toolkit's canonical SMILES.
+    keep_main: only the largest connected component is written (the reference's _keep_main_molecule)."""
+    return MolNexTRSingleton.get_instance().canonical_smiles(smiles_list, expand=expand, normalize=normalize, kekulize=kekulize,
+                                                             **({"keep_main": True} if keep_main else {}))
 
 
 def get_predictions(imagepath: str, atoms_bonds: bool = False, smiles: bool = True, predicted_molfile: bool = False):

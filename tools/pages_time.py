@@ -41,6 +41,9 @@ is part of the product path and no number is asserted.
     as they came — on the synthetic checkpoint's predictions (near-complete graphs), on hand-made molecules of drug-like size
     with aromatic rings, and on those with the rings in Kekule form; and mnx_kekulize_pack, the inverse pass, on the same tables
     at the default step limit and at a limit of one step; `--normalize-out FILE` writes the table to a file of its own.
+(k) (only when asked for: --part k) the main molecule on the device: mnx_main_pack alone, against mnx_expand_pack on the same
+    tables (the neighbouring pass of the same three-launch shape), on the drug-like tables of part x and on those with every fifth
+    bond record taken out, so that most molecules fall apart; `--main-out FILE` writes the table to a file of its own.
 The variants of a part alternate inside every repeat (A B A B ...), the table reports the median and the min .. max spread of
 each, and the spread of the fp32 path against itself is the yardstick for "not slower".
 """
@@ -787,6 +790,77 @@ def part_f(repeats, lines):
     eng.close()
 
 
+def part_k(repeats, lines):
+    """The main molecule on the device: one mnx_main_pack call (three launches) between two events, alternating with one
+    mnx_expand_pack call on the same input tables. Every output buffer has the exact size; the tables stay on the device."""
+    import ctypes as C
+    from molnextr_amd import engine as E
+    dev = torch.device("cuda", 0)
+    ck = W.synthetic_checkpoint(0)
+    eng = Engine(ck["encoder"], ck["decoder"], device=0, max_batch=2)
+    ptr = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
+    stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)      # noqa: E731
+    buf = lambda k: torch.empty(max(int(k), 1), dtype=torch.uint8, device=dev)      # noqa: E731
+
+    def measure(rec, what):
+        tables, args = eng._packed_tables(rec)
+        n = len(rec["mols"])
+        out = {"x": eng.expand_pack(rec), "k": eng.main_pack(rec)}
+        sizes = {k: (len(r["atoms"]), len(r["bonds"]), len(r["text"])) for k, r in out.items()}
+        mols_d, totals_d = buf(n * 40), torch.zeros(4, dtype=torch.int32, device=dev)
+        tab = {k: (buf(v[0] * 24), buf(v[1] * 16), buf(v[2])) for k, v in sizes.items()}
+        origin_d = torch.empty(max(max(v[0] for v in sizes.values()), 1), dtype=torch.int16, device=dev)
+
+        def table_pass(fn, k):
+            a, b, t = tab[k]
+            return fn(eng.h, *args, ptr(mols_d), ptr(a), sizes[k][0], ptr(b), sizes[k][1], ptr(t), sizes[k][2], ptr(origin_d), ptr(totals_d),
+                      stream())
+
+        calls = {"mnx_expand_pack": lambda: table_pass(eng.lib.mnx_expand_pack, "x"),
+                 "mnx_main_pack": lambda: table_pass(eng.lib.mnx_main_pack, "k")}
+        us = {k: [] for k in calls}
+        for i in range(repeats + 3):
+            for k, call in calls.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                a.record()
+                rc = call()
+                b.record()
+                torch.cuda.synchronize()
+                assert rc == 0 and not int(totals_d[3]), k
+                if i >= 3:
+                    us[k].append(a.elapsed_time(b) * 1000.0)
+        assert tab["k"][0][:sizes["k"][0] * 24].cpu().numpy().tobytes() == out["k"]["atoms"].tobytes()
+        assert tab["k"][1][:sizes["k"][1] * 16].cpu().numpy().tobytes() == out["k"]["bonds"].tobytes()
+        flags = out["k"]["mols"]["flags"]
+        lines.append(f"(k) one call over {n} {what}: {len(rec['atoms'])} atoms, {len(rec['bonds'])} bonds -> {sizes['k'][0]} atoms, "
+                     f"{sizes['k'][1]} bonds; atoms dropped in {int((flags & E.MOL_MAIN_KEPT != 0).sum())} molecules, a tie in "
+                     f"{int((flags & E.MOL_MAIN_TIE != 0).sum())}, refused {int((flags & E.MOL_MAIN_REFUSED != 0).sum())}")
+        lines.append("  device us between two events around the launches, the two alternating   median [min .. max]")
+        for k in us:
+            lines.append(f"  {k:24s} {fmt(us[k])} us")
+        lines.append(f"  main / expand, median {statistics.median(us['mnx_main_pack']) / statistics.median(us['mnx_expand_pack']):.2f}")
+
+    def thinned(mols, atoms, bonds, text, every=5):
+        """the same tables without every fifth bond record of a molecule: most molecules fall into several components"""
+        mols, keep = mols.copy(), np.ones(len(bonds), bool)
+        for m in mols:
+            keep[int(m["bond0"]) + every - 1:int(m["bond0"]) + int(m["n_bonds"]):every] = False
+        at = np.concatenate([[0], np.cumsum(keep)])
+        first, last = mols["bond0"].astype(np.int64), mols["bond0"].astype(np.int64) + mols["n_bonds"]
+        mols["bond0"], mols["n_bonds"] = at[first], at[last] - at[first]
+        return mols, atoms, bonds[keep], text
+
+    for labels, thin, what in ((False, False, "hand-made molecules of drug-like size (one component: the pass copies)"),
+                               (True, False, "hand-made molecules of drug-like size with a table label at every ninth atom"),
+                               (False, True, "hand-made molecules of drug-like size without every fifth bond record")):
+        mols, atoms, bonds, text = druglike_records(1024, labels=labels)
+        if thin:
+            mols, atoms, bonds, text = thinned(mols, atoms, bonds, text)
+        measure({"mols": mols, "atoms": atoms, "bonds": bonds, "text": text}, what)
+    eng.close()
+
+
 def part_r(repeats, lines):
     """SMILES read on the device: one mnx_smiles_read call (three launches) over the strings of 1024 hand-made molecules of
     drug-like size between two events, alternating with the one mnx_smiles_pack call that writes those strings from the packed
@@ -904,6 +978,7 @@ def main():
     ap.add_argument("--read-out", default=None, help="write the table of part r to this file")
     ap.add_argument("--normalize-out", default=None, help="write the table of part n to this file")
     ap.add_argument("--formula-out", default=None, help="write the table of part f to this file")
+    ap.add_argument("--main-out", default=None, help="write the table of part k to this file")
     ap.add_argument("--pack-only", type=int, default=0, help="run this many mnx_graph_pack calls over 1024 images and exit")
     args = ap.parse_args()
     parts = args.part.split(",")
@@ -972,6 +1047,13 @@ def main():
         if args.formula_out:
             os.makedirs(os.path.dirname(os.path.abspath(args.formula_out)), exist_ok=True)
             with open(args.formula_out, "w") as f:
+                f.write("\n".join([lines[0]] + lines[first:]) + "\n")
+    if "k" in parts:
+        first = len(lines)
+        part_k(args.repeats, lines)
+        if args.main_out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.main_out)), exist_ok=True)
+            with open(args.main_out, "w") as f:
                 f.write("\n".join([lines[0]] + lines[first:]) + "\n")
     text = "\n".join(lines)
     print(text)
