@@ -1156,18 +1156,24 @@ class Engine:
         data = self._sized_text(fn, args + [_ptr(recs), _ptr(order)], int(cap) if cap is not None else n * self.SMILES_GUESS, tail)
         return recs.cpu().numpy().view(SMILES_DTYPE), order[:na].cpu().numpy().view(np.uint16), data
 
-    def _grow_pack(self, fn: str, rec: dict, caps, keep_device: bool, tail=()) -> dict:
-        """expand_pack and formula_pack: lib.<fn>(h, tables, mols_out, arenas, origin, totals, *tail, stream) from the input's
-        sizes plus room for a label of about ten atoms per molecule, or caps, with 'origin' uint16 [atoms]"""
+    # margin, side, key of _tables_pass for the three frames of a pass: one that grows a molecule (room for a label of about ten
+    # atoms), one that selects atoms (nothing grows), one that respells them (a new symbol is rarely longer than the old one)
+    GROWS, SELECTS, RESPELLS = ((12, 12, 16), torch.int16, "origin"), ((0, 0, 0), torch.int16, "origin"), ((0, 0, 2), torch.uint8, "atom_notes")
+
+    def _tables_pass(self, fn: str, rec: dict, caps, keep_device: bool, margin, side, key: str, tail=()) -> dict:
+        """The five passes from tables to tables: lib.<fn>(h, tables, mols_out, arenas, per_atom, totals, *tail, stream) from the
+        input's sizes plus margin = (atoms, bonds, text bytes) per molecule, or caps. side, key: the per-atom output's torch dtype
+        and its key in the result — int16 -> 'origin' as uint16 [atoms], uint8 -> 'atom_notes'."""
         dev = torch.device("cuda", self.device)
         n = len(rec["mols"])
         tables, args = self._packed_tables(rec)
         if caps is None:
-            caps = (len(rec["atoms"]) + 12 * n, len(rec["bonds"]) + 12 * n, len(rec["text"]) + 16 * n)
+            caps = tuple(len(rec[k]) + m * n for k, m in zip(("atoms", "bonds", "text"), margin))
         out = self._sized_tables(fn, n, caps,
-                                 lambda mols, arenas, totals, origin: getattr(self.lib, fn)(self.h, *args, mols, *arenas, origin, totals, *tail, _stream()),
-                                 dev, keep_device, side=torch.int16)
-        out["origin"] = out.pop("side").cpu().numpy().view(np.uint16)
+                                 lambda mols, arenas, totals, per_atom: getattr(self.lib, fn)(self.h, *args, mols, *arenas, per_atom, totals, *tail, _stream()),
+                                 dev, keep_device, side=side)
+        per_atom = out.pop("side").cpu().numpy()
+        out[key] = per_atom.view(np.uint16) if side == torch.int16 else per_atom
         return out
 
     def expand_pack(self, rec: dict, caps=None, keep_device: bool = False) -> dict:
@@ -1178,7 +1184,7 @@ class Engine:
         the atoms of a fragment share the label's coordinates; mols['flags'] carries MOL_EXPANDED / MOL_LABEL_LEFT /
         MOL_EXPAND_REFUSED. Starts from the input's sizes plus a margin (or caps = (atom_cap, bond_cap, text_cap)) and repeats
         at most once with the sizes `totals` reports. keep_device: also 'device', as graph_pack."""
-        return self._grow_pack("mnx_expand_pack", rec, caps, keep_device)
+        return self._tables_pass("mnx_expand_pack", rec, caps, keep_device, *self.GROWS)
 
     def formula_pack(self, rec: dict, caps=None, keep_device: bool = False, max_steps: int = 0) -> dict:
         """graph_pack's records (or smiles_read's) -> the same molecules with every condensed-formula label ('CH2CH3', 'N(CH3)2',
@@ -1189,7 +1195,7 @@ class Engine:
         'totals', 'origin' —; mols['flags'] carries MOL_FORMULA_EXPANDED / MOL_FORMULA_LEFT / MOL_FORMULA_LIMIT /
         MOL_FORMULA_REFUSED. max_steps: the placements one label's search may try (0: FORMULA_DEFAULT_STEPS). Sizes itself as
         expand_pack does; keep_device: also 'device', as graph_pack."""
-        return self._grow_pack("mnx_formula_pack", rec, caps, keep_device, (int(max_steps),))
+        return self._tables_pass("mnx_formula_pack", rec, caps, keep_device, *self.GROWS, (int(max_steps),))
 
     def main_pack(self, rec: dict, caps=None, keep_device: bool = False) -> dict:
         """graph_pack's records (or expand_pack's, or smiles_read's) -> of every molecule the connected component with the most
@@ -1200,29 +1206,7 @@ class Engine:
         behind expand_pack, so that a label counts with the atoms it stands for, and in front of kekulize_pack. Sized from the
         input — nothing grows — or caps = (atom_cap, bond_cap, text_cap), then once more with the sizes `totals` reports.
         keep_device: also 'device', as graph_pack."""
-        dev = torch.device("cuda", self.device)
-        tables, args = self._packed_tables(rec)
-        if caps is None:
-            caps = (len(rec["atoms"]), len(rec["bonds"]), len(rec["text"]))
-        out = self._sized_tables("mnx_main_pack", len(rec["mols"]), caps,
-                                 lambda mols, arenas, totals, origin: self.lib.mnx_main_pack(self.h, *args, mols, *arenas, origin, totals, _stream()),
-                                 dev, keep_device, side=torch.int16)
-        out["origin"] = out.pop("side").cpu().numpy().view(np.uint16)
-        return out
-
-    def _respell_pack(self, fn: str, rec: dict, caps, keep_device: bool, tail=()) -> dict:
-        """normalize_pack and kekulize_pack: lib.<fn>(h, tables, mols_out, arenas, atom_notes, totals, *tail, stream) from the
-        input's sizes — a new symbol is rarely longer than the old one — or caps, with 'atom_notes' uint8 [atoms]"""
-        dev = torch.device("cuda", self.device)
-        n = len(rec["mols"])
-        tables, args = self._packed_tables(rec)
-        if caps is None:
-            caps = (len(rec["atoms"]), len(rec["bonds"]), len(rec["text"]) + 2 * n)
-        out = self._sized_tables(fn, n, caps,
-                                 lambda mols, arenas, totals, notes: getattr(self.lib, fn)(self.h, *args, mols, *arenas, notes, totals, *tail, _stream()),
-                                 dev, keep_device, side=torch.uint8)
-        out["atom_notes"] = out.pop("side").cpu().numpy()
-        return out
+        return self._tables_pass("mnx_main_pack", rec, caps, keep_device, *self.SELECTS)
 
     def normalize_pack(self, rec: dict, caps=None, keep_device: bool = False) -> dict:
         """graph_pack's records (or expand_pack's, or smiles_read's) -> the same molecules with one normal spelling per atom
@@ -1234,7 +1218,7 @@ class Engine:
         MOL_AROMATIZED / MOL_UNBRACKETED / MOL_NORMALIZE_REFUSED. Starts from the input's sizes (a new symbol is rarely longer
         than the old one; or caps = (atom_cap, bond_cap, text_cap)) and repeats at most once with the sizes `totals` reports.
         keep_device: also 'device', as graph_pack."""
-        return self._respell_pack("mnx_normalize_pack", rec, caps, keep_device)
+        return self._tables_pass("mnx_normalize_pack", rec, caps, keep_device, *self.RESPELLS)
 
     def kekulize_pack(self, rec: dict, caps=None, keep_device: bool = False, max_steps: int = 0) -> dict:
         """graph_pack's records (or expand_pack's, or smiles_read's) -> the same molecules with every aromatic system that has a
@@ -1246,7 +1230,7 @@ class Engine:
         aromatic atom, NOTE_KEKULIZED / NOTE_KEKULE_LEFT (with NOTE_KEKULE_LIMIT) / NOTE_COPIED. Atom and bond counts and order
         are the input's; mols['flags'] carries MOL_KEKULIZED / MOL_KEKULE_LEFT / MOL_KEKULIZE_REFUSED. Run it behind expand_pack
         and in front of normalize_pack. Sizes itself as normalize_pack does; keep_device: also 'device', as graph_pack."""
-        return self._respell_pack("mnx_kekulize_pack", rec, caps, keep_device, (int(max_steps),))
+        return self._tables_pass("mnx_kekulize_pack", rec, caps, keep_device, *self.RESPELLS, (int(max_steps),))
 
     def smiles_read(self, strings, caps=None, keep_device: bool = False) -> dict:
         """SMILES strings (str or bytes) -> the molecules as packed tables, read on the device (mnx_smiles_read; the rule:

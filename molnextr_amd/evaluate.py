@@ -236,18 +236,29 @@ def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: 
     gold side is left as read, as in the reference, whose --keep_main trims predictions only. The other scores stay as they
     are. Only the component rule is the reference's (_keep_main_molecule): the comparison is still this
     project's canonical string and NOT the reference's RDKit `graph` score."""
+    from .chain import run_chain
     from .engine import READ_REFUSED, SMILES_REFUSED
     from .shard import MAX_LEN
     kmax = engine.max_atoms
     dev = torch.device("cuda", engine.device)
     gold = ["" if g is None or (isinstance(g, float) and np.isnan(g)) else str(g) for g in gold]
     assert len(gold) == len(records)
+    # the scores a flag adds: its name, the passes in front of the writer (chain.run_chain orders them), whether the gold side too
+    extra = [row for row, given in ((("graph_match_normalized", ("normalize",), True), normalize),
+                                    (("graph_match_kekulized", ("kekulize", "normalize"), True), kekulize),
+                                    (("graph_match_formula", ("formula", "expand"), True), formula),
+                                    (("graph_match_main", ("keep_main",), False), keep_main)) if given]
+    equal = dict.fromkeys(["graph_match_device"] + [row[0] for row in extra], 0)
+    unreadable = refused = 0
 
-    def texts(rec):
-        recs, _, data, _, _ = engine.smiles_pack(rec, canonical=True)
+    def texts(rec, passes=()):
+        recs, _, data, _, _ = engine.smiles_pack(run_chain(engine, rec, passes, keep_last=True)[1], canonical=True)
         return [None if int(r["flags"]) & SMILES_REFUSED else data[int(r["text0"]):int(r["text0"]) + int(r["len"])] for r in recs]
 
-    equal = equal_normalized = equal_kekulized = equal_formula = equal_main = unreadable = refused = 0
+    def score(name, pred, want, read):
+        equal[name] += sum(not int(r["flags"]) & READ_REFUSED and p is not None and w is not None and p == w
+                           for p, w, r in zip(pred, want, read["read"]))
+
     for c0 in range(0, len(gold), chunk):
         rows = torch.from_numpy(np.ascontiguousarray(records[c0:c0 + chunk])).to(dev)
         n = rows.shape[0]
@@ -256,41 +267,15 @@ def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: 
                "atom_idx": rows[:, 2 + MAX_LEN:2 + MAX_LEN + kmax].contiguous(),
                "edges": e32.view(torch.uint8)[:, :kmax * kmax].reshape(n, kmax, kmax).contiguous()}
         packed = engine.graph_pack(out, keep_device=True)
-        pred = texts(packed)
         read = engine.smiles_read(gold[c0:c0 + chunk], keep_device=True)
-        want = want_read = texts(read)
-        for p, w, r in zip(pred, want, read["read"]):
-            bad = bool(int(r["flags"]) & READ_REFUSED)
-            unreadable += bad
-            refused += p is None
-            equal += (not bad) and p is not None and w is not None and p == w
-        if normalize:
-            pred = texts(engine.normalize_pack(packed, keep_device=True))
-            want = texts(engine.normalize_pack(read, keep_device=True))
-            for p, w, r in zip(pred, want, read["read"]):
-                equal_normalized += not int(r["flags"]) & READ_REFUSED and p is not None and w is not None and p == w
-        if kekulize:
-            pred, want = (texts(engine.normalize_pack(engine.kekulize_pack(side, keep_device=True), keep_device=True)) for side in (packed, read))
-            for p, w, r in zip(pred, want, read["read"]):
-                equal_kekulized += not int(r["flags"]) & READ_REFUSED and p is not None and w is not None and p == w
-        if formula:
-            pred, want = (texts(engine.expand_pack(engine.formula_pack(side, keep_device=True), keep_device=True)) for side in (packed, read))
-            for p, w, r in zip(pred, want, read["read"]):
-                equal_formula += not int(r["flags"]) & READ_REFUSED and p is not None and w is not None and p == w
-        if keep_main:
-            pred = texts(engine.main_pack(packed, keep_device=True))
-            for p, w, r in zip(pred, want_read, read["read"]):
-                equal_main += not int(r["flags"]) & READ_REFUSED and p is not None and w is not None and p == w
-    scores = {"graph_match_device": equal / len(gold) if gold else 0.0, "gold_unreadable": int(unreadable), "pred_refused": int(refused)}
-    if normalize:
-        scores["graph_match_normalized"] = equal_normalized / len(gold) if gold else 0.0
-    if kekulize:
-        scores["graph_match_kekulized"] = equal_kekulized / len(gold) if gold else 0.0
-    if formula:
-        scores["graph_match_formula"] = equal_formula / len(gold) if gold else 0.0
-    if keep_main:
-        scores["graph_match_main"] = equal_main / len(gold) if gold else 0.0
-    return scores
+        pred, want = texts(packed), texts(read)
+        unreadable += sum(bool(int(r["flags"]) & READ_REFUSED) for r in read["read"])
+        refused += sum(p is None for p in pred)
+        score("graph_match_device", pred, want, read)
+        for name, passes, both in extra:
+            score(name, texts(packed, passes), texts(read, passes) if both else want, read)
+    return {"graph_match_device": equal.pop("graph_match_device") / len(gold) if gold else 0.0, "gold_unreadable": int(unreadable),
+            "pred_refused": int(refused), **{name: e / len(gold) if gold else 0.0 for name, e in equal.items()}}
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -360,14 +345,9 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if not 1 <= args.batch_size <= MAX_BATCH_SIZE:
         ap.error(f"--batch_size must be 1..{MAX_BATCH_SIZE} (reference batches of 2 x batch_size <= {2 * MAX_BATCH_SIZE} rows)")
-    if args.graph_normalize and not args.graph_match:
-        ap.error("--graph_normalize adds a score to --graph_match")
-    if args.graph_kekulize and not args.graph_match:
-        ap.error("--graph_kekulize adds a score to --graph_match")
-    if args.graph_formula and not args.graph_match:
-        ap.error("--graph_formula adds a score to --graph_match")
-    if args.graph_keep_main and not args.graph_match:
-        ap.error("--graph_keep_main adds a score to --graph_match")
+    for flag in ("graph_normalize", "graph_kekulize", "graph_formula", "graph_keep_main"):
+        if getattr(args, flag) and not args.graph_match:
+            ap.error(f"--{flag} adds a score to --graph_match")
     dtype = args.dtype or ("fp16" if args.fp16 else DEFAULT_DTYPE)
     max_batch = max(64, 2 * args.batch_size)          # one reference batch is encoded in one launch group
     world = int(os.environ.get("WORLD_SIZE", "1"))

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import weights as W
+from .chain import BY_NAME, PASSES, run_chain
 from .engine import DEFAULT_DTYPE, MOL_FORMULA_LEFT, MOL_TRUNCATED, NOTE_H_MASK, SMILES_NO_POSITION, SMILES_REFUSED, Engine, MnxError
 from .preprocess import load_image_rgb, transform_image, transform_image_gray
 from .tokenizer import coords_labels, get_tokenizer
@@ -140,6 +141,84 @@ def unpack_graphs(mols, atoms, bonds, text, coord_bins: int = 64, with_scores: b
     return preds
 
 
+def _origin_stage(stage: dict, graphs: List[dict]) -> List[dict]:
+    """Per molecule the dict of a pass that adds or drops atoms (formula, expand, keep_main): graphs = unpack_graphs(stage)."""
+    mols, origin = stage["mols"], stage["origin"].tolist()
+    return [{"symbols": g["chartok_coords"]["symbols"], "coords": g["chartok_coords"]["coords"], "bonds": g["bonds"],
+             "origin": origin[a0:a0 + na], "flags": flags}
+            for g, a0, na, flags in zip(graphs, mols["atom0"].tolist(), mols["n_atoms"].tolist(), mols["flags"].tolist())]
+
+
+def _notes_stage(stage: dict, graphs: List[dict]) -> List[dict]:
+    """Per molecule the dict of a pass that respells the atoms (kekulize, normalize): graphs = unpack_graphs(stage)."""
+    mols, notes, hydrogens = stage["mols"], stage["atom_notes"].tolist(), (stage["atom_notes"] & NOTE_H_MASK).tolist()
+    return [{"symbols": g["chartok_coords"]["symbols"], "bonds": g["bonds"], "hydrogens": hydrogens[a0:a0 + na],
+             "notes": notes[a0:a0 + na], "flags": flags}
+            for g, a0, na, flags in zip(graphs, mols["atom0"].tolist(), mols["n_atoms"].tolist(), mols["flags"].tolist())]
+
+
+_STAGE_DICTS = {"origin": _origin_stage, "atom_notes": _notes_stage}
+
+
+def packed_predictions(engine: Engine, out: dict, tok, on=(), compute_confidence: bool = False, molfile: bool = False,
+                       molfile_scale=None, smiles: bool = False, stereo: bool = False, double_bonds: bool = False,
+                       canonical: bool = False, symmetry: bool = False) -> List[dict]:
+    """predict_pipeline(packed=True) behind Engine.predict: `out`, its result dict, through mnx_graph_pack, the passes named in
+    `on` (chain.run_chain: their order, and which stage keeps its tables on the device), the canonical ranking and the two
+    writers, to the per-image dicts that predict_pipeline describes. tok: the 'chartok_coords' tokenizer."""
+    writer = molfile or smiles
+    drawn = engine.graph_pack(out, keep_device=writer or bool(on))       # what the predicted atoms and bonds are read from
+    if (drawn["mols"]["flags"] & MOL_TRUNCATED).any():
+        raise RuntimeError(f"a molecule has more atoms than the engine capacity max_atoms={engine.max_atoms}")
+    stages, rec = run_chain(engine, drawn, on, keep_last=writer)         # rec: what the writers read
+    ranked = engine.smiles_pack(rec, stereo=stereo, double_bonds=double_bonds, canonical=True,
+                                **({"symmetry": True} if symmetry else {})) if canonical else None
+
+    # The ranks are those of the tables the writer read. They are cut per molecule at the offsets of the last record that adds or
+    # drops atoms, and travel with that record's dicts alone: a respelling pass keeps every count — except that it empties a
+    # molecule it refuses, and the lists behind such a molecule are then cut at the wrong offsets, as they always were (DESIGN 4.25).
+    counted = ([drawn] + [stages[row.name] for row in PASSES if row.name in stages and row.side == "origin"])[-1]
+
+    def unpack(r):
+        return unpack_graphs(r["mols"], r["atoms"], r["bonds"], r["text"], tok.maxx, compute_confidence,
+                             **({"rank": ranked[3], "sym_class": ranked[4]} if canonical and r is counted else {}))
+
+    preds = unpack(drawn)
+    for row in PASSES:
+        if row.name not in stages:
+            continue
+        graphs = unpack(stages[row.name])
+        for p, g, d in zip(preds, graphs, _STAGE_DICTS[row.side](stages[row.name], graphs)):
+            p[row.key] = d
+            for key in ("canonical_rank", "symmetry_class"):
+                if key in g:
+                    p[key] = g[key]
+    if "formula" in stages:
+        for p in preds:
+            before, found = p["chartok_coords"]["symbols"], p["formula"]
+            after, left = found["symbols"], found["flags"] & MOL_FORMULA_LEFT
+            found["replaced"] = [a for a, s in enumerate(before) if after[a] != s]
+            found["left"] = [a for a, s in enumerate(before) if after[a] == s and left and formula_candidate(s)]
+            if "expand" in stages:                                       # through the formula pass back to the predicted atom
+                p["expanded"]["origin"] = [found["origin"][k] for k in p["expanded"]["origin"]]
+    if molfile:
+        files, data = engine.molfile_pack(rec, scale=molfile_scale)
+        for p, f in zip(preds, files):
+            t0, n = int(f["text0"]), int(f["len"])
+            p["molfile"] = data[t0:t0 + n].decode("utf-8", errors="replace") if n else None
+    if smiles:
+        recs, order, data = ranked[:3] if canonical else \
+            engine.smiles_pack(rec, stereo=stereo, **({"double_bonds": True} if double_bonds else {}))
+        for p, r, m in zip(preds, recs, rec["mols"]):
+            t0, n, a0, na = int(r["text0"]), int(r["len"]), int(m["atom0"]), int(m["n_atoms"])
+            written = not int(r["flags"]) & SMILES_REFUSED               # an empty molecule is written as the empty string
+            p["graph_smiles"] = data[t0:t0 + n].decode("ascii") if written else None
+            p["graph_smiles_order"] = order[a0:a0 + na].tolist() if written else None
+            if symmetry:
+                p["stereo_atoms"] = ranked[5][a0:a0 + na].tolist() if written else None
+    return preds
+
+
 def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_batch_size: int = 16,
                      max_len: Optional[int] = None, beam_size: int = 1, compute_confidence: bool = False,
                      labels=None, free_run=False, packed: bool = False, molfile: bool = False,
@@ -220,22 +299,15 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
     describe the main molecule, and every dict gains 'main' = {'symbols', 'coords', 'bonds', 'origin' (per kept atom, its index
     in the molecule the pass received: expanded['symbols'] with expand, else formula['symbols'] with formula, else the predicted
     atoms), 'flags' (MOL_MAIN_KEPT / MOL_MAIN_TIE of engine.py)}; the per-atom lists of the writers have one entry per atom of
-    main['symbols']. The predicted atoms and bonds ('chartok_coords', 'bonds') are what they are without it."""
-    tok = (tokenizer or get_tokenizer())["chartok_coords"]
-    if formula and not packed:
-        raise ValueError("formula=True needs packed=True: the labels are replaced in the packed tables")
-    if keep_main and not packed:
-        raise ValueError("keep_main=True needs packed=True: the atoms are dropped from the packed tables")
-    if normalize and not packed:
-        raise ValueError("normalize=True needs packed=True: the atoms are respelled in the packed tables")
-    if kekulize and not packed:
-        raise ValueError("kekulize=True needs packed=True: the aromatic systems are rewritten in the packed tables")
-    if expand and not packed:
-        raise ValueError("expand=True needs packed=True: the labels are replaced in the packed tables")
-    if molfile and not packed:
-        raise ValueError("molfile=True needs packed=True: the molfiles are written from the packed tables")
-    if smiles and not packed:
-        raise ValueError("smiles=True needs packed=True: the graph SMILES are written from the packed tables")
+    main['symbols']. The predicted atoms and bonds ('chartok_coords', 'bonds') are what they are without it.
+    The order of the five passes — formula, expand, keep_main, kekulize, normalize — stands in chain.PASSES."""
+    tok =(tokenizer or get_tokenizer())["chartok_coords"]
+    why = {**{p.name: p.packed_why for p in PASSES}, "molfile": "the molfiles are written from the packed tables",
+           "smiles": "the graph SMILES are written from the packed tables"}
+    for name, given in (("formula", formula), ("keep_main", keep_main), ("normalize", normalize), ("kekulize", kekulize),
+                        ("expand", expand), ("molfile", molfile), ("smiles", smiles)):      # the order they are reported in
+        if given and not packed:
+            raise ValueError(f"{name}=True needs packed=True: {why[name]}")
     if stereo and not smiles:
         raise ValueError("stereo=True needs smiles=True: the marks are written into the graph SMILES")
     if double_bonds and not smiles:
@@ -258,88 +330,10 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
         conf.update(labels=labels, free_run=free_run)
     out = engine.predict(images, ref_batch=ref_batch_size, max_len=max_len, beam=beam_size, **conf)
     if packed:
-        rec = engine.graph_pack(out, keep_device=molfile or smiles)
-        if (rec["mols"]["flags"] & MOL_TRUNCATED).any():
-            raise RuntimeError(f"a molecule has more atoms than the engine capacity max_atoms={engine.max_atoms}")
-        drawn = rec                                                      # what the predicted atoms and bonds are read from
-        if formula:
-            rec = formula_rec = engine.formula_pack(drawn, keep_device=molfile or smiles or normalize or kekulize or expand or keep_main)
-        if expand:
-            rec = engine.expand_pack(rec, keep_device=molfile or smiles or normalize or kekulize or keep_main)     # what the writers read
-        grown_rec = rec
-        if keep_main:
-            rec = main_rec = engine.main_pack(rec, keep_device=molfile or smiles or normalize or kekulize)
-        if kekulize:
-            rec = kekule_rec = engine.kekulize_pack(rec, keep_device=molfile or smiles or normalize)
-        if normalize:
-            rec = engine.normalize_pack(rec, keep_device=molfile or smiles)
-        ranked = engine.smiles_pack(rec, stereo=stereo, double_bonds=double_bonds, canonical=True,
-                                    **({"symmetry": True} if symmetry else {})) if canonical else None
-        per_atom = {"rank": ranked[3], "sym_class": ranked[4]} if canonical else {}
-        preds = unpack_graphs(drawn["mols"], drawn["atoms"], drawn["bonds"], drawn["text"], tok.maxx, compute_confidence,
-                              **({} if expand or formula or keep_main else per_atom))
-        if formula:
-            found = unpack_graphs(formula_rec["mols"], formula_rec["atoms"], formula_rec["bonds"], formula_rec["text"], tok.maxx,
-                                  compute_confidence, **({} if expand or keep_main else per_atom))
-            for p, g, m in zip(preds, found, formula_rec["mols"]):
-                a0, na = int(m["atom0"]), int(m["n_atoms"])
-                before, after = p["chartok_coords"]["symbols"], g["chartok_coords"]["symbols"]
-                p["formula"] = {"symbols": after, "coords": g["chartok_coords"]["coords"], "bonds": g["bonds"],
-                                "origin": formula_rec["origin"][a0:a0 + na].tolist(), "flags": int(m["flags"]),
-                                "replaced": [a for a, s in enumerate(before) if after[a] != s],
-                                "left": [a for a, s in enumerate(before) if after[a] == s and int(m["flags"]) & MOL_FORMULA_LEFT
-                                         and formula_candidate(s)]}
-                for key in ("canonical_rank", "symmetry_class"):
-                    if key in g:
-                        p[key] = g[key]
-        if expand:
-            grown = unpack_graphs(grown_rec["mols"], grown_rec["atoms"], grown_rec["bonds"], grown_rec["text"], tok.maxx,
-                                  compute_confidence, **({} if keep_main else per_atom))
-            for p, g, m in zip(preds, grown, grown_rec["mols"]):
-                a0, na = int(m["atom0"]), int(m["n_atoms"])
-                origin = grown_rec["origin"][a0:a0 + na].tolist()
-                if formula:                                              # through the formula pass back to the predicted atom
-                    origin = [p["formula"]["origin"][k] for k in origin]
-                p["expanded"] = {"symbols": g["chartok_coords"]["symbols"], "coords": g["chartok_coords"]["coords"],
-                                 "bonds": g["bonds"], "origin": origin, "flags": int(m["flags"])}
-                for key in ("canonical_rank", "symmetry_class"):
-                    if key in g:
-                        p[key] = g[key]
-        if keep_main:
-            kept = unpack_graphs(main_rec["mols"], main_rec["atoms"], main_rec["bonds"], main_rec["text"], tok.maxx,
-                                 compute_confidence, **per_atom)
-            for p, g, m in zip(preds, kept, main_rec["mols"]):
-                a0, na = int(m["atom0"]), int(m["n_atoms"])
-                p["main"] = {"symbols": g["chartok_coords"]["symbols"], "coords": g["chartok_coords"]["coords"],
-                             "bonds": g["bonds"], "origin": main_rec["origin"][a0:a0 + na].tolist(), "flags": int(m["flags"])}
-                for key in ("canonical_rank", "symmetry_class"):
-                    if key in g:
-                        p[key] = g[key]
-        for key, respelled in (("kekulized", kekule_rec if kekulize else None), ("normalized", rec if normalize else None)):
-            if respelled is None:
-                continue
-            after = unpack_graphs(respelled["mols"], respelled["atoms"], respelled["bonds"], respelled["text"], tok.maxx, compute_confidence)
-            for p, g, m in zip(preds, after, respelled["mols"]):
-                a0, na = int(m["atom0"]), int(m["n_atoms"])
-                notes = respelled["atom_notes"][a0:a0 + na]
-                p[key] = {"symbols": g["chartok_coords"]["symbols"], "bonds": g["bonds"],
-                          "hydrogens": (notes & NOTE_H_MASK).tolist(), "notes": notes.tolist(), "flags": int(m["flags"])}
-        if molfile:
-            files, data = engine.molfile_pack(rec, scale=molfile_scale)
-            for p, f in zip(preds, files):
-                t0, n = int(f["text0"]), int(f["len"])
-                p["molfile"] = data[t0:t0 + n].decode("utf-8", errors="replace") if n else None
-        if smiles:
-            recs, order, data = ranked[:3] if canonical else \
-                engine.smiles_pack(rec, stereo=stereo, **({"double_bonds": True} if double_bonds else {}))
-            for p, r, m in zip(preds, recs, rec["mols"]):
-                t0, n, a0, na = int(r["text0"]), int(r["len"]), int(m["atom0"]), int(m["n_atoms"])
-                written = not int(r["flags"]) & SMILES_REFUSED               # an empty molecule is written as the empty string
-                p["graph_smiles"] = data[t0:t0 + n].decode("ascii") if written else None
-                p["graph_smiles_order"] = order[a0:a0 + na].tolist() if written else None
-                if symmetry:
-                    p["stereo_atoms"] = ranked[5][a0:a0 + na].tolist() if written else None
-        return preds
+        on = [name for name, given in (("formula", formula), ("expand", expand), ("keep_main", keep_main), ("kekulize", kekulize),
+                                       ("normalize", normalize)) if given]
+        return packed_predictions(engine, out, tok, on, compute_confidence, molfile, molfile_scale, smiles, stereo, double_bonds,
+                                  canonical, symmetry)
     scores = out["scores"].cpu().numpy() if beam_size > 1 else None
     lens = out["lengths"].cpu().numpy()
     toks = out["tokens"].cpu().numpy()
@@ -399,35 +393,20 @@ def canonical_smiles(engine: Engine, smiles_list, expand: bool = False, normaliz
     smiles_list = list(smiles_list)
     if not smiles_list:
         return []
-    rec = engine.smiles_read(smiles_list, keep_device=True)
-    read = rec["read"]
-    if formula:
-        rec = engine.formula_pack(rec, keep_device=True)
-    formula_flags = rec["mols"]["flags"]
-    if expand:
-        rec = engine.expand_pack(rec, keep_device=True)
-    if keep_main:
-        rec = engine.main_pack(rec, keep_device=True)
-    main_flags = rec["mols"]["flags"]
-    if kekulize:
-        rec = engine.kekulize_pack(rec, keep_device=True)
-    kekulize_flags = rec["mols"]["flags"]
-    if normalize:
-        rec = engine.normalize_pack(rec, keep_device=True)
+    on = [name for name, given in (("formula", formula), ("expand", expand), ("keep_main", keep_main), ("kekulize", kekulize),
+                                   ("normalize", normalize)) if given]
+    read = engine.smiles_read(smiles_list, keep_device=True)
+    stages, rec = run_chain(engine, read, on, keep_last=True)
     recs, _, data, _, _ = engine.smiles_pack(rec, canonical=True)
     out = []
-    for r, w, m, kf, ff, mf in zip(read, recs, rec["mols"], kekulize_flags, formula_flags, main_flags):
+    for r, w in zip(read["read"], recs):
         ok = not (int(r["flags"]) & READ_REFUSED or int(w["flags"]) & SMILES_REFUSED)
         out.append({"smiles": data[int(w["text0"]):int(w["text0"]) + int(w["len"])].decode("utf-8", "replace") if ok else None,
                     "read_flags": int(r["flags"]), "err_pos": int(r["err_pos"]), "smiles_flags": int(w["flags"])})
-        if normalize:
-            out[-1]["normalize_flags"] = int(m["flags"])
-        if kekulize:
-            out[-1]["kekulize_flags"] = int(kf)
-        if formula:
-            out[-1]["formula_flags"] = int(ff)
-        if keep_main:
-            out[-1]["main_flags"] = int(mf)
+    for row in PASSES:
+        if row.name in stages and row.flags_key:
+            for item, flags in zip(out, stages[row.name]["mols"]["flags"]):
+                item[row.flags_key] = int(flags)
     return out
 
 
@@ -566,21 +545,11 @@ class molnextr:
         self.graph_symmetry = bool(graph_symmetry)
         if self.graph_symmetry and not (self.graph_smiles and self.graph_canonical):
             raise ValueError("graph_symmetry=True needs graph_smiles=True and graph_canonical=True: the rule reads the symmetry classes")
-        self.graph_expand = bool(graph_expand)
-        if self.graph_expand and not (self.graph_smiles or self.graph_molfile):
-            raise ValueError("graph_expand=True needs graph_smiles=True or graph_molfile=True: the expanded molecule is what they write")
-        self.graph_normalize = bool(graph_normalize)
-        if self.graph_normalize and not (self.graph_smiles or self.graph_molfile):
-            raise ValueError("graph_normalize=True needs graph_smiles=True or graph_molfile=True: the normalised molecule is what they write")
-        self.graph_kekulize = bool(graph_kekulize)
-        if self.graph_kekulize and not (self.graph_smiles or self.graph_molfile):
-            raise ValueError("graph_kekulize=True needs graph_smiles=True or graph_molfile=True: the kekulised molecule is what they write")
-        self.graph_formula = bool(graph_formula)
-        if self.graph_formula and not (self.graph_smiles or self.graph_molfile):
-            raise ValueError("graph_formula=True needs graph_smiles=True or graph_molfile=True: the molecule with its formulas replaced is what they write")
-        self.graph_keep_main = bool(graph_keep_main)
-        if self.graph_keep_main and not (self.graph_smiles or self.graph_molfile):
-            raise ValueError("graph_keep_main=True needs graph_smiles=True or graph_molfile=True: the main molecule is what they write")
+        for name, given in (("expand", graph_expand), ("normalize", graph_normalize), ("kekulize", graph_kekulize),
+                            ("formula", graph_formula), ("keep_main", graph_keep_main)):       # the order they are reported in
+            setattr(self, "graph_" + name, bool(given))
+            if given and not (self.graph_smiles or self.graph_molfile):
+                raise ValueError(f"graph_{name}=True needs graph_smiles=True or graph_molfile=True: {BY_NAME[name].written} is what they write")
         self.engine = Engine(states["encoder"], states["decoder"], device=device.index or 0, max_batch=max_batch,
                              dtype=dtype, image_format=image_format)
         self.input_size = args.input_size
@@ -591,8 +560,8 @@ class molnextr:
                          formula: bool = False, keep_main: bool = False) -> List[dict]:
         """The canonical graph SMILES of the caller's own strings, for comparison with 'predicted_smiles' of graph_canonical=True
         (model.canonical_smiles: read on the device, optionally expanded and normalised, written without marks)."""
-        return canonical_smiles(self.engine, smiles_list, expand=expand, normalize=normalize, kekulize=kekulize,
-                                **({"formula": True} if formula else {}), **({"keep_main": True} if keep_main else {}))
+        given = {"expand": expand, "normalize": normalize, "kekulize": kekulize, "formula": formula, "keep_main": keep_main}
+        return canonical_smiles(self.engine, smiles_list, **{name: True for name, v in given.items() if v})
 
     _groups_done = 0          # groups of the running predict_images call that have produced predictions
 
@@ -774,16 +743,7 @@ class molnextr:
                 conf["canonical"] = True
             if self.graph_symmetry:
                 conf["symmetry"] = True
-        if self.graph_expand:
-            conf["expand"] = True
-        if self.graph_normalize:
-            conf["normalize"] = True
-        if self.graph_kekulize:
-            conf["kekulize"] = True
-        if self.graph_formula:
-            conf["formula"] = True
-        if self.graph_keep_main:
-            conf["keep_main"] = True
+        conf.update({row.name: True for row in PASSES if getattr(self, "graph_" + row.name)})      # a flag travels only when it is on
         gen = self._prefetched(groups)
         try:
             for x in gen:
@@ -831,16 +791,13 @@ class molnextr:
                 d["canonical_rank"], d["symmetry_class"] = pred["canonical_rank"], pred["symmetry_class"]
             if "stereo_atoms" in pred:                        # graph_symmetry: per atom, as the ranks
                 d["stereo_atoms"] = pred["stereo_atoms"]
-            if "expanded" in pred:                            # graph_expand: the molecule the two strings describe; the ranks then
-                d["expanded"] = pred["expanded"]              # follow expanded['symbols'], not atom_sets
+            for row in PASSES:                                # graph_<name>: the molecule as it left that pass; the ranks follow
+                if row.key in pred:                           # the atoms of the last one that adds or drops any, not atom_sets
+                    d[row.key] = pred[row.key]
             if "normalized" in pred:                          # graph_normalize: per atom of the molecule that was written
-                d["hydrogens"], d["normalized"] = pred["normalized"]["hydrogens"], pred["normalized"]
-            if "kekulized" in pred:                           # graph_kekulize: the molecule as it left mnx_kekulize_pack
-                d["kekulized"] = pred["kekulized"]
-            if "formula" in pred:                             # graph_formula: the molecule as it left mnx_formula_pack
-                d["formula"] = pred["formula"]
-            if "main" in pred:                                # graph_keep_main: the main molecule and where its atoms came from
-                d["main_atoms"], d["main"] = pred["main"]["origin"], pred["main"]
+                d["hydrogens"] = pred["normalized"]["hydrogens"]
+            if "main" in pred:                                # graph_keep_main: where the main molecule's atoms came from
+                d["main_atoms"] = pred["main"]["origin"]
             if return_atoms_bonds:
                 c = pred["chartok_coords"]
                 atoms = []
