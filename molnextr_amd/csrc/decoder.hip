@@ -112,7 +112,8 @@ hipError_t kvq_pack_enqueue(const float* src, char* dst, int n_blocks, int S, in
 }
 
 // =============================================================================================
-// Decode tick. Rows are SLOTS (dec_types.h): up to 256 sequences resident at once, each at its own position t.
+// Decode tick. Rows are SLOTS (dec_types.h): up to cfg.dec_slots (<= MAX_SLOTS) sequences resident at once, each at its own
+// position t.
 // One tick advances every alive slot by one token:
 //   dec_begin_kernel                  PE ranks of every slot, alive counters
 //   per layer (8 kernels)             dec_linear<LN1|embed, qkv>, dec_attn(self), dec_linear<wo,+res>,

@@ -1885,8 +1885,8 @@ static int predict_impl(mnx_engine* h, const char* name, const void* images, int
                 }
             }
         }
-        if (tf) fprintf(tf, "%.3f seq %d live %zu next %d next_enc %d done %d free_tiles %zu\n", now_ms() - t_begin, seq,
-                        live.size(), next, ring.next_enc, done, free_tiles.size());
+        if (tf) fprintf(tf, "%.3f seq %d live %zu next %d next_enc %d done %d free_tiles %zu scan %d rows_cap %d\n",
+                        now_ms() - t_begin, seq, live.size(), next, ring.next_enc, done, free_tiles.size(), scan, rows_cap);
         ++seq;
         if (seq > 200000) { h->err = std::string(name) + ": watchdog (decode did not terminate)"; return MNX_ERR_HIP; }
     }
