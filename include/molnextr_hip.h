@@ -260,7 +260,8 @@ int mnx_edges(mnx_engine* h, const float* hidden, const int32_t* atom_idx, const
  *   out      device fp32 [3,img_size,img_size] — one image of mnx_encode's input
  * Asynchronous on `stream`. Bit-identical to molnextr_amd/preprocess.py. CropWhite / PadToSquare are pinned on the
  * reference's own classes (golden crop boxes, shapes, content hashes); the OpenCV resize / gray arithmetic is restated
- * from its documented behaviour and unpinned (OpenCV is not installable here), see DESIGN.md. */
+ * from its documented behaviour and held within 2 grey levels of exact bilinear interpolation (tests/test_gpu_prep_ref.py);
+ * OpenCV's exact rounding inside that bound is unpinned (OpenCV is not installable here), see DESIGN.md. */
 int mnx_preprocess(mnx_engine* h, const uint8_t* rgb, int32_t height, int32_t width, int32_t pad,
                    int32_t pad_to_square, int32_t* crop_out, float* out, void* stream);
 

@@ -3,7 +3,9 @@
 //   reference MolNexTR/dataset.py:158-185 (augment=False), MolNexTR/data_aug.py:98-143, MolNexTR/model.py:104.
 // Integer / byte work, HBM-trivial (one pass over the page for the bounding box, then 4 taps per output pixel).
 // It computes bit for bit what molnextr_amd/preprocess.py computes (the host restatement of albumentations 1.1.0 /
-// OpenCV semantics; neither library exists in the build image, so both are "parity unpinned" against the reference).
+// OpenCV semantics). Pinned: both lie within 2 grey levels of exact half-pixel-centre bilinear interpolation in float64
+// (tests/prep_ref.py, anchored on torch.nn.functional.interpolate; tests/test_gpu_prep_ref.py holds these kernels to it).
+// Not pinned: OpenCV's exact rounding inside that bound, see molnextr_amd/preprocess.py.
 #include "common.h"
 #include "kernels.h"
 

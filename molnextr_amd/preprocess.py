@@ -9,8 +9,12 @@ restated from their documented behaviour: `cv2.resize(INTER_LINEAR)` on uint8 = 
 switches to area averaging for exact integer scale 2, is NOT restated); `cv2.cvtColor(RGB2GRAY)` = (R*4899 + G*9617 + B*1868 + 8192) >> 14; Normalize =
 (x/255 - mean) / std. CropWhite and PadToSquare ARE pinned: tools/gen_golden.py drives the reference's own classes
 (MolNexTR/data_aug.py) on ragged pages and tests/test_preprocess.py checks crop boxes, shapes and content hashes
-(tests/golden/crop_pad.json). The OpenCV resize / gray arithmetic stays UNPINNED until a box with OpenCV can produce
-fixtures.
+(tests/golden/crop_pad.json). The resize / gray SEMANTICS are pinned too: tests/test_prep_ref_host.py (host) and
+tests/test_gpu_prep_ref.py (device) hold every gray byte within 2 grey levels of exact half-pixel-centre bilinear
+interpolation in float64 (tests/prep_ref.py, its resize anchored on torch.nn.functional.interpolate), the mean error inside
+a derived window, and show that a list of wrong variants (tap position, weights, pad / square / crop geometry, channel
+order, the two rounding constants) fails those checks. NOT pinned: OpenCV's exact rounding and its fixed-point weight
+format (which of the values inside that bound cv2 writes); that takes fixtures made on a box that has OpenCV.
 """
 import numpy as np
 

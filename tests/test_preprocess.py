@@ -1,5 +1,6 @@
-"""CPU: host pre-processing restated from albumentations/OpenCV semantics (unpinned: neither library is installed;
-these tests pin our own documented behaviour and the invariants the reference transform has)."""
+"""CPU: host pre-processing restated from albumentations/OpenCV semantics: our own documented behaviour and the invariants
+the reference transform has. The resize / gray semantics are held to a float64 bilinear reference in
+tests/test_prep_ref_host.py; what OpenCV's own rounding would give inside that bound is stated in molnextr_amd/preprocess.py."""
 import numpy as np
 
 from molnextr_amd.preprocess import crop_white, resize_bilinear_u8, to_gray_rgb, transform_image, MEAN, STD

@@ -610,7 +610,8 @@ def gen_guided(Encoder, Decoder, args, tok, ck):
 def gen_crop_pad():
     """CropWhite(pad=50) and PadToSquare of the reference's own data_aug.py (imported through a minimal
     albumentations / cv2 stand-in: both classes are pure numpy apart from a constant-border pad) on ragged pages:
-    crop parameters, output shapes and content hashes. Resize / ToGray stay unpinned (OpenCV is not installed)."""
+    crop parameters, output shapes and content hashes. Resize / ToGray have no golden (OpenCV is not installed); tests/prep_ref.py
+    holds their semantics to exact bilinear interpolation."""
     from MolNexTR.data_aug import CropWhite, PadToSquare
     cw, ps = CropWhite(pad=50), PadToSquare()
     cases = []

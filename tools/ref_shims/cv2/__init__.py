@@ -1,6 +1,6 @@
 """Container-only stand-in for the `cv2` names MolNexTR/data_aug.py touches at IMPORT time (default arguments) and
 the one call CropWhite / PadToSquare make through albumentations (constant-border padding). Not OpenCV: no resize,
-no colour conversion — those stay unpinned."""
+no colour conversion — OpenCV's exact rounding of those stays unpinned."""
 INTER_NEAREST, INTER_LINEAR, INTER_CUBIC, INTER_AREA = 0, 1, 2, 3
 BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_101 = 0, 1, 2, 3, 4
 FONT_HERSHEY_SIMPLEX = 0
