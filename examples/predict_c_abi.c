@@ -179,6 +179,30 @@ static int print_first_expanded_smiles(mnx_engine* eng, int n_images, const mnx_
                    (mol.flags & MNX_MOL_MAIN_TIE) ? ", a tie" : "");
             rc = print_first_canonical_smiles(eng, n_images, mols3_dev, atoms3_dev, bonds3_dev, text3_dev, totals);
         }
+        if (rc == MNX_OK) {     /* behind the chain: the path fingerprint of every main molecule (mnx_fingerprint_pack, this library's
+                                 * own rule, not RDKit's bits) and how similar molecule 0 is to the last one (mnx_tanimoto) */
+            mnx_fp* fp_dev = NULL, fp;
+            uint32_t *bits_dev = NULL, both = 0, *both_dev = NULL;
+            double similarity = 0.0, *similarity_dev = NULL;
+            hipMalloc((void**)&fp_dev, (size_t)n_images * sizeof(mnx_fp));
+            hipMalloc((void**)&bits_dev, (size_t)n_images * MNX_FP_WORDS * sizeof(uint32_t));
+            hipMalloc((void**)&both_dev, sizeof both);
+            hipMalloc((void**)&similarity_dev, sizeof similarity);
+            rc = mnx_fingerprint_pack(eng, mols3_dev, n_images, atoms3_dev, totals[0], bonds3_dev, totals[1], text3_dev, totals[2], fp_dev,
+                                      bits_dev, /*max_bonds=*/0, /*max_steps=*/0, /*stream=*/NULL);
+            if (rc == MNX_OK)
+                rc = mnx_tanimoto(eng, bits_dev, bits_dev + (size_t)(n_images - 1) * MNX_FP_WORDS, 1, both_dev, /*either=*/NULL,
+                                  similarity_dev, /*stream=*/NULL);
+            if (rc != MNX_OK) fprintf(stderr, "%s\n", mnx_last_error(eng));
+            else {
+                hipMemcpy(&fp, fp_dev, sizeof fp, 2);
+                hipMemcpy(&both, both_dev, sizeof both, 2);
+                hipMemcpy(&similarity, similarity_dev, sizeof similarity, 2);
+                printf("molecule 0, fingerprint: %u bits%s, %u shared with molecule %d, Tanimoto %.3f\n", (unsigned)fp.n_bits,
+                       (fp.flags & MNX_FP_LIMIT) ? " (step limit)" : "", (unsigned)both, n_images - 1, similarity);
+            }
+            hipFree(fp_dev); hipFree(bits_dev); hipFree(both_dev); hipFree(similarity_dev);
+        }
         hipFree(mols3_dev); hipFree(atoms3_dev); hipFree(bonds3_dev); hipFree(text3_dev);
     }
     hipFree(mols2_dev); hipFree(totals_dev); hipFree(atoms2_dev); hipFree(bonds2_dev); hipFree(text2_dev);

@@ -1298,6 +1298,83 @@ int mnx_smiles_read(mnx_engine* h, const char* bytes, uint32_t n_bytes, const ui
                     mnx_read* recs, mnx_atom* atoms, uint32_t atom_cap, mnx_bond* bonds, uint32_t bond_cap, char* text,
                     uint32_t text_cap, uint32_t* totals, void* stream);
 
+/* Path fingerprints, on the device: of every packed molecule a set of 2048 bits that says which paths of atoms and bonds it holds,
+ * and (mnx_tanimoto, below) the similarity of two such sets. Everything else at the end of the chain of passes is a yes or a no —
+ * the same canonical string or not —; this is the graded answer: how far a prediction is from its gold structure, which known
+ * compound is nearest. A sink like the writers, not a pass: packed tables in, a fixed-size record and 64 words per molecule out.
+ * Intended order: mnx_graph_pack or mnx_smiles_read -> the passes -> mnx_kekulize_pack -> mnx_normalize_pack -> THIS CALL: behind
+ * the last two an aromatic and a Kekule spelling of one ring give the same atoms and bonds and so the same bits.
+ * THE RULE IS THIS LIBRARY'S OWN, after the idea of Daylight's and RDKit's path fingerprints. It does NOT produce RDKit's bits
+ * (RDKFingerprint) and its similarities are not RDKit's: no toolkit is at hand to compare with, and none has seen these bits. The
+ * reference's evaluate.py only names the metric and the path length of 7.
+ *
+ * Admission, as mnx_smiles_pack_canonical admits a molecule for its ranks, with the same bits and values: MNX_FP_TOO_LARGE (bit
+ *   0) more than 999 atoms or 999 bonds; MNX_FP_BEYOND_TABLES (bit 1) its records, or a symbol, reach beyond the tables passed;
+ *   MNX_FP_BAD_BOND (bit 4) the same atom pair in two bond records, a record with i == j, or an end that is no atom of the
+ *   molecule. MNX_FP_PSEUDO_ATOM (bit 2) and MNX_FP_TRUNCATED (bit 3, a copy of MNX_MOL_TRUNCATED) are informational, as in
+ *   mnx_smiles; a molecule refused on bit 0 or 1 has had no atom read and so never bit 2.
+ * Atom key. k(a) = fmix32(fnv1a_bytes(text(a))), text(a) being the bytes a writer puts down for the atom without a stereo mark:
+ *   the at most 12 bytes that the canonical ranks take as their initial key (mnx_smiles_pack_canonical), so 'C', 'c', '[NH3+]',
+ *   '[13CH3]' differ, a pseudo-atom is '*' and a numbered R-group '[n*]'.
+ * Bond word. 1 for a bond record of type 1, 5 or 6 (a wedge is a single bond), 2 for type 2, 3 for type 3, 4 for type 4, 5 for
+ *   any other type. `rev` is not read.
+ * Paths. A path is a sequence of distinct atoms a0 .. aL, consecutive ones joined by a bond record, 0 <= L <= max_bonds; L = 0 is
+ *   the single atom. max_bonds is 1 .. MNX_FP_MAX_BONDS (7, the reference's maxPath); 0 means 7. A walk never returns to an atom
+ *   it holds, so a ring is never closed: a ring of 6 is seen as its paths of up to 5 bonds.
+ * Path hash. The word sequence of a path is k(a0), c1, k(a1), .., cL, k(aL). H(seq) is FNV-1a over 32-bit words: h = 2166136261,
+ *   then h = (h ^ w) * 16777619 mod 2^32 for every word; fnv1a_bytes is the same over bytes. fmix32 is murmur3's finaliser: h ^= h
+ *   >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16. The path's hash is p = fmix32(min(H(seq), H(seq
+ *   reversed))): both ends of a path give one value, and so does every numbering of the atoms.
+ * Bits. A path sets bit p & 2047 and bit (p >> 11) & 2047. Bit t is word t >> 5, mask 1u << (t & 31).
+ * Step limit. For a directed bond s = (a -> n), P(s) is the number of paths of 1 .. max_bonds bonds that begin with it: a property
+ *   of the graph, not of how the work is split. A molecule with any P(s) > max_steps gets MNX_FP_LIMIT (bit 16) and no bits.
+ *   max_steps == 0 means MNX_FP_DEFAULT_STEPS; more than MNX_FP_MAX_STEPS is an argument error (a dense graph could otherwise
+ *   hold a workgroup for minutes). The largest P(s) is 73 for taxol, 59 for coronene, 52 for atorvastatin — a drawn molecule is
+ *   far from the limit —, 1957 for the complete graph on 8 atoms and 8660 for the one on 9.
+ * A molecule refused on bit 0, 1 or 4, or limited, has all 64 words zero and n_bits 0. The empty molecule is admitted: no bits.
+ * recs[b]: flags; n_bits, the number of bits set; max_paths, the largest P(s) — 0 without bonds or when refused, 0xFFFFFFFF when
+ *   limited —; reserved 0.
+ * Inputs as mnx_smiles_pack's: mols [n], 1 <= n <= 65536; atoms [n_atom_records], bonds [n_bond_records] (8-byte aligned), text
+ * [n_text_bytes]; mnx_set_symbol_tables must have been called. Outputs, device pointers the caller allocated: recs [n], bits
+ * uint32 [n][64] (4-byte aligned). Deterministic word for word: the bits are ORs and max_paths is a maximum in on-chip memory,
+ * neither of which depends on the order of its operands; no atomic decides a position. Records and words are written whole. One
+ * launch, asynchronous on `stream`, no allocation, no host synchronisation.
+ * MNX_ERR_INVALID_ARG (with mnx_last_error, "mnx_fingerprint_pack: ..."): a null pointer (an input table of 0 records may be
+ * null), n outside 1..65536, misaligned records, no symbol tables set, max_bonds above 7, max_steps above MNX_FP_MAX_STEPS;
+ * nothing is launched then. */
+typedef struct mnx_fp {
+    uint32_t flags;             /* MNX_FP_* */
+    uint32_t n_bits;            /* bits set in the molecule's 64 words */
+    uint32_t max_paths;         /* the largest number of paths from one directed bond; 0xFFFFFFFF with MNX_FP_LIMIT */
+    uint32_t reserved;          /* 0 */
+} mnx_fp;
+#define MNX_FP_TOO_LARGE 1u
+#define MNX_FP_BEYOND_TABLES 2u
+#define MNX_FP_PSEUDO_ATOM 4u
+#define MNX_FP_TRUNCATED 8u
+#define MNX_FP_BAD_BOND 16u
+#define MNX_FP_LIMIT 65536u
+#define MNX_FP_WORDS 64u
+#define MNX_FP_MAX_BONDS 7u
+#define MNX_FP_DEFAULT_STEPS 4096u
+#define MNX_FP_MAX_STEPS (1u << 20)
+int mnx_fingerprint_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
+                         const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_fp* recs,
+                         uint32_t* bits, uint32_t max_bonds, uint32_t max_steps, void* stream);
+
+/* The Tanimoto similarity of rows of fingerprints, pair by pair: row i of a against row i of b, each 64 words as
+ * mnx_fingerprint_pack writes them. both[i] = popcount(a[i] & b[i]), either[i] = popcount(a[i] | b[i]), similarity[i] = (double)
+ * both[i] / (double)either[i], and 0.0 when either[i] == 0: this library's own choice — an empty side is a refused, limited or
+ * empty molecule, and that is a mismatch here as it is everywhere else. One correctly rounded division of two integers below
+ * 2049: the same double on host and device. No all-pairs matrix: pass the rows paired as they are to be compared.
+ * a, b: device uint32 [n][64], 1 <= n <= 65536 (they may be the same pointer). both, either: device uint32 [n]; similarity: device
+ * double [n]; each of the three may be null, not all of them. One launch, asynchronous on `stream`, no allocation, no host
+ * synchronisation; needs no tables.
+ * MNX_ERR_INVALID_ARG (with mnx_last_error, "mnx_tanimoto: ..."): a or b null, all three outputs null, n outside 1..65536, a
+ * pointer that is not 4-byte (similarity: 8-byte) aligned; nothing is launched then. */
+int mnx_tanimoto(mnx_engine* h, const uint32_t* a, const uint32_t* b, int32_t n, uint32_t* both, uint32_t* either,
+                 double* similarity, void* stream);
+
 /* mnx_predict with beam search (BASELINE config 5): the same inputs and outputs, every reference batch searched as
  * mnx_decode_beam does (n_best = 1: the best hypothesis; atom positions and the bond head run on ITS tokens and decoder
  * outputs) while the encoder of the following launch groups runs on the second stream. Up to MNX_BEAM_GROUPS (environment,

@@ -1,7 +1,9 @@
 """The passes that take packed molecule tables to packed molecule tables, in the one order they run in (the rule:
 include/molnextr_hip.h — formula in front of expand, keep_main behind it, kekulize in front of normalize), and the one function
 that runs them. predict_pipeline, canonical_smiles, the facade and evaluate's --graph_match read the order, the keys and the
-error clauses here; a new pass is one row, one Engine method and one paragraph in their docstrings."""
+error clauses here; a new pass is one row, one Engine method and one paragraph in their docstrings. What reads the
+last record without writing tables again — the molfile and SMILES writers, the path fingerprint (Engine.fingerprint_pack) — is a
+sink, not a row: it runs behind run_chain's last record, which keep_last keeps on the device for it."""
 import collections
 
 # name: the option's name everywhere (graph_<name> on the facade); method: the Engine method; key: where a prediction dict

@@ -282,6 +282,13 @@ hipError_t normalize_pack_enqueue(const SymbolTables* st_dev, const PackedTables
 // s. max_steps: the pairings one system's search may try, 0 = MNX_KEKULE_DEFAULT_STEPS.
 hipError_t kekulize_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, const TablesOut& o, unsigned char* atom_notes,
                                  unsigned* totals, unsigned max_steps, hipStream_t s);
+// fingerprint.hip: of every molecule of t the path fingerprint — 64 words behind one another in `bits`, a record in recs
+// (mnx_fingerprint_pack): one launch on s. max_bonds 1 .. 7 and max_steps 1 .. MNX_FP_MAX_STEPS, the defaults resolved
+hipError_t fingerprint_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, mnx_fp* recs, unsigned* bits,
+                                    unsigned max_bonds, unsigned max_steps, hipStream_t s);
+// the Tanimoto similarity of row r of a and row r of b, n rows of 64 words (mnx_tanimoto; each output may be null): one launch on s
+hipError_t tanimoto_enqueue(const unsigned* a, const unsigned* b, int n, unsigned* both, unsigned* either, double* similarity,
+                            hipStream_t s);
 // smiles_read.hip: string b = bytes[offsets[b] .. offsets[b + 1]) read as SMILES into packed tables of mnx_graph_pack's record types
 // (mnx_smiles_read): count, scan and fill, three launches on s
 hipError_t smiles_read_enqueue(const unsigned char* bytes, unsigned n_bytes, const unsigned* offsets, int n, mnx_read* recs,

@@ -1677,6 +1677,38 @@ int mnx_smiles_pack_symmetric(mnx_engine* h, const mnx_mol* mols, int32_t n, con
                        true, atom_marks);
 }
 
+int mnx_fingerprint_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
+                         const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_fp* recs,
+                         uint32_t* bits, uint32_t max_bonds, uint32_t max_steps, void* stream) {
+    const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
+    if (int rc = check_packed_tables(h, "mnx_fingerprint_pack", t, !recs || !bits, (((uintptr_t)recs | (uintptr_t)bits) & 3) != 0,
+                                     "recs and bits 4-byte"))
+        return rc;
+    if (max_bonds > MNX_FP_MAX_BONDS) { h->err = "mnx_fingerprint_pack: max_bonds must be 1 to 7, or 0 for 7"; return MNX_ERR_INVALID_ARG; }
+    if (max_steps > MNX_FP_MAX_STEPS) {
+        h->err = "mnx_fingerprint_pack: max_steps must not exceed MNX_FP_MAX_STEPS (1048576)";
+        return MNX_ERR_INVALID_ARG;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, fingerprint_pack_enqueue(h->st_dev, t, recs, bits, max_bonds ? max_bonds : MNX_FP_MAX_BONDS,
+                                       max_steps ? max_steps : MNX_FP_DEFAULT_STEPS, (hipStream_t)stream));
+    return MNX_OK;
+}
+
+int mnx_tanimoto(mnx_engine* h, const uint32_t* a, const uint32_t* b, int32_t n, uint32_t* both, uint32_t* either,
+                 double* similarity, void* stream) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    auto bad = [&](const char* m) { h->err = std::string("mnx_tanimoto: ") + m; return MNX_ERR_INVALID_ARG; };
+    if (!a || !b) return bad("null pointer");
+    if (!both && !either && !similarity) return bad("both, either and similarity are all null");
+    if (n < 1 || n > 65536) return bad("1 <= n <= 65536 required");
+    if ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)both | (uintptr_t)either) & 3) || ((uintptr_t)similarity & 7))
+        return bad("a, b, both and either must be 4-byte aligned, similarity 8-byte");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, tanimoto_enqueue(a, b, n, both, either, similarity, (hipStream_t)stream));
+    return MNX_OK;
+}
+
 int mnx_atom_scan(mnx_engine* h, const int32_t* tokens, const int32_t* lengths, int32_t n, int32_t T, int32_t kmax,
                   int32_t* atom_idx, int32_t* n_atoms, void* stream) {
     if (!h || !tokens || !lengths || !atom_idx || !n_atoms || n < 1 || T < 1 || kmax < 1) return MNX_ERR_INVALID_ARG;

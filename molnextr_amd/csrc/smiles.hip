@@ -19,6 +19,7 @@
 
 #include "../../include/molnextr_hip.h"
 #include "atom_symbol.h"
+#include "atom_write.h"
 #include "block_scan.h"
 #include "dec_types.h"
 
@@ -39,7 +40,6 @@ constexpr unsigned REFUSED = PT_TOO_LARGE | PT_BEYOND_TABLES | MNX_SMILES_DUPLIC
 //   bits 0-9 the neighbour, bits 10-12 the bond's written class, bits 13-22 the atom that owns the list, bit 23 a bond of the
 //   search tree (to the parent or to a child); every other bond is a ring bond; STEREO only: bit 24 the bond is a wedge (class
 //   5) as the owner sees it, bit 25 a dash (class 6). The rank sorts copy whole entries, so the bits travel with them.
-constexpr unsigned B_SINGLE = 0, B_DOUBLE = 1, B_TRIPLE = 2, B_AROMATIC = 3, B_ANY = 4;
 constexpr unsigned SLOT_TREE = 1u << 23, SLOT_UP = 1u << 24, SLOT_DOWN = 1u << 25;
 __device__ __forceinline__ unsigned slot_nbr(unsigned e) { return e & 1023u; }
 __device__ __forceinline__ unsigned slot_cls(unsigned e) { return e >> 10 & 7u; }
@@ -47,10 +47,6 @@ __device__ __forceinline__ unsigned slot_owner(unsigned e) { return e >> 13 & 10
 __device__ __forceinline__ unsigned slot_seen(unsigned cls) { return cls == 5 ? SLOT_UP : cls == 6 ? SLOT_DOWN : 0u; }
 __device__ __forceinline__ long long slot_z(unsigned e) { return (long long)(e >> 24 & 1u) - (long long)(e >> 25 & 1u); }
 
-// the written class of a bond record's `type`: a wedge is a single bond
-__device__ __forceinline__ unsigned bond_class(unsigned ty) {
-    return (ty == 1 || ty == 5 || ty == 6) ? B_SINGLE : ty == 2 ? B_DOUBLE : ty == 3 ? B_TRIPLE : ty == 4 ? B_AROMATIC : B_ANY;
-}
 // det of the rows a, b, c, exact in 64 bits (|x|, |y| < 2^18 and |z| <= 2 here)
 __device__ __forceinline__ long long det3(long long ax, long long ay, long long az, long long bx, long long by, long long bz,
                                           long long cx, long long cy, long long cz) {
@@ -65,42 +61,6 @@ __device__ __forceinline__ char bond_symbol(unsigned cls, bool both_aromatic) {
         case B_TRIPLE: return '#';
         case B_AROMATIC: return both_aromatic ? 0 : ':';
         default: return '~';
-    }
-}
-
-template <typename Put>
-__device__ __forceinline__ void put_number(unsigned v, Put put) {       // decimal, v <= 999
-    if (v >= 100) put((char)('0' + v / 100));
-    if (v >= 10) put((char)('0' + v / 10 % 10));
-    put((char)('0' + v % 10));
-}
-
-// One atom's text from its interpretation (atom_symbol.h), the two bytes of its element and its stereo mark (0 none, 1 '@',
-// 2 '@@': only a bracket atom ever has one).
-template <typename Put>
-__device__ __forceinline__ void put_atom(unsigned w, unsigned el, unsigned mark, Put put) {
-    const unsigned cls = info_cls(w);
-    if (cls == CLS_PSEUDO) { put('*'); return; }
-    if (cls == CLS_RNUM) { put('['); put_number(info_num(w), put); put('*'); put(']'); return; }
-    const char e0 = (char)(el & 255u), e1 = (char)(el >> 8 & 255u);
-    const bool bracket = (w & 4u) != 0;
-    if (bracket) {
-        put('[');
-        if (info_num(w)) put_number(info_num(w), put);
-    }
-    put(e0 == 'R' && e1 == ' ' ? '*' : info_aromatic(w) ? (char)(e0 + 32) : e0);
-    if (e1 != ' ') put(e1);
-    if (bracket) {
-        if (mark >= 1) put('@');
-        if (mark >= 2) put('@');
-        const int h = info_h(w), q = info_charge(w);
-        if (h >= 1) put('H');
-        if (h >= 2) put((char)('0' + h));
-        if (q != 0) {
-            put(q > 0 ? '+' : '-');
-            if (q > 1 || q < -1) put_number((unsigned)(q > 0 ? q : -q), put);
-        }
-        put(']');
     }
 }
 

@@ -30,7 +30,7 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
            "mnx_set_symbol_tables", "mnx_molfile_pack", "mnx_smiles_pack", "mnx_smiles_pack_stereo",
            "mnx_smiles_pack_marks", "mnx_smiles_pack_canonical", "mnx_smiles_pack_symmetric", "mnx_set_fragments", "mnx_expand_pack", "mnx_smiles_read",
            "mnx_beam_scripted", "mnx_edge_probs", "mnx_normalize_pack", "mnx_kekulize_pack", "mnx_formula_pack",
-           "mnx_decode_beam_forced", "mnx_main_pack")
+           "mnx_decode_beam_forced", "mnx_main_pack", "mnx_fingerprint_pack", "mnx_tanimoto")
 
 # Encoder operand modes (include/molnextr_hip.h MNX_DTYPE_*). "fp16x3" — split fp16 operands, three MFMA terms per
 # product, fp32-class results — is the default: it is the fastest mode whose results stay a factor of four inside north_star's
@@ -169,6 +169,14 @@ SMILES_NO_POSITION = 0xFFFF             # `order` of an atom whose molecule got 
 READ_DTYPE = np.dtype([("flags", "<u4"), ("err_pos", "<u4"), ("n_rings", "<u4"), ("reserved", "<u4")], align=True)
 READ_SYNTAX, READ_TOO_LARGE, READ_STEREO_DROPPED, READ_BEYOND = 1, 2, 4, 8
 READ_REFUSED = READ_SYNTAX | READ_TOO_LARGE | READ_BEYOND      # the empty molecule stands in its place
+# mnx_fp, one molecule of mnx_fingerprint_pack (16 bytes; its FP_WORDS words of bits stand in a table of their own), and its flags
+# (MNX_FP_*): bits 0-3 as mnx_smiles'; the same atom pair in two bond records, a bond from an atom to itself or to no atom of the
+# molecule; a directed bond begins more than max_steps paths. FP_DEFAULT_STEPS is what max_steps = 0 stands for, FP_MAX_STEPS the
+# most a caller may pass, FP_MAX_BONDS the longest path (what max_bonds = 0 stands for)
+FP_DTYPE = np.dtype([("flags", "<u4"), ("n_bits", "<u4"), ("max_paths", "<u4"), ("reserved", "<u4")], align=True)
+FP_TOO_LARGE, FP_BEYOND_TABLES, FP_PSEUDO_ATOM, FP_TRUNCATED, FP_BAD_BOND, FP_LIMIT = 1, 2, 4, 8, 16, 1 << 16
+FP_REFUSED = FP_TOO_LARGE | FP_BEYOND_TABLES | FP_BAD_BOND      # no fingerprint: every word 0 (as with FP_LIMIT)
+FP_WORDS, FP_MAX_BONDS, FP_DEFAULT_STEPS, FP_MAX_STEPS = 64, 7, 4096, 1 << 20
 
 
 def vocab_text(tok):
@@ -325,6 +333,10 @@ def load_library():
     lib.mnx_formula_pack.argtypes = lib.mnx_kekulize_pack.argtypes
     lib.mnx_main_pack.restype = C.c_int
     lib.mnx_main_pack.argtypes = lib.mnx_expand_pack.argtypes           # expand's arguments exactly
+    lib.mnx_fingerprint_pack.restype = C.c_int                          # the writers' input side, recs, bits, max_bonds, max_steps
+    lib.mnx_fingerprint_pack.argtypes = lib.mnx_smiles_pack.argtypes[:9] + [vp, vp, C.c_uint32, C.c_uint32, vp]
+    lib.mnx_tanimoto.restype = C.c_int
+    lib.mnx_tanimoto.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     lib.mnx_smiles_read.restype = C.c_int
     lib.mnx_smiles_read.argtypes = [vp, vp, C.c_uint32, vp, i32, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp]
     lib.mnx_atom_scan.restype = C.c_int
@@ -1231,6 +1243,48 @@ class Engine:
         are the input's; mols['flags'] carries MOL_KEKULIZED / MOL_KEKULE_LEFT / MOL_KEKULIZE_REFUSED. Run it behind expand_pack
         and in front of normalize_pack. Sizes itself as normalize_pack does; keep_device: also 'device', as graph_pack."""
         return self._tables_pass("mnx_kekulize_pack", rec, caps, keep_device, *self.RESPELLS, (int(max_steps),))
+
+    def fingerprint_pack(self, rec: dict, max_bonds: int = 0, max_steps: int = 0, keep_device: bool = False) -> dict:
+        """graph_pack's records (or any pass's, or smiles_read's) -> {'fp' [n] FP_DTYPE, 'bits' uint32 [n, FP_WORDS]}: of every
+        molecule the 2048 bits of its paths of up to max_bonds bonds (mnx_fingerprint_pack; the rule: include/molnextr_hip.h —
+        this library's own, after the idea of Daylight's and RDKit's path fingerprints, NOT RDKit's bits). max_bonds 1 .. 7 (0:
+        FP_MAX_BONDS); max_steps: the paths one directed bond may begin (0: FP_DEFAULT_STEPS; FP_MAX_STEPS at the most), beyond
+        which the molecule gets FP_LIMIT. A molecule with a bit of FP_REFUSED or FP_LIMIT has every word 0; fp['n_bits'] counts
+        the bits, fp['max_paths'] is the largest number of paths from one directed bond. Run it behind kekulize_pack and
+        normalize_pack, so that an aromatic and a Kekule spelling give the same bits. One launch, nothing to size. keep_device:
+        'bits' stays a device tensor (int32 [n, FP_WORDS], the same words), for tanimoto."""
+        dev = torch.device("cuda", self.device)
+        n = len(rec["mols"])
+        tables, args = self._packed_tables(rec)
+        recs = torch.empty(n * FP_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        bits = torch.empty((n, FP_WORDS), dtype=torch.int32, device=dev)
+        self._check(self.lib.mnx_fingerprint_pack(self.h, *args, _ptr(recs), _ptr(bits), int(max_bonds), int(max_steps), _stream()),
+                    "mnx_fingerprint_pack")
+        return {"fp": recs.cpu().numpy().view(FP_DTYPE), "bits": bits if keep_device else bits.cpu().numpy().view(np.uint32)}
+
+    def tanimoto(self, a, b) -> dict:
+        """Two tables of fingerprints [n, FP_WORDS] (fingerprint_pack's 'bits': numpy uint32 or the device tensors), row i of a
+        against row i of b -> {'both' uint32 [n], 'either' uint32 [n], 'similarity' float64 [n]}: the bits both rows hold, the
+        bits either holds, and their quotient — 0.0 where neither holds a bit: an empty side is a mismatch (mnx_tanimoto)."""
+        dev = torch.device("cuda", self.device)
+
+        def rows(x):
+            if not isinstance(x, torch.Tensor):
+                x = torch.from_numpy(np.array(x, dtype=np.uint32).view(np.int32))      # a copy: the caller's rows may be read-only
+            x = x.to(dev).contiguous()
+            if x.dim() != 2 or x.shape[1] != FP_WORDS or x.dtype != torch.int32:
+                raise ValueError(f"tanimoto needs [n, {FP_WORDS}] words of 32 bits, not {tuple(x.shape)} {x.dtype}")
+            return x
+
+        a, b = rows(a), rows(b)
+        if a.shape != b.shape:
+            raise ValueError(f"tanimoto compares row with row: {tuple(a.shape)} against {tuple(b.shape)}")
+        n = a.shape[0]
+        both, either = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+        similarity = torch.empty(n, dtype=torch.float64, device=dev)
+        self._check(self.lib.mnx_tanimoto(self.h, _ptr(a), _ptr(b), n, _ptr(both), _ptr(either), _ptr(similarity), _stream()), "mnx_tanimoto")
+        return {"both": both.cpu().numpy().view(np.uint32), "either": either.cpu().numpy().view(np.uint32),
+                "similarity": similarity.cpu().numpy()}
 
     def smiles_read(self, strings, caps=None, keep_device: bool = False) -> dict:
         """SMILES strings (str or bytes) -> the molecules as packed tables, read on the device (mnx_smiles_read; the rule:

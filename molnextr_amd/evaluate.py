@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import sys
 from typing import Callable, Dict, List, Optional, Sequence
@@ -238,11 +239,7 @@ def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: 
     project's canonical string and NOT the reference's RDKit `graph` score."""
     from .chain import run_chain
     from .engine import READ_REFUSED, SMILES_REFUSED
-    from .shard import MAX_LEN
-    kmax = engine.max_atoms
-    dev = torch.device("cuda", engine.device)
-    gold = ["" if g is None or (isinstance(g, float) and np.isnan(g)) else str(g) for g in gold]
-    assert len(gold) == len(records)
+    gold = _gold_strings(gold, records)
     # the scores a flag adds: its name, the passes in front of the writer (chain.run_chain orders them), whether the gold side too
     extra = [row for row, given in ((("graph_match_normalized", ("normalize",), True), normalize),
                                     (("graph_match_kekulized", ("kekulize", "normalize"), True), kekulize),
@@ -259,15 +256,7 @@ def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: 
         equal[name] += sum(not int(r["flags"]) & READ_REFUSED and p is not None and w is not None and p == w
                            for p, w, r in zip(pred, want, read["read"]))
 
-    for c0 in range(0, len(gold), chunk):
-        rows = torch.from_numpy(np.ascontiguousarray(records[c0:c0 + chunk])).to(dev)
-        n = rows.shape[0]
-        e32 = rows[:, 2 + MAX_LEN + kmax:].contiguous()
-        out = {"lengths": rows[:, 0].contiguous(), "n_atoms": rows[:, 1].contiguous(), "tokens": rows[:, 2:2 + MAX_LEN].contiguous(),
-               "atom_idx": rows[:, 2 + MAX_LEN:2 + MAX_LEN + kmax].contiguous(),
-               "edges": e32.view(torch.uint8)[:, :kmax * kmax].reshape(n, kmax, kmax).contiguous()}
-        packed = engine.graph_pack(out, keep_device=True)
-        read = engine.smiles_read(gold[c0:c0 + chunk], keep_device=True)
+    for packed, read in _both_sides(engine, records, gold, chunk):
         pred, want = texts(packed), texts(read)
         unreadable += sum(bool(int(r["flags"]) & READ_REFUSED) for r in read["read"])
         refused += sum(p is None for p in pred)
@@ -276,6 +265,51 @@ def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: 
             score(name, texts(packed, passes), texts(read, passes) if both else want, read)
     return {"graph_match_device": equal.pop("graph_match_device") / len(gold) if gold else 0.0, "gold_unreadable": int(unreadable),
             "pred_refused": int(refused), **{name: e / len(gold) if gold else 0.0 for name, e in equal.items()}}
+
+
+def _gold_strings(gold, records) -> List[str]:
+    """the gold column as strings, an empty cell as the empty string; one per record"""
+    gold = ["" if g is None or (isinstance(g, float) and np.isnan(g)) else str(g) for g in gold]
+    assert len(gold) == len(records)
+    return gold
+
+
+def _both_sides(engine, records: np.ndarray, gold: Sequence[str], chunk: int):
+    """Per chunk of the gathered dense records (shard.pack_records layout) and their gold strings: (the predictions through
+    graph_pack, the strings through mnx_smiles_read), both with their tables on the device — what the scores of --graph_match
+    compare."""
+    from .shard import MAX_LEN
+    kmax = engine.max_atoms
+    dev = torch.device("cuda", engine.device)
+    for c0 in range(0, len(gold), chunk):
+        rows = torch.from_numpy(np.ascontiguousarray(records[c0:c0 + chunk])).to(dev)
+        n = rows.shape[0]
+        e32 = rows[:, 2 + MAX_LEN + kmax:].contiguous()
+        out = {"lengths": rows[:, 0].contiguous(), "n_atoms": rows[:, 1].contiguous(), "tokens": rows[:, 2:2 + MAX_LEN].contiguous(),
+               "atom_idx": rows[:, 2 + MAX_LEN:2 + MAX_LEN + kmax].contiguous(),
+               "edges": e32.view(torch.uint8)[:, :kmax * kmax].reshape(n, kmax, kmax).contiguous()}
+        yield engine.graph_pack(out, keep_device=True), engine.smiles_read(gold[c0:c0 + chunk], keep_device=True)
+
+
+def graph_tanimoto_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: int = 512, max_bonds: int = 0) -> Dict[str, float]:
+    """--graph_tanimoto: the one graded score beside graph_match_scores' yes-or-no ones, on the same records and gold column (a
+    function of its own: graph_match_scores' parameter list is closed). graph_tanimoto is the mean Tanimoto similarity of
+    prediction against gold by this library's path fingerprint (mnx_fingerprint_pack, mnx_tanimoto: paths of up to max_bonds
+    bonds, --graph_tanimoto_bonds, 0 = 7). BOTH sides pass through mnx_kekulize_pack and mnx_normalize_pack first, so
+    that aromatic and Kekule spellings agree; a refused, unreadable or limited side scores 0. tanimoto_limited counts the sides
+    that passed the step limit (FP_LIMIT). This is NOT the reference's RDKit `tanimoto` score: the reference only names the
+    metric and the path length; the bits are this library's own and no toolkit has seen them."""
+    from .chain import run_chain
+    from .engine import FP_LIMIT
+    gold = _gold_strings(gold, records)
+    limited, similar = 0, []                                   # per item, summed once at the end: no chunk size changes a bit
+    for sides in _both_sides(engine, records, gold, chunk):
+        fps = [engine.fingerprint_pack(run_chain(engine, rec, ("kekulize", "normalize"), keep_last=True)[1], max_bonds=max_bonds,
+                                       keep_device=True) for rec in sides]
+        limited += sum(int(((fp["fp"]["flags"] & FP_LIMIT) != 0).sum()) for fp in fps)
+        # a refused or limited side holds no bit and an unreadable gold string is the empty molecule: each scores 0 by itself
+        similar += engine.tanimoto(fps[0]["bits"], fps[1]["bits"])["similarity"].tolist()
+    return {"graph_tanimoto": math.fsum(similar) / len(gold) if gold else 0.0, "tanimoto_limited": int(limited)}
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -332,6 +366,14 @@ def build_parser() -> argparse.ArgumentParser:
                          "the gold side is left as read, as the reference's --keep_main trims predictions only. The other scores "
                          "stay as they are. Only the component rule is the reference's: the comparison is this project's canonical "
                          "string, NOT the reference's RDKit `graph` score")
+    ap.add_argument("--graph_tanimoto", action="store_true",
+                    help="opt-in, with --graph_match: add graph_tanimoto, the mean Tanimoto similarity of prediction against gold by "
+                         "this library's own path fingerprint (mnx_fingerprint_pack; both sides through mnx_kekulize_pack and "
+                         "mnx_normalize_pack first; DESIGN 4.26), and tanimoto_limited, the sides that passed the step limit. A "
+                         "refused, unreadable or limited side scores 0. The other scores stay as they are. NOT the reference's RDKit "
+                         "`tanimoto` score: the bits are not RDKit's and no toolkit has seen them")
+    ap.add_argument("--graph_tanimoto_bonds", type=int, default=0, metavar="N",
+                    help="with --graph_tanimoto: the longest path in bonds, 1..7; 0 (default) = 7, the reference's maxPath")
     return ap
 
 
@@ -345,9 +387,13 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if not 1 <= args.batch_size <= MAX_BATCH_SIZE:
         ap.error(f"--batch_size must be 1..{MAX_BATCH_SIZE} (reference batches of 2 x batch_size <= {2 * MAX_BATCH_SIZE} rows)")
-    for flag in ("graph_normalize", "graph_kekulize", "graph_formula", "graph_keep_main"):
+    for flag in ("graph_normalize", "graph_kekulize", "graph_formula", "graph_keep_main", "graph_tanimoto"):
         if getattr(args, flag) and not args.graph_match:
             ap.error(f"--{flag} adds a score to --graph_match")
+    if args.graph_tanimoto_bonds and not args.graph_tanimoto:
+        ap.error("--graph_tanimoto_bonds sets the path length of --graph_tanimoto")
+    if not 0 <= args.graph_tanimoto_bonds <= 7:
+        ap.error("--graph_tanimoto_bonds must be 1..7, or 0 for 7")
     dtype = args.dtype or ("fp16" if args.fp16 else DEFAULT_DTYPE)
     max_batch = max(64, 2 * args.batch_size)          # one reference batch is encoded in one launch group
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -399,6 +445,8 @@ def main(argv=None):
                 scores.update(graph_match_scores(engine, kept["records"], list(df["SMILES"]), normalize=args.graph_normalize,
                                                  kekulize=args.graph_kekulize, **({"formula": True} if args.graph_formula else {}),
                                                  **({"keep_main": True} if args.graph_keep_main else {})))
+                if args.graph_tanimoto:
+                    scores.update(graph_tanimoto_scores(engine, kept["records"], list(df["SMILES"]), max_bonds=args.graph_tanimoto_bonds))
         print(write_predictions(args.save_path, args.test_file, table, scores), json.dumps(scores))
     if world > 1:
         dist.barrier()

@@ -19,7 +19,8 @@ import torch
 
 from . import weights as W
 from .chain import BY_NAME, PASSES, run_chain
-from .engine import DEFAULT_DTYPE, MOL_FORMULA_LEFT, MOL_TRUNCATED, NOTE_H_MASK, SMILES_NO_POSITION, SMILES_REFUSED, Engine, MnxError
+from .engine import (DEFAULT_DTYPE, FP_LIMIT, FP_REFUSED, FP_WORDS, MOL_FORMULA_LEFT, MOL_TRUNCATED, NOTE_H_MASK, SMILES_NO_POSITION,
+                     SMILES_REFUSED, Engine, MnxError)
 from .preprocess import load_image_rgb, transform_image, transform_image_gray
 from .tokenizer import coords_labels, get_tokenizer
 
@@ -162,11 +163,11 @@ _STAGE_DICTS = {"origin": _origin_stage, "atom_notes": _notes_stage}
 
 def packed_predictions(engine: Engine, out: dict, tok, on=(), compute_confidence: bool = False, molfile: bool = False,
                        molfile_scale=None, smiles: bool = False, stereo: bool = False, double_bonds: bool = False,
-                       canonical: bool = False, symmetry: bool = False) -> List[dict]:
+                       canonical: bool = False, symmetry: bool = False, fingerprint: bool = False) -> List[dict]:
     """predict_pipeline(packed=True) behind Engine.predict: `out`, its result dict, through mnx_graph_pack, the passes named in
-    `on` (chain.run_chain: their order, and which stage keeps its tables on the device), the canonical ranking and the two
-    writers, to the per-image dicts that predict_pipeline describes. tok: the 'chartok_coords' tokenizer."""
-    writer = molfile or smiles
+    `on` (chain.run_chain: their order, and which stage keeps its tables on the device), the canonical ranking, the two
+    writers and the fingerprint, to the per-image dicts that predict_pipeline describes. tok: the 'chartok_coords' tokenizer."""
+    writer = molfile or smiles or fingerprint                            # the sinks: they read the last record on the device
     drawn = engine.graph_pack(out, keep_device=writer or bool(on))       # what the predicted atoms and bonds are read from
     if (drawn["mols"]["flags"] & MOL_TRUNCATED).any():
         raise RuntimeError(f"a molecule has more atoms than the engine capacity max_atoms={engine.max_atoms}")
@@ -216,6 +217,10 @@ def packed_predictions(engine: Engine, out: dict, tok, on=(), compute_confidence
             p["graph_smiles_order"] = order[a0:a0 + na].tolist() if written else None
             if symmetry:
                 p["stereo_atoms"] = ranked[5][a0:a0 + na].tolist() if written else None
+    if fingerprint:
+        fp = engine.fingerprint_pack(rec)
+        for p, r, words in zip(preds, fp["fp"], fp["bits"]):
+            p["fingerprint"] = None if int(r["flags"]) & (FP_REFUSED | FP_LIMIT) else words.tobytes()
     return preds
 
 
@@ -300,7 +305,31 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
     in the molecule the pass received: expanded['symbols'] with expand, else formula['symbols'] with formula, else the predicted
     atoms), 'flags' (MOL_MAIN_KEPT / MOL_MAIN_TIE of engine.py)}; the per-atom lists of the writers have one entry per atom of
     main['symbols']. The predicted atoms and bonds ('chartok_coords', 'bonds') are what they are without it.
-    The order of the five passes — formula, expand, keep_main, kekulize, normalize — stands in chain.PASSES."""
+    The order of the five passes — formula, expand, keep_main, kekulize, normalize — stands in chain.PASSES.
+    predict_fingerprints is this call with the path fingerprint of every molecule in its dict."""
+    return _pipeline(engine, images, tokenizer, ref_batch_size, max_len, beam_size, compute_confidence, labels, free_run, packed,
+                     molfile, molfile_scale, smiles, stereo, double_bonds, canonical, expand, symmetry, normalize, kekulize, formula,
+                     keep_main, fingerprint=False)
+
+
+def predict_fingerprints(engine: Engine, images: torch.Tensor, tokenizer=None, **options) -> List[dict]:
+    """predict_pipeline(engine, images, tokenizer, packed=True, **options) with one more sink behind the last pass, beside the
+    writers: every dict gains 'fingerprint', the 2048 bits of the molecule's paths of up to 7 bonds as 256 bytes (64
+    little-endian words of mnx_fingerprint_pack; the rule: include/molnextr_hip.h — this library's own, after the idea of
+    Daylight's and RDKit's path fingerprints, NOT RDKit's bits), None for a molecule that is refused (FP_REFUSED) or passes the
+    step limit (FP_LIMIT). options: predict_pipeline's keywords (packed is set here: the paths are walked in the packed tables);
+    kekulize=True and normalize=True make an aromatic and a Kekule drawing give the same bits. Engine.tanimoto compares two. A
+    function of its own because predict_pipeline's parameter list is closed."""
+    if not options.setdefault("packed", True):
+        raise ValueError("predict_fingerprints needs packed=True: the paths are walked in the packed tables")
+    return _pipeline(engine, images, tokenizer, fingerprint=True, **options)
+
+
+def _pipeline(engine, images, tokenizer=None, ref_batch_size=16, max_len=None, beam_size=1, compute_confidence=False, labels=None,
+              free_run=False, packed=False, molfile=False, molfile_scale=None, smiles=False, stereo=False, double_bonds=False,
+              canonical=False, expand=False, symmetry=False, normalize=False, kekulize=False, formula=False, keep_main=False,
+              fingerprint=False) -> List[dict]:
+    """The body of predict_pipeline (its arguments, its defaults) and of predict_fingerprints (fingerprint=True)."""
     tok =(tokenizer or get_tokenizer())["chartok_coords"]
     why = {**{p.name: p.packed_why for p in PASSES}, "molfile": "the molfiles are written from the packed tables",
            "smiles": "the graph SMILES are written from the packed tables"}
@@ -333,7 +362,7 @@ def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_b
         on = [name for name, given in (("formula", formula), ("expand", expand), ("keep_main", keep_main), ("kekulize", kekulize),
                                        ("normalize", normalize)) if given]
         return packed_predictions(engine, out, tok, on, compute_confidence, molfile, molfile_scale, smiles, stereo, double_bonds,
-                                  canonical, symmetry)
+                                  canonical, symmetry, fingerprint)
     scores = out["scores"].cpu().numpy() if beam_size > 1 else None
     lens = out["lengths"].cpu().numpy()
     toks = out["tokens"].cpu().numpy()
@@ -408,6 +437,40 @@ def canonical_smiles(engine: Engine, smiles_list, expand: bool = False, normaliz
             for item, flags in zip(out, stages[row.name]["mols"]["flags"]):
                 item[row.flags_key] = int(flags)
     return out
+
+
+def smiles_fingerprints(engine: Engine, smiles_list, max_bonds: int = 0, **passes) -> List[dict]:
+    """The path fingerprints of a caller's own SMILES: mnx_smiles_read, the passes named (canonical_smiles' pass options, in the
+    chain's order), then mnx_fingerprint_pack instead of a writer. Per item {'fingerprint': the 2048 bits of the molecule's paths
+    of up to max_bonds bonds (0: 7) as 256 bytes — this library's own rule, NOT RDKit's bits —, None where the reader refused the
+    string or the molecule is refused or limited; 'read_flags' (engine.READ_*), 'fingerprint_flags' (engine.FP_*)}."""
+    from .engine import READ_REFUSED
+    smiles_list = list(smiles_list)
+    if not smiles_list:
+        return []
+    unknown = set(passes) - set(BY_NAME)
+    if unknown:
+        raise TypeError(f"smiles_fingerprints: no pass named {sorted(unknown)}")
+    read = engine.smiles_read(smiles_list, keep_device=True)
+    fp = engine.fingerprint_pack(run_chain(engine, read, [name for name, given in passes.items() if given], keep_last=True)[1], max_bonds=max_bonds)
+    return [{"fingerprint": None if int(r["flags"]) & READ_REFUSED or int(f["flags"]) & (FP_REFUSED | FP_LIMIT) else words.tobytes(),
+             "read_flags": int(r["flags"]), "fingerprint_flags": int(f["flags"])} for r, f, words in zip(read["read"], fp["fp"], fp["bits"])]
+
+
+def tanimoto(engine: Engine, smiles_a, smiles_b, **passes) -> List[float]:
+    """The Tanimoto similarity of the path fingerprints of two lists of SMILES, item by item (mnx_fingerprint_pack and
+    mnx_tanimoto; passes: smiles_fingerprints' options — kekulize=True, normalize=True make aromatic and Kekule spellings agree).
+    A string the reader refuses and a molecule that is refused or limited score 0.0, as two empty molecules do. This library's own
+    fingerprint: NOT RDKit's, and not the reference's `tanimoto` score."""
+    smiles_a, smiles_b = list(smiles_a), list(smiles_b)
+    if len(smiles_a) != len(smiles_b):
+        raise ValueError(f"tanimoto compares item with item: {len(smiles_a)} strings against {len(smiles_b)}")
+    if not smiles_a:
+        return []
+    empty = bytes(4 * FP_WORDS)
+    sides = [[x["fingerprint"] or empty for x in smiles_fingerprints(engine, side, **passes)] for side in (smiles_a, smiles_b)]
+    a, b = (np.frombuffer(b"".join(side), np.uint32).reshape(-1, FP_WORDS) for side in sides)
+    return engine.tanimoto(a, b)["similarity"].tolist()
 
 
 def page_scale(image) -> tuple:
@@ -487,7 +550,12 @@ class molnextr:
     graph_kekulize) = only the connected component with the most atoms is written, among equals the one with the lowest atom
     (mnx_main_pack: the reference's _keep_main_molecule — salts, counter-ions and stray atoms are dropped), and every output
     dict gains 'main_atoms', the kept atoms' indices in the molecule the pass received (expanded['symbols'] with graph_expand,
-    atom_sets without), and 'main' (symbols, coords, bonds, origin, flags). The per-atom lists then follow main['symbols']."""
+    atom_sets without), and 'main' (symbols, coords, bonds, origin, flags). The per-atom lists then follow main['symbols'].
+    graph_fingerprint: an attribute, set behind the constructor, whose parameter list is closed (`m.graph_fingerprint = True`;
+    opt-in, default False; the results are put together on the device as with packed_results) = every output dict gains
+    'fingerprint', 256 bytes: the 2048 bits of the paths of up to 7 bonds of the molecule behind the graph_* passes
+    (mnx_fingerprint_pack through predict_fingerprints: this library's own rule, NOT RDKit's bits), None for a molecule that is
+    refused or passes the step limit. molnextr.tanimoto compares SMILES strings by the same fingerprint."""
 
     image_format = "fp32"
     packed_results = False
@@ -502,6 +570,7 @@ class molnextr:
     graph_kekulize = False
     graph_formula = False
     graph_keep_main = False
+    graph_fingerprint = False
 
     def __init__(self, model_path, device=None, max_batch: int = 32, dtype: str = DEFAULT_DTYPE,
                  device_preprocess: bool = True, image_format: str = "fp32", packed_results: bool = False,
@@ -562,6 +631,11 @@ class molnextr:
         (model.canonical_smiles: read on the device, optionally expanded and normalised, written without marks)."""
         given = {"expand": expand, "normalize": normalize, "kekulize": kekulize, "formula": formula, "keep_main": keep_main}
         return canonical_smiles(self.engine, smiles_list, **{name: True for name, v in given.items() if v})
+
+    def tanimoto(self, smiles_a, smiles_b, **passes) -> List[float]:
+        """The similarity of two lists of SMILES, item by item, by this library's path fingerprint (model.tanimoto; passes:
+        smiles_fingerprints' options). NOT RDKit's fingerprint."""
+        return tanimoto(self.engine, smiles_a, smiles_b, **passes)
 
     _groups_done = 0          # groups of the running predict_images call that have produced predictions
 
@@ -732,7 +806,7 @@ class molnextr:
         group = (self.group_images // batch_size) * batch_size
         groups = [input_images[i:i + group] for i in range(0, len(input_images), group)]
         conf = {"compute_confidence": True} if return_confidence else {}
-        if self.packed_results or self.graph_molfile or self.graph_smiles:
+        if self.packed_results or self.graph_molfile or self.graph_smiles or self.graph_fingerprint:
             conf["packed"] = True
         if self.graph_smiles:
             conf["smiles"] = True
@@ -754,7 +828,8 @@ class molnextr:
                     rows = slice(len(preds), len(preds) + x.shape[0])
                     conf.update(labels=labels[rows], free_run=cut[rows])
                 preds += self._with_fallback(
-                    lambda eng: predict_pipeline(eng, x, self.tokenizer, ref_batch_size=batch_size, **conf))
+                    lambda eng: (predict_fingerprints if self.graph_fingerprint else predict_pipeline)(
+                        eng, x, self.tokenizer, ref_batch_size=batch_size, **conf))
                 self._groups_done += 1
         finally:
             if hasattr(gen, "close"):
@@ -798,6 +873,8 @@ class molnextr:
                 d["hydrogens"] = pred["normalized"]["hydrogens"]
             if "main" in pred:                                # graph_keep_main: where the main molecule's atoms came from
                 d["main_atoms"] = pred["main"]["origin"]
+            if "fingerprint" in pred:                         # graph_fingerprint: 256 bytes, None when refused or limited
+                d["fingerprint"] = pred["fingerprint"]
             if return_atoms_bonds:
                 c = pred["chartok_coords"]
                 atoms = []

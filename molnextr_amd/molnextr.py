@@ -58,6 +58,13 @@ def canonical_smiles(smiles_list, expand: bool = False, normalize: bool = False,
                                                              **({"keep_main": True} if keep_main else {}))
 
 
+def tanimoto(smiles_a, smiles_b, **passes):
+    """The similarity of two lists of SMILES, item by item, as a list of floats (no reference counterpart; model.tanimoto): the
+    Tanimoto similarity of this library's own path fingerprints, NOT RDKit's. passes: canonical_smiles' pass options; kekulize=True
+    and normalize=True make aromatic and Kekule spellings agree. A refused or limited side scores 0.0."""
+    return MolNexTRSingleton.get_instance().tanimoto(smiles_a, smiles_b, **passes)
+
+
 def get_predictions(imagepath: str, atoms_bonds: bool = False, smiles: bool = True, predicted_molfile: bool = False):
     """Predictions for one chemical-structure image (reference molnextr.py:214-309)."""
     start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

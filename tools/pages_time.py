@@ -44,6 +44,9 @@ is part of the product path and no number is asserted.
 (k) (only when asked for: --part k) the main molecule on the device: mnx_main_pack alone, against mnx_expand_pack on the same
     tables (the neighbouring pass of the same three-launch shape), on the drug-like tables of part x and on those with every fifth
     bond record taken out, so that most molecules fall apart; `--main-out FILE` writes the table to a file of its own.
+(p) (only when asked for: --part p) path fingerprints on the device: one mnx_fingerprint_pack call (one launch) against one
+    mnx_smiles_pack_canonical call (four launches) on the same drug-like tables, at paths of up to 7 bonds and of up to 2, then
+    one mnx_tanimoto call over the rows against their neighbours; `--fingerprint-out FILE` writes the table to a file of its own.
 The variants of a part alternate inside every repeat (A B A B ...), the table reports the median and the min .. max spread of
 each, and the spread of the fp32 path against itself is the yardstick for "not slower".
 """
@@ -861,6 +864,66 @@ def part_k(repeats, lines):
     eng.close()
 
 
+def part_p(repeats, lines):
+    """Path fingerprints on the device: one mnx_fingerprint_pack call between two events, alternating with one
+    mnx_smiles_pack_canonical call on the same input tables, and one mnx_tanimoto call over the rows it wrote."""
+    import ctypes as C
+    from molnextr_amd import engine as E
+    dev = torch.device("cuda", 0)
+    ck = W.synthetic_checkpoint(0)
+    eng = Engine(ck["encoder"], ck["decoder"], device=0, max_batch=2)
+    ptr = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
+    stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)      # noqa: E731
+    buf = lambda k: torch.empty(max(int(k), 1), dtype=torch.uint8, device=dev)      # noqa: E731
+
+    def measure(rec, what):
+        tables, args = eng._packed_tables(rec)
+        n, na = len(rec["mols"]), len(rec["atoms"])
+        want, written = eng.fingerprint_pack(rec), eng.smiles_pack(rec, canonical=True)
+        fp_d, bits_d = buf(n * 16), torch.empty((n, E.FP_WORDS), dtype=torch.int32, device=dev)
+        recs_d, out_d, totals_w = buf(n * 16), buf(len(written[2])), torch.zeros(2, dtype=torch.int32, device=dev)
+        words = [torch.empty(max(na, 1), dtype=torch.int16, device=dev) for _ in range(3)]
+        both_d, either_d = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+        sim_d = torch.empty(n, dtype=torch.float64, device=dev)
+        turned_d = torch.roll(torch.from_numpy(want["bits"].view(np.int32)).to(dev), 1, 0).contiguous()
+
+        def fingerprint(max_bonds):
+            return eng.lib.mnx_fingerprint_pack(eng.h, *args, ptr(fp_d), ptr(bits_d), max_bonds, 0, stream())
+
+        calls = {"mnx_smiles_pack_canonical": lambda: eng.lib.mnx_smiles_pack_canonical(
+                     eng.h, *args, ptr(recs_d), ptr(words[0]), ptr(words[1]), ptr(words[2]), ptr(out_d), len(written[2]), ptr(totals_w), 0, stream()),
+                 "mnx_fingerprint_pack, 2 bonds": lambda: fingerprint(2), "mnx_fingerprint_pack": lambda: fingerprint(0),
+                 "mnx_tanimoto": lambda: eng.lib.mnx_tanimoto(eng.h, ptr(bits_d), ptr(turned_d), n, ptr(both_d), ptr(either_d), ptr(sim_d), stream())}
+        us = {k: [] for k in calls}
+        for i in range(repeats + 3):
+            for k, call in calls.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                a.record()
+                rc = call()
+                b.record()
+                torch.cuda.synchronize()
+                assert rc == 0, k
+                if i >= 3:
+                    us[k].append(a.elapsed_time(b) * 1000.0)
+        assert bits_d.cpu().numpy().view(np.uint32).tobytes() == want["bits"].tobytes() and not int(totals_w[1])
+        fp = want["fp"]
+        lines.append(f"(p) one call over {n} {what}: {na} atoms, {len(rec['bonds'])} bonds; bits set per molecule median "
+                     f"{int(np.median(fp['n_bits']))} [{int(fp['n_bits'].min())} .. {int(fp['n_bits'].max())}], most paths from one directed "
+                     f"bond {int(fp['max_paths'].max())}, limited {int((fp['flags'] & E.FP_LIMIT != 0).sum())}, refused "
+                     f"{int((fp['flags'] & E.FP_REFUSED != 0).sum())}; mean similarity to the neighbouring row {float(sim_d.mean()):.3f}")
+        lines.append("  device us between two events around the launches, the four alternating   median [min .. max]")
+        for k in us:
+            lines.append(f"  {k:30s} {fmt(us[k])} us")
+        lines.append(f"  fingerprint / canonical writer, median {statistics.median(us['mnx_fingerprint_pack']) / statistics.median(us['mnx_smiles_pack_canonical']):.2f}")
+
+    for labels, what in ((False, "hand-made molecules of drug-like size"),
+                         (True, "hand-made molecules of drug-like size with a table label at every ninth atom")):
+        mols, atoms, bonds, text = druglike_records(1024, labels=labels)
+        measure({"mols": mols, "atoms": atoms, "bonds": bonds, "text": text}, what)
+    eng.close()
+
+
 def part_r(repeats, lines):
     """SMILES read on the device: one mnx_smiles_read call (three launches) over the strings of 1024 hand-made molecules of
     drug-like size between two events, alternating with the one mnx_smiles_pack call that writes those strings from the packed
@@ -979,6 +1042,7 @@ def main():
     ap.add_argument("--normalize-out", default=None, help="write the table of part n to this file")
     ap.add_argument("--formula-out", default=None, help="write the table of part f to this file")
     ap.add_argument("--main-out", default=None, help="write the table of part k to this file")
+    ap.add_argument("--fingerprint-out", default=None, help="write the table of part p to this file")
     ap.add_argument("--pack-only", type=int, default=0, help="run this many mnx_graph_pack calls over 1024 images and exit")
     args = ap.parse_args()
     parts = args.part.split(",")
@@ -1054,6 +1118,13 @@ def main():
         if args.main_out:
             os.makedirs(os.path.dirname(os.path.abspath(args.main_out)), exist_ok=True)
             with open(args.main_out, "w") as f:
+                f.write("\n".join([lines[0]] + lines[first:]) + "\n")
+    if "p" in parts:
+        first = len(lines)
+        part_p(args.repeats, lines)
+        if args.fingerprint_out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.fingerprint_out)), exist_ok=True)
+            with open(args.fingerprint_out, "w") as f:
                 f.write("\n".join([lines[0]] + lines[first:]) + "\n")
     text = "\n".join(lines)
     print(text)
