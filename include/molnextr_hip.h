@@ -1298,6 +1298,92 @@ int mnx_smiles_read(mnx_engine* h, const char* bytes, uint32_t n_bytes, const ui
                     mnx_read* recs, mnx_atom* atoms, uint32_t atom_cap, mnx_bond* bonds, uint32_t bond_cap, char* text,
                     uint32_t text_cap, uint32_t* totals, void* stream);
 
+/* V2000 molfiles read on the device into the packed tables: the inverse of mnx_molfile_pack. A molfile carries what the stereo
+ * writers read and a SMILES cannot — 2D coordinates and wedge flags —, so through this call the stereo of a caller's own molecule
+ * reaches mnx_smiles_pack_stereo / _marks / _canonical / _symmetric, the fingerprints and every pass; and the molfile writer has a
+ * reader that is its check. File b is bytes[offsets[b] .. offsets[b+1]). Everything not said here is as in mnx_smiles_read: the
+ * outputs, totals[4], the capacity protocol, three launches, asynchronous, no allocation, no host synchronisation, deterministic
+ * word for word, records written whole. No symbol tables are needed. den = cfg.coord_bins - 1, as in mnx_molfile_pack.
+ * THE RULE IS THIS LIBRARY'S OWN: the format is the CTfile specification's, the spelling of an atom (brackets, hydrogens, lower
+ * case, '@') is what makes mnx_molfile_pack's own files come back as the tables they were written from. It is NOT a toolkit's
+ * valence or aromaticity model, and no toolkit has read these tables.
+ *
+ * scale: device int32 [n, 2] = {Sx, Sy} in units of 1e-4, each clamped to 1..10000000; null: 100000 each — the writer's argument
+ *   with the writer's meaning. fit: 0 or 1; fit = 1 with a scale is an argument error.
+ * Lines end with '\n'; one '\r' directly in front of it is dropped; the last line may lack the '\n'. A byte a line does not have
+ *   reads as a blank. A numeric field "%3d" is its bytes with blanks trimmed: empty = 0, else an optional '-' and 1 to 3 digits;
+ *   anything else breaks the rule at that line.
+ * Layout. Lines 1 to 3 are ignored. Line 4 holds the atom count in columns 1-3 and the bond count in 4-6 (negative: SYNTAX);
+ *   "V3000" anywhere on it is SYNTAX at line 4. Then the atom lines, the bond lines and the property block. Nothing behind the
+ *   FIRST line that begins "M  END" — whatever that line would otherwise be — is ever read: SDF data items and "$$$$" may follow.
+ *   A file without such a line is SYNTAX at (number of lines + 1); so is a line the layout needs and the file, cut behind its
+ *   "M  END" line, does not have: at (lines read + 1). A file of zero bytes is the empty molecule with flags 0.
+ * Atom line k (line 4 + k): shorter than 31 bytes is SYNTAX. Columns 1-10 x, 11-20 y (z is not read): blanks, an optional '-',
+ *   one or more digits, optionally '.' and zero or more digits, nothing else; the value in units of 1e-4 is the integer part *
+ *   10000 + the first four fraction digits right-padded with zeros. Columns 32-34 the symbol, blanks trimmed; 35-36 the mass
+ *   difference (nonzero: IGNORED); 37-39 the charge code 0 -> 0, 1 -> +3, 2 -> +2, 3 -> +1, 4 -> 0 with IGNORED, 5 -> -1, 6 -> -2,
+ *   7 -> -3, else SYNTAX; 49-51 the valence v, 0..15, else SYNTAX.
+ * Bond line: a1, a2, type, stereo in columns 1-3, 4-6, 7-9, 10-12. a1 and a2 in 1..atoms and different, else SYNTAX. Type 1..4;
+ *   5..8 refuses the file with QUERY; else SYNTAX. Stereo 0 none; 1 class 5 and 6 class 6, on type 1 only; 4 on type 1 and 3 on
+ *   type 2 a plain bond with STEREO_EITHER; anything else SYNTAX. A wedge line "begins at" a1. The record has i < j: a1 < a2
+ *   gives (a1, a2, cls, flip(cls)), a1 > a2 gives (a2, a1, flip(cls), cls), flip: 5 <-> 6. Records sorted by i, then j. The same
+ *   pair on two lines is SYNTAX at the later line.
+ * Property block, up to "M  END". "A  nnn": the next line is the alias of atom nnn (an empty one: no alias; more than 70 bytes:
+ *   SYNTAX at it; no line in front of "M  END": SYNTAX at the "A  " line); bytes below 0x20 and 0x7f are stored as '?'. A line
+ *   that is an alias's text is nothing else, whatever it begins with. "M  CHG", "M  ISO", "M  RGP": a count of 1..8 in columns
+ *   7-9 and entries " aaa vvv" from column 10 + 8e; CHG values -15..15, ISO and RGP 0..999; an atom or value out of range is
+ *   SYNTAX. The first "M  CHG" line resets every atom-block charge to 0. Of two entries of one kind (or two aliases) for one atom
+ *   the later in file order wins. Every other line is skipped and sets IGNORED.
+ * One atom's symbol; the molecule's text is the symbols behind one another, smiles_len their total length (no SMILES). s: the sum
+ *   of its bond orders (classes 1, 5, 6 count 1, 2 counts 2, 3 counts 3, 4 counts 0); arom: it has a class-4 bond.
+ *   1 an alias: '[' alias ']', LABEL. 2 else "R#" with an RGP value n > 0: "[Rn]", LABEL. 3 "D" / "T": H with isotope 2 / 3, which
+ *   an M ISO entry overrides. 4 "R", "R#", "A", "Q", "L", "X", "*" and the empty symbol: the element '*'. 5 any other symbol that
+ *   is none of the 118 elements: '[' symbol ']', LABEL. 6 an element: lower case exactly when arom and it is one of B C N O P S
+ *   Se As. Bracketed when it has a charge, an isotope or v != 0, is outside B C N O P S F Cl Br I '*', or is marked. H of a
+ *   bracket atom: v != 0 and not arom: max(0, (v == 15 ? 0 : v) - s); arom: 0 (the writer's own known limit: [nH] comes back as
+ *   n); else from the table B 3, C 4, N 3|5, O 2, P 3|5, S 2|4|6, F Cl Br I 1, N+ P+ 4, O+ S+ C+ C- 3, N- 2, O- S- 1, B- 4 — the
+ *   smallest target >= s, minus s, 0 without one — with H_DEFAULT set; above 9 written as 9. Marked: an upper-case C with charge
+ *   0 and isotope 0 at which a wedge line begins and whose H (computed as above, bracketed or not) is <= 1. Spelled '[' isotope?
+ *   element '@'? ('H' | 'Hn')? ('+' | '-' | sign and 2..15)? ']', or the bare element. Only '@' is ever written: the writers read
+ *   a mark's presence, not its sense.
+ * Records: index = k, every score 0, mols[b].flags = 0. Bins with fit = 0: xb = (2 ux den + Sx) / (2 Sx), yb = den - (2 uy den +
+ *   Sy) / (2 Sy) in integers; a negative coordinate gives 0 before the subtraction, a result above den gives den, either sets
+ *   CLAMPED. This is the exact inverse of the writer whenever S > den: the writer's rounding moves u by at most 1/2, that is the
+ *   quotient by at most den / (2 S) < 1/2. fit = 1: with minx, miny and span = max(maxx - minx, maxy - miny, 1) over the file's
+ *   atoms, xb = (2 (ux - minx) den + span) / (2 span), yb = den - the same in y: one uniform scale, never CLAMPED.
+ * Refusals. A refused file is the empty molecule with exactly one of the bits, tested in this order: BEYOND (the offsets are out
+ *   of order or lie beyond n_bytes); TOO_LARGE (more than 262144 bytes, or more than 8192 lines with no "M  END" among the first
+ *   8192; three columns hold no count above 999); SYNTAX or QUERY with err_line = the lowest 1-based line at which a rule
+ *   breaks — SYNTAX where both break at that line.
+ * Limits. Reading is the inverse of mnx_molfile_pack on what a drawing holds — wedges from [C@H] / [C@] to a neighbour that is
+ *   no such centre, rev = flip(type), lower-case atoms on class-4 bonds —, not a projection on arbitrary tables: a plain C at
+ *   which a wedge begins comes back as [C@H], a wedge between two centres changes its owner, [nH] comes back as n. An alias's
+ *   text that begins "M  END" ends the file.
+ * Examples: "\n\n\n  2  1\n<C at 1.0 2.0>\n<O at 0 0>\n  1  2  1  0\nM  END\n" -> 2 atoms "C" "O", text "CO", bond (0, 1, 1, 1).
+ *   The same bond line as "  2  1  1  1": (0, 1, 6, 5). An atom "N" with "M  CHG  1   1   1" and v = 4, no bonds: "[NH4+]".
+ *
+ * MNX_ERR_INVALID_ARG (with mnx_last_error, "mnx_molfile_read: ..."): a null pointer, n outside 1..65536, fit outside 0..1 or
+ * fit = 1 with a scale, cfg.coord_bins below 2, misaligned records (mols, atoms, bonds 8-byte; recs, offsets, scale, totals
+ * 4-byte); nothing is launched then. */
+typedef struct mnx_molread {        /* 16 bytes, like mnx_read */
+    uint32_t flags;                 /* MNX_MOLREAD_* */
+    uint32_t err_line;              /* refusal by SYNTAX / QUERY: the lowest 1-based line at which a rule breaks; else 0 */
+    uint32_t n_marked;              /* atoms spelled with '@' */
+    uint32_t reserved;              /* 0 */
+} mnx_molread;
+#define MNX_MOLREAD_SYNTAX 1u          /* refusals: exactly one of bits 0, 1, 3, 4 */
+#define MNX_MOLREAD_TOO_LARGE 2u
+#define MNX_MOLREAD_BEYOND 8u
+#define MNX_MOLREAD_QUERY 16u
+#define MNX_MOLREAD_STEREO_EITHER 32u  /* notes, not refusals */
+#define MNX_MOLREAD_H_DEFAULT 64u
+#define MNX_MOLREAD_CLAMPED 128u
+#define MNX_MOLREAD_IGNORED 256u
+#define MNX_MOLREAD_LABEL 512u
+int mnx_molfile_read(mnx_engine* h, const char* bytes, uint32_t n_bytes, const uint32_t* offsets, int32_t n,
+                     const int32_t* scale, int32_t fit, mnx_mol* mols, mnx_molread* recs, mnx_atom* atoms, uint32_t atom_cap,
+                     mnx_bond* bonds, uint32_t bond_cap, char* text, uint32_t text_cap, uint32_t* totals, void* stream);
+
 /* Path fingerprints, on the device: of every packed molecule a set of 2048 bits that says which paths of atoms and bonds it holds,
  * and (mnx_tanimoto, below) the similarity of two such sets. Everything else at the end of the chain of passes is a yes or a no —
  * the same canonical string or not —; this is the graded answer: how far a prediction is from its gold structure, which known

@@ -293,6 +293,11 @@ hipError_t tanimoto_enqueue(const unsigned* a, const unsigned* b, int n, unsigne
 // (mnx_smiles_read): count, scan and fill, three launches on s
 hipError_t smiles_read_enqueue(const unsigned char* bytes, unsigned n_bytes, const unsigned* offsets, int n, mnx_read* recs,
                                const TablesOut& o, unsigned* totals, hipStream_t s);
+// molfile_read.hip: file b = bytes[offsets[b] .. offsets[b + 1]) read as a V2000 molfile into packed tables of mnx_graph_pack's
+// record types (mnx_molfile_read): count, scan and fill, three launches on s. scale: int [n, 2] or null; fit 0 or 1; den =
+// cfg.coord_bins - 1
+hipError_t molfile_read_enqueue(const unsigned char* bytes, unsigned n_bytes, const unsigned* offsets, int n, const int* scale,
+                                int fit, unsigned den, mnx_molread* recs, const TablesOut& o, unsigned* totals, hipStream_t s);
 hipError_t edges_enqueue(const DecWeights& w, const DecBuffers& bf, const float* hidden, const int* slot_map,
                          const int* atom_idx, const int* n_atoms, int B, int kmax, int row_stride_T,
                          unsigned char* edges, double* scores, hipStream_t s);

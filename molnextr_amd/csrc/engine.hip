@@ -1617,6 +1617,25 @@ int mnx_smiles_read(mnx_engine* h, const char* bytes, uint32_t n_bytes, const ui
     return MNX_OK;
 }
 
+int mnx_molfile_read(mnx_engine* h, const char* bytes, uint32_t n_bytes, const uint32_t* offsets, int32_t n,
+                     const int32_t* scale, int32_t fit, mnx_mol* mols, mnx_molread* recs, mnx_atom* atoms, uint32_t atom_cap,
+                     mnx_bond* bonds, uint32_t bond_cap, char* text, uint32_t text_cap, uint32_t* totals, void* stream) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    auto bad = [&](const char* m) { h->err = std::string("mnx_molfile_read: ") + m; return MNX_ERR_INVALID_ARG; };
+    const TablesOut o = tables_out(mols, atoms, atom_cap, bonds, bond_cap, text, text_cap);
+    if ((!bytes && n_bytes) || !offsets || !recs || tables_out_null(o, totals)) return bad("null pointer");
+    if (n < 1 || n > 65536) return bad("1 <= n <= 65536 required");
+    if (fit != 0 && fit != 1) return bad("fit must be 0 or 1");
+    if (fit && scale) return bad("fit = 1 takes no scale");
+    if (tables_out_skew(o, totals) || (((uintptr_t)recs | (uintptr_t)offsets | (uintptr_t)scale) & 3))
+        return bad("mols, atoms and bonds must be 8-byte aligned, recs, offsets, scale and totals 4-byte");
+    if (h->cfg.coord_bins < 2) return bad("cfg.coord_bins must be at least 2");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, molfile_read_enqueue((const unsigned char*)bytes, n_bytes, offsets, n, scale, fit, (unsigned)h->cfg.coord_bins - 1u, recs, o,
+                                   totals, (hipStream_t)stream));
+    return MNX_OK;
+}
+
 // mnx_smiles_pack, mnx_smiles_pack_stereo, mnx_smiles_pack_marks, mnx_smiles_pack_canonical and mnx_smiles_pack_symmetric: one
 // check, one enqueue path, a pair of kernels per set of marks; canonical: on the ranks that one more kernel in front of them
 // leaves in `rank`; symmetric: canonical with the symmetry rule, which needs `sym_class` too

@@ -30,7 +30,7 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
            "mnx_set_symbol_tables", "mnx_molfile_pack", "mnx_smiles_pack", "mnx_smiles_pack_stereo",
            "mnx_smiles_pack_marks", "mnx_smiles_pack_canonical", "mnx_smiles_pack_symmetric", "mnx_set_fragments", "mnx_expand_pack", "mnx_smiles_read",
            "mnx_beam_scripted", "mnx_edge_probs", "mnx_normalize_pack", "mnx_kekulize_pack", "mnx_formula_pack",
-           "mnx_decode_beam_forced", "mnx_main_pack", "mnx_fingerprint_pack", "mnx_tanimoto")
+           "mnx_decode_beam_forced", "mnx_main_pack", "mnx_fingerprint_pack", "mnx_tanimoto", "mnx_molfile_read")
 
 # Encoder operand modes (include/molnextr_hip.h MNX_DTYPE_*). "fp16x3" — split fp16 operands, three MFMA terms per
 # product, fp32-class results — is the default: it is the fastest mode whose results stay a factor of four inside north_star's
@@ -169,6 +169,14 @@ SMILES_NO_POSITION = 0xFFFF             # `order` of an atom whose molecule got 
 READ_DTYPE = np.dtype([("flags", "<u4"), ("err_pos", "<u4"), ("n_rings", "<u4"), ("reserved", "<u4")], align=True)
 READ_SYNTAX, READ_TOO_LARGE, READ_STEREO_DROPPED, READ_BEYOND = 1, 2, 4, 8
 READ_REFUSED = READ_SYNTAX | READ_TOO_LARGE | READ_BEYOND      # the empty molecule stands in its place
+# mnx_molread, one file of mnx_molfile_read (16 bytes), and its flags (MNX_MOLREAD_*): a rule breaks at line err_line (SYNTAX; QUERY
+# for a query bond type); more than 262144 bytes or 8192 lines; offsets beyond the bytes passed — the refusals —; and the notes: a
+# bond of either / unknown stereo read as plain, an H count from the default-valence table, a coordinate outside the bins, a line or
+# field that was skipped, an atom that is a label
+MOLREAD_DTYPE = np.dtype([("flags", "<u4"), ("err_line", "<u4"), ("n_marked", "<u4"), ("reserved", "<u4")], align=True)
+MOLREAD_SYNTAX, MOLREAD_TOO_LARGE, MOLREAD_BEYOND, MOLREAD_QUERY = 1, 2, 8, 16
+MOLREAD_STEREO_EITHER, MOLREAD_H_DEFAULT, MOLREAD_CLAMPED, MOLREAD_IGNORED, MOLREAD_LABEL = 32, 64, 128, 256, 512
+MOLREAD_REFUSED = MOLREAD_SYNTAX | MOLREAD_TOO_LARGE | MOLREAD_BEYOND | MOLREAD_QUERY      # the empty molecule stands in its place
 # mnx_fp, one molecule of mnx_fingerprint_pack (16 bytes; its FP_WORDS words of bits stand in a table of their own), and its flags
 # (MNX_FP_*): bits 0-3 as mnx_smiles'; the same atom pair in two bond records, a bond from an atom to itself or to no atom of the
 # molecule; a directed bond begins more than max_steps paths. FP_DEFAULT_STEPS is what max_steps = 0 stands for, FP_MAX_STEPS the
@@ -339,6 +347,8 @@ def load_library():
     lib.mnx_tanimoto.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     lib.mnx_smiles_read.restype = C.c_int
     lib.mnx_smiles_read.argtypes = [vp, vp, C.c_uint32, vp, i32, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp]
+    lib.mnx_molfile_read.restype = C.c_int
+    lib.mnx_molfile_read.argtypes = [vp, vp, C.c_uint32, vp, i32, vp, i32, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp]
     lib.mnx_atom_scan.restype = C.c_int
     lib.mnx_atom_scan.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.mnx_preprocess.restype = C.c_int
@@ -1314,6 +1324,46 @@ class Engine:
                                      self.h, _ptr(d_bytes), len(arena), _ptr(d_off), n, mols, _ptr(recs), *arenas, totals, _stream()),
                                  dev, keep_device)
         out["read"] = recs.cpu().numpy().view(READ_DTYPE)
+        return out
+
+    def molfile_read(self, files, scale=None, fit: bool = False, caps=None, keep_device: bool = False) -> dict:
+        """V2000 molfiles (bytes or str, one molecule each; model.split_sdf cuts an SDF) -> the molecules as packed tables with
+        their coordinate bins and wedge classes, read on the device (mnx_molfile_read; the rule — this library's own, NOT a
+        toolkit's valence model: include/molnextr_hip.h): a dict with graph_pack's keys — 'mols', 'atoms', 'bonds', 'text',
+        'totals' — plus 'read' [n] MOLREAD_DTYPE (flags MOLREAD_*, err_line, n_marked). Every pass and writer takes it as it is;
+        smiles_pack(stereo=True, double_bonds=True) finds the marks a SMILES cannot bring. A refused file (MOLREAD_REFUSED) is the
+        empty molecule. scale: int [n, 2] = (Sx, Sy) per file in units of 1e-4, None = 100000 each — molfile_pack's argument, and
+        with the scale a file was written at the bins come back exactly; fit=True (no scale then): one uniform scale per file that
+        fits its atoms into the bins, for files drawn elsewhere. Starts from one atom and one bond per 48 bytes (or caps =
+        (atom_cap, bond_cap, text_cap)) and repeats at most once with the sizes `totals` reports. keep_device: also 'device', as
+        graph_pack."""
+        dev = torch.device("cuda", self.device)
+        raw = [x.encode("utf-8") if isinstance(x, str) else bytes(x) for x in files]
+        n = len(raw)
+        if n < 1:
+            raise ValueError("molfile_read needs at least one file")
+        if fit and scale is not None:
+            raise ValueError("molfile_read: fit=True takes no scale")
+        lens = np.fromiter((len(x) for x in raw), dtype=np.int64, count=n)
+        if int(lens.sum()) > 0xFFFFFFFF:
+            raise ValueError("molfile_read: more than 2^32 - 1 bytes in one call")
+        offsets = np.zeros(n + 1, dtype=np.uint32)
+        offsets[1:] = np.cumsum(lens)
+        arena = b"".join(raw)
+        d_bytes = torch.frombuffer(bytearray(arena) or bytearray(8), dtype=torch.uint8).to(dev)
+        d_off = torch.from_numpy(offsets.view(np.int32)).to(dev)
+        sc = None
+        if scale is not None:
+            sc = torch.as_tensor(np.ascontiguousarray(scale, dtype=np.int32).reshape(n, 2)).to(dev)
+        recs = torch.empty(n * MOLREAD_DTYPE.itemsize, dtype=torch.uint8, device=dev)   # per file: one for both attempts
+        if caps is None:        # an atom line has 31 bytes at least, a bond line 12 in the writer's files; a symbol is short
+            caps = (len(arena) // 48 + n, len(arena) // 48 + n, len(arena) // 16 + n)
+        out = self._sized_tables("mnx_molfile_read", n, caps,
+                                 lambda mols, arenas, totals: self.lib.mnx_molfile_read(
+                                     self.h, _ptr(d_bytes), len(arena), _ptr(d_off), n, _ptr(sc), int(bool(fit)), mols, _ptr(recs), *arenas,
+                                     totals, _stream()),
+                                 dev, keep_device)
+        out["read"] = recs.cpu().numpy().view(MOLREAD_DTYPE)
         return out
 
     def atom_scan(self, tokens: torch.Tensor, lengths: torch.Tensor, kmax: Optional[int] = None):

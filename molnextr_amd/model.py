@@ -418,25 +418,73 @@ def canonical_smiles(engine: Engine, smiles_list, expand: bool = False, normaliz
     keep_main: mnx_main_pack behind the expansion and in front of kekulize — only the connected component with the most atoms is
     written, among equals the one with the lowest atom (the reference's _keep_main_molecule: 'CCO.[Na+]' is written as 'CCO'
     is); the items gain 'main_flags' (engine.MOL_MAIN_KEPT / MOL_MAIN_TIE)."""
-    from .engine import READ_REFUSED, SMILES_REFUSED
+    from .engine import READ_REFUSED
     smiles_list = list(smiles_list)
     if not smiles_list:
         return []
     on = [name for name, given in (("formula", formula), ("expand", expand), ("keep_main", keep_main), ("kekulize", kekulize),
                                    ("normalize", normalize)) if given]
-    read = engine.smiles_read(smiles_list, keep_device=True)
+    return _canonical_of_read(engine, engine.smiles_read(smiles_list, keep_device=True), on, READ_REFUSED, "err_pos")
+
+
+def _canonical_of_read(engine: Engine, read: dict, on, refused: int, err_key: str, **marks) -> List[dict]:
+    """The back half of canonical_smiles and canonical_molfiles: a reader's tables through the passes named in `on` and the
+    canonical writer (marks: smiles_pack's stereo / double_bonds / symmetry), one item per molecule; refused: the reader's refusal
+    bits, err_key: the field of read['read'] that says where it refused"""
+    from .engine import SMILES_REFUSED
     stages, rec = run_chain(engine, read, on, keep_last=True)
-    recs, _, data, _, _ = engine.smiles_pack(rec, canonical=True)
+    written = engine.smiles_pack(rec, canonical=True, **marks)          # symmetry adds a sixth value
+    recs, data = written[0], written[2]
     out = []
     for r, w in zip(read["read"], recs):
-        ok = not (int(r["flags"]) & READ_REFUSED or int(w["flags"]) & SMILES_REFUSED)
+        ok = not (int(r["flags"]) & refused or int(w["flags"]) & SMILES_REFUSED)
         out.append({"smiles": data[int(w["text0"]):int(w["text0"]) + int(w["len"])].decode("utf-8", "replace") if ok else None,
-                    "read_flags": int(r["flags"]), "err_pos": int(r["err_pos"]), "smiles_flags": int(w["flags"])})
+                    "read_flags": int(r["flags"]), err_key: int(r[err_key]), "smiles_flags": int(w["flags"])})
     for row in PASSES:
         if row.name in stages and row.flags_key:
             for item, flags in zip(out, stages[row.name]["mols"]["flags"]):
                 item[row.flags_key] = int(flags)
     return out
+
+
+def split_sdf(data) -> List[bytes]:
+    """The records of an SDF (bytes or str) as bytes, split at the lines "$$$$" (host only): each begins with its molfile, whose
+    "M  END" line ends what mnx_molfile_read reads, so the data items behind it may stay. Nothing but line ends behind the last
+    "$$$$" is no record."""
+    data = data.encode("utf-8") if isinstance(data, str) else bytes(data)
+    out, start, at = [], 0, 0
+    while at < len(data):
+        nl = data.find(b"\n", at)
+        end = len(data) if nl < 0 else nl + 1
+        if data[at:end].rstrip(b"\r\n") == b"$$$$":
+            out.append(data[start:at])
+            start = end
+        at = end
+    if data[start:].strip(b"\r\n"):
+        out.append(data[start:])
+    return out
+
+
+def canonical_molfiles(engine: Engine, molfiles, fit: bool = True, scale=None, stereo: bool = False, double_bonds: bool = False,
+                       symmetry: bool = False, expand: bool = False, normalize: bool = False, kekulize: bool = False,
+                       formula: bool = False, keep_main: bool = False) -> List[dict]:
+    """A caller's own V2000 molfiles (bytes or str, one molecule each; split_sdf cuts an SDF) in the form the device writes
+    predictions in: mnx_molfile_read, the passes named (canonical_smiles' options, in the chain's order), then
+    mnx_smiles_pack_canonical — with stereo / double_bonds the '@' / '@@' and '/' '\\' that the file's wedges and coordinates
+    resolve, which no SMILES brings into the chain; symmetry: mnx_smiles_pack_symmetric's rule. fit (the default): one uniform
+    scale per file that fits its atoms into the coordinate bins; else scale = (Sx, Sy) per file, mnx_molfile_pack's argument (None
+    with fit=False: 100000 each). Per item canonical_smiles' keys with 'err_line' (of MOLREAD_SYNTAX / MOLREAD_QUERY) in the
+    place of 'err_pos'; 'read_flags' are engine.MOLREAD_*. This library's own reading and ranking, NOT a toolkit's."""
+    from .engine import MOLREAD_REFUSED
+    molfiles = list(molfiles)
+    if not molfiles:
+        return []
+    if scale is not None:
+        fit = False
+    on = [name for name, given in (("formula", formula), ("expand", expand), ("keep_main", keep_main), ("kekulize", kekulize),
+                                   ("normalize", normalize)) if given]
+    read = engine.molfile_read(molfiles, scale=scale, fit=fit, keep_device=True)
+    return _canonical_of_read(engine, read, on, MOLREAD_REFUSED, "err_line", stereo=stereo, double_bonds=double_bonds, symmetry=symmetry)
 
 
 def smiles_fingerprints(engine: Engine, smiles_list, max_bonds: int = 0, **passes) -> List[dict]:
@@ -451,10 +499,28 @@ def smiles_fingerprints(engine: Engine, smiles_list, max_bonds: int = 0, **passe
     unknown = set(passes) - set(BY_NAME)
     if unknown:
         raise TypeError(f"smiles_fingerprints: no pass named {sorted(unknown)}")
-    read = engine.smiles_read(smiles_list, keep_device=True)
+    return _fingerprints_of_read(engine, engine.smiles_read(smiles_list, keep_device=True), passes, READ_REFUSED, max_bonds)
+
+
+def _fingerprints_of_read(engine: Engine, read: dict, passes: dict, refused: int, max_bonds: int) -> List[dict]:
+    """The back half of smiles_fingerprints and molfile_fingerprints: a reader's tables through the passes given and
+    mnx_fingerprint_pack, one item per molecule; refused: the reader's refusal bits"""
     fp = engine.fingerprint_pack(run_chain(engine, read, [name for name, given in passes.items() if given], keep_last=True)[1], max_bonds=max_bonds)
-    return [{"fingerprint": None if int(r["flags"]) & READ_REFUSED or int(f["flags"]) & (FP_REFUSED | FP_LIMIT) else words.tobytes(),
+    return [{"fingerprint": None if int(r["flags"]) & refused or int(f["flags"]) & (FP_REFUSED | FP_LIMIT) else words.tobytes(),
              "read_flags": int(r["flags"]), "fingerprint_flags": int(f["flags"])} for r, f, words in zip(read["read"], fp["fp"], fp["bits"])]
+
+
+def molfile_fingerprints(engine: Engine, molfiles, max_bonds: int = 0, **passes) -> List[dict]:
+    """The path fingerprints of a caller's own V2000 molfiles: mnx_molfile_read, the passes named, then mnx_fingerprint_pack —
+    smiles_fingerprints' items, 'read_flags' being engine.MOLREAD_*. The bits hold no coordinates, so no scale is asked for."""
+    from .engine import MOLREAD_REFUSED
+    molfiles = list(molfiles)
+    if not molfiles:
+        return []
+    unknown = set(passes) - set(BY_NAME)
+    if unknown:
+        raise TypeError(f"molfile_fingerprints: no pass named {sorted(unknown)}")
+    return _fingerprints_of_read(engine, engine.molfile_read(molfiles, fit=True, keep_device=True), passes, MOLREAD_REFUSED, max_bonds)
 
 
 def tanimoto(engine: Engine, smiles_a, smiles_b, **passes) -> List[float]:
@@ -631,6 +697,11 @@ class molnextr:
         (model.canonical_smiles: read on the device, optionally expanded and normalised, written without marks)."""
         given = {"expand": expand, "normalize": normalize, "kekulize": kekulize, "formula": formula, "keep_main": keep_main}
         return canonical_smiles(self.engine, smiles_list, **{name: True for name, v in given.items() if v})
+
+    def canonical_molfiles(self, molfiles, **options) -> List[dict]:
+        """The canonical graph SMILES of the caller's own V2000 molfiles, with the stereo marks their wedges and coordinates
+        resolve when stereo / double_bonds are given (model.canonical_molfiles, whose options these are)."""
+        return canonical_molfiles(self.engine, molfiles, **options)
 
     def tanimoto(self, smiles_a, smiles_b, **passes) -> List[float]:
         """The similarity of two lists of SMILES, item by item, by this library's path fingerprint (model.tanimoto; passes:

@@ -58,6 +58,14 @@ def canonical_smiles(smiles_list, expand: bool = False, normalize: bool = False,
                                                              **({"keep_main": True} if keep_main else {}))
 
 
+def canonical_molfiles(molfiles, **options):
+    """The caller's own V2000 molfiles (model.split_sdf cuts an SDF) in the canonical form the device writes (no reference
+    counterpart; model.canonical_molfiles, whose options these are — stereo=True and double_bonds=True write the marks that the
+    files' wedges and coordinates resolve): per item {'smiles' (None where refused), 'read_flags', 'err_line', 'smiles_flags'}.
+    This library's own reading of a molfile, not a toolkit's."""
+    return MolNexTRSingleton.get_instance().canonical_molfiles(molfiles, **options)
+
+
 def tanimoto(smiles_a, smiles_b, **passes):
     """The similarity of two lists of SMILES, item by item, as a list of floats (no reference counterpart; model.tanimoto): the
     Tanimoto similarity of this library's own path fingerprints, NOT RDKit's. passes: canonical_smiles' pass options; kekulize=True

@@ -32,6 +32,10 @@ is part of the product path and no number is asserted.
 (r) (only when asked for: --part r) SMILES read on the device: one mnx_smiles_read call over the strings of 1024 hand-made
     molecules of drug-like size against the one mnx_smiles_pack call that writes those strings, then the worst strings the
     reader admits, each alone in a call; `--read-out FILE` writes the table to a file of its own.
+(v) (only when asked for: --part v) molfile read on the device: one mnx_molfile_read call over the V2000 molfiles of 1024 hand-made
+    molecules of drug-like size against the one mnx_molfile_pack call that writes those files and against mnx_smiles_read on the
+    same molecules' SMILES, then the worst files the reader admits, each alone in a call; `--molread-out FILE` writes the table
+    to a file of its own.
 (f) (only when asked for: --part f) condensed formulas on the device: mnx_formula_pack alone, against mnx_expand_pack on the same
     tables (the same frame: count, scan, fill, one workgroup per molecule), on the drug-like tables of part x and on those with a
     condensed formula in the place of every label; at the default step limit and at a limit of one step, where every search ends
@@ -1004,6 +1008,100 @@ def part_r(repeats, lines):
     eng.close()
 
 
+def part_v(repeats, lines):
+    """Molfile read on the device: one mnx_molfile_read call (three launches) over the V2000 molfiles of 1024 hand-made molecules
+    of drug-like size between two events, alternating with the one mnx_molfile_pack call that writes those files and with
+    mnx_smiles_read on the SMILES of the same molecules; then the worst files the reader admits, each alone in a call."""
+    import ctypes as C
+    from molnextr_amd import engine as E
+    dev = torch.device("cuda", 0)
+    ck = W.synthetic_checkpoint(0)
+    eng = Engine(ck["encoder"], ck["decoder"], device=0, max_batch=2)
+    ptr = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
+    stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)      # noqa: E731
+    buf = lambda k: torch.empty(max(int(k), 1), dtype=torch.uint8, device=dev)      # noqa: E731
+
+    def timed(calls, check):
+        us = {k: [] for k in calls}
+        for i in range(repeats + 3):
+            for k, call in calls.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                a.record()
+                rc = call()
+                b.record()
+                torch.cuda.synchronize()
+                assert rc == 0 and check(k), k
+                if i >= 3:
+                    us[k].append(a.elapsed_time(b) * 1000.0)
+        return us
+
+    def reader(texts, molfiles):
+        """(the call on exact-size buffers, its buffers, the result of Engine.molfile_read or Engine.smiles_read)"""
+        got = eng.molfile_read(texts) if molfiles else eng.smiles_read(texts)
+        arena = b"".join(texts)
+        offsets = np.zeros(len(texts) + 1, np.uint32)
+        offsets[1:] = np.cumsum([len(x) for x in texts])
+        d_bytes = torch.frombuffer(bytearray(arena), dtype=torch.uint8).to(dev)
+        d_off = torch.from_numpy(offsets.view(np.int32)).to(dev)
+        n, (na, nb, nt) = len(texts), (int(v) for v in got["totals"][:3])
+        keep = (d_bytes, d_off, buf(n * 40), buf(n * 16), buf(na * 24), buf(nb * 16), buf(nt), torch.empty(4, dtype=torch.int32, device=dev))
+        tail = (ptr(keep[2]), ptr(keep[3]), ptr(keep[4]), na, ptr(keep[5]), nb, ptr(keep[6]), nt, ptr(keep[7]))
+
+        def call():
+            if molfiles:
+                return eng.lib.mnx_molfile_read(eng.h, ptr(keep[0]), len(arena), ptr(keep[1]), n, None, 0, *tail, stream())
+            return eng.lib.mnx_smiles_read(eng.h, ptr(keep[0]), len(arena), ptr(keep[1]), n, *tail, stream())
+        return call, keep, got
+
+    mols, atoms, bonds, text = druglike_records(1024)
+    rec = {"mols": mols, "atoms": atoms, "bonds": bonds, "text": text}
+    tables, args = eng._packed_tables(rec)
+    files, data = eng.molfile_pack(rec)
+    texts = [data[int(r["text0"]):int(r["text0"]) + int(r["len"])] for r in files]
+    srecs, _, sdata = eng.smiles_pack(rec)
+    strings = [sdata[int(r["text0"]):int(r["text0"]) + int(r["len"])] for r in srecs]
+    files_d, out_d, totals_w = buf(len(mols) * 16), buf(len(data)), torch.empty(2, dtype=torch.int32, device=dev)
+    read, keep, got = reader(texts, True)
+    sread, skeep, sgot = reader(strings, False)
+    assert not (got["read"]["flags"] & E.MOLREAD_REFUSED).any() and got["mols"]["n_atoms"].tolist() == mols["n_atoms"].tolist()
+    assert got["mols"]["n_bonds"].tolist() == mols["n_bonds"].tolist() and got["atoms"]["x_bin"].tolist() == atoms["x_bin"].tolist()
+    us = timed({"mnx_molfile_pack": lambda: eng.lib.mnx_molfile_pack(eng.h, *args, None, ptr(files_d), ptr(out_d), len(data), ptr(totals_w), stream()),
+                "mnx_molfile_read": read, "mnx_smiles_read": sread},
+               lambda k: not int(totals_w[1] if k == "mnx_molfile_pack" else (keep if k == "mnx_molfile_read" else skeep)[7][3]))
+    assert out_d.cpu().numpy().tobytes() == data and keep[6].cpu().numpy().tobytes() == got["text"]
+    lines.append(f"(v) one call over {len(mols)} hand-made molecules of drug-like size: {len(atoms)} atoms, {len(bonds)} bonds, {len(data)} bytes "
+                 f"of molfiles (mnx_molfile_pack writes them, mnx_molfile_read reads those very files back), {len(sdata)} bytes of SMILES")
+    lines.append("  device us between two events around the launches, the three alternating   median [min .. max]")
+    for k in us:
+        lines.append(f"  {k:18s} {fmt(us[k])} us")
+    lines.append(f"  read / write, median {statistics.median(us['mnx_molfile_read']) / statistics.median(us['mnx_molfile_pack']):.2f}; "
+                 f"molfile read / SMILES read, median {statistics.median(us['mnx_molfile_read']) / statistics.median(us['mnx_smiles_read']):.2f}")
+    atom = b"    0.0000    0.0000    0.0000 C   0  0  0  0  0  0  0  0  0  0  0  0"
+    head = lambda na, nb: b"\n\n\n%3d%3d  0  0  0  0  0  0  0  0999 V2000\n" % (na, nb)      # noqa: E731
+    ring = b"".join(b"%3d%3d  1  0\n" % (k + 1, (k + 1) % 999 + 1) for k in range(999))
+    small = head(1, 0) + atom + b"\nM  END\n"
+    full = head(999, 999) + (atom + b"\n") * 999 + ring + b"".join(b"A  %3d\nlabel%d\n" % (k + 1, k) for k in range(999)) + b"M  END\n"
+    many = head(1, 0) + atom + b"\n" + b"G\n" * (8192 - 6) + b"M  END\n"
+    worst = {"one atom": small,
+             "999 atoms, 999 bonds, 999 aliases": full,
+             "8192 lines": many,
+             "262144 bytes, the molecule behind a first line of 100 KB": b"x" * 100000 + full + b"y" * (262144 - 100000 - len(full))}
+    assert all(len(s) <= 262144 for s in worst.values()) and len(worst["262144 bytes, the molecule behind a first line of 100 KB"]) == 262144
+    calls, keeps = {}, {}
+    for k, s in worst.items():
+        calls[k], keeps[k], got = reader([s], True)
+        assert not int(got["read"]["flags"][0]) & E.MOLREAD_REFUSED, (k, got["read"])
+        lines.append(f"  {k}: {len(s)} bytes, {s.count(10)} lines -> {int(got['mols']['n_atoms'][0])} atoms, {int(got['mols']['n_bonds'][0])} bonds, "
+                     f"{int(got['mols']['smiles_len'][0])} bytes of symbols")
+    us = timed(calls, lambda k: not int(keeps[k][7][3]))
+    lines.append("  one file per call (one workgroup of 256 in count and in fill, three launches)   median [min .. max]")
+    base = statistics.median(us["one atom"])
+    for k in us:
+        lines.append(f"  {k:58s} {fmt(us[k])} us   {statistics.median(us[k]) - base:+.1f} us against one atom")
+    eng.close()
+
+
 def part_c(eng, repeats, lines):
     from molnextr_amd.preprocess import normalise_gray
     dev = torch.device("cuda", eng.device)
@@ -1039,6 +1137,7 @@ def main():
     ap.add_argument("--smiles-out", default=None, help="write the table of part s to this file")
     ap.add_argument("--expand-out", default=None, help="write the table of part x to this file")
     ap.add_argument("--read-out", default=None, help="write the table of part r to this file")
+    ap.add_argument("--molread-out", default=None, help="write the table of part v to this file")
     ap.add_argument("--normalize-out", default=None, help="write the table of part n to this file")
     ap.add_argument("--formula-out", default=None, help="write the table of part f to this file")
     ap.add_argument("--main-out", default=None, help="write the table of part k to this file")
@@ -1097,6 +1196,13 @@ def main():
         if args.read_out:
             os.makedirs(os.path.dirname(os.path.abspath(args.read_out)), exist_ok=True)
             with open(args.read_out, "w") as f:
+                f.write("\n".join([lines[0]] + lines[first:]) + "\n")
+    if "v" in parts:
+        first = len(lines)
+        part_v(args.repeats, lines)
+        if args.molread_out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.molread_out)), exist_ok=True)
+            with open(args.molread_out, "w") as f:
                 f.write("\n".join([lines[0]] + lines[first:]) + "\n")
     if "n" in parts:
         first = len(lines)
