@@ -2,9 +2,9 @@
 // fingerprints (mnx_tanimoto): the one graded answer behind the chain of passes, where every other comparison is a yes or a no.
 // The rule stands in include/molnextr_hip.h ("Path fingerprints"): this library's own, after the idea of Daylight's and RDKit's
 // path fingerprints, NOT their bits. One launch each: the outputs have a fixed size, so there is nothing to count and scan.
-//   fingerprint  one workgroup per molecule. The prologue is canon_rank_kernel's (smiles.hip): admission, the atoms'
-//                interpretation, degrees and unsorted neighbour lists by LDS atomics, the duplicate test. An atom's key is a hash
-//                of the bytes the canonical ranks key on (atom_write.h). The work items are the atoms (the paths of no bonds) and
+//   fingerprint  one workgroup per molecule: admission and the atoms' interpretation (atom_symbol.h), then the unsorted neighbour
+//                lists and the duplicate test of mol_graph.h. An atom's key is a hash of the bytes the canonical ranks key
+//                on (atom_write.h). The work items are the atoms (the paths of no bonds) and
 //                the directed bonds, strided over the threads; a thread walks the paths that begin with its bond depth first
 //                (path_search.h) on a stack of its own in LDS and sets their bits in one bitset in LDS.
 //   tanimoto     a wave per pair of rows, a lane per word: two popcounts, two wave sums, one division.
@@ -16,9 +16,8 @@
 #include "../../include/molnextr_hip.h"
 #include "atom_symbol.h"
 #include "atom_write.h"
-#include "block_scan.h"
 #include "dec_types.h"
-#include "path_search.h"
+#include "mol_graph.h"
 
 namespace mnx {
 
@@ -29,10 +28,7 @@ static_assert(MNX_FP_WORDS == 64 && MNX_FP_MAX_BONDS == paths::MAX_BONDS, "64 wo
 
 namespace {
 
-constexpr int FP_THREADS = 256;
-constexpr int FP_MAX = 1024;                 // atoms held in LDS (999 at most)
-constexpr int FP_PER = FP_MAX / FP_THREADS;
-constexpr int FP_SLOTS = 2 * FP_MAX;         // neighbour-list entries: two per bond (999 bonds at most)
+constexpr int FP_THREADS = MG_THREADS, FP_MAX = MG_MAX, FP_SLOTS = MG_SLOTS;     // the sizes of mol_graph.h
 
 __global__ __launch_bounds__(FP_THREADS) void fingerprint_kernel(
         const PackedTables t, const SymbolTables* __restrict__ st, mnx_fp* __restrict__ recs, unsigned* __restrict__ bits,
@@ -68,37 +64,10 @@ __global__ __launch_bounds__(FP_THREADS) void fingerprint_kernel(
     if (__syncthreads_or(bad)) { refuse(base_flags | PT_BEYOND_TABLES); return; }
     const unsigned atom_flags = base_flags | (__syncthreads_or(pseudo) ? PT_PSEUDO_ATOM : 0u);
 
-    // ---- degrees; a record with i == j or an end that is no atom of the molecule refuses it, as a duplicate pair does ----
-    bad = 0;
-    for (int k = tid; k < nb; k += FP_THREADS) {
-        const unsigned i = B[k].i, j = B[k].j;
-        if (i >= (unsigned)na || j >= (unsigned)na || i == j) { bad = 1; continue; }
-        atomicAdd(&cnt[i], 1u);                           // a count does not depend on the order of its increments
-        atomicAdd(&cnt[j], 1u);
-    }
-    if (__syncthreads_or(bad)) { refuse(atom_flags | MNX_FP_BAD_BOND); return; }
-    {
-        unsigned d[FP_PER], sum = 0, total;
-#pragma unroll
-        for (int q = 0; q < FP_PER; ++q) { d[q] = cnt[FP_PER * tid + q]; sum += d[q]; }
-        unsigned e = block_scan_excl<FP_THREADS>(sum, scan, &total);
-#pragma unroll
-        for (int q = 0; q < FP_PER; ++q) { off[FP_PER * tid + q] = e; cnt[FP_PER * tid + q] = 0; e += d[q]; }
-        if (tid == 0) off[FP_MAX] = total;
-    }
-    __syncthreads();
-    for (int k = tid; k < nb; k += FP_THREADS) {
-        const unsigned i = B[k].i, j = B[k].j, c = bond_class(B[k].type) + 1u;      // the bond word; `rev` is not read
-        lst[off[i] + atomicAdd(&cnt[i], 1u)] = paths::entry(j, c, i);    // any slot of the list: the set of paths is the same
-        lst[off[j] + atomicAdd(&cnt[j], 1u)] = paths::entry(i, c, j);
-    }
-    __syncthreads();
-    int dup = 0;
-    for (int s = tid; s < 2 * nb; s += FP_THREADS) {
-        const unsigned e = lst[s], mine = paths::entry_nbr(e), a = paths::entry_owner(e);
-        for (unsigned u = off[a]; u < off[a + 1]; ++u) dup |= paths::entry_nbr(lst[u]) == mine && u != (unsigned)s;
-    }
-    if (__syncthreads_or(dup)) { refuse(atom_flags | MNX_FP_BAD_BOND); return; }
+    // ---- the neighbour lists (mol_graph.h); a bad record refuses the molecule, as a duplicate pair does ----
+    if (__syncthreads_or(graph_degrees(mol, cnt))) { refuse(atom_flags | MNX_FP_BAD_BOND); return; }
+    graph_lists(mol, cnt, off, scan, lst, [&](int k) { return bond_class(B[k].type) + 1u; });      // the bond word; `rev` is not read
+    if (__syncthreads_or(graph_duplicate(mol, off, lst))) { refuse(atom_flags | MNX_FP_BAD_BOND); return; }
 
     // ---- the atom keys: the written bytes of the canonical ranks' initial key, hashed; a thread rewrites its own entries ----
     unsigned* key = info;

@@ -31,7 +31,9 @@ PATHS_HD unsigned path_hash(unsigned forward, unsigned backward) { return fmix32
 // the path of no bonds: the atom alone
 PATHS_HD unsigned atom_hash(unsigned key) { return path_hash(fnv(FNV_BASIS, key), fnv(FNV_BASIS, key)); }
 
-// ---- an entry of a neighbour list: bits 0-9 the neighbour, bits 10-12 the bond word (1 .. 5), bits 13-22 the list's owner ----
+// ---- an entry of a neighbour list, the one definition (mol_graph.h builds the lists): bits 0-9 the neighbour, bits 10-12 the bond
+//      word (1 .. 5; the SMILES writer keeps the written class there), bits 13-22 the list's owner, a kernel's own from ENTRY_BITS ----
+constexpr unsigned ENTRY_ATOM_BITS = 10, ENTRY_BITS = 2 * ENTRY_ATOM_BITS + 3;
 PATHS_HD unsigned entry(unsigned nbr, unsigned word, unsigned owner) { return nbr | word << 10 | owner << 13; }
 PATHS_HD unsigned entry_nbr(unsigned e) { return e & 1023u; }
 PATHS_HD unsigned entry_word(unsigned e) { return e >> 10 & 7u; }

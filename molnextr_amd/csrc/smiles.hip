@@ -11,8 +11,8 @@
 //   count  one workgroup per molecule: the walk and the length of its string -> recs[b].len / flags / n_rings
 //   scan   exclusive scan of the lengths over the molecules -> recs[b].text0, totals
 //   fill   one workgroup per molecule: the walk again, the bytes behind text0 and the atoms' positions in `order`
-// Inside a workgroup: atoms and neighbour lists in parallel, ONE lane for the search and the ring numbers (at most 999 atoms
-// and 999 bonds: kept simple), then every atom's piece of the string in parallel, placed by a prefix scan. LDS atomics only
+// Inside a workgroup: atoms and neighbour lists (mol_graph.h) in parallel, ONE lane for the search and the ring numbers (at most
+// 999 atoms and 999 bonds: kept simple), then every atom's piece of the string in parallel, placed by a prefix scan. LDS atomics only
 // count degrees and hand out slots of an unsorted list that is sorted afterwards, so no atomic decides a position or an order.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -22,6 +22,7 @@
 #include "atom_write.h"
 #include "block_scan.h"
 #include "dec_types.h"
+#include "mol_graph.h"
 
 namespace mnx {
 
@@ -29,21 +30,16 @@ static_assert(sizeof(mnx_smiles) == 16, "record layout of molnextr_hip.h");
 
 namespace {
 
-constexpr int SM_THREADS = 256;
-constexpr int SM_MAX = 1024;             // atoms held in LDS (999 at most)
-constexpr int SM_PER = SM_MAX / SM_THREADS;
-constexpr int SM_SLOTS = 2 * SM_MAX;     // neighbour-list entries: two per bond (999 bonds at most)
+constexpr int SM_THREADS = MG_THREADS, SM_MAX = MG_MAX, SM_PER = MG_PER, SM_SLOTS = MG_SLOTS;     // the sizes of mol_graph.h
 constexpr unsigned NONE = 0xFFFFu;
 constexpr unsigned REFUSED = PT_TOO_LARGE | PT_BEYOND_TABLES | MNX_SMILES_DUPLICATE_BOND | MNX_SMILES_RING_NUMBERS;
 
-// ---- one entry of a neighbour list ----
-//   bits 0-9 the neighbour, bits 10-12 the bond's written class, bits 13-22 the atom that owns the list, bit 23 a bond of the
-//   search tree (to the parent or to a child); every other bond is a ring bond; STEREO only: bit 24 the bond is a wedge (class
-//   5) as the owner sees it, bit 25 a dash (class 6). The rank sorts copy whole entries, so the bits travel with them.
+// ---- the writer's own bits of a neighbour-list entry, above neighbour, written class (entry_word) and owner (path_search.h) ----
+//   bit 23 a bond of the search tree (to the parent or to a child); every other bond is a ring bond; STEREO only: bit 24 the
+//   bond is a wedge (class 5) as the owner sees it, bit 25 a dash (class 6). The rank sorts copy whole entries, so the bits
+//   travel with them.
 constexpr unsigned SLOT_TREE = 1u << 23, SLOT_UP = 1u << 24, SLOT_DOWN = 1u << 25;
-__device__ __forceinline__ unsigned slot_nbr(unsigned e) { return e & 1023u; }
-__device__ __forceinline__ unsigned slot_cls(unsigned e) { return e >> 10 & 7u; }
-__device__ __forceinline__ unsigned slot_owner(unsigned e) { return e >> 13 & 1023u; }
+static_assert(SLOT_TREE == 1u << paths::ENTRY_BITS, "the first bit above the shared fields");
 __device__ __forceinline__ unsigned slot_seen(unsigned cls) { return cls == 5 ? SLOT_UP : cls == 6 ? SLOT_DOWN : 0u; }
 __device__ __forceinline__ long long slot_z(unsigned e) { return (long long)(e >> 24 & 1u) - (long long)(e >> 25 & 1u); }
 
@@ -92,8 +88,8 @@ __device__ __forceinline__ unsigned long long block_min(unsigned long long v, un
 }
 
 // One workgroup per molecule: rank[atom0 + a] and sym_class[atom0 + a] (may be null) of every atom, 0xFFFF where the molecule
-// is refused on flag bits 0, 1 or 4, and the tie bits in recs[b].flags (0 without one), which count keeps. The prologue is
-// smiles_kernel's: admission, the atoms' interpretation, degrees and unsorted lists by LDS atomics, the duplicate test. The
+// is refused on flag bits 0, 1 or 4, and the tie bits in recs[b].flags (0 without one), which count keeps. The prologue:
+// admission and the atoms' interpretation (atom_symbol.h), the unsorted lists and the duplicate test of mol_graph.h. The
 // keys never leave LDS: per round every list entry becomes r(n) * 8 + c (13 bits), each list is rank-sorted, and an atom's
 // new rank is a count over the other atoms, its list compared only with those of equal old rank (which have its degree: the
 // first key holds it and a round only splits classes). No atomic decides a rank: the lists are sorted by value each round.
@@ -130,36 +126,10 @@ __global__ __launch_bounds__(SM_THREADS) void canon_rank_kernel(
         xy[a] = a < na ? (unsigned)mol.A[a].x_bin << 16 | mol.A[a].y_bin : 0u;
     }
     __syncthreads();
-    for (int k = tid; k < nb; k += SM_THREADS) {
-        const unsigned i = B[k].i, j = B[k].j;
-        if (i >= (unsigned)na || j >= (unsigned)na || i == j) { bad = 1; continue; }
-        atomicAdd(&cnt[i], 1u);                           // a count does not depend on the order of its increments
-        atomicAdd(&cnt[j], 1u);
-    }
+    bad |= graph_degrees(mol, cnt);
     if (__syncthreads_or(bad)) { refuse(); return; }
-    {
-        unsigned d[SM_PER], sum = 0, total;
-#pragma unroll
-        for (int q = 0; q < SM_PER; ++q) { d[q] = cnt[SM_PER * tid + q]; sum += d[q]; }
-        unsigned e = block_scan_excl<SM_THREADS>(sum, scan, &total);
-#pragma unroll
-        for (int q = 0; q < SM_PER; ++q) { off[SM_PER * tid + q] = e; cnt[SM_PER * tid + q] = 0; e += d[q]; }
-        if (tid == 0) off[SM_MAX] = total;
-    }
-    __syncthreads();
-    for (int k = tid; k < nb; k += SM_THREADS) {
-        const unsigned i = B[k].i, j = B[k].j, ty = B[k].type;
-        const unsigned cls = bond_class(ty);
-        raw[off[i] + atomicAdd(&cnt[i], 1u)] = j | cls << 10 | i << 13;   // any slot of the list: every round sorts by value
-        raw[off[j] + atomicAdd(&cnt[j], 1u)] = i | cls << 10 | j << 13;
-    }
-    __syncthreads();
-    int dup = 0;
-    for (int s = tid; s < 2 * nb; s += SM_THREADS) {
-        const unsigned e = raw[s], mine = slot_nbr(e), a = slot_owner(e);
-        for (unsigned u = off[a]; u < off[a + 1]; ++u) dup |= slot_nbr(raw[u]) == mine && u != (unsigned)s;
-    }
-    if (__syncthreads_or(dup)) { refuse(); return; }
+    graph_lists(mol, cnt, off, scan, raw, [&](int k) { return bond_class(B[k].type); });      // any slot: every round sorts by value
+    if (__syncthreads_or(graph_duplicate(mol, off, raw))) { refuse(); return; }
 
     // ---- the initial key: the atom's written bytes (12 at most: '[', three digits, two letters, 'H' digit, sign and two
     //      digits, ']'), then its degree ----
@@ -192,10 +162,10 @@ __global__ __launch_bounds__(SM_THREADS) void canon_rank_kernel(
     //      in vmin the lowest new rank among this thread's atoms that another atom shares ----
     unsigned vmin = NONE;
     auto round = [&]() {
-        for (int s = tid; s < 2 * nb; s += SM_THREADS) key[s] = (unsigned short)(rk[slot_nbr(raw[s])] * 8u + slot_cls(raw[s]));
+        for (int s = tid; s < 2 * nb; s += SM_THREADS) key[s] = (unsigned short)(rk[entry_nbr(raw[s])] * 8u + entry_word(raw[s]));
         __syncthreads();
         for (int s = tid; s < 2 * nb; s += SM_THREADS) {
-            const unsigned a = slot_owner(raw[s]), mine = key[s];
+            const unsigned a = entry_owner(raw[s]), mine = key[s];
             unsigned at = off[a];
             for (unsigned u = off[a]; u < off[a + 1]; ++u) at += key[u] < mine || (key[u] == mine && u < (unsigned)s);
             lst[at] = (unsigned short)mine;
@@ -338,15 +308,11 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
         if (CANON) rnk[a] = a < na ? rank[m.atom0 + a] : (unsigned short)NONE;
     }
     __syncthreads();
-    for (int k = tid; k < nb; k += SM_THREADS) {
-        const unsigned i = B[k].i, j = B[k].j;
-        if (i >= (unsigned)na || j >= (unsigned)na || i == j) { bad = 1; continue; }     // i == j: the molfile writer writes it
+    bad |= graph_degrees(mol, cnt, [&](int k, unsigned i, unsigned j) {     // (a record with i == j: the molfile writer writes it)
         const unsigned ty = type_of(k, i, j);
         wedge |= ty == 5 || ty == 6;
         any |= ty < 1 || ty > 6;
-        atomicAdd(&cnt[i], 1u);                           // a count does not depend on the order of its increments
-        atomicAdd(&cnt[j], 1u);
-    }
+    });
     if (__syncthreads_or(bad)) {                          // (count refuses; fill never comes here: count left len = 0)
         if (!FILL) record(0, base_flags | PT_BEYOND_TABLES, 0);
         return;
@@ -358,34 +324,18 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
         if (SYM) sym_on = !pseudo;
     }
 
-    // ---- neighbour lists: offsets from a scan of the degrees, entries as the bonds come, then each list in ascending order ----
-    {
-        unsigned d[SM_PER], sum = 0, total;
-#pragma unroll
-        for (int q = 0; q < SM_PER; ++q) { d[q] = cnt[SM_PER * tid + q]; sum += d[q]; }
-        unsigned e = block_scan_excl<SM_THREADS>(sum, scan, &total);
-#pragma unroll
-        for (int q = 0; q < SM_PER; ++q) { off[SM_PER * tid + q] = e; cnt[SM_PER * tid + q] = 0; e += d[q]; }
-        if (tid == 0) off[SM_MAX] = total;
-    }
-    __syncthreads();
-    for (int k = tid; k < nb; k += SM_THREADS) {
-        const unsigned i = B[k].i, j = B[k].j, ty = type_of(k, i, j);
-        const unsigned cls = bond_class(ty);
-        const unsigned si = STEREO ? slot_seen(B[k].type) : 0u, sj = STEREO ? slot_seen(B[k].rev) : 0u;     // edges[i][j], edges[j][i]
-        raw[off[i] + atomicAdd(&cnt[i], 1u)] = j | cls << 10 | i << 13 | si;  // any slot of the list: the sort below fixes the order
-        raw[off[j] + atomicAdd(&cnt[j], 1u)] = i | cls << 10 | j << 13 | sj;
-    }
-    __syncthreads();
+    // ---- neighbour lists: entries as the bonds come (end 0 sees edges[i][j], end 1 edges[j][i]), then each list in ascending order ----
+    graph_lists(mol, cnt, off, scan, raw, [&](int k) { return bond_class(type_of(k, B[k].i, B[k].j)); },
+                [&](int k, int end) { return STEREO ? slot_seen(end ? B[k].rev : B[k].type) : 0u; });
     int dup = 0;
-    for (int s = tid; s < 2 * nb; s += SM_THREADS) {      // rank of every entry inside its list; equal neighbours = a duplicate pair
-        const unsigned e = raw[s], mine = slot_nbr(e), a = slot_owner(e);
+    for (int s = tid; s < 2 * nb; s += SM_THREADS) {      // rank of every entry inside its list, with mol_graph.h's duplicate test
+        const unsigned e = raw[s], mine = entry_nbr(e), a = entry_owner(e);
         unsigned rank = 0;
         for (unsigned t = off[a]; t < off[a + 1]; ++t) {
-            const unsigned n = slot_nbr(raw[t]);
+            const unsigned n = entry_nbr(raw[t]);
             if (CANON) rank += rnk[n] < rnk[mine] || (rnk[n] == rnk[mine] && t < (unsigned)s);
             else rank += n < mine || (n == mine && t < (unsigned)s);
-            dup |= n == mine && t != (unsigned)s;
+            dup |= graph_twice(n, t, mine, (unsigned)s);
         }
         adj[off[a] + rank] = e;
     }
@@ -427,7 +377,7 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
                     continue;
                 }
                 cur[a] = (unsigned short)(c + 1);
-                const unsigned n = slot_nbr(adj[c]);
+                const unsigned n = entry_nbr(adj[c]);
                 if (n == parent[a]) { adj[c] |= SLOT_TREE; continue; }
                 if (pos[n] != NONE) continue;             // a ring bond
                 adj[c] |= SLOT_TREE;
@@ -455,9 +405,9 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
 
     // ---- every list once more, now in ascending written position of the neighbour: ring closures, then ring openings ----
     for (int s = tid; s < 2 * nb; s += SM_THREADS) {
-        const unsigned e = adj[s], mine = pos[slot_nbr(e)], a = slot_owner(e);
+        const unsigned e = adj[s], mine = pos[entry_nbr(e)], a = entry_owner(e);
         unsigned rank = 0;
-        for (unsigned t = off[a]; t < off[a + 1]; ++t) rank += pos[slot_nbr(adj[t])] < mine;
+        for (unsigned t = off[a]; t < off[a + 1]; ++t) rank += pos[entry_nbr(adj[t])] < mine;
         raw[off[a] + rank] = e;
     }
     __syncthreads();
@@ -473,10 +423,10 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
             used[0] &= ~closed[0]; used[1] &= ~closed[1];
             closed[0] = closed[1] = 0;
             unsigned opens = 0;
-            for (unsigned s = off[a]; s < off[a + 1]; ++s) opens += !(raw[s] & SLOT_TREE) && pos[slot_nbr(raw[s])] > (unsigned)p;
+            for (unsigned s = off[a]; s < off[a + 1]; ++s) opens += !(raw[s] & SLOT_TREE) && pos[entry_nbr(raw[s])] > (unsigned)p;
             if (in_use + opens > 99u) { fail = 1; break; }
             for (unsigned s = off[a]; s < off[a + 1]; ++s) {
-                const unsigned e = raw[s], n = slot_nbr(e);
+                const unsigned e = raw[s], n = entry_nbr(e);
                 if (e & SLOT_TREE) continue;
                 if (pos[n] < (unsigned)p) {
                     const unsigned k = rnum[s] - 1u;
@@ -490,7 +440,7 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
                 unsigned lo = off[n], hi = off[n + 1] - 1u;           // n's entry for a: its list is ordered by written position
                 while (lo < hi) {
                     const unsigned mid = (lo + hi) >> 1;
-                    if (pos[slot_nbr(raw[mid])] < (unsigned)p) lo = mid + 1u; else hi = mid;
+                    if (pos[entry_nbr(raw[mid])] < (unsigned)p) lo = mid + 1u; else hi = mid;
                 }
                 rnum[lo] = (unsigned char)(k + 1u);
             }
@@ -510,7 +460,7 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
         for (int a = tid; a < na; a += SM_THREADS) {
             unsigned l = NONE;
             for (unsigned s = off[a]; s < off[a + 1]; ++s)
-                if (!(raw[s] & SLOT_TREE)) l = min(l, (unsigned)pos[slot_nbr(raw[s])]);
+                if (!(raw[s] & SLOT_TREE)) l = min(l, (unsigned)pos[entry_nbr(raw[s])]);
             cur[a] = (unsigned short)l;
         }
         __syncthreads();
@@ -524,7 +474,7 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
     // an equal pair at u: two neighbours other than `skip` of one class, both on bonds off every cycle
     auto equal_pair = [&](unsigned u, unsigned skip) {
         auto free_nbr = [&](unsigned e) {                 // the neighbour of a list entry of u, NONE where the bond is on a cycle
-            const unsigned n = slot_nbr(e), x = pos[n] < pos[u] ? u : n;
+            const unsigned n = entry_nbr(e), x = pos[n] < pos[u] ? u : n;
             return (e & SLOT_TREE) && n != skip && cur[x] >= pos[x] ? n : NONE;
         };
         for (unsigned s = off[u]; s + 1 < off[u + 1]; ++s) {
@@ -553,16 +503,16 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
                 unsigned seen = 0, other = 0;
                 for (unsigned s = lo; s < hi; ++s) {
                     seen |= raw[s] & (SLOT_UP | SLOT_DOWN);
-                    other |= slot_cls(raw[s]) != B_SINGLE;
+                    other |= entry_word(raw[s]) != B_SINGLE;
                 }
                 const unsigned deg = hi - lo;
                 const bool candidate = seen && !other && info_cls(w) == CLS_ATOM && deg + (unsigned)info_h(w) == 4u;
                 if (SYM && sym_on && candidate) sym = equal_pair((unsigned)a, NONE);      // symmetry first: no determinant then
                 if (candidate && !sym) {
                     const unsigned e0 = raw[lo], e1 = raw[lo + 1], e2 = raw[lo + 2], e3 = deg == 4u ? raw[lo + 3] : e2;
-                    auto group = [&](unsigned e) { return !(e & SLOT_TREE) ? 1 : pos[slot_nbr(e)] < p ? 0 : 2; };
+                    auto group = [&](unsigned e) { return !(e & SLOT_TREE) ? 1 : pos[entry_nbr(e)] < p ? 0 : 2; };
                     const long long cx = mol.A[a].x_bin, cy = mol.A[a].y_bin;
-                    const mnx_atom A0 = mol.A[slot_nbr(e0)], A1 = mol.A[slot_nbr(e1)], A2 = mol.A[slot_nbr(e2)], A3 = mol.A[slot_nbr(e3)];
+                    const mnx_atom A0 = mol.A[entry_nbr(e0)], A1 = mol.A[entry_nbr(e1)], A2 = mol.A[entry_nbr(e2)], A3 = mol.A[entry_nbr(e3)];
                     const long long x0 = A0.x_bin - cx, y0 = cy - A0.y_bin, z0 = slot_z(e0);      // the image's y points down
                     const long long x1 = A1.x_bin - cx, y1 = cy - A1.y_bin, z1 = slot_z(e1);
                     const long long x2 = A2.x_bin - cx, y2 = cy - A2.y_bin, z2 = slot_z(e2);
@@ -610,7 +560,7 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
             if (!SYM) {                                   // (SYM: low stands since the pass in front of STEREO)
                 unsigned l = NONE;
                 for (unsigned s = off[a]; s < off[a + 1]; ++s)
-                    if (!(raw[s] & SLOT_TREE)) l = min(l, (unsigned)pos[slot_nbr(raw[s])]);
+                    if (!(raw[s] & SLOT_TREE)) l = min(l, (unsigned)pos[entry_nbr(raw[s])]);
                 low[a] = (unsigned short)l;
             }
             child_dir[a] = 0;
@@ -642,9 +592,9 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
                 const unsigned u = end ? (unsigned)c : a, v = end ? a : (unsigned)c;
                 int before = 0;
                 for (unsigned s = off[u]; s < off[u + 1]; ++s) {
-                    const unsigned e = raw[s], n = slot_nbr(e);
-                    if (n == v) { candidate &= slot_cls(e) == B_DOUBLE; continue; }
-                    candidate &= slot_cls(e) == B_SINGLE;
+                    const unsigned e = raw[s], n = entry_nbr(e);
+                    if (n == v) { candidate &= entry_word(e) == B_DOUBLE; continue; }
+                    candidate &= entry_word(e) == B_SINGLE;
                     const int sd = side(u, n);
                     resolved &= sd != 0 && sd != before;
                     before = sd;
@@ -660,7 +610,7 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
             for (int end = 0; end < 2; ++end) {
                 const unsigned u = end ? (unsigned)c : a, v = end ? a : (unsigned)c;
                 for (unsigned s = off[u]; s < off[u + 1]; ++s) {        // tree bonds in written order: a's parent, then the children
-                    const unsigned e = raw[s], n = slot_nbr(e);
+                    const unsigned e = raw[s], n = entry_nbr(e);
                     if (n == v || !(e & SLOT_TREE)) continue;
                     const unsigned up = side(u, n) > 0;
                     if (pos[n] < pos[u]) f0 = up;
@@ -706,7 +656,7 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
             auto has_directed = [&](unsigned u) {
                 unsigned any_dir = child_dir[u];
                 for (unsigned s = off[u]; s < off[u + 1]; ++s)
-                    if ((raw[s] & SLOT_TREE) && pos[slot_nbr(raw[s])] > pos[u]) any_dir |= child_dir[slot_nbr(raw[s])];
+                    if ((raw[s] & SLOT_TREE) && pos[entry_nbr(raw[s])] > pos[u]) any_dir |= child_dir[entry_nbr(raw[s])];
                 return any_dir != 0;
             };
             for (int k = tid; k < nb; k += SM_THREADS) {  // a double bond without marks of its own between two directed bonds
@@ -731,8 +681,8 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
             if (paren[a]) put('(');
             for (unsigned s = off[a]; s < off[a + 1]; ++s) {
                 const unsigned e = raw[s];
-                if ((e & SLOT_TREE) && slot_nbr(e) == par) {
-                    const char c = EZ && done_child[a] ? (char)done_child[a] : bond_symbol(slot_cls(e), aromatic && info_aromatic(info[par]));
+                if ((e & SLOT_TREE) && entry_nbr(e) == par) {
+                    const char c = EZ && done_child[a] ? (char)done_child[a] : bond_symbol(entry_word(e), aromatic && info_aromatic(info[par]));
                     if (c) put(c);
                     break;
                 }
@@ -740,10 +690,10 @@ __global__ __launch_bounds__(SM_THREADS) void smiles_kernel(
         }
         put_atom(w, elem[a], STEREO ? mark_of(a) : 0u, put);
         for (unsigned s = off[a]; s < off[a + 1]; ++s) {
-            const unsigned e = raw[s], n = slot_nbr(e), r = rnum[s];
+            const unsigned e = raw[s], n = entry_nbr(e), r = rnum[s];
             if (e & SLOT_TREE) continue;
             if (pos[n] > p) {
-                const char c = bond_symbol(slot_cls(e), aromatic && info_aromatic(info[n]));
+                const char c = bond_symbol(entry_word(e), aromatic && info_aromatic(info[n]));
                 if (c) put(c);
             }
             if (r >= 10) { put('%'); put((char)('0' + r / 10)); }
