@@ -8,7 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/molnextr_hip.h"
-#include "dec_types.h"
+#include "table_types.h"
 
 namespace mnx {
 
@@ -174,7 +174,7 @@ __device__ __forceinline__ unsigned interpret_atom(const SymbolTables* __restric
     return interpret_atom(st, s, n, sym, &name);
 }
 
-// ---- one molecule of the packed tables (PackedTables, dec_types.h) ----
+// ---- one molecule of the packed tables (PackedTables, table_types.h) ----
 // the flag bits that mean the same in both writers' records (molnextr_hip.h)
 constexpr unsigned PT_TOO_LARGE = MNX_MOLFILE_TOO_LARGE, PT_BEYOND_TABLES = MNX_MOLFILE_BEYOND_TABLES;
 constexpr unsigned PT_PSEUDO_ATOM = MNX_MOLFILE_PSEUDO_ATOM, PT_TRUNCATED = MNX_MOLFILE_TRUNCATED;

@@ -1,13 +1,8 @@
-// dec_types.h — decoder-side device structures shared by decoder.hip and engine.hip (internal).
+// dec_types.h — the decoder's device structures and the enqueue prototypes of decoder.hip and dec_fused.hip, shared with the
+// host files engine*.hip (internal). The packed-table layer's are table_types.h and table_passes.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-struct mnx_mol;     // include/molnextr_hip.h: the records of mnx_graph_pack
-struct mnx_atom;
-struct mnx_bond;
-struct mnx_molfile; // the record of mnx_molfile_pack
-struct mnx_smiles;  // the record of mnx_smiles_pack
 
 namespace mnx {
 
@@ -136,12 +131,6 @@ struct TokenClasses {
     int lbracket, rbracket, id_C, id_l, id_B, id_r, x0, y0, vocab;
 };
 
-// names of the vocabulary's symbol ids as UTF-8 bytes (mnx_set_vocab_text): what graph_pack.hip spells the SMILES with
-struct VocabText {
-    unsigned char len[256];        // bytes of id i's name, 0..8 (0 beyond the ids that were set)
-    unsigned char name[256][8];
-};
-
 // fp32 projected memory K / V of `n_blocks` (image, layer, K|V, head) blocks of S rows -> quantised blocks at dst (kvq.h)
 hipError_t kvq_pack_enqueue(const float* src, char* dst, int n_blocks, int S, int Sq, hipStream_t s);
 // Label-guided decoding (mnx_decode_guided / mnx_predict_guided): what an admission installs for its rows. The engine owns
@@ -199,105 +188,6 @@ hipError_t confidence_enqueue(const DecBuffers& b, const TokenClasses* tc_dev, c
 hipError_t confidence_enqueue_raw(const TokenClasses* tc_dev, const int* tokens, const int* lens, const float* logp, int n,
                                   int T, int kmax, const int* atom_idx, const int* n_atoms, const double* scores,
                                   double* atom_scores, double* overall, hipStream_t s);
-// the arenas a table writer (mnx_graph_pack, mnx_expand_pack, mnx_smiles_read) fills: the molecule records, then the atom and
-// bond records as 64-bit words and the text, each with its capacity in records / bytes. Passed to kernels by value; what is
-// done with it is in tables_out.h.
-struct TablesOut {
-    mnx_mol* mols;
-    unsigned long long* atoms;  unsigned atom_cap;
-    unsigned long long* bonds;  unsigned bond_cap;
-    char* text;                 unsigned text_cap;
-};
-// graph_pack.hip: the dense outputs of n rows ([n,T] ids, [n,kmax] atoms, [n,kmax,kmax] bonds; the three score pointers all
-// null or all set) as packed records (mnx_graph_pack): count, scan and fill, three launches on s
-hipError_t graph_pack_enqueue(const TokenClasses* tc_dev, const VocabText* vt_dev, const int* tokens, const int* lens, int n,
-                              int T, int kmax, const int* atom_idx, const int* n_atoms, const unsigned char* edges,
-                              const double* atom_scores, const double* edge_scores, const double* overall, const TablesOut& o,
-                              unsigned* totals, hipStream_t s);
-// the R-group and abbreviation names (mnx_set_symbol_tables), sorted bytewise: what atom_symbol.h looks an atom's symbol up in
-struct SymbolTables {
-    int n;
-    unsigned char len[512];        // bytes of name i, 1..16
-    unsigned char kind[512];       // 1 R-group, 2 abbreviation
-    unsigned char name[512][16];
-};
-// the packed tables of mnx_graph_pack as mnx_molfile_pack and mnx_smiles_pack receive them: each table with the number of records
-// the caller vouches for (a molecule that points beyond them is refused, atom_symbol.h). Passed to kernels by value.
-struct PackedTables {
-    const mnx_mol* mols;        int n;
-    const mnx_atom* atoms;      unsigned n_atom_records;
-    const mnx_bond* bonds;      unsigned n_bond_records;
-    const unsigned char* text;  unsigned n_text_bytes;
-};
-// molfile.hip: the molecules of t as V2000 molfiles behind one another in `out` (mnx_molfile_pack): count, scan and fill, three
-// launches on s
-hipError_t molfile_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, const int* scale, int coord_bins,
-                                mnx_molfile* files, char* out, unsigned out_cap, unsigned* totals, hipStream_t s);
-// smiles.hip: the molecules of t as graph SMILES behind one another in `out`, the atoms' written positions in `order` (may be
-// null) (mnx_smiles_pack; marks, MNX_SMILES_MARK_*: with the '@' / '@@' of mnx_smiles_pack_stereo and the '/' '\\' of
-// mnx_smiles_pack_marks): count, scan and fill, three launches on s.
-// rank set (null otherwise): the same on canonical atom ranks (mnx_smiles_pack_canonical) — one launch in front leaves the ranks
-// in `rank` and the symmetry classes in `sym_class` (may be null), then count, scan and fill on those ranks; four launches on s.
-// symmetric (rank and sym_class set): the same four launches with the symmetry rule of mnx_smiles_pack_symmetric for the marks,
-// every atom's MNX_ATOM_* bits in `atom_marks` (may be null)
-hipError_t smiles_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, unsigned marks, mnx_smiles* recs,
-                               unsigned short* order, unsigned short* rank, unsigned short* sym_class, char* out,
-                               unsigned out_cap, unsigned* totals, hipStream_t s, bool symmetric = false,
-                               unsigned char* atom_marks = nullptr);
-// the fragment library (mnx_set_fragments) as the device holds it: ONE allocation — the table of fragment indices parallel to
-// SymbolTables' names, the fragment records, then their atoms, bonds and symbol bytes. The host has validated all of it and has
-// sorted every fragment's bonds by (i, j), so the bonds from atom 0 (the attachment atom) are the first n_bonds0 of a fragment.
-struct FragRec {
-    unsigned atom0, bond0, text0;       // where its atoms / bonds / symbol bytes begin in the three arrays
-    unsigned short n_atoms, n_bonds, n_bonds0, text_len;    // 1..32 atoms; text_len: its symbols behind one another
-};
-struct FragView {                       // passed to kernels by value
-    const int* frag_of_name;            // [SymbolTables::n] fragment index or -1
-    const FragRec* frag;
-    const unsigned* atoms;              // sym0 (bytes from the fragment's text0) | sym_len << 16
-    const unsigned* bonds;              // i | j << 8 | type << 16
-    const unsigned char* text;
-};
-// expand.hip: the molecules of t with every abbreviation label that has a fragment replaced by the fragment's atoms and bonds,
-// as packed tables of the same record types (mnx_expand_pack): count, scan and fill, three launches on s
-hipError_t expand_pack_enqueue(const SymbolTables* st_dev, const FragView& fv, const PackedTables& t, const TablesOut& o,
-                               unsigned short* origin, unsigned* totals, hipStream_t s);
-// formula.hip: the molecules of t with every condensed-formula label that the search finds a structure for replaced by its atoms and
-// bonds, as packed tables of the same record types (mnx_formula_pack): count, scan and fill, three launches on s. max_steps: the
-// placements one label's search may try, 0 = MNX_FORMULA_DEFAULT_STEPS.
-hipError_t formula_pack_enqueue(const SymbolTables* st_dev, const FragView& fv, const PackedTables& t, const TablesOut& o,
-                                unsigned short* origin, unsigned* totals, unsigned max_steps, hipStream_t s);
-// main_mol.hip: of every molecule of t the connected component with the most atoms (among equals the one with the lowest atom), the
-// other atoms and their bonds dropped, as packed tables of the same record types (mnx_main_pack): count, scan and fill, three
-// launches on s
-hipError_t main_pack_enqueue(const PackedTables& t, const TablesOut& o, unsigned short* origin, unsigned* totals, hipStream_t s);
-// normalize.hip: the molecules of t with one normal spelling per atom — aromatic rings perceived, hydrogens counted, brackets
-// dropped where a reader infers them — as packed tables of the same record types (mnx_normalize_pack): count, scan and fill,
-// three launches on s; atom_notes (may be null) receives one byte per output atom
-hipError_t normalize_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, const TablesOut& o, unsigned char* atom_notes,
-                                  unsigned* totals, hipStream_t s);
-
-// kekulize.hip: the molecules of t with every aromatic system that has a Kekule structure written as one — upper-case atoms,
-// double and single bonds — as packed tables of the same record types (mnx_kekulize_pack): count, scan and fill, asynchronous on
-// s. max_steps: the pairings one system's search may try, 0 = MNX_KEKULE_DEFAULT_STEPS.
-hipError_t kekulize_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, const TablesOut& o, unsigned char* atom_notes,
-                                 unsigned* totals, unsigned max_steps, hipStream_t s);
-// fingerprint.hip: of every molecule of t the path fingerprint — 64 words behind one another in `bits`, a record in recs
-// (mnx_fingerprint_pack): one launch on s. max_bonds 1 .. 7 and max_steps 1 .. MNX_FP_MAX_STEPS, the defaults resolved
-hipError_t fingerprint_pack_enqueue(const SymbolTables* st_dev, const PackedTables& t, mnx_fp* recs, unsigned* bits,
-                                    unsigned max_bonds, unsigned max_steps, hipStream_t s);
-// the Tanimoto similarity of row r of a and row r of b, n rows of 64 words (mnx_tanimoto; each output may be null): one launch on s
-hipError_t tanimoto_enqueue(const unsigned* a, const unsigned* b, int n, unsigned* both, unsigned* either, double* similarity,
-                            hipStream_t s);
-// smiles_read.hip: string b = bytes[offsets[b] .. offsets[b + 1]) read as SMILES into packed tables of mnx_graph_pack's record types
-// (mnx_smiles_read): count, scan and fill, three launches on s
-hipError_t smiles_read_enqueue(const unsigned char* bytes, unsigned n_bytes, const unsigned* offsets, int n, mnx_read* recs,
-                               const TablesOut& o, unsigned* totals, hipStream_t s);
-// molfile_read.hip: file b = bytes[offsets[b] .. offsets[b + 1]) read as a V2000 molfile into packed tables of mnx_graph_pack's
-// record types (mnx_molfile_read): count, scan and fill, three launches on s. scale: int [n, 2] or null; fit 0 or 1; den =
-// cfg.coord_bins - 1
-hipError_t molfile_read_enqueue(const unsigned char* bytes, unsigned n_bytes, const unsigned* offsets, int n, const int* scale,
-                                int fit, unsigned den, mnx_molread* recs, const TablesOut& o, unsigned* totals, hipStream_t s);
 hipError_t edges_enqueue(const DecWeights& w, const DecBuffers& bf, const float* hidden, const int* slot_map,
                          const int* atom_idx, const int* n_atoms, int B, int kmax, int row_stride_T,
                          unsigned char* edges, double* scores, hipStream_t s);

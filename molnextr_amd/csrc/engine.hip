@@ -1,160 +1,27 @@
-// engine.hip — host side of libmolnextr_hip.so: weight packing, workspace, encode/decode/edges orchestration,
-// hipGraph replay of the decode step. Implements include/molnextr_hip.h.
-#include "../../include/molnextr_hip.h"
-
-#include <hip/hip_runtime.h>
-
+// engine.hip — host side of libmolnextr_hip.so, the model path: weight packing, workspace, encode/decode/edges orchestration,
+// hipGraph replay of the decode step. Implements the model's part of include/molnextr_hip.h; the packed-table entry points are
+// engine_tables.hip, the test aids and probes engine_lab.hip, what the three share engine_impl.h.
 #include <time.h>
-#include <algorithm>
 #include <cmath>
-#include <cstdint>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <memory>
-#include <string>
-#include <tuple>
 #include <unordered_map>
-#include <vector>
 
-#include "dec_types.h"
+#include "engine_impl.h"
 #include "kernels.h"
 #include "kvq.h"
 
 using namespace mnx;
-
-namespace {
-
-thread_local std::string g_create_error;   // message of the calling thread's last failed mnx_create
-
-// One GEMM weight in its operand form: a single 16-bit (or fp32) plane, or — split modes — a hi plane with the lo plane
-// `lo` elements behind it, both holding 2^k * W (k per matrix, fp16 split only); oscale = 2^-k.
-struct W16 {
-    void* p = nullptr;
-    size_t lo = 0;
-    float oscale = 1.f;
-};
-struct BlockW {
-    float *ln1_g, *ln1_b, *table, *qkv_b, *proj_b, *ln2_g, *ln2_b, *fc1_b, *fc2_b;
-    W16 qkv_w, proj_w, fc1_w, fc2_w;
-};
-struct StageW {
-    std::vector<BlockW> blocks;
-    float *m_g = nullptr, *m_b = nullptr;
-    W16 m_w;
-    int C = 0, heads = 0;
-};
-// op classes of the split modes (mnx_set_split_terms)
-enum { SPL_QKV = 1, SPL_ATTN = 2, SPL_PROJ = 4, SPL_FC1 = 8, SPL_FC2 = 16, SPL_MERGE = 32, SPL_ALL = 63 };
-struct GraphKey {
-    int slots, rows, trace, forced, tile, guided;
-    bool operator<(const GraphKey& o) const {
-        return std::tie(slots, rows, trace, forced, tile, guided) < std::tie(o.slots, o.rows, o.trace, o.forced, o.tile, o.guided);
-    }
-};
-
-}  // namespace
 
 #ifndef MNX_PLANE_SKEW
 #define MNX_PLANE_SKEW 4352
 #endif
 static constexpr size_t PLANE_SKEW = MNX_PLANE_SKEW;   // elements (8704 bytes; 16-byte aligned for the LDS-DMA)
 
-struct mnx_engine {
-    mnx_config cfg;
-    int device = 0;
-    std::string err;
-    std::vector<void*> allocs;
-    size_t bytes = 0;
-    // encoder
-    float *pe_wt = nullptr, *pe_b = nullptr, *pe_g = nullptr, *pe_beta = nullptr, *fn_g = nullptr, *fn_b = nullptr;
-    std::vector<StageW> stages;
-    float *xa = nullptr, *xb = nullptr;              // fp32 residual stream ping-pong
-    void *xn16 = nullptr, *qkv16 = nullptr, *attn16 = nullptr, *h16 = nullptr;
-    size_t xn_lo = 0, qkv_lo = 0, attn_lo = 0, h_lo = 0;   // split modes: element offset of each buffer's lo plane
-    int dt = 0;                                             // kernels.h MNX_DT_* the encoder kernels run (FP16X3M -> MNX_DT_F16X3)
-    int split_mask = SPL_ALL;                               // op classes evaluated with their full term count (others: hi.hi only)
-    // per stage: op classes whose full term count is TWO (ah.wh + ah.wl) in the blocks [two_first, two_last] of the stage (the
-    // patch-merging reduction counts as the stage's last block): FP16X3M, mnx_set_op_terms
-    int two_mask[4] = {0, 0, 0, 0};
-    int two_first[4] = {0, 0, 0, 0}, two_last[4] = {1 << 30, 1 << 30, 1 << 30, 1 << 30};
-    int* enc_flag = nullptr;                                // device: set when the final LayerNorm sees a non-finite row
-    float* zero_bias = nullptr;                             // [2 * widest C] zeros: the bias of the patch-merging reductions
-    int zero_bias_n = 0;
-    int tap_item = -1;
-    float* tap_dst = nullptr;
-    // decoder
-    DecWeights dw{};
-    DecBuffers db{};
-    float* out_trace = nullptr;
-    int* forced_ids = nullptr;  // [32, max_len] teacher-forcing ids of mnx_decode_forced (lazy; test aid)
-    int* script_nact = nullptr; // [max_len] n_active of every step of mnx_beam_scripted (lazy; test aid)
-    int* beam_script = nullptr; // [2][max_len][32 x 8] parents, then ids, of mnx_decode_beam_forced (lazy; test aid)
-    int* guide_labels = nullptr;   // [dec_slots, max_len + 2] label row of every slot, {ids held, the ids}: label-guided decoding
-                                   // (mnx_decode_guided / mnx_predict_guided; lazy, written at admission — dec_types.h GuideRows)
-    BeamBuffers beam{};        // allocated lazily on the first mnx_decode_beam
-    int* prep_bbox = nullptr;  // scratch of mnx_preprocess
-    int* prep_bbox_batch = nullptr;   // [MNX_PREP_MAX_PAGES][4]: scratch of mnx_preprocess_batch (its own: the two may not share)
-    float* beam_hidden = nullptr;   // mnx_predict_beam: [32, max_len, dec_dim] decoder outputs of the winners (lazy)
-    int* host_flag = nullptr;  // pinned: [2][1 + MAX_CHUNKS] poll snapshots + slot lists
-    std::map<GraphKey, hipGraphExec_t> graphs;
-    // continuous-batching pipeline (mnx_predict)
-    hipStream_t enc_stream = nullptr;
-    float* feat_ring[2] = {nullptr, nullptr};
-    hipEvent_t ev_enc_done[2] = {nullptr, nullptr}, ev_feat_free[2] = {nullptr, nullptr}, ev_poll[2] = {nullptr, nullptr};
-    int* slot_lists = nullptr;          // device [MAX_CHUNKS][32]: slot list of every 32-slot row tile
-    int* rowc_seq = nullptr;            // device [MAX_REF_BATCH]: 0, 1, 2, ... (row indices of a chunk's tiles at admission)
-    TokenClasses* tc_dev = nullptr;
-    bool have_tc = false;
-    VocabText* vt_dev = nullptr;        // names of the symbol ids (mnx_set_vocab_text), read by mnx_graph_pack
-    bool have_vt = false;
-    SymbolTables* st_dev = nullptr;     // R-group and abbreviation names (mnx_set_symbol_tables), read by mnx_molfile_pack and mnx_smiles_pack
-    bool have_st = false;
-    int st_n = 0;                       // names of the last mnx_set_symbol_tables
-    void* frag_dev = nullptr;           // the fragment library (mnx_set_fragments): one allocation, fv points into it; read by mnx_expand_pack
-    FragView fv{};
-    bool have_frag = false;
-    int n_chunk_bufs = 0;
-    bool use_graph = true;
-    // greedy ticks of up to dec_fused_max rows run as three launches per layer (dec_fused.hip): dec_tile rows per workgroup in
-    // the two attention stages (256 threads per row), dec_tile_ff rows in the feed-forward stage; larger ticks keep the
-    // 8-launches-per-layer kernels of decoder.hip (knobs MNX_DEC_TILE, MNX_DEC_TILE_FF, MNX_DEC_FUSED_MAX);
-    // dec_tile -1: 2 rows per workgroup up to 64 rows of capacity, 4 beyond
-    int dec_tile = -1, dec_tile_ff = 4, dec_fused_max = 128;
-    // ticks of more than dec_fused_max and up to dec_mid_max rows run the MID form (dec_fused.hip: dec_fa cut into a 16-row
-    // linear launch and an attention launch, 4 launches per layer; bit-identical to the fused form, so that the capacity the
-    // host happens to pick — it follows poll timing — is invisible in the results up to dec_mid_max rows); beyond that the
-    // 8-launches-per-layer kernels of decoder.hip, whose 32-row linears move the fewest bytes per row (MNX_DEC_MID_MAX;
-    // 4096 = every capacity: bit-reproducible jobs of any size, slower at >= 1024 rows)
-    int dec_mid_max = 0;
-    hipStream_t own_stream = nullptr;   // used when the caller passes the legacy null stream (not capturable)
-    // profiling (bench aid)
-    bool profiling = false;
-    int prof_stride = 1;       // bracket the GEMMs of every prof_stride-th mnx_encode call ...
-    int prof_calls = 0;        // ... counted since mnx_profile_enable
-    int prof_groups = 0;       // encode calls bracketed so far (capped: the event pool stays small)
-    int prof_max_groups = 4;
-    struct Ev { hipEvent_t a, b; double work; int kind; };   // kind 0 / 4 GEMM (work = FLOP; 4 = block Linears with C >= 512), 1 LayerNorm, 2 window attention, 3 patch embed (work = algorithmic HBM bytes)
-    std::vector<Ev> ev_pool;
-    size_t ev_used = 0;
-};
-
 namespace {
 
-#define HIPCHK(h, expr)                                                                                   \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess) {                                                                           \
-            (h)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                                 \
-            return MNX_ERR_HIP;                                                                           \
-        }                                                                                                 \
-    } while (0)
-
-#define MNXCHK(expr)                                                                                      \
-    do {                                                                                                  \
-        const int rc_ = (expr);                                                                           \
-        if (rc_ != MNX_OK) return rc_;                                                                    \
-    } while (0)
+thread_local std::string g_create_error;   // message of the calling thread's last failed mnx_create
 
 struct Packer {
     mnx_engine* h;
@@ -855,7 +722,7 @@ int mnx_encode_gray8(mnx_engine* h, const uint8_t* gray, int32_t B, float* featu
 
 }  // extern "C"
 
-namespace {
+namespace mnx {
 
 // The stream an entry point runs on, after selecting the engine's device: the caller's, or — for the legacy null stream,
 // which is not capturable — the engine's own default-flag stream (created on first use), which synchronises implicitly with
@@ -870,15 +737,9 @@ int caller_stream(mnx_engine* h, void* stream, hipStream_t* s) {
     return MNX_OK;
 }
 
-// A device buffer allocated by the first call that needs it and kept (allocs, bytes) until mnx_destroy
-template <typename T>
-int lazy_alloc(mnx_engine* h, T** p, size_t bytes) {
-    if (*p) return MNX_OK;
-    HIPCHK(h, hipMalloc((void**)p, bytes));
-    h->allocs.push_back(*p);
-    h->bytes += bytes;
-    return MNX_OK;
-}
+}  // namespace mnx
+
+namespace {
 
 // The decoder memory of n images (n <= ROW_TILE: the fp32 scratch db.memory / db.mem_kv32 holds that many) from their encoder
 // features: enc_transform, then the cross-attention K / V of all layers in one SGEMM, packed into memory blocks
@@ -978,29 +839,6 @@ int guide_rows(mnx_engine* h, const int32_t* src, int L, int max_len, GuideRows*
     return MNX_OK;
 }
 
-// Captures what enqueue() puts on s into a graph and instantiates it; the hipGraph_t is released on every path
-template <typename F>
-int capture_graph(mnx_engine* h, const char* what, hipStream_t s, F&& enqueue, hipGraphExec_t* out) {
-    *out = nullptr;
-    HIPCHK(h, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    hipGraph_t g = nullptr;
-    hipError_t e = enqueue();
-    const hipError_t e2 = hipStreamEndCapture(s, &g);
-    if (e == hipSuccess) e = e2;
-    const char* step = "capture";
-    if (e == hipSuccess) {
-        step = "instantiate";
-        e = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
-    }
-    if (g) hipGraphDestroy(g);
-    if (e != hipSuccess) {
-        *out = nullptr;
-        h->err = std::string(what) + " " + step + " failed: " + hipGetErrorString(e);
-        return MNX_ERR_HIP;
-    }
-    return MNX_OK;
-}
-
 // The graph of one greedy tick, captured on first use and kept until mnx_destroy (null under MNX_NO_GRAPH)
 int get_tick_graph(mnx_engine* h, int slots, int rows, float* trace, int trace_rows, hipStream_t s, hipGraphExec_t* out,
                    const int* forced = nullptr, bool guided = false) {
@@ -1012,21 +850,6 @@ int get_tick_graph(mnx_engine* h, int slots, int rows, float* trace, int trace_r
     if (it != h->graphs.end()) { *out = it->second; return MNX_OK; }
     MNXCHK(capture_graph(h, "decode tick", s, [&]() { return enqueue_tick(h, slots, rows, trace, trace_rows, s, forced, guided); }, out));
     h->graphs[key] = *out;
-    return MNX_OK;
-}
-
-// The step loop of mnx_decode_greedy / beam search: up to max_len steps in groups of 8 (a replay of exec each, or — no
-// graph — enqueue()); after every group the begin kernel over `slots` slots counts the alive rows, the host reads the count
-// back and stops at 0
-template <typename F>
-int run_steps(mnx_engine* h, hipGraphExec_t exec, F&& enqueue, int slots, int max_len, hipStream_t s) {
-    for (int t = 0; t < max_len; t += 8) {
-        for (int i = 0; i < std::min(8, max_len - t); ++i) HIPCHK(h, exec ? hipGraphLaunch(exec, s) : enqueue());
-        HIPCHK(h, dec_enqueue_status(h->db, slots, s));
-        HIPCHK(h, hipMemcpyAsync(h->host_flag, &h->db.st->n_active, sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-        if (*h->host_flag == 0) break;
-    }
     return MNX_OK;
 }
 
@@ -1070,9 +893,9 @@ int decode_greedy_impl(mnx_engine* h, const float* features, int32_t B, const in
     return MNX_OK;
 }
 
-// kept hypotheses of all images (32 images x 8 ... 256 x 1) and how many of them one of B images may keep
-constexpr int BEAM_POOL = ROW_TILE * MAX_BEAM;
-inline int beam_pool_stride(int B) { return std::min(MAX_BEAM, BEAM_POOL / B); }
+}  // namespace
+
+namespace mnx {
 
 // The engine's beam-search buffers (allocated by the first search) set up for B images x `beam` hypotheses
 int beam_buffers(mnx_engine* h, int B, int ref_batch, int beam, int n_best, bool hidden) {
@@ -1097,7 +920,7 @@ int beam_buffers(mnx_engine* h, int B, int ref_batch, int beam, int n_best, bool
 // step's choice; logits_trace (may be null): device [max_len][B x beam][V], row (t, slot) written by the head
 int decode_beam_groups(mnx_engine* h, const float* const* feats, int G, int ref_batch, int n_total, int beam, int n_best,
                        int max_len, int32_t* tokens, int32_t* lengths, float* scores, float* hidden, hipStream_t s,
-                       const int* script = nullptr, float* logits_trace = nullptr) {
+                       const int* script, float* logits_trace) {
     const int B = n_total;
     // capacities: MAX_BEAM_IMGS images x MAX_BEAM hypotheses of state; 256 kept hypotheses (32 images x 8 ... 256 x 1)
     MNXCHK(beam_buffers(h, B, ref_batch, beam, n_best, hidden != nullptr));
@@ -1123,7 +946,7 @@ int decode_beam_groups(mnx_engine* h, const float* const* feats, int G, int ref_
     return MNX_OK;
 }
 
-}  // namespace
+}  // namespace mnx
 
 extern "C" {
 
@@ -1282,22 +1105,6 @@ int mnx_edges(mnx_engine* h, const float* hidden, const int32_t* atom_idx, const
     return MNX_OK;
 }
 
-// mnx_edge_probs (test aid): mnx_edges, then what edge_pair_kernel left in edge_prob for this B and kmax
-int mnx_edge_probs(mnx_engine* h, const float* hidden, const int32_t* atom_idx, const int32_t* n_atoms, int32_t B,
-                   int32_t kmax, int32_t max_len, uint8_t* edges, double* scores, float* probs, void* stream) {
-    if (!h) return MNX_ERR_INVALID_ARG;
-    if (!hidden || !atom_idx || !n_atoms || !edges || !probs || B < 1 || kmax < 1 || max_len < 1) {
-        h->err = "mnx_edge_probs: null/empty argument";
-        return MNX_ERR_INVALID_ARG;
-    }
-    if (B > ROW_TILE || kmax > h->db.kmax) { h->err = "mnx_edge_probs: B <= 32 and kmax <= cfg.max_atoms required"; return MNX_ERR_CAPACITY; }
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, edges_enqueue(h->dw, h->db, hidden, nullptr, atom_idx, n_atoms, B, kmax, max_len, edges, scores, (hipStream_t)stream));
-    HIPCHK(h, hipMemcpyAsync(probs, h->db.edge_prob, (size_t)B * kmax * kmax * 8 * sizeof(float), hipMemcpyDeviceToDevice,
-                             (hipStream_t)stream));
-    return MNX_OK;
-}
-
 int mnx_set_token_classes(mnx_engine* h, const uint8_t* flags, int32_t n, int32_t lbracket, int32_t rbracket,
                           int32_t id_C, int32_t id_l, int32_t id_B, int32_t id_r) {
     if (!h || !flags || n < 1 || n > 256) return MNX_ERR_INVALID_ARG;
@@ -1308,423 +1115,6 @@ int mnx_set_token_classes(mnx_engine* h, const uint8_t* flags, int32_t n, int32_
     tc.x0 = h->cfg.sym_offset; tc.y0 = h->cfg.sym_offset + h->cfg.coord_bins; tc.vocab = h->cfg.vocab;
     HIPCHK(h, hipMemcpy(h->tc_dev, &tc, sizeof(tc), hipMemcpyHostToDevice));
     h->have_tc = true;
-    return MNX_OK;
-}
-
-int mnx_set_vocab_text(mnx_engine* h, const char* bytes, const uint32_t* offsets, int32_t n) {
-    if (!h) return MNX_ERR_INVALID_ARG;
-    if (!bytes || !offsets || n < 1 || n > 256) { h->err = "mnx_set_vocab_text: null pointer or n outside 1..256"; return MNX_ERR_INVALID_ARG; }
-    if (n != h->cfg.sym_offset) {     // a shorter table would spell shortened SMILES without a word
-        h->err = "mnx_set_vocab_text: n = " + std::to_string(n) + " names, but the vocabulary has cfg.sym_offset = " +
-                 std::to_string(h->cfg.sym_offset) + " symbol ids";
-        return MNX_ERR_INVALID_ARG;
-    }
-    if (offsets[0] != 0) { h->err = "mnx_set_vocab_text: offsets[0] must be 0"; return MNX_ERR_INVALID_ARG; }
-    VocabText vt{};
-    for (int i = 0; i < n; ++i) {
-        if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 8) {
-            h->err = "mnx_set_vocab_text: name of id " + std::to_string(i) + " is longer than 8 bytes or its offsets decrease";
-            return MNX_ERR_INVALID_ARG;
-        }
-        vt.len[i] = (unsigned char)(offsets[i + 1] - offsets[i]);
-        memcpy(vt.name[i], bytes + offsets[i], vt.len[i]);
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipMemcpy(h->vt_dev, &vt, sizeof(vt), hipMemcpyHostToDevice));
-    h->have_vt = true;
-    return MNX_OK;
-}
-
-// The output tables of mnx_graph_pack, mnx_expand_pack and mnx_smiles_read with their `totals`: what each tests of them
-static TablesOut tables_out(mnx_mol* mols, mnx_atom* atoms, uint32_t atom_cap, mnx_bond* bonds, uint32_t bond_cap, char* text,
-                            uint32_t text_cap) {
-    return TablesOut{mols, (unsigned long long*)atoms, atom_cap, (unsigned long long*)bonds, bond_cap, text, text_cap};
-}
-static bool tables_out_null(const TablesOut& o, const uint32_t* totals) {
-    return !o.mols || !totals || (!o.atoms && o.atom_cap) || (!o.bonds && o.bond_cap) || (!o.text && o.text_cap);
-}
-static bool tables_out_skew(const TablesOut& o, const uint32_t* totals) {
-    return ((((uintptr_t)o.mols | (uintptr_t)o.atoms | (uintptr_t)o.bonds) & 7) | ((uintptr_t)totals & 3)) != 0;
-}
-
-int mnx_graph_pack(mnx_engine* h, const int32_t* tokens, const int32_t* lengths, int32_t n, int32_t T,
-                   const int32_t* atom_idx, const int32_t* n_atoms, const uint8_t* edges, int32_t kmax,
-                   const double* atom_scores, const double* edge_scores, const double* overall_score, mnx_mol* mols,
-                   mnx_atom* atoms, uint32_t atom_cap, mnx_bond* bonds, uint32_t bond_cap, char* text, uint32_t text_cap,
-                   uint32_t* totals, void* stream) {
-    if (!h) return MNX_ERR_INVALID_ARG;
-    const TablesOut o = tables_out(mols, atoms, atom_cap, bonds, bond_cap, text, text_cap);
-    if (!tokens || !lengths || !atom_idx || !n_atoms || !edges || tables_out_null(o, totals)) {
-        h->err = "mnx_graph_pack: null pointer";
-        return MNX_ERR_INVALID_ARG;
-    }
-    if (n < 1 || n > 65536 || T < 1 || T > 512 || kmax < 1 || kmax > h->db.kmax) {
-        h->err = "mnx_graph_pack: 1 <= n <= 65536, 1 <= T <= 512 and 1 <= kmax <= cfg.max_atoms required";
-        return MNX_ERR_INVALID_ARG;
-    }
-    const int n_scores = (atom_scores != nullptr) + (edge_scores != nullptr) + (overall_score != nullptr);
-    if (n_scores != 0 && n_scores != 3) {
-        h->err = "mnx_graph_pack: atom_scores, edge_scores and overall_score go together (all three or none)";
-        return MNX_ERR_INVALID_ARG;
-    }
-    if (tables_out_skew(o, totals)) {
-        h->err = "mnx_graph_pack: mols, atoms and bonds must be 8-byte aligned, totals 4-byte";
-        return MNX_ERR_INVALID_ARG;
-    }
-    if (!h->have_tc) { h->err = "mnx_graph_pack: call mnx_set_token_classes first"; return MNX_ERR_INVALID_ARG; }
-    if (!h->have_vt) { h->err = "mnx_graph_pack: call mnx_set_vocab_text first"; return MNX_ERR_INVALID_ARG; }
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, graph_pack_enqueue(h->tc_dev, h->vt_dev, tokens, lengths, n, T, kmax, atom_idx, n_atoms, edges, atom_scores,
-                                 edge_scores, overall_score, o, totals, (hipStream_t)stream));
-    return MNX_OK;
-}
-
-int mnx_set_symbol_tables(mnx_engine* h, const char* bytes, const uint32_t* offsets, const uint8_t* kinds, int32_t n) {
-    if (!h) return MNX_ERR_INVALID_ARG;
-    auto bad = [&](const std::string& m) { h->err = "mnx_set_symbol_tables: " + m; return MNX_ERR_INVALID_ARG; };
-    if (n < 0 || n > 512) return bad("n outside 0..512");
-    if (n > 0 && (!bytes || !offsets || !kinds)) return bad("null pointer");
-    if (n > 0 && offsets[0] != 0) return bad("offsets[0] must be 0");
-    auto st = std::make_unique<SymbolTables>();
-    memset(st.get(), 0, sizeof(SymbolTables));
-    st->n = n;
-    for (int i = 0; i < n; ++i) {
-        if (offsets[i + 1] <= offsets[i] || offsets[i + 1] - offsets[i] > 16)
-            return bad("name " + std::to_string(i) + " is empty or longer than 16 bytes, or its offsets decrease");
-        if (kinds[i] != 1 && kinds[i] != 2) return bad("kinds[" + std::to_string(i) + "] must be 1 (R-group) or 2 (abbreviation)");
-        st->len[i] = (unsigned char)(offsets[i + 1] - offsets[i]);
-        st->kind[i] = kinds[i];
-        memcpy(st->name[i], bytes + offsets[i], st->len[i]);
-        if (i > 0) {        // bytewise order, a prefix in front of the longer name: what the device's binary search assumes
-            const int m = std::min(st->len[i - 1], st->len[i]), c = memcmp(st->name[i - 1], st->name[i], (size_t)m);
-            if (c > 0 || (c == 0 && st->len[i - 1] >= st->len[i]))
-                return bad("names must be strictly ascending bytewise; name " + std::to_string(i) + " is not behind its predecessor");
-        }
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipMemcpy(h->st_dev, st.get(), sizeof(SymbolTables), hipMemcpyHostToDevice));
-    h->have_st = true;
-    h->st_n = n;
-    h->have_frag = false;       // a fragment table is parallel to the names it was set for
-    return MNX_OK;
-}
-
-int mnx_set_fragments(mnx_engine* h, const mnx_mol* frags, int32_t n_frags, const mnx_atom* atoms, uint32_t na, const mnx_bond* bonds,
-                      uint32_t nb, const char* text, uint32_t nt, const int32_t* frag_of_name, int32_t n_names) {
-    if (!h) return MNX_ERR_INVALID_ARG;
-    auto bad = [&](const std::string& m) { h->err = "mnx_set_fragments: " + m; return MNX_ERR_INVALID_ARG; };
-    if (!h->have_st) return bad("call mnx_set_symbol_tables first");
-    if (n_frags < 0 || n_frags > 512) return bad("n_frags outside 0..512");
-    if (n_names != h->st_n) return bad("n_names must be the n of mnx_set_symbol_tables (" + std::to_string(h->st_n) + ")");
-    if ((n_frags > 0 && !frags) || (na && !atoms) || (nb && !bonds) || (nt && !text) || (n_names > 0 && !frag_of_name))
-        return bad("null pointer");
-    // the device copy, put together on the host: bonds sorted by (i, j), every fragment's symbols behind one another
-    std::vector<FragRec> rec((size_t)n_frags);
-    std::vector<unsigned> fa, fb;
-    std::vector<unsigned char> ft;
-    for (int f = 0; f < n_frags; ++f) {
-        const mnx_mol& m = frags[f];
-        const std::string who = "fragment " + std::to_string(f);
-        if (m.n_atoms < 1 || m.n_atoms > 32) return bad(who + " has " + std::to_string(m.n_atoms) + " atoms; 1 to 32 required");
-        if ((uint64_t)m.atom0 + m.n_atoms > na || (uint64_t)m.bond0 + m.n_bonds > nb || (uint64_t)m.text0 + m.smiles_len > nt)
-            return bad(who + ": its records end behind a table");
-        FragRec& r = rec[(size_t)f];
-        r.atom0 = (unsigned)fa.size(); r.bond0 = (unsigned)fb.size(); r.text0 = (unsigned)ft.size();
-        r.n_atoms = (unsigned short)m.n_atoms;
-        unsigned len = 0;
-        for (uint32_t a = 0; a < m.n_atoms; ++a) {
-            const mnx_atom& x = atoms[m.atom0 + a];
-            if (x.sym_len < 1 || x.sym_len > 8) return bad(who + ", atom " + std::to_string(a) + ": a symbol has 1 to 8 bytes");
-            if ((uint64_t)m.text0 + x.sym0 + x.sym_len > nt) return bad(who + ", atom " + std::to_string(a) + ": its symbol ends behind the text");
-            fa.push_back(len | (unsigned)x.sym_len << 16);
-            ft.insert(ft.end(), (const unsigned char*)text + m.text0 + x.sym0, (const unsigned char*)text + m.text0 + x.sym0 + x.sym_len);
-            len += x.sym_len;
-        }
-        r.text_len = (unsigned short)len;
-        std::vector<unsigned> own;
-        for (uint32_t k = 0; k < m.n_bonds; ++k) {
-            const mnx_bond& x = bonds[m.bond0 + k];
-            const std::string which = who + ", bond " + std::to_string(k);
-            if (!(x.i < x.j && x.j < m.n_atoms)) return bad(which + ": i < j < n_atoms required");
-            if (x.type < 1 || x.type > 4 || x.rev != x.type) return bad(which + ": type 1 to 4 and rev == type required");
-            own.push_back((unsigned)x.i | (unsigned)x.j << 8 | (unsigned)x.type << 16);
-        }
-        std::sort(own.begin(), own.end(), [](unsigned p, unsigned q) { return ((p & 0xff) << 8 | (p >> 8 & 0xff)) < ((q & 0xff) << 8 | (q >> 8 & 0xff)); });
-        unsigned n0 = 0;
-        for (size_t k = 0; k < own.size(); ++k) {
-            if (k > 0 && (own[k] & 0xffff) == (own[k - 1] & 0xffff)) return bad(who + ": the same pair of atoms in two bonds");
-            n0 += (own[k] & 0xff) == 0;
-        }
-        r.n_bonds = (unsigned short)own.size();
-        r.n_bonds0 = (unsigned short)n0;
-        fb.insert(fb.end(), own.begin(), own.end());
-    }
-    std::vector<unsigned char> kinds((size_t)std::max(n_names, 1));
-    {   // the kinds as the device holds them
-        auto st = std::make_unique<SymbolTables>();
-        HIPCHK(h, hipSetDevice(h->device));
-        HIPCHK(h, hipMemcpy(st.get(), h->st_dev, sizeof(SymbolTables), hipMemcpyDeviceToHost));
-        memcpy(kinds.data(), st->kind, (size_t)n_names);
-    }
-    for (int k = 0; k < n_names; ++k) {
-        if (frag_of_name[k] < -1 || frag_of_name[k] >= n_frags) return bad("frag_of_name[" + std::to_string(k) + "] outside -1.." + std::to_string(n_frags - 1));
-        if (frag_of_name[k] >= 0 && kinds[(size_t)k] != 2) return bad("frag_of_name[" + std::to_string(k) + "]: only an abbreviation (kind 2) takes a fragment");
-    }
-    // one allocation: frag_of_name | records | atoms | bonds | text, each part 8-byte aligned
-    auto up8 = [](size_t v) { return (v + 7) & ~(size_t)7; };
-    const size_t o_rec = up8((size_t)std::max(n_names, 1) * sizeof(int)), o_atoms = o_rec + up8(std::max(rec.size(), (size_t)1) * sizeof(FragRec));
-    const size_t o_bonds = o_atoms + up8(std::max(fa.size(), (size_t)1) * 4), o_text = o_bonds + up8(std::max(fb.size(), (size_t)1) * 4);
-    const size_t total = o_text + up8(std::max(ft.size(), (size_t)1));
-    std::vector<unsigned char> blob(total, 0);
-    if (n_names) memcpy(blob.data(), frag_of_name, (size_t)n_names * sizeof(int));
-    if (!rec.empty()) memcpy(blob.data() + o_rec, rec.data(), rec.size() * sizeof(FragRec));
-    if (!fa.empty()) memcpy(blob.data() + o_atoms, fa.data(), fa.size() * 4);
-    if (!fb.empty()) memcpy(blob.data() + o_bonds, fb.data(), fb.size() * 4);
-    if (!ft.empty()) memcpy(blob.data() + o_text, ft.data(), ft.size());
-    void* dev = nullptr;
-    HIPCHK(h, hipMalloc(&dev, total));
-    if (hipError_t e = hipMemcpy(dev, blob.data(), total, hipMemcpyHostToDevice); e != hipSuccess) {
-        hipFree(dev);
-        h->err = std::string("mnx_set_fragments: hipMemcpy: ") + hipGetErrorString(e);
-        return MNX_ERR_HIP;
-    }
-    if (h->frag_dev) {          // an earlier table may still be read by launches in flight
-        (void)hipDeviceSynchronize();
-        hipFree(h->frag_dev);
-    }
-    h->frag_dev = dev;
-    const unsigned char* d = (const unsigned char*)dev;
-    h->fv = FragView{(const int*)d, (const FragRec*)(d + o_rec), (const unsigned*)(d + o_atoms), (const unsigned*)(d + o_bonds), d + o_text};
-    h->have_frag = true;
-    return MNX_OK;
-}
-
-// What mnx_molfile_pack, mnx_expand_pack, mnx_normalize_pack, mnx_kekulize_pack and the five mnx_smiles_pack* test before they launch, in
-// the order in which a call refused for two reasons reports them. Its own pointers (outs_null, outs_skew) the entry point tests; `aligned` ends its alignment message.
-static int check_packed_tables(mnx_engine* h, const char* fn, const PackedTables& t, bool outs_null, bool outs_skew,
-                               const char* aligned, bool reads_symbols = true) {
-    if (!h) return MNX_ERR_INVALID_ARG;
-    auto bad = [&](const std::string& m) { h->err = std::string(fn) + ": " + m; return MNX_ERR_INVALID_ARG; };
-    if (!t.mols || (!t.atoms && t.n_atom_records) || (!t.bonds && t.n_bond_records) || (!t.text && t.n_text_bytes) || outs_null)
-        return bad("null pointer");
-    if (t.n < 1 || t.n > 65536) return bad("1 <= n <= 65536 required");
-    if ((((uintptr_t)t.mols | (uintptr_t)t.atoms | (uintptr_t)t.bonds) & 7) || outs_skew)
-        return bad(std::string("mols, atoms and bonds must be 8-byte aligned, ") + aligned);
-    if (reads_symbols && !h->have_st) return bad("call mnx_set_symbol_tables first");
-    return MNX_OK;
-}
-
-int mnx_molfile_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
-                     const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes,
-                     const int32_t* scale, mnx_molfile* files, char* out, uint32_t out_cap, uint32_t* totals, void* stream) {
-    const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
-    if (int rc = check_packed_tables(h, "mnx_molfile_pack", t, !files || !totals || (!out && out_cap),
-                                     (((uintptr_t)files | (uintptr_t)totals | (uintptr_t)scale) & 3) != 0, "files, scale and totals 4-byte"))
-        return rc;
-    if (h->cfg.coord_bins < 2) { h->err = "mnx_molfile_pack: cfg.coord_bins must be at least 2"; return MNX_ERR_INVALID_ARG; }
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, molfile_pack_enqueue(h->st_dev, t, scale, h->cfg.coord_bins, files, out, out_cap, totals, (hipStream_t)stream));
-    return MNX_OK;
-}
-
-// mnx_expand_pack and mnx_formula_pack (formula, with its max_steps): one check, one way to the pass's three launches
-static int grow_pack(mnx_engine* h, const char* fn, const PackedTables& t, const TablesOut& o, uint16_t* origin, uint32_t* totals,
-                     void* stream, bool formula = false, uint32_t max_steps = 0) {
-    if (int rc = check_packed_tables(h, fn, t, tables_out_null(o, totals), tables_out_skew(o, totals) || ((uintptr_t)origin & 1) != 0,
-                                     "the output tables too, totals 4-byte, origin 2-byte"))
-        return rc;
-    if (!h->have_frag) { h->err = std::string(fn) + ": call mnx_set_fragments first"; return MNX_ERR_INVALID_ARG; }
-    HIPCHK(h, hipSetDevice(h->device));
-    if (formula) HIPCHK(h, formula_pack_enqueue(h->st_dev, h->fv, t, o, origin, totals, max_steps, (hipStream_t)stream));
-    else HIPCHK(h, expand_pack_enqueue(h->st_dev, h->fv, t, o, origin, totals, (hipStream_t)stream));
-    return MNX_OK;
-}
-
-int mnx_expand_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
-                    const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_mol* mols_out,
-                    mnx_atom* atoms_out, uint32_t atom_cap, mnx_bond* bonds_out, uint32_t bond_cap, char* text_out, uint32_t text_cap,
-                    uint16_t* origin, uint32_t* totals, void* stream) {
-    const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
-    const TablesOut o = tables_out(mols_out, atoms_out, atom_cap, bonds_out, bond_cap, text_out, text_cap);
-    return grow_pack(h, "mnx_expand_pack", t, o, origin, totals, stream);
-}
-
-int mnx_formula_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
-                     const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_mol* mols_out,
-                     mnx_atom* atoms_out, uint32_t atom_cap, mnx_bond* bonds_out, uint32_t bond_cap, char* text_out, uint32_t text_cap,
-                     uint16_t* origin, uint32_t* totals, uint32_t max_steps, void* stream) {
-    const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
-    const TablesOut o = tables_out(mols_out, atoms_out, atom_cap, bonds_out, bond_cap, text_out, text_cap);
-    return grow_pack(h, "mnx_formula_pack", t, o, origin, totals, stream, true, max_steps);
-}
-
-// mnx_main_pack reads no symbol: it needs neither symbol tables nor fragments
-int mnx_main_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
-                  const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_mol* mols_out,
-                  mnx_atom* atoms_out, uint32_t atom_cap, mnx_bond* bonds_out, uint32_t bond_cap, char* text_out, uint32_t text_cap,
-                  uint16_t* origin, uint32_t* totals, void* stream) {
-    const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
-    const TablesOut o = tables_out(mols_out, atoms_out, atom_cap, bonds_out, bond_cap, text_out, text_cap);
-    if (int rc = check_packed_tables(h, "mnx_main_pack", t, tables_out_null(o, totals), tables_out_skew(o, totals) || ((uintptr_t)origin & 1) != 0,
-                                     "the output tables too, totals 4-byte, origin 2-byte", false))
-        return rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, main_pack_enqueue(t, o, origin, totals, (hipStream_t)stream));
-    return MNX_OK;
-}
-
-// mnx_normalize_pack and mnx_kekulize_pack (kekulize, with its max_steps): one check, one way to the pass's three launches
-static int respell_pack(mnx_engine* h, const char* fn, const PackedTables& t, const TablesOut& o, uint8_t* atom_notes, uint32_t* totals,
-                        void* stream, bool kekulize = false, uint32_t max_steps = 0) {
-    if (int rc = check_packed_tables(h, fn, t, tables_out_null(o, totals), tables_out_skew(o, totals), "the output tables too, totals 4-byte"))
-        return rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (kekulize) HIPCHK(h, kekulize_pack_enqueue(h->st_dev, t, o, atom_notes, totals, max_steps, (hipStream_t)stream));
-    else HIPCHK(h, normalize_pack_enqueue(h->st_dev, t, o, atom_notes, totals, (hipStream_t)stream));
-    return MNX_OK;
-}
-
-int mnx_normalize_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
-                       const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_mol* mols_out,
-                       mnx_atom* atoms_out, uint32_t atom_cap, mnx_bond* bonds_out, uint32_t bond_cap, char* text_out,
-                       uint32_t text_cap, uint8_t* atom_notes, uint32_t* totals, void* stream) {
-    const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
-    const TablesOut o = tables_out(mols_out, atoms_out, atom_cap, bonds_out, bond_cap, text_out, text_cap);
-    return respell_pack(h, "mnx_normalize_pack", t, o, atom_notes, totals, stream);
-}
-
-int mnx_kekulize_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
-                      const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_mol* mols_out,
-                      mnx_atom* atoms_out, uint32_t atom_cap, mnx_bond* bonds_out, uint32_t bond_cap, char* text_out,
-                      uint32_t text_cap, uint8_t* atom_notes, uint32_t* totals, uint32_t max_steps, void* stream) {
-    const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
-    const TablesOut o = tables_out(mols_out, atoms_out, atom_cap, bonds_out, bond_cap, text_out, text_cap);
-    return respell_pack(h, "mnx_kekulize_pack", t, o, atom_notes, totals, stream, true, max_steps);
-}
-
-int mnx_smiles_read(mnx_engine* h, const char* bytes, uint32_t n_bytes, const uint32_t* offsets, int32_t n, mnx_mol* mols,
-                    mnx_read* recs, mnx_atom* atoms, uint32_t atom_cap, mnx_bond* bonds, uint32_t bond_cap, char* text,
-                    uint32_t text_cap, uint32_t* totals, void* stream) {
-    if (!h) return MNX_ERR_INVALID_ARG;
-    auto bad = [&](const char* m) { h->err = std::string("mnx_smiles_read: ") + m; return MNX_ERR_INVALID_ARG; };
-    const TablesOut o = tables_out(mols, atoms, atom_cap, bonds, bond_cap, text, text_cap);
-    if ((!bytes && n_bytes) || !offsets || !recs || tables_out_null(o, totals)) return bad("null pointer");
-    if (n < 1 || n > 65536) return bad("1 <= n <= 65536 required");
-    if (tables_out_skew(o, totals) || (((uintptr_t)recs | (uintptr_t)offsets) & 3))
-        return bad("mols, atoms and bonds must be 8-byte aligned, recs, offsets and totals 4-byte");
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, smiles_read_enqueue((const unsigned char*)bytes, n_bytes, offsets, n, recs, o, totals, (hipStream_t)stream));
-    return MNX_OK;
-}
-
-int mnx_molfile_read(mnx_engine* h, const char* bytes, uint32_t n_bytes, const uint32_t* offsets, int32_t n,
-                     const int32_t* scale, int32_t fit, mnx_mol* mols, mnx_molread* recs, mnx_atom* atoms, uint32_t atom_cap,
-                     mnx_bond* bonds, uint32_t bond_cap, char* text, uint32_t text_cap, uint32_t* totals, void* stream) {
-    if (!h) return MNX_ERR_INVALID_ARG;
-    auto bad = [&](const char* m) { h->err = std::string("mnx_molfile_read: ") + m; return MNX_ERR_INVALID_ARG; };
-    const TablesOut o = tables_out(mols, atoms, atom_cap, bonds, bond_cap, text, text_cap);
-    if ((!bytes && n_bytes) || !offsets || !recs || tables_out_null(o, totals)) return bad("null pointer");
-    if (n < 1 || n > 65536) return bad("1 <= n <= 65536 required");
-    if (fit != 0 && fit != 1) return bad("fit must be 0 or 1");
-    if (fit && scale) return bad("fit = 1 takes no scale");
-    if (tables_out_skew(o, totals) || (((uintptr_t)recs | (uintptr_t)offsets | (uintptr_t)scale) & 3))
-        return bad("mols, atoms and bonds must be 8-byte aligned, recs, offsets, scale and totals 4-byte");
-    if (h->cfg.coord_bins < 2) return bad("cfg.coord_bins must be at least 2");
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, molfile_read_enqueue((const unsigned char*)bytes, n_bytes, offsets, n, scale, fit, (unsigned)h->cfg.coord_bins - 1u, recs, o,
-                                   totals, (hipStream_t)stream));
-    return MNX_OK;
-}
-
-// mnx_smiles_pack, mnx_smiles_pack_stereo, mnx_smiles_pack_marks, mnx_smiles_pack_canonical and mnx_smiles_pack_symmetric: one
-// check, one enqueue path, a pair of kernels per set of marks; canonical: on the ranks that one more kernel in front of them
-// leaves in `rank`; symmetric: canonical with the symmetry rule, which needs `sym_class` too
-static int smiles_pack(mnx_engine* h, const char* fn, uint32_t marks, const PackedTables& t, mnx_smiles* recs, uint16_t* order,
-                       char* out, uint32_t out_cap, uint32_t* totals, void* stream, bool canonical = false, uint16_t* rank = nullptr,
-                       uint16_t* sym_class = nullptr, bool symmetric = false, uint8_t* atom_marks = nullptr) {
-    if (int rc = check_packed_tables(h, fn, t, !recs || !totals || (!out && out_cap) || (canonical && !rank) || (symmetric && !sym_class),
-                                     (((uintptr_t)recs | (uintptr_t)totals) & 3) != 0 ||
-                                         (((uintptr_t)order | (uintptr_t)rank | (uintptr_t)sym_class) & 1) != 0,
-                                     canonical ? "recs and totals 4-byte, order, rank and sym_class 2-byte" : "recs and totals 4-byte, order 2-byte"))
-        return rc;
-    if (marks & ~(MNX_SMILES_MARK_TETRAHEDRAL | MNX_SMILES_MARK_DOUBLE_BOND)) {
-        h->err = std::string(fn) + ": marks may hold MNX_SMILES_MARK_TETRAHEDRAL and MNX_SMILES_MARK_DOUBLE_BOND only";
-        return MNX_ERR_INVALID_ARG;
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, smiles_pack_enqueue(h->st_dev, t, marks, recs, order, rank, sym_class, out, out_cap, totals, (hipStream_t)stream, symmetric,
-                                  atom_marks));
-    return MNX_OK;
-}
-
-int mnx_smiles_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
-                    const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_smiles* recs,
-                    uint16_t* order, char* out, uint32_t out_cap, uint32_t* totals, void* stream) {
-    const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
-    return smiles_pack(h, "mnx_smiles_pack", 0u, t, recs, order, out, out_cap, totals, stream);
-}
-
-int mnx_smiles_pack_stereo(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
-                           const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes,
-                           mnx_smiles* recs, uint16_t* order, char* out, uint32_t out_cap, uint32_t* totals, void* stream) {
-    const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
-    return smiles_pack(h, "mnx_smiles_pack_stereo", MNX_SMILES_MARK_TETRAHEDRAL, t, recs, order, out, out_cap, totals, stream);
-}
-
-int mnx_smiles_pack_marks(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
-                          const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes,
-                          mnx_smiles* recs, uint16_t* order, char* out, uint32_t out_cap, uint32_t* totals, uint32_t marks,
-                          void* stream) {
-    const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
-    return smiles_pack(h, "mnx_smiles_pack_marks", marks, t, recs, order, out, out_cap, totals, stream);
-}
-
-int mnx_smiles_pack_canonical(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
-                              const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes,
-                              mnx_smiles* recs, uint16_t* order, uint16_t* rank, uint16_t* sym_class, char* out,
-                              uint32_t out_cap, uint32_t* totals, uint32_t marks, void* stream) {
-    const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
-    return smiles_pack(h, "mnx_smiles_pack_canonical", marks, t, recs, order, out, out_cap, totals, stream, true, rank, sym_class);
-}
-
-int mnx_smiles_pack_symmetric(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
-                              const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes,
-                              mnx_smiles* recs, uint16_t* order, uint16_t* rank, uint16_t* sym_class, uint8_t* atom_marks,
-                              char* out, uint32_t out_cap, uint32_t* totals, uint32_t marks, void* stream) {
-    const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
-    return smiles_pack(h, "mnx_smiles_pack_symmetric", marks, t, recs, order, out, out_cap, totals, stream, true, rank, sym_class,
-                       true, atom_marks);
-}
-
-int mnx_fingerprint_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mnx_atom* atoms, uint32_t n_atom_records,
-                         const mnx_bond* bonds, uint32_t n_bond_records, const char* text, uint32_t n_text_bytes, mnx_fp* recs,
-                         uint32_t* bits, uint32_t max_bonds, uint32_t max_steps, void* stream) {
-    const PackedTables t{mols, n, atoms, n_atom_records, bonds, n_bond_records, (const unsigned char*)text, n_text_bytes};
-    if (int rc = check_packed_tables(h, "mnx_fingerprint_pack", t, !recs || !bits, (((uintptr_t)recs | (uintptr_t)bits) & 3) != 0,
-                                     "recs and bits 4-byte"))
-        return rc;
-    if (max_bonds > MNX_FP_MAX_BONDS) { h->err = "mnx_fingerprint_pack: max_bonds must be 1 to 7, or 0 for 7"; return MNX_ERR_INVALID_ARG; }
-    if (max_steps > MNX_FP_MAX_STEPS) {
-        h->err = "mnx_fingerprint_pack: max_steps must not exceed MNX_FP_MAX_STEPS (1048576)";
-        return MNX_ERR_INVALID_ARG;
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, fingerprint_pack_enqueue(h->st_dev, t, recs, bits, max_bonds ? max_bonds : MNX_FP_MAX_BONDS,
-                                       max_steps ? max_steps : MNX_FP_DEFAULT_STEPS, (hipStream_t)stream));
-    return MNX_OK;
-}
-
-int mnx_tanimoto(mnx_engine* h, const uint32_t* a, const uint32_t* b, int32_t n, uint32_t* both, uint32_t* either,
-                 double* similarity, void* stream) {
-    if (!h) return MNX_ERR_INVALID_ARG;
-    auto bad = [&](const char* m) { h->err = std::string("mnx_tanimoto: ") + m; return MNX_ERR_INVALID_ARG; };
-    if (!a || !b) return bad("null pointer");
-    if (!both && !either && !similarity) return bad("both, either and similarity are all null");
-    if (n < 1 || n > 65536) return bad("1 <= n <= 65536 required");
-    if ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)both | (uintptr_t)either) & 3) || ((uintptr_t)similarity & 7))
-        return bad("a, b, both and either must be 4-byte aligned, similarity 8-byte");
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, tanimoto_enqueue(a, b, n, both, either, similarity, (hipStream_t)stream));
     return MNX_OK;
 }
 
@@ -1996,376 +1386,6 @@ int mnx_predict_guided(mnx_engine* h, const void* images, int32_t img_format, in
     const ConfOut conf{token_logp, edge_scores, atom_scores, overall_score};
     return predict_impl(h, "mnx_predict_guided", images, img_format, n_img, ref_batch, max_len, 1, tokens, lengths, n_atoms,
                         atom_idx, edges, kmax, n_conf ? &conf : nullptr, stream, labels, L);
-}
-
-int mnx_gemm_clock(mnx_engine* h, int32_t reset, double* mhz) {
-    if (!h || !mhz) return MNX_ERR_INVALID_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipDeviceSynchronize());
-    HIPCHK(h, x3_clock_read(mhz, reset != 0));
-    return MNX_OK;
-}
-
-int mnx_probe_mfma(mnx_engine* h, int32_t ms_target, double* tflops, double* mhz, void* stream) {
-    if (!h || !tflops || !mhz || ms_target < 1 || ms_target > 2000) return MNX_ERR_INVALID_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    // 8 MFMAs of 16 cycles per iteration and wave, two waves per SIMD: ~256 cycles per iteration at ~1.9 GHz
-    const int iters = (int)((double)ms_target * 1e-3 * 1.9e9 / 256.0);
-    HIPCHK(h, mfma_probe(iters, (hipStream_t)stream, tflops, mhz));
-    return MNX_OK;
-}
-
-int mnx_profile_enable(mnx_engine* h, int32_t enable) {
-    if (!h) return MNX_ERR_INVALID_ARG;
-    h->profiling = enable != 0;
-    h->prof_stride = enable > 1 ? enable : 1;
-    h->prof_calls = 0;
-    h->prof_groups = 0;
-    return MNX_OK;
-}
-
-int mnx_profile_read(mnx_engine* h, int32_t kind, double* ms_out, double* work_out, int64_t* launches_out) {
-    if (!h) return MNX_ERR_INVALID_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    double ms = 0.0, work = 0.0;
-    int64_t n = 0;
-    for (size_t i = 0; i < h->ev_used; ++i) {
-        if (h->ev_pool[i].kind != kind) continue;
-        float t = 0.f;
-        HIPCHK(h, hipEventSynchronize(h->ev_pool[i].b));
-        HIPCHK(h, hipEventElapsedTime(&t, h->ev_pool[i].a, h->ev_pool[i].b));
-        ms += t;
-        work += h->ev_pool[i].work;
-        ++n;
-    }
-    if (ms_out) *ms_out = ms;
-    if (work_out) *work_out = work;
-    if (launches_out) *launches_out = n;
-    if (kind < 0) h->ev_used = 0;       // kind < 0: reset the pool (after the per-kind reads)
-    return MNX_OK;
-}
-
-int mnx_probe_decode_attn(mnx_engine* h, int32_t rows, int32_t t, int32_t iters, double* self_ms, double* cross_ms,
-                          void* stream) {
-    if (!h || rows < 1 || rows > h->db.slots || t < 0 || t >= h->db.T || iters < 1) return MNX_ERR_INVALID_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (auto& e : ev) HIPCHK(h, hipEventCreate(&e));
-    hipError_t err = dec_probe_attn(h->dw, h->db, rows, t, iters, ev, s);
-    if (err == hipSuccess) err = hipStreamSynchronize(s);
-    float a = 0.f, b = 0.f;
-    if (err == hipSuccess) err = hipEventElapsedTime(&a, ev[0], ev[1]);
-    if (err == hipSuccess) err = hipEventElapsedTime(&b, ev[2], ev[3]);
-    for (auto& e : ev) hipEventDestroy(e);
-    if (err != hipSuccess) { h->err = std::string("mnx_probe_decode_attn: ") + hipGetErrorString(err); return MNX_ERR_HIP; }
-    if (self_ms) *self_ms = (double)a / iters;
-    if (cross_ms) *cross_ms = (double)b / iters;
-    return MNX_OK;
-}
-
-int mnx_gemm16(mnx_engine* h, int32_t epi, const void* A, const void* W, void* C, const float* bias, int32_t M,
-               int32_t N, int32_t K, void* stream) {
-    if (!h || !A || !W || !C) return MNX_ERR_INVALID_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    const int dt = dt_base(h->dt);
-    if (!bias && N <= h->zero_bias_n) bias = h->zero_bias;
-    if (epi & 0x100) {      // test aid: the persistent fp32-output kernel (gemm_res.hip) whatever the dispatch would choose
-        epi &= 0xff;
-        if (!gemm_res_supports(dt, epi, M, N, K)) { h->err = "mnx_gemm16: shape / epilogue not supported by gemm_res"; return MNX_ERR_INVALID_ARG; }
-        HIPCHK(h, launch_gemm_res(dt, epi, A, W, (float*)C, bias, epi == EPI_RESID_F32 ? (const float*)C : nullptr, M, N, K,
-                                  (hipStream_t)stream));
-        return MNX_OK;
-    }
-    HIPCHK(h, launch_gemm16(dt, epi, A, W, C, bias, epi == EPI_RESID_F32 ? (const float*)C : nullptr, M, N, K,
-                            (hipStream_t)stream));
-    return MNX_OK;
-}
-
-int mnx_gemm16_split(mnx_engine* h, int32_t epi, const void* A, int64_t a_lo, const void* W, int64_t w_lo, float oscale,
-                     void* C, int64_t c_lo, const float* bias, int32_t M, int32_t N, int32_t K, int32_t terms,
-                     void* stream) {
-    if (!h || !A || !W || !C) return MNX_ERR_INVALID_ARG;
-    if (!dt_split(h->dt)) { h->err = "mnx_gemm16_split: the engine's compute_dtype is not a split mode"; return MNX_ERR_INVALID_ARG; }
-    if (a_lo < 0 || w_lo < 0 || c_lo < 0) { h->err = "mnx_gemm16_split: negative plane offset"; return MNX_ERR_INVALID_ARG; }
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!bias) {            // the kernels take a bias vector unconditionally: the engine's zero vector stands in
-        if (N > h->zero_bias_n) { h->err = "mnx_gemm16_split: bias == NULL needs N <= 2 * the widest stage"; return MNX_ERR_CAPACITY; }
-        bias = h->zero_bias;
-    }
-    if (terms < 1 || terms > 3 || (terms == 2 && h->dt != MNX_DT_F16X3)) {
-        h->err = "mnx_gemm16_split: terms must be 1, 3 or (FP16X3 / FP16X3M only) 2";
-        return MNX_ERR_INVALID_ARG;
-    }
-    SplitArgs sp;
-    sp.a_lo = (size_t)a_lo; sp.w_lo = (size_t)w_lo; sp.c_lo = (size_t)c_lo; sp.oscale = oscale; sp.terms = terms;
-    if (epi & 0x400) { sp.c_planes = 1; epi &= ~0x400; }      // 16-bit epilogues: the hi output plane only
-    if (epi & 0x200) {      // test aid: the 128x128 kernel whatever the dispatch would choose
-        epi &= 0xff;
-        HIPCHK(h, launch_gemm16_tile128(h->dt, epi, A, W, C, bias, epi == EPI_RESID_F32 ? (const float*)C : nullptr, M, N, K,
-                                        (hipStream_t)stream, &sp));
-        return MNX_OK;
-    }
-    if (epi & 0x100) {      // test aid: gemm_res.hip whatever the dispatch would choose
-        epi &= 0xff;
-        if (!gemm_res_supports(h->dt, epi, M, N, K)) { h->err = "mnx_gemm16_split: not supported by gemm_res"; return MNX_ERR_INVALID_ARG; }
-        HIPCHK(h, launch_gemm_res(h->dt, epi, A, W, (float*)C, bias, epi == EPI_RESID_F32 ? (const float*)C : nullptr,
-                                  M, N, K, (hipStream_t)stream, &sp));
-        return MNX_OK;
-    }
-    HIPCHK(h, launch_gemm16(h->dt, epi, A, W, C, bias, epi == EPI_RESID_F32 ? (const float*)C : nullptr, M, N,
-                            K, (hipStream_t)stream, &sp));
-    return MNX_OK;
-}
-
-int mnx_window_attn(mnx_engine* h, const void* qkv, int64_t qkv_lo, const float* table, void* out, int64_t out_lo,
-                    int32_t B, int32_t H, int32_t W, int32_t C, int32_t heads, int32_t shift, int32_t terms, void* stream) {
-    if (!h) return MNX_ERR_INVALID_ARG;
-    auto bad = [&](const char* m) { h->err = std::string("mnx_window_attn: ") + m; return MNX_ERR_INVALID_ARG; };
-    if (!qkv || !table || !out) return bad("null pointer");
-    if (((uintptr_t)qkv | (uintptr_t)out) & 15) return bad("qkv and out must be 16-byte aligned");
-    if (B < 1 || H < 12 || W < 12 || H % 12 || W % 12) return bad("B >= 1 and H, W positive multiples of the window (12) required");
-    if (heads < 1 || C != heads * 32) return bad("C must be heads * 32 (head_dim 32)");
-    if (shift < 0 || shift >= 12) return bad("shift must be 0..11");
-    const int64_t rows = (int64_t)B * H * W;
-    if (rows > INT32_MAX || (int64_t)B * (H / 12) * (W / 12) * heads > INT32_MAX)
-        return bad("B * H * W and the number of (window, head) items must fit in int32");
-    const bool split = dt_split(h->dt);
-    const int base = terms & 0xff;
-    if ((terms & ~0x1ff) || (split ? (base != 1 && base != 3) || ((terms & 0x100) && base != 3) : terms != 1))
-        return bad("terms must be 1 or 3 (| 0x100 with 3) for the split compute_dtypes and 1 for the others");
-    if (split) {
-        if (qkv_lo < rows * 3 * C || out_lo < rows * C || (qkv_lo | out_lo) & 7)
-            return bad("qkv_lo / out_lo must be at least the hi plane's size and multiples of 8 elements");
-        if ((int64_t)H * W * 3 * C * 2 > ((int64_t)1 << 32)) return bad("one image's qkv plane exceeds 2^32 bytes");
-    } else if (qkv_lo || out_lo) {
-        return bad("qkv_lo / out_lo must be 0 for the single-plane compute_dtypes");
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, launch_window_attn(h->dt, qkv, table, out, B, H, W, C, heads, shift, (hipStream_t)stream, (size_t)qkv_lo,
-                                 (size_t)out_lo, terms));
-    return MNX_OK;
-}
-
-int mnx_kv_block(mnx_engine* h, int32_t which, int32_t layer, int32_t owner, int32_t head, void* dst, void* stream) {
-    if (!h) return MNX_ERR_INVALID_ARG;
-    auto bad = [&](const char* m) { h->err = std::string("mnx_kv_block: ") + m; return MNX_ERR_INVALID_ARG; };
-    const mnx_config& c = h->cfg;
-    const DecBuffers& db = h->db;
-    if (!dst) return bad("null dst");
-    if (which < 0 || which > 3) return bad("which must be 0 (self K), 1 (self V), 2 (memory K) or 3 (memory V)");
-    if (layer < 0 || layer >= c.dec_layers || head < 0 || head >= c.dec_heads) return bad("layer or head out of range");
-    const char* src;
-    size_t bytes;
-    if (which < 2) {
-        if (owner < 0 || owner >= db.slots) return bad("slot out of range");
-        bytes = kvq_block_bytes(db.Tq);   // self_k / self_v: [layer][slot][head] blocks of Tq rows
-        src = (which == 0 ? db.self_k : db.self_v) + (((size_t)layer * db.slots + owner) * c.dec_heads + head) * bytes;
-    } else {
-        if (owner < 0 || owner >= db.mem_blocks) return bad("memory block out of range");
-        bytes = kvq_block_bytes(db.Sq);   // mem_kv: [memory block][layer][K|V][head] blocks of Sq rows
-        src = db.mem_kv + ((((size_t)owner * c.dec_layers + layer) * 2 + (which - 2)) * c.dec_heads + head) * bytes;
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return MNX_OK;
-}
-
-int mnx_beam_scripted(mnx_engine* h, const float* table, int32_t B, int32_t beam, int32_t n_best, int32_t max_len, int32_t V,
-                      int32_t eos, int32_t* tokens, int32_t* lengths, float* scores, int32_t* steps_run, int32_t* tr_parent,
-                      int32_t* tr_token, float* tr_score, int32_t* tr_alive, int32_t* tr_n_active, void* stream) {
-    if (!h) return MNX_ERR_INVALID_ARG;
-    auto bad = [&](const char* m) { h->err = std::string("mnx_beam_scripted: ") + m; return MNX_ERR_INVALID_ARG; };
-    const mnx_config& c = h->cfg;
-    if (!table || !tokens || !lengths || !scores || !steps_run) return bad("null table, tokens, lengths, scores or steps_run");
-    const int n_tr = !!tr_parent + !!tr_token + !!tr_score + !!tr_alive + !!tr_n_active;
-    if (n_tr != 0 && n_tr != 5) return bad("the five trace pointers must be all null or all set");
-    if (B < 1) return bad("B must be 1..32");
-    if (beam < 1 || beam > MAX_BEAM) return bad("beam must be 1..8");
-    if (n_best < 1 || n_best > beam) return bad("n_best must be 1..beam");
-    if (V < 2 || V > BEAM_LP_STRIDE) return bad("V must be 2..256");
-    if (eos < 0 || eos >= V) return bad("eos must be 0..V-1");
-    if (max_len < 1 || max_len > c.max_len || c.max_len + 1 > BEAM_ANC_MAX) return bad("max_len must be 1..cfg.max_len (<= 511)");
-    // the pool first: with B <= 32 it keeps 8 per image, so only a larger B can ask for more than it holds
-    if (n_best > beam_pool_stride(B)) return bad("n_best exceeds the hypotheses the pool keeps per image (256 / B)");
-    if (B > ROW_TILE) return bad("B must be 1..32");
-    if (B * beam > h->db.slots) return bad("B x beam exceeds dec_slots");
-    hipStream_t s;
-    MNXCHK(caller_stream(h, stream, &s));
-    MNXCHK(beam_buffers(h, B, B, beam, n_best, false));
-    MNXCHK(lazy_alloc(h, &h->script_nact, (size_t)c.max_len * 4));
-    BeamBuffers run = h->beam;
-    run.phid = nullptr;
-    run.tr_parent = tr_parent; run.tr_token = tr_token; run.tr_score = tr_score; run.tr_alive = tr_alive;
-    HIPCHK(h, dec_enqueue_reset(h->db, s));
-    HIPCHK(h, beam_enqueue_init(h->db, run, max_len, s));
-    const int rows = (B * beam + ROW_TILE - 1) / ROW_TILE * ROW_TILE;
-    int step = 0;       // steps enqueued so far; the loop is run_steps' (groups of 8, then the alive count), without a graph
-    MNXCHK(run_steps(h, nullptr, [&]() { return beam_enqueue_script_step(h->db, run, table, V, eos, h->script_nact + step++, s); },
-                     rows, max_len, s));
-    HIPCHK(h, beam_enqueue_gather(h->db, run, max_len, tokens, lengths, scores, nullptr, s));
-    std::vector<int> nact(step);
-    HIPCHK(h, hipMemcpyAsync(nact.data(), h->script_nact, (size_t)step * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    int n_run = 0;      // a step whose begin kernel found no row alive ran nothing
-    while (n_run < step && nact[n_run] > 0) ++n_run;
-    if (tr_n_active && n_run)
-        HIPCHK(h, hipMemcpyAsync(tr_n_active, h->script_nact, (size_t)n_run * 4, hipMemcpyDeviceToDevice, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    *steps_run = n_run;
-    return MNX_OK;
-}
-
-int mnx_decode_beam_forced(mnx_engine* h, const float* features, int32_t B, int32_t beam, int32_t n_best, int32_t max_len,
-                           const int32_t* script_parent, const int32_t* script_token, int64_t script_len, int32_t* tokens,
-                           int32_t* lengths, float* scores, float* hidden, float* logits_trace, void* stream) {
-    if (!h) return MNX_ERR_INVALID_ARG;
-    auto bad = [&](const std::string& m) { h->err = "mnx_decode_beam_forced: " + m; return MNX_ERR_INVALID_ARG; };
-    const mnx_config& c = h->cfg;
-    if (!features || !script_parent || !script_token || !tokens || !lengths || !scores)
-        return bad("null features, script_parent, script_token, tokens, lengths or scores");
-    if (B < 1 || B > ROW_TILE) return bad("B must be 1..32");
-    if (beam < 1 || beam > MAX_BEAM) return bad("beam must be 1..8");
-    if (n_best < 1 || n_best > beam) return bad("n_best must be 1..beam");
-    if (max_len < 1 || max_len > c.max_len || c.max_len + 1 > BEAM_ANC_MAX) return bad("max_len must be 1..cfg.max_len (<= 511)");
-    if (c.vocab > BEAM_LP_STRIDE) return bad("the vocabulary exceeds 256 ids");
-    if (B * beam > h->db.slots) return bad("B x beam exceeds dec_slots");
-    const size_t n = (size_t)max_len * B * beam;
-    if (script_len < 0 || (uint64_t)script_len < n) return bad("script_len is less than max_len x B x beam");
-    // the script as the device will read it: every element checked on its way into the copy that is uploaded
-    std::vector<int> script(2 * n);
-    auto at = [&](size_t i, int x) {
-        return "[" + std::to_string(i / ((size_t)B * beam)) + "][" + std::to_string(i / beam % B) + "][" + std::to_string(i % beam) +
-               "] = " + std::to_string(x);
-    };
-    for (size_t i = 0; i < n; ++i) {
-        const int p = script_parent[i], v = script_token[i];
-        if (p < 0 || p >= beam) return bad("script_parent" + at(i, p) + " is outside 0..beam-1");
-        if (v < 0 || v >= c.vocab) return bad("script_token" + at(i, v) + " is outside 0..vocab-1");
-        script[i] = p; script[n + i] = v;
-    }
-    hipStream_t s;
-    MNXCHK(caller_stream(h, stream, &s));
-    MNXCHK(lazy_alloc(h, &h->beam_script, (size_t)2 * c.max_len * ROW_TILE * MAX_BEAM * 4));
-    HIPCHK(h, hipMemcpyAsync(h->beam_script, script.data(), 2 * n * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipStreamSynchronize(s));      // `script` is pageable host memory of this call
-    return decode_beam_groups(h, &features, 1, B, B, beam, n_best, max_len, tokens, lengths, scores, hidden, s, h->beam_script,
-                              logits_trace);
-}
-
-// ---- test aids: the encoder's non-GEMM kernels and the fp32 SGEMM on caller buffers (tests/test_gpu_encoder_ops.py) ----
-// Each checks everything its launcher assumes (and what the launcher leaves to the encoder: positive sizes, alignment of
-// the 16-byte accesses) and launches nothing when it refuses.
-static bool misaligned16(std::initializer_list<const void*> ps) {
-    uintptr_t a = 0;
-    for (const void* p : ps) a |= (uintptr_t)p;
-    return (a & 15) != 0;
-}
-
-int mnx_patch_embed(mnx_engine* h, const void* img, int32_t img_format, const float* w_t, const float* bias,
-                    const float* gamma, const float* beta, float* x, int32_t B, int32_t S, int32_t C, void* stream) {
-    if (!h) return MNX_ERR_INVALID_ARG;
-    auto bad = [&](const char* m) { h->err = std::string("mnx_patch_embed: ") + m; return MNX_ERR_INVALID_ARG; };
-    if (img_format != MNX_IMG_F32 && img_format != MNX_IMG_GRAY8) return bad("img_format must be MNX_IMG_F32 or MNX_IMG_GRAY8");
-    if (!img || !w_t || !bias || !gamma || !beta || !x) return bad("null pointer");
-    if (misaligned16({w_t, bias, gamma, beta, x})) return bad("w_t, bias, gamma, beta and x must be 16-byte aligned");
-    if ((uintptr_t)img & (img_format == MNX_IMG_GRAY8 ? 3 : 15))
-        return bad("img must be 16-byte (MNX_IMG_F32) or 4-byte (MNX_IMG_GRAY8) aligned");
-    if (C < 32 || C > 128 || (C & 31)) return bad("C must be 32, 64, 96 or 128");
-    if (S < 4 || (S & 3)) return bad("S must be a positive multiple of the patch size (4)");
-    if (B < 1 || B > 65535) return bad("B must be 1..65535");
-    if ((int64_t)B * (S / 4) * (S / 4) > INT32_MAX) return bad("B * (S/4)^2 must fit in int32");
-    HIPCHK(h, hipSetDevice(h->device));
-    if (img_format == MNX_IMG_GRAY8)
-        HIPCHK(h, launch_patch_embed_gray8((const uint8_t*)img, w_t, bias, gamma, beta, x, B, S, C, (hipStream_t)stream));
-    else
-        HIPCHK(h, launch_patch_embed((const float*)img, w_t, bias, gamma, beta, x, B, S, C, (hipStream_t)stream));
-    return MNX_OK;
-}
-
-int mnx_layernorm16(mnx_engine* h, const float* x, const float* gamma, const float* beta, void* y16, int64_t y_lo,
-                    float* y32, int32_t M, int32_t C, float eps, int32_t planes, int32_t* flag, void* stream) {
-    if (!h) return MNX_ERR_INVALID_ARG;
-    auto bad = [&](const char* m) { h->err = std::string("mnx_layernorm16: ") + m; return MNX_ERR_INVALID_ARG; };
-    if (!x || !gamma || !beta) return bad("null pointer");
-    if (!y16 && !y32) return bad("y16 and y32 are both null");
-    if (misaligned16({x, gamma, beta, y32}) || ((uintptr_t)y16 & 7) || (h->dt == MNX_DT_F32 && ((uintptr_t)y16 & 15)))
-        return bad("x, gamma, beta and y32 must be 16-byte aligned, y16 8-byte (16-byte for FP32)");
-    if ((uintptr_t)flag & 3) return bad("flag must be 4-byte aligned");
-    if (M < 1 || (int64_t)M + 8 > INT32_MAX) return bad("M must be positive (and M + 8 fit in int32)");
-    if (C < 4 || C > 2048 || (C & 3)) return bad("C must be a multiple of 4 in 4..2048");
-    if (!(eps >= 0.f)) return bad("eps must be >= 0");
-    if (planes != 1 && planes != 2) return bad("planes must be 1 or 2");
-    if (dt_split(h->dt)) {
-        if (planes == 2 && y16 && (y_lo < (int64_t)M * C || (y_lo & 7)))
-            return bad("y_lo must be at least M * C and a multiple of 8 elements");
-        if (y_lo < 0) return bad("y_lo must not be negative");
-    } else if (y_lo || planes != 2) {
-        return bad("y_lo must be 0 and planes 2 for the single-plane compute_dtypes");
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, launch_layernorm16(h->dt, x, gamma, beta, y16, y32, M, C, eps, (hipStream_t)stream, (size_t)y_lo, flag, planes));
-    return MNX_OK;
-}
-
-int mnx_merge_ln16(mnx_engine* h, const float* x, const float* gamma, const float* beta, void* y16, int64_t y_lo,
-                   int32_t B, int32_t H, int32_t W, int32_t C, float eps, int32_t planes, void* stream) {
-    if (!h) return MNX_ERR_INVALID_ARG;
-    auto bad = [&](const char* m) { h->err = std::string("mnx_merge_ln16: ") + m; return MNX_ERR_INVALID_ARG; };
-    if (!x || !gamma || !beta || !y16) return bad("null pointer");
-    if (misaligned16({x, gamma, beta}) || ((uintptr_t)y16 & 7) || (h->dt == MNX_DT_F32 && ((uintptr_t)y16 & 15)))
-        return bad("x, gamma and beta must be 16-byte aligned, y16 8-byte (16-byte for FP32)");
-    if (B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1)) return bad("B >= 1 and H, W positive even numbers required");
-    if (C < 4 || 4 * (int64_t)C > 2048 || (C & 3)) return bad("C must be a multiple of 4 in 4..512");
-    if ((int64_t)B * H * W > INT32_MAX) return bad("B * H * W must fit in int32");
-    if (!(eps >= 0.f)) return bad("eps must be >= 0");
-    if (planes != 1 && planes != 2) return bad("planes must be 1 or 2");
-    const int64_t out = (int64_t)B * (H / 2) * (W / 2) * 4 * C;
-    if (dt_split(h->dt)) {
-        if (planes == 2 && (y_lo < out || (y_lo & 7))) return bad("y_lo must be at least B * H/2 * W/2 * 4C and a multiple of 8 elements");
-        if (y_lo < 0) return bad("y_lo must not be negative");
-    } else if (y_lo || planes != 2) {
-        return bad("y_lo must be 0 and planes 2 for the single-plane compute_dtypes");
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, launch_merge_ln16(h->dt, x, gamma, beta, y16, B, H, W, C, eps, (hipStream_t)stream, (size_t)y_lo, planes));
-    return MNX_OK;
-}
-
-int mnx_cast16(mnx_engine* h, const float* x, void* y16, int64_t y_lo, int64_t n, float scale, void* stream) {
-    if (!h) return MNX_ERR_INVALID_ARG;
-    auto bad = [&](const char* m) { h->err = std::string("mnx_cast16: ") + m; return MNX_ERR_INVALID_ARG; };
-    if (!x || !y16) return bad("null pointer");
-    if (((uintptr_t)x & 15) || ((uintptr_t)y16 & 7) || (h->dt == MNX_DT_F32 && ((uintptr_t)y16 & 15)))
-        return bad("x must be 16-byte aligned, y16 8-byte (16-byte for FP32)");
-    if (n < 4 || (n & 3)) return bad("n must be a positive multiple of 4");
-    if (dt_split(h->dt)) {
-        if (y_lo < n || (y_lo & 3)) return bad("y_lo must be at least n and a multiple of 4 elements");
-        if (!(scale > 0.f) || !(scale < INFINITY)) return bad("scale must be positive and finite");
-    } else if (y_lo) {
-        return bad("y_lo must be 0 for the single-plane compute_dtypes");
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, launch_cast16(h->dt, x, y16, (size_t)n, (hipStream_t)stream, (size_t)y_lo, scale));
-    return MNX_OK;
-}
-
-int mnx_sgemm_tn(mnx_engine* h, const float* A, const float* W, const float* bias, float* C, int32_t M, int32_t N,
-                 int32_t K, int32_t perm_S, void* stream) {
-    if (!h) return MNX_ERR_INVALID_ARG;
-    auto bad = [&](const char* m) { h->err = std::string("mnx_sgemm_tn: ") + m; return MNX_ERR_INVALID_ARG; };
-    if (!A || !W || !C) return bad("null pointer");
-    if (misaligned16({A, W, bias, C})) return bad("A, W, bias and C must be 16-byte aligned");
-    if (M < 1 || N < 4 || K < 16) return bad("M >= 1, N >= 4 and K >= 16 required");
-    if (K & 15) return bad("K must be a multiple of 16");
-    if (N & 3) return bad("N must be a multiple of 4");
-    if (perm_S < 0) return bad("perm_S must not be negative");
-    if (perm_S > 0 && (N & 255)) return bad("perm_S needs N to be a multiple of 256");
-    if (perm_S > 0 && M % perm_S) return bad("perm_S must divide M");
-    if ((M + 63) / 64 > 65535) return bad("M must be at most 65535 * 64");
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, launch_sgemm_tn(A, W, bias, C, M, N, K, (hipStream_t)stream, perm_S));
-    return MNX_OK;
 }
 
 }  // extern "C"

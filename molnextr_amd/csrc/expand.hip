@@ -16,8 +16,8 @@
 
 #include "../../include/molnextr_hip.h"
 #include "atom_symbol.h"
-#include "dec_types.h"
 #include "grow_pass.h"
+#include "table_passes.h"
 
 namespace mnx {
 namespace {

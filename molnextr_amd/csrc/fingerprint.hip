@@ -16,8 +16,8 @@
 #include "../../include/molnextr_hip.h"
 #include "atom_symbol.h"
 #include "atom_write.h"
-#include "dec_types.h"
 #include "mol_graph.h"
+#include "table_passes.h"
 
 namespace mnx {
 

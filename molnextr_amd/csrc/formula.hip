@@ -17,9 +17,9 @@
 #include "../../include/molnextr_hip.h"
 #include "atom_spell.h"
 #include "atom_symbol.h"
-#include "dec_types.h"
 #include "formula_search.h"
 #include "grow_pass.h"
+#include "table_passes.h"
 
 namespace mnx {
 namespace {

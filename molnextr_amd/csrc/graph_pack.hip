@@ -11,7 +11,8 @@
 
 #include "../../include/molnextr_hip.h"
 #include "atom_walk.h"
-#include "dec_types.h"
+#include "dec_types.h"       // TokenClasses: the ids are walked with the model's token classes (atom_walk.h)
+#include "table_passes.h"
 #include "tables_out.h"
 
 namespace mnx {

@@ -9,6 +9,7 @@
 // then ONE LANE PER SYSTEM runs the search of kekule_search.h, the systems of a molecule side by side, everything in LDS; then
 // every atom's new symbol.
 #include "respell_pass.h"
+#include "table_passes.h"
 #include "kekule_search.h"              // behind the HIP runtime, which the tools' host build of it does without
 
 namespace mnx {

@@ -18,8 +18,8 @@
 #include <stdint.h>
 
 #include "../../include/molnextr_hip.h"
-#include "dec_types.h"
 #include "select_pass.h"
+#include "table_passes.h"
 
 namespace mnx {
 namespace {

@@ -13,7 +13,7 @@
 #include "../../include/molnextr_hip.h"
 #include "atom_symbol.h"
 #include "block_scan.h"
-#include "dec_types.h"
+#include "table_passes.h"
 
 namespace mnx {
 

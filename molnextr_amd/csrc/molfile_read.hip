@@ -19,8 +19,8 @@
 #include <stdint.h>
 
 #include "../../include/molnextr_hip.h"
-#include "dec_types.h"
 #include "molfile_fields.h"
+#include "table_passes.h"
 #include "tables_out.h"
 
 namespace mnx {

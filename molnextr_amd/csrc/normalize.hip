@@ -9,6 +9,7 @@
 // bonds and atoms that lie on such a ring, once to judge every ring —, then every atom's new symbol. Every loop has a bound known
 // at compile time or is a stride over the molecule's records.
 #include "respell_pass.h"
+#include "table_passes.h"
 
 namespace mnx {
 namespace {

@@ -21,8 +21,8 @@
 #include "atom_symbol.h"
 #include "atom_write.h"
 #include "block_scan.h"
-#include "dec_types.h"
 #include "mol_graph.h"
+#include "table_passes.h"
 
 namespace mnx {
 

@@ -19,7 +19,7 @@
 #include <stdint.h>
 
 #include "../../include/molnextr_hip.h"
-#include "dec_types.h"
+#include "table_passes.h"
 #include "tables_out.h"
 
 namespace mnx {

@@ -2,14 +2,14 @@
 // respell_pass.h, expand.hip and formula.hip through grow_pass.h, main_mol.hip through select_pass.h), once (internal): how the fields of an atom and a bond record
 // lie in their 64-bit words, the capped stores behind an offset, what a count kernel leaves in mnx_mol, the scan over the
 // molecules between count and fill, and the three launches. A fill kernel says where a record's fields come from; where they
-// go is here. The arenas arrive as a TablesOut (dec_types.h). One molecule of a pass from tables to tables is table_pass.h.
+// go is here. The arenas arrive as a TablesOut (table_types.h). One molecule of a pass from tables to tables is table_pass.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
 #include "../../include/molnextr_hip.h"
 #include "block_scan.h"
-#include "dec_types.h"
+#include "table_types.h"
 
 namespace mnx {
 
