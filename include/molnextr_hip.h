@@ -1461,6 +1461,91 @@ int mnx_fingerprint_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mn
 int mnx_tanimoto(mnx_engine* h, const uint32_t* a, const uint32_t* b, int32_t n, uint32_t* both, uint32_t* either,
                  double* similarity, void* stream);
 
+/* Substructure search, on the device: for pairs of a QUERY molecule Q and a TARGET molecule T, each one molecule of a set of packed
+ * tables (the two sets may be the same), whether Q embeds in T, how often, and where: the first embedding as a map from Q's atoms
+ * to T's, whose mnx_atom records carry the coordinate bins — a scaffold found is a place on the page. Run in both directions on
+ * molecules with equal atom and bond counts it is a test of graph isomorphism that depends on no canonical ranking (the ranks have
+ * a KNOWN LIMIT, mnx_smiles_pack_canonical). A sink like mnx_fingerprint_pack: packed tables in, a record and a map per pair out.
+ * Intended order: both sides -> the passes -> mnx_kekulize_pack -> mnx_normalize_pack -> THIS CALL, so that both have one spelling.
+ * THE RULE IS THIS LIBRARY'S OWN. It is NOT RDKit's HasSubstructMatch, it is not SMARTS, and no toolkit has checked it.
+ *
+ * Admission. Each side is admitted exactly as mnx_fingerprint_pack admits a molecule. The target's bits stand in flags bits 0-4
+ *   with the MNX_FP_* values, the query's in bits 8-12 (the same values << MNX_MATCH_QUERY_SHIFT); bits 2 and 3 (10 and 11) are
+ *   informational. MNX_MATCH_QUERY_TOO_LARGE (bit 5): a query that is otherwise admitted has more than MNX_MATCH_MAX_QUERY (64)
+ *   atoms or more than MNX_MATCH_MAX_QUERY_BONDS (128) bonds. MNX_MATCH_QUERY_EMPTY (bit 6): an admitted query has no atom.
+ *   MNX_MATCH_BAD_PAIR (bit 17): the pair names a molecule index outside either table — the indices are device data, so this is
+ *   no argument error; no other bit is set then. The refusing bits are 0, 1, 4, 8, 9, 12, 5, 6 and 17: a refused pair has
+ *   n_matches 0, steps 0 and a map of all 0xFFFF. Both sides' bits are always reported, whichever refuses.
+ * Atom match, query atom q against target atom t. q is a WILDCARD when it is a pseudo-atom, a numbered R-group, or an atom whose
+ *   element a writer puts down as '*'; a wildcard matches every target atom. Otherwise t must be a plain atom, not itself spelled
+ *   '*', with the same element, the same aromatic (lower-case) bit and the same charge, and the same isotope unless q's isotope is
+ *   0. LIMITS: H counts and brackets are NOT compared ('[NH4+]' matches '[N+]', 'N' matches '[NH2]'), and stereo is NOT compared
+ *   (wedges count as single bonds, '@' marks were dropped by the readers). deg(q) <= deg(t) follows; it is no separate condition.
+ * Bond match. A bond record's class is 0 for type 1, 5 or 6 (a wedge is a single bond), 1 for type 2, 2 for type 3, 3 for type 4
+ *   and 4 (ANY) for every other type. A query bond of class ANY matches every target bond; any other class matches a target bond
+ *   of the same class only (a target bond of class ANY is matched by a query bond of class ANY alone). `rev` is not read.
+ * Embedding. An injective map of Q's atoms into T's atoms such that every pair of atoms matches and every query bond lies on a
+ *   matching target bond. Further target bonds among the images are allowed — the match is NOT induced: propane embeds in
+ *   cyclopropane, cyclopropane does not embed in propane. Embeddings are counted as maps: benzene embeds 12 times in toluene.
+ * Order of the query atoms. Breadth first from the lowest-numbered atom not yet placed, an atom's neighbours in ascending index,
+ *   repeated until every atom is placed (a disconnected query is supported). Position k has parent[k], its breadth-first parent;
+ *   the first atom of each component has none. This order defines "the first embedding" and the steps.
+ * Candidates. At position 0 each target atom in turn is the ROOT of a search of its own. At a later position with a parent the
+ *   candidates are the neighbours of the parent's image in ascending target index; at the first atom of a later component they
+ *   are all target atoms, ascending. A candidate is ACCEPTED when it is not yet an image, the atoms match, and every query bond
+ *   from this atom to an atom placed earlier has a matching target bond.
+ * Steps. Every candidate examined costs one step, whatever rejects it, and so does the root. The depth-first search from root r
+ *   ends when it runs out of candidates, when it reaches its max_matches-th embedding, or when its step count S(r) passes
+ *   max_steps (it is then BROKEN OFF).
+ * Results. n_matches = min(max_matches, the sum over all roots of the embeddings found). steps = the maximum over the roots of
+ *   S(r), max_steps + 1 for a search broken off. MNX_MATCH_LIMIT (bit 16): some root was broken off and n_matches < max_matches
+ *   — the count is then a lower bound; n_matches >= 1 is a certain yes with or without bit 16. The map: the first embedding of
+ *   the lowest root that has one — the lexicographically smallest image sequence along the order —, maps[p][a] the image of query
+ *   atom a, 0xFFFF beyond the query's atoms or without a match. All of these are properties of the two graphs, not of how the
+ *   roots are dealt to lanes: no search stops because another has found something.
+ * max_matches: 0 means 1; more than 65535 is an argument error. max_steps: 0 means MNX_MATCH_DEFAULT_STEPS; more than
+ *   MNX_MATCH_MAX_STEPS is an argument error (a dense graph must not park a workgroup for minutes).
+ *   Measured with the oracle of tests/substructure_ref.py, the largest S(r) at max_matches 1 / 65535: benzene in coronene 18 / 131,
+ *   naphthalene in coronene 105 / 175, an aromatic 12-ring in coronene 160 / 1397, an aromatic 12-chain in coronene 22 / 709, the
+ *   cholest-5-ene core in cholesterol 89 / 110 (the saturated gonane core, which the double bond keeps out: 131 / 131), the taxane
+ *   core in taxol 59 / 85, coronene in itself 423 / 423, an aromatic 18-ring in coronene 100 / 3739, aromatic chains of 24 and 25
+ *   atoms in coronene (24 atoms) 3063 / 3805 and 3815 / 3815; the 64 random pairs of tests/test_gpu_substructure.py 23 / 25. The
+ *   default is the next power of two at least 16 times above the largest, 3815. LIMIT: no all-carbon query in these polycycles came
+ *   near 1 << 20, but a dense target does — a chain of seven C and one N in the complete graph on nine C takes 231689 steps to be
+ *   refuted and is reported with bit 16 at the default, not searched to the end.
+ * recs[p]: flags; n_matches; steps; reserved 0.
+ * Inputs: the two sides as mnx_fingerprint_pack's input side, 1 <= nq, nt <= 65536; pairs: device uint32 [n_pairs][2], the query
+ * index then the target index, 1 <= n_pairs <= 1048576; mnx_set_symbol_tables must have been called. Outputs, device pointers the
+ * caller allocated: recs [n_pairs], maps uint16 [n_pairs][MNX_MATCH_MAX_QUERY]. Deterministic word for word: the embeddings are
+ * summed, the steps a maximum and the winning root a minimum in on-chip memory, none of which depends on the order of its
+ * operands; no atomic decides a result. Records and maps are written whole. One launch, asynchronous on `stream`, no allocation,
+ * no host synchronisation.
+ * MNX_ERR_INVALID_ARG (with mnx_last_error, "mnx_substructure_match: ..."): a null pointer (an input table of 0 records may be
+ * null), nq or nt outside 1..65536, n_pairs outside 1..1048576, misaligned pointers (records 8-byte, pairs and recs 4-byte, maps
+ * 2-byte), no symbol tables set, max_matches above 65535, max_steps above MNX_MATCH_MAX_STEPS; nothing is launched then. */
+typedef struct mnx_match {
+    uint32_t flags;             /* MNX_FP_* of the target, the same << MNX_MATCH_QUERY_SHIFT of the query, MNX_MATCH_* */
+    uint32_t n_matches;         /* embeddings found, max_matches at the most */
+    uint32_t steps;             /* the longest search of one root; max_steps + 1 when one was broken off */
+    uint32_t reserved;          /* 0 */
+} mnx_match;
+#define MNX_MATCH_QUERY_TOO_LARGE 32u
+#define MNX_MATCH_QUERY_EMPTY 64u
+#define MNX_MATCH_QUERY_SHIFT 8
+#define MNX_MATCH_LIMIT 65536u
+#define MNX_MATCH_BAD_PAIR 131072u
+#define MNX_MATCH_MAX_QUERY 64u
+#define MNX_MATCH_MAX_QUERY_BONDS 128u
+#define MNX_MATCH_DEFAULT_STEPS 65536u
+#define MNX_MATCH_MAX_STEPS (1u << 20)
+int mnx_substructure_match(mnx_engine* h,
+                           const mnx_mol* q_mols, int32_t nq, const mnx_atom* q_atoms, uint32_t q_atom_records, const mnx_bond* q_bonds,
+                           uint32_t q_bond_records, const char* q_text, uint32_t q_text_bytes,
+                           const mnx_mol* t_mols, int32_t nt, const mnx_atom* t_atoms, uint32_t t_atom_records, const mnx_bond* t_bonds,
+                           uint32_t t_bond_records, const char* t_text, uint32_t t_text_bytes,
+                           const uint32_t* pairs, int32_t n_pairs, mnx_match* recs, uint16_t* maps,
+                           uint32_t max_matches, uint32_t max_steps, void* stream);
+
 /* mnx_predict with beam search (BASELINE config 5): the same inputs and outputs, every reference batch searched as
  * mnx_decode_beam does (n_best = 1: the best hypothesis; atom positions and the bond head run on ITS tokens and decoder
  * outputs) while the encoder of the following launch groups runs on the second stream. Up to MNX_BEAM_GROUPS (environment,

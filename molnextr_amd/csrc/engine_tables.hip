@@ -331,6 +331,35 @@ int mnx_fingerprint_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mn
     return MNX_OK;
 }
 
+int mnx_substructure_match(mnx_engine* h,
+                           const mnx_mol* q_mols, int32_t nq, const mnx_atom* q_atoms, uint32_t q_atom_records, const mnx_bond* q_bonds,
+                           uint32_t q_bond_records, const char* q_text, uint32_t q_text_bytes,
+                           const mnx_mol* t_mols, int32_t nt, const mnx_atom* t_atoms, uint32_t t_atom_records, const mnx_bond* t_bonds,
+                           uint32_t t_bond_records, const char* t_text, uint32_t t_text_bytes,
+                           const uint32_t* pairs, int32_t n_pairs, mnx_match* recs, uint16_t* maps,
+                           uint32_t max_matches, uint32_t max_steps, void* stream) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    auto bad = [&](const char* m) { h->err = std::string("mnx_substructure_match: ") + m; return MNX_ERR_INVALID_ARG; };
+    const PackedTables q = packed_tables(q_mols, nq, q_atoms, q_atom_records, q_bonds, q_bond_records, q_text, q_text_bytes);
+    const PackedTables t = packed_tables(t_mols, nt, t_atoms, t_atom_records, t_bonds, t_bond_records, t_text, t_text_bytes);
+    for (const PackedTables* s : {&q, &t})
+        if (!s->mols || (!s->atoms && s->n_atom_records) || (!s->bonds && s->n_bond_records) || (!s->text && s->n_text_bytes))
+            return bad("null pointer");
+    if (!pairs || !recs || !maps) return bad("null pointer");
+    if (nq < 1 || nq > 65536 || nt < 1 || nt > 65536) return bad("1 <= nq <= 65536 and 1 <= nt <= 65536 required");
+    if (n_pairs < 1 || n_pairs > 1048576) return bad("1 <= n_pairs <= 1048576 required");
+    if ((((uintptr_t)q.mols | (uintptr_t)q.atoms | (uintptr_t)q.bonds | (uintptr_t)t.mols | (uintptr_t)t.atoms | (uintptr_t)t.bonds) & 7) ||
+        (((uintptr_t)pairs | (uintptr_t)recs) & 3) || ((uintptr_t)maps & 1))
+        return bad("mols, atoms and bonds of both sides must be 8-byte aligned, pairs and recs 4-byte, maps 2-byte");
+    if (!h->have_st) return bad("call mnx_set_symbol_tables first");
+    if (max_matches > 65535) return bad("max_matches must not exceed 65535");
+    if (max_steps > MNX_MATCH_MAX_STEPS) return bad("max_steps must not exceed MNX_MATCH_MAX_STEPS (1048576)");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, match_enqueue(h->st_dev, q, t, pairs, n_pairs, recs, maps, max_matches ? max_matches : 1u,
+                            max_steps ? max_steps : MNX_MATCH_DEFAULT_STEPS, (hipStream_t)stream));
+    return MNX_OK;
+}
+
 int mnx_tanimoto(mnx_engine* h, const uint32_t* a, const uint32_t* b, int32_t n, uint32_t* both, uint32_t* either,
                  double* similarity, void* stream) {
     if (!h) return MNX_ERR_INVALID_ARG;

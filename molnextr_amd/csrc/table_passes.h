@@ -61,6 +61,11 @@ hipError_t fingerprint_pack_enqueue(const SymbolTables* st_dev, const PackedTabl
 // the Tanimoto similarity of row r of a and row r of b, n rows of 64 words (mnx_tanimoto; each output may be null): one launch on s
 hipError_t tanimoto_enqueue(const unsigned* a, const unsigned* b, int n, unsigned* both, unsigned* either, double* similarity,
                             hipStream_t s);
+// match.hip: for pair p = (pairs[2p], pairs[2p + 1]) whether, how often and where molecule pairs[2p] of q embeds in molecule
+// pairs[2p + 1] of t — a record in recs, MNX_MATCH_MAX_QUERY target atoms in maps (mnx_substructure_match): one launch on s.
+// max_matches 1 .. 65535 and max_steps 1 .. MNX_MATCH_MAX_STEPS, the defaults resolved
+hipError_t match_enqueue(const SymbolTables* st_dev, const PackedTables& q, const PackedTables& t, const unsigned* pairs, int n_pairs,
+                         mnx_match* recs, unsigned short* maps, unsigned max_matches, unsigned max_steps, hipStream_t s);
 // smiles_read.hip: string b = bytes[offsets[b] .. offsets[b + 1]) read as SMILES into packed tables of mnx_graph_pack's record types
 // (mnx_smiles_read): count, scan and fill, three launches on s
 hipError_t smiles_read_enqueue(const unsigned char* bytes, unsigned n_bytes, const unsigned* offsets, int n, mnx_read* recs,

@@ -30,7 +30,8 @@ SYMBOLS = ("mnx_abi_version", "mnx_create", "mnx_destroy", "mnx_last_error", "mn
            "mnx_set_symbol_tables", "mnx_molfile_pack", "mnx_smiles_pack", "mnx_smiles_pack_stereo",
            "mnx_smiles_pack_marks", "mnx_smiles_pack_canonical", "mnx_smiles_pack_symmetric", "mnx_set_fragments", "mnx_expand_pack", "mnx_smiles_read",
            "mnx_beam_scripted", "mnx_edge_probs", "mnx_normalize_pack", "mnx_kekulize_pack", "mnx_formula_pack",
-           "mnx_decode_beam_forced", "mnx_main_pack", "mnx_fingerprint_pack", "mnx_tanimoto", "mnx_molfile_read")
+           "mnx_decode_beam_forced", "mnx_main_pack", "mnx_fingerprint_pack", "mnx_tanimoto", "mnx_molfile_read",
+           "mnx_substructure_match")
 
 # Encoder operand modes (include/molnextr_hip.h MNX_DTYPE_*). "fp16x3" — split fp16 operands, three MFMA terms per
 # product, fp32-class results — is the default: it is the fastest mode whose results stay a factor of four inside north_star's
@@ -185,6 +186,15 @@ FP_DTYPE = np.dtype([("flags", "<u4"), ("n_bits", "<u4"), ("max_paths", "<u4"), 
 FP_TOO_LARGE, FP_BEYOND_TABLES, FP_PSEUDO_ATOM, FP_TRUNCATED, FP_BAD_BOND, FP_LIMIT = 1, 2, 4, 8, 16, 1 << 16
 FP_REFUSED = FP_TOO_LARGE | FP_BEYOND_TABLES | FP_BAD_BOND      # no fingerprint: every word 0 (as with FP_LIMIT)
 FP_WORDS, FP_MAX_BONDS, FP_DEFAULT_STEPS, FP_MAX_STEPS = 64, 7, 4096, 1 << 20
+# mnx_match, one pair of mnx_substructure_match (16 bytes; its map of MATCH_MAX_QUERY target atoms stands in a table of its own), and
+# its flags (MNX_MATCH_*): bits 0-4 the target's admission with the FP_* values, bits 8-12 the query's (<< MATCH_QUERY_SHIFT); the
+# query has more than MATCH_MAX_QUERY atoms or MATCH_MAX_QUERY_BONDS bonds, or none; a root's search passed max_steps and fewer than
+# max_matches embeddings were found (the count is a lower bound); a pair names a molecule outside a table. MATCH_DEFAULT_STEPS is what
+# max_steps = 0 stands for, MATCH_MAX_STEPS the most a caller may pass, MATCH_NO_ATOM a map entry beyond the query or without a match
+MATCH_DTYPE = np.dtype([("flags", "<u4"), ("n_matches", "<u4"), ("steps", "<u4"), ("reserved", "<u4")], align=True)
+MATCH_QUERY_TOO_LARGE, MATCH_QUERY_EMPTY, MATCH_LIMIT, MATCH_BAD_PAIR, MATCH_QUERY_SHIFT = 32, 64, 1 << 16, 1 << 17, 8
+MATCH_REFUSED = FP_REFUSED | FP_REFUSED << MATCH_QUERY_SHIFT | MATCH_QUERY_TOO_LARGE | MATCH_QUERY_EMPTY | MATCH_BAD_PAIR   # no search
+MATCH_MAX_QUERY, MATCH_MAX_QUERY_BONDS, MATCH_DEFAULT_STEPS, MATCH_MAX_STEPS, MATCH_NO_ATOM = 64, 128, 65536, 1 << 20, 0xFFFF
 
 
 def vocab_text(tok):
@@ -343,6 +353,9 @@ def load_library():
     lib.mnx_main_pack.argtypes = lib.mnx_expand_pack.argtypes           # expand's arguments exactly
     lib.mnx_fingerprint_pack.restype = C.c_int                          # the writers' input side, recs, bits, max_bonds, max_steps
     lib.mnx_fingerprint_pack.argtypes = lib.mnx_smiles_pack.argtypes[:9] + [vp, vp, C.c_uint32, C.c_uint32, vp]
+    lib.mnx_substructure_match.restype = C.c_int                        # the input side twice, pairs, n_pairs, recs, maps, max_matches, max_steps
+    lib.mnx_substructure_match.argtypes = (lib.mnx_smiles_pack.argtypes[:9] + lib.mnx_smiles_pack.argtypes[1:9] +
+                                           [vp, i32, vp, vp, C.c_uint32, C.c_uint32, vp])
     lib.mnx_tanimoto.restype = C.c_int
     lib.mnx_tanimoto.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     lib.mnx_smiles_read.restype = C.c_int
@@ -1295,6 +1308,38 @@ class Engine:
         self._check(self.lib.mnx_tanimoto(self.h, _ptr(a), _ptr(b), n, _ptr(both), _ptr(either), _ptr(similarity), _stream()), "mnx_tanimoto")
         return {"both": both.cpu().numpy().view(np.uint32), "either": either.cpu().numpy().view(np.uint32),
                 "similarity": similarity.cpu().numpy()}
+
+    def substructure_match(self, query_rec: dict, target_rec: dict, pairs=None, max_matches: int = 1, max_steps: int = 0,
+                           keep_device: bool = False) -> dict:
+        """Two sets of records (graph_pack's, any pass's, a reader's; host arrays or keep_device=True outputs, and they may be the
+        same dict) -> {'match' [n_pairs] MATCH_DTYPE, 'map' uint16 [n_pairs, MATCH_MAX_QUERY]}: per pair (query index, target
+        index) whether the query molecule embeds in the target molecule (mnx_substructure_match; the rule: include/molnextr_hip.h
+        — this library's own, NOT RDKit's HasSubstructMatch and not SMARTS). pairs: int [n_pairs, 2]; None pairs one query with
+        every target, or item with item where the counts are equal. match['n_matches'] counts the embeddings up to max_matches
+        (0: 1), match['steps'] is the longest search of one root, map[p][a] the target atom under query atom a in the first
+        embedding (MATCH_NO_ATOM beyond the query or without a match). max_steps: the candidates one root's search may examine
+        (0: MATCH_DEFAULT_STEPS; MATCH_MAX_STEPS at the most), beyond which the pair gets MATCH_LIMIT unless max_matches
+        embeddings were found. A pair with a bit of MATCH_REFUSED was not searched. Run both sides through kekulize_pack and
+        normalize_pack first, so that an aromatic query finds a Kekule drawing. One launch, nothing to size. keep_device: 'map'
+        stays a device tensor (int16 [n_pairs, MATCH_MAX_QUERY], the same words)."""
+        dev = torch.device("cuda", self.device)
+        nq, nt = len(query_rec["mols"]), len(target_rec["mols"])
+        if pairs is None:
+            if nq != 1 and nq != nt:
+                raise ValueError(f"substructure_match pairs one query with every target or item with item: {nq} queries against {nt} targets")
+            pairs = np.stack([np.zeros(nt, np.int64) if nq == 1 else np.arange(nt), np.arange(nt)], axis=1)
+        pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
+        if len(pairs) and (pairs.min() < 0 or pairs.max() > 0xFFFFFFFF):
+            raise ValueError("substructure_match: a pair index outside 0 .. 2^32 - 1")
+        n = len(pairs)
+        q_tables, q_args = self._packed_tables(query_rec)
+        t_tables, t_args = self._packed_tables(target_rec)
+        d_pairs = torch.from_numpy(pairs.astype(np.uint32).view(np.int32)).to(dev)
+        recs = torch.empty(n * MATCH_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        maps = torch.empty((n, MATCH_MAX_QUERY), dtype=torch.int16, device=dev)
+        self._check(self.lib.mnx_substructure_match(self.h, *q_args, *t_args, _ptr(d_pairs), n, _ptr(recs), _ptr(maps), int(max_matches),
+                                                    int(max_steps), _stream()), "mnx_substructure_match")
+        return {"match": recs.cpu().numpy().view(MATCH_DTYPE), "map": maps if keep_device else maps.cpu().numpy().view(np.uint16)}
 
     def smiles_read(self, strings, caps=None, keep_device: bool = False) -> dict:
         """SMILES strings (str or bytes) -> the molecules as packed tables, read on the device (mnx_smiles_read; the rule:

@@ -312,6 +312,28 @@ def graph_tanimoto_scores(engine, records: np.ndarray, gold: Sequence[str], chun
     return {"graph_tanimoto": math.fsum(similar) / len(gold) if gold else 0.0, "tanimoto_limited": int(limited)}
 
 
+def graph_isomorphic_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: int = 512, max_steps: int = 0) -> Dict[str, float]:
+    """--graph_isomorphic: graph_match_kekulized's question asked of the graphs instead of a string, on the same records and gold
+    column (a function of its own: graph_match_scores' parameter list is closed). BOTH sides pass through mnx_kekulize_pack and
+    mnx_normalize_pack; graph_match_isomorphic is the share of items whose prediction and gold have equal atom and bond counts
+    and embed in each other (model.same_graph's rule on the tables: mnx_substructure_match in both directions). It
+    depends on no canonical ranking, so a correct prediction that the ranks' KNOWN LIMIT gives another string than its gold counts
+    here. isomorphic_skipped counts the items that were not compared — a side of more than 64 atoms, a refused side, a search
+    broken off at max_steps (0: MATCH_DEFAULT_STEPS) without a match —; they count as mismatches. An unreadable gold string is the
+    empty molecule and a mismatch. This is NOT the reference's RDKit `graph` score: atoms and bonds are compared by this library's
+    own rule (H counts and stereo are not compared), and no toolkit has checked it."""
+    from .chain import run_chain
+    from .model import _same_graph_tables
+    gold = _gold_strings(gold, records)
+    same = skipped = 0
+    for sides in _both_sides(engine, records, gold, chunk):
+        pred, want = (run_chain(engine, rec, ("kekulize", "normalize"), keep_last=True)[1] for rec in sides)
+        yes, unknown = _same_graph_tables(engine, pred, want, max_steps)
+        same += sum(yes)
+        skipped += sum(unknown)
+    return {"graph_match_isomorphic": same / len(gold) if gold else 0.0, "isomorphic_skipped": int(skipped)}
+
+
 def build_parser() -> argparse.ArgumentParser:
     from .engine import DTYPES
     ap = argparse.ArgumentParser(description="MolNexTR test-set inference on MI355X (reference main.py --do_test)")
@@ -372,6 +394,12 @@ def build_parser() -> argparse.ArgumentParser:
                          "mnx_normalize_pack first; DESIGN 4.26), and tanimoto_limited, the sides that passed the step limit. A "
                          "refused, unreadable or limited side scores 0. The other scores stay as they are. NOT the reference's RDKit "
                          "`tanimoto` score: the bits are not RDKit's and no toolkit has seen them")
+    ap.add_argument("--graph_isomorphic", action="store_true",
+                    help="opt-in, with --graph_match: add graph_match_isomorphic, the share of predictions that are the same graph as "
+                         "their gold string by a subgraph search in both directions (mnx_substructure_match; both sides through "
+                         "mnx_kekulize_pack and mnx_normalize_pack first; DESIGN 4.30) — it depends on no canonical ranking —, and "
+                         "isomorphic_skipped, the items not compared (over 64 atoms, refused or limited; mismatches). The other scores "
+                         "stay as they are. NOT the reference's RDKit `graph` score: this library's own atom and bond match")
     ap.add_argument("--graph_tanimoto_bonds", type=int, default=0, metavar="N",
                     help="with --graph_tanimoto: the longest path in bonds, 1..7; 0 (default) = 7, the reference's maxPath")
     return ap
@@ -387,7 +415,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if not 1 <= args.batch_size <= MAX_BATCH_SIZE:
         ap.error(f"--batch_size must be 1..{MAX_BATCH_SIZE} (reference batches of 2 x batch_size <= {2 * MAX_BATCH_SIZE} rows)")
-    for flag in ("graph_normalize", "graph_kekulize", "graph_formula", "graph_keep_main", "graph_tanimoto"):
+    for flag in ("graph_normalize", "graph_kekulize", "graph_formula", "graph_keep_main", "graph_tanimoto", "graph_isomorphic"):
         if getattr(args, flag) and not args.graph_match:
             ap.error(f"--{flag} adds a score to --graph_match")
     if args.graph_tanimoto_bonds and not args.graph_tanimoto:
@@ -447,6 +475,8 @@ def main(argv=None):
                                                  **({"keep_main": True} if args.graph_keep_main else {})))
                 if args.graph_tanimoto:
                     scores.update(graph_tanimoto_scores(engine, kept["records"], list(df["SMILES"]), max_bonds=args.graph_tanimoto_bonds))
+                if args.graph_isomorphic:
+                    scores.update(graph_isomorphic_scores(engine, kept["records"], list(df["SMILES"])))
         print(write_predictions(args.save_path, args.test_file, table, scores), json.dumps(scores))
     if world > 1:
         dist.barrier()

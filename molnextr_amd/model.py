@@ -19,7 +19,7 @@ import torch
 
 from . import weights as W
 from .chain import BY_NAME, PASSES, run_chain
-from .engine import (DEFAULT_DTYPE, FP_LIMIT, FP_REFUSED, FP_WORDS, MOL_FORMULA_LEFT, MOL_TRUNCATED, NOTE_H_MASK, SMILES_NO_POSITION,
+from .engine import (DEFAULT_DTYPE, FP_LIMIT, FP_REFUSED, FP_WORDS, MATCH_BAD_PAIR, MATCH_LIMIT, MATCH_REFUSED, MOL_FORMULA_LEFT, MOL_TRUNCATED, NOTE_H_MASK, SMILES_NO_POSITION,
                      SMILES_REFUSED, Engine, MnxError)
 from .preprocess import load_image_rgb, transform_image, transform_image_gray
 from .tokenizer import coords_labels, get_tokenizer
@@ -163,11 +163,12 @@ _STAGE_DICTS = {"origin": _origin_stage, "atom_notes": _notes_stage}
 
 def packed_predictions(engine: Engine, out: dict, tok, on=(), compute_confidence: bool = False, molfile: bool = False,
                        molfile_scale=None, smiles: bool = False, stereo: bool = False, double_bonds: bool = False,
-                       canonical: bool = False, symmetry: bool = False, fingerprint: bool = False) -> List[dict]:
+                       canonical: bool = False, symmetry: bool = False, fingerprint: bool = False, substructure=None) -> List[dict]:
     """predict_pipeline(packed=True) behind Engine.predict: `out`, its result dict, through mnx_graph_pack, the passes named in
     `on` (chain.run_chain: their order, and which stage keeps its tables on the device), the canonical ranking, the two
-    writers and the fingerprint, to the per-image dicts that predict_pipeline describes. tok: the 'chartok_coords' tokenizer."""
-    writer = molfile or smiles or fingerprint                            # the sinks: they read the last record on the device
+    writers, the fingerprint and the substructure search (substructure: a list of query SMILES, or None), to the per-image dicts
+    that predict_pipeline describes. tok: the 'chartok_coords' tokenizer."""
+    writer = molfile or smiles or fingerprint or substructure is not None    # the sinks: they read the last record on the device
     drawn = engine.graph_pack(out, keep_device=writer or bool(on))       # what the predicted atoms and bonds are read from
     if (drawn["mols"]["flags"] & MOL_TRUNCATED).any():
         raise RuntimeError(f"a molecule has more atoms than the engine capacity max_atoms={engine.max_atoms}")
@@ -221,7 +222,43 @@ def packed_predictions(engine: Engine, out: dict, tok, on=(), compute_confidence
         fp = engine.fingerprint_pack(rec)
         for p, r, words in zip(preds, fp["fp"], fp["bits"]):
             p["fingerprint"] = None if int(r["flags"]) & (FP_REFUSED | FP_LIMIT) else words.tobytes()
+    if substructure is not None:
+        for p, found in zip(preds, _substructures_of(engine, rec, list(substructure), on, tok.maxx)):
+            p["substructure"] = found
     return preds
+
+
+def _matched(flags: int, n_matches: int):
+    """True: the query embeds; False: it does not; None: the pair was refused, or a search was broken off before one was found"""
+    if flags & MATCH_REFUSED:
+        return None
+    return True if n_matches else None if flags & MATCH_LIMIT else False
+
+
+def _substructures_of(engine: Engine, rec: dict, queries, on, coord_bins: int) -> List[list]:
+    """Per molecule of rec (a record of the chain, its tables on the device) one item per query SMILES: {'matched' (_matched),
+    'atoms': the molecule's atoms under the query's atoms in the query's atom order, None without a match, 'coords': their page
+    coordinates, bin / (coord_bins - 1) as unpack_graphs computes them}. The queries are read on the device and pass through the
+    passes of `on`, as the molecules did: one spelling on both sides. One launch for all pairs."""
+    n, nq = len(rec["mols"]), len(queries)
+    if not nq or not n:
+        return [[] for _ in range(n)]
+    q_rec = run_chain(engine, engine.smiles_read(queries, keep_device=True), on, keep_last=True)[1]
+    pairs = np.stack([np.tile(np.arange(nq), n), np.repeat(np.arange(n), nq)], axis=1)
+    res = engine.substructure_match(q_rec, rec, pairs)
+    den = coord_bins - 1
+    a_x, a_y = rec["atoms"]["x_bin"].tolist(), rec["atoms"]["y_bin"].tolist()
+    out = []
+    for t, a0 in enumerate(rec["mols"]["atom0"].tolist()):
+        items = []
+        for k in range(nq):
+            r, images = res["match"][t * nq + k], res["map"][t * nq + k]
+            matched = _matched(int(r["flags"]), int(r["n_matches"]))
+            atoms = images[:int(q_rec["mols"]["n_atoms"][k])].tolist() if matched else None
+            items.append({"matched": matched, "atoms": atoms,
+                          "coords": [[a_x[a0 + a] / den, a_y[a0 + a] / den] for a in atoms] if matched else None})
+        out.append(items)
+    return out
 
 
 def predict_pipeline(engine: Engine, images: torch.Tensor, tokenizer=None, ref_batch_size: int = 16,
@@ -325,11 +362,26 @@ def predict_fingerprints(engine: Engine, images: torch.Tensor, tokenizer=None, *
     return _pipeline(engine, images, tokenizer, fingerprint=True, **options)
 
 
+def predict_substructures(engine: Engine, images: torch.Tensor, queries, tokenizer=None, **options) -> List[dict]:
+    """predict_pipeline(engine, images, tokenizer, packed=True, **options) with one more sink behind the last pass, beside the
+    writers and the fingerprint: every dict gains 'substructure', per query SMILES of `queries` {'matched': True, False, or None
+    when the pair was refused or its search broken off without a match; 'atoms': the predicted atoms (of the molecule behind the
+    passes) under the query's atoms, in the query's atom order; 'coords': their page coordinates} — does this prediction hold that
+    scaffold, and where on the page (mnx_substructure_match; the rule: include/molnextr_hip.h — this library's own, NOT RDKit's
+    HasSubstructMatch and not SMARTS). The queries are read on the device and pass through the same passes as the predictions;
+    kekulize=True and normalize=True make an aromatic query find a Kekule drawing. options: predict_pipeline's keywords, and
+    fingerprint=True for predict_fingerprints' key. A function of its own because predict_pipeline's parameter list is closed."""
+    if not options.setdefault("packed", True):
+        raise ValueError("predict_substructures needs packed=True: the search runs in the packed tables")
+    return _pipeline(engine, images, tokenizer, substructure=list(queries), **options)
+
+
 def _pipeline(engine, images, tokenizer=None, ref_batch_size=16, max_len=None, beam_size=1, compute_confidence=False, labels=None,
               free_run=False, packed=False, molfile=False, molfile_scale=None, smiles=False, stereo=False, double_bonds=False,
               canonical=False, expand=False, symmetry=False, normalize=False, kekulize=False, formula=False, keep_main=False,
-              fingerprint=False) -> List[dict]:
-    """The body of predict_pipeline (its arguments, its defaults) and of predict_fingerprints (fingerprint=True)."""
+              fingerprint=False, substructure=None) -> List[dict]:
+    """The body of predict_pipeline (its arguments, its defaults), of predict_fingerprints (fingerprint=True) and of
+    predict_substructures (substructure: the query SMILES)."""
     tok =(tokenizer or get_tokenizer())["chartok_coords"]
     why = {**{p.name: p.packed_why for p in PASSES}, "molfile": "the molfiles are written from the packed tables",
            "smiles": "the graph SMILES are written from the packed tables"}
@@ -362,7 +414,7 @@ def _pipeline(engine, images, tokenizer=None, ref_batch_size=16, max_len=None, b
         on = [name for name, given in (("formula", formula), ("expand", expand), ("keep_main", keep_main), ("kekulize", kekulize),
                                        ("normalize", normalize)) if given]
         return packed_predictions(engine, out, tok, on, compute_confidence, molfile, molfile_scale, smiles, stereo, double_bonds,
-                                  canonical, symmetry, fingerprint)
+                                  canonical, symmetry, fingerprint, substructure)
     scores = out["scores"].cpu().numpy() if beam_size > 1 else None
     lens = out["lengths"].cpu().numpy()
     toks = out["tokens"].cpu().numpy()
@@ -539,6 +591,68 @@ def tanimoto(engine: Engine, smiles_a, smiles_b, **passes) -> List[float]:
     return engine.tanimoto(a, b)["similarity"].tolist()
 
 
+def _chained(engine: Engine, smiles_list, passes: dict, who: str):
+    """a caller's strings read on the device and sent through the passes named: (the reader's record, the last record)"""
+    unknown = set(passes) - set(BY_NAME)
+    if unknown:
+        raise TypeError(f"{who}: no pass named {sorted(unknown)}")
+    read = engine.smiles_read(list(smiles_list), keep_device=True)
+    return read, run_chain(engine, read, [name for name, given in passes.items() if given], keep_last=True)[1]
+
+
+def smiles_substructure(engine: Engine, queries, targets, pairs=None, max_matches: int = 1, **passes) -> List[dict]:
+    """Substructure search on a caller's own SMILES: both lists through mnx_smiles_read and the passes named (canonical_smiles' pass
+    options, in the chain's order; kekulize=True, normalize=True make aromatic and Kekule spellings agree), then
+    mnx_substructure_match. pairs: [(query index, target index)]; None pairs one query with every target, or item with item where
+    the lists are equally long (anything else: ValueError). Per pair {'matched': True, False, or None where a string was not read,
+    the pair was refused or a search was broken off without a match; 'n_matches': the embeddings counted, max_matches at the most;
+    'atoms': the target's atoms under the query's atoms in the query's atom order, None without a match; 'flags' (engine.MATCH_*)}.
+    This library's own rule (include/molnextr_hip.h): NOT RDKit's HasSubstructMatch, not SMARTS — H counts and stereo are not
+    compared."""
+    from .engine import READ_REFUSED
+    queries, targets = list(queries), list(targets)
+    if not queries or not targets:
+        return []
+    (q_read, q_rec), (t_read, t_rec) = (_chained(engine, side, passes, "smiles_substructure") for side in (queries, targets))
+    res = engine.substructure_match(q_rec, t_rec, pairs, max_matches=max_matches)
+    if pairs is None:
+        pairs = [(0 if len(queries) == 1 else k, k) for k in range(len(targets))]
+    out = []
+    for (qi, ti), r, images in zip(pairs, res["match"], res["map"]):
+        flags, n = int(r["flags"]), int(r["n_matches"])
+        unread = flags & MATCH_BAD_PAIR == 0 and (int(q_read["read"]["flags"][qi]) | int(t_read["read"]["flags"][ti])) & READ_REFUSED
+        matched = None if unread else _matched(flags, n)
+        out.append({"matched": matched, "n_matches": n, "atoms": images[:int(q_rec["mols"]["n_atoms"][qi])].tolist() if matched else None,
+                    "flags": flags})
+    return out
+
+
+def _same_graph_tables(engine: Engine, a_rec: dict, b_rec: dict, max_steps: int = 0):
+    """Two records of equally many molecules, item by item: (same, skipped) — same[i]: the atom and bond counts are equal, a
+    embeds in b and b embeds in a (mnx_substructure_match both ways: the rule is asymmetric at wildcards, at isotope 0 and at bonds
+    of class ANY); skipped[i]: a direction was refused (a side of more than MATCH_MAX_QUERY atoms among them) or broken off without
+    a match, so same[i] is False without the graphs having been compared"""
+    ab, ba = (engine.substructure_match(x, y, max_steps=max_steps)["match"] for x, y in ((a_rec, b_rec), (b_rec, a_rec)))
+    equal = (a_rec["mols"]["n_atoms"] == b_rec["mols"]["n_atoms"]) & (a_rec["mols"]["n_bonds"] == b_rec["mols"]["n_bonds"])
+    found = (ab["n_matches"] > 0) & (ba["n_matches"] > 0)
+    unknown = [_matched(int(x["flags"]), int(x["n_matches"])) is None or _matched(int(y["flags"]), int(y["n_matches"])) is None for x, y in zip(ab, ba)]
+    return (equal & found).tolist(), (equal & ~found & np.array(unknown, bool)).tolist()
+
+
+def same_graph(engine: Engine, smiles_a, smiles_b, **passes) -> List[bool]:
+    """Are these the same graph, item by item — asked of the graphs, not of a string: both lists through mnx_smiles_read and the
+    passes named (smiles_substructure's options), then item i is True when the atom and bond counts are equal, a embeds in b and b
+    embeds in a (mnx_substructure_match in both directions). It depends on no canonical ranking, so the drawings that the ranks'
+    known limit gives two canonical strings are one graph here. By this library's own atom and bond match: H counts and stereo are
+    not compared, a molecule of more than 64 atoms is never the same as anything."""
+    smiles_a, smiles_b = list(smiles_a), list(smiles_b)
+    if len(smiles_a) != len(smiles_b):
+        raise ValueError(f"same_graph compares item with item: {len(smiles_a)} strings against {len(smiles_b)}")
+    if not smiles_a:
+        return []
+    return _same_graph_tables(engine, _chained(engine, smiles_a, passes, "same_graph")[1], _chained(engine, smiles_b, passes, "same_graph")[1])[0]
+
+
 def page_scale(image) -> tuple:
     """(Sx, Sy) of mnx_molfile_pack for one input page [height, width, ...]: Sx = round(100000 * width / height), the reference's
     `ratio` times its factor 10 (chemical.py:935-937) in units of 1e-4, inside the call's range; Sy = 100000."""
@@ -621,7 +735,12 @@ class molnextr:
     opt-in, default False; the results are put together on the device as with packed_results) = every output dict gains
     'fingerprint', 256 bytes: the 2048 bits of the paths of up to 7 bonds of the molecule behind the graph_* passes
     (mnx_fingerprint_pack through predict_fingerprints: this library's own rule, NOT RDKit's bits), None for a molecule that is
-    refused or passes the step limit. molnextr.tanimoto compares SMILES strings by the same fingerprint."""
+    refused or passes the step limit. molnextr.tanimoto compares SMILES strings by the same fingerprint.
+    graph_substructure: an attribute like graph_fingerprint (`m.graph_substructure = ["c1ccccc1", "C(=O)O"]`; default None) = a
+    list of query SMILES; every output dict gains 'substructure', per query {'matched', 'atoms', 'coords'}: whether the molecule
+    behind the graph_* passes holds the query, under which of its atoms and where on the page (mnx_substructure_match through
+    predict_substructures: this library's own rule, NOT RDKit's HasSubstructMatch and not SMARTS). molnextr.has_substructure asks
+    the same of SMILES strings."""
 
     image_format = "fp32"
     packed_results = False
@@ -637,6 +756,7 @@ class molnextr:
     graph_formula = False
     graph_keep_main = False
     graph_fingerprint = False
+    graph_substructure = None
 
     def __init__(self, model_path, device=None, max_batch: int = 32, dtype: str = DEFAULT_DTYPE,
                  device_preprocess: bool = True, image_format: str = "fp32", packed_results: bool = False,
@@ -707,6 +827,11 @@ class molnextr:
         """The similarity of two lists of SMILES, item by item, by this library's path fingerprint (model.tanimoto; passes:
         smiles_fingerprints' options). NOT RDKit's fingerprint."""
         return tanimoto(self.engine, smiles_a, smiles_b, **passes)
+
+    def has_substructure(self, smiles_list, query, **passes) -> List:
+        """Per string of smiles_list whether it holds the query SMILES: True, False, or None where a string was not read or the
+        search gave no answer (model.smiles_substructure; passes: its options). NOT RDKit's HasSubstructMatch."""
+        return [item["matched"] for item in smiles_substructure(self.engine, [query], smiles_list, **passes)]
 
     _groups_done = 0          # groups of the running predict_images call that have produced predictions
 
@@ -877,7 +1002,7 @@ class molnextr:
         group = (self.group_images // batch_size) * batch_size
         groups = [input_images[i:i + group] for i in range(0, len(input_images), group)]
         conf = {"compute_confidence": True} if return_confidence else {}
-        if self.packed_results or self.graph_molfile or self.graph_smiles or self.graph_fingerprint:
+        if self.packed_results or self.graph_molfile or self.graph_smiles or self.graph_fingerprint or self.graph_substructure is not None:
             conf["packed"] = True
         if self.graph_smiles:
             conf["smiles"] = True
@@ -898,9 +1023,13 @@ class molnextr:
                 if labels is not None:
                     rows = slice(len(preds), len(preds) + x.shape[0])
                     conf.update(labels=labels[rows], free_run=cut[rows])
-                preds += self._with_fallback(
-                    lambda eng: (predict_fingerprints if self.graph_fingerprint else predict_pipeline)(
-                        eng, x, self.tokenizer, ref_batch_size=batch_size, **conf))
+                if self.graph_substructure is not None:       # predict_fingerprints' key travels as an option of this route
+                    job = lambda eng: predict_substructures(eng, x, list(self.graph_substructure), self.tokenizer, ref_batch_size=batch_size,  # noqa: E731
+                                                            **({"fingerprint": True} if self.graph_fingerprint else {}), **conf)
+                else:
+                    job = lambda eng: (predict_fingerprints if self.graph_fingerprint else predict_pipeline)(  # noqa: E731
+                        eng, x, self.tokenizer, ref_batch_size=batch_size, **conf)
+                preds += self._with_fallback(job)
                 self._groups_done += 1
         finally:
             if hasattr(gen, "close"):
@@ -946,6 +1075,8 @@ class molnextr:
                 d["main_atoms"] = pred["main"]["origin"]
             if "fingerprint" in pred:                         # graph_fingerprint: 256 bytes, None when refused or limited
                 d["fingerprint"] = pred["fingerprint"]
+            if "substructure" in pred:                        # graph_substructure: per query matched / atoms / coords
+                d["substructure"] = pred["substructure"]
             if return_atoms_bonds:
                 c = pred["chartok_coords"]
                 atoms = []

@@ -73,6 +73,14 @@ def tanimoto(smiles_a, smiles_b, **passes):
     return MolNexTRSingleton.get_instance().tanimoto(smiles_a, smiles_b, **passes)
 
 
+def has_substructure(smiles_list, query, **passes):
+    """Per string of smiles_list whether it holds the query SMILES as a substructure: True, False, or None where a string was not
+    read or the search gave no answer (no reference counterpart; model.smiles_substructure). passes: canonical_smiles' pass options;
+    kekulize=True and normalize=True make aromatic and Kekule spellings agree. This library's own rule, NOT RDKit's
+    HasSubstructMatch and not SMARTS: H counts and stereo are not compared."""
+    return MolNexTRSingleton.get_instance().has_substructure(smiles_list, query, **passes)
+
+
 def get_predictions(imagepath: str, atoms_bonds: bool = False, smiles: bool = True, predicted_molfile: bool = False):
     """Predictions for one chemical-structure image (reference molnextr.py:214-309)."""
     start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
