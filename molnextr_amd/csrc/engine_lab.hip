@@ -93,9 +93,20 @@ int mnx_probe_decode_attn(mnx_engine* h, int32_t rows, int32_t t, int32_t iters,
     return MNX_OK;
 }
 
+// What the GEMM test aids refuse before any launch, in words (the launchers repeat the shape checks, but their refusal is a
+// bare hipErrorInvalidValue, and a null pointer used to return without touching the handle's error text at all).
+static const char* gemm16_refusal(int dtype, const void* A, const void* W, const void* C, int M, int N, int K) {
+    if (!A || !W || !C) return "null A, W or C";
+    if (M <= 0) return "M must be positive";
+    if (K <= 0 || (K & 7) || N <= 0 || (N & 7)) return "K and N must be positive multiples of 8";
+    if (dt_base(dtype) == MNX_DT_F32 && (K & 15)) return "the fp32 kernel needs K to be a multiple of 16";
+    return nullptr;
+}
+
 int mnx_gemm16(mnx_engine* h, int32_t epi, const void* A, const void* W, void* C, const float* bias, int32_t M,
                int32_t N, int32_t K, void* stream) {
-    if (!h || !A || !W || !C) return MNX_ERR_INVALID_ARG;
+    if (!h) return MNX_ERR_INVALID_ARG;
+    if (const char* why = gemm16_refusal(h->dt, A, W, C, M, N, K)) { h->err = std::string("mnx_gemm16: ") + why; return MNX_ERR_INVALID_ARG; }
     HIPCHK(h, hipSetDevice(h->device));
     const int dt = dt_base(h->dt);
     if (!bias && N <= h->zero_bias_n) bias = h->zero_bias;
@@ -114,7 +125,8 @@ int mnx_gemm16(mnx_engine* h, int32_t epi, const void* A, const void* W, void* C
 int mnx_gemm16_split(mnx_engine* h, int32_t epi, const void* A, int64_t a_lo, const void* W, int64_t w_lo, float oscale,
                      void* C, int64_t c_lo, const float* bias, int32_t M, int32_t N, int32_t K, int32_t terms,
                      void* stream) {
-    if (!h || !A || !W || !C) return MNX_ERR_INVALID_ARG;
+    if (!h) return MNX_ERR_INVALID_ARG;
+    if (const char* why = gemm16_refusal(h->dt, A, W, C, M, N, K)) { h->err = std::string("mnx_gemm16_split: ") + why; return MNX_ERR_INVALID_ARG; }
     if (!dt_split(h->dt)) { h->err = "mnx_gemm16_split: the engine's compute_dtype is not a split mode"; return MNX_ERR_INVALID_ARG; }
     if (a_lo < 0 || w_lo < 0 || c_lo < 0) { h->err = "mnx_gemm16_split: negative plane offset"; return MNX_ERR_INVALID_ARG; }
     HIPCHK(h, hipSetDevice(h->device));

@@ -535,11 +535,11 @@ static int x3_main_rows(int dtype, int epi, int M, int N, int K, int terms) {
     return tm_main * 256;
 }
 
-const char* gemm16_route(int dtype, int epi, int M, int N, int K, int terms, bool has_bias) {
+const char* gemm16_route(int dtype, int epi, int M, int N, int K, int terms, bool has_bias, int c_planes) {
     const int r = x3_main_rows(dtype, epi, M, N, K, terms);
     if (r == M) return "x3";
     if (r > 0) return "x3+128";
-    if (has_bias && gemm256_supports(dtype, epi, M, N, K)) return "g256";
+    if (has_bias && !(dt_split(dtype) && c_planes == 1) && gemm256_supports(dtype, epi, M, N, K)) return "g256";   // as launch_gemm16
     if (gemm_res_preferred(dtype, epi, M, N, K)) return "gres";
     return "128";
 }
@@ -562,7 +562,9 @@ hipError_t launch_gemm16(int dtype, int epi, const void* A, const void* W, void*
     // shape-only dispatch (never data-dependent, never environment-dependent): the persistent 256x256 kernel for the
     // 16-bit-output layers whose tile count fills the chip, the persistent 256x128 kernel for the fp32-output layers
     // likewise, the 128x128 kernel for everything else
-    if (bias && gemm256_supports(dtype, epi, M, N, K)) return launch_gemm256(dtype, epi, A, W, C, bias, M, N, K, s, sp);
+    // (gemm256_kernel's one-term split form always stores both output planes: a one-plane output stays on the 128x128 kernel)
+    const bool one_plane = dt_split(dtype) && sp && sp->c_planes == 1;
+    if (bias && !one_plane && gemm256_supports(dtype, epi, M, N, K)) return launch_gemm256(dtype, epi, A, W, C, bias, M, N, K, s, sp);
     if (gemm_res_preferred(dtype, epi, M, N, K)) return launch_gemm_res(dtype, epi, A, W, (float*)C, bias, resid, M, N, K, s, sp);
     return launch_gemm16_tile128(dtype, epi, A, W, C, bias, resid, M, N, K, s, sp);
 }

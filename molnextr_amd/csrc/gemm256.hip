@@ -906,6 +906,9 @@ hipError_t launch_gemm256(int dtype, int epi, const void* A, const void* W, void
     const SplitArgs spv = split ? *sp : SplitArgs();
     if (split && spv.terms >= 2)        // three / two terms: the shared-fill six- / four-phase kernel
         return launch_gemm256x3(dtype, epi, A, W, C, bias, nullptr, M, N, K, s, sp);
+    // one term: gemm256_kernel<SPLIT> stores hi AND lo (its counted waits assume both planes' stores); with c_planes == 1 it
+    // would write the lo plane c_lo = 0 elements behind the hi plane, over it
+    if (split && spv.c_planes != 2) return hipErrorInvalidValue;
     const int tm = M / TM, tn = N / TN;
     const int grid = tm * tn < 256 ? tm * tn : 256;
 #define MNX_G256_CASE(TT, E, SP)                                                                                          \

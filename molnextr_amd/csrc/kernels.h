@@ -41,7 +41,8 @@ hipError_t launch_gemm16(int dtype, int epi, const void* A, const void* W, void*
                          const float* resid, int M, int N, int K, hipStream_t s, const SplitArgs* sp = nullptr);
 // which kernel(s) launch_gemm16 runs a layer on: "x3" (gemm256x3), "x3+128" (whole rounds on gemm256x3, remaining rows on
 // the 128x128 kernel), "g256", "gres", "128" — shape-only; used by tools/gemm_lab to label its table
-const char* gemm16_route(int dtype, int epi, int M, int N, int K, int terms, bool has_bias);
+// (c_planes as SplitArgs::c_planes: a one-plane output of a one-term split layer stays on the 128x128 kernel)
+const char* gemm16_route(int dtype, int epi, int M, int N, int K, int terms, bool has_bias, int c_planes = 2);
 // the 128x128-tile kernel of gemm.hip without the dispatch to gemm256.hip (tools/gemm_lab compares the two)
 hipError_t launch_gemm16_tile128(int dtype, int epi, const void* A, const void* W, void* C, const float* bias,
                                  const float* resid, int M, int N, int K, hipStream_t s, const SplitArgs* sp = nullptr);

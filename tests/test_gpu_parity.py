@@ -58,7 +58,7 @@ def test_gemm_all_epilogues(dev, M, N, K):
     A = torch.randn(M, K, generator=g).to(dev).bfloat16()
     Wt = (torch.randn(N, K, generator=g) / K ** 0.5).to(dev).bfloat16()   # asymmetric, transposition-detecting
     bias = torch.randn(N, generator=g).to(dev)
-    ref = A.float() @ Wt.float().t() + bias
+    ref = A.double() @ Wt.double().t() + bias.double()            # float64: exact products of the 16-bit operands
     out = torch.zeros(M, N, device=dev)
     eng.gemm16(3, A, Wt, out, bias)
     assert (out - ref).abs().max().item() < 2e-4
@@ -218,7 +218,7 @@ def test_gemm_persistent_256_tile_kernel(dev, dtype, M, N, K):
     A = torch.randn(M, K, generator=g).to(dev).to(td)
     Wt = (torch.randn(N, K, generator=g) / K ** 0.5).to(dev).to(td)
     bias = torch.randn(N, generator=g).to(dev)
-    ref = A.float() @ Wt.float().t() + bias
+    ref = A.double() @ Wt.double().t() + bias.double()
     tol = 4e-2 if dtype == "bf16" else 6e-3
     o16 = torch.zeros(M, N, device=dev, dtype=td)
     e.gemm16(0, A, Wt, o16, bias)
