@@ -1,9 +1,12 @@
 """The passes that take packed molecule tables to packed molecule tables, in the one order they run in (the rule:
 include/molnextr_hip.h — formula in front of expand, keep_main behind it, kekulize in front of normalize), and the one function
-that runs them. predict_pipeline, canonical_smiles, the facade and evaluate's --graph_match read the order, the keys and the
-error clauses here; a new pass is one row, one Engine method and one paragraph in their docstrings. What reads the
-last record without writing tables again — the molfile and SMILES writers, the path fingerprint (Engine.fingerprint_pack) — is a
-sink, not a row: it runs behind run_chain's last record, which keep_last keeps on the device for it."""
+that runs them, with the two that turn a caller's options into its `on` list (passes_on: the five keyword flags; named_passes:
+**passes, with the TypeError for a name that is no pass). predict_pipeline (model.py), canonical_smiles and the other
+caller-facing table functions (graphs.py), the facade and evaluate's --graph_match read the order, the keys and the error
+clauses here; a new pass is one row here, one method of engine_tables.TableCalls, its prototype and flags in abi.py and one
+paragraph in the docstrings. What reads the last record without writing tables again — the molfile and
+SMILES writers, the path fingerprint (Engine.fingerprint_pack) — is a sink, not a row: it runs behind run_chain's last record,
+which keep_last keeps on the device for it."""
 import collections
 
 # name: the option's name everywhere (graph_<name> on the facade); method: the Engine method; key: where a prediction dict
@@ -37,3 +40,19 @@ def run_chain(engine, rec, on, keep_last: bool):
     for k, p in enumerate(todo):
         rec = stages[p.name] = getattr(engine, p.method)(rec, keep_device=bool(keep_last) or k + 1 < len(todo))
     return stages, rec
+
+
+def passes_on(formula=False, expand=False, keep_main=False, kekulize=False, normalize=False):
+    """The five keyword flags of predict_pipeline, canonical_smiles and canonical_molfiles -> the names that are on, in the
+    order of PASSES: run_chain's `on`."""
+    given = {"formula": formula, "expand": expand, "keep_main": keep_main, "kekulize": kekulize, "normalize": normalize}
+    return [p.name for p in PASSES if given[p.name]]
+
+
+def named_passes(who: str, passes: dict):
+    """A caller's **passes (smiles_fingerprints, molfile_fingerprints, smiles_substructure, same_graph) -> the names that are
+    on, in the order of PASSES; TypeError in the name of `who` for a key that is no pass."""
+    unknown = set(passes) - set(BY_NAME)
+    if unknown:
+        raise TypeError(f"{who}: no pass named {sorted(unknown)}")
+    return passes_on(**passes)

@@ -80,7 +80,7 @@ class PeerFailed(RuntimeError):
 
 class RangeFallback(RuntimeError):
     """Raised by run_inference on EVERY rank when any rank's encoder left the fp16 range of the operand mode: the caller
-    rebuilds its engine in the fallback mode (engine.RANGE_FALLBACK) and repeats the whole evaluation."""
+    rebuilds its engine in the fallback mode (abi.RANGE_FALLBACK) and repeats the whole evaluation."""
 
 
 MAX_BATCH_SIZE = 256      # --batch_size: per-rank reference batches of 2 x 256 = 512 rows (Engine.MAX_REF_BATCH)
@@ -116,7 +116,7 @@ def run_inference(engine, load_image: Callable[[int], np.ndarray], n_items: int,
     # ANY other failure of one rank (capacity, a missing image file, a HIP error) must not leave its peers in that collective
     # either: the ranks exchange a status code — 0 ok, 1 range error, 2 fatal — and the fatal rank re-raises its own error
     # after the exchange, the others raise PeerFailed.
-    from .engine import MnxError, range_fallback_dtype
+    from .abi import MnxError, range_fallback_dtype
     range_err, fatal = None, None
     try:
         for g0 in range(0, len(mine), step):
@@ -238,7 +238,7 @@ def graph_match_scores(engine, records: np.ndarray, gold: Sequence[str], chunk: 
     are. Only the component rule is the reference's (_keep_main_molecule): the comparison is still this
     project's canonical string and NOT the reference's RDKit `graph` score."""
     from .chain import run_chain
-    from .engine import READ_REFUSED, SMILES_REFUSED
+    from .abi import READ_REFUSED, SMILES_REFUSED
     gold = _gold_strings(gold, records)
     # the scores a flag adds: its name, the passes in front of the writer (chain.run_chain orders them), whether the gold side too
     extra = [row for row, given in ((("graph_match_normalized", ("normalize",), True), normalize),
@@ -300,7 +300,7 @@ def graph_tanimoto_scores(engine, records: np.ndarray, gold: Sequence[str], chun
     that passed the step limit (FP_LIMIT). This is NOT the reference's RDKit `tanimoto` score: the reference only names the
     metric and the path length; the bits are this library's own and no toolkit has seen them."""
     from .chain import run_chain
-    from .engine import FP_LIMIT
+    from .abi import FP_LIMIT
     gold = _gold_strings(gold, records)
     limited, similar = 0, []                                   # per item, summed once at the end: no chunk size changes a bit
     for sides in _both_sides(engine, records, gold, chunk):
@@ -323,7 +323,7 @@ def graph_isomorphic_scores(engine, records: np.ndarray, gold: Sequence[str], ch
     empty molecule and a mismatch. This is NOT the reference's RDKit `graph` score: atoms and bonds are compared by this library's
     own rule (H counts and stereo are not compared), and no toolkit has checked it."""
     from .chain import run_chain
-    from .model import _same_graph_tables
+    from .graphs import _same_graph_tables
     gold = _gold_strings(gold, records)
     same = skipped = 0
     for sides in _both_sides(engine, records, gold, chunk):
@@ -335,7 +335,7 @@ def graph_isomorphic_scores(engine, records: np.ndarray, gold: Sequence[str], ch
 
 
 def build_parser() -> argparse.ArgumentParser:
-    from .engine import DTYPES
+    from .abi import DTYPES
     ap = argparse.ArgumentParser(description="MolNexTR test-set inference on MI355X (reference main.py --do_test)")
     ap.add_argument("--data_path", default=".")
     ap.add_argument("--test_file", required=True, help="CSV with file_path (and SMILES / image_id) columns")
@@ -345,7 +345,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--batch_size", type=int, default=4,
                     help=f"per-GPU batch size, 1..{MAX_BATCH_SIZE} (main.py's default 256); inference uses twice that")
     ap.add_argument("--dtype", default=None, choices=sorted(DTYPES),
-                    help="encoder operand mode; default engine.DEFAULT_DTYPE = fp16x3 (every token / atom / bond as the reference's fp32 path; "
+                    help="encoder operand mode; default abi.DEFAULT_DTYPE = fp16x3 (every token / atom / bond as the reference's fp32 path; "
                          "fp16x3m = qkv / fc1 / fc2 of Swin stage 3 on two product terms: faster, tokens exact on everything measured, raw logits up to "
                          "1.2e-3 off on a hostile checkpoint)")
     ap.add_argument("--fp16", action="store_true",
@@ -409,7 +409,8 @@ def main(argv=None):
     import pandas as pd
     import torch.distributed as dist
     from . import weights as W
-    from .engine import DEFAULT_DTYPE, Engine
+    from .abi import DEFAULT_DTYPE
+    from .engine import Engine
     from .preprocess import load_image_rgb
     ap = build_parser()
     args = ap.parse_args(argv)
@@ -451,7 +452,7 @@ def main(argv=None):
     except RangeFallback as err:
         # the reference evaluates any checkpoint; an activation beyond the fp16 range must not end the run. All ranks arrive
         # here together (run_inference agrees on the flag before its gather): one table, one operand mode.
-        from .engine import RANGE_FALLBACK
+        from .abi import RANGE_FALLBACK
         to = RANGE_FALLBACK.get(dtype)
         if to is None:
             raise

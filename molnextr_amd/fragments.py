@@ -126,7 +126,7 @@ def load(path: str = _PATH) -> dict:
 def pack(table: dict):
     """{name: SMILES} -> (mols MOL_DTYPE [n_frags], atoms ATOM_DTYPE, bonds BOND_DTYPE, text bytes, names [n_frags] of lists):
     one record per DISTINCT fragment SMILES (synonyms share it), in sorted order of the SMILES; names[f] = its names."""
-    from .engine import ATOM_DTYPE, BOND_DTYPE, MOL_DTYPE
+    from .abi import ATOM_DTYPE, BOND_DTYPE, MOL_DTYPE
     by_smiles = {}
     for name, smi in table.items():
         by_smiles.setdefault(smi, []).append(name)
