@@ -1690,6 +1690,34 @@ int mnx_cast16(mnx_engine* h, const float* x, void* y16, int64_t y_lo, int64_t n
 int mnx_sgemm_tn(mnx_engine* h, const float* A, const float* W, const float* bias, float* C, int32_t M, int32_t N,
                  int32_t K, int32_t perm_S, void* stream);
 
+/* Test aid: ONE launch of one linear of the 8-launches-per-layer decode tick (mnx::dec_linear_kernel<pro, epi>,
+ * molnextr_amd/csrc/decoder.hip) on caller device buffers, under a scripted tick state (tests/test_gpu_dec_linear.py).
+ *   out[r, n] = epi( pro(in)[r, :] . W[n, :] + bias[n] )      for the rows r < n_alive of `capacity` launched rows
+ * pro: 0 the input as it is | 1 LayerNorm(gamma, beta, eps 1e-6) of `in` — with part != null of
+ *      (((p0 + p1) + ...) + p[n_part-1]) + in, p_z = part + z * part_stride, and that sum is also written to x_write
+ *      [capacity, 256] | 2 LayerNorm of emb[prev_tok] * 16 + pe[rank] (the engine's tables; `in` is not read), which is
+ *      also written to x_write.
+ * epi: 0 N = 768: columns 0..255 * 32^-1/2 -> out [capacity, 256]; columns 256..511 / 512..767 are quantised into row t of
+ *      the slot's eight key / value blocks of the engine's LAYER-0 self cache (read them with mnx_kv_block) |
+ *      1 out [capacity, N] += result (in place) | 2 result * 32^-1/2 | 3 erf-GELU(result) |
+ *      4 K-slice partial sums: plane z = out + z * part_stride holds the products over k in [256 z, 256 z + 256), the bias
+ *      in plane 0 alone (K / 256 planes).
+ * Only the six pairs the tick uses exist: (2,0), (1,0), (0,1), (1,2), (1,3), (0,4).
+ * in [capacity, K], W [N, K], bias [N], gamma / beta [K]: device fp32, 16-byte aligned. N a multiple of 32, K of 256;
+ * K = 256 unless pro = 0; capacity a multiple of 32, at most dec_slots; 1 <= n_alive <= capacity.
+ * rows: HOST int32 [n_alive][4] = {slot, t, prev_tok, rowc} of every alive sequence, all of one reference batch: slots
+ * distinct in 0..dec_slots-1 (in any order, with gaps), t < max_len, prev_tok < vocab, rowc < 512 (distinct rowc give
+ * distinct PE ranks). The call resets the decoder state, installs these rows, runs the production begin kernel over all
+ * dec_slots — row r of every buffer is the alive slot with the r-th smallest slot NUMBER, its PE rank the number of alive
+ * rows with a smaller rowc —, launches the linear and resets the state again. Rows n_alive..capacity-1 are idle: the
+ * kernel may read them and stores nothing for them, nor to any cache block.
+ * MNX_ERR_INVALID_ARG (with mnx_last_error, "mnx_dec_linear: ...") for a null or misaligned pointer, another (pro, epi), or
+ * any size or script entry outside what is stated; nothing is launched then. Overwrites the decoder state: not to be
+ * called while a decode call is in flight. Synchronises `stream` before it returns. */
+int mnx_dec_linear(mnx_engine* h, int32_t pro, int32_t epi, const float* in, const float* W, const float* bias,
+                   const float* gamma, const float* beta, const float* part, int32_t n_part, int32_t part_stride, float* out,
+                   float* x_write, int32_t N, int32_t K, int32_t capacity, int32_t n_alive, const int32_t* rows, void* stream);
+
 /* Measurement aid for bench.py: while enabled, mnx_encode brackets every kernel launch of the sampled calls with a
  * pair of HIP events recorded on the stream the kernel is launched on (also inside mnx_predict, i.e. live in a timed
  * region). `enable` = n > 0: every n-th mnx_encode call since the enable is sampled, at most 4 calls (the event pool

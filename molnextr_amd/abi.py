@@ -277,6 +277,7 @@ _STATUS_CALLS = {       # everything that returns an mnx_status
     "mnx_merge_ln16": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _f32, _i32, _vp],
     "mnx_cast16": [_vp, _vp, _vp, _i64, _i64, _f32, _vp],
     "mnx_sgemm_tn": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
+    "mnx_dec_linear": [_vp, _i32, _i32] + [_vp] * 6 + [_i32, _i32, _vp, _vp] + [_i32] * 4 + [_vp, _vp],
     "mnx_profile_enable": [_vp, _i32],
     "mnx_profile_read": [_vp, _i32, _f64p, _f64p, C.POINTER(_i64)],
     "mnx_probe_decode_attn": [_vp, _i32, _i32, _i32, _f64p, _f64p, _vp],

@@ -172,6 +172,19 @@ hipError_t beam_enqueue_script_step(const DecBuffers& b, const BeamBuffers& bm, 
                                     int* n_active_out, hipStream_t s);
 hipError_t dec_probe_attn(const DecWeights& w, const DecBuffers& b, int rows, int t, int iters, hipEvent_t* ev,
                           hipStream_t s);
+// mnx_dec_linear (test aid): one launch of dec_linear_kernel<pro, epi> at `capacity` rows on caller buffers, between a reset, the
+// scripted state of n_alive rows {slot, t, prev_tok, rowc} (device int4, chunk 0), the production begin kernel over b.slots and a
+// last reset. emb / pe and (EPI 0) the layer-0 self cache are the engine's. Everything is validated by the caller (engine_lab.hip).
+struct DecLinearCall {
+    int pro, epi;
+    const float *in, *W, *bias, *gamma, *beta, *part;
+    int n_part, part_stride;
+    float *out, *x_write;
+    int N, K, capacity, n_alive;
+    const int4* rows;
+};
+bool dec_linear_instantiated(int pro, int epi);
+hipError_t dec_lab_linear(const DecWeights& w, const DecBuffers& b, const DecLinearCall& c, hipStream_t s);
 hipError_t dec_enqueue_admit_rows(const DecBuffers& b, const int* chunk_ids_dev, int n, int max_len, int stop_on_eos,
                                   hipStream_t s, const GuideRows* g = nullptr);
 hipError_t gather_enqueue(const DecBuffers& b, const int* slots_dev, int n_rows, int out_len, int* o_tokens, int* o_len,

@@ -1042,6 +1042,45 @@ hipError_t dec_probe_attn(const DecWeights& w, const DecBuffers& b, int rows, in
     return e != hipSuccess ? e : hipGetLastError();
 }
 
+// ---- test aid (mnx_dec_linear): ONE launch of one instantiated dec_linear_kernel<PRO, EPI> on caller buffers under a scripted
+// tick state. rows[i] = {slot, t, prev_tok, rowc} of alive row i, all of chunk 0 (distinct slots, validated on the host); the
+// production begin kernel then builds the row view, the PE ranks and n_active from them.
+__global__ void dec_script_state_kernel(DecState* st, const int4* __restrict__ rows, int n, int max_len) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        const int4 r = rows[i];
+        const int s = r.x;
+        st->alive[s] = 1; st->t[s] = r.y; st->prev_tok[s] = r.z; st->len[s] = r.y; st->chunk[s] = 0;
+        st->rowc[s] = r.w; st->rank[s] = 0; st->mem_blk[s] = 0; st->max_len[s] = max_len; st->stop_on_eos[s] = 0;
+    }
+}
+
+bool dec_linear_instantiated(int pro, int epi) {
+    const int key = pro * 10 + epi;
+    return pro >= 0 && pro <= 2 && epi >= 0 && epi <= 4 && (key == 20 || key == 10 || key == 1 || key == 12 || key == 13 || key == 4);
+}
+
+hipError_t dec_lab_linear(const DecWeights& w, const DecBuffers& b, const DecLinearCall& c, hipStream_t s) {
+    if (!dec_linear_instantiated(c.pro, c.epi)) return hipErrorInvalidValue;    // nothing enqueued
+    LinArgs a = {};
+    a.in = c.in; a.W = c.W; a.bias = c.bias; a.gamma = c.gamma; a.beta = c.beta; a.out = c.out; a.x_write = c.x_write;
+    a.part = c.part; a.n_part = c.n_part; a.part_stride = c.part_stride; a.N = c.N; a.K = c.K;
+    a.emb = w.emb; a.pe = w.pe; a.st = b.st; a.T = b.T; a.heads = w.heads;
+    a.kcache = b.self_k; a.vcache = b.self_v; a.Tq = b.Tq;        // EPI 0: the engine's layer-0 self cache
+    hipLaunchKernelGGL(dec_reset_kernel, dim3(1), dim3(BEGIN_THREADS), 0, s, b.st);
+    hipLaunchKernelGGL(dec_script_state_kernel, dim3((c.n_alive + 255) / 256), dim3(256), 0, s, b.st, c.rows, c.n_alive, b.T);
+    hipLaunchKernelGGL(dec_begin_kernel, dim3(1), dim3(BEGIN_THREADS), 0, s, b.st, b.slots);
+    const int key = c.pro * 10 + c.epi;
+    if (key == 20) lin<2, 0>(s, a, c.capacity);
+    else if (key == 10) lin<1, 0>(s, a, c.capacity);
+    else if (key == 1) lin<0, 1>(s, a, c.capacity);
+    else if (key == 12) lin<1, 2>(s, a, c.capacity);
+    else if (key == 13) lin<1, 3>(s, a, c.capacity);
+    else lin<0, 4>(s, a, c.capacity);
+    hipLaunchKernelGGL(dec_reset_kernel, dim3(1), dim3(BEGIN_THREADS), 0, s, b.st);
+    return hipGetLastError();
+}
+
 }  // namespace mnx
 
 namespace mnx {

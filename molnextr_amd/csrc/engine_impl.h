@@ -76,6 +76,7 @@ struct mnx_engine {
     int* forced_ids = nullptr;  // [32, max_len] teacher-forcing ids of mnx_decode_forced (lazy; test aid)
     int* script_nact = nullptr; // [max_len] n_active of every step of mnx_beam_scripted (lazy; test aid)
     int* beam_script = nullptr; // [2][max_len][32 x 8] parents, then ids, of mnx_decode_beam_forced (lazy; test aid)
+    int* lin_script = nullptr;  // [MAX_SLOTS][4] scripted rows {slot, t, prev_tok, rowc} of mnx_dec_linear (lazy; test aid)
     int* guide_labels = nullptr;   // [dec_slots, max_len + 2] label row of every slot, {ids held, the ids}: label-guided decoding
                                    // (mnx_decode_guided / mnx_predict_guided; lazy, written at admission — dec_types.h GuideRows)
     mnx::BeamBuffers beam{};        // allocated lazily on the first mnx_decode_beam

@@ -409,4 +409,59 @@ int mnx_sgemm_tn(mnx_engine* h, const float* A, const float* W, const float* bia
     return MNX_OK;
 }
 
+// ---- test aid: one linear of the 8-launches-per-layer decode tick on caller buffers (tests/test_gpu_dec_linear.py) ----
+int mnx_dec_linear(mnx_engine* h, int32_t pro, int32_t epi, const float* in, const float* W, const float* bias,
+                   const float* gamma, const float* beta, const float* part, int32_t n_part, int32_t part_stride, float* out,
+                   float* x_write, int32_t N, int32_t K, int32_t capacity, int32_t n_alive, const int32_t* rows, void* stream) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    auto bad = [&](const std::string& m) { h->err = "mnx_dec_linear: " + m; return MNX_ERR_INVALID_ARG; };
+    const mnx_config& c = h->cfg;
+    const DecBuffers& db = h->db;
+    if (!dec_linear_instantiated(pro, epi))
+        return bad("(pro, epi) must be one of the instantiated pairs (2,0), (1,0), (0,1), (1,2), (1,3), (0,4)");
+    const bool reads_part = pro == 1 && part;
+    if (!W || !bias || !out || !rows || (pro != 2 && !in) || (pro != 0 && (!gamma || !beta)) || ((pro == 2 || reads_part) && !x_write))
+        return bad("null pointer (W, bias, out, rows; in unless pro = 2; gamma, beta unless pro = 0; x_write with pro = 2 or part)");
+    if (part && pro != 1) return bad("part is read by pro = 1 alone and must be null otherwise");
+    if (misaligned16({in, W, bias, gamma, beta, part, out, x_write}))
+        return bad("in, W, bias, gamma, beta, part, out and x_write must be 16-byte aligned");
+    if (capacity < ROW_TILE || capacity % ROW_TILE || capacity > db.slots)
+        return bad("capacity must be a multiple of 32 in 32..dec_slots");
+    if (n_alive < 1 || n_alive > capacity || n_alive > c.pe_len) return bad("n_alive must be 1..capacity (and at most pe_len)");
+    if (N < 32 || N % 32 || N > 65536) return bad("N must be a multiple of 32 in 32..65536");
+    if (K < 256 || K % 256 || K > 16384) return bad("K must be a multiple of 256 in 256..16384");
+    if (pro != 0 && K != 256) return bad("K must be 256 with pro = 1 or 2 (the LayerNorm row)");
+    if (epi == 0 && N != 768) return bad("N must be 768 with epi = 0 (query | keys | values)");
+    if (epi == 0 && (c.dec_dim != 256 || c.dec_heads != 8)) return bad("epi = 0 needs an engine of dec_dim 256 and 8 heads");
+    if (reads_part && (n_part < 1 || n_part > 16)) return bad("n_part must be 1..16 with part");
+    if ((reads_part || epi == 4) && (part_stride % 4 || (int64_t)part_stride < (int64_t)capacity * (epi == 4 ? N : 256)))
+        return bad("part_stride must be a multiple of 4 and at least capacity * 256 (epi = 4: capacity * N) floats");
+    if (epi == 4 && (int64_t)part_stride * (K / 256) > INT32_MAX) return bad("part_stride * K / 256 must fit in int32");
+    std::vector<int> script((size_t)n_alive * 4);
+    std::vector<char> seen((size_t)db.slots, 0);
+    for (int i = 0; i < n_alive; ++i) {
+        const int slot = rows[4 * i], t = rows[4 * i + 1], tok = rows[4 * i + 2], rowc = rows[4 * i + 3];
+        const std::string at = "rows[" + std::to_string(i) + "]: ";
+        if (slot < 0 || slot >= db.slots) return bad(at + "slot " + std::to_string(slot) + " is outside 0..dec_slots-1");
+        if (seen[slot]) return bad(at + "slot " + std::to_string(slot) + " is repeated");
+        seen[slot] = 1;
+        if (t < 0 || t >= c.max_len) return bad(at + "t " + std::to_string(t) + " is outside 0..max_len-1");
+        if (tok < 0 || tok >= c.vocab) return bad(at + "prev_tok " + std::to_string(tok) + " is outside 0..vocab-1");
+        if (rowc < 0 || rowc >= MAX_REF_BATCH) return bad(at + "rowc " + std::to_string(rowc) + " is outside 0..511");
+        for (int j = 0; j < 4; ++j) script[4 * i + j] = rows[4 * i + j];
+    }
+    hipStream_t s;
+    MNXCHK(caller_stream(h, stream, &s));
+    MNXCHK(lazy_alloc(h, &h->lin_script, (size_t)MAX_SLOTS * 4 * sizeof(int)));
+    HIPCHK(h, hipMemcpyAsync(h->lin_script, script.data(), script.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    DecLinearCall call = {};
+    call.pro = pro; call.epi = epi; call.in = in; call.W = W; call.bias = bias; call.gamma = gamma; call.beta = beta;
+    call.part = reads_part ? part : nullptr; call.n_part = n_part; call.part_stride = part_stride; call.out = out;
+    call.x_write = x_write; call.N = N; call.K = K; call.capacity = capacity; call.n_alive = n_alive;
+    call.rows = (const int4*)h->lin_script;
+    HIPCHK(h, dec_lab_linear(h->dw, h->db, call, s));
+    HIPCHK(h, hipStreamSynchronize(s));      // `script` is pageable host memory of this call
+    return MNX_OK;
+}
+
 }  // extern "C"

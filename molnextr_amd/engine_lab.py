@@ -237,6 +237,18 @@ class LabCalls:
         self._check(self.lib.mnx_sgemm_tn(self.h, _ptr(A), _ptr(Wt), _ptr(bias), _ptr(Cout), M, N, K, perm_S, _stream()),
                     "mnx_sgemm_tn")
 
+    def dec_linear(self, pro: int, epi: int, x: Optional[torch.Tensor], Wt: torch.Tensor, bias: torch.Tensor,
+                   out: torch.Tensor, rows, capacity: int, N: int, K: int, gamma: Optional[torch.Tensor] = None,
+                   beta: Optional[torch.Tensor] = None, part: Optional[torch.Tensor] = None, n_part: int = 0,
+                   part_stride: int = 0, x_write: Optional[torch.Tensor] = None):
+        """mnx_dec_linear: one launch of the decode tick's linear <pro, epi> at `capacity` rows; rows = the alive sequences
+        [(slot, t, prev_tok, rowc), ...] (host). Row r of x / out / x_write / part is the alive slot with the r-th smallest
+        slot number. epi 0 writes the engine's layer-0 self cache (kv_block), epi 4 K / 256 planes part_stride floats apart."""
+        script = torch.as_tensor(rows, dtype=torch.int32).reshape(-1, 4).contiguous()
+        self._check(self.lib.mnx_dec_linear(self.h, pro, epi, _ptr(x), _ptr(Wt), _ptr(bias), _ptr(gamma), _ptr(beta), _ptr(part),
+                                            n_part, part_stride, _ptr(out), _ptr(x_write), N, K, capacity, script.shape[0],
+                                            _ptr(script), _stream()), "mnx_dec_linear")
+
     def gemm16(self, epi: int, A: torch.Tensor, Wt: torch.Tensor, Cout: torch.Tensor, bias: Optional[torch.Tensor]):
         M, K = A.shape
         N = Wt.shape[0]

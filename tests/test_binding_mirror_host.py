@@ -6,6 +6,7 @@ moved name is one object under both paths. Nothing here loads the library.
 
 tests/golden/python_surface.json holds the surface of the commit before the split (7f87ae7), written there by
   git archive 7f87ae7 | tar -x -C $T && (cd $T && python -c "import json, molnextr_amd.engine as e, molnextr_amd.model as m; K = ('_ptr', '_stream', '_pipeline', '_same_graph_tables'); s = lambda o: sorted(n for n in dir(o) if not n.startswith('_') or n in K); print(json.dumps({'engine': s(e), 'model': s(m), 'Engine': sorted(dir(e.Engine))}, indent=1))") > tests/golden/python_surface.json
+A lab call added since is entered by hand where it sorts ('Engine': dec_linear).
 """
 import ctypes
 import itertools
@@ -151,7 +152,7 @@ def test_every_record_struct_matches_its_dtypes(tmp_path):
 def test_the_old_import_paths_reach_the_same_objects():
     with open(os.path.join(ROOT, "tests", "golden", "python_surface.json")) as f:
         surface = json.load(f)
-    assert (len(surface["engine"]), len(surface["model"]), len(surface["Engine"])) == (141, 52, 102)
+    assert (len(surface["engine"]), len(surface["model"]), len(surface["Engine"])) == (141, 52, 103)
     for module, names in ((engine, surface["engine"]), (model, surface["model"]), (engine.Engine, surface["Engine"])):
         missing = [n for n in names if not hasattr(module, n)]
         assert not missing, f"{module.__name__} lost {missing}"
