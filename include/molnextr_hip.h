@@ -1461,6 +1461,51 @@ int mnx_fingerprint_pack(mnx_engine* h, const mnx_mol* mols, int32_t n, const mn
 int mnx_tanimoto(mnx_engine* h, const uint32_t* a, const uint32_t* b, int32_t n, uint32_t* both, uint32_t* either,
                  double* similarity, void* stream);
 
+/* Nearest rows, on the device: for every row of `queries` the k rows of `library` that are nearest to it by the Tanimoto
+ * similarity above — which known compound is nearest —, without the nq * nl pairs of rows ever being written down. Both are tables
+ * of 64-word rows as mnx_fingerprint_pack writes them, and they may be the same pointer. THE FINGERPRINT IS THIS LIBRARY'S OWN, so
+ * the neighbours are not those RDKit's fingerprints would give. There is no count of all rows above a threshold and k is at most
+ * MNX_NEAREST_MAX_K (64).
+ *
+ * Pair quantities, for query q and library row r: both = popcount(Q & R), either = popcount(Q | R), s = (double)both /
+ *   (double)either, and 0.0 when either == 0: exactly mnx_tanimoto's numbers for that pair.
+ * Order. Row x comes before row y for a query if and only if both_x * either_y > both_y * either_x (a pair with either == 0
+ *   counting as 0 / 1), or the two products are equal and index_x < index_y. A total order: the result cannot depend on how the
+ *   work is split, on the grid, or on which wave arrives first. It is the order of the doubles s: two different fractions with
+ *   denominators below 2049 differ by at least 1 / (2048 * 2047), far above one ulp, so each rounds to its own double.
+ * Result per query: the first k rows in that order, 1 <= k <= MNX_NEAREST_MAX_K, of those the ones with s >= min_similarity (the
+ *   cut of the sorted k equals a filter in front, so the double is computed k times per query). count[q] says how many were kept;
+ *   index[q][j], both[q][j], either[q][j] and similarity[q][j] hold them for j < count[q], and MNX_NEAREST_NONE, 0, 0 and 0.0
+ *   behind that. A library of fewer than k rows gives fewer.
+ * flags. MNX_NEAREST_SKIP_SELF: library row q is no candidate for query q — the nearest OTHER row when a set is searched in
+ *   itself. Any other bit is an argument error.
+ * queries: device uint32 [nq][64], 1 <= nq <= MNX_NEAREST_MAX_QUERIES (4096); library: device uint32 [nl][64], 1 <= nl <=
+ * MNX_NEAREST_MAX_ROWS (2^24); 0 <= min_similarity <= 1. Outputs, device pointers the caller allocated: count uint32 [nq]; index,
+ * both, either uint32 [nq][k]; similarity double [nq][k]; written whole. both, either and similarity may each be null, count and
+ * index may not. work: device scratch of at least mnx_tanimoto_search_work_bytes(nq, nl, k) bytes, 8-byte aligned; what it holds
+ * after the call is unspecified. That size is 8 * k * min(nq * min(MNX_NEAREST_MAX_LISTS, slabs), 32768 + nq) bytes with slabs =
+ * ceil(nl / MNX_NEAREST_SLAB_ROWS): never more than nq * k * 8 * MNX_NEAREST_MAX_LISTS, monotone in each argument, and 0 for
+ * arguments the call would refuse.
+ * Geometry (exported because tests take their shapes from it): a workgroup holds MNX_NEAREST_QUERY_TILE queries at once and walks
+ * slabs of MNX_NEAREST_SLAB_ROWS library rows; a query has at most MNX_NEAREST_MAX_LISTS partial lists of k candidates in `work`,
+ * merged by the second launch. Deterministic word for word: no atomic, global or on chip. Two launches, asynchronous on `stream`,
+ * no allocation, no host synchronisation; needs no tables.
+ * MNX_ERR_INVALID_ARG (with mnx_last_error, "mnx_tanimoto_search: ..."): queries, library, count, index or work null; nq outside
+ * 1..4096, nl outside 1..2^24, k outside 1..64; min_similarity NaN or outside [0, 1]; an unknown flag bit; work_bytes too small; a
+ * word pointer that is not 4-byte aligned, similarity or work not 8-byte; nothing is launched then. */
+#define MNX_NEAREST_MAX_K 64u
+#define MNX_NEAREST_MAX_QUERIES 4096u
+#define MNX_NEAREST_MAX_ROWS (1u << 24)
+#define MNX_NEAREST_NONE 0xFFFFFFFFu
+#define MNX_NEAREST_SKIP_SELF 1u
+#define MNX_NEAREST_QUERY_TILE 32u
+#define MNX_NEAREST_SLAB_ROWS 256u
+#define MNX_NEAREST_MAX_LISTS 512u
+size_t mnx_tanimoto_search_work_bytes(int32_t nq, uint32_t nl, uint32_t k);
+int mnx_tanimoto_search(mnx_engine* h, const uint32_t* queries, int32_t nq, const uint32_t* library, uint32_t nl, uint32_t k,
+                        double min_similarity, uint32_t flags, uint32_t* count, uint32_t* index, uint32_t* both,
+                        uint32_t* either, double* similarity, void* work, size_t work_bytes, void* stream);
+
 /* Substructure search, on the device: for pairs of a QUERY molecule Q and a TARGET molecule T, each one molecule of a set of packed
  * tables (the two sets may be the same), whether Q embeds in T, how often, and where: the first embedding as a map from Q's atoms
  * to T's, whose mnx_atom records carry the coordinate bins — a scaffold found is a place on the page. Run in both directions on

@@ -183,6 +183,11 @@ MATCH_DTYPE = np.dtype([("flags", "<u4"), ("n_matches", "<u4"), ("steps", "<u4")
 MATCH_QUERY_TOO_LARGE, MATCH_QUERY_EMPTY, MATCH_LIMIT, MATCH_BAD_PAIR, MATCH_QUERY_SHIFT = 32, 64, 1 << 16, 1 << 17, 8
 MATCH_REFUSED = FP_REFUSED | FP_REFUSED << MATCH_QUERY_SHIFT | MATCH_QUERY_TOO_LARGE | MATCH_QUERY_EMPTY | MATCH_BAD_PAIR   # no search
 MATCH_MAX_QUERY, MATCH_MAX_QUERY_BONDS, MATCH_DEFAULT_STEPS, MATCH_MAX_STEPS, MATCH_NO_ATOM = 64, 128, 65536, 1 << 20, 0xFFFF
+# mnx_tanimoto_search (MNX_NEAREST_*): the most neighbours, queries and library rows of one call; the index behind a query's last
+# hit; the flag that keeps library row q from query q; and the call's geometry — the queries a workgroup holds at once, the library
+# rows of a slab, the partial lists of a query at the most — from which the tests take their shapes
+NEAREST_MAX_K, NEAREST_MAX_QUERIES, NEAREST_MAX_ROWS, NEAREST_NONE, NEAREST_SKIP_SELF = 64, 4096, 1 << 24, 0xFFFFFFFF, 1
+NEAREST_QUERY_TILE, NEAREST_SLAB_ROWS, NEAREST_MAX_LISTS = 32, 256, 512
 
 
 PREP_MAX_PAGES = 4096                   # include/molnextr_hip.h MNX_PREP_MAX_PAGES: pages per mnx_preprocess_batch call
@@ -262,6 +267,8 @@ _STATUS_CALLS = {       # everything that returns an mnx_status
     "mnx_fingerprint_pack": [_vp] + _TABLES_IN + [_vp, _vp, _u32, _u32, _vp],                        # recs, bits, max_bonds, max_steps
     "mnx_substructure_match": [_vp] + _TABLES_IN + _TABLES_IN + [_vp, _i32, _vp, _vp, _u32, _u32, _vp],   # both sides, pairs, n_pairs, recs, maps, max_matches, max_steps
     "mnx_tanimoto": [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
+    # queries, nq, library, nl, k, min_similarity, flags, the five outputs, work, work_bytes
+    "mnx_tanimoto_search": [_vp, _vp, _i32, _vp, _u32, _u32, C.c_double, _u32] + [_vp] * 6 + [C.c_size_t, _vp],
     "mnx_smiles_read": [_vp] + _BYTES_IN + [_vp, _vp] + _ARENAS + [_vp, _vp],                        # mols, recs, the arenas, totals
     "mnx_molfile_read": [_vp] + _BYTES_IN + [_vp, _i32, _vp, _vp] + _ARENAS + [_vp, _vp],            # scale, fit in front of them
     # engine_lab.hip: the test and measurement aids
@@ -285,7 +292,7 @@ _STATUS_CALLS = {       # everything that returns an mnx_status
     "mnx_probe_mfma": [_vp, _i32, _f64p, _f64p, _vp],
 }
 PROTOTYPES = {"mnx_abi_version": (C.c_int, []), "mnx_destroy": (None, [_vp]), "mnx_last_error": (C.c_char_p, [_vp]),
-              "mnx_workspace_bytes": (C.c_size_t, [_vp]), **{name: (C.c_int, args) for name, args in _STATUS_CALLS.items()}}
+              "mnx_workspace_bytes": (C.c_size_t, [_vp]), "mnx_tanimoto_search_work_bytes": (C.c_size_t, [_i32, _u32, _u32]), **{name: (C.c_int, args) for name, args in _STATUS_CALLS.items()}}
 SYMBOLS = tuple(PROTOTYPES)
 
 

@@ -374,4 +374,33 @@ int mnx_tanimoto(mnx_engine* h, const uint32_t* a, const uint32_t* b, int32_t n,
     return MNX_OK;
 }
 
+static bool nearest_shape_ok(int32_t nq, uint32_t nl, uint32_t k) {
+    return nq >= 1 && nq <= (int32_t)MNX_NEAREST_MAX_QUERIES && nl >= 1 && nl <= MNX_NEAREST_MAX_ROWS && k >= 1 && k <= MNX_NEAREST_MAX_K;
+}
+
+size_t mnx_tanimoto_search_work_bytes(int32_t nq, uint32_t nl, uint32_t k) {
+    return nearest_shape_ok(nq, nl, k) ? tanimoto_search_work_bytes(nq, nl, k) : 0;
+}
+
+int mnx_tanimoto_search(mnx_engine* h, const uint32_t* queries, int32_t nq, const uint32_t* library, uint32_t nl, uint32_t k,
+                        double min_similarity, uint32_t flags, uint32_t* count, uint32_t* index, uint32_t* both,
+                        uint32_t* either, double* similarity, void* work, size_t work_bytes, void* stream) {
+    if (!h) return MNX_ERR_INVALID_ARG;
+    auto bad = [&](const char* m) { h->err = std::string("mnx_tanimoto_search: ") + m; return MNX_ERR_INVALID_ARG; };
+    if (!queries || !library || !count || !index || !work) return bad("null pointer");
+    if (nq < 1 || nq > (int32_t)MNX_NEAREST_MAX_QUERIES) return bad("1 <= nq <= 4096 required");
+    if (nl < 1 || nl > MNX_NEAREST_MAX_ROWS) return bad("1 <= nl <= 16777216 required");
+    if (k < 1 || k > MNX_NEAREST_MAX_K) return bad("1 <= k <= 64 required");
+    if (!(min_similarity >= 0.0 && min_similarity <= 1.0)) return bad("0 <= min_similarity <= 1 required");       // a NaN fails both
+    if (flags & ~MNX_NEAREST_SKIP_SELF) return bad("flags may hold MNX_NEAREST_SKIP_SELF only");
+    if (work_bytes < tanimoto_search_work_bytes(nq, nl, k)) return bad("work_bytes is below mnx_tanimoto_search_work_bytes(nq, nl, k)");
+    if ((((uintptr_t)queries | (uintptr_t)library | (uintptr_t)count | (uintptr_t)index | (uintptr_t)both | (uintptr_t)either) & 3) ||
+        (((uintptr_t)similarity | (uintptr_t)work) & 7))
+        return bad("queries, library, count, index, both and either must be 4-byte aligned, similarity and work 8-byte");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, tanimoto_search_enqueue(queries, nq, library, nl, k, min_similarity, flags, count, index, both, either, similarity, work,
+                                      (hipStream_t)stream));
+    return MNX_OK;
+}
+
 }  // extern "C"

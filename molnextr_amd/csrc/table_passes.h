@@ -61,6 +61,12 @@ hipError_t fingerprint_pack_enqueue(const SymbolTables* st_dev, const PackedTabl
 // the Tanimoto similarity of row r of a and row r of b, n rows of 64 words (mnx_tanimoto; each output may be null): one launch on s
 hipError_t tanimoto_enqueue(const unsigned* a, const unsigned* b, int n, unsigned* both, unsigned* either, double* similarity,
                             hipStream_t s);
+// nearest.hip: for every row of `queries` the k nearest rows of `library` by that similarity (mnx_tanimoto_search; both, either and
+// similarity may be null): scan and merge, two launches on s. The arguments checked, `work` of tanimoto_search_work_bytes at least
+size_t tanimoto_search_work_bytes(int nq, unsigned nl, unsigned k);
+hipError_t tanimoto_search_enqueue(const unsigned* queries, int nq, const unsigned* library, unsigned nl, unsigned k,
+                                   double min_similarity, unsigned flags, unsigned* count, unsigned* index, unsigned* both,
+                                   unsigned* either, double* similarity, void* work, hipStream_t s);
 // match.hip: for pair p = (pairs[2p], pairs[2p + 1]) whether, how often and where molecule pairs[2p] of q embeds in molecule
 // pairs[2p + 1] of t — a record in recs, MNX_MATCH_MAX_QUERY target atoms in maps (mnx_substructure_match): one launch on s.
 // max_matches 1 .. 65535 and max_steps 1 .. MNX_MATCH_MAX_STEPS, the defaults resolved

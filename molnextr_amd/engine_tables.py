@@ -1,5 +1,6 @@
 """The packed-table layer of `class Engine` (engine.py), the Python side of csrc/engine_tables.hip: graph_pack, the two writers,
-the five passes from tables to tables, the fingerprint, tanimoto, the substructure search and the two readers. A new pass adds
+the five passes from tables to tables, the fingerprint, tanimoto, the nearest-row search, the substructure search and the two
+readers. A new pass adds
 its method here (one line over _tables_pass), its prototype and flags to abi.py and its row to chain.PASSES."""
 from __future__ import annotations
 
@@ -9,7 +10,7 @@ import numpy as np
 import torch
 
 from .abi import (ATOM_DTYPE, BOND_DTYPE, FP_DTYPE, FP_WORDS, MATCH_DTYPE, MATCH_MAX_QUERY, MOL_DTYPE, MOLFILE_DTYPE, MOLREAD_DTYPE,
-                  READ_DTYPE, SMILES_DTYPE, SMILES_MARK_DOUBLE_BOND, SMILES_MARK_TETRAHEDRAL, MnxError, _ptr, _stream)
+                  NEAREST_MAX_K, NEAREST_MAX_QUERIES, NEAREST_MAX_ROWS, NEAREST_SKIP_SELF, READ_DTYPE, SMILES_DTYPE, SMILES_MARK_DOUBLE_BOND, SMILES_MARK_TETRAHEDRAL, MnxError, _ptr, _stream)
 
 
 class TableCalls:
@@ -291,16 +292,7 @@ class TableCalls:
         against row i of b -> {'both' uint32 [n], 'either' uint32 [n], 'similarity' float64 [n]}: the bits both rows hold, the
         bits either holds, and their quotient — 0.0 where neither holds a bit: an empty side is a mismatch (mnx_tanimoto)."""
         dev = torch.device("cuda", self.device)
-
-        def rows(x):
-            if not isinstance(x, torch.Tensor):
-                x = torch.from_numpy(np.array(x, dtype=np.uint32).view(np.int32))      # a copy: the caller's rows may be read-only
-            x = x.to(dev).contiguous()
-            if x.dim() != 2 or x.shape[1] != FP_WORDS or x.dtype != torch.int32:
-                raise ValueError(f"tanimoto needs [n, {FP_WORDS}] words of 32 bits, not {tuple(x.shape)} {x.dtype}")
-            return x
-
-        a, b = rows(a), rows(b)
+        a, b = self._fp_rows(a, "tanimoto"), self._fp_rows(b, "tanimoto")
         if a.shape != b.shape:
             raise ValueError(f"tanimoto compares row with row: {tuple(a.shape)} against {tuple(b.shape)}")
         n = a.shape[0]
@@ -309,6 +301,52 @@ class TableCalls:
         self._check(self.lib.mnx_tanimoto(self.h, _ptr(a), _ptr(b), n, _ptr(both), _ptr(either), _ptr(similarity), _stream()), "mnx_tanimoto")
         return {"both": both.cpu().numpy().view(np.uint32), "either": either.cpu().numpy().view(np.uint32),
                 "similarity": similarity.cpu().numpy()}
+
+    def _fp_rows(self, x, who: str) -> torch.Tensor:
+        """rows of fingerprints, numpy uint32 or a device int32 tensor [n, FP_WORDS], as a contiguous tensor on the engine's device"""
+        if not isinstance(x, torch.Tensor):
+            x = torch.from_numpy(np.array(x, dtype=np.uint32).view(np.int32))          # a copy: the caller's rows may be read-only
+        x = x.to(torch.device("cuda", self.device)).contiguous()
+        if x.dim() != 2 or x.shape[1] != FP_WORDS or x.dtype != torch.int32:
+            raise ValueError(f"{who} needs [n, {FP_WORDS}] words of 32 bits, not {tuple(x.shape)} {x.dtype}")
+        return x
+
+    def tanimoto_search(self, queries, library, k: int = 1, min_similarity: float = 0.0, skip_self: bool = False,
+                        keep_device: bool = False) -> dict:
+        """Two tables of fingerprints (fingerprint_pack's 'bits': numpy uint32 or device int32 tensors [n, FP_WORDS]) -> for every
+        row of `queries` its k nearest rows of `library` by Tanimoto similarity (mnx_tanimoto_search; the rule and the order:
+        include/molnextr_hip.h): {'count' uint32 [nq], 'index', 'both', 'either' uint32 [nq, k], 'similarity' float64 [nq, k]}.
+        Row q holds count[q] hits — the first k by similarity, among equals the lower index, of those the ones at or above
+        min_similarity —, and NEAREST_NONE, 0, 0 and 0.0 behind them. 1 <= k <= NEAREST_MAX_K; the library has at most
+        NEAREST_MAX_ROWS rows. skip_self: library row q is no candidate for query q (a set searched in itself). More than
+        NEAREST_MAX_QUERIES queries run in chunks of that many; with skip_self that is refused, because a chunk's rows are not
+        the library's rows of the same number. This library's own fingerprint, NOT RDKit's. keep_device: the five stay device
+        tensors (int32 for the words)."""
+        dev = torch.device("cuda", self.device)
+        q, lib = self._fp_rows(queries, "tanimoto_search"), self._fp_rows(library, "tanimoto_search")
+        nq, nl, k = q.shape[0], lib.shape[0], int(k)
+        if nq < 1 or not 1 <= nl <= NEAREST_MAX_ROWS or not 1 <= k <= NEAREST_MAX_K:
+            raise ValueError(f"tanimoto_search needs a query, 1 .. {NEAREST_MAX_ROWS} library rows and 1 <= k <= {NEAREST_MAX_K}: "
+                             f"{nq} queries, {nl} rows, k = {k}")
+        if skip_self and nq > NEAREST_MAX_QUERIES:
+            raise ValueError(f"tanimoto_search: skip_self takes at most {NEAREST_MAX_QUERIES} queries (one call): a chunk of {nq} "
+                             "queries would skip the wrong rows")
+        count = torch.empty(nq, dtype=torch.int32, device=dev)
+        index, both, either = (torch.empty((nq, k), dtype=torch.int32, device=dev) for _ in range(3))
+        similarity = torch.empty((nq, k), dtype=torch.float64, device=dev)
+        step = min(nq, NEAREST_MAX_QUERIES)
+        work_bytes = int(self.lib.mnx_tanimoto_search_work_bytes(step, nl, k))
+        work = torch.empty(work_bytes // 8, dtype=torch.int64, device=dev)
+        for at in range(0, nq, step):
+            rows = slice(at, min(at + step, nq))
+            self._check(self.lib.mnx_tanimoto_search(self.h, _ptr(q[rows]), rows.stop - at, _ptr(lib), nl, k, float(min_similarity),
+                                                     NEAREST_SKIP_SELF if skip_self else 0, _ptr(count[rows]), _ptr(index[rows]),
+                                                     _ptr(both[rows]), _ptr(either[rows]), _ptr(similarity[rows]), _ptr(work), work_bytes,
+                                                     _stream()), "mnx_tanimoto_search")
+        out = {"count": count, "index": index, "both": both, "either": either, "similarity": similarity}
+        if keep_device:
+            return out
+        return {key: t.cpu().numpy() if key == "similarity" else t.cpu().numpy().view(np.uint32) for key, t in out.items()}
 
     def substructure_match(self, query_rec: dict, target_rec: dict, pairs=None, max_matches: int = 1, max_steps: int = 0,
                            keep_device: bool = False) -> dict:

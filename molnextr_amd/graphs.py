@@ -1,6 +1,7 @@
 """The caller-facing functions of the packed-table layer: predictions out of the packed records (unpack_graphs,
 packed_predictions), and a caller's own SMILES and molfiles through the readers, the chain of passes (chain.py) and a writer or
-sink — canonical_smiles, canonical_molfiles, the fingerprints, tanimoto, the substructure search, same_graph. Each takes an
+sink — canonical_smiles, canonical_molfiles, the fingerprints, tanimoto, the nearest-row search (smiles_library, nearest_smiles),
+the substructure search, same_graph. Each takes an
 Engine and calls its table methods (engine_tables.TableCalls); the flags come from abi.py. The model path — decode_batch,
 predict_pipeline and the reference's facade — is model.py, from where every name here is still importable.
 """
@@ -80,12 +81,14 @@ _STAGE_DICTS = {"origin": _origin_stage, "atom_notes": _notes_stage}
 
 def packed_predictions(engine: Engine, out: dict, tok, on=(), compute_confidence: bool = False, molfile: bool = False,
                        molfile_scale=None, smiles: bool = False, stereo: bool = False, double_bonds: bool = False,
-                       canonical: bool = False, symmetry: bool = False, fingerprint: bool = False, substructure=None) -> List[dict]:
+                       canonical: bool = False, symmetry: bool = False, fingerprint: bool = False, substructure=None,
+                       nearest=None) -> List[dict]:
     """predict_pipeline(packed=True) behind Engine.predict: `out`, its result dict, through mnx_graph_pack, the passes named in
     `on` (chain.run_chain: their order, and which stage keeps its tables on the device), the canonical ranking, the two
-    writers, the fingerprint and the substructure search (substructure: a list of query SMILES, or None), to the per-image dicts
-    that predict_pipeline describes. tok: the 'chartok_coords' tokenizer."""
-    writer = molfile or smiles or fingerprint or substructure is not None    # the sinks: they read the last record on the device
+    writers, the fingerprint, the substructure search (substructure: a list of query SMILES, or None) and the nearest-row search
+    (nearest: (library, k, min_similarity) of model.predict_nearest, or None), to the per-image dicts that predict_pipeline
+    describes. tok: the 'chartok_coords' tokenizer."""
+    writer = molfile or smiles or fingerprint or substructure is not None or nearest is not None    # the sinks: they read the last record on the device
     drawn = engine.graph_pack(out, keep_device=writer or bool(on))       # what the predicted atoms and bonds are read from
     if (drawn["mols"]["flags"] & MOL_TRUNCATED).any():
         raise RuntimeError(f"a molecule has more atoms than the engine capacity max_atoms={engine.max_atoms}")
@@ -135,10 +138,18 @@ def packed_predictions(engine: Engine, out: dict, tok, on=(), compute_confidence
             p["graph_smiles_order"] = order[a0:a0 + na].tolist() if written else None
             if symmetry:
                 p["stereo_atoms"] = ranked[5][a0:a0 + na].tolist() if written else None
-    if fingerprint:
-        fp = engine.fingerprint_pack(rec)
-        for p, r, words in zip(preds, fp["fp"], fp["bits"]):
-            p["fingerprint"] = None if int(r["flags"]) & (FP_REFUSED | FP_LIMIT) else words.tobytes()
+    if fingerprint or nearest is not None:
+        fp = engine.fingerprint_pack(rec, keep_device=nearest is not None)
+        if fingerprint:
+            for p, r, words in zip(preds, fp["fp"], fp["bits"].cpu().numpy().view(np.uint32) if nearest is not None else fp["bits"]):
+                p["fingerprint"] = None if int(r["flags"]) & (FP_REFUSED | FP_LIMIT) else words.tobytes()
+        if nearest is not None:
+            library, k, min_similarity = nearest
+            if not isinstance(library, dict):                            # a list of SMILES: through the passes the predictions took
+                library = smiles_library(engine, library, **{name: True for name in on})
+            answered = [not int(r["flags"]) & (FP_REFUSED | FP_LIMIT) for r in fp["fp"]]
+            for p, found in zip(preds, _nearest_of(engine, fp["bits"], answered, library, k, min_similarity)):
+                p["nearest"] = found
     if substructure is not None:
         for p, found in zip(preds, _substructures_of(engine, rec, list(substructure), on, tok.maxx)):
             p["substructure"] = found
@@ -316,6 +327,51 @@ def tanimoto(engine: Engine, smiles_a, smiles_b, **passes) -> List[float]:
     sides = [[x["fingerprint"] or empty for x in smiles_fingerprints(engine, side, **passes)] for side in (smiles_a, smiles_b)]
     a, b = (np.frombuffer(b"".join(side), np.uint32).reshape(-1, FP_WORDS) for side in sides)
     return engine.tanimoto(a, b)["similarity"].tolist()
+
+
+def smiles_library(engine: Engine, smiles_list, max_bonds: int = 0, **passes) -> dict:
+    """A caller's own list of known compounds, read and fingerprinted once, for any number of nearest_smiles and predict_nearest
+    calls: mnx_smiles_read, the passes named (smiles_fingerprints' options), mnx_fingerprint_pack. {'bits': the fingerprints as a
+    device tensor int32 [n, FP_WORDS], 'flags': per string abi.FP_* of its fingerprint with bit 31 set where the reader refused
+    the string (either way every word is 0 then and the row scores 0.0 against everything), 'smiles': the strings}. Search it
+    with the passes it was made with: kekulize=True, normalize=True on both sides make aromatic and Kekule spellings agree."""
+    smiles_list = list(smiles_list)
+    if not smiles_list:
+        raise ValueError("smiles_library: an empty library has no nearest row")
+    on = named_passes("smiles_library", passes)
+    read = engine.smiles_read(smiles_list, keep_device=True)
+    fp = engine.fingerprint_pack(run_chain(engine, read, on, keep_last=True)[1], max_bonds=max_bonds, keep_device=True)
+    unread = (read["read"]["flags"] & READ_REFUSED) != 0
+    return {"bits": fp["bits"], "flags": (fp["fp"]["flags"] | np.where(unread, np.uint32(1 << 31), np.uint32(0))).astype(np.uint32),
+            "smiles": [s.decode("utf-8", "replace") if isinstance(s, bytes) else s for s in smiles_list]}
+
+
+def _nearest_of(engine: Engine, bits, answered, library: dict, k: int, min_similarity: float) -> List[list]:
+    """Per row of bits (fingerprints on the device) its hits in the library of smiles_library: [{'index', 'smiles',
+    'similarity'}] in mnx_tanimoto_search's order; [] for a row that is not `answered` — it has no fingerprint. One search."""
+    res = engine.tanimoto_search(bits, library["bits"], k=k, min_similarity=min_similarity)
+    names = library["smiles"]
+    return [[{"index": int(i), "smiles": names[int(i)], "similarity": float(s)} for i, s in zip(row[:n], sims[:n])] if ok else []
+            for ok, n, row, sims in zip(answered, res["count"].tolist(), res["index"], res["similarity"])]
+
+
+def nearest_smiles(engine: Engine, queries, library, k: int = 1, min_similarity: float = 0.0, **passes) -> List[list]:
+    """Which known compound is nearest: per query SMILES the k nearest strings of `library` — a list of SMILES, or
+    smiles_library's dict, made once — by the Tanimoto similarity of this library's path fingerprints (mnx_tanimoto_search: the
+    first k by similarity, among equals the lower library index, of those the ones at or above min_similarity). Per query a list
+    of {'index', 'smiles', 'similarity'}; [] for a query that was not read, was refused or passed the step limit. passes:
+    smiles_fingerprints' pass options, applied to the queries and to a library given as a list. NOT RDKit's fingerprint, k <=
+    NEAREST_MAX_K, and no count of all rows above a threshold."""
+    queries = list(queries)
+    if not queries:
+        return []
+    on = named_passes("nearest_smiles", passes)
+    if not isinstance(library, dict):
+        library = smiles_library(engine, library, **passes)
+    read = engine.smiles_read(queries, keep_device=True)
+    fp = engine.fingerprint_pack(run_chain(engine, read, on, keep_last=True)[1], keep_device=True)
+    answered = [not (int(r["flags"]) & READ_REFUSED or int(f["flags"]) & (FP_REFUSED | FP_LIMIT)) for r, f in zip(read["read"], fp["fp"])]
+    return _nearest_of(engine, fp["bits"], answered, library, k, min_similarity)
 
 
 def _chained(engine: Engine, smiles_list, passes: dict, who: str):

@@ -23,8 +23,8 @@ from .abi import (DEFAULT_DTYPE, FP_LIMIT, FP_REFUSED, FP_WORDS, MATCH_BAD_PAIR,
 from .chain import BY_NAME, PASSES, passes_on, run_chain  # noqa: F401
 from .engine import Engine
 from .graphs import (_same_graph_tables, canonical_molfiles, canonical_smiles, formula_candidate,  # noqa: F401
-                     molfile_fingerprints, packed_predictions, page_scale, same_graph, smiles_fingerprints, smiles_substructure,
-                     split_sdf, tanimoto, unpack_graphs)
+                     molfile_fingerprints, nearest_smiles, packed_predictions, page_scale, same_graph, smiles_fingerprints,
+                     smiles_library, smiles_substructure, split_sdf, tanimoto, unpack_graphs)
 from .preprocess import load_image_rgb, transform_image, transform_image_gray
 from .tokenizer import coords_labels, get_tokenizer
 
@@ -221,12 +221,28 @@ def predict_substructures(engine: Engine, images: torch.Tensor, queries, tokeniz
     return _pipeline(engine, images, tokenizer, substructure=list(queries), **options)
 
 
+def predict_nearest(engine: Engine, images: torch.Tensor, library, k: int = 1, min_similarity: float = 0.0, tokenizer=None,
+                    **options) -> List[dict]:
+    """predict_pipeline(engine, images, tokenizer, packed=True, **options) with one more sink behind the last pass, beside the
+    writers, the fingerprint and the substructure search: every dict gains 'nearest', the k compounds of `library` nearest to the
+    prediction by the Tanimoto similarity of this library's path fingerprints — [{'index', 'smiles', 'similarity'}], the first k
+    by similarity, among equals the lower index, of those the ones at or above min_similarity; [] for a molecule that is refused
+    or passes the step limit (mnx_fingerprint_pack, mnx_tanimoto_search; the rule: include/molnextr_hip.h — NOT RDKit's
+    fingerprint, k <= NEAREST_MAX_K). library: a list of SMILES, read on the device and sent through the same passes as the
+    predictions, or graphs.smiles_library's dict, made once with those passes. options: predict_pipeline's keywords, fingerprint=True
+    for predict_fingerprints' key and substructure=[...] for predict_substructures'. A function of its own because
+    predict_pipeline's parameter list is closed."""
+    if not options.setdefault("packed", True):
+        raise ValueError("predict_nearest needs packed=True: the fingerprints are made from the packed tables")
+    return _pipeline(engine, images, tokenizer, nearest=(library, int(k), float(min_similarity)), **options)
+
+
 def _pipeline(engine, images, tokenizer=None, ref_batch_size=16, max_len=None, beam_size=1, compute_confidence=False, labels=None,
               free_run=False, packed=False, molfile=False, molfile_scale=None, smiles=False, stereo=False, double_bonds=False,
               canonical=False, expand=False, symmetry=False, normalize=False, kekulize=False, formula=False, keep_main=False,
-              fingerprint=False, substructure=None) -> List[dict]:
-    """The body of predict_pipeline (its arguments, its defaults), of predict_fingerprints (fingerprint=True) and of
-    predict_substructures (substructure: the query SMILES)."""
+              fingerprint=False, substructure=None, nearest=None) -> List[dict]:
+    """The body of predict_pipeline (its arguments, its defaults), of predict_fingerprints (fingerprint=True), of
+    predict_substructures (substructure: the query SMILES) and of predict_nearest (nearest: (library, k, min_similarity))."""
     tok =(tokenizer or get_tokenizer())["chartok_coords"]
     why = {**{p.name: p.packed_why for p in PASSES}, "molfile": "the molfiles are written from the packed tables",
            "smiles": "the graph SMILES are written from the packed tables"}
@@ -258,7 +274,7 @@ def _pipeline(engine, images, tokenizer=None, ref_batch_size=16, max_len=None, b
     if packed:
         on = passes_on(formula, expand, keep_main, kekulize, normalize)
         return packed_predictions(engine, out, tok, on, compute_confidence, molfile, molfile_scale, smiles, stereo, double_bonds,
-                                  canonical, symmetry, fingerprint, substructure)
+                                  canonical, symmetry, fingerprint, substructure, nearest)
     scores = out["scores"].cpu().numpy() if beam_size > 1 else None
     lens = out["lengths"].cpu().numpy()
     toks = out["tokens"].cpu().numpy()
@@ -364,7 +380,12 @@ class molnextr:
     list of query SMILES; every output dict gains 'substructure', per query {'matched', 'atoms', 'coords'}: whether the molecule
     behind the graph_* passes holds the query, under which of its atoms and where on the page (mnx_substructure_match through
     predict_substructures: this library's own rule, NOT RDKit's HasSubstructMatch and not SMARTS). molnextr.has_substructure asks
-    the same of SMILES strings."""
+    the same of SMILES strings.
+    graph_nearest: an attribute like graph_fingerprint (`m.graph_nearest = ["CCO", "c1ccccc1"]`, or model.smiles_library's dict made
+    once with the graph_* passes that are on; default None) = a library of known compounds; every output dict gains 'nearest',
+    the graph_nearest_k (an attribute, default 1, at most 64) compounds nearest to the molecule behind the graph_* passes as
+    [{'index', 'smiles', 'similarity'}], [] for a molecule without a fingerprint (mnx_tanimoto_search through predict_nearest: this
+    library's own fingerprint, NOT RDKit's). molnextr.nearest asks the same of SMILES strings."""
 
     image_format = "fp32"
     packed_results = False
@@ -381,6 +402,8 @@ class molnextr:
     graph_keep_main = False
     graph_fingerprint = False
     graph_substructure = None
+    graph_nearest = None
+    graph_nearest_k = 1
 
     def __init__(self, model_path, device=None, max_batch: int = 32, dtype: str = DEFAULT_DTYPE,
                  device_preprocess: bool = True, image_format: str = "fp32", packed_results: bool = False,
@@ -451,6 +474,11 @@ class molnextr:
         """The similarity of two lists of SMILES, item by item, by this library's path fingerprint (model.tanimoto; passes:
         smiles_fingerprints' options). NOT RDKit's fingerprint."""
         return tanimoto(self.engine, smiles_a, smiles_b, **passes)
+
+    def nearest(self, smiles_list, library, k: int = 1, **passes) -> List[list]:
+        """Per string of smiles_list its k nearest strings of `library` (a list of SMILES, or model.smiles_library's dict) as
+        [{'index', 'smiles', 'similarity'}] (model.nearest_smiles; passes: its options). NOT RDKit's fingerprint."""
+        return nearest_smiles(self.engine, smiles_list, library, k=k, **passes)
 
     def has_substructure(self, smiles_list, query, **passes) -> List:
         """Per string of smiles_list whether it holds the query SMILES: True, False, or None where a string was not read or the
@@ -625,7 +653,8 @@ class molnextr:
         group = (self.group_images // batch_size) * batch_size
         groups = [input_images[i:i + group] for i in range(0, len(input_images), group)]
         conf = {"compute_confidence": True} if return_confidence else {}
-        if self.packed_results or self.graph_molfile or self.graph_smiles or self.graph_fingerprint or self.graph_substructure is not None:
+        if (self.packed_results or self.graph_molfile or self.graph_smiles or self.graph_fingerprint or self.graph_substructure is not None
+                or self.graph_nearest is not None):
             conf["packed"] = True
         if self.graph_smiles:
             conf["smiles"] = True
@@ -637,6 +666,10 @@ class molnextr:
             if self.graph_symmetry:
                 conf["symmetry"] = True
         conf.update({row.name: True for row in PASSES if getattr(self, "graph_" + row.name)})      # a flag travels only when it is on
+        if self.graph_nearest is not None:                    # a list is read and fingerprinted once per call, not once per group
+            library = self.graph_nearest if isinstance(self.graph_nearest, dict) else smiles_library(
+                self.engine, self.graph_nearest, **{row.name: True for row in PASSES if row.name in conf})
+            conf["nearest"] = (library, int(self.graph_nearest_k), 0.0)
         gen = self._prefetched(groups)
         try:
             for x in gen:
@@ -649,6 +682,9 @@ class molnextr:
                 if self.graph_substructure is not None:       # predict_fingerprints' key travels as an option of this route
                     job = lambda eng: predict_substructures(eng, x, list(self.graph_substructure), self.tokenizer, ref_batch_size=batch_size,  # noqa: E731
                                                             **({"fingerprint": True} if self.graph_fingerprint else {}), **conf)
+                elif "nearest" in conf and not self.graph_fingerprint:    # on either route above predict_nearest's key travels in conf
+                    rest = {key: v for key, v in conf.items() if key != "nearest"}
+                    job = lambda eng: predict_nearest(eng, x, *conf["nearest"], self.tokenizer, ref_batch_size=batch_size, **rest)  # noqa: E731
                 else:
                     job = lambda eng: (predict_fingerprints if self.graph_fingerprint else predict_pipeline)(  # noqa: E731
                         eng, x, self.tokenizer, ref_batch_size=batch_size, **conf)
@@ -700,6 +736,8 @@ class molnextr:
                 d["fingerprint"] = pred["fingerprint"]
             if "substructure" in pred:                        # graph_substructure: per query matched / atoms / coords
                 d["substructure"] = pred["substructure"]
+            if "nearest" in pred:                             # graph_nearest: the nearest known compounds, index / smiles / similarity
+                d["nearest"] = pred["nearest"]
             if return_atoms_bonds:
                 c = pred["chartok_coords"]
                 atoms = []

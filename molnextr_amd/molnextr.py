@@ -73,6 +73,14 @@ def tanimoto(smiles_a, smiles_b, **passes):
     return MolNexTRSingleton.get_instance().tanimoto(smiles_a, smiles_b, **passes)
 
 
+def nearest(smiles_list, library_smiles, k: int = 1, **passes):
+    """Per string of smiles_list the k strings of library_smiles nearest to it, as a list of {'index', 'smiles', 'similarity'} (no
+    reference counterpart; model.nearest_smiles): by the Tanimoto similarity of this library's own path fingerprints, NOT RDKit's;
+    k <= 64. passes: canonical_smiles' pass options; kekulize=True and normalize=True make aromatic and Kekule spellings agree. A
+    string that was not read or has no fingerprint gets []."""
+    return MolNexTRSingleton.get_instance().nearest(smiles_list, library_smiles, k=k, **passes)
+
+
 def has_substructure(smiles_list, query, **passes):
     """Per string of smiles_list whether it holds the query SMILES as a substructure: True, False, or None where a string was not
     read or the search gave no answer (no reference counterpart; model.smiles_substructure). passes: canonical_smiles' pass options;
